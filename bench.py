@@ -11,8 +11,12 @@ are already resident in HBM, followed (N > 1) by the single RCCL all-gather of t
 Workload = BASELINE.json configs[2]: batch 256 per GPU (weak scaling: N GPUs process N*256 frames per step).
 Steps are issued round-robin to `--inflight` sessions (default 3), each with its own HIP stream and workspace, the way a
 serving loop would keep the GPU busy: the march kernels of the path run one wave per frame and leave most of a CU idle,
-which the other session's kernels fill.  `--inflight 1` gives strictly serial steps; `stage_ms` / `roofline` are always
-measured on one session alone.  Rank 0 prints ONE JSON line.
+which the other session's kernels fill.  `--inflight 1` gives strictly serial steps.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given, and prints
+the headline figure.  `--full` adds everything else, measured after the timed region: the CPU baselines (before the GPU is initialised),
+the per-stage HIP-event times (`stage_ms`, on one session alone), the roofline of the dominant stage, the DFT-GEMM record, and the two
+extra figures (constants as shipped, BASELINE configs[1]).
 """
 from __future__ import annotations
 
@@ -194,6 +198,42 @@ def _traffic_table():
     return (tj if src["matches_this_build"] else {}), src
 
 
+DUMP_BYTES = 60 * 10**6     # --dump-outputs: at most this many bytes of arrays (64 MB with headers and margin)
+DUMP_SEED = 0
+
+
+def _save_finite(d, name, t, dtype):
+    """t -> d/<name>.npy in `dtype`, every value finite.  A floating output also gets d/<name>_finite.npy (1 where the value is finite,
+    0 where it is not) and its non-finite entries are written as 0: the depth map is NaN outside the eroded ROI and on unreliable pixels,
+    and that layout is part of what the path computes."""
+    a = t.to(dtype).cpu().numpy()
+    if t.is_floating_point():
+        fin = np.isfinite(a)
+        np.save(os.path.join(d, name + "_finite.npy"), fin.astype(a.dtype))
+        a = np.where(fin, a, a.dtype.type(0))
+    np.save(os.path.join(d, name + ".npy"), a)
+
+
+def dump_outputs(d, out):
+    """what a caller of the timed path receives from its last step -> d/<name>.npy: the maps (height_map_mm, output_reliable) as float32,
+    the scalar records and status as float64, each floating output with its finite mask (_save_finite).  When the maps of the whole batch
+    exceed DUMP_BYTES, the maps are those of a fixed sample of frames: np.sort(np.random.default_rng(DUMP_SEED).choice(batch, m,
+    replace=False)), m as large as fits; scalars and status are always whole."""
+    os.makedirs(d, exist_ok=True)
+    b = int(out["status"].shape[0])
+    maps = [k for k in ("height_map_mm", "output_reliable") if k in out]
+    small = [k for k in ("scalars", "status") if k in out]
+    files = lambda k: 2 if out[k].is_floating_point() else 1            # the value file (+ its finite mask)
+    room = DUMP_BYTES - sum(out[k].numel() * 8 * files(k) for k in small)
+    per_frame = sum(out[k][0].numel() * 4 * files(k) for k in maps)
+    m = min(b, max(1, room // max(1, per_frame)))
+    idx = None if m == b else torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(b, m, replace=False)))
+    for k in maps:
+        _save_finite(d, k, out[k] if idx is None else out[k][idx.to(out[k].device)], torch.float32)
+    for k in small:
+        _save_finite(d, k, out[k], torch.float64)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -205,8 +245,12 @@ def main():
     ap.add_argument("--inflight", type=int, default=3,
                     help="sessions (each with its own HIP stream and workspace) that take the steps in turn, so consecutive steps overlap on the GPU; "
                          "1 = strictly serial steps")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the two extra figures measured after the timed region (constants as shipped, configs[1]): profiling runs")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline figure: CPU baselines, per-stage times, roofline and DFT-GEMM records, the two extra figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, every value finite, at most 64 MB; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the two extra figures measured after the timed region (constants as shipped, configs[1]): profiling runs")
     ap.add_argument("--kernel-tier", action="append", default=[], metavar="NAME=VALUE",
                     help="diagnostic A/B runs: kernel tier hooks of csrc/test_hooks.h (e.g. telea_two_tier=0); the default run sets none")
     ap.add_argument("--cpu-budget-s", type=float, default=16.0)
@@ -214,6 +258,8 @@ def main():
                     help="BASELINE configs[4] as SURVEY.md 8(d) restates it: uncached (reference, deformed) pairs, carrier search + reference "
                          "demodulation per sample (no fusion of any kind exists upstream); default batch 128 = 1024 / 8 per GPU")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.pairs and args.batch == 256:
         args.batch = 128
 
@@ -221,7 +267,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cpu_one = cpu_all = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_one, cpu_all = cpu_baselines(args.size, args.constants, args.cpu_budget_s, args.pairs)      # before any HIP call: forks workers
     if world > 1:
         import torch.distributed as dist
@@ -281,22 +327,27 @@ def main():
     stepper = Stepper(run, sensors, outs, streams, gathers, torch.cuda.stream)
     elapsed = timed_steps(stepper, args.warmup, args.steps, dist if world > 1 else None, lambda: torch.cuda.synchronize(dev), dev)
     status_bad = int((out["status"] != 0).sum().item())
+    if args.dump_outputs and rank == 0:
+        last = (stepper.n - 1) % len(sensors)       # the session that took the last timed step; N > 1: the gathered records of all ranks
+        dump_outputs(args.dump_outputs, gathers[last].views() if gathers is not None else outs[last])
 
+    # --full from here on: everything below is measured after the timed region and reuses its sessions and outputs
     # per-kernel device times (HIP events recorded by the library on the launch stream), separate passes
-    sensor.enable_stage_timing(True)
     acc = {}
     reps = 5
-    for _ in range(reps):
-        run(sensor, out)
-        for k, v in sensor.stage_times_ms().items():
-            acc[k] = acc.get(k, 0.0) + v / reps
-    sensor.enable_stage_timing(False)
+    if args.full:
+        sensor.enable_stage_timing(True)
+        for _ in range(reps):
+            run(sensor, out)
+            for k, v in sensor.stage_times_ms().items():
+                acc[k] = acc.get(k, 0.0) + v / reps
+        sensor.enable_stage_timing(False)
 
     # SURVEY.md 8(d) asks for two more figures next to the headline; both are measured AFTER (outside) the timed region, on rank 0 at N = 1:
     #  * the same batch with the reference's constants AS SHIPPED (pixel constants not rescaled from 1182 to this frame size);
     #  * BASELINE configs[1] as the survey restates it: batch 64, the demodulation stage alone (the path's only dense contraction).
     extra = {}
-    if rank == 0 and world == 1 and not args.pairs and not args.kernel_tier and not args.no_extras and n == 224:
+    if args.full and rank == 0 and world == 1 and not args.pairs and not args.kernel_tier and not args.no_extras and n == 224:
         other_const = "shipped" if args.constants == "scaled" else "scaled"
         cfg2 = pkg.FtpConfig.as_shipped() if other_const == "shipped" else pkg.FtpConfig.scaled(n)
         sensors2 = [pkg.FtpSensor(ref3, pkg.synth.roi_circle(n), cfg2, cal, neg, fm, max_batch=B, device=dev) for _ in sensors]
@@ -324,27 +375,6 @@ def main():
         del s64, o64
 
     if rank == 0:
-        P = n * n
-        dom = max(acc, key=acc.get)
-        # algorithmic bytes of the dominant kernel per launch (DESIGN.md "Kernels"):
-        #   k_unwrap_fast:        reads wrapped f32 + mask u8 (+ quality f32 for the seed), writes unwrapped f32 -> 9 B/px (13 with the seed search)
-        #   k_telea_window_mw:    reads image f32 + bad-mask u8, writes image f32 -> 9 B/px
-        #   k_robust_polyfit (x3): reads z f32 + mask u8, writes residual f32 -> 9 B/px per call
-        per_px = {"unwrap check (k_unwrap_fast)": 9.0, "inpaint (k_telea_window_mw)": 9.0, "detrend (3x IRLS)": 27.0}.get(dom, 8.0)
-        alg_bytes = per_px * P * B
-        achieved = alg_bytes / (acc[dom] * 1e-3) / 1e9
-        # HBM traffic per launch from the PMC counters: collected by separate rocprofv3 --pmc runs (tools/prof_pmc.sh ->
-        # tools/collect_profiles.py -> profiles/traffic_rNN.json), never in this run; reported only when that file was measured on
-        # exactly these kernel sources, null otherwise (`traffic_source` says which file and why)
-        tj, traffic_source = ({}, None) if args.pairs else _traffic_table()
-        traffic = tj.get(dom) if isinstance(tj.get(dom), (int, float)) else None
-        # the other two heavy stages, for context: that traffic over this run's stage time
-        other = []
-        for k in ("unwrap check (k_unwrap_fast)", "detrend (3x IRLS)", "inpaint (k_telea_window_mw)"):
-            if k != dom and k in acc and isinstance(tj.get(k), (int, float)) and acc[k] > 0:
-                rate = tj[k] / (acc[k] * 1e-3) / 1e9
-                other.append({"kernel": k, "kernel_ms": round(acc[k], 4), "traffic": tj[k], "hbm_GBps": round(rate, 1),
-                              "frac_of_hbm_peak": round(rate / HBM_PEAK_GBS, 4)})
         line = {
             "metric": "frames/sec (224x224 -> force-map) at batch 256" if not args.pairs else
                       "pairs/sec (uncached (reference, deformed) 224x224 pairs -> force-map), BASELINE configs[4] restated",
@@ -371,25 +401,49 @@ def main():
                 "global_batch": world * B, "frame": [n, n, 3], "input_dtype": "fp16", "constants": args.constants,
                 "parallelism": f"dp{world}", "inflight_batches": len(sensors), "frames_with_nonzero_status": status_bad,
             },
-            "roofline": {
-                "bound": "hbm",
-                # (the stage names are the library's, fixed per stage: frames beyond the window march's capacity go cluster by cluster)
-                "kernel": dom if n * n <= 8 * 14464 else dom.replace("k_telea_window_mw", "k_telea_clusters2 + k_telea_big_clusters"),
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                "kernel_ms": acc[dom], "algorithmic_bytes_per_launch": alg_bytes,
-                "note": {"detrend (3x IRLS)": "three IRLS fits per frame, samples register-resident (one 1024-thread workgroup per frame): ~33 sweeps over "
-                                              "the samples per fit (6 normal-equation sweeps, 10 exact medians), bound by VALU issue, not by bytes",
-                         }.get(dom, "dominant stage is latency- / issue-bound (dependent steps inside one workgroup per frame), not bandwidth-bound"),
-                "other_heavy_stages": other,
-            },
-            # the one dense contraction of the path: the pruned-DFT stages 1 and 4 as float64 GEMMs on the matrix cores (v_mfma_f64_16x16x4_f64).
-            # FLOPs of the two MFMA kernels over the WHOLE demodulation stage's event time (a lower bound on the kernels' own utilisation: the
-            # stage also holds the two small non-MFMA stages and the amplitude / atan2 epilogue; per-kernel times: profiles/*_kernel_table.txt)
-            "dft_gemm": _dft_gemm_record(acc.get("pruned-dft demod", 0.0), B, n, sensor, 1),
-            "stage_ms": {k: round(v, 4) for k, v in acc.items()},
-            "serial_ms_per_step": round(sum(acc.values()), 4),
         }
+        if args.full:
+            P = n * n
+            dom = max(acc, key=acc.get)
+            # algorithmic bytes of the dominant kernel per launch (DESIGN.md "Kernels"):
+            #   k_unwrap_fast:        reads wrapped f32 + mask u8 (+ quality f32 for the seed), writes unwrapped f32 -> 9 B/px (13 with the seed search)
+            #   k_telea_window_mw:    reads image f32 + bad-mask u8, writes image f32 -> 9 B/px
+            #   k_robust_polyfit (x3): reads z f32 + mask u8, writes residual f32 -> 9 B/px per call
+            per_px = {"unwrap check (k_unwrap_fast)": 9.0, "inpaint (k_telea_window_mw)": 9.0, "detrend (3x IRLS)": 27.0}.get(dom, 8.0)
+            alg_bytes = per_px * P * B
+            achieved = alg_bytes / (acc[dom] * 1e-3) / 1e9
+            # HBM traffic per launch from the PMC counters: collected by separate rocprofv3 --pmc runs (tools/prof_pmc.sh ->
+            # tools/collect_profiles.py -> profiles/traffic_rNN.json), never in this run; reported only when that file was measured on
+            # exactly these kernel sources, null otherwise (`traffic_source` says which file and why)
+            tj, traffic_source = ({}, None) if args.pairs else _traffic_table()
+            traffic = tj.get(dom) if isinstance(tj.get(dom), (int, float)) else None
+            # the other two heavy stages, for context: that traffic over this run's stage time
+            other = []
+            for k in ("unwrap check (k_unwrap_fast)", "detrend (3x IRLS)", "inpaint (k_telea_window_mw)"):
+                if k != dom and k in acc and isinstance(tj.get(k), (int, float)) and acc[k] > 0:
+                    rate = tj[k] / (acc[k] * 1e-3) / 1e9
+                    other.append({"kernel": k, "kernel_ms": round(acc[k], 4), "traffic": tj[k], "hbm_GBps": round(rate, 1),
+                                  "frac_of_hbm_peak": round(rate / HBM_PEAK_GBS, 4)})
+            line.update({
+                "roofline": {
+                    "bound": "hbm",
+                    # (the stage names are the library's, fixed per stage: frames beyond the window march's capacity go cluster by cluster)
+                    "kernel": dom if n * n <= 8 * 14464 else dom.replace("k_telea_window_mw", "k_telea_clusters2 + k_telea_big_clusters"),
+                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                    "kernel_ms": acc[dom], "algorithmic_bytes_per_launch": alg_bytes,
+                    "note": {"detrend (3x IRLS)": "three IRLS fits per frame, samples register-resident (one 1024-thread workgroup per frame): ~33 sweeps over "
+                                                  "the samples per fit (6 normal-equation sweeps, 10 exact medians), bound by VALU issue, not by bytes",
+                             }.get(dom, "dominant stage is latency- / issue-bound (dependent steps inside one workgroup per frame), not bandwidth-bound"),
+                    "other_heavy_stages": other,
+                },
+                # the one dense contraction of the path: the pruned-DFT stages 1 and 4 as float64 GEMMs on the matrix cores (v_mfma_f64_16x16x4_f64).
+                # FLOPs of the two MFMA kernels over the WHOLE demodulation stage's event time (a lower bound on the kernels' own utilisation: the
+                # stage also holds the two small non-MFMA stages and the amplitude / atan2 epilogue; per-kernel times: profiles/*_kernel_table.txt)
+                "dft_gemm": _dft_gemm_record(acc.get("pruned-dft demod", 0.0), B, n, sensor, 1),
+                "stage_ms": {k: round(v, 4) for k, v in acc.items()},
+                "serial_ms_per_step": round(sum(acc.values()), 4),
+            })
         line.update(extra)
         if cpu_one is not None:
             line["cpu_baseline"] = cpu_one

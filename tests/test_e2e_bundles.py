@@ -83,13 +83,13 @@ def test_report_covers_all_five_stored_pairs():
         assert abs(r["peak_mm_oracle"] - r["peak_mm_reference"]) <= 1e-2 * r["peak_mm_reference"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Final_demos_images"), reason="reference tree not present")
 def test_alignment_restatement_regenerates_fixture():
-    """decode + phase correlation + ECC from the JPEGs reproduce the committed aligned crop (deterministic restatement)."""
+    """decode + phase correlation + ECC from the JPEGs reproduce the committed aligned crop (deterministic restatement).  The JPEGs are the
+    reference's demo photographs, committed as tests/golden/FINAL_reference.jpg / FINAL_E_deformed.jpg."""
     from oracle import align_oracle as A
     fx = _fixture()
-    R = "/root/reference/Final_demos_images"
-    rg, dg, circle, info = A.aligned_crops(f"{R}/FINAL_reference.jpg", f"{R}/FINAL_E_deformed.jpg", ((1873, 1703), (1599, 707), (2575, 950)))
+    rg, dg, circle, info = A.aligned_crops(os.path.join(G, "FINAL_reference.jpg"), os.path.join(G, "FINAL_E_deformed.jpg"),
+                                           ((1873, 1703), (1599, 707), (2575, 950)))
     assert circle == fx["circle"]
     assert np.array_equal(rg, fx["ref"])
     assert np.array_equal(dg, fx["def"])

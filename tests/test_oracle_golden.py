@@ -121,18 +121,27 @@ def test_stored_demo_tails_reproduced():
         assert O.estimate_mm_per_px(s["estimated_grating_period_px"]) == s["mm_per_px"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Multimodal_Sensor"), reason="reference tree not mounted")
 def test_oracle_tail_on_full_stored_bundles():
+    """The force tail on the full height maps the reference stored for its five demos.  The maps and masks are the committed fixtures
+    tests/golden/e2e_<name>.npz (height_crop and bit-packed masks of each stored height_map_bundle.npz); the stored bundles' mask counts in
+    ref_tail_demos.json tie each fixture to its bundle, and the stored eroded ROI is exactly the finite part of the stored map."""
     meta = json.load(open(os.path.join(G, "ref_tail_demos.json")))
     best = meta["force_model"]
+    n = 1182
     for name, d in meta["demos"].items():
-        b = np.load(f"/root/reference/Multimodal_Sensor/Demos_report/{name}/force_sensing/ftp_run/height_map_bundle.npz")
-        h = b["height_crop"]
+        b = np.load(os.path.join(G, f"e2e_{name}.npz"))
+        unpack = lambda k: np.unpackbits(b[k])[: n * n].reshape(n, n).astype(bool)
+        h = b["height_crop_reference"]
+        roi_eroded = np.isfinite(h)
+        assert int(roi_eroded.sum()) == d["roi_px"], name
+        assert int(unpack("reliable_bits").sum()) == d["reliable_px"], name
+        assert int(unpack("contact_kept_bits").sum()) == d["contact_kept_px"], name
+        assert int(unpack("contact_dilated_bits").sum()) == d["contact_dilated_px"], name
         v, a, md = O.depth_map_to_volume_cm3(h, np.isfinite(h), d["stored"]["mm_per_px"], 0.01)
         r = d["reference_tail_on_bundle"]
         assert (v, a, md) == (r["volume_cm3"], r["contact_area_mm2"], r["max_depth_mm"])
         assert O.predict_force_from_volume(best, v) == r["force_N"]
-        assert O.argmax_depth_mm(h, b["crop_roi_eroded"]) == d["argmax_depth_index"]
+        assert O.argmax_depth_mm(h, roi_eroded) == d["argmax_depth_index"]
 
 
 def test_fft_precision_modes_agree():

@@ -4,6 +4,7 @@
 usage: python tools/collect_profiles.py <tag> [<round>]     (e.g. r01 r01)
 Reads   gpurun_out/bench_default.json, gpurun_out/bench_serial.json, gpurun_out/prof_<tag>/**/kernel_stats.csv,
         gpurun_out/pmc_<tag>_{FETCH_SIZE,WRITE_SIZE}/**/counter_collection.csv (newest file of each kind only)
+        (bench_default.json and bench_serial.json are lines of `bench.py --full`: the summary reads bench_default.json's roofline)
 Writes  profiles/bench_<round>.json, bench_<round>_serial.json, <round>_kernel_stats.csv, <round>_kernel_table.txt,
         <round>_pmc_summary.json, traffic_<round>.json
 HBM bytes per launch = (2 * FETCH_SIZE + WRITE_SIZE) * 1024: separate --pmc passes, FETCH_SIZE doubled per the gfx950 correction of
