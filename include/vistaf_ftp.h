@@ -42,13 +42,14 @@ extern "C" {
 /* per-frame status written by predict_batch (d_status[b]) */
 #define VISTAF_FRAME_OK 0
 #define VISTAF_FRAME_EMPTY_RELIABLE 1   /* upstream: main() logs and returns None (shape_ftp.py:1677-1679) */
-#define VISTAF_FRAME_QUEUE_OVERFLOW 2   /* internal work queue exhausted (never for valid sizes) */
-#define VISTAF_FRAME_NO_CARRIER 3       /* pair mode: no usable carrier peak in this sample's reference frame.  DELIBERATE RESTRICTION: a
-                                         * carrier whose (2*patch_half_width_bins+1)^2 patch is clipped by the spectrum border (carrier
-                                         * within 10 bins of Nyquist, i.e. a fringe period of ~2 px) is refused in pair mode, whereas
-                                         * upstream clips the patch and goes on (shape_ftp.py:930-948); session mode (set_reference)
-                                         * accepts clipped patches as upstream does.  Parity for that edge is unpinned (no stored
-                                         * output of the reference covers it). */
+#define VISTAF_FRAME_QUEUE_OVERFLOW 2   /* internal work queue exhausted (never for valid sizes).  Only the phase-unwrap queues can still
+                                         * raise it: a frame whose big-cluster inpaint march (native-size crops) outgrows its queue is
+                                         * re-marched whole by the whole-frame kernel, whose queue holds every cell of the frame. */
+#define VISTAF_FRAME_NO_CARRIER 3       /* pair mode: no usable carrier in this sample's reference frame -- no spectrum peak, or a
+                                         * non-positive fringe period.  A carrier whose (2*patch_half_width_bins+1)^2 patch is clipped
+                                         * by the spectrum border is processed with the clipped patch, as upstream (shape_ftp.py:930-948)
+                                         * and session mode do, with the bits of a session built on that reference.  Parity for that edge
+                                         * is unpinned (no stored output of the reference covers it). */
 
 /* input frame formats */
 #define VISTAF_FMT_GRAY_U8 0    /* [B,h,w] uint8 (cv2.cvtColor(...,BGR2GRAY) already applied) */

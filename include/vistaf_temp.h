@@ -57,12 +57,16 @@ typedef struct vistaf_tempseg_config {   /* Code/temperature_sensor.py:67-82, de
 #define VISTAF_TS_CARRIER_PERIOD_PX 12
 
 int vistaf_tempseg_default_config(vistaf_tempseg_config *cfg);
+/* Any frame size H, W >= 1.  The session allocates the segmentation's workspace (hipFFT plan, band-pass tables and planes) on its first
+ * vistaf_tempseg_segment call; a session used for the feature planes, the colour support or the map stages only never allocates it. */
 int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf_tempseg_handle **out);
 void vistaf_tempseg_destroy(vistaf_tempseg_handle *h);
 
 /* d_bgr [H,W,3] uint8 (cv2.imread order), d_roi [H,W] uint8 0/1 (roi_full).  Outputs [H,W] uint8 0/1, any may be NULL:
  * d_dark / d_light (dark_final, light_final), d_roi_eff, d_sat; info_host[VISTAF_TEMPSEG_NINFO] on the HOST.
- * Errors as upstream: VISTAF_E_STATE when the ROI is empty after the saturation exclusion (:445-446).  Synchronises `stream`. */
+ * Errors as upstream: VISTAF_E_STATE when the ROI is empty after the saturation exclusion (:445-446).  Synchronises `stream`.
+ * SIZE LIMIT of this function only: H must be a multiple of 16 (the band-pass DFT runs in 16-row matrix-core strips) and both sides >= 64;
+ * other sizes return VISTAF_E_INVALID ("segment: frame height must be a multiple of 16 ...").  The functions below have no such limit. */
 /* DELIBERATE RESTRICTION: returns VISTAF_E_NOCARRIER ("carrier band leaves the spectrum") when the band-pass disc of radius
  * bandpass_radius_bins around the carrier peak is clipped by the spectrum border; upstream multiplies by the clipped disc and goes on
  * (temperature_sensor.py:463-468).  Such a carrier is within 22 bins of Nyquist (stripe period ~2 px); parity for that edge is unpinned. */
@@ -80,7 +84,8 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
  *                                (dilate_bool_mask :583-590, MORPH_ELLIPSE; defaults COLOR_CHROMA_MIN 10.0 :86, COLOR_SUPPORT_DILATE 3 :87;
  *                                the threshold is compared in float32 like NumPy does for a Python scalar).  d_chroma / d_support may be NULL;
  *                                the masks are only needed for d_support.
- * Both are asynchronous on `stream`; the handle's frame size applies. */
+ * Both are asynchronous on `stream`; the handle's frame size applies, any H, W >= 1 (tiled per-pixel kernels with clamped borders and the
+ * bit-plane / row-span morphology: neither needs the segmentation's size limit). */
 int vistaf_temp_feature_planes(vistaf_tempseg_handle *h, const uint8_t *d_bgr, int blur_ksize, float *d_L, float *d_a, float *d_b, float *d_gray,
                                void *stream);
 int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const float *d_b, const uint8_t *d_light, const uint8_t *d_roi_eff,
@@ -98,7 +103,8 @@ int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const 
  *                               counts_host[4] = roi, wide_ok, color_ok, blend pixels (may be NULL; non-NULL synchronises `stream`)
  *   vistaf_temp_oriented_blur   :705-747 `oriented_gaussian_blur_float(map, roi, angle_rad, sigma_across, sigma_along)`: warpAffine (INTER_LINEAR,
  *                               BORDER_REFLECT; the ROI with INTER_NEAREST) by getRotationMatrix2D, anisotropic GaussianBlur, rotate back.
- *                               Uploads the two tap vectors (synchronises `stream`). */
+ *                               Uploads the two tap vectors (synchronises `stream`).
+ * All four are per-pixel kernels (and the whole-frame Telea march) with no frame-size limit: any H, W >= 1. */
 typedef struct vistaf_temp_fuse_config {     /* Code/temperature_sensor.py:55-64, defaults as shipped */
     double color_t_min, color_t_max;         /* 20, 33 */
     double color_guard_band, switch_margin_c;/* 0.5, 1.0 */

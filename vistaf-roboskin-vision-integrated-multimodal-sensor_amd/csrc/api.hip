@@ -68,7 +68,7 @@ struct vistaf_ftp_handle {
     // uncached-pair mode (vistaf_ftp_predict_pairs): per-frame carriers, tables and reference fields, allocated on first use
     CarrierGeom *pgeom = nullptr;
     double2 *pEx = nullptr, *pEy = nullptr, *pGx = nullptr, *pGy = nullptr, *pcref = nullptr;
-    float *pamp_ref = nullptr, *win_full = nullptr;
+    float *pamp_ref = nullptr, *pwin = nullptr, *hann_tab = nullptr;     // pwin: [maxB][pmax^2] per-sample windows; hann_tab: hann(M)[i] at [M * pmax + i]
     bool pairs_ready = false;
     Tiers tiers;                                       // kernel tier selection (test hook; defaults = production kernels)
     bool keep_planes = false;                          // test hook: also write planes that only the parity tests read (float64 field)
@@ -94,6 +94,7 @@ struct vistaf_ftp_handle {
     int *cnt_a, *cnt_valid, *rel_count, *contact_count, *bg_count, *bad_count, *flipped;
     unsigned int *gmax;
     int32_t *status;
+    int32_t *big_only;                  // [maxB] frames handed from the big-cluster march to the whole-frame kernel (launch_inpaint_big_handback)
     unsigned long long *cc_best;        // [maxB] largest-component key of launch_cc_largest on large frames
     double *scalars;
     float *req_hi, *req_g, *req_med, *req_amp, *req_contact, *req_core;   // device percentile requests
@@ -234,7 +235,14 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
                 ClusterPlanes left;
                 launch_inpaint_clusters(hd->img, hd->bad1, range, hd->inpaint_cl_scratch, &bad_big, &left, B, h, w, st);
                 if (timed) hipEventRecord(hd->ev[ST_INPAINT], st);      // (after the LDS cluster pass: its bookkeeping counts as mask work)
-                launch_inpaint_big_clusters(hd->img, bad_big, range, hd->inpaint_scratch, hd->status, left, B, h, w, st, hd->tiers.big_queue_lds != 0);
+                launch_inpaint_big_clusters(hd->img, bad_big, range, hd->inpaint_scratch, hd->status, left, B, h, w, st, hd->tiers.big_queue_lds != 0,
+                                            hd->tiers.big_gq_cap);
+                // a frame whose big-cluster queue overflowed (status 2) goes whole to the whole-frame kernel, whose queue cannot overflow
+                // (~0.25 s per native crop: a rare path); the other frames only pay for the hand-back launch and two early-exit grids
+                if (hd->tiers.big_fallback) {
+                    launch_inpaint_big_handback(hd->status, hd->big_only, B, st);
+                    launch_inpaint_telea(hd->img, bad_big, range, hd->inpaint_scratch, hd->status, hd->big_only, B, h, w, st);
+                }
             } else {
                 if (timed && mode == 1) hipEventRecord(hd->ev[ST_INPAINT], st);
                 if (mode != 1) only = launch_inpaint_window(hd->img, seq_mask, range, hd->inpaint_win_scratch, B, h, w, st, timed ? hd->ev[ST_INPAINT] : nullptr,
@@ -407,6 +415,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     TRY(dalloc(hd, &hd->cnt_a, mb)); TRY(dalloc(hd, &hd->cnt_valid, mb)); TRY(dalloc(hd, &hd->rel_count, mb));
     TRY(dalloc(hd, &hd->contact_count, mb)); TRY(dalloc(hd, &hd->bg_count, mb)); TRY(dalloc(hd, &hd->bad_count, mb));
     TRY(dalloc(hd, &hd->flipped, mb)); TRY(dalloc(hd, &hd->gmax, mb)); TRY(dalloc(hd, &hd->status, mb)); TRY(dalloc(hd, &hd->cc_best, mb));
+    TRY(dalloc(hd, &hd->big_only, mb));
     TRY(dalloc(hd, &hd->scalars, mb * VISTAF_NSCALARS));
     TRY(dalloc(hd, &hd->hole_med, mb)); TRY(dalloc(hd, &hd->hole_fill, mb));
     hd->named["mu"] = {hd->mu, sizeof(float)}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float)}; hd->named["thr_g"] = {hd->thr_g, sizeof(float)};
@@ -440,7 +449,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
 
 // carrier search + tables + demodulation of nb reference frames that preprocess() has left in hd->iw / hd->mu (shape_ftp.py:867-961).
 // Asynchronous; geometry lands in geom_dev[0..nb).  ph / pw: patch size the DFT launches use (session mode: read back from the geometry
-// between the two halves; pair mode: the full 2*bw+1 square, frames whose patch is clipped by the spectrum border are refused).
+// between the two halves; pair mode: every sample's own ph x pw inside the full 2*bw+1 square, clipped patches included).
 static int reference_search(vistaf_ftp_handle *hd, int nb, CarrierGeom *geom_dev, hipStream_t st)
 {
     const vistaf_ftp_config &c = hd->cfg;
@@ -727,10 +736,15 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
         size_t mb = hd->maxB;
         if ((rc = dalloc(hd, &hd->pgeom, mb)) || (rc = dalloc(hd, &hd->pEx, mb * w * pm)) || (rc = dalloc(hd, &hd->pGx, mb * w * pm)) ||
             (rc = dalloc(hd, &hd->pEy, mb * h * pm)) || (rc = dalloc(hd, &hd->pGy, mb * h * pm)) || (rc = dalloc(hd, &hd->pcref, mb * P)) ||
-            (rc = dalloc(hd, &hd->pamp_ref, mb * P)) || (rc = dalloc(hd, &hd->win_full, (size_t)pm * pm)))
+            (rc = dalloc(hd, &hd->pamp_ref, mb * P)) || (rc = dalloc(hd, &hd->pwin, mb * pm * pm)) || (rc = dalloc(hd, &hd->hann_tab, (size_t)(pm + 1) * pm)))
             return rc;
-        std::vector<float> win = hann_patch(pm, pm);
-        HIPCHK(hipMemcpy(hd->win_full, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
+        // every 1-D window a patch of up to pmax bins can need, as hann_patch() rounds it: the device forms each sample's window from these
+        std::vector<float> tab((size_t)(pm + 1) * pm, 0.0f);
+        for (int M = 1; M <= pm; M++) {
+            const std::vector<float> row = hann_patch(1, M);
+            std::copy(row.begin(), row.end(), tab.begin() + (size_t)M * pm);
+        }
+        HIPCHK(hipMemcpy(hd->hann_tab, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
         hd->pairs_ready = true;
     }
     HIPCHK(hipMemsetAsync(hd->status, 0, sizeof(int32_t) * B, st));
@@ -747,16 +761,17 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
     int rc = reference_search(hd, B, hd->pgeom, st);
     if (rc) return rc;
     launch_pair_status(hd->pgeom, pm, hd->status, together ? hd->status + B : nullptr, B, st);
-    launch_build_tables(hd->pgeom, 1, hd->pEx, hd->pEy, hd->pGx, hd->pGy, sx, sy, B, h, w, pad, hd->Hf, hd->Wf, pm, st);
-    launch_dft_forward(hd->iw, hd->mu, hd->pEx, hd->pEy, sx, sy, hd->win_full, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st);
+    // every sample's patch in a pmax x pmax slot: its own ph x pw bins (fewer where the spectrum border clips it), zeros beyond
+    launch_build_tables(hd->pgeom, 1, hd->pEx, hd->pEy, hd->pGx, hd->pGy, sx, sy, B, h, w, pad, hd->Hf, hd->Wf, pm, st, hd->hann_tab, hd->pwin);
+    launch_dft_forward(hd->iw, hd->mu, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm);
     launch_dft_inverse(hd->patch, pm * pm, hd->pGx, hd->pGy, sx, sy, hd->tmpT, hd->pcref, hd->pamp_ref, nullptr, nullptr, 0, nullptr, nullptr, B, h, w,
-                       pm, pm, st);
+                       pm, pm, st, hd->pgeom);
     // ---- deformed frames, carrier locked to their own reference
     if (!together) preprocess(hd, d_defs, format, B, st, timed);
     if (timed) hipEventRecord(hd->ev[ST_DEMOD], st);
-    launch_dft_forward(iw_def, mu_def, hd->pEx, hd->pEy, sx, sy, hd->win_full, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st);
+    launch_dft_forward(iw_def, mu_def, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm);
     launch_dft_inverse(hd->patch, pm * pm, hd->pGx, hd->pGy, sx, sy, hd->tmpT, hd->keep_planes ? hd->field : nullptr, hd->amp, hd->pcref, hd->pamp_ref,
-                       (size_t)P, hd->prod, hd->wrapped, B, h, w, pm, pm, st);
+                       (size_t)P, hd->prod, hd->wrapped, B, h, w, pm, pm, st, hd->pgeom);
     return post_demod(hd, B, d_height_mm, d_reliable, d_scalars, d_status, hd->pgeom, st, bad_def);
 }
 
@@ -814,6 +829,8 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "fit_capped") hd->tiers.fit_capped = value != 0;
     else if (n == "telea_mw") hd->tiers.telea_mw = value != 0;
     else if (n == "big_queue_lds") hd->tiers.big_queue_lds = value != 0;
+    else if (n == "big_gq_cap" && (value == 0 || (value >= 64 && (value & (value - 1)) == 0))) hd->tiers.big_gq_cap = value;
+    else if (n == "big_fallback") hd->tiers.big_fallback = value != 0;
     else if (n == "unwrap_fast") hd->tiers.unwrap_fast = value != 0;
     else if (n == "big_chain") hd->tiers.big_chain = value != 0;
     else if (n == "keep_planes") hd->keep_planes = value != 0;

@@ -116,11 +116,12 @@ __global__ __launch_bounds__(256) void k_dft_fwd1_mfma(const float *__restrict__
 
 // stage 2: patch[b, a, c] = win[a,c] * sum_y Ey[a, y] * T[b, y, c]   (complex128 spectrum value times the float32 window, as upstream's
 // `patch *= win` under complex128: both parts times the window in float64)
-__global__ void k_dft_fwd2(const double2 *__restrict__ T, const double2 *__restrict__ Ey_all, size_t ey_stride, const float *__restrict__ win,
-                           double2 *__restrict__ patch, int h, int ph, int pw, int pstride)
+__global__ void k_dft_fwd2(const double2 *__restrict__ T, const double2 *__restrict__ Ey_all, size_t ey_stride, const float *__restrict__ win_all,
+                           int win_stride, double2 *__restrict__ patch, int h, int ph, int pw, int pstride)
 {
     size_t b = blockIdx.x;
     const double2 *Ey = Ey_all + b * ey_stride;
+    const float *win = win_all + b * (size_t)win_stride;
     const double2 *Tb = T + b * (size_t)h * pw;
     for (int t = threadIdx.x; t < ph * pw; t += blockDim.x) {       // one pass for patches up to 32 x 32 bins
         int a = t / pw, c = t % pw;
@@ -144,7 +145,8 @@ __global__ void k_dft_fwd2(const double2 *__restrict__ T, const double2 *__restr
 }
 
 void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, const double2 *Ey, size_t tab_stride_x, size_t tab_stride_y,
-                        const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st)
+                        const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st,
+                        int win_stride)
 {
     int rb = 256 / pw;
     if (rb > DFT_RB) rb = DFT_RB;
@@ -158,22 +160,25 @@ void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, con
         dim3 g1((h + rb * DFT_RR - 1) / (rb * DFT_RR), B);
         hipLaunchKernelGGL(k_dft_fwd1, g1, dim3(256), (size_t)rb * DFT_RR * w * sizeof(float), st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, rb);
     }
-    hipLaunchKernelGGL(k_dft_fwd2, dim3(B), dim3(std::min(1024, ((ph * pw + 63) / 64) * 64)), 0, st, (const double2 *)tmpT, Ey, tab_stride_y, win, patch, h, ph, pw,
-                       patch_stride);
+    hipLaunchKernelGGL(k_dft_fwd2, dim3(B), dim3(std::min(1024, ((ph * pw + 63) / 64) * 64)), 0, st, (const double2 *)tmpT, Ey, tab_stride_y, win, win_stride, patch, h,
+                       ph, pw, patch_stride);
 }
 
 // stage 3: Q[b, a, x] = sum_c patch[b, a, c] * Gx[c, x]
+// (geom: pair mode, rows a >= the sample's ph are never read by stage 4 and sums stop at its pw; ph / pw are the layout)
 __global__ void k_dft_inv1(const double2 *__restrict__ patch, int pstride, const double2 *__restrict__ Gx_all, size_t gx_stride,
-                           double2 *__restrict__ Q, int w, int ph, int pw)
+                           double2 *__restrict__ Q, int w, int ph, int pw, const CarrierGeom *__restrict__ geom)
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x;
     int a = blockIdx.y;
     size_t b = blockIdx.z;
     if (x >= w) return;
+    const int pwb = geom ? max(0, min(geom[b].pw, pw)) : pw;
+    if (geom && a >= max(0, min(geom[b].ph, ph))) return;
     const double2 *Gx = Gx_all + b * gx_stride;
     const double2 *pr = patch + b * (size_t)pstride + (size_t)a * pw;
     double ar = 0.0, ai = 0.0;
-    for (int c = 0; c < pw; c++) {
+    for (int c = 0; c < pwb; c++) {
         const double2 p = pr[c], g = Gx[(size_t)c * w + x];
         cmac(ar, ai, p.x, p.y, g.x, g.y);
     }
@@ -190,7 +195,7 @@ __global__ void k_dft_inv1(const double2 *__restrict__ patch, int pstride, const
 __global__ __launch_bounds__(256) void k_dft_inv2_mfma(const double2 *__restrict__ Q, const double2 *__restrict__ Gy_all, size_t gy_stride,
                                                        double2 *__restrict__ field, float *__restrict__ amp, const double2 *__restrict__ cref_all,
                                                        const float *__restrict__ amp_ref_all, size_t ref_stride, float *__restrict__ prod,
-                                                       float *__restrict__ wrapped, int h, int w, int ph)
+                                                       float *__restrict__ wrapped, int h, int w, int ph, const CarrierGeom *__restrict__ geom)
 {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const int x0 = blockIdx.x * 64, y0 = (blockIdx.y * 4 + wid) * 16;
@@ -203,11 +208,12 @@ __global__ __launch_bounds__(256) void k_dft_inv2_mfma(const double2 *__restrict
     v4f64 cre[4], cim[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) { cre[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; cim[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; }
-    const int K = 2 * ph;
+    const int phb = geom ? max(0, min(geom[b].ph, ph)) : ph;     // the sample's own extent: K and the re / im split as a launch of that size
+    const int K = 2 * phb;
     for (int k0 = 0; k0 < K; k0 += 4) {
         const int k = k0 + kk;
-        const bool in = k < K, hi = k >= ph;
-        const int kq = in ? (hi ? k - ph : k) : 0;
+        const bool in = k < K, hi = k >= phb;
+        const int kq = in ? (hi ? k - phb : k) : 0;
         const double a = in ? G[((size_t)ya * ph + kq) * 2 + (hi ? 1 : 0)] : 0.0;
         double2 q[4];
 #pragma unroll
@@ -247,11 +253,11 @@ __global__ __launch_bounds__(256) void k_dft_inv2_mfma(const double2 *__restrict
 
 void launch_dft_inverse(const double2 *patch, int patch_stride, const double2 *Gx, const double2 *Gy, size_t tab_stride_x, size_t tab_stride_y,
                         double2 *tmpQ, double2 *field, float *amp, const double2 *cref, const float *amp_ref, size_t ref_stride, float *prod,
-                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st)
+                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom)
 {
-    hipLaunchKernelGGL(k_dft_inv1, dim3((w + 255) / 256, ph, B), dim3(256), 0, st, patch, patch_stride, Gx, tab_stride_x, tmpQ, w, ph, pw);
+    hipLaunchKernelGGL(k_dft_inv1, dim3((w + 255) / 256, ph, B), dim3(256), 0, st, patch, patch_stride, Gx, tab_stride_x, tmpQ, w, ph, pw, geom);
     hipLaunchKernelGGL(k_dft_inv2_mfma, dim3((w + 63) / 64, (h + 63) / 64, B), dim3(256), 0, st, (const double2 *)tmpQ, Gy, tab_stride_y, field, amp, cref,
-                       amp_ref, ref_stride, prod, wrapped, h, w, ph);
+                       amp_ref, ref_stride, prod, wrapped, h, w, ph, geom);
 }
 
 // ---- full spectrum magnitude (reference-frame carrier search, shape_ftp.py:867-872), float64 as np.abs(fft2(float64)) ----

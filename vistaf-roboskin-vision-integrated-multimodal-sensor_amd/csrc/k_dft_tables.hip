@@ -10,6 +10,7 @@
 //   k_build_tables     Ex/Ey (forward, reflect padding of cv2.copyMakeBorder(BORDER_REFLECT) folded in) and
 //                      Gx/Gy (inverse: re-centred patch, crop, sub-bin ramp :955-960 and 1/(Hf*Wf) folded in)
 // Angles are reduced exactly in integers before sincospi, so a twiddle is good to ~2e-16.
+#include <algorithm>
 #include "kernels.hpp"
 
 namespace vf {
@@ -77,7 +78,8 @@ __global__ void k_pair_status(const CarrierGeom *__restrict__ geom, int pmax, in
     if (b >= B) return;
     const CarrierGeom g = geom[b];
     if (status2 && status[b] == 0 && status2[b] != 0) status[b] = status2[b];
-    if (!g.ok || g.ph != pmax || g.pw != pmax || !(g.period > 1e-12)) status[b] = 3;
+    if (!g.ok || !(g.period > 1e-12)) status[b] = 3;      // a patch clipped by the spectrum border is processed, as in session mode
+    (void)pmax;
 }
 void launch_pair_status(const CarrierGeom *geom, int pmax, int32_t *status, const int32_t *status2, int B, hipStream_t st)
 {
@@ -106,29 +108,39 @@ __device__ inline void foreach_reflection(int s, int n, int pad, int N, F body)
     }
 }
 
-// grid: (ceil(max(w,h) * pmax / 256), 4 tables, B); table strides in elements
+// grid: (ceil(max(w,h, pmax) * pmax / 256), 4 tables, B); table strides in elements.
+// Session mode: the tables of the ph x pw patch, packed.  Pair mode (hann != null): laid out for pmax x pmax (lh = lw = pmax), every entry
+// beyond the sample's own ph / pw zero, so that a batch of samples with clipped and unclipped patches shares one launch geometry.
 __global__ __launch_bounds__(256) void k_build_tables(const CarrierGeom *__restrict__ geom, int geom_stride, double2 *__restrict__ Ex_all,
                                                       double2 *__restrict__ Ey_all, double2 *__restrict__ Gx_all, double2 *__restrict__ Gy_all,
-                                                      size_t sx, size_t sy, int h, int w, int pad, int Hf, int Wf, int pmax)
+                                                      size_t sx, size_t sy, int h, int w, int pad, int Hf, int Wf, int pmax,
+                                                      const float *__restrict__ hann, float *__restrict__ win_all)
 {
     const size_t b = blockIdx.z;
     const CarrierGeom g = geom[b * geom_stride];
-    const int ph = min(g.ph, pmax), pw = min(g.pw, pmax);
+    const int ph = max(0, min(g.ph, pmax)), pw = max(0, min(g.pw, pmax));
+    const int lh = hann ? pmax : ph, lw = hann ? pmax : pw;          // layout extents
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     const int cxs = Wf / 2, cys = Hf / 2;
     switch (blockIdx.y) {
     case 0: {   // Ex[xs][c] = sum_X exp(-2 pi i f_c X / Wf), f_c = x0 + c - cxs
-        if (t >= w * pw) return;
-        const int xs = t / pw, c = t - xs * pw;
+        if (t >= w * lw) return;
+        const int xs = t / lw, c = t - xs * lw;
+        if (c >= pw) { Ex_all[b * sx + t] = make_double2(0.0, 0.0); return; }
         const long long f = posmod((long long)g.x0 + c - cxs, Wf);
         double er = 0.0, ei = 0.0;
         foreach_reflection(xs, w, pad, Wf, [&](int X) { const double2 u = unit_root((f * X) % Wf, Wf, -1.0); er += u.x; ei += u.y; });
         Ex_all[b * sx + t] = make_double2(er, ei);
         break;
     }
-    case 1: {   // Ey[a][ys]
-        if (t >= ph * h) return;
+    case 1: {   // Ey[a][ys]; pair mode: also the sample's window np.hanning(ph)[:, None] * np.hanning(pw)[None, :] in float32, zero beyond ph x pw
+        if (hann && t < pmax * pmax) {
+            const int a = t / pmax, c = t - a * pmax;
+            win_all[b * (size_t)pmax * pmax + t] = (a < ph && c < pw) ? __fmul_rn(hann[ph * pmax + a], hann[pw * pmax + c]) : 0.0f;
+        }
+        if (t >= lh * h) return;
         const int a = t / h, ys = t - a * h;
+        if (a >= ph) { Ey_all[b * sy + t] = make_double2(0.0, 0.0); return; }
         const long long f = posmod((long long)g.y0 + a - cys, Hf);
         double er = 0.0, ei = 0.0;
         foreach_reflection(ys, h, pad, Hf, [&](int Y) { const double2 u = unit_root((f * Y) % Hf, Hf, -1.0); er += u.x; ei += u.y; });
@@ -136,8 +148,9 @@ __global__ __launch_bounds__(256) void k_build_tables(const CarrierGeom *__restr
         break;
     }
     case 2: {   // Gx[c][x] = exp(+2 pi i ((c - pw/2) - dpx) (x + pad) / Wf): integer part reduced exactly, sub-bin part |.| <= pi
-        if (t >= pw * w) return;
+        if (t >= lw * w) return;
         const int c = t / w, x = t - c * w;
+        if (c >= pw) { Gx_all[b * sx + t] = make_double2(0.0, 0.0); return; }
         const long long X = x + pad;
         const long long m = posmod((long long)(g.keep_carrier ? g.x0 + c - cxs : c - pw / 2) * X, Wf);
         double s, co;
@@ -146,8 +159,9 @@ __global__ __launch_bounds__(256) void k_build_tables(const CarrierGeom *__restr
         break;
     }
     default: {  // Gy[y][a], with the 1 / (Hf * Wf) of ifft2
-        if (t >= h * ph) return;
-        const int y = t / ph, a = t - y * ph;
+        if (t >= h * lh) return;
+        const int y = t / lh, a = t - y * lh;
+        if (a >= ph) { Gy_all[b * sy + t] = make_double2(0.0, 0.0); return; }
         const long long Y = y + pad;
         const long long m = posmod((long long)(g.keep_carrier ? g.y0 + a - cys : a - ph / 2) * Y, Hf);
         double s, co;
@@ -160,11 +174,12 @@ __global__ __launch_bounds__(256) void k_build_tables(const CarrierGeom *__restr
 }
 
 void launch_build_tables(const CarrierGeom *geom, int geom_stride, double2 *Ex, double2 *Ey, double2 *Gx, double2 *Gy, size_t stride_x,
-                         size_t stride_y, int B, int h, int w, int pad, int Hf, int Wf, int pmax, hipStream_t st)
+                         size_t stride_y, int B, int h, int w, int pad, int Hf, int Wf, int pmax, hipStream_t st, const float *pair_hann,
+                         float *pair_win)
 {
-    const int n = (h > w ? h : w) * pmax;
-    hipLaunchKernelGGL(k_build_tables, dim3((n + 255) / 256, 4, B), dim3(256), 0, st, geom, geom_stride, Ex, Ey, Gx, Gy, stride_x, stride_y, h, w,
-                       pad, Hf, Wf, pmax);
+    const int n = std::max((h > w ? h : w) * pmax, pmax * pmax);
+    hipLaunchKernelGGL(k_build_tables, dim3((n + 255) / 256, 4, B), dim3(256), 0, st, geom, geom_stride, Ex, Ey, Gx, Gy, stride_x,
+                       stride_y, h, w, pad, Hf, Wf, pmax, pair_hann, pair_win);
 }
 
 // Full-spectrum tables (carrier search): Exf[xs][f] (w x Wh, Wh = Wf/2 + 1: the spectrum of a real frame is Hermitian), Eyf[f][ys] (Hf x h),

@@ -207,7 +207,8 @@ __global__ __launch_bounds__(64) void k_telea_big_clusters(float *__restrict__ i
                                                            const int32_t *__restrict__ labels_all, const int32_t *__restrict__ list_all,
                                                            const int32_t *__restrict__ count, const int32_t *__restrict__ xmin,
                                                            const int32_t *__restrict__ ymin, const int32_t *__restrict__ xmax,
-                                                           const int32_t *__restrict__ ymax, int32_t *status, int range, int h, int w, int gq_cap, int lds_cap, int lds_use)
+                                                           const int32_t *__restrict__ ymax, int32_t *status, int range, int h, int w, int gq_stride, int gq_cap,
+                                                           int lds_cap, int lds_use)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char bg_lds[];
     const int lane = threadIdx.x;
@@ -218,7 +219,7 @@ __global__ __launch_bounds__(64) void k_telea_big_clusters(float *__restrict__ i
     float *t = gT + b * en, *im = gim + b * en;
     uint8_t *f = gf + b * en;
     float *img = img_all + b * (size_t)P;
-    unsigned long long *gq = gq_all + (b * gridDim.x + blockIdx.x) * (size_t)gq_cap;
+    unsigned long long *gq = gq_all + (b * gridDim.x + blockIdx.x) * (size_t)gq_stride;      // gq_cap <= gq_stride
     for (int c = blockIdx.x; c < ncl; c += gridDim.x) {
         const int rootp = list_all[b * (size_t)P + c];
         const size_t root = b * (size_t)P + rootp;
@@ -237,7 +238,7 @@ __global__ __launch_bounds__(64) void k_telea_big_clusters(float *__restrict__ i
         bool ok;
         if (need <= lds_use) ok = bg_march<true>(W, t, im, f, bg_lds, gq, gq_cap, lds_cap, range, lane);
         else ok = bg_march<false>(W, t, im, f, bg_lds, gq, gq_cap, lds_cap, range, lane);
-        if (!ok) { if (lane == 0) status[b] = 2; continue; }
+        if (!ok) { if (lane == 0) status[b] = 2; continue; }          // the frame goes to the whole-frame kernel (launch_inpaint_big_handback)
         bg_each(W, f, lane, [&](int cell, uint8_t v) {
             if (v & W_HOLE) { const int Y = cell / ew, X = cell - Y * ew; img[(size_t)(Y - M) * w + (X - M)] = im[cell]; }
         });
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(64) void k_telea_big_clusters(float *__restrict__ i
 
 // The hole pixels of `bad_big` (clusters too large for an LDS window), one wave per cluster, up to 32 waves per frame.
 void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, void *scratch, int32_t *status, const ClusterPlanes &left, int B, int h,
-                                 int w, hipStream_t st, bool lds_queue)
+                                 int w, hipStream_t st, bool lds_queue, int gq_cap_test)
 {
     const int M = range + 1;
     const size_t en = (size_t)(h + 2 * M) * (w + 2 * M);
@@ -255,7 +256,9 @@ void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, 
     float *gim = gT + (size_t)B * en;
     uint8_t *gf = (uint8_t *)(gim + (size_t)B * en);
     unsigned long long *gq = (unsigned long long *)((((uintptr_t)(gf + (size_t)B * en)) + 255) & ~(uintptr_t)255);
-    const int nslot = bg_slots(h, w), gq_cap = bg_gq_cap(h, w);
+    const int nslot = bg_slots(h, w), gq_stride = bg_gq_cap(h, w);
+    // the capacity checked by the march: the slice itself, or (test hook) a smaller power of two inside it -- pushes stay within the slice
+    const int gq_cap = (gq_cap_test >= 64 && gq_cap_test < gq_stride && (gq_cap_test & (gq_cap_test - 1)) == 0) ? gq_cap_test : gq_stride;
     hipLaunchKernelGGL(k_bg_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, img, bad_big, left.dil, gT, gim, gf, range, h, w);
     // LDS queue: 16384 entries (128 KB, one march per CU) while the batch has fewer big clusters than the chip has CUs -- a native crop has
     // about ten --, 8192 (two marches per CU) for larger batches; a cluster whose cell counts exceed the queue takes the global slice
@@ -263,7 +266,23 @@ void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, 
     static DynLdsOnce lds_once;
     ensure_dyn_lds(lds_once, (const void *)k_telea_big_clusters, BG_QCAP * 8 + 256);
     hipLaunchKernelGGL(k_telea_big_clusters, dim3(nslot, B), dim3(64), (size_t)lds_cap * 8 + 256, st, img, gT, gim, gf, gq, left.labels, left.list, left.count,
-                       left.xmin, left.ymin, left.xmax, left.ymax, status, range, h, w, gq_cap, lds_cap, lds_queue ? lds_cap : 0);
+                       left.xmin, left.ymin, left.xmax, left.ymax, status, range, h, w, gq_stride, gq_cap, lds_cap, lds_queue ? lds_cap : 0);
+}
+
+// A frame with an overflowed big cluster is left partly inpainted (the clusters that finished are written, the overflowed one is not).  The
+// whole-frame kernel, whose queue holds every cell of the frame, then re-marches ALL of the frame's big-cluster pixels: clusters are
+// separated by more than the estimator's reach (k_inpaint_cl.hip), so the finished ones come out with the same bits again.
+__global__ void k_bg_handback(int32_t *__restrict__ status, int32_t *__restrict__ only, int B)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int s = status[b];
+    only[b] = s == 2 ? 1 : 0;
+    if (s == 2) status[b] = 0;
+}
+void launch_inpaint_big_handback(int32_t *status, int32_t *only, int B, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_bg_handback, dim3((B + 63) / 64), dim3(64), 0, st, status, only, B);
 }
 
 }  // namespace vf

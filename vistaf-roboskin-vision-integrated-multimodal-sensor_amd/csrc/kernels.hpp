@@ -18,6 +18,8 @@ struct Tiers {
     int unwrap_fast = 1;        // 1: frames whose wrapped field is verified path-independent skip the priority flood (k_unwrap_fast.hip); 0: always flood
     int big_chain = 1;          // 1: frames of 512 x 512 and more take k_big.hip's chains of streaming kernels for the exact selections and the IRLS fits; 0: one workgroup per frame
     int big_queue_lds = 1;      // 1: a big cluster's march keeps its queue in LDS whenever its cell counts bound the queue (k_inpaint_big.hip); 0: always this wave's slice of global memory
+    int big_gq_cap = 0;         // test only: capacity (entries, power of two) the big-cluster march checks its global queue slice against; 0: the slice's own size
+    int big_fallback = 1;       // 1: frames whose big-cluster queue overflowed are re-marched by the whole-frame kernel; 0: they keep status 2 (test only)
     int telea_mw = 1;           // 1: the 16-wave window kernel (ordering pass + dataflow fills, k_inpaint_mw.hip) as first tier, single-wave tiers behind it; 0: single-wave tiers only
 };
 
@@ -63,21 +65,29 @@ struct CarrierGeom {
     int ok;
     int keep_carrier;           // 0: the patch is re-centred at DC before the inverse transform (FTP, :945-948); 1: band-pass in place
 };
-// table strides are in elements per frame (0: one table for the whole batch)
+// table strides are in elements per frame (0: one table for the whole batch).  ph / pw: the patch layout (pair mode: pmax x pmax, each sample's
+// own extents inside it, tables and window zero beyond them); win_stride: elements per frame of the window (0: one window for the batch)
 void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, const double2 *Ey, size_t tab_stride_x, size_t tab_stride_y,
-                        const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st);
-// field (may be null): float64 field out; cref/amp_ref (may be null): reference field -> wrapped phase difference and amp product
+                        const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st,
+                        int win_stride = 0);
+// field (may be null): float64 field out; cref/amp_ref (may be null): reference field -> wrapped phase difference and amp product.
+// geom (pair mode, may be null): the sums run over each sample's own geom[b].ph x geom[b].pw bins of the ph x pw layout, in the order of a
+// ph x pw launch of that size (session mode), so a clipped patch gives the bits of its own session
 void launch_dft_inverse(const double2 *patch, int patch_stride, const double2 *Gx, const double2 *Gy, size_t tab_stride_x, size_t tab_stride_y,
                         double2 *tmpQ, double2 *field, float *amp, const double2 *cref, const float *amp_ref, size_t ref_stride, float *prod,
-                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st);
+                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom = nullptr);
 void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_full, const double2 *Ey_full, double2 *tmp,
                          double *mag, int B, int h, int w, int Hf, int Wf, hipStream_t st);
 void launch_top_peaks(const double *mag, int B, int Hf, int Wf, int dc, int npeaks, double *out_xyv /* [B][192] */, hipStream_t st);
 void launch_carrier_choose(const double *peaks, int npk, const double *mag, int Hf, int Wf, int bw, double max_dy_frac, CarrierGeom *geom, int B,
                            hipStream_t st);
+// pair_hann (pair mode, may be null): hann(M)[i] as float32 at pair_hann[M * pmax + i], 1 <= M <= pmax.  Given, the tables are laid out for a
+// pmax x pmax patch with zeros beyond each sample's ph / pw, and pair_win[b] (pmax x pmax) receives the sample's window hann(ph) x hann(pw)
+// (zeros elsewhere) -- the float32 products hann_patch() forms on the host for a session
 void launch_build_tables(const CarrierGeom *geom, int geom_stride, double2 *Ex, double2 *Ey, double2 *Gx, double2 *Gy, size_t stride_x,
-                         size_t stride_y, int B, int h, int w, int pad, int Hf, int Wf, int pmax, hipStream_t st);
-// pair mode: frames without a usable carrier (or whose patch is clipped by the spectrum border) get status VISTAF_FRAME_NO_CARRIER
+                         size_t stride_y, int B, int h, int w, int pad, int Hf, int Wf, int pmax, hipStream_t st, const float *pair_hann = nullptr,
+                         float *pair_win = nullptr);
+// pair mode: frames without a usable carrier (no peak, or a non-positive period) get status VISTAF_FRAME_NO_CARRIER
 void launch_pair_status(const CarrierGeom *geom, int pmax, int32_t *status, const int32_t *status2, int B, hipStream_t st);
 void launch_build_full_tables(double2 *Exf, double2 *Eyf, int h, int w, int pad, int Hf, int Wf, hipStream_t st);
 
@@ -113,8 +123,11 @@ struct ClusterPlanes { const int32_t *labels, *list, *count, *xmin, *ymin, *xmax
 // the clusters the LDS windows left over, each on its own wave over padded global planes with the queue in LDS (k_inpaint_big.hip)
 size_t inpaint_big_scratch_bytes_per_frame(int h, int w);
 bool inpaint_big_supported(int range);
+// gq_cap (test hook big_gq_cap): capacity the march checks its global queue slice against, a power of two <= the slice; 0: the slice's size
 void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, void *scratch, int32_t *status, const ClusterPlanes &left, int B, int h,
-                                 int w, hipStream_t st, bool lds_queue = true);
+                                 int w, hipStream_t st, bool lds_queue = true, int gq_cap = 0);
+// status[b] == 2 (a big cluster's queue overflowed) -> only[b] = 1 and status[b] = 0, else only[b] = 0: the frames for launch_inpaint_telea
+void launch_inpaint_big_handback(int32_t *status, int32_t *only, int B, hipStream_t st);
 void launch_inpaint_clusters(float *img, const uint8_t *bad, int range, void *scratch, uint8_t **bad_big_out, ClusterPlanes *left, int B, int h, int w,
                              hipStream_t st);
 

@@ -186,6 +186,7 @@ struct vistaf_tempseg_handle {
     uint32_t *tm_stats = nullptr;
     int32_t *tm_status = nullptr;
     unsigned long long *tm_counts = nullptr;
+    bool tm_ready = false, seg_ready = false;       // raised once every buffer of the set is allocated (tm_ensure / seg_ensure)
     LabCoef lab;
 };
 
@@ -222,26 +223,20 @@ void vistaf_tempseg_destroy(vistaf_tempseg_handle *h)
     delete h;
 }
 
-int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf_tempseg_handle **out)
+// The segmentation's workspace: planes, spectrum, DFT tables, illumination taps and the hipFFT plan.  Built on the first segment call, so
+// that a session used for the feature planes or the map stages only never pays for it; seg_ready is raised only once all of it exists.
+static int seg_ensure(vistaf_tempseg_handle *h)
 {
-    if (!cfg || !out) return set_error(VISTAF_E_INVALID, "null argument");
-    if (H < 64 || W < 64 || H % 16) return set_error(VISTAF_E_INVALID, "frame height must be a multiple of 16 (matrix-core strips), both sides >= 64");
-    const int R = cfg->seg_band_radius;
-    if (R < 1 || 2 * R + 1 > 127 || cfg->n_peaks < 1 || cfg->n_peaks > 64) return set_error(VISTAF_E_INVALID, "band radius / peak count out of range");
-    for (int k : {ensure_odd(std::max(1, cfg->post_close_ky)), ensure_odd(std::max(1, cfg->post_open_ky)), ensure_odd(cfg->sat_dilate_ksize)})
-        if (k > 33) return set_error(VISTAF_E_INVALID, "structuring element taller than 33");
-    for (int k : {ensure_odd(std::max(1, cfg->post_close_kx)), ensure_odd(std::max(1, cfg->post_open_kx))})
-        if (k > 127) return set_error(VISTAF_E_INVALID, "structuring element wider than 127");
-    vistaf_tempseg_handle *h = new vistaf_tempseg_handle();
-    h->cfg = *cfg; h->H = H; h->W = W; h->P = (size_t)H * W; h->pm = 2 * R + 1;
+    if (h->seg_ready) return 0;
+    const vistaf_tempseg_config *cfg = &h->cfg;
+    const int H = h->H, W = h->W, R = cfg->seg_band_radius, pm = h->pm;
     const size_t P = h->P;
-    const int pm = h->pm;
     int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { vistaf_tempseg_destroy(h); return rc; } } while (0)
+#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     TRY(talloc(h, &h->gray, P)); TRY(talloc(h, &h->g, P)); TRY(talloc(h, &h->tmpf, P)); TRY(talloc(h, &h->blur, P)); TRY(talloc(h, &h->norm, P));
     TRY(talloc(h, &h->inorm, P)); TRY(talloc(h, &h->amp, P)); TRY(talloc(h, &h->med, 4)); TRY(talloc(h, &h->cnt, 4));
     TRY(talloc(h, &h->sat0, P)); TRY(talloc(h, &h->sat, P)); TRY(talloc(h, &h->roi_eff, P)); TRY(talloc(h, &h->ma, P)); TRY(talloc(h, &h->mb, P));
-    TRY(talloc(h, &h->m1, P)); TRY(talloc(h, &h->m2, P)); TRY(talloc(h, &h->prefix, P));
+    TRY(talloc(h, &h->m2, P));
     TRY(talloc(h, &h->F, (size_t)H * (W / 2 + 1))); TRY(talloc(h, &h->mag, P)); TRY(talloc(h, &h->peaks, 192));
     TRY(talloc(h, &h->partial, (size_t)4 * TS_RB)); TRY(talloc(h, &h->sums, 8));
     TRY(talloc(h, &h->Ex, (size_t)W * pm)); TRY(talloc(h, &h->Gx, (size_t)W * pm)); TRY(talloc(h, &h->Ey, (size_t)H * pm)); TRY(talloc(h, &h->Gy, (size_t)H * pm));
@@ -249,25 +244,53 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
     TRY(talloc(h, &h->win, (size_t)pm * pm)); TRY(talloc(h, &h->req_med, 1));
     {
         const float neg = -1.0f;                                    // launch_select: a negative request is the median
-        if (hipMemcpy(h->req_med, &neg, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
+        if (hipMemcpy(h->req_med, &neg, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
         std::vector<float> win((size_t)pm * pm);                    // the band-pass disc (:463-465) as the patch "window"
         for (int a = 0; a < pm; a++)
             for (int c = 0; c < pm; c++) win[(size_t)a * pm + c] = ((a - R) * (a - R) + (c - R) * (c - R) <= R * R) ? 1.0f : 0.0f;
-        if (hipMemcpy(h->win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
+        if (hipMemcpy(h->win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
     }
+    h->gksize = 0;
     if (cfg->seg_illum_sigma > 0) {
         const double sigma = (double)cfg->seg_illum_sigma;
-        const int n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;    // cv::GaussianBlur ksize rule, CV_32F
-        if (n > 511) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_INVALID, "illumination sigma too large"); }
+        const int n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;    // cv::GaussianBlur ksize rule, CV_32F (size checked at create)
         std::vector<double> t(n);
         double s2 = -0.5 / (sigma * sigma), sum = 0;
         for (int i = 0; i < n; i++) { double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
         std::vector<float> f(n);
         for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
         TRY(talloc(h, &h->gk, (size_t)n));
-        if (hipMemcpy(h->gk, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
+        if (hipMemcpy(h->gk, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
         h->gksize = n;
     }
+    if (!h->have_plan) {
+        if (hipfftPlan2d(&h->plan, H, W, HIPFFT_R2C) != HIPFFT_SUCCESS) return set_error(VISTAF_E_HIP, "hipfftPlan2d failed");
+        h->have_plan = true;
+    }
+#undef TRY
+    h->seg_ready = true;
+    return 0;
+}
+
+int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf_tempseg_handle **out)
+{
+    if (!cfg || !out) return set_error(VISTAF_E_INVALID, "null argument");
+    if (H < 1 || W < 1) return set_error(VISTAF_E_INVALID, "frame sides must be >= 1");
+    const int R = cfg->seg_band_radius;
+    if (R < 1 || 2 * R + 1 > 127 || cfg->n_peaks < 1 || cfg->n_peaks > 64) return set_error(VISTAF_E_INVALID, "band radius / peak count out of range");
+    for (int k : {ensure_odd(std::max(1, cfg->post_close_ky)), ensure_odd(std::max(1, cfg->post_open_ky)), ensure_odd(cfg->sat_dilate_ksize)})
+        if (k > 33) return set_error(VISTAF_E_INVALID, "structuring element taller than 33");
+    for (int k : {ensure_odd(std::max(1, cfg->post_close_kx)), ensure_odd(std::max(1, cfg->post_open_kx))})
+        if (k > 127) return set_error(VISTAF_E_INVALID, "structuring element wider than 127");
+    if (cfg->seg_illum_sigma > 0 && (((int)std::nearbyint((double)cfg->seg_illum_sigma * 4 * 2 + 1)) | 1) > 511)
+        return set_error(VISTAF_E_INVALID, "illumination sigma too large");
+    vistaf_tempseg_handle *h = new vistaf_tempseg_handle();
+    h->cfg = *cfg; h->H = H; h->W = W; h->P = (size_t)H * W; h->pm = 2 * R + 1;
+    const size_t P = h->P;
+    int rc = 0;
+#define TRY(x) do { rc = (x); if (rc) { vistaf_tempseg_destroy(h); return rc; } } while (0)
+    // what the colour support needs (a mask plane and the morphology's prefix scratch); the segmentation's workspace waits for seg_ensure
+    TRY(talloc(h, &h->m1, P)); TRY(talloc(h, &h->prefix, P));
     {
         // The integer tables of OpenCV's 8-bit BGR2LAB: sRGB gamma of i / 255 scaled by 255 * 2^3, the Lab cube-root function of
         // i / (255 * 2^3) scaled by 2^15, and the sRGB -> XYZ (D65) matrix over the white point scaled by 2^12.
@@ -291,8 +314,6 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
         if (hipMemcpy(h->gamma_tab, gt.data(), gt.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->cbrt_tab, ct.data(), ct.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
     }
-    if (hipfftPlan2d(&h->plan, H, W, HIPFFT_R2C) != HIPFFT_SUCCESS) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "hipfftPlan2d failed"); }
-    h->have_plan = true;
 #undef TRY
     *out = h;
     return 0;
@@ -302,6 +323,10 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
                            uint8_t *d_sat, double *info, void *stream)
 {
     if (!h || !d_bgr || !d_roi) return set_error(VISTAF_E_INVALID, "null argument");
+    if (h->H < 64 || h->W < 64 || h->H % 16)
+        return set_error(VISTAF_E_INVALID, "segment: frame height must be a multiple of 16 (matrix-core strips of the band-pass DFT), both sides >= 64");
+    int rc_ws = seg_ensure(h);
+    if (rc_ws) return rc_ws;
     hipStream_t st = (hipStream_t)stream;
     const vistaf_tempseg_config &c = h->cfg;
     const int H = h->H, W = h->W, pm = h->pm, R = c.seg_band_radius;
@@ -425,7 +450,7 @@ int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const 
 // ---- map-domain stages (Code/temperature_sensor.py:538-640, :705-747); parity unpinned (k_tempmap.hip)
 static int tm_ensure(vistaf_tempseg_handle *h)
 {
-    if (h->tmA) return 0;
+    if (h->tm_ready) return 0;
     int rc = 0;
 #define TMTRY(x) do { rc = (x); if (rc) return rc; } while (0)
     TMTRY(talloc(h, &h->tmA, h->P)); TMTRY(talloc(h, &h->tmB, h->P));
@@ -435,6 +460,7 @@ static int tm_ensure(vistaf_tempseg_handle *h)
     TMTRY(talloc(h, &p, inpaint_scratch_bytes_per_frame(h->H, h->W))); h->tm_scratch = p;
     TMTRY(talloc(h, &h->tm_stats, (size_t)4)); TMTRY(talloc(h, &h->tm_status, (size_t)4)); TMTRY(talloc(h, &h->tm_counts, (size_t)4));
 #undef TMTRY
+    h->tm_ready = true;
     return 0;
 }
 static int tm_done(const char *what)

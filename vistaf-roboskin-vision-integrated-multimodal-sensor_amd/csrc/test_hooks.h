@@ -20,6 +20,10 @@ extern "C" {
  *       "telea_mw"     1 (default) 16-wave window kernel (ordering pass + dataflow fills) in front of the single-wave tiers, 0 single-wave tiers only
  *       "big_queue_lds" 1 (default) the march of a cluster no LDS window takes (k_inpaint_big.hip) keeps its queue in LDS whenever the cluster's cell
  *                      counts bound it, 0 always in the wave's slice of global memory (the path of clusters beyond that bound)
+ *       "big_gq_cap"   capacity (entries, a power of two >= 64) that the big-cluster march checks its global queue slice against; 0 (default)
+ *                      the slice's own size.  Only shrinks the capacity: the slice stride stays, pushes stay bounds-checked (overflow -> status 2)
+ *       "big_fallback" 1 (default) a frame whose big-cluster queue overflowed (status 2) is re-marched whole by the whole-frame kernel,
+ *                      0 the frame keeps status 2 and its overflowed cluster stays unfilled (shows that an overflow happened)
  *       "fit_capped"   0 (default) the 128-VGPR column polyfit, 1 the register-capped variant (96 VGPRs) that shares a CU with LDS-heavy one-wave kernels
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
