@@ -89,9 +89,9 @@ typedef struct vistaf_ftp_config {
     int32_t bad_inpaint_radius;         /* :123 3    */
     int32_t dilate_kernel_size;         /* :129 15   */
     int32_t dilate_iters;               /* :130 2    */
-    int32_t n_fft_peaks;                /* :168 12   */
+    int32_t n_fft_peaks;                /* :168 12   (1..64: vistaf_ftp_create refuses other values with VISTAF_E_INVALID) */
     int32_t plane_order_for_removal;    /* :212 1    */
-    int32_t irls_iters;                 /* :1100 6   */
+    int32_t irls_iters;                 /* :1100 6   (>= 1: with none upstream's IRLS loop binds no coefficients; refused below 1) */
     int32_t hole_neighborhood_px;       /* :140 11   (only read when reliable_smooth_sigma_px == 0, see :1770-1801) */
     int32_t hole_min_dist_px;           /* :142 4    */
     int32_t inpaint_radius;             /* :144 5    */

@@ -750,10 +750,13 @@ def process_frame(def_gray_u8, ref_state, cfg, cal_model, cal_use_neg=True,
         thr = nanpercentile_safe(abs_res, 95, mask=reliable, fallback=0.0)
     contact = (abs_res >= float(thr)) & reliable & np.isfinite(abs_res)
     frac = contact.sum() / max(1, reliable.sum())
+    contact_fallback = None
     if frac < cfg.min_contact_frac:
+        contact_fallback = "min"
         thr2 = nanpercentile_safe(abs_res, 95, mask=reliable, fallback=thr)
         contact = (abs_res >= float(thr2)) & reliable & np.isfinite(abs_res)
     elif frac > cfg.max_contact_frac:
+        contact_fallback = "max"
         thr2 = nanpercentile_safe(abs_res, 98, mask=reliable, fallback=thr)
         contact = (abs_res >= float(thr2)) & reliable & np.isfinite(abs_res)
     se = cv.ellipse_se(int(cfg.dilate_kernel_size))
@@ -853,7 +856,7 @@ def process_frame(def_gray_u8, ref_state, cfg, cal_model, cal_use_neg=True,
         out["inter"] = {
             "demod": dd, "quality": quality, "amp_thr": amp_thr, "thresholded": thresholded,
             "wrapped": wrapped, "unwrapped": unwrapped, "deramped": deramped, "residual0": residual0,
-            "contact_thr": thr, "background": background, "coef": coef, "bg_med": bg_med,
-            "zeroed": zeroed, "height_smooth": height_map, "core_thr": core_thr, "height_rel": height_rel,
+            "contact_thr": thr, "contact_frac": frac, "contact_fallback": contact_fallback, "background": background, "coef": coef, "bg_med": bg_med,
+            "zeroed": zeroed, "height_smooth": height_map, "core_thr": core_thr, "height_rel": height_rel, "depth_mm": depth_mm,
         }
     return out

@@ -51,6 +51,10 @@ def test_header_comments_state_what_is_refused():
     qo = ftp_h[ftp_h.index("#define VISTAF_FRAME_QUEUE_OVERFLOW"):]
     qo = qo[:qo.index("*/")]
     assert "unwrap" in qo and "whole-frame" in qo
+    # constants the reference would not compute the same way are refused at create, and the header says so next to the field
+    for field, limit in (("n_fft_peaks", "1..64"), ("irls_iters", ">= 1")):
+        line = next(ln for ln in ftp_h.splitlines() if re.search(r"\b%s;" % field, ln))
+        assert limit in line and "refuse" in line, line
     temp_h = _read(ROOT, "include", "vistaf_temp.h")
     assert "multiple of 16" in temp_h and "any H, W >= 1" in temp_h
     ts = _read(PKG_DIR, "csrc", "tempseg.hip")

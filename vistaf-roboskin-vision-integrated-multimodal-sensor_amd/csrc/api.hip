@@ -321,7 +321,8 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
         return fail(VISTAF_E_INVALID, "Unknown model type in calibration");
     if (cfg->poly_order < 1 || cfg->poly_order > 2 || cfg->plane_order_for_removal < 0 || cfg->plane_order_for_removal > 2)
         return fail(VISTAF_E_INVALID, "polynomial order must be 1 or 2 (plane_order_for_removal: 0 = no pre-removal)");
-    if (cfg->patch_half_width_bins < 3 && cfg->patch_half_width_bins != 0) {}
+    if (cfg->irls_iters < 1) return fail(VISTAF_E_INVALID, "irls_iters must be >= 1 (robust_polyfit2d binds no coefficients otherwise)");
+    if (cfg->n_fft_peaks < 1 || cfg->n_fft_peaks > 64) return fail(VISTAF_E_INVALID, "n_fft_peaks must be 1..64");
     int bwp = std::max(3, cfg->patch_half_width_bins);
     if (2 * bwp + 1 > 255) return fail(VISTAF_E_INVALID, "patch too wide");
     vistaf_ftp_handle *hd = new vistaf_ftp_handle();
@@ -477,7 +478,7 @@ static int reference_search(vistaf_ftp_handle *hd, int nb, CarrierGeom *geom_dev
             return rc;
         hd->search_cap = cap;
     }
-    const int npk = std::min(std::max(1, c.n_fft_peaks), 64);
+    const int npk = c.n_fft_peaks;                  // 1..64, checked by vistaf_ftp_create
     launch_dft_full_mag(hd->iw, hd->mu, hd->Exf, hd->Eyf, hd->search_tmp, hd->search_mag, nb, h, w, Hf, Wf, st);
     launch_top_peaks(hd->search_mag, nb, Hf, Wf, c.dc_exclusion, npk, hd->search_peaks, st);
     launch_carrier_choose(hd->search_peaks, npk, hd->search_mag, Hf, Wf, std::max(3, c.patch_half_width_bins), c.peak_max_dy_from_center, geom_dev, nb, st);
@@ -555,10 +556,12 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
             launch_morph_seq(hd->rel0, hd->rel1, hd->rel2, B, h, w, hd->se_close, ops, 2 * c.valid_close_iters, hd->roi, nullptr, st, hd->morph_pre);
             src = hd->rel1;
         } else {
-            for (int it = 0; it < c.valid_close_iters; it++) { launch_morph(src, dst, B, h, w, hd->se_close, true, nullptr, nullptr, st, hd->morph_pre); std::swap(src, dst); }
-            for (int it = 0; it < c.valid_close_iters; it++) {
-                launch_morph(src, dst, B, h, w, hd->se_close, false, it == c.valid_close_iters - 1 ? hd->roi : nullptr, nullptr, st, hd->morph_pre);
-                std::swap(src, dst);
+            // rel1 / rel2 alternate; rel0 keeps the thresholded mask (the "rel0" intermediate)
+            for (int it = 0; it < 2 * c.valid_close_iters; it++) {
+                const bool dil = it < c.valid_close_iters;
+                launch_morph(src, dst, B, h, w, hd->se_close, dil, it == 2 * c.valid_close_iters - 1 ? hd->roi : nullptr, nullptr, st, hd->morph_pre);
+                src = dst;
+                dst = dst == hd->rel1 ? hd->rel2 : hd->rel1;
             }
         }
         launch_cc_label(src, hd->labels, B, h, w, st);
@@ -593,11 +596,13 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, hd->tiers.fit_capped, hd->tiers.big_chain ? hd->big_scratch : nullptr);
     launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
-    launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, (float)c.min_contact_frac, (float)c.max_contact_frac,
+    launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
                         hd->contact, hd->thr_used, B, P, st);
     {
-        int iters = std::max(1, c.dilate_iters);
-        if (iters <= 4) {
+        // cv2.dilate with 0 iterations is a copy (contact is inside reliable already)
+        int iters = c.dilate_iters;
+        if (iters <= 0) HIPCHK(hipMemcpyAsync(hd->contact_d, hd->contact, (size_t)B * P, hipMemcpyDeviceToDevice, st));
+        else if (iters <= 4) {
             int ops[4] = {1, 1, 1, 1};
             launch_morph_seq(hd->contact, hd->contact_d, hd->cand, B, h, w, hd->se_contact, ops, iters, nullptr, hd->reliable, st, hd->morph_pre);   // cand is free until the blob filter
         } else {
@@ -666,7 +671,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     if (timed) hipEventRecord(hd->ev[ST_MM_BLOB], st);
     launch_to_mm(hd->unitless, hd->roi, hd->hcurve, hd->use_neg, hd->depth, hd->cand, hd->gmax, B, P, st);
     launch_cc_label(hd->cand, hd->labels, B, h, w, st);
-    launch_blob_filter(hd->depth, hd->cand, hd->labels, hd->peak_bits, hd->gmax, (float)c.contact_blob_min_peak_mm,
+    launch_blob_filter(hd->depth, hd->cand, hd->labels, hd->peak_bits, hd->gmax, c.contact_blob_min_peak_mm,
                        c.contact_blob_min_peak_rel_frac, hd->kept, B, P, st);
 
     // ---- force tail (multimodal_sensor.py:388-419) + arg-extrema

@@ -17,48 +17,10 @@
 
 namespace vf {
 
-constexpr int DFT_RB = 12;   // row groups per workgroup in stage 1 (12 * 21 = 252 threads)
-constexpr int DFT_RR = 4;    // rows per thread in stage 1: every twiddle loaded feeds DFT_RR rows
-
 __device__ inline void cmac(double &ar, double &ai, double er, double ei, double vr, double vi)
 {
     ar = fma(er, vr, ar); ar = fma(-ei, vi, ar);
     ai = fma(er, vi, ai); ai = fma(ei, vr, ai);
-}
-
-// stage 1: T[b, y, c] = sum_x (iw[b,y,x] - mu[b]) * Ex[x, c].  Thread = (row group, c); the rows of the block are staged in LDS.
-__global__ __launch_bounds__(256) void k_dft_fwd1(const float *__restrict__ iw, const float *__restrict__ mu,
-                                                  const double2 *__restrict__ Ex_all, size_t ex_stride, double2 *__restrict__ T, int h, int w,
-                                                  int pw, int rb)
-{
-    extern __shared__ float rows[];   // rb * DFT_RR * w
-    size_t b = blockIdx.y;
-    const double2 *Ex = Ex_all + b * ex_stride;
-    int y0 = blockIdx.x * rb * DFT_RR;
-    int nr = min(rb * DFT_RR, h - y0);
-    const float *src = iw + b * (size_t)h * w + (size_t)y0 * w;
-    float m = mu ? mu[b] : 0.f;
-    for (int i = threadIdx.x; i < nr * w; i += blockDim.x) rows[i] = __fsub_rn(src[i], m);
-    for (int i = nr * w + threadIdx.x; i < rb * DFT_RR * w; i += blockDim.x) rows[i] = 0.f;
-    __syncthreads();
-    int rg = threadIdx.x / pw, c = threadIdx.x % pw;
-    if (rg >= rb || rg * DFT_RR >= nr) return;
-    const float *r = rows + rg * DFT_RR * w;
-    double ar[DFT_RR], ai[DFT_RR];
-#pragma unroll
-    for (int k = 0; k < DFT_RR; k++) { ar[k] = 0.0; ai[k] = 0.0; }
-    for (int x = 0; x < w; x++) {
-        const double2 e = Ex[(size_t)x * pw + c];
-#pragma unroll
-        for (int k = 0; k < DFT_RR; k++) {
-            const double v = r[k * w + x];
-            ar[k] = fma(v, e.x, ar[k]);
-            ai[k] = fma(v, e.y, ai[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < DFT_RR; k++)
-        if (rg * DFT_RR + k < nr) T[(b * (size_t)h + y0 + rg * DFT_RR + k) * pw + c] = make_double2(ar[k], ai[k]);
 }
 
 // stage 1 as a float64 GEMM on the matrix cores: C[row = (b, y)][n] = sum_x V[row][x] * E[x][n], n = 0..2*pw-1 (real parts of the pw bins,
@@ -66,18 +28,25 @@ __global__ __launch_bounds__(256) void k_dft_fwd1(const float *__restrict__ iw, 
 // D[row = (lane >> 4) + 4 * reg][col = lane & 15].  One wave owns a strip of 16 image rows and all column tiles (<= DFT_MAXT at a time);
 // operands come straight from global memory / L2 (the table is 2 * pw * w doubles), one element per lane and k-step.  This is the only dense
 // contraction of the path; float64 keeps the accumulation the parity of the demodulated field relies on.
+// The rows form nseg segments of seg_rows rows, each with its own table (Ex_all + seg * ex_stride): one segment of B * h rows for a shared
+// table, one per frame for per-frame tables (pair mode).  Strips start at each segment's first row, so a strip never mixes two tables, at
+// any h.  An output row depends only on its own input row and the table (the same k-steps in the same order), not on the strip it sits
+// in: a pair sample gives the bits of a session built on its reference.
 typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int DFT_MAXT = 4;            // column tiles (16 columns each) accumulated per pass over x
 __global__ __launch_bounds__(256) void k_dft_fwd1_mfma(const float *__restrict__ iw, const float *__restrict__ mu, const double2 *__restrict__ Ex_all,
-                                                       size_t ex_stride, double2 *__restrict__ T, int h, int w, int pw, int rows_total)
+                                                       size_t ex_stride, double2 *__restrict__ T, int h, int w, int pw, int seg_rows, int nseg)
 {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const int row0 = (blockIdx.x * 4 + wid) * 16;
-    if (row0 >= rows_total) return;
+    const int sps = (seg_rows + 15) / 16;                       // strips per segment
+    const int strip = blockIdx.x * 4 + wid;
+    if (strip >= nseg * sps) return;
+    const int seg = strip / sps;
+    const int row0 = seg * seg_rows + (strip - seg * sps) * 16;
+    const int row_end = (seg + 1) * seg_rows;                   // one past the segment's last row
     const int r = lane & 15, kk = lane >> 4;
-    const int grow = min(row0 + r, rows_total - 1);            // rows past the end repeat the last one (never stored)
-    const size_t b = (size_t)(row0 / h);                       // a strip never straddles frames in the table choice: h % 16 == 0 is required
-    const double *E = (const double *)(Ex_all + b * ex_stride);
+    const int grow = min(row0 + r, row_end - 1);                // rows past the segment repeat its last one (never stored)
+    const double *E = (const double *)(Ex_all + (size_t)seg * ex_stride);
     const float *src = iw + (size_t)grow * w;
     const float m = mu ? mu[grow / h] : 0.f;
     const int ncol = 2 * pw, ntile = (ncol + 15) / 16;
@@ -108,7 +77,7 @@ __global__ __launch_bounds__(256) void k_dft_fwd1_mfma(const float *__restrict__
 #pragma unroll
             for (int q = 0; q < 4; q++) {
                 const int row = row0 + kk + 4 * q;
-                if (row < rows_total) ((double *)(T + (size_t)row * pw + c))[n < pw ? 0 : 1] = acc[t][q];
+                if (row < row_end) ((double *)(T + (size_t)row * pw + c))[n < pw ? 0 : 1] = acc[t][q];
             }
         }
     }
@@ -148,18 +117,10 @@ void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, con
                         const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st,
                         int win_stride)
 {
-    int rb = 256 / pw;
-    if (rb > DFT_RB) rb = DFT_RB;
-    const int rb_lds = (int)((60 * 1024) / ((size_t)DFT_RR * w * sizeof(float)));     // staged rows must fit the default dynamic LDS limit
-    if (rb > rb_lds) rb = rb_lds;
-    if (rb < 1) rb = 1;
-    if (h % 16 == 0 || tab_stride_x == 0) {      // matrix-core form: a strip of 16 rows must use ONE table (shared, or inside one frame)
-        const int rows = B * h;
-        hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3(((rows + 15) / 16 + 3) / 4), dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, rows);
-    } else {
-        dim3 g1((h + rb * DFT_RR - 1) / (rb * DFT_RR), B);
-        hipLaunchKernelGGL(k_dft_fwd1, g1, dim3(256), (size_t)rb * DFT_RR * w * sizeof(float), st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, rb);
-    }
+    // per-frame tables (tab_stride_x != 0): one segment per frame; a shared table: the whole batch is one segment
+    const int seg_rows = tab_stride_x ? h : B * h, nseg = tab_stride_x ? B : 1;
+    const int strips = nseg * ((seg_rows + 15) / 16);
+    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3((strips + 3) / 4), dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
     hipLaunchKernelGGL(k_dft_fwd2, dim3(B), dim3(std::min(1024, ((ph * pw + 63) / 64) * 64)), 0, st, (const double2 *)tmpT, Ey, tab_stride_y, win, win_stride, patch, h,
                        ph, pw, patch_stride);
 }
@@ -319,7 +280,7 @@ void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_hal
                          double *mag, int B, int h, int w, int Hf, int Wf, hipStream_t st)
 {
     const int Wh = Wf / 2 + 1, rows = B * h;
-    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3(((rows + 15) / 16 + 3) / 4), dim3(256), 0, st, iw, mu, Ex_half, (size_t)0, tmp, h, w, Wh, rows);
+    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3(((rows + 15) / 16 + 3) / 4), dim3(256), 0, st, iw, mu, Ex_half, (size_t)0, tmp, h, w, Wh, rows, 1);
     hipLaunchKernelGGL(k_full2_mfma, dim3((Wh + 63) / 64, (Hf + 63) / 64, B), dim3(256), 0, st, (const double2 *)tmp, Ey_full, mag, h, Hf, Wf, Wh);
 }
 

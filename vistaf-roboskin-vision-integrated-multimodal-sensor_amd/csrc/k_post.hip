@@ -26,7 +26,7 @@ __global__ void k_contact_count(const float *__restrict__ res, const uint8_t *__
 }
 
 __global__ void k_contact_mask(const float *__restrict__ res, const uint8_t *__restrict__ reliable, const float *__restrict__ thr3,
-                               const int *__restrict__ contact_count, const int *__restrict__ rel_count, float min_frac, float max_frac,
+                               const int *__restrict__ contact_count, const int *__restrict__ rel_count, double min_frac, double max_frac,
                                uint8_t *__restrict__ contact, float *__restrict__ thr_used, int P)
 {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -34,9 +34,10 @@ __global__ void k_contact_mask(const float *__restrict__ res, const uint8_t *__r
     float thr = thr3[b * 3];
     if (!finitef(thr)) thr = thr3[b * 3 + 1];
     int rc = rel_count[b];
+    // float64 fraction against the float64 constants, as upstream's NumPy compares them (a bound narrowed to float32 moves the boundary)
     double frac = (double)contact_count[b] / (double)(rc > 1 ? rc : 1);
-    if (frac < (double)min_frac) { float t2 = thr3[b * 3 + 1]; if (finitef(t2)) thr = t2; }
-    else if (frac > (double)max_frac) { float t2 = thr3[b * 3 + 2]; if (finitef(t2)) thr = t2; }
+    if (frac < min_frac) { float t2 = thr3[b * 3 + 1]; if (finitef(t2)) thr = t2; }
+    else if (frac > max_frac) { float t2 = thr3[b * 3 + 2]; if (finitef(t2)) thr = t2; }
     if (p == 0) thr_used[b] = thr;
     if (p >= P) return;
     float v = fabsf(res[b * (size_t)P + p]);
@@ -44,7 +45,7 @@ __global__ void k_contact_mask(const float *__restrict__ res, const uint8_t *__r
 }
 
 void launch_contact_mask(const float *res, const uint8_t *reliable, const float *thr3, const int *rel_count, int *contact_count,
-                         float min_frac, float max_frac, uint8_t *contact, float *thr_used, int B, int P, hipStream_t st)
+                         double min_frac, double max_frac, uint8_t *contact, float *thr_used, int B, int P, hipStream_t st)
 {
     hipMemsetAsync(contact_count, 0, sizeof(int) * B, st);
     int gx = (P + 256 * 16 - 1) / (256 * 16);
@@ -236,7 +237,7 @@ __global__ void k_blob_peaks(const float *__restrict__ depth, const int32_t *__r
     }
 }
 __global__ void k_blob_apply(float *__restrict__ depth, const uint8_t *__restrict__ cand, const int32_t *__restrict__ labels,
-                             const unsigned int *__restrict__ peak_bits, const unsigned int *__restrict__ gmax_bits, float min_peak_mm,
+                             const unsigned int *__restrict__ peak_bits, const unsigned int *__restrict__ gmax_bits, double min_peak_mm,
                              double rel_frac, uint8_t *__restrict__ kept, int P)
 {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -245,17 +246,19 @@ __global__ void k_blob_apply(float *__restrict__ depth, const uint8_t *__restric
     size_t i = b * (size_t)P + p;
     bool k = false;
     if (cand[i]) {
+        // the threshold is formed in float64 (Python floats, :1247-1250); `peaks >= thr` then compares a float32 array with a Python
+        // float, which NumPy 2 rounds to float32 first: the comparison is float32 against float32(thr)
         double gmax = (double)__uint_as_float(gmax_bits[b]);
-        double thr = (double)min_peak_mm;
+        double thr = min_peak_mm;
         if (rel_frac >= 0.0) thr = fmax(thr, rel_frac * gmax);
-        double peak = (double)__uint_as_float(peak_bits[b * (size_t)P + labels[i]]);
-        k = peak >= thr;
+        float peak = __uint_as_float(peak_bits[b * (size_t)P + labels[i]]);
+        k = peak >= (float)thr;
         if (!k) depth[i] = 0.f;
     }
     if (kept) kept[i] = (uint8_t)k;
 }
 void launch_blob_filter(float *depth, const uint8_t *cand, const int32_t *labels, unsigned int *peak_bits,
-                        const unsigned int *gmax_bits, float min_peak_mm, double rel_frac, uint8_t *kept, int B, int P,
+                        const unsigned int *gmax_bits, double min_peak_mm, double rel_frac, uint8_t *kept, int B, int P,
                         hipStream_t st)
 {
     hipMemsetAsync(peak_bits, 0, sizeof(unsigned int) * (size_t)B * P, st);

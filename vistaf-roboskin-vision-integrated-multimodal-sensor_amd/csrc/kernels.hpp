@@ -166,7 +166,7 @@ struct PostParams {
     double grating_pitch_mm = 0.0;
 };
 void launch_contact_mask(const float *res, const uint8_t *reliable, const float *thr3, const int *rel_count, int *contact_count,
-                         float min_frac, float max_frac, uint8_t *contact, float *thr_used, int B, int P, hipStream_t st);
+                         double min_frac, double max_frac, uint8_t *contact, float *thr_used, int B, int P, hipStream_t st);
 void launch_background(const uint8_t *reliable, const uint8_t *contact_d, const int *rel_count, int *bg_count, uint8_t *background,
                        int B, int P, hipStream_t st);
 void launch_sub_scalar_mask(const float *src, const float *scalar, const uint8_t *mask, float *z0, float *m_out, int B, int P,
@@ -181,7 +181,7 @@ void launch_finalize_unitless(const float *hfinal_z0, const float *smooth_num, c
 void launch_to_mm(const float *unitless, const uint8_t *roi, Curve curve, int use_neg, float *depth, uint8_t *cand,
                   unsigned int *gmax_bits, int B, int P, hipStream_t st);
 void launch_blob_filter(float *depth, const uint8_t *cand, const int32_t *labels, unsigned int *peak_bits,
-                        const unsigned int *gmax_bits, float min_peak_mm, double rel_frac, uint8_t *kept, int B, int P,
+                        const unsigned int *gmax_bits, double min_peak_mm, double rel_frac, uint8_t *kept, int B, int P,
                         hipStream_t st);
 void launch_tail(const float *height_mm, const uint8_t *roi_or_null, const float *unitless_or_null, const uint8_t *roi_static,
                  PostParams pp, double *scalars, int nscal, double *out3_or_null, int B, int P, hipStream_t st, void *scratch = nullptr,
