@@ -46,10 +46,15 @@ typedef struct vistaf_align_config {
 #define VISTAF_AI_RHO 9           /* ECC correlation coefficient (NaN when ECC failed: cv2.error upstream, :576-578) */
 #define VISTAF_AI_ECC_ITERS 10    /* iterations executed */
 #define VISTAF_AI_ECC_FAILED 11   /* 1: lambda_d <= 0 or NaN rho -> the unaligned crop is returned, as upstream does */
+/* With use_ecc = 0 the record holds the shift and response, the identity warp, rho = -1, iters = 0 and failed = 0, and the output
+ * crop is the (shifted) grey crop itself.  A failed frame's iters counts the failing iteration. */
 
 void vistaf_align_default_config(vistaf_align_config *cfg);
 
-/* full-frame size H x W, fixed ROI circle (centre cx, cy and radius r in full-frame pixels: circle_from_3_points, :1499) */
+/* full-frame size H x W, fixed ROI circle (centre cx, cy and radius r in full-frame pixels: circle_from_3_points, :1499).
+ * Refused with VISTAF_E_INVALID: H or W < 16; r < 4; max_batch < 1; shift_blur_sigma <= 0 or NaN; ecc_iters < 1; a clipped crop box
+ * [max(0, cx-r), min(W, cx+r)) x [max(0, cy-r), min(H, cy+r)) under 8 px in either direction; a Gaussian (shift_blur_sigma, or
+ * ecc_gauss_sigma when > 0) of more than 511 taps (ksize = round(8 sigma + 1) | 1).  ecc_gauss_sigma <= 0 skips the ECC blur. */
 int vistaf_align_create(const vistaf_align_config *cfg, int H, int W, int cx, int cy, int r, int max_batch, vistaf_align_handle **out);
 void vistaf_align_destroy(vistaf_align_handle *h);
 
@@ -61,7 +66,7 @@ int vistaf_align_geometry(const vistaf_align_handle *h, int32_t *x1, int32_t *y1
  * d_ref_gray_crop (optional, [crop_h, crop_w] uint8) receives the reference crop for vistaf_ftp_set_reference. */
 int vistaf_align_set_reference(vistaf_align_handle *h, const uint8_t *d_ref_bgr, uint8_t *d_ref_gray_crop, void *stream);
 
-/* B deformed photographs [B,H,W,3] uint8 BGR -> aligned grey ROI crops [B,crop_h,crop_w] uint8 (input of
+/* B (1 <= B <= max_batch, else VISTAF_E_STATE) deformed photographs [B,H,W,3] uint8 BGR -> aligned grey ROI crops [B,crop_h,crop_w] uint8 (input of
  * vistaf_ftp_predict_batch with VISTAF_FMT_GRAY_U8) and the [B, VISTAF_ALIGN_NINFO] records.  Synchronises the stream
  * (the ECC iteration count is data dependent). */
 int vistaf_align_batch(vistaf_align_handle *h, const uint8_t *d_def_bgr, int B, uint8_t *d_def_gray_aligned, double *d_info, void *stream);

@@ -74,7 +74,8 @@ def _optimal_dft_size(n: int) -> int:
         m += 1
 
 
-def phase_correlate(a: np.ndarray, b: np.ndarray, window: Optional[np.ndarray]) -> Tuple[Tuple[float, float], float]:
+def correlation_surface(a: np.ndarray, b: np.ndarray, window: Optional[np.ndarray]) -> np.ndarray:
+    """the fftshifted [M, N] float32 phase-correlation surface cv2.phaseCorrelate takes its arg-max and centroid from"""
     h, w = a.shape
     M, N = _optimal_dft_size(h), _optimal_dft_size(w)
     pa = np.zeros((M, N), np.float32)
@@ -91,7 +92,17 @@ def phase_correlate(a: np.ndarray, b: np.ndarray, window: Optional[np.ndarray]) 
     p = f1 * np.conj(f2)
     mag = np.abs(p)
     c = np.where(mag > 0, p / np.maximum(mag, np.finfo(np.float32).tiny), 0)
-    corr = np.fft.fftshift(np.real(np.fft.ifft2(c))).astype(np.float32) * np.float32(M * N)   # cv::idft without DFT_SCALE
+    return np.fft.fftshift(np.real(np.fft.ifft2(c))).astype(np.float32) * np.float32(M * N)   # cv::idft without DFT_SCALE
+
+
+def phase_correlate(a: np.ndarray, b: np.ndarray, window: Optional[np.ndarray]) -> Tuple[Tuple[float, float], float]:
+    return peak_centroid(correlation_surface(a, b, window))
+
+
+def peak_centroid(corr: np.ndarray) -> Tuple[Tuple[float, float], float]:
+    """cv2.phaseCorrelate's last steps on the fftshifted surface: first arg-max, 5x5 weighted centroid clamped to the plane
+    (weightedCentroid), shift = centre - centroid, response = window sum / (M N)"""
+    M, N = corr.shape
     py, px = np.unravel_index(int(np.argmax(corr)), corr.shape)
     y0, y1 = max(0, py - 2), min(M - 1, py + 2)
     x0, x1 = max(0, px - 2), min(N - 1, px + 2)
@@ -105,10 +116,10 @@ def phase_correlate(a: np.ndarray, b: np.ndarray, window: Optional[np.ndarray]) 
     return (N / 2.0 - cx, M / 2.0 - cy), response
 
 
-def estimate_global_shift(ref_gray_f32: np.ndarray, def_gray_f32: np.ndarray):
-    """shape_ftp.py:529-535."""
-    rb = cvlite.gaussian_blur(ref_gray_f32, 7.0)
-    db = cvlite.gaussian_blur(def_gray_f32, 7.0)
+def estimate_global_shift(ref_gray_f32: np.ndarray, def_gray_f32: np.ndarray, sigma: float = 7.0):
+    """shape_ftp.py:529-535 (`sigma`: the GaussianBlur sigma, 7 upstream)."""
+    rb = cvlite.gaussian_blur(ref_gray_f32, float(sigma))
+    db = cvlite.gaussian_blur(def_gray_f32, float(sigma))
     h, w = rb.shape
     return phase_correlate(rb, db, hanning_window(h, w))
 
@@ -219,9 +230,17 @@ def _filter_dx(img: np.ndarray, axis: int) -> np.ndarray:
     return (np.float32(0.5) * p[2:, 1:-1] - np.float32(0.5) * p[:-2, 1:-1]).astype(np.float32)
 
 
+class EccError(RuntimeError):
+    """cv2.error raised inside findTransformECC; `iters`: the iterations started, the failing one included."""
+
+    def __init__(self, msg: str, iters: int):
+        super().__init__(msg)
+        self.iters = int(iters)
+
+
 def find_transform_ecc_euclidean(template: np.ndarray, image: np.ndarray, mask_u8: Optional[np.ndarray], iters: int, eps: float):
     """cv2.findTransformECC(template, image, eye(2,3), MOTION_EUCLIDEAN, (EPS|COUNT, iters, eps), inputMask, gaussFiltSize=1).
-    Returns (rho, warp float32 2x3)."""
+    Returns (rho, warp float32 2x3, iterations executed); raises EccError where OpenCV raises cv2.error."""
     hs, ws = template.shape
     tpl = template.astype(np.float32)
     img = image.astype(np.float32)
@@ -258,19 +277,25 @@ def find_transform_ecc_euclidean(template: np.ndarray, image: np.ndarray, mask_u
         J = [j0, gxw, gyw]
         hess = np.array([[float(np.dot(J[a].ravel().astype(np.float64), J[b].ravel().astype(np.float64))) for b in range(3)] for a in range(3)],
                         np.float32)
-        hinv = np.linalg.inv(hess.astype(np.float64)).astype(np.float32)
+        try:
+            hinv = np.linalg.inv(hess.astype(np.float64)).astype(np.float32)
+        except np.linalg.LinAlgError:
+            # hessian.inv() is cv::invert(DECOMP_LU): a singular matrix gives a zero inverse, not an error; the NaN rho below
+            # (a frame without gradients has no variance either) is what raises upstream
+            hinv = np.zeros((3, 3), np.float32)
         corr = float(np.dot(tz.ravel().astype(np.float64), iwz.ravel().astype(np.float64)))
         last_rho = rho
-        rho = corr / (img_norm * tmp_norm)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            rho = float(np.float64(corr) / np.float64(img_norm * tmp_norm))       # 0/0 is NaN, as in C++
         if not np.isfinite(rho):
-            raise RuntimeError("ECC: NaN correlation")
+            raise EccError("ECC: NaN correlation", it)
         proj = lambda v: np.array([float(np.dot(J[a].ravel().astype(np.float64), v.ravel().astype(np.float64))) for a in range(3)], np.float32)
         ip, tp = proj(iwz), proj(tz)
         iph = (hinv @ ip).astype(np.float32)
         lam_n = img_norm * img_norm - float(np.dot(ip.astype(np.float64), iph.astype(np.float64)))
         lam_d = corr - float(np.dot(tp.astype(np.float64), iph.astype(np.float64)))
         if lam_d <= 0.0:
-            raise RuntimeError("ECC stopped before convergence (lambda_d <= 0)")
+            raise EccError("ECC stopped before convergence (lambda_d <= 0)", it)
         lam = lam_n / lam_d
         err = (np.float32(lam) * tz - iwz).astype(np.float32)
         dp = (hinv @ proj(err)).astype(np.float32)
@@ -284,7 +309,7 @@ def find_transform_ecc_euclidean(template: np.ndarray, image: np.ndarray, mask_u
 
 
 def align_crop_ecc(ref_u8: np.ndarray, mov_u8: np.ndarray, mask_bool: Optional[np.ndarray], iters=300, eps=1e-7, gauss_filt=5):
-    """shape_ftp.py:549-578 (mode "euclidean")."""
+    """shape_ftp.py:549-578 (mode "euclidean").  Returns (aligned u8, warp, rho, iterations executed); rho is NaN when ECC failed."""
     ref = ref_u8.astype(np.float32) / np.float32(255.0)
     mov = mov_u8.astype(np.float32) / np.float32(255.0)
     if gauss_filt and gauss_filt > 0:
@@ -293,34 +318,50 @@ def align_crop_ecc(ref_u8: np.ndarray, mov_u8: np.ndarray, mask_bool: Optional[n
     m = None if mask_bool is None else (mask_bool.astype(np.uint8) * 255)
     try:
         rho, warp, n_it = find_transform_ecc_euclidean(ref, mov, m, int(iters), float(eps))
-    except RuntimeError:
+    except EccError as e:
         # cv2.error in the reference: the unaligned crop and the identity warp are used (shape_ftp.py:576-578)
-        return mov_u8, np.eye(2, 3, dtype=np.float32), float("nan"), 0
+        return mov_u8, np.eye(2, 3, dtype=np.float32), float("nan"), e.iters
     aligned = warp_affine(mov_u8, warp, True, border="reflect")
     return aligned, warp, float(rho), n_it
+
+
+def crop_geometry(H: int, W: int, circle):
+    """shape_ftp.py:1500-1519: crop box (x1, x2, y1, y2) of the ROI circle clipped to the H x W frame, and the circle (cx, cy, r) in the crop."""
+    cx, cy, r = (int(v) for v in circle)
+    x1, x2, y1, y2 = max(0, cx - r), min(W, cx + r), max(0, cy - r), min(H, cy + r)
+    cxl, cyl = cx - x1, cy - y1
+    rl = int(min(r, cxl, cyl, (x2 - x1) - 1 - cxl, (y2 - y1) - 1 - cyl))
+    return (x1, x2, y1, y2), (cxl, cyl, rl)
+
+
+def aligned_crops_arrays(ref_bgr: np.ndarray, def_bgr: np.ndarray, circle, apply_global_shift=True, use_ecc=True,
+                         ecc_iters=300, ecc_eps=1e-7, ecc_gauss=5, gray_generation: int = 4, shift_blur_sigma: float = 7.0):
+    """shape_ftp.main :1481-1537 on decoded [H, W, 3] uint8 BGR frames and the full-frame ROI circle (cx, cy, r).
+    Returns (ref_gray crop u8, aligned deformed gray crop u8, (cx, cy, r) local, info).  info: shift, response, crop, warp, rho,
+    ecc_iters, ecc_failed; with ECC off the identity warp, rho -1 and 0 iterations (the record vistaf_align_batch writes)."""
+    H, W = ref_bgr.shape[:2]
+    shift, response = estimate_global_shift(bgr2gray_u8(ref_bgr, gray_generation).astype(np.float32), bgr2gray_u8(def_bgr, gray_generation).astype(np.float32),
+                                            shift_blur_sigma)
+    if apply_global_shift:
+        M = np.array([[1, 0, shift[0]], [0, 1, shift[1]]], np.float32)
+        def_bgr = warp_affine(def_bgr, M, False, border="reflect")
+    (x1, x2, y1, y2), (cxl, cyl, rl) = crop_geometry(H, W, circle)
+    ref_gray = bgr2gray_u8(ref_bgr[y1:y2, x1:x2], gray_generation)
+    def_gray = bgr2gray_u8(def_bgr[y1:y2, x1:x2], gray_generation)
+    h, w = ref_gray.shape
+    info = {"shift": shift, "response": response, "crop": (x1, x2, y1, y2), "warp": np.eye(2, 3, dtype=np.float32), "rho": -1.0, "ecc_iters": 0,
+            "ecc_failed": False}
+    if use_ecc:
+        from . import ftp_oracle as O
+        circ = O.circular_mask(h, w, cxl, cyl, rl)
+        def_gray, warp, rho, n_it = align_crop_ecc(ref_gray, def_gray, circ, ecc_iters, ecc_eps, ecc_gauss)
+        info.update(warp=warp, rho=rho, ecc_iters=n_it, ecc_failed=not np.isfinite(rho))
+    return ref_gray, def_gray, (cxl, cyl, rl), info
 
 
 def aligned_crops(reference_path: str, deformed_path: str, circle_pts, apply_global_shift=True, use_ecc=True,
                   ecc_iters=300, ecc_eps=1e-7, ecc_gauss=5, gray_generation: int = 4):
     """shape_ftp.main :1471-1537: returns (ref_gray crop u8, aligned deformed gray crop u8, (cx, cy, r) local, info)."""
     from . import ftp_oracle as O
-    ref_bgr = imread_bgr(reference_path)
-    def_bgr = imread_bgr(deformed_path)
-    H, W = ref_bgr.shape[:2]
-    shift, response = estimate_global_shift(bgr2gray_u8(ref_bgr, gray_generation).astype(np.float32), bgr2gray_u8(def_bgr, gray_generation).astype(np.float32))
-    if apply_global_shift:
-        M = np.array([[1, 0, shift[0]], [0, 1, shift[1]]], np.float32)
-        def_bgr = warp_affine(def_bgr, M, False, border="reflect")
-    cx, cy, r = O.circle_from_3_points(*circle_pts)
-    x1, x2, y1, y2 = max(0, cx - r), min(W, cx + r), max(0, cy - r), min(H, cy + r)
-    ref_gray = bgr2gray_u8(ref_bgr[y1:y2, x1:x2], gray_generation)
-    def_gray = bgr2gray_u8(def_bgr[y1:y2, x1:x2], gray_generation)
-    h, w = ref_gray.shape
-    cxl, cyl = cx - x1, cy - y1
-    rl = int(min(r, cxl, cyl, w - 1 - cxl, h - 1 - cyl))
-    info = {"shift": shift, "response": response, "crop": (x1, x2, y1, y2)}
-    if use_ecc:
-        circ = O.circular_mask(h, w, cxl, cyl, rl)
-        def_gray, warp, rho, n_it = align_crop_ecc(ref_gray, def_gray, circ, ecc_iters, ecc_eps, ecc_gauss)
-        info.update(warp=warp, rho=rho, ecc_iters=n_it)
-    return ref_gray, def_gray, (cxl, cyl, rl), info
+    return aligned_crops_arrays(imread_bgr(reference_path), imread_bgr(deformed_path), O.circle_from_3_points(*circle_pts), apply_global_shift,
+                                use_ecc, ecc_iters, ecc_eps, ecc_gauss, gray_generation)
