@@ -7,8 +7,8 @@
  *                              with its helpers _make_saturation_mask (:378-387), _illum_normalize (:363-375), _find_top_peaks (:316-337),
  *                              _choose_carrier_peak (:339-360) and _postprocess_mask (:390-406)
  *
- * The temperature regressors themselves (TempModel.predict, :236) are NOT here: their parameters only exist as pickled scikit-learn
- * pipelines (.joblib).  All image pointers are HIP device pointers; `stream` is a hipStream_t passed as void*.  Every function returns 0
+ * The temperature regressors themselves (TempModel.predict, :236) are in include/vistaf_tempmodel.h, evaluated from exported parameters.
+ * All image pointers are HIP device pointers; `stream` is a hipStream_t passed as void*.  Every function returns 0
  * or a negative VISTAF_E_* code (vistaf_ftp.h); vistaf_ftp_last_error() holds the message.  The full-frame spectrum of the carrier search
  * is a plain library transform (hipFFT, float32: only the POSITION of the strongest peaks is read from it); the band-pass around the chosen
  * carrier is the library's own pruned float64 DFT on the matrix cores, everything else hand-written HIP.

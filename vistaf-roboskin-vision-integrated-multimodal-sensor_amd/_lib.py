@@ -31,6 +31,7 @@ TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vista
                 "vistaf_temp_feature_planes", "vistaf_temp_color_support",
                 "vistaf_temp_clamp_map", "vistaf_temp_inpaint_map", "vistaf_temp_fuse_maps", "vistaf_temp_oriented_blur"]   # include/vistaf_temp.h
 TEMPSEG_NINFO = 16
+TEMPMODEL_EXPORTS = ["vistaf_tmodel_create", "vistaf_tmodel_destroy", "vistaf_tmodel_predict_maps", "vistaf_tmodel_predict_rows"]   # include/vistaf_tempmodel.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -117,7 +118,14 @@ def load():
     lib.vistaf_temp_inpaint_map.argtypes = [vp, vp, vp, ci, vp, vp]
     lib.vistaf_temp_fuse_maps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(CTempFuseConfig), vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
     lib.vistaf_temp_oriented_blur.argtypes = [vp, vp, vp, cd, cd, cd, vp, vp]
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS:
+    i32p, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(cd)
+    lib.vistaf_tmodel_create.argtypes = [ci, i32p, dp, dp, ci, ci, ci, i32p, dp, cd, ci, dp, dp, cd, cd, ci, ctypes.POINTER(vp)]
+    lib.vistaf_tmodel_destroy.argtypes = [vp]
+    lib.vistaf_tmodel_destroy.restype = None
+    lib.vistaf_tmodel_predict_maps.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int64,
+                                               ctypes.c_int64, vp]
+    lib.vistaf_tmodel_predict_rows.argtypes = [vp, vp, ci, ctypes.c_int64, vp, vp]
+    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS:
         getattr(lib, fn)
     _lib = lib
     return lib

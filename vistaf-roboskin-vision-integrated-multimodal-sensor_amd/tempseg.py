@@ -6,7 +6,7 @@ Reference interface mirrored: Code/temperature_sensor.py
   * `compute_feature_planes(image_bgr, blur_ksize) -> {"L", "a", "b", "gray"}`                            (:278-293)
   * the chroma / colour-support test of `main()` (with `dilate_bool_mask`, :583-590)                       (:793-799)
 backed by `vistaf_tempseg_*` of libvistaf_ftp.so (include/vistaf_temp.h).  PyTorch only holds the device buffers.  The temperature
-regressors (`TempModel.predict`, :236) are not part of this slice: their parameters only exist as pickled scikit-learn pipelines.
+regressors (`TempModel.predict`, :236) are in tempmodel.py, evaluated from exported parameters.
 """
 from __future__ import annotations
 
