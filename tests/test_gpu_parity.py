@@ -201,11 +201,11 @@ def test_unwrap_with_true_wraps_and_parent_tree(pkg, cal):
     assert saw_wrap
 
 
-def test_big_frame_flood_reproduces_the_heap_order(pkg, cal):
+def test_big_frame_flood_and_its_handback_reproduce_the_heap_order(pkg, cal):
     """Frames beyond the uint16 rank range (here 320 x 320 = 103 684 padded pixels; the native crops have 1.4 M) take the bitmap flood of
     k_unwrap_big.hip: 32-bit ranks, priority queue as a three-level bitmap in LDS, plane in global memory, up to 8 pops per step.
     Deformations of several 2*pi; the parent of every pixel must equal the reference heap's, bit for bit, and the generic one-pop
-    kernel (test hook flood_tier = 0) must give the same tree."""
+    kernel (test hook big_flood_handback = 1: the bitmap flood hands every frame to it) must give the same tree."""
     n, nb = 320, 2
     cfg = pkg.FtpConfig.scaled(n)
     ref, sensor = _sensor(pkg, cal, n, cfg, nb, config=5)
@@ -244,12 +244,11 @@ def test_big_frame_flood_reproduces_the_heap_order(pkg, cal):
         assert np.array_equal(par_all[b * P:(b + 1) * P].reshape(n, n), par_o), b
         _check_frame(out, b, o, n)
     assert saw_wrap
-    for tier in (0, 3):       # 0: generic kernel only; 3: bitmap flood hands every frame back (the path of masks larger than its bitmap)
-        sensor._test_set("flood_tier", tier)
-        sensor.predict_batch(frames)
-        torch.cuda.synchronize()
-        assert np.array_equal(sensor.intermediate("parent", nb, torch.int32).cpu().numpy(), par_all), tier
-        assert np.array_equal(sensor.intermediate("unwrapped", nb).cpu().numpy(), uw_all, equal_nan=True), tier
+    sensor._test_set("big_flood_handback", 1)      # the bitmap flood hands every frame back (the path of masks larger than its bitmap)
+    sensor.predict_batch(frames)
+    torch.cuda.synchronize()
+    assert np.array_equal(sensor.intermediate("parent", nb, torch.int32).cpu().numpy(), par_all)
+    assert np.array_equal(sensor.intermediate("unwrapped", nb).cpu().numpy(), uw_all, equal_nan=True)
 
 
 def test_input_formats_agree(pkg, cal):
@@ -424,34 +423,26 @@ def test_non_square_odd_sizes(pkg, cal):
 
 
 
-@pytest.mark.parametrize("var,val", [("inpaint_tier", 1), ("inpaint_tier", 0), ("flood_tier", 1), ("flood_tier", 0), ("chamfer_twopass", 1), ("unwrap_fast", 0)])
+@pytest.mark.parametrize("var,val", [("inpaint_tier", 1), ("inpaint_tier", 0), ("chamfer_twopass", 1), ("unwrap_fast", 0)])
 def test_alternative_kernel_tiers_agree(pkg, cal, var, val):
-    """The fallback / opt-in kernels (whole-frame and cluster-parallel Telea, one-pop and scan floods, two-pass chamfer) stay
+    """The fallback / opt-in kernels (whole-frame and cluster-parallel Telea, two-pass chamfer, the flood behind the consistency check) stay
     parity-green: same frames through the default path and through the alternative, compared with each other and with the oracle."""
     n, nb = 224, 6
     cfg = pkg.FtpConfig.scaled(n)
     ref, sensor = _sensor(pkg, cal, n, cfg, nb, config=3)
     frames = pkg.synth.deformed_batch(n, 40, nb, config=3)
-    if var == "flood_tier":
-        sensor._test_set("unwrap_fast", 0)                                  # the flood tiers are compared tree by tree: every frame through the flood
     base = sensor.predict_batch(frames)
     torch.cuda.synchronize()
     hm0 = base["height_map_mm"].cpu().numpy().copy()
-    par0 = sensor.intermediate("parent", nb, torch.int32).cpu().numpy().copy()
     img0 = sensor.intermediate("img", nb).cpu().numpy().copy()
     sensor._test_set(var, val)                                              # csrc/test_hooks.h: per-session, not an environment switch
     alt = sensor.predict_batch(frames)
     torch.cuda.synchronize()
     hm1 = alt["height_map_mm"].cpu().numpy().copy()
-    par1 = sensor.intermediate("parent", nb, torch.int32).cpu().numpy().copy()
     st = alt["status"].cpu().numpy()
     assert (st == 0).all()
-    if var == "unwrap_fast":
-        assert np.array_equal(hm0, hm1, equal_nan=True)                     # consistency check + parallel integration against the priority flood
-    elif var != "inpaint_tier":
-        if var == "flood_tier":
-            assert np.array_equal(par0, par1)                               # the growth tree is an integer result: identical
-        assert np.array_equal(hm0, hm1, equal_nan=True)
+    if var != "inpaint_tier":
+        assert np.array_equal(hm0, hm1, equal_nan=True)                     # unwrap_fast: consistency check + parallel integration against the priority flood
     else:
         # every Telea tier (frame window, whole frame, cluster by cluster in LDS windows / on the global planes) pops in the queue's order and
         # sums the estimator in OpenCV's order: same inpainted plane, bit for bit, hence the same map

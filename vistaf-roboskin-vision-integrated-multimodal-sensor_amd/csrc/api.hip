@@ -585,16 +585,16 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // ---- unwrap (shape_ftp.py:1702)
     if (timed) hipEventRecord(hd->ev[ST_UNWRAP_RANK], st);
     launch_unwrap(hd->wrapped, qual, hd->reliable, hd->unwrapped, hd->parent, hd->unwrap_scratch, hd->status, B, h, w, st,
-                  timed ? hd->ev[ST_UNWRAP_TREE] : nullptr, timed ? hd->ev[ST_UNWRAP] : nullptr, hd->tiers.flood, hd->tiers.unwrap_fast ? hd->unwrap_need : nullptr);
+                  timed ? hd->ev[ST_UNWRAP_TREE] : nullptr, timed ? hd->ev[ST_UNWRAP] : nullptr, hd->tiers.big_flood_handback != 0, hd->tiers.unwrap_fast ? hd->unwrap_need : nullptr);
 
     // ---- plane removal + two-pass detrend (shape_ftp.py:1706, :1716-1751)
     if (timed) hipEventRecord(hd->ev[ST_DETREND], st);
     if (c.plane_order_for_removal > 0)
         // debug_ramp gates on the reliable count, NaN pixels included (:1364-1366), robust_polyfit2d on 200 finite samples (:1103)
-        launch_robust_polyfit(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, B, h, w, st, hd->tiers.fit_capped, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+        launch_robust_polyfit(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
     else   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, hd->tiers.fit_capped, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
     launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
     launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
                         hd->contact, hd->thr_used, B, P, st);
@@ -617,7 +617,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         }
     }
     launch_background(hd->reliable, hd->contact_d, hd->rel_count, hd->bg_count, hd->background, B, P, st);
-    launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, hd->tiers.fit_capped, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
     launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
 
     // ---- reliable-only smoothing + sign flip (shape_ftp.py:1753-1768)
@@ -828,10 +828,9 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     if (!hd || !name) return fail(VISTAF_E_INVALID, "null argument");
     const std::string n(name);
     if (n == "inpaint_tier" && value >= 0 && value <= 2) hd->tiers.inpaint = value;
-    else if (n == "flood_tier" && value >= 0 && value <= 3) hd->tiers.flood = value;
+    else if (n == "big_flood_handback") hd->tiers.big_flood_handback = value != 0;
     else if (n == "chamfer_twopass") hd->tiers.chamfer_twopass = value != 0;
     else if (n == "telea_two_tier") hd->tiers.telea_two_tier = value != 0;
-    else if (n == "fit_capped") hd->tiers.fit_capped = value != 0;
     else if (n == "telea_mw") hd->tiers.telea_mw = value != 0;
     else if (n == "big_queue_lds") hd->tiers.big_queue_lds = value != 0;
     else if (n == "big_gq_cap" && (value == 0 || (value >= 64 && (value & (value - 1)) == 0))) hd->tiers.big_gq_cap = value;

@@ -558,18 +558,12 @@ void fit_debug_dump()
 #define VF_FIT_PASS z_all, mask_all, order, iters, c, min_count, min_mask_count, coef_out, resid_all, h, w, cols_pad, groups
 template <int RP, int GT>
 __global__ __launch_bounds__(SEL_T) void k_robust_polyfit_col(VF_FIT_ARGS) { robust_polyfit_col_body<RP, SEL_T, GT>(VF_FIT_PASS); }
-// register-capped variant (5 waves per SIMD = 96 VGPRs, the rest of the samples' working set spills to scratch): its workgroup fits on a CU
-// NEXT TO the one-wave march (72 VGPRs, 111 KB of LDS) or flood (64, 109 KB) of another session in flight, where the 128-VGPR workgroup
-// needs every register of the CU and has to wait for the march / flood to drain
-template <int RP, int GT>
-__global__ __launch_bounds__(SEL_T) __attribute__((amdgpu_waves_per_eu(5, 5))) void k_robust_polyfit_col_w5(VF_FIT_ARGS) { robust_polyfit_col_body<RP, SEL_T, GT>(VF_FIT_PASS); }
 #undef VF_FIT_ARGS
 #undef VF_FIT_PASS
 
 // min_count: 200 fitted pixels upstream (:1103); min_mask_count: 500 mask pixels for the debug_ramp call (shape_ftp.py:1364-1366), else 0
-// capped: 1 = prefer the register-capped variant where it exists (RP 56, four row groups), 0 = 128-VGPR variants only
 void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
-                           float *resid_out, int B, int h, int w, hipStream_t st, int capped, void *big_scratch)
+                           float *resid_out, int B, int h, int w, hipStream_t st, void *big_scratch)
 {
     if (big_scratch && big_frames(B, h * w)) {                   // large frames: every sweep over all pixels of the batch (k_big.hip)
         launch_robust_polyfit_big(z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, B, h, w, big_scratch, st);
@@ -583,8 +577,7 @@ void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int i
     const int groups = cols_pad <= NT ? std::min(NT / cols_pad, h) : 0;
     const int need = groups ? (h + groups - 1) / groups : 1 << 30;
     if (need <= 64 && h + groups * 16 <= FIT_YTAB) {
-        if (capped == 1 && groups == 4 && need > 48 && need <= 56) VF_FIT_COL((k_robust_polyfit_col_w5<56, 4>), SEL_T, 4);
-        else if (groups == 4 && need > 32) {
+        if (groups == 4 && need > 32) {
             if (need <= 48) VF_FIT_COL((k_robust_polyfit_col<48, 4>), SEL_T, 4);
             else if (need <= 56) VF_FIT_COL((k_robust_polyfit_col<56, 4>), SEL_T, 4);
             else VF_FIT_COL((k_robust_polyfit_col<64, 4>), SEL_T, 4);

@@ -3,32 +3,33 @@
 // The reference grows a region from the best-quality pixel with a max-heap of tuples
 // (-q, y, x, py, px).  That is Prim-style growth with a total order: the next pixel is the frontier
 // pixel with the largest (q, then smallest (y, x)), and its parent is the lexicographically smallest
-// (py, px) among its neighbours visited so far.  The growth order is inherently sequential, so:
-//   k_unwrap_flood  one wavefront per frame replays exactly that order (frontier keys in LDS, 64-lane
-//                   arg-max per step, the 8 neighbours examined by 8 lanes) and records only the
-//                   spanning tree (parent index per pixel);
-//   k_unwrap_inc / k_unwrap_jump / k_unwrap_apply  (parallel) turn the tree into integer wrap counts
-//                   by pointer jumping (integer sums are associative, so any evaluation order gives
-//                   the tree's exact counts) and write u = w + 2*pi*k.
+// (py, px) among its neighbours visited so far.  The growth order is inherently sequential; launch_unwrap picks the flood by the
+// size of the padded frame, EN = (h+2)*(w+2):
+//   EN <= 65533      uint16 ranks and the batched flood in LDS (k_unwrap_rank.hip, k_unwrap_batch.hip), whose pop log
+//                    k_unwrap_replay turns into wrap counts;
+//   EN < 2^26        32-bit ranks and the bitmap flood (k_unwrap_big.hip); the frames whose mask outgrows its bitmap go to
+//                    k_unwrap_flood, then every frame to k_unwrap_tree;
+//   larger           k_unwrap_flood, then k_unwrap_tree.
+// The last two kernels live here:
+//   k_unwrap_flood  one wavefront per frame replays exactly that order (frontier keys and pixel states in global memory,
+//                   64-lane arg-max per step, the 8 neighbours examined by 8 lanes) and records only the spanning tree
+//                   (parent index per pixel);
+//   k_unwrap_tree   (parallel) turns the tree into integer wrap counts by pointer jumping (integer sums are associative,
+//                   so any evaluation order gives the tree's exact counts) and writes u = w + 2*pi*k.
 // In exact arithmetic u[p] - w[p] is the same multiple of 2*pi as in the reference's
 // u[p] = u[parent] + angle(exp(1j*(w[p]-w[parent]))) chain; only float32 rounding along the chain differs.
 #include "kernels.hpp"
 
 namespace vf {
 
-__device__ inline uint8_t ld_st(const uint8_t *st, int i, bool lds)
-{
-    if (lds) return st[i];
-    return __hip_atomic_load(st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ inline uint8_t ld_st(const uint8_t *st, int i) { return __hip_atomic_load(st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-template <bool LS>
+// fq / fi / st: the frontier keys and indices (cap entries per frame) and the pixel states, in global memory
 __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ quality_all, const uint8_t *__restrict__ mask_all,
                                                      int32_t *__restrict__ parent_all, uint8_t *gst, uint32_t *gfq, uint32_t *gfi,
                                                      int cap, int32_t *status, int h, int w, const int32_t *__restrict__ only, const int32_t *__restrict__ need_frame)
 {
     if (need_frame && !need_frame[blockIdx.x]) return;        // the consistency check settled this frame (k_unwrap_fast.hip)
-    extern __shared__ unsigned char lds_raw[];
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
     if (only && !only[b]) return;                    // big-frame path: only the frames the bitmap flood handed back
@@ -36,10 +37,8 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
     const float *quality = quality_all + b * (size_t)P;
     const uint8_t *mask = mask_all + b * (size_t)P;
     int32_t *parent = parent_all + b * (size_t)P;
-    uint32_t *fq, *fi;
-    uint8_t *st;
-    if (LS) { fq = (uint32_t *)lds_raw; fi = fq + cap; st = (uint8_t *)(fi + cap); }
-    else { fq = gfq + b * (size_t)cap; fi = gfi + b * (size_t)cap; st = gst + b * (size_t)P; }
+    uint32_t *fq = gfq + b * (size_t)cap, *fi = gfi + b * (size_t)cap;
+    uint8_t *st = gst + b * (size_t)P;
 
     // st: 0 untouched, 1 in frontier, 2 visited.  Seed = first arg-max of q over the mask.
     unsigned long long best = 0;
@@ -68,7 +67,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
         if (lane < 8) {
             int l = lane < 4 ? lane : lane + 1;          // skip the centre of the 3x3
             int ny = y + l / 3 - 1, nx = x + l % 3 - 1;
-            if (ny >= 0 && ny < h && nx >= 0 && nx < w) { np = ny * w + nx; s = ld_st(st, np, LS); }
+            if (ny >= 0 && ny < h && nx >= 0 && nx < w) { np = ny * w + nx; s = ld_st(st, np); }
         }
         unsigned long long vis = __ballot(s == 2);
         int par = cur;
@@ -91,7 +90,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
         F += cnt;
         is_seed = false;
         if (F == 0) break;
-        if (!LS) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
 
         // ---- pop the frontier maximum: (q desc, index asc)
         uint32_t bq = 0, bi = 0xffffffffu;
@@ -114,7 +113,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
         int last = F - 1;
         if (lane == 0 && slot != last) { fq[slot] = fq[last]; fi[slot] = fi[last]; }
         F = last;
-        if (!LS) __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     }
     if (overflow && lane == 0) status[b] = 2;
 }
@@ -125,7 +124,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
 // (par, inc) by (par[par], inc + inc[par]) IN PLACE and asynchronously: every word always states a true
 // relation "k[p] = k[par] + inc" (the k are fixed by the tree), and a parent's word is read with one 64-bit
 // load, so any interleaving is consistent; rounds repeat until every pixel points at the seed.
-// ppar_all (optional): parents in PADDED (h+2)x(w+2) index space as written by the ranked flood kernels;
+// ppar_all (optional): parents in PADDED (h+2)x(w+2) index space as written by the bitmap flood (k_unwrap_big.hip);
 // they are converted here and stored to parent_all (the plane the parity tests read back).
 __device__ inline unsigned long long ld_u64c(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline void st_u64c(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -217,9 +216,8 @@ static size_t unwrap_flood_scratch_bytes_per_frame(int h, int w)
 size_t unwrap_scratch_bytes_per_frame(int h, int w) { return unwrap_flood_scratch_bytes_per_frame(h, w) + unwrap_fast_scratch_bytes_per_frame(h, w) + 16; }
 
 bool unwrap_ranked_supported(int h, int w);
-bool launch_unwrap_ranked(const float *quality, const uint8_t *mask, uint32_t *g0, uint32_t *g1, uint32_t *g2, uint32_t *g3,
-                          int32_t *ppar, size_t gstride, uint16_t *rank16, int32_t *seed, int32_t *status, int B, int h, int w,
-                          hipStream_t st, hipEvent_t ev_flood, int flood_tier, const int32_t *need);
+void launch_unwrap_ranked(const float *quality, const uint8_t *mask, uint32_t *g0, uint32_t *g2, int32_t *ppar, size_t gstride, uint16_t *rank16,
+                          int32_t *seed, int B, int h, int w, hipStream_t st, hipEvent_t ev_flood, const int32_t *need);
 void launch_unwrap_replay(const float *wrapped, const uint32_t *order, size_t ostride, const int32_t *ppar, size_t gstride, int32_t *tree,
                           float *unwrapped, int B, int h, int w, hipStream_t st, const int32_t *need);
 bool unwrap_big_supported(int h, int w);
@@ -231,26 +229,19 @@ void launch_unwrap_rank32(const float *quality, const uint8_t *mask, uint32_t *g
 void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t *n, const uint32_t *inv, size_t inv_stride, int32_t *ppar,
                              size_t gstride, int32_t *need_generic, bool force_generic, int B, int h, int w, hipStream_t st, const int32_t *need);
 
-static int unwrap_lds_cap(int P)
-{
-    long avail = 160 * 1024 - (long)((P + 15) & ~15);
-    if (avail < 64 * 1024) return 0;
-    return (int)((avail / 8) & ~63);
-}
-
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
-                   void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid, hipEvent_t ev_flood, int flood_tier, int32_t *need_buf)
+                   void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid, hipEvent_t ev_flood, bool big_handback,
+                   int32_t *need_buf)
 {
     int P = h * w;
     size_t n = (size_t)B * P;
     size_t EN = (size_t)(h + 2) * (w + 2);           // per-frame stride of the uint32 planes
-    // scratch: [B*P st bytes][5 x B*EN u32][B*EN u16 rank codes][B seeds]
+    // scratch: [B*P st bytes][5 x B*EN u32][B*EN rank codes][B seeds, ...]
     uint8_t *gst = (uint8_t *)scratch;
     uint32_t *g0 = (uint32_t *)((uint8_t *)scratch + ((n + 255) & ~(size_t)255));
     size_t gn = (size_t)B * EN;
     uint32_t *g1 = g0 + gn, *g2 = g1 + gn, *g3 = g2 + gn, *g4 = g3 + gn;
-    int cap = unwrap_lds_cap(P);
-    const int32_t *ppar = nullptr;
+    uint8_t *after = (uint8_t *)(((uintptr_t)(g4 + gn) + 255) & ~(uintptr_t)255);
     // First the consistency check (k_unwrap_fast.hip): frames whose wrapped field is path-independent on the seed's component get their
     // plane from a parallel integration, and every kernel of the priority flood below skips them (need[b] = 0).  The parent plane of
     // such a frame is not produced (it is a by-product of the flood; the parity tests that compare trees switch the check off).
@@ -261,47 +252,35 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
         need = need_buf;
     }
     if (unwrap_ranked_supported(h, w)) {
-        uint8_t *after = (uint8_t *)(g4 + gn);
-        after = (uint8_t *)(((uintptr_t)after + 255) & ~(uintptr_t)255);
+        // frames of at most 65533 padded pixels: uint16 ranks, the batched flood in LDS, then the replay of its pop log (g2)
         uint16_t *rank16 = (uint16_t *)after;
         int32_t *seed = (int32_t *)(after + (((gn + 8 * (size_t)B) * 2 + 255) & ~(size_t)255));
-        bool logged = launch_unwrap_ranked(quality, mask, g0, g1, g2, g3, (int32_t *)g4, EN, rank16, seed, status, B, h, w, st, ev_flood, flood_tier, need);
-        ppar = (const int32_t *)g4;
-        if (logged) {
-            if (ev_mid) hipEventRecord(ev_mid, st);
-            launch_unwrap_replay(wrapped, g2, 2 * EN, ppar, EN, parent, unwrapped, B, h, w, st, need);
-            return;
-        }
-    } else if (unwrap_big_supported(h, w) && flood_tier >= 2) {
+        launch_unwrap_ranked(quality, mask, g0, g2, (int32_t *)g4, EN, rank16, seed, B, h, w, st, ev_flood, need);
+        if (ev_mid) hipEventRecord(ev_mid, st);
+        launch_unwrap_replay(wrapped, g2, 2 * EN, (const int32_t *)g4, EN, parent, unwrapped, B, h, w, st, need);
+    } else if (unwrap_big_supported(h, w)) {
         // frames beyond the uint16 rank range (native crops): 32-bit ranks, bitmap priority queue in LDS, plane in global memory
-        // (k_unwrap_big.hip); masks too large for the bitmap go through the generic kernel below, frame by frame
-        uint8_t *after = (uint8_t *)(g4 + gn);
-        after = (uint8_t *)(((uintptr_t)after + 255) & ~(uintptr_t)255);
+        // (k_unwrap_big.hip); masks too large for the bitmap (big_handback: every mask) go through the generic kernel, frame by frame
         uint32_t *rank32 = (uint32_t *)after;
         int32_t *seed = (int32_t *)(after + (((gn + 8 * (size_t)B) * 4 + 255) & ~(size_t)255));
         int32_t *nmask = seed + B, *need_generic = nmask + B;
         launch_unwrap_rank32(quality, mask, g0, g2, EN, rank32, seed, nmask, B, h, w, st, need);
         if (ev_flood) hipEventRecord(ev_flood, st);
-        launch_unwrap_flood_big(rank32, seed, nmask, g0, 2 * EN, (int32_t *)g4, EN, need_generic, flood_tier == 3, B, h, w, st, need);
+        launch_unwrap_flood_big(rank32, seed, nmask, g0, 2 * EN, (int32_t *)g4, EN, need_generic, big_handback, B, h, w, st, need);
         // (the generic kernel's frontier arrays reuse g0 | g1: the sorted indices are dead by now)
-        hipLaunchKernelGGL(k_unwrap_flood<false>, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, need_generic, need);
+        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, need_generic, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
         hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)g4, EN, (unsigned long long *)g0, unwrapped, h, w,
                            need_generic, need);
-        return;
-    } else if (cap > 0) {
-        if (ev_flood) hipEventRecord(ev_flood, st);
-        static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_unwrap_flood<true>, 160 * 1024);
-        size_t lds = (size_t)cap * 8 + ((P + 15) & ~15);
-        hipLaunchKernelGGL(k_unwrap_flood<true>, dim3(B), dim3(64), lds, st, quality, mask, parent, gst, g0, g1, cap, status, h, w, (const int32_t *)nullptr, need);
     } else {
+        // frames of 2^26 padded pixels and more: the generic kernel, frontier and pixel states in global memory
         if (ev_flood) hipEventRecord(ev_flood, st);
-        hipLaunchKernelGGL(k_unwrap_flood<false>, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, (const int32_t *)nullptr, need);
+        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, (const int32_t *)nullptr, need);
+        if (ev_mid) hipEventRecord(ev_mid, st);
+        // g0|g1 (2 x B*EN uint32, contiguous) hold the per-pixel 64-bit words; stride EN words per frame
+        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)nullptr, EN, (unsigned long long *)g0, unwrapped, h, w,
+                           (const int32_t *)nullptr, need);
     }
-    if (ev_mid) hipEventRecord(ev_mid, st);
-    // g0|g1 (2 x B*EN uint32, contiguous) hold the per-pixel 64-bit words; stride EN words per frame
-    hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, ppar, EN, (unsigned long long *)g0, unwrapped, h, w, (const int32_t *)nullptr, need);
 }
 
 }  // namespace vf

@@ -1,7 +1,11 @@
-// k_unwrap_flood_batch: the growth loop of unwrap_quality_guided (shape_ftp.py:1043-1080), several pops per
-// step.  Same contract as k_unwrap_flood_hot (k_unwrap_hot.hip): one wavefront per frame, padded uint16 rank
-// plane in LDS (0 outside the mask, 1 visited, 2 frontier, >= 3 rank code), parents written in padded index
-// space, frontier = sorted HOT register list (<= 64 entries, code << 16 | pixel) + COLD bitmap over rank codes.
+// k_unwrap_flood_batch: the growth loop of unwrap_quality_guided (shape_ftp.py:1043-1080) for frames whose padded plane has at most
+// 65533 pixels, several pops per step.  One wavefront per frame holds the padded uint16 rank plane of k_unwrap_rank in LDS (0 outside
+// the mask and on the border, 1 visited, 2 frontier, >= 3 rank code) and writes parents in padded index space.  The frontier is split
+// in two, with the invariant  every HOT entry > every COLD entry:
+//   HOT   up to 64 entries (rank code << 16 | padded pixel index) kept SORTED, one per lane, in a VGPR;
+//   COLD  a two-level bitmap over rank codes in LDS (codes are unique per frame).  When HOT runs short, the top cold codes are pulled
+//         out of the bitmap already in descending order and their pixel indices come from the rank kernel's sorted index array.
+// A new entry goes to HOT only if it outranks the current HOT tail (then it outranks everything cold), otherwise to COLD.
 //
 // The reference pops ONE pixel at a time, but measured on this path 95 % of the pixels a pop adds to the
 // frontier rank below the 64 best frontier entries, and those best entries are scattered along the frontier.
@@ -21,6 +25,9 @@ namespace vf {
 
 constexpr int BT_NW = 1024;    // 64-bit words of the cold bitmap (codes < 65536)
 constexpr int BT_K = 8;        // candidates per step
+// LDS of k_unwrap_flood_batch: rank plane, cold bitmap + its summary words, refill staging, inv slice
+constexpr long batch_lds_bytes(long EN) { return ((EN + 7) & ~7L) * 2 + (BT_NW + 16) * 8 + 256 + 512; }
+static_assert(batch_lds_bytes(65533) <= 160 * 1024, "every frame of the uint16 rank range (unwrap_ranked_supported) fits the LDS");
 #ifdef VISTAF_DEBUG
 __device__ unsigned long long g_batch_dbg[8];      // frame 0: steps, candidates, commits, steps cut by (i) / (ii), refills, HOT inserts
 #define BT_COUNT(i, v) do { if (b == 0 && lane == 0) g_batch_dbg[i] += (unsigned long long)(v); } while (0)
@@ -336,18 +343,10 @@ __global__ __launch_bounds__(64 * RP_NW) void k_unwrap_replay(const float *__res
     }
 }
 
-bool unwrap_batch_supported(int h, int w)
-{
-    long EN = (long)(h + 2) * (w + 2);
-    long lds = (((EN + 7) & ~7L)) * 2 + (BT_NW + 16) * 8 + 256 + 512;
-    return EN <= 65533 && lds <= 160 * 1024;
-}
-
 void launch_unwrap_flood_batch(const uint16_t *rank16, const int32_t *seed, const uint32_t *inv, size_t inv_stride, int32_t *ppar, size_t gstride,
                                uint32_t *order, size_t ostride, int B, int h, int w, hipStream_t st, const int32_t *need)
 {
-    long EN = (long)(h + 2) * (w + 2);
-    size_t lds = (size_t)(((EN + 7) & ~7L)) * 2 + (BT_NW + 16) * 8 + 256 + 512;
+    const size_t lds = (size_t)batch_lds_bytes((long)(h + 2) * (w + 2));
     static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_unwrap_flood_batch, 160 * 1024);
     const uint32_t magic = (uint32_t)(0x100000000ull / (unsigned)(w + 2)) + 1u;     // idx / (w + 2) == umulhi(idx, magic) for idx < 65536

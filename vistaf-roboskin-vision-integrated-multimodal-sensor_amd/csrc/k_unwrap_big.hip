@@ -1,5 +1,5 @@
 // k_unwrap_flood_big: the growth loop of unwrap_quality_guided (shape_ftp.py:1043-1080) for frames whose padded plane does not fit the LDS
-// (more than 65533 padded pixels: the native 1182 x 1182 crops).  Same contract as the LDS-resident floods (k_unwrap_batch.hip): the total
+// (more than 65533 padded pixels: the native 1182 x 1182 crops).  Same contract as the LDS-resident batch flood (k_unwrap_batch.hip): the total
 // order of the reference's heap, (-q, y, x), is turned into RANKS up front (k_unwrap_rank32), the frontier is the set of ranks whose bit is
 // set, a pop is "highest set bit", the parent of a popped pixel is its lexicographically smallest visited neighbour.
 //
@@ -15,7 +15,7 @@
 //            visited neighbour or share a fresh neighbour with it);
 //       (ii) a fresh neighbour that outranks a later candidate has to pop before it: the prefix ends before that candidate.
 //   A step costs two dependent global round trips (sorted index -> pixel, pixel -> neighbour codes) instead of a scan of the whole
-//   frontier array per pop (k_unwrap_flood<false>, which stays the fallback for masks of more than 1.23 M pixels).
+//   frontier array per pop (k_unwrap_flood, which stays the fallback for masks of more than 1.23 M pixels).
 #include <cstdio>
 #include "kernels.hpp"
 
@@ -230,7 +230,7 @@ bool unwrap_big_supported(int h, int w)
     return EN > 65533 && EN < (1L << 26);
 }
 
-// force_generic (test hook flood_tier = 3): hand every frame back, which exercises the per-frame fallback plumbing at small sizes
+// force_generic (test hook big_flood_handback): hand every frame back, which exercises the per-frame fallback plumbing on masks that fit the bitmap
 void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t *n, const uint32_t *inv, size_t inv_stride, int32_t *ppar,
                              size_t gstride, int32_t *need_generic, bool force_generic, int B, int h, int w, hipStream_t st, const int32_t *need)
 {

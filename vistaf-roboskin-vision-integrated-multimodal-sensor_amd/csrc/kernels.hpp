@@ -8,12 +8,12 @@
 namespace vf {
 
 // Which of the parity-equivalent kernels a stage runs.  Defaults are the production kernels; the alternatives are fallbacks for
-// sizes the defaults do not cover and stay selectable so the parity tests can pin them against the defaults (csrc/test_hooks.h).
+// sizes or masks the defaults do not cover and stay selectable so the parity tests can pin them against the defaults (csrc/test_hooks.h).
+// The fields marked "test only" force such a fallback on inputs that would not take it.
 struct Tiers {
     int inpaint = 2;            // 2: frame-window march (k_telea_window) + whole-frame fallback; 1: whole-frame kernel only; 0: cluster front end first
-    int flood = 2;              // 2: batched pops (k_unwrap_flood_batch / k_unwrap_flood_big); 1: one pop per step (k_unwrap_flood_hot); 0: frontier scan; 3: test only (test_hooks.h)
+    int big_flood_handback = 0; // test only: 1 = the bitmap flood of frames beyond the uint16 rank range (k_unwrap_big.hip) hands every frame to the generic kernel
     int chamfer_twopass = 0;    // 1: force the one-wave two-pass chamfer even where the LDS closed form applies
-    int fit_capped = 0;        // 0: 128-VGPR column polyfit (default since the march and the flood stopped pinning CUs for milliseconds: 1.49 against 1.79 ms per step); 1: register-capped variant (96 VGPRs, shares a CU with LDS-heavy one-wave kernels)
     int telea_two_tier = 1;     // 1: 111 KB first tier of the window march + full-size retry of the frames it hands back; 0: full size only
     int unwrap_fast = 1;        // 1: frames whose wrapped field is verified path-independent skip the priority flood (k_unwrap_fast.hip); 0: always flood
     int big_chain = 1;          // 1: frames of 512 x 512 and more take k_big.hip's chains of streaming kernels for the exact selections and the IRLS fits; 0: one workgroup per frame
@@ -135,12 +135,12 @@ void launch_inpaint_clusters(float *img, const uint8_t *bad, int range, void *sc
 size_t unwrap_scratch_bytes_per_frame(int h, int w);
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
                    void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid,
-                   hipEvent_t ev_flood = nullptr, int flood_tier = 2, int32_t *need_buf = nullptr);      // need_buf [B]: enables the consistency check (k_unwrap_fast.hip)
+                   hipEvent_t ev_flood = nullptr, bool big_handback = false, int32_t *need_buf = nullptr);      // need_buf [B]: enables the consistency check (k_unwrap_fast.hip)
 
 // ---- k_fit.hip --------------------------------------------------------------------------------
 // min_count: fitted (mask & finite) pixels needed (:1103); min_mask_count: mask pixels needed, NaN included (debug_ramp's own gate, :1364)
 void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
-                           float *resid_out, int B, int h, int w, hipStream_t st, int capped = 1, void *big_scratch = nullptr);
+                           float *resid_out, int B, int h, int w, hipStream_t st, void *big_scratch = nullptr);
 
 // ---- k_holes.hip (hole stage, shape_ftp.py:1153-1204, :1770-1801; live only when reliable_smooth_sigma_px == 0) ----------------------
 void launch_zeroed_keep_nan(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, int B, int P, hipStream_t st);

@@ -8,8 +8,8 @@
 extern "C" {
 #endif
 /* name: "inpaint_tier"  2 window march + whole-frame fallback (default), 1 whole-frame kernel only, 0 cluster front end first
- *       "flood_tier"    2 batched pops (default), 1 one pop per step, 0 frontier scan; 3 (frames beyond the uint16 rank range only): the
- *                       bitmap flood hands every frame back to the generic kernel, as it does for masks larger than its bitmap
+ *       "big_flood_handback" 0 (default), 1 (frames beyond the uint16 rank range only): the bitmap flood hands every frame back to the
+ *                      generic kernel, as it does for masks larger than its bitmap
  *       "chamfer_twopass" 1 forces the one-wave two-pass chamfer transform (also for the wide frontier band of native crops, where batches
  *                      below 16 frames take the closed form)
  *       "telea_two_tier" 1 (default) 111 KB first tier of the window march + full-size retry, 0 full-size march only
@@ -24,7 +24,6 @@ extern "C" {
  *                      the slice's own size.  Only shrinks the capacity: the slice stride stays, pushes stay bounds-checked (overflow -> status 2)
  *       "big_fallback" 1 (default) a frame whose big-cluster queue overflowed (status 2) is re-marched whole by the whole-frame kernel,
  *                      0 the frame keeps status 2 and its overflowed cluster stays unfilled (shows that an overflow happened)
- *       "fit_capped"   0 (default) the 128-VGPR column polyfit, 1 the register-capped variant (96 VGPRs) that shares a CU with LDS-heavy one-wave kernels
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 #ifdef __cplusplus
