@@ -17,6 +17,8 @@ from . import tempseg
 from .tempseg import TempSegConfig, TempSegmenter, segment_dark_light_gratings_periodic_fft, compute_feature_planes, color_support_mask
 from . import tempmodel
 from .tempmodel import TempModel, predict_map_for_mask, predict_maps
+from . import tempsensor
+from .tempsensor import TempSensor, TempSensorConfig, map_statistics
 from .writers import (export_heightmap_files, height_map_bundle, multimodal_summary, result_record, temperature_statistics,
                       write_multimodal_summary, write_result_csv, write_result_json)
 
@@ -24,4 +26,4 @@ __all__ = ["FtpConfig", "FtpSensor", "SCALAR_NAMES", "depth_map_to_volume_cm3", 
            "load_force_calibration", "predict", "predict_force_from_volume", "synth", "parallel", "FtpAligner", "circle_from_3_points", "calibrate", "_lib", "export_heightmap_files",
            "height_map_bundle", "result_record", "write_result_csv", "write_result_json", "multimodal_summary", "temperature_statistics",
            "write_multimodal_summary", "tempseg", "TempSegConfig", "TempSegmenter", "segment_dark_light_gratings_periodic_fft", "compute_feature_planes", "color_support_mask",
-           "tempmodel", "TempModel", "predict_map_for_mask", "predict_maps"]
+           "tempmodel", "TempModel", "predict_map_for_mask", "predict_maps", "tempsensor", "TempSensor", "TempSensorConfig", "map_statistics"]

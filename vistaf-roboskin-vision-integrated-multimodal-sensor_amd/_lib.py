@@ -32,6 +32,9 @@ TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vista
                 "vistaf_temp_clamp_map", "vistaf_temp_inpaint_map", "vistaf_temp_fuse_maps", "vistaf_temp_oriented_blur"]   # include/vistaf_temp.h
 TEMPSEG_NINFO = 16
 TEMPMODEL_EXPORTS = ["vistaf_tmodel_create", "vistaf_tmodel_destroy", "vistaf_tmodel_predict_maps", "vistaf_tmodel_predict_rows"]   # include/vistaf_tempmodel.h
+TSENSOR_EXPORTS = ["vistaf_tsensor_default_config", "vistaf_tsensor_create", "vistaf_tsensor_destroy", "vistaf_tsensor_predict",
+                   "vistaf_tsensor_stats_create", "vistaf_tsensor_stats_destroy", "vistaf_tsensor_map_statistics"]   # include/vistaf_tempsensor.h
+TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -69,6 +72,12 @@ class CTempSegConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("seg_band_radius", "seg_dc_exclusion", "seg_illum_sigma", "sat_thresh_gray", "sat_dilate_ksize",
                                                 "post_close_kx", "post_close_ky", "post_open_kx", "post_open_ky", "n_peaks")] + \
                [("seg_peak_max_dy_from_center", ctypes.c_double)]
+
+
+class CTSensorConfig(ctypes.Structure):
+    _fields_ = [("seg", CTempSegConfig), ("fuse", CTempFuseConfig)] + \
+               [(n, ctypes.c_int32) for n in ("blur_ksize", "color_support_dilate", "wide_inpaint_radius", "color_inpaint_radius")] + \
+               [(n, ctypes.c_double) for n in ("color_chroma_min", "color_clamp_pad", "smooth_sigma_across", "smooth_sigma_along")]
 
 
 _lib = None
@@ -125,7 +134,16 @@ def load():
     lib.vistaf_tmodel_predict_maps.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int64,
                                                ctypes.c_int64, vp]
     lib.vistaf_tmodel_predict_rows.argtypes = [vp, vp, ci, ctypes.c_int64, vp, vp]
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS:
+    lib.vistaf_tsensor_default_config.argtypes = [ctypes.POINTER(CTSensorConfig)]
+    lib.vistaf_tsensor_create.argtypes = [ctypes.POINTER(CTSensorConfig), ci, ci, vp, vp, ctypes.POINTER(vp)]
+    lib.vistaf_tsensor_destroy.argtypes = [vp]
+    lib.vistaf_tsensor_destroy.restype = None
+    lib.vistaf_tsensor_predict.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(cd), vp, ctypes.POINTER(cd), vp]
+    lib.vistaf_tsensor_stats_create.argtypes = [ci, ci, ctypes.POINTER(vp)]
+    lib.vistaf_tsensor_stats_destroy.argtypes = [vp]
+    lib.vistaf_tsensor_stats_destroy.restype = None
+    lib.vistaf_tsensor_map_statistics.argtypes = [vp, vp, vp, vp, ctypes.POINTER(cd), vp]
+    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS:
         getattr(lib, fn)
     _lib = lib
     return lib

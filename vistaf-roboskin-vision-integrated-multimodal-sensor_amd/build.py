@@ -27,7 +27,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", "vistaf_ftp.h"), os.path.join(HERE, "..", "include", "vistaf_align.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_temp.h"), os.path.join(HERE, "..", "include", "vistaf_tempmodel.h")]
+                                                     os.path.join(HERE, "..", "include", "vistaf_temp.h"), os.path.join(HERE, "..", "include", "vistaf_tempmodel.h"),
+                                                     os.path.join(HERE, "..", "include", "vistaf_tempsensor.h")]
     jobs = []
     objs = []
     for s in srcs:

@@ -214,4 +214,10 @@ void launch_tm_warp_linear(const float *src, float *dst, const TmAff &a, int h, 
 void launch_tm_warp_nearest(const uint8_t *src, uint8_t *dst, const TmAff &a, int h, int w, hipStream_t st);
 void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t P, hipStream_t st);
 
+// ---- k_tempstats.hip (NumPy-exact mean / median / std / min / max / count of a float32 map over a valid mask, or isfinite when NULL):
+// out[6] doubles on the device; scratch of tstats_scratch_bytes, plus big_scratch_bytes(1, h, w) when tstats_needs_big_scratch (else NULL)
+size_t tstats_scratch_bytes(int h, int w);
+bool tstats_needs_big_scratch(int h, int w);
+void launch_tstats(const float *map, const uint8_t *valid, int h, int w, void *scratch, void *big_scratch, double *out, hipStream_t st);
+
 }  // namespace vf

@@ -529,30 +529,57 @@ static TmAff tm_invert(const double *m)                                         
     a.m[3] = A21; a.m[4] = A22; a.m[5] = -A21 * m[2] - A22 * m[5];
     return a;
 }
-static int tm_taps(double sigma, float *d_k, int &n, hipStream_t st)             // cv::getGaussianKernel(ksize(sigma), sigma, CV_32F)
+static int tm_taps(double sigma, std::vector<float> &f)                          // cv::getGaussianKernel(ksize(sigma), sigma, CV_32F)
 {
-    n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;
+    const int n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;
     if (n > 1023) return set_error(VISTAF_E_INVALID, "smoothing sigma too large");
     std::vector<double> t(n);
     const double s2 = -0.5 / (sigma * sigma);
     double sum = 0;
     for (int i = 0; i < n; i++) { const double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-    std::vector<float> f(n);
+    f.resize(n);
     for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-    if (hipMemcpyAsync(d_k, f.data(), n * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return set_error(VISTAF_E_HIP, "oriented blur: taps");
     return 0;
 }
 
-int vistaf_temp_oriented_blur(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double angle_rad, double sigma_across, double sigma_along,
-                              float *d_out, void *stream)
+}  // extern "C"
+
+namespace vf {
+
+// Both workspaces of a segmentation session at once (vistaf_tsensor_create allocates everything up front).
+int tempseg_prepare(vistaf_tempseg_handle *h)
 {
-    if (!h || !d_map || !d_roi || !d_out) return set_error(VISTAF_E_INVALID, "null argument");
+    int rc = seg_ensure(h);
+    return rc ? rc : tm_ensure(h);
+}
+
+// The two tap vectors of oriented_gaussian_blur_float (:705-747), uploaded to d_kx / d_ky (1024 floats each; synchronises `st`).
+// nx = ny = 0 when both sigmas are <= 0 (the blur is then the ROI mask alone).
+int temp_blur_taps(double sigma_across, double sigma_along, float *d_kx, int &nx, float *d_ky, int &ny, hipStream_t st)
+{
+    nx = ny = 0;
+    if (sigma_across <= 0 && sigma_along <= 0) return 0;      // :713-716
+    double sx = sigma_across > 0 ? sigma_across : 0.0, sy = sigma_along > 0 ? sigma_along : 0.0;
+    if (sx <= 0) return set_error(VISTAF_E_INVALID, "sigma_across must be positive when sigma_along is (cv::GaussianBlur needs sigmaX > 0 for ksize (0, 0))");
+    if (sy <= 0) sy = sx;                                     // cv::createGaussianKernels: sigmaY <= 0 takes sigmaX
+    std::vector<float> fx, fy;
+    int rc = tm_taps(sx, fx);
+    if (rc || (rc = tm_taps(sy, fy))) return rc;
+    if (hipMemcpyAsync(d_kx, fx.data(), fx.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_ky, fy.data(), fy.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return set_error(VISTAF_E_HIP, "oriented blur: taps");
+    nx = (int)fx.size(); ny = (int)fy.size();
+    return 0;
+}
+
+// The blur itself on taps already on the device (asynchronous on `st`).
+int temp_blur_apply(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double angle_rad, const float *d_kx, int nx, const float *d_ky,
+                    int ny, float *d_out, hipStream_t st)
+{
     int rc = tm_ensure(h);
     if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
     const size_t P = h->P;
-    if (sigma_across <= 0 && sigma_along <= 0) {              // :713-716
+    if (nx == 0) {
         launch_tm_mask_nan(d_map, d_roi, d_out, P, st);
         return tm_done("oriented blur");
     }
@@ -561,20 +588,31 @@ int vistaf_temp_oriented_blur(vistaf_tempseg_handle *h, const float *d_map, cons
     tm_rotation(cx, cy, angle_deg, M);
     tm_rotation(cx, cy, -angle_deg, Mi);
     const TmAff a = tm_invert(M), ai = tm_invert(Mi);
-    double sx = sigma_across > 0 ? sigma_across : 0.0, sy = sigma_along > 0 ? sigma_along : 0.0;
-    if (sx <= 0) return set_error(VISTAF_E_INVALID, "sigma_across must be positive when sigma_along is (cv::GaussianBlur needs sigmaX > 0 for ksize (0, 0))");
-    if (sy <= 0) sy = sx;                                     // cv::createGaussianKernels: sigmaY <= 0 takes sigmaX
-    int nx = 0, ny = 0;
-    if ((rc = tm_taps(sx, h->tm_kx, nx, st)) || (rc = tm_taps(sy, h->tm_ky, ny, st))) return rc;
     launch_tm_zero_nonfinite(d_map, h->tmA, P, st);
     launch_tm_warp_linear(h->tmA, h->tmB, a, h->H, h->W, st);                   // rot_map
     launch_tm_warp_nearest(d_roi, h->tmM1, a, h->H, h->W, st);                  // rot_roi
-    launch_gauss_rows(h->tmB, h->tmA, h->tm_kx, nx, 1, h->H, h->W, st);
-    launch_gauss_cols(h->tmA, h->tmB, h->tm_ky, ny, 1, h->H, h->W, st);         // blurred
+    launch_gauss_rows(h->tmB, h->tmA, d_kx, nx, 1, h->H, h->W, st);
+    launch_gauss_cols(h->tmA, h->tmB, d_ky, ny, 1, h->H, h->W, st);             // blurred
     launch_tm_warp_linear(h->tmB, h->tmA, ai, h->H, h->W, st);                  // back
     launch_tm_warp_nearest(h->tmM1, h->tmM2, ai, h->H, h->W, st);               // back_roi
     launch_tm_mask_nan(h->tmA, h->tmM2, d_out, P, st);
     return tm_done("oriented blur");
+}
+
+}  // namespace vf
+
+extern "C" {
+
+int vistaf_temp_oriented_blur(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double angle_rad, double sigma_across, double sigma_along,
+                              float *d_out, void *stream)
+{
+    if (!h || !d_map || !d_roi || !d_out) return set_error(VISTAF_E_INVALID, "null argument");
+    int rc = tm_ensure(h);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    int nx = 0, ny = 0;
+    if ((rc = temp_blur_taps(sigma_across, sigma_along, h->tm_kx, nx, h->tm_ky, ny, st))) return rc;
+    return temp_blur_apply(h, d_map, d_roi, angle_rad, h->tm_kx, nx, h->tm_ky, ny, d_out, st);
 }
 
 }  // extern "C"
