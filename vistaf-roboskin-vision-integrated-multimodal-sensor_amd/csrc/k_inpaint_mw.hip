@@ -18,11 +18,15 @@
 //      The bench frames: 6 generations for the outside pass, 7-9 for the hole, ~2 000 pops each in ~160 / ~230 dependence levels
 //      (the band pixels' raster-order chains make up 100 of them), ~1 400 fills in ~200 levels (tools/telea_dag.py).
 //
-// Phases (all 16 waves unless noted): window flags + ring | outside pass (icvCalcFMM with negate), generation by generation |
-// the march's ordering pass over the hole, generation by generation | image load, negate, dependence counters of the fills |
+// Phases (all 16 waves unless noted): window flags + ring (and the counts of ring, band and hole cells) | generation 0 of both FMM passes
+// (the band pixels in raster order) | the outside pass (icvCalcFMM with negate) on waves 0-5 and, AT THE SAME TIME, the march's ordering pass
+// over the hole on waves 6-15, each generation by generation in scratch sized from its cell counts (frames whose counts do not fit run the
+// two passes one after the other on all 16 waves in the fixed-size scratch) | image load, negate, dependence counters of the fills |
 // the estimates (telea_fill_known_T: the single-wave fill block minus solve and push) from a ready queue | write back.
 // Frames whose window, queues or lists do not fit are flagged in fb[] for the full-size single-wave tier (k_telea_window_retry).
+#include <algorithm>
 #include <cstdio>
+#include <vector>
 #include "kernels.hpp"
 #include <type_traits>
 #include "telea_common.hpp"
@@ -31,22 +35,30 @@ namespace vf {
 
 constexpr int MW_WAVES = 16;
 constexpr int MW_T = MW_WAVES * 64;
+constexpr int MW_WAVES_OUT = 6;     // concurrent passes: waves [0, 6) run the outside pass, the other 10 the ordering pass (measured: 8 / 8 and 5 / 11 are slower)
 constexpr int MW_CELLS = 10752;     // window cells: 11 B each (T f32, image f32, fill number u16, flags u8)
 constexpr int MW_FILLS = 4096;      // hole pixels per frame
 constexpr int MW_RING_U = 6;
 constexpr int GP_POOL = 4096;       // pushes of one FMM pass (the pool is append-only: popped entries are blanked)
 constexpr int GP_GEN = 2048;        // entries of one generation
 constexpr int GP_MAXGEN = 32;
-constexpr int GP_CNT = 256;         // chunk counts / bitmap prefix
-// fill-number plane: hole pixel not filled yet / not a hole pixel / filled (number pending) / queued in the current generation with rank r
-constexpr uint16_t FI_INSIDE = 0x3FFFu, FI_NOHOLE = 0x3FFEu, FI_FILLED = 0x3FFDu, FI_PEND = 0x8000u;
-enum { MWC_FAIL = 0, MWC_NFILL, MWC_HEAD, MWC_TAIL, MWC_POOLN, MWC_GENN, MWC_TMIN, MWC_N = 16 };
+constexpr int GP_CNT = 256;         // chunk counts / bitmap prefix / bins of the ranking
+constexpr int GP_BINS = 64;         // ranking of a generation: bins on T - T_min (cnt[0, 64): sizes, cnt[64, 128): starts)
+// fill-number plane: hole pixel not filled yet / not a hole pixel / filled (number pending) / queued in the current generation with rank r.
+// A rank mark carries the bit of the pass it belongs to (generation 0, the band pixels, belongs to both: each pass clears its own bit when it
+// pops the pixel); marks stay out of the fill-number range (>= FI_PEND > FI_FILLED)
+constexpr uint16_t FI_INSIDE = 0x3FFFu, FI_NOHOLE = 0x3FFEu, FI_FILLED = 0x3FFDu, FI_PEND = 0x8000u, FI_OUT = 0x4000u, FI_ORD = 0x2000u, FI_RANK = 0x07FFu;
+enum { MWC_FAIL = 0, MWC_NFILL, MWC_HEAD, MWC_TAIL, MWC_POOLN, MWC_GENN, MWC_TMIN, MWC_BAR, MWC_NRING, MWC_NHOLE, MWC_NBAND, MWC_N = 16 };
 constexpr size_t MW_REGION_A = (size_t)GP_POOL * 8;          // FMM: pool; fills: dependence counters u32 + ready queue u32
-constexpr size_t MW_LDS = MW_REGION_A + (size_t)MW_CELLS * 11 + (size_t)MW_FILLS * 2 + GP_CNT * 4 + MWC_N * 4;
+// the passes' scratch: region A and the image plane, adjacent (the image is loaded after the passes)
+constexpr size_t MW_SCRATCH = MW_REGION_A + (size_t)MW_CELLS * 4;
+constexpr size_t MW_LDS = MW_CELLS * 4 + MW_SCRATCH + (size_t)MW_CELLS * 2 + (size_t)MW_FILLS * 2 + 2 * (GP_CNT * 4 + MWC_N * 4) + MW_CELLS;
 static_assert(MW_LDS <= 160 * 1024, "one CU's LDS");
 static_assert((size_t)MW_FILLS * 8 <= MW_REGION_A, "dependence counters and ready queue of the fills");
 static_assert((size_t)GP_GEN * (8 + 4) + GP_GEN * 4 / 8 <= (size_t)MW_CELLS * 4, "generation scratch lives in the image plane until the image is loaded");
-static_assert(MW_FILLS < FI_FILLED && GP_GEN <= 0x800 && MW_CELLS <= 0x4000 && MW_CELLS / 64 <= GP_CNT && GP_GEN * 4 / 32 <= GP_CNT, "field widths");
+static_assert(MW_FILLS < FI_FILLED && GP_GEN <= FI_RANK + 1 && MW_CELLS <= 0x4000 && MW_CELLS / 64 <= GP_CNT && GP_GEN * 4 / 32 <= GP_CNT && 2 * GP_BINS <= GP_CNT,
+              "field widths");
+static_assert(MW_WAVES_OUT > 0 && MW_WAVES_OUT < MW_WAVES, "wave split");
 
 #ifdef VISTAF_DEBUG
 __device__ unsigned long long g_mw_dbg[1024][16];
@@ -61,17 +73,36 @@ __device__ unsigned long long g_mw_dbg[1024][16];
 #endif
 
 struct GenScratch {
-    unsigned long long *pool;       // [GP_POOL] (T bits | generation | parent's rank | neighbour | cell), blank = ~0
-    unsigned long long *gen;        // [GP_GEN] the current generation in pop order
-    uint32_t *dep;                  // [GP_GEN] earlier entries of the generation within Manhattan distance 3 that have not popped yet
-    uint32_t *bitmap;               // [GP_GEN * 4 / 32] fills of the generation by (rank, neighbour)
+    unsigned long long *pool;       // [pcap] (T bits | generation | parent's rank | neighbour | cell), blank = ~0
+    unsigned long long *gen;        // [gcap] the current generation in pop order
+    uint32_t *dep;                  // [gcap] earlier entries of the generation within Manhattan distance 3 that have not popped yet
+    uint32_t *bitmap;               // [GP_GEN * 4 / 32] fills of the generation by (rank, neighbour) (ordering pass)
     int *cnt;                       // [GP_CNT]
-    int *ctl;
+    int *ctl;                       // [MWC_N]
+    int pcap, gcap;                 // pushes of the pass, entries of a generation (gcap <= GP_GEN)
+};
+// The waves that run one FMM pass: the whole workgroup (barrier: s_barrier), or one part of it while the other part runs the other pass
+// (barrier: an arrival counter in LDS that only counts this part's waves)
+template <bool SPLIT>
+struct WaveGroup {
+    int nthr, tid, wave;            // threads of the group, this thread's and this wave's index in it
+    int *bar;                       // SPLIT: arrival counter, one increment per wave and barrier
+    int phase;                      // SPLIT: arrivals that complete this wave's latest barrier
+    __device__ __attribute__((always_inline)) void sync()
+    {
+        if (!SPLIT) { __syncthreads(); return; }
+        phase += nthr >> 6;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        if ((tid & 63) == 0) __hip_atomic_fetch_add(bar, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        while (__hip_atomic_load(bar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < phase) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
 };
 __device__ inline unsigned long long gp_key(float T, int g, int rank, int nb, int cell)
 {
     return ((unsigned long long)__float_as_uint(T) << 32) | ((unsigned long long)(((uint32_t)g << 27) | ((uint32_t)rank << 16) | ((uint32_t)nb << 14) | (uint32_t)cell));
 }
+__device__ inline bool gp_marked(unsigned v, uint16_t mb) { return (v & (FI_PEND | mb)) == (FI_PEND | mb); }
 __device__ inline int wave_excl_scan(int v, int lane, int &total)
 {
     int s = v;
@@ -81,8 +112,8 @@ __device__ inline int wave_excl_scan(int v, int lane, int &total)
 }
 
 // The pops of one generation on one wave.  A pop needs 16 lanes (4 neighbours x 4 quadrants), so the wave holds FOUR entries at a time, one
-// per 16-lane group: 64 entries of the generation are held by the workgroup's waves, claimed in pop order (the first entry that has not
-// popped yet is therefore always held and has no open dependence: the loop makes progress whatever the others wait for).  Every turn a group
+// per 16-lane group: 4 x (the group's waves) entries of the generation are held, claimed in pop order (the first entry that has not popped
+// yet is therefore always held and has no open dependence: the loop makes progress whatever the others wait for).  Every turn a group
 // without an entry claims the next one, every group looks at its entry's counter of earlier entries in reach that have not popped yet, and the
 // groups whose counter is 0 pop together -- two such entries are never in reach of each other (the later one would be waiting for the earlier).
 // ORDER: the march's ordering pass (states in the fill-number plane), else the outside pass (states in the flag bytes).
@@ -90,6 +121,7 @@ template <bool ORDER>
 __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScratch &S, float *t, uint8_t *f, uint16_t *fi, int M, int g, int wh, int ww,
                                                                   uint32_t mg_ww, int lane)
 {
+    constexpr uint16_t MB = ORDER ? FI_ORD : FI_OUT;
     const TeleaOutsideConsts oc = telea_outside_consts(lane, ww);       // per 16-lane group: 4 neighbours x 4 quadrants
     const int nbi = (lane >> 2) & 3, grp = lane >> 4, li = lane & 15;
     // the 24 cells within Manhattan distance 3: lane li of a group takes cells li and li + 16
@@ -132,7 +164,8 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
                 const bool nin0 = non[0] && py + ndy[0] >= 0 && py + ndy[0] < wh && px + ndx[0] >= 0 && px + ndx[0] < ww;
                 const bool nin1 = non[1] && py + ndy[1] >= 0 && py + ndy[1] < wh && px + ndx[1] >= 0 && px + ndx[1] < ww;
                 // every read of the pop in one round: the neighbour's state, the two arguments of its quadrant (an address outside the window's
-                // planes returns junk nobody looks at), the rank marks around p (entries that wait for this pop keep their mark until they pop)
+                // planes, or a cell of the other pass, returns a value nobody looks at), the rank marks around p (entries that wait for this
+                // pop keep their mark until they pop)
                 const float a11 = t[p1], a22 = t[p2];
                 bool in0, in1, in2;
                 if (ORDER) { const uint16_t s0 = fi[pn], s1 = fi[p1], s2 = fi[p2]; in0 = s0 == FI_INSIDE; in1 = s1 == FI_INSIDE; in2 = s2 == FI_INSIDE; }
@@ -144,8 +177,13 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
                     o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0x4E, 0xf, 0xf, false)); dist = o < dist ? o : dist;
                 }
                 if (li == 0) {                          // the entry leaves the queue (this also drops its rank mark)
-                    if (ORDER) fi[p] = g == 0 ? FI_NOHOLE : FI_FILLED;
-                    else { f[p] = (uint8_t)(g == 0 ? (W_SEED | W_CHANGE) : W_CHANGE); fi[p] = FI_NOHOLE; }
+                    if (g == 0) {                       // a band pixel: the other pass may still hold its own mark on it
+                        __hip_atomic_fetch_and((uint32_t *)fi + (p >> 1), ~((uint32_t)MB << ((p & 1) << 4)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                        if (!ORDER) f[p] = (uint8_t)(W_SEED | W_CHANGE);
+                    } else {
+                        if (ORDER) fi[p] = FI_FILLED;
+                        else { f[p] = W_CHANGE; fi[p] = FI_NOHOLE; }
+                    }
                 }
                 plead = in0 && (li & 3) == 0;
                 pdist = dist; ppn = pn; pr = r;
@@ -153,13 +191,10 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
                     t[pn] = dist;
                     if (ORDER) fi[pn] = FI_FILLED; else f[pn] = W_BAND;
                 }
-                // release the later entries in reach.  The stores above and the decrements below are LDS operations of one wave: the LDS
-                // unit executes them in issue order, so a wave that sees its counter at 0 sees the stores (no s_waitcnt between them: the
-                // compiler only has to keep the order)
-                asm volatile("" ::: "memory");
-                const unsigned rv0 = v0 & 0x7FFFu, rv1 = v1 & 0x7FFFu;
-                if (nin0 && (v0 & FI_PEND) && rv0 > (unsigned)r) __hip_atomic_fetch_sub(&S.dep[rv0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (nin1 && (v1 & FI_PEND) && rv1 > (unsigned)r) __hip_atomic_fetch_sub(&S.dep[rv1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                // release the later entries in reach: a wave that reads its counter at 0 (acquire) sees the stores above
+                const unsigned rv0 = v0 & FI_RANK, rv1 = v1 & FI_RANK;
+                if (nin0 && gp_marked(v0, MB) && rv0 > (unsigned)r) __hip_atomic_fetch_sub(&S.dep[rv0], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+                if (nin1 && gp_marked(v1, MB) && rv1 > (unsigned)r) __hip_atomic_fetch_sub(&S.dep[rv1], 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 r = -1;
             }
             continue;                                   // look at the counters again before any housekeeping
@@ -171,7 +206,7 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
             int base = 0;
             if (lane == 0) base = atomicAdd(&ctl[MWC_POOLN], cnt);
             base = __builtin_amdgcn_readfirstlane(base);
-            const bool fits = base + cnt <= GP_POOL;
+            const bool fits = base + cnt <= S.pcap;
             if (!fits && lane == 0) ctl[MWC_FAIL] = 1;
             if (plead) {
                 if (fits) S.pool[base + __popcll(pb & ((1ull << lane) - 1ull))] = gp_key(pdist, g, pr, nbi, ppn);
@@ -198,55 +233,71 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
     }
 }
 
-// One FMM pass over the window, generation by generation.  Returns false (uniformly) when a capacity was exceeded.
-template <bool ORDER>
-__device__ __attribute__((always_inline)) inline bool gp_pass(const GenScratch &S, float *t, uint8_t *f, uint16_t *fi, uint16_t *flist, int cells, int wh, int ww,
-                                                              uint32_t mg_ww, int tid, int lane, int wave)
+// Generation 0 of both FMM passes, on all 16 waves: the band pixels in raster order (T = 0) into gen (and gen2), rank-marked for both passes
+// when `mark`.  Returns the size of the generation, -1 (uniformly) when it exceeds GP_GEN.
+__device__ inline int gp_gen0(unsigned long long *gen, unsigned long long *gen2, int *cnt, int *ctl, const uint8_t *f, uint16_t *fi, bool mark, int cells,
+                              int lane, int wave)
 {
-    int *ctl = S.ctl;
-    // generation 0: the band pixels in raster order (T = 0)
     const int nchunk = (cells + 63) >> 6;
     for (int ch = wave; ch < nchunk; ch += MW_WAVES) {
         const int li = ch * 64 + lane;
         const unsigned long long bal = __ballot(li < cells && (f[li] & W_SEED));
-        if (lane == 0) S.cnt[ch] = __popcll(bal);
+        if (lane == 0) cnt[ch] = __popcll(bal);
     }
-    if (tid == 0) { ctl[MWC_POOLN] = 0; ctl[MWC_TMIN] = (int)0xFFFFFFFFu; if (ORDER) ctl[MWC_NFILL] = 0; }
     __syncthreads();
     if (wave == 0) {
         int a[4], sum = 0;
 #pragma unroll
-        for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; a[k] = ch < nchunk ? S.cnt[ch] : 0; sum += a[k]; }
+        for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; a[k] = ch < nchunk ? cnt[ch] : 0; sum += a[k]; }
         int total;
         int ex = wave_excl_scan(sum, lane, total);
 #pragma unroll
-        for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; if (ch < nchunk) S.cnt[ch] = ex; ex += a[k]; }
+        for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; if (ch < nchunk) cnt[ch] = ex; ex += a[k]; }
         if (lane == 0) ctl[MWC_GENN] = total;
     }
     __syncthreads();
-    int M = ctl[MWC_GENN];
-    if (M > GP_GEN) return false;
+    const int M = ctl[MWC_GENN];
+    if (M > GP_GEN) return -1;
     for (int ch = wave; ch < nchunk; ch += MW_WAVES) {
         const int li = ch * 64 + lane;
         const bool sd = li < cells && (f[li] & W_SEED);
         const unsigned long long bal = __ballot(sd);
-        if (sd) { const int r = S.cnt[ch] + __popcll(bal & ((1ull << lane) - 1ull)); S.gen[r] = gp_key(0.f, 0, r, 0, li); }
+        if (sd) {
+            const int r = cnt[ch] + __popcll(bal & ((1ull << lane) - 1ull));
+            gen[r] = gp_key(0.f, 0, r, 0, li);
+            if (gen2) gen2[r] = gp_key(0.f, 0, r, 0, li);
+            if (mark) fi[li] = (uint16_t)(FI_PEND | FI_OUT | FI_ORD | r);
+        }
     }
     __syncthreads();
+    return M;
+}
 
+// One FMM pass over the window from its generation 0 (M entries, marked), generation by generation, on the waves of G.  Returns false
+// (uniformly in G) when a capacity was exceeded.
+template <bool ORDER, bool SPLIT>
+__device__ __attribute__((always_inline)) inline bool gp_gens(const GenScratch &S, WaveGroup<SPLIT> &G, float *t, uint8_t *f, uint16_t *fi, uint16_t *flist,
+                                                              int M, int wh, int ww, uint32_t mg_ww, int lane)
+{
+    constexpr uint16_t MB = ORDER ? FI_ORD : FI_OUT;
+    constexpr int NW = !SPLIT ? MW_WAVES : ORDER ? MW_WAVES - MW_WAVES_OUT : MW_WAVES_OUT;
+    constexpr int K = (GP_GEN / 64 + NW - 1) / NW;                     // generation entries per thread
+    const int tid = G.tid, nthr = G.nthr;
+    int *ctl = S.ctl;
     GSTART();
     for (int g = 0;; g++) {
-        // rank marks
-        for (int r = tid; r < M; r += MW_T) {
-            const int cell = (int)((uint32_t)S.gen[r] & 0x3FFFu);
-            fi[cell] = (uint16_t)(FI_PEND | r);
-        }
-        if (ORDER) for (int i = tid; i < GP_GEN * 4 / 32; i += MW_T) S.bitmap[i] = 0;
+        // rank marks (generation 0 was marked for both passes at once)
+        if (g > 0)
+            for (int r = tid; r < M; r += nthr) {
+                const int cell = (int)((uint32_t)S.gen[r] & 0x3FFFu);
+                fi[cell] = (uint16_t)(FI_PEND | MB | r);
+            }
+        if (ORDER) for (int i = tid; i < GP_GEN * 4 / 32; i += nthr) S.bitmap[i] = 0;
         if (tid == 0) { ctl[MWC_HEAD] = 0; ctl[MWC_TAIL] = 0; ctl[MWC_GENN] = 0; }
         const int pool_n0 = ctl[MWC_POOLN];
-        __syncthreads();
+        G.sync();
         // dependence counters: earlier entries of this generation within Manhattan distance 3
-        for (int r = tid; r < M; r += MW_T) {
+        for (int r = tid; r < M; r += nthr) {
             const int cell = (int)((uint32_t)S.gen[r] & 0x3FFFu);
             const int py = (int)__umulhi((uint32_t)cell, mg_ww), px = cell - py * ww;
             uint32_t c = 0;
@@ -259,21 +310,21 @@ __device__ __attribute__((always_inline)) inline bool gp_pass(const GenScratch &
                     if (dy == 0 && dx == 0) continue;
                     const bool in = yin && px + dx >= 0 && px + dx < ww;
                     const unsigned v = fi[in ? cell + dy * ww + dx : cell];
-                    c += (in && (v & FI_PEND) && (v & 0x7FFFu) < (unsigned)r) ? 1u : 0u;
+                    c += (in && gp_marked(v, MB) && (v & FI_RANK) < (unsigned)r) ? 1u : 0u;
                 }
             }
             S.dep[r] = c;
         }
-        __syncthreads();
+        G.sync();
         GACC(11);
         gp_pop_loop<ORDER>(S, t, f, fi, M, g, wh, ww, mg_ww, lane);
-        __syncthreads();
+        G.sync();
         GACC(12);
         if (ctl[MWC_FAIL]) return false;
         const int pool_n = ctl[MWC_POOLN];
         if (ORDER) {
             // number this generation's fills in push order = by (parent's rank, neighbour)
-            if (wave == 0) {
+            if (G.wave == 0) {
                 int a[4], sum = 0;
 #pragma unroll
                 for (int k = 0; k < 4; k++) { a[k] = __popc(S.bitmap[lane * 4 + k]); sum += a[k]; }
@@ -282,58 +333,76 @@ __device__ __attribute__((always_inline)) inline bool gp_pass(const GenScratch &
 #pragma unroll
                 for (int k = 0; k < 4; k++) { S.cnt[lane * 4 + k] = ex; ex += a[k]; }
             }
-            __syncthreads();
+            G.sync();
             const int nf0 = ctl[MWC_NFILL];
-            for (int i = pool_n0 + tid; i < pool_n; i += MW_T) {
+            for (int i = pool_n0 + tid; i < pool_n; i += nthr) {
                 const uint32_t lo = (uint32_t)S.pool[i];
                 const unsigned bi = (lo >> 14) & 0x1FFFu;                  // rank * 4 + neighbour
                 const int num = nf0 + S.cnt[bi >> 5] + __popc(S.bitmap[bi >> 5] & ((1u << (bi & 31)) - 1u));
                 if (num < MW_FILLS) flist[num] = (uint16_t)(lo & 0x3FFFu);
             }
-            __syncthreads();
+            G.sync();
             if (tid == 0) ctl[MWC_NFILL] = nf0 + (pool_n - pool_n0);
         }
         GACC(13);
         // the next generation: everything below T_head + 0.70
         {
             uint32_t mn = 0xFFFFFFFFu;
-            for (int i = tid; i < pool_n; i += MW_T) { const uint32_t tb = (uint32_t)(S.pool[i] >> 32); mn = tb < mn ? tb : mn; }
+            for (int i = tid; i < pool_n; i += nthr) { const uint32_t tb = (uint32_t)(S.pool[i] >> 32); mn = tb < mn ? tb : mn; }
             for (int o = 32; o; o >>= 1) { const uint32_t u = (uint32_t)__shfl_xor((int)mn, o, 64); mn = u < mn ? u : mn; }
             if (lane == 0 && mn != 0xFFFFFFFFu) atomicMin((unsigned int *)&ctl[MWC_TMIN], mn);
+            if (tid < GP_BINS) S.cnt[tid] = 0;
         }
-        __syncthreads();
+        G.sync();
         const uint32_t tmin = (uint32_t)ctl[MWC_TMIN];
         if (tmin == 0xFFFFFFFFu) break;                                   // queue empty: the pass is complete
         if (g + 1 >= GP_MAXGEN) return false;
         const uint32_t thr = __float_as_uint(__uint_as_float(tmin) + 0.70f);
-        for (int i = tid; i < pool_n; i += MW_T) {
+        for (int i = tid; i < pool_n; i += nthr) {
             const unsigned long long k = S.pool[i];
             if ((uint32_t)(k >> 32) < thr) {
                 const int slot = atomicAdd(&ctl[MWC_GENN], 1);
-                if (slot < GP_GEN) S.gen[slot] = k;
+                if (slot < S.gcap) S.gen[slot] = k;
                 S.pool[i] = ~0ull;
             }
         }
-        __syncthreads();
+        G.sync();
         M = ctl[MWC_GENN];
         if (tid == 0) ctl[MWC_TMIN] = (int)0xFFFFFFFFu;
-        if (M > GP_GEN) return false;
-        // pop order of the generation: rank = number of smaller keys (keys are unique)
+        if (M > S.gcap) return false;
+        // pop order of the generation: rank = number of smaller keys (keys are unique).  The bin of a key, floor((T - T_min) * 91) <= 63, never
+        // decreases with the key, so every key of a lower bin is smaller: rank = start of the bin + smaller keys in the bin
         {
-            unsigned long long my[2];
-            int c[2] = {0, 0};
+            const float tmf = __uint_as_float(tmin);
+            unsigned long long my[K];
+            int bn[K], pos[K];
 #pragma unroll
-            for (int k = 0; k < 2; k++) my[k] = tid + k * MW_T < M ? S.gen[tid + k * MW_T] : ~0ull;
-            if (M <= MW_T) {
-                for (int j = 0; j < M; j++) c[0] += S.gen[j] < my[0] ? 1 : 0;
-            } else {
-                for (int j = 0; j < M; j++) { const unsigned long long kj = S.gen[j]; c[0] += kj < my[0] ? 1 : 0; c[1] += kj < my[1] ? 1 : 0; }
+            for (int k = 0; k < K; k++) {
+                const int i = tid + k * nthr;
+                my[k] = i < M ? S.gen[i] : ~0ull;
+                const int b = i < M ? (int)((__uint_as_float((uint32_t)(my[k] >> 32)) - tmf) * 91.0f) : 0;
+                bn[k] = b < GP_BINS - 1 ? b : GP_BINS - 1;
+                pos[k] = i < M ? atomicAdd(&S.cnt[bn[k]], 1) : 0;
             }
-            __syncthreads();
+            G.sync();
+            if (G.wave == 0) { int total; S.cnt[GP_BINS + lane] = wave_excl_scan(S.cnt[lane], lane, total); }      // GP_BINS == 64 lanes
+            G.sync();
 #pragma unroll
-            for (int k = 0; k < 2; k++) if (tid + k * MW_T < M) S.gen[c[k]] = my[k];
+            for (int k = 0; k < K; k++) if (tid + k * nthr < M) S.gen[S.cnt[GP_BINS + bn[k]] + pos[k]] = my[k];
+            G.sync();
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                if (tid + k * nthr >= M) continue;
+                const int b0 = S.cnt[GP_BINS + bn[k]], n = S.cnt[bn[k]];
+                int c = 0;
+                for (int j = 0; j < n; j++) c += S.gen[b0 + j] < my[k] ? 1 : 0;
+                pos[k] = b0 + c;
+            }
+            G.sync();
+#pragma unroll
+            for (int k = 0; k < K; k++) if (tid + k * nthr < M) S.gen[pos[k]] = my[k];
         }
-        __syncthreads();
+        G.sync();
         GACC(14);
 #ifdef VISTAF_DEBUG
         if (threadIdx.x == 0 && blockIdx.x < 1024) g_mw_dbg[blockIdx.x][15]++;
@@ -368,15 +437,15 @@ __device__ __attribute__((always_inline)) inline void mw_fill_loop(const TeleaWi
         const unsigned k = e & 0xFFFFu;
         const int pi = (int)(e >> 16);
         // the fill numbers around pi are read before the estimate (they do not change), the counters of the later ones are decremented
-        // right behind its stores: LDS operations of one wave execute in issue order, no wait is needed between them
+        // behind its stores with release; the decrement that frees a fill acquires the earlier ones' releases and hands them on to the
+        // wave that takes the fill from the queue
         const unsigned c0 = non[0] ? fi[pi + noff[0]] : 0u, c1 = non[1] ? fi[pi + noff[1]] : 0u;
         telea_fill_known_T<NS>(win, mc, pi, lane);
-        asm volatile("" ::: "memory");
         auto release = [&](unsigned c) {
             if (c > k && c < FI_FILLED) {
-                if (atomicSub(&dep[c], 1u) == 1u) {
+                if (__hip_atomic_fetch_sub(&dep[c], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) == 1u) {
                     const int slot = atomicAdd(&ctl[MWC_TAIL], 1);
-                    __hip_atomic_store(&rq[slot], c | ((unsigned)flist[c] << 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_store(&rq[slot], c | ((unsigned)flist[c] << 16), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }
         };
@@ -405,21 +474,15 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
     float *img = img_all + (size_t)b * P;
     const uint8_t *bad = bad_all + (size_t)b * P;
 
-    unsigned char *regA = mw_lds;                                // [MW_REGION_A]
-    float *t = (float *)(regA + MW_REGION_A);                    // [MW_CELLS]
-    float *im = t + MW_CELLS;                                    // [MW_CELLS]; generation scratch until the image is loaded
+    float *t = (float *)mw_lds;                                  // [MW_CELLS]
+    unsigned char *regA = (unsigned char *)(t + MW_CELLS);       // [MW_REGION_A]; FMM scratch together with im
+    float *im = (float *)(regA + MW_REGION_A);                   // [MW_CELLS]; FMM scratch until the image is loaded
     uint16_t *fi = (uint16_t *)(im + MW_CELLS);                  // [MW_CELLS]
     uint16_t *flist = fi + MW_CELLS;                             // [MW_FILLS]
-    int *cntv = (int *)(flist + MW_FILLS);                       // [GP_CNT]
-    int *ctl = cntv + GP_CNT;                                    // [MWC_N]
-    uint8_t *f = (uint8_t *)(ctl + MWC_N);                       // [MW_CELLS]
-    GenScratch S;
-    S.pool = (unsigned long long *)regA;
-    S.gen = (unsigned long long *)im;
-    S.dep = (uint32_t *)(S.gen + GP_GEN);
-    S.bitmap = S.dep + GP_GEN;
-    S.cnt = cntv;
-    S.ctl = ctl;
+    int *cntv = (int *)(flist + MW_FILLS);                       // [2][GP_CNT] outside pass, ordering pass
+    int *ctl = cntv + 2 * GP_CNT;                                // [2][MWC_N] outside pass (and everything after the passes), ordering pass
+    int *ctl2 = ctl + MWC_N;
+    uint8_t *f = (uint8_t *)(ctl2 + MWC_N);                      // [MW_CELLS]
     const uint32_t mg_ww = (uint32_t)(0x100000000ull / (unsigned)ww) + 1u;       // li / ww == umulhi(li, mg_ww) for li < 2^16
     MSTAMP(0);
 #ifdef VISTAF_DEBUG
@@ -427,7 +490,8 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
 #endif
 
     // ---- window flags (hole / border bits), T = 1e6
-    if (tid < MWC_N) ctl[tid] = 0;
+    if (tid < 2 * MWC_N) ctl[tid] = tid % MWC_N == MWC_TMIN ? (int)0xFFFFFFFFu : 0;
+    int nhole = 0, nring = 0, nband = 0;                         // this thread's cells of each kind
     for (int base = 0; base < cells; base += MW_T * 4) {
         uint8_t bd[4];
         bool interior[4];
@@ -445,6 +509,7 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
             const int li = base + k * MW_T + tid;
             if (li >= cells) continue;
             const bool hole = interior[k] && bd[k];
+            nhole += hole ? 1 : 0;
             f[li] = !interior[k] ? W_BORDER : hole ? W_HOLE : (uint8_t)0;
             fi[li] = hole ? FI_INSIDE : FI_NOHOLE;
             t[li] = 1.0e6f;
@@ -493,21 +558,82 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
             }
             // (reads of this sweep look at W_ROW / W_HOLE only, bits 5 and 6, which the byte stores below never change)
             if (me & (W_BORDER | W_HOLE)) continue;                          // hole pixels are KNOWN for the outside pass
-            if (nb4 & W_HOLE) { f[li] = me | W_SEED; t[li] = 0.f; }
-            else if (a & W_ROW) f[li] = me | W_INSIDE;                       // writes bits 0-1 only
+            if (nb4 & W_HOLE) { f[li] = me | W_SEED; t[li] = 0.f; nband++; }
+            else if (a & W_ROW) { f[li] = me | W_INSIDE; nring++; }          // writes bits 0-1 only
         }
     }
+    for (int o = 32; o; o >>= 1) { nhole += __shfl_xor(nhole, o, 64); nring += __shfl_xor(nring, o, 64); nband += __shfl_xor(nband, o, 64); }
+    if (lane == 0) { atomicAdd(&ctl[MWC_NHOLE], nhole); atomicAdd(&ctl[MWC_NRING], nring); atomicAdd(&ctl[MWC_NBAND], nband); }
     __syncthreads();
     MSTAMP(1);
 
     // ---- the two FMM passes.  They touch disjoint cells apart from the band pixels both start from (ring cells have no hole neighbour,
-    // hole pixels no ring neighbour; band pixels keep T = 0), so their order does not matter
-    bool ok = gp_pass<false>(S, t, f, fi, flist, cells, wh, ww, mg_ww, tid, lane, wave);
+    // hole pixels no ring neighbour; band pixels keep T = 0; the outside pass keeps its states in the flag bytes, the ordering pass in the
+    // fill-number plane, and a rank mark names its pass), so their order does not matter: they run at the same time on their own waves
+    // when the scratch of both fits.  A pass pushes each of its cells (ring cells, hole pixels) at most once, and a generation holds band
+    // pixels or pushed cells only: that sizes its pool and generation
+    nring = ctl[MWC_NRING]; nhole = ctl[MWC_NHOLE]; nband = ctl[MWC_NBAND];
+    GenScratch So, Sh;
+    So.cnt = cntv; So.ctl = ctl;
+    Sh.cnt = cntv + GP_CNT; Sh.ctl = ctl2;
+    const int go = min(GP_GEN, max(nband, nring)), gh = min(GP_GEN, max(nband, nhole));
+    const bool split = (size_t)(nring + nhole + go + gh) * 8 + (size_t)(go + gh) * 4 + GP_GEN * 4 / 8 <= MW_SCRATCH;
+    if (split) {
+        So.pool = (unsigned long long *)regA; So.pcap = nring;
+        Sh.pool = So.pool + nring; Sh.pcap = nhole;
+        So.gen = Sh.pool + nhole; So.gcap = go;
+        Sh.gen = So.gen + go; Sh.gcap = gh;
+        So.dep = (uint32_t *)(Sh.gen + gh);
+        Sh.dep = So.dep + go;
+        Sh.bitmap = Sh.dep + gh;
+        So.bitmap = nullptr;
+    } else {                                                     // one pass after the other in the same scratch
+        So.pool = (unsigned long long *)regA; So.pcap = GP_POOL;
+        So.gen = (unsigned long long *)im; So.gcap = GP_GEN;
+        So.dep = (uint32_t *)(So.gen + GP_GEN);
+        So.bitmap = So.dep + GP_GEN;
+        Sh.pool = So.pool; Sh.pcap = So.pcap; Sh.gen = So.gen; Sh.gcap = So.gcap; Sh.dep = So.dep; Sh.bitmap = So.bitmap;
+    }
+    const int M0 = gp_gen0(So.gen, split ? Sh.gen : nullptr, So.cnt, So.ctl, f, fi, true, cells, lane, wave);
     MSTAMP(2);
-    __syncthreads();
-    if (ok) ok = gp_pass<true>(S, t, f, fi, flist, cells, wh, ww, mg_ww, tid, lane, wave);
+    bool ok = M0 >= 0;
+    if (ok && split) {
+        if (wave < MW_WAVES_OUT) {
+            WaveGroup<true> G{MW_WAVES_OUT * 64, tid, wave, &ctl[MWC_BAR], 0};
+            if (!gp_gens<false, true>(So, G, t, f, fi, flist, M0, wh, ww, mg_ww, lane) && tid == 0) ctl[MWC_FAIL] = 1;
+#ifdef VISTAF_DEBUG
+            if (tid == 0 && b < 1024) g_mw_dbg[b][7] = __builtin_amdgcn_s_memtime();
+#endif
+        } else {
+            WaveGroup<true> G{(MW_WAVES - MW_WAVES_OUT) * 64, tid - MW_WAVES_OUT * 64, wave - MW_WAVES_OUT, &ctl2[MWC_BAR], 0};
+            if (!gp_gens<true, true>(Sh, G, t, f, fi, flist, M0, wh, ww, mg_ww, lane) && G.tid == 0) ctl2[MWC_FAIL] = 1;
+#ifdef VISTAF_DEBUG
+            if (G.tid == 0 && b < 1024) g_mw_dbg[b][8] = __builtin_amdgcn_s_memtime();
+#endif
+        }
+        __syncthreads();
+        ok = !ctl[MWC_FAIL] && !ctl2[MWC_FAIL];
+    } else if (ok) {
+        WaveGroup<false> G{MW_T, tid, wave, nullptr, 0};
+        ok = gp_gens<false, false>(So, G, t, f, fi, flist, M0, wh, ww, mg_ww, lane);
+#ifdef VISTAF_DEBUG
+        if (tid == 0 && b < 1024) g_mw_dbg[b][7] = __builtin_amdgcn_s_memtime();
+#endif
+        __syncthreads();
+        if (ok) {
+            // the band pixels again (their ordering-pass marks are still in place)
+            const int M1 = gp_gen0(Sh.gen, nullptr, Sh.cnt, Sh.ctl, f, fi, false, cells, lane, wave);
+            ok = M1 >= 0 && gp_gens<true, false>(Sh, G, t, f, fi, flist, M1, wh, ww, mg_ww, lane);
+        }
+#ifdef VISTAF_DEBUG
+        if (tid == 0 && b < 1024) g_mw_dbg[b][8] = __builtin_amdgcn_s_memtime();
+#endif
+    }
     MSTAMP(3);
-    const int nfill = ctl[MWC_NFILL];
+#ifdef VISTAF_DEBUG
+    if (tid == 0 && b < 1024) g_mw_dbg[b][9] = split;
+#endif
+    const int nfill = ctl2[MWC_NFILL];
     if (!ok || nfill > MW_FILLS) { if (tid == 0) fb[b] = 1; return; }     // nothing has been written back: the single-wave tier marches this frame
     __syncthreads();
 
@@ -544,7 +670,7 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
             uint32_t cnt = 0;
             for (int dk = -D; dk <= D; dk++) {
                 const uint16_t *row = fi + pi + dk * ww;
-                for (int dl = -D; dl <= D; dl++) cnt += row[dl] < (unsigned)k ? 1u : 0u;       // FI_NOHOLE is not
+                for (int dl = -D; dl <= D; dl++) cnt += row[dl] < (unsigned)k ? 1u : 0u;       // FI_NOHOLE and the band pixels' spent marks are not
             }
             dep[k] = cnt;
             if (cnt == 0) { const int slot = atomicAdd(&ctl[MWC_TAIL], 1); rq[slot] = (uint32_t)k | ((uint32_t)pi << 16); }
@@ -595,20 +721,32 @@ void telea_window_mw_debug_dump(int B)
 {
     static unsigned long long hbuf[1024][16];
     if (hipMemcpyFromSymbol(hbuf, HIP_SYMBOL(g_mw_dbg), sizeof(hbuf)) != hipSuccess) return;
-    int worst = 0;
-    double mean = 0;
+    // per frame: flags+ring, generation 0, outside pass, ordering pass (from its start: the end of generation 0 when the passes run at the same
+    // time, the end of the outside pass when they do not), both passes, image+counters, fills, total
+    const char *names[8] = {"flags+ring", "gen0", "outside", "ordering", "both passes", "image+counters", "fills", "total"};
+    std::vector<std::vector<double>> ph(8);
+    int nsplit = 0, n = 0;
     for (int b = 0; b < B && b < 1024; b++) {
-        if (hbuf[b][6] - hbuf[b][0] > hbuf[worst][6] - hbuf[worst][0]) worst = b;
-        mean += (double)(hbuf[b][6] - hbuf[b][0]) / B;
+        const unsigned long long *x = hbuf[b];
+        if (x[6] <= x[0] || x[3] < x[2]) continue;       // frames without hole pixels, or handed to another tier
+        const bool sp = x[9] != 0;
+        nsplit += sp;
+        n++;
+        const double v[8] = {(double)(x[1] - x[0]), (double)(x[2] - x[1]), (double)(x[7] - x[2]), (double)(x[8] - (sp ? x[2] : x[7])), (double)(x[3] - x[2]),
+                             (double)(x[4] - x[3]), (double)(x[5] - x[4]), (double)(x[6] - x[0])};
+        for (int i = 0; i < 8; i++) ph[i].push_back(v[i]);
     }
-    for (int b : {0, worst}) {
-        unsigned long long *x = hbuf[b];
-        printf("[telea mw dbg] frame %d cycles: flags+ring %llu | outside pass %llu | ordering pass %llu | image+negate+counters %llu | fills %llu | "
-               "write back %llu | fills %llu cells %llu | mean total over frames %.0f || both passes, %llu generation changes: marks+counters %llu | pops %llu | "
-               "numbering %llu | min+select+sort %llu\n",
-               b, x[1] - x[0], x[2] - x[1], x[3] - x[2], x[4] - x[3], x[5] - x[4], x[6] - x[5], x[10] >> 32, x[10] & 0xffffffffull, mean, x[15], x[11], x[12], x[13],
-               x[14]);
+    if (!n) return;
+    printf("[telea mw dbg] %d frames (%d with concurrent passes) cycles median / max:", n, nsplit);
+    for (int i = 0; i < 8; i++) {
+        std::vector<double> &v = ph[i];
+        std::sort(v.begin(), v.end());
+        printf(" %s %.0f / %.0f%s", names[i], v[v.size() / 2], v.back(), i < 7 ? " |" : "\n");
     }
+    const unsigned long long *x = hbuf[0];
+    printf("[telea mw dbg] frame 0: fills %llu cells %llu; generations (the outside pass only when concurrent) %llu: marks+counters %llu | pops %llu | "
+           "numbering %llu | min+select+rank %llu\n",
+           x[10] >> 32, x[10] & 0xffffffffull, x[15], x[11], x[12], x[13], x[14]);
 }
 #endif
 
