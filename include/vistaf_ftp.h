@@ -135,6 +135,27 @@ typedef struct vistaf_ftp_config {
 #define VISTAF_S_BAD_PIXELS 14       /* shape_ftp.py:826 count */
 #define VISTAF_S_RESERVED 15
 
+/* per-contact record written by vistaf_ftp_contacts: d_contacts[(b*max_contacts + k)*VISTAF_NCONTACT + i] (double).  An extension: the
+ * reference reports one volume / area / depth / force per frame (the scalars above) and has no per-contact counterpart. */
+#define VISTAF_NCONTACT 16
+#define VISTAF_CONTACT_PIXELS 0          /* pixels of the component                                               */
+#define VISTAF_CONTACT_CONTACT_PIXELS 1  /* pixels of it with depth > depth_eps_mm (float32 compare, as the tail)  */
+#define VISTAF_CONTACT_AREA_MM2 2        /* contact pixels * mm_per_px^2                                           */
+#define VISTAF_CONTACT_VOLUME_CM3 3      /* float32(sum of depth over the contact pixels) * mm_per_px^2 / 1000     */
+#define VISTAF_CONTACT_MAX_DEPTH_MM 4    /* maximum of depth over the component                                    */
+#define VISTAF_CONTACT_ARGMAX_INDEX 5    /* row-major index of the first pixel that attains it                     */
+#define VISTAF_CONTACT_CENTROID_X 6      /* depth-weighted mean x over the contact pixels (crop coordinates); NaN without contact pixels */
+#define VISTAF_CONTACT_CENTROID_Y 7
+#define VISTAF_CONTACT_FORCE_N 8         /* the session's force curve evaluated at THIS contact's volume: what the reference would report had
+                                          * the contact been alone in the frame.  The curve is not linear, so the contacts' forces do not add
+                                          * up to the frame's VISTAF_S_FORCE_N. */
+#define VISTAF_CONTACT_BBOX_X0 9         /* bounding box of the component, inclusive */
+#define VISTAF_CONTACT_BBOX_Y0 10
+#define VISTAF_CONTACT_BBOX_X1 11
+#define VISTAF_CONTACT_BBOX_Y1 12
+                                         /* 13..15 reserved (NaN) */
+#define VISTAF_MAX_CONTACTS 64
+
 /* reference-frame info returned by vistaf_ftp_get_reference_info: out[0..7] =
  * peak_x_refined, peak_y_refined, kx, ky, fft_h, fft_w, estimated_period_px, mm_per_px */
 #define VISTAF_NREFINFO 8
@@ -182,6 +203,19 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
 /* Reference-frame info of the samples of the last predict_pairs: out[b*VISTAF_NREFINFO + i], fields as
  * vistaf_ftp_get_reference_info.  Synchronises `stream`. */
 int vistaf_ftp_get_pair_info(vistaf_ftp_handle *hd, int batch, double *out, void *stream);
+
+/* Per-contact table of the last predict_batch / predict_pairs (`batch` must be that call's batch).  A contact is one 8-connected component
+ * of the blob filter's kept mask (shape_ftp.py:1215-1271, the "contact_kept_by_depth" plane); the table is a second read-out of planes the
+ * session still holds and changes none of them.  Per frame the contacts are ordered by maximum depth, descending, ties by the index of the
+ * arg-max pixel, ascending -- row 0 is the contact of the frame's VISTAF_S_ARGMAX_DEPTH_INDEX pixel.  Outputs (device):
+ *   d_contacts      [B, max_contacts, VISTAF_NCONTACT] double: the first max_contacts contacts in that order, unused rows all NaN
+ *   d_count         [B] int32: number of contacts of the frame whatever max_contacts is (count > max_contacts: the table is truncated)
+ *   d_contact_index [B,h,w] int8 or NULL: row of the contact a pixel belongs to, -1 elsewhere (pixels of the contacts beyond max_contacts too)
+ * A frame whose status is not VISTAF_FRAME_OK has count 0 and NaN rows.  Two calls on the same state give the same bits.
+ * VISTAF_E_STATE before any predict or when `batch` differs from the last predict's; VISTAF_E_INVALID for max_contacts outside
+ * 1..VISTAF_MAX_CONTACTS or a NULL d_contacts / d_count.  Asynchronous on `stream`; allocates nothing. */
+int vistaf_ftp_contacts(vistaf_ftp_handle *hd, int batch, int max_contacts, double *d_contacts, int32_t *d_count,
+                        int8_t *d_contact_index, void *stream);
 
 /* Copy a named intermediate plane of the last predict_batch (parity tests / debugging) into d_dst.
  * Returns the number of bytes per frame through *bytes_per_frame; d_dst may be NULL to query. */

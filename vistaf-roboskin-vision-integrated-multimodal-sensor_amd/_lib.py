@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libvistaf_ftp.so")
 
 NSCALARS = 16
 NREFINFO = 8
+NCONTACT = 16           # doubles per row of the per-contact table (VISTAF_NCONTACT)
+MAX_CONTACTS = 64
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
@@ -21,7 +23,7 @@ CURVE_TYPES = {"linear0": 0, "linear": 1, "poly2": 2, "sat_exp": 3, "growth": 4,
 EXPORTS = [
     "vistaf_ftp_abi_version", "vistaf_ftp_last_error", "vistaf_ftp_default_config", "vistaf_ftp_create",
     "vistaf_ftp_set_reference", "vistaf_ftp_get_reference_info", "vistaf_ftp_predict_batch", "vistaf_ftp_predict_pairs",
-    "vistaf_ftp_get_pair_info",
+    "vistaf_ftp_get_pair_info", "vistaf_ftp_contacts",
     "vistaf_ftp_get_intermediate", "vistaf_ftp_stage_count", "vistaf_ftp_stage_name",
     "vistaf_ftp_enable_stage_timing", "vistaf_ftp_get_stage_times", "vistaf_ftp_destroy",
     "vistaf_depth_map_to_volume", "vistaf_predict_force_from_volume",
@@ -105,6 +107,7 @@ def load():
     lib.vistaf_ftp_predict_batch.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.vistaf_ftp_predict_pairs.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
     lib.vistaf_ftp_get_pair_info.argtypes = [vp, ci, ctypes.POINTER(cd), vp]
+    lib.vistaf_ftp_contacts.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     lib.vistaf_ftp_get_intermediate.argtypes = [vp, ctypes.c_char_p, vp, ci, ctypes.POINTER(ctypes.c_size_t), vp]
     lib.vistaf_ftp_stage_count.restype = ci
     lib.vistaf_ftp_stage_name.restype = ctypes.c_char_p

@@ -99,6 +99,11 @@ struct vistaf_ftp_handle {
     double *scalars;
     float *req_hi, *req_g, *req_med, *req_amp, *req_contact, *req_core;   // device percentile requests
 
+    // per-contact read-out (vistaf_ftp_contacts): buffers sized by max_batch, and what the last predict was
+    ContactScratch contacts_ws{};
+    int last_batch = 0;                 // 0: no predict yet
+    bool last_pairs = false;
+
     bool timing = false;
     hipEvent_t ev[ST_COUNT + 1];
     bool ev_made = false;
@@ -419,6 +424,12 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     TRY(dalloc(hd, &hd->big_only, mb));
     TRY(dalloc(hd, &hd->scalars, mb * VISTAF_NSCALARS));
     TRY(dalloc(hd, &hd->hole_med, mb)); TRY(dalloc(hd, &hd->hole_fill, mb));
+    {
+        ContactScratch &cs = hd->contacts_ws;
+        cs.cap = contact_root_capacity(h, w);
+        TRY(dalloc(hd, &cs.arg, n)); TRY(dalloc(hd, &cs.list, mb * cs.cap)); TRY(dalloc(hd, &cs.nroots, mb)); TRY(dalloc(hd, &cs.nsel, mb));
+        TRY(dalloc(hd, &cs.selkey, mb * VISTAF_MAX_CONTACTS)); TRY(dalloc(hd, &cs.part, contact_part_words(max_batch, P)));
+    }
     hd->named["mu"] = {hd->mu, sizeof(float)}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float)}; hd->named["thr_g"] = {hd->thr_g, sizeof(float)};
     hd->named["coef"] = {hd->coef, 6 * sizeof(float)}; hd->named["thr3"] = {hd->thr3, 3 * sizeof(float)};
     hd->named["core_thr"] = {hd->core_thr, sizeof(float)}; hd->named["core_med"] = {hd->core_med, sizeof(float)};
@@ -695,6 +706,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
 #endif
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
+    hd->last_batch = B; hd->last_pairs = pair_geom != nullptr;
     return 0;
 }
 
@@ -792,6 +804,23 @@ int vistaf_ftp_get_pair_info(vistaf_ftp_handle *hd, int batch, double *out /* [b
         o[0] = g[b].peak_x; o[1] = g[b].peak_y; o[2] = g[b].kx; o[3] = g[b].ky; o[4] = hd->Hf; o[5] = hd->Wf; o[6] = g[b].period;
         o[7] = g[b].period > 1e-12 ? hd->cfg.grating_pitch_mm / g[b].period : 0.0;
     }
+    return 0;
+}
+
+int vistaf_ftp_contacts(vistaf_ftp_handle *hd, int B, int max_contacts, double *d_contacts, int32_t *d_count, int8_t *d_contact_index, void *stream)
+{
+    if (!hd || !d_contacts || !d_count) return fail(VISTAF_E_INVALID, "null argument");
+    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return fail(VISTAF_E_INVALID, "max_contacts must be 1..64");
+    if (hd->last_batch == 0) return fail(VISTAF_E_STATE, "no predict_batch / predict_pairs before contacts");
+    if (B != hd->last_batch) return fail(VISTAF_E_STATE, "batch differs from the last predict's");
+    const vistaf_ftp_config &c = hd->cfg;
+    PostParams pp;      // as the tail takes them
+    pp.mm_per_px = hd->mm_per_px; pp.depth_eps_mm = c.depth_eps_mm; pp.period_px = hd->period; pp.force_curve = hd->fcurve;
+    pp.pair_geom = hd->last_pairs ? hd->pgeom : nullptr; pp.grating_pitch_mm = c.grating_pitch_mm;
+    launch_contacts(hd->depth, hd->kept, hd->labels, hd->peak_bits, hd->status, pp, hd->contacts_ws, max_contacts, d_contacts, VISTAF_NCONTACT, d_count,
+                    d_contact_index, B, hd->h, hd->w, (hipStream_t)stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -192,6 +192,21 @@ void launch_mark_empty(const int *rel_count, int32_t *status, int B, hipStream_t
 void launch_copy_out(const float *depth, const uint8_t *reliable, const int32_t *status, float *out_h, uint8_t *out_r, int B, int P,
                      hipStream_t st);
 
+// ---- k_contacts.hip (per-contact read-out of the planes a predict leaves behind: vistaf_ftp_contacts) ------------------------------------
+struct ContactScratch {
+    int32_t *arg;                    // [B, P] by root: first pixel of the component's peak, then the contact's row (-1 beyond max_contacts)
+    int32_t *list; int cap;          // [B, cap] kept roots of the frame, cap = contact_root_capacity(h, w)
+    int *nroots, *nsel;              // [B] kept roots found / contacts of the frame (0 for a frame whose status is not OK)
+    unsigned long long *selkey;      // [B, 64] peak bits << 32 | ~argmax of the ranked contacts
+    unsigned long long *part;        // contact_part_words(max_batch, P) partial records
+};
+int contact_root_capacity(int h, int w);
+size_t contact_part_words(int max_batch, int P);
+// contacts [B, K, nfield] double (nfield >= 13, fields as VISTAF_CONTACT_*), count [B], index [B, P] int8 or null
+void launch_contacts(const float *depth, const uint8_t *kept, const int32_t *labels, const unsigned int *peak_bits, const int32_t *status,
+                     PostParams pp, const ContactScratch &cs, int K, double *contacts, int nfield, int32_t *count, int8_t *index, int B, int h, int w,
+                     hipStream_t st);
+
 // ---- k_big.hip (large frames: selection and IRLS fit as chains of streaming kernels over all pixels of the batch)
 size_t big_scratch_bytes(int B, int h, int w);
 bool big_frames(int B, int P);

@@ -30,6 +30,11 @@ SCALAR_NAMES = [
     "mm_per_px", "min_height_unitless", "argmin_unitless_index", "reliable_count", "sign_flipped", "amp_threshold",
     "contact_threshold", "bg_median", "bad_pixels", "reserved",
 ]
+# fields of a row of the per-contact table, in the order of the VISTAF_CONTACT_* indices (include/vistaf_ftp.h); 13..15 are reserved
+CONTACT_NAMES = [
+    "pixels", "contact_pixels", "contact_area_mm2", "volume_cm3", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y", "force_N",
+    "bbox_x0", "bbox_y0", "bbox_x1", "bbox_y1",
+]
 
 
 def load_calibration(json_path: str) -> Tuple[Dict[str, Any], bool]:
@@ -263,6 +268,29 @@ class FtpSensor:
             _lib.check(self._lib.vistaf_ftp_get_pair_info(self._h, batch, info, _stream_ptr(self.device)))
         return [self._info_dict(info, b * _lib.NREFINFO) for b in range(batch)]
 
+    def contacts(self, max_contacts: int = 8, index_plane: bool = False) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict_batch / predict_pairs (vistaf_ftp_contacts; an extension, the reference has no
+        counterpart).  A contact is one 8-connected component of the `contact_kept_by_depth` mask; per frame they are ordered by maximum
+        depth, descending.  Returns device tensors: contacts [B,K,16] f64 (fields CONTACT_NAMES, unused rows NaN), count [B] i32 (all
+        contacts of the frame, also when more than K) and, with index_plane, contact_index [B,h,w] i8 (row of the pixel's contact, else -1).
+        `force_N` of a row is the force curve at that contact's own volume; the curve is not linear, the rows do not add up to the frame's."""
+        last = getattr(self, "_last_out", None)
+        if last is None:
+            raise RuntimeError("contacts() needs a previous predict_batch / predict_pairs")
+        b, k = int(last["status"].shape[0]), int(max_contacts)
+        if not 1 <= k <= _lib.MAX_CONTACTS:
+            raise ValueError(f"max_contacts must be 1..{_lib.MAX_CONTACTS}")
+        out = {
+            "contacts": torch.empty((b, k, _lib.NCONTACT), dtype=torch.float64, device=self.device),
+            "count": torch.empty((b,), dtype=torch.int32, device=self.device),
+        }
+        if index_plane:
+            out["contact_index"] = torch.empty((b, self.h, self.w), dtype=torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.vistaf_ftp_contacts(self._h, b, k, out["contacts"].data_ptr(), out["count"].data_ptr(),
+                                                     out["contact_index"].data_ptr() if index_plane else None, _stream_ptr(self.device)))
+        return out
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -314,10 +342,12 @@ class FtpSensor:
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
-    def predict(self, image) -> Optional[Dict[str, Any]]:
+    def predict(self, image, contacts: Optional[int] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
-        Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679)."""
+        Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
+        contacts=K adds a "contacts" key: the frame's (at most K) contacts as dicts of CONTACT_NAMES plus `centroid_xy`, `argmax_xy` and
+        `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars."""
         o = self.predict_batch(image)
         torch.cuda.synchronize(self.device)
         status = int(o["status"][0].item())
@@ -338,6 +368,17 @@ class FtpSensor:
                 res[name] = float(s[i])
         res["argmax_depth_index"] = int(s[4])
         res["argmin_unitless_index"] = int(s[8])
+        if contacts is not None:
+            from .writers import contacts_table
+            c = self.contacts(int(contacts))
+            rows = contacts_table(c["contacts"].cpu().numpy(), c["count"].cpu().numpy())
+            for r in rows:
+                r.pop("frame")
+                r["centroid_xy"] = (r["centroid_x"], r["centroid_y"])
+                r["argmax_xy"] = (r["argmax_index"] % self.w, r["argmax_index"] // self.w)
+                r["bbox"] = (r["bbox_x0"], r["bbox_y0"], r["bbox_x1"], r["bbox_y1"])
+            res["contacts"] = rows
+            res["contact_count"] = int(c["count"][0].item())
         return res
 
 

@@ -10,6 +10,10 @@
 * `multimodal_summary` / `write_multimodal_summary` -- `Code/multimodal_sensor.py:592-650` with its metric extractors (:214-280): the
   `multimodal_summary.json` of a combined force + temperature session (same keys, order and nesting).
 
+* `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
+  `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
+  it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
+
 These functions take NumPy arrays (what `FtpSensor.predict` / `FtpSensor.masks` return); nothing here touches the GPU.
 """
 from __future__ import annotations
@@ -26,6 +30,10 @@ CROP_MASK_KEYS = ("roi_eroded", "reliable", "output_reliable", "circ_mask", "con
                   "contact_dilated")                                                    # shape_ftp.py:1898-1906, in that order
 RESULT_CSV_FIELDS = ("reference_path", "deformed_path", "volume_cm3", "force_N", "contact_area_mm2", "max_depth_mm", "mm_per_px",
                      "estimated_grating_period_px", "ftp_output_dir", "force_model_type")   # force_sensor.py:269-280
+CONTACT_FIELDS = ("pixels", "contact_pixels", "contact_area_mm2", "volume_cm3", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
+                  "force_N", "bbox_x0", "bbox_y0", "bbox_x1", "bbox_y1")                  # VISTAF_CONTACT_* order (include/vistaf_ftp.h)
+CONTACT_INT_FIELDS = ("pixels", "contact_pixels", "argmax_index", "bbox_x0", "bbox_y0", "bbox_x1", "bbox_y1")
+CONTACTS_CSV_FIELDS = ("frame", "contact") + CONTACT_FIELDS
 
 
 def _safe_float(x, default):
@@ -81,6 +89,50 @@ def write_result_csv(output_dir: str, record: Mapping[str, Any]) -> str:
         row = {k: record[k] for k in RESULT_CSV_FIELDS if k != "force_model_type"}
         row["force_model_type"] = record["force_model"].get("type", "")
         w.writerow(row)
+    return path
+
+
+def contacts_table(contacts, count) -> list:
+    """Row dicts of the per-contact table: contacts [B,K,>=13] (or [K,>=13] for one frame) float64 as `FtpSensor.contacts` returns it, count
+    [B] (or a scalar).  One dict per written contact, frames in order, contacts in the table's order (deepest first): `frame`, `contact`
+    and CONTACT_FIELDS, the counts / indices / box as ints.  A frame with count > K contributes its K written rows (the table is
+    truncated there, which `count` shows); NaN rows are skipped."""
+    c = np.asarray(contacts, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if c.ndim == 2:
+        c = c[None]
+    if c.ndim != 3 or c.shape[2] < len(CONTACT_FIELDS) or c.shape[0] != n.shape[0]:
+        raise ValueError("contacts must be [B,K,>=13] with count [B]")
+    rows = []
+    for b in range(c.shape[0]):
+        for k in range(min(int(n[b]), c.shape[1])):
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(CONTACT_FIELDS):
+                row[name] = int(c[b, k, i]) if name in CONTACT_INT_FIELDS else float(c[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def contacts_record(contacts, count) -> Dict[str, Any]:
+    """{"contact_count": [per frame], "contacts": [row dicts]} for a JSON document of the caller's own (never result.json, whose schema is
+    the reference's).  A NaN centroid (a contact without a pixel above depth_eps_mm) becomes null."""
+    rows = contacts_table(contacts, count)
+    for r in rows:
+        for k, v in r.items():
+            if isinstance(v, float) and not math.isfinite(v):
+                r[k] = None
+    return {"contact_count": [int(v) for v in np.atleast_1d(np.asarray(count))], "contacts": rows}
+
+
+def write_contacts_csv(output_dir: str, contacts, count, filename: str = "contacts.csv") -> str:
+    """contacts.csv: one line per written contact, columns CONTACTS_CSV_FIELDS, floats with repr() (they read back to the same doubles)."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(CONTACTS_CSV_FIELDS))
+        w.writeheader()
+        for row in contacts_table(contacts, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
     return path
 
 
