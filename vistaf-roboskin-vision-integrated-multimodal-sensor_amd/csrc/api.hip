@@ -190,6 +190,9 @@ void blur(vistaf_ftp_handle *hd, const float *src, float *dst, const GKern &g, i
     launch_gauss_blur(src, hd->tmpf, dst, g.d, g.k, B, hd->h, hd->w, st);
 }
 
+// whether the element-wise passes around this blur run inside its tile (k_blurchain.hip): short kernels only, Tiers::fused_chains
+bool fuses(const vistaf_ftp_handle *hd, const GKern &g) { return hd->tiers.fused_chains && g.k > 0 && g.k <= GF_MAXK; }
+
 float q32_of(double pct) { return (float)pct / 100.0f; }   // np.true_divide(q, float32(100))
 
 int upload_req(vistaf_ftp_handle *hd, float **d, const std::vector<float> &v)
@@ -258,10 +261,13 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     } else if (timed) hipEventRecord(hd->ev[ST_INPAINT], st);
     if (timed) hipEventRecord(hd->ev[ST_PREPROC], st);
     blur(hd, hd->img, hd->blurA, hd->g_illum, B, st);
-    launch_illum_norm(hd->img, hd->blurA, hd->inorm, B, P, st);
-    const float *in = hd->inorm;
-    if (hd->g_pre.k) { blur(hd, hd->inorm, hd->blurA, hd->g_pre, B, st); in = hd->blurA; }
-    launch_mul_static(in, hd->apo, hd->iw, B, P, st);
+    if (fuses(hd, hd->g_pre)) launch_illum_pre_apod(hd->img, hd->blurA, hd->apo, hd->iw, hd->g_pre.d, hd->g_pre.k, B, h, w, st);
+    else {
+        launch_illum_norm(hd->img, hd->blurA, hd->inorm, B, P, st);
+        const float *in = hd->inorm;
+        if (hd->g_pre.k) { blur(hd, hd->inorm, hd->blurA, hd->g_pre, B, st); in = hd->blurA; }
+        launch_mul_static(in, hd->apo, hd->iw, B, P, st);
+    }
     launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
 }
 
@@ -634,7 +640,8 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // ---- reliable-only smoothing + sign flip (shape_ftp.py:1753-1768)
     if (timed) hipEventRecord(hd->ev[ST_SMOOTH_FLIP], st);
     const bool smooth_rel = hd->g_rel.k > 0;
-    if (smooth_rel) {
+    if (fuses(hd, hd->g_rel)) launch_smooth_reliable(hd->detr, hd->bg_med, hd->reliable, hd->hmap, hd->g_rel.d, hd->g_rel.k, B, h, w, st);
+    else if (smooth_rel) {
         launch_sub_scalar_mask(hd->detr, hd->bg_med, hd->reliable, hd->z0, hd->mplane, B, P, st);
         blur(hd, hd->z0, hd->num, hd->g_rel, B, st);
         blur(hd, hd->mplane, hd->den, hd->g_rel, B, st);
@@ -673,14 +680,21 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // second one lands in planes that are idle at this point (`area` as the integer temporary, `depth` -- written by to_mm below)
     if (use_band) launch_chamfer_pair(orel, hd->rowdist, hd->dist, hd->area, hd->depth, B, h, w, c.frontier_zero_band_px + 2, st, hd->tiers.chamfer_twopass != 0);
     else HIPCHK(hipMemsetAsync(hd->dist, 0x7f, (size_t)B * P * sizeof(float), st));   // huge distance: taper weight 1
-    launch_frontier_compose(hd->hmap, orel, hd->roi, hd->dist, use_band ? band : 1.0f, hd->z0f, B, P, st);
-    if (hd->g_unrel.k) blur(hd, hd->z0f, hd->snum, hd->g_unrel, B, st);
-    launch_finalize_unitless(hd->z0f, hd->g_unrel.k ? hd->snum : nullptr, hd->roi_den, orel, hd->roi, use_band ? hd->depth : hd->dist, band, use_band ? 1 : 0,
-                             hd->unitless, B, P, st);
+    const bool fuse_compose = fuses(hd, hd->g_unrel);      // then the mm curve runs in the same kernel and counts as composition
+    if (fuse_compose)
+        launch_compose_finalize_mm(hd->hmap, orel, hd->roi, hd->dist, use_band ? band : 1.0f, hd->roi_den, use_band ? hd->depth : hd->dist, band,
+                                   use_band ? 1 : 0, hd->hcurve, hd->use_neg, hd->unitless, hd->depth, hd->cand, hd->gmax, hd->g_unrel.d, hd->g_unrel.k,
+                                   B, h, w, st);
+    else {
+        launch_frontier_compose(hd->hmap, orel, hd->roi, hd->dist, use_band ? band : 1.0f, hd->z0f, B, P, st);
+        if (hd->g_unrel.k) blur(hd, hd->z0f, hd->snum, hd->g_unrel, B, st);
+        launch_finalize_unitless(hd->z0f, hd->g_unrel.k ? hd->snum : nullptr, hd->roi_den, orel, hd->roi, use_band ? hd->depth : hd->dist, band, use_band ? 1 : 0,
+                                 hd->unitless, B, P, st);
+    }
 
     // ---- unitless -> mm, blob filter (shape_ftp.py:1850-1873)
     if (timed) hipEventRecord(hd->ev[ST_MM_BLOB], st);
-    launch_to_mm(hd->unitless, hd->roi, hd->hcurve, hd->use_neg, hd->depth, hd->cand, hd->gmax, B, P, st);
+    if (!fuse_compose) launch_to_mm(hd->unitless, hd->roi, hd->hcurve, hd->use_neg, hd->depth, hd->cand, hd->gmax, B, P, st);
     launch_cc_label(hd->cand, hd->labels, B, h, w, st);
     launch_blob_filter(hd->depth, hd->cand, hd->labels, hd->peak_bits, hd->gmax, c.contact_blob_min_peak_mm,
                        c.contact_blob_min_peak_rel_frac, hd->kept, B, P, st);
@@ -866,6 +880,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "big_fallback") hd->tiers.big_fallback = value != 0;
     else if (n == "unwrap_fast") hd->tiers.unwrap_fast = value != 0;
     else if (n == "big_chain") hd->tiers.big_chain = value != 0;
+    else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
     else return fail(VISTAF_E_INVALID, "unknown test hook or value: " + n);
     return 0;

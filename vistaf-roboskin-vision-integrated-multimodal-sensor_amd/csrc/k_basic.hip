@@ -6,6 +6,8 @@
 //   gauss_rows/cols cv2.GaussianBlur((0,0), sigma) REFLECT_101  (shape_ftp.py:746, :831, :836, :1145-1146)
 //   illum_norm     I/(blur+1e-6) - 1                            (shape_ftp.py:832)
 #include "kernels.hpp"
+#include "gauss_tile.hpp"
+#include "pixel_ops.hpp"
 
 namespace vf {
 
@@ -358,34 +360,7 @@ __global__ __launch_bounds__(256) void k_gauss_rows(const float *__restrict__ sr
     }
 }
 
-// Column pass: cv::SymmColumnFilter's symmetric form, s = k[r]*S[y]; s = fma(k[r+j], S[y+j] + S[y-j], s) for j = 1..r (the order the
-// parity tests' CPU restatement executes too: same operations in the same order, so the same bits).  Each thread produces
-// GC_R consecutive rows of one column; lanes run along x so every row read is coalesced.  The two source rows a step needs for its GC_R
-// outputs are the previous step's shifted by one row, so a step costs two new reads (register windows `up` / `dn`).
-constexpr int GC_R = 8;
-
-template <class Load>
-__device__ inline void gauss_col_symm(Load ld, const float *__restrict__ kern, int r, float (&acc)[GC_R])
-{
-    // ld(i): source value i rows below the centre of output 0 (i in [-r, GC_R - 1 + r])
-    float up[GC_R], dn[GC_R];
-    const float kc = kern[r];
-#pragma unroll
-    for (int o = 0; o < GC_R; o++) { const float v = ld(o); acc[o] = __fmul_rn(kc, v); up[o] = v; dn[o] = v; }
-    for (int j = 1; j <= r; j++) {
-        const float nu = ld(GC_R - 1 + j), nd = ld(-j);
-#pragma unroll
-        for (int o = 0; o < GC_R - 1; o++) up[o] = up[o + 1];
-        up[GC_R - 1] = nu;
-#pragma unroll
-        for (int o = GC_R - 1; o > 0; o--) dn[o] = dn[o - 1];
-        dn[0] = nd;
-        const float kj = kern[r + j];
-#pragma unroll
-        for (int o = 0; o < GC_R; o++) acc[o] = fmaf(kj, __fadd_rn(up[o], dn[o]), acc[o]);
-    }
-}
-
+// Column pass: gauss_col_symm (gauss_tile.hpp), GC_R consecutive rows of one column per thread.
 // global-memory form (kernels too long for the LDS tile)
 __global__ __launch_bounds__(256) void k_gauss_cols(const float *__restrict__ src, float *__restrict__ dst,
                                                     const float *__restrict__ kern, int ksize, int h, int w)
@@ -444,67 +419,24 @@ void launch_gauss_cols(const float *src, float *dst, const float *kern, int ksiz
     hipLaunchKernelGGL(k_gauss_cols, grid, dim3(256), 0, st, src, dst, kern, ksize, h, w);
 }
 
-// Both passes in one kernel for short kernels (ksize <= GF_MAXK): a 64 x 32 output tile with its halo goes through LDS once -- row pass
-// into a second LDS plane (rounded to float exactly as the intermediate plane of the two-kernel path is), column pass out of it -- so the
-// intermediate plane never travels to memory.  Same taps, same order of the operations per output: same bits as the two kernels.
-constexpr int GF_TX = 64, GF_TY = 32, GF_MAXK = 15;
+// Both passes in one kernel for short kernels (ksize <= GF_MAXK): the tile body of gauss_tile.hpp with nothing in front and nothing behind.
+template <int RMAX>
 __global__ __launch_bounds__(256) void k_gauss_fused(const float *__restrict__ src, float *__restrict__ dst, const float *__restrict__ kern,
                                                      int ksize, int h, int w)
 {
-    __shared__ float in_t[(GF_TY + GF_MAXK - 1) * (GF_TX + GF_MAXK - 1)];
-    __shared__ float mid_t[(GF_TY + GF_MAXK - 1) * GF_TX];
-    const int r = ksize / 2;
-    const int tw = GF_TX + 2 * r, th = GF_TY + 2 * r;
-    const int x0 = blockIdx.x * GF_TX, y0 = blockIdx.y * GF_TY;
-    const size_t b = blockIdx.z;
-    const float *plane = src + b * (size_t)h * w;
-    // tile with halo: a wave per tile row, the lane's (at most two) source columns reflected once
-    {
-        const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        const int sx0 = reflect101(x0 + lane - r, w), sx1 = reflect101(x0 + lane + 64 - r, w);
-        const bool two = lane + 64 < tw;
-        for (int ty = wv; ty < th; ty += 4) {
-            const float *row = plane + (size_t)reflect101(y0 + ty - r, h) * w;
-            in_t[ty * tw + lane] = row[sx0];
-            if (two) in_t[ty * tw + lane + 64] = row[sx1];
-        }
-    }
-    __syncthreads();
-    // row pass: th rows x 64 columns, FOUR adjacent outputs per thread out of one sliding window of taps (ksize + 3 LDS reads instead of
-    // 4 ksize); every output is still  s = k[0] S[0]; s = fma(k[j], S[j], s)  in ascending j
-    for (int q = threadIdx.x; q < th * 16; q += 256) {
-        const int ty = q >> 4, tx = (q & 15) * 4;
-        const float *t = in_t + ty * tw + tx;
-        float v0 = t[0], v1 = t[1], v2 = t[2], v3 = t[3];
-        const float k0 = kern[0];
-        float a0 = k0 * v0, a1 = k0 * v1, a2 = k0 * v2, a3 = k0 * v3;
-        for (int j = 1; j < ksize; j++) {
-            v0 = v1; v1 = v2; v2 = v3; v3 = t[j + 3];
-            const float kj = kern[j];
-            a0 = fmaf(kj, v0, a0); a1 = fmaf(kj, v1, a1); a2 = fmaf(kj, v2, a2); a3 = fmaf(kj, v3, a3);
-        }
-        float *m = mid_t + ty * GF_TX + tx;
-        m[0] = a0; m[1] = a1; m[2] = a2; m[3] = a3;
-    }
-    __syncthreads();
-    // column pass: symmetric sum over GC_R output rows of one column (gauss_col_symm)
-    const int tx = threadIdx.x & 63, tg = threadIdx.x >> 6;
-    const int x = x0 + tx, yb = y0 + tg * GC_R;
-    if (x >= w || yb >= h) return;
-    const float *tc = mid_t + (tg * GC_R + r) * GF_TX + tx;
-    float acc[GC_R];
-    gauss_col_symm([&](int i) { return tc[i * GF_TX]; }, kern, r, acc);
-#pragma unroll
-    for (int o = 0; o < GC_R; o++)
-        if (yb + o < h) dst[b * (size_t)h * w + (size_t)(yb + o) * w + x] = acc[o];
+    __shared__ __align__(16) GaussTile<RMAX, 1> tile;
+    const size_t P = (size_t)h * w;
+    gauss_tile(tile,
+               [&](size_t b, int y, int x, float (&v)[1]) { v[0] = src[b * P + (size_t)y * w + x]; },
+               [&](size_t b, int y, int x, const float (&blur)[1], const float (&)[1]) { dst[b * P + (size_t)y * w + x] = blur[0]; },
+               kern, ksize, h, w);
 }
 
 // separable blur src -> dst (tmp: intermediate plane of the two-kernel path)
 void launch_gauss_blur(const float *src, float *tmp, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st)
 {
-    static_assert(GF_TY == 4 * GC_R, "four waves of GC_R rows");
     if (ksize <= GF_MAXK && src != dst) {
-        hipLaunchKernelGGL(k_gauss_fused, dim3((w + GF_TX - 1) / GF_TX, (h + GF_TY - 1) / GF_TY, B), dim3(256), 0, st, src, dst, kern, ksize, h, w);
+        VF_LAUNCH_GAUSS_TILE(k_gauss_fused, ksize, B, h, w, st, src, dst, kern, ksize, h, w);
         return;
     }
     launch_gauss_rows(src, tmp, kern, ksize, B, h, w, st);
@@ -516,8 +448,7 @@ __global__ void k_illum_norm(const float *__restrict__ img, const float *__restr
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    // float32: img / (blur + 1e-6) - 1.0
-    out[i] = __fsub_rn(__fdiv_rn(img[i], __fadd_rn(blur[i], 1e-6f)), 1.0f);
+    out[i] = illum_norm_px(img[i], blur[i]);
 }
 void launch_illum_norm(const float *img, const float *blur, float *out, int B, int P, hipStream_t st)
 {
@@ -530,7 +461,7 @@ __global__ void k_mul_static(const float *__restrict__ a, const float *__restric
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     size_t b = blockIdx.y;
     if (p >= P) return;
-    out[b * (size_t)P + p] = __fmul_rn(a[b * (size_t)P + p], stat[p]);
+    out[b * (size_t)P + p] = mul_static_px(a[b * (size_t)P + p], stat[p]);
 }
 void launch_mul_static(const float *a, const float *stat, float *out, int B, int P, hipStream_t st)
 {

@@ -2,10 +2,9 @@
 // contact / background masks, masked smoothing glue, sign flip, frontier taper, composition,
 // unitless -> mm curve, blob filter, volume / area / max-depth / force / arg-extremum reductions.
 #include "kernels.hpp"
+#include "pixel_ops.hpp"
 
 namespace vf {
-
-__device__ inline float nanf32() { return __uint_as_float(0x7fc00000u); }
 
 // ---- contact mask (shape_ftp.py:1719-1732) -----------------------------------------------------
 // counts[b] = #{reliable & finite & |res| >= thr3[b,0]}
@@ -87,10 +86,10 @@ __global__ void k_sub_scalar_mask(const float *__restrict__ src, const float *__
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    float v = __fsub_rn(src[i], scalar[b]);
-    bool ok = mask[i] && finitef(v);
-    z0[i] = ok ? v : 0.f;
-    m_out[i] = ok ? 1.f : 0.f;
+    float z, m;
+    sub_scalar_mask_px(src[i], scalar[b], mask[i], z, m);
+    z0[i] = z;
+    m_out[i] = m;
 }
 void launch_sub_scalar_mask(const float *src, const float *scalar, const uint8_t *mask, float *z0, float *m_out, int B, int P,
                             hipStream_t st)
@@ -102,7 +101,7 @@ void launch_sub_scalar_mask(const float *src, const float *scalar, const uint8_t
 __global__ void k_div_planes(const float *__restrict__ num, const float *__restrict__ den, float *__restrict__ out, size_t n)
 {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = __fdiv_rn(num[i], __fadd_rn(den[i], 1e-6f));
+    if (i < n) out[i] = div_planes_px(num[i], den[i]);
 }
 void launch_div_planes(const float *num, const float *den, float *out, int B, int P, hipStream_t st)
 {
@@ -135,16 +134,8 @@ __global__ void k_frontier_compose(const float *__restrict__ hmap, const uint8_t
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    float v = 0.f;
-    if (reliable[i] && roi[p]) {
-        const float hgt = hmap[i];        // finite: `reliable` is output_reliable = reliable & isfinite(height) (:1801)
-        float de = fmaxf(__fsub_rn(dist_in[i], 1.0f), 0.0f);
-        float t = __fdiv_rn(de, fmaxf(1e-6f, band));
-        t = fminf(fmaxf(t, 0.0f), 1.0f);
-        float wgt = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
-        v = __fmul_rn(hgt, wgt);
-    }
-    z0[i] = v;
+    const bool on = reliable[i] && roi[p];
+    z0[i] = frontier_compose_px(on, on ? hmap[i] : 0.f, on ? dist_in[i] : 0.f, band);
 }
 void launch_frontier_compose(const float *hmap, const uint8_t *reliable, const uint8_t *roi, const float *dist_in, float band,
                              float *hfinal_z0, int B, int P, hipStream_t st)
@@ -161,20 +152,10 @@ __global__ void k_finalize_unitless(const float *__restrict__ z0, const float *_
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    float v = nanf32();
-    if (roi[p]) {
-        bool rel = reliable[i] != 0;
-        v = z0[i];
-        if (!rel) {
-            if (smooth_num) v = __fdiv_rn(smooth_num[i], roi_den[p]);
-            if (use_band) {
-                float de = fmaxf(__fsub_rn(dist_out[i], 1.0f), 0.0f);
-                if (de <= band) v = 0.f;
-            }
-        }
-        if (finitef(v)) v = fminf(v, 0.0f);
-    }
-    unitless[i] = v;
+    const bool in_roi = roi[p] != 0, rel = in_roi && reliable[i] != 0, unrel = in_roi && !rel;
+    const bool have_smooth = smooth_num != nullptr;
+    unitless[i] = finalize_unitless_px(in_roi, rel, in_roi ? z0[i] : 0.f, have_smooth, unrel && have_smooth ? smooth_num[i] : 0.f,
+                                       unrel && have_smooth ? roi_den[p] : 1.f, use_band != 0, unrel && use_band ? dist_out[i] : 0.f, band);
 }
 void launch_finalize_unitless(const float *hfinal_z0, const float *smooth_num, const float *roi_den, const uint8_t *reliable,
                               const uint8_t *roi, const float *dist_out, float band, int use_band, float *unitless, int B, int P,
@@ -193,15 +174,9 @@ __global__ void k_to_mm(const float *__restrict__ unitless, const uint8_t *__res
     unsigned int mx = 0;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
         size_t i = b * (size_t)P + p;
-        float hgt = unitless[i];
-        float d = hgt;   // NaN stays NaN
-        if (hgt == hgt) {
-            double x = use_neg ? -(double)hgt : (double)hgt;
-            x = fmax(x, 0.0);
-            d = (float)curve_eval(curve, x);
-        }
+        float d;
+        bool c = to_mm_px(unitless[i], roi[p] != 0, curve, use_neg, d);
         depth[i] = d;
-        bool c = roi[p] && finitef(d) && d > 0.0f;
         cand[i] = (uint8_t)c;
         if (c) { unsigned int u = __float_as_uint(d); if (u > mx) mx = u; }
     }

@@ -21,6 +21,7 @@ struct Tiers {
     int big_gq_cap = 0;         // test only: capacity (entries, power of two) the big-cluster march checks its global queue slice against; 0: the slice's own size
     int big_fallback = 1;       // 1: frames whose big-cluster queue overflowed are re-marched by the whole-frame kernel; 0: they keep status 2 (test only)
     int telea_mw = 1;           // 1: the 16-wave window kernel (ordering pass + dataflow fills, k_inpaint_mw.hip) as first tier, single-wave tiers behind it; 0: single-wave tiers only
+    int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
 
 struct RowSpanSE {      // structuring element as per-row x spans (cv::getStructuringElement ELLIPSE)
@@ -44,6 +45,21 @@ void launch_gauss_cols(const float *src, float *dst, const float *kern, int ksiz
 void launch_illum_norm(const float *img, const float *blur, float *out, int B, int P, hipStream_t st);
 void launch_mul_static(const float *a, const float *stat, float *out, int B, int P, hipStream_t st);
 void launch_count_u8(const uint8_t *m, int *counts, int B, int P, hipStream_t st);
+
+constexpr int GF_MAXK = 15;     // longest Gaussian that takes the one-kernel LDS tile (gauss_tile.hpp); longer ones run a row and a column kernel
+
+// ---- k_blurchain.hip: short blurs (ksize <= GF_MAXK) with their neighbouring element-wise passes fused in ------------------------------
+// iw = blur(img / (blur_illum + 1e-6) - 1) * apo
+void launch_illum_pre_apod(const float *img, const float *blur_illum, const float *apo, float *iw, const float *kern, int ksize, int B, int h,
+                           int w, hipStream_t st);
+// hmap = blur(z0) / (blur(m) + 1e-6), (z0, m) of launch_sub_scalar_mask
+void launch_smooth_reliable(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, const float *kern, int ksize, int B,
+                            int h, int w, hipStream_t st);
+// launch_frontier_compose, blur, launch_finalize_unitless and launch_to_mm in one; dist_out may be the plane `depth`
+void launch_compose_finalize_mm(const float *hmap, const uint8_t *reliable, const uint8_t *roi, const float *dist_in, float taper_band,
+                                const float *roi_den, const float *dist_out, float band, int use_band, Curve curve, int use_neg, float *unitless,
+                                float *depth, uint8_t *cand, unsigned int *gmax_bits, const float *kern, int ksize, int B, int h, int w,
+                                hipStream_t st);
 
 // ---- k_select.hip -----------------------------------------------------------------------------
 // Per frame: values vals[b*P+i] (|.| if use_abs) over pixels with mask != 0 (mask_stride 0: one static

@@ -1,0 +1,76 @@
+// Per-pixel expressions of the element-wise passes around the short Gaussian blurs.  Each one is called by its own streaming kernel
+// (k_basic.hip, k_post.hip) and by the fused blur kernels (k_blurchain.hip), so both paths execute the same operations in the same order.
+// The explicit __f*_rn keep every rounding where the reference has it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "common.hpp"
+
+namespace vf {
+
+__device__ inline float nanf32() { return __uint_as_float(0x7fc00000u); }
+
+// float32: img / (blur + 1e-6) - 1.0
+__device__ inline float illum_norm_px(float img, float blur) { return __fsub_rn(__fdiv_rn(img, __fadd_rn(blur, 1e-6f)), 1.0f); }
+
+__device__ inline float mul_static_px(float a, float stat) { return __fmul_rn(a, stat); }
+
+// zeroed = src - scalar; z0 = zeroed on (mask & finite) else 0; m = that mask as float   (shape_ftp.py:1750, :1756, :1142-1144)
+__device__ inline void sub_scalar_mask_px(float src, float scalar, uint8_t mask, float &z0, float &m)
+{
+    float v = __fsub_rn(src, scalar);
+    bool ok = mask && finitef(v);
+    z0 = ok ? v : 0.f;
+    m = ok ? 1.f : 0.f;
+}
+
+// num / (den + 1e-6)   (shape_ftp.py:1146-1147)
+__device__ inline float div_planes_px(float num, float den) { return __fdiv_rn(num, __fadd_rn(den, 1e-6f)); }
+
+// frontier taper inside reliable (shape_ftp.py:1287-1318): the smoothstep weight of the distance to the outside; 0 off the reliable ROI
+// pixels, where hgt and dist_in do not matter (computed and discarded: no branch, so a caller's loads of them need not wait for the mask)
+__device__ inline float frontier_compose_px(bool rel_roi, float hgt, float dist_in, float band)
+{
+    // hgt finite where it counts: `reliable` is output_reliable = reliable & isfinite(height) (:1801)
+    float de = fmaxf(__fsub_rn(dist_in, 1.0f), 0.0f);
+    float t = __fdiv_rn(de, fmaxf(1e-6f, band));
+    t = fminf(fmaxf(t, 0.0f), 1.0f);
+    float wgt = __fmul_rn(__fmul_rn(t, t), __fsub_rn(3.0f, __fmul_rn(2.0f, t)));
+    float v = __fmul_rn(hgt, wgt);
+    return rel_roi ? v : 0.f;
+}
+
+// unreliable ROI <- masked blur, outside band <- 0, clamp positives, NaN outside ROI (shape_ftp.py:1820-1841).  smooth_num / roi_den are
+// only looked at on unreliable ROI pixels with have_smooth, dist_out only on those with use_band.
+__device__ inline float finalize_unitless_px(bool roi, bool rel, float z0, bool have_smooth, float smooth_num, float roi_den, bool use_band,
+                                             float dist_out, float band)
+{
+    float v = nanf32();
+    if (roi) {
+        v = z0;
+        if (!rel) {
+            if (have_smooth) v = __fdiv_rn(smooth_num, roi_den);
+            if (use_band) {
+                float de = fmaxf(__fsub_rn(dist_out, 1.0f), 0.0f);
+                if (de <= band) v = 0.f;
+            }
+        }
+        if (finitef(v)) v = fminf(v, 0.0f);
+    }
+    return v;
+}
+
+// unitless -> mm (shape_ftp.py:682-705) and the blob candidate flag (:1232-1236); returns the candidate flag
+__device__ inline bool to_mm_px(float hgt, bool roi, const Curve &curve, int use_neg, float &depth)
+{
+    float d = hgt;   // NaN stays NaN
+    if (hgt == hgt) {
+        double x = use_neg ? -(double)hgt : (double)hgt;
+        x = fmax(x, 0.0);
+        d = (float)curve_eval(curve, x);
+    }
+    depth = d;
+    return roi && finitef(d) && d > 0.0f;
+}
+
+}  // namespace vf

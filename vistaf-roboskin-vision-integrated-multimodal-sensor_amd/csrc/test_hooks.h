@@ -24,6 +24,9 @@ extern "C" {
  *                      the slice's own size.  Only shrinks the capacity: the slice stride stays, pushes stay bounds-checked (overflow -> status 2)
  *       "big_fallback" 1 (default) a frame whose big-cluster queue overflowed (status 2) is re-marched whole by the whole-frame kernel,
  *                      0 the frame keeps status 2 and its overflowed cluster stays unfilled (shows that an overflow happened)
+ *       "fused_chains" 1 (default) the element-wise passes around a Gaussian of at most 15 taps (illumination normalise / apodise, masked
+ *                      smoothing's prologue and division, frontier taper / clamp / mm curve) run inside the blur's tile (k_blurchain.hip) and the
+ *                      planes between them (inorm, z0, mplane, num, den, z0f, snum) are not written; 0 one streaming kernel per pass
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 #ifdef __cplusplus
