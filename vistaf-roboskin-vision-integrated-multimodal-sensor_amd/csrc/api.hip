@@ -124,18 +124,28 @@ int dalloc(vistaf_ftp_handle *hd, T **p, size_t count, const char *name = nullpt
     return 0;
 }
 
-int make_gkern(vistaf_ftp_handle *hd, double sigma, GKern *g)
+// taps of cv::GaussianBlur(src, (0, 0), sigma) for CV_32F: ksize rule and float32 taps of cv::getGaussianKernel.  0: ok
+int gauss_taps(double sigma, std::vector<float> &f)
 {
-    g->k = 0; g->d = nullptr;
-    if (!(sigma > 0)) return 0;
     int n = cv_round(sigma * 4 * 2 + 1) | 1;       // cv::GaussianBlur ksize rule, CV_32F
     if (n > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
     std::vector<double> t(n);
     double s2 = -0.5 / (sigma * sigma), sum = 0;
     for (int i = 0; i < n; i++) { double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-    std::vector<float> f(n);
+    f.resize(n);
     for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-    int rc = dalloc(hd, &g->d, n);
+    return 0;
+}
+
+int make_gkern(vistaf_ftp_handle *hd, double sigma, GKern *g)
+{
+    g->k = 0; g->d = nullptr;
+    if (!(sigma > 0)) return 0;
+    std::vector<float> f;
+    int rc = gauss_taps(sigma, f);
+    if (rc) return rc;
+    const int n = (int)f.size();
+    rc = dalloc(hd, &g->d, n);
     if (rc) return rc;
     if (hipMemcpy(g->d, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(VISTAF_E_HIP, "memcpy gkern");
     g->k = n;
@@ -884,6 +894,72 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "keep_planes") hd->keep_planes = value != 0;
     else return fail(VISTAF_E_INVALID, "unknown test hook or value: " + n);
     return 0;
+}
+
+// ---- the selection, IRLS fit and plain blur launchers on caller-supplied device planes (csrc/test_hooks.h).  Not on the predict path.
+namespace {
+// scratch of the k_big.hip chain for one call, by `variant`: 0 as vistaf_ftp_create allocates it (frames of 512 x 512 and more), 1 none, 2 required
+int hook_scratch(int variant, int B, int h, int w, bool chain_ok, void **scratch)
+{
+    *scratch = nullptr;
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    if (variant == 2 && !chain_ok) return fail(VISTAF_E_INVALID, "variant 2: the k_big.hip chain does not take this batch");
+    if (variant == 1 || (variant == 0 && (size_t)h * w < 262144)) return 0;
+    HIPCHK(hipMalloc(scratch, big_scratch_bytes(B, h, w) + 256));
+    return 0;
+}
+int hook_finish(void *a, void *b, hipStream_t st)
+{
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(st);
+    if (a) (void)hipFree(a);
+    if (b) (void)hipFree(b);
+    if (e1 != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e1));
+    if (e2 != hipSuccess) return fail(VISTAF_E_HIP, std::string("sync: ") + hipGetErrorString(e2));
+    return 0;
+}
+}  // namespace
+
+int vistaf_ftp_test_select(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, int use_abs, const float *reqs, int nreq,
+                           float *out, int *counts, int B, int P, int variant, void *stream)
+{
+    if (!vals || !mask || !reqs || !out || B < 1 || P < 1 || nreq < 1 || (mask_stride != 0 && mask_stride != (size_t)P))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    void *scratch = nullptr;
+    int rc = hook_scratch(variant, B, 1, P, nreq <= 4 && big_frames(B, P), &scratch);
+    if (rc) return rc;
+    launch_select(vals, mask, mask_stride, le_thr, use_abs != 0, reqs, nreq, out, counts, B, P, (hipStream_t)stream, scratch);
+    return hook_finish(scratch, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,
+                            float *resid, int B, int h, int w, int variant, void *stream)
+{
+    if (!z || !mask || !coef || !resid || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || order < 1 || order > 2 || iters < 1)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    void *scratch = nullptr;
+    int rc = hook_scratch(variant, B, h, w, big_frames(B, h * w), &scratch);
+    if (rc) return rc;
+    const int inst = polyfit_variant(B, h, w, scratch != nullptr);
+    launch_robust_polyfit(z, mask, order, iters, c, min_count, min_mask_count, coef, resid, B, h, w, (hipStream_t)stream, scratch);
+    rc = hook_finish(scratch, nullptr, (hipStream_t)stream);
+    return rc ? rc : inst;
+}
+
+int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream)
+{
+    if (!src || !dst || src == dst || B < 1 || h < 1 || w < 1 || !(sigma > 0)) return fail(VISTAF_E_INVALID, "bad argument");
+    std::vector<float> f;
+    int rc = gauss_taps(sigma, f);
+    if (rc) return rc;
+    float *taps = nullptr, *tmp = nullptr;
+    HIPCHK(hipMalloc((void **)&taps, f.size() * sizeof(float)));
+    if (hipMalloc((void **)&tmp, (size_t)B * h * w * sizeof(float)) != hipSuccess) { (void)hipFree(taps); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    if (hipMemcpy(taps, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(taps); (void)hipFree(tmp);
+        return fail(VISTAF_E_HIP, "memcpy taps");
+    }
+    launch_gauss_blur(src, tmp, dst, taps, (int)f.size(), B, h, w, (hipStream_t)stream);
+    return hook_finish(taps, tmp, (hipStream_t)stream);
 }
 
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,

@@ -561,35 +561,55 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit_col(VF_FIT_ARGS) { rob
 #undef VF_FIT_ARGS
 #undef VF_FIT_PASS
 
+// Which of the ten kernels fits a batch of B frames of h x w (big: the caller holds scratch for the k_big.hip chain).  The one place
+// where the choice is made: the launcher below switches on the result, the tests read it through vistaf_ftp_test_polyfit.
+// Column kernels: thread t owns one column padded to 64 (cols_pad), the 1024 threads form `groups` row groups, a thread keeps
+// need = ceil(h / groups) samples in registers (<= 64) and the yn table must hold h + groups * 16 rows.
+int polyfit_variant(int B, int h, int w, bool big, int *cols_pad_out, int *groups_out)
+{
+    if (big && big_frames(B, h * w)) return FITV_BIG;
+    constexpr int NT = SEL_T;                      // threads of every column kernel (robust_polyfit_col_body's NT): the row groups follow from it
+    const int cols_pad = ((w + 63) / 64) * 64;
+    const int groups = cols_pad <= NT ? std::min(NT / cols_pad, h) : 0;
+    const int need = groups ? (h + groups - 1) / groups : 1 << 30;
+    if (cols_pad_out) *cols_pad_out = cols_pad;
+    if (groups_out) *groups_out = groups;
+    if (need <= 64 && h + groups * 16 <= FIT_YTAB) {
+        if (groups == 4 && need > 32) return need <= 48 ? FITV_COL48_G4 : need <= 56 ? FITV_COL56_G4 : FITV_COL64_G4;
+        return need <= 16 ? FITV_COL16 : need <= 32 ? FITV_COL32 : need <= 48 ? FITV_COL48 : need <= 56 ? FITV_COL56 : FITV_COL64;
+    }
+    // i / w == umulhi(i, magic) for every i < h * w as long as h * w * w < 2^32
+    return (unsigned long long)h * w * w < 0x100000000ull ? FITV_GENERIC : FITV_GENERIC_DIV;
+}
+
 // min_count: 200 fitted pixels upstream (:1103); min_mask_count: 500 mask pixels for the debug_ramp call (shape_ftp.py:1364-1366), else 0
 void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
                            float *resid_out, int B, int h, int w, hipStream_t st, void *big_scratch)
 {
-    if (big_scratch && big_frames(B, h * w)) {                   // large frames: every sweep over all pixels of the batch (k_big.hip)
-        launch_robust_polyfit_big(z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, B, h, w, big_scratch, st);
-        return;
-    }
-    // i / w == umulhi(i, magic) for every i < h * w as long as h * w * w < 2^32
-    const uint32_t magic = ((unsigned long long)h * w * w < 0x100000000ull) ? (uint32_t)(0x100000000ull / (unsigned)w) + 1u : 0u;
-    const int cols_pad = ((w + 63) / 64) * 64;
+    int cols_pad = 0, groups = 0;                                // of the column kernels, as polyfit_variant worked them out
+    const int variant = polyfit_variant(B, h, w, big_scratch != nullptr, &cols_pad, &groups);
 #define VF_FIT_COL(KERNEL, NTV, GR) hipLaunchKernelGGL(KERNEL, dim3(B), dim3(NTV), 0, st, z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, h, w, cols_pad, GR)
-    constexpr int NT = SEL_T;                      // threads of every column kernel below (robust_polyfit_col_body's NT): the row groups follow from it
-    const int groups = cols_pad <= NT ? std::min(NT / cols_pad, h) : 0;
-    const int need = groups ? (h + groups - 1) / groups : 1 << 30;
-    if (need <= 64 && h + groups * 16 <= FIT_YTAB) {
-        if (groups == 4 && need > 32) {
-            if (need <= 48) VF_FIT_COL((k_robust_polyfit_col<48, 4>), SEL_T, 4);
-            else if (need <= 56) VF_FIT_COL((k_robust_polyfit_col<56, 4>), SEL_T, 4);
-            else VF_FIT_COL((k_robust_polyfit_col<64, 4>), SEL_T, 4);
-        } else if (need <= 16) VF_FIT_COL((k_robust_polyfit_col<16, 0>), SEL_T, groups);
-        else if (need <= 32) VF_FIT_COL((k_robust_polyfit_col<32, 0>), SEL_T, groups);
-        else if (need <= 48) VF_FIT_COL((k_robust_polyfit_col<48, 0>), SEL_T, groups);
-        else if (need <= 56) VF_FIT_COL((k_robust_polyfit_col<56, 0>), SEL_T, groups);
-        else VF_FIT_COL((k_robust_polyfit_col<64, 0>), SEL_T, groups);
-        return;
+    switch (variant) {
+    case FITV_BIG:                                               // large frames: every sweep over all pixels of the batch (k_big.hip)
+        launch_robust_polyfit_big(z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, B, h, w, big_scratch, st);
+        break;
+    case FITV_COL48_G4: VF_FIT_COL((k_robust_polyfit_col<48, 4>), SEL_T, 4); break;
+    case FITV_COL56_G4: VF_FIT_COL((k_robust_polyfit_col<56, 4>), SEL_T, 4); break;
+    case FITV_COL64_G4: VF_FIT_COL((k_robust_polyfit_col<64, 4>), SEL_T, 4); break;
+    case FITV_COL16: VF_FIT_COL((k_robust_polyfit_col<16, 0>), SEL_T, groups); break;
+    case FITV_COL32: VF_FIT_COL((k_robust_polyfit_col<32, 0>), SEL_T, groups); break;
+    case FITV_COL48: VF_FIT_COL((k_robust_polyfit_col<48, 0>), SEL_T, groups); break;
+    case FITV_COL56: VF_FIT_COL((k_robust_polyfit_col<56, 0>), SEL_T, groups); break;
+    case FITV_COL64: VF_FIT_COL((k_robust_polyfit_col<64, 0>), SEL_T, groups); break;
+    case FITV_GENERIC:
+        hipLaunchKernelGGL(k_robust_polyfit, dim3(B), dim3(SEL_T), 0, st, z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, h, w,
+                           (uint32_t)(0x100000000ull / (unsigned)w) + 1u);
+        break;
+    default:                                                     // FITV_GENERIC_DIV: magic 0, plain division
+        hipLaunchKernelGGL(k_robust_polyfit, dim3(B), dim3(SEL_T), 0, st, z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, h, w, 0u);
+        break;
     }
 #undef VF_FIT_COL
-    hipLaunchKernelGGL(k_robust_polyfit, dim3(B), dim3(SEL_T), 0, st, z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, h, w, magic);
 }
 
 }  // namespace vf

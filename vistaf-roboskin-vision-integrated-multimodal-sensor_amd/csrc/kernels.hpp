@@ -157,6 +157,11 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
 // min_count: fitted (mask & finite) pixels needed (:1103); min_mask_count: mask pixels needed, NaN included (debug_ramp's own gate, :1364)
 void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
                            float *resid_out, int B, int h, int w, hipStream_t st, void *big_scratch = nullptr);
+// the kernel launch_robust_polyfit starts for (B, h, w); big: scratch for the k_big.hip chain is at hand.  FITV_COL<RP>[_G4]: k_robust_polyfit_col<RP, 0 | 4>,
+// FITV_GENERIC / FITV_GENERIC_DIV: k_robust_polyfit with the multiply-high row index / with a plain division (h * w * w >= 2^32)
+enum FitVariant { FITV_BIG = 0, FITV_GENERIC, FITV_GENERIC_DIV, FITV_COL16, FITV_COL32, FITV_COL48, FITV_COL56, FITV_COL64, FITV_COL48_G4, FITV_COL56_G4,
+                  FITV_COL64_G4, FITV_COUNT };
+int polyfit_variant(int B, int h, int w, bool big, int *cols_pad_out = nullptr, int *groups_out = nullptr);   // the column kernels' launch geometry, if asked
 
 // ---- k_holes.hip (hole stage, shape_ftp.py:1153-1204, :1770-1801; live only when reliable_smooth_sigma_px == 0) ----------------------
 void launch_zeroed_keep_nan(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, int B, int P, hipStream_t st);

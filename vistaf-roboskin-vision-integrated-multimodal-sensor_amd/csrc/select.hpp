@@ -210,12 +210,14 @@ __device__ inline void block_minmax(F get, int P, SelShared &sh, uint32_t &n, ui
     __syncthreads();
 }
 
-// NumPy 2.x percentile (method 'linear') of float32 data, float32 arithmetic:
-//   vi = n*q + (1 + q*(-1)) - 1 ; prev = floor(vi) ; gamma = vi - prev
+// NumPy 2.x percentile (method 'linear') of float32 data, float32 arithmetic.  The linear method has its own virtual index,
+// (n - 1) * q (numpy/lib/_function_base_impl.py: _QuantileMethods['linear']), not the general n*q + (alpha + q*(1 - alpha - beta)) - 1:
+//   vi = (n-1)*q ; prev = floor(vi) ; gamma = vi - prev
 //   res = a + (b-a)*gamma  [ b - (b-a)*(1-gamma) when gamma >= 0.5 ]
+// (The general form rounds differently in float32 and moved the result by a few ulps: [-2.5, 7] at q = 8 gave 0xbfdeb84e for 0xbfdeb852.)
 __device__ inline void np_percentile_index(uint32_t n, float q32, uint32_t &k, float &gamma, bool &top)
 {
-    float vi = __fsub_rn(__fadd_rn(__fmul_rn((float)n, q32), __fadd_rn(1.0f, __fmul_rn(q32, -1.0f))), 1.0f);
+    const float vi = __fmul_rn((float)(n - 1), q32);
     top = vi >= (float)(n - 1);
     if (vi < 0.0f) { k = 0; gamma = 0.0f; return; }
     float pf = floorf(vi);

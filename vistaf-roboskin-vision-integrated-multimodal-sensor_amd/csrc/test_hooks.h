@@ -29,6 +29,31 @@ extern "C" {
  *                      planes between them (inorm, z0, mplane, num, den, z0f, snum) are not written; 0 one streaming kernel per pass
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
+
+/* The production launchers of three kernel families on device planes of the caller, so that a test can feed them inputs no fringe image
+ * produces.  Every call runs on `stream`, waits for it and returns 0 (or a VISTAF_E_* code; text in vistaf_ftp_last_error).
+ * variant: 0 dispatch as a session does (the k_big.hip chain for planes of 262144 pixels and more, in batches it takes),
+ *          1 the one-workgroup-per-frame kernels whatever the size,
+ *          2 the k_big.hip chain; VISTAF_E_INVALID when it does not take (B, plane size).  Its scratch is allocated and freed by the call. */
+
+/* launch_select: per frame b, the order statistics reqs[0..nreq) of { x = vals[b][i] : mask[b * mask_stride + i] != 0, x finite, then
+ * x = |x| if use_abs, then x <= le_thr[b] if le_thr } into out[b * nreq + j] and their count into counts[b] (may be NULL).  A request is
+ * float32(q) / float32(100) for the percentile q, negative for the median.  mask_stride: 0 (one mask for the batch) or P.  No valid
+ * element: every result is the quiet NaN 0x7fc00000 and the count 0 (block_percentile / block_median of select.hpp, k_sb_setup of
+ * k_big.hip); that is where the reference's nanpercentile_safe / nanmedian_safe hand back the caller's fallback value. */
+int vistaf_ftp_test_select(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, int use_abs, const float *reqs, int nreq,
+                           float *out, int *counts, int B, int P, int variant, void *stream);
+
+/* launch_robust_polyfit: coef[b * 6 + 0..6) (entries 3..5 zero for order 1) and resid[b] = z[b] - fit over the whole plane (NaN where z is).
+ * Fewer than min_count fitted pixels (mask != 0 and z finite), or min_mask_count > 0 and fewer mask pixels than that: coefficients all
+ * zero and resid = z - 0.  Returns the launched instance (FitVariant of kernels.hpp: 0 chain, 1 generic, 2 generic with plain division,
+ * 3..7 column kernels of 16, 32, 48, 56, 64 rows per thread, 8..10 the four-group kernels of 48, 56, 64 rows) or a negative error. */
+int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,
+                            float *resid, int B, int h, int w, int variant, void *stream);
+
+/* launch_gauss_blur (src != dst) with the taps a session builds for `sigma`: up to 15 taps the one-kernel LDS tile, beyond the row and
+ * the column kernel. */
+int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream);
 #ifdef __cplusplus
 }
 #endif
