@@ -84,7 +84,8 @@ struct vistaf_ftp_handle {
     uint8_t *out_rel = nullptr, *hole_cand = nullptr;      // hole stage only (reliable_smooth_sigma_px == 0)
     float *hole_med = nullptr, *hole_fill = nullptr;
     int32_t *labels, *area, *rowdist, *parent;
-    unsigned int *peak_bits;
+    unsigned int *peak_bits;    // by component ROOT only: the component's peak (float bits) of the last predict.  Other entries are 0 after the separate
+                                // kernels and stale after the fused back end (which sets the roots only): never index it by pixel
     uint16_t *morph_pre;
     void *inpaint_scratch, *inpaint_cl_scratch, *inpaint_win_scratch, *unwrap_scratch;
     void *big_scratch = nullptr;      // k_big.hip (frames of 512 x 512 and more), else null
@@ -705,19 +706,29 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // ---- unitless -> mm, blob filter (shape_ftp.py:1850-1873)
     if (timed) hipEventRecord(hd->ev[ST_MM_BLOB], st);
     if (!fuse_compose) launch_to_mm(hd->unitless, hd->roi, hd->hcurve, hd->use_neg, hd->depth, hd->cand, hd->gmax, B, P, st);
-    launch_cc_label(hd->cand, hd->labels, B, h, w, st);
-    launch_blob_filter(hd->depth, hd->cand, hd->labels, hd->peak_bits, hd->gmax, c.contact_blob_min_peak_mm,
-                       c.contact_blob_min_peak_rel_frac, hd->kept, B, P, st);
-
-    // ---- force tail (multimodal_sensor.py:388-419) + arg-extrema
-    if (timed) hipEventRecord(hd->ev[ST_TAIL], st);
     PostParams pp;
     pp.mm_per_px = hd->mm_per_px; pp.depth_eps_mm = c.depth_eps_mm; pp.period_px = hd->period; pp.force_curve = hd->fcurve;
     pp.pair_geom = pair_geom; pp.grating_pitch_mm = c.grating_pitch_mm;
-    launch_tail(hd->depth, nullptr, hd->unitless, hd->roi, pp, hd->scalars, VISTAF_NSCALARS, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr,
-                hd->big_scratch ? big_scratch_bytes(hd->maxB, h, w) : 0);
+    // frames whose label forest fits LDS: labels, blob filter, force tail + arg-extrema and the copy to the caller's planes in one launch
+    // (stage timing: the whole launch counts as mm_blob, and the tail stage below is left with k_fill_scalars and the two small copies)
+    const bool fused_backend = hd->tiers.fused_backend && backend_fused_fits(h, w);
+    if (fused_backend)
+        launch_backend_fused(hd->depth, hd->cand, hd->gmax, hd->unitless, hd->roi, orel, hd->status, c.contact_blob_min_peak_mm,
+                             c.contact_blob_min_peak_rel_frac, pp, hd->labels, hd->peak_bits, hd->kept, hd->scalars, VISTAF_NSCALARS, d_height_mm,
+                             d_reliable, B, h, w, st);
+    else {
+        launch_cc_label(hd->cand, hd->labels, B, h, w, st);
+        launch_blob_filter(hd->depth, hd->cand, hd->labels, hd->peak_bits, hd->gmax, c.contact_blob_min_peak_mm,
+                           c.contact_blob_min_peak_rel_frac, hd->kept, B, P, st);
+    }
+
+    // ---- force tail (multimodal_sensor.py:388-419) + arg-extrema
+    if (timed) hipEventRecord(hd->ev[ST_TAIL], st);
+    if (!fused_backend)
+        launch_tail(hd->depth, nullptr, hd->unitless, hd->roi, pp, hd->scalars, VISTAF_NSCALARS, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr,
+                    hd->big_scratch ? big_scratch_bytes(hd->maxB, h, w) : 0);
     launch_fill_scalars(hd->scalars, VISTAF_NSCALARS, hd->rel_count, hd->flipped, hd->amp_thr, hd->thr_used, hd->bg_med, bad_count, B, st);
-    launch_copy_out(hd->depth, orel, hd->status, d_height_mm, d_reliable, B, P, st);
+    if (!fused_backend) launch_copy_out(hd->depth, orel, hd->status, d_height_mm, d_reliable, B, P, st);
     if (d_scalars) HIPCHK(hipMemcpyAsync(d_scalars, hd->scalars, sizeof(double) * VISTAF_NSCALARS * B, hipMemcpyDeviceToDevice, st));
     if (d_status) HIPCHK(hipMemcpyAsync(d_status, hd->status, sizeof(int32_t) * B, hipMemcpyDeviceToDevice, st));
     if (timed) {
@@ -891,6 +902,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "unwrap_fast") hd->tiers.unwrap_fast = value != 0;
     else if (n == "big_chain") hd->tiers.big_chain = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
+    else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
     else return fail(VISTAF_E_INVALID, "unknown test hook or value: " + n);
     return 0;
@@ -960,6 +972,20 @@ int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int
     }
     launch_gauss_blur(src, tmp, dst, taps, (int)f.size(), B, h, w, (hipStream_t)stream);
     return hook_finish(taps, tmp, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream)
+{
+    if (!mask || !dist_a || (pair && !dist_b) || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || cap_px < 0)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (w > 512 && !(pair && w <= 1280)) return fail(VISTAF_E_INVALID, "no two-pass instance for this width");
+    const size_t n = (size_t)B * h * w;
+    int32_t *tmp_a = nullptr, *tmp_b = nullptr;
+    HIPCHK(hipMalloc((void **)&tmp_a, n * sizeof(int32_t)));
+    if (pair && hipMalloc((void **)&tmp_b, n * sizeof(int32_t)) != hipSuccess) { (void)hipFree(tmp_a); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, true);
+    else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, true);
+    return hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
 }
 
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,

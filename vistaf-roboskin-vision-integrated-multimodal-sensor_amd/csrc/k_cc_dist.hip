@@ -9,6 +9,7 @@
 // of label words go through agent-scope relaxed atomics (served by L2, never a stale L1 line).
 #include <cstdlib>
 #include "kernels.hpp"
+#include "backend_device.hpp"
 
 namespace vf {
 
@@ -106,103 +107,15 @@ __global__ void k_cc_flatten(const uint8_t *__restrict__ mask, int32_t *__restri
     if (mask[b * (size_t)P + p]) { int r = cc_find(L, p); if (r != p) atomicMin(&L[p], r); }
 }
 
-// ---- LDS-resident variant for frames of at most 65535 pixels: the whole label forest lives in LDS as one
-// uint16 per pixel, so finds and unions are LDS round trips instead of L2 round trips.  LDS has no 16-bit
-// atomics: the "hang root b under a" step is a 32-bit CAS on the word holding the label.
-__device__ inline uint32_t cc16_min(uint16_t *L, int i, uint32_t val)
-{
-    uint32_t *wp = (uint32_t *)L + (i >> 1);
-    const int sh = (i & 1) * 16;
-    uint32_t old = *(volatile uint32_t *)wp;
-    for (;;) {
-        uint32_t cur = (old >> sh) & 0xffffu;
-        if (cur <= val) return cur;
-        uint32_t nw = (old & ~(0xffffu << sh)) | (val << sh);
-        uint32_t prev = atomicCAS(wp, old, nw);
-        if (prev == old) return cur;
-        old = prev;
-    }
-}
-__device__ inline int cc16_find(uint16_t *L, int i)
-{
-    volatile uint16_t *V = L;
-    for (;;) {
-        int p = V[i];
-        if (p == i) return i;
-        int g = V[p];
-        if (g == p) return p;
-        V[i] = (uint16_t)g;      // path halving (benign race: g is an ancestor of i)
-        i = g;
-    }
-}
-__device__ inline void cc16_unite(uint16_t *L, int a, int b)
-{
-    for (;;) {
-        a = cc16_find(L, a);
-        b = cc16_find(L, b);
-        if (a == b) return;
-        if (a > b) { int t = a; a = b; b = t; }
-        uint32_t old = cc16_min(L, b, (uint32_t)a);
-        if ((int)old == b) return;
-        b = (int)old;
-    }
-}
-
-// MLDS: the mask plane is staged in LDS too (P bytes behind the forest), so every neighbour test is an LDS read
+// ---- LDS-resident variant for frames of at most 65535 pixels: the whole label forest lives in LDS as one uint16 per pixel (cc16_* and
+// cc_lds_build in backend_device.hpp, shared with k_backend.hip).  MLDS: the mask plane is staged in LDS too (P bytes behind the forest)
 template <bool MLDS>
 __global__ __launch_bounds__(1024) void k_cc_label_lds(const uint8_t *__restrict__ mask, int32_t *__restrict__ labels, int h, int w)
 {
     extern __shared__ __attribute__((aligned(16))) uint16_t L16[];
     size_t b = blockIdx.x;
     int P = h * w;
-    const uint8_t *mg = mask + b * (size_t)P;
-    uint8_t *ml = (uint8_t *)(L16 + ((P + 2 + 7) & ~7));
-    if (MLDS) {
-        for (int p = threadIdx.x * 4; p < P; p += blockDim.x * 4) {
-            if (p + 3 < P && ((((uintptr_t)mg) & 3) == 0)) *(uint32_t *)(ml + p) = *(const uint32_t *)(mg + p);
-            else for (int k = 0; k < 4 && p + k < P; k++) ml[p + k] = mg[p + k];
-        }
-        __syncthreads();
-    }
-    const uint8_t *m = MLDS ? (const uint8_t *)ml : mg;
-    // Every pixel starts at the left end of its horizontal run (a prefix-max scan of the positions of the zero pixels of the row: 16
-    // waves, one row at a time each), so a run is one tree from the start and only the contacts between runs of adjacent rows are left
-    // to unite -- a few hundred unions per frame instead of four per pixel.  Roots are minimum pixel indices either way: same labels.
-    {
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nwv = blockDim.x >> 6;
-        for (int y = wid; y < h; y += nwv) {
-            int carry = -1;                                     // position of the last zero pixel seen in the row
-            for (int x0 = 0; x0 < w; x0 += 64) {
-                const int x = x0 + lane;
-                const bool on = x < w && m[y * w + x];
-                int lz = (x < w && !on) ? x : (int)0x80000000;
-                int t;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x111, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x112, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x114, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x118, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x142, 0xa, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x143, 0xc, 0xf, false); lz = t > lz ? t : lz;
-                lz = lz > carry ? lz : carry;
-                carry = __builtin_amdgcn_readlane(lz, 63);
-                if (x < w) L16[y * w + x] = on ? (uint16_t)(y * w + lz + 1) : (uint16_t)0xffffu;
-            }
-        }
-    }
-    if ((P & 1) && threadIdx.x == 0) L16[P] = 0xffffu;
-    __syncthreads();
-    for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        if (!m[p]) continue;
-        const int y = p / w, x = p - y * w;
-        if (y == 0) continue;
-        const bool left = x > 0 && m[p - 1];
-        const bool ul = x > 0 && m[p - w - 1], up = m[p - w] != 0, ur = x < w - 1 && m[p - w + 1];
-        // the run above-left / above: already united through the left neighbour when that one touches it too
-        if ((ul || up) && !left) cc16_unite(L16, p, ul ? p - w - 1 : p - w);
-        // a run that starts above-right
-        if (ur && !up) cc16_unite(L16, p, p - w + 1);
-    }
-    __syncthreads();
+    const uint8_t *m = cc_lds_build<MLDS>(mask + b * (size_t)P, h, w, L16);
     int32_t *out = labels + b * (size_t)P;
     for (int p = threadIdx.x; p < P; p += blockDim.x) out[p] = m[p] ? cc16_find(L16, p) : -1;
 }
@@ -210,11 +123,11 @@ __global__ __launch_bounds__(1024) void k_cc_label_lds(const uint8_t *__restrict
 void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st)
 {
     int P = h * w;
-    const size_t forest = (size_t)((P + 2 + 7) & ~7) * 2;
-    if (P <= 65535 && forest + (size_t)P + 16 <= 160 * 1024) {
+    const size_t forest = cc_lds_forest_bytes(P);
+    if (P <= 65535 && cc_lds_bytes(P) <= 160 * 1024) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<true>, 160 * 1024);
-        hipLaunchKernelGGL(k_cc_label_lds<true>, dim3(B), dim3(1024), forest + (size_t)P + 16, st, mask, labels, h, w);
+        hipLaunchKernelGGL(k_cc_label_lds<true>, dim3(B), dim3(1024), cc_lds_bytes(P), st, mask, labels, h, w);
         return;
     }
     if (P <= 65535 && forest <= 150 * 1024) {
@@ -454,9 +367,14 @@ __global__ void k_chamfer_cols(const int32_t *__restrict__ g, float *__restrict_
 // prefix scan, so a wave that holds PPL consecutive columns per lane does a row in a few dozen instructions
 // (lane-local scan, one DPP wave scan for the carries, one DPP shift for the neighbours across lanes).  The
 // backward pass is the mirror image.  Integer arithmetic throughout: results equal the sequential loops bit for
-// bit.  Rows are prefetched CH2_RING rows ahead (a single wave has nothing else to hide memory latency with).
+// bit.
+// A single wave has nothing else to hide memory latency with, and a row step is short next to a round trip to memory, so the rows are
+// prefetched ch2_ring(PPL) rows ahead into registers (the wave is alone on its SIMD: launch_bounds(64) leaves it 512 VGPRs).  The
+// depth is what the 6-bit vmcnt counter can tell apart: with aligned rows (w a multiple of 4, planes aligned as hipMalloc leaves them) a
+// row is PPL / 4 dword loads of the mask or dwordx4 loads of the temporary plane and as many dwordx4 stores, 2 * PPL / 4 operations, and
+// at most 63 may be outstanding behind the load a row waits for.  Other widths load and store element by element (and wait earlier).
 constexpr int CH2_INF = 0x7fffffff >> 2;     // cv DIST_MAX: border / initial value of the temporary plane
-constexpr int CH2_RING = 4;
+__host__ __device__ constexpr int ch2_ring(int ppl) { return ppl == 4 ? 31 : ppl == 8 ? 15 : 6; }
 
 __device__ inline int ch2_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }   // lane l <- l-1
 __device__ inline int ch2_shl1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }   // lane l <- l+1
@@ -473,12 +391,73 @@ __device__ inline int ch2_scan_min_up(int v)
     t = __builtin_amdgcn_update_dpp(big, v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;
     return v;
 }
+// mask bytes of columns x0 .. x0 + PPL of row y, four to a word (0 beyond the frame)
+template <int PPL>
+__device__ inline void ch2_load_mask(const uint8_t *__restrict__ src, int y, int h, int w, int x0, bool vec, uint32_t (&m)[PPL / 4])
+{
+#pragma unroll
+    for (int q = 0; q < PPL / 4; q++) {
+        const int x = x0 + 4 * q;
+        uint32_t v = 0;
+        if (y < h && x < w) {
+            const uint8_t *s = src + (size_t)y * w + x;
+            if (vec) v = *(const uint32_t *)s;
+            else {
+                v = s[0];
+                if (x + 1 < w) v |= (uint32_t)s[1] << 8;
+                if (x + 2 < w) v |= (uint32_t)s[2] << 16;
+                if (x + 3 < w) v |= (uint32_t)s[3] << 24;
+            }
+        }
+        m[q] = v;
+    }
+}
+// columns x0 .. x0 + PPL of row y of the temporary plane (CH2_INF beyond the frame; y < 0: no row)
+template <int PPL>
+__device__ inline void ch2_load_tmp(const int32_t *__restrict__ tmp, int y, int w, int x0, bool vec, int (&v)[PPL])
+{
+#pragma unroll
+    for (int q = 0; q < PPL / 4; q++) {
+        const int x = x0 + 4 * q;
+        int4 t = make_int4(CH2_INF, CH2_INF, CH2_INF, CH2_INF);
+        if (y >= 0 && x < w) {
+            const int32_t *s = tmp + (size_t)y * w + x;
+            if (vec) t = *(const int4 *)s;
+            else {
+                t.x = s[0];
+                if (x + 1 < w) t.y = s[1];
+                if (x + 2 < w) t.z = s[2];
+                if (x + 3 < w) t.w = s[3];
+            }
+        }
+        v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+    }
+}
+template <int PPL, typename T, typename T4>
+__device__ inline void ch2_store_row(T *__restrict__ dst, int y, int w, int x0, bool vec, const T (&v)[PPL])
+{
+#pragma unroll
+    for (int q = 0; q < PPL / 4; q++) {
+        const int x = x0 + 4 * q;
+        if (x >= w) continue;
+        T *d = dst + (size_t)y * w + x;
+        if (vec) { T4 t; t.x = v[4 * q]; t.y = v[4 * q + 1]; t.z = v[4 * q + 2]; t.w = v[4 * q + 3]; *(T4 *)d = t; }
+        else {
+            d[0] = v[4 * q];
+            if (x + 1 < w) d[1] = v[4 * q + 1];
+            if (x + 2 < w) d[2] = v[4 * q + 2];
+            if (x + 3 < w) d[3] = v[4 * q + 3];
+        }
+    }
+}
 
 template <int PPL>
 __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src_all, int invert, int32_t *__restrict__ tmp_all,
                                                  float *__restrict__ dist_all, int32_t *__restrict__ tmp2_all, float *__restrict__ dist2_all, int B,
                                                  int h, int w)
 {
+    static_assert(PPL % 4 == 0, "columns per lane come in groups of four");
+    constexpr int RING = ch2_ring(PPL);
     // workgroups [B, 2B) (launch_chamfer_pair): the distance to the complementary set of the same frames, into the second pair of planes
     const int lane = threadIdx.x;
     size_t b = blockIdx.x;
@@ -489,20 +468,20 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
     float *dist = dist_all + b * P;
     const int x0 = lane * PPL;
     const int step = CH_HV * PPL;
+    // every group of four columns is one aligned word of the mask and one aligned 16 bytes of the two 4-byte planes (wave-uniform)
+    const bool vec = (w & 3) == 0 && ((uintptr_t)src_all & 3) == 0 && ((uintptr_t)tmp_all & 15) == 0 && ((uintptr_t)dist_all & 15) == 0;
 
     // ---- forward pass (top-left to bottom-right); the result plane goes to tmp
     {
         int up[PPL];
 #pragma unroll
         for (int j = 0; j < PPL; j++) up[j] = CH2_INF;
-        uint8_t ring[CH2_RING][PPL];
+        uint32_t ring[RING][PPL / 4];
 #pragma unroll
-        for (int r = 0; r < CH2_RING; r++)
+        for (int r = 0; r < RING; r++) ch2_load_mask<PPL>(src, r, h, w, x0, vec, ring[r]);
+        for (int y0 = 0; y0 < h; y0 += RING) {
 #pragma unroll
-            for (int j = 0; j < PPL; j++) ring[r][j] = (r < h && x0 + j < w) ? src[(size_t)r * w + x0 + j] : (uint8_t)0;
-        for (int y0 = 0; y0 < h; y0 += CH2_RING) {
-#pragma unroll
-            for (int r = 0; r < CH2_RING; r++) {
+            for (int r = 0; r < RING; r++) {
                 const int y = y0 + r;
                 if (y >= h) break;
                 const int upl = ch2_shr1(up[PPL - 1], CH2_INF), upr = ch2_shl1(up[0], CH2_INF);
@@ -510,15 +489,15 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     const bool in = x0 + j < w;
-                    const bool zero = in && (invert ? ring[r][j] != 0 : ring[r][j] == 0);
+                    const uint32_t px = (ring[r][j >> 2] >> (8 * (j & 3))) & 0xffu;
+                    const bool zero = in && (invert ? px != 0 : px == 0);
                     const int a = (j > 0 ? up[j - 1] : upl) + CH_DG, c = (j < PPL - 1 ? up[j + 1] : upr) + CH_DG, u = up[j] + CH_HV;
                     int m = a < u ? a : u;
                     m = c < m ? c : m;
                     t[j] = zero ? 0 : m;
                 }
                 // next row of the ring
-#pragma unroll
-                for (int j = 0; j < PPL; j++) ring[r][j] = (y + CH2_RING < h && x0 + j < w) ? src[(size_t)(y + CH2_RING) * w + x0 + j] : (uint8_t)0;
+                ch2_load_mask<PPL>(src, y + RING, h, w, x0, vec, ring[r]);
                 // d(x) = min(t(x), d(x-1) + HV): lane-local scan, carries across lanes by a wave scan of (last - step * lane)
 #pragma unroll
                 for (int j = 1; j < PPL; j++) { int v = t[j - 1] + CH_HV; t[j] = v < t[j] ? v : t[j]; }
@@ -528,8 +507,8 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
                 for (int j = 0; j < PPL; j++) {
                     int v = carry + CH_HV * (j + 1);
                     up[j] = v < t[j] ? v : t[j];
-                    if (x0 + j < w) tmp[(size_t)y * w + x0 + j] = up[j];
                 }
+                ch2_store_row<PPL, int32_t, int4>(tmp, y, w, x0, vec, up);
             }
         }
     }
@@ -539,14 +518,12 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
         int dn[PPL];
 #pragma unroll
         for (int j = 0; j < PPL; j++) dn[j] = CH2_INF;
-        int ring[CH2_RING][PPL];
+        int ring[RING][PPL];
 #pragma unroll
-        for (int r = 0; r < CH2_RING; r++)
+        for (int r = 0; r < RING; r++) ch2_load_tmp<PPL>(tmp, h - 1 - r, w, x0, vec, ring[r]);
+        for (int y0 = 0; y0 < h; y0 += RING) {
 #pragma unroll
-            for (int j = 0; j < PPL; j++) ring[r][j] = (h - 1 - r >= 0 && x0 + j < w) ? tmp[(size_t)(h - 1 - r) * w + x0 + j] : CH2_INF;
-        for (int y0 = 0; y0 < h; y0 += CH2_RING) {
-#pragma unroll
-            for (int r = 0; r < CH2_RING; r++) {
+            for (int r = 0; r < RING; r++) {
                 const int y = h - 1 - (y0 + r);
                 if (y < 0) break;
                 const int dnl = ch2_shr1(dn[PPL - 1], CH2_INF), dnr = ch2_shl1(dn[0], CH2_INF);
@@ -559,8 +536,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
                     const int cur = x0 + j < w ? ring[r][j] : CH2_INF;
                     t[j] = m < cur ? m : cur;
                 }
-#pragma unroll
-                for (int j = 0; j < PPL; j++) ring[r][j] = (y - CH2_RING >= 0 && x0 + j < w) ? tmp[(size_t)(y - CH2_RING) * w + x0 + j] : CH2_INF;
+                ch2_load_tmp<PPL>(tmp, y - RING, w, x0, vec, ring[r]);
                 // d(x) = min(t(x), d(x+1) + HV): the same scan on mirrored lanes
 #pragma unroll
                 for (int j = PPL - 2; j >= 0; j--) { int v = t[j + 1] + CH_HV; t[j] = v < t[j] ? v : t[j]; }
@@ -572,15 +548,14 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
                 first = ch2_scan_min_up(first);
                 first = __builtin_amdgcn_ds_bpermute(ml << 2, first) + step * ml;            // final value of this lane's first column
                 const int carry = ch2_shl1(first, CH2_INF);                                  // d(x0 + PPL)
+                float o[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     int v = carry + CH_HV * (PPL - j);
                     dn[j] = v < t[j] ? v : t[j];
-                    if (x0 + j < w) {
-                        int o = dn[j] > CH2_INF ? CH2_INF : dn[j];
-                        dist[(size_t)y * w + x0 + j] = (float)o * (1.0f / 65536.0f);
-                    }
+                    o[j] = (float)(dn[j] > CH2_INF ? CH2_INF : dn[j]) * (1.0f / 65536.0f);
                 }
+                ch2_store_row<PPL, float, float4>(dist, y, w, x0, vec, o);
             }
         }
     }
@@ -694,7 +669,8 @@ void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *di
 }
 
 // distance to the zero pixels (-> dist_a) and to the non-zero pixels (-> dist_b) of the same masks.  The two-pass kernel is one wave per
-// frame, so both transforms of a batch run side by side in ONE launch of 2B workgroups (the chip holds four times that many waves).
+// frame, so both transforms of a batch run side by side in ONE launch of 2B workgroups.  All of them are resident at once: the prefetch rings
+// cost 144 to 175 VGPRs, so each of the chip's 1024 SIMDs holds at least two such waves, 2048 or more against the 512 of a batch of 256.
 void launch_chamfer_pair(const uint8_t *src, int32_t *tmp_a, float *dist_a, int32_t *tmp_b, float *dist_b, int B, int h, int w, int cap_px,
                          hipStream_t st, bool force_twopass)
 {

@@ -2,6 +2,7 @@
 // contact / background masks, masked smoothing glue, sign flip, frontier taper, composition,
 // unitless -> mm curve, blob filter, volume / area / max-depth / force / arg-extremum reductions.
 #include "kernels.hpp"
+#include "backend_device.hpp"
 #include "pixel_ops.hpp"
 
 namespace vf {
@@ -221,13 +222,8 @@ __global__ void k_blob_apply(float *__restrict__ depth, const uint8_t *__restric
     size_t i = b * (size_t)P + p;
     bool k = false;
     if (cand[i]) {
-        // the threshold is formed in float64 (Python floats, :1247-1250); `peaks >= thr` then compares a float32 array with a Python
-        // float, which NumPy 2 rounds to float32 first: the comparison is float32 against float32(thr)
-        double gmax = (double)__uint_as_float(gmax_bits[b]);
-        double thr = min_peak_mm;
-        if (rel_frac >= 0.0) thr = fmax(thr, rel_frac * gmax);
         float peak = __uint_as_float(peak_bits[b * (size_t)P + labels[i]]);
-        k = peak >= (float)thr;
+        k = peak >= blob_keep_threshold(gmax_bits[b], min_peak_mm, rel_frac);
         if (!k) depth[i] = 0.f;
     }
     if (kept) kept[i] = (uint8_t)k;
@@ -251,81 +247,11 @@ __global__ __launch_bounds__(1024) void k_tail(const float *__restrict__ height_
                                                const float *__restrict__ unitless, const uint8_t *__restrict__ roi_static, PostParams pp,
                                                double *__restrict__ scalars, int nscal, double *__restrict__ out3, int P)
 {
-    __shared__ double sd[16];
-    __shared__ unsigned long long s64[16];
-    size_t b = blockIdx.x;
+    // the body is tail_frame (backend_device.hpp), shared with the fused back end (k_backend.hip) so that both give the same bits
+    const size_t b = blockIdx.x;
     const float *H = height_mm + b * (size_t)P;
-    const uint8_t *R = roi_frame ? roi_frame + b * (size_t)P : nullptr;
-    // ONE pass over the planes, four pixels per thread in flight: the dominant sign (nansum(neg) > nansum(pos); float32 sums upstream,
-    // double here) is only known at the end, so the volume / area / maximum are accumulated for both signs and the right set is kept.
-    // Per thread the pixels come in the same order as in separate passes: the sums are the same bits.
-    const float *U = unitless ? unitless + b * (size_t)P : nullptr;
-    const bool want_arg = scalars != nullptr;
-    const float eps = (float)pp.depth_eps_mm;
-    double sp = 0, sn = 0, volp = 0, voln = 0;
-    int cntp = 0, cntn = 0;
-    unsigned long long mxp = 0, mxn = 0, am = 0, an = ~0ull;
-    constexpr int TU = 4;
-    const int T = blockDim.x;
-    for (int p0 = threadIdx.x; p0 < P; p0 += TU * T) {
-        float v[TU], u[TU];
-        uint8_t rf[TU], rs[TU];
-#pragma unroll
-        for (int k = 0; k < TU; k++) {
-            const int p = p0 + k * T;
-            const bool inb = p < P;
-            v[k] = inb ? H[p] : nanf32();
-            rf[k] = (inb && R) ? R[p] : (uint8_t)0;
-            rs[k] = (inb && want_arg) ? roi_static[p] : (uint8_t)0;
-            u[k] = (inb && U) ? U[p] : nanf32();
-        }
-#pragma unroll
-        for (int k = 0; k < TU; k++) {
-            const int p = p0 + k * T;
-            if (p >= P) break;
-            const float vv = v[k];
-            if (vv == vv) { if (vv > 0.f) sp += vv; else sn += -vv; }
-            const bool in = R ? rf[k] != 0 : finitef(vv);
-            float dp = fmaxf(vv, 0.f), dn = fmaxf(-vv, 0.f);
-            if (!in || !finitef(dp)) dp = 0.f;
-            if (!in || !finitef(dn)) dn = 0.f;
-            if (dp > eps) { volp += dp; cntp++; const unsigned long long key = (unsigned long long)__float_as_uint(dp) << 32; if (key > mxp) mxp = key; }
-            if (dn > eps) { voln += dn; cntn++; const unsigned long long key = (unsigned long long)__float_as_uint(dn) << 32; if (key > mxn) mxn = key; }
-            if (rs[k] && finitef(vv)) {            // arg-max of depth (mm) over roi & finite: first occurrence of the maximum
-                const unsigned long long key = ((unsigned long long)f2key(vv) << 32) | (unsigned int)(0xffffffffu - (unsigned int)p);
-                if (key > am) am = key;
-            }
-            if (rs[k] && finitef(u[k])) {          // arg-min of unitless height over roi & finite: first occurrence of the minimum
-                const unsigned long long key = ((unsigned long long)f2key(u[k]) << 32) | (unsigned int)p;
-                if (key < an) an = key;
-            }
-        }
-    }
-    sp = block_sum<double>(sp, sd);
-    sn = block_sum<double>(sn, sd);
-    const bool use_neg = (float)sn > (float)sp;
-    double vol = block_sum<double>(use_neg ? voln : volp, sd);
-    double cntd = block_sum<double>((double)(use_neg ? cntn : cntp), sd);
-    unsigned long long mx = block_max_u64(use_neg ? mxn : mxp, s64);
-    double period_px = pp.period_px, mm_per_px = pp.mm_per_px;
-    if (pp.pair_geom) { period_px = pp.pair_geom[b].period; mm_per_px = period_px > 1e-12 ? pp.grating_pitch_mm / period_px : 0.0; }
-    double area_px = mm_per_px * mm_per_px;
-    double volume_cm3 = cntd > 0 ? (double)(float)vol * area_px / 1000.0 : 0.0;
-    double area_mm2 = cntd * area_px;
-    double maxd = cntd > 0 ? (double)__uint_as_float((unsigned int)(mx >> 32)) : 0.0;
-    if (out3 && threadIdx.x == 0) { out3[b * 3] = volume_cm3; out3[b * 3 + 1] = area_mm2; out3[b * 3 + 2] = maxd; }
-    if (!scalars) return;
-    am = block_max_u64(am, s64);
-    if (unitless) an = block_min_u64(an, s64);
-    if (threadIdx.x == 0) {
-        double *S = scalars + b * (size_t)nscal;
-        S[0] = volume_cm3; S[1] = area_mm2; S[2] = maxd;
-        S[3] = curve_eval(pp.force_curve, volume_cm3);
-        S[4] = am ? (double)(0xffffffffu - (unsigned int)(am & 0xffffffffu)) : -1.0;
-        S[5] = period_px; S[6] = mm_per_px;
-        if (unitless && an != ~0ull) { S[7] = (double)key2f((unsigned int)(an >> 32)); S[8] = (double)(unsigned int)(an & 0xffffffffu); }
-        else { S[7] = (double)nanf32(); S[8] = -1.0; }
-    }
+    tail_frame([H](int p) { return H[p]; }, roi_frame ? roi_frame + b * (size_t)P : nullptr, unitless ? unitless + b * (size_t)P : nullptr, roi_static,
+               pp, scalars, nscal, out3, (int)b, P);
 }
 // The same tail for frames where one workgroup per frame leaves the chip idle (eight native crops: 1.1 ms): k_tail_part accumulates a block's
 // 4096 pixels exactly as k_tail accumulates a thread's, k_tail_final adds the blocks' partial results up in a fixed order (deterministic;

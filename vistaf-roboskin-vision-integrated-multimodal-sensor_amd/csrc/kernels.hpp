@@ -21,6 +21,7 @@ struct Tiers {
     int big_gq_cap = 0;         // test only: capacity (entries, power of two) the big-cluster march checks its global queue slice against; 0: the slice's own size
     int big_fallback = 1;       // 1: frames whose big-cluster queue overflowed are re-marched by the whole-frame kernel; 0: they keep status 2 (test only)
     int telea_mw = 1;           // 1: the 16-wave window kernel (ordering pass + dataflow fills, k_inpaint_mw.hip) as first tier, single-wave tiers behind it; 0: single-wave tiers only
+    int fused_backend = 1;      // 1: frames whose label forest fits LDS run blob filter, force tail and output copy in one launch per batch (k_backend.hip); 0: the separate kernels
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
 
@@ -255,5 +256,12 @@ void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t 
 size_t tstats_scratch_bytes(int h, int w);
 bool tstats_needs_big_scratch(int h, int w);
 void launch_tstats(const float *map, const uint8_t *valid, int h, int w, void *scratch, void *big_scratch, double *out, hipStream_t st);
+
+// ---- k_backend.hip (blob filter, force tail and output copy of LDS-sized frames in one launch: the fused_backend tier) -------------------
+bool backend_fused_fits(int h, int w);      // the frames launch_cc_label labels with the mask staged in LDS, less the tail's reduction scratch
+void launch_backend_fused(float *depth, const uint8_t *cand, const unsigned int *gmax_bits, const float *unitless, const uint8_t *roi_static,
+                          const uint8_t *reliable, const int32_t *status, double min_peak_mm, double rel_frac, PostParams pp, int32_t *labels,
+                          unsigned int *peak_bits, uint8_t *kept, double *scalars, int nscal, float *out_h, uint8_t *out_r, int B, int h, int w,
+                          hipStream_t st);
 
 }  // namespace vf

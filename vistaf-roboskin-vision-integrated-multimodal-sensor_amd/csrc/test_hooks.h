@@ -27,6 +27,10 @@ extern "C" {
  *       "fused_chains" 1 (default) the element-wise passes around a Gaussian of at most 15 taps (illumination normalise / apodise, masked
  *                      smoothing's prologue and division, frontier taper / clamp / mm curve) run inside the blur's tile (k_blurchain.hip) and the
  *                      planes between them (inorm, z0, mplane, num, den, z0f, snum) are not written; 0 one streaming kernel per pass
+ *       "fused_backend" 1 (default) frames whose label forest fits LDS (the ones launch_cc_label labels with the mask staged in LDS) run the blob
+ *                      filter, the force tail and the copy to the caller's planes in one launch (k_backend.hip); 0 the separate kernels
+ *                      (labels, peak plane clear, peaks, decision, tail, copy).  Same bits either way.  With stage timing on, the fused launch is charged
+ *                      to the mm / blob stage as a whole (tail and copy included); the tail stage then holds k_fill_scalars and the two copies only
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
@@ -54,6 +58,12 @@ int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int 
 /* launch_gauss_blur (src != dst) with the taps a session builds for `sigma`: up to 15 taps the one-kernel LDS tile, beyond the row and
  * the column kernel. */
 int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream);
+
+/* The one-wave two-pass chamfer transform (cv::distanceTransform DIST_L2, 3x3) forced, whatever kernel a session would pick for (h, w, cap_px).
+ * pair != 0: launch_chamfer_pair, ONE launch for dist_a[b] = distance to the zero pixels and dist_b[b] = distance to the non-zero pixels of
+ * mask[b] (w <= 1280; beyond 512 columns only a band of more than 64 rows, cap_px >= 60 and h > 64, takes the two-pass kernel); pair == 0: launch_chamfer, dist_a only, to the zero pixels or (invert != 0) to the non-zero pixels (w <= 512).
+ * Planes are [B, h, w]; the integer temporaries are allocated and freed by the call. */
+int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream);
 #ifdef __cplusplus
 }
 #endif
