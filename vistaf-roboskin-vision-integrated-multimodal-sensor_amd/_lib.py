@@ -15,6 +15,11 @@ NSCALARS = 16
 NREFINFO = 8
 NCONTACT = 16           # doubles per row of the per-contact table (VISTAF_NCONTACT)
 MAX_CONTACTS = 64
+NTRACK = 16             # doubles per row of the contact tracker's table (VISTAF_NTRACK, include/vistaf_track.h)
+# fields of a row in the order of the VISTAF_TRACK_* indices; 10..15 are reserved
+TRACK_NAMES = ["track_id", "age_frames", "parent_row", "events", "overlap_px", "dx", "dy", "dforce_N", "dvolume_cm3", "origin_track_id"]
+TRACK_EVENTS = {"born": 1, "split": 2, "merged": 4, "gated": 8}       # VISTAF_TRACKEV_*, bits of the `events` field
+FATE_ENDED, FATE_NO_ROW = -1, -2 ** 31                              # d_fate codes; -(2 + j): absorbed into contact j; >= 0: the continuing row
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
@@ -39,6 +44,7 @@ TEMPMODEL_EXPORTS = ["vistaf_tmodel_create", "vistaf_tmodel_destroy", "vistaf_tm
 TSENSOR_EXPORTS = ["vistaf_tsensor_default_config", "vistaf_tsensor_create", "vistaf_tsensor_destroy", "vistaf_tsensor_predict",
                    "vistaf_tsensor_stats_create", "vistaf_tsensor_stats_destroy", "vistaf_tsensor_map_statistics"]   # include/vistaf_tempsensor.h
 TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
+TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_reset", "vistaf_track_destroy"]   # include/vistaf_track.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -152,7 +158,12 @@ def load():
     lib.vistaf_tsensor_stats_destroy.argtypes = [vp]
     lib.vistaf_tsensor_stats_destroy.restype = None
     lib.vistaf_tsensor_map_statistics.argtypes = [vp, vp, vp, vp, ctypes.POINTER(cd), vp]
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS:
+    lib.vistaf_track_create.argtypes = [ci, ci, ci, ci, cd, ctypes.POINTER(vp)]
+    lib.vistaf_track_update.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp]
+    lib.vistaf_track_reset.argtypes = [vp]
+    lib.vistaf_track_destroy.argtypes = [vp]
+    lib.vistaf_track_destroy.restype = None
+    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS:
         getattr(lib, fn)
     _lib = lib
     return lib

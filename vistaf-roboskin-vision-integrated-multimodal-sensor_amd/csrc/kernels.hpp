@@ -224,6 +224,7 @@ struct ContactScratch {
 };
 int contact_root_capacity(int h, int w);
 size_t contact_part_words(int max_batch, int P);
+bool ct_chunked(int B, int P);       // chunk tier (workgroups over CT_CHUNK pixels) instead of one workgroup per frame; k_tracks.hip splits the same frames
 // contacts [B, K, nfield] double (nfield >= 13, fields as VISTAF_CONTACT_*), count [B], index [B, P] int8 or null
 void launch_contacts(const float *depth, const uint8_t *kept, const int32_t *labels, const unsigned int *peak_bits, const int32_t *status,
                      PostParams pp, const ContactScratch &cs, int K, double *contacts, int nfield, int32_t *count, int8_t *index, int B, int h, int w,

@@ -201,6 +201,9 @@ class FtpSensor:
         return _lib.FMT_BGR_F16 if t.dim() == 4 else _lib.FMT_GRAY_F16
 
     def close(self):
+        if getattr(self, "_tracker", None) is not None:
+            self._tracker.close()
+            self._tracker = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -289,6 +292,28 @@ class FtpSensor:
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_ftp_contacts(self._h, b, k, out["contacts"].data_ptr(), out["count"].data_ptr(),
                                                      out["contact_index"].data_ptr() if index_plane else None, _stream_ptr(self.device)))
+        return out
+
+    def track(self, max_contacts: int = 8, gate_px: float = 0.0, reset: bool = False) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus its link to the frames before it (tracks.ContactTracker; an extension, the reference
+        has no counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands the result to the session's tracker, created on
+        first use: the frames of this predict follow the frames of the predict of the previous `track` call.  Returns the contacts dict
+        plus tracks [B,K,16] f64 (fields TRACK_NAMES: persistent id, age, parent row, events, overlap, motion) and fate [B,K] i32.
+        reset=True forgets the frames seen so far and restarts ids at 0; max_contacts and gate_px can only change together with it."""
+        from .tracks import ContactTracker
+        k, gate = int(max_contacts), float(gate_px)
+        tr = getattr(self, "_tracker", None)
+        if tr is not None and (tr.max_contacts != k or tr.gate_px != gate):
+            if not reset:
+                raise ValueError("max_contacts / gate_px differ from the running tracker's: pass reset=True to start over with them")
+            tr.close()
+            tr = self._tracker = None
+        out = self.contacts(k, index_plane=True)
+        if tr is None:
+            tr = self._tracker = ContactTracker(self.h, self.w, self.max_batch, k, gate, device=self.device)
+        elif reset:
+            tr.reset()
+        out.update(tr.update(out["contact_index"], out["contacts"], out["count"]))
         return out
 
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:

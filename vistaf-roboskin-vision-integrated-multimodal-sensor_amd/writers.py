@@ -10,6 +10,9 @@
 * `multimodal_summary` / `write_multimodal_summary` -- `Code/multimodal_sensor.py:592-650` with its metric extractors (:214-280): the
   `multimodal_summary.json` of a combined force + temperature session (same keys, order and nesting).
 
+* `tracks_table` / `write_tracks_csv` -- the contact tracker's table (`FtpSensor.track`, `tracks.ContactTracker`) as row dicts and as
+  `tracks.csv`; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -34,6 +37,10 @@ CONTACT_FIELDS = ("pixels", "contact_pixels", "contact_area_mm2", "volume_cm3", 
                   "force_N", "bbox_x0", "bbox_y0", "bbox_x1", "bbox_y1")                  # VISTAF_CONTACT_* order (include/vistaf_ftp.h)
 CONTACT_INT_FIELDS = ("pixels", "contact_pixels", "argmax_index", "bbox_x0", "bbox_y0", "bbox_x1", "bbox_y1")
 CONTACTS_CSV_FIELDS = ("frame", "contact") + CONTACT_FIELDS
+TRACK_FIELDS = ("track_id", "age_frames", "parent_row", "events", "overlap_px", "dx", "dy", "dforce_N", "dvolume_cm3",
+                "origin_track_id")                                                        # VISTAF_TRACK_* order (include/vistaf_track.h)
+TRACK_INT_FIELDS = ("track_id", "age_frames", "parent_row", "events", "overlap_px", "origin_track_id")
+TRACKS_CSV_FIELDS = ("frame", "contact") + TRACK_FIELDS
 
 
 def _safe_float(x, default):
@@ -132,6 +139,41 @@ def write_contacts_csv(output_dir: str, contacts, count, filename: str = "contac
         w = csv.DictWriter(f, fieldnames=list(CONTACTS_CSV_FIELDS))
         w.writeheader()
         for row in contacts_table(contacts, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def tracks_table(tracks, contacts, count) -> list:
+    """Row dicts of the contact tracker's table: tracks [B,K,>=10] (or [K,>=10] for one frame) float64 as `FtpSensor.track` returns it, with
+    the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact`
+    (the row in both tables) and TRACK_FIELDS, the ids / age / rows / bitmask / pixel count as ints; dx .. dvolume_cm3 are NaN at birth."""
+    t = np.asarray(tracks, dtype=np.float64)
+    c = np.asarray(contacts, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if c.ndim == 2:
+        c = c[None]
+    if t.ndim != 3 or t.shape[2] < len(TRACK_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
+        raise ValueError("tracks must be [B,K,>=10] with contacts [B,K,>=13] and count [B]")
+    rows = []
+    for b in range(t.shape[0]):
+        for k in range(min(int(n[b]), t.shape[1])):
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(TRACK_FIELDS):
+                row[name] = int(t[b, k, i]) if name in TRACK_INT_FIELDS else float(t[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def write_tracks_csv(output_dir: str, tracks, contacts, count, filename: str = "tracks.csv") -> str:
+    """tracks.csv: one line per written contact, columns TRACKS_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(TRACKS_CSV_FIELDS))
+        w.writeheader()
+        for row in tracks_table(tracks, contacts, count):
             w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
     return path
 
