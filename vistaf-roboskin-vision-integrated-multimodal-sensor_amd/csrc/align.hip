@@ -20,47 +20,14 @@
 #include <string>
 #include <vector>
 
-#include "../../include/vistaf_ftp.h"
 #include "../../include/vistaf_align.h"
-#include "kernels.hpp"
+#include "host_util.hpp"
 
-namespace vf { int set_error(int code, const std::string &msg); }
 using namespace vf;
-
-#define ACHK(x)                                                                                              \
-    do {                                                                                                     \
-        hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) return set_error(VISTAF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-#define FCHK(x)                                                                                        \
-    do {                                                                                               \
-        hipfftResult r_ = (x);                                                                         \
-        if (r_ != HIPFFT_SUCCESS) return set_error(VISTAF_E_HIP, std::string(#x) + ": hipfft error " + std::to_string((int)r_)); \
-    } while (0)
 
 namespace {
 
-constexpr int AB_BITS = 10, AB_SCALE = 1 << AB_BITS, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
 constexpr int ECC_NSUM = 21, ECC_BLOCKS = 128, ECC_T = 256;
-
-struct Aff { double m[6]; };      // source = M * (x, y, 1): the inverse map warpAffine iterates with
-
-__device__ inline long long cvr(double v) { return __double2ll_rn(v); }          // cvRound / saturate_cast<int>(double): half to even
-
-// fixed-point source coordinate of destination pixel (x, y): integer part and 1/32 fraction (WarpAffineInvoker)
-__device__ inline void src_coord(const Aff &a, int x, int y, int round_delta, int shift, int &X, int &Y)
-{
-    long long ad = cvr(a.m[0] * x * AB_SCALE), bd = cvr(a.m[3] * x * AB_SCALE);
-    long long X0 = cvr((a.m[1] * y + a.m[2]) * AB_SCALE) + round_delta, Y0 = cvr((a.m[4] * y + a.m[5]) * AB_SCALE) + round_delta;
-    X = (int)((X0 + ad) >> shift);
-    Y = (int)((Y0 + bd) >> shift);
-}
-__device__ inline int reflect_b(int p, int n)       // BORDER_REFLECT
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p - 1 : 2 * n - 1 - p;
-    return p;
-}
 
 __global__ void k_bgr2gray(const uint8_t *__restrict__ bgr, uint8_t *__restrict__ g8, float *__restrict__ gf, size_t n, int coeffs3x)
 {
@@ -142,9 +109,9 @@ __global__ void k_warp_u8(const uint8_t *__restrict__ src, uint8_t *__restrict__
     int x = x1 + blockIdx.x * blockDim.x + threadIdx.x, y = y1 + blockIdx.y;
     if (x >= x2) return;
     int X, Y;
-    src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
+    warp_src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
     const int sx = X >> INTER_BITS, sy = Y >> INTER_BITS, ax = X & (INTER_TAB - 1), ay = Y & (INTER_TAB - 1);
-    const int xa = reflect_b(sx, w), xb = reflect_b(sx + 1, w), ya = reflect_b(sy, h), yb = reflect_b(sy + 1, h);
+    const int xa = reflect_edge(sx, w), xb = reflect_edge(sx + 1, w), ya = reflect_edge(sy, h), yb = reflect_edge(sy + 1, h);
     const int w00 = (INTER_TAB - ax) * (INTER_TAB - ay) * 32, w01 = ax * (INTER_TAB - ay) * 32, w10 = (INTER_TAB - ax) * ay * 32, w11 = ax * ay * 32;
     uint8_t *o = dst + ((size_t)(y - y1) * (x2 - x1) + (x - x1)) * C;
 #pragma unroll
@@ -223,14 +190,14 @@ __global__ __launch_bounds__(ECC_T) void k_ecc_accumulate(const float *__restric
     for (size_t p = (size_t)blockIdx.x * ECC_T + threadIdx.x; p < P; p += (size_t)gridDim.x * ECC_T) {
         const int y = (int)(p / w), x = (int)(p - (size_t)y * w);
         int X, Y;
-        src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
+        warp_src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
         const int sx = X >> INTER_BITS, sy = Y >> INTER_BITS;
         const float fx = (float)(X & (INTER_TAB - 1)) / 32.0f, fy = (float)(Y & (INTER_TAB - 1)) / 32.0f;
         const float w00 = (1.f - fx) * (1.f - fy), w01 = fx * (1.f - fy), w10 = (1.f - fx) * fy, w11 = fx * fy;
         const float iw = bilin_f(img, h, w, sx, sy, w00, w01, w10, w11);
         const float gxw = bilin_f(gx, h, w, sx, sy, w00, w01, w10, w11), gyw = bilin_f(gy, h, w, sx, sy, w00, w01, w10, w11);
         int Xn, Yn;
-        src_coord(a, x, y, AB_SCALE / 2, AB_BITS, Xn, Yn);                    // INTER_NEAREST
+        warp_src_coord(a, x, y, AB_SCALE / 2, AB_BITS, Xn, Yn);               // INTER_NEAREST
         const bool in = Xn >= 0 && Xn < w && Yn >= 0 && Yn < h && premask[(size_t)Yn * w + Xn] != 0;
         const float hatx = -((float)x * h1) - ((float)y * h0), haty = ((float)x * h0) - ((float)y * h1);
         const double j0 = (double)(gxw * hatx + gyw * haty), j1 = (double)gxw, j2 = (double)gyw;
@@ -340,9 +307,9 @@ __global__ void k_ecc_apply(const uint8_t *__restrict__ mov_all, uint8_t *__rest
     Aff a;
     for (int i = 0; i < 6; i++) a.m[i] = (double)st.warp[i];
     int X, Y;
-    src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
+    warp_src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
     const int sx = X >> INTER_BITS, sy = Y >> INTER_BITS, ax = X & (INTER_TAB - 1), ay = Y & (INTER_TAB - 1);
-    const int xa = reflect_b(sx, w), xb = reflect_b(sx + 1, w), ya = reflect_b(sy, h), yb = reflect_b(sy + 1, h);
+    const int xa = reflect_edge(sx, w), xb = reflect_edge(sx + 1, w), ya = reflect_edge(sy, h), yb = reflect_edge(sy + 1, h);
     const int w00 = (INTER_TAB - ax) * (INTER_TAB - ay) * 32, w01 = ax * (INTER_TAB - ay) * 32, w10 = (INTER_TAB - ax) * ay * 32, w11 = ax * ay * 32;
     int acc = mov[(size_t)ya * w + xa] * w00 + mov[(size_t)ya * w + xb] * w01 + mov[(size_t)yb * w + xa] * w10 + mov[(size_t)yb * w + xb] * w11;
     int v = (acc + (1 << 14)) >> 15;
@@ -365,24 +332,13 @@ int optimal_dft(int n)
     }
 }
 
-int gauss_taps(double sigma, std::vector<float> &f)
-{
-    int n = ((int)lrint(sigma * 4 * 2 + 1)) | 1;         // cv::GaussianBlur ksize rule, CV_32F
-    std::vector<double> t(n);
-    double s2 = -0.5 / (sigma * sigma), sum = 0;
-    for (int i = 0; i < n; i++) { double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-    f.resize(n);
-    for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-    return n;
-}
-
 }  // namespace
 
 struct vistaf_align_handle {
     vistaf_align_config cfg;
     int H, W, M, N, cx, cy, r, maxB;
     int x1, y1, x2, y2, ch, cw, cxl, cyl, rl;
-    std::vector<void *> allocs;
+    DeviceAllocs allocs;
     float *g7 = nullptr, *g5 = nullptr;
     int k7 = 0, k5 = 0;
     float *gray_f = nullptr, *tmp_f = nullptr, *pad_f = nullptr, *corr = nullptr;        // full-frame planes
@@ -398,17 +354,6 @@ struct vistaf_align_handle {
     int *done_host = nullptr;
 };
 
-template <typename T>
-static int aalloc(vistaf_align_handle *h, T **p, size_t n)
-{
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T) + 256);
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
-
 extern "C" {
 
 void vistaf_align_default_config(vistaf_align_config *c)
@@ -422,7 +367,7 @@ void vistaf_align_destroy(vistaf_align_handle *h)
 {
     if (!h) return;
     if (h->have_plans) { hipfftDestroy(h->plan_r2c); hipfftDestroy(h->plan_c2r); }
-    for (void *p : h->allocs) (void)hipFree(p);
+    h->allocs.free_all();
     delete h;
 }
 
@@ -441,25 +386,26 @@ int vistaf_align_create(const vistaf_align_config *cfg, int H, int W, int cx, in
     h->cxl = cx - h->x1; h->cyl = cy - h->y1;
     h->rl = std::min(std::min(r, h->cxl), std::min(std::min(h->cyl, h->cw - 1 - h->cxl), h->ch - 1 - h->cyl));
 #define TRYA(x) do { int rc_ = (x); if (rc_) { vistaf_align_destroy(h); return rc_; } } while (0)
-    std::vector<float> t7, t5;
-    h->k7 = gauss_taps(cfg->shift_blur_sigma, t7);
-    TRYA(aalloc(h, &h->g7, t7.size()));
+    const std::vector<float> t7 = gauss_taps(cfg->shift_blur_sigma);
+    h->k7 = (int)t7.size();
+    TRYA(h->allocs.alloc(&h->g7, t7.size()));
     if (hipMemcpy(h->g7, t7.data(), t7.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_align_destroy(h); return set_error(VISTAF_E_HIP, "memcpy taps"); }
     if (cfg->ecc_gauss_sigma > 0) {
-        h->k5 = gauss_taps(cfg->ecc_gauss_sigma, t5);
-        TRYA(aalloc(h, &h->g5, t5.size()));
+        const std::vector<float> t5 = gauss_taps(cfg->ecc_gauss_sigma);
+        h->k5 = (int)t5.size();
+        TRYA(h->allocs.alloc(&h->g5, t5.size()));
         if (hipMemcpy(h->g5, t5.data(), t5.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_align_destroy(h); return set_error(VISTAF_E_HIP, "memcpy taps"); }
     }
     if (h->k7 > 511 || h->k5 > 511) { vistaf_align_destroy(h); return set_error(VISTAF_E_INVALID, "gaussian sigma too large"); }
     const size_t FP = (size_t)H * W, MP = (size_t)h->M * h->N, HP = (size_t)h->M * (h->N / 2 + 1), CP = (size_t)h->ch * h->cw;
-    TRYA(aalloc(h, &h->gray_f, FP)); TRYA(aalloc(h, &h->tmp_f, FP)); TRYA(aalloc(h, &h->pad_f, MP)); TRYA(aalloc(h, &h->corr, MP));
-    TRYA(aalloc(h, &h->F_ref, HP)); TRYA(aalloc(h, &h->F_def, HP));
-    TRYA(aalloc(h, &h->crop_bgr, CP * 3));
-    TRYA(aalloc(h, &h->peak_part, 256));
-    TRYA(aalloc(h, &h->ref_gray, CP)); TRYA(aalloc(h, &h->circ, CP)); TRYA(aalloc(h, &h->tpl, CP)); TRYA(aalloc(h, &h->crop_tmp, CP * max_batch));
-    TRYA(aalloc(h, &h->mov_u8, CP * max_batch)); TRYA(aalloc(h, &h->mov_f, CP * max_batch)); TRYA(aalloc(h, &h->mov_tmp, CP * max_batch));
-    TRYA(aalloc(h, &h->gx, CP * max_batch)); TRYA(aalloc(h, &h->gy, CP * max_batch));
-    TRYA(aalloc(h, &h->st, (size_t)max_batch)); TRYA(aalloc(h, &h->partial, (size_t)max_batch * ECC_BLOCKS * ECC_NSUM));
+    TRYA(h->allocs.alloc(&h->gray_f, FP)); TRYA(h->allocs.alloc(&h->tmp_f, FP)); TRYA(h->allocs.alloc(&h->pad_f, MP)); TRYA(h->allocs.alloc(&h->corr, MP));
+    TRYA(h->allocs.alloc(&h->F_ref, HP)); TRYA(h->allocs.alloc(&h->F_def, HP));
+    TRYA(h->allocs.alloc(&h->crop_bgr, CP * 3));
+    TRYA(h->allocs.alloc(&h->peak_part, 256));
+    TRYA(h->allocs.alloc(&h->ref_gray, CP)); TRYA(h->allocs.alloc(&h->circ, CP)); TRYA(h->allocs.alloc(&h->tpl, CP)); TRYA(h->allocs.alloc(&h->crop_tmp, CP * max_batch));
+    TRYA(h->allocs.alloc(&h->mov_u8, CP * max_batch)); TRYA(h->allocs.alloc(&h->mov_f, CP * max_batch)); TRYA(h->allocs.alloc(&h->mov_tmp, CP * max_batch));
+    TRYA(h->allocs.alloc(&h->gx, CP * max_batch)); TRYA(h->allocs.alloc(&h->gy, CP * max_batch));
+    TRYA(h->allocs.alloc(&h->st, (size_t)max_batch)); TRYA(h->allocs.alloc(&h->partial, (size_t)max_batch * ECC_BLOCKS * ECC_NSUM));
     if (hipfftPlan2d(&h->plan_r2c, h->M, h->N, HIPFFT_R2C) != HIPFFT_SUCCESS || hipfftPlan2d(&h->plan_c2r, h->M, h->N, HIPFFT_C2R) != HIPFFT_SUCCESS) {
         vistaf_align_destroy(h);
         return set_error(VISTAF_E_HIP, "hipfftPlan2d failed");
@@ -491,8 +437,8 @@ static int frame_spectrum(vistaf_align_handle *h, const uint8_t *d_bgr, float2 *
     hipLaunchKernelGGL(k_hann_mul, dim3((h->W + 255) / 256, h->H), dim3(256), 0, st, h->gray_f, h->H, h->W);
     const float *src = h->gray_f;
     if (h->M != h->H || h->N != h->W) {
-        ACHK(hipMemsetAsync(h->pad_f, 0, (size_t)h->M * h->N * sizeof(float), st));
-        ACHK(hipMemcpy2DAsync(h->pad_f, (size_t)h->N * sizeof(float), h->gray_f, (size_t)h->W * sizeof(float), (size_t)h->W * sizeof(float), h->H, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemsetAsync(h->pad_f, 0, (size_t)h->M * h->N * sizeof(float), st));
+        HIPCHK(hipMemcpy2DAsync(h->pad_f, (size_t)h->N * sizeof(float), h->gray_f, (size_t)h->W * sizeof(float), (size_t)h->W * sizeof(float), h->H, hipMemcpyDeviceToDevice, st));
         src = h->pad_f;
     }
     FCHK(hipfftSetStream(h->plan_r2c, st));
@@ -518,8 +464,8 @@ int vistaf_align_set_reference(vistaf_align_handle *h, const uint8_t *d_ref_bgr,
         launch_gauss_rows(h->tpl, h->crop_tmp, h->g5, h->k5, 1, h->ch, h->cw, st);
         launch_gauss_cols(h->crop_tmp, h->tpl, h->g5, h->k5, 1, h->ch, h->cw, st);
     }
-    if (d_ref_gray_crop) ACHK(hipMemcpyAsync(d_ref_gray_crop, h->ref_gray, CP, hipMemcpyDeviceToDevice, st));
-    ACHK(hipStreamSynchronize(st));
+    if (d_ref_gray_crop) HIPCHK(hipMemcpyAsync(d_ref_gray_crop, h->ref_gray, CP, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
     h->have_ref = true;
     return 0;
 }
@@ -531,7 +477,7 @@ int vistaf_align_batch(vistaf_align_handle *h, const uint8_t *d_def_bgr, int B, 
     if (B < 1 || B > h->maxB) return set_error(VISTAF_E_STATE, "batch exceeds max_batch");
     hipStream_t st = (hipStream_t)stream;
     const size_t FP = (size_t)h->H * h->W, CP = (size_t)h->ch * h->cw, HP = (size_t)h->M * (h->N / 2 + 1);
-    ACHK(hipMemsetAsync(d_info, 0, sizeof(double) * VISTAF_ALIGN_NINFO * B, st));
+    HIPCHK(hipMemsetAsync(d_info, 0, sizeof(double) * VISTAF_ALIGN_NINFO * B, st));
     std::vector<double> shifts(3 * (size_t)B, 0.0);
     for (int b = 0; b < B; b++) {
         const uint8_t *bgr = d_def_bgr + (size_t)b * FP * 3;
@@ -547,8 +493,8 @@ int vistaf_align_batch(vistaf_align_handle *h, const uint8_t *d_def_bgr, int B, 
         // ---- warpAffine of the ROI window only (the rest of the shifted frame is never looked at), then BGR2GRAY
         Aff a = {{1, 0, 0, 0, 1, 0}};
         if (h->cfg.apply_global_shift) {
-            ACHK(hipMemcpyAsync(&shifts[3 * (size_t)b], info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-            ACHK(hipStreamSynchronize(st));
+            HIPCHK(hipMemcpyAsync(&shifts[3 * (size_t)b], info, 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
             // M = [[1,0,dx],[0,1,dy]] as float32, inverted in double (cv::invertAffineTransform)
             const double dx = (double)(float)shifts[3 * (size_t)b], dy = (double)(float)shifts[3 * (size_t)b + 1];
             a.m[2] = -dx; a.m[5] = -dy;
@@ -572,8 +518,8 @@ int vistaf_align_batch(vistaf_align_handle *h, const uint8_t *d_def_bgr, int B, 
             hipLaunchKernelGGL(k_ecc_accumulate, dim3(ECC_BLOCKS, B), dim3(ECC_T), 0, st, h->tpl, h->mov_f, h->gx, h->gy, h->circ, h->st, h->partial, h->ch, h->cw);
             hipLaunchKernelGGL(k_ecc_update, dim3(B), dim3(64), 0, st, h->st, h->partial, ECC_BLOCKS, h->cfg.ecc_iters, h->cfg.ecc_eps);
             if ((it & 7) == 7) {                                   // all frames converged?  (the iteration count is data dependent)
-                ACHK(hipMemcpyAsync(hs.data(), h->st, sizeof(EccState) * B, hipMemcpyDeviceToHost, st));
-                ACHK(hipStreamSynchronize(st));
+                HIPCHK(hipMemcpyAsync(hs.data(), h->st, sizeof(EccState) * B, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 bool all = true;
                 for (int b = 0; b < B; b++) all = all && hs[b].done;
                 if (all) break;
@@ -581,13 +527,11 @@ int vistaf_align_batch(vistaf_align_handle *h, const uint8_t *d_def_bgr, int B, 
         }
         hipLaunchKernelGGL(k_ecc_apply, dim3((h->cw + 255) / 256, h->ch, B), dim3(256), 0, st, h->mov_u8, d_out, h->st, d_info, h->ch, h->cw);
     } else {
-        ACHK(hipMemcpyAsync(d_out, h->mov_u8, CP * B, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipMemcpyAsync(d_out, h->mov_u8, CP * B, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(k_ecc_apply, dim3(1, 1, B), dim3(1), 0, st, h->mov_u8, h->mov_u8, h->st, d_info, 0, 0);   // identity warps into the records
     }
-    ACHK(hipStreamSynchronize(st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return 0;
+    HIPCHK(hipStreamSynchronize(st));
+    return launch_ok("launch");
 }
 
 }  // extern "C"

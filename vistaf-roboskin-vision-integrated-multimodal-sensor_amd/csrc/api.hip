@@ -11,8 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/vistaf_ftp.h"
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 using namespace vf;
 #include "test_hooks.h"
@@ -23,11 +22,6 @@ namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); voi
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 namespace vf { int set_error(int code, const std::string &msg) { return fail(code, msg); } }   // for the other translation units of the ABI
-#define HIPCHK(x)                                                                                         \
-    do {                                                                                                  \
-        hipError_t e_ = (x);                                                                              \
-        if (e_ != hipSuccess) return fail(VISTAF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 
@@ -37,8 +31,6 @@ enum Stage { ST_GRAY_BAD = 0, ST_INPAINT, ST_PREPROC, ST_DEMOD, ST_RELIABLE, ST_
              ST_TAIL, ST_COUNT };
 const char *kStageNames[ST_COUNT] = {"gray+badpix", "inpaint (k_telea_window_mw)", "illum+blur+apod+median", "pruned-dft demod", "reliable mask",
                                      "unwrap check (k_unwrap_fast)", "unwrap flood (fallback)", "unwrap tree (fallback)", "detrend (3x IRLS)", "smooth+flip", "frontier+compose", "mm+blob filter", "tail"};
-
-int cv_round(double v) { return (int)std::nearbyint(v); }
 
 }  // namespace
 
@@ -74,8 +66,9 @@ struct vistaf_ftp_handle {
     bool keep_planes = false;                          // test hook: also write planes that only the parity tests read (float64 field)
 
     // workspace (maxB frames)
-    std::map<std::string, std::pair<void *, size_t>> named;   // name -> (ptr, bytes per frame)
-    std::vector<void *> allocs;
+    struct Named { void *p; size_t bytes; bool per_frame; };   // bytes: per frame, or of the whole plane when it is static
+    std::map<std::string, Named> named;
+    DeviceAllocs allocs;
     float *img, *grad, *tmpf, *blurA, *inorm, *iw, *amp, *prod, *quality, *wrapped, *unwrapped, *phase1, *resid0, *detr, *z0, *mplane,
         *num, *den, *hmap, *dist, *z0f, *snum, *unitless, *depth;
     double2 *field, *patch;
@@ -116,37 +109,19 @@ namespace {
 template <typename T>
 int dalloc(vistaf_ftp_handle *hd, T **p, size_t count, const char *name = nullptr, size_t per_frame = 0)
 {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-    if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    hd->allocs.push_back(q);
-    *p = (T *)q;
-    if (name) hd->named[name] = {q, per_frame};
-    return 0;
-}
-
-// taps of cv::GaussianBlur(src, (0, 0), sigma) for CV_32F: ksize rule and float32 taps of cv::getGaussianKernel.  0: ok
-int gauss_taps(double sigma, std::vector<float> &f)
-{
-    int n = cv_round(sigma * 4 * 2 + 1) | 1;       // cv::GaussianBlur ksize rule, CV_32F
-    if (n > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
-    std::vector<double> t(n);
-    double s2 = -0.5 / (sigma * sigma), sum = 0;
-    for (int i = 0; i < n; i++) { double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-    f.resize(n);
-    for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-    return 0;
+    const int rc = hd->allocs.alloc(p, count);
+    if (!rc && name) hd->named[name] = {*p, per_frame, true};
+    return rc;
 }
 
 int make_gkern(vistaf_ftp_handle *hd, double sigma, GKern *g)
 {
     g->k = 0; g->d = nullptr;
     if (!(sigma > 0)) return 0;
-    std::vector<float> f;
-    int rc = gauss_taps(sigma, f);
-    if (rc) return rc;
+    if (gauss_ksize(sigma) > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
+    const std::vector<float> f = gauss_taps(sigma);
     const int n = (int)f.size();
-    rc = dalloc(hd, &g->d, n);
+    int rc = dalloc(hd, &g->d, n);
     if (rc) return rc;
     if (hipMemcpy(g->d, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(VISTAF_E_HIP, "memcpy gkern");
     g->k = n;
@@ -183,16 +158,7 @@ int make_se(int k, RowSpanSE *se, bool force_odd = true)
 {
     if (force_odd) k = std::max(3, k | 1);
     if (k > 33) return fail(VISTAF_E_INVALID, "structuring element larger than 33");
-    se->k = k;
-    int r = k / 2, c = k / 2;
-    double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
-    for (int i = 0; i < k; i++) {
-        int dy = i - r;
-        int dx = cv_round(c * std::sqrt((r * r - dy * dy) * inv_r2));
-        int j1 = std::max(c - dx, 0), j2 = std::min(c + dx + 1, k);
-        se->lo[i] = (int8_t)(j1 - c);
-        se->hi[i] = (int8_t)(j2 - 1 - c);
-    }
+    *se = ellipse_se(k);
     return 0;
 }
 
@@ -203,6 +169,9 @@ void blur(vistaf_ftp_handle *hd, const float *src, float *dst, const GKern &g, i
 
 // whether the element-wise passes around this blur run inside its tile (k_blurchain.hip): short kernels only, Tiers::fused_chains
 bool fuses(const vistaf_ftp_handle *hd, const GKern &g) { return hd->tiers.fused_chains && g.k > 0 && g.k <= GF_MAXK; }
+
+// scratch of the k_big.hip chains, or null when the one-workgroup kernels are to run (Tiers::big_chain)
+void *chain_scratch(const vistaf_ftp_handle *hd) { return hd->tiers.big_chain ? hd->big_scratch : nullptr; }
 
 float q32_of(double pct) { return (float)pct / 100.0f; }   // np.true_divide(q, float32(100))
 
@@ -228,8 +197,8 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);
     if (c.bad_pixel_enable) {
         launch_sobel_mag(hd->img, hd->grad, B, h, w, st);
-        launch_select(hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
-        launch_select(hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+        launch_select(hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, P, st, chain_scratch(hd));
+        launch_select(hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, P, st, chain_scratch(hd));
         launch_bad_flags(hd->img, hd->grad, hd->valid, hd->thr_hi, hd->thr_g, hd->bad0, B, P, st);
         uint8_t *src = hd->bad0, *dst = hd->bad1;
         if (c.bad_dilate_ksize > 1)
@@ -279,7 +248,7 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
         if (hd->g_pre.k) { blur(hd, hd->inorm, hd->blurA, hd->g_pre, B, st); in = hd->blurA; }
         launch_mul_static(in, hd->apo, hd->iw, B, P, st);
     }
-    launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, chain_scratch(hd));
 }
 
 // np.hanning(ph)[:,None] * np.hanning(pw)[None,:] in float32 (shape_ftp.py:800-807); np.hanning(M) = 0.5 + 0.5*cos(pi*n/(M-1)), n = 1-M, 3-M, ...
@@ -290,6 +259,23 @@ std::vector<float> hann_patch(int ph, int pw)
     for (int a = 0; a < ph; a++)
         for (int c = 0; c < pw; c++) win[(size_t)a * pw + c] = hann(ph, a) * hann(pw, c);
     return win;
+}
+
+// scale, calibration and carriers of the force tail and the per-contact read-out; pair_geom: per-frame carriers (pair mode) or null
+PostParams post_params(const vistaf_ftp_handle *hd, const CarrierGeom *pair_geom)
+{
+    PostParams pp;
+    pp.mm_per_px = hd->mm_per_px; pp.depth_eps_mm = hd->cfg.depth_eps_mm; pp.period_px = hd->period; pp.force_curve = hd->fcurve;
+    pp.pair_geom = pair_geom; pp.grating_pitch_mm = hd->cfg.grating_pitch_mm;
+    return pp;
+}
+
+// the stage-timing events, created when a timed predict first needs them
+void ensure_events(vistaf_ftp_handle *hd)
+{
+    if (hd->ev_made) return;
+    for (int i = 0; i <= ST_COUNT; i++) hipEventCreate(&hd->ev[i]);
+    hd->ev_made = true;
 }
 
 template <typename T>
@@ -328,7 +314,7 @@ int vistaf_ftp_default_config(vistaf_ftp_config *c)
 void vistaf_ftp_destroy(vistaf_ftp_handle *hd)
 {
     if (!hd) return;
-    for (void *p : hd->allocs) hipFree(p);
+    hd->allocs.free_all();
     if (hd->ev_made) for (int i = 0; i <= ST_COUNT; i++) hipEventDestroy(hd->ev[i]);
     delete hd;
 }
@@ -377,7 +363,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
             roif[(size_t)y * w + x] = roi[(size_t)y * w + x] ? 1.f : 0.f;
         }
     TRY(upload(hd, &hd->roi, roi)); TRY(upload(hd, &hd->valid, valid)); TRY(upload(hd, &hd->apo, apo));
-    hd->named["roi"] = {hd->roi, 0};
+    hd->named["roi"] = {hd->roi, (size_t)P, false};
     TRY(make_gkern(hd, cfg->illum_sigma_px, &hd->g_illum));
     if (!hd->g_illum.k) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_INVALID, "illum_sigma_px must be > 0"); }
     TRY(make_gkern(hd, cfg->pre_blur_sigma_px, &hd->g_pre));
@@ -430,7 +416,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     TRY(dalloc(hd, &hd->Ey, (size_t)h * pmax)); TRY(dalloc(hd, &hd->Gy, (size_t)h * pmax));
     TRY(dalloc(hd, &hd->win, (size_t)pmax * pmax)); TRY(dalloc(hd, &hd->geom, 1));
     TRY(dalloc(hd, &hd->cref, (size_t)P)); TRY(dalloc(hd, &hd->amp_ref, (size_t)P));
-    hd->named["cref"] = {hd->cref, 0}; hd->named["amp_ref"] = {hd->amp_ref, 0};
+    hd->named["cref"] = {hd->cref, (size_t)P * sizeof(double2), false}; hd->named["amp_ref"] = {hd->amp_ref, (size_t)P * sizeof(float), false};
     size_t mb = max_batch;
     TRY(dalloc(hd, &hd->thr_hi, mb)); TRY(dalloc(hd, &hd->thr_g, mb)); TRY(dalloc(hd, &hd->mu, mb)); TRY(dalloc(hd, &hd->amp_thr, mb));
     TRY(dalloc(hd, &hd->thr3, mb * 3)); TRY(dalloc(hd, &hd->thr_used, mb)); TRY(dalloc(hd, &hd->bg_med, mb));
@@ -447,9 +433,9 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
         TRY(dalloc(hd, &cs.arg, n)); TRY(dalloc(hd, &cs.list, mb * cs.cap)); TRY(dalloc(hd, &cs.nroots, mb)); TRY(dalloc(hd, &cs.nsel, mb));
         TRY(dalloc(hd, &cs.selkey, mb * VISTAF_MAX_CONTACTS)); TRY(dalloc(hd, &cs.part, contact_part_words(max_batch, P)));
     }
-    hd->named["mu"] = {hd->mu, sizeof(float)}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float)}; hd->named["thr_g"] = {hd->thr_g, sizeof(float)};
-    hd->named["coef"] = {hd->coef, 6 * sizeof(float)}; hd->named["thr3"] = {hd->thr3, 3 * sizeof(float)};
-    hd->named["core_thr"] = {hd->core_thr, sizeof(float)}; hd->named["core_med"] = {hd->core_med, sizeof(float)};
+    hd->named["mu"] = {hd->mu, sizeof(float), true}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float), true}; hd->named["thr_g"] = {hd->thr_g, sizeof(float), true};
+    hd->named["coef"] = {hd->coef, 6 * sizeof(float), true}; hd->named["thr3"] = {hd->thr3, 3 * sizeof(float), true};
+    hd->named["core_thr"] = {hd->core_thr, sizeof(float), true}; hd->named["core_med"] = {hd->core_med, sizeof(float), true};
     TRY(upload_req(hd, &hd->req_hi, {q32_of(cfg->bad_intensity_percentile)}));
     TRY(upload_req(hd, &hd->req_g, {q32_of(cfg->bad_gradient_percentile)}));
     TRY(upload_req(hd, &hd->req_med, {-1.0f}));
@@ -495,10 +481,7 @@ static int reference_search(vistaf_ftp_handle *hd, int nb, CarrierGeom *geom_dev
         const int cap = std::min(std::max(nb, 2 * hd->search_cap), std::max(nb, hd->maxB));
         if (hd->search_cap > 0) {
             HIPCHK(hipStreamSynchronize(st));          // earlier searches on this stream may still read the old set
-            for (void *q : {(void *)hd->search_tmp, (void *)hd->search_mag, (void *)hd->search_peaks}) {
-                auto it = std::find(hd->allocs.begin(), hd->allocs.end(), q);
-                if (it != hd->allocs.end()) { hipFree(q); hd->allocs.erase(it); }
-            }
+            hd->allocs.release(hd->search_tmp); hd->allocs.release(hd->search_mag); hd->allocs.release(hd->search_peaks);
             hd->search_tmp = nullptr; hd->search_mag = nullptr; hd->search_peaks = nullptr; hd->search_cap = 0;
         }
         if ((rc = dalloc(hd, &hd->search_tmp, (size_t)cap * h * (Wf / 2 + 1) + 64)) || (rc = dalloc(hd, &hd->search_mag, (size_t)cap * Hf * Wf)) ||
@@ -519,7 +502,7 @@ int vistaf_ftp_set_reference(vistaf_ftp_handle *hd, const void *d_ref, int forma
     if (format < 0 || format > 3) return fail(VISTAF_E_INVALID, "bad frame format");
     hipStream_t st = (hipStream_t)stream;
     const vistaf_ftp_config &c = hd->cfg;
-    int h = hd->h, w = hd->w, P = hd->P, Hf = hd->Hf, Wf = hd->Wf, pad = std::max(0, c.fft_pad_px);
+    int h = hd->h, w = hd->w, Hf = hd->Hf, Wf = hd->Wf, pad = std::max(0, c.fft_pad_px);
     hd->have_ref = false;
     HIPCHK(hipMemsetAsync(hd->status, 0, sizeof(int32_t) * hd->maxB, st));
     preprocess(hd, d_ref, format, 1, st, false);
@@ -545,7 +528,6 @@ int vistaf_ftp_set_reference(vistaf_ftp_handle *hd, const void *d_ref, int forma
     hd->period = g.period;
     hd->mm_per_px = hd->period > 1e-12 ? c.grating_pitch_mm / hd->period : 0.0;
     hd->have_ref = true;
-    (void)P;
     return 0;
 }
 
@@ -569,11 +551,10 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
 
     // ---- reliable mask (shape_ftp.py:739-775)
     if (timed) hipEventRecord(hd->ev[ST_RELIABLE], st);
-    const float *qual = hd->prod;
-    if (hd->g_qual.k) { blur(hd, hd->prod, hd->quality, hd->g_qual, B, st); qual = hd->quality; }
+    if (hd->g_qual.k) blur(hd, hd->prod, hd->quality, hd->g_qual, B, st);
     else HIPCHK(hipMemcpyAsync(hd->quality, hd->prod, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    qual = hd->quality;
-    launch_select(qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    const float *qual = hd->quality;
+    launch_select(qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, P, st, chain_scratch(hd));
     launch_threshold_mask(qual, hd->roi, hd->amp_thr, hd->rel0, B, P, st);
     {
         // MORPH_CLOSE with n iterations = n dilations then n erosions; the eroded-ROI mask applies to the result
@@ -619,11 +600,11 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     if (timed) hipEventRecord(hd->ev[ST_DETREND], st);
     if (c.plane_order_for_removal > 0)
         // debug_ramp gates on the reliable count, NaN pixels included (:1364-1366), robust_polyfit2d on 200 finite samples (:1103)
-        launch_robust_polyfit(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+        launch_robust_polyfit(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, B, h, w, st, chain_scratch(hd));
     else   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
-    launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
+    launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, chain_scratch(hd));
     launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
                         hd->contact, hd->thr_used, B, P, st);
     {
@@ -645,8 +626,8 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         }
     }
     launch_background(hd->reliable, hd->contact_d, hd->rel_count, hd->bg_count, hd->background, B, P, st);
-    launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
-    launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, chain_scratch(hd));
+    launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, chain_scratch(hd));
 
     // ---- reliable-only smoothing + sign flip (shape_ftp.py:1753-1768)
     if (timed) hipEventRecord(hd->ev[ST_SMOOTH_FLIP], st);
@@ -658,8 +639,8 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         blur(hd, hd->mplane, hd->den, hd->g_rel, B, st);
         launch_div_planes(hd->num, hd->den, hd->hmap, B, P, st);
     } else launch_zeroed_keep_nan(hd->detr, hd->bg_med, hd->reliable, hd->hmap, B, P, st);      // NaN stays NaN: the hole stage below is live
-    launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
-    launch_select(hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+    launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, P, st, chain_scratch(hd));
+    launch_select(hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, P, st, chain_scratch(hd));
     launch_core_flip(hd->hmap, hd->core_med, hd->flipped, B, P, st);
 
     // ---- internal holes of the reliable region (shape_ftp.py:1770-1801): with the smoothing every reliable pixel is finite here and
@@ -669,9 +650,9 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         const int ksz = std::max(3, c.hole_neighborhood_px | 1);
         launch_chamfer(hd->reliable, false, hd->rowdist, hd->dist, B, h, w, c.hole_min_dist_px + 1, st, hd->tiers.chamfer_twopass != 0);
         launch_hole_candidates(hd->hmap, hd->reliable, hd->dist, ksz, (float)c.hole_known_fraction, (float)c.hole_min_dist_px, hd->hole_cand, B, h, w, st);
-        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, P, st, chain_scratch(hd));
         launch_hole_tmp(hd->hmap, hd->reliable, hd->hole_cand, hd->hole_med, hd->z0, B, P, st);
-        launch_select(hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr);
+        launch_select(hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, P, st, chain_scratch(hd));
         launch_hole_zin(hd->z0, hd->hole_fill, B, P, st);
         {
             const int range = std::min(100, std::max(1, cv_round((double)c.inpaint_radius)));
@@ -706,9 +687,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // ---- unitless -> mm, blob filter (shape_ftp.py:1850-1873)
     if (timed) hipEventRecord(hd->ev[ST_MM_BLOB], st);
     if (!fuse_compose) launch_to_mm(hd->unitless, hd->roi, hd->hcurve, hd->use_neg, hd->depth, hd->cand, hd->gmax, B, P, st);
-    PostParams pp;
-    pp.mm_per_px = hd->mm_per_px; pp.depth_eps_mm = c.depth_eps_mm; pp.period_px = hd->period; pp.force_curve = hd->fcurve;
-    pp.pair_geom = pair_geom; pp.grating_pitch_mm = c.grating_pitch_mm;
+    const PostParams pp = post_params(hd, pair_geom);
     // frames whose label forest fits LDS: labels, blob filter, force tail + arg-extrema and the copy to the caller's planes in one launch
     // (stage timing: the whole launch counts as mm_blob, and the tail stage below is left with k_fill_scalars and the two small copies)
     const bool fused_backend = hd->tiers.fused_backend && backend_fused_fits(h, w);
@@ -725,7 +704,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     // ---- force tail (multimodal_sensor.py:388-419) + arg-extrema
     if (timed) hipEventRecord(hd->ev[ST_TAIL], st);
     if (!fused_backend)
-        launch_tail(hd->depth, nullptr, hd->unitless, hd->roi, pp, hd->scalars, VISTAF_NSCALARS, nullptr, B, P, st, hd->tiers.big_chain ? hd->big_scratch : nullptr,
+        launch_tail(hd->depth, nullptr, hd->unitless, hd->roi, pp, hd->scalars, VISTAF_NSCALARS, nullptr, B, P, st, chain_scratch(hd),
                     hd->big_scratch ? big_scratch_bytes(hd->maxB, h, w) : 0);
     launch_fill_scalars(hd->scalars, VISTAF_NSCALARS, hd->rel_count, hd->flipped, hd->amp_thr, hd->thr_used, hd->bg_med, bad_count, B, st);
     if (!fused_backend) launch_copy_out(hd->depth, orel, hd->status, d_height_mm, d_reliable, B, P, st);
@@ -739,8 +718,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
 #ifdef VISTAF_DEBUG
     if (getenv("VISTAF_TELEA_DBG")) { hipStreamSynchronize(st); telea_debug_dump(); telea_window_debug_dump(B); telea_window_mw_debug_dump(B); fit_debug_dump(); unwrap_big_debug_dump(); unwrap_batch_debug_dump(); }
 #endif
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
+    if (const int rc = launch_ok("launch")) return rc;
     hd->last_batch = B; hd->last_pairs = pair_geom != nullptr;
     return 0;
 }
@@ -756,7 +734,7 @@ int vistaf_ftp_predict_batch(vistaf_ftp_handle *hd, const void *d_frames, int fo
     hipStream_t st = (hipStream_t)stream;
     int h = hd->h, w = hd->w;
     bool timed = hd->timing;
-    if (timed && !hd->ev_made) { for (int i = 0; i <= ST_COUNT; i++) hipEventCreate(&hd->ev[i]); hd->ev_made = true; }
+    if (timed) ensure_events(hd);
     HIPCHK(hipMemsetAsync(hd->status, 0, sizeof(int32_t) * B, st));
 
     preprocess(hd, d_frames, format, B, st, timed);
@@ -782,7 +760,7 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
     const vistaf_ftp_config &c = hd->cfg;
     int h = hd->h, w = hd->w, P = hd->P, pad = std::max(0, c.fft_pad_px), pm = hd->pmax;
     bool timed = hd->timing;
-    if (timed && !hd->ev_made) { for (int i = 0; i <= ST_COUNT; i++) hipEventCreate(&hd->ev[i]); hd->ev_made = true; }
+    if (timed) ensure_events(hd);
     if (!hd->pairs_ready) {
         int rc;
         size_t mb = hd->maxB;
@@ -848,15 +826,10 @@ int vistaf_ftp_contacts(vistaf_ftp_handle *hd, int B, int max_contacts, double *
     if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return fail(VISTAF_E_INVALID, "max_contacts must be 1..64");
     if (hd->last_batch == 0) return fail(VISTAF_E_STATE, "no predict_batch / predict_pairs before contacts");
     if (B != hd->last_batch) return fail(VISTAF_E_STATE, "batch differs from the last predict's");
-    const vistaf_ftp_config &c = hd->cfg;
-    PostParams pp;      // as the tail takes them
-    pp.mm_per_px = hd->mm_per_px; pp.depth_eps_mm = c.depth_eps_mm; pp.period_px = hd->period; pp.force_curve = hd->fcurve;
-    pp.pair_geom = hd->last_pairs ? hd->pgeom : nullptr; pp.grating_pitch_mm = c.grating_pitch_mm;
+    const PostParams pp = post_params(hd, hd->last_pairs ? hd->pgeom : nullptr);      // as the tail took them
     launch_contacts(hd->depth, hd->kept, hd->labels, hd->peak_bits, hd->status, pp, hd->contacts_ws, max_contacts, d_contacts, VISTAF_NCONTACT, d_count,
                     d_contact_index, B, hd->h, hd->w, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return 0;
+    return launch_ok("launch");
 }
 
 int vistaf_ftp_get_intermediate(vistaf_ftp_handle *hd, const char *name, void *d_dst, int batch, size_t *bytes_per_frame, void *stream)
@@ -864,10 +837,9 @@ int vistaf_ftp_get_intermediate(vistaf_ftp_handle *hd, const char *name, void *d
     if (!hd || !name) return fail(VISTAF_E_INVALID, "null argument");
     auto it = hd->named.find(name);
     if (it == hd->named.end()) return fail(VISTAF_E_INVALID, std::string("unknown intermediate: ") + name);
-    size_t per = it->second.second;
-    size_t total = per ? per * (size_t)batch : (std::string(name) == "cref" ? (size_t)hd->P * sizeof(double2) : std::string(name) == "amp_ref" ? (size_t)hd->P * sizeof(float) : (size_t)hd->P);
-    if (bytes_per_frame) *bytes_per_frame = per ? per : total;
-    if (d_dst) HIPCHK(hipMemcpyAsync(d_dst, it->second.first, total, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const vistaf_ftp_handle::Named &pl = it->second;
+    if (bytes_per_frame) *bytes_per_frame = pl.bytes;
+    if (d_dst) HIPCHK(hipMemcpyAsync(d_dst, pl.p, pl.per_frame ? pl.bytes * (size_t)batch : pl.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
 
@@ -960,9 +932,8 @@ int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int 
 int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream)
 {
     if (!src || !dst || src == dst || B < 1 || h < 1 || w < 1 || !(sigma > 0)) return fail(VISTAF_E_INVALID, "bad argument");
-    std::vector<float> f;
-    int rc = gauss_taps(sigma, f);
-    if (rc) return rc;
+    if (gauss_ksize(sigma) > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
+    const std::vector<float> f = gauss_taps(sigma);
     float *taps = nullptr, *tmp = nullptr;
     HIPCHK(hipMalloc((void **)&taps, f.size() * sizeof(float)));
     if (hipMalloc((void **)&tmp, (size_t)B * h * w * sizeof(float)) != hipSuccess) { (void)hipFree(taps); return fail(VISTAF_E_HIP, "hipMalloc"); }
@@ -995,9 +966,7 @@ int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int 
     PostParams pp;
     pp.mm_per_px = mm_per_px; pp.depth_eps_mm = depth_eps_mm; pp.period_px = 0; pp.force_curve = Curve{0, 0, 0, 0};
     launch_tail(d_height, d_roi, nullptr, nullptr, pp, nullptr, 0, d_out, batch, h * w, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return 0;
+    return launch_ok("launch");
 }
 
 int vistaf_predict_force_from_volume(const vistaf_curve *curve, double volume_cm3, double *force_out)

@@ -36,6 +36,10 @@ __device__ inline float key2f(uint32_t k)
 }
 
 __device__ inline bool finitef(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+__device__ inline bool finitef(double v) { return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
+// the quiet NaN every kernel writes (NumPy's np.nan bits)
+__device__ inline float nanf32() { return __uint_as_float(0x7fc00000u); }
+__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // ---- wave-level reductions on the DPP network (no LDS round trips): quad xor 1, quad xor 2, row_half_mirror,
 // row_mirror leave the row result in every lane of a 16-lane row; row_bcast15 / row_bcast31 then carry it
@@ -91,6 +95,48 @@ __device__ inline unsigned long long wave_max_u64(unsigned long long v)
 __device__ inline unsigned long long wave_min_u64(unsigned long long v)
 {
     return wave_reduce_raw<unsigned long long>(v, ~0ull, [](unsigned long long a, unsigned long long b) { return b < a ? b : a; });
+}
+
+// ---- wave-level inclusive scans on the same network: row_shr 1/2/4/8 scan each 16-lane row (bound_ctrl: lanes without a source read 0),
+// row_bcast15 / row_bcast31 then add the totals of the rows below.  0 must be op's identity (sums; maxima of values >= 0).
+template <typename F>
+__device__ inline uint32_t wave_scan_raw(uint32_t v, F op)
+{
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true));
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true));
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true));
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true));
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false));
+    v = op(v, (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+__device__ inline uint32_t wave_scan_add(uint32_t v) { return wave_scan_raw(v, [](uint32_t a, uint32_t b) { return a + b; }); }
+__device__ inline int wave_scan_add(int v) { return (int)wave_scan_add((uint32_t)v); }
+__device__ inline uint32_t wave_scan_max(uint32_t v) { return wave_scan_raw(v, [](uint32_t a, uint32_t b) { return b > a ? b : a; }); }
+// exclusive prefix sum and the wave total
+__device__ inline int wave_excl_scan(int v, int &total)
+{
+    const int incl = wave_scan_add(v);
+    total = __builtin_amdgcn_readlane(incl, 63);
+    return incl - v;
+}
+// the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1); the lane without a source takes `fill`
+__device__ inline uint32_t wave_shr1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false); }
+__device__ inline int wave_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }
+__device__ inline int wave_shl1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }
+
+// ---- cv::warpAffine's fixed-point source coordinates (WarpAffineInvoker)
+constexpr int AB_BITS = 10, AB_SCALE = 1 << AB_BITS, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
+struct Aff { double m[6]; };      // source = M * (x, y, 1): the inverse map warpAffine iterates with
+__device__ inline long long cvr(double v) { return __double2ll_rn(v); }          // cvRound / saturate_cast<int>(double): half to even
+// source coordinate of destination pixel (x, y).  INTER_LINEAR: round_delta = AB_SCALE / INTER_TAB / 2, shift = AB_BITS - INTER_BITS (integer
+// part and 1/32 fraction); INTER_NEAREST: round_delta = AB_SCALE / 2, shift = AB_BITS
+__device__ inline void warp_src_coord(const Aff &a, int x, int y, int round_delta, int shift, int &X, int &Y)
+{
+    const long long ad = cvr(a.m[0] * x * AB_SCALE), bd = cvr(a.m[3] * x * AB_SCALE);
+    const long long X0 = cvr((a.m[1] * y + a.m[2]) * AB_SCALE) + round_delta, Y0 = cvr((a.m[4] * y + a.m[5]) * AB_SCALE) + round_delta;
+    X = (int)((X0 + ad) >> shift);
+    Y = (int)((Y0 + bd) >> shift);
 }
 
 // block-wide sum for blockDim.x <= 1024; `scratch` must hold 16 elements of T; result valid in all threads

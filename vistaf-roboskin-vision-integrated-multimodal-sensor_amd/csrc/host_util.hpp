@@ -1,0 +1,116 @@
+// Host-side plumbing shared by the translation units behind the C ABI (api.hip, align.hip, tempseg.hip, tempsensor.hip, k_tempmodel.hip,
+// k_tracks.hip): error reporting, the owning list of device allocations, and the OpenCV constant tables (Gaussian taps, structuring
+// elements) that more than one modality builds.  Host only; nothing here launches a kernel.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "../../include/vistaf_ftp.h"
+#include "kernels.hpp"
+
+struct vistaf_tempseg_handle;
+
+namespace vf {
+
+// records the calling thread's last-error text (vistaf_ftp_last_error) and returns `code`; defined in api.hip
+int set_error(int code, const std::string &msg);
+
+#define HIPCHK(x)                                                                                                     \
+    do {                                                                                                              \
+        const hipError_t e_ = (x);                                                                                    \
+        if (e_ != hipSuccess) return vf::set_error(VISTAF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));    \
+    } while (0)
+#define FCHK(x)                                                                                                                            \
+    do {                                                                                                                                   \
+        const hipfftResult r_ = (x);                                                                                                       \
+        if (r_ != HIPFFT_SUCCESS) return vf::set_error(VISTAF_E_HIP, std::string(#x) + ": hipfft error " + std::to_string((int)r_));      \
+    } while (0)
+
+// after a run of launches: 0, or VISTAF_E_HIP with "<what>: <the runtime's text>"
+inline int launch_ok(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_error(VISTAF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The device buffers a handle owns; every buffer carries 256 bytes of padding behind its last element.
+struct DeviceAllocs {
+    std::vector<void *> ptrs;
+    template <typename T>
+    int alloc(T **p, size_t count)
+    {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
+        if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+        ptrs.push_back(q);
+        *p = (T *)q;
+        return 0;
+    }
+    void release(void *p)       // one buffer before the others; null and foreign pointers are ignored
+    {
+        const auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (p && it != ptrs.end()) { (void)hipFree(p); ptrs.erase(it); }
+    }
+    void free_all()
+    {
+        for (void *p : ptrs) (void)hipFree(p);
+        ptrs.clear();
+    }
+};
+
+inline int cv_round(double v) { return (int)std::nearbyint(v); }      // cvRound: half to even
+inline int odd_up(int k) { return (k % 2) ? k : k + 1; }
+inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
+
+// cv::GaussianBlur(src, (0, 0), sigma) on CV_32F: the ksize rule, and the float32 taps of cv::getGaussianKernel for that size.  Callers cap
+// the size themselves (their kernels differ in the longest filter they take).
+inline int gauss_ksize(double sigma) { return cv_round(sigma * 4 * 2 + 1) | 1; }
+inline std::vector<float> gauss_taps(double sigma)
+{
+    const int n = gauss_ksize(sigma);
+    std::vector<double> t(n);
+    const double s2 = -0.5 / (sigma * sigma);
+    double sum = 0;
+    for (int i = 0; i < n; i++) { const double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
+    std::vector<float> f(n);
+    for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
+    return f;
+}
+
+// cv::getStructuringElement(MORPH_ELLIPSE, (k, k)) as row spans, anchor at (k/2, k/2); k <= 33 (checked by the callers)
+inline RowSpanSE ellipse_se(int k)
+{
+    RowSpanSE se;
+    se.k = k;
+    const int r = k / 2, c = k / 2;
+    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+    for (int i = 0; i < 33; i++) { se.lo[i] = 1; se.hi[i] = -1; }
+    for (int i = 0; i < k; i++) {
+        const int dy = i - r;
+        const int dx = cv_round(c * std::sqrt((r * r - dy * dy) * inv_r2));
+        const int j1 = std::max(c - dx, 0), j2 = std::min(c + dx + 1, k);
+        se.lo[i] = (int8_t)(j1 - c);
+        se.hi[i] = (int8_t)(j2 - 1 - c);
+    }
+    return se;
+}
+// MORPH_RECT kx x ky: ky <= 33 rows of the same span
+inline RowSpanSE rect_se(int kx, int ky)
+{
+    RowSpanSE se;
+    se.k = ky;
+    for (int i = 0; i < 33; i++) { se.lo[i] = (int8_t)(-(kx / 2)); se.hi[i] = (int8_t)(kx / 2); }
+    return se;
+}
+
+// tempseg.hip, for the temperature session (tempsensor.hip): both workspaces of a segmentation session at once, and the two halves of
+// the oriented blur (taps uploaded once, the blur itself asynchronous on taps already on the device)
+int tempseg_prepare(vistaf_tempseg_handle *h);
+int temp_blur_taps(double sigma_across, double sigma_along, float *d_kx, int &nx, float *d_ky, int &ny, hipStream_t st);
+int temp_blur_apply(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double angle_rad, const float *d_kx, int nx, const float *d_ky,
+                    int ny, float *d_out, hipStream_t st);
+
+}  // namespace vf

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include "kernels.hpp"
 #include "select.hpp"
+#include "chol.hpp"
 
 namespace vf {
 
@@ -375,21 +376,6 @@ __global__ __launch_bounds__(FB_T) void k_fb_sums(const float *__restrict__ z_al
     }
 }
 
-template <int N>
-__device__ inline bool fb_chol(double (&A)[6][6], double (&rhs)[6])
-{
-    double L[N][N], inv[N];
-    for (int i = 0; i < N; i++)
-        for (int j = 0; j <= i; j++) {
-            double s = A[i][j];
-            for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k];
-            if (i == j) { if (!(s > 0.0)) return false; L[i][i] = sqrt(s); inv[i] = 1.0 / L[i][i]; }
-            else L[i][j] = s * inv[j];
-        }
-    for (int i = 0; i < N; i++) { double s = rhs[i]; for (int k = 0; k < i; k++) s -= L[i][k] * rhs[k]; rhs[i] = s * inv[i]; }
-    for (int i = N - 1; i >= 0; i--) { double s = rhs[i]; for (int k = i + 1; k < N; k++) s -= L[k][i] * rhs[k]; rhs[i] = s * inv[i]; }
-    return true;
-}
 constexpr int FS_CHUNKS = 12;           // 21 * 12 = 252 threads
 // partials in block order -> coefficients; the value range of the residuals for the two selections (bounds on |fit|, as k_fit.hip)
 __global__ __launch_bounds__(256) void k_fb_solve(FitState *fs, const double *partial, SbFrame *sel_fr, int nblk, int order)
@@ -423,7 +409,7 @@ __global__ __launch_bounds__(256) void k_fb_solve(FitState *fs, const double *pa
             for (int j = 0; j < 6; j++) A[i][j] = mono(ea[i] + ea[j], eb[i] + eb[j]);
             rhs[i] = s_sum[15 + i];
         }
-        const bool ok = nc == 6 ? fb_chol<6>(A, rhs) : fb_chol<3>(A, rhs);
+        const bool ok = nc == 6 ? chol_solve<6>(A, rhs) : chol_solve<3>(A, rhs);
         float fb = 0.f;
         for (int i = 0; i < 6; i++) { s.coef[i] = (ok && i < nc) ? (float)rhs[i] : 0.f; fb += fabsf(s.coef[i]); }
         fb = fb * 1.0001f + 1e-30f;

@@ -376,8 +376,6 @@ __global__ void k_chamfer_cols(const int32_t *__restrict__ g, float *__restrict_
 constexpr int CH2_INF = 0x7fffffff >> 2;     // cv DIST_MAX: border / initial value of the temporary plane
 __host__ __device__ constexpr int ch2_ring(int ppl) { return ppl == 4 ? 31 : ppl == 8 ? 15 : 6; }
 
-__device__ inline int ch2_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }   // lane l <- l-1
-__device__ inline int ch2_shl1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x130, 0xf, 0xf, false); }   // lane l <- l+1
 // inclusive prefix minimum over lanes 0..l
 __device__ inline int ch2_scan_min_up(int v)
 {
@@ -484,7 +482,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
             for (int r = 0; r < RING; r++) {
                 const int y = y0 + r;
                 if (y >= h) break;
-                const int upl = ch2_shr1(up[PPL - 1], CH2_INF), upr = ch2_shl1(up[0], CH2_INF);
+                const int upl = wave_shr1(up[PPL - 1], CH2_INF), upr = wave_shl1(up[0], CH2_INF);
                 int t[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
@@ -502,7 +500,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
 #pragma unroll
                 for (int j = 1; j < PPL; j++) { int v = t[j - 1] + CH_HV; t[j] = v < t[j] ? v : t[j]; }
                 const int sc = ch2_scan_min_up(t[PPL - 1] - step * lane) + step * lane;      // final value of this lane's last column
-                const int carry = ch2_shr1(sc, CH2_INF);                                     // d(x0 - 1)
+                const int carry = wave_shr1(sc, CH2_INF);                                     // d(x0 - 1)
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     int v = carry + CH_HV * (j + 1);
@@ -526,7 +524,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
             for (int r = 0; r < RING; r++) {
                 const int y = h - 1 - (y0 + r);
                 if (y < 0) break;
-                const int dnl = ch2_shr1(dn[PPL - 1], CH2_INF), dnr = ch2_shl1(dn[0], CH2_INF);
+                const int dnl = wave_shr1(dn[PPL - 1], CH2_INF), dnr = wave_shl1(dn[0], CH2_INF);
                 int t[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
@@ -547,7 +545,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
                 first = __builtin_amdgcn_ds_bpermute(ml << 2, first);
                 first = ch2_scan_min_up(first);
                 first = __builtin_amdgcn_ds_bpermute(ml << 2, first) + step * ml;            // final value of this lane's first column
-                const int carry = ch2_shl1(first, CH2_INF);                                  // d(x0 + PPL)
+                const int carry = wave_shl1(first, CH2_INF);                                  // d(x0 + PPL)
                 float o[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {

@@ -24,8 +24,6 @@ namespace vf {
 
 namespace {
 
-__device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
-
 // partial record of one contact: pixels, contact pixels (sums), x0, y0 (min), x1, y1 (max), then the float64 sums of depth, x * depth, y * depth
 constexpr int CT_NF = 9, CT_F_MIN = 2, CT_F_MAX = 4, CT_F_DBL = 6;
 constexpr int CT_CHUNK = 8192, CT_MAXK = 64;

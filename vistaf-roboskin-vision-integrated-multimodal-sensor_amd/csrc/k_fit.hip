@@ -24,6 +24,7 @@ namespace vf { __device__ unsigned long long g_fit_dbg[16]; __device__ unsigned 
 #define FIT_START() do { } while (0)
 #endif
 #include "select.hpp"
+#include "chol.hpp"
 
 namespace vf {
 
@@ -78,41 +79,6 @@ struct FitCtx {
         return ok;
     }
 };
-
-// solve the symmetric positive definite N x N system in place (fully unrolled: everything stays in registers);
-// returns false if not SPD
-template <int N>
-__device__ inline bool chol_solve(double (&A)[6][6], double (&rhs)[6])
-{
-    // one reciprocal per pivot (the 27 divisions of the textbook form are a long dependent chain on the one thread that solves)
-    double L[N][N], inv[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            double s = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= L[i][k] * L[j][k];
-            if (i == j) { if (!(s > 0.0)) return false; L[i][i] = sqrt(s); inv[i] = 1.0 / L[i][i]; }
-            else L[i][j] = s * inv[j];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        double s = rhs[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= L[i][k] * rhs[k];
-        rhs[i] = s * inv[i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; i--) {
-        double s = rhs[i];
-#pragma unroll
-        for (int k = i + 1; k < N; k++) s -= L[k][i] * rhs[k];
-        rhs[i] = s * inv[i];
-    }
-    return true;
-}
 
 __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restrict__ z_all, const uint8_t *__restrict__ mask_all, int order,
                                                           int iters, float c, int min_count, int min_mask_count, float *__restrict__ coef_out,

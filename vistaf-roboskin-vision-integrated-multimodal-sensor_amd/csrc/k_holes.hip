@@ -14,8 +14,6 @@
 
 namespace vf {
 
-__device__ inline float hl_nan() { return __uint_as_float(0x7fc00000u); }
-
 // height_map = phase_zeroed = detrended - bg_med (:1750-1753): NaN wherever the detrended phase is (outside reliable, unreached pixels)
 __global__ void k_zeroed_keep_nan(const float *__restrict__ detr, const float *__restrict__ bg_med, const uint8_t *__restrict__ reliable,
                                   float *__restrict__ hmap, int P)
@@ -24,7 +22,7 @@ __global__ void k_zeroed_keep_nan(const float *__restrict__ detr, const float *_
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    hmap[i] = reliable[i] ? __fsub_rn(detr[i], bg_med[b]) : hl_nan();
+    hmap[i] = reliable[i] ? __fsub_rn(detr[i], bg_med[b]) : nanf32();
 }
 void launch_zeroed_keep_nan(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, int B, int P, hipStream_t st)
 {
@@ -74,7 +72,7 @@ __global__ void k_hole_tmp(const float *__restrict__ hmap, const uint8_t *__rest
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    float v = hl_nan();
+    float v = nanf32();
     if (reliable[i] && !cand[i]) {
         const float hv = hmap[i];
         float m = med[b];
@@ -115,7 +113,7 @@ __global__ void k_hole_merge(float *__restrict__ hmap, const uint8_t *__restrict
     float v = hmap[i];
     if (cand[i]) v = zin[i];
     const bool rel = reliable[i] != 0;
-    if (!rel) v = hl_nan();
+    if (!rel) v = nanf32();
     hmap[i] = v;
     out_rel[i] = (uint8_t)(rel && finitef(v));
 }

@@ -98,17 +98,6 @@ __device__ inline int tq_pop(TQueue &q, int lane)
     return __builtin_amdgcn_readfirstlane(idx);
 }
 
-// full-wave float sum (DPP butterfly; result uniform)
-__device__ inline float dpp_sum_f32(float x)
-{
-    int v = __float_as_int(x);
-#define VF_ADD(ctrl, rm)                                                                          \
-    v = __float_as_int(__int_as_float(v) + __int_as_float(__builtin_amdgcn_update_dpp(0, v, ctrl, rm, 0xf, false)));
-    VF_ADD(0xB1, 0xf) VF_ADD(0x4E, 0xf) VF_ADD(0x141, 0xf) VF_ADD(0x140, 0xf) VF_ADD(0x142, 0xa) VF_ADD(0x143, 0xc)
-#undef VF_ADD
-    return __int_as_float(__builtin_amdgcn_readlane(v, 63));
-}
-
 template <bool LF>
 __device__ inline float fmm_solve(const uint8_t *f, const float *t, int p1, int p2)
 {

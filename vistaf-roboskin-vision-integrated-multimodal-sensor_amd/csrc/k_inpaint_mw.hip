@@ -103,13 +103,6 @@ __device__ inline unsigned long long gp_key(float T, int g, int rank, int nb, in
     return ((unsigned long long)__float_as_uint(T) << 32) | ((unsigned long long)(((uint32_t)g << 27) | ((uint32_t)rank << 16) | ((uint32_t)nb << 14) | (uint32_t)cell));
 }
 __device__ inline bool gp_marked(unsigned v, uint16_t mb) { return (v & (FI_PEND | mb)) == (FI_PEND | mb); }
-__device__ inline int wave_excl_scan(int v, int lane, int &total)
-{
-    int s = v;
-    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(s, o, 64); if (lane >= o) s += u; }
-    total = __shfl(s, 63, 64);
-    return s - v;
-}
 
 // The pops of one generation on one wave.  A pop needs 16 lanes (4 neighbours x 4 quadrants), so the wave holds FOUR entries at a time, one
 // per 16-lane group: 4 x (the group's waves) entries of the generation are held, claimed in pop order (the first entry that has not popped
@@ -250,7 +243,7 @@ __device__ inline int gp_gen0(unsigned long long *gen, unsigned long long *gen2,
 #pragma unroll
         for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; a[k] = ch < nchunk ? cnt[ch] : 0; sum += a[k]; }
         int total;
-        int ex = wave_excl_scan(sum, lane, total);
+        int ex = wave_excl_scan(sum, total);
 #pragma unroll
         for (int k = 0; k < 4; k++) { const int ch = lane * 4 + k; if (ch < nchunk) cnt[ch] = ex; ex += a[k]; }
         if (lane == 0) ctl[MWC_GENN] = total;
@@ -329,7 +322,7 @@ __device__ __attribute__((always_inline)) inline bool gp_gens(const GenScratch &
 #pragma unroll
                 for (int k = 0; k < 4; k++) { a[k] = __popc(S.bitmap[lane * 4 + k]); sum += a[k]; }
                 int total;
-                int ex = wave_excl_scan(sum, lane, total);
+                int ex = wave_excl_scan(sum, total);
 #pragma unroll
                 for (int k = 0; k < 4; k++) { S.cnt[lane * 4 + k] = ex; ex += a[k]; }
             }
@@ -385,7 +378,7 @@ __device__ __attribute__((always_inline)) inline bool gp_gens(const GenScratch &
                 pos[k] = i < M ? atomicAdd(&S.cnt[bn[k]], 1) : 0;
             }
             G.sync();
-            if (G.wave == 0) { int total; S.cnt[GP_BINS + lane] = wave_excl_scan(S.cnt[lane], lane, total); }      // GP_BINS == 64 lanes
+            if (G.wave == 0) { int total; S.cnt[GP_BINS + lane] = wave_excl_scan(S.cnt[lane], total); }      // GP_BINS == 64 lanes
             G.sync();
 #pragma unroll
             for (int k = 0; k < K; k++) if (tid + k * nthr < M) S.gen[S.cnt[GP_BINS + bn[k]] + pos[k]] = my[k];

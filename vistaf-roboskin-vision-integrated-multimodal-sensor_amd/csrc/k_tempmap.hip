@@ -2,27 +2,9 @@
 // fuse_maps_per_pixel, oriented_gaussian_blur_float.  PARITY UNPINNED: the reference tree holds no output of these stages (its
 // temperature_map_*.npy are among the blobs that were not mounted) and the regressors that feed them only exist as pickles; the kernels are
 // checked on synthetic planes against the test suite's CPU restatement of the source text (temp_oracle.py).  All streaming, one thread per pixel.
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 namespace vf {
-
-namespace {
-constexpr int AB_BITS = 10, AB_SCALE = 1 << AB_BITS, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
-__device__ inline long long tm_cvr(double v) { return __double2ll_rn(v); }
-__device__ inline void tm_src_coord(const TmAff &a, int x, int y, int round_delta, int shift, int &X, int &Y)
-{
-    const long long ad = tm_cvr(a.m[0] * x * AB_SCALE), bd = tm_cvr(a.m[3] * x * AB_SCALE);
-    const long long X0 = tm_cvr((a.m[1] * y + a.m[2]) * AB_SCALE) + round_delta, Y0 = tm_cvr((a.m[4] * y + a.m[5]) * AB_SCALE) + round_delta;
-    X = (int)((X0 + ad) >> shift);
-    Y = (int)((Y0 + bd) >> shift);
-}
-__device__ inline int tm_reflect(int p, int n)       // BORDER_REFLECT
-{
-    if (n == 1) return 0;
-    while (p < 0 || p >= n) p = p < 0 ? -p - 1 : 2 * n - 1 - p;
-    return p;
-}
-}  // namespace
 
 // clamp_map (:538-543): clipped inside the ROI where finite, NaN outside
 __global__ void k_tm_clamp(const float *__restrict__ m, const uint8_t *__restrict__ roi, float lo, float hi, float *__restrict__ out, size_t P)
@@ -30,7 +12,7 @@ __global__ void k_tm_clamp(const float *__restrict__ m, const uint8_t *__restric
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
     float v = m[i];
-    if (!roi[i]) v = __uint_as_float(0x7fc00000u);
+    if (!roi[i]) v = nanf32();
     else if (finitef(v)) v = fminf(fmaxf(v, lo), hi);
     out[i] = v;
 }
@@ -78,7 +60,7 @@ __global__ void k_tm_unscale(const float *__restrict__ m, const uint8_t *__restr
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= P) return;
-    const float qnan = __uint_as_float(0x7fc00000u);
+    const float qnan = nanf32();
     if (!roi[i]) { out[i] = qnan; return; }
     const float v = m[i];
     if (stats[0] == 0 || stats[1] == 0) { out[i] = v; return; }
@@ -108,7 +90,7 @@ __global__ void k_tm_fuse(const uint8_t *__restrict__ roi, const float *__restri
             f = __fadd_rn(__fmul_rn(wgt, cv), __fmul_rn(__fsub_rn(1.0f, wgt), wv));
             s = 128;
         }
-        if (!r) f = __uint_as_float(0x7fc00000u);
+        if (!r) f = nanf32();
         else if (finitef(f)) f = fminf(fmaxf(f, c.final_lo), c.final_hi);
         fin[i] = f;
         if (source) source[i] = s;
@@ -134,9 +116,9 @@ __global__ void k_tm_warp_linear(const float *__restrict__ src, float *__restric
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
     int X, Y;
-    tm_src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
+    warp_src_coord(a, x, y, AB_SCALE / INTER_TAB / 2, AB_BITS - INTER_BITS, X, Y);
     const int sx = X >> INTER_BITS, sy = Y >> INTER_BITS, ax = X & (INTER_TAB - 1), ay = Y & (INTER_TAB - 1);
-    const int xa = tm_reflect(sx, w), xb = tm_reflect(sx + 1, w), ya = tm_reflect(sy, h), yb = tm_reflect(sy + 1, h);
+    const int xa = reflect_edge(sx, w), xb = reflect_edge(sx + 1, w), ya = reflect_edge(sy, h), yb = reflect_edge(sy + 1, h);
     const float fx = __fdiv_rn((float)ax, (float)INTER_TAB), fy = __fdiv_rn((float)ay, (float)INTER_TAB);
     const float gx = __fsub_rn(1.0f, fx), gy = __fsub_rn(1.0f, fy);
     const float w00 = __fmul_rn(gx, gy), w01 = __fmul_rn(fx, gy), w10 = __fmul_rn(gx, fy), w11 = __fmul_rn(fx, fy);
@@ -149,42 +131,40 @@ __global__ void k_tm_warp_nearest(const uint8_t *__restrict__ src, uint8_t *__re
     const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
     if (x >= w) return;
     int X, Y;
-    tm_src_coord(a, x, y, AB_SCALE / 2, AB_BITS, X, Y);
+    warp_src_coord(a, x, y, AB_SCALE / 2, AB_BITS, X, Y);
     dst[(size_t)y * w + x] = (X >= 0 && X < w && Y >= 0 && Y < h && src[(size_t)Y * w + X]) ? 1 : 0;
 }
 __global__ void k_tm_mask_nan(const float *__restrict__ m, const uint8_t *__restrict__ keep, float *__restrict__ out, size_t P)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < P) out[i] = keep[i] ? m[i] : __uint_as_float(0x7fc00000u);
+    if (i < P) out[i] = keep[i] ? m[i] : nanf32();
 }
-
-static inline dim3 g1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 
 void launch_tm_clamp(const float *m, const uint8_t *roi, float lo, float hi, float *out, size_t P, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_tm_clamp, g1(P), dim3(256), 0, st, m, roi, lo, hi, out, P);
+    hipLaunchKernelGGL(k_tm_clamp, grid1(P), dim3(256), 0, st, m, roi, lo, hi, out, P);
 }
 void launch_tm_stats(const float *m, const uint8_t *roi, uint32_t *stats, size_t P, hipStream_t st)
 {
     static const uint32_t init[4] = {0u, 0u, 0xFFFFFFFFu, 0u};
     (void)hipMemcpyAsync(stats, init, sizeof(init), hipMemcpyHostToDevice, st);
-    hipLaunchKernelGGL(k_tm_stats, g1(P), dim3(256), 0, st, m, roi, stats, P);
+    hipLaunchKernelGGL(k_tm_stats, grid1(P), dim3(256), 0, st, m, roi, stats, P);
 }
 void launch_tm_scale(const float *m, const uint8_t *roi, const uint32_t *stats, float *scaled, uint8_t *miss, size_t P, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_tm_scale, g1(P), dim3(256), 0, st, m, roi, stats, scaled, miss, P);
+    hipLaunchKernelGGL(k_tm_scale, grid1(P), dim3(256), 0, st, m, roi, stats, scaled, miss, P);
 }
 void launch_tm_unscale(const float *m, const uint8_t *roi, const uint32_t *stats, const float *filled, float *out, size_t P, hipStream_t st)
 {
-    hipLaunchKernelGGL(k_tm_unscale, g1(P), dim3(256), 0, st, m, roi, stats, filled, out, P);
+    hipLaunchKernelGGL(k_tm_unscale, grid1(P), dim3(256), 0, st, m, roi, stats, filled, out, P);
 }
 void launch_tm_fuse(const uint8_t *roi, const float *wide, const float *color, const TmFuse &c, float *fin, uint8_t *source, unsigned long long *counts, size_t P,
                     hipStream_t st)
 {
     if (counts) (void)hipMemsetAsync(counts, 0, 4 * sizeof(unsigned long long), st);
-    hipLaunchKernelGGL(k_tm_fuse, g1(P), dim3(256), 0, st, roi, wide, color, c, fin, source, counts, P);
+    hipLaunchKernelGGL(k_tm_fuse, grid1(P), dim3(256), 0, st, roi, wide, color, c, fin, source, counts, P);
 }
-void launch_tm_zero_nonfinite(const float *m, float *out, size_t P, hipStream_t st) { hipLaunchKernelGGL(k_tm_zero_nonfinite, g1(P), dim3(256), 0, st, m, out, P); }
+void launch_tm_zero_nonfinite(const float *m, float *out, size_t P, hipStream_t st) { hipLaunchKernelGGL(k_tm_zero_nonfinite, grid1(P), dim3(256), 0, st, m, out, P); }
 void launch_tm_warp_linear(const float *src, float *dst, const TmAff &a, int h, int w, hipStream_t st)
 {
     hipLaunchKernelGGL(k_tm_warp_linear, dim3((w + 255) / 256, h), dim3(256), 0, st, src, dst, a, h, w);
@@ -193,6 +173,6 @@ void launch_tm_warp_nearest(const uint8_t *src, uint8_t *dst, const TmAff &a, in
 {
     hipLaunchKernelGGL(k_tm_warp_nearest, dim3((w + 255) / 256, h), dim3(256), 0, st, src, dst, a, h, w);
 }
-void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t P, hipStream_t st) { hipLaunchKernelGGL(k_tm_mask_nan, g1(P), dim3(256), 0, st, m, keep, out, P); }
+void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t P, hipStream_t st) { hipLaunchKernelGGL(k_tm_mask_nan, grid1(P), dim3(256), 0, st, m, keep, out, P); }
 
 }  // namespace vf

@@ -13,10 +13,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/vistaf_ftp.h"
 #include "../../include/vistaf_tempmodel.h"
+#include "host_util.hpp"
 
-namespace vf { int set_error(int code, const std::string &msg); }
 using namespace vf;
 
 namespace {
@@ -176,7 +175,7 @@ __global__ __launch_bounds__(256) void k_tmodel_map(const TmMapArgs a)
         }
     }
     if (lds_n) __syncthreads();
-    const float qnan = __uint_as_float(0x7fc00000u);
+    const float qnan = nanf32();
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.P; i += (size_t)gridDim.x * blockDim.x) {
         bool in[NM], any = false;
 #pragma unroll
@@ -360,7 +359,7 @@ int vistaf_tmodel_predict_maps(int n_models, const vistaf_tmodel *const *models,
     hipStream_t st = (hipStream_t)stream;
     if (n_models == 1) hipLaunchKernelGGL(k_tmodel_map<1>, dim3(blocks), dim3(threads), shmem, st, a);
     else hipLaunchKernelGGL(k_tmodel_map<2>, dim3(blocks), dim3(threads), shmem, st, a);
-    return tm_hip(hipGetLastError(), "tmodel_predict_maps");
+    return launch_ok("tmodel_predict_maps");
 }
 
 int vistaf_tmodel_predict_rows(const vistaf_tmodel *m, const void *d_rows, int rows_dtype, int64_t n_rows, double *d_out, void *stream)
@@ -377,7 +376,7 @@ int vistaf_tmodel_predict_rows(const vistaf_tmodel *m, const void *d_rows, int r
     const TmDev *p = (const TmDev *)m->dev;
     if (rows_dtype == 0) hipLaunchKernelGGL(k_tmodel_rows<float>, dim3((unsigned)blocks), dim3(threads), 0, st, p, (const float *)d_rows, n_rows, d_out);
     else hipLaunchKernelGGL(k_tmodel_rows<double>, dim3((unsigned)blocks), dim3(threads), 0, st, p, (const double *)d_rows, n_rows, d_out);
-    return tm_hip(hipGetLastError(), "tmodel_predict_rows");
+    return launch_ok("tmodel_predict_rows");
 }
 
 }  // extern "C"

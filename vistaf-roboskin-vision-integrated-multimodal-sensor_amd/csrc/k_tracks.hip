@@ -20,11 +20,9 @@
 // state give the same bits.
 #include <string>
 
-#include "../../include/vistaf_ftp.h"
 #include "../../include/vistaf_track.h"
-#include "kernels.hpp"
+#include "host_util.hpp"
 
-namespace vf { int set_error(int code, const std::string &msg); }
 using namespace vf;
 
 namespace {
@@ -41,9 +39,7 @@ struct TrackState {
     double rows[TR_MAXK * VISTAF_NCONTACT];      // its contacts table
 };
 
-__device__ inline double tr_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
-__device__ inline bool tr_finite(double v) { return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
-__device__ inline double tr_sub(double a, double b) { const double d = a - b; return d != d ? tr_nan() : d; }      // one subtraction; one NaN
+__device__ inline double tr_sub(double a, double b) { const double d = a - b; return d != d ? nan64() : d; }      // one subtraction; one NaN
 __device__ inline unsigned int tr_nonneg(uint4 v) { return (~v.x | ~v.y | ~v.z | ~v.w) & 0x80808080u; }           // some byte >= 0
 
 template <int NT>
@@ -123,10 +119,10 @@ __global__ __launch_bounds__(64) void k_tr_link(const unsigned int *__restrict__
     n = n < 0 ? 0 : (n > K ? K : n);
     for (int e = lane; e < K * K; e += 64) O[(e / K) * TR_LDS_ROW + e % K] = ovl[t * (size_t)K * K + e];
     merged[lane] = 0;
-    const double px = lane < m ? prow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_X] : tr_nan();
-    const double py = lane < m ? prow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_Y] : tr_nan();
-    const double cx = lane < n ? crow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_X] : tr_nan();
-    const double cy = lane < n ? crow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_Y] : tr_nan();
+    const double px = lane < m ? prow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_X] : nan64();
+    const double py = lane < m ? prow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_Y] : nan64();
+    const double cx = lane < n ? crow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_X] : nan64();
+    const double cy = lane < n ? crow[lane * VISTAF_NCONTACT + VISTAF_CONTACT_CENTROID_Y] : nan64();
     pcx[lane] = px;
     pcy[lane] = py;
     __syncthreads();
@@ -148,8 +144,8 @@ __global__ __launch_bounds__(64) void k_tr_link(const unsigned int *__restrict__
     // step 4
     bool gated = false;
     if (gate_on) {
-        bool cand_j = lane < n && bp < 0 && tr_finite(cx) && tr_finite(cy);
-        unsigned long long imask = __ballot(lane < m && bn < 0 && tr_finite(px) && tr_finite(py));
+        bool cand_j = lane < n && bp < 0 && finitef(cx) && finitef(cy);
+        unsigned long long imask = __ballot(lane < m && bn < 0 && finitef(px) && finitef(py));
         unsigned long long best_d = ~0ull;
         int best_i = -1;
         bool stale = true;
@@ -185,7 +181,7 @@ __global__ __launch_bounds__(64) void k_tr_link(const unsigned int *__restrict__
     fate[t * (size_t)K + lane] = fate_i;
     double *o = tracks + (t * (size_t)K + lane) * VISTAF_NTRACK;
     if (lane >= n) {
-        for (int f = 0; f < VISTAF_NTRACK; f++) o[f] = tr_nan();
+        for (int f = 0; f < VISTAF_NTRACK; f++) o[f] = nan64();
         return;
     }
     // VISTAF_TRACK_ID, _AGE_FRAMES and _ORIGIN_TRACK_ID of a used row are k_tr_ids'
@@ -195,11 +191,11 @@ __global__ __launch_bounds__(64) void k_tr_link(const unsigned int *__restrict__
     o[VISTAF_TRACK_EVENTS] = (double)ev;
     o[VISTAF_TRACK_OVERLAP_PX] = (double)overlap;
     const double *me = crow + lane * VISTAF_NCONTACT, *pa = prow + (parent < 0 ? 0 : parent) * VISTAF_NCONTACT;
-    o[VISTAF_TRACK_DX] = parent < 0 ? tr_nan() : tr_sub(cx, pcx[parent]);
-    o[VISTAF_TRACK_DY] = parent < 0 ? tr_nan() : tr_sub(cy, pcy[parent]);
-    o[VISTAF_TRACK_DFORCE_N] = parent < 0 ? tr_nan() : tr_sub(me[VISTAF_CONTACT_FORCE_N], pa[VISTAF_CONTACT_FORCE_N]);
-    o[VISTAF_TRACK_DVOLUME_CM3] = parent < 0 ? tr_nan() : tr_sub(me[VISTAF_CONTACT_VOLUME_CM3], pa[VISTAF_CONTACT_VOLUME_CM3]);
-    for (int f = VISTAF_TRACK_ORIGIN_TRACK_ID + 1; f < VISTAF_NTRACK; f++) o[f] = tr_nan();
+    o[VISTAF_TRACK_DX] = parent < 0 ? nan64() : tr_sub(cx, pcx[parent]);
+    o[VISTAF_TRACK_DY] = parent < 0 ? nan64() : tr_sub(cy, pcy[parent]);
+    o[VISTAF_TRACK_DFORCE_N] = parent < 0 ? nan64() : tr_sub(me[VISTAF_CONTACT_FORCE_N], pa[VISTAF_CONTACT_FORCE_N]);
+    o[VISTAF_TRACK_DVOLUME_CM3] = parent < 0 ? nan64() : tr_sub(me[VISTAF_CONTACT_VOLUME_CM3], pa[VISTAF_CONTACT_VOLUME_CM3]);
+    for (int f = VISTAF_TRACK_ORIGIN_TRACK_ID + 1; f < VISTAF_NTRACK; f++) o[f] = nan64();
 }
 
 __global__ __launch_bounds__(64) void k_tr_ids(const int32_t *__restrict__ linkrow, const double *__restrict__ contacts, int B, int K,
@@ -242,13 +238,6 @@ __global__ __launch_bounds__(64) void k_tr_ids(const int32_t *__restrict__ linkr
     for (int e = lane; e < K * VISTAF_NCONTACT; e += 64) state->rows[e] = last[e];
 }
 
-int tr_launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return 0;
-}
-
 }  // namespace
 
 struct vistaf_track_handle {
@@ -260,12 +249,6 @@ struct vistaf_track_handle {
     int8_t *carry_plane = nullptr;         // [P] index plane of the last frame
     TrackState *state = nullptr;
 };
-
-#define TR_HIPCHK(x)                                                                                               \
-    do {                                                                                                           \
-        const hipError_t e_ = (x);                                                                                 \
-        if (e_ != hipSuccess) return set_error(VISTAF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));      \
-    } while (0)
 
 extern "C" {
 
@@ -316,24 +299,24 @@ int vistaf_track_update(vistaf_track_handle *tr, const int8_t *d_contact_index, 
     hipStream_t st = (hipStream_t)stream;
     const int K = tr->K, P = tr->P;
     if (tr->reset_pending) {
-        TR_HIPCHK(hipMemsetAsync(tr->state, 0, sizeof(TrackState), st));           // m = 0, next_id = 0
-        TR_HIPCHK(hipMemsetAsync(tr->carry_plane, 0xff, (size_t)P, st));
+        HIPCHK(hipMemsetAsync(tr->state, 0, sizeof(TrackState), st));           // m = 0, next_id = 0
+        HIPCHK(hipMemsetAsync(tr->carry_plane, 0xff, (size_t)P, st));
         tr->reset_pending = false;
     }
     if (ct_chunked(B, P)) {
         const int nblk = (P + TR_CHUNK - 1) / TR_CHUNK;
-        TR_HIPCHK(hipMemsetAsync(tr->ovl, 0, sizeof(unsigned int) * (size_t)B * K * K, st));
+        HIPCHK(hipMemsetAsync(tr->ovl, 0, sizeof(unsigned int) * (size_t)B * K * K, st));
         hipLaunchKernelGGL(k_tr_overlap<256>, dim3(nblk, B), dim3(256), 0, st, d_contact_index, tr->carry_plane, K, P, TR_CHUNK / 16, tr->ovl);
     } else {
         hipLaunchKernelGGL(k_tr_overlap<1024>, dim3(1, B), dim3(1024), 0, st, d_contact_index, tr->carry_plane, K, P, (P >> 4) + 1, tr->ovl);
     }
-    if (int rc = tr_launched("k_tr_overlap")) return rc;
-    TR_HIPCHK(hipMemcpyAsync(tr->carry_plane, d_contact_index + (size_t)(B - 1) * P, (size_t)P, hipMemcpyDeviceToDevice, st));
+    if (int rc = launch_ok("k_tr_overlap")) return rc;
+    HIPCHK(hipMemcpyAsync(tr->carry_plane, d_contact_index + (size_t)(B - 1) * P, (size_t)P, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_tr_link, dim3(B), dim3(64), 0, st, tr->ovl, d_contacts, d_count, tr->state, K, tr->gate_px > 0.0 ? 1 : 0,
                        tr->gate_px * tr->gate_px, d_tracks, d_fate, tr->linkrow);
-    if (int rc = tr_launched("k_tr_link")) return rc;
+    if (int rc = launch_ok("k_tr_link")) return rc;
     hipLaunchKernelGGL(k_tr_ids, dim3(1), dim3(64), 0, st, tr->linkrow, d_contacts, B, K, tr->state, d_tracks);
-    return tr_launched("k_tr_ids");
+    return launch_ok("k_tr_ids");
 }
 
 }  // extern "C"

@@ -35,19 +35,7 @@ __device__ unsigned long long g_batch_dbg[8];      // frame 0: steps, candidates
 #define BT_COUNT(i, v) do { } while (0)
 #endif
 
-__device__ inline uint32_t bt_shr1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false); }
 __device__ inline uint32_t bt_bperm(uint32_t v, int src_lane) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src_lane << 2, (int)v); }
-
-// inclusive prefix sum over the 64 lanes (DPP row shifts + row broadcasts)
-__device__ inline int bt_scan_add(int v)
-{
-#define BT_STEP(ctrl, rmask) v += __builtin_amdgcn_update_dpp(0, v, ctrl, rmask, 0xf, true);
-    BT_STEP(0x111, 0xf) BT_STEP(0x112, 0xf) BT_STEP(0x114, 0xf) BT_STEP(0x118, 0xf)
-#undef BT_STEP
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);      // row_bcast15 into rows 1 and 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);      // row_bcast31 into rows 2 and 3
-    return v;
-}
 
 __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__restrict__ rank_all, const int32_t *__restrict__ seed_in,
                                                            const uint32_t *__restrict__ inv_all, size_t inv_stride, int32_t *__restrict__ ppar_all,
@@ -119,7 +107,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
                 const int wi = wtop - lane;
                 const unsigned long long word = wi >= 0 ? L0[wi] : 0ull;
                 const int cnt = (int)__popcll(word);
-                const int incl = bt_scan_add(cnt);
+                const int incl = wave_scan_add(cnt);
                 const int pre = incl - cnt;
                 const int room = 64 - H;
                 int take = room - pre;
@@ -226,7 +214,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
             const uint32_t el = (uint32_t)__builtin_amdgcn_readlane((int)e, l);
             if (H > 0 && !(el > tailv)) { coldb |= 1ull << l; continue; }   // the tail moved up meanwhile
             const uint32_t displaced = (uint32_t)__builtin_amdgcn_readlane((int)hot, 63);
-            const uint32_t prev = bt_shr1(hot, 0xFFFFFFFFu);              // lane l <- l-1, lane 0 <- "infinity"
+            const uint32_t prev = wave_shr1(hot, 0xFFFFFFFFu);              // lane l <- l-1, lane 0 <- "infinity"
             hot = hot > el ? hot : (prev > el ? el : prev);               // branch-free sorted insertion
             if (H == 0) tailv = el;
             if (H < 64) H++;

@@ -71,30 +71,6 @@ __device__ inline int uf_c(float wa, float wb, bool &tie)
     return (int)k;
 }
 
-// inclusive prefix sum / prefix maximum (values >= 0) over the 64 lanes on the DPP network; the value of lane - 1 (lane 0: `first`)
-__device__ inline uint32_t uf_scan_add(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-__device__ inline uint32_t uf_scan_max(uint32_t v)
-{
-#define UF_MX(ctrl, rm, bc) { const uint32_t o_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rm, 0xf, bc); v = o_ > v ? o_ : v; }
-    UF_MX(0x111, 0xf, true) UF_MX(0x112, 0xf, true) UF_MX(0x114, 0xf, true) UF_MX(0x118, 0xf, true) UF_MX(0x142, 0xa, false) UF_MX(0x143, 0xc, false)
-#undef UF_MX
-    return v;
-}
-__device__ inline uint32_t uf_prev_lane(uint32_t v, uint32_t first, int lane)
-{
-    const uint32_t s = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false);        // wave_shr:1
-    return lane == 0 ? first : s;
-}
-
 // ---- runs per row, seed.  Every wave of the row kernels takes rw consecutive rows (small frames: fewer, longer-lived waves)
 __global__ __launch_bounds__(1024) void k_uf_count(const float *__restrict__ quality_all, const uint8_t *__restrict__ mask_all, UfPlanes U, int h, int w, int rw)
 {
@@ -119,7 +95,7 @@ __global__ __launch_bounds__(1024) void k_uf_count(const float *__restrict__ qua
             for (int j = 0; j < UF_CH; j++) {
                 const int x = c0 + 64 * j + lane;
                 const uint32_t on = mm[j] ? 1u : 0u;
-                const uint32_t ml = uf_prev_lane(on, last, lane);
+                const uint32_t ml = wave_shr1(on, last);
                 cnt += __popcll(__ballot(on && !ml));
                 last = (uint32_t)__builtin_amdgcn_readlane((int)on, 63);
                 const unsigned long long key = ((unsigned long long)f2key(qq[j]) << 32) | (uint32_t)(0x7fffffff - (y * w + x));
@@ -150,7 +126,7 @@ __global__ __launch_bounds__(1024) void k_uf_scan(UfPlanes U, int h)
     for (int y0 = 1; y0 <= h; y0 += 1024) {
         const int y = y0 + tid;
         const int v = y <= h ? rb[y] : 0;
-        const int incl = (int)uf_scan_add((uint32_t)v);
+        const int incl = (int)wave_scan_add((uint32_t)v);
         if (lane == 63) s_w[wave] = incl;
         __syncthreads();
         int base = s_carry;
@@ -202,14 +178,14 @@ __global__ __launch_bounds__(1024) void k_uf_rows(const float *__restrict__ wrap
             const int x = c0 + 64 * j + lane;
             if (c0 + 64 * j >= w) break;
             const uint32_t on = mm[j] ? 1u : 0u;
-            const uint32_t ml = uf_prev_lane(on, last_m, lane);
-            const float wl = __uint_as_float(uf_prev_lane(__float_as_uint(ww[j]), last_w, lane));
+            const uint32_t ml = wave_shr1(on, last_m);
+            const float wl = __uint_as_float(wave_shr1(__float_as_uint(ww[j]), last_w));
             int v = 0;
             if (on && ml) v = uf_c(wl, ww[j], bad);
             const bool start = on && !ml;
             // k relative to the run's first pixel = prefix sum of c along the row minus its value at the run's first pixel (where c = 0)
-            const uint32_t ps = uf_scan_add((uint32_t)v);
-            const uint32_t sl = uf_scan_max(start ? (uint32_t)lane + 1u : 0u);               // 0: the run began in an earlier chunk
+            const uint32_t ps = wave_scan_add((uint32_t)v);
+            const uint32_t sl = wave_scan_max(start ? (uint32_t)lane + 1u : 0u);               // 0: the run began in an earlier chunk
             const uint32_t pstart = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((sl ? sl - 1u : 0u) << 2), (int)ps);
             v = sl ? (int)(ps - pstart) : (int)ps + carry_v;
             const unsigned long long sb = __ballot(start);
@@ -276,14 +252,14 @@ __global__ __launch_bounds__(1024) void k_uf_edges(const float *__restrict__ wra
                 const int x = c0 + 64 * j + lane;
                 if (c0 + 64 * j >= w) break;
                 const uint32_t mD = kd[j] != -128 ? 1u : 0u, mU = ku[j] != -128 ? 1u : 0u;
-                const uint32_t pmD = uf_prev_lane(mD, lmD, lane), pmU = uf_prev_lane(mU, lmU, lane);
+                const uint32_t pmD = wave_shr1(mD, lmD), pmU = wave_shr1(mU, lmU);
                 const unsigned long long sbD = __ballot(mD && !pmD), sbU = __ballot(mU && !pmU);
                 const uint32_t iD = (uint32_t)(rbD + cnD + __popcll(sbD & le_mask) - 1), iU = (uint32_t)(rbU + cnU + __popcll(sbU & le_mask) - 1);
-                const uint32_t piD = uf_prev_lane(iD, liD, lane), piU = uf_prev_lane(iU, liU, lane);
+                const uint32_t piD = wave_shr1(iD, liD), piU = wave_shr1(iU, liU);
                 const uint32_t kDu = (uint32_t)(int)kd[j], kUu = (uint32_t)(int)ku[j];
-                const uint32_t pkD = uf_prev_lane(kDu, lkD, lane), pkU = uf_prev_lane(kUu, lkU, lane);
+                const uint32_t pkD = wave_shr1(kDu, lkD), pkU = wave_shr1(kUu, lkU);
                 const uint32_t wDu = __float_as_uint(wd[j]), wUu = __float_as_uint(wu[j]);
-                const uint32_t pwD = uf_prev_lane(wDu, lwD, lane), pwU = uf_prev_lane(wUu, lwU, lane);
+                const uint32_t pwD = wave_shr1(wDu, lwD), pwU = wave_shr1(wUu, lwU);
                 if (mD && y == sy && x == sx && iD < (uint32_t)U.rcap) U.rstate[ro + iD] = UF_KNOWN | (uint32_t)(uint16_t)(int16_t)(-(int)kd[j]);
                 // (run above, run below, k above, k below, w above, w below) of the up to three pairs of this column
                 auto emit = [&](uint32_t i, uint32_t jn, int ka, int kb, float wa, float wb) {
@@ -384,7 +360,7 @@ __global__ __launch_bounds__(1024) void k_uf_absolute(UfPlanes U, int h, int w, 
             const int x = c0 + 64 * j + lane;
             if (c0 + 64 * j >= w) break;
             const uint32_t on = kv[j] != -128 ? 1u : 0u;
-            const uint32_t ml = uf_prev_lane(on, last_m, lane);
+            const uint32_t ml = wave_shr1(on, last_m);
             const unsigned long long sb = __ballot(on && !ml);
             const int idx = rb + carry_n + __popcll(sb & le_mask) - 1;
             if (on) {

@@ -239,7 +239,7 @@ void launch_robust_polyfit_big(const float *z, const uint8_t *mask, int order, i
                                float *resid_out, int B, int h, int w, void *scratch, hipStream_t st);
 
 // ---- k_tempmap.hip (map-domain stages of the temperature modality; parity unpinned, see the file)
-struct TmAff { double m[6]; };          // source = M * (x, y, 1): the inverse map cv::warpAffine iterates with
+using TmAff = Aff;                      // the inverse map of the two warps (common.hpp)
 struct TmFuse { float color_lo, color_hi, low_th, high_th, final_lo, final_hi; };
 void launch_tm_clamp(const float *m, const uint8_t *roi, float lo, float hi, float *out, size_t P, hipStream_t st);
 void launch_tm_stats(const float *m, const uint8_t *roi, uint32_t *stats, size_t P, hipStream_t st);

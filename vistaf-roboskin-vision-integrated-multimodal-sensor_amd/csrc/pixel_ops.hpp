@@ -8,8 +8,6 @@
 
 namespace vf {
 
-__device__ inline float nanf32() { return __uint_as_float(0x7fc00000u); }
-
 // float32: img / (blur + 1e-6) - 1.0
 __device__ inline float illum_norm_px(float img, float blur) { return __fsub_rn(__fdiv_rn(img, __fadd_rn(blur, 1e-6f)), 1.0f); }
 

@@ -50,18 +50,6 @@ __device__ inline void sel_foreach(F get, int P, B body)
     }
 }
 
-// inclusive prefix sum over the 64 lanes of a wave (DPP row shifts + row broadcasts)
-__device__ inline uint32_t wave_scan_add(uint32_t v)
-{
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, true);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-
 // Finds keys of rank k and k+1 (ascending, 0-based) among the n valid elements.
 // each(body) calls body(key) for every valid element of this thread (the same elements on every call).
 // n must be > 0 and k < n.  Result in all threads.
@@ -237,7 +225,7 @@ __device__ inline float np_lerp(float a, float b, float t)
 template <class F>
 __device__ inline float block_percentile(F get, int P, float q32, SelShared &sh, uint32_t n, uint32_t kmin, uint32_t kmax)
 {
-    if (n == 0) return __uint_as_float(0x7fc00000u);
+    if (n == 0) return nanf32();
     uint32_t k; float g; bool top;
     np_percentile_index(n, q32, k, g, top);
     uint32_t ka, kb;
@@ -253,7 +241,7 @@ __device__ inline float block_percentile(F get, int P, float q32, SelShared &sh,
 template <int NT = SEL_T, class Each>
 __device__ __attribute__((always_inline)) inline float block_median_each(Each each, SelShared &sh, uint32_t n, uint32_t kmin, uint32_t kmax)
 {
-    if (n == 0) return __uint_as_float(0x7fc00000u);
+    if (n == 0) return nanf32();
     if (n == 1) return key2f(kmin);
     uint32_t ka, kb;
     block_select2_each<NT>(each, n, (n & 1u) ? (n - 1) / 2 : n / 2 - 1, sh, kmin, kmax, ka, kb);

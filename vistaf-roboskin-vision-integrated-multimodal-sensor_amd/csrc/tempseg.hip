@@ -16,18 +16,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/vistaf_ftp.h"
 #include "../../include/vistaf_temp.h"
-#include "kernels.hpp"
+#include "host_util.hpp"
 
-namespace vf { int set_error(int code, const std::string &msg); }
 using namespace vf;
-
-#define TCHK(x)                                                                                                  \
-    do {                                                                                                         \
-        hipError_t e_ = (x);                                                                                     \
-        if (e_ != hipSuccess) return set_error(VISTAF_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_));   \
-    } while (0)
 
 namespace {
 
@@ -132,31 +124,6 @@ __global__ __launch_bounds__(256) void k_ts_sign(const double2 *__restrict__ z, 
     if (threadIdx.x == 0) { double *o = partial + 4 * (size_t)blockIdx.x; o[0] = ga; o[1] = na; o[2] = gb; o[3] = nb; }
 }
 
-RowSpanSE rect_se(int kx, int ky)
-{
-    RowSpanSE se;
-    se.k = ky;
-    for (int i = 0; i < 33; i++) { se.lo[i] = (int8_t)(-(kx / 2)); se.hi[i] = (int8_t)(kx / 2); }
-    return se;
-}
-RowSpanSE ellipse_se(int k)
-{
-    RowSpanSE se;
-    se.k = k;
-    const int r = k / 2, c = k / 2;
-    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
-    for (int i = 0; i < 33; i++) { se.lo[i] = 1; se.hi[i] = -1; }
-    for (int i = 0; i < k; i++) {
-        const int dy = i - r;
-        const int dx = (int)std::nearbyint(c * std::sqrt((r * r - dy * dy) * inv_r2));
-        const int j1 = std::max(c - dx, 0), j2 = std::min(c + dx + 1, k);
-        se.lo[i] = (int8_t)(j1 - c);
-        se.hi[i] = (int8_t)(j2 - 1 - c);
-    }
-    return se;
-}
-int ensure_odd(int k) { return (k % 2) ? k : k + 1; }
-
 constexpr int TS_RB = 1024;      // blocks of the two-level reductions
 
 }  // namespace
@@ -165,7 +132,7 @@ struct vistaf_tempseg_handle {
     vistaf_tempseg_config cfg;
     int H = 0, W = 0, pm = 0;
     size_t P = 0;
-    std::vector<void *> allocs;
+    DeviceAllocs allocs;
     float *gray = nullptr, *g = nullptr, *tmpf = nullptr, *blur = nullptr, *norm = nullptr, *inorm = nullptr, *amp = nullptr, *gk = nullptr, *win = nullptr, *med = nullptr;
     int gksize = 0;
     uint8_t *sat0 = nullptr, *sat = nullptr, *roi_eff = nullptr, *ma = nullptr, *mb = nullptr, *m1 = nullptr, *m2 = nullptr;
@@ -190,20 +157,6 @@ struct vistaf_tempseg_handle {
     LabCoef lab;
 };
 
-namespace {
-template <typename T>
-int talloc(vistaf_tempseg_handle *h, T **p, size_t count)
-{
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
-inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
-}  // namespace
-
 extern "C" {
 
 int vistaf_tempseg_default_config(vistaf_tempseg_config *c)
@@ -218,7 +171,7 @@ int vistaf_tempseg_default_config(vistaf_tempseg_config *c)
 void vistaf_tempseg_destroy(vistaf_tempseg_handle *h)
 {
     if (!h) return;
-    for (void *p : h->allocs) hipFree(p);
+    h->allocs.free_all();
     if (h->have_plan) hipfftDestroy(h->plan);
     delete h;
 }
@@ -233,15 +186,15 @@ static int seg_ensure(vistaf_tempseg_handle *h)
     const size_t P = h->P;
     int rc = 0;
 #define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
-    TRY(talloc(h, &h->gray, P)); TRY(talloc(h, &h->g, P)); TRY(talloc(h, &h->tmpf, P)); TRY(talloc(h, &h->blur, P)); TRY(talloc(h, &h->norm, P));
-    TRY(talloc(h, &h->inorm, P)); TRY(talloc(h, &h->amp, P)); TRY(talloc(h, &h->med, 4)); TRY(talloc(h, &h->cnt, 4));
-    TRY(talloc(h, &h->sat0, P)); TRY(talloc(h, &h->sat, P)); TRY(talloc(h, &h->roi_eff, P)); TRY(talloc(h, &h->ma, P)); TRY(talloc(h, &h->mb, P));
-    TRY(talloc(h, &h->m2, P));
-    TRY(talloc(h, &h->F, (size_t)H * (W / 2 + 1))); TRY(talloc(h, &h->mag, P)); TRY(talloc(h, &h->peaks, 192));
-    TRY(talloc(h, &h->partial, (size_t)4 * TS_RB)); TRY(talloc(h, &h->sums, 8));
-    TRY(talloc(h, &h->Ex, (size_t)W * pm)); TRY(talloc(h, &h->Gx, (size_t)W * pm)); TRY(talloc(h, &h->Ey, (size_t)H * pm)); TRY(talloc(h, &h->Gy, (size_t)H * pm));
-    TRY(talloc(h, &h->T, (size_t)std::max(H, W) * pm)); TRY(talloc(h, &h->patch, (size_t)pm * pm)); TRY(talloc(h, &h->z, P)); TRY(talloc(h, &h->geom, 1));
-    TRY(talloc(h, &h->win, (size_t)pm * pm)); TRY(talloc(h, &h->req_med, 1));
+    TRY(h->allocs.alloc(&h->gray, P)); TRY(h->allocs.alloc(&h->g, P)); TRY(h->allocs.alloc(&h->tmpf, P)); TRY(h->allocs.alloc(&h->blur, P)); TRY(h->allocs.alloc(&h->norm, P));
+    TRY(h->allocs.alloc(&h->inorm, P)); TRY(h->allocs.alloc(&h->amp, P)); TRY(h->allocs.alloc(&h->med, 4)); TRY(h->allocs.alloc(&h->cnt, 4));
+    TRY(h->allocs.alloc(&h->sat0, P)); TRY(h->allocs.alloc(&h->sat, P)); TRY(h->allocs.alloc(&h->roi_eff, P)); TRY(h->allocs.alloc(&h->ma, P)); TRY(h->allocs.alloc(&h->mb, P));
+    TRY(h->allocs.alloc(&h->m2, P));
+    TRY(h->allocs.alloc(&h->F, (size_t)H * (W / 2 + 1))); TRY(h->allocs.alloc(&h->mag, P)); TRY(h->allocs.alloc(&h->peaks, 192));
+    TRY(h->allocs.alloc(&h->partial, (size_t)4 * TS_RB)); TRY(h->allocs.alloc(&h->sums, 8));
+    TRY(h->allocs.alloc(&h->Ex, (size_t)W * pm)); TRY(h->allocs.alloc(&h->Gx, (size_t)W * pm)); TRY(h->allocs.alloc(&h->Ey, (size_t)H * pm)); TRY(h->allocs.alloc(&h->Gy, (size_t)H * pm));
+    TRY(h->allocs.alloc(&h->T, (size_t)std::max(H, W) * pm)); TRY(h->allocs.alloc(&h->patch, (size_t)pm * pm)); TRY(h->allocs.alloc(&h->z, P)); TRY(h->allocs.alloc(&h->geom, 1));
+    TRY(h->allocs.alloc(&h->win, (size_t)pm * pm)); TRY(h->allocs.alloc(&h->req_med, 1));
     {
         const float neg = -1.0f;                                    // launch_select: a negative request is the median
         if (hipMemcpy(h->req_med, &neg, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
@@ -252,14 +205,9 @@ static int seg_ensure(vistaf_tempseg_handle *h)
     }
     h->gksize = 0;
     if (cfg->seg_illum_sigma > 0) {
-        const double sigma = (double)cfg->seg_illum_sigma;
-        const int n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;    // cv::GaussianBlur ksize rule, CV_32F (size checked at create)
-        std::vector<double> t(n);
-        double s2 = -0.5 / (sigma * sigma), sum = 0;
-        for (int i = 0; i < n; i++) { double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-        std::vector<float> f(n);
-        for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-        TRY(talloc(h, &h->gk, (size_t)n));
+        const std::vector<float> f = gauss_taps((double)cfg->seg_illum_sigma);      // (size checked at create)
+        const int n = (int)f.size();
+        TRY(h->allocs.alloc(&h->gk, (size_t)n));
         if (hipMemcpy(h->gk, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
         h->gksize = n;
     }
@@ -278,11 +226,11 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
     if (H < 1 || W < 1) return set_error(VISTAF_E_INVALID, "frame sides must be >= 1");
     const int R = cfg->seg_band_radius;
     if (R < 1 || 2 * R + 1 > 127 || cfg->n_peaks < 1 || cfg->n_peaks > 64) return set_error(VISTAF_E_INVALID, "band radius / peak count out of range");
-    for (int k : {ensure_odd(std::max(1, cfg->post_close_ky)), ensure_odd(std::max(1, cfg->post_open_ky)), ensure_odd(cfg->sat_dilate_ksize)})
+    for (int k : {odd_up(std::max(1, cfg->post_close_ky)), odd_up(std::max(1, cfg->post_open_ky)), odd_up(cfg->sat_dilate_ksize)})
         if (k > 33) return set_error(VISTAF_E_INVALID, "structuring element taller than 33");
-    for (int k : {ensure_odd(std::max(1, cfg->post_close_kx)), ensure_odd(std::max(1, cfg->post_open_kx))})
+    for (int k : {odd_up(std::max(1, cfg->post_close_kx)), odd_up(std::max(1, cfg->post_open_kx))})
         if (k > 127) return set_error(VISTAF_E_INVALID, "structuring element wider than 127");
-    if (cfg->seg_illum_sigma > 0 && (((int)std::nearbyint((double)cfg->seg_illum_sigma * 4 * 2 + 1)) | 1) > 511)
+    if (cfg->seg_illum_sigma > 0 && gauss_ksize((double)cfg->seg_illum_sigma) > 511)
         return set_error(VISTAF_E_INVALID, "illumination sigma too large");
     vistaf_tempseg_handle *h = new vistaf_tempseg_handle();
     h->cfg = *cfg; h->H = H; h->W = W; h->P = (size_t)H * W; h->pm = 2 * R + 1;
@@ -290,7 +238,7 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
     int rc = 0;
 #define TRY(x) do { rc = (x); if (rc) { vistaf_tempseg_destroy(h); return rc; } } while (0)
     // what the colour support needs (a mask plane and the morphology's prefix scratch); the segmentation's workspace waits for seg_ensure
-    TRY(talloc(h, &h->m1, P)); TRY(talloc(h, &h->prefix, P));
+    TRY(h->allocs.alloc(&h->m1, P)); TRY(h->allocs.alloc(&h->prefix, P));
     {
         // The integer tables of OpenCV's 8-bit BGR2LAB: sRGB gamma of i / 255 scaled by 255 * 2^3, the Lab cube-root function of
         // i / (255 * 2^3) scaled by 2^15, and the sRGB -> XYZ (D65) matrix over the white point scaled by 2^12.
@@ -298,19 +246,19 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
         for (int i = 0; i < 256; i++) {
             const double x = (double)((float)i / 255.0f);
             const double g = x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4);
-            gt[i] = (uint16_t)std::nearbyint(255.0 * (1 << LAB_GAMMA_SHIFT) * g);
+            gt[i] = (uint16_t)cv_round(255.0 * (1 << LAB_GAMMA_SHIFT) * g);
         }
         for (int i = 0; i < LAB_CBRT_N; i++) {
             const double x = (double)i / (255.0 * (1 << LAB_GAMMA_SHIFT));
             const double f = x < 0.008856 ? x * 7.787 + 0.13793103448275862 : std::cbrt(x);
-            ct[i] = (uint16_t)std::nearbyint((double)(1 << LAB_SHIFT2) * f);
+            ct[i] = (uint16_t)cv_round((double)(1 << LAB_SHIFT2) * f);
         }
         const double m[9] = {0.412453, 0.357580, 0.180423, 0.212671, 0.715160, 0.072169, 0.019334, 0.119193, 0.950227};
         const double wp[3] = {0.950456, 1.0, 1.088754};
-        for (int i = 0; i < 9; i++) h->lab.c[i] = (int)std::nearbyint((double)(1 << LAB_SHIFT) * m[i] / wp[i / 3]);
+        for (int i = 0; i < 9; i++) h->lab.c[i] = cv_round((double)(1 << LAB_SHIFT) * m[i] / wp[i / 3]);
         h->lab.lscale = (116 * 255 + 50) / 100;
         h->lab.lshift = -((16 * 255 * (1 << LAB_SHIFT2) + 50) / 100);
-        TRY(talloc(h, &h->gamma_tab, (size_t)256)); TRY(talloc(h, &h->cbrt_tab, (size_t)LAB_CBRT_N));
+        TRY(h->allocs.alloc(&h->gamma_tab, (size_t)256)); TRY(h->allocs.alloc(&h->cbrt_tab, (size_t)LAB_CBRT_N));
         if (hipMemcpy(h->gamma_tab, gt.data(), gt.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
             hipMemcpy(h->cbrt_tab, ct.data(), ct.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
     }
@@ -334,11 +282,11 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
     // ---- gray, saturation mask, effective ROI (:378-387, :441-446)
     launch_to_gray(d_bgr, VISTAF_FMT_BGR_U8, h->gray, 1, (int)P, st);
     hipLaunchKernelGGL(k_ts_sat0, grid1(P), dim3(256), 0, st, h->gray, d_roi, (float)c.sat_thresh_gray, h->sat0, P);
-    const int ks = ensure_odd(c.sat_dilate_ksize);
+    const int ks = odd_up(c.sat_dilate_ksize);
     if (ks > 1) {
         launch_morph(h->sat0, h->m1, 1, H, W, ellipse_se(ks), true, nullptr, nullptr, st, h->prefix);
         hipLaunchKernelGGL(k_ts_and, grid1(P), dim3(256), 0, st, h->m1, d_roi, h->sat, P);
-    } else TCHK(hipMemcpyAsync(h->sat, h->sat0, P, hipMemcpyDeviceToDevice, st));
+    } else HIPCHK(hipMemcpyAsync(h->sat, h->sat0, P, hipMemcpyDeviceToDevice, st));
     hipLaunchKernelGGL(k_ts_and_not, grid1(P), dim3(256), 0, st, d_roi, h->sat, h->roi_eff, P);
     // ---- median fill, illumination normalisation (:448-452, :363-375)
     launch_select(h->gray, h->roi_eff, P, nullptr, false, h->req_med, 1, h->med, h->cnt, 1, (int)P, st);
@@ -356,17 +304,17 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
     launch_carrier_choose(h->peaks, c.n_peaks, h->mag, H, W, R, c.seg_peak_max_dy_from_center, h->geom, 1, st);
     CarrierGeom g;
     int cnt_eff = 0;
-    TCHK(hipMemcpyAsync(&g, h->geom, sizeof(g), hipMemcpyDeviceToHost, st));
-    TCHK(hipMemcpyAsync(&cnt_eff, h->cnt, sizeof(int), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(&g, h->geom, sizeof(g), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&cnt_eff, h->cnt, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     if (cnt_eff == 0) return set_error(VISTAF_E_STATE, "ROI became empty after saturation exclusion. Lower SAT_THRESH_GRAY / dilation.");
     if (!g.ok) return set_error(VISTAF_E_NOCARRIER, "Could not find FFT peaks for stripe carrier.");
     const int peak_x = g.px_raw, peak_y = g.py_raw;
     if (peak_x - R < 0 || peak_x + R >= W || peak_y - R < 0 || peak_y + R >= H) return set_error(VISTAF_E_NOCARRIER, "carrier band leaves the spectrum");
     // ---- band-pass around the integer peak, in place (:463-468): pruned float64 DFT of the (2R+1)^2 bins, disc window, inverse
     g.x0 = peak_x - R; g.y0 = peak_y - R; g.ph = pm; g.pw = pm; g.dpx = 0.0; g.dpy = 0.0; g.keep_carrier = 1;
-    TCHK(hipMemcpyAsync(h->geom, &g, sizeof(g), hipMemcpyHostToDevice, st));
-    TCHK(hipStreamSynchronize(st));                                 // `g` is a host temporary
+    HIPCHK(hipMemcpyAsync(h->geom, &g, sizeof(g), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));                                 // `g` is a host temporary
     launch_build_tables(h->geom, 0, h->Ex, h->Ey, h->Gx, h->Gy, 0, 0, 1, H, W, 0, H, W, pm, st);
     launch_dft_forward(h->inorm, nullptr, h->Ex, h->Ey, 0, 0, h->win, h->T, h->patch, pm * pm, 1, H, W, pm, pm, st);
     launch_dft_inverse(h->patch, pm * pm, h->Gx, h->Gy, 0, 0, h->T, h->z, h->amp, nullptr, nullptr, 0, nullptr, nullptr, 1, H, W, pm, pm, st);
@@ -374,21 +322,21 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
     hipLaunchKernelGGL(k_ts_csum, dim3(TS_RB), dim3(256), 0, st, h->z, h->inorm, h->roi_eff, h->partial, P);
     hipLaunchKernelGGL(k_ts_final2, dim3(1), dim3(64), 0, st, h->partial, TS_RB, 2, h->sums);
     double cs[2];
-    TCHK(hipMemcpyAsync(cs, h->sums, sizeof(cs), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(cs, h->sums, sizeof(cs), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     const double phi0 = (std::isfinite(cs[0]) && std::isfinite(cs[1])) ? std::atan2(cs[1], cs[0]) : 0.0;
     hipLaunchKernelGGL(k_ts_sign, dim3(TS_RB), dim3(256), 0, st, h->z, std::cos(phi0), std::sin(phi0), h->roi_eff, h->gray, h->ma, h->partial, P);
     hipLaunchKernelGGL(k_ts_final2, dim3(1), dim3(64), 0, st, h->partial, TS_RB, 4, h->sums);
     double ab[4];
-    TCHK(hipMemcpyAsync(ab, h->sums, sizeof(ab), hipMemcpyDeviceToHost, st));
-    TCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(ab, h->sums, sizeof(ab), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     const double mean_a = ab[1] > 0 ? ab[0] / ab[1] : 1e9, mean_b = ab[3] > 0 ? ab[2] / ab[3] : 1e9;
     const bool a_dark = mean_a <= mean_b;
     const uint8_t *dark_raw = h->ma;
     if (!a_dark) { hipLaunchKernelGGL(k_ts_and_not, grid1(P), dim3(256), 0, st, h->roi_eff, h->ma, h->mb, P); dark_raw = h->mb; }
     // ---- close (kx x ky rectangle) then open, inside roi_eff (:390-406); an empty mask stays empty through all four steps
-    const RowSpanSE kc = rect_se(ensure_odd(std::max(1, c.post_close_kx)), ensure_odd(std::max(1, c.post_close_ky)));
-    const RowSpanSE ko = rect_se(ensure_odd(std::max(1, c.post_open_kx)), ensure_odd(std::max(1, c.post_open_ky)));
+    const RowSpanSE kc = rect_se(odd_up(std::max(1, c.post_close_kx)), odd_up(std::max(1, c.post_close_ky)));
+    const RowSpanSE ko = rect_se(odd_up(std::max(1, c.post_open_kx)), odd_up(std::max(1, c.post_open_ky)));
     launch_morph(dark_raw, h->m1, 1, H, W, kc, true, nullptr, nullptr, st, h->prefix);
     launch_morph(h->m1, h->m2, 1, H, W, kc, false, nullptr, nullptr, st, h->prefix);
     launch_morph(h->m2, h->m1, 1, H, W, ko, false, nullptr, nullptr, st, h->prefix);
@@ -397,14 +345,13 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
     int counts[4] = {0, 0, 0, 0};
     const uint8_t *cm[4] = {d_roi, h->sat, h->m2, h->m1};
     for (int i = 0; i < 4; i++) launch_count_u8(cm[i], h->cnt + i, 1, (int)P, st);
-    TCHK(hipMemcpyAsync(counts, h->cnt, sizeof(counts), hipMemcpyDeviceToHost, st));
-    if (d_dark) TCHK(hipMemcpyAsync(d_dark, h->m2, P, hipMemcpyDeviceToDevice, st));
-    if (d_light) TCHK(hipMemcpyAsync(d_light, h->m1, P, hipMemcpyDeviceToDevice, st));
-    if (d_roi_eff) TCHK(hipMemcpyAsync(d_roi_eff, h->roi_eff, P, hipMemcpyDeviceToDevice, st));
-    if (d_sat) TCHK(hipMemcpyAsync(d_sat, h->sat, P, hipMemcpyDeviceToDevice, st));
-    TCHK(hipStreamSynchronize(st));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
+    HIPCHK(hipMemcpyAsync(counts, h->cnt, sizeof(counts), hipMemcpyDeviceToHost, st));
+    if (d_dark) HIPCHK(hipMemcpyAsync(d_dark, h->m2, P, hipMemcpyDeviceToDevice, st));
+    if (d_light) HIPCHK(hipMemcpyAsync(d_light, h->m1, P, hipMemcpyDeviceToDevice, st));
+    if (d_roi_eff) HIPCHK(hipMemcpyAsync(d_roi_eff, h->roi_eff, P, hipMemcpyDeviceToDevice, st));
+    if (d_sat) HIPCHK(hipMemcpyAsync(d_sat, h->sat, P, hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (const int rc = launch_ok("launch")) return rc;
     if (info) {
         for (int i = 0; i < VISTAF_TEMPSEG_NINFO; i++) info[i] = 0.0;
         const double dx = (double)(peak_x - W / 2), dy = (double)(peak_y - H / 2);
@@ -423,12 +370,10 @@ int vistaf_temp_feature_planes(vistaf_tempseg_handle *h, const uint8_t *d_bgr, i
                                void *stream)
 {
     if (!h || !d_bgr) return set_error(VISTAF_E_INVALID, "null argument");
-    const int k = blur_ksize > 1 ? ensure_odd(blur_ksize) : 1;
+    const int k = blur_ksize > 1 ? odd_up(blur_ksize) : 1;
     if (k != 1 && k != 5) return set_error(VISTAF_E_INVALID, "blur_ksize must be 5 (BLUR_KSIZE as shipped) or <= 1 (no smoothing)");
     launch_feature_planes(d_bgr, h->gamma_tab, h->cbrt_tab, h->lab, k == 5, d_L, d_a, d_b, d_gray, h->H, h->W, (hipStream_t)stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return 0;
+    return launch_ok("launch");
 }
 
 int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const float *d_b, const uint8_t *d_light, const uint8_t *d_roi_eff,
@@ -437,14 +382,12 @@ int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const 
     if (!h || !d_a || !d_b) return set_error(VISTAF_E_INVALID, "null argument");
     if (d_support && (!d_light || !d_roi_eff || !d_sat)) return set_error(VISTAF_E_INVALID, "the support mask needs the light, roi_eff and sat masks");
     hipStream_t st = (hipStream_t)stream;
-    const int k = ensure_odd(dilate_ksize);
+    const int k = odd_up(dilate_ksize);
     if (k > 33) return set_error(VISTAF_E_INVALID, "structuring element taller than 33");
     const uint8_t *light_d = d_light;
     if (d_support && k > 1) { launch_morph(d_light, h->m1, 1, h->H, h->W, ellipse_se(k), true, nullptr, nullptr, st, h->prefix); light_d = h->m1; }
     launch_color_support(d_a, d_b, light_d, d_roi_eff, d_sat, (float)chroma_min, d_chroma, d_support, h->P, st);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("launch: ") + hipGetErrorString(e));
-    return 0;
+    return launch_ok("launch");
 }
 
 // ---- map-domain stages (Code/temperature_sensor.py:538-640, :705-747); parity unpinned (k_tempmap.hip)
@@ -453,28 +396,21 @@ static int tm_ensure(vistaf_tempseg_handle *h)
     if (h->tm_ready) return 0;
     int rc = 0;
 #define TMTRY(x) do { rc = (x); if (rc) return rc; } while (0)
-    TMTRY(talloc(h, &h->tmA, h->P)); TMTRY(talloc(h, &h->tmB, h->P));
-    TMTRY(talloc(h, &h->tmM1, h->P)); TMTRY(talloc(h, &h->tmM2, h->P));
-    TMTRY(talloc(h, &h->tm_kx, (size_t)1024)); TMTRY(talloc(h, &h->tm_ky, (size_t)1024));
+    TMTRY(h->allocs.alloc(&h->tmA, h->P)); TMTRY(h->allocs.alloc(&h->tmB, h->P));
+    TMTRY(h->allocs.alloc(&h->tmM1, h->P)); TMTRY(h->allocs.alloc(&h->tmM2, h->P));
+    TMTRY(h->allocs.alloc(&h->tm_kx, (size_t)1024)); TMTRY(h->allocs.alloc(&h->tm_ky, (size_t)1024));
     uint8_t *p = nullptr;
-    TMTRY(talloc(h, &p, inpaint_scratch_bytes_per_frame(h->H, h->W))); h->tm_scratch = p;
-    TMTRY(talloc(h, &h->tm_stats, (size_t)4)); TMTRY(talloc(h, &h->tm_status, (size_t)4)); TMTRY(talloc(h, &h->tm_counts, (size_t)4));
+    TMTRY(h->allocs.alloc(&p, inpaint_scratch_bytes_per_frame(h->H, h->W))); h->tm_scratch = p;
+    TMTRY(h->allocs.alloc(&h->tm_stats, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_status, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_counts, (size_t)4));
 #undef TMTRY
     h->tm_ready = true;
     return 0;
 }
-static int tm_done(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return 0;
-}
-
 int vistaf_temp_clamp_map(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double lo, double hi, float *d_out, void *stream)
 {
     if (!h || !d_map || !d_roi || !d_out) return set_error(VISTAF_E_INVALID, "null argument");
     launch_tm_clamp(d_map, d_roi, (float)lo, (float)hi, d_out, h->P, (hipStream_t)stream);
-    return tm_done("clamp_map");
+    return launch_ok("clamp_map");
 }
 
 int vistaf_temp_inpaint_map(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, int radius, float *d_out, void *stream)
@@ -489,7 +425,7 @@ int vistaf_temp_inpaint_map(vistaf_tempseg_handle *h, const float *d_map, const 
     (void)hipMemsetAsync(h->tm_status, 0, sizeof(int32_t), st);
     launch_inpaint_telea(h->tmA, h->tmM1, radius, h->tm_scratch, h->tm_status, nullptr, 1, h->H, h->W, st, true);
     launch_tm_unscale(d_map, d_roi, h->tm_stats, h->tmA, d_out, h->P, st);
-    return tm_done("inpaint_temperature_map");
+    return launch_ok("inpaint_temperature_map");
 }
 
 int vistaf_temp_fuse_maps(vistaf_tempseg_handle *h, const uint8_t *d_roi, const float *d_wide, const float *d_color, const vistaf_temp_fuse_config *cfg,
@@ -510,7 +446,7 @@ int vistaf_temp_fuse_maps(vistaf_tempseg_handle *h, const uint8_t *d_roi, const 
             return set_error(VISTAF_E_HIP, "fuse_maps: counters");
         for (int i = 0; i < 4; i++) counts_host[i] = (int64_t)hc[i];
     }
-    return tm_done("fuse_maps_per_pixel");
+    return launch_ok("fuse_maps_per_pixel");
 }
 
 static void tm_rotation(double cx, double cy, double angle_deg, double *M)      // cv::getRotationMatrix2D, scale 1
@@ -528,18 +464,6 @@ static TmAff tm_invert(const double *m)                                         
     a.m[0] = A11; a.m[1] = A12; a.m[2] = -A11 * m[2] - A12 * m[5];
     a.m[3] = A21; a.m[4] = A22; a.m[5] = -A21 * m[2] - A22 * m[5];
     return a;
-}
-static int tm_taps(double sigma, std::vector<float> &f)                          // cv::getGaussianKernel(ksize(sigma), sigma, CV_32F)
-{
-    const int n = ((int)std::nearbyint(sigma * 4 * 2 + 1)) | 1;
-    if (n > 1023) return set_error(VISTAF_E_INVALID, "smoothing sigma too large");
-    std::vector<double> t(n);
-    const double s2 = -0.5 / (sigma * sigma);
-    double sum = 0;
-    for (int i = 0; i < n; i++) { const double x = i - (n - 1) * 0.5; t[i] = std::exp(s2 * x * x); sum += t[i]; }
-    f.resize(n);
-    for (int i = 0; i < n; i++) f[i] = (float)(t[i] * (1.0 / sum));
-    return 0;
 }
 
 }  // extern "C"
@@ -562,9 +486,8 @@ int temp_blur_taps(double sigma_across, double sigma_along, float *d_kx, int &nx
     double sx = sigma_across > 0 ? sigma_across : 0.0, sy = sigma_along > 0 ? sigma_along : 0.0;
     if (sx <= 0) return set_error(VISTAF_E_INVALID, "sigma_across must be positive when sigma_along is (cv::GaussianBlur needs sigmaX > 0 for ksize (0, 0))");
     if (sy <= 0) sy = sx;                                     // cv::createGaussianKernels: sigmaY <= 0 takes sigmaX
-    std::vector<float> fx, fy;
-    int rc = tm_taps(sx, fx);
-    if (rc || (rc = tm_taps(sy, fy))) return rc;
+    if (gauss_ksize(sx) > 1023 || gauss_ksize(sy) > 1023) return set_error(VISTAF_E_INVALID, "smoothing sigma too large");
+    const std::vector<float> fx = gauss_taps(sx), fy = gauss_taps(sy);
     if (hipMemcpyAsync(d_kx, fx.data(), fx.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(d_ky, fy.data(), fy.size() * sizeof(float), hipMemcpyHostToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
         return set_error(VISTAF_E_HIP, "oriented blur: taps");
@@ -581,7 +504,7 @@ int temp_blur_apply(vistaf_tempseg_handle *h, const float *d_map, const uint8_t 
     const size_t P = h->P;
     if (nx == 0) {
         launch_tm_mask_nan(d_map, d_roi, d_out, P, st);
-        return tm_done("oriented blur");
+        return launch_ok("oriented blur");
     }
     const double cx = h->W / 2.0, cy = h->H / 2.0, angle_deg = -angle_rad * 180.0 / 3.14159265358979323846;
     double M[6], Mi[6];
@@ -596,7 +519,7 @@ int temp_blur_apply(vistaf_tempseg_handle *h, const float *d_map, const uint8_t 
     launch_tm_warp_linear(h->tmB, h->tmA, ai, h->H, h->W, st);                  // back
     launch_tm_warp_nearest(h->tmM1, h->tmM2, ai, h->H, h->W, st);               // back_roi
     launch_tm_mask_nan(h->tmA, h->tmM2, d_out, P, st);
-    return tm_done("oriented blur");
+    return launch_ok("oriented blur");
 }
 
 }  // namespace vf

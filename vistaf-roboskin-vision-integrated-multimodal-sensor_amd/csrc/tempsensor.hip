@@ -8,17 +8,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/vistaf_ftp.h"
 #include "../../include/vistaf_tempsensor.h"
-#include "kernels.hpp"
+#include "host_util.hpp"
 
-namespace vf {
-int set_error(int code, const std::string &msg);
-int tempseg_prepare(vistaf_tempseg_handle *h);
-int temp_blur_taps(double sigma_across, double sigma_along, float *d_kx, int &nx, float *d_ky, int &ny, hipStream_t st);
-int temp_blur_apply(vistaf_tempseg_handle *h, const float *d_map, const uint8_t *d_roi, double angle_rad, const float *d_kx, int nx, const float *d_ky,
-                    int ny, float *d_out, hipStream_t st);
-}
 using namespace vf;
 
 struct vistaf_tstats {
@@ -34,7 +26,7 @@ struct vistaf_tsensor {
     const vistaf_tmodel *models[2] = {nullptr, nullptr};
     vistaf_tempseg_handle *seg = nullptr;
     vistaf_tstats *stats = nullptr;
-    std::vector<void *> allocs;
+    DeviceAllocs allocs;
     float *planes = nullptr;                // L, a, b, gray
     float *raw = nullptr;                   // wide_raw, color_raw
     float *tmp = nullptr, *wide = nullptr, *color = nullptr, *fused = nullptr;
@@ -42,26 +34,6 @@ struct vistaf_tsensor {
     float *kx = nullptr, *ky = nullptr;
     int nx = 0, ny = 0;
 };
-
-namespace {
-template <typename T>
-int salloc(std::vector<void *> &allocs, T **p, size_t count)
-{
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, count * sizeof(T) + 256);
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
-int odd_up(int k) { return (k % 2) ? k : k + 1; }      // cv's ksize rule, as the segmentation applies it
-int launched(const char *what)
-{
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_error(VISTAF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-    return 0;
-}
-}  // namespace
 
 extern "C" {
 
@@ -108,7 +80,7 @@ int vistaf_tsensor_map_statistics(vistaf_tstats *s, const float *d_map, const ui
     hipStream_t st = (hipStream_t)stream;
     double *out = d_stats ? d_stats : s->out;
     launch_tstats(d_map, d_valid, s->H, s->W, s->scratch, s->big, out, st);
-    int rc = launched("map_statistics");
+    int rc = launch_ok("map_statistics");
     if (rc) return rc;
     if (stats_host) {
         if (hipMemcpyAsync(stats_host, out, VISTAF_TSENSOR_NSTATS * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess ||
@@ -121,7 +93,7 @@ int vistaf_tsensor_map_statistics(vistaf_tstats *s, const float *d_map, const ui
 void vistaf_tsensor_destroy(vistaf_tsensor *h)
 {
     if (!h) return;
-    for (void *p : h->allocs) (void)hipFree(p);
+    h->allocs.free_all();
     vistaf_tempseg_destroy(h->seg);
     vistaf_tsensor_stats_destroy(h->stats);
     delete h;
@@ -149,10 +121,10 @@ int vistaf_tsensor_create(const vistaf_tsensor_config *cfg, int H, int W, const 
     TRY(vistaf_tempseg_create(&cfg->seg, H, W, &h->seg));
     TRY(tempseg_prepare(h->seg));
     TRY(vistaf_tsensor_stats_create(H, W, &h->stats));
-    TRY(salloc(h->allocs, &h->planes, 4 * P)); TRY(salloc(h->allocs, &h->raw, 2 * P)); TRY(salloc(h->allocs, &h->tmp, P));
-    TRY(salloc(h->allocs, &h->wide, P)); TRY(salloc(h->allocs, &h->color, P)); TRY(salloc(h->allocs, &h->fused, P));
-    TRY(salloc(h->allocs, &h->masks, VISTAF_TSENSOR_NMASKS * P)); TRY(salloc(h->allocs, &h->source, P));
-    TRY(salloc(h->allocs, &h->kx, 1024)); TRY(salloc(h->allocs, &h->ky, 1024));
+    TRY(h->allocs.alloc(&h->planes, 4 * P)); TRY(h->allocs.alloc(&h->raw, 2 * P)); TRY(h->allocs.alloc(&h->tmp, P));
+    TRY(h->allocs.alloc(&h->wide, P)); TRY(h->allocs.alloc(&h->color, P)); TRY(h->allocs.alloc(&h->fused, P));
+    TRY(h->allocs.alloc(&h->masks, VISTAF_TSENSOR_NMASKS * P)); TRY(h->allocs.alloc(&h->source, P));
+    TRY(h->allocs.alloc(&h->kx, 1024)); TRY(h->allocs.alloc(&h->ky, 1024));
     TRY(temp_blur_taps(cfg->smooth_sigma_across, cfg->smooth_sigma_along, h->kx, h->nx, h->ky, h->ny, nullptr));
 #undef TRY
     *out = h;
@@ -201,7 +173,7 @@ int vistaf_tsensor_predict(vistaf_tsensor *h, const uint8_t *d_bgr, const uint8_
         for (int i = 0; i < VISTAF_TEMPSEG_NINFO; i++) info_host[i] = seg_info[i];
         for (int i = 0; i < 4; i++) info_host[VISTAF_TEMPSEG_NINFO + i] = (double)counts[i];
     }
-    return launched("tsensor_predict");
+    return launch_ok("tsensor_predict");
 }
 
 }  // extern "C"
