@@ -20,6 +20,12 @@ NTRACK = 16             # doubles per row of the contact tracker's table (VISTAF
 TRACK_NAMES = ["track_id", "age_frames", "parent_row", "events", "overlap_px", "dx", "dy", "dforce_N", "dvolume_cm3", "origin_track_id"]
 TRACK_EVENTS = {"born": 1, "split": 2, "merged": 4, "gated": 8}       # VISTAF_TRACKEV_*, bits of the `events` field
 FATE_ENDED, FATE_NO_ROW = -1, -2 ** 31                              # d_fate codes; -(2 + j): absorbed into contact j; >= 0: the continuing row
+NSHAPE = 24             # doubles per row of the per-contact shape table (VISTAF_NSHAPE, include/vistaf_shape.h)
+# fields of a row in the order of the VISTAF_SHAPE_* indices; 18..23 are reserved
+SHAPE_NAMES = ["contact_pixels", "boundary_pixels", "footprint_cx", "footprint_cy", "major_axis_mm", "minor_axis_mm", "orientation_rad",
+               "fit_pixels", "fit_status", "apex_x", "apex_y", "apex_depth_mm", "curvature_1_per_mm", "curvature_2_per_mm",
+               "curvature_axis_rad", "radius_1_mm", "radius_2_mm", "fit_rms_mm"]
+SHAPE_FIT = {"ok": 0, "none": 1, "not_a_cap": 2}                     # VISTAF_SHAPEFIT_*, values of the `fit_status` field
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
@@ -45,6 +51,7 @@ TSENSOR_EXPORTS = ["vistaf_tsensor_default_config", "vistaf_tsensor_create", "vi
                    "vistaf_tsensor_stats_create", "vistaf_tsensor_stats_destroy", "vistaf_tsensor_map_statistics"]   # include/vistaf_tempsensor.h
 TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
 TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_reset", "vistaf_track_destroy"]   # include/vistaf_track.h
+SHAPE_EXPORTS = ["vistaf_shape_create", "vistaf_shape_measure", "vistaf_shape_destroy"]   # include/vistaf_shape.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -163,7 +170,11 @@ def load():
     lib.vistaf_track_reset.argtypes = [vp]
     lib.vistaf_track_destroy.argtypes = [vp]
     lib.vistaf_track_destroy.restype = None
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS:
+    lib.vistaf_shape_create.argtypes = [ci, ci, ci, ci, cd, ctypes.POINTER(vp)]
+    lib.vistaf_shape_measure.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]
+    lib.vistaf_shape_destroy.argtypes = [vp]
+    lib.vistaf_shape_destroy.restype = None
+    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS:
         getattr(lib, fn)
     _lib = lib
     return lib

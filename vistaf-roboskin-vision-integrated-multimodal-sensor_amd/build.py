@@ -28,7 +28,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
     hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", "vistaf_ftp.h"), os.path.join(HERE, "..", "include", "vistaf_align.h"),
                                                      os.path.join(HERE, "..", "include", "vistaf_temp.h"), os.path.join(HERE, "..", "include", "vistaf_tempmodel.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_tempsensor.h"), os.path.join(HERE, "..", "include", "vistaf_track.h")]
+                                                     os.path.join(HERE, "..", "include", "vistaf_tempsensor.h"), os.path.join(HERE, "..", "include", "vistaf_track.h"),
+                                                     os.path.join(HERE, "..", "include", "vistaf_shape.h")]
     jobs = []
     objs = []
     for s in srcs:

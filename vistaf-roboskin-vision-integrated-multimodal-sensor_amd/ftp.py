@@ -204,6 +204,9 @@ class FtpSensor:
         if getattr(self, "_tracker", None) is not None:
             self._tracker.close()
             self._tracker = None
+        if getattr(self, "_shapes", None) is not None:
+            self._shapes.close()
+            self._shapes = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -316,6 +319,26 @@ class FtpSensor:
         out.update(tr.update(out["contact_index"], out["contacts"], out["count"]))
         return out
 
+    def shapes(self, max_contacts: int = 8, fit_min_fraction: float = 0.5) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the shape of every contact (shapes.ContactShapes; an extension, the reference has no
+        counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map, the frames' mm_per_px (the
+        `scalars` column) and the session's depth_eps_mm to the session's shape read-out, created on first use and rebuilt when
+        max_contacts or fit_min_fraction change.  Returns the contacts dict plus shapes [B,K,24] f64 (fields SHAPE_NAMES: footprint
+        ellipse, boundary pixels, apex, curvatures and radii of the fitted cap, residual)."""
+        from .shapes import ContactShapes
+        k, frac = int(max_contacts), float(fit_min_fraction)
+        sh = getattr(self, "_shapes", None)
+        if sh is not None and (sh.max_contacts != k or sh.fit_min_fraction != frac):
+            sh.close()
+            sh = self._shapes = None
+        out = self.contacts(k, index_plane=True)
+        if sh is None:
+            sh = self._shapes = ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device)
+        last = self._last_out
+        out["shapes"] = sh.measure(last["height_map_mm"], out["contact_index"], out["contacts"], out["count"],
+                                   last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm)
+        return out
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -367,12 +390,15 @@ class FtpSensor:
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
-    def predict(self, image, contacts: Optional[int] = None) -> Optional[Dict[str, Any]]:
+    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
         contacts=K adds a "contacts" key: the frame's (at most K) contacts as dicts of CONTACT_NAMES plus `centroid_xy`, `argmax_xy` and
-        `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars."""
+        `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars.
+        shapes=True (with contacts=K) adds a "shapes" key: one dict of SHAPE_NAMES per entry of "contacts" (`FtpSensor.shapes`)."""
+        if shapes and contacts is None:
+            raise ValueError("shapes=True needs contacts=K")
         o = self.predict_batch(image)
         torch.cuda.synchronize(self.device)
         status = int(o["status"][0].item())
@@ -394,8 +420,8 @@ class FtpSensor:
         res["argmax_depth_index"] = int(s[4])
         res["argmin_unitless_index"] = int(s[8])
         if contacts is not None:
-            from .writers import contacts_table
-            c = self.contacts(int(contacts))
+            from .writers import contacts_table, shapes_table
+            c = self.shapes(int(contacts)) if shapes else self.contacts(int(contacts))
             rows = contacts_table(c["contacts"].cpu().numpy(), c["count"].cpu().numpy())
             for r in rows:
                 r.pop("frame")
@@ -404,6 +430,10 @@ class FtpSensor:
                 r["bbox"] = (r["bbox_x0"], r["bbox_y0"], r["bbox_x1"], r["bbox_y1"])
             res["contacts"] = rows
             res["contact_count"] = int(c["count"][0].item())
+            if shapes:
+                res["shapes"] = shapes_table(c["shapes"].cpu().numpy(), c["contacts"].cpu().numpy(), c["count"].cpu().numpy())
+                for r in res["shapes"]:
+                    r.pop("frame")
         return res
 
 

@@ -13,6 +13,9 @@
 * `tracks_table` / `write_tracks_csv` -- the contact tracker's table (`FtpSensor.track`, `tracks.ContactTracker`) as row dicts and as
   `tracks.csv`; an extension as the contacts table.
 
+* `shapes_table` / `write_shapes_csv` -- the per-contact shape table (`FtpSensor.shapes`, `shapes.ContactShapes`) as row dicts and as
+  `shapes.csv`; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -41,6 +44,11 @@ TRACK_FIELDS = ("track_id", "age_frames", "parent_row", "events", "overlap_px", 
                 "origin_track_id")                                                        # VISTAF_TRACK_* order (include/vistaf_track.h)
 TRACK_INT_FIELDS = ("track_id", "age_frames", "parent_row", "events", "overlap_px", "origin_track_id")
 TRACKS_CSV_FIELDS = ("frame", "contact") + TRACK_FIELDS
+SHAPE_FIELDS = ("contact_pixels", "boundary_pixels", "footprint_cx", "footprint_cy", "major_axis_mm", "minor_axis_mm", "orientation_rad",
+                "fit_pixels", "fit_status", "apex_x", "apex_y", "apex_depth_mm", "curvature_1_per_mm", "curvature_2_per_mm",
+                "curvature_axis_rad", "radius_1_mm", "radius_2_mm", "fit_rms_mm")          # VISTAF_SHAPE_* order (include/vistaf_shape.h)
+SHAPE_INT_FIELDS = ("contact_pixels", "boundary_pixels", "fit_pixels", "fit_status")
+SHAPES_CSV_FIELDS = ("frame", "contact") + SHAPE_FIELDS
 
 
 def _safe_float(x, default):
@@ -174,6 +182,41 @@ def write_tracks_csv(output_dir: str, tracks, contacts, count, filename: str = "
         w = csv.DictWriter(f, fieldnames=list(TRACKS_CSV_FIELDS))
         w.writeheader()
         for row in tracks_table(tracks, contacts, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def shapes_table(shapes, contacts, count) -> list:
+    """Row dicts of the per-contact shape table: shapes [B,K,>=18] (or [K,>=18] for one frame) float64 as `FtpSensor.shapes` returns it, with
+    the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact`
+    (the row in both tables) and SHAPE_FIELDS, the pixel counts and the fit status as ints; what a status leaves out is NaN."""
+    t = np.asarray(shapes, dtype=np.float64)
+    c = np.asarray(contacts, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if c.ndim == 2:
+        c = c[None]
+    if t.ndim != 3 or t.shape[2] < len(SHAPE_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
+        raise ValueError("shapes must be [B,K,>=18] with contacts [B,K,>=13] and count [B]")
+    rows = []
+    for b in range(t.shape[0]):
+        for k in range(min(int(n[b]), t.shape[1])):
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(SHAPE_FIELDS):
+                row[name] = int(t[b, k, i]) if name in SHAPE_INT_FIELDS else float(t[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def write_shapes_csv(output_dir: str, shapes, contacts, count, filename: str = "shapes.csv") -> str:
+    """shapes.csv: one line per written contact, columns SHAPES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(SHAPES_CSV_FIELDS))
+        w.writeheader()
+        for row in shapes_table(shapes, contacts, count):
             w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
     return path
 
