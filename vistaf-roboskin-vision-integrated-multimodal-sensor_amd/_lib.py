@@ -26,6 +26,11 @@ SHAPE_NAMES = ["contact_pixels", "boundary_pixels", "footprint_cx", "footprint_c
                "fit_pixels", "fit_status", "apex_x", "apex_y", "apex_depth_mm", "curvature_1_per_mm", "curvature_2_per_mm",
                "curvature_axis_rad", "radius_1_mm", "radius_2_mm", "fit_rms_mm"]
 SHAPE_FIT = {"ok": 0, "none": 1, "not_a_cap": 2}                     # VISTAF_SHAPEFIT_*, values of the `fit_status` field
+NTAXEL, NTAXELFRAME, TAXEL_NONE = 12, 8, 0xFFFF                      # VISTAF_NTAXEL, VISTAF_NTAXELFRAME, VISTAF_TAXEL_NONE (include/vistaf_taxel.h)
+# fields of a taxel row in the order of the VISTAF_TAXEL_* indices (10, 11 are reserved), and of a frame row (VISTAF_TAXELFRAME_*)
+TAXEL_NAMES = ["contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
+               "force_N", "pressure_kPa"]
+TAXEL_FRAME_NAMES = ["active_taxels", "volume_cm3", "force_N", "cop_x", "cop_y", "moment_x_Nmm", "moment_y_Nmm", "peak_taxel"]
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
@@ -52,6 +57,7 @@ TSENSOR_EXPORTS = ["vistaf_tsensor_default_config", "vistaf_tsensor_create", "vi
 TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
 TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_reset", "vistaf_track_destroy"]   # include/vistaf_track.h
 SHAPE_EXPORTS = ["vistaf_shape_create", "vistaf_shape_measure", "vistaf_shape_destroy"]   # include/vistaf_shape.h
+TAXEL_EXPORTS = ["vistaf_taxel_create", "vistaf_taxel_measure", "vistaf_taxel_layout_info", "vistaf_taxel_destroy"]   # include/vistaf_taxel.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -174,7 +180,12 @@ def load():
     lib.vistaf_shape_measure.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]
     lib.vistaf_shape_destroy.argtypes = [vp]
     lib.vistaf_shape_destroy.restype = None
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS:
+    lib.vistaf_taxel_create.argtypes = [ci, ci, ci, vp, ci, cd, cd, ctypes.POINTER(vp)]
+    lib.vistaf_taxel_measure.argtypes = [vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
+    lib.vistaf_taxel_layout_info.argtypes = [vp, vp]
+    lib.vistaf_taxel_destroy.argtypes = [vp]
+    lib.vistaf_taxel_destroy.restype = None
+    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS:
         getattr(lib, fn)
     _lib = lib
     return lib

@@ -207,6 +207,9 @@ class FtpSensor:
         if getattr(self, "_shapes", None) is not None:
             self._shapes.close()
             self._shapes = None
+        if getattr(self, "_taxels", None) is not None:
+            self._taxels.close()
+            self._taxels = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -339,6 +342,28 @@ class FtpSensor:
                                    last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm)
         return out
 
+    def taxels(self, layout) -> Dict[str, torch.Tensor]:
+        """Taxel read-out of the last predict (taxels.TaxelReadout; an extension, the reference has no counterpart): the height map reduced to
+        the fixed cells of `layout` (taxels.grid_layout, polar_layout, from_map) and to the frame's wrench.  Hands the predict's height map,
+        the frames' mm_per_px and force_N (the `scalars` columns), their status and the session's depth_eps_mm to the session's read-out,
+        created on first use and rebuilt when another layout object is given.  Returns device tensors: taxels [B,T,12] f64 (fields
+        TAXEL_NAMES) and frame [B,8] f64 (fields TAXEL_FRAME_NAMES); a frame whose status is not 0 has NaN rows."""
+        from .taxels import TaxelReadout
+        last = getattr(self, "_last_out", None)
+        if last is None:
+            raise RuntimeError("taxels() needs a previous predict_batch / predict_pairs")
+        if layout.shape != (self.h, self.w):
+            raise ValueError(f"the layout is {layout.shape[0]} x {layout.shape[1]}, the session's frames are {self.h} x {self.w}")
+        tx = getattr(self, "_taxels", None)
+        if tx is not None and tx.layout is not layout:
+            tx.close()
+            tx = self._taxels = None
+        if tx is None:
+            tx = self._taxels = TaxelReadout(layout, self.max_batch, device=self.device)
+        sc = last["scalars"]
+        return tx.measure(last["height_map_mm"], sc[:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
+                          force_N=sc[:, SCALAR_NAMES.index("force_N")], status=last["status"])
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -390,13 +415,15 @@ class FtpSensor:
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
-    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False) -> Optional[Dict[str, Any]]:
+    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
         contacts=K adds a "contacts" key: the frame's (at most K) contacts as dicts of CONTACT_NAMES plus `centroid_xy`, `argmax_xy` and
         `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars.
-        shapes=True (with contacts=K) adds a "shapes" key: one dict of SHAPE_NAMES per entry of "contacts" (`FtpSensor.shapes`)."""
+        shapes=True (with contacts=K) adds a "shapes" key: one dict of SHAPE_NAMES per entry of "contacts" (`FtpSensor.shapes`).
+        taxels=layout adds "taxels", the ndarray [T,12] of `FtpSensor.taxels` (fields TAXEL_NAMES), and "taxel_frame", a dict of
+        TAXEL_FRAME_NAMES (active_taxels and peak_taxel as ints, peak_taxel -1 without contact)."""
         if shapes and contacts is None:
             raise ValueError("shapes=True needs contacts=K")
         o = self.predict_batch(image)
@@ -434,15 +461,21 @@ class FtpSensor:
                 res["shapes"] = shapes_table(c["shapes"].cpu().numpy(), c["contacts"].cpu().numpy(), c["count"].cpu().numpy())
                 for r in res["shapes"]:
                     r.pop("frame")
+        if taxels is not None:
+            from .writers import taxel_frame_record
+            t = self.taxels(taxels)
+            res["taxels"] = t["taxels"][0].cpu().numpy()
+            res["taxel_frame"] = taxel_frame_record(t["frame"][0].cpu().numpy())
         return res
 
 
 _default_sensor: Optional[FtpSensor] = None
 
 
-def predict(image, reference=None, **kwargs) -> Optional[Dict[str, Any]]:
+def predict(image, reference=None, taxels=None, **kwargs) -> Optional[Dict[str, Any]]:
     """predict(image[, reference]) -> force map dict.  With `reference` (and, the first time, the keyword
-    arguments of FtpSensor) a session is (re)built; later calls reuse it."""
+    arguments of FtpSensor) a session is (re)built; later calls reuse it.  taxels=layout adds the "taxels" and
+    "taxel_frame" keys of `FtpSensor.predict`."""
     global _default_sensor
     if reference is not None or _default_sensor is None:
         if reference is None:
@@ -451,4 +484,4 @@ def predict(image, reference=None, **kwargs) -> Optional[Dict[str, Any]]:
             _default_sensor.close()
         kwargs.setdefault("max_batch", 1)
         _default_sensor = FtpSensor(reference, **kwargs)
-    return _default_sensor.predict(image)
+    return _default_sensor.predict(image, taxels=taxels)

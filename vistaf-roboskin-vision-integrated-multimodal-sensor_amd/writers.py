@@ -16,6 +16,9 @@
 * `shapes_table` / `write_shapes_csv` -- the per-contact shape table (`FtpSensor.shapes`, `shapes.ContactShapes`) as row dicts and as
   `shapes.csv`; an extension as the contacts table.
 
+* `taxels_table` / `write_taxels_csv` / `taxel_frame_record` -- the taxel read-out (`FtpSensor.taxels`, `taxels.TaxelReadout`) as row dicts,
+  as `taxels.csv`, and the frame row as a dict; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -49,6 +52,12 @@ SHAPE_FIELDS = ("contact_pixels", "boundary_pixels", "footprint_cx", "footprint_
                 "curvature_axis_rad", "radius_1_mm", "radius_2_mm", "fit_rms_mm")          # VISTAF_SHAPE_* order (include/vistaf_shape.h)
 SHAPE_INT_FIELDS = ("contact_pixels", "boundary_pixels", "fit_pixels", "fit_status")
 SHAPES_CSV_FIELDS = ("frame", "contact") + SHAPE_FIELDS
+TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
+                "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
+TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
+TAXELS_CSV_FIELDS = ("frame", "taxel") + TAXEL_FIELDS
+TAXEL_FRAME_FIELDS = ("active_taxels", "volume_cm3", "force_N", "cop_x", "cop_y", "moment_x_Nmm", "moment_y_Nmm", "peak_taxel")   # VISTAF_TAXELFRAME_*
+TAXEL_FRAME_INT_FIELDS = ("active_taxels", "peak_taxel")                                  # peak_taxel is -1 without an active taxel
 
 
 def _safe_float(x, default):
@@ -219,6 +228,51 @@ def write_shapes_csv(output_dir: str, shapes, contacts, count, filename: str = "
         for row in shapes_table(shapes, contacts, count):
             w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
     return path
+
+
+def _int_or_minus_one(v: float) -> int:
+    return -1 if math.isnan(v) else int(v)
+
+
+def taxels_table(taxels) -> list:
+    """Row dicts of the taxel read-out: taxels [B,T,>=10] (or [T,>=10] for one frame) float64 as `FtpSensor.taxels` returns it.  One dict per
+    frame and taxel, in that order: `frame`, `taxel` and TAXEL_FIELDS, the pixel count and the arg-max index as ints (-1: a taxel without
+    contact has no arg-max).  A frame whose rows are NaN (its status was not 0) has no rows."""
+    t = np.asarray(taxels, dtype=np.float64)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim != 3 or t.shape[2] < len(TAXEL_FIELDS):
+        raise ValueError("taxels must be [B,T,>=10]")
+    rows = []
+    for b in range(t.shape[0]):
+        if np.isnan(t[b, :, 0]).all():
+            continue
+        for k in range(t.shape[1]):
+            row: Dict[str, Any] = {"frame": b, "taxel": k}
+            for i, name in enumerate(TAXEL_FIELDS):
+                row[name] = _int_or_minus_one(t[b, k, i]) if name in TAXEL_INT_FIELDS else float(t[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def write_taxels_csv(output_dir: str, taxels, filename: str = "taxels.csv") -> str:
+    """taxels.csv: one line per frame and taxel, columns TAXELS_CSV_FIELDS, floats with repr()."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(TAXELS_CSV_FIELDS))
+        w.writeheader()
+        for row in taxels_table(taxels):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def taxel_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=8] of the taxel read-out as a dict of TAXEL_FRAME_FIELDS; active_taxels and peak_taxel as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(TAXEL_FRAME_FIELDS):
+        raise ValueError("the frame row must be [>=8]")
+    return {name: (_int_or_minus_one(f[i]) if name in TAXEL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(TAXEL_FRAME_FIELDS)}
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
