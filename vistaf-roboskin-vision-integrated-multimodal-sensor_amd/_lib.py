@@ -31,6 +31,12 @@ NTAXEL, NTAXELFRAME, TAXEL_NONE = 12, 8, 0xFFFF                      # VISTAF_NT
 TAXEL_NAMES = ["contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                "force_N", "pressure_kPa"]
 TAXEL_FRAME_NAMES = ["active_taxels", "volume_cm3", "force_N", "cop_x", "cop_y", "moment_x_Nmm", "moment_y_Nmm", "peak_taxel"]
+NTHERMAL, NTHERMALFRAME = 16, 8                                      # VISTAF_NTHERMAL, VISTAF_NTHERMALFRAME (include/vistaf_thermal.h)
+# fields of a thermal row in the order of the VISTAF_THERMAL_* indices (12..15 are reserved), and of a frame row (VISTAF_THERMALFRAME_*; 7 is reserved)
+THERMAL_NAMES = ["contact_pixels", "valid_pixels", "coverage", "mean_C", "weighted_mean_C", "min_C", "max_C", "std_C", "peak_temp_C",
+                 "surround_pixels", "surround_mean_C", "contrast_C"]
+THERMAL_FRAME_NAMES = ["registered_pixels", "skin_mean_C", "contact_pixels", "contact_mean_C", "contrast_C", "hottest_contact", "coldest_contact"]
+ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
@@ -58,6 +64,7 @@ TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
 TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_reset", "vistaf_track_destroy"]   # include/vistaf_track.h
 SHAPE_EXPORTS = ["vistaf_shape_create", "vistaf_shape_measure", "vistaf_shape_destroy"]   # include/vistaf_shape.h
 TAXEL_EXPORTS = ["vistaf_taxel_create", "vistaf_taxel_measure", "vistaf_taxel_layout_info", "vistaf_taxel_destroy"]   # include/vistaf_taxel.h
+THERMAL_EXPORTS = ["vistaf_thermal_create", "vistaf_thermal_register", "vistaf_thermal_measure", "vistaf_thermal_destroy"]   # include/vistaf_thermal.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -185,7 +192,13 @@ def load():
     lib.vistaf_taxel_layout_info.argtypes = [vp, vp]
     lib.vistaf_taxel_destroy.argtypes = [vp]
     lib.vistaf_taxel_destroy.restype = None
-    for fn in EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS:
+    lib.vistaf_thermal_create.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
+    lib.vistaf_thermal_register.argtypes = [vp, vp, vp, ci, vp, vp]
+    lib.vistaf_thermal_measure.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
+    lib.vistaf_thermal_destroy.argtypes = [vp]
+    lib.vistaf_thermal_destroy.restype = None
+    for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
+               THERMAL_EXPORTS):
         getattr(lib, fn)
     _lib = lib
     return lib

@@ -61,6 +61,7 @@ class FtpAligner:
         self._lib.vistaf_align_default_config(ctypes.byref(cfg))
         cfg.apply_global_shift = int(apply_global_shift); cfg.use_ecc = int(use_ecc); cfg.ecc_iters = int(ecc_iters)
         cfg.ecc_eps = float(ecc_eps); cfg.ecc_gauss_sigma = float(ecc_gauss_sigma); cfg.shift_blur_sigma = float(shift_blur_sigma)
+        self.apply_global_shift = bool(apply_global_shift)      # what thermal.ThermalReadout.from_aligner needs beside the geometry
         cfg.gray_coeffs = int(gray_coeffs)       # 0: OpenCV 4.x BGR2GRAY coefficients, 1: OpenCV 3.x (include/vistaf_align.h)
         self.max_batch = int(max_batch)
         self._h = ctypes.c_void_p()

@@ -29,7 +29,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", "vistaf_ftp.h"), os.path.join(HERE, "..", "include", "vistaf_align.h"),
                                                      os.path.join(HERE, "..", "include", "vistaf_temp.h"), os.path.join(HERE, "..", "include", "vistaf_tempmodel.h"),
                                                      os.path.join(HERE, "..", "include", "vistaf_tempsensor.h"), os.path.join(HERE, "..", "include", "vistaf_track.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_shape.h"), os.path.join(HERE, "..", "include", "vistaf_taxel.h")]
+                                                     os.path.join(HERE, "..", "include", "vistaf_shape.h"), os.path.join(HERE, "..", "include", "vistaf_taxel.h"),
+                                                     os.path.join(HERE, "..", "include", "vistaf_thermal.h")]
     jobs = []
     objs = []
     for s in srcs:

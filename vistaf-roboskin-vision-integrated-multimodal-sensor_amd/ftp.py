@@ -210,6 +210,9 @@ class FtpSensor:
         if getattr(self, "_taxels", None) is not None:
             self._taxels.close()
             self._taxels = None
+        if getattr(self, "_thermal", None) is not None:
+            self._thermal.close()
+            self._thermal = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -364,6 +367,28 @@ class FtpSensor:
         return tx.measure(last["height_map_mm"], sc[:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
                           force_N=sc[:, SCALAR_NAMES.index("force_N")], status=last["status"])
 
+    def thermal(self, temperature_crop, max_contacts: int = 8, surround_margin_px: int = 8) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the temperature of every contact (thermal.ThermalReadout; an extension, the reference has
+        no counterpart).  `temperature_crop` [B,h,w] f32 is the caller's: a temperature map registered into the aligned crop by
+        `ThermalReadout.register`.  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map and status and the
+        session's depth_eps_mm to the session's read-out, created on first use and rebuilt when max_contacts or surround_margin_px change.
+        Returns the contacts dict plus thermal [B,K,16] f64 (fields THERMAL_NAMES) and thermal_frame [B,8] f64 (fields THERMAL_FRAME_NAMES)."""
+        from .thermal import ThermalReadout
+        k, margin = int(max_contacts), int(surround_margin_px)
+        th = getattr(self, "_thermal", None)
+        if th is not None and (th.max_contacts != k or th.surround_margin_px != margin):
+            th.close()
+            th = self._thermal = None
+        out = self.contacts(k, index_plane=True)
+        if th is None:                                     # measure needs the crop's size only; the photograph's is register's business
+            th = self._thermal = ThermalReadout(self.h, self.w, max(self.h, 2), max(self.w, 2), (0, 0), False, self.max_batch, k, margin,
+                                                device=self.device)
+        last = self._last_out
+        r = th.measure(temperature_crop, last["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self.config.depth_eps_mm,
+                       status=last["status"])
+        out["thermal"], out["thermal_frame"] = r["thermal"], r["frame"]
+        return out
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -415,7 +440,7 @@ class FtpSensor:
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
-    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None) -> Optional[Dict[str, Any]]:
+    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -423,9 +448,13 @@ class FtpSensor:
         `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars.
         shapes=True (with contacts=K) adds a "shapes" key: one dict of SHAPE_NAMES per entry of "contacts" (`FtpSensor.shapes`).
         taxels=layout adds "taxels", the ndarray [T,12] of `FtpSensor.taxels` (fields TAXEL_NAMES), and "taxel_frame", a dict of
-        TAXEL_FRAME_NAMES (active_taxels and peak_taxel as ints, peak_taxel -1 without contact)."""
+        TAXEL_FRAME_NAMES (active_taxels and peak_taxel as ints, peak_taxel -1 without contact).
+        thermal=temperature_crop (with contacts=K; [h,w] f32 from `ThermalReadout.register`) adds "thermal", one dict of THERMAL_NAMES per
+        entry of "contacts", and "thermal_frame", a dict of THERMAL_FRAME_NAMES (`FtpSensor.thermal`)."""
         if shapes and contacts is None:
             raise ValueError("shapes=True needs contacts=K")
+        if thermal is not None and contacts is None:
+            raise ValueError("thermal=temperature_crop needs contacts=K")
         o = self.predict_batch(image)
         torch.cuda.synchronize(self.device)
         status = int(o["status"][0].item())
@@ -461,6 +490,14 @@ class FtpSensor:
                 res["shapes"] = shapes_table(c["shapes"].cpu().numpy(), c["contacts"].cpu().numpy(), c["count"].cpu().numpy())
                 for r in res["shapes"]:
                     r.pop("frame")
+            if thermal is not None:
+                from .writers import thermal_frame_record, thermal_table
+                crop = torch.as_tensor(thermal)
+                t = self.thermal(crop[None] if crop.dim() == 2 else crop, int(contacts))
+                res["thermal"] = thermal_table(t["thermal"].cpu().numpy(), t["contacts"].cpu().numpy(), t["count"].cpu().numpy())
+                for r in res["thermal"]:
+                    r.pop("frame")
+                res["thermal_frame"] = thermal_frame_record(t["thermal_frame"][0].cpu().numpy())
         if taxels is not None:
             from .writers import taxel_frame_record
             t = self.taxels(taxels)

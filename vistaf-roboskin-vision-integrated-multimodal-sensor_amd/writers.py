@@ -19,6 +19,9 @@
 * `taxels_table` / `write_taxels_csv` / `taxel_frame_record` -- the taxel read-out (`FtpSensor.taxels`, `taxels.TaxelReadout`) as row dicts,
   as `taxels.csv`, and the frame row as a dict; an extension as the contacts table.
 
+* `thermal_table` / `write_thermal_csv` / `thermal_frame_record` -- the thermal read-out (`FtpSensor.thermal`, `thermal.ThermalReadout`) as row
+  dicts, as `thermal.csv`, and the frame row as a dict; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -58,6 +61,13 @@ TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                           
 TAXELS_CSV_FIELDS = ("frame", "taxel") + TAXEL_FIELDS
 TAXEL_FRAME_FIELDS = ("active_taxels", "volume_cm3", "force_N", "cop_x", "cop_y", "moment_x_Nmm", "moment_y_Nmm", "peak_taxel")   # VISTAF_TAXELFRAME_*
 TAXEL_FRAME_INT_FIELDS = ("active_taxels", "peak_taxel")                                  # peak_taxel is -1 without an active taxel
+THERMAL_FIELDS = ("contact_pixels", "valid_pixels", "coverage", "mean_C", "weighted_mean_C", "min_C", "max_C", "std_C", "peak_temp_C",
+                  "surround_pixels", "surround_mean_C", "contrast_C")                     # VISTAF_THERMAL_* order (include/vistaf_thermal.h)
+THERMAL_INT_FIELDS = ("contact_pixels", "valid_pixels", "surround_pixels")
+THERMAL_CSV_FIELDS = ("frame", "contact") + THERMAL_FIELDS
+THERMAL_FRAME_FIELDS = ("registered_pixels", "skin_mean_C", "contact_pixels", "contact_mean_C", "contrast_C", "hottest_contact",
+                        "coldest_contact")                                                # VISTAF_THERMALFRAME_*
+THERMAL_FRAME_INT_FIELDS = ("registered_pixels", "contact_pixels", "hottest_contact", "coldest_contact")   # -1 for NaN: no contact has a mean
 
 
 def _safe_float(x, default):
@@ -273,6 +283,53 @@ def taxel_frame_record(frame_row) -> Dict[str, Any]:
     if f.ndim != 1 or f.shape[0] < len(TAXEL_FRAME_FIELDS):
         raise ValueError("the frame row must be [>=8]")
     return {name: (_int_or_minus_one(f[i]) if name in TAXEL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(TAXEL_FRAME_FIELDS)}
+
+
+def thermal_table(thermal, contacts, count) -> list:
+    """Row dicts of the thermal read-out: thermal [B,K,>=12] (or [K,>=12] for one frame) float64 as `FtpSensor.thermal` returns it, with the
+    contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact` (the row
+    in both tables) and THERMAL_FIELDS, the pixel counts as ints; what has no value is NaN.  A frame whose rows are NaN (its status was not
+    0) has no rows."""
+    t = np.asarray(thermal, dtype=np.float64)
+    c = np.asarray(contacts, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if c.ndim == 2:
+        c = c[None]
+    if t.ndim != 3 or t.shape[2] < len(THERMAL_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
+        raise ValueError("thermal must be [B,K,>=12] with contacts [B,K,>=13] and count [B]")
+    rows = []
+    for b in range(t.shape[0]):
+        for k in range(min(int(n[b]), t.shape[1])):
+            if np.isnan(t[b, k, 0]):
+                continue
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(THERMAL_FIELDS):
+                row[name] = int(t[b, k, i]) if name in THERMAL_INT_FIELDS else float(t[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def write_thermal_csv(output_dir: str, thermal, contacts, count, filename: str = "thermal.csv") -> str:
+    """thermal.csv: one line per written contact, columns THERMAL_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one
+    (but for frames whose status was not 0)."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(THERMAL_CSV_FIELDS))
+        w.writeheader()
+        for row in thermal_table(thermal, contacts, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def thermal_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=7] of the thermal read-out as a dict of THERMAL_FRAME_FIELDS; the pixel counts and the two rows as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(THERMAL_FRAME_FIELDS):
+        raise ValueError("the frame row must be [>=7]")
+    return {name: (_int_or_minus_one(f[i]) if name in THERMAL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(THERMAL_FRAME_FIELDS)}
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
