@@ -268,6 +268,14 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
     }
 }
 
+// lane l's value of v as a wave-uniform value (two v_readlane)
+__device__ inline double readlane_f64(double v, int l)
+{
+    const unsigned long long r = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)r, l), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(r >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
 // ------------------------------------------------------------------------------------------------------------------------------------
 // Register-resident, column-owning variant for the batched frame sizes (w <= 1024, h / floor(1024 / w64) <= 64; 224 x 224: RP = 56).
 //
@@ -297,11 +305,10 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     FIT_START();
     __shared__ SelShared sh;
     __shared__ double s_part[NT / 64][21];
-    __shared__ double s_sum[21];
     __shared__ float s_coef[6];
     __shared__ float s_yn[FIT_YTAB];
     const size_t b = blockIdx.x;
-    const int P = h * w, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int P = h * w, tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nc = order >= 2 ? 6 : 3;
     const float *z = z_all + b * (size_t)P;
     const uint8_t *m = mask_all + b * (size_t)P;
@@ -383,8 +390,13 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     };
 
     float csig = 1.f;
-    for (int it = 0; do_fit && it < iters; it++) {
-        // ---- column sums P_b = sum w^2 yn^b (b = 0..4), Q_b = sum w^2 z yn^b (b = 0..2), float64
+    // one weighted least-squares step with NC = 3 (order 1) or 6 coefficients: sweep, reduction, solve.  An order-1 step accumulates and
+    // reduces only the nine sums its 3 x 3 system reads (the monomials of degree <= 2 from P_0..P_2, x Q_0, Q_1, Q_0), each formed by the
+    // same operations in the same order as in the order-2 step.
+    auto irls_step = [&](auto ncc, int it) {
+        constexpr int NC = decltype(ncc)::value, DEG = NC == 6 ? 4 : 2;
+        constexpr int NM = (DEG + 1) * (DEG + 2) / 2, NV = NM + NC;           // monomial sums, all sums: 15 + 6 or 6 + 3
+        // ---- column sums P_b = sum w^2 yn^b (b = 0..DEG), Q_b = sum w^2 z yn^b (b = 0..DEG / 2), float64
         double Pb[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, Qb[3] = {0.0, 0.0, 0.0};
         const float inv_csig = __fdiv_rn(1.0f, csig);
         int g0 = grp;
@@ -400,53 +412,66 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
                 }
                 const double yd = (double)s_yn[g0 + groups * u];
                 const double w2 = (double)wt * (double)wt;
-                const double t1 = w2 * yd, t2 = t1 * yd, t3 = t2 * yd, t4 = t3 * yd;
-                Pb[0] += w2; Pb[1] += t1; Pb[2] += t2; Pb[3] += t3; Pb[4] += t4;
+                const double t1 = w2 * yd, t2 = t1 * yd;
+                Pb[0] += w2; Pb[1] += t1; Pb[2] += t2;
                 const double zw = w2 * (double)zz;
-                Qb[0] += zw; Qb[1] = fma(zw, yd, Qb[1]); Qb[2] = fma(zw, yd * yd, Qb[2]);
+                Qb[0] += zw; Qb[1] = fma(zw, yd, Qb[1]);
+                if constexpr (NC == 6) {
+                    const double t3 = t2 * yd, t4 = t3 * yd;
+                    Pb[3] += t3; Pb[4] += t4;
+                    Qb[2] = fma(zw, yd * yd, Qb[2]);
+                }
             }
         }
-        // the 15 monomial sums m[a][b] = sum x^a P_b (a + b <= 4) and the 6 right-hand sides, reduced over the workgroup
-        double v21[21];
+        // the monomial sums m[a][b] = sum x^a P_b (a + b <= DEG) and the right-hand sides, reduced over the workgroup
+        double vs[NV];
         {
             const double x1 = (double)xn, x2 = x1 * x1, x3 = x2 * x1, x4 = x2 * x2;
             const double xp[5] = {1.0, x1, x2, x3, x4};
             int k = 0;
 #pragma unroll
-            for (int bb = 0; bb <= 4; bb++)
+            for (int bb = 0; bb <= DEG; bb++)
 #pragma unroll
-                for (int aa = 0; aa + bb <= 4; aa++) v21[k++] = xp[aa] * Pb[bb];     // k = index of (a, b), b-major
-            v21[15] = x1 * Qb[0]; v21[16] = Qb[1]; v21[17] = Qb[0]; v21[18] = x2 * Qb[0]; v21[19] = x1 * Qb[1]; v21[20] = Qb[2];
+                for (int aa = 0; aa + bb <= DEG; aa++) vs[k++] = xp[aa] * Pb[bb];     // k = index of (a, b), b-major
+            vs[NM + 0] = x1 * Qb[0]; vs[NM + 1] = Qb[1]; vs[NM + 2] = Qb[0];
+            if constexpr (NC == 6) { vs[NM + 3] = x2 * Qb[0]; vs[NM + 4] = x1 * Qb[1]; vs[NM + 5] = Qb[2]; }
         }
         SEL_STAMP(6);
 #pragma unroll
-        for (int i = 0; i < 21; i++) {
-            const double v = wave_sum(v21[i]);
+        for (int i = 0; i < NV; i++) {
+            const double v = wave_sum(vs[i]);
             if (lane == 0) s_part[wid][i] = v;
         }
         __syncthreads();
         SEL_STAMP(11);
-        if (tid < 21) {
-            double v = 0.0;
-            for (int k = 0; k < NT / 64; k++) v += s_part[k][tid];
-            s_sum[tid] = v;
-        }
-        __syncthreads();
-        SEL_STAMP(12);
-        if (tid == 0) {
-            // monomial (a, b) -> index in v21: b-major with 5, 4, 3, 2, 1 entries
-            auto mono = [&](int a, int bb) -> double { const int base[5] = {0, 5, 9, 12, 14}; return s_sum[base[bb] + a]; };
+        // Wave 0 alone finishes the step: lane i < NV adds the NT / 64 partials of sum i in their fixed order, the sums reach the solver
+        // as scalars through v_readlane (no second LDS round trip and no barrier in between), and every lane of the wave runs the same
+        // solve on them -- as fast as one lane would.
+        if (wid == 0) {
+            double sv = 0.0;
+            const int si = lane < NV ? lane : NV - 1;
+            for (int k = 0; k < NT / 64; k++) sv += s_part[k][si];
+            double S[NV];
+#pragma unroll
+            for (int i = 0; i < NV; i++) S[i] = readlane_f64(sv, i);
+            SEL_STAMP(12);
+            // monomial (a, b) -> index in vs: b-major with DEG + 1, DEG, ... entries
             const int ea[6] = {1, 0, 0, 2, 1, 0}, eb[6] = {0, 1, 0, 0, 1, 2};          // exponents of the basis [x, y, 1, x^2, xy, y^2]
             double A[6][6], rhs[6];
 #pragma unroll
             for (int i = 0; i < 6; i++) {
 #pragma unroll
-                for (int j = 0; j < 6; j++) A[i][j] = mono(ea[i] + ea[j], eb[i] + eb[j]);
-                rhs[i] = s_sum[15 + i];
+                for (int j = 0; j < 6; j++) {
+                    const int a = ea[i] + ea[j], bb = eb[i] + eb[j], k = bb * (DEG + 1) - bb * (bb - 1) / 2 + a;
+                    A[i][j] = (i < NC && j < NC) ? S[k < NM ? k : 0] : 0.0;
+                }
+                rhs[i] = i < NC ? S[NM + i] : 0.0;
             }
-            bool ok = nc == 6 ? chol_solve<6>(A, rhs) : chol_solve<3>(A, rhs);
+            const bool ok = chol_solve<NC>(A, rhs);
+            if (lane == 0) {
 #pragma unroll
-            for (int i = 0; i < 6; i++) s_coef[i] = (ok && i < nc) ? (float)rhs[i] : 0.f;
+                for (int i = 0; i < 6; i++) s_coef[i] = (ok && i < NC) ? (float)rhs[i] : 0.f;
+            }
         }
         SEL_STAMP(13);
         __syncthreads();
@@ -454,6 +479,10 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         At = fmaf(coef[3], __fmul_rn(xn, xn), fmaf(coef[0], xn, coef[2]));
         Bt = fmaf(coef[4], xn, coef[1]);
         SEL_STAMP(7);
+    };
+    for (int it = 0; do_fit && it < iters; it++) {
+        if (nc == 6) irls_step(std::integral_constant<int, 6>(), it);
+        else irls_step(std::integral_constant<int, 3>(), it);
         if (it == iters - 1) break;   // the weights of the last iteration are never used upstream
         // ---- sigma = 1.4826 * (median |r - median r| + 1e-6); the value ranges come from bounds on |fit| (|xn|, |yn| <= 1)
         uint32_t kmin, kmax;
