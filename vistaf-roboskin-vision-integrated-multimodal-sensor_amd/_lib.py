@@ -51,7 +51,7 @@ EXPORTS = [
     "vistaf_depth_map_to_volume", "vistaf_predict_force_from_volume",
 ]
 # csrc/test_hooks.h: kernel tier selection / debug planes for the parity tests, and the selection, fit and blur launchers on planes of the test's own
-TEST_EXPORTS = ["vistaf_ftp_test_set", "vistaf_ftp_test_select", "vistaf_ftp_test_polyfit", "vistaf_ftp_test_gauss",
+TEST_EXPORTS = ["vistaf_ftp_test_set", "vistaf_ftp_test_select", "vistaf_ftp_test_select_instance", "vistaf_ftp_test_select_chained", "vistaf_ftp_test_polyfit", "vistaf_ftp_test_gauss",
                 "vistaf_ftp_test_chamfer"]
 TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vistaf_tempseg_destroy", "vistaf_tempseg_segment",
                 "vistaf_temp_feature_planes", "vistaf_temp_color_support",
@@ -148,6 +148,8 @@ def load():
     lib.vistaf_predict_force_from_volume.argtypes = [ctypes.POINTER(Curve), cd, ctypes.POINTER(cd)]
     lib.vistaf_ftp_test_set.argtypes = [vp, ctypes.c_char_p, ci]
     lib.vistaf_ftp_test_select.argtypes = [vp, vp, ctypes.c_size_t, vp, ci, vp, ci, vp, vp, ci, ci, ci, vp]
+    lib.vistaf_ftp_test_select_instance.argtypes = [ci, ci, ci, ci]
+    lib.vistaf_ftp_test_select_chained.argtypes = [vp, vp, ctypes.c_size_t, ci, vp, ci, vp, vp, ci, ci, vp]
     lib.vistaf_ftp_test_polyfit.argtypes = [vp, vp, ci, ci, ctypes.c_float, ci, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.vistaf_ftp_test_gauss.argtypes = [vp, vp, cd, ci, ci, ci, vp]
     lib.vistaf_ftp_test_chamfer.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]

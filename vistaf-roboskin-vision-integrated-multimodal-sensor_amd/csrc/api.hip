@@ -91,7 +91,7 @@ struct vistaf_ftp_handle {
     int32_t *big_only;                  // [maxB] frames handed from the big-cluster march to the whole-frame kernel (launch_inpaint_big_handback)
     unsigned long long *cc_best;        // [maxB] largest-component key of launch_cc_largest on large frames
     double *scalars;
-    float *req_hi, *req_g, *req_med, *req_amp, *req_contact, *req_core;   // device percentile requests
+    float *req_hi, *req_g, *req_med, *req_amp, *req_contact, *req_core, *req_core_med;   // device percentile requests
 
     // per-contact read-out (vistaf_ftp_contacts): buffers sized by max_batch, and what the last predict was
     ContactScratch contacts_ws{};
@@ -197,8 +197,8 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);
     if (c.bad_pixel_enable) {
         launch_sobel_mag(hd->img, hd->grad, B, h, w, st);
-        launch_select(hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, P, st, chain_scratch(hd));
-        launch_select(hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, P, st, chain_scratch(hd));
+        launch_select(hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        launch_select(hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
         launch_bad_flags(hd->img, hd->grad, hd->valid, hd->thr_hi, hd->thr_g, hd->bad0, B, P, st);
         uint8_t *src = hd->bad0, *dst = hd->bad1;
         if (c.bad_dilate_ksize > 1)
@@ -248,7 +248,7 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
         if (hd->g_pre.k) { blur(hd, hd->inorm, hd->blurA, hd->g_pre, B, st); in = hd->blurA; }
         launch_mul_static(in, hd->apo, hd->iw, B, P, st);
     }
-    launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, chain_scratch(hd));
+    launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
 }
 
 // np.hanning(ph)[:,None] * np.hanning(pw)[None,:] in float32 (shape_ftp.py:800-807); np.hanning(M) = 0.5 + 0.5*cos(pi*n/(M-1)), n = 1-M, 3-M, ...
@@ -442,6 +442,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     TRY(upload_req(hd, &hd->req_amp, {q32_of(cfg->amp_valid_percentile)}));
     TRY(upload_req(hd, &hd->req_contact, {q32_of(cfg->contact_percentile), q32_of(95.0), q32_of(98.0)}));
     TRY(upload_req(hd, &hd->req_core, {q32_of(cfg->contact_core_percentile)}));
+    TRY(upload_req(hd, &hd->req_core_med, {q32_of(cfg->contact_core_percentile), -1.0f}));      // the chained pair: core threshold, median below it
     // den of the ROI-wide masked smooth is frame independent: blur(roi) + 1e-6 (shape_ftp.py:1146, :1821)
     TRY(dalloc(hd, &hd->roi_den, (size_t)P));
     if (hd->g_unrel.k) {
@@ -554,7 +555,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     if (hd->g_qual.k) blur(hd, hd->prod, hd->quality, hd->g_qual, B, st);
     else HIPCHK(hipMemcpyAsync(hd->quality, hd->prod, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     const float *qual = hd->quality;
-    launch_select(qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, P, st, chain_scratch(hd));
+    launch_select(qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
     launch_threshold_mask(qual, hd->roi, hd->amp_thr, hd->rel0, B, P, st);
     {
         // MORPH_CLOSE with n iterations = n dilations then n erosions; the eroded-ROI mask applies to the result
@@ -604,7 +605,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     else   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
-    launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, chain_scratch(hd));
+    launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
     launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
                         hd->contact, hd->thr_used, B, P, st);
     {
@@ -627,7 +628,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     }
     launch_background(hd->reliable, hd->contact_d, hd->rel_count, hd->bg_count, hd->background, B, P, st);
     launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, chain_scratch(hd));
-    launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, chain_scratch(hd));
+    launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
 
     // ---- reliable-only smoothing + sign flip (shape_ftp.py:1753-1768)
     if (timed) hipEventRecord(hd->ev[ST_SMOOTH_FLIP], st);
@@ -639,8 +640,13 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         blur(hd, hd->mplane, hd->den, hd->g_rel, B, st);
         launch_div_planes(hd->num, hd->den, hd->hmap, B, P, st);
     } else launch_zeroed_keep_nan(hd->detr, hd->bg_med, hd->reliable, hd->hmap, B, P, st);      // NaN stays NaN: the hole stage below is live
-    launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, P, st, chain_scratch(hd));
-    launch_select(hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, P, st, chain_scratch(hd));
+    // core threshold, then the median of the elements up to it: one chained launch where the keys stay in registers, else two launches
+    float *const core_outs[2] = {hd->core_thr, hd->core_med};
+    if (select_variant(B, P, 2, chain_scratch(hd) != nullptr, hd->tiers.select_resident != 0) < SELV_RES16 ||
+        launch_select_chained(hd->hmap, hd->reliable, (size_t)P, false, hd->req_core_med, 2, core_outs, nullptr, B, P, st) < 0) {
+        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        launch_select(hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+    }
     launch_core_flip(hd->hmap, hd->core_med, hd->flipped, B, P, st);
 
     // ---- internal holes of the reliable region (shape_ftp.py:1770-1801): with the smoothing every reliable pixel is finite here and
@@ -650,9 +656,9 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         const int ksz = std::max(3, c.hole_neighborhood_px | 1);
         launch_chamfer(hd->reliable, false, hd->rowdist, hd->dist, B, h, w, c.hole_min_dist_px + 1, st, hd->tiers.chamfer_twopass != 0);
         launch_hole_candidates(hd->hmap, hd->reliable, hd->dist, ksz, (float)c.hole_known_fraction, (float)c.hole_min_dist_px, hd->hole_cand, B, h, w, st);
-        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, P, st, chain_scratch(hd));
+        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
         launch_hole_tmp(hd->hmap, hd->reliable, hd->hole_cand, hd->hole_med, hd->z0, B, P, st);
-        launch_select(hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, P, st, chain_scratch(hd));
+        launch_select(hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
         launch_hole_zin(hd->z0, hd->hole_fill, B, P, st);
         {
             const int range = std::min(100, std::max(1, cv_round((double)c.inpaint_radius)));
@@ -873,6 +879,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "big_fallback") hd->tiers.big_fallback = value != 0;
     else if (n == "unwrap_fast") hd->tiers.unwrap_fast = value != 0;
     else if (n == "big_chain") hd->tiers.big_chain = value != 0;
+    else if (n == "select_resident") hd->tiers.select_resident = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
     else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
@@ -908,11 +915,32 @@ int vistaf_ftp_test_select(const float *vals, const uint8_t *mask, size_t mask_s
 {
     if (!vals || !mask || !reqs || !out || B < 1 || P < 1 || nreq < 1 || (mask_stride != 0 && mask_stride != (size_t)P))
         return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 3) return fail(VISTAF_E_INVALID, "variant must be 0, 1, 2 or 3");
     void *scratch = nullptr;
-    int rc = hook_scratch(variant, B, 1, P, nreq <= 4 && big_frames(B, P), &scratch);
+    int rc = hook_scratch(variant == 3 ? 1 : variant, B, 1, P, nreq <= 4 && big_frames(B, P), &scratch);
     if (rc) return rc;
-    launch_select(vals, mask, mask_stride, le_thr, use_abs != 0, reqs, nreq, out, counts, B, P, (hipStream_t)stream, scratch);
+    launch_select(vals, mask, mask_stride, le_thr, use_abs != 0, reqs, nreq, out, counts, B, P, (hipStream_t)stream, scratch, variant != 3);
     return hook_finish(scratch, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_select_instance(int B, int P, int nreq, int variant)
+{
+    if (B < 1 || P < 1 || nreq < 1 || variant < 0 || variant > 3) return fail(VISTAF_E_INVALID, "bad argument");
+    const bool chain_ok = nreq <= 4 && big_frames(B, P);
+    if (variant == 2 && !chain_ok) return fail(VISTAF_E_INVALID, "variant 2: the k_big.hip chain does not take this batch");
+    return select_variant(B, P, nreq, variant == 2 || (variant == 0 && P >= 262144), variant != 3);
+}
+
+int vistaf_ftp_test_select_chained(const float *vals, const uint8_t *mask, size_t mask_stride, int use_abs, const float *reqs, int nreq, float *out,
+                                   int *counts, int B, int P, void *stream)
+{
+    if (!vals || !mask || !reqs || !out || B < 1 || P < 1 || nreq < 1 || nreq > 4 || (mask_stride != 0 && mask_stride != (size_t)P))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    float *outs[4] = {out, out + B, out + 2 * (size_t)B, out + 3 * (size_t)B};
+    const int inst = launch_select_chained(vals, mask, mask_stride, use_abs != 0, reqs, nreq, outs, counts, B, P, (hipStream_t)stream);
+    if (inst < 0) return fail(VISTAF_E_INVALID, "no resident instance takes this plane size");
+    const int rc = hook_finish(nullptr, nullptr, (hipStream_t)stream);
+    return rc ? rc : inst;
 }
 
 int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,

@@ -22,6 +22,7 @@ struct Tiers {
     int big_fallback = 1;       // 1: frames whose big-cluster queue overflowed are re-marched by the whole-frame kernel; 0: they keep status 2 (test only)
     int telea_mw = 1;           // 1: the 16-wave window kernel (ordering pass + dataflow fills, k_inpaint_mw.hip) as first tier, single-wave tiers behind it; 0: single-wave tiers only
     int fused_backend = 1;      // 1: frames whose label forest fits LDS run blob filter, force tail and output copy in one launch per batch (k_backend.hip); 0: the separate kernels
+    int select_resident = 1;    // 1: the exact selections of planes of up to 65536 pixels keep their keys in registers (k_select_resident) and the core threshold and core median share a launch; 0: the streaming k_select, one launch per selection
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
 
@@ -66,8 +67,19 @@ void launch_compose_finalize_mm(const float *hmap, const uint8_t *reliable, cons
 // Per frame: values vals[b*P+i] (|.| if use_abs) over pixels with mask != 0 (mask_stride 0: one static
 // mask for all frames), finite, and (le_thr ? value <= le_thr[b] : true).
 // reqs[j] >= 0: percentile with q32 = reqs[j];  reqs[j] < 0: median.   out[b*nreq+j], counts[b].
+// big_scratch: k_big.hip's chain for large frames; resident: planes of up to 65536 pixels take k_select_resident (false: always the streaming k_select)
 void launch_select(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, bool use_abs,
-                   const float *reqs_dev, int nreq, float *out, int *counts, int B, int P, hipStream_t st, void *big_scratch = nullptr);      // big_scratch: k_big.hip's chain for large frames
+                   const float *reqs_dev, int nreq, float *out, int *counts, int B, int P, hipStream_t st, void *big_scratch = nullptr,
+                   bool resident = true);
+// the kernel launch_select starts for (B, P, nreq); big: scratch for the k_big.hip chain is at hand.  SELV_RES<NS>: k_select_resident<NS>, planes of up to 1024 NS pixels
+enum SelectVariant { SELV_BIG = 0, SELV_STREAM, SELV_RES16, SELV_RES32, SELV_RES49, SELV_RES64, SELV_COUNT };
+int select_variant(int B, int P, int nreq, bool big, bool resident);
+// A chain of selections in one launch of the resident kernel: request 0 as launch_select without a threshold, request j > 0 over the elements
+// that also satisfy value <= result[j - 1] (what a second launch_select with le_thr = the first one's output computes); result j of frame b
+// goes to outs[j][b] (nreq <= 4 host pointers to device arrays), counts[b] is the count of request 0.  Returns the instance launched, or -1
+// with nothing launched when no resident instance takes P: the caller then runs one launch_select per link.
+int launch_select_chained(const float *vals, const uint8_t *mask, size_t mask_stride, bool use_abs, const float *reqs_dev, int nreq,
+                          float *const *outs, int *counts, int B, int P, hipStream_t st);
 
 // ---- k_dft.hip / k_dft_tables.hip ----------------------------------------------------------------
 // carrier of one reference frame (shape_ftp.py:878-913, :930-961)

@@ -31,6 +31,9 @@ extern "C" {
  *                      filter, the force tail and the copy to the caller's planes in one launch (k_backend.hip); 0 the separate kernels
  *                      (labels, peak plane clear, peaks, decision, tail, copy).  Same bits either way.  With stage timing on, the fused launch is charged
  *                      to the mm / blob stage as a whole (tail and copy included); the tail stage then holds k_fill_scalars and the two copies only
+ *       "select_resident" 1 (default) the exact selections of planes of up to 65536 pixels run k_select_resident (every element loaded once, its key
+ *                      kept in a register for all sweeps) and the core threshold and the core median below it share one chained launch; 0 the
+ *                      streaming k_select, one launch per selection (two for the core pair).  Same bits either way
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
@@ -38,7 +41,9 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
  * produces.  Every call runs on `stream`, waits for it and returns 0 (or a VISTAF_E_* code; text in vistaf_ftp_last_error).
  * variant: 0 dispatch as a session does (the k_big.hip chain for planes of 262144 pixels and more, in batches it takes),
  *          1 the one-workgroup-per-frame kernels whatever the size,
- *          2 the k_big.hip chain; VISTAF_E_INVALID when it does not take (B, plane size).  Its scratch is allocated and freed by the call. */
+ *          2 the k_big.hip chain; VISTAF_E_INVALID when it does not take (B, plane size).  Its scratch is allocated and freed by the call.
+ *          3 (vistaf_ftp_test_select only) the streaming one-workgroup-per-frame kernel k_select whatever the size; under variant 1 planes of
+ *            up to 65536 pixels take the register-resident k_select_resident and only larger ones k_select. */
 
 /* launch_select: per frame b, the order statistics reqs[0..nreq) of { x = vals[b][i] : mask[b * mask_stride + i] != 0, x finite, then
  * x = |x| if use_abs, then x <= le_thr[b] if le_thr } into out[b * nreq + j] and their count into counts[b] (may be NULL).  A request is
@@ -47,6 +52,18 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
  * k_big.hip); that is where the reference's nanpercentile_safe / nanmedian_safe hand back the caller's fallback value. */
 int vistaf_ftp_test_select(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, int use_abs, const float *reqs, int nreq,
                            float *out, int *counts, int B, int P, int variant, void *stream);
+
+/* The kernel vistaf_ftp_test_select(.., B, P, variant) launches (SelectVariant of kernels.hpp: 0 the k_big.hip chain, 1 the streaming k_select,
+ * 2..5 k_select_resident with 16, 32, 49, 64 key slots per thread, for planes of up to 1024 slots pixels), or a negative error.  Launches nothing. */
+int vistaf_ftp_test_select_instance(int B, int P, int nreq, int variant);
+
+/* launch_select_chained: nreq <= 4 requests over the same plane and mask in one launch of the resident kernel.  Request 0 is what
+ * vistaf_ftp_test_select computes without a threshold; request j > 0 runs over the elements that also satisfy x <= result[j - 1] (float
+ * comparison: -0.0 <= 0.0 holds, a NaN result leaves no element), i.e. what a further vistaf_ftp_test_select with le_thr = the previous results
+ * computes.  out[j * B + b] (one [B] array per request), counts[b] the count of request 0 (may be NULL).  Returns the instance launched (2..5 as
+ * above), VISTAF_E_INVALID when the plane has more than 65536 pixels (a session then runs one launch per request). */
+int vistaf_ftp_test_select_chained(const float *vals, const uint8_t *mask, size_t mask_stride, int use_abs, const float *reqs, int nreq, float *out,
+                                   int *counts, int B, int P, void *stream);
 
 /* launch_robust_polyfit: coef[b * 6 + 0..6) (entries 3..5 zero for order 1) and resid[b] = z[b] - fit over the whole plane (NaN where z is).
  * Fewer than min_count fitted pixels (mask != 0 and z finite), or min_mask_count > 0 and fewer mask pixels than that: coefficients all
