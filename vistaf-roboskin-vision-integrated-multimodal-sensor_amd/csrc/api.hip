@@ -81,7 +81,8 @@ struct vistaf_ftp_handle {
                                 // kernels and stale after the fused back end (which sets the roots only): never index it by pixel
     uint16_t *morph_pre;
     void *inpaint_scratch, *inpaint_cl_scratch, *inpaint_win_scratch, *unwrap_scratch;
-    void *big_scratch = nullptr;      // k_big.hip (frames of 512 x 512 and more), else null
+    void *big_scratch = nullptr;      // k_big.hip (large_frame), else null
+    size_t big_scratch_bytes = 0;
     int32_t *unwrap_need;       // [max_batch] 1: the frame went through the priority flood, 0: the consistency check settled it
     // small per-frame arrays
     float *thr_hi, *thr_g, *mu, *amp_thr, *thr3, *thr_used, *bg_med, *core_thr, *core_med, *coef;
@@ -183,6 +184,13 @@ int upload_req(vistaf_ftp_handle *hd, float **d, const std::vector<float> &v)
     return 0;
 }
 
+// launch_select with the session's chain scratch and selection tier
+void select(vistaf_ftp_handle *hd, const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, bool use_abs, const float *reqs, int nreq,
+            float *out, int *counts, int B, hipStream_t st)
+{
+    launch_select(vals, mask, mask_stride, le_thr, use_abs, reqs, nreq, out, counts, B, hd->P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+}
+
 // preprocessing shared by reference and deformed frames: frames -> iw (apodised, normalised) and mu
 // frames2 (pair mode, when the workspace holds 2 * nframes): a second set of nframes frames preprocessed in the SAME launches, as frames
 // [nframes, 2 * nframes) of every plane -- the one-wave-per-frame march then runs once over twice as many CUs instead of twice
@@ -197,8 +205,8 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);
     if (c.bad_pixel_enable) {
         launch_sobel_mag(hd->img, hd->grad, B, h, w, st);
-        launch_select(hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
-        launch_select(hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        select(hd, hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, st);
+        select(hd, hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, st);
         launch_bad_flags(hd->img, hd->grad, hd->valid, hd->thr_hi, hd->thr_g, hd->bad0, B, P, st);
         uint8_t *src = hd->bad0, *dst = hd->bad1;
         if (c.bad_dilate_ksize > 1)
@@ -248,7 +256,7 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
         if (hd->g_pre.k) { blur(hd, hd->inorm, hd->blurA, hd->g_pre, B, st); in = hd->blurA; }
         launch_mul_static(in, hd->apo, hd->iw, B, P, st);
     }
-    launch_select(hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+    select(hd, hd->iw, hd->valid, 0, nullptr, false, hd->req_med, 1, hd->mu, nullptr, B, st);
 }
 
 // np.hanning(ph)[:,None] * np.hanning(pw)[None,:] in float32 (shape_ftp.py:800-807); np.hanning(M) = 0.5 + 0.5*cos(pi*n/(M-1)), n = 1-M, 3-M, ...
@@ -400,11 +408,14 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
 #undef PLANE
     {
         void *p = nullptr;
-        TRY(dalloc(hd, (uint8_t **)&p, inpaint_scratch_bytes_per_frame(h, w) * max_batch)); hd->inpaint_scratch = p;
-        TRY(dalloc(hd, (uint8_t **)&p, inpaint_cl_scratch_bytes_per_frame(h, w) * max_batch + 2048)); hd->inpaint_cl_scratch = p;
+        TRY(dalloc(hd, (uint8_t **)&p, inpaint_scratch_bytes(max_batch, h, w))); hd->inpaint_scratch = p;
+        TRY(dalloc(hd, (uint8_t **)&p, inpaint_cl_scratch_bytes(max_batch, h, w))); hd->inpaint_cl_scratch = p;
         TRY(dalloc(hd, (uint8_t **)&p, inpaint_win_scratch_bytes(max_batch))); hd->inpaint_win_scratch = p;
-        TRY(dalloc(hd, (uint8_t **)&p, unwrap_scratch_bytes_per_frame(h, w) * max_batch + 1024)); hd->unwrap_scratch = p;
-        if ((size_t)h * w >= 262144) { TRY(dalloc(hd, (uint8_t **)&p, big_scratch_bytes(max_batch, h, w))); hd->big_scratch = p; }
+        TRY(dalloc(hd, (uint8_t **)&p, unwrap_scratch_bytes(max_batch, h, w))); hd->unwrap_scratch = p;
+        if (large_frame((size_t)P)) {
+            hd->big_scratch_bytes = big_scratch_bytes(max_batch, h, w);
+            TRY(dalloc(hd, (uint8_t **)&p, hd->big_scratch_bytes)); hd->big_scratch = p;
+        }
         TRY(dalloc(hd, &hd->unwrap_need, (size_t)max_batch, "unwrap_need", sizeof(int32_t)));
         HIPCHK(hipMemset(hd->unwrap_need, 0xff, (size_t)max_batch * sizeof(int32_t)));        // -1: never written (the check is off or does not cover this frame size)
     }
@@ -555,7 +566,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     if (hd->g_qual.k) blur(hd, hd->prod, hd->quality, hd->g_qual, B, st);
     else HIPCHK(hipMemcpyAsync(hd->quality, hd->prod, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     const float *qual = hd->quality;
-    launch_select(qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+    select(hd, qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, st);
     launch_threshold_mask(qual, hd->roi, hd->amp_thr, hd->rel0, B, P, st);
     {
         // MORPH_CLOSE with n iterations = n dilations then n erosions; the eroded-ROI mask applies to the result
@@ -605,7 +616,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     else   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
-    launch_select(hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+    select(hd, hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, st);
     launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
                         hd->contact, hd->thr_used, B, P, st);
     {
@@ -628,7 +639,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     }
     launch_background(hd->reliable, hd->contact_d, hd->rel_count, hd->bg_count, hd->background, B, P, st);
     launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, chain_scratch(hd));
-    launch_select(hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+    select(hd, hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, st);
 
     // ---- reliable-only smoothing + sign flip (shape_ftp.py:1753-1768)
     if (timed) hipEventRecord(hd->ev[ST_SMOOTH_FLIP], st);
@@ -644,8 +655,8 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     float *const core_outs[2] = {hd->core_thr, hd->core_med};
     if (select_variant(B, P, 2, chain_scratch(hd) != nullptr, hd->tiers.select_resident != 0) < SELV_RES16 ||
         launch_select_chained(hd->hmap, hd->reliable, (size_t)P, false, hd->req_core_med, 2, core_outs, nullptr, B, P, st) < 0) {
-        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
-        launch_select(hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        select(hd, hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_core, 1, hd->core_thr, nullptr, B, st);
+        select(hd, hd->hmap, hd->reliable, (size_t)P, hd->core_thr, false, hd->req_med, 1, hd->core_med, nullptr, B, st);
     }
     launch_core_flip(hd->hmap, hd->core_med, hd->flipped, B, P, st);
 
@@ -656,9 +667,9 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         const int ksz = std::max(3, c.hole_neighborhood_px | 1);
         launch_chamfer(hd->reliable, false, hd->rowdist, hd->dist, B, h, w, c.hole_min_dist_px + 1, st, hd->tiers.chamfer_twopass != 0);
         launch_hole_candidates(hd->hmap, hd->reliable, hd->dist, ksz, (float)c.hole_known_fraction, (float)c.hole_min_dist_px, hd->hole_cand, B, h, w, st);
-        launch_select(hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        select(hd, hd->hmap, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_med, nullptr, B, st);
         launch_hole_tmp(hd->hmap, hd->reliable, hd->hole_cand, hd->hole_med, hd->z0, B, P, st);
-        launch_select(hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
+        select(hd, hd->z0, hd->reliable, (size_t)P, nullptr, false, hd->req_med, 1, hd->hole_fill, nullptr, B, st);
         launch_hole_zin(hd->z0, hd->hole_fill, B, P, st);
         {
             const int range = std::min(100, std::max(1, cv_round((double)c.inpaint_radius)));
@@ -711,7 +722,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     if (timed) hipEventRecord(hd->ev[ST_TAIL], st);
     if (!fused_backend)
         launch_tail(hd->depth, nullptr, hd->unitless, hd->roi, pp, hd->scalars, VISTAF_NSCALARS, nullptr, B, P, st, chain_scratch(hd),
-                    hd->big_scratch ? big_scratch_bytes(hd->maxB, h, w) : 0);
+                    hd->big_scratch_bytes);
     launch_fill_scalars(hd->scalars, VISTAF_NSCALARS, hd->rel_count, hd->flipped, hd->amp_thr, hd->thr_used, hd->bg_med, bad_count, B, st);
     if (!fused_backend) launch_copy_out(hd->depth, orel, hd->status, d_height_mm, d_reliable, B, P, st);
     if (d_scalars) HIPCHK(hipMemcpyAsync(d_scalars, hd->scalars, sizeof(double) * VISTAF_NSCALARS * B, hipMemcpyDeviceToDevice, st));
@@ -895,8 +906,8 @@ int hook_scratch(int variant, int B, int h, int w, bool chain_ok, void **scratch
     *scratch = nullptr;
     if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
     if (variant == 2 && !chain_ok) return fail(VISTAF_E_INVALID, "variant 2: the k_big.hip chain does not take this batch");
-    if (variant == 1 || (variant == 0 && (size_t)h * w < 262144)) return 0;
-    HIPCHK(hipMalloc(scratch, big_scratch_bytes(B, h, w) + 256));
+    if (variant == 1 || (variant == 0 && !large_frame((size_t)h * w))) return 0;
+    HIPCHK(hipMalloc(scratch, big_scratch_bytes(B, h, w)));
     return 0;
 }
 int hook_finish(void *a, void *b, hipStream_t st)
@@ -928,7 +939,7 @@ int vistaf_ftp_test_select_instance(int B, int P, int nreq, int variant)
     if (B < 1 || P < 1 || nreq < 1 || variant < 0 || variant > 3) return fail(VISTAF_E_INVALID, "bad argument");
     const bool chain_ok = nreq <= 4 && big_frames(B, P);
     if (variant == 2 && !chain_ok) return fail(VISTAF_E_INVALID, "variant 2: the k_big.hip chain does not take this batch");
-    return select_variant(B, P, nreq, variant == 2 || (variant == 0 && P >= 262144), variant != 3);
+    return select_variant(B, P, nreq, variant == 2 || (variant == 0 && large_frame((size_t)P)), variant != 3);
 }
 
 int vistaf_ftp_test_select_chained(const float *vals, const uint8_t *mask, size_t mask_stride, int use_abs, const float *reqs, int nreq, float *out,
@@ -985,6 +996,28 @@ int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *di
     if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, true);
     else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, true);
     return hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
+                                    size_t *total)
+{
+    if (!stage || !names || !offset || !bytes || !align || !total || B < 1 || h < 1 || w < 1 || range < 1 || cap < 1) return fail(VISTAF_E_INVALID, "bad argument");
+    const std::string s(stage);
+    std::vector<ScratchRegion> regions;
+    if (s == "unwrap") *total = unwrap_scratch_bytes(B, h, w, &regions);
+    else if (s == "telea") *total = telea_scratch_bytes(B, h, w, &regions);
+    else if (s == "inpaint_big") *total = inpaint_big_scratch_bytes(B, h, w, range, &regions);
+    else if (s == "inpaint_cl") *total = inpaint_cl_scratch_bytes(B, h, w, &regions);
+    else if (s == "inpaint_win") *total = inpaint_win_scratch_bytes(B, &regions);
+    else if (s == "big") *total = big_scratch_bytes(B, h, w, &regions);
+    else if (s == "tstats") *total = tstats_scratch_bytes(h, w, &regions);
+    if (regions.empty()) return fail(VISTAF_E_INVALID, "unknown stage: " + s);
+    if ((int)regions.size() > cap) return fail(VISTAF_E_INVALID, "more regions than cap");
+    for (size_t i = 0; i < regions.size(); i++) {
+        snprintf(names + 32 * i, 32, "%s", regions[i].name ? regions[i].name : "");
+        offset[i] = regions[i].offset; bytes[i] = regions[i].bytes; align[i] = regions[i].align;
+    }
+    return (int)regions.size();
 }
 
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,

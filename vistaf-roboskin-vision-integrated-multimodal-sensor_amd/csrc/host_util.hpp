@@ -1,10 +1,13 @@
 // Host-side plumbing shared by the translation units behind the C ABI (api.hip, align.hip, tempseg.hip, tempsensor.hip, k_tempmodel.hip,
-// k_tracks.hip): error reporting, the owning list of device allocations, and the OpenCV constant tables (Gaussian taps, structuring
-// elements) that more than one modality builds.  Host only; nothing here launches a kernel.
+// k_tracks.hip) and by the launchers that cut a scratch buffer into planes: error reporting, the owning list of device allocations, the
+// carver of the scratch layouts, and the OpenCV constant tables (Gaussian taps, structuring elements) that more than one modality builds.
+// Host only; nothing here launches a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <cassert>
 #include <cmath>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -59,6 +62,30 @@ struct DeviceAllocs {
         for (void *p : ptrs) (void)hipFree(p);
         ptrs.clear();
     }
+};
+
+// Cuts one device buffer into aligned regions, in the order of the take() calls.  base == nullptr: counts only (pointers come back null), which
+// is how every *_scratch_bytes() sizes the buffer its launcher carves: one function states a layout.  Offsets are rounded relative to base.
+// base must be 256-byte aligned, as a hipMalloc pointer is: a launcher handed a pointer into the middle of a buffer aborts here (the assert is
+// live in the shipped library) -- carve sub-buffers with take(), do not offset by hand.  rec: the regions, for the layout read-out of the tests.
+struct ScratchRegion { const char *name; size_t offset, bytes, align; };
+struct ScratchLayout {
+    explicit ScratchLayout(void *base, ScratchRec *rec = nullptr) : base_((uint8_t *)base), rec_(rec) { assert(((uintptr_t)base & 255) == 0); }
+    template <class T>
+    T *take(size_t count, size_t align = 256, const char *name = nullptr)
+    {
+        off_ = (off_ + align - 1) & ~(align - 1);
+        if (rec_) rec_->push_back({name, off_, count * sizeof(T), align});
+        T *p = base_ ? (T *)(base_ + off_) : nullptr;
+        off_ += count * sizeof(T);
+        return p;
+    }
+    size_t bytes() const { return off_; }      // end of the last region
+
+private:
+    uint8_t *base_;
+    ScratchRec *rec_;
+    size_t off_ = 0;
 };
 
 inline int cv_round(double v) { return (int)std::nearbyint(v); }      // cvRound: half to even

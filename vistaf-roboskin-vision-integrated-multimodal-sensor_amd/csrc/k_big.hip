@@ -14,7 +14,7 @@
 // Arithmetic per sample, keys, median / percentile interpolation and the residual plane are those of k_fit.hip / select.hpp.
 #include <algorithm>
 #include <cstdio>
-#include "kernels.hpp"
+#include "host_util.hpp"
 #include "select.hpp"
 #include "chol.hpp"
 
@@ -461,22 +461,21 @@ __global__ __launch_bounds__(256) void k_fb_resid(const float *__restrict__ z_al
     out_all[b * (size_t)P + i] = __fsub_rn(z_all[b * (size_t)P + i], fit);
 }
 
-// scratch layout: [B] SbFrame | [B * SB_MAXREQ] SbReq | [B * SB_MAXREQ * SB_NB] u32 histograms | [B] FitState | [B * nblk * 21] double partials
-struct BigScratch { SbFrame *fr; SbReq *rq; uint32_t *hist; FitState *fs; double *partial; };
-static BigScratch big_carve(void *scratch, int B, int P)
-{
-    BigScratch s;
-    uint8_t *p = (uint8_t *)scratch;
-    s.fr = (SbFrame *)p; p += (((size_t)B * sizeof(SbFrame)) + 255) & ~(size_t)255;
-    s.rq = (SbReq *)p; p += (((size_t)B * SB_MAXREQ * sizeof(SbReq)) + 255) & ~(size_t)255;
-    s.hist = (uint32_t *)p; p += (size_t)B * SB_MAXREQ * SB_NB * 4;
-    s.fs = (FitState *)p; p += (((size_t)B * sizeof(FitState)) + 255) & ~(size_t)255;
-    s.partial = (double *)p;
-    (void)P;
-    return s;
-}
 static int sweep_blocks(int P) { return (P + SB_T * SB_PX - 1) / (SB_T * SB_PX); }
 static int tile_blocks(int h, int w) { return ((w + SB_T - 1) / SB_T) * ((h + SB_PX - 1) / SB_PX); }
+// the partial sums are sized for the larger of the fit's two grids over an h x w frame (a selection on a flat plane, h = 1, uses none)
+struct BigScratch { SbFrame *fr; SbReq *rq; uint32_t *hist; FitState *fs; double *partial; };
+static BigScratch big_scratch(ScratchLayout &L, int B, int h, int w)
+{
+    const size_t nb = (size_t)B, P = (size_t)h * w;
+    BigScratch S;
+    S.fr = L.take<SbFrame>(nb, 256, "fr");
+    S.rq = L.take<SbReq>(nb * SB_MAXREQ, 256, "rq");
+    S.hist = L.take<uint32_t>(nb * SB_MAXREQ * SB_NB, 256, "hist");
+    S.fs = L.take<FitState>(nb, 256, "fs");
+    S.partial = L.take<double>(nb * std::max((P + FB_T * FB_PX - 1) / (FB_T * FB_PX), (size_t)tile_blocks(h, w)) * 21, 256, "partial");
+    return S;
+}
 template <class Src>
 static int sweep_grid(const Src &src, int P)
 {
@@ -499,20 +498,15 @@ static void select_levels(const Src &src, const BigScratch &S, const float *reqs
 
 }  // namespace
 
-size_t big_scratch_bytes(int B, int h, int w)
-{
-    const size_t P = (size_t)h * w;
-    return ((((size_t)B * sizeof(SbFrame)) + 255) & ~(size_t)255) + ((((size_t)B * SB_MAXREQ * sizeof(SbReq)) + 255) & ~(size_t)255) +
-           (size_t)B * SB_MAXREQ * SB_NB * 4 + ((((size_t)B * sizeof(FitState)) + 255) & ~(size_t)255) +
-           (size_t)B * std::max((P + FB_T * FB_PX - 1) / (FB_T * FB_PX), (size_t)tile_blocks(h, w)) * 21 * sizeof(double) + 1024;
-}
+size_t big_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); big_scratch(L, B, h, w); return L.bytes(); }
 // frames large enough that a batch cannot fill the chip with one workgroup per frame
-bool big_frames(int B, int P) { return P >= 262144 && B <= 192; }
+bool big_frames(int B, int P) { return large_frame((size_t)P) && B <= 192; }
 
 void launch_select_big(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, bool use_abs, const float *reqs_dev, int nreq,
                        float *out, int *counts, int B, int P, void *scratch, hipStream_t st)
 {
-    const BigScratch S = big_carve(scratch, B, P);
+    ScratchLayout L(scratch);
+    const BigScratch S = big_scratch(L, B, 1, P);      // a flat plane: the selection reads nothing behind `fs`, whatever (h, w) sized the buffer
     PlaneSrc src{vals, mask, mask_stride, le_thr, use_abs ? 1 : 0, P};
     (void)hipMemsetAsync(S.hist, 0, (size_t)B * SB_MAXREQ * SB_NB * 4, st);
     hipLaunchKernelGGL(k_sb_frame_init, dim3((B + 63) / 64), dim3(64), 0, st, S.fr, B);
@@ -524,7 +518,8 @@ void launch_robust_polyfit_big(const float *z, const uint8_t *mask, int order, i
                                float *resid_out, int B, int h, int w, void *scratch, hipStream_t st)
 {
     const int P = h * w;
-    const BigScratch S = big_carve(scratch, B, P);
+    ScratchLayout L(scratch);
+    const BigScratch S = big_scratch(L, B, h, w);
     const int nblk = (P + FB_T * FB_PX - 1) / (FB_T * FB_PX);
     (void)hipMemsetAsync(S.hist, 0, (size_t)B * SB_MAXREQ * SB_NB * 4, st);
     hipLaunchKernelGGL(k_sb_frame_init, dim3((B + 63) / 64), dim3(64), 0, st, S.fr, B);

@@ -271,7 +271,7 @@ __global__ __launch_bounds__(256) void k_ccl_out(const int32_t *__restrict__ lab
 void launch_cc_largest(const int32_t *labels, int32_t *area_scratch, unsigned long long *best, const uint8_t *and_static,
                        uint8_t *out, int B, int P, hipStream_t st)
 {
-    if (best && P >= 262144 && B <= 192) {
+    if (best && big_frames(B, P)) {
         (void)hipMemsetAsync(area_scratch, 0, (size_t)B * P * sizeof(int32_t), st);
         (void)hipMemsetAsync(best, 0, (size_t)B * sizeof(unsigned long long), st);
         hipLaunchKernelGGL(k_ccl_area, dim3((P + 1023) / 1024, B), dim3(256), 0, st, labels, area_scratch, P);

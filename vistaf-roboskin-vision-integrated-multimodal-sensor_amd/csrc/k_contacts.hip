@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_ct_final(const unsigned long long *__re
 
 }  // namespace
 
-bool ct_chunked(int B, int P) { return P >= 262144 && B <= 192; }      // the frames launch_tail splits as well
+bool ct_chunked(int B, int P) { return big_frames(B, P); }      // the frames launch_tail splits as well
 
 int contact_root_capacity(int h, int w) { return ((h + 1) / 2) * ((w + 1) / 2); }      // 8-connected components of an h x w mask: no more than this
 size_t contact_part_words(int max_batch, int P)

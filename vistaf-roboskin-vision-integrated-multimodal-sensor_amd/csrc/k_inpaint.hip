@@ -11,7 +11,7 @@
 // global memory.  Global mutable words are read with agent-scope relaxed atomic loads (L2-served)
 // and every store is drained (workgroup fence) before the next dependent read.
 #include <cstdio>
-#include "kernels.hpp"
+#include "host_util.hpp"
 #include "telea_common.hpp"
 
 namespace vf {
@@ -403,12 +403,25 @@ void telea_debug_dump()
 }
 #endif
 
-size_t inpaint_scratch_bytes_per_frame(int h, int w)
+// planes of the whole-frame kernel over the frame padded by one cell, en = (h + 2)(w + 2)
+struct TeleaScratch {
+    float *T;               // [B, en]
+    uint8_t *flags;         // [B, 2 en] the two flag planes of a frame, one behind the other
+    uint32_t *queue;        // [B, 2 en] keys, then indices: the queue of frames too large for LDS
+    int32_t *nbad;          // [B]
+};
+static TeleaScratch telea_scratch(ScratchLayout &L, int B, int h, int w)
 {
-    size_t en = (size_t)(h + 2) * (w + 2);
-    // the whole-frame kernel's planes, or those of the big-cluster kernel (k_inpaint_big.hip): never both in one step
-    return std::max(en * sizeof(float) + 2 * en + 8 * en /*global queue (large frames)*/ + 64 + 8 + 256, inpaint_big_scratch_bytes_per_frame(h, w));
+    const size_t n = (size_t)B * (h + 2) * (w + 2);
+    TeleaScratch S;
+    S.T = L.take<float>(n, 256, "T");
+    S.flags = L.take<uint8_t>(2 * n, 256, "flags");
+    S.queue = L.take<uint32_t>(2 * n, 256, "queue");
+    S.nbad = L.take<int32_t>((size_t)B, 256, "nbad");
+    return S;
 }
+size_t telea_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); telea_scratch(L, B, h, w); return L.bytes(); }
+size_t inpaint_scratch_bytes(int B, int h, int w) { return std::max(telea_scratch_bytes(B, h, w), inpaint_big_scratch_bytes(B, h, w)); }
 
 static size_t telea_lds_bytes(int h, int w)
 {
@@ -419,21 +432,18 @@ static size_t telea_lds_bytes(int h, int w)
 void launch_inpaint_telea(float *img, const uint8_t *bad, int range, void *scratch, int32_t *status, const int32_t *only, int B, int h,
                           int w, hipStream_t st, bool round_u8)
 {
-    size_t en = (size_t)(h + 2) * (w + 2);
-    // scratch layout: [B*en floats T][B*2*en bytes flags]
-    float *gT = (float *)scratch;
-    uint8_t *gflags = (uint8_t *)scratch + (size_t)B * en * sizeof(float);
-    uint32_t *gqueue = (uint32_t *)((((uintptr_t)scratch + (size_t)B * en * sizeof(float) + (size_t)B * en * 2) + 255) & ~(uintptr_t)255);
-    int32_t *nbad = (int32_t *)(gqueue + (size_t)B * en * 2);
-    hipMemsetAsync(nbad, 0, sizeof(int32_t) * B, st);
-    hipLaunchKernelGGL(k_telea_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, bad, gflags, gT, nbad, only, range, h, w);
+    const size_t en = (size_t)(h + 2) * (w + 2);
+    ScratchLayout L(scratch);
+    const TeleaScratch S = telea_scratch(L, B, h, w);
+    hipMemsetAsync(S.nbad, 0, sizeof(int32_t) * B, st);
+    hipLaunchKernelGGL(k_telea_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, bad, S.flags, S.T, S.nbad, only, range, h, w);
     size_t lds_full = telea_lds_bytes(h, w);
     if (lds_full <= 160 * 1024) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_telea<true>, 160 * 1024);
-        hipLaunchKernelGGL(k_telea<true>, dim3(B), dim3(64), lds_full, st, img, bad, range, gflags, gT, gqueue, nbad, status, h, w, round_u8 ? 1 : 0);
+        hipLaunchKernelGGL(k_telea<true>, dim3(B), dim3(64), lds_full, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, status, h, w, round_u8 ? 1 : 0);
     } else {
-        hipLaunchKernelGGL(k_telea<false>, dim3(B), dim3(64), 0, st, img, bad, range, gflags, gT, gqueue, nbad, status, h, w, round_u8 ? 1 : 0);
+        hipLaunchKernelGGL(k_telea<false>, dim3(B), dim3(64), 0, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, status, h, w, round_u8 ? 1 : 0);
     }
 }
 

@@ -9,7 +9,7 @@
 // The planes are shared by all clusters of a frame: clusters touch disjoint cells (k_inpaint_cl.hip), a wave only ever reads cells its own
 // cluster owns or cells nobody writes, and a wave sees its own global stores in program order.
 #include <type_traits>
-#include "kernels.hpp"
+#include "host_util.hpp"
 #include "telea_common.hpp"
 
 namespace vf {
@@ -27,11 +27,30 @@ static int bg_gq_cap(int h, int w)
     while ((size_t)cap * 2 <= per) cap *= 2;
     return cap;
 }
-// T f32 | image f32 | flags u8 over the padded frame, then the queue slices
-size_t inpaint_big_scratch_bytes_per_frame(int h, int w)
+// planes over the frame padded by M = range + 1 cells, en = (h + 2 M)(w + 2 M), then one queue slice per wave
+struct BigClScratch {
+    float *T, *im;                      // [B, en]
+    uint8_t *f;                         // [B, en]
+    unsigned long long *gq;             // [B, nslot, gq_stride]
+    int nslot, gq_stride;               // waves per frame, entries per slice: by (h, w) alone
+};
+static BigClScratch inpaint_big_scratch(ScratchLayout &L, int B, int h, int w, int M)
 {
-    const size_t en = (size_t)(h + 2 * BG_MAXPAD) * (w + 2 * BG_MAXPAD);
-    return en * 9 + (size_t)bg_slots(h, w) * bg_gq_cap(h, w) * 8 + 1024;
+    const size_t n = (size_t)B * (h + 2 * M) * (w + 2 * M);
+    BigClScratch S;
+    S.nslot = bg_slots(h, w);
+    S.gq_stride = bg_gq_cap(h, w);
+    S.T = L.take<float>(n, 256, "T");
+    S.im = L.take<float>(n, 256, "im");
+    S.f = L.take<uint8_t>(n, 256, "f");
+    S.gq = L.take<unsigned long long>((size_t)B * S.nslot * S.gq_stride, 256, "gq");
+    return S;
+}
+size_t inpaint_big_scratch_bytes(int B, int h, int w, int range, ScratchRec *rec)
+{
+    ScratchLayout L(nullptr, rec);
+    inpaint_big_scratch(L, B, h, w, range ? range + 1 : BG_MAXPAD);
+    return L.bytes();
 }
 bool inpaint_big_supported(int range) { return range >= 1 && range + 1 <= BG_MAXPAD; }
 
@@ -252,20 +271,18 @@ void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, 
 {
     const int M = range + 1;
     const size_t en = (size_t)(h + 2 * M) * (w + 2 * M);
-    float *gT = (float *)scratch;
-    float *gim = gT + (size_t)B * en;
-    uint8_t *gf = (uint8_t *)(gim + (size_t)B * en);
-    unsigned long long *gq = (unsigned long long *)((((uintptr_t)(gf + (size_t)B * en)) + 255) & ~(uintptr_t)255);
-    const int nslot = bg_slots(h, w), gq_stride = bg_gq_cap(h, w);
+    ScratchLayout L(scratch);
+    const BigClScratch S = inpaint_big_scratch(L, B, h, w, M);
+    const int nslot = S.nslot, gq_stride = S.gq_stride;
     // the capacity checked by the march: the slice itself, or (test hook) a smaller power of two inside it -- pushes stay within the slice
     const int gq_cap = (gq_cap_test >= 64 && gq_cap_test < gq_stride && (gq_cap_test & (gq_cap_test - 1)) == 0) ? gq_cap_test : gq_stride;
-    hipLaunchKernelGGL(k_bg_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, img, bad_big, left.dil, gT, gim, gf, range, h, w);
+    hipLaunchKernelGGL(k_bg_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, img, bad_big, left.dil, S.T, S.im, S.f, range, h, w);
     // LDS queue: 16384 entries (128 KB, one march per CU) while the batch has fewer big clusters than the chip has CUs -- a native crop has
     // about ten --, 8192 (two marches per CU) for larger batches; a cluster whose cell counts exceed the queue takes the global slice
     const int lds_cap = B <= 16 ? BG_QCAP : BG_QCAP / 2;
     static DynLdsOnce lds_once;
     ensure_dyn_lds(lds_once, (const void *)k_telea_big_clusters, BG_QCAP * 8 + 256);
-    hipLaunchKernelGGL(k_telea_big_clusters, dim3(nslot, B), dim3(64), (size_t)lds_cap * 8 + 256, st, img, gT, gim, gf, gq, left.labels, left.list, left.count,
+    hipLaunchKernelGGL(k_telea_big_clusters, dim3(nslot, B), dim3(64), (size_t)lds_cap * 8 + 256, st, img, S.T, S.im, S.f, S.gq, left.labels, left.list, left.count,
                        left.xmin, left.ymin, left.xmax, left.ymax, status, range, h, w, gq_stride, gq_cap, lds_cap, lds_queue ? lds_cap : 0);
 }
 

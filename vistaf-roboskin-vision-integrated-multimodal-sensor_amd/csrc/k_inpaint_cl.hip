@@ -12,7 +12,7 @@
 //   3. k_telea_clusters2 (k_inpaint_win.hip) marches every listed cluster on its own LDS window, one wave each,
 //      and flags the ones whose queue overflowed;
 //   4. k_split_bad builds the hole mask of the flagged clusters for the frame-window / whole-frame kernels.
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 namespace vf {
 
@@ -90,12 +90,31 @@ __global__ void k_split_bad(const uint8_t *__restrict__ bad, const int32_t *__re
     bad_big[i] = (uint8_t)(bad[i] && big[b * (size_t)P + labels[i]]);
 }
 
-// scratch layout per frame: dil u8[P] | labels i32[P] | xmin,ymin,xmax,ymax i32[P] x4 | list i32[P] | big u8[P] | bad_big u8[P] | count
-size_t inpaint_cl_scratch_bytes_per_frame(int h, int w)
+struct ClusterScratch {
+    uint8_t *dil;                       // [B, P] hole mask dilated by range + 1
+    int32_t *labels;                    // [B, P]
+    int32_t *xmin, *ymin, *xmax, *ymax; // [B, P] by root; xmin | ymin are one region, xmax | ymax another (one memset initialises each pair)
+    int32_t *list;                      // [B, P]
+    uint8_t *big, *bad_big;             // [B, P]
+    int32_t *count;                     // [B]
+};
+static ClusterScratch inpaint_cl_scratch(ScratchLayout &L, int B, int h, int w)
 {
-    size_t P = (size_t)h * w;
-    return P * (1 + 4 + 16 + 4 + 1 + 1) + 64;
+    const size_t n = (size_t)B * h * w;
+    ClusterScratch S;
+    S.dil = L.take<uint8_t>(n, 256, "dil");
+    S.labels = L.take<int32_t>(n, 256, "labels");
+    S.xmin = L.take<int32_t>(2 * n, 256, "xmin_ymin");
+    S.ymin = S.xmin ? S.xmin + n : nullptr;
+    S.xmax = L.take<int32_t>(2 * n, 256, "xmax_ymax");
+    S.ymax = S.xmax ? S.xmax + n : nullptr;
+    S.list = L.take<int32_t>(n, 256, "list");
+    S.big = L.take<uint8_t>(n, 256, "big");
+    S.bad_big = L.take<uint8_t>(n, 256, "bad_big");
+    S.count = L.take<int32_t>((size_t)B, 256, "count");
+    return S;
 }
+size_t inpaint_cl_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); inpaint_cl_scratch(L, B, h, w); return L.bytes(); }
 
 bool inpaint_clusters_supported(int range) { return inpaint_big_supported(range); }     // the left-over clusters need k_inpaint_big.hip
 
@@ -110,37 +129,28 @@ void launch_inpaint_clusters(float *img, const uint8_t *bad, int range, void *sc
 {
     const int P = h * w;
     const size_t n = (size_t)B * P;
-    uint8_t *base = (uint8_t *)scratch;
-    uint8_t *dil = base; base += (n + 255) & ~(size_t)255;
-    int32_t *labels = (int32_t *)base; base += n * 4;
-    int32_t *xmin = (int32_t *)base; base += n * 4;
-    int32_t *ymin = (int32_t *)base; base += n * 4;
-    int32_t *xmax = (int32_t *)base; base += n * 4;
-    int32_t *ymax = (int32_t *)base; base += n * 4;
-    int32_t *list = (int32_t *)base; base += n * 4;
-    uint8_t *big = base; base += (n + 255) & ~(size_t)255;
-    uint8_t *bad_big = base; base += (n + 255) & ~(size_t)255;
-    int32_t *count = (int32_t *)base;
+    ScratchLayout L(scratch);
+    const ClusterScratch S = inpaint_cl_scratch(L, B, h, w);
     RowSpanSE se;
     const int R = range + 1;   // hole pixels interact only within Chebyshev distance 2*range+1; R = range would already separate them
     se.k = 2 * R + 1;
     for (int i = 0; i < se.k; i++) { se.lo[i] = (int8_t)(-R); se.hi[i] = (int8_t)R; }
-    launch_morph(bad, dil, B, h, w, se, true, nullptr, nullptr, st);
-    launch_cc_label(dil, labels, B, h, w, st);
-    (void)hipMemsetAsync(xmin, 0x7f, n * 8, st);          // xmin, ymin
-    (void)hipMemsetAsync(xmax, 0, n * 8, st);             // xmax, ymax
-    (void)hipMemsetAsync(count, 0, (size_t)B * 4, st);
+    launch_morph(bad, S.dil, B, h, w, se, true, nullptr, nullptr, st);
+    launch_cc_label(S.dil, S.labels, B, h, w, st);
+    (void)hipMemsetAsync(S.xmin, 0x7f, n * 8, st);          // xmin, ymin
+    (void)hipMemsetAsync(S.xmax, 0, n * 8, st);             // xmax, ymax
+    (void)hipMemsetAsync(S.count, 0, (size_t)B * 4, st);
     dim3 g((P + 255) / 256, B);
-    hipLaunchKernelGGL(k_cluster_bbox, g, dim3(256), 0, st, bad, labels, xmin, ymin, xmax, ymax, h, w);
-    hipLaunchKernelGGL(k_cluster_list, g, dim3(256), 0, st, labels, xmin, ymin, xmax, ymax, list, count, big, range, inpaint_cluster_cells_cap(), h, w);
-    launch_telea_clusters2(img, bad, labels, list, count, xmin, ymin, xmax, ymax, big, range, B, h, w, st);
-    hipLaunchKernelGGL(k_split_bad, g, dim3(256), 0, st, bad, labels, big, bad_big, P);
-    *bad_big_out = bad_big;
+    hipLaunchKernelGGL(k_cluster_bbox, g, dim3(256), 0, st, bad, S.labels, S.xmin, S.ymin, S.xmax, S.ymax, h, w);
+    hipLaunchKernelGGL(k_cluster_list, g, dim3(256), 0, st, S.labels, S.xmin, S.ymin, S.xmax, S.ymax, S.list, S.count, S.big, range, inpaint_cluster_cells_cap(), h, w);
+    launch_telea_clusters2(img, bad, S.labels, S.list, S.count, S.xmin, S.ymin, S.xmax, S.ymax, S.big, range, B, h, w, st);
+    hipLaunchKernelGGL(k_split_bad, g, dim3(256), 0, st, bad, S.labels, S.big, S.bad_big, P);
+    *bad_big_out = S.bad_big;
     if (left) {
         // the list of the clusters marched above is dead: it now takes the roots that are left
-        (void)hipMemsetAsync(count, 0, (size_t)B * 4, st);
-        hipLaunchKernelGGL(k_cluster_list_big, g, dim3(256), 0, st, labels, xmin, big, list, count, h, w);
-        left->dil = dil; left->labels = labels; left->list = list; left->count = count; left->xmin = xmin; left->ymin = ymin; left->xmax = xmax; left->ymax = ymax;
+        (void)hipMemsetAsync(S.count, 0, (size_t)B * 4, st);
+        hipLaunchKernelGGL(k_cluster_list_big, g, dim3(256), 0, st, S.labels, S.xmin, S.big, S.list, S.count, h, w);
+        left->dil = S.dil; left->labels = S.labels; left->list = S.list; left->count = S.count; left->xmin = S.xmin; left->ymin = S.ymin; left->xmax = S.xmax; left->ymax = S.ymax;
     }
 }
 

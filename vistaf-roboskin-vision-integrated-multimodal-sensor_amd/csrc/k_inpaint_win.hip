@@ -21,7 +21,7 @@
 //   * queue entries are packed (T bits << 32 | cell) so a push moves one 64-bit word per lane;
 //   * the (2r+1)^2 estimator terms are accumulated per lane over the 64-neighbour chunks and reduced once.
 #include <cstdio>
-#include "kernels.hpp"
+#include "host_util.hpp"
 #include <type_traits>
 #include "telea_common.hpp"
 
@@ -380,18 +380,30 @@ void telea_window_debug_dump(int B)
 }
 #endif
 
-size_t inpaint_win_scratch_bytes(int B) { return (size_t)B * 5 * sizeof(int32_t) + 256; }
+struct WinScratch {
+    int32_t *box;           // [4][B] xmin, ymin, xmax, ymax of the hole pixels
+    int32_t *fb;            // [B] fallback flags; the fifth plane of box's region (one memset clears planes 2..4)
+};
+static WinScratch inpaint_win_scratch(ScratchLayout &L, int B)
+{
+    WinScratch S;
+    S.box = L.take<int32_t>(5 * (size_t)B, 256, "box_fb");
+    S.fb = S.box ? S.box + 4 * (size_t)B : nullptr;
+    return S;
+}
+size_t inpaint_win_scratch_bytes(int B, ScratchRec *rec) { ScratchLayout L(nullptr, rec); inpaint_win_scratch(L, B); return L.bytes(); }
 
-// box scratch: [4][B] bbox planes + [B] fallback flags.  Returns the device pointer of the fallback flags.
+// Returns the device pointer of the fallback flags.
 int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *scratch, int B, int h, int w, hipStream_t st, hipEvent_t ev_march,
                                bool two_tier, bool mw)
 {
-    int32_t *box = (int32_t *)scratch, *fb = box + 4 * (size_t)B;
-    (void)hipMemsetAsync(box, 0x7f, (size_t)B * 8, st);
-    (void)hipMemsetAsync(box + 2 * (size_t)B, 0, (size_t)B * 12, st);
+    ScratchLayout L(scratch);
+    const WinScratch S = inpaint_win_scratch(L, B);
+    (void)hipMemsetAsync(S.box, 0x7f, (size_t)B * 8, st);
+    (void)hipMemsetAsync(S.box + 2 * (size_t)B, 0, (size_t)B * 12, st);
     const int P = h * w;
-    if (P % 16 == 0) hipLaunchKernelGGL(k_bad_bbox<true>, dim3((P / 16 + 255) / 256, B), dim3(256), 0, st, bad, box, B, h, w);
-    else hipLaunchKernelGGL(k_bad_bbox<false>, dim3((P + 255) / 256, B), dim3(256), 0, st, bad, box, B, h, w);
+    if (P % 16 == 0) hipLaunchKernelGGL(k_bad_bbox<true>, dim3((P / 16 + 255) / 256, B), dim3(256), 0, st, bad, S.box, B, h, w);
+    else hipLaunchKernelGGL(k_bad_bbox<false>, dim3((P + 255) / 256, B), dim3(256), 0, st, bad, S.box, B, h, w);
     auto lds_bytes = [](int cells, int q) { return (size_t)cells * 9 + (size_t)q * 8 + 256; };
     static DynLdsOnce lds_once, lds_once_retry;
     ensure_dyn_lds(lds_once, (const void *)k_telea_window, 160 * 1024);
@@ -399,16 +411,16 @@ int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *
     if (ev_march) (void)hipEventRecord(ev_march, st);     // stage timing: the march starts here (the bbox pass belongs to the mask stage)
     if (mw && inpaint_window_mw_supported(range)) {
         // first tier: one 16-wave workgroup per frame (k_inpaint_mw.hip); what it hands back goes to the full-size single-wave march
-        launch_telea_window_mw(img, bad, box, fb, range, B, h, w, st);
-        hipLaunchKernelGGL(k_telea_window_retry, dim3(std::min(B, WN2_GRID)), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, box, fb, range, B, h, w,
+        launch_telea_window_mw(img, bad, S.box, S.fb, range, B, h, w, st);
+        hipLaunchKernelGGL(k_telea_window_retry, dim3(std::min(B, WN2_GRID)), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, S.box, S.fb, range, B, h, w,
                            WN_CELLS, WN_QCAP);
     } else if (two_tier) {
-        hipLaunchKernelGGL(k_telea_window, dim3(B), dim3(64), lds_bytes(WN1_CELLS, WN1_QCAP), st, img, bad, box, fb, range, B, h, w, WN1_CELLS, WN1_QCAP);
-        hipLaunchKernelGGL(k_telea_window_retry, dim3(std::min(B, WN2_GRID)), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, box, fb, range, B, h, w,
+        hipLaunchKernelGGL(k_telea_window, dim3(B), dim3(64), lds_bytes(WN1_CELLS, WN1_QCAP), st, img, bad, S.box, S.fb, range, B, h, w, WN1_CELLS, WN1_QCAP);
+        hipLaunchKernelGGL(k_telea_window_retry, dim3(std::min(B, WN2_GRID)), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, S.box, S.fb, range, B, h, w,
                            WN_CELLS, WN_QCAP);
     } else
-        hipLaunchKernelGGL(k_telea_window, dim3(B), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, box, fb, range, B, h, w, WN_CELLS, WN_QCAP);
-    return fb;
+        hipLaunchKernelGGL(k_telea_window, dim3(B), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, S.box, S.fb, range, B, h, w, WN_CELLS, WN_QCAP);
+    return S.fb;
 }
 
 }  // namespace vf

@@ -352,7 +352,7 @@ void launch_tail(const float *height_mm, const uint8_t *roi_or_null, const float
                  PostParams pp, double *scalars, int nscal, double *out3_or_null, int B, int P, hipStream_t st, void *scratch, size_t scratch_bytes)
 {
     const int nblk = (P + TP_T * TP_PX - 1) / (TP_T * TP_PX);
-    if (scratch && P >= 262144 && B <= 192 && (size_t)B * nblk * TP_WORDS * 8 <= scratch_bytes) {
+    if (scratch && big_frames(B, P) && (size_t)B * nblk * TP_WORDS * 8 <= scratch_bytes) {
         unsigned long long *part = (unsigned long long *)scratch;
         hipLaunchKernelGGL(k_tail_part, dim3(nblk, B), dim3(TP_T), 0, st, height_mm, roi_or_null, unitless_or_null, roi_static, (float)pp.depth_eps_mm,
                            scalars != nullptr ? 1 : 0, part, P);

@@ -16,7 +16,7 @@
 // Known difference: the median is selected among the FINITE valid values; NumPy's counts +-inf too (only an explicit mask can hold them; the
 // chain's isfinite mask never does).  The sign of a zero min / max when +0 and -0 tie follows no fixed element order here (nor in NumPy's
 // SIMD reduction).
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 namespace vf {
 namespace {
@@ -271,39 +271,33 @@ __global__ __launch_bounds__(256) void k_st_final(StWork w, int sq, double *__re
     out[5] = (double)n;
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-StWork st_carve(void *scratch, size_t P)
+StWork tstats_scratch(ScratchLayout &L, int h, int w)
 {
-    const size_t nt = (P + ST_TILE - 1) / ST_TILE;
-    uint8_t *p = (uint8_t *)scratch;
-    StWork w;
-    w.s = (StState *)p; p += al256(sizeof(StState));
-    w.vals = (float *)p; p += al256(P * 4);
-    w.sel = p; p += al256(P);
-    w.tcnt = (uint32_t *)p; p += al256(nt * 4);
-    w.tnan = (uint32_t *)p; p += al256(nt * 4);
-    w.toff = (uint32_t *)p; p += al256(nt * 4);
-    w.tmin = (float *)p; p += al256(nt * 4);
-    w.tmax = (float *)p; p += al256(nt * 4);
-    w.bsum = (float *)p;
-    return w;
+    const size_t P = (size_t)h * w, nt = (P + ST_TILE - 1) / ST_TILE, nb = (P + ST_BUF - 1) / ST_BUF;
+    StWork wk;
+    wk.s = L.take<StState>(1, 256, "s");
+    wk.vals = L.take<float>(P, 256, "vals");
+    wk.sel = L.take<uint8_t>(P, 256, "sel");
+    wk.tcnt = L.take<uint32_t>(nt, 256, "tcnt");
+    wk.tnan = L.take<uint32_t>(nt, 256, "tnan");
+    wk.toff = L.take<uint32_t>(nt, 256, "toff");
+    wk.tmin = L.take<float>(nt, 256, "tmin");
+    wk.tmax = L.take<float>(nt, 256, "tmax");
+    wk.bsum = L.take<float>(nb, 256, "bsum");
+    return wk;
 }
 
 }  // namespace
 
-size_t tstats_scratch_bytes(int h, int w)
-{
-    const size_t P = (size_t)h * w, nt = (P + ST_TILE - 1) / ST_TILE, nb = (P + ST_BUF - 1) / ST_BUF;
-    return al256(sizeof(StState)) + al256(P * 4) + al256(P) + 5 * al256(nt * 4) + al256(nb * 4) + 256;
-}
+size_t tstats_scratch_bytes(int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); tstats_scratch(L, h, w); return L.bytes(); }
 
 bool tstats_needs_big_scratch(int h, int w) { return big_frames(1, h * w); }
 
 void launch_tstats(const float *map, const uint8_t *valid, int h, int w, void *scratch, void *big_scratch, double *out, hipStream_t st)
 {
     const size_t P = (size_t)h * w;
-    const StWork wk = st_carve(scratch, P);
+    ScratchLayout L(scratch);
+    const StWork wk = tstats_scratch(L, h, w);
     const unsigned nt = (unsigned)((P + ST_TILE - 1) / ST_TILE), nb = (unsigned)((P + ST_BUF - 1) / ST_BUF);
     hipLaunchKernelGGL(k_st_init, dim3(1), dim3(1), 0, st, wk.s);
     hipLaunchKernelGGL(k_st_count, dim3(nt), dim3(ST_T), 0, st, map, valid, wk, P);

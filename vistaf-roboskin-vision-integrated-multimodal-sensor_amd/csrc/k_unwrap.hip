@@ -18,7 +18,7 @@
 //                   so any evaluation order gives the tree's exact counts) and writes u = w + 2*pi*k.
 // In exact arithmetic u[p] - w[p] is the same multiple of 2*pi as in the reference's
 // u[p] = u[parent] + angle(exp(1j*(w[p]-w[parent]))) chain; only float32 rounding along the chain differs.
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 namespace vf {
 
@@ -204,25 +204,52 @@ __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ 
     }
 }
 
-size_t unwrap_fast_scratch_bytes_per_frame(int h, int w);
-static size_t unwrap_flood_scratch_bytes_per_frame(int h, int w)
-{
-    size_t P = (size_t)h * w, EN = (size_t)(h + 2) * (w + 2);
-    const size_t code_bytes = EN > 65533 ? 4 * EN + 32 : 2 * EN + 16;     // uint32 rank codes for frames beyond the uint16 range
-    return P /*st*/ + 5 * EN * sizeof(uint32_t) /*sort / frontier / jump buffers / padded parents*/ + code_bytes /*rank codes*/ + 64 /*seed, n, flag*/ + 1536 /*alignment of the sub-planes, also for a batch of one*/;
-}
-
-// the flood's planes for B frames come first, the consistency check's (k_unwrap_fast.hip) behind them
-size_t unwrap_scratch_bytes_per_frame(int h, int w) { return unwrap_flood_scratch_bytes_per_frame(h, w) + unwrap_fast_scratch_bytes_per_frame(h, w) + 16; }
-
 bool unwrap_ranked_supported(int h, int w);
+
+// The flood's planes, then the check's.  EN = (h + 2)(w + 2) is the per-frame stride of the uint32 planes; sort_a and sort_b are two of them
+// each (2 EN per frame), and what they hold changes along a path:
+struct UnwrapScratch {
+    uint8_t *state;                     // [B, P] pixel states of the generic flood
+    uint32_t *sort_a, *sort_b;          // [B, 2 EN] the rank kernels' 8-byte sort records; sort_a then holds the sorted pixel indices (stride 2 EN)
+    int32_t *ppar;                      // [B, EN] parents in padded index space (batched and bitmap floods)
+    void *rank;                         // [B, EN + 8] rank codes: uint16 while EN <= 65533, else uint32
+    int32_t *seed, *nmask, *need_generic;   // [B]
+    uint32_t *pop_log;                  // = sort_b: the batched flood's pop log (stride 2 EN), written once the ranks are out
+    uint32_t *frontier_q, *frontier_i;  // = sort_a, sort_a + B EN: the generic flood's frontier (stride P), the sorted indices being dead by then
+    unsigned long long *tree_words;     // = sort_a: k_unwrap_tree's 64-bit words (stride EN), after the floods
+    UfPlanes check;
+    size_t EN;
+};
+static UnwrapScratch unwrap_scratch(ScratchLayout &L, int B, int h, int w)
+{
+    UnwrapScratch S;
+    S.EN = (size_t)(h + 2) * (w + 2);
+    const size_t nb = (size_t)B, gn = nb * S.EN;
+    S.state = L.take<uint8_t>(nb * h * w, 256, "state");
+    S.sort_a = L.take<uint32_t>(2 * gn, 256, "sort_a");
+    S.sort_b = L.take<uint32_t>(2 * gn, 256, "sort_b");
+    S.ppar = L.take<int32_t>(gn, 256, "ppar");
+    if (unwrap_ranked_supported(h, w)) S.rank = L.take<uint16_t>(gn + 8 * nb, 256, "rank");
+    else S.rank = L.take<uint32_t>(gn + 8 * nb, 256, "rank");
+    S.seed = L.take<int32_t>(nb, 256, "seed");
+    S.nmask = L.take<int32_t>(nb, 256, "nmask");
+    S.need_generic = L.take<int32_t>(nb, 256, "need_generic");
+    S.pop_log = S.sort_b;
+    S.frontier_q = S.sort_a;
+    S.frontier_i = S.sort_a ? S.sort_a + gn : nullptr;
+    S.tree_words = (unsigned long long *)S.sort_a;
+    S.check = unwrap_fast_planes(L, B, h, w);
+    return S;
+}
+size_t unwrap_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); unwrap_scratch(L, B, h, w); return L.bytes(); }
+
 void launch_unwrap_ranked(const float *quality, const uint8_t *mask, uint32_t *g0, uint32_t *g2, int32_t *ppar, size_t gstride, uint16_t *rank16,
                           int32_t *seed, int B, int h, int w, hipStream_t st, hipEvent_t ev_flood, const int32_t *need);
 void launch_unwrap_replay(const float *wrapped, const uint32_t *order, size_t ostride, const int32_t *ppar, size_t gstride, int32_t *tree,
                           float *unwrapped, int B, int h, int w, hipStream_t st, const int32_t *need);
 bool unwrap_big_supported(int h, int w);
 bool unwrap_fast_supported(int h, int w);
-void launch_unwrap_fast(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *need, void *scratch, int B, int h, int w,
+void launch_unwrap_fast(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *need, const UfPlanes &U, int B, int h, int w,
                         hipStream_t st);
 void launch_unwrap_rank32(const float *quality, const uint8_t *mask, uint32_t *gA, uint32_t *gB, size_t gstride, uint32_t *rank32, int32_t *seed,
                           int32_t *n_out, int B, int h, int w, hipStream_t st, const int32_t *need);
@@ -233,52 +260,39 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
                    void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid, hipEvent_t ev_flood, bool big_handback,
                    int32_t *need_buf)
 {
-    int P = h * w;
-    size_t n = (size_t)B * P;
-    size_t EN = (size_t)(h + 2) * (w + 2);           // per-frame stride of the uint32 planes
-    // scratch: [B*P st bytes][5 x B*EN u32][B*EN rank codes][B seeds, ...]
-    uint8_t *gst = (uint8_t *)scratch;
-    uint32_t *g0 = (uint32_t *)((uint8_t *)scratch + ((n + 255) & ~(size_t)255));
-    size_t gn = (size_t)B * EN;
-    uint32_t *g1 = g0 + gn, *g2 = g1 + gn, *g3 = g2 + gn, *g4 = g3 + gn;
-    uint8_t *after = (uint8_t *)(((uintptr_t)(g4 + gn) + 255) & ~(uintptr_t)255);
+    const int P = h * w;
+    ScratchLayout L(scratch);
+    const UnwrapScratch S = unwrap_scratch(L, B, h, w);
+    const size_t EN = S.EN;
     // First the consistency check (k_unwrap_fast.hip): frames whose wrapped field is path-independent on the seed's component get their
     // plane from a parallel integration, and every kernel of the priority flood below skips them (need[b] = 0).  The parent plane of
     // such a frame is not produced (it is a by-product of the flood; the parity tests that compare trees switch the check off).
     const int32_t *need = nullptr;
     if (need_buf && unwrap_fast_supported(h, w)) {
-        void *fs = (void *)(((uintptr_t)scratch + unwrap_flood_scratch_bytes_per_frame(h, w) * (size_t)B + 255) & ~(uintptr_t)255);
-        launch_unwrap_fast(wrapped, quality, mask, unwrapped, need_buf, fs, B, h, w, st);
+        launch_unwrap_fast(wrapped, quality, mask, unwrapped, need_buf, S.check, B, h, w, st);
         need = need_buf;
     }
     if (unwrap_ranked_supported(h, w)) {
-        // frames of at most 65533 padded pixels: uint16 ranks, the batched flood in LDS, then the replay of its pop log (g2)
-        uint16_t *rank16 = (uint16_t *)after;
-        int32_t *seed = (int32_t *)(after + (((gn + 8 * (size_t)B) * 2 + 255) & ~(size_t)255));
-        launch_unwrap_ranked(quality, mask, g0, g2, (int32_t *)g4, EN, rank16, seed, B, h, w, st, ev_flood, need);
+        // frames of at most 65533 padded pixels: uint16 ranks, the batched flood in LDS, then the replay of its pop log
+        launch_unwrap_ranked(quality, mask, S.sort_a, S.sort_b, S.ppar, EN, (uint16_t *)S.rank, S.seed, B, h, w, st, ev_flood, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
-        launch_unwrap_replay(wrapped, g2, 2 * EN, (const int32_t *)g4, EN, parent, unwrapped, B, h, w, st, need);
+        launch_unwrap_replay(wrapped, S.pop_log, 2 * EN, S.ppar, EN, parent, unwrapped, B, h, w, st, need);
     } else if (unwrap_big_supported(h, w)) {
         // frames beyond the uint16 rank range (native crops): 32-bit ranks, bitmap priority queue in LDS, plane in global memory
         // (k_unwrap_big.hip); masks too large for the bitmap (big_handback: every mask) go through the generic kernel, frame by frame
-        uint32_t *rank32 = (uint32_t *)after;
-        int32_t *seed = (int32_t *)(after + (((gn + 8 * (size_t)B) * 4 + 255) & ~(size_t)255));
-        int32_t *nmask = seed + B, *need_generic = nmask + B;
-        launch_unwrap_rank32(quality, mask, g0, g2, EN, rank32, seed, nmask, B, h, w, st, need);
+        launch_unwrap_rank32(quality, mask, S.sort_a, S.sort_b, EN, (uint32_t *)S.rank, S.seed, S.nmask, B, h, w, st, need);
         if (ev_flood) hipEventRecord(ev_flood, st);
-        launch_unwrap_flood_big(rank32, seed, nmask, g0, 2 * EN, (int32_t *)g4, EN, need_generic, big_handback, B, h, w, st, need);
-        // (the generic kernel's frontier arrays reuse g0 | g1: the sorted indices are dead by now)
-        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, need_generic, need);
+        launch_unwrap_flood_big((uint32_t *)S.rank, S.seed, S.nmask, S.sort_a, 2 * EN, S.ppar, EN, S.need_generic, big_handback, B, h, w, st, need);
+        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, S.state, S.frontier_q, S.frontier_i, P, status, h, w, S.need_generic, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
-        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)g4, EN, (unsigned long long *)g0, unwrapped, h, w,
-                           need_generic, need);
+        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)S.ppar, EN, S.tree_words, unwrapped, h, w,
+                           S.need_generic, need);
     } else {
         // frames of 2^26 padded pixels and more: the generic kernel, frontier and pixel states in global memory
         if (ev_flood) hipEventRecord(ev_flood, st);
-        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, gst, g0, g1, P, status, h, w, (const int32_t *)nullptr, need);
+        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, S.state, S.frontier_q, S.frontier_i, P, status, h, w, (const int32_t *)nullptr, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
-        // g0|g1 (2 x B*EN uint32, contiguous) hold the per-pixel 64-bit words; stride EN words per frame
-        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)nullptr, EN, (unsigned long long *)g0, unwrapped, h, w,
+        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)nullptr, EN, S.tree_words, unwrapped, h, w,
                            (const int32_t *)nullptr, need);
     }
 }

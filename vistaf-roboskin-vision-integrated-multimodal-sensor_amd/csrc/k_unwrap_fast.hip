@@ -23,7 +23,7 @@
 // kernels serve 224 x 224 and the native 1182 x 1182 crops.
 #include <algorithm>
 #include <cstdio>
-#include "kernels.hpp"
+#include "host_util.hpp"
 
 namespace vf {
 
@@ -32,20 +32,6 @@ constexpr int UF_CH = 4;              // 64-pixel chunks of a row in flight per 
 constexpr int UF_PASSES = 8;          // sweeps over the edge list between two barriers of the offset propagation
 constexpr int UF_LDS_RUNS = 6144, UF_LDS_EDGES = 12288;      // propagation in LDS: 4 B per run + 6 B per edge = 96 KB
 enum { UFC_NEDGE = 0, UFC_FAIL = 1, UFC_R = 2, UFC_N = 4 };
-
-// per-frame planes of the check, carved out of the unwrap scratch (dead again before the flood kernels of a failed frame start)
-struct UfPlanes {
-    int8_t *kk;                 // [P16] k of the pixel (relative to its run, later absolute); -128 = not in the mask, -127 = never reached
-    int32_t *rowbase;           // [hp] first run of each row; rowbase[h] = number of runs
-    uint32_t *rstate;           // [rcap] UF_KNOWN | (offset & 0xFFFF)
-    uint16_t *rs, *re, *ry;     // [rcap] first / last column, row
-    uint16_t *ei, *ej;          // [ecap] run above, run below
-    int16_t *ed;                // [ecap] offset[below] - offset[above]
-    unsigned long long *seedkey;// [B]
-    int32_t *ctl;               // [B][UFC_N]
-    size_t P16, hp;
-    int rcap, ecap;
-};
 
 // c(a -> b): the integer k that brings d = w[b] - w[a] into (-pi, pi], i.e. what k_unwrap_tree's float64  k = -rint(d / 2 pi) + one correction
 // step yields.  The wrapped plane comes from atan2, so |d| <= 2 pi and k is -1, 0 or +1: decided here by comparing the float32 difference
@@ -445,42 +431,33 @@ __global__ __launch_bounds__(256) void k_uf_plane(const float *__restrict__ wrap
     }
 }
 
-static void uf_caps(int h, int w, int &rcap, int &ecap)
+// the check's planes for B frames, each plane batch-major: the tail of unwrap_scratch()'s layout (k_unwrap.hip)
+UfPlanes unwrap_fast_planes(ScratchLayout &L, int B, int h, int w)
 {
-    (void)w;
-    rcap = std::min(60000, std::max(4096, 8 * h));
-    ecap = std::min(65000, 2 * rcap);
-}
-size_t unwrap_fast_scratch_bytes_per_frame(int h, int w)
-{
-    int rcap, ecap;
-    uf_caps(h, w, rcap, ecap);
-    const size_t P16 = ((size_t)h * w + 15) & ~(size_t)15, hp = ((size_t)h + 2 + 3) & ~(size_t)3;
-    return P16 + hp * 4 + (size_t)rcap * 10 + (size_t)ecap * 6 + 8 + UFC_N * 4 + 64;
+    UfPlanes U;
+    U.rcap = std::min(60000, std::max(4096, 8 * h));
+    U.ecap = std::min(65000, 2 * U.rcap);
+    U.P16 = ((size_t)h * w + 15) & ~(size_t)15;
+    U.hp = ((size_t)h + 2 + 3) & ~(size_t)3;
+    const size_t nb = (size_t)B, nr = (size_t)U.rcap * nb, ne = (size_t)U.ecap * nb;
+    U.kk = L.take<int8_t>(U.P16 * nb, 256, "check.kk");
+    U.rowbase = L.take<int32_t>(U.hp * nb, 256, "check.rowbase");
+    U.rstate = L.take<uint32_t>(nr, 256, "check.rstate");
+    U.rs = L.take<uint16_t>(nr, 256, "check.rs");
+    U.re = L.take<uint16_t>(nr, 256, "check.re");
+    U.ry = L.take<uint16_t>(nr, 256, "check.ry");
+    U.ei = L.take<uint16_t>(ne, 256, "check.ei");
+    U.ej = L.take<uint16_t>(ne, 256, "check.ej");
+    U.ed = L.take<int16_t>(ne, 256, "check.ed");
+    U.seedkey = L.take<unsigned long long>(nb, 256, "check.seedkey");
+    U.ctl = L.take<int32_t>(nb * UFC_N, 256, "check.ctl");
+    return U;
 }
 bool unwrap_fast_supported(int h, int w) { return h >= 2 && w >= 2 && h <= 32767 && w <= 65535 && (long long)h * w < 0x7fffffffLL; }
 
-// scratch: unwrap_fast_scratch_bytes_per_frame(h, w) * B bytes, 16-byte aligned
-void launch_unwrap_fast(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *need, void *scratch, int B, int h, int w,
+void launch_unwrap_fast(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *need, const UfPlanes &U, int B, int h, int w,
                         hipStream_t st)
 {
-    UfPlanes U;
-    uf_caps(h, w, U.rcap, U.ecap);
-    U.P16 = ((size_t)h * w + 15) & ~(size_t)15;
-    U.hp = ((size_t)h + 2 + 3) & ~(size_t)3;
-    uint8_t *p = (uint8_t *)scratch;
-    U.kk = (int8_t *)p; p += U.P16 * B;
-    U.rowbase = (int32_t *)p; p += U.hp * 4 * B;
-    U.rstate = (uint32_t *)p; p += (size_t)U.rcap * 4 * B;
-    U.rs = (uint16_t *)p; p += (size_t)U.rcap * 2 * B;
-    U.re = (uint16_t *)p; p += (size_t)U.rcap * 2 * B;
-    U.ry = (uint16_t *)p; p += (size_t)U.rcap * 2 * B;
-    U.ei = (uint16_t *)p; p += (size_t)U.ecap * 2 * B;
-    U.ej = (uint16_t *)p; p += (size_t)U.ecap * 2 * B;
-    U.ed = (int16_t *)p; p += (size_t)U.ecap * 2 * B;
-    p = (uint8_t *)(((uintptr_t)p + 15) & ~(uintptr_t)15);
-    U.seedkey = (unsigned long long *)p; p += (size_t)8 * B;
-    U.ctl = (int32_t *)p;
     (void)hipMemsetAsync(U.seedkey, 0, (size_t)8 * B, st);
     // rows per wave: enough waves to fill the chip several times over, no more (a wave that lives for one row is all dispatch overhead)
     // (measured at 224 x 224 x 256: 4 waves x 4 rows 0.31 ms, 8 x 2 0.33, 2 x 8 0.34, 4 x 1 0.36, 16 x 1 0.41 -- the shape is not what these passes cost)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "common.hpp"
 
 namespace vf {
@@ -25,6 +26,15 @@ struct Tiers {
     int select_resident = 1;    // 1: the exact selections of planes of up to 65536 pixels keep their keys in registers (k_select_resident) and the core threshold and core median share a launch; 0: the streaming k_select, one launch per selection
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
+
+// Frames of 512 x 512 pixels and more: the ones whose per-frame stages are split over the chip (k_big.hip and the chunked tiers)
+inline bool large_frame(size_t P) { return P >= 262144; }
+
+// host_util.hpp: the bump carver every scratch layout is written with, beside its launcher.  The *_scratch_bytes() below run the same layout on a
+// null base; `rec` (vistaf_ftp_test_scratch_regions only) receives the regions
+struct ScratchLayout;
+struct ScratchRegion;
+using ScratchRec = std::vector<ScratchRegion>;
 
 struct RowSpanSE {      // structuring element as per-row x spans (cv::getStructuringElement ELLIPSE)
     int k;              // k x k, anchor at centre (k <= 33)
@@ -132,13 +142,16 @@ void launch_chamfer_pair(const uint8_t *src, int32_t *tmp_a, float *dist_a, int3
 void launch_erode_by_dist(const float *dist, const uint8_t *src, float margin, uint8_t *out, int B, int P, hipStream_t st);
 
 // ---- k_inpaint.hip ----------------------------------------------------------------------------
-size_t inpaint_scratch_bytes_per_frame(int h, int w);
+// the whole-frame kernel's planes; inpaint_scratch_bytes: the buffer launch_inpaint_telea and launch_inpaint_big_clusters share (never both in
+// one step), the larger of the two layouts
+size_t telea_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
+size_t inpaint_scratch_bytes(int B, int h, int w);
 // `only` (device, [B], may be null): process just the frames with only[b] != 0
 void launch_inpaint_telea(float *img, const uint8_t *bad, int range, void *scratch, int32_t *status, const int32_t *only, int B, int h, int w,
                           hipStream_t st, bool round_u8 = false);      // round_u8: 8-bit image semantics (values 0..255 held as floats, OpenCV's rounding of every estimate)
 
 // ---- k_inpaint_win.hip (LDS-resident window kernel; returns the per-frame fallback flags for launch_inpaint_telea)
-size_t inpaint_win_scratch_bytes(int B);
+size_t inpaint_win_scratch_bytes(int B, ScratchRec *rec = nullptr);
 // ---- k_inpaint_mw.hip (16 waves per frame: ordering pass, then the estimates as a dataflow; flags the frames it cannot take in fb[])
 bool inpaint_window_mw_supported(int range);
 void launch_telea_window_mw(float *img, const uint8_t *bad, const int32_t *box, int32_t *fb, int range, int B, int h, int w, hipStream_t st);
@@ -146,11 +159,12 @@ int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *
                                hipEvent_t ev_march = nullptr, bool two_tier = true, bool mw = true);
 
 // ---- k_inpaint_cl.hip (cluster-parallel front end; leaves oversized clusters in *bad_big_out) ----------
-size_t inpaint_cl_scratch_bytes_per_frame(int h, int w);
+size_t inpaint_cl_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
 bool inpaint_clusters_supported(int range);
 struct ClusterPlanes { const int32_t *labels, *list, *count, *xmin, *ymin, *xmax, *ymax; const uint8_t *dil; };     // [B, P] planes indexed by component root; dil = hole mask dilated by range + 1
 // the clusters the LDS windows left over, each on its own wave over padded global planes with the queue in LDS (k_inpaint_big.hip)
-size_t inpaint_big_scratch_bytes_per_frame(int h, int w);
+// range 0: at the widest padding launch_inpaint_big_clusters takes, which is what a session allocates
+size_t inpaint_big_scratch_bytes(int B, int h, int w, int range = 0, ScratchRec *rec = nullptr);
 bool inpaint_big_supported(int range);
 // gq_cap (test hook big_gq_cap): capacity the march checks its global queue slice against, a power of two <= the slice; 0: the slice's size
 void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, void *scratch, int32_t *status, const ClusterPlanes &left, int B, int h,
@@ -161,7 +175,21 @@ void launch_inpaint_clusters(float *img, const uint8_t *bad, int range, void *sc
                              hipStream_t st);
 
 // ---- k_unwrap.hip -----------------------------------------------------------------------------
-size_t unwrap_scratch_bytes_per_frame(int h, int w);
+// per-frame planes of the consistency check (k_unwrap_fast.hip), dead again before the flood kernels of a failed frame start
+struct UfPlanes {
+    int8_t *kk;                 // [P16] k of the pixel (relative to its run, later absolute); -128 = not in the mask, -127 = never reached
+    int32_t *rowbase;           // [hp] first run of each row; rowbase[h] = number of runs
+    uint32_t *rstate;           // [rcap] UF_KNOWN | (offset & 0xFFFF)
+    uint16_t *rs, *re, *ry;     // [rcap] first / last column, row
+    uint16_t *ei, *ej;          // [ecap] run above, run below
+    int16_t *ed;                // [ecap] offset[below] - offset[above]
+    unsigned long long *seedkey;// [B]
+    int32_t *ctl;               // [B][UFC_N]
+    size_t P16, hp;
+    int rcap, ecap;
+};
+UfPlanes unwrap_fast_planes(ScratchLayout &L, int B, int h, int w);
+size_t unwrap_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
                    void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid,
                    hipEvent_t ev_flood = nullptr, bool big_handback = false, int32_t *need_buf = nullptr);      // need_buf [B]: enables the consistency check (k_unwrap_fast.hip)
@@ -243,8 +271,8 @@ void launch_contacts(const float *depth, const uint8_t *kept, const int32_t *lab
                      hipStream_t st);
 
 // ---- k_big.hip (large frames: selection and IRLS fit as chains of streaming kernels over all pixels of the batch)
-size_t big_scratch_bytes(int B, int h, int w);
-bool big_frames(int B, int P);
+size_t big_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
+bool big_frames(int B, int P);      // large_frame(P) in a batch small enough that one workgroup per frame cannot fill the chip
 void launch_select_big(const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, bool use_abs, const float *reqs_dev, int nreq,
                        float *out, int *counts, int B, int P, void *scratch, hipStream_t st);
 void launch_robust_polyfit_big(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
@@ -266,7 +294,7 @@ void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t 
 
 // ---- k_tempstats.hip (NumPy-exact mean / median / std / min / max / count of a float32 map over a valid mask, or isfinite when NULL):
 // out[6] doubles on the device; scratch of tstats_scratch_bytes, plus big_scratch_bytes(1, h, w) when tstats_needs_big_scratch (else NULL)
-size_t tstats_scratch_bytes(int h, int w);
+size_t tstats_scratch_bytes(int h, int w, ScratchRec *rec = nullptr);
 bool tstats_needs_big_scratch(int h, int w);
 void launch_tstats(const float *map, const uint8_t *valid, int h, int w, void *scratch, void *big_scratch, double *out, hipStream_t st);
 

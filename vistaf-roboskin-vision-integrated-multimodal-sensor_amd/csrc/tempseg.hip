@@ -400,7 +400,7 @@ static int tm_ensure(vistaf_tempseg_handle *h)
     TMTRY(h->allocs.alloc(&h->tmM1, h->P)); TMTRY(h->allocs.alloc(&h->tmM2, h->P));
     TMTRY(h->allocs.alloc(&h->tm_kx, (size_t)1024)); TMTRY(h->allocs.alloc(&h->tm_ky, (size_t)1024));
     uint8_t *p = nullptr;
-    TMTRY(h->allocs.alloc(&p, inpaint_scratch_bytes_per_frame(h->H, h->W))); h->tm_scratch = p;
+    TMTRY(h->allocs.alloc(&p, inpaint_scratch_bytes(1, h->H, h->W))); h->tm_scratch = p;
     TMTRY(h->allocs.alloc(&h->tm_stats, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_status, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_counts, (size_t)4));
 #undef TMTRY
     h->tm_ready = true;

@@ -39,7 +39,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
 /* The production launchers of three kernel families on device planes of the caller, so that a test can feed them inputs no fringe image
  * produces.  Every call runs on `stream`, waits for it and returns 0 (or a VISTAF_E_* code; text in vistaf_ftp_last_error).
- * variant: 0 dispatch as a session does (the k_big.hip chain for planes of 262144 pixels and more, in batches it takes),
+ * variant: 0 dispatch as a session does (the k_big.hip chain for planes of 512 x 512 pixels and more -- large_frame of kernels.hpp --, in batches it takes),
  *          1 the one-workgroup-per-frame kernels whatever the size,
  *          2 the k_big.hip chain; VISTAF_E_INVALID when it does not take (B, plane size).  Its scratch is allocated and freed by the call.
  *          3 (vistaf_ftp_test_select only) the streaming one-workgroup-per-frame kernel k_select whatever the size; under variant 1 planes of
@@ -81,6 +81,14 @@ int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int
  * mask[b] (w <= 1280; beyond 512 columns only a band of more than 64 rows, cap_px >= 60 and h > 64, takes the two-pass kernel); pair == 0: launch_chamfer, dist_a only, to the zero pixels or (invert != 0) to the non-zero pixels (w <= 512).
  * Planes are [B, h, w]; the integer temporaries are allocated and freed by the call. */
 int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream);
+
+/* The scratch layout of one stage, from a counting pass of the function its launcher carves with (ScratchLayout, host_util.hpp).  Makes no HIP
+ * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored).
+ * Region i, in carve order: names + 32 * i (NUL-terminated), offset[i], bytes[i], align[i]; *total = the size the stage's *_scratch_bytes
+ * returns (for "inpaint_big": at this range, not at the widest padding).  Returns the number of regions, or VISTAF_E_INVALID for an unknown
+ * stage, a bad shape, or more regions than `cap`. */
+int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
+                                    size_t *total);
 #ifdef __cplusplus
 }
 #endif
