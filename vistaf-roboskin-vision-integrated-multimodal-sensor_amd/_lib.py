@@ -52,7 +52,8 @@ EXPORTS = [
 ]
 # csrc/test_hooks.h: kernel tier selection / debug planes for the parity tests, and the selection, fit and blur launchers on planes of the test's own
 TEST_EXPORTS = ["vistaf_ftp_test_set", "vistaf_ftp_test_select", "vistaf_ftp_test_select_instance", "vistaf_ftp_test_select_chained", "vistaf_ftp_test_polyfit", "vistaf_ftp_test_gauss",
-                "vistaf_ftp_test_chamfer", "vistaf_ftp_test_scratch_regions"]
+                "vistaf_ftp_test_chamfer", "vistaf_ftp_test_scratch_regions", "vistaf_ftp_test_cc_label", "vistaf_ftp_test_cc_largest",
+                "vistaf_ftp_test_chamfer_dispatch", "vistaf_ftp_test_blob_filter"]
 TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vistaf_tempseg_destroy", "vistaf_tempseg_segment",
                 "vistaf_temp_feature_planes", "vistaf_temp_color_support",
                 "vistaf_temp_clamp_map", "vistaf_temp_inpaint_map", "vistaf_temp_fuse_maps", "vistaf_temp_oriented_blur"]   # include/vistaf_temp.h
@@ -153,6 +154,10 @@ def load():
     lib.vistaf_ftp_test_polyfit.argtypes = [vp, vp, ci, ci, ctypes.c_float, ci, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.vistaf_ftp_test_gauss.argtypes = [vp, vp, cd, ci, ci, ci, vp]
     lib.vistaf_ftp_test_chamfer.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]
+    lib.vistaf_ftp_test_cc_label.argtypes = [vp, vp, ci, ci, ci, ci, vp]
+    lib.vistaf_ftp_test_cc_largest.argtypes = [vp, vp, vp, ci, ci, ci, vp]
+    lib.vistaf_ftp_test_chamfer_dispatch.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]
+    lib.vistaf_ftp_test_blob_filter.argtypes = [vp, vp, vp, vp, cd, cd, vp, ci, ci, vp]
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.vistaf_ftp_test_scratch_regions.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, ci, ctypes.c_char_p, szp, szp, szp, szp]
     lib.vistaf_tempseg_default_config.argtypes = [ctypes.POINTER(CTempSegConfig)]

@@ -998,6 +998,56 @@ int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *di
     return hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
 }
 
+// ---- the mask topology launchers (labelling, largest component, chamfer dispatch, blob filter) on caller-supplied device planes
+int vistaf_ftp_test_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, int variant, void *stream)
+{
+    if (!mask || !labels || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull) return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 1) return fail(VISTAF_E_INVALID, "variant must be 0 or 1");
+    const int tier = cc_label_tier(h, w, variant == 1);
+    launch_cc_label(mask, labels, B, h, w, (hipStream_t)stream, variant == 1);
+    const int rc = hook_finish(nullptr, nullptr, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+
+int vistaf_ftp_test_cc_largest(const int32_t *labels, const uint8_t *and_static, uint8_t *out, int B, int P, int variant, void *stream)
+{
+    if (!labels || !out || B < 1 || P < 1) return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    int32_t *area = nullptr;
+    unsigned long long *best = nullptr;
+    HIPCHK(hipMalloc((void **)&area, (size_t)B * P * sizeof(int32_t)));
+    if (hipMalloc((void **)&best, (size_t)B * sizeof(unsigned long long)) != hipSuccess) { (void)hipFree(area); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    const int tier = cc_largest_tier(B, P, true, variant);
+    launch_cc_largest(labels, area, best, and_static, out, B, P, (hipStream_t)stream, variant);
+    const int rc = hook_finish(area, best, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+
+int vistaf_ftp_test_chamfer_dispatch(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream)
+{
+    if (!mask || !dist_a || (pair && !dist_b) || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || cap_px < 0)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    const int tier = pair ? chamfer_pair_tier(B, h, w, cap_px) : chamfer_tier(h, w, cap_px);
+    const size_t n = (size_t)B * h * w;
+    int32_t *tmp_a = nullptr, *tmp_b = nullptr;
+    HIPCHK(hipMalloc((void **)&tmp_a, n * sizeof(int32_t)));
+    if (pair && hipMalloc((void **)&tmp_b, n * sizeof(int32_t)) != hipSuccess) { (void)hipFree(tmp_a); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, false);
+    else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, false);
+    const int rc = hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+
+int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const int32_t *labels, const float *gmax, double min_peak_mm, double rel_frac,
+                                uint8_t *kept, int B, int P, void *stream)
+{
+    if (!depth_inout || !cand || !labels || !gmax || !kept || B < 1 || P < 1) return fail(VISTAF_E_INVALID, "bad argument");
+    unsigned int *peak_bits = nullptr;
+    HIPCHK(hipMalloc((void **)&peak_bits, (size_t)B * P * sizeof(unsigned int)));
+    launch_blob_filter(depth_inout, cand, labels, peak_bits, (const unsigned int *)gmax, min_peak_mm, rel_frac, kept, B, P, (hipStream_t)stream);
+    return hook_finish(peak_bits, nullptr, (hipStream_t)stream);
+}
+
 int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
                                     size_t *total)
 {

@@ -120,20 +120,28 @@ __global__ __launch_bounds__(1024) void k_cc_label_lds(const uint8_t *__restrict
     for (int p = threadIdx.x; p < P; p += blockDim.x) out[p] = m[p] ? cc16_find(L16, p) : -1;
 }
 
-void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st)
+int cc_label_tier(int h, int w, bool force_global)
+{
+    const int P = h * w;
+    if (force_global || P > 65535) return CCT_GLOBAL;
+    if (cc_lds_bytes(P) <= 160 * 1024) return CCT_LDS_MASK;
+    return cc_lds_forest_bytes(P) <= 150 * 1024 ? CCT_LDS : CCT_GLOBAL;
+}
+
+void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st, bool force_global)
 {
     int P = h * w;
-    const size_t forest = cc_lds_forest_bytes(P);
-    if (P <= 65535 && cc_lds_bytes(P) <= 160 * 1024) {
+    const int tier = cc_label_tier(h, w, force_global);
+    if (tier == CCT_LDS_MASK) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<true>, 160 * 1024);
         hipLaunchKernelGGL(k_cc_label_lds<true>, dim3(B), dim3(1024), cc_lds_bytes(P), st, mask, labels, h, w);
         return;
     }
-    if (P <= 65535 && forest <= 150 * 1024) {
+    if (tier == CCT_LDS) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<false>, 160 * 1024);
-        hipLaunchKernelGGL(k_cc_label_lds<false>, dim3(B), dim3(1024), forest, st, mask, labels, h, w);
+        hipLaunchKernelGGL(k_cc_label_lds<false>, dim3(B), dim3(1024), cc_lds_forest_bytes(P), st, mask, labels, h, w);
         return;
     }
     const dim3 g((P + 255) / 256, B);
@@ -267,11 +275,17 @@ __global__ __launch_bounds__(256) void k_ccl_out(const int32_t *__restrict__ lab
     out[b * (size_t)P + p] = (uint8_t)(labels[b * (size_t)P + p] == broot && (and_static ? and_static[p] : (uint8_t)1));
 }
 
+int cc_largest_tier(int B, int P, bool have_best, int force)
+{
+    if (force) return force == CCL_BATCH && have_best ? CCL_BATCH : CCL_FRAME;
+    return have_best && big_frames(B, P) ? CCL_BATCH : CCL_FRAME;
+}
+
 // best: [B] scratch words (large frames only)
 void launch_cc_largest(const int32_t *labels, int32_t *area_scratch, unsigned long long *best, const uint8_t *and_static,
-                       uint8_t *out, int B, int P, hipStream_t st)
+                       uint8_t *out, int B, int P, hipStream_t st, int force)
 {
-    if (best && big_frames(B, P)) {
+    if (cc_largest_tier(B, P, best != nullptr, force) == CCL_BATCH) {
         (void)hipMemsetAsync(area_scratch, 0, (size_t)B * P * sizeof(int32_t), st);
         (void)hipMemsetAsync(best, 0, (size_t)B * sizeof(unsigned long long), st);
         hipLaunchKernelGGL(k_ccl_area, dim3((P + 1023) / 1024, B), dim3(256), 0, st, labels, area_scratch, P);
@@ -645,22 +659,44 @@ __global__ __launch_bounds__(1024) void k_chamfer_lds(const uint8_t *__restrict_
     }
 }
 
-void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *dist, int B, int h, int w, int cap_px, hipStream_t st, bool force_twopass)
+// rows either side of a pixel that the closed form looks at: every zero pixel within cap_px + 2 of it lies that close
+static int chamfer_cap_rows(int h, int cap_px)
+{
+    const int cap = (int)((cap_px + 2) / 0.955) + 2;
+    return cap > h ? h : cap;
+}
+int chamfer_tier(int h, int w, int cap_px, bool force_twopass)
 {
     // small caps (the erosion margins): a handful of rows per pixel on 16 waves; for wide bands the per-pixel loop costs more than
     // the one-wave two-pass kernel (measured at cap 46: 345 us against 200 us)
-    int cap = (int)((cap_px + 2) / 0.955) + 2;
-    if (cap > h) cap = h;
-    if (!force_twopass && cap <= 16 && (size_t)h * w * 2 <= 150 * 1024 && w <= 512) {
+    if (!force_twopass && chamfer_cap_rows(h, cap_px) <= 16 && (size_t)h * w * 2 <= 150 * 1024 && w <= 512) return CHT_LDS;
+    // beyond the two-pass kernel's 512 columns: closed form of the same two passes, exact up to cap_px (all that the callers look at)
+    return w <= 512 ? CHT_TWOPASS : CHT_ROWCOL;
+}
+int chamfer_pair_tier(int B, int h, int w, int cap_px, bool force_twopass)
+{
+    // wide bands on wide frames (native crops, band 200 px): the closed form walks up to 2 * cap rows per pixel (0.3 ms per frame, all CUs),
+    // the two-pass kernel a frame's rows once each way on one wave per frame and set (4 ms, all frames side by side): the latter from 16 frames on
+    const int cap = chamfer_cap_rows(h, cap_px);
+    const bool two_pass = (force_twopass || cap > 16 || (size_t)h * w * 2 > 150 * 1024) && (w <= 512 || (w <= 1280 && cap > 64 && (B >= 16 || force_twopass)));
+    return two_pass ? CHT_TWOPASS : chamfer_tier(h, w, cap_px, false);
+}
+
+void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *dist, int B, int h, int w, int cap_px, hipStream_t st, bool force_twopass)
+{
+    const int cap = chamfer_cap_rows(h, cap_px);
+    const int tier = chamfer_tier(h, w, cap_px, force_twopass);
+    if (tier == CHT_LDS) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_chamfer_lds, 160 * 1024);
         hipLaunchKernelGGL(k_chamfer_lds, dim3(B), dim3(1024), (size_t)h * w * 2, st, src, invert ? 1 : 0, dist, h, w, cap);
         return;
     }
-    (void)cap_px;
-    if (w <= 256) { hipLaunchKernelGGL(k_chamfer2<4>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w); return; }
-    if (w <= 512) { hipLaunchKernelGGL(k_chamfer2<8>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w); return; }
-    // wider frames: closed form of the same two passes, exact up to cap_px (all that the callers look at)
+    if (tier == CHT_TWOPASS) {
+        if (w <= 256) hipLaunchKernelGGL(k_chamfer2<4>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w);
+        else hipLaunchKernelGGL(k_chamfer2<8>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w);
+        return;
+    }
     int rows = B * h;
     hipLaunchKernelGGL(k_rowdist, dim3((rows + 3) / 4), dim3(256), 0, st, src, invert ? 1 : 0, rowdist, h, w, B);
     hipLaunchKernelGGL(k_chamfer_cols, dim3((w + 255) / 256, h, B), dim3(256), 0, st, rowdist, dist, h, w, cap);
@@ -672,12 +708,7 @@ void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *di
 void launch_chamfer_pair(const uint8_t *src, int32_t *tmp_a, float *dist_a, int32_t *tmp_b, float *dist_b, int B, int h, int w, int cap_px,
                          hipStream_t st, bool force_twopass)
 {
-    int cap = (int)((cap_px + 2) / 0.955) + 2;
-    if (cap > h) cap = h;
-    // wide bands on wide frames (native crops, band 200 px): the closed form walks up to 2 * cap rows per pixel (0.3 ms per frame, all CUs),
-    // the two-pass kernel a frame's rows once each way on one wave per frame and set (4 ms, all frames side by side): the latter from 16 frames on
-    const bool two_pass = (force_twopass || cap > 16 || (size_t)h * w * 2 > 150 * 1024) && (w <= 512 || (w <= 1280 && cap > 64 && (B >= 16 || force_twopass)));
-    if (!two_pass) {
+    if (chamfer_pair_tier(B, h, w, cap_px, force_twopass) != CHT_TWOPASS) {
         launch_chamfer(src, false, tmp_a, dist_a, B, h, w, cap_px, st, false);
         launch_chamfer(src, true, tmp_b, dist_b, B, h, w, cap_px, st, false);
         return;

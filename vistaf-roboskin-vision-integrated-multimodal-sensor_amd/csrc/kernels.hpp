@@ -132,9 +132,22 @@ void launch_build_full_tables(double2 *Exf, double2 *Eyf, int h, int w, int pad,
 
 // ---- k_cc_dist.hip ----------------------------------------------------------------------------
 void launch_threshold_mask(const float *q, const uint8_t *roi, const float *thr, uint8_t *out, int B, int P, hipStream_t st);
-void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st);
+// the kernels launch_cc_label starts for an h x w frame: the LDS forest with the mask staged behind it, the LDS forest reading the mask from
+// memory, or the union-find in global memory (init, merge, flatten); force_global: the last whatever the size (tests only)
+enum CcLabelTier { CCT_LDS_MASK = 0, CCT_LDS = 1, CCT_GLOBAL = 2 };
+int cc_label_tier(int h, int w, bool force_global = false);
+void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st, bool force_global = false);
+// the kernels launch_cc_largest starts: k_cc_largest (one workgroup per frame) or the three kernels over the whole batch (big_frames, and
+// `best` at hand).  force: 0 dispatch, else the tier itself (tests only; CCL_BATCH needs `best`)
+enum CcLargestTier { CCL_FRAME = 1, CCL_BATCH = 2 };
+int cc_largest_tier(int B, int P, bool have_best, int force = 0);
 void launch_cc_largest(const int32_t *labels, int32_t *area_scratch, unsigned long long *best, const uint8_t *and_static,
-                       uint8_t *out, int B, int P, hipStream_t st);
+                       uint8_t *out, int B, int P, hipStream_t st, int force = 0);
+// the kernels launch_chamfer / launch_chamfer_pair start: the closed form in LDS, the one-wave two-pass transform, or the closed form through
+// the row-distance plane in memory
+enum ChamferTier { CHT_LDS = 0, CHT_TWOPASS = 1, CHT_ROWCOL = 2 };
+int chamfer_tier(int h, int w, int cap_px, bool force_twopass = false);
+int chamfer_pair_tier(int B, int h, int w, int cap_px, bool force_twopass = false);
 void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *dist, int B, int h, int w, int cap_px, hipStream_t st,
                     bool force_twopass = false);
 void launch_chamfer_pair(const uint8_t *src, int32_t *tmp_a, float *dist_a, int32_t *tmp_b, float *dist_b, int B, int h, int w, int cap_px,

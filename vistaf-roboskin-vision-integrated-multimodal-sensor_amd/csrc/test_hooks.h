@@ -82,6 +82,37 @@ int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int
  * Planes are [B, h, w]; the integer temporaries are allocated and freed by the call. */
 int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream);
 
+/* The mask topology launchers (k_cc_dist.hip, k_post.hip) on device planes of the caller.  Every call refuses a NULL plane (and_static apart), a
+ * size below 1 and an unknown variant with VISTAF_E_INVALID before anything is allocated or launched, runs on `stream`, waits for it, and
+ * returns the tier it launched (the value of the pure function the launcher itself dispatches on) or a negative VISTAF_E_* code.
+ *
+ * launch_cc_label: labels[b][p] = the smallest pixel index of the 8-connected component of pixel p of mask[b] (mask != 0), -1 off the mask.
+ * variant: 0 dispatch as a session does, 1 the global union-find kernels (k_cc_init, k_cc_merge, k_cc_flatten) whatever the size.
+ * Returns CcLabelTier of kernels.hpp: 0 the LDS forest with the mask staged in LDS (up to 54606 pixels), 1 the LDS forest alone (up to
+ * 65535 pixels), 2 the global kernels. */
+int vistaf_ftp_test_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, int variant, void *stream);
+
+/* launch_cc_largest on a label plane as above: out[b][p] = (labels[b][p] == root of the largest component of frame b) && and_static[p];
+ * ties go to the smallest root, a frame without a component gives zeros.  and_static: one [P] plane for the batch, or NULL (all ones).
+ * variant: 0 dispatch (the three kernels over the whole batch when big_frames(B, P)), 1 k_cc_largest (one workgroup per frame), 2 the batch
+ * kernels, whatever the size.  Returns CcLargestTier: 1 k_cc_largest, 2 the batch kernels.  The area and key scratch is the call's own. */
+int vistaf_ftp_test_cc_largest(const int32_t *labels, const uint8_t *and_static, uint8_t *out, int B, int P, int variant, void *stream);
+
+/* launch_chamfer (pair == 0: dist_a = distance to the zero pixels, or with invert != 0 to the non-zero pixels) or launch_chamfer_pair
+ * (pair != 0: dist_a to the zero, dist_b to the non-zero pixels) as a session calls them: nothing forced.  Returns ChamferTier: 0
+ * k_chamfer_lds, 1 k_chamfer2, 2 k_rowdist + k_chamfer_cols.  Tiers 0 and 2 are the closed form over a band of rows: equal to the two-pass
+ * transform wherever that one is at most cap_px + 2, and beyond cap_px + 2 (and no smaller than it) everywhere else. */
+int vistaf_ftp_test_chamfer_dispatch(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px,
+                                     void *stream);
+
+/* launch_blob_filter, the separate kernels (k_blob_peaks, k_blob_apply): kept[b][p] = cand[b][p] && peak of p's component >= threshold of
+ * frame b, and depth_inout is zeroed at the candidates that are not kept.  labels: as vistaf_ftp_test_cc_label writes them for the plane
+ * `cand` (every candidate pixel must carry a root: the kernel indexes the peak plane with it).  gmax: [B] float32, the frame maxima whose
+ * bits k_to_mm leaves.  The threshold is float32(max(min_peak_mm, rel_frac * gmax[b])) formed in float64, min_peak_mm alone for
+ * rel_frac < 0.  Returns 0. */
+int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const int32_t *labels, const float *gmax, double min_peak_mm, double rel_frac,
+                                uint8_t *kept, int B, int P, void *stream);
+
 /* The scratch layout of one stage, from a counting pass of the function its launcher carves with (ScratchLayout, host_util.hpp).  Makes no HIP
  * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored).
  * Region i, in carve order: names + 32 * i (NUL-terminated), offset[i], bytes[i], align[i]; *total = the size the stage's *_scratch_bytes
