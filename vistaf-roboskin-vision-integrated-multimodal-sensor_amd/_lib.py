@@ -36,6 +36,12 @@ NTHERMAL, NTHERMALFRAME = 16, 8                                      # VISTAF_NT
 THERMAL_NAMES = ["contact_pixels", "valid_pixels", "coverage", "mean_C", "weighted_mean_C", "min_C", "max_C", "std_C", "peak_temp_C",
                  "surround_pixels", "surround_mean_C", "contrast_C"]
 THERMAL_FRAME_NAMES = ["registered_pixels", "skin_mean_C", "contact_pixels", "contact_mean_C", "contrast_C", "hottest_contact", "coldest_contact"]
+NTEMPORAL = 16          # doubles per frame row of the temporal read-out (VISTAF_NTEMPORAL, include/vistaf_temporal.h)
+# fields of a frame row in the order of the VISTAF_TEMPORAL_* indices
+TEMPORAL_NAMES = ["touch_pixels", "onset_pixels", "release_pixels", "loading_pixels", "unloading_pixels", "filtered_volume_cm3", "dvolume_cm3_per_s",
+                  "max_filtered_mm", "argmax_index", "max_rate_mm_per_s", "max_rate_index", "min_rate_mm_per_s", "min_rate_index",
+                  "longest_dwell_frames", "events", "gap_frames"]
+TEMPORAL_EVENTS = {"touch_began": 1, "touch_ended": 2}                # VISTAF_TEMPEV_*, bits of the `events` field
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -66,6 +72,8 @@ TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_res
 SHAPE_EXPORTS = ["vistaf_shape_create", "vistaf_shape_measure", "vistaf_shape_destroy"]   # include/vistaf_shape.h
 TAXEL_EXPORTS = ["vistaf_taxel_create", "vistaf_taxel_measure", "vistaf_taxel_layout_info", "vistaf_taxel_destroy"]   # include/vistaf_taxel.h
 THERMAL_EXPORTS = ["vistaf_thermal_create", "vistaf_thermal_register", "vistaf_thermal_measure", "vistaf_thermal_destroy"]   # include/vistaf_thermal.h
+TEMPORAL_EXPORTS = ["vistaf_temporal_create", "vistaf_temporal_update", "vistaf_temporal_state", "vistaf_temporal_reset",
+                    "vistaf_temporal_destroy"]   # include/vistaf_temporal.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -206,8 +214,14 @@ def load():
     lib.vistaf_thermal_measure.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
     lib.vistaf_thermal_destroy.argtypes = [vp]
     lib.vistaf_thermal_destroy.restype = None
+    lib.vistaf_temporal_create.argtypes = [ci, ci, ci, cd, cd, cd, cd, ctypes.POINTER(vp)]
+    lib.vistaf_temporal_update.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp]
+    lib.vistaf_temporal_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.vistaf_temporal_reset.argtypes = [vp]
+    lib.vistaf_temporal_destroy.argtypes = [vp]
+    lib.vistaf_temporal_destroy.restype = None
     for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
-               THERMAL_EXPORTS):
+               THERMAL_EXPORTS + TEMPORAL_EXPORTS):
         getattr(lib, fn)
     _lib = lib
     return lib

@@ -213,6 +213,9 @@ class FtpSensor:
         if getattr(self, "_thermal", None) is not None:
             self._thermal.close()
             self._thermal = None
+        if getattr(self, "_temporal", None) is not None:
+            self._temporal.close()
+            self._temporal = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -389,6 +392,31 @@ class FtpSensor:
         out["thermal"], out["thermal_frame"] = r["thermal"], r["frame"]
         return out
 
+    def temporal(self, alpha: float = 0.5, on_mm: float = 0.05, off_mm: float = 0.02, frame_period_s: float = 1.0 / 30.0, reset: bool = False,
+                 planes: bool = False) -> Dict[str, torch.Tensor]:
+        """Temporal read-out of the last predict (temporal.TemporalReadout; an extension, the reference has no counterpart): every pixel's
+        filtered depth, rate, touch bit, dwell and peak hold, carried from call to call.  Hands the predict's height map, the frames'
+        mm_per_px (the `scalars` column) and their status to the session's read-out, created on first use: the frames of this predict follow
+        the frames of the predict of the previous `temporal` call.  Returns device tensors: frames [B,16] f64 (fields TEMPORAL_NAMES) and,
+        with planes=True, filtered [B,h,w] f32 and touch [B,h,w] u8.  reset=True forgets the stream; alpha, on_mm, off_mm and
+        frame_period_s can only change together with it."""
+        from .temporal import TemporalReadout
+        last = getattr(self, "_last_out", None)
+        if last is None:
+            raise RuntimeError("temporal() needs a previous predict_batch / predict_pairs")
+        prm = (float(alpha), float(on_mm), float(off_mm), float(frame_period_s))
+        tp = getattr(self, "_temporal", None)
+        if tp is not None and (tp.alpha, tp.on_mm, tp.off_mm, tp.frame_period_s) != prm:
+            if not reset:
+                raise ValueError("alpha / on_mm / off_mm / frame_period_s differ from the running read-out's: pass reset=True to start over with them")
+            tp.close()
+            tp = self._temporal = None
+        if tp is None:
+            tp = self._temporal = TemporalReadout(self.h, self.w, self.max_batch, *prm, device=self.device)
+        elif reset:
+            tp.reset()
+        return tp.update(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], status=last["status"], planes=planes)
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -440,7 +468,8 @@ class FtpSensor:
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
-    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None) -> Optional[Dict[str, Any]]:
+    def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
+                temporal: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -450,7 +479,10 @@ class FtpSensor:
         taxels=layout adds "taxels", the ndarray [T,12] of `FtpSensor.taxels` (fields TAXEL_NAMES), and "taxel_frame", a dict of
         TAXEL_FRAME_NAMES (active_taxels and peak_taxel as ints, peak_taxel -1 without contact).
         thermal=temperature_crop (with contacts=K; [h,w] f32 from `ThermalReadout.register`) adds "thermal", one dict of THERMAL_NAMES per
-        entry of "contacts", and "thermal_frame", a dict of THERMAL_FRAME_NAMES (`FtpSensor.thermal`)."""
+        entry of "contacts", and "thermal_frame", a dict of THERMAL_FRAME_NAMES (`FtpSensor.thermal`).
+        temporal=dict(...) (the keyword arguments of `FtpSensor.temporal` but `planes`) adds "temporal_frame", a dict of TEMPORAL_NAMES:
+        this frame follows the frame of the previous predict that asked for it.  A frame for which None is returned or an error raised
+        does not reach the read-out."""
         if shapes and contacts is None:
             raise ValueError("shapes=True needs contacts=K")
         if thermal is not None and contacts is None:
@@ -503,6 +535,9 @@ class FtpSensor:
             t = self.taxels(taxels)
             res["taxels"] = t["taxels"][0].cpu().numpy()
             res["taxel_frame"] = taxel_frame_record(t["frame"][0].cpu().numpy())
+        if temporal is not None:
+            from .writers import temporal_frame_record
+            res["temporal_frame"] = temporal_frame_record(self.temporal(**dict(temporal, planes=False))["frames"][0].cpu().numpy())
         return res
 
 

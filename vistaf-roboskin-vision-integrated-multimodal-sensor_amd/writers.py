@@ -22,6 +22,9 @@
 * `thermal_table` / `write_thermal_csv` / `thermal_frame_record` -- the thermal read-out (`FtpSensor.thermal`, `thermal.ThermalReadout`) as row
   dicts, as `thermal.csv`, and the frame row as a dict; an extension as the contacts table.
 
+* `temporal_table` / `write_temporal_csv` / `temporal_frame_record` -- the frame rows of the temporal read-out (`FtpSensor.temporal`,
+  `temporal.TemporalReadout`) as row dicts, as `temporal.csv`, and one row as a dict; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -67,6 +70,12 @@ THERMAL_INT_FIELDS = ("contact_pixels", "valid_pixels", "surround_pixels")
 THERMAL_CSV_FIELDS = ("frame", "contact") + THERMAL_FIELDS
 THERMAL_FRAME_FIELDS = ("registered_pixels", "skin_mean_C", "contact_pixels", "contact_mean_C", "contrast_C", "hottest_contact",
                         "coldest_contact")                                                # VISTAF_THERMALFRAME_*
+TEMPORAL_FIELDS = ("touch_pixels", "onset_pixels", "release_pixels", "loading_pixels", "unloading_pixels", "filtered_volume_cm3", "dvolume_cm3_per_s",
+                   "max_filtered_mm", "argmax_index", "max_rate_mm_per_s", "max_rate_index", "min_rate_mm_per_s", "min_rate_index",
+                   "longest_dwell_frames", "events", "gap_frames")                          # VISTAF_TEMPORAL_* order (include/vistaf_temporal.h)
+TEMPORAL_INT_FIELDS = ("touch_pixels", "onset_pixels", "release_pixels", "loading_pixels", "unloading_pixels", "argmax_index", "max_rate_index",
+                       "min_rate_index", "longest_dwell_frames", "events", "gap_frames")   # -1 for NaN: no touching pixel, or a skipped frame
+TEMPORAL_CSV_FIELDS = ("frame", "skipped") + TEMPORAL_FIELDS
 THERMAL_FRAME_INT_FIELDS = ("registered_pixels", "contact_pixels", "hottest_contact", "coldest_contact")   # -1 for NaN: no contact has a mean
 
 
@@ -330,6 +339,43 @@ def thermal_frame_record(frame_row) -> Dict[str, Any]:
     if f.ndim != 1 or f.shape[0] < len(THERMAL_FRAME_FIELDS):
         raise ValueError("the frame row must be [>=7]")
     return {name: (_int_or_minus_one(f[i]) if name in THERMAL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(THERMAL_FRAME_FIELDS)}
+
+
+def temporal_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=16] of the temporal read-out as a dict of TEMPORAL_FIELDS; counts, indices, dwell, events and gap as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(TEMPORAL_FIELDS):
+        raise ValueError("the frame row must be [>=16]")
+    return {name: (_int_or_minus_one(f[i]) if name in TEMPORAL_INT_FIELDS else float(f[i])) for i, name in enumerate(TEMPORAL_FIELDS)}
+
+
+def temporal_table(frames) -> list:
+    """Row dicts of the temporal read-out: frames [B,>=16] (or [>=16] for one frame) float64 as `FtpSensor.temporal` returns it.  One dict per
+    frame, skipped frames included: `frame`, `skipped` (1 for a frame whose status was not 0: its row is NaN but for gap_frames) and
+    TEMPORAL_FIELDS as `temporal_frame_record` gives them."""
+    t = np.asarray(frames, dtype=np.float64)
+    if t.ndim == 1:
+        t = t[None]
+    if t.ndim != 2 or t.shape[1] < len(TEMPORAL_FIELDS):
+        raise ValueError("frames must be [B,>=16]")
+    rows = []
+    for b in range(t.shape[0]):
+        row: Dict[str, Any] = {"frame": b, "skipped": int(np.isnan(t[b, 0]))}
+        row.update(temporal_frame_record(t[b]))
+        rows.append(row)
+    return rows
+
+
+def write_temporal_csv(output_dir: str, frames, filename: str = "temporal.csv") -> str:
+    """temporal.csv: one line per frame, columns TEMPORAL_CSV_FIELDS, floats with repr()."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(TEMPORAL_CSV_FIELDS))
+        w.writeheader()
+        for row in temporal_table(frames):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
