@@ -42,6 +42,13 @@ TEMPORAL_NAMES = ["touch_pixels", "onset_pixels", "release_pixels", "loading_pix
                   "max_filtered_mm", "argmax_index", "max_rate_mm_per_s", "max_rate_index", "min_rate_mm_per_s", "min_rate_index",
                   "longest_dwell_frames", "events", "gap_frames"]
 TEMPORAL_EVENTS = {"touch_began": 1, "touch_ended": 2}                # VISTAF_TEMPEV_*, bits of the `events` field
+NCLOUD_POINT, NCLOUD_FRAME = 8, 12                                   # VISTAF_NCLOUD_POINT, VISTAF_NCLOUD_FRAME (include/vistaf_cloud.h)
+# fields of a point record in the order of the VISTAF_CLOUD_* indices, and of a frame row (VISTAF_CLOUDFRAME_*; 11 is reserved)
+CLOUD_POINT_NAMES = ["x", "y", "z", "nx", "ny", "nz", "curvature", "gaussian_curvature"]
+CLOUD_FRAME_NAMES = ["surface_pixels", "points", "points_written", "projected_area_mm2", "surface_area_mm2", "mean_normal_x", "mean_normal_y",
+                     "mean_normal_z", "tilt_deg", "max_slope_deg", "max_slope_index"]
+# launch geometry of the point-cloud kernels (VISTAF_CLOUD_CHUNK_THREADS, _SCAN_THREADS, _ROW_LANES, _ROW_UNROLL): fixes the order of the frame sums
+CLOUD_CHUNK_THREADS, CLOUD_SCAN_THREADS, CLOUD_ROW_LANES, CLOUD_ROW_UNROLL = 256, 1024, 64, 4
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -74,6 +81,7 @@ TAXEL_EXPORTS = ["vistaf_taxel_create", "vistaf_taxel_measure", "vistaf_taxel_la
 THERMAL_EXPORTS = ["vistaf_thermal_create", "vistaf_thermal_register", "vistaf_thermal_measure", "vistaf_thermal_destroy"]   # include/vistaf_thermal.h
 TEMPORAL_EXPORTS = ["vistaf_temporal_create", "vistaf_temporal_update", "vistaf_temporal_state", "vistaf_temporal_reset",
                     "vistaf_temporal_destroy"]   # include/vistaf_temporal.h
+CLOUD_EXPORTS = ["vistaf_cloud_create", "vistaf_cloud_measure", "vistaf_cloud_destroy"]   # include/vistaf_cloud.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -220,8 +228,12 @@ def load():
     lib.vistaf_temporal_reset.argtypes = [vp]
     lib.vistaf_temporal_destroy.argtypes = [vp]
     lib.vistaf_temporal_destroy.restype = None
+    lib.vistaf_cloud_create.argtypes = [ci, ci, ci, ctypes.c_int64, ci, cd, cd, ctypes.POINTER(vp)]
+    lib.vistaf_cloud_measure.argtypes = [vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp, vp, vp, vp]
+    lib.vistaf_cloud_destroy.argtypes = [vp]
+    lib.vistaf_cloud_destroy.restype = None
     for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
-               THERMAL_EXPORTS + TEMPORAL_EXPORTS):
+               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS):
         getattr(lib, fn)
     _lib = lib
     return lib

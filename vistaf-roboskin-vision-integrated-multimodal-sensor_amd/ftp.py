@@ -216,6 +216,9 @@ class FtpSensor:
         if getattr(self, "_temporal", None) is not None:
             self._temporal.close()
             self._temporal = None
+        if getattr(self, "_cloud", None) is not None:
+            self._cloud.close()
+            self._cloud = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -417,6 +420,35 @@ class FtpSensor:
             tp.reset()
         return tp.update(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], status=last["status"], planes=planes)
 
+    def cloud(self, max_points: Optional[int] = None, stride: int = 1, labels: bool = False, max_contacts: int = 8) -> Dict[str, torch.Tensor]:
+        """Point-cloud read-out of the last predict (cloud.CloudReadout; an extension, the reference has no counterpart): the surface pixels
+        (depth > the session's depth_eps_mm) of every frame, every stride-th column and row, as points in millimetres about the crop centre
+        with a unit normal, mean and Gaussian curvature each.  Hands the predict's height map, the frames' mm_per_px (the `scalars` column)
+        and their status to the session's read-out, created on first use and rebuilt when max_points or stride change; labels=True also
+        hands over the index plane of `contacts(max_contacts, index_plane=True)`.  Returns device tensors: points [max_points,8] f32 (fields
+        CLOUD_POINT_NAMES), pixel [max_points] i32, label [max_points] i8 (with labels=True), offsets [B+1] i64, frame [B,12] f64 (fields
+        CLOUD_FRAME_NAMES); `CloudReadout.trim` cuts the written part.  The default max_points is the lattice pixels of one frame or one
+        eighth of those of max_batch frames, whichever is larger -- a sizing choice (a contact covers a small part of the crop), not a
+        measurement.  More points than max_points is reported (offsets beyond max_points, points_written below points, `trim`'s overflow),
+        not raised."""
+        from .cloud import CloudReadout
+        last = getattr(self, "_last_out", None)
+        if last is None:
+            raise RuntimeError("cloud() needs a previous predict_batch / predict_pairs")
+        stride = int(stride)
+        if max_points is None:
+            lattice = ((self.h + stride - 1) // stride) * ((self.w + stride - 1) // stride) if stride >= 1 else 1
+            max_points = max(lattice, (lattice * self.max_batch + 7) // 8)
+        cl = getattr(self, "_cloud", None)
+        if cl is not None and (cl.max_points, cl.stride) != (int(max_points), stride):
+            cl.close()
+            cl = self._cloud = None
+        if cl is None:
+            cl = self._cloud = CloudReadout(self.h, self.w, self.max_batch, int(max_points), stride, device=self.device)
+        index = self.contacts(int(max_contacts), index_plane=True)["contact_index"] if labels else None
+        return cl.measure(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
+                          status=last["status"], contact_index=index)
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -469,7 +501,7 @@ class FtpSensor:
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
-                temporal: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -482,7 +514,10 @@ class FtpSensor:
         entry of "contacts", and "thermal_frame", a dict of THERMAL_FRAME_NAMES (`FtpSensor.thermal`).
         temporal=dict(...) (the keyword arguments of `FtpSensor.temporal` but `planes`) adds "temporal_frame", a dict of TEMPORAL_NAMES:
         this frame follows the frame of the previous predict that asked for it.  A frame for which None is returned or an error raised
-        does not reach the read-out."""
+        does not reach the read-out.
+        cloud=dict(...) (the keyword arguments of `FtpSensor.cloud`, possibly none) adds "cloud", the ndarray [N,8] of the frame's written
+        points (fields CLOUD_POINT_NAMES), "cloud_pixel", their pixel indices [N], "cloud_label" [N] with labels=True, and "cloud_frame", a
+        dict of CLOUD_FRAME_NAMES."""
         if shapes and contacts is None:
             raise ValueError("shapes=True needs contacts=K")
         if thermal is not None and contacts is None:
@@ -538,6 +573,15 @@ class FtpSensor:
         if temporal is not None:
             from .writers import temporal_frame_record
             res["temporal_frame"] = temporal_frame_record(self.temporal(**dict(temporal, planes=False))["frames"][0].cpu().numpy())
+        if cloud is not None:
+            from .writers import cloud_frame_record
+            raw = self.cloud(**cloud)
+            c = self._cloud.trim(raw)
+            res["cloud"] = c["points"].cpu().numpy()
+            res["cloud_pixel"] = c["pixel"].cpu().numpy()
+            if "label" in c:
+                res["cloud_label"] = c["label"].cpu().numpy()
+            res["cloud_frame"] = cloud_frame_record(c["frame"][0].cpu().numpy())
         return res
 
 

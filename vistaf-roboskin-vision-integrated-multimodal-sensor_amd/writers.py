@@ -25,6 +25,9 @@
 * `temporal_table` / `write_temporal_csv` / `temporal_frame_record` -- the frame rows of the temporal read-out (`FtpSensor.temporal`,
   `temporal.TemporalReadout`) as row dicts, as `temporal.csv`, and one row as a dict; an extension as the contacts table.
 
+* `cloud_frame_record` / `write_cloud_ply` -- the frame row of the point-cloud read-out (`FtpSensor.cloud`, `cloud.CloudReadout`) as a dict, and
+  its points as a binary little-endian PLY file; an extension as the contacts table.
+
 * `contacts_table` / `write_contacts_csv` / `contacts_record` -- the per-contact table of `FtpSensor.contacts` as row dicts, as
   `contacts.csv`, and as a `{"contact_count", "contacts"}` block for a JSON of the caller's own.  An extension with no reference schema:
   it is never merged into result.json / result.csv / multimodal_summary.json, which keep the reference's keys.
@@ -76,6 +79,10 @@ TEMPORAL_FIELDS = ("touch_pixels", "onset_pixels", "release_pixels", "loading_pi
 TEMPORAL_INT_FIELDS = ("touch_pixels", "onset_pixels", "release_pixels", "loading_pixels", "unloading_pixels", "argmax_index", "max_rate_index",
                        "min_rate_index", "longest_dwell_frames", "events", "gap_frames")   # -1 for NaN: no touching pixel, or a skipped frame
 TEMPORAL_CSV_FIELDS = ("frame", "skipped") + TEMPORAL_FIELDS
+CLOUD_POINT_FIELDS = ("x", "y", "z", "nx", "ny", "nz", "curvature", "gaussian_curvature")   # VISTAF_CLOUD_* order (include/vistaf_cloud.h); the PLY properties
+CLOUD_FRAME_FIELDS = ("surface_pixels", "points", "points_written", "projected_area_mm2", "surface_area_mm2", "mean_normal_x", "mean_normal_y",
+                      "mean_normal_z", "tilt_deg", "max_slope_deg", "max_slope_index")      # VISTAF_CLOUDFRAME_* order; field 11 is reserved
+CLOUD_FRAME_INT_FIELDS = ("surface_pixels", "points", "points_written", "max_slope_index")   # -1 for NaN: no surface pixel, or a skipped frame
 THERMAL_FRAME_INT_FIELDS = ("registered_pixels", "contact_pixels", "hottest_contact", "coldest_contact")   # -1 for NaN: no contact has a mean
 
 
@@ -375,6 +382,45 @@ def write_temporal_csv(output_dir: str, frames, filename: str = "temporal.csv") 
         w.writeheader()
         for row in temporal_table(frames):
             w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def cloud_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=11] of the point-cloud read-out as a dict of CLOUD_FRAME_FIELDS; the counts and the index as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(CLOUD_FRAME_FIELDS):
+        raise ValueError("the frame row must be [>=11]")
+    return {name: (_int_or_minus_one(f[i]) if name in CLOUD_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(CLOUD_FRAME_FIELDS)}
+
+
+def write_cloud_ply(path: str, points, label=None) -> str:
+    """points [N,8] float32 (the written part of the point-cloud read-out: `CloudReadout.trim`) as a binary little-endian PLY file: one vertex
+    per point with the float properties CLOUD_POINT_FIELDS (x y z nx ny nz curvature gaussian_curvature) and, when label [N] is given, a
+    char property `label` (the row of the point's contact, -1 for none).  Millimetres, the frame of include/vistaf_cloud.h."""
+    pts = np.asarray(points)
+    if pts.ndim != 2 or pts.shape[1] != len(CLOUD_POINT_FIELDS):
+        raise ValueError("points must be [N,8]")
+    fields = [(name, "<f4") for name in CLOUD_POINT_FIELDS]
+    if label is not None:
+        lab = np.asarray(label)
+        if lab.shape != (pts.shape[0],):
+            raise ValueError("label must be [N] for the N points")
+        fields.append(("label", "i1"))
+    body = np.empty(pts.shape[0], dtype=np.dtype(fields))
+    for i, name in enumerate(CLOUD_POINT_FIELDS):
+        body[name] = pts[:, i]
+    if label is not None:
+        body["label"] = lab
+    header = ["ply", "format binary_little_endian 1.0", "comment millimetres; x right, y down, z away from the camera",
+              "element vertex %d" % pts.shape[0]]
+    header += ["property float %s" % name for name in CLOUD_POINT_FIELDS]
+    if label is not None:
+        header.append("property char label")
+    header.append("end_header")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(body.tobytes())
     return path
 
 
