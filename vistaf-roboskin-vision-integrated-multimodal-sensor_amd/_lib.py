@@ -49,6 +49,12 @@ CLOUD_FRAME_NAMES = ["surface_pixels", "points", "points_written", "projected_ar
                      "mean_normal_z", "tilt_deg", "max_slope_deg", "max_slope_index"]
 # launch geometry of the point-cloud kernels (VISTAF_CLOUD_CHUNK_THREADS, _SCAN_THREADS, _ROW_LANES, _ROW_UNROLL): fixes the order of the frame sums
 CLOUD_CHUNK_THREADS, CLOUD_SCAN_THREADS, CLOUD_ROW_LANES, CLOUD_ROW_UNROLL = 256, 1024, 64, 4
+NMOTION, NMOTIONFRAME = 24, 8                                       # VISTAF_NMOTION, VISTAF_NMOTIONFRAME (include/vistaf_motion.h)
+# fields of a motion row in the order of the VISTAF_MOTION_* indices (20..23 are reserved), and of a frame row (VISTAF_MOTIONFRAME_*)
+MOTION_NAMES = ["parent_row", "template_pixels", "status", "iterations", "tx_px", "ty_px", "theta_rad", "beta_mm", "tx_mm", "ty_mm", "centre_x",
+                "centre_y", "rms_before_mm", "rms_after_mm", "last_step_px", "se_tx_px", "se_ty_px", "se_theta_rad", "tx_minus_dx", "ty_minus_dy"]
+MOTION_FRAME_NAMES = ["registered", "max_slide_mm", "max_slide_row", "max_twist_rad", "max_twist_row", "mean_tx_mm", "mean_ty_mm", "mean_rms_after_mm"]
+MOTION_STATUS = {"ok": 0, "not_converged": 1, "no_parent": 2, "too_few": 3, "singular": 4}   # VISTAF_MOTIONST_*, values of the `status` field
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -82,6 +88,7 @@ THERMAL_EXPORTS = ["vistaf_thermal_create", "vistaf_thermal_register", "vistaf_t
 TEMPORAL_EXPORTS = ["vistaf_temporal_create", "vistaf_temporal_update", "vistaf_temporal_state", "vistaf_temporal_reset",
                     "vistaf_temporal_destroy"]   # include/vistaf_temporal.h
 CLOUD_EXPORTS = ["vistaf_cloud_create", "vistaf_cloud_measure", "vistaf_cloud_destroy"]   # include/vistaf_cloud.h
+MOTION_EXPORTS = ["vistaf_motion_create", "vistaf_motion_update", "vistaf_motion_reset", "vistaf_motion_destroy"]   # include/vistaf_motion.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -232,8 +239,13 @@ def load():
     lib.vistaf_cloud_measure.argtypes = [vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp, vp, vp, vp]
     lib.vistaf_cloud_destroy.argtypes = [vp]
     lib.vistaf_cloud_destroy.restype = None
+    lib.vistaf_motion_create.argtypes = [ci, ci, ci, ci, ci, cd, ci, ci, ctypes.POINTER(vp)]
+    lib.vistaf_motion_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
+    lib.vistaf_motion_reset.argtypes = [vp]
+    lib.vistaf_motion_destroy.argtypes = [vp]
+    lib.vistaf_motion_destroy.restype = None
     for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
-               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS):
+               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS + MOTION_EXPORTS):
         getattr(lib, fn)
     _lib = lib
     return lib

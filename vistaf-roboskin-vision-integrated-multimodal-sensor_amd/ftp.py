@@ -219,6 +219,9 @@ class FtpSensor:
         if getattr(self, "_cloud", None) is not None:
             self._cloud.close()
             self._cloud = None
+        if getattr(self, "_motion", None) is not None:
+            self._motion.close()
+            self._motion = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -449,6 +452,34 @@ class FtpSensor:
         return cl.measure(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
                           status=last["status"], contact_index=index)
 
+    def motion(self, max_contacts: int = 8, gate_px: float = 0.0, reset: bool = False, iterations: int = 8, tol_px: float = 1e-3,
+               min_pixels: int = 16, init_from_centroid: bool = True) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict, its link to the frames before it and the motion of every linked contact against the skin
+        (motion.ContactMotion; an extension, the reference has no counterpart).  Calls `track(max_contacts, gate_px, reset)` -- the tracker
+        it needs -- and hands its result, the predict's height map, the frames' mm_per_px (the `scalars` column) and the session's
+        depth_eps_mm to the session's motion read-out, created on first use: the frames of this predict follow the frames of the predict
+        of the previous `motion` call, so `track` must not be called in between.  Returns the dict of `track` plus motion [B,K,24] f64
+        (fields MOTION_NAMES: slide tx / ty, twist theta, depth change beta, residuals, standard errors) and motion_frame [B,8] f64 (fields
+        MOTION_FRAME_NAMES).  reset=True forgets the frames seen so far; the other arguments can only change together with it."""
+        from .motion import ContactMotion
+        k = int(max_contacts)
+        par = (k, int(iterations), float(tol_px), int(min_pixels), bool(init_from_centroid))
+        mo = getattr(self, "_motion", None)
+        if mo is not None and (mo.max_contacts, mo.iterations, mo.tol_px, mo.min_pixels, mo.init_from_centroid) != par:
+            if not reset:
+                raise ValueError("the arguments differ from the running motion read-out's: pass reset=True to start over with them")
+            mo.close()
+            mo = self._motion = None
+        out = self.track(k, gate_px, reset)
+        if mo is None:
+            mo = self._motion = ContactMotion(self.h, self.w, self.max_batch, *par, device=self.device)
+        elif reset:
+            mo.reset()
+        last = self._last_out
+        out.update(mo.update(last["height_map_mm"], out["contact_index"], out["contacts"], out["count"], out["tracks"],
+                             last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm))
+        return out
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -501,7 +532,8 @@ class FtpSensor:
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
-                temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
+                motion: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -517,7 +549,12 @@ class FtpSensor:
         does not reach the read-out.
         cloud=dict(...) (the keyword arguments of `FtpSensor.cloud`, possibly none) adds "cloud", the ndarray [N,8] of the frame's written
         points (fields CLOUD_POINT_NAMES), "cloud_pixel", their pixel indices [N], "cloud_label" [N] with labels=True, and "cloud_frame", a
-        dict of CLOUD_FRAME_NAMES."""
+        dict of CLOUD_FRAME_NAMES.
+        motion=dict(...) (with contacts=K; the keyword arguments of `FtpSensor.motion` but `max_contacts`, possibly none) adds "tracks", one
+        dict of TRACK_NAMES per entry of "contacts", "motion", one dict of MOTION_NAMES per entry, and "motion_frame", a dict of
+        MOTION_FRAME_NAMES: this frame follows the frame of the previous predict that asked for it."""
+        if motion is not None and contacts is None:
+            raise ValueError("motion=dict(...) needs contacts=K")
         if shapes and contacts is None:
             raise ValueError("shapes=True needs contacts=K")
         if thermal is not None and contacts is None:
@@ -565,6 +602,15 @@ class FtpSensor:
                 for r in res["thermal"]:
                     r.pop("frame")
                 res["thermal_frame"] = thermal_frame_record(t["thermal_frame"][0].cpu().numpy())
+            if motion is not None:
+                from .writers import motion_frame_record, motion_table, tracks_table
+                mo = self.motion(**dict(motion, max_contacts=int(contacts)))
+                tab, cnt = mo["contacts"].cpu().numpy(), mo["count"].cpu().numpy()
+                res["tracks"] = tracks_table(mo["tracks"].cpu().numpy(), tab, cnt)
+                res["motion"] = motion_table(mo["motion"].cpu().numpy(), tab, cnt)
+                for r in res["tracks"] + res["motion"]:
+                    r.pop("frame")
+                res["motion_frame"] = motion_frame_record(mo["motion_frame"][0].cpu().numpy())
         if taxels is not None:
             from .writers import taxel_frame_record
             t = self.taxels(taxels)

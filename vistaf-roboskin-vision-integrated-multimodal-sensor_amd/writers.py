@@ -83,6 +83,14 @@ CLOUD_POINT_FIELDS = ("x", "y", "z", "nx", "ny", "nz", "curvature", "gaussian_cu
 CLOUD_FRAME_FIELDS = ("surface_pixels", "points", "points_written", "projected_area_mm2", "surface_area_mm2", "mean_normal_x", "mean_normal_y",
                       "mean_normal_z", "tilt_deg", "max_slope_deg", "max_slope_index")      # VISTAF_CLOUDFRAME_* order; field 11 is reserved
 CLOUD_FRAME_INT_FIELDS = ("surface_pixels", "points", "points_written", "max_slope_index")   # -1 for NaN: no surface pixel, or a skipped frame
+MOTION_FIELDS = ("parent_row", "template_pixels", "status", "iterations", "tx_px", "ty_px", "theta_rad", "beta_mm", "tx_mm", "ty_mm", "centre_x",
+                 "centre_y", "rms_before_mm", "rms_after_mm", "last_step_px", "se_tx_px", "se_ty_px", "se_theta_rad", "tx_minus_dx",
+                 "ty_minus_dy")                                                          # VISTAF_MOTION_* order (include/vistaf_motion.h)
+MOTION_INT_FIELDS = ("parent_row", "template_pixels", "status", "iterations")
+MOTION_CSV_FIELDS = ("frame", "contact") + MOTION_FIELDS
+MOTION_FRAME_FIELDS = ("registered", "max_slide_mm", "max_slide_row", "max_twist_rad", "max_twist_row", "mean_tx_mm", "mean_ty_mm",
+                       "mean_rms_after_mm")                                              # VISTAF_MOTIONFRAME_*
+MOTION_FRAME_INT_FIELDS = ("registered", "max_slide_row", "max_twist_row")               # -1 for NaN: no registered row, or a frame without contacts
 THERMAL_FRAME_INT_FIELDS = ("registered_pixels", "contact_pixels", "hottest_contact", "coldest_contact")   # -1 for NaN: no contact has a mean
 
 
@@ -422,6 +430,49 @@ def write_cloud_ply(path: str, points, label=None) -> str:
         f.write(("\n".join(header) + "\n").encode("ascii"))
         f.write(body.tobytes())
     return path
+
+
+def motion_table(motion, contacts, count) -> list:
+    """Row dicts of the contact motion table: motion [B,K,>=20] (or [K,>=20] for one frame) float64 as `FtpSensor.motion` returns it, with
+    the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `tracks_table`: `frame`, `contact`
+    (the row in both tables) and MOTION_FIELDS, the parent row, pixel count, status and iterations as ints; what a status leaves out is NaN."""
+    t = np.asarray(motion, dtype=np.float64)
+    c = np.asarray(contacts, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if c.ndim == 2:
+        c = c[None]
+    if t.ndim != 3 or t.shape[2] < len(MOTION_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
+        raise ValueError("motion must be [B,K,>=20] with contacts [B,K,>=13] and count [B]")
+    rows = []
+    for b in range(t.shape[0]):
+        for k in range(min(int(n[b]), t.shape[1])):
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(MOTION_FIELDS):
+                row[name] = int(t[b, k, i]) if name in MOTION_INT_FIELDS else float(t[b, k, i])
+            rows.append(row)
+    return rows
+
+
+def write_motion_csv(output_dir: str, motion, contacts, count, filename: str = "motion.csv") -> str:
+    """motion.csv: one line per written contact, columns MOTION_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(MOTION_CSV_FIELDS))
+        w.writeheader()
+        for row in motion_table(motion, contacts, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def motion_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=8] of the motion read-out as a dict of MOTION_FRAME_FIELDS; the count and the two rows as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(MOTION_FRAME_FIELDS):
+        raise ValueError("the frame row must be [>=8]")
+    return {name: (_int_or_minus_one(f[i]) if name in MOTION_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(MOTION_FRAME_FIELDS)}
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
