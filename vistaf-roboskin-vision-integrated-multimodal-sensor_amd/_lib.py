@@ -55,6 +55,12 @@ MOTION_NAMES = ["parent_row", "template_pixels", "status", "iterations", "tx_px"
                 "centre_y", "rms_before_mm", "rms_after_mm", "last_step_px", "se_tx_px", "se_ty_px", "se_theta_rad", "tx_minus_dx", "ty_minus_dy"]
 MOTION_FRAME_NAMES = ["registered", "max_slide_mm", "max_slide_row", "max_twist_rad", "max_twist_row", "mean_tx_mm", "mean_ty_mm", "mean_rms_after_mm"]
 MOTION_STATUS = {"ok": 0, "not_converged": 1, "no_parent": 2, "too_few": 3, "singular": 4}   # VISTAF_MOTIONST_*, values of the `status` field
+NPRESSURE, NPRESSUREFRAME = 16, 12                                  # VISTAF_NPRESSURE, VISTAF_NPRESSUREFRAME (include/vistaf_pressure.h)
+# fields of a pressure row in the order of the VISTAF_PRESSURE_* indices (13..15 are reserved), and of a frame row (VISTAF_PRESSUREFRAME_*)
+PRESSURE_NAMES = ["pixels", "force_model_N", "tensile_model_N", "force_N", "mean_kPa", "peak_kPa", "peak_index", "cop_x", "cop_y", "offset_x_mm",
+                  "offset_y_mm", "peak_over_mean", "edge_share"]
+PRESSURE_FRAME_NAMES = ["contacts", "force_model_N", "tensile_model_N", "outside_model_N", "scale", "E_effective_MPa", "peak_kPa", "peak_index",
+                        "peak_row", "cop_x", "cop_y", "status"]
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -72,7 +78,7 @@ EXPORTS = [
 # csrc/test_hooks.h: kernel tier selection / debug planes for the parity tests, and the selection, fit and blur launchers on planes of the test's own
 TEST_EXPORTS = ["vistaf_ftp_test_set", "vistaf_ftp_test_select", "vistaf_ftp_test_select_instance", "vistaf_ftp_test_select_chained", "vistaf_ftp_test_polyfit", "vistaf_ftp_test_gauss",
                 "vistaf_ftp_test_chamfer", "vistaf_ftp_test_scratch_regions", "vistaf_ftp_test_cc_label", "vistaf_ftp_test_cc_largest",
-                "vistaf_ftp_test_chamfer_dispatch", "vistaf_ftp_test_blob_filter"]
+                "vistaf_ftp_test_chamfer_dispatch", "vistaf_ftp_test_blob_filter", "vistaf_ftp_test_dft_full_mag"]
 TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vistaf_tempseg_destroy", "vistaf_tempseg_segment",
                 "vistaf_temp_feature_planes", "vistaf_temp_color_support",
                 "vistaf_temp_clamp_map", "vistaf_temp_inpaint_map", "vistaf_temp_fuse_maps", "vistaf_temp_oriented_blur"]   # include/vistaf_temp.h
@@ -89,6 +95,7 @@ TEMPORAL_EXPORTS = ["vistaf_temporal_create", "vistaf_temporal_update", "vistaf_
                     "vistaf_temporal_destroy"]   # include/vistaf_temporal.h
 CLOUD_EXPORTS = ["vistaf_cloud_create", "vistaf_cloud_measure", "vistaf_cloud_destroy"]   # include/vistaf_cloud.h
 MOTION_EXPORTS = ["vistaf_motion_create", "vistaf_motion_update", "vistaf_motion_reset", "vistaf_motion_destroy"]   # include/vistaf_motion.h
+PRESSURE_EXPORTS = ["vistaf_pressure_create", "vistaf_pressure_measure", "vistaf_pressure_destroy"]   # include/vistaf_pressure.h
 ALIGN_EXPORTS = [            # include/vistaf_align.h
     "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
     "vistaf_align_set_reference", "vistaf_align_batch",
@@ -181,6 +188,7 @@ def load():
     lib.vistaf_ftp_test_cc_largest.argtypes = [vp, vp, vp, ci, ci, ci, vp]
     lib.vistaf_ftp_test_chamfer_dispatch.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]
     lib.vistaf_ftp_test_blob_filter.argtypes = [vp, vp, vp, vp, cd, cd, vp, ci, ci, vp]
+    lib.vistaf_ftp_test_dft_full_mag.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
     szp = ctypes.POINTER(ctypes.c_size_t)
     lib.vistaf_ftp_test_scratch_regions.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, ci, ctypes.c_char_p, szp, szp, szp, szp]
     lib.vistaf_tempseg_default_config.argtypes = [ctypes.POINTER(CTempSegConfig)]
@@ -244,8 +252,12 @@ def load():
     lib.vistaf_motion_reset.argtypes = [vp]
     lib.vistaf_motion_destroy.argtypes = [vp]
     lib.vistaf_motion_destroy.restype = None
+    lib.vistaf_pressure_create.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, ctypes.POINTER(vp)]
+    lib.vistaf_pressure_measure.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp, vp]
+    lib.vistaf_pressure_destroy.argtypes = [vp]
+    lib.vistaf_pressure_destroy.restype = None
     for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
-               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS + MOTION_EXPORTS):
+               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS + MOTION_EXPORTS + PRESSURE_EXPORTS):
         getattr(lib, fn)
     _lib = lib
     return lib

@@ -31,7 +31,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
                                                      os.path.join(HERE, "..", "include", "vistaf_tempsensor.h"), os.path.join(HERE, "..", "include", "vistaf_track.h"),
                                                      os.path.join(HERE, "..", "include", "vistaf_shape.h"), os.path.join(HERE, "..", "include", "vistaf_taxel.h"),
                                                      os.path.join(HERE, "..", "include", "vistaf_thermal.h"), os.path.join(HERE, "..", "include", "vistaf_temporal.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_cloud.h"), os.path.join(HERE, "..", "include", "vistaf_motion.h")]
+                                                     os.path.join(HERE, "..", "include", "vistaf_cloud.h"), os.path.join(HERE, "..", "include", "vistaf_motion.h"),
+                                                     os.path.join(HERE, "..", "include", "vistaf_pressure.h")]
     jobs = []
     objs = []
     for s in srcs:

@@ -1061,6 +1061,7 @@ int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int 
     else if (s == "inpaint_win") *total = inpaint_win_scratch_bytes(B, &regions);
     else if (s == "big") *total = big_scratch_bytes(B, h, w, &regions);
     else if (s == "tstats") *total = tstats_scratch_bytes(h, w, &regions);
+    else if (s == "pressure") *total = pressure_scratch_bytes(B, h, w, range, &regions);      // range: pad_px
     if (regions.empty()) return fail(VISTAF_E_INVALID, "unknown stage: " + s);
     if ((int)regions.size() > cap) return fail(VISTAF_E_INVALID, "more regions than cap");
     for (size_t i = 0; i < regions.size(); i++) {
@@ -1068,6 +1069,14 @@ int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int 
         offset[i] = regions[i].offset; bytes[i] = regions[i].bytes; align[i] = regions[i].align;
     }
     return (int)regions.size();
+}
+
+int vistaf_ftp_test_dft_full_mag(const float *planes, const void *Ex_half, const void *Ey_full, void *tmp, double *mag, int B, int h, int w, int Hf,
+                                 int Wf, void *stream)
+{
+    if (!planes || !Ex_half || !Ey_full || !tmp || !mag || B < 1 || h < 1 || w < 1 || Hf < h || Wf < w) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_dft_full_mag(planes, nullptr, (const double2 *)Ex_half, (const double2 *)Ey_full, (double2 *)tmp, mag, B, h, w, Hf, Wf, (hipStream_t)stream);
+    return launch_ok("launch_dft_full_mag");
 }
 
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,

@@ -14,6 +14,7 @@
 // every sample carries its own carrier) or shared by the batch (0).
 #include <algorithm>
 #include "kernels.hpp"
+#include "cgemm_mfma.hpp"
 
 namespace vf {
 
@@ -32,7 +33,6 @@ __device__ inline void cmac(double &ar, double &ai, double er, double ei, double
 // table, one per frame for per-frame tables (pair mode).  Strips start at each segment's first row, so a strip never mixes two tables, at
 // any h.  An output row depends only on its own input row and the table (the same k-steps in the same order), not on the strip it sits
 // in: a pair sample gives the bits of a session built on its reference.
-typedef double v4f64 __attribute__((ext_vector_type(4)));
 constexpr int DFT_MAXT = 4;            // column tiles (16 columns each) accumulated per pass over x
 __global__ __launch_bounds__(256) void k_dft_fwd1_mfma(const float *__restrict__ iw, const float *__restrict__ mu, const double2 *__restrict__ Ex_all,
                                                        size_t ex_stride, double2 *__restrict__ T, int h, int w, int pw, int seg_rows, int nseg)
@@ -167,25 +167,8 @@ __global__ __launch_bounds__(256) void k_dft_inv2_mfma(const double2 *__restrict
     const double2 *Qb = Q + b * (size_t)ph * w;
     const int ya = min(y0 + r, h - 1);
     v4f64 cre[4], cim[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) { cre[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; cim[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; }
     const int phb = geom ? max(0, min(geom[b].ph, ph)) : ph;     // the sample's own extent: K and the re / im split as a launch of that size
-    const int K = 2 * phb;
-    for (int k0 = 0; k0 < K; k0 += 4) {
-        const int k = k0 + kk;
-        const bool in = k < K, hi = k >= phb;
-        const int kq = in ? (hi ? k - phb : k) : 0;
-        const double a = in ? G[((size_t)ya * ph + kq) * 2 + (hi ? 1 : 0)] : 0.0;
-        double2 q[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) q[t] = Qb[(size_t)kq * w + min(x0 + 16 * t + r, w - 1)];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const double bre = in ? (hi ? -q[t].y : q[t].x) : 0.0, bim = in ? (hi ? q[t].x : q[t].y) : 0.0;
-            cre[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bre, cre[t], 0, 0, 0);
-            cim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bim, cim[t], 0, 0, 0);
-        }
-    }
+    cgemm16x64_mfma(G, ph, phb, Qb, w, w, ya, x0, lane, cre, cim);
     const double2 *cref = cref_all ? cref_all + b * ref_stride : nullptr;
     const float *amp_ref = amp_ref_all ? amp_ref_all + b * ref_stride : nullptr;
 #pragma unroll
@@ -238,24 +221,7 @@ __global__ __launch_bounds__(256) void k_full2_mfma(const double2 *__restrict__ 
     const double2 *Tb = T + b * (size_t)h * Wh;
     const int ya = min(y0 + r, Hf - 1);
     v4f64 cre[4], cim[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) { cre[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; cim[t] = (v4f64){0.0, 0.0, 0.0, 0.0}; }
-    const int K = 2 * h;
-    for (int k0 = 0; k0 < K; k0 += 4) {
-        const int k = k0 + kk;
-        const bool in = k < K, hi = k >= h;
-        const int kq = in ? (hi ? k - h : k) : 0;
-        const double a = in ? G[((size_t)ya * h + kq) * 2 + (hi ? 1 : 0)] : 0.0;
-        double2 q[4];
-#pragma unroll
-        for (int t = 0; t < 4; t++) q[t] = Tb[(size_t)kq * Wh + min(x0 + 16 * t + r, Wh - 1)];
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const double bre = in ? (hi ? -q[t].y : q[t].x) : 0.0, bim = in ? (hi ? q[t].x : q[t].y) : 0.0;
-            cre[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bre, cre[t], 0, 0, 0);
-            cim[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bim, cim[t], 0, 0, 0);
-        }
-    }
+    cgemm16x64_mfma(G, h, h, Tb, Wh, Wh, ya, x0, lane, cre, cim);
     double *mag = mag_all + b * (size_t)Hf * Wf;
     const int cy = Hf / 2, cx = Wf / 2;
 #pragma unroll
@@ -275,12 +241,19 @@ __global__ __launch_bounds__(256) void k_full2_mfma(const double2 *__restrict__ 
     }
 }
 
+// stage 1 alone with one table for the batch: T[b*h + y][c] = sum_x (iw[b][y][x] - mu[b]) * Ex[x][c], c = 0..nc-1 (mu may be null)
+void launch_dft_rows(const float *iw, const float *mu, const double2 *Ex, double2 *T, int B, int h, int w, int nc, hipStream_t st)
+{
+    const int rows = B * h;
+    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3(((rows + 15) / 16 + 3) / 4), dim3(256), 0, st, iw, mu, Ex, (size_t)0, T, h, w, nc, rows, 1);
+}
+
 // Ex_half: [w][Wh] (Wh = Wf/2 + 1), Ey_full: [Hf][h]; tmp: [B*h][Wh] double2
 void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_half, const double2 *Ey_full, double2 *tmp,
                          double *mag, int B, int h, int w, int Hf, int Wf, hipStream_t st)
 {
-    const int Wh = Wf / 2 + 1, rows = B * h;
-    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3(((rows + 15) / 16 + 3) / 4), dim3(256), 0, st, iw, mu, Ex_half, (size_t)0, tmp, h, w, Wh, rows, 1);
+    const int Wh = Wf / 2 + 1;
+    launch_dft_rows(iw, mu, Ex_half, tmp, B, h, w, Wh, st);
     hipLaunchKernelGGL(k_full2_mfma, dim3((Wh + 63) / 64, (Hf + 63) / 64, B), dim3(256), 0, st, (const double2 *)tmp, Ey_full, mag, h, Hf, Wf, Wh);
 }
 

@@ -117,6 +117,8 @@ void launch_dft_inverse(const double2 *patch, int patch_stride, const double2 *G
                         float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom = nullptr);
 void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_full, const double2 *Ey_full, double2 *tmp,
                          double *mag, int B, int h, int w, int Hf, int Wf, hipStream_t st);
+// stage 1 of launch_dft_full_mag alone (the row transform of the pressure read-out too): T [B*h][nc] = (iw - mu) . Ex, Ex [w][nc]; mu may be null
+void launch_dft_rows(const float *iw, const float *mu, const double2 *Ex, double2 *T, int B, int h, int w, int nc, hipStream_t st);
 void launch_top_peaks(const double *mag, int B, int Hf, int Wf, int dc, int npeaks, double *out_xyv /* [B][192] */, hipStream_t st);
 void launch_carrier_choose(const double *peaks, int npk, const double *mag, int Hf, int Wf, int bw, double max_dy_frac, CarrierGeom *geom, int B,
                            hipStream_t st);
@@ -317,5 +319,8 @@ void launch_backend_fused(float *depth, const uint8_t *cand, const unsigned int 
                           const uint8_t *reliable, const int32_t *status, double min_peak_mm, double rel_frac, PostParams pp, int32_t *labels,
                           unsigned int *peak_bits, uint8_t *kept, double *scalars, int nscal, float *out_h, uint8_t *out_r, int B, int h, int w,
                           hipStream_t st);
+
+// ---- k_pressure.hip (the pressure read-out, include/vistaf_pressure.h): its workspace of max_batch frames of h x w with pad_px of zero fill
+size_t pressure_scratch_bytes(int B, int h, int w, int pad, ScratchRec *rec = nullptr);
 
 }  // namespace vf

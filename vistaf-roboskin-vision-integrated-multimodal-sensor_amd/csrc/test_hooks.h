@@ -114,12 +114,19 @@ int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const i
                                 uint8_t *kept, int B, int P, void *stream);
 
 /* The scratch layout of one stage, from a counting pass of the function its launcher carves with (ScratchLayout, host_util.hpp).  Makes no HIP
- * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored).
+ * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored),
+ * and "pressure" (the workspace of vistaf_pressure.h; range = pad_px).
  * Region i, in carve order: names + 32 * i (NUL-terminated), offset[i], bytes[i], align[i]; *total = the size the stage's *_scratch_bytes
  * returns (for "inpaint_big": at this range, not at the widest padding).  Returns the number of regions, or VISTAF_E_INVALID for an unknown
  * stage, a bad shape, or more regions than `cap`. */
 int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
                                     size_t *total);
+
+/* launch_dft_full_mag (the reference frame's full-spectrum magnitude, k_dft.hip) on planes and tables of the caller's, for the timing of
+ * tests/diag/bench_pressure.py: planes [B,h,w] float32, Ex_half [w][Wf/2+1] and Ey_full [Hf][h] complex128, tmp [B*h][Wf/2+1] complex128,
+ * mag [B,Hf,Wf] float64, all on the device.  Asynchronous on `stream`. */
+int vistaf_ftp_test_dft_full_mag(const float *planes, const void *Ex_half, const void *Ey_full, void *tmp, double *mag, int B, int h, int w, int Hf,
+                                 int Wf, void *stream);
 #ifdef __cplusplus
 }
 #endif

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import math
 from typing import Any, Dict, Optional, Tuple
 
 import numpy as np
@@ -222,6 +223,9 @@ class FtpSensor:
         if getattr(self, "_motion", None) is not None:
             self._motion.close()
             self._motion = None
+        if getattr(self, "_pressure", None) is not None:
+            self._pressure.close()
+            self._pressure = None
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -480,6 +484,34 @@ class FtpSensor:
                              last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm))
         return out
 
+    def pressure(self, max_contacts: int = 8, pad_px: int = 32, E_mpa: float = 1.0, nu: float = 0.45, thickness_mm: float = math.inf,
+                 reset: bool = False) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the contact pressure map of an elastic skin under its height map
+        (pressure.PressureReadout; an extension, the reference has no counterpart).  E_mpa, nu and thickness_mm (math.inf: a half-space)
+        describe the skin and are the caller's: the package holds no material data, and the defaults are placeholders, not measurements.
+        Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map, the frames' mm_per_px and force_N (the
+        `scalars` columns), their status and the session's depth_eps_mm to the session's read-out, created on first use.  Returns the
+        contacts dict plus pressure_kpa [B,h,w] f32, pressure [B,K,16] f64 (fields PRESSURE_NAMES) and pressure_frame [B,12] f64 (fields
+        PRESSURE_FRAME_NAMES).  The other arguments can only change together with reset=True, which rebuilds the read-out with them."""
+        from .pressure import PressureReadout
+        k = int(max_contacts)
+        par = (k, int(pad_px), float(E_mpa), float(nu), float(thickness_mm))
+        pr = getattr(self, "_pressure", None)
+        if pr is not None and (pr.max_contacts, pr.pad_px, pr.E_mpa, pr.nu, pr.thickness_mm) != par:
+            if not reset:
+                raise ValueError("the arguments differ from the running pressure read-out's: pass reset=True to start over with them")
+            pr.close()
+            pr = self._pressure = None
+        out = self.contacts(k, index_plane=True)
+        if pr is None:
+            pr = self._pressure = PressureReadout(self.h, self.w, self.max_batch, *par, device=self.device)
+        last = self._last_out
+        sc = last["scalars"]
+        r = pr.measure(last["height_map_mm"], sc[:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm, contact_index=out["contact_index"],
+                       contacts=out["contacts"], count=out["count"], force_N=sc[:, SCALAR_NAMES.index("force_N")], status=last["status"])
+        out["pressure_kpa"], out["pressure"], out["pressure_frame"] = r["pressure_kpa"], r["rows"], r["frame"]
+        return out
+
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
@@ -533,7 +565,7 @@ class FtpSensor:
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
-                motion: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -552,7 +584,10 @@ class FtpSensor:
         dict of CLOUD_FRAME_NAMES.
         motion=dict(...) (with contacts=K; the keyword arguments of `FtpSensor.motion` but `max_contacts`, possibly none) adds "tracks", one
         dict of TRACK_NAMES per entry of "contacts", "motion", one dict of MOTION_NAMES per entry, and "motion_frame", a dict of
-        MOTION_FRAME_NAMES: this frame follows the frame of the previous predict that asked for it."""
+        MOTION_FRAME_NAMES: this frame follows the frame of the previous predict that asked for it.
+        pressure=dict(...) (the keyword arguments of `FtpSensor.pressure` but `max_contacts`: E_mpa, nu, thickness_mm, pad_px) adds
+        "pressure_kpa", the ndarray [h,w] f32 of the contact pressure, "pressure_frame", a dict of PRESSURE_FRAME_NAMES, and, with contacts=K,
+        "pressure", one dict of PRESSURE_NAMES per entry of "contacts"."""
         if motion is not None and contacts is None:
             raise ValueError("motion=dict(...) needs contacts=K")
         if shapes and contacts is None:
@@ -611,6 +646,16 @@ class FtpSensor:
                 for r in res["tracks"] + res["motion"]:
                     r.pop("frame")
                 res["motion_frame"] = motion_frame_record(mo["motion_frame"][0].cpu().numpy())
+        if pressure is not None:
+            from .writers import pressure_frame_record, pressure_table
+            running = getattr(self, "_pressure", None)          # without contacts=K the table's size is nobody's concern: keep the running one
+            pr = self.pressure(**dict(pressure, max_contacts=int(contacts) if contacts is not None else (running.max_contacts if running else 8)))
+            res["pressure_kpa"] = pr["pressure_kpa"][0].cpu().numpy()
+            res["pressure_frame"] = pressure_frame_record(pr["pressure_frame"][0].cpu().numpy())
+            if contacts is not None:
+                res["pressure"] = pressure_table(pr["pressure"].cpu().numpy(), pr["count"].cpu().numpy())
+                for r in res["pressure"]:
+                    r.pop("frame")
         if taxels is not None:
             from .writers import taxel_frame_record
             t = self.taxels(taxels)

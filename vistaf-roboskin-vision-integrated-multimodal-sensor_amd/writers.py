@@ -90,6 +90,13 @@ MOTION_INT_FIELDS = ("parent_row", "template_pixels", "status", "iterations")
 MOTION_CSV_FIELDS = ("frame", "contact") + MOTION_FIELDS
 MOTION_FRAME_FIELDS = ("registered", "max_slide_mm", "max_slide_row", "max_twist_rad", "max_twist_row", "mean_tx_mm", "mean_ty_mm",
                        "mean_rms_after_mm")                                              # VISTAF_MOTIONFRAME_*
+PRESSURE_FIELDS = ("pixels", "force_model_N", "tensile_model_N", "force_N", "mean_kPa", "peak_kPa", "peak_index", "cop_x", "cop_y", "offset_x_mm",
+                   "offset_y_mm", "peak_over_mean", "edge_share")                         # VISTAF_PRESSURE_* order (include/vistaf_pressure.h)
+PRESSURE_INT_FIELDS = ("pixels", "peak_index")
+PRESSURE_CSV_FIELDS = ("frame", "contact") + PRESSURE_FIELDS
+PRESSURE_FRAME_FIELDS = ("contacts", "force_model_N", "tensile_model_N", "outside_model_N", "scale", "E_effective_MPa", "peak_kPa", "peak_index",
+                         "peak_row", "cop_x", "cop_y", "status")                          # VISTAF_PRESSUREFRAME_* order
+PRESSURE_FRAME_INT_FIELDS = ("contacts", "peak_index", "peak_row", "status")              # -1 for NaN: a frame whose status is not 0
 MOTION_FRAME_INT_FIELDS = ("registered", "max_slide_row", "max_twist_row")               # -1 for NaN: no registered row, or a frame without contacts
 THERMAL_FRAME_INT_FIELDS = ("registered_pixels", "contact_pixels", "hottest_contact", "coldest_contact")   # -1 for NaN: no contact has a mean
 
@@ -473,6 +480,49 @@ def motion_frame_record(frame_row) -> Dict[str, Any]:
     if f.ndim != 1 or f.shape[0] < len(MOTION_FRAME_FIELDS):
         raise ValueError("the frame row must be [>=8]")
     return {name: (_int_or_minus_one(f[i]) if name in MOTION_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(MOTION_FRAME_FIELDS)}
+
+
+def pressure_table(rows, count) -> list:
+    """Row dicts of the pressure table: rows [B,K,>=13] (or [K,>=13] for one frame) float64 as `FtpSensor.pressure` returns it, with count [B]
+    of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact` (the row in both tables) and PRESSURE_FIELDS,
+    the pixel count and the peak's index as ints; a field whose divisor is 0 is NaN."""
+    t = np.asarray(rows, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim != 3 or t.shape[2] < len(PRESSURE_FIELDS) or t.shape[0] != n.shape[0]:
+        raise ValueError("rows must be [B,K,>=13] with count [B]")
+    out = []
+    for b in range(t.shape[0]):
+        for k in range(min(max(int(n[b]), 0), t.shape[1])):
+            if not np.isfinite(t[b, k, 0]):               # a frame whose status is not 0
+                continue
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(PRESSURE_FIELDS):
+                row[name] = _int_or_minus_one(t[b, k, i]) if name in PRESSURE_INT_FIELDS else float(t[b, k, i])
+            out.append(row)
+    return out
+
+
+def write_pressure_csv(output_dir: str, rows, count, filename: str = "pressure.csv") -> str:
+    """pressure.csv: one line per written contact, columns PRESSURE_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(PRESSURE_CSV_FIELDS))
+        w.writeheader()
+        for row in pressure_table(rows, count):
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def pressure_frame_record(frame_row) -> Dict[str, Any]:
+    """One frame row [>=12] of the pressure read-out as a dict of PRESSURE_FRAME_FIELDS; the count, the peak's index and row and the status
+    as ints (-1 for NaN)."""
+    f = np.asarray(frame_row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(PRESSURE_FRAME_FIELDS):
+        raise ValueError("the frame row must be [>=12]")
+    return {name: (_int_or_minus_one(f[i]) if name in PRESSURE_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(PRESSURE_FRAME_FIELDS)}
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
