@@ -22,7 +22,6 @@ EXACT = ("parent_row", "template_pixels", "status", "iterations", "centre_x", "c
 FRAME_EXACT = ("registered", "max_slide_row", "max_twist_row")
 OK, NOT_CONVERGED, NO_PARENT, TOO_FEW, SINGULAR = 0, 1, 2, 3, 4
 T_PARENT, T_DX, T_DY = 2, 5, 6                                   # VISTAF_TRACK_* indices the read-out reads
-C_X0, C_Y0, C_X1, C_Y1 = SH.C_X0, SH.C_Y0, SH.C_X1, SH.C_Y1
 FLOOR = 2.0 ** -32
 
 
@@ -171,16 +170,9 @@ def numpy_motion(depth_mm, contact_index, contacts, count, tracks, mm_per_px, ep
                 motion[t, k, :4] = [pr if np.isfinite(pr) else -1.0, 0, NO_PARENT, 0]
                 continue
             p = int(pr)
-            box = prev["table"][p, [C_X0, C_Y0, C_X1, C_Y1]]
-            inbox = np.zeros((h, w), bool)
-            bw = bh = 0
-            if np.isfinite(box).all() and (np.abs(box) <= 1.0e9).all():
-                bx0, by0, bx1, by1 = (int(v) for v in box)
-                x0, y0, x1, y1 = max(bx0, 0), max(by0, 0), min(bx1, w - 1), min(by1, h - 1)
-                if x1 >= x0 and y1 >= y0:
-                    bw, bh = x1 - x0 + 1, y1 - y0 + 1
-                    inbox[y0:y1 + 1, x0:x1 + 1] = True
-            mask = inbox & (prev["index"] == p) & (_plane(prev["depth"]) > np.float32(eps))
+            clipped = SH.table_box(prev["table"][p], h, w)[1]
+            bw, bh = (clipped[2] - clipped[0] + 1, clipped[3] - clipped[1] + 1) if clipped else (0, 0)
+            mask = SH.box_mask(clipped, h, w) & (prev["index"] == p) & (_plane(prev["depth"]) > np.float32(eps))
             start = (DX, DY) if init_from_centroid and np.isfinite(DX) and np.isfinite(DY) else (0.0, 0.0)
             motion[t, k] = register(prev["depth"], depth_mm[t], mask, (bw, bh), float(mm_per_px[t]), start, (DX, DY), iterations, tol_px, min_pixels,
                                     order, p)

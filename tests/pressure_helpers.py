@@ -9,6 +9,8 @@ import math
 
 import numpy as np
 
+import shapes_helpers as SH
+
 FIELDS = ("pixels", "force_model_N", "tensile_model_N", "force_N", "mean_kPa", "peak_kPa", "peak_index", "cop_x", "cop_y", "offset_x_mm",
           "offset_y_mm", "peak_over_mean", "edge_share")
 FRAME_FIELDS = ("contacts", "force_model_N", "tensile_model_N", "outside_model_N", "scale", "E_effective_MPa", "peak_kPa", "peak_index", "peak_row",
@@ -105,14 +107,6 @@ def matmul_pressure(depth32, mm_per_px, eps, pad, E, nu, t, status=None):
 
 
 # ------------------------------------------------------------------------------------------------------------ the tables
-def _clip_box(row, h, w):
-    v = row[list(BBOX)]
-    if not np.all(np.isfinite(v)):
-        return None
-    x0, y0, x1, y1 = max(int(v[0]), 0), max(int(v[1]), 0), min(int(v[2]), w - 1), min(int(v[3]), h - 1)
-    return (x0, y0, x1, y1) if x1 >= x0 and y1 >= y0 else None
-
-
 def tables(p32, mm_per_px, K, E, index=None, contacts=None, count=None, force=None, status=None):
     """(rows [B,K,16] or None, frame [B,12], terms): the header's step 4 on the float32 planes p32 with math.fsum.  terms[(b, k)] is the
     number of pixels of the row, terms[b] that of the frame: the N of the tolerance."""
@@ -133,11 +127,7 @@ def tables(p32, mm_per_px, K, E, index=None, contacts=None, count=None, force=No
         kk = 0 if index is None else min(max(int(count[b]), 0), K)
         raw = []
         for k in range(kk):
-            box = _clip_box(contacts[b, k], h, w)
-            m = np.zeros((h, w), dtype=bool)
-            if box is not None:
-                x0, y0, x1, y1 = box
-                m[y0:y1 + 1, x0:x1 + 1] = index[b, y0:y1 + 1, x0:x1 + 1] == k
+            m = SH.box_mask(SH.table_box(contacts[b, k], h, w)[1], h, w) & (index[b] == k)
             ys, xs = np.nonzero(m)
             n = len(ys)
             v = p[ys, xs]

@@ -51,6 +51,26 @@ def _fit_normal_equations(X, d):
     return np.linalg.solve(L.T, np.linalg.solve(L, rhs))
 
 
+def table_box(row, h, w, margin=0):
+    """The box of a contacts-table row as the read-outs' headers read it: ((bx0, by0, bx1, by1), clipped).  The first is the table's own
+    integers; a value that is not finite or beyond +-1e9 gives no box, (0, 0, -1, -1).  `clipped` is (x0, y0, x1, y1), the box grown by
+    `margin` on every side and cut to the h x w frame, or None where there is no box or nothing of it lies inside."""
+    v = np.asarray(row, dtype=np.float64)[[C_X0, C_Y0, C_X1, C_Y1]]
+    if not (np.isfinite(v).all() and (np.abs(v) <= 1.0e9).all()):
+        return (0, 0, -1, -1), None
+    bx0, by0, bx1, by1 = own = tuple(int(t) for t in v)
+    x0, y0, x1, y1 = max(bx0 - margin, 0), max(by0 - margin, 0), min(bx1 + margin, w - 1), min(by1 + margin, h - 1)
+    return own, ((x0, y0, x1, y1) if x1 >= x0 and y1 >= y0 else None)
+
+
+def box_mask(clipped, h, w):
+    m = np.zeros((h, w), bool)
+    if clipped is not None:
+        x0, y0, x1, y1 = clipped
+        m[y0:y1 + 1, x0:x1 + 1] = True
+    return m
+
+
 def _shapes(depth_mm, contact_index, contacts, count, mm_per_px, eps, frac, fit):
     depth_mm, contact_index = np.asarray(depth_mm, dtype=np.float32), np.asarray(contact_index)
     contacts = np.asarray(contacts, dtype=np.float64)
@@ -63,14 +83,8 @@ def _shapes(depth_mm, contact_index, contacts, count, mm_per_px, eps, frac, fit)
         kk = min(max(int(count[b]), 0), K)
         for k in range(kk):
             row, o = contacts[b, k], out[b, k]
-            box = row[[C_X0, C_Y0, C_X1, C_Y1]]
-            inbox = np.zeros((h, w), bool)
-            if np.isfinite(box).all():
-                bx0, by0, bx1, by1 = (int(v) for v in box)
-                inbox[max(by0, 0):max(min(by1, h - 1) + 1, 0), max(bx0, 0):max(min(bx1, w - 1) + 1, 0)] = True
-            else:
-                bx0, by0, bx1, by1 = 0, 0, -1, -1
-            cm = inbox & (contact_index[b] == k) & (d32 > np.float32(eps))
+            (bx0, by0, bx1, by1), clipped = table_box(row, h, w)
+            cm = box_mask(clipped, h, w) & (contact_index[b] == k) & (d32 > np.float32(eps))
             pad = np.pad(cm, 1)
             inner = cm & pad[1:-1, :-2] & pad[1:-1, 2:] & pad[:-2, 1:-1] & pad[2:, 1:-1]
             ys, xs = np.nonzero(cm)

@@ -119,16 +119,9 @@ def _fsum(a):
 
 def _box(row, h, w, margin):
     """(box mask, grown box mask) of a table row, as the header reads it"""
-    own, grown = np.zeros((h, w), bool), np.zeros((h, w), bool)
-    b = row[[SH.C_X0, SH.C_Y0, SH.C_X1, SH.C_Y1]]
-    if not (np.isfinite(b).all() and (np.abs(b) <= 1.0e9).all()):
-        return own, grown
-    x0, y0, x1, y1 = (int(v) for v in b)
-    if x1 < x0 or y1 < y0:
-        return own, grown
-    own[max(y0, 0):max(min(y1, h - 1) + 1, 0), max(x0, 0):max(min(x1, w - 1) + 1, 0)] = True
-    grown[max(y0 - margin, 0):max(min(y1 + margin, h - 1) + 1, 0), max(x0 - margin, 0):max(min(x1 + margin, w - 1) + 1, 0)] = True
-    return own, grown
+    (x0, y0, x1, y1), own = SH.table_box(row, h, w)
+    grown = SH.table_box(row, h, w, margin)[1] if x1 >= x0 and y1 >= y0 else None     # an inverted box is no box: it does not grow into one
+    return SH.box_mask(own, h, w), SH.box_mask(grown, h, w)
 
 
 def _thermal(temp_crop, depth_mm, contact_index, contacts, count, eps, margin, status, total):

@@ -16,23 +16,23 @@ from typing import Any, Dict, Optional, Tuple
 import torch
 
 from . import _lib
+from ._readout import Readout, ptr
 
 CLOUD_POINT_NAMES = _lib.CLOUD_POINT_NAMES
 CLOUD_FRAME_NAMES = _lib.CLOUD_FRAME_NAMES
 
 
-class CloudReadout:
+class CloudReadout(Readout):
     """A point-cloud read-out for h x w planes, at most `max_batch` frames and `max_points` written points per call.  stride (1..64) keeps
     every stride-th column and row; origin (x, y) is the pixel that becomes X = Y = 0, by default the crop centre ((w - 1) / 2, (h - 1) / 2).
     More points than max_points is not an error: the offsets are never capped, the frame rows count what was written, and `trim` reports
     `overflow`.  Creating it needs no device, `measure` does."""
+    _destroy = "vistaf_cloud_destroy"
 
     def __init__(self, h: int, w: int, max_batch: int, max_points: int, stride: int = 1, origin: Optional[Tuple[float, float]] = None, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.h, self.w, self.max_batch, self.max_points, self.stride = int(h), int(w), int(max_batch), int(max_points), int(stride)
         self.origin = ((self.w - 1) / 2.0, (self.h - 1) / 2.0) if origin is None else (float(origin[0]), float(origin[1]))
-        self.device = torch.device(device)
+        self._open(device, need_device=False)
         _lib.check(self._lib.vistaf_cloud_create(self.h, self.w, self.max_batch, self.max_points, self.stride, self.origin[0], self.origin[1],
                                                  ctypes.byref(self._h)))
 
@@ -44,19 +44,12 @@ class CloudReadout:
         frame [B,12] f64 (fields CLOUD_FRAME_NAMES, field 11 reserved).  Only the first min(offsets[B], max_points) entries of points, pixel
         and label are written; `trim` cuts them.  out: tensors "points", "pixel", "label" of the caller's own (contiguous, on the device,
         at least max_points long) to write into instead of new ones."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("CloudReadout.measure needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        dep = torch.as_tensor(depth).to(self.device, torch.float32).contiguous()
-        mpp = torch.as_tensor(mm_per_px).to(self.device, torch.float64).contiguous()
-        if dep.dim() != 3 or tuple(dep.shape[1:]) != (self.h, self.w):
-            raise ValueError(f"depth must be [B,{self.h},{self.w}]")
+        self._need_device("measure")
+        dep = self._t(depth, torch.float32, (None, self.h, self.w), f"depth must be [B,{self.h},{self.w}]")
         b = int(dep.shape[0])
-        sta = None if status is None else torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        idx = None if contact_index is None else torch.as_tensor(contact_index).to(self.device, torch.int8).contiguous()
-        if tuple(mpp.shape) != (b,) or (sta is not None and tuple(sta.shape) != (b,)):
-            raise ValueError("mm_per_px and status must be [B] for the B frames of depth")
-        if idx is not None and tuple(idx.shape) != tuple(dep.shape):
-            raise ValueError("contact_index must have the shape of depth")
+        msg = "mm_per_px and status must be [B] for the B frames of depth"
+        mpp, sta = self._t(mm_per_px, torch.float64, (b,), msg), self._t(status, torch.int32, (b,), msg)
+        idx = self._t(contact_index, torch.int8, dep.shape, "contact_index must have the shape of depth")
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         given = out or {}
@@ -74,11 +67,9 @@ class CloudReadout:
         res["offsets"] = torch.empty((b + 1,), dtype=torch.int64, device=self.device)
         res["frame"] = torch.empty((b, _lib.NCLOUD_FRAME), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_cloud_measure(self._h, dep.data_ptr(), mpp.data_ptr(), sta.data_ptr() if sta is not None else None,
-                                                      idx.data_ptr() if idx is not None else None, float(depth_eps_mm), b,
+            _lib.check(self._lib.vistaf_cloud_measure(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), ptr(idx), float(depth_eps_mm), b,
                                                       res["points"].data_ptr(), res["pixel"].data_ptr(),
-                                                      res["label"].data_ptr() if idx is not None else None, res["offsets"].data_ptr(),
-                                                      res["frame"].data_ptr(), int(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                      ptr(res.get("label")), res["offsets"].data_ptr(), res["frame"].data_ptr(), self._stream()))
         return res
 
     def trim(self, out: Dict[str, torch.Tensor]) -> Dict[str, Any]:
@@ -90,14 +81,3 @@ class CloudReadout:
         res: Dict[str, Any] = {k: out[k][:n] for k in ("points", "pixel", "label") if k in out}
         res.update(offsets=out["offsets"], frame=out["frame"], total=total, overflow=total > self.max_points)
         return res
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_cloud_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

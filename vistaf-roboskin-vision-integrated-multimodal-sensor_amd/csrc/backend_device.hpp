@@ -163,7 +163,7 @@ __device__ inline void tail_frame(HeightFn height, const uint8_t *__restrict__ R
             if (dp > eps) { volp += dp; cntp++; const unsigned long long key = (unsigned long long)__float_as_uint(dp) << 32; if (key > mxp) mxp = key; }
             if (dn > eps) { voln += dn; cntn++; const unsigned long long key = (unsigned long long)__float_as_uint(dn) << 32; if (key > mxn) mxn = key; }
             if (rs[k] && finitef(vv)) {            // arg-max of depth (mm) over roi & finite: first occurrence of the maximum
-                const unsigned long long key = ((unsigned long long)f2key(vv) << 32) | (unsigned int)(0xffffffffu - (unsigned int)p);
+                const unsigned long long key = argmax_key(vv, (unsigned int)p);
                 if (key > am) am = key;
             }
             if (rs[k] && finitef(u[k])) {          // arg-min of unitless height over roi & finite: first occurrence of the minimum

@@ -34,6 +34,8 @@ __device__ inline float key2f(uint32_t k)
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __uint_as_float(u);
 }
+// arg-max key: the larger value wins, among equal values the smaller index
+__device__ inline unsigned long long argmax_key(float v, unsigned i) { return ((unsigned long long)f2key(v) << 32) | (0xffffffffu - i); }
 
 __device__ inline bool finitef(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ inline bool finitef(double v) { return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }

@@ -1,7 +1,6 @@
-// Host-side plumbing shared by the translation units behind the C ABI (api.hip, align.hip, tempseg.hip, tempsensor.hip, k_tempmodel.hip,
-// k_tracks.hip) and by the launchers that cut a scratch buffer into planes: error reporting, the owning list of device allocations, the
-// carver of the scratch layouts, and the OpenCV constant tables (Gaussian taps, structuring elements) that more than one modality builds.
-// Host only; nothing here launches a kernel.
+// Host-side plumbing shared by every translation unit that defines functions of the C ABI and by the launchers that cut a scratch buffer
+// into planes: error reporting, the owning list of device allocations, the carver of the scratch layouts, and the OpenCV constant tables
+// (Gaussian taps, structuring elements) that more than one modality builds.  Host only; nothing here launches a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>

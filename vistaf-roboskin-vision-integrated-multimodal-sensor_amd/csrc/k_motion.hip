@@ -22,6 +22,7 @@
 #include "../../include/vistaf_motion.h"
 #include "../../include/vistaf_track.h"
 #include "chol.hpp"
+#include "contact_rows.hpp"
 #include "host_util.hpp"
 
 using namespace vf;
@@ -51,13 +52,6 @@ MoBufs motion_scratch(ScratchLayout &L, size_t P, int K)
     return bf;
 }
 
-__device__ inline bool mo_box_value(double v, int &o)
-{
-    if (!finitef(v) || v < -1.0e9 || v > 1.0e9) return false;
-    o = (int)v;
-    return true;
-}
-
 __device__ inline int mo_clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 struct MoPlane {
@@ -79,22 +73,6 @@ struct MoPlane {
         const double top = (1.0 - fx) * (double)at32(x0, y0) + fx * (double)at32(x1, y0);
         const double bot = (1.0 - fx) * (double)at32(x0, y1) + fx * (double)at32(x1, y1);
         return (1.0 - fy) * top + fy * bot;
-    }
-};
-
-// the walk over the clipped box of the parent, pixel i to thread i mod MO_NT
-struct MoBox {
-    int x0, y0, bw, total, step_x, step_y;
-    template <typename F>
-    __device__ inline void each(int tid, F f) const
-    {
-        int x = bw ? tid % bw : 0, y = bw ? tid / bw : 0;
-        for (int i = tid; i < total; i += MO_NT) {
-            f(x0 + x, y0 + y);
-            x += step_x;
-            y += step_y;
-            if (x >= bw) { x -= bw; y++; }
-        }
     }
 };
 
@@ -131,14 +109,8 @@ __global__ __launch_bounds__(MO_NT) void k_motion(const float *__restrict__ dept
     const int k = blockIdx.x, t = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     double *out = motion + ((size_t)t * K + k) * VISTAF_NMOTION;
-    int kk = count[t];
-    kk = kk < 0 ? 0 : (kk > K ? K : kk);
-    if (k >= kk) {
-        if (tid < VISTAF_NMOTION) out[tid] = nan64();
-        return;
-    }
-    int m = t ? count[t - 1] : (have_carry ? carry_count[0] : 0);
-    m = m < 0 ? 0 : (m > K ? K : m);
+    if (nan_row(k >= clamp_count(count[t], K), out, VISTAF_NMOTION)) return;
+    const int m = clamp_count(t ? count[t - 1] : (have_carry ? carry_count[0] : 0), K);
     const double *trow = tracks + ((size_t)t * K + k) * VISTAF_NTRACK;
     const double pr = trow[VISTAF_TRACK_PARENT_ROW], DX = trow[VISTAF_TRACK_DX], DY = trow[VISTAF_TRACK_DY];
     if (!finitef(pr) || pr < 0.0 || pr >= (double)m) {
@@ -156,13 +128,9 @@ __global__ __launch_bounds__(MO_NT) void k_motion(const float *__restrict__ dept
     const MoPlane T{t ? depth + (size_t)(t - 1) * P : carry_depth, h, w}, I{depth + (size_t)t * P, h, w};
     const int8_t *pidx = t ? index + (size_t)(t - 1) * P : carry_index;
     const double *prow = (t ? contacts + (size_t)(t - 1) * K * VISTAF_NCONTACT : carry_table) + (size_t)p * VISTAF_NCONTACT;
-    int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-    const bool box_ok = mo_box_value(prow[VISTAF_CONTACT_BBOX_X0], bx0) && mo_box_value(prow[VISTAF_CONTACT_BBOX_Y0], by0) &&
-                        mo_box_value(prow[VISTAF_CONTACT_BBOX_X1], bx1) && mo_box_value(prow[VISTAF_CONTACT_BBOX_Y1], by1);
-    const int x0 = bx0 < 0 ? 0 : bx0, y0 = by0 < 0 ? 0 : by0, x1 = bx1 > w - 1 ? w - 1 : bx1, y1 = by1 > h - 1 ? h - 1 : by1;
-    const int bw = box_ok && x1 >= x0 ? x1 - x0 + 1 : 0, bh = box_ok && y1 >= y0 ? y1 - y0 + 1 : 0;
-    const MoBox box{x0, y0, bw, bw * bh, bw ? MO_NT - (MO_NT / bw) * bw : 0, bw ? MO_NT / bw : 0};       // total <= h * w < 2^31
-    const double R = 0.5 * sqrt((double)bw * (double)bw + (double)bh * (double)bh);
+    const ContactBox box(prow, h, w);                       // the parent's
+    const double R = 0.5 * sqrt((double)box.bw * (double)box.bw + (double)box.bh * (double)box.bh);
+    const BoxWalk<MO_NT> walk(box, tid);
     // is (x, y), inside the frame, a template pixel; d = its depth
     auto templ = [&](int x, int y, float &d) {
         d = T.at32(x, y);
@@ -171,7 +139,7 @@ __global__ __launch_bounds__(MO_NT) void k_motion(const float *__restrict__ dept
 
     // ---- sweep 0: n and the centre, exact integers
     unsigned long long n = 0, sx = 0, sy = 0;
-    box.each(tid, [&](int x, int y) {
+    walk.each([&](int x, int y) {
         float d;
         if (templ(x, y, d)) { n++; sx += (unsigned long long)x; sy += (unsigned long long)y; }
     });
@@ -199,7 +167,7 @@ __global__ __launch_bounds__(MO_NT) void k_motion(const float *__restrict__ dept
     double hs[MO_NH];
 #pragma unroll
     for (int j = 0; j < MO_NH; j++) hs[j] = 0.0;
-    box.each(tid, [&](int x, int y) {
+    walk.each([&](int x, int y) {
         float d;
         if (!templ(x, y, d)) return;
         const double Tx = (T.at(x + 1, y) - T.at(x - 1, y)) / 2.0, Ty = (T.at(x, y + 1) - T.at(x, y - 1)) / 2.0;
@@ -229,7 +197,7 @@ __global__ __launch_bounds__(MO_NT) void k_motion(const float *__restrict__ dept
         double bs[MO_NB];
 #pragma unroll
         for (int j = 0; j < MO_NB; j++) bs[j] = 0.0;
-        box.each(tid, [&](int x, int y) {
+        walk.each([&](int x, int y) {
             float d;
             if (!templ(x, y, d)) return;
             const double Tx = (T.at(x + 1, y) - T.at(x - 1, y)) / 2.0, Ty = (T.at(x, y + 1) - T.at(x, y - 1)) / 2.0;
@@ -282,8 +250,7 @@ __global__ __launch_bounds__(64) void k_motion_frames(const double *__restrict__
     __shared__ int sok[64];
     const int b = blockIdx.x, lane = threadIdx.x;
     double *o = frame + (size_t)b * VISTAF_NMOTIONFRAME;
-    int kk = count[b];
-    kk = kk < 0 ? 0 : (kk > K ? K : kk);
+    const int kk = clamp_count(count[b], K);
     if (kk == 0) {
         if (lane < VISTAF_NMOTIONFRAME) o[lane] = nan64();
         return;

@@ -285,7 +285,7 @@ __global__ __launch_bounds__(TP_T) void k_tail_part(const float *__restrict__ he
         if (dp > eps) { volp += dp; cntp++; const unsigned long long key = (unsigned long long)__float_as_uint(dp) << 32; if (key > mxp) mxp = key; }
         if (dn > eps) { voln += dn; cntn++; const unsigned long long key = (unsigned long long)__float_as_uint(dn) << 32; if (key > mxn) mxn = key; }
         if (rs && finitef(vv)) {
-            const unsigned long long key = ((unsigned long long)f2key(vv) << 32) | (unsigned int)(0xffffffffu - (unsigned int)p);
+            const unsigned long long key = argmax_key(vv, (unsigned int)p);
             if (key > am) am = key;
         }
         if (rs && finitef(uu)) {

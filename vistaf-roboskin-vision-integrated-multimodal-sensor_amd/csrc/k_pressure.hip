@@ -27,6 +27,7 @@
 
 #include "../../include/vistaf_pressure.h"
 #include "cgemm_mfma.hpp"
+#include "contact_rows.hpp"
 #include "host_util.hpp"
 
 using namespace vf;
@@ -176,15 +177,6 @@ __global__ __launch_bounds__(256) void k_pressure_inv2(const double *__restrict_
     }
 }
 
-__device__ inline bool pr_box_value(double v, int &o)
-{
-    if (!finitef(v) || v < -1.0e9 || v > 1.0e9) return false;
-    o = (int)v;
-    return true;
-}
-
-__device__ inline unsigned long long pr_key(float v, unsigned i) { return ((unsigned long long)f2key(v) << 32) | (0xffffffffu - i); }
-
 __global__ __launch_bounds__(PR_NT) void k_pressure_rows(const float *__restrict__ p, const int8_t *__restrict__ index, const double *__restrict__ contacts,
                                                          const int32_t *__restrict__ count, const double *__restrict__ mm_per_px,
                                                          const int32_t *__restrict__ status, int h, int w, int K, double *__restrict__ rows)
@@ -195,26 +187,15 @@ __global__ __launch_bounds__(PR_NT) void k_pressure_rows(const float *__restrict
     const size_t b = blockIdx.y;
     double *row = rows + (b * (size_t)K + k) * VISTAF_NPRESSURE;
     const bool ok = !status || status[b] == 0;
-    const int cnt = ok ? count[b] : 0, kk = cnt < 0 ? 0 : (cnt > K ? K : cnt);
-    if (k >= kk) {                                      // workgroup-uniform
-        if (tid < VISTAF_NPRESSURE) row[tid] = nan64();
-        return;
-    }
-    const double *crow = contacts + (b * (size_t)K + k) * VISTAF_NCONTACT;
-    int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-    const bool fin = pr_box_value(crow[VISTAF_CONTACT_BBOX_X0], bx0) && pr_box_value(crow[VISTAF_CONTACT_BBOX_Y0], by0) &&
-                     pr_box_value(crow[VISTAF_CONTACT_BBOX_X1], bx1) && pr_box_value(crow[VISTAF_CONTACT_BBOX_Y1], by1);
-    bx0 = max(bx0, 0); by0 = max(by0, 0); bx1 = min(bx1, w - 1); by1 = min(by1, h - 1);
-    const int bw = (fin && bx1 >= bx0) ? bx1 - bx0 + 1 : 0, bh = (fin && by1 >= by0) ? by1 - by0 + 1 : 0;
-    const int total = bw * bh;                          // <= h * w < 2^31
+    if (nan_row(k >= clamp_count(ok ? count[b] : 0, K), row, VISTAF_NPRESSURE)) return;
+    const ContactBox box(contacts + (b * (size_t)K + k) * VISTAF_NCONTACT, h, w);
     const float *pf = p + b * (size_t)h * w;
     const int8_t *ix = index + b * (size_t)h * w;
     double Pp = 0.0, Pn = 0.0, Xp = 0.0, Yp = 0.0, Pe = 0.0;
     unsigned long long n = 0, Sx = 0, Sy = 0, key = 0;
-    for (int i = tid; i < total; i += PR_NT) {
-        const int x = bx0 + i % bw, y = by0 + i / bw;
+    BoxWalk<PR_NT>(box, tid).each([&](int x, int y) {
         const size_t o = (size_t)y * w + x;
-        if (ix[o] != k) continue;
+        if (ix[o] != k) return;
         const float v32 = pf[o];
         const double v = (double)v32, vp = v > 0.0 ? v : 0.0;
         n++; Sx += (unsigned)x; Sy += (unsigned)y;
@@ -224,9 +205,9 @@ __global__ __launch_bounds__(PR_NT) void k_pressure_rows(const float *__restrict
         Yp += (double)y * vp;
         const bool edge = x == 0 || y == 0 || x == w - 1 || y == h - 1 || ix[o - 1] != k || ix[o + 1] != k || ix[o - w] != k || ix[o + w] != k;
         if (edge) Pe += vp;
-        const unsigned long long ky = pr_key(v32, (unsigned)o);
+        const unsigned long long ky = argmax_key(v32, (unsigned)o);
         key = ky > key ? ky : key;
-    }
+    });
     Pp = block_sum<double>(Pp, sd); Pn = block_sum<double>(Pn, sd); Xp = block_sum<double>(Xp, sd); Yp = block_sum<double>(Yp, sd);
     Pe = block_sum<double>(Pe, sd);
     n = block_sum<unsigned long long>(n, s64); Sx = block_sum<unsigned long long>(Sx, s64); Sy = block_sum<unsigned long long>(Sy, s64);
@@ -269,7 +250,7 @@ __global__ __launch_bounds__(PR_FT) void k_pressure_frame(const float *__restric
         if (tid < VISTAF_NPRESSUREFRAME) fr[tid] = tid == VISTAF_PRESSUREFRAME_STATUS ? (double)st : nan64();
         return;
     }
-    const int cnt = index ? count[b] : 0, kk = cnt < 0 ? 0 : (cnt > K ? K : cnt);
+    const int kk = clamp_count(index ? count[b] : 0, K);
     const float *pf = p + b * (size_t)P;
     const int8_t *ix = index ? index + b * (size_t)P : nullptr;
     double Tn = 0.0, Out = 0.0;
@@ -280,7 +261,7 @@ __global__ __launch_bounds__(PR_FT) void k_pressure_frame(const float *__restric
         Tn += -v > 0.0 ? -v : 0.0;
         const int id = ix ? (int)ix[i] : -1;
         if (id < 0 || id >= kk) Out += fabs(v);
-        const unsigned long long ky = pr_key(v32, i);
+        const unsigned long long ky = argmax_key(v32, i);
         key = ky > key ? ky : key;
     }
     Tn = block_sum<double>(Tn, sd);

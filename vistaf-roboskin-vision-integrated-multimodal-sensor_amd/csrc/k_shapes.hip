@@ -16,6 +16,7 @@
 
 #include "../../include/vistaf_shape.h"
 #include "chol.hpp"
+#include "contact_rows.hpp"
 #include "host_util.hpp"
 
 using namespace vf;
@@ -37,14 +38,6 @@ __device__ inline double sh_half_angle(double p, double q)
 __device__ inline double sh_poly(const double *c, double u, double v)
 {
     return c[0] + c[1] * u + c[2] * v + c[3] * (u * u) + c[4] * (u * v) + c[5] * (v * v);
-}
-
-// the table's box: finite values inside the int range, else nothing
-__device__ inline bool sh_box_value(double v, int &o)
-{
-    if (!finitef(v) || v < -1.0e9 || v > 1.0e9) return false;
-    o = (int)v;
-    return true;
 }
 
 struct ShapeFrame {
@@ -89,8 +82,8 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
     const ShapeFrame fr{depth + b * P, index + b * P, h, w, k, eps};
     // the box: u, v from the table's own, the walk over its part inside the frame
     int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-    const bool box_ok = sh_box_value(row[VISTAF_CONTACT_BBOX_X0], bx0) && sh_box_value(row[VISTAF_CONTACT_BBOX_Y0], by0) &&
-                        sh_box_value(row[VISTAF_CONTACT_BBOX_X1], bx1) && sh_box_value(row[VISTAF_CONTACT_BBOX_Y1], by1);
+    const bool box_ok = box_value(row[VISTAF_CONTACT_BBOX_X0], bx0) && box_value(row[VISTAF_CONTACT_BBOX_Y0], by0) &&
+                        box_value(row[VISTAF_CONTACT_BBOX_X1], bx1) && box_value(row[VISTAF_CONTACT_BBOX_Y1], by1);
     const double xc = ((double)bx0 + (double)bx1) / 2.0, yc = ((double)by0 + (double)by1) / 2.0;
     const double hx = fmax(((double)bx1 - (double)bx0) / 2.0, 1.0), hy = fmax(((double)by1 - (double)by0) / 2.0, 1.0);
     const int x0 = bx0 < 0 ? 0 : bx0, y0 = by0 < 0 ? 0 : by0, x1 = bx1 > w - 1 ? w - 1 : bx1, y1 = by1 > h - 1 ? h - 1 : by1;

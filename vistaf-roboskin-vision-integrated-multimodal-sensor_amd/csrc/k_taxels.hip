@@ -36,8 +36,6 @@ constexpr int TX_S = VISTAF_TAXEL_FORCE_N, TX_SX = 10, TX_SY = 11;      // where
 
 struct TxSlot { int32_t taxel; int32_t part; };         // taxel < 0: idle; part = index | parts << 8
 
-__device__ inline unsigned long long tx_key(float d, unsigned p) { return ((unsigned long long)f2key(d) << 32) | (0xffffffffu - p); }
-
 struct TxAcc {
     double S = 0.0, Sx = 0.0, Sy = 0.0;
     unsigned long long key = 0;                         // largest (depth, -index); 0 is below the key of every contact pixel's
@@ -53,7 +51,7 @@ struct TxAcc {
             S += dd;
             Sx += (double)x * dd;
             Sy += (double)y * dd;
-            const unsigned long long k = tx_key(d, y * w + x);
+            const unsigned long long k = argmax_key(d, y * w + x);
             key = k > key ? k : key;
         }
     }
@@ -159,7 +157,7 @@ __global__ __launch_bounds__(64) void k_taxel_frame(const uint32_t *__restrict__
             S = row[TX_S]; Sx = row[TX_SX]; Sy = row[TX_SY];
             if (row[VISTAF_TAXEL_CONTACT_PIXELS] > 0.0) {
                 active++;
-                const unsigned long long k = tx_key((float)row[VISTAF_TAXEL_MAX_DEPTH_MM], (unsigned)t);
+                const unsigned long long k = argmax_key((float)row[VISTAF_TAXEL_MAX_DEPTH_MM], (unsigned)t);
                 peak = k > peak ? k : peak;
             }
         }

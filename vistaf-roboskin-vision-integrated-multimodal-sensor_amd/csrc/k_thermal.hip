@@ -22,6 +22,7 @@
 
 #include "../../include/vistaf_align.h"
 #include "../../include/vistaf_thermal.h"
+#include "contact_rows.hpp"
 #include "host_util.hpp"
 
 using namespace vf;
@@ -67,14 +68,6 @@ __global__ __launch_bounds__(TR_NT) void k_thermal_register(const float *__restr
     crop[(size_t)b * P + i] = t;
 }
 
-// the table's box: finite values inside the int range, else nothing (k_shape's reading)
-__device__ inline bool th_box_value(double v, int &o)
-{
-    if (!finitef(v) || v < -1.0e9 || v > 1.0e9) return false;
-    o = (int)v;
-    return true;
-}
-
 __global__ __launch_bounds__(TH_NT) void k_thermal_contacts(const float *__restrict__ temp, const float *__restrict__ depth, const int8_t *__restrict__ index,
                                                             const double *__restrict__ contacts, const int32_t *__restrict__ count,
                                                             const int32_t *__restrict__ status, float eps, int margin, int h, int w, int K,
@@ -86,62 +79,44 @@ __global__ __launch_bounds__(TH_NT) void k_thermal_contacts(const float *__restr
     const int b = blockIdx.x / K, k = blockIdx.x - b * K;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     double *out = thermal + (size_t)blockIdx.x * VISTAF_NTHERMAL;
-    int kk = count[b];
-    kk = kk < 0 ? 0 : (kk > K ? K : kk);
-    if (k >= kk || (status && status[b] != 0)) {
-        if (tid < VISTAF_NTHERMAL) out[tid] = nan64();
-        return;
-    }
+    const int kk = clamp_count(count[b], K);
+    if (nan_row(k >= kk || (status && status[b] != 0), out, VISTAF_NTHERMAL)) return;
     const double *row = contacts + (size_t)blockIdx.x * VISTAF_NCONTACT;
     const size_t P = (size_t)h * w;
     const float *tp = temp + b * P, *dp = depth + b * P;
     const int8_t *ip = index + b * P;
-    int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
-    const bool box_ok = th_box_value(row[VISTAF_CONTACT_BBOX_X0], bx0) && th_box_value(row[VISTAF_CONTACT_BBOX_Y0], by0) &&
-                        th_box_value(row[VISTAF_CONTACT_BBOX_X1], bx1) && th_box_value(row[VISTAF_CONTACT_BBOX_Y1], by1) && bx1 >= bx0 && by1 >= by0;
-    // the box and the grown box, each clipped to the frame (|b..| <= 1e9, margin <= 4096: no overflow)
-    const int x0 = bx0 < 0 ? 0 : bx0, y0 = by0 < 0 ? 0 : by0, x1 = bx1 > w - 1 ? w - 1 : bx1, y1 = by1 > h - 1 ? h - 1 : by1;
-    const int gx0 = bx0 - margin < 0 ? 0 : bx0 - margin, gy0 = by0 - margin < 0 ? 0 : by0 - margin;
-    const int gx1 = bx1 + margin > w - 1 ? w - 1 : bx1 + margin, gy1 = by1 + margin > h - 1 ? h - 1 : by1 + margin;
-    const int bw = box_ok && x1 >= x0 && y1 >= y0 ? x1 - x0 + 1 : 0, bh = bw ? y1 - y0 + 1 : 0;
-    const int gw = box_ok && gx1 >= gx0 && gy1 >= gy0 ? gx1 - gx0 + 1 : 0, gh = gw ? gy1 - gy0 + 1 : 0;
+    // the box and the grown box, each clipped to the frame (|b..| <= 1e9, margin <= 4096: no overflow).  An inverted box is no box: it must
+    // not grow into one
+    const ContactBox box(row, h, w);
+    const ContactBox grown(box.bx0 - margin, box.by0 - margin, box.bx1 + margin, box.by1 + margin, box.ok && box.bx1 >= box.bx0 && box.by1 >= box.by0, h, w);
 
     // ---- sweep 1 over the grown box: counts, sums, min / max keys
     uint32_t n = 0, nv = 0, ns = 0, kmax = 0, kmin = 0;             // kmin holds ~key: 0 = none for both
     double st = 0.0, sd = 0.0, sdt = 0.0, ss = 0.0;
-    {
-        const int total = gw * gh;                                   // <= h * w < 2^31
-        const int step_y = gw ? TH_NT / gw : 0, step_x = gw ? TH_NT - step_y * gw : 0;
-        int x = gw ? tid % gw : 0, y = gw ? tid / gw : 0;
-        for (int i = tid; i < total; i += TH_NT) {
-            const int px = gx0 + x, py = gy0 + y;
-            const size_t p = (size_t)py * w + px;
-            const int idx = ip[p];
-            const float t = tp[p];
-            const bool fin = finitef(t);
-            if (idx == k && bw && px >= x0 && px <= x1 && py >= y0 && py <= y1) {
-                float d = dp[p];
-                if (d != d) d = 0.0f;
-                if (d > eps) {
-                    n++;
-                    if (fin) {
-                        const double td = (double)t, dd = (double)d;
-                        const uint32_t key = f2key(t);
-                        nv++;
-                        st += td; sd += dd; sdt += dd * td;
-                        kmax = key > kmax ? key : kmax;
-                        kmin = ~key > kmin ? ~key : kmin;
-                    }
+    BoxWalk<TH_NT>(grown, tid).each([&](int px, int py) {
+        const size_t p = (size_t)py * w + px;
+        const int idx = ip[p];
+        const float t = tp[p];
+        const bool fin = finitef(t);
+        if (idx == k && px >= box.x0 && px <= box.x1 && py >= box.y0 && py <= box.y1) {       // no pixel passes for a box outside the frame
+            float d = dp[p];
+            if (d != d) d = 0.0f;
+            if (d > eps) {
+                n++;
+                if (fin) {
+                    const double td = (double)t, dd = (double)d;
+                    const uint32_t key = f2key(t);
+                    nv++;
+                    st += td; sd += dd; sdt += dd * td;
+                    kmax = key > kmax ? key : kmax;
+                    kmin = ~key > kmin ? ~key : kmin;
                 }
-            } else if ((idx < 0 || idx >= kk) && fin) {
-                ns++;
-                ss += (double)t;
             }
-            x += step_x;
-            y += step_y;
-            if (x >= gw) { x -= gw; y++; }
+        } else if ((idx < 0 || idx >= kk) && fin) {
+            ns++;
+            ss += (double)t;
         }
-    }
+    });
     // workgroup results: DPP tree in a wave, waves in order
     {
         const uint32_t c0 = wave_sum(n), c1 = wave_sum(nv), c2 = wave_sum(ns), c3 = wave_max_u32(kmax), c4 = wave_max_u32(kmin);
@@ -191,26 +166,18 @@ __global__ __launch_bounds__(TH_NT) void k_thermal_contacts(const float *__restr
     // ---- sweep 2 over the table's own box: squared deviations from the finished mean
     const double mean = mean_s;
     double s2 = 0.0;
-    {
-        const int total = bw * bh;                                   // nv >= 1: the box is not empty
-        const int step_y = TH_NT / bw, step_x = TH_NT - step_y * bw;
-        int x = tid % bw, y = tid / bw;
-        for (int i = tid; i < total; i += TH_NT) {
-            const size_t p = (size_t)(y0 + y) * w + (x0 + x);
-            const float t = tp[p];
-            if (ip[p] == k && finitef(t)) {
-                float d = dp[p];
-                if (d != d) d = 0.0f;
-                if (d > eps) {
-                    const double r = (double)t - mean;
-                    s2 += r * r;
-                }
+    BoxWalk<TH_NT>(box, tid).each([&](int px, int py) {
+        const size_t p = (size_t)py * w + px;
+        const float t = tp[p];
+        if (ip[p] == k && finitef(t)) {
+            float d = dp[p];
+            if (d != d) d = 0.0f;
+            if (d > eps) {
+                const double r = (double)t - mean;
+                s2 += r * r;
             }
-            x += step_x;
-            y += step_y;
-            if (x >= bw) { x -= bw; y++; }
         }
-    }
+    });
     s2 = wave_sum(s2);
     if (lane == 0) wf[wid][0] = s2;                                  // every read of wf[][0] lies before the barrier above
     __syncthreads();
@@ -233,8 +200,7 @@ __global__ __launch_bounds__(TF_NT) void k_thermal_frame(const float *__restrict
         if (tid < VISTAF_NTHERMALFRAME) out[tid] = nan64();
         return;
     }
-    int kk = count[b];
-    kk = kk < 0 ? 0 : (kk > K ? K : kk);
+    const int kk = clamp_count(count[b], K);
     const size_t P = (size_t)h * w;
     const float *tp = temp + b * P, *dp = depth + b * P;
     const int8_t *ip = index + b * P;

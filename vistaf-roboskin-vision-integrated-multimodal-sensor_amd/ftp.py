@@ -139,6 +139,7 @@ class FtpSensor:
         own reference frame; `frame_shape` = (h, w) is needed instead)."""
         self._lib = _lib.load()
         self._h = ctypes.c_void_p()
+        self._readouts: Dict[str, Tuple[tuple, Any]] = {}          # the live read-outs: name -> (the parameters it was built with, the object)
         if not torch.cuda.is_available():
             raise RuntimeError("FtpSensor needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
         self.device = torch.device(device)
@@ -202,30 +203,8 @@ class FtpSensor:
         return _lib.FMT_BGR_F16 if t.dim() == 4 else _lib.FMT_GRAY_F16
 
     def close(self):
-        if getattr(self, "_tracker", None) is not None:
-            self._tracker.close()
-            self._tracker = None
-        if getattr(self, "_shapes", None) is not None:
-            self._shapes.close()
-            self._shapes = None
-        if getattr(self, "_taxels", None) is not None:
-            self._taxels.close()
-            self._taxels = None
-        if getattr(self, "_thermal", None) is not None:
-            self._thermal.close()
-            self._thermal = None
-        if getattr(self, "_temporal", None) is not None:
-            self._temporal.close()
-            self._temporal = None
-        if getattr(self, "_cloud", None) is not None:
-            self._cloud.close()
-            self._cloud = None
-        if getattr(self, "_motion", None) is not None:
-            self._motion.close()
-            self._motion = None
-        if getattr(self, "_pressure", None) is not None:
-            self._pressure.close()
-            self._pressure = None
+        for name in list(getattr(self, "_readouts", {})):
+            self._readouts.pop(name)[1].close()
         if getattr(self, "_h", None) is not None and self._h.value:
             self._lib.vistaf_ftp_destroy(self._h)
             self._h = ctypes.c_void_p()
@@ -235,6 +214,53 @@ class FtpSensor:
             self.close()
         except Exception:
             pass
+
+    # -- the session's read-outs ------------------------------------------------------------------
+    def _matching(self, name: str, key: tuple, reset: Optional[bool] = None, differ: str = ""):
+        """The live read-out `name` if it was built with the parameters `key`, else None.  One built with other parameters is closed:
+        always when reset is None (the read-out is rebuilt silently), only with reset=True otherwise, ValueError(differ) without."""
+        live = self._readouts.get(name)
+        if live is None or live[0] == key:
+            return live and live[1]
+        if reset is False:
+            raise ValueError(differ)
+        self._readouts.pop(name)[1].close()
+        return None
+
+    def _keep(self, name: str, key: tuple, readout):
+        self._readouts[name] = (key, readout)
+        return readout
+
+    def _live(self, name: str):
+        live = getattr(self, "_readouts", {}).get(name)
+        return live and live[1]
+
+    _tracker = property(lambda self: self._live("tracker"))
+    _shapes = property(lambda self: self._live("shapes"))
+    _taxels = property(lambda self: self._live("taxels"))
+    _thermal = property(lambda self: self._live("thermal"))
+    _temporal = property(lambda self: self._live("temporal"))
+    _cloud = property(lambda self: self._live("cloud"))
+    _motion = property(lambda self: self._live("motion"))
+    _pressure = property(lambda self: self._live("pressure"))
+
+    def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
+        last = getattr(self, "_last_out", None)
+        if last is None:
+            raise RuntimeError(f"{who}() needs a previous {what}")
+        return last
+
+    def _scalar(self, name: str) -> torch.Tensor:
+        """the column `name` of the last predict's scalars"""
+        return self._last_out["scalars"][:, SCALAR_NAMES.index(name)]
+
+    def _new_out(self, b: int) -> Dict[str, torch.Tensor]:
+        return {
+            "height_map_mm": torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device),
+            "output_reliable": torch.empty((b, self.h, self.w), dtype=torch.uint8, device=self.device),
+            "scalars": torch.empty((b, _lib.NSCALARS), dtype=torch.float64, device=self.device),
+            "status": torch.empty((b,), dtype=torch.int32, device=self.device),
+        }
 
     # -- batched device API ------------------------------------------------------------------------
     def predict_batch(self, frames, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
@@ -247,12 +273,7 @@ class FtpSensor:
         if b > self.max_batch:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
-            out = {
-                "height_map_mm": torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device),
-                "output_reliable": torch.empty((b, self.h, self.w), dtype=torch.uint8, device=self.device),
-                "scalars": torch.empty((b, _lib.NSCALARS), dtype=torch.float64, device=self.device),
-                "status": torch.empty((b,), dtype=torch.int32, device=self.device),
-            }
+            out = self._new_out(b)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_ftp_predict_batch(
                 self._h, t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(), out["output_reliable"].data_ptr(),
@@ -273,12 +294,7 @@ class FtpSensor:
         if b > self.max_batch:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
-            out = {
-                "height_map_mm": torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device),
-                "output_reliable": torch.empty((b, self.h, self.w), dtype=torch.uint8, device=self.device),
-                "scalars": torch.empty((b, _lib.NSCALARS), dtype=torch.float64, device=self.device),
-                "status": torch.empty((b,), dtype=torch.int32, device=self.device),
-            }
+            out = self._new_out(b)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_ftp_predict_pairs(
                 self._h, r.data_ptr(), t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(), out["output_reliable"].data_ptr(),
@@ -299,9 +315,7 @@ class FtpSensor:
         depth, descending.  Returns device tensors: contacts [B,K,16] f64 (fields CONTACT_NAMES, unused rows NaN), count [B] i32 (all
         contacts of the frame, also when more than K) and, with index_plane, contact_index [B,h,w] i8 (row of the pixel's contact, else -1).
         `force_N` of a row is the force curve at that contact's own volume; the curve is not linear, the rows do not add up to the frame's."""
-        last = getattr(self, "_last_out", None)
-        if last is None:
-            raise RuntimeError("contacts() needs a previous predict_batch / predict_pairs")
+        last = self._last("contacts")
         b, k = int(last["status"].shape[0]), int(max_contacts)
         if not 1 <= k <= _lib.MAX_CONTACTS:
             raise ValueError(f"max_contacts must be 1..{_lib.MAX_CONTACTS}")
@@ -324,15 +338,10 @@ class FtpSensor:
         reset=True forgets the frames seen so far and restarts ids at 0; max_contacts and gate_px can only change together with it."""
         from .tracks import ContactTracker
         k, gate = int(max_contacts), float(gate_px)
-        tr = getattr(self, "_tracker", None)
-        if tr is not None and (tr.max_contacts != k or tr.gate_px != gate):
-            if not reset:
-                raise ValueError("max_contacts / gate_px differ from the running tracker's: pass reset=True to start over with them")
-            tr.close()
-            tr = self._tracker = None
+        tr = self._matching("tracker", (k, gate), bool(reset), "max_contacts / gate_px differ from the running tracker's: pass reset=True to start over with them")
         out = self.contacts(k, index_plane=True)
         if tr is None:
-            tr = self._tracker = ContactTracker(self.h, self.w, self.max_batch, k, gate, device=self.device)
+            tr = self._keep("tracker", (k, gate), ContactTracker(self.h, self.w, self.max_batch, k, gate, device=self.device))
         elif reset:
             tr.reset()
         out.update(tr.update(out["contact_index"], out["contacts"], out["count"]))
@@ -346,16 +355,12 @@ class FtpSensor:
         ellipse, boundary pixels, apex, curvatures and radii of the fitted cap, residual)."""
         from .shapes import ContactShapes
         k, frac = int(max_contacts), float(fit_min_fraction)
-        sh = getattr(self, "_shapes", None)
-        if sh is not None and (sh.max_contacts != k or sh.fit_min_fraction != frac):
-            sh.close()
-            sh = self._shapes = None
+        sh = self._matching("shapes", (k, frac))
         out = self.contacts(k, index_plane=True)
         if sh is None:
-            sh = self._shapes = ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device)
-        last = self._last_out
-        out["shapes"] = sh.measure(last["height_map_mm"], out["contact_index"], out["contacts"], out["count"],
-                                   last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm)
+            sh = self._keep("shapes", (k, frac), ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device))
+        out["shapes"] = sh.measure(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
+                                   self.config.depth_eps_mm)
         return out
 
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
@@ -365,20 +370,14 @@ class FtpSensor:
         created on first use and rebuilt when another layout object is given.  Returns device tensors: taxels [B,T,12] f64 (fields
         TAXEL_NAMES) and frame [B,8] f64 (fields TAXEL_FRAME_NAMES); a frame whose status is not 0 has NaN rows."""
         from .taxels import TaxelReadout
-        last = getattr(self, "_last_out", None)
-        if last is None:
-            raise RuntimeError("taxels() needs a previous predict_batch / predict_pairs")
+        last = self._last("taxels")
         if layout.shape != (self.h, self.w):
             raise ValueError(f"the layout is {layout.shape[0]} x {layout.shape[1]}, the session's frames are {self.h} x {self.w}")
-        tx = getattr(self, "_taxels", None)
-        if tx is not None and tx.layout is not layout:
-            tx.close()
-            tx = self._taxels = None
+        tx = self._matching("taxels", (layout,))                  # the layout by identity: it defines no equality
         if tx is None:
-            tx = self._taxels = TaxelReadout(layout, self.max_batch, device=self.device)
-        sc = last["scalars"]
-        return tx.measure(last["height_map_mm"], sc[:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
-                          force_N=sc[:, SCALAR_NAMES.index("force_N")], status=last["status"])
+            tx = self._keep("taxels", (layout,), TaxelReadout(layout, self.max_batch, device=self.device))
+        return tx.measure(last["height_map_mm"], self._scalar("mm_per_px"), self.config.depth_eps_mm, force_N=self._scalar("force_N"),
+                          status=last["status"])
 
     def thermal(self, temperature_crop, max_contacts: int = 8, surround_margin_px: int = 8) -> Dict[str, torch.Tensor]:
         """Per-contact table of the last predict plus the temperature of every contact (thermal.ThermalReadout; an extension, the reference has
@@ -388,14 +387,11 @@ class FtpSensor:
         Returns the contacts dict plus thermal [B,K,16] f64 (fields THERMAL_NAMES) and thermal_frame [B,8] f64 (fields THERMAL_FRAME_NAMES)."""
         from .thermal import ThermalReadout
         k, margin = int(max_contacts), int(surround_margin_px)
-        th = getattr(self, "_thermal", None)
-        if th is not None and (th.max_contacts != k or th.surround_margin_px != margin):
-            th.close()
-            th = self._thermal = None
+        th = self._matching("thermal", (k, margin))
         out = self.contacts(k, index_plane=True)
         if th is None:                                     # measure needs the crop's size only; the photograph's is register's business
-            th = self._thermal = ThermalReadout(self.h, self.w, max(self.h, 2), max(self.w, 2), (0, 0), False, self.max_batch, k, margin,
-                                                device=self.device)
+            th = self._keep("thermal", (k, margin), ThermalReadout(self.h, self.w, max(self.h, 2), max(self.w, 2), (0, 0), False, self.max_batch, k,
+                                                                  margin, device=self.device))
         last = self._last_out
         r = th.measure(temperature_crop, last["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self.config.depth_eps_mm,
                        status=last["status"])
@@ -411,21 +407,15 @@ class FtpSensor:
         with planes=True, filtered [B,h,w] f32 and touch [B,h,w] u8.  reset=True forgets the stream; alpha, on_mm, off_mm and
         frame_period_s can only change together with it."""
         from .temporal import TemporalReadout
-        last = getattr(self, "_last_out", None)
-        if last is None:
-            raise RuntimeError("temporal() needs a previous predict_batch / predict_pairs")
+        last = self._last("temporal")
         prm = (float(alpha), float(on_mm), float(off_mm), float(frame_period_s))
-        tp = getattr(self, "_temporal", None)
-        if tp is not None and (tp.alpha, tp.on_mm, tp.off_mm, tp.frame_period_s) != prm:
-            if not reset:
-                raise ValueError("alpha / on_mm / off_mm / frame_period_s differ from the running read-out's: pass reset=True to start over with them")
-            tp.close()
-            tp = self._temporal = None
+        tp = self._matching("temporal", prm, bool(reset),
+                            "alpha / on_mm / off_mm / frame_period_s differ from the running read-out's: pass reset=True to start over with them")
         if tp is None:
-            tp = self._temporal = TemporalReadout(self.h, self.w, self.max_batch, *prm, device=self.device)
+            tp = self._keep("temporal", prm, TemporalReadout(self.h, self.w, self.max_batch, *prm, device=self.device))
         elif reset:
             tp.reset()
-        return tp.update(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], status=last["status"], planes=planes)
+        return tp.update(last["height_map_mm"], self._scalar("mm_per_px"), status=last["status"], planes=planes)
 
     def cloud(self, max_points: Optional[int] = None, stride: int = 1, labels: bool = False, max_contacts: int = 8) -> Dict[str, torch.Tensor]:
         """Point-cloud read-out of the last predict (cloud.CloudReadout; an extension, the reference has no counterpart): the surface pixels
@@ -439,22 +429,15 @@ class FtpSensor:
         measurement.  More points than max_points is reported (offsets beyond max_points, points_written below points, `trim`'s overflow),
         not raised."""
         from .cloud import CloudReadout
-        last = getattr(self, "_last_out", None)
-        if last is None:
-            raise RuntimeError("cloud() needs a previous predict_batch / predict_pairs")
+        last = self._last("cloud")
         stride = int(stride)
         if max_points is None:
             lattice = ((self.h + stride - 1) // stride) * ((self.w + stride - 1) // stride) if stride >= 1 else 1
             max_points = max(lattice, (lattice * self.max_batch + 7) // 8)
-        cl = getattr(self, "_cloud", None)
-        if cl is not None and (cl.max_points, cl.stride) != (int(max_points), stride):
-            cl.close()
-            cl = self._cloud = None
-        if cl is None:
-            cl = self._cloud = CloudReadout(self.h, self.w, self.max_batch, int(max_points), stride, device=self.device)
+        key = (int(max_points), stride)
+        cl = self._matching("cloud", key) or self._keep("cloud", key, CloudReadout(self.h, self.w, self.max_batch, *key, device=self.device))
         index = self.contacts(int(max_contacts), index_plane=True)["contact_index"] if labels else None
-        return cl.measure(last["height_map_mm"], last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm,
-                          status=last["status"], contact_index=index)
+        return cl.measure(last["height_map_mm"], self._scalar("mm_per_px"), self.config.depth_eps_mm, status=last["status"], contact_index=index)
 
     def motion(self, max_contacts: int = 8, gate_px: float = 0.0, reset: bool = False, iterations: int = 8, tol_px: float = 1e-3,
                min_pixels: int = 16, init_from_centroid: bool = True) -> Dict[str, torch.Tensor]:
@@ -468,20 +451,14 @@ class FtpSensor:
         from .motion import ContactMotion
         k = int(max_contacts)
         par = (k, int(iterations), float(tol_px), int(min_pixels), bool(init_from_centroid))
-        mo = getattr(self, "_motion", None)
-        if mo is not None and (mo.max_contacts, mo.iterations, mo.tol_px, mo.min_pixels, mo.init_from_centroid) != par:
-            if not reset:
-                raise ValueError("the arguments differ from the running motion read-out's: pass reset=True to start over with them")
-            mo.close()
-            mo = self._motion = None
+        mo = self._matching("motion", par, bool(reset), "the arguments differ from the running motion read-out's: pass reset=True to start over with them")
         out = self.track(k, gate_px, reset)
         if mo is None:
-            mo = self._motion = ContactMotion(self.h, self.w, self.max_batch, *par, device=self.device)
+            mo = self._keep("motion", par, ContactMotion(self.h, self.w, self.max_batch, *par, device=self.device))
         elif reset:
             mo.reset()
-        last = self._last_out
-        out.update(mo.update(last["height_map_mm"], out["contact_index"], out["contacts"], out["count"], out["tracks"],
-                             last["scalars"][:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm))
+        out.update(mo.update(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], out["tracks"],
+                             self._scalar("mm_per_px"), self.config.depth_eps_mm))
         return out
 
     def pressure(self, max_contacts: int = 8, pad_px: int = 32, E_mpa: float = 1.0, nu: float = 0.45, thickness_mm: float = math.inf,
@@ -496,19 +473,13 @@ class FtpSensor:
         from .pressure import PressureReadout
         k = int(max_contacts)
         par = (k, int(pad_px), float(E_mpa), float(nu), float(thickness_mm))
-        pr = getattr(self, "_pressure", None)
-        if pr is not None and (pr.max_contacts, pr.pad_px, pr.E_mpa, pr.nu, pr.thickness_mm) != par:
-            if not reset:
-                raise ValueError("the arguments differ from the running pressure read-out's: pass reset=True to start over with them")
-            pr.close()
-            pr = self._pressure = None
+        pr = self._matching("pressure", par, bool(reset), "the arguments differ from the running pressure read-out's: pass reset=True to start over with them")
         out = self.contacts(k, index_plane=True)
         if pr is None:
-            pr = self._pressure = PressureReadout(self.h, self.w, self.max_batch, *par, device=self.device)
+            pr = self._keep("pressure", par, PressureReadout(self.h, self.w, self.max_batch, *par, device=self.device))
         last = self._last_out
-        sc = last["scalars"]
-        r = pr.measure(last["height_map_mm"], sc[:, SCALAR_NAMES.index("mm_per_px")], self.config.depth_eps_mm, contact_index=out["contact_index"],
-                       contacts=out["contacts"], count=out["count"], force_N=sc[:, SCALAR_NAMES.index("force_N")], status=last["status"])
+        r = pr.measure(last["height_map_mm"], self._scalar("mm_per_px"), self.config.depth_eps_mm, contact_index=out["contact_index"],
+                       contacts=out["contacts"], count=out["count"], force_N=self._scalar("force_N"), status=last["status"])
         out["pressure_kpa"], out["pressure"], out["pressure_frame"] = r["pressure_kpa"], r["rows"], r["frame"]
         return out
 
@@ -533,9 +504,7 @@ class FtpSensor:
     def masks(self, index: int = 0) -> Dict[str, np.ndarray]:
         """The seven boolean crop masks of frame `index` of the last predict_batch, under the names the reference stores
         them with in height_map_bundle.npz (Code/shape_ftp.py:1898-1906)."""
-        last = getattr(self, "_last_out", None)
-        if last is None:
-            raise RuntimeError("masks() needs a previous predict_batch")
+        last = self._last("masks", "predict_batch")
         batch = int(last["status"].shape[0])
 
         def plane(name):
@@ -648,7 +617,7 @@ class FtpSensor:
                 res["motion_frame"] = motion_frame_record(mo["motion_frame"][0].cpu().numpy())
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table
-            running = getattr(self, "_pressure", None)          # without contacts=K the table's size is nobody's concern: keep the running one
+            running = self._pressure                            # without contacts=K the table's size is nobody's concern: keep the running one
             pr = self.pressure(**dict(pressure, max_contacts=int(contacts) if contacts is not None else (running.max_contacts if running else 8)))
             res["pressure_kpa"] = pr["pressure_kpa"][0].cpu().numpy()
             res["pressure_frame"] = pressure_frame_record(pr["pressure_frame"][0].cpu().numpy())

@@ -12,11 +12,12 @@ from __future__ import annotations
 
 import ctypes
 import math
-from typing import Dict, Optional
+from typing import Dict
 
 import torch
 
 from . import _lib
+from ._readout import Readout, ptr
 
 PRESSURE_NAMES = _lib.PRESSURE_NAMES
 PRESSURE_FRAME_NAMES = _lib.PRESSURE_FRAME_NAMES
@@ -35,21 +36,18 @@ def _check_model(max_contacts: int, pad_px: int, E_mpa: float, nu: float, thickn
         raise ValueError("thickness_mm must be > 0 or math.inf")
 
 
-class PressureReadout:
+class PressureReadout(Readout):
     """A pressure read-out for h x w planes, at most `max_batch` frames per call, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` that feeds it; 0: the plane and the frame row only).  The depth plane is zero-filled to (h + pad_px) x (w + pad_px)
     before the transform, which is what keeps the periodic images of a contact away from it."""
+    _destroy = "vistaf_pressure_destroy"
 
     def __init__(self, h: int, w: int, max_batch: int, max_contacts: int = 8, pad_px: int = 32, E_mpa: float = 1.0, nu: float = 0.45,
                  thickness_mm: float = math.inf, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.h, self.w, self.max_batch, self.max_contacts, self.pad_px = int(h), int(w), int(max_batch), int(max_contacts), int(pad_px)
         self.E_mpa, self.nu, self.thickness_mm = float(E_mpa), float(nu), float(thickness_mm)
         _check_model(self.max_contacts, self.pad_px, self.E_mpa, self.nu, self.thickness_mm)
-        if not torch.cuda.is_available():
-            raise RuntimeError("PressureReadout needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
+        self._open(device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_pressure_create(self.h, self.w, self.max_batch, self.max_contacts, self.pad_px, self.E_mpa, self.nu,
                                                         self.thickness_mm, ctypes.byref(self._h)))
@@ -61,15 +59,11 @@ class PressureReadout:
         status [B] int32 are optional (device or host).  Returns device tensors: pressure_kpa [B,h,w] f32, frame [B,12] f64 (fields
         PRESSURE_FRAME_NAMES) and, with max_contacts > 0, rows [B,K,16] f64 (fields PRESSURE_NAMES, unused rows and fields NaN).  A frame
         whose status is not 0 has a zero plane and NaN rows."""
-        dep = torch.as_tensor(depth_mm).to(self.device, torch.float32).contiguous()
-        mpp = torch.as_tensor(mm_per_px).to(self.device, torch.float64).contiguous()
-        if dep.dim() != 3 or tuple(dep.shape[1:]) != (self.h, self.w):
-            raise ValueError(f"depth_mm must be [B,{self.h},{self.w}]")
+        dep = self._t(depth_mm, torch.float32, (None, self.h, self.w), f"depth_mm must be [B,{self.h},{self.w}]")
         b, k = int(dep.shape[0]), self.max_contacts
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
-        if tuple(mpp.shape) != (b,):
-            raise ValueError("mm_per_px must be [B] for the B frames of depth_mm")
+        mpp = self._t(mm_per_px, torch.float64, (b,), "mm_per_px must be [B] for the B frames of depth_mm")
         if not math.isfinite(float(depth_eps_mm)):
             raise ValueError("depth_eps_mm must be finite")
         given = [a is not None for a in (contact_index, contacts, count)]
@@ -77,35 +71,17 @@ class PressureReadout:
             raise ValueError("contact_index, contacts and count go together, and with max_contacts > 0 only")
         idx = tab = cnt = None
         if k > 0:
-            idx = torch.as_tensor(contact_index).to(self.device, torch.int8).contiguous()
-            tab = torch.as_tensor(contacts).to(self.device, torch.float64).contiguous()
-            cnt = torch.as_tensor(count).to(self.device, torch.int32).contiguous()
-            if tuple(idx.shape) != tuple(dep.shape) or tuple(tab.shape) != (b, k, _lib.NCONTACT) or tuple(cnt.shape) != (b,):
-                raise ValueError(f"contact_index must be [B,{self.h},{self.w}], contacts [B,{k},{_lib.NCONTACT}] and count [B]")
-        frc = None if force_N is None else torch.as_tensor(force_N).to(self.device, torch.float64).contiguous()
-        sta = None if status is None else torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        if (frc is not None and tuple(frc.shape) != (b,)) or (sta is not None and tuple(sta.shape) != (b,)):
-            raise ValueError("force_N and status must be [B] for the B frames of depth_mm")
+            msg = f"contact_index must be [B,{self.h},{self.w}], contacts [B,{k},{_lib.NCONTACT}] and count [B]"
+            idx, tab = self._t(contact_index, torch.int8, dep.shape, msg), self._t(contacts, torch.float64, (b, k, _lib.NCONTACT), msg)
+            cnt = self._t(count, torch.int32, (b,), msg)
+        msg = "force_N and status must be [B] for the B frames of depth_mm"
+        frc, sta = self._t(force_N, torch.float64, (b,), msg), self._t(status, torch.int32, (b,), msg)
         out = {"pressure_kpa": torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device),
                "frame": torch.empty((b, _lib.NPRESSUREFRAME), dtype=torch.float64, device=self.device)}
         if k > 0:
             out["rows"] = torch.empty((b, k, _lib.NPRESSURE), dtype=torch.float64, device=self.device)
-
-        def ptr(t: Optional[torch.Tensor]):
-            return None if t is None else t.data_ptr()
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_pressure_measure(self._h, dep.data_ptr(), ptr(idx), ptr(tab), ptr(cnt), mpp.data_ptr(), ptr(frc), ptr(sta),
                                                          float(depth_eps_mm), b, out["pressure_kpa"].data_ptr(), ptr(out.get("rows")),
-                                                         out["frame"].data_ptr(), int(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                         out["frame"].data_ptr(), self._stream()))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_pressure_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

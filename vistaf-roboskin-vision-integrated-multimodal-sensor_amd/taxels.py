@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._readout import Readout, ptr
 
 TAXEL_NAMES = _lib.TAXEL_NAMES
 TAXEL_FRAME_NAMES = _lib.TAXEL_FRAME_NAMES
@@ -105,17 +106,16 @@ def from_map(array, origin=None, n_taxels: Optional[int] = None, names=None) -> 
     return TaxelLayout(np.where(none, NONE, a).astype(np.uint16), n_taxels, origin if origin is not None else ((w - 1) / 2.0, (h - 1) / 2.0), names)
 
 
-class TaxelReadout:
+class TaxelReadout(Readout):
     """A taxel read-out for planes of the layout's size, at most `max_batch` frames per call.  The layout is inverted here, on the host;
     `layout_info` needs no device, `measure` does."""
+    _destroy = "vistaf_taxel_destroy"
 
     def __init__(self, layout: TaxelLayout, max_batch: int, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.layout, self.max_batch = layout, int(max_batch)
         self.h, self.w = layout.shape
         self.n_taxels = layout.n_taxels
-        self.device = torch.device(device)
+        self._open(device, need_device=False)
         _lib.check(self._lib.vistaf_taxel_create(self.h, self.w, self.max_batch, layout.map.ctypes.data, self.n_taxels, layout.origin[0],
                                                  layout.origin[1], ctypes.byref(self._h)))
 
@@ -129,17 +129,11 @@ class TaxelReadout:
         """depth_mm [B,h,w] float32 (the height map of a predict), mm_per_px [B] float64, force_N [B] float64 or None (forces, pressures and
         moments are then NaN), status [B] int32 or None (every frame OK; a frame whose status is not 0 gets NaN rows), device or host.
         Returns the device tensors {"taxels": [B,T,12] f64 (fields TAXEL_NAMES), "frame": [B,8] f64 (fields TAXEL_FRAME_NAMES)}."""
-        if not torch.cuda.is_available():
-            raise RuntimeError("TaxelReadout.measure needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        dep = torch.as_tensor(depth_mm).to(self.device, torch.float32).contiguous()
-        mpp = torch.as_tensor(mm_per_px).to(self.device, torch.float64).contiguous()
-        if dep.dim() != 3 or tuple(dep.shape[1:]) != (self.h, self.w):
-            raise ValueError(f"depth_mm must be [B,{self.h},{self.w}]")
+        self._need_device("measure")
+        dep = self._t(depth_mm, torch.float32, (None, self.h, self.w), f"depth_mm must be [B,{self.h},{self.w}]")
         b = int(dep.shape[0])
-        frc = None if force_N is None else torch.as_tensor(force_N).to(self.device, torch.float64).contiguous()
-        sta = None if status is None else torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        if tuple(mpp.shape) != (b,) or (frc is not None and tuple(frc.shape) != (b,)) or (sta is not None and tuple(sta.shape) != (b,)):
-            raise ValueError("mm_per_px, force_N and status must be [B] for the B frames of depth_mm")
+        msg = "mm_per_px, force_N and status must be [B] for the B frames of depth_mm"
+        mpp, frc, sta = self._t(mm_per_px, torch.float64, (b,), msg), self._t(force_N, torch.float64, (b,), msg), self._t(status, torch.int32, (b,), msg)
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         if not math.isfinite(float(depth_eps_mm)):
@@ -147,19 +141,6 @@ class TaxelReadout:
         out = {"taxels": torch.empty((b, self.n_taxels, _lib.NTAXEL), dtype=torch.float64, device=self.device),
                "frame": torch.empty((b, _lib.NTAXELFRAME), dtype=torch.float64, device=self.device)}
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_taxel_measure(self._h, dep.data_ptr(), mpp.data_ptr(), frc.data_ptr() if frc is not None else None,
-                                                      sta.data_ptr() if sta is not None else None, float(depth_eps_mm), b,
-                                                      out["taxels"].data_ptr(), out["frame"].data_ptr(),
-                                                      int(torch.cuda.current_stream(self.device).cuda_stream)))
+            _lib.check(self._lib.vistaf_taxel_measure(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(frc), ptr(sta), float(depth_eps_mm), b,
+                                                      out["taxels"].data_ptr(), out["frame"].data_ptr(), self._stream()))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_taxel_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

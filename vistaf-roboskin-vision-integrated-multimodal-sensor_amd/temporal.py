@@ -15,29 +15,25 @@ from typing import Dict
 import torch
 
 from . import _lib
+from ._readout import Readout, ptr
 
 TEMPORAL_NAMES = _lib.TEMPORAL_NAMES
 TEMPORAL_EVENTS = _lib.TEMPORAL_EVENTS
 
 
-class TemporalReadout:
+class TemporalReadout(Readout):
     """A temporal read-out for h x w planes, at most `max_batch` frames per update.  alpha in (0, 1] is the filter's weight of the new
     frame, on_mm > off_mm >= 0 the thresholds of the touch bit (each rounded once to float32), frame_period_s > 0 the fixed time between
     frames.  Frames of one update are consecutive in time, and frame 0 of an update follows the last frame of the update before it: the
     read-out keeps five state planes on the device until `reset()`.  Creating it needs no device, `update` and `state` do."""
+    _destroy = "vistaf_temporal_destroy"
 
     def __init__(self, h: int, w: int, max_batch: int, alpha: float, on_mm: float, off_mm: float, frame_period_s: float, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.h, self.w, self.max_batch = int(h), int(w), int(max_batch)
         self.alpha, self.on_mm, self.off_mm, self.frame_period_s = float(alpha), float(on_mm), float(off_mm), float(frame_period_s)
-        self.device = torch.device(device)
+        self._open(device, need_device=False)
         _lib.check(self._lib.vistaf_temporal_create(self.h, self.w, self.max_batch, self.alpha, self.on_mm, self.off_mm, self.frame_period_s,
                                                     ctypes.byref(self._h)))
-
-    def _need_device(self, what: str):
-        if not torch.cuda.is_available():
-            raise RuntimeError(f"TemporalReadout.{what} needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
 
     def update(self, depth, mm_per_px, status=None, planes: bool = False) -> Dict[str, torch.Tensor]:
         """depth [B,h,w] float32 (the height map of a predict), mm_per_px [B] float64, status [B] int32 or None (every frame OK; a frame
@@ -45,14 +41,10 @@ class TemporalReadout:
         tensor {"frames": [B,16] f64 (fields TEMPORAL_NAMES)} and, with planes=True, "filtered" [B,h,w] f32 and "touch" [B,h,w] u8, the
         state after every frame."""
         self._need_device("update")
-        dep = torch.as_tensor(depth).to(self.device, torch.float32).contiguous()
-        mpp = torch.as_tensor(mm_per_px).to(self.device, torch.float64).contiguous()
-        if dep.dim() != 3 or tuple(dep.shape[1:]) != (self.h, self.w):
-            raise ValueError(f"depth must be [B,{self.h},{self.w}]")
+        dep = self._t(depth, torch.float32, (None, self.h, self.w), f"depth must be [B,{self.h},{self.w}]")
         b = int(dep.shape[0])
-        sta = None if status is None else torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-        if tuple(mpp.shape) != (b,) or (sta is not None and tuple(sta.shape) != (b,)):
-            raise ValueError("mm_per_px and status must be [B] for the B frames of depth")
+        msg = "mm_per_px and status must be [B] for the B frames of depth"
+        mpp, sta = self._t(mm_per_px, torch.float64, (b,), msg), self._t(status, torch.int32, (b,), msg)
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         out = {"frames": torch.empty((b, _lib.NTEMPORAL), dtype=torch.float64, device=self.device)}
@@ -60,10 +52,9 @@ class TemporalReadout:
             out["filtered"] = torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device)
             out["touch"] = torch.empty((b, self.h, self.w), dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temporal_update(self._h, dep.data_ptr(), mpp.data_ptr(), sta.data_ptr() if sta is not None else None, b,
+            _lib.check(self._lib.vistaf_temporal_update(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), b,
                                                         out["frames"].data_ptr(), out["filtered"].data_ptr() if planes else None,
-                                                        out["touch"].data_ptr() if planes else None,
-                                                        int(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                        out["touch"].data_ptr() if planes else None, self._stream()))
         return out
 
     def state(self) -> Dict[str, torch.Tensor]:
@@ -77,21 +68,9 @@ class TemporalReadout:
                "hold": torch.empty((self.h, self.w), dtype=torch.float32, device=self.device)}
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_temporal_state(self._h, out["filt"].data_ptr(), out["rate"].data_ptr(), out["touch"].data_ptr(),
-                                                       out["dwell"].data_ptr(), out["hold"].data_ptr(),
-                                                       int(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                       out["dwell"].data_ptr(), out["hold"].data_ptr(), self._stream()))
         return out
 
     def reset(self):
         """forget the stream: the next update starts from an untouched, unprimed state"""
         _lib.check(self._lib.vistaf_temporal_reset(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_temporal_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

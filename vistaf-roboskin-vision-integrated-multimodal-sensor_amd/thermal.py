@@ -15,20 +15,20 @@ import math
 import torch
 
 from . import _lib
+from ._readout import Readout, ptr
 
 THERMAL_NAMES = _lib.THERMAL_NAMES
 THERMAL_FRAME_NAMES = _lib.THERMAL_FRAME_NAMES
 
 
-class ThermalReadout:
+class ThermalReadout(Readout):
     """A thermal read-out for h x w crops of H x W photographs cropped at `crop_origin` = (x1, y1), at most `max_batch` frames per call,
     tables of `max_contacts` rows (the K of the `FtpSensor.contacts` call that feeds it).  `apply_global_shift` is the aligner's flag: whether
     the recorded shift was applied to the photograph.  The surround of a contact is its box grown by `surround_margin_px`."""
+    _destroy = "vistaf_thermal_destroy"
 
     def __init__(self, h: int, w: int, H: int, W: int, crop_origin=(0, 0), apply_global_shift: bool = True, max_batch: int = 1,
                  max_contacts: int = 8, surround_margin_px: int = 8, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.h, self.w, self.H, self.W = int(h), int(w), int(H), int(W)
         self.crop_origin = (int(crop_origin[0]), int(crop_origin[1]))
         self.apply_global_shift = bool(apply_global_shift)
@@ -37,9 +37,7 @@ class ThermalReadout:
             raise ValueError(f"max_contacts must be 1..{_lib.MAX_CONTACTS}")
         if not 0 <= self.surround_margin_px <= 4096:
             raise ValueError("surround_margin_px must be 0..4096")
-        if not torch.cuda.is_available():
-            raise RuntimeError("ThermalReadout needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
+        self._open(device)
         _lib.check(self._lib.vistaf_thermal_create(self.h, self.w, self.H, self.W, *self.crop_origin, int(self.apply_global_shift), self.max_batch,
                                                    self.max_contacts, self.surround_margin_px, ctypes.byref(self._h)))
 
@@ -49,9 +47,6 @@ class ThermalReadout:
         return cls(*aligner.crop_shape, aligner.H, aligner.W, aligner.crop_box[:2], aligner.apply_global_shift,
                    aligner.max_batch if max_batch is None else max_batch, max_contacts, surround_margin_px, device=aligner.device)
 
-    def _stream(self) -> int:
-        return int(torch.cuda.current_stream(self.device).cuda_stream)
-
     def register(self, temperature_map_C, align_info=None) -> torch.Tensor:
         """temperature_map_C [B,H,W] (or [H,W]) float32 in the photograph's frame, NaN where it has no value (`TempSensor.predict`);
         align_info [B,12] float64 as `FtpAligner.align` returns it under "info" (device or host), or None: no shift, identity warp.
@@ -59,20 +54,14 @@ class ThermalReadout:
         t = torch.as_tensor(temperature_map_C)
         if t.dim() == 2:
             t = t[None]
-        t = t.to(self.device, torch.float32).contiguous()
-        if t.dim() != 3 or tuple(t.shape[1:]) != (self.H, self.W):
-            raise ValueError(f"temperature_map_C must be [B,{self.H},{self.W}]")
+        t = self._t(t, torch.float32, (None, self.H, self.W), f"temperature_map_C must be [B,{self.H},{self.W}]")
         b = int(t.shape[0])
-        info = None
-        if align_info is not None:
-            info = torch.as_tensor(align_info).to(self.device, torch.float64).contiguous()
-            if tuple(info.shape) != (b, _lib.ALIGN_NINFO):
-                raise ValueError(f"align_info must be [B,{_lib.ALIGN_NINFO}] for the B frames of temperature_map_C")
+        info = self._t(align_info, torch.float64, (b, _lib.ALIGN_NINFO), f"align_info must be [B,{_lib.ALIGN_NINFO}] for the B frames of temperature_map_C")
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         out = torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_thermal_register(self._h, t.data_ptr(), None if info is None else info.data_ptr(), b, out.data_ptr(),
+            _lib.check(self._lib.vistaf_thermal_register(self._h, t.data_ptr(), ptr(info), b, out.data_ptr(),
                                                          self._stream()))
         return out
 
@@ -81,21 +70,13 @@ class ThermalReadout:
         [B,K,16] float64 and count [B] int32 as `FtpSensor.contacts(K, index_plane=True)` returns them, status [B] int32 or None (every frame
         OK).  Returns device tensors {"thermal": [B,K,16] f64 (fields THERMAL_NAMES, unused rows and fields NaN), "frame": [B,8] f64 (fields
         THERMAL_FRAME_NAMES)}; a frame whose status is not 0 has NaN rows."""
-        tmp = torch.as_tensor(temp_crop).to(self.device, torch.float32).contiguous()
-        dep = torch.as_tensor(depth_mm).to(self.device, torch.float32).contiguous()
-        idx = torch.as_tensor(contact_index).to(self.device, torch.int8).contiguous()
-        tab = torch.as_tensor(contacts).to(self.device, torch.float64).contiguous()
-        cnt = torch.as_tensor(count).to(self.device, torch.int32).contiguous()
-        if idx.dim() != 3 or tuple(idx.shape[1:]) != (self.h, self.w) or tuple(dep.shape) != tuple(idx.shape) or tuple(tmp.shape) != tuple(idx.shape):
-            raise ValueError(f"temp_crop, depth_mm and contact_index must be [B,{self.h},{self.w}]")
+        msg = f"temp_crop, depth_mm and contact_index must be [B,{self.h},{self.w}]"
+        idx = self._t(contact_index, torch.int8, (None, self.h, self.w), msg)
+        tmp, dep = self._t(temp_crop, torch.float32, idx.shape, msg), self._t(depth_mm, torch.float32, idx.shape, msg)
         b = int(idx.shape[0])
-        if tuple(tab.shape) != (b, self.max_contacts, _lib.NCONTACT) or tuple(cnt.shape) != (b,):
-            raise ValueError(f"contacts must be [B,{self.max_contacts},{_lib.NCONTACT}] and count [B] for the B frames of contact_index")
-        st = None
-        if status is not None:
-            st = torch.as_tensor(status).to(self.device, torch.int32).contiguous()
-            if tuple(st.shape) != (b,):
-                raise ValueError("status must be [B] for the B frames of contact_index")
+        msg = f"contacts must be [B,{self.max_contacts},{_lib.NCONTACT}] and count [B] for the B frames of contact_index"
+        tab, cnt = self._t(contacts, torch.float64, (b, self.max_contacts, _lib.NCONTACT), msg), self._t(count, torch.int32, (b,), msg)
+        st = self._t(status, torch.int32, (b,), "status must be [B] for the B frames of contact_index")
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         if not math.isfinite(float(depth_eps_mm)):
@@ -104,17 +85,6 @@ class ThermalReadout:
                "frame": torch.empty((b, _lib.NTHERMALFRAME), dtype=torch.float64, device=self.device)}
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_thermal_measure(self._h, tmp.data_ptr(), dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(),
-                                                        None if st is None else st.data_ptr(), float(depth_eps_mm), b, out["thermal"].data_ptr(),
+                                                        ptr(st), float(depth_eps_mm), b, out["thermal"].data_ptr(),
                                                         out["frame"].data_ptr(), self._stream()))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_thermal_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

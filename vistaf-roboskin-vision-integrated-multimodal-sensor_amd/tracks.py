@@ -14,28 +14,26 @@ from typing import Dict
 import torch
 
 from . import _lib
+from ._readout import Readout
 
 TRACK_NAMES = _lib.TRACK_NAMES
 TRACK_EVENTS = _lib.TRACK_EVENTS
 
 
-class ContactTracker:
+class ContactTracker(Readout):
     """A tracker for h x w index planes, at most `max_batch` frames per update, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` calls that feed it).  gate_px > 0 adds the gate stage: contacts without any overlap are linked when their centroids
     are no further apart than gate_px, nearest pair first.  Frames of one update are consecutive in time, and frame 0 of an update follows
     the last frame of the update before it: the tracker keeps that frame on the device until `reset()`."""
+    _destroy = "vistaf_track_destroy"
 
     def __init__(self, h: int, w: int, max_batch: int, max_contacts: int = 8, gate_px: float = 0.0, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self.h, self.w, self.max_batch, self.max_contacts, self.gate_px = int(h), int(w), int(max_batch), int(max_contacts), float(gate_px)
         if not 1 <= self.max_contacts <= _lib.MAX_CONTACTS:
             raise ValueError(f"max_contacts must be 1..{_lib.MAX_CONTACTS}")
         if not (math.isfinite(self.gate_px) and self.gate_px >= 0.0):
             raise ValueError("gate_px must be finite and >= 0")
-        if not torch.cuda.is_available():
-            raise RuntimeError("ContactTracker needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
+        self._open(device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_track_create(self.h, self.w, self.max_batch, self.max_contacts, self.gate_px, ctypes.byref(self._h)))
 
@@ -43,34 +41,19 @@ class ContactTracker:
         """contact_index [B,h,w] int8, contacts [B,K,16] float64, count [B] int32, as `FtpSensor.contacts(K, index_plane=True)` returns them
         (device or host).  Returns device tensors: tracks [B,K,16] f64 (fields TRACK_NAMES, unused rows and fields NaN) and fate [B,K] i32
         (what became of row i of the frame before: the continuing row, -1 ended, -(2 + j) absorbed into contact j, INT32_MIN no such row)."""
-        idx = torch.as_tensor(contact_index).to(self.device, torch.int8).contiguous()
-        tab = torch.as_tensor(contacts).to(self.device, torch.float64).contiguous()
-        cnt = torch.as_tensor(count).to(self.device, torch.int32).contiguous()
-        if idx.dim() != 3 or tuple(idx.shape[1:]) != (self.h, self.w):
-            raise ValueError(f"contact_index must be [B,{self.h},{self.w}]")
+        idx = self._t(contact_index, torch.int8, (None, self.h, self.w), f"contact_index must be [B,{self.h},{self.w}]")
         b = int(idx.shape[0])
-        if tuple(tab.shape) != (b, self.max_contacts, _lib.NCONTACT) or tuple(cnt.shape) != (b,):
-            raise ValueError(f"contacts must be [B,{self.max_contacts},{_lib.NCONTACT}] and count [B] for the B frames of contact_index")
+        msg = f"contacts must be [B,{self.max_contacts},{_lib.NCONTACT}] and count [B] for the B frames of contact_index"
+        tab, cnt = self._t(contacts, torch.float64, (b, self.max_contacts, _lib.NCONTACT), msg), self._t(count, torch.int32, (b,), msg)
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         out = {"tracks": torch.empty((b, self.max_contacts, _lib.NTRACK), dtype=torch.float64, device=self.device),
                "fate": torch.empty((b, self.max_contacts), dtype=torch.int32, device=self.device)}
         with torch.cuda.device(self.device):
             _lib.check(self._lib.vistaf_track_update(self._h, idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), b, out["tracks"].data_ptr(),
-                                                     out["fate"].data_ptr(), int(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                     out["fate"].data_ptr(), self._stream()))
         return out
 
     def reset(self):
         """forget the carried frame and restart ids at 0"""
         _lib.check(self._lib.vistaf_track_reset(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_track_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -157,25 +157,64 @@ def write_result_csv(output_dir: str, record: Mapping[str, Any]) -> str:
     return path
 
 
+def _int_or_minus_one(v: float) -> int:
+    return -1 if math.isnan(v) else int(v)
+
+
+def _table(rows, count, fields, int_fields, error: str, *, with_contacts=None, skip_first=None, int_conv=int) -> list:
+    """The row dicts of a per-contact table [B,K,>=len(fields)] (or [K,..] for one frame) with count [B]: `frame`, `contact` and `fields`,
+    the `int_fields` through int_conv, for the first min(count, K) rows of every frame.  with_contacts: the contacts table of the same
+    frames, whose [B,K] must agree.  skip_first: rows for whose first field it holds are left out.  ValueError(error) for other shapes."""
+    t = np.asarray(rows, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 2:
+        t = t[None]
+    ok = t.ndim == 3 and t.shape[2] >= len(fields) and t.shape[0] == n.shape[0]
+    if with_contacts is not None:
+        c = np.asarray(with_contacts, dtype=np.float64)
+        if c.ndim == 2:
+            c = c[None]
+        ok = ok and c.ndim == 3 and c.shape[:2] == t.shape[:2]
+    if not ok:
+        raise ValueError(error)
+    out = []
+    for b in range(t.shape[0]):
+        for k in range(min(max(int(n[b]), 0), t.shape[1])):
+            if skip_first is not None and skip_first(t[b, k, 0]):
+                continue
+            row: Dict[str, Any] = {"frame": b, "contact": k}
+            for i, name in enumerate(fields):
+                row[name] = int_conv(t[b, k, i]) if name in int_fields else float(t[b, k, i])
+            out.append(row)
+    return out
+
+
+def _write_csv(output_dir: str, filename: str, fieldnames, rows) -> str:
+    """one line per row dict, floats with repr() (they read back to the same doubles)"""
+    os.makedirs(output_dir, exist_ok=True)
+    path = os.path.join(output_dir, filename)
+    with open(path, "w", newline="", encoding="utf-8") as f:
+        w = csv.DictWriter(f, fieldnames=list(fieldnames))
+        w.writeheader()
+        for row in rows:
+            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
+    return path
+
+
+def _frame_record(row, fields, int_fields) -> Dict[str, Any]:
+    """one frame row [>=len(fields)] as a dict of `fields`, the `int_fields` as ints (-1 for NaN)"""
+    f = np.asarray(row, dtype=np.float64)
+    if f.ndim != 1 or f.shape[0] < len(fields):
+        raise ValueError(f"the frame row must be [>={len(fields)}]")
+    return {name: (_int_or_minus_one(f[i]) if name in int_fields else float(f[i])) for i, name in enumerate(fields)}
+
+
 def contacts_table(contacts, count) -> list:
     """Row dicts of the per-contact table: contacts [B,K,>=13] (or [K,>=13] for one frame) float64 as `FtpSensor.contacts` returns it, count
     [B] (or a scalar).  One dict per written contact, frames in order, contacts in the table's order (deepest first): `frame`, `contact`
     and CONTACT_FIELDS, the counts / indices / box as ints.  A frame with count > K contributes its K written rows (the table is
     truncated there, which `count` shows); NaN rows are skipped."""
-    c = np.asarray(contacts, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if c.ndim == 2:
-        c = c[None]
-    if c.ndim != 3 or c.shape[2] < len(CONTACT_FIELDS) or c.shape[0] != n.shape[0]:
-        raise ValueError("contacts must be [B,K,>=13] with count [B]")
-    rows = []
-    for b in range(c.shape[0]):
-        for k in range(min(int(n[b]), c.shape[1])):
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(CONTACT_FIELDS):
-                row[name] = int(c[b, k, i]) if name in CONTACT_INT_FIELDS else float(c[b, k, i])
-            rows.append(row)
-    return rows
+    return _table(contacts, count, CONTACT_FIELDS, CONTACT_INT_FIELDS, "contacts must be [B,K,>=13] with count [B]")
 
 
 def contacts_record(contacts, count) -> Dict[str, Any]:
@@ -191,88 +230,33 @@ def contacts_record(contacts, count) -> Dict[str, Any]:
 
 def write_contacts_csv(output_dir: str, contacts, count, filename: str = "contacts.csv") -> str:
     """contacts.csv: one line per written contact, columns CONTACTS_CSV_FIELDS, floats with repr() (they read back to the same doubles)."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(CONTACTS_CSV_FIELDS))
-        w.writeheader()
-        for row in contacts_table(contacts, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, CONTACTS_CSV_FIELDS, contacts_table(contacts, count))
 
 
 def tracks_table(tracks, contacts, count) -> list:
     """Row dicts of the contact tracker's table: tracks [B,K,>=10] (or [K,>=10] for one frame) float64 as `FtpSensor.track` returns it, with
     the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact`
     (the row in both tables) and TRACK_FIELDS, the ids / age / rows / bitmask / pixel count as ints; dx .. dvolume_cm3 are NaN at birth."""
-    t = np.asarray(tracks, dtype=np.float64)
-    c = np.asarray(contacts, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if t.ndim == 2:
-        t = t[None]
-    if c.ndim == 2:
-        c = c[None]
-    if t.ndim != 3 or t.shape[2] < len(TRACK_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
-        raise ValueError("tracks must be [B,K,>=10] with contacts [B,K,>=13] and count [B]")
-    rows = []
-    for b in range(t.shape[0]):
-        for k in range(min(int(n[b]), t.shape[1])):
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(TRACK_FIELDS):
-                row[name] = int(t[b, k, i]) if name in TRACK_INT_FIELDS else float(t[b, k, i])
-            rows.append(row)
-    return rows
+    return _table(tracks, count, TRACK_FIELDS, TRACK_INT_FIELDS, "tracks must be [B,K,>=10] with contacts [B,K,>=13] and count [B]",
+                  with_contacts=contacts)
 
 
 def write_tracks_csv(output_dir: str, tracks, contacts, count, filename: str = "tracks.csv") -> str:
     """tracks.csv: one line per written contact, columns TRACKS_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(TRACKS_CSV_FIELDS))
-        w.writeheader()
-        for row in tracks_table(tracks, contacts, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, TRACKS_CSV_FIELDS, tracks_table(tracks, contacts, count))
 
 
 def shapes_table(shapes, contacts, count) -> list:
     """Row dicts of the per-contact shape table: shapes [B,K,>=18] (or [K,>=18] for one frame) float64 as `FtpSensor.shapes` returns it, with
     the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact`
     (the row in both tables) and SHAPE_FIELDS, the pixel counts and the fit status as ints; what a status leaves out is NaN."""
-    t = np.asarray(shapes, dtype=np.float64)
-    c = np.asarray(contacts, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if t.ndim == 2:
-        t = t[None]
-    if c.ndim == 2:
-        c = c[None]
-    if t.ndim != 3 or t.shape[2] < len(SHAPE_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
-        raise ValueError("shapes must be [B,K,>=18] with contacts [B,K,>=13] and count [B]")
-    rows = []
-    for b in range(t.shape[0]):
-        for k in range(min(int(n[b]), t.shape[1])):
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(SHAPE_FIELDS):
-                row[name] = int(t[b, k, i]) if name in SHAPE_INT_FIELDS else float(t[b, k, i])
-            rows.append(row)
-    return rows
+    return _table(shapes, count, SHAPE_FIELDS, SHAPE_INT_FIELDS, "shapes must be [B,K,>=18] with contacts [B,K,>=13] and count [B]",
+                  with_contacts=contacts)
 
 
 def write_shapes_csv(output_dir: str, shapes, contacts, count, filename: str = "shapes.csv") -> str:
     """shapes.csv: one line per written contact, columns SHAPES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(SHAPES_CSV_FIELDS))
-        w.writeheader()
-        for row in shapes_table(shapes, contacts, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
-
-
-def _int_or_minus_one(v: float) -> int:
-    return -1 if math.isnan(v) else int(v)
+    return _write_csv(output_dir, filename, SHAPES_CSV_FIELDS, shapes_table(shapes, contacts, count))
 
 
 def taxels_table(taxels) -> list:
@@ -298,22 +282,12 @@ def taxels_table(taxels) -> list:
 
 def write_taxels_csv(output_dir: str, taxels, filename: str = "taxels.csv") -> str:
     """taxels.csv: one line per frame and taxel, columns TAXELS_CSV_FIELDS, floats with repr()."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(TAXELS_CSV_FIELDS))
-        w.writeheader()
-        for row in taxels_table(taxels):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, TAXELS_CSV_FIELDS, taxels_table(taxels))
 
 
 def taxel_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=8] of the taxel read-out as a dict of TAXEL_FRAME_FIELDS; active_taxels and peak_taxel as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(TAXEL_FRAME_FIELDS):
-        raise ValueError("the frame row must be [>=8]")
-    return {name: (_int_or_minus_one(f[i]) if name in TAXEL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(TAXEL_FRAME_FIELDS)}
+    return _frame_record(frame_row, TAXEL_FRAME_FIELDS, TAXEL_FRAME_INT_FIELDS)
 
 
 def thermal_table(thermal, contacts, count) -> list:
@@ -321,54 +295,24 @@ def thermal_table(thermal, contacts, count) -> list:
     contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact` (the row
     in both tables) and THERMAL_FIELDS, the pixel counts as ints; what has no value is NaN.  A frame whose rows are NaN (its status was not
     0) has no rows."""
-    t = np.asarray(thermal, dtype=np.float64)
-    c = np.asarray(contacts, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if t.ndim == 2:
-        t = t[None]
-    if c.ndim == 2:
-        c = c[None]
-    if t.ndim != 3 or t.shape[2] < len(THERMAL_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
-        raise ValueError("thermal must be [B,K,>=12] with contacts [B,K,>=13] and count [B]")
-    rows = []
-    for b in range(t.shape[0]):
-        for k in range(min(int(n[b]), t.shape[1])):
-            if np.isnan(t[b, k, 0]):
-                continue
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(THERMAL_FIELDS):
-                row[name] = int(t[b, k, i]) if name in THERMAL_INT_FIELDS else float(t[b, k, i])
-            rows.append(row)
-    return rows
+    return _table(thermal, count, THERMAL_FIELDS, THERMAL_INT_FIELDS, "thermal must be [B,K,>=12] with contacts [B,K,>=13] and count [B]",
+                  with_contacts=contacts, skip_first=np.isnan)
 
 
 def write_thermal_csv(output_dir: str, thermal, contacts, count, filename: str = "thermal.csv") -> str:
     """thermal.csv: one line per written contact, columns THERMAL_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one
     (but for frames whose status was not 0)."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(THERMAL_CSV_FIELDS))
-        w.writeheader()
-        for row in thermal_table(thermal, contacts, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, THERMAL_CSV_FIELDS, thermal_table(thermal, contacts, count))
 
 
 def thermal_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=7] of the thermal read-out as a dict of THERMAL_FRAME_FIELDS; the pixel counts and the two rows as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(THERMAL_FRAME_FIELDS):
-        raise ValueError("the frame row must be [>=7]")
-    return {name: (_int_or_minus_one(f[i]) if name in THERMAL_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(THERMAL_FRAME_FIELDS)}
+    return _frame_record(frame_row, THERMAL_FRAME_FIELDS, THERMAL_FRAME_INT_FIELDS)
 
 
 def temporal_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=16] of the temporal read-out as a dict of TEMPORAL_FIELDS; counts, indices, dwell, events and gap as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(TEMPORAL_FIELDS):
-        raise ValueError("the frame row must be [>=16]")
-    return {name: (_int_or_minus_one(f[i]) if name in TEMPORAL_INT_FIELDS else float(f[i])) for i, name in enumerate(TEMPORAL_FIELDS)}
+    return _frame_record(frame_row, TEMPORAL_FIELDS, TEMPORAL_INT_FIELDS)
 
 
 def temporal_table(frames) -> list:
@@ -390,22 +334,12 @@ def temporal_table(frames) -> list:
 
 def write_temporal_csv(output_dir: str, frames, filename: str = "temporal.csv") -> str:
     """temporal.csv: one line per frame, columns TEMPORAL_CSV_FIELDS, floats with repr()."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(TEMPORAL_CSV_FIELDS))
-        w.writeheader()
-        for row in temporal_table(frames):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, TEMPORAL_CSV_FIELDS, temporal_table(frames))
 
 
 def cloud_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=11] of the point-cloud read-out as a dict of CLOUD_FRAME_FIELDS; the counts and the index as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(CLOUD_FRAME_FIELDS):
-        raise ValueError("the frame row must be [>=11]")
-    return {name: (_int_or_minus_one(f[i]) if name in CLOUD_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(CLOUD_FRAME_FIELDS)}
+    return _frame_record(frame_row, CLOUD_FRAME_FIELDS, CLOUD_FRAME_INT_FIELDS)
 
 
 def write_cloud_ply(path: str, points, label=None) -> str:
@@ -443,86 +377,37 @@ def motion_table(motion, contacts, count) -> list:
     """Row dicts of the contact motion table: motion [B,K,>=20] (or [K,>=20] for one frame) float64 as `FtpSensor.motion` returns it, with
     the contacts table [B,K,>=13] and count [B] of the same frames.  One dict per written contact, as `tracks_table`: `frame`, `contact`
     (the row in both tables) and MOTION_FIELDS, the parent row, pixel count, status and iterations as ints; what a status leaves out is NaN."""
-    t = np.asarray(motion, dtype=np.float64)
-    c = np.asarray(contacts, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if t.ndim == 2:
-        t = t[None]
-    if c.ndim == 2:
-        c = c[None]
-    if t.ndim != 3 or t.shape[2] < len(MOTION_FIELDS) or c.ndim != 3 or c.shape[:2] != t.shape[:2] or t.shape[0] != n.shape[0]:
-        raise ValueError("motion must be [B,K,>=20] with contacts [B,K,>=13] and count [B]")
-    rows = []
-    for b in range(t.shape[0]):
-        for k in range(min(int(n[b]), t.shape[1])):
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(MOTION_FIELDS):
-                row[name] = int(t[b, k, i]) if name in MOTION_INT_FIELDS else float(t[b, k, i])
-            rows.append(row)
-    return rows
+    return _table(motion, count, MOTION_FIELDS, MOTION_INT_FIELDS, "motion must be [B,K,>=20] with contacts [B,K,>=13] and count [B]",
+                  with_contacts=contacts)
 
 
 def write_motion_csv(output_dir: str, motion, contacts, count, filename: str = "motion.csv") -> str:
     """motion.csv: one line per written contact, columns MOTION_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(MOTION_CSV_FIELDS))
-        w.writeheader()
-        for row in motion_table(motion, contacts, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, MOTION_CSV_FIELDS, motion_table(motion, contacts, count))
 
 
 def motion_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=8] of the motion read-out as a dict of MOTION_FRAME_FIELDS; the count and the two rows as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(MOTION_FRAME_FIELDS):
-        raise ValueError("the frame row must be [>=8]")
-    return {name: (_int_or_minus_one(f[i]) if name in MOTION_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(MOTION_FRAME_FIELDS)}
+    return _frame_record(frame_row, MOTION_FRAME_FIELDS, MOTION_FRAME_INT_FIELDS)
 
 
 def pressure_table(rows, count) -> list:
     """Row dicts of the pressure table: rows [B,K,>=13] (or [K,>=13] for one frame) float64 as `FtpSensor.pressure` returns it, with count [B]
     of the same frames.  One dict per written contact, as `contacts_table`: `frame`, `contact` (the row in both tables) and PRESSURE_FIELDS,
     the pixel count and the peak's index as ints; a field whose divisor is 0 is NaN."""
-    t = np.asarray(rows, dtype=np.float64)
-    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
-    if t.ndim == 2:
-        t = t[None]
-    if t.ndim != 3 or t.shape[2] < len(PRESSURE_FIELDS) or t.shape[0] != n.shape[0]:
-        raise ValueError("rows must be [B,K,>=13] with count [B]")
-    out = []
-    for b in range(t.shape[0]):
-        for k in range(min(max(int(n[b]), 0), t.shape[1])):
-            if not np.isfinite(t[b, k, 0]):               # a frame whose status is not 0
-                continue
-            row: Dict[str, Any] = {"frame": b, "contact": k}
-            for i, name in enumerate(PRESSURE_FIELDS):
-                row[name] = _int_or_minus_one(t[b, k, i]) if name in PRESSURE_INT_FIELDS else float(t[b, k, i])
-            out.append(row)
-    return out
+    return _table(rows, count, PRESSURE_FIELDS, PRESSURE_INT_FIELDS, "rows must be [B,K,>=13] with count [B]",
+                  skip_first=lambda v: not np.isfinite(v), int_conv=_int_or_minus_one)        # not finite: a frame whose status is not 0
 
 
 def write_pressure_csv(output_dir: str, rows, count, filename: str = "pressure.csv") -> str:
     """pressure.csv: one line per written contact, columns PRESSURE_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
-    os.makedirs(output_dir, exist_ok=True)
-    path = os.path.join(output_dir, filename)
-    with open(path, "w", newline="", encoding="utf-8") as f:
-        w = csv.DictWriter(f, fieldnames=list(PRESSURE_CSV_FIELDS))
-        w.writeheader()
-        for row in pressure_table(rows, count):
-            w.writerow({k: (repr(v) if isinstance(v, float) else v) for k, v in row.items()})
-    return path
+    return _write_csv(output_dir, filename, PRESSURE_CSV_FIELDS, pressure_table(rows, count))
 
 
 def pressure_frame_record(frame_row) -> Dict[str, Any]:
     """One frame row [>=12] of the pressure read-out as a dict of PRESSURE_FRAME_FIELDS; the count, the peak's index and row and the status
     as ints (-1 for NaN)."""
-    f = np.asarray(frame_row, dtype=np.float64)
-    if f.ndim != 1 or f.shape[0] < len(PRESSURE_FRAME_FIELDS):
-        raise ValueError("the frame row must be [>=12]")
-    return {name: (_int_or_minus_one(f[i]) if name in PRESSURE_FRAME_INT_FIELDS else float(f[i])) for i, name in enumerate(PRESSURE_FRAME_FIELDS)}
+    return _frame_record(frame_row, PRESSURE_FRAME_FIELDS, PRESSURE_FRAME_INT_FIELDS)
 
 
 def height_map_bundle(height_crop: np.ndarray, crop_masks: Mapping[str, np.ndarray], crop_box: Tuple[int, int, int, int],
