@@ -1,6 +1,8 @@
-"""What the read-out classes share: the library handle's life, the device check, the stream and the coercion of an argument."""
+"""What the classes that wrap a handle of the C ABI share: the handle's life, the device check, the stream, the one way to call the library
+and the coercion of an argument."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 
 import torch
@@ -8,7 +10,20 @@ import torch
 from . import _lib
 
 
-class Readout:
+def stream(device) -> int:
+    """the current stream of `device`, as the `void *stream` argument of the ABI"""
+    return int(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(device, name: str, *args):
+    """The library function `name` with `device` current, or as things are for device None (a function that touches no device: argument
+    checks, host tables, flags -- these also run where there is no device).  A return other than 0 raises with the library's last-error
+    text (ValueError for VISTAF_E_INVALID, RuntimeError otherwise)."""
+    with torch.cuda.device(device) if device is not None else contextlib.nullcontext():
+        _lib.check(getattr(_lib.load(), name)(*args))
+
+
+class Handle:
     """Base of the classes that wrap one handle of the C ABI.  `_destroy` names the library function that frees the handle."""
     _destroy = ""
 
@@ -26,7 +41,10 @@ class Readout:
                                "there is no CPU path")
 
     def _stream(self) -> int:
-        return int(torch.cuda.current_stream(self.device).cuda_stream)
+        return stream(self.device)
+
+    def _call(self, name: str, *args, on_device: bool = True):
+        call(self.device if on_device else None, name, *args)
 
     def _t(self, value, dtype, shape=None, message: str = ""):
         """value as a contiguous tensor of `dtype` on the device; None stays None.  shape: what it must be, None as its first entry for

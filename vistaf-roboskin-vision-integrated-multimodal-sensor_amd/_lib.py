@@ -67,39 +67,8 @@ FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
 CURVE_TYPES = {"linear0": 0, "linear": 1, "poly2": 2, "sat_exp": 3, "growth": 4, "hinge_saturating": 5}
 
-EXPORTS = [
-    "vistaf_ftp_abi_version", "vistaf_ftp_last_error", "vistaf_ftp_default_config", "vistaf_ftp_create",
-    "vistaf_ftp_set_reference", "vistaf_ftp_get_reference_info", "vistaf_ftp_predict_batch", "vistaf_ftp_predict_pairs",
-    "vistaf_ftp_get_pair_info", "vistaf_ftp_contacts",
-    "vistaf_ftp_get_intermediate", "vistaf_ftp_stage_count", "vistaf_ftp_stage_name",
-    "vistaf_ftp_enable_stage_timing", "vistaf_ftp_get_stage_times", "vistaf_ftp_destroy",
-    "vistaf_depth_map_to_volume", "vistaf_predict_force_from_volume",
-]
-# csrc/test_hooks.h: kernel tier selection / debug planes for the parity tests, and the selection, fit and blur launchers on planes of the test's own
-TEST_EXPORTS = ["vistaf_ftp_test_set", "vistaf_ftp_test_select", "vistaf_ftp_test_select_instance", "vistaf_ftp_test_select_chained", "vistaf_ftp_test_polyfit", "vistaf_ftp_test_gauss",
-                "vistaf_ftp_test_chamfer", "vistaf_ftp_test_scratch_regions", "vistaf_ftp_test_cc_label", "vistaf_ftp_test_cc_largest",
-                "vistaf_ftp_test_chamfer_dispatch", "vistaf_ftp_test_blob_filter", "vistaf_ftp_test_dft_full_mag"]
-TEMP_EXPORTS = ["vistaf_tempseg_default_config", "vistaf_tempseg_create", "vistaf_tempseg_destroy", "vistaf_tempseg_segment",
-                "vistaf_temp_feature_planes", "vistaf_temp_color_support",
-                "vistaf_temp_clamp_map", "vistaf_temp_inpaint_map", "vistaf_temp_fuse_maps", "vistaf_temp_oriented_blur"]   # include/vistaf_temp.h
 TEMPSEG_NINFO = 16
-TEMPMODEL_EXPORTS = ["vistaf_tmodel_create", "vistaf_tmodel_destroy", "vistaf_tmodel_predict_maps", "vistaf_tmodel_predict_rows"]   # include/vistaf_tempmodel.h
-TSENSOR_EXPORTS = ["vistaf_tsensor_default_config", "vistaf_tsensor_create", "vistaf_tsensor_destroy", "vistaf_tsensor_predict",
-                   "vistaf_tsensor_stats_create", "vistaf_tsensor_stats_destroy", "vistaf_tsensor_map_statistics"]   # include/vistaf_tempsensor.h
 TSENSOR_NINFO, TSENSOR_NMASKS, TSENSOR_NSTATS = TEMPSEG_NINFO + 4, 5, 6
-TRACK_EXPORTS = ["vistaf_track_create", "vistaf_track_update", "vistaf_track_reset", "vistaf_track_destroy"]   # include/vistaf_track.h
-SHAPE_EXPORTS = ["vistaf_shape_create", "vistaf_shape_measure", "vistaf_shape_destroy"]   # include/vistaf_shape.h
-TAXEL_EXPORTS = ["vistaf_taxel_create", "vistaf_taxel_measure", "vistaf_taxel_layout_info", "vistaf_taxel_destroy"]   # include/vistaf_taxel.h
-THERMAL_EXPORTS = ["vistaf_thermal_create", "vistaf_thermal_register", "vistaf_thermal_measure", "vistaf_thermal_destroy"]   # include/vistaf_thermal.h
-TEMPORAL_EXPORTS = ["vistaf_temporal_create", "vistaf_temporal_update", "vistaf_temporal_state", "vistaf_temporal_reset",
-                    "vistaf_temporal_destroy"]   # include/vistaf_temporal.h
-CLOUD_EXPORTS = ["vistaf_cloud_create", "vistaf_cloud_measure", "vistaf_cloud_destroy"]   # include/vistaf_cloud.h
-MOTION_EXPORTS = ["vistaf_motion_create", "vistaf_motion_update", "vistaf_motion_reset", "vistaf_motion_destroy"]   # include/vistaf_motion.h
-PRESSURE_EXPORTS = ["vistaf_pressure_create", "vistaf_pressure_measure", "vistaf_pressure_destroy"]   # include/vistaf_pressure.h
-ALIGN_EXPORTS = [            # include/vistaf_align.h
-    "vistaf_align_default_config", "vistaf_align_create", "vistaf_align_destroy", "vistaf_align_geometry",
-    "vistaf_align_set_reference", "vistaf_align_batch",
-]
 
 
 class Curve(ctypes.Structure):
@@ -141,6 +110,137 @@ class CTSensorConfig(ctypes.Structure):
                [(n, ctypes.c_double) for n in ("color_chroma_min", "color_clamp_pad", "smooth_sigma_across", "smooth_sigma_along")]
 
 
+class AlignConfig(ctypes.Structure):
+    _fields_ = [("apply_global_shift", ctypes.c_int32), ("use_ecc", ctypes.c_int32), ("ecc_iters", ctypes.c_int32), ("gray_coeffs", ctypes.c_int32),
+                ("ecc_eps", ctypes.c_double), ("ecc_gauss_sigma", ctypes.c_double), ("shift_blur_sigma", ctypes.c_double)]
+
+
+vp, ci, cd, cf, cs, sz, i32, i64, P = (ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_float, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int32,
+                                       ctypes.c_int64, ctypes.POINTER)
+# The C ABI, stated once: every exported function -> (restype, argtypes), grouped by the header that declares it and in its order.  load()
+# applies the table; tests/test_abi_surface.py holds it against the prototypes.  A device pointer or a stream is vp, a handle vp, its slot P(vp).
+SIGNATURES = {
+    "EXPORTS": {        # include/vistaf_ftp.h
+        "vistaf_ftp_abi_version": (ci, []),
+        "vistaf_ftp_last_error": (cs, []),
+        "vistaf_ftp_default_config": (ci, [P(CConfig)]),
+        "vistaf_ftp_create": (ci, [P(CConfig), ci, ci, ci, ci, ci, ci, P(Curve), ci, P(Curve), P(vp)]),
+        "vistaf_ftp_set_reference": (ci, [vp, vp, ci, vp]),
+        "vistaf_ftp_get_reference_info": (ci, [vp, P(cd)]),
+        "vistaf_ftp_predict_batch": (ci, [vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+        "vistaf_ftp_predict_pairs": (ci, [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]),
+        "vistaf_ftp_get_pair_info": (ci, [vp, ci, P(cd), vp]),
+        "vistaf_ftp_contacts": (ci, [vp, ci, ci, vp, vp, vp, vp]),
+        "vistaf_ftp_get_intermediate": (ci, [vp, cs, vp, ci, P(sz), vp]),
+        "vistaf_ftp_stage_count": (ci, []),
+        "vistaf_ftp_stage_name": (cs, [ci]),
+        "vistaf_ftp_enable_stage_timing": (ci, [vp, ci]),
+        "vistaf_ftp_get_stage_times": (ci, [vp, P(cf), ci]),
+        "vistaf_ftp_destroy": (None, [vp]),
+        "vistaf_depth_map_to_volume": (ci, [vp, vp, ci, ci, ci, cd, cd, vp, vp]),
+        "vistaf_predict_force_from_volume": (ci, [P(Curve), cd, P(cd)]),
+    },
+    "ALIGN_EXPORTS": {        # include/vistaf_align.h
+        "vistaf_align_default_config": (None, [P(AlignConfig)]),
+        "vistaf_align_create": (ci, [P(AlignConfig), ci, ci, ci, ci, ci, ci, P(vp)]),
+        "vistaf_align_destroy": (None, [vp]),
+        "vistaf_align_geometry": (ci, [vp] + [P(i32)] * 9),
+        "vistaf_align_set_reference": (ci, [vp, vp, vp, vp]),
+        "vistaf_align_batch": (ci, [vp, vp, ci, vp, vp, vp]),
+    },
+    "TEST_EXPORTS": {        # csrc/test_hooks.h
+        "vistaf_ftp_test_set": (ci, [vp, cs, ci]),
+        "vistaf_ftp_test_select": (ci, [vp, vp, sz, vp, ci, vp, ci, vp, vp, ci, ci, ci, vp]),
+        "vistaf_ftp_test_select_instance": (ci, [ci, ci, ci, ci]),
+        "vistaf_ftp_test_select_chained": (ci, [vp, vp, sz, ci, vp, ci, vp, vp, ci, ci, vp]),
+        "vistaf_ftp_test_polyfit": (ci, [vp, vp, ci, ci, cf, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_gauss": (ci, [vp, vp, cd, ci, ci, ci, vp]),
+        "vistaf_ftp_test_chamfer": (ci, [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_scratch_regions": (ci, [cs, ci, ci, ci, ci, ci, cs, P(sz), P(sz), P(sz), P(sz)]),
+        "vistaf_ftp_test_cc_label": (ci, [vp, vp, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_cc_largest": (ci, [vp, vp, vp, ci, ci, ci, vp]),
+        "vistaf_ftp_test_chamfer_dispatch": (ci, [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_blob_filter": (ci, [vp, vp, vp, vp, cd, cd, vp, ci, ci, vp]),
+        "vistaf_ftp_test_dft_full_mag": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+    },
+    "TEMP_EXPORTS": {        # include/vistaf_temp.h
+        "vistaf_tempseg_default_config": (ci, [P(CTempSegConfig)]),
+        "vistaf_tempseg_create": (ci, [P(CTempSegConfig), ci, ci, P(vp)]),
+        "vistaf_tempseg_destroy": (None, [vp]),
+        "vistaf_tempseg_segment": (ci, [vp, vp, vp, vp, vp, vp, vp, P(cd), vp]),
+        "vistaf_temp_feature_planes": (ci, [vp, vp, ci, vp, vp, vp, vp, vp]),
+        "vistaf_temp_color_support": (ci, [vp, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp]),
+        "vistaf_temp_clamp_map": (ci, [vp, vp, vp, cd, cd, vp, vp]),
+        "vistaf_temp_inpaint_map": (ci, [vp, vp, vp, ci, vp, vp]),
+        "vistaf_temp_fuse_maps": (ci, [vp, vp, vp, vp, P(CTempFuseConfig), vp, vp, P(i64), vp]),
+        "vistaf_temp_oriented_blur": (ci, [vp, vp, vp, cd, cd, cd, vp, vp]),
+    },
+    "TEMPMODEL_EXPORTS": {        # include/vistaf_tempmodel.h
+        "vistaf_tmodel_create": (ci, [ci, P(i32), P(cd), P(cd), ci, ci, ci, P(i32), P(cd), cd, ci, P(cd), P(cd), cd, cd, ci, P(vp)]),
+        "vistaf_tmodel_destroy": (None, [vp]),
+        "vistaf_tmodel_predict_maps": (ci, [ci, P(vp), P(vp), P(vp), P(vp), i64, i64, vp]),
+        "vistaf_tmodel_predict_rows": (ci, [vp, vp, ci, i64, vp, vp]),
+    },
+    "TSENSOR_EXPORTS": {        # include/vistaf_tempsensor.h
+        "vistaf_tsensor_default_config": (ci, [P(CTSensorConfig)]),
+        "vistaf_tsensor_create": (ci, [P(CTSensorConfig), ci, ci, vp, vp, P(vp)]),
+        "vistaf_tsensor_destroy": (None, [vp]),
+        "vistaf_tsensor_predict": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, P(cd), vp, P(cd), vp]),
+        "vistaf_tsensor_stats_create": (ci, [ci, ci, P(vp)]),
+        "vistaf_tsensor_stats_destroy": (None, [vp]),
+        "vistaf_tsensor_map_statistics": (ci, [vp, vp, vp, vp, P(cd), vp]),
+    },
+    "TRACK_EXPORTS": {        # include/vistaf_track.h
+        "vistaf_track_create": (ci, [ci, ci, ci, ci, cd, P(vp)]),
+        "vistaf_track_update": (ci, [vp, vp, vp, vp, ci, vp, vp, vp]),
+        "vistaf_track_reset": (ci, [vp]),
+        "vistaf_track_destroy": (None, [vp]),
+    },
+    "SHAPE_EXPORTS": {        # include/vistaf_shape.h
+        "vistaf_shape_create": (ci, [ci, ci, ci, ci, cd, P(vp)]),
+        "vistaf_shape_measure": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, vp, vp]),
+        "vistaf_shape_destroy": (None, [vp]),
+    },
+    "TAXEL_EXPORTS": {        # include/vistaf_taxel.h
+        "vistaf_taxel_create": (ci, [ci, ci, ci, vp, ci, cd, cd, P(vp)]),
+        "vistaf_taxel_measure": (ci, [vp, vp, vp, vp, vp, cf, ci, vp, vp, vp]),
+        "vistaf_taxel_layout_info": (ci, [vp, vp]),
+        "vistaf_taxel_destroy": (None, [vp]),
+    },
+    "THERMAL_EXPORTS": {        # include/vistaf_thermal.h
+        "vistaf_thermal_create": (ci, [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, P(vp)]),
+        "vistaf_thermal_register": (ci, [vp, vp, vp, ci, vp, vp]),
+        "vistaf_thermal_measure": (ci, [vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp]),
+        "vistaf_thermal_destroy": (None, [vp]),
+    },
+    "TEMPORAL_EXPORTS": {        # include/vistaf_temporal.h
+        "vistaf_temporal_create": (ci, [ci, ci, ci, cd, cd, cd, cd, P(vp)]),
+        "vistaf_temporal_update": (ci, [vp, vp, vp, vp, ci, vp, vp, vp, vp]),
+        "vistaf_temporal_state": (ci, [vp, vp, vp, vp, vp, vp, vp]),
+        "vistaf_temporal_reset": (ci, [vp]),
+        "vistaf_temporal_destroy": (None, [vp]),
+    },
+    "CLOUD_EXPORTS": {        # include/vistaf_cloud.h
+        "vistaf_cloud_create": (ci, [ci, ci, ci, i64, ci, cd, cd, P(vp)]),
+        "vistaf_cloud_measure": (ci, [vp, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp, vp]),
+        "vistaf_cloud_destroy": (None, [vp]),
+    },
+    "MOTION_EXPORTS": {        # include/vistaf_motion.h
+        "vistaf_motion_create": (ci, [ci, ci, ci, ci, ci, cd, ci, ci, P(vp)]),
+        "vistaf_motion_update": (ci, [vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp]),
+        "vistaf_motion_reset": (ci, [vp]),
+        "vistaf_motion_destroy": (None, [vp]),
+    },
+    "PRESSURE_EXPORTS": {        # include/vistaf_pressure.h
+        "vistaf_pressure_create": (ci, [ci, ci, ci, ci, ci, cd, cd, cd, P(vp)]),
+        "vistaf_pressure_measure": (ci, [vp, vp, vp, vp, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp]),
+        "vistaf_pressure_destroy": (None, [vp]),
+    },
+}
+# the names of each group, for the tests that hold them against the headers
+(EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
+ TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
+
 _lib = None
 
 
@@ -155,110 +255,10 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    lib.vistaf_ftp_abi_version.restype = ci
-    lib.vistaf_ftp_last_error.restype = ctypes.c_char_p
-    lib.vistaf_ftp_default_config.argtypes = [ctypes.POINTER(CConfig)]
-    lib.vistaf_ftp_create.argtypes = [ctypes.POINTER(CConfig), ci, ci, ci, ci, ci, ci, ctypes.POINTER(Curve), ci,
-                                      ctypes.POINTER(Curve), ctypes.POINTER(vp)]
-    lib.vistaf_ftp_set_reference.argtypes = [vp, vp, ci, vp]
-    lib.vistaf_ftp_get_reference_info.argtypes = [vp, ctypes.POINTER(cd)]
-    lib.vistaf_ftp_predict_batch.argtypes = [vp, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.vistaf_ftp_predict_pairs.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp, vp, vp]
-    lib.vistaf_ftp_get_pair_info.argtypes = [vp, ci, ctypes.POINTER(cd), vp]
-    lib.vistaf_ftp_contacts.argtypes = [vp, ci, ci, vp, vp, vp, vp]
-    lib.vistaf_ftp_get_intermediate.argtypes = [vp, ctypes.c_char_p, vp, ci, ctypes.POINTER(ctypes.c_size_t), vp]
-    lib.vistaf_ftp_stage_count.restype = ci
-    lib.vistaf_ftp_stage_name.restype = ctypes.c_char_p
-    lib.vistaf_ftp_stage_name.argtypes = [ci]
-    lib.vistaf_ftp_enable_stage_timing.argtypes = [vp, ci]
-    lib.vistaf_ftp_get_stage_times.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ci]
-    lib.vistaf_ftp_destroy.argtypes = [vp]
-    lib.vistaf_ftp_destroy.restype = None
-    lib.vistaf_depth_map_to_volume.argtypes = [vp, vp, ci, ci, ci, cd, cd, vp, vp]
-    lib.vistaf_predict_force_from_volume.argtypes = [ctypes.POINTER(Curve), cd, ctypes.POINTER(cd)]
-    lib.vistaf_ftp_test_set.argtypes = [vp, ctypes.c_char_p, ci]
-    lib.vistaf_ftp_test_select.argtypes = [vp, vp, ctypes.c_size_t, vp, ci, vp, ci, vp, vp, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_select_instance.argtypes = [ci, ci, ci, ci]
-    lib.vistaf_ftp_test_select_chained.argtypes = [vp, vp, ctypes.c_size_t, ci, vp, ci, vp, vp, ci, ci, vp]
-    lib.vistaf_ftp_test_polyfit.argtypes = [vp, vp, ci, ci, ctypes.c_float, ci, ci, vp, vp, ci, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_gauss.argtypes = [vp, vp, cd, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_chamfer.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_cc_label.argtypes = [vp, vp, ci, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_cc_largest.argtypes = [vp, vp, vp, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_chamfer_dispatch.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]
-    lib.vistaf_ftp_test_blob_filter.argtypes = [vp, vp, vp, vp, cd, cd, vp, ci, ci, vp]
-    lib.vistaf_ftp_test_dft_full_mag.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]
-    szp = ctypes.POINTER(ctypes.c_size_t)
-    lib.vistaf_ftp_test_scratch_regions.argtypes = [ctypes.c_char_p, ci, ci, ci, ci, ci, ctypes.c_char_p, szp, szp, szp, szp]
-    lib.vistaf_tempseg_default_config.argtypes = [ctypes.POINTER(CTempSegConfig)]
-    lib.vistaf_tempseg_create.argtypes = [ctypes.POINTER(CTempSegConfig), ci, ci, ctypes.POINTER(vp)]
-    lib.vistaf_tempseg_destroy.argtypes = [vp]
-    lib.vistaf_tempseg_destroy.restype = None
-    lib.vistaf_tempseg_segment.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(cd), vp]
-    lib.vistaf_temp_feature_planes.argtypes = [vp, vp, ci, vp, vp, vp, vp, vp]
-    lib.vistaf_temp_color_support.argtypes = [vp, vp, vp, vp, vp, vp, cd, ci, vp, vp, vp]
-    lib.vistaf_temp_clamp_map.argtypes = [vp, vp, vp, cd, cd, vp, vp]
-    lib.vistaf_temp_inpaint_map.argtypes = [vp, vp, vp, ci, vp, vp]
-    lib.vistaf_temp_fuse_maps.argtypes = [vp, vp, vp, vp, ctypes.POINTER(CTempFuseConfig), vp, vp, ctypes.POINTER(ctypes.c_int64), vp]
-    lib.vistaf_temp_oriented_blur.argtypes = [vp, vp, vp, cd, cd, cd, vp, vp]
-    i32p, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(cd)
-    lib.vistaf_tmodel_create.argtypes = [ci, i32p, dp, dp, ci, ci, ci, i32p, dp, cd, ci, dp, dp, cd, cd, ci, ctypes.POINTER(vp)]
-    lib.vistaf_tmodel_destroy.argtypes = [vp]
-    lib.vistaf_tmodel_destroy.restype = None
-    lib.vistaf_tmodel_predict_maps.argtypes = [ci, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.c_int64,
-                                               ctypes.c_int64, vp]
-    lib.vistaf_tmodel_predict_rows.argtypes = [vp, vp, ci, ctypes.c_int64, vp, vp]
-    lib.vistaf_tsensor_default_config.argtypes = [ctypes.POINTER(CTSensorConfig)]
-    lib.vistaf_tsensor_create.argtypes = [ctypes.POINTER(CTSensorConfig), ci, ci, vp, vp, ctypes.POINTER(vp)]
-    lib.vistaf_tsensor_destroy.argtypes = [vp]
-    lib.vistaf_tsensor_destroy.restype = None
-    lib.vistaf_tsensor_predict.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.POINTER(cd), vp, ctypes.POINTER(cd), vp]
-    lib.vistaf_tsensor_stats_create.argtypes = [ci, ci, ctypes.POINTER(vp)]
-    lib.vistaf_tsensor_stats_destroy.argtypes = [vp]
-    lib.vistaf_tsensor_stats_destroy.restype = None
-    lib.vistaf_tsensor_map_statistics.argtypes = [vp, vp, vp, vp, ctypes.POINTER(cd), vp]
-    lib.vistaf_track_create.argtypes = [ci, ci, ci, ci, cd, ctypes.POINTER(vp)]
-    lib.vistaf_track_update.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp]
-    lib.vistaf_track_reset.argtypes = [vp]
-    lib.vistaf_track_destroy.argtypes = [vp]
-    lib.vistaf_track_destroy.restype = None
-    lib.vistaf_shape_create.argtypes = [ci, ci, ci, ci, cd, ctypes.POINTER(vp)]
-    lib.vistaf_shape_measure.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]
-    lib.vistaf_shape_destroy.argtypes = [vp]
-    lib.vistaf_shape_destroy.restype = None
-    lib.vistaf_taxel_create.argtypes = [ci, ci, ci, vp, ci, cd, cd, ctypes.POINTER(vp)]
-    lib.vistaf_taxel_measure.argtypes = [vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
-    lib.vistaf_taxel_layout_info.argtypes = [vp, vp]
-    lib.vistaf_taxel_destroy.argtypes = [vp]
-    lib.vistaf_taxel_destroy.restype = None
-    lib.vistaf_thermal_create.argtypes = [ci, ci, ci, ci, ci, ci, ci, ci, ci, ci, ctypes.POINTER(vp)]
-    lib.vistaf_thermal_register.argtypes = [vp, vp, vp, ci, vp, vp]
-    lib.vistaf_thermal_measure.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
-    lib.vistaf_thermal_destroy.argtypes = [vp]
-    lib.vistaf_thermal_destroy.restype = None
-    lib.vistaf_temporal_create.argtypes = [ci, ci, ci, cd, cd, cd, cd, ctypes.POINTER(vp)]
-    lib.vistaf_temporal_update.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp]
-    lib.vistaf_temporal_state.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    lib.vistaf_temporal_reset.argtypes = [vp]
-    lib.vistaf_temporal_destroy.argtypes = [vp]
-    lib.vistaf_temporal_destroy.restype = None
-    lib.vistaf_cloud_create.argtypes = [ci, ci, ci, ctypes.c_int64, ci, cd, cd, ctypes.POINTER(vp)]
-    lib.vistaf_cloud_measure.argtypes = [vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp, vp, vp, vp]
-    lib.vistaf_cloud_destroy.argtypes = [vp]
-    lib.vistaf_cloud_destroy.restype = None
-    lib.vistaf_motion_create.argtypes = [ci, ci, ci, ci, ci, cd, ci, ci, ctypes.POINTER(vp)]
-    lib.vistaf_motion_update.argtypes = [vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp]
-    lib.vistaf_motion_reset.argtypes = [vp]
-    lib.vistaf_motion_destroy.argtypes = [vp]
-    lib.vistaf_motion_destroy.restype = None
-    lib.vistaf_pressure_create.argtypes = [ci, ci, ci, ci, ci, cd, cd, cd, ctypes.POINTER(vp)]
-    lib.vistaf_pressure_measure.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp, vp, vp]
-    lib.vistaf_pressure_destroy.argtypes = [vp]
-    lib.vistaf_pressure_destroy.restype = None
-    for fn in (EXPORTS + ALIGN_EXPORTS + TEST_EXPORTS + TEMP_EXPORTS + TEMPMODEL_EXPORTS + TSENSOR_EXPORTS + TRACK_EXPORTS + SHAPE_EXPORTS + TAXEL_EXPORTS +
-               THERMAL_EXPORTS + TEMPORAL_EXPORTS + CLOUD_EXPORTS + MOTION_EXPORTS + PRESSURE_EXPORTS):
-        getattr(lib, fn)
+    for group in SIGNATURES.values():
+        for name, (restype, argtypes) in group.items():
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 

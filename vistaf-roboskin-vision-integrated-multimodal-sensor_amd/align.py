@@ -15,13 +15,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle
 
-NINFO = 12
-
-
-class AlignConfig(ctypes.Structure):
-    _fields_ = [("apply_global_shift", ctypes.c_int32), ("use_ecc", ctypes.c_int32), ("ecc_iters", ctypes.c_int32), ("gray_coeffs", ctypes.c_int32),
-                ("ecc_eps", ctypes.c_double), ("ecc_gauss_sigma", ctypes.c_double), ("shift_blur_sigma", ctypes.c_double)]
+NINFO, AlignConfig = _lib.ALIGN_NINFO, _lib.AlignConfig
 
 
 def circle_from_3_points(p1, p2, p3) -> Tuple[int, int, int]:
@@ -36,22 +32,15 @@ def circle_from_3_points(p1, p2, p3) -> Tuple[int, int, int]:
     return int(round(ux)), int(round(uy)), int(round(r))
 
 
-def _stream_ptr(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-class FtpAligner:
+class FtpAligner(Handle):
     """Session for the alignment of deformed photographs to one reference photograph (full frames, uint8 BGR)."""
+    _destroy = "vistaf_align_destroy"
 
     def __init__(self, reference_bgr, circle: Optional[Tuple[int, int, int]] = None,
                  circle_points: Sequence[Tuple[int, int]] = ((1873, 1703), (1599, 707), (2575, 950)),      # shape_ftp.py:41-43
                  apply_global_shift: bool = True, use_ecc: bool = True, ecc_iters: int = 300, ecc_eps: float = 1e-7,
                  ecc_gauss_sigma: float = 5.0, max_batch: int = 1, device=None, gray_coeffs: int = 0, shift_blur_sigma: float = 7.0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("FtpAligner needs a HIP device (there is no CPU fallback)")
-        self._lib = _lib.load()
-        self._lib.vistaf_align_create.restype = ctypes.c_int
-        self.device = torch.device(device if device is not None else "cuda:0")
+        self._open(device if device is not None else "cuda:0")
         ref = self._as_bgr(reference_bgr)
         if ref.shape[0] != 1:
             raise ValueError("one reference frame expected")
@@ -64,18 +53,14 @@ class FtpAligner:
         self.apply_global_shift = bool(apply_global_shift)      # what thermal.ThermalReadout.from_aligner needs beside the geometry
         cfg.gray_coeffs = int(gray_coeffs)       # 0: OpenCV 4.x BGR2GRAY coefficients, 1: OpenCV 3.x (include/vistaf_align.h)
         self.max_batch = int(max_batch)
-        self._h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_align_create(ctypes.byref(cfg), self.H, self.W, *self.circle_full, self.max_batch, ctypes.byref(self._h)))
+        self._call("vistaf_align_create", ctypes.byref(cfg), self.H, self.W, *self.circle_full, self.max_batch, ctypes.byref(self._h))
         g = [ctypes.c_int32() for _ in range(9)]
-        _lib.check(self._lib.vistaf_align_geometry(self._h, *[ctypes.byref(v) for v in g]))
+        self._call("vistaf_align_geometry", self._h, *[ctypes.byref(v) for v in g], on_device=False)
         self.crop_box = (g[0].value, g[1].value, g[2].value, g[3].value)              # x1, y1, x2, y2
         self.crop_shape = (g[4].value, g[5].value)
         self.circle_crop = (g[6].value, g[7].value, g[8].value)
         self.reference_gray_crop = torch.empty(self.crop_shape, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_align_set_reference(self._h, ctypes.c_void_p(ref.data_ptr()), ctypes.c_void_p(self.reference_gray_crop.data_ptr()),
-                                                             _stream_ptr(self.device)))
+        self._call("vistaf_align_set_reference", self._h, ref.data_ptr(), self.reference_gray_crop.data_ptr(), self._stream())
 
     def _as_bgr(self, frames) -> torch.Tensor:
         t = torch.as_tensor(frames)
@@ -95,20 +80,7 @@ class FtpAligner:
             raise RuntimeError("Reference and deformed images have different sizes.")        # shape_ftp.py:1479-1480
         out = torch.empty((b,) + self.crop_shape, dtype=torch.uint8, device=self.device)
         info = torch.empty((b, NINFO), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_align_batch(self._h, ctypes.c_void_p(t.data_ptr()), b, ctypes.c_void_p(out.data_ptr()),
-                                                     ctypes.c_void_p(info.data_ptr()), _stream_ptr(self.device)))
+        self._call("vistaf_align_batch", self._h, t.data_ptr(), b, out.data_ptr(), info.data_ptr(), self._stream())
         hi = info.cpu().numpy()
         return {"aligned_gray": out, "info": hi, "shift": hi[:, 0:2].copy(), "response": hi[:, 2].copy(), "warp": hi[:, 3:9].reshape(b, 2, 3).copy(),
                 "rho": hi[:, 9].copy(), "ecc_iters": hi[:, 10].astype(int), "ecc_failed": hi[:, 11].astype(bool)}
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            self._lib.vistaf_align_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

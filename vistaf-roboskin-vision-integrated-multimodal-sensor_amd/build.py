@@ -26,13 +26,7 @@ def _newer(target: str, deps) -> bool:
 def build(force: bool = False, verbose: bool = False) -> str:
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + [os.path.join(HERE, "..", "include", "vistaf_ftp.h"), os.path.join(HERE, "..", "include", "vistaf_align.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_temp.h"), os.path.join(HERE, "..", "include", "vistaf_tempmodel.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_tempsensor.h"), os.path.join(HERE, "..", "include", "vistaf_track.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_shape.h"), os.path.join(HERE, "..", "include", "vistaf_taxel.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_thermal.h"), os.path.join(HERE, "..", "include", "vistaf_temporal.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_cloud.h"), os.path.join(HERE, "..", "include", "vistaf_motion.h"),
-                                                     os.path.join(HERE, "..", "include", "vistaf_pressure.h")]
+    hdrs = glob.glob(os.path.join(CSRC, "*.hpp")) + glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "..", "include", "*.h"))
     jobs = []
     objs = []
     for s in srcs:

@@ -16,13 +16,13 @@ from typing import Any, Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._readout import Readout, ptr
+from ._handle import Handle, ptr
 
 CLOUD_POINT_NAMES = _lib.CLOUD_POINT_NAMES
 CLOUD_FRAME_NAMES = _lib.CLOUD_FRAME_NAMES
 
 
-class CloudReadout(Readout):
+class CloudReadout(Handle):
     """A point-cloud read-out for h x w planes, at most `max_batch` frames and `max_points` written points per call.  stride (1..64) keeps
     every stride-th column and row; origin (x, y) is the pixel that becomes X = Y = 0, by default the crop centre ((w - 1) / 2, (h - 1) / 2).
     More points than max_points is not an error: the offsets are never capped, the frame rows count what was written, and `trim` reports
@@ -33,8 +33,8 @@ class CloudReadout(Readout):
         self.h, self.w, self.max_batch, self.max_points, self.stride = int(h), int(w), int(max_batch), int(max_points), int(stride)
         self.origin = ((self.w - 1) / 2.0, (self.h - 1) / 2.0) if origin is None else (float(origin[0]), float(origin[1]))
         self._open(device, need_device=False)
-        _lib.check(self._lib.vistaf_cloud_create(self.h, self.w, self.max_batch, self.max_points, self.stride, self.origin[0], self.origin[1],
-                                                 ctypes.byref(self._h)))
+        self._call("vistaf_cloud_create", self.h, self.w, self.max_batch, self.max_points, self.stride, self.origin[0], self.origin[1],
+                   ctypes.byref(self._h), on_device=False)
 
     def measure(self, depth, mm_per_px, depth_eps_mm: float, status=None, contact_index=None, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
         """depth [B,h,w] float32 (the height map of a predict), mm_per_px [B] float64, status [B] int32 or None (every frame OK; a frame whose
@@ -66,10 +66,9 @@ class CloudReadout(Readout):
             res[name] = t
         res["offsets"] = torch.empty((b + 1,), dtype=torch.int64, device=self.device)
         res["frame"] = torch.empty((b, _lib.NCLOUD_FRAME), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_cloud_measure(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), ptr(idx), float(depth_eps_mm), b,
-                                                      res["points"].data_ptr(), res["pixel"].data_ptr(),
-                                                      ptr(res.get("label")), res["offsets"].data_ptr(), res["frame"].data_ptr(), self._stream()))
+        self._call("vistaf_cloud_measure", self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), ptr(idx), float(depth_eps_mm), b,
+                   res["points"].data_ptr(), res["pixel"].data_ptr(), ptr(res.get("label")), res["offsets"].data_ptr(), res["frame"].data_ptr(),
+                   self._stream())
         return res
 
     def trim(self, out: Dict[str, torch.Tensor]) -> Dict[str, Any]:

@@ -376,42 +376,37 @@ int vistaf_align_create(const vistaf_align_config *cfg, int H, int W, int cx, in
     if (!cfg || !out) return set_error(VISTAF_E_INVALID, "null argument");
     if (H < 16 || W < 16 || r < 4 || max_batch < 1) return set_error(VISTAF_E_INVALID, "bad geometry");
     if (!(cfg->shift_blur_sigma > 0) || cfg->ecc_iters < 1) return set_error(VISTAF_E_INVALID, "bad alignment config");
-    vistaf_align_handle *h = new vistaf_align_handle();
+    Created<vistaf_align_handle> h(new vistaf_align_handle(), vistaf_align_destroy);
     h->cfg = *cfg; h->H = H; h->W = W; h->cx = cx; h->cy = cy; h->r = r; h->maxB = max_batch;
     h->M = optimal_dft(H); h->N = optimal_dft(W);
     // ROI bounding box and local circle (shape_ftp.py:1502-1519)
     h->x1 = std::max(0, cx - r); h->x2 = std::min(W, cx + r); h->y1 = std::max(0, cy - r); h->y2 = std::min(H, cy + r);
     h->cw = h->x2 - h->x1; h->ch = h->y2 - h->y1;
-    if (h->cw < 8 || h->ch < 8) { delete h; return set_error(VISTAF_E_INVALID, "ROI outside the frame"); }
+    if (h->cw < 8 || h->ch < 8) return set_error(VISTAF_E_INVALID, "ROI outside the frame");
     h->cxl = cx - h->x1; h->cyl = cy - h->y1;
     h->rl = std::min(std::min(r, h->cxl), std::min(std::min(h->cyl, h->cw - 1 - h->cxl), h->ch - 1 - h->cyl));
-#define TRYA(x) do { int rc_ = (x); if (rc_) { vistaf_align_destroy(h); return rc_; } } while (0)
     const std::vector<float> t7 = gauss_taps(cfg->shift_blur_sigma);
     h->k7 = (int)t7.size();
-    TRYA(h->allocs.alloc(&h->g7, t7.size()));
-    if (hipMemcpy(h->g7, t7.data(), t7.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_align_destroy(h); return set_error(VISTAF_E_HIP, "memcpy taps"); }
+    TRY(h->allocs.upload(&h->g7, t7));
     if (cfg->ecc_gauss_sigma > 0) {
         const std::vector<float> t5 = gauss_taps(cfg->ecc_gauss_sigma);
         h->k5 = (int)t5.size();
-        TRYA(h->allocs.alloc(&h->g5, t5.size()));
-        if (hipMemcpy(h->g5, t5.data(), t5.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_align_destroy(h); return set_error(VISTAF_E_HIP, "memcpy taps"); }
+        TRY(h->allocs.upload(&h->g5, t5));
     }
-    if (h->k7 > 511 || h->k5 > 511) { vistaf_align_destroy(h); return set_error(VISTAF_E_INVALID, "gaussian sigma too large"); }
+    if (h->k7 > 511 || h->k5 > 511) return set_error(VISTAF_E_INVALID, "gaussian sigma too large");
     const size_t FP = (size_t)H * W, MP = (size_t)h->M * h->N, HP = (size_t)h->M * (h->N / 2 + 1), CP = (size_t)h->ch * h->cw;
-    TRYA(h->allocs.alloc(&h->gray_f, FP)); TRYA(h->allocs.alloc(&h->tmp_f, FP)); TRYA(h->allocs.alloc(&h->pad_f, MP)); TRYA(h->allocs.alloc(&h->corr, MP));
-    TRYA(h->allocs.alloc(&h->F_ref, HP)); TRYA(h->allocs.alloc(&h->F_def, HP));
-    TRYA(h->allocs.alloc(&h->crop_bgr, CP * 3));
-    TRYA(h->allocs.alloc(&h->peak_part, 256));
-    TRYA(h->allocs.alloc(&h->ref_gray, CP)); TRYA(h->allocs.alloc(&h->circ, CP)); TRYA(h->allocs.alloc(&h->tpl, CP)); TRYA(h->allocs.alloc(&h->crop_tmp, CP * max_batch));
-    TRYA(h->allocs.alloc(&h->mov_u8, CP * max_batch)); TRYA(h->allocs.alloc(&h->mov_f, CP * max_batch)); TRYA(h->allocs.alloc(&h->mov_tmp, CP * max_batch));
-    TRYA(h->allocs.alloc(&h->gx, CP * max_batch)); TRYA(h->allocs.alloc(&h->gy, CP * max_batch));
-    TRYA(h->allocs.alloc(&h->st, (size_t)max_batch)); TRYA(h->allocs.alloc(&h->partial, (size_t)max_batch * ECC_BLOCKS * ECC_NSUM));
-    if (hipfftPlan2d(&h->plan_r2c, h->M, h->N, HIPFFT_R2C) != HIPFFT_SUCCESS || hipfftPlan2d(&h->plan_c2r, h->M, h->N, HIPFFT_C2R) != HIPFFT_SUCCESS) {
-        vistaf_align_destroy(h);
+    TRY(h->allocs.alloc(&h->gray_f, FP)); TRY(h->allocs.alloc(&h->tmp_f, FP)); TRY(h->allocs.alloc(&h->pad_f, MP)); TRY(h->allocs.alloc(&h->corr, MP));
+    TRY(h->allocs.alloc(&h->F_ref, HP)); TRY(h->allocs.alloc(&h->F_def, HP));
+    TRY(h->allocs.alloc(&h->crop_bgr, CP * 3));
+    TRY(h->allocs.alloc(&h->peak_part, 256));
+    TRY(h->allocs.alloc(&h->ref_gray, CP)); TRY(h->allocs.alloc(&h->circ, CP)); TRY(h->allocs.alloc(&h->tpl, CP)); TRY(h->allocs.alloc(&h->crop_tmp, CP * max_batch));
+    TRY(h->allocs.alloc(&h->mov_u8, CP * max_batch)); TRY(h->allocs.alloc(&h->mov_f, CP * max_batch)); TRY(h->allocs.alloc(&h->mov_tmp, CP * max_batch));
+    TRY(h->allocs.alloc(&h->gx, CP * max_batch)); TRY(h->allocs.alloc(&h->gy, CP * max_batch));
+    TRY(h->allocs.alloc(&h->st, (size_t)max_batch)); TRY(h->allocs.alloc(&h->partial, (size_t)max_batch * ECC_BLOCKS * ECC_NSUM));
+    if (hipfftPlan2d(&h->plan_r2c, h->M, h->N, HIPFFT_R2C) != HIPFFT_SUCCESS || hipfftPlan2d(&h->plan_c2r, h->M, h->N, HIPFFT_C2R) != HIPFFT_SUCCESS)
         return set_error(VISTAF_E_HIP, "hipfftPlan2d failed");
-    }
     h->have_plans = true;
-    *out = h;
+    *out = h.release();
     return 0;
 }
 

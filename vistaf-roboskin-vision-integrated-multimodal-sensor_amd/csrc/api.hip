@@ -121,11 +121,8 @@ int make_gkern(vistaf_ftp_handle *hd, double sigma, GKern *g)
     if (!(sigma > 0)) return 0;
     if (gauss_ksize(sigma) > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
     const std::vector<float> f = gauss_taps(sigma);
-    const int n = (int)f.size();
-    int rc = dalloc(hd, &g->d, n);
-    if (rc) return rc;
-    if (hipMemcpy(g->d, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(VISTAF_E_HIP, "memcpy gkern");
-    g->k = n;
+    TRY(hd->allocs.upload(&g->d, f));
+    g->k = (int)f.size();
     return 0;
 }
 
@@ -175,14 +172,6 @@ bool fuses(const vistaf_ftp_handle *hd, const GKern &g) { return hd->tiers.fused
 void *chain_scratch(const vistaf_ftp_handle *hd) { return hd->tiers.big_chain ? hd->big_scratch : nullptr; }
 
 float q32_of(double pct) { return (float)pct / 100.0f; }   // np.true_divide(q, float32(100))
-
-int upload_req(vistaf_ftp_handle *hd, float **d, const std::vector<float> &v)
-{
-    int rc = dalloc(hd, d, v.size());
-    if (rc) return rc;
-    if (hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return fail(VISTAF_E_HIP, "memcpy req");
-    return 0;
-}
 
 // launch_select with the session's chain scratch and selection tier
 void select(vistaf_ftp_handle *hd, const float *vals, const uint8_t *mask, size_t mask_stride, const float *le_thr, bool use_abs, const float *reqs, int nreq,
@@ -286,15 +275,6 @@ void ensure_events(vistaf_ftp_handle *hd)
     hd->ev_made = true;
 }
 
-template <typename T>
-int upload(vistaf_ftp_handle *hd, T **d, const std::vector<T> &v)
-{
-    int rc = dalloc(hd, d, v.size());
-    if (rc) return rc;
-    if (hipMemcpy(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return fail(VISTAF_E_HIP, "memcpy upload");
-    return 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -341,15 +321,15 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     if (cfg->n_fft_peaks < 1 || cfg->n_fft_peaks > 64) return fail(VISTAF_E_INVALID, "n_fft_peaks must be 1..64");
     int bwp = std::max(3, cfg->patch_half_width_bins);
     if (2 * bwp + 1 > 255) return fail(VISTAF_E_INVALID, "patch too wide");
-    vistaf_ftp_handle *hd = new vistaf_ftp_handle();
+    Created<vistaf_ftp_handle> own(new vistaf_ftp_handle(), vistaf_ftp_destroy);
+    vistaf_ftp_handle *hd = own.get();
+    DeviceAllocs &mem = hd->allocs;
     hd->cfg = *cfg; hd->h = h; hd->w = w; hd->P = h * w; hd->cx = cx; hd->cy = cy; hd->r = r; hd->maxB = max_batch;
     hd->hcurve = Curve{height_curve->type, height_curve->a, height_curve->b, height_curve->c};
     hd->fcurve = Curve{force_curve->type, force_curve->a, force_curve->b, force_curve->c};
     hd->use_neg = use_negated_height ? 1 : 0;
     int P = hd->P;
     size_t n = (size_t)max_batch * P;
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { vistaf_ftp_destroy(hd); return rc; } } while (0)
     // static planes (shape_ftp.py:383-403, :1519-1528)
     std::vector<uint8_t> roi(P), valid(P);
     std::vector<float> apo(P), roif(P);
@@ -370,10 +350,10 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
             valid[(size_t)y * w + x] = a > 1e-6f;
             roif[(size_t)y * w + x] = roi[(size_t)y * w + x] ? 1.f : 0.f;
         }
-    TRY(upload(hd, &hd->roi, roi)); TRY(upload(hd, &hd->valid, valid)); TRY(upload(hd, &hd->apo, apo));
+    TRY(mem.upload(&hd->roi, roi)); TRY(mem.upload(&hd->valid, valid)); TRY(mem.upload(&hd->apo, apo));
     hd->named["roi"] = {hd->roi, (size_t)P, false};
     TRY(make_gkern(hd, cfg->illum_sigma_px, &hd->g_illum));
-    if (!hd->g_illum.k) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_INVALID, "illum_sigma_px must be > 0"); }
+    if (!hd->g_illum.k) return fail(VISTAF_E_INVALID, "illum_sigma_px must be > 0");
     TRY(make_gkern(hd, cfg->pre_blur_sigma_px, &hd->g_pre));
     TRY(make_gkern(hd, cfg->quality_smooth_sigma_px, &hd->g_qual));
     TRY(make_gkern(hd, cfg->reliable_smooth_sigma_px, &hd->g_rel));
@@ -382,15 +362,13 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     TRY(make_se(cfg->valid_close_kernel, &hd->se_close));
     {   // cv2.getStructuringElement(ELLIPSE, (k,k)) with k as given (shape_ftp.py:1734)
         int k = cfg->dilate_kernel_size;
-        if (k < 1 || k > 33) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_INVALID, "dilate_kernel_size out of range"); }
+        if (k < 1 || k > 33) return fail(VISTAF_E_INVALID, "dilate_kernel_size out of range");
         TRY(make_se(k, &hd->se_contact, false));
     }
     if (!(cfg->reliable_smooth_sigma_px > 0)) {     // the hole stage is live (shape_ftp.py:1770-1801)
         if (cfg->hole_neighborhood_px < 1 || cfg->hole_neighborhood_px > 255 || cfg->hole_min_dist_px < 0 || cfg->inpaint_radius < 1 ||
-            !(cfg->hole_known_fraction >= 0.0)) {
-            vistaf_ftp_destroy(hd);
+            !(cfg->hole_known_fraction >= 0.0))
             return fail(VISTAF_E_INVALID, "hole-stage constants out of range");
-        }
     }
     // workspace
 #define PLANE(T, name) TRY(dalloc(hd, &hd->name, n, #name, (size_t)P * sizeof(T)))
@@ -447,30 +425,29 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     hd->named["mu"] = {hd->mu, sizeof(float), true}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float), true}; hd->named["thr_g"] = {hd->thr_g, sizeof(float), true};
     hd->named["coef"] = {hd->coef, 6 * sizeof(float), true}; hd->named["thr3"] = {hd->thr3, 3 * sizeof(float), true};
     hd->named["core_thr"] = {hd->core_thr, sizeof(float), true}; hd->named["core_med"] = {hd->core_med, sizeof(float), true};
-    TRY(upload_req(hd, &hd->req_hi, {q32_of(cfg->bad_intensity_percentile)}));
-    TRY(upload_req(hd, &hd->req_g, {q32_of(cfg->bad_gradient_percentile)}));
-    TRY(upload_req(hd, &hd->req_med, {-1.0f}));
-    TRY(upload_req(hd, &hd->req_amp, {q32_of(cfg->amp_valid_percentile)}));
-    TRY(upload_req(hd, &hd->req_contact, {q32_of(cfg->contact_percentile), q32_of(95.0), q32_of(98.0)}));
-    TRY(upload_req(hd, &hd->req_core, {q32_of(cfg->contact_core_percentile)}));
-    TRY(upload_req(hd, &hd->req_core_med, {q32_of(cfg->contact_core_percentile), -1.0f}));      // the chained pair: core threshold, median below it
+    TRY(mem.upload(&hd->req_hi, std::vector<float>{q32_of(cfg->bad_intensity_percentile)}));
+    TRY(mem.upload(&hd->req_g, std::vector<float>{q32_of(cfg->bad_gradient_percentile)}));
+    TRY(mem.upload(&hd->req_med, std::vector<float>{-1.0f}));
+    TRY(mem.upload(&hd->req_amp, std::vector<float>{q32_of(cfg->amp_valid_percentile)}));
+    TRY(mem.upload(&hd->req_contact, std::vector<float>{q32_of(cfg->contact_percentile), q32_of(95.0), q32_of(98.0)}));
+    TRY(mem.upload(&hd->req_core, std::vector<float>{q32_of(cfg->contact_core_percentile)}));
+    TRY(mem.upload(&hd->req_core_med, std::vector<float>{q32_of(cfg->contact_core_percentile), -1.0f}));      // the chained pair: core threshold, median below it
     // den of the ROI-wide masked smooth is frame independent: blur(roi) + 1e-6 (shape_ftp.py:1146, :1821)
     TRY(dalloc(hd, &hd->roi_den, (size_t)P));
     if (hd->g_unrel.k) {
         float *tmp_roi = nullptr;
-        TRY(upload(hd, &tmp_roi, roif));
+        TRY(mem.upload(&tmp_roi, roif));
         launch_gauss_rows(tmp_roi, hd->tmpf, hd->g_unrel.d, hd->g_unrel.k, 1, h, w, 0);
         launch_gauss_cols(hd->tmpf, hd->roi_den, hd->g_unrel.d, hd->g_unrel.k, 1, h, w, 0);
         std::vector<float> hden(P);
-        if (hipMemcpy(hden.data(), hd->roi_den, P * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_HIP, "roi_den readback"); }
+        HIPCHK(hipMemcpy(hden.data(), hd->roi_den, P * sizeof(float), hipMemcpyDeviceToHost));
         for (int i = 0; i < P; i++) hden[i] = hden[i] + 1e-6f;
-        if (hipMemcpy(hd->roi_den, hden.data(), P * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_HIP, "roi_den upload"); }
+        HIPCHK(hipMemcpy(hd->roi_den, hden.data(), P * sizeof(float), hipMemcpyHostToDevice));
     }
     hd->Hf = h + 2 * std::max(0, cfg->fft_pad_px);
     hd->Wf = w + 2 * std::max(0, cfg->fft_pad_px);
-    if (hipDeviceSynchronize() != hipSuccess) { vistaf_ftp_destroy(hd); return fail(VISTAF_E_HIP, "create sync"); }
-#undef TRY
-    *out = hd;
+    HIPCHK(hipDeviceSynchronize());
+    *out = own.release();
     return 0;
 }
 

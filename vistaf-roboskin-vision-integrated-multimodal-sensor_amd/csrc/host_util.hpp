@@ -7,6 +7,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -31,6 +32,18 @@ int set_error(int code, const std::string &msg);
         if (r_ != HIPFFT_SUCCESS) return vf::set_error(VISTAF_E_HIP, std::string(#x) + ": hipfft error " + std::to_string((int)r_));      \
     } while (0)
 
+// a step of a create or a launcher that returns a VISTAF code: leave with it unless it is 0
+#define TRY(x)                    \
+    do {                          \
+        const int rc_ = (x);      \
+        if (rc_) return rc_;      \
+    } while (0)
+
+// What a vistaf_*_create holds its new handle in: Created<H> hd(new H(), vistaf_x_destroy).  Every early return (plain, TRY, HIPCHK, FCHK)
+// then destroys the handle and what it owns so far; the last line of the create is `*out = hd.release()`.
+template <class H>
+using Created = std::unique_ptr<H, void (*)(H *)>;
+
 // after a run of launches: 0, or VISTAF_E_HIP with "<what>: <the runtime's text>"
 inline int launch_ok(const char *what)
 {
@@ -51,6 +64,15 @@ struct DeviceAllocs {
         *p = (T *)q;
         return 0;
     }
+    template <typename T>
+    int upload(T **p, const T *host, size_t n)       // a new buffer of n elements holding a copy of host[0..n)
+    {
+        TRY(alloc(p, n));
+        HIPCHK(hipMemcpy(*p, host, n * sizeof(T), hipMemcpyHostToDevice));
+        return 0;
+    }
+    template <typename T>
+    int upload(T **p, const std::vector<T> &host) { return upload(p, host.data(), host.size()); }
     void release(void *p)       // one buffer before the others; null and foreign pointers are ignored
     {
         const auto it = std::find(ptrs.begin(), ptrs.end(), p);
@@ -86,6 +108,22 @@ private:
     ScratchRec *rec_;
     size_t off_ = 0;
 };
+
+// The lazily built workspace of a handle: one buffer of `owner`, laid out by layout(ScratchLayout &), which returns the struct of its
+// pointers.  Sizes it with a null layout, allocates, carves; *bufs and buf are set only when all of it succeeded.  A no-op once buf is set.
+template <class Bufs, class Layout>
+int ensure_carved(DeviceAllocs &owner, void *&buf, Bufs *bufs, Layout layout)
+{
+    if (buf) return 0;
+    ScratchLayout size(nullptr);
+    layout(size);
+    uint8_t *p = nullptr;
+    TRY(owner.alloc(&p, size.bytes()));
+    ScratchLayout carve(p);
+    *bufs = layout(carve);
+    buf = p;
+    return 0;
+}
 
 inline int cv_round(double v) { return (int)std::nearbyint(v); }      // cvRound: half to even
 inline int odd_up(int k) { return (k % 2) ? k : k + 1; }

@@ -311,6 +311,7 @@ struct vistaf_cloud_handle {
     double ox = 0.0, oy = 0.0;
     void *buf = nullptr;
     ClBufs bf = {};
+    DeviceAllocs mem;
 };
 
 extern "C" {
@@ -318,7 +319,7 @@ extern "C" {
 void vistaf_cloud_destroy(vistaf_cloud_handle *cl)
 {
     if (!cl) return;
-    if (cl->buf) (void)hipFree(cl->buf);
+    cl->mem.free_all();
     delete cl;
 }
 
@@ -333,18 +334,16 @@ int vistaf_cloud_create(int h, int w, int max_batch, int64_t max_points, int str
     if (stride < 1 || stride > 64) return set_error(VISTAF_E_INVALID, "stride must be 1..64");
     if (!std::isfinite(origin_x)) return set_error(VISTAF_E_INVALID, "origin_x must be finite");
     if (!std::isfinite(origin_y)) return set_error(VISTAF_E_INVALID, "origin_y must be finite");
-    vistaf_cloud_handle *cl = new vistaf_cloud_handle();
+    Created<vistaf_cloud_handle> cl(new vistaf_cloud_handle(), vistaf_cloud_destroy);
     cl->maxB = max_batch;
     cl->g = ClGeom{(unsigned)h * (unsigned)w, (unsigned)w, (unsigned)h, (unsigned)stride};
     cl->V = cl->g.P % 4u == 0u ? 4 : 1;
     cl->nchunks = (cl->g.P + (unsigned)(CL_NT * cl->V) - 1u) / (unsigned)(CL_NT * cl->V);
-    if ((unsigned long long)max_batch * cl->nchunks > 0x7fffffffull) {                   // the scan indexes the counts with 32 bits
-        delete cl;
+    if ((unsigned long long)max_batch * cl->nchunks > 0x7fffffffull)                     // the scan indexes the counts with 32 bits
         return set_error(VISTAF_E_INVALID, "max_batch times the chunks of a frame must be below 2^31");
-    }
     cl->max_points = (long long)max_points;
     cl->ox = origin_x; cl->oy = origin_y;
-    *out = cl;
+    *out = cl.release();
     return 0;
 }
 
@@ -364,13 +363,7 @@ int vistaf_cloud_measure(vistaf_cloud_handle *cl, const float *d_depth_mm, const
     if (((uintptr_t)d_pixel & 3u) || ((uintptr_t)d_offsets & 7u) || ((uintptr_t)d_frame & 7u))
         return set_error(VISTAF_E_INVALID, "pixel must be 4-byte aligned, offsets and frame 8-byte aligned");
     if (cl->V == 4 && ((uintptr_t)d_depth_mm & 15u)) return set_error(VISTAF_E_INVALID, "h * w is a multiple of 4: depth_mm must be 16-byte aligned");
-    if (!cl->buf) {
-        ScratchLayout count(nullptr);
-        cloud_scratch(count, cl->maxB, cl->nchunks);
-        HIPCHK(hipMalloc(&cl->buf, count.bytes() + 256));
-        ScratchLayout carve(cl->buf);
-        cl->bf = cloud_scratch(carve, cl->maxB, cl->nchunks);
-    }
+    TRY(ensure_carved(cl->mem, cl->buf, &cl->bf, [&](ScratchLayout &L) { return cloud_scratch(L, cl->maxB, cl->nchunks); }));
     const hipStream_t st = (hipStream_t)stream;
     const dim3 grid(cl->nchunks, (unsigned)B);
     const unsigned N = (unsigned)B * cl->nchunks;

@@ -305,6 +305,7 @@ struct vistaf_motion_handle {
     bool have_carry = false;               // false after create and reset: frame 0 of the next update has no frame before it
     void *buf = nullptr;
     MoBufs bf = {};
+    DeviceAllocs mem;
 };
 
 extern "C" {
@@ -312,7 +313,7 @@ extern "C" {
 void vistaf_motion_destroy(vistaf_motion_handle *mo)
 {
     if (!mo) return;
-    if (mo->buf) (void)hipFree(mo->buf);
+    mo->mem.free_all();
     delete mo;
 }
 
@@ -328,10 +329,10 @@ int vistaf_motion_create(int h, int w, int max_batch, int max_contacts, int iter
     if (!(tol_px >= 0.0) || !std::isfinite(tol_px)) return set_error(VISTAF_E_INVALID, "tol_px must be finite and >= 0");
     if (min_pixels < 1) return set_error(VISTAF_E_INVALID, "min_pixels must be >= 1");
     if (init_from_centroid != 0 && init_from_centroid != 1) return set_error(VISTAF_E_INVALID, "init_from_centroid must be 0 or 1");
-    vistaf_motion_handle *mo = new vistaf_motion_handle();
+    Created<vistaf_motion_handle> mo(new vistaf_motion_handle(), vistaf_motion_destroy);
     mo->h = h; mo->w = w; mo->maxB = max_batch; mo->K = max_contacts; mo->iterations = iterations; mo->tol_px = tol_px;
     mo->min_pixels = min_pixels; mo->init_centroid = init_from_centroid;
-    *out = mo;
+    *out = mo.release();
     return 0;
 }
 
@@ -363,13 +364,7 @@ int vistaf_motion_update(vistaf_motion_handle *mo, const float *d_depth_mm, cons
         return set_error(VISTAF_E_INVALID, "contacts, tracks, mm_per_px, motion and frame must be 8-byte aligned");
     const size_t P = (size_t)mo->h * mo->w;
     const int K = mo->K;
-    if (!mo->buf) {
-        ScratchLayout size(nullptr);
-        motion_scratch(size, P, K);
-        HIPCHK(hipMalloc(&mo->buf, size.bytes() + 256));
-        ScratchLayout carve(mo->buf);
-        mo->bf = motion_scratch(carve, P, K);
-    }
+    TRY(ensure_carved(mo->mem, mo->buf, &mo->bf, [&](ScratchLayout &L) { return motion_scratch(L, P, K); }));
     const hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(k_motion, dim3((unsigned)K, (unsigned)B), dim3(MO_NT), 0, st, d_depth_mm, d_contact_index, d_contacts, d_count, d_tracks, d_mm_per_px,
                        mo->bf.depth, mo->bf.index, mo->bf.table, mo->bf.count, mo->have_carry ? 1 : 0, depth_eps_mm, mo->h, mo->w, K, mo->iterations,

@@ -322,25 +322,14 @@ struct vistaf_pressure_handle {
 static int pressure_upload(vistaf_pressure_handle *pr)
 {
     if (pr->uploaded) return 0;
-    ScratchLayout size(nullptr);
-    pressure_scratch(size, pr->maxB, pr->h, pr->w, pr->pad);
-    if (pr->mem.alloc(&pr->d_Ex, pr->Ex.size()) || pr->mem.alloc(&pr->d_Ey, pr->Ey.size()) || pr->mem.alloc(&pr->d_Fy, pr->Fy.size()) ||
-        pr->mem.alloc(&pr->d_Rx, pr->Rx.size()) || pr->mem.alloc((uint8_t **)&pr->buf, size.bytes())) {
-        pr->mem.free_all();
-        return VISTAF_E_HIP;
-    }
-    hipError_t e = hipMemcpy(pr->d_Ex, pr->Ex.data(), pr->Ex.size() * sizeof(double2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pr->d_Ey, pr->Ey.data(), pr->Ey.size() * sizeof(double2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pr->d_Fy, pr->Fy.data(), pr->Fy.size() * sizeof(double2), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(pr->d_Rx, pr->Rx.data(), pr->Rx.size() * sizeof(double), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        pr->mem.free_all();
-        return set_error(VISTAF_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    ScratchLayout carve(pr->buf);
-    pr->bf = pressure_scratch(carve, pr->maxB, pr->h, pr->w, pr->pad);
-    pr->uploaded = true;
-    return 0;
+    int rc = pr->mem.upload(&pr->d_Ex, pr->Ex);
+    if (!rc) rc = pr->mem.upload(&pr->d_Ey, pr->Ey);
+    if (!rc) rc = pr->mem.upload(&pr->d_Fy, pr->Fy);
+    if (!rc) rc = pr->mem.upload(&pr->d_Rx, pr->Rx);
+    if (!rc) rc = ensure_carved(pr->mem, pr->buf, &pr->bf, [&](ScratchLayout &L) { return pressure_scratch(L, pr->maxB, pr->h, pr->w, pr->pad); });
+    if (rc) pr->mem.free_all();                         // the next measure starts over
+    pr->uploaded = !rc;
+    return rc;
 }
 
 extern "C" {
@@ -364,7 +353,7 @@ int vistaf_pressure_create(int h, int w, int max_batch, int max_contacts, int pa
     if (!(E_mpa > 0.0) || !std::isfinite(E_mpa)) return set_error(VISTAF_E_INVALID, "E_mpa must be finite and > 0");
     if (!(nu >= 0.0 && nu <= 0.49)) return set_error(VISTAF_E_INVALID, "nu must be 0..0.49");
     if (!(thickness_mm > 0.0)) return set_error(VISTAF_E_INVALID, "thickness_mm must be > 0 or +inf");
-    vistaf_pressure_handle *pr = new vistaf_pressure_handle();
+    Created<vistaf_pressure_handle> pr(new vistaf_pressure_handle(), vistaf_pressure_destroy);
     pr->h = h; pr->w = w; pr->maxB = max_batch; pr->K = max_contacts; pr->pad = pad_px;
     const int Ph = pr->Ph = h + pad_px, Pw = pr->Pw = w + pad_px, Wh = pr->Wh = Pw / 2 + 1;
     PrModel &m = pr->m;
@@ -393,7 +382,7 @@ int vistaf_pressure_create(int h, int w, int max_batch, int max_contacts, int pa
             pr->Rx[(size_t)(2 * c) * w + x] = e.x;
             pr->Rx[(size_t)(2 * c + 1) * w + x] = e.y;
         }
-    *out = pr;
+    *out = pr.release();
     return 0;
 }
 

@@ -258,9 +258,9 @@ int vistaf_shape_create(int h, int w, int max_batch, int max_contacts, double fi
     if (max_batch < 1 || (long long)max_batch * VISTAF_MAX_CONTACTS > 0x7fffffffll) return set_error(VISTAF_E_INVALID, "max_batch must be 1..2^25");
     if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return set_error(VISTAF_E_INVALID, "max_contacts must be 1..64");
     if (!(fit_min_fraction >= 0.0) || !(fit_min_fraction < 1.0)) return set_error(VISTAF_E_INVALID, "fit_min_fraction must be in [0, 1)");
-    vistaf_shape_handle *sh = new vistaf_shape_handle();
+    Created<vistaf_shape_handle> sh(new vistaf_shape_handle(), vistaf_shape_destroy);
     sh->h = h; sh->w = w; sh->maxB = max_batch; sh->K = max_contacts; sh->fit_min_fraction = fit_min_fraction;
-    *out = sh;
+    *out = sh.release();
     return 0;
 }
 

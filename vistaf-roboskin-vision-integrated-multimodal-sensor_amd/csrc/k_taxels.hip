@@ -256,7 +256,7 @@ int vistaf_taxel_create(int h, int w, int max_batch, const uint16_t *layout, int
         start[v + 1]++;
     }
     for (int t = 0; t < T; t++) start[t + 1] += start[t];
-    vistaf_taxel_handle *tx = new vistaf_taxel_handle();
+    Created<vistaf_taxel_handle> tx(new vistaf_taxel_handle(), vistaf_taxel_destroy);
     tx->h = h; tx->w = w; tx->maxB = max_batch; tx->T = T; tx->ox = origin_x; tx->oy = origin_y;
     tx->pixels.resize(start[T]);
     // counting sort in row-major order: within a taxel the indices ascend
@@ -288,7 +288,7 @@ int vistaf_taxel_create(int h, int w, int max_batch, const uint16_t *layout, int
     }
     while (tx->slots.size() % TX_NW) tx->slots.push_back(TxSlot{-1, 1 << 8});
     tx->start = std::move(start);
-    *out = tx;
+    *out = tx.release();
     return 0;
 }
 

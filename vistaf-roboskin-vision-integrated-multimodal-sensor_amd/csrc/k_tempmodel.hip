@@ -214,10 +214,6 @@ __global__ __launch_bounds__(256) void k_tmodel_rows(const TmDev *__restrict__ p
     out[i] = tm_iso(p, p->iso_x, p->iso_y, tm_eval<R>(p, x0, x1, x2, x3));
 }
 
-int tm_hip(hipError_t e, const char *what)
-{
-    return e == hipSuccess ? 0 : set_error(VISTAF_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
-}
 bool finite_all(const double *v, int n)
 {
     for (int i = 0; i < n; i++)
@@ -229,7 +225,8 @@ bool finite_all(const double *v, int n)
 
 struct vistaf_tmodel {
     TmDev host;          // host copy (iso_x / iso_y point into dev)
-    void *dev = nullptr; // TmDev followed by the isotonic tables
+    char *dev = nullptr; // TmDev followed by the isotonic tables
+    DeviceAllocs mem;
     int device = 0;
 };
 
@@ -296,35 +293,29 @@ int vistaf_tmodel_create(int n_features, const int32_t *feature_planes, const do
             return set_error(VISTAF_E_INVALID, "tmodel_create: out_of_bounds must be 0 (clip) or 1 (nan)");
         t.iso_k = n_iso; t.iso_nan = iso_out_of_bounds; t.iso_xmin = iso_x_min; t.iso_xmax = iso_x_max;
     }
-    vistaf_tmodel *m = new vistaf_tmodel();
-    int rc = tm_hip(hipGetDevice(&m->device), "tmodel_create: hipGetDevice");
+    Created<vistaf_tmodel> m(new vistaf_tmodel(), vistaf_tmodel_destroy);
+    HIPCHK(hipGetDevice(&m->device));
     const size_t bytes = sizeof(TmDev) + 2 * sizeof(double) * (size_t)n_iso;
-    if (!rc) rc = tm_hip(hipMalloc(&m->dev, bytes), "tmodel_create: hipMalloc");
-    if (!rc) {
-        double *tab = (double *)((char *)m->dev + sizeof(TmDev));
-        t.iso_x = n_iso ? tab : nullptr;
-        t.iso_y = n_iso ? tab + n_iso : nullptr;
-        std::vector<char> blob(bytes);
-        std::memcpy(blob.data(), &t, sizeof(TmDev));
-        if (n_iso) {
-            std::memcpy(blob.data() + sizeof(TmDev), iso_x, sizeof(double) * n_iso);
-            std::memcpy(blob.data() + sizeof(TmDev) + sizeof(double) * n_iso, iso_y, sizeof(double) * n_iso);
-        }
-        rc = tm_hip(hipMemcpy(m->dev, blob.data(), bytes, hipMemcpyHostToDevice), "tmodel_create: upload");
+    TRY(m->mem.alloc(&m->dev, bytes));
+    double *tab = (double *)(m->dev + sizeof(TmDev));
+    t.iso_x = n_iso ? tab : nullptr;
+    t.iso_y = n_iso ? tab + n_iso : nullptr;
+    std::vector<char> blob(bytes);
+    std::memcpy(blob.data(), &t, sizeof(TmDev));
+    if (n_iso) {
+        std::memcpy(blob.data() + sizeof(TmDev), iso_x, sizeof(double) * n_iso);
+        std::memcpy(blob.data() + sizeof(TmDev) + sizeof(double) * n_iso, iso_y, sizeof(double) * n_iso);
     }
-    if (rc) {
-        vistaf_tmodel_destroy(m);
-        return rc;
-    }
+    HIPCHK(hipMemcpy(m->dev, blob.data(), bytes, hipMemcpyHostToDevice));
     m->host = t;
-    *out = m;
+    *out = m.release();
     return 0;
 }
 
 void vistaf_tmodel_destroy(vistaf_tmodel *m)
 {
     if (!m) return;
-    if (m->dev) (void)hipFree(m->dev);
+    m->mem.free_all();
     delete m;
 }
 

@@ -310,6 +310,7 @@ struct vistaf_temporal_handle {
     bool reset_pending = true;                          // the state is not read by the next update: it starts from zero
     void *buf = nullptr;
     TpPlanes pl = {};
+    DeviceAllocs mem;
 };
 
 extern "C" {
@@ -317,7 +318,7 @@ extern "C" {
 void vistaf_temporal_destroy(vistaf_temporal_handle *tp)
 {
     if (!tp) return;
-    if (tp->buf) (void)hipFree(tp->buf);
+    tp->mem.free_all();
     delete tp;
 }
 
@@ -335,13 +336,13 @@ int vistaf_temporal_create(int h, int w, int max_batch, double alpha, double on_
     if (!std::isfinite(off_mm) || !(off >= 0.0f)) return set_error(VISTAF_E_INVALID, "off_mm must be finite and >= 0");
     if (!(on > off)) return set_error(VISTAF_E_INVALID, "on_mm must be greater than off_mm");
     if (!std::isfinite(frame_period_s) || !(frame_period_s > 0.0)) return set_error(VISTAF_E_INVALID, "frame_period_s must be finite and > 0");
-    vistaf_temporal_handle *tp = new vistaf_temporal_handle();
+    Created<vistaf_temporal_handle> tp(new vistaf_temporal_handle(), vistaf_temporal_destroy);
     tp->h = h; tp->w = w; tp->maxB = max_batch;
     tp->P = (unsigned)h * (unsigned)w;
     tp->V = tp->P % 4u == 0u ? 4 : 1;
     tp->nchunks = (tp->P + (unsigned)(TP_NT * tp->V) - 1u) / (unsigned)(TP_NT * tp->V);
     tp->prm = TpParams{a, on, off, frame_period_s};
-    *out = tp;
+    *out = tp.release();
     return 0;
 }
 
@@ -362,13 +363,7 @@ int vistaf_temporal_update(vistaf_temporal_handle *tp, const float *d_depth, con
     if (B < 1 || B > tp->maxB) return set_error(VISTAF_E_INVALID, "batch must be 1..max_batch");
     if (tp->V == 4 && ((((uintptr_t)d_depth | (uintptr_t)d_filtered) & 15u) || ((uintptr_t)d_touch & 3u)))
         return set_error(VISTAF_E_INVALID, "h * w is a multiple of 4: depth and filtered must be 16-byte aligned, touch 4-byte aligned");
-    if (!tp->buf) {
-        ScratchLayout count(nullptr);
-        temporal_scratch(count, tp->P, tp->maxB, tp->nchunks);
-        HIPCHK(hipMalloc(&tp->buf, count.bytes() + 256));
-        ScratchLayout carve(tp->buf);
-        tp->pl = temporal_scratch(carve, tp->P, tp->maxB, tp->nchunks);
-    }
+    TRY(ensure_carved(tp->mem, tp->buf, &tp->pl, [&](ScratchLayout &L) { return temporal_scratch(L, tp->P, tp->maxB, tp->nchunks); }));
     const hipStream_t st = (hipStream_t)stream;
     const int reset = tp->reset_pending ? 1 : 0;
     if (tp->V == 4)

@@ -284,10 +284,10 @@ int vistaf_thermal_create(int h, int w, int H, int W, int crop_x1, int crop_y1, 
     if (max_batch < 1 || max_batch > 65535) return set_error(VISTAF_E_INVALID, "max_batch must be 1..65535");
     if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return set_error(VISTAF_E_INVALID, "max_contacts must be 1..64");
     if (surround_margin_px < 0 || surround_margin_px > 4096) return set_error(VISTAF_E_INVALID, "surround_margin_px must be 0..4096");
-    vistaf_thermal_handle *th = new vistaf_thermal_handle();
+    Created<vistaf_thermal_handle> th(new vistaf_thermal_handle(), vistaf_thermal_destroy);
     th->h = h; th->w = w; th->H = H; th->W = W; th->crop_x1 = crop_x1; th->crop_y1 = crop_y1; th->use_shift = apply_global_shift != 0;
     th->maxB = max_batch; th->K = max_contacts; th->margin = surround_margin_px;
-    *out = th;
+    *out = th.release();
     return 0;
 }
 

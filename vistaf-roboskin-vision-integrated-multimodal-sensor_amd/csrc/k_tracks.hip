@@ -248,6 +248,7 @@ struct vistaf_track_handle {
     int32_t *linkrow = nullptr;            // [maxB, 64] parent | origin << 8 of every row, for k_tr_ids
     int8_t *carry_plane = nullptr;         // [P] index plane of the last frame
     TrackState *state = nullptr;
+    DeviceAllocs mem;
 };
 
 extern "C" {
@@ -255,10 +256,7 @@ extern "C" {
 void vistaf_track_destroy(vistaf_track_handle *tr)
 {
     if (!tr) return;
-    (void)hipFree(tr->ovl);
-    (void)hipFree(tr->linkrow);
-    (void)hipFree(tr->carry_plane);
-    (void)hipFree(tr->state);
+    tr->mem.free_all();
     delete tr;
 }
 
@@ -270,17 +268,13 @@ int vistaf_track_create(int h, int w, int max_batch, int max_contacts, double ga
     if (max_batch < 1) return set_error(VISTAF_E_INVALID, "max_batch must be >= 1");
     if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return set_error(VISTAF_E_INVALID, "max_contacts must be 1..64");
     if (!(gate_px >= 0.0) || !(gate_px <= 1.7976931348623157e308)) return set_error(VISTAF_E_INVALID, "gate_px must be finite and >= 0");
-    vistaf_track_handle *tr = new vistaf_track_handle();
+    Created<vistaf_track_handle> tr(new vistaf_track_handle(), vistaf_track_destroy);
     tr->h = h; tr->w = w; tr->P = h * w; tr->maxB = max_batch; tr->K = max_contacts; tr->gate_px = gate_px;
-    hipError_t e = hipMalloc((void **)&tr->ovl, sizeof(unsigned int) * (size_t)max_batch * max_contacts * max_contacts);
-    if (e == hipSuccess) e = hipMalloc((void **)&tr->linkrow, sizeof(int32_t) * (size_t)max_batch * TR_MAXK);
-    if (e == hipSuccess) e = hipMalloc((void **)&tr->carry_plane, (size_t)tr->P + 16);
-    if (e == hipSuccess) e = hipMalloc((void **)&tr->state, sizeof(TrackState));
-    if (e != hipSuccess) {
-        vistaf_track_destroy(tr);
-        return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    }
-    *out = tr;
+    TRY(tr->mem.alloc(&tr->ovl, (size_t)max_batch * max_contacts * max_contacts));
+    TRY(tr->mem.alloc(&tr->linkrow, (size_t)max_batch * TR_MAXK));
+    TRY(tr->mem.alloc(&tr->carry_plane, (size_t)tr->P + 16));
+    TRY(tr->mem.alloc(&tr->state, 1));
+    *out = tr.release();
     return 0;
 }
 

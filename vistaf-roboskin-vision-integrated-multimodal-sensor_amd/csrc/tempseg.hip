@@ -184,8 +184,6 @@ static int seg_ensure(vistaf_tempseg_handle *h)
     const vistaf_tempseg_config *cfg = &h->cfg;
     const int H = h->H, W = h->W, R = cfg->seg_band_radius, pm = h->pm;
     const size_t P = h->P;
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     TRY(h->allocs.alloc(&h->gray, P)); TRY(h->allocs.alloc(&h->g, P)); TRY(h->allocs.alloc(&h->tmpf, P)); TRY(h->allocs.alloc(&h->blur, P)); TRY(h->allocs.alloc(&h->norm, P));
     TRY(h->allocs.alloc(&h->inorm, P)); TRY(h->allocs.alloc(&h->amp, P)); TRY(h->allocs.alloc(&h->med, 4)); TRY(h->allocs.alloc(&h->cnt, 4));
     TRY(h->allocs.alloc(&h->sat0, P)); TRY(h->allocs.alloc(&h->sat, P)); TRY(h->allocs.alloc(&h->roi_eff, P)); TRY(h->allocs.alloc(&h->ma, P)); TRY(h->allocs.alloc(&h->mb, P));
@@ -194,28 +192,24 @@ static int seg_ensure(vistaf_tempseg_handle *h)
     TRY(h->allocs.alloc(&h->partial, (size_t)4 * TS_RB)); TRY(h->allocs.alloc(&h->sums, 8));
     TRY(h->allocs.alloc(&h->Ex, (size_t)W * pm)); TRY(h->allocs.alloc(&h->Gx, (size_t)W * pm)); TRY(h->allocs.alloc(&h->Ey, (size_t)H * pm)); TRY(h->allocs.alloc(&h->Gy, (size_t)H * pm));
     TRY(h->allocs.alloc(&h->T, (size_t)std::max(H, W) * pm)); TRY(h->allocs.alloc(&h->patch, (size_t)pm * pm)); TRY(h->allocs.alloc(&h->z, P)); TRY(h->allocs.alloc(&h->geom, 1));
-    TRY(h->allocs.alloc(&h->win, (size_t)pm * pm)); TRY(h->allocs.alloc(&h->req_med, 1));
     {
         const float neg = -1.0f;                                    // launch_select: a negative request is the median
-        if (hipMemcpy(h->req_med, &neg, sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
+        TRY(h->allocs.upload(&h->req_med, &neg, 1));
         std::vector<float> win((size_t)pm * pm);                    // the band-pass disc (:463-465) as the patch "window"
         for (int a = 0; a < pm; a++)
             for (int c = 0; c < pm; c++) win[(size_t)a * pm + c] = ((a - R) * (a - R) + (c - R) * (c - R) <= R * R) ? 1.0f : 0.0f;
-        if (hipMemcpy(h->win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
+        TRY(h->allocs.upload(&h->win, win));
     }
     h->gksize = 0;
     if (cfg->seg_illum_sigma > 0) {
         const std::vector<float> f = gauss_taps((double)cfg->seg_illum_sigma);      // (size checked at create)
-        const int n = (int)f.size();
-        TRY(h->allocs.alloc(&h->gk, (size_t)n));
-        if (hipMemcpy(h->gk, f.data(), n * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return set_error(VISTAF_E_HIP, "memcpy");
-        h->gksize = n;
+        TRY(h->allocs.upload(&h->gk, f));
+        h->gksize = (int)f.size();
     }
     if (!h->have_plan) {
         if (hipfftPlan2d(&h->plan, H, W, HIPFFT_R2C) != HIPFFT_SUCCESS) return set_error(VISTAF_E_HIP, "hipfftPlan2d failed");
         h->have_plan = true;
     }
-#undef TRY
     h->seg_ready = true;
     return 0;
 }
@@ -232,11 +226,9 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
         if (k > 127) return set_error(VISTAF_E_INVALID, "structuring element wider than 127");
     if (cfg->seg_illum_sigma > 0 && gauss_ksize((double)cfg->seg_illum_sigma) > 511)
         return set_error(VISTAF_E_INVALID, "illumination sigma too large");
-    vistaf_tempseg_handle *h = new vistaf_tempseg_handle();
+    Created<vistaf_tempseg_handle> h(new vistaf_tempseg_handle(), vistaf_tempseg_destroy);
     h->cfg = *cfg; h->H = H; h->W = W; h->P = (size_t)H * W; h->pm = 2 * R + 1;
     const size_t P = h->P;
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { vistaf_tempseg_destroy(h); return rc; } } while (0)
     // what the colour support needs (a mask plane and the morphology's prefix scratch); the segmentation's workspace waits for seg_ensure
     TRY(h->allocs.alloc(&h->m1, P)); TRY(h->allocs.alloc(&h->prefix, P));
     {
@@ -258,12 +250,9 @@ int vistaf_tempseg_create(const vistaf_tempseg_config *cfg, int H, int W, vistaf
         for (int i = 0; i < 9; i++) h->lab.c[i] = cv_round((double)(1 << LAB_SHIFT) * m[i] / wp[i / 3]);
         h->lab.lscale = (116 * 255 + 50) / 100;
         h->lab.lshift = -((16 * 255 * (1 << LAB_SHIFT2) + 50) / 100);
-        TRY(h->allocs.alloc(&h->gamma_tab, (size_t)256)); TRY(h->allocs.alloc(&h->cbrt_tab, (size_t)LAB_CBRT_N));
-        if (hipMemcpy(h->gamma_tab, gt.data(), gt.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(h->cbrt_tab, ct.data(), ct.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { vistaf_tempseg_destroy(h); return set_error(VISTAF_E_HIP, "memcpy"); }
+        TRY(h->allocs.upload(&h->gamma_tab, gt)); TRY(h->allocs.upload(&h->cbrt_tab, ct));
     }
-#undef TRY
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
@@ -394,15 +383,12 @@ int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const 
 static int tm_ensure(vistaf_tempseg_handle *h)
 {
     if (h->tm_ready) return 0;
-    int rc = 0;
-#define TMTRY(x) do { rc = (x); if (rc) return rc; } while (0)
-    TMTRY(h->allocs.alloc(&h->tmA, h->P)); TMTRY(h->allocs.alloc(&h->tmB, h->P));
-    TMTRY(h->allocs.alloc(&h->tmM1, h->P)); TMTRY(h->allocs.alloc(&h->tmM2, h->P));
-    TMTRY(h->allocs.alloc(&h->tm_kx, (size_t)1024)); TMTRY(h->allocs.alloc(&h->tm_ky, (size_t)1024));
+    TRY(h->allocs.alloc(&h->tmA, h->P)); TRY(h->allocs.alloc(&h->tmB, h->P));
+    TRY(h->allocs.alloc(&h->tmM1, h->P)); TRY(h->allocs.alloc(&h->tmM2, h->P));
+    TRY(h->allocs.alloc(&h->tm_kx, (size_t)1024)); TRY(h->allocs.alloc(&h->tm_ky, (size_t)1024));
     uint8_t *p = nullptr;
-    TMTRY(h->allocs.alloc(&p, inpaint_scratch_bytes(1, h->H, h->W))); h->tm_scratch = p;
-    TMTRY(h->allocs.alloc(&h->tm_stats, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_status, (size_t)4)); TMTRY(h->allocs.alloc(&h->tm_counts, (size_t)4));
-#undef TMTRY
+    TRY(h->allocs.alloc(&p, inpaint_scratch_bytes(1, h->H, h->W))); h->tm_scratch = p;
+    TRY(h->allocs.alloc(&h->tm_stats, (size_t)4)); TRY(h->allocs.alloc(&h->tm_status, (size_t)4)); TRY(h->allocs.alloc(&h->tm_counts, (size_t)4));
     h->tm_ready = true;
     return 0;
 }

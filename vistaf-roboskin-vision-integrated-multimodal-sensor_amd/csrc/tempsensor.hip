@@ -15,8 +15,9 @@ using namespace vf;
 
 struct vistaf_tstats {
     int H = 0, W = 0;
-    void *scratch = nullptr, *big = nullptr;
+    uint8_t *scratch = nullptr, *big = nullptr;
     double *out = nullptr;                  // the results when the caller passes no device buffer
+    DeviceAllocs allocs;
 };
 
 struct vistaf_tsensor {
@@ -52,9 +53,7 @@ int vistaf_tsensor_default_config(vistaf_tsensor_config *c)
 void vistaf_tsensor_stats_destroy(vistaf_tstats *s)
 {
     if (!s) return;
-    if (s->scratch) (void)hipFree(s->scratch);
-    if (s->big) (void)hipFree(s->big);
-    if (s->out) (void)hipFree(s->out);
+    s->allocs.free_all();
     delete s;
 }
 
@@ -63,13 +62,12 @@ int vistaf_tsensor_stats_create(int H, int W, vistaf_tstats **out)
     if (!out) return set_error(VISTAF_E_INVALID, "null argument");
     if (H < 1 || W < 1) return set_error(VISTAF_E_INVALID, "map sides must be >= 1");
     if ((long long)H * W > 0x7fffffffll) return set_error(VISTAF_E_INVALID, "map larger than 2^31 pixels");
-    vistaf_tstats *s = new vistaf_tstats();
+    Created<vistaf_tstats> s(new vistaf_tstats(), vistaf_tsensor_stats_destroy);
     s->H = H; s->W = W;
-    hipError_t e = hipMalloc(&s->scratch, tstats_scratch_bytes(H, W));
-    if (e == hipSuccess && tstats_needs_big_scratch(H, W)) e = hipMalloc(&s->big, big_scratch_bytes(1, H, W));
-    if (e == hipSuccess) e = hipMalloc((void **)&s->out, VISTAF_TSENSOR_NSTATS * sizeof(double));
-    if (e != hipSuccess) { vistaf_tsensor_stats_destroy(s); return set_error(VISTAF_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-    *out = s;
+    TRY(s->allocs.alloc(&s->scratch, tstats_scratch_bytes(H, W)));
+    if (tstats_needs_big_scratch(H, W)) TRY(s->allocs.alloc(&s->big, big_scratch_bytes(1, H, W)));
+    TRY(s->allocs.alloc(&s->out, VISTAF_TSENSOR_NSTATS));
+    *out = s.release();
     return 0;
 }
 
@@ -112,12 +110,10 @@ int vistaf_tsensor_create(const vistaf_tsensor_config *cfg, int H, int W, const 
     const int kb = cfg->blur_ksize > 1 ? odd_up(cfg->blur_ksize) : 1;
     if (kb != 1 && kb != 5) return set_error(VISTAF_E_INVALID, "tsensor_create: blur_ksize must be 5 (BLUR_KSIZE as shipped) or <= 1 (no smoothing)");
     if (odd_up(cfg->color_support_dilate) > 33) return set_error(VISTAF_E_INVALID, "tsensor_create: colour support dilation taller than 33");
-    vistaf_tsensor *h = new vistaf_tsensor();
+    Created<vistaf_tsensor> h(new vistaf_tsensor(), vistaf_tsensor_destroy);
     h->cfg = *cfg; h->H = H; h->W = W; h->P = (size_t)H * W;
     h->models[0] = wide_model; h->models[1] = color_model;
     const size_t P = h->P;
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) { vistaf_tsensor_destroy(h); return rc; } } while (0)
     TRY(vistaf_tempseg_create(&cfg->seg, H, W, &h->seg));
     TRY(tempseg_prepare(h->seg));
     TRY(vistaf_tsensor_stats_create(H, W, &h->stats));
@@ -126,8 +122,7 @@ int vistaf_tsensor_create(const vistaf_tsensor_config *cfg, int H, int W, const 
     TRY(h->allocs.alloc(&h->masks, VISTAF_TSENSOR_NMASKS * P)); TRY(h->allocs.alloc(&h->source, P));
     TRY(h->allocs.alloc(&h->kx, 1024)); TRY(h->allocs.alloc(&h->ky, 1024));
     TRY(temp_blur_taps(cfg->smooth_sigma_across, cfg->smooth_sigma_along, h->kx, h->nx, h->ky, h->ny, nullptr));
-#undef TRY
-    *out = h;
+    *out = h.release();
     return 0;
 }
 
@@ -146,8 +141,6 @@ int vistaf_tsensor_predict(vistaf_tsensor *h, const uint8_t *d_bgr, const uint8_
     float *wide = d_wide ? d_wide : h->wide, *color = d_color ? d_color : h->color;
     uint8_t *source = d_source ? d_source : h->source;
     double seg_info[VISTAF_TEMPSEG_NINFO];
-    int rc = 0;
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     // 1-3: segmentation, feature planes, colour support (:770-799 on the full frame)
     TRY(vistaf_tempseg_segment(h->seg, d_bgr, d_roi, dark, light, roi_eff, sat, seg_info, stream));
     TRY(vistaf_temp_feature_planes(h->seg, d_bgr, c.blur_ksize, L, A, B, G, stream));
@@ -168,7 +161,6 @@ int vistaf_tsensor_predict(vistaf_tsensor *h, const uint8_t *d_bgr, const uint8_
     TRY(temp_blur_apply(h->seg, h->fused, d_roi, seg_info[VISTAF_TS_CARRIER_ANGLE_RAD], h->kx, h->nx, h->ky, h->ny, d_final, st));
     // 9: statistics of the final map over its finite pixels
     if (d_stats || stats_host) TRY(vistaf_tsensor_map_statistics(h->stats, d_final, nullptr, d_stats, stats_host, stream));
-#undef TRY
     if (info_host) {
         for (int i = 0; i < VISTAF_TEMPSEG_NINFO; i++) info_host[i] = seg_info[i];
         for (int i = 0; i < 4; i++) info_host[VISTAF_TEMPSEG_NINFO + i] = (double)counts[i];

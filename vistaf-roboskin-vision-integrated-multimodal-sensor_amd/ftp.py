@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, call, stream
 from .config import FtpConfig
 
 SCALAR_NAMES = [
@@ -82,15 +83,10 @@ def estimate_mm_per_px(estimated_grating_period_px: Optional[float], grating_pit
 
 def predict_force_from_volume(best_model: Dict[str, Any], volume_cm3: float) -> float:
     """force_sensor.predict_force_from_volume (Code/force_sensor.py:149-167) through the C ABI."""
-    lib = _lib.load()
     c = _curve(best_model, "force calibration JSON")
     out = ctypes.c_double()
-    _lib.check(lib.vistaf_predict_force_from_volume(ctypes.byref(c), float(volume_cm3), ctypes.byref(out)))
+    call(None, "vistaf_predict_force_from_volume", ctypes.byref(c), float(volume_cm3), ctypes.byref(out))
     return float(out.value)
-
-
-def _stream_ptr(device) -> int:
-    return int(torch.cuda.current_stream(device).cuda_stream)
 
 
 def depth_map_to_volume_cm3(height_map_mm, roi_mask, mm_per_px: float, depth_eps_mm: float = 0.01, device="cuda:0"):
@@ -98,7 +94,7 @@ def depth_map_to_volume_cm3(height_map_mm, roi_mask, mm_per_px: float, depth_eps
 
     height_map_mm: [h,w] or [B,h,w] (numpy or torch); roi_mask: same shape bool/uint8 or None for
     isfinite(height).  Returns (volume_cm3, contact_area_mm2, max_depth_mm) floats, or a [B,3] array."""
-    lib = _lib.load()
+    _lib.load()                                             # a missing library is reported before anything touches the device
     dev = torch.device(device)
     h_t = torch.as_tensor(np.asarray(height_map_mm, dtype=np.float32) if not torch.is_tensor(height_map_mm) else height_map_mm)
     single = h_t.dim() == 2
@@ -115,21 +111,21 @@ def depth_map_to_volume_cm3(height_map_mm, roi_mask, mm_per_px: float, depth_eps
         r_t = r_t.to(dev).to(torch.uint8).contiguous()
     b, hh, ww = h_t.shape
     out = torch.empty((b, 3), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.vistaf_depth_map_to_volume(h_t.data_ptr(), r_t.data_ptr() if r_t is not None else None, b, hh, ww,
-                                                  float(mm_per_px), float(depth_eps_mm), out.data_ptr(), _stream_ptr(dev)))
+    call(dev, "vistaf_depth_map_to_volume", h_t.data_ptr(), r_t.data_ptr() if r_t is not None else None, b, hh, ww, float(mm_per_px),
+         float(depth_eps_mm), out.data_ptr(), stream(dev))
     res = out.cpu().numpy()
     if single:
         return float(res[0, 0]), float(res[0, 1]), float(res[0, 2])
     return res
 
 
-class FtpSensor:
+class FtpSensor(Handle):
     """One FTP session: a reference frame, an ROI circle, constants and the two calibration curves.
 
     The reference frame is demodulated once on the GPU (Code/shape_ftp.py:1632-1639 does it on every
     call); `predict_batch` then runs Code/shape_ftp.py:1641-2037 + the force tail for B frames.
     """
+    _destroy = "vistaf_ftp_destroy"
 
     def __init__(self, reference, roi_circle: Optional[Tuple[int, int, int]] = None, config: Optional[FtpConfig] = None,
                  height_model: Optional[Dict[str, Any]] = None, use_negated_height: bool = True,
@@ -137,12 +133,8 @@ class FtpSensor:
                  frame_shape: Optional[Tuple[int, int]] = None):
         """reference: the session's reference frame, or None for a session that only runs `predict_pairs` (every sample then brings its
         own reference frame; `frame_shape` = (h, w) is needed instead)."""
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
         self._readouts: Dict[str, Tuple[tuple, Any]] = {}          # the live read-outs: name -> (the parameters it was built with, the object)
-        if not torch.cuda.is_available():
-            raise RuntimeError("FtpSensor needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
+        self._open(device)
         self.config = config or FtpConfig.as_shipped()
         if height_model is None or force_model is None:
             raise KeyError("height_model and force_model (the 'best_model' blocks of the calibration JSONs) are required")
@@ -163,17 +155,13 @@ class FtpSensor:
         self.height_model, self.force_model = height_model, force_model
         cc = self.config.to_c()
         hc, fc = _curve(height_model, "calibration"), _curve(force_model, "force calibration JSON")
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_create(ctypes.byref(cc), self.h, self.w, *self.roi_circle, self.max_batch,
-                                                   ctypes.byref(hc), int(bool(use_negated_height)), ctypes.byref(fc),
-                                                   ctypes.byref(self._h)))
-            if ref is not None:
-                fmt = self._format_of(ref)
-                _lib.check(self._lib.vistaf_ftp_set_reference(self._h, ref.data_ptr(), fmt, _stream_ptr(self.device)))
+        self._call("vistaf_ftp_create", ctypes.byref(cc), self.h, self.w, *self.roi_circle, self.max_batch, ctypes.byref(hc),
+                   int(bool(use_negated_height)), ctypes.byref(fc), ctypes.byref(self._h))
         self.reference_info = None
         if ref is not None:
+            self._call("vistaf_ftp_set_reference", self._h, ref.data_ptr(), self._format_of(ref), self._stream())
             info = (ctypes.c_double * _lib.NREFINFO)()
-            _lib.check(self._lib.vistaf_ftp_get_reference_info(self._h, info))
+            self._call("vistaf_ftp_get_reference_info", self._h, info, on_device=False)
             self.reference_info = self._info_dict(info, 0)
 
     @staticmethod
@@ -205,15 +193,7 @@ class FtpSensor:
     def close(self):
         for name in list(getattr(self, "_readouts", {})):
             self._readouts.pop(name)[1].close()
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_ftp_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
     # -- the session's read-outs ------------------------------------------------------------------
     def _matching(self, name: str, key: tuple, reset: Optional[bool] = None, differ: str = ""):
@@ -274,10 +254,8 @@ class FtpSensor:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
             out = self._new_out(b)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_predict_batch(
-                self._h, t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(), out["output_reliable"].data_ptr(),
-                out["scalars"].data_ptr(), out["status"].data_ptr(), _stream_ptr(self.device)))
+        self._call("vistaf_ftp_predict_batch", self._h, t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(),
+                   out["output_reliable"].data_ptr(), out["scalars"].data_ptr(), out["status"].data_ptr(), self._stream())
         self._last_out = out
         return out
 
@@ -295,18 +273,15 @@ class FtpSensor:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
             out = self._new_out(b)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_predict_pairs(
-                self._h, r.data_ptr(), t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(), out["output_reliable"].data_ptr(),
-                out["scalars"].data_ptr(), out["status"].data_ptr(), _stream_ptr(self.device)))
+        self._call("vistaf_ftp_predict_pairs", self._h, r.data_ptr(), t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(),
+                   out["output_reliable"].data_ptr(), out["scalars"].data_ptr(), out["status"].data_ptr(), self._stream())
         self._last_out = out
         return out
 
     def pair_info(self, batch: int):
         """reference_info of every sample of the last predict_pairs"""
         info = (ctypes.c_double * (_lib.NREFINFO * batch))()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_get_pair_info(self._h, batch, info, _stream_ptr(self.device)))
+        self._call("vistaf_ftp_get_pair_info", self._h, batch, info, self._stream())
         return [self._info_dict(info, b * _lib.NREFINFO) for b in range(batch)]
 
     def contacts(self, max_contacts: int = 8, index_plane: bool = False) -> Dict[str, torch.Tensor]:
@@ -325,9 +300,8 @@ class FtpSensor:
         }
         if index_plane:
             out["contact_index"] = torch.empty((b, self.h, self.w), dtype=torch.int8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_contacts(self._h, b, k, out["contacts"].data_ptr(), out["count"].data_ptr(),
-                                                     out["contact_index"].data_ptr() if index_plane else None, _stream_ptr(self.device)))
+        self._call("vistaf_ftp_contacts", self._h, b, k, out["contacts"].data_ptr(), out["count"].data_ptr(),
+                   out["contact_index"].data_ptr() if index_plane else None, self._stream())
         return out
 
     def track(self, max_contacts: int = 8, gate_px: float = 0.0, reset: bool = False) -> Dict[str, torch.Tensor]:
@@ -486,12 +460,10 @@ class FtpSensor:
     def intermediate(self, name: str, batch: int, dtype=torch.float32) -> torch.Tensor:
         """Copy of a named intermediate plane of the last predict_batch (parity tests)."""
         per = ctypes.c_size_t()
-        _lib.check(self._lib.vistaf_ftp_get_intermediate(self._h, name.encode(), None, batch, ctypes.byref(per), None))
+        self._call("vistaf_ftp_get_intermediate", self._h, name.encode(), None, batch, ctypes.byref(per), None, on_device=False)
         nbytes = per.value * (batch if name not in ("roi", "cref", "amp_ref") else 1)
         buf = torch.empty((nbytes,), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_ftp_get_intermediate(self._h, name.encode(), buf.data_ptr(), batch, ctypes.byref(per),
-                                                             _stream_ptr(self.device)))
+        self._call("vistaf_ftp_get_intermediate", self._h, name.encode(), buf.data_ptr(), batch, ctypes.byref(per), self._stream())
         torch.cuda.synchronize(self.device)
         return buf.view(dtype)
 
@@ -499,7 +471,7 @@ class FtpSensor:
         """Test hook (csrc/test_hooks.h, not part of the boundary): select a fallback / opt-in kernel tier of a stage
         ("inpaint_tier", "big_flood_handback", "chamfer_twopass", "telea_two_tier", "telea_mw", "unwrap_fast", "big_chain", "big_queue_lds",
         "big_gq_cap", "big_fallback", "fused_chains", "fused_backend", "select_resident") or keep debug planes ("keep_planes")."""
-        _lib.check(self._lib.vistaf_ftp_test_set(self._h, name.encode(), int(value)))
+        self._call("vistaf_ftp_test_set", self._h, name.encode(), int(value), on_device=False)
 
     def masks(self, index: int = 0) -> Dict[str, np.ndarray]:
         """The seven boolean crop masks of frame `index` of the last predict_batch, under the names the reference stores
@@ -523,12 +495,12 @@ class FtpSensor:
         }
 
     def enable_stage_timing(self, enable: bool = True):
-        _lib.check(self._lib.vistaf_ftp_enable_stage_timing(self._h, int(enable)))
+        self._call("vistaf_ftp_enable_stage_timing", self._h, int(enable), on_device=False)
 
     def stage_times_ms(self) -> Dict[str, float]:
         n = self._lib.vistaf_ftp_stage_count()
         arr = (ctypes.c_float * n)()
-        _lib.check(self._lib.vistaf_ftp_get_stage_times(self._h, arr, n))
+        self._call("vistaf_ftp_get_stage_times", self._h, arr, n, on_device=False)
         return {self._lib.vistaf_ftp_stage_name(i).decode(): float(arr[i]) for i in range(n)}
 
     # -- single-frame API in the reference's vocabulary ---------------------------------------------

@@ -14,14 +14,14 @@ from typing import Dict
 import torch
 
 from . import _lib
-from ._readout import Readout
+from ._handle import Handle
 
 MOTION_NAMES = _lib.MOTION_NAMES
 MOTION_FRAME_NAMES = _lib.MOTION_FRAME_NAMES
 MOTION_STATUS = _lib.MOTION_STATUS
 
 
-class ContactMotion(Readout):
+class ContactMotion(Handle):
     """A motion read-out for h x w planes, at most `max_batch` frames per update, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` and `ContactTracker` that feed it).  Every linked contact is registered with exactly `iterations` (1..16)
     Gauss-Newton steps; its status is ok when the last step is at most `tol_px`.  A parent with fewer than `min_pixels` contact pixels is
@@ -44,9 +44,8 @@ class ContactMotion(Readout):
         if self.min_pixels < 1:
             raise ValueError("min_pixels must be >= 1")
         self._open(device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_motion_create(self.h, self.w, self.max_batch, self.max_contacts, self.iterations, self.tol_px,
-                                                      self.min_pixels, int(self.init_from_centroid), ctypes.byref(self._h)))
+        self._call("vistaf_motion_create", self.h, self.w, self.max_batch, self.max_contacts, self.iterations, self.tol_px, self.min_pixels,
+                   int(self.init_from_centroid), ctypes.byref(self._h))
 
     def update(self, depth_mm, contact_index, contacts, count, tracks, mm_per_px, depth_eps_mm: float) -> Dict[str, torch.Tensor]:
         """depth_mm [B,h,w] float32 (the height map of a predict), contact_index [B,h,w] int8, contacts [B,K,16] float64 and count [B] int32
@@ -67,12 +66,10 @@ class ContactMotion(Readout):
             raise ValueError("depth_eps_mm must be finite")
         out = {"motion": torch.empty((b, self.max_contacts, _lib.NMOTION), dtype=torch.float64, device=self.device),
                "motion_frame": torch.empty((b, _lib.NMOTIONFRAME), dtype=torch.float64, device=self.device)}
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_motion_update(self._h, dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), trk.data_ptr(),
-                                                      mpp.data_ptr(), float(depth_eps_mm), b, out["motion"].data_ptr(),
-                                                      out["motion_frame"].data_ptr(), self._stream()))
+        self._call("vistaf_motion_update", self._h, dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), trk.data_ptr(), mpp.data_ptr(),
+                   float(depth_eps_mm), b, out["motion"].data_ptr(), out["motion_frame"].data_ptr(), self._stream())
         return out
 
     def reset(self):
         """forget the carried frame: every contact of the next frame is without a parent"""
-        _lib.check(self._lib.vistaf_motion_reset(self._h))
+        self._call("vistaf_motion_reset", self._h, on_device=False)

@@ -17,7 +17,7 @@ from typing import Dict
 import torch
 
 from . import _lib
-from ._readout import Readout, ptr
+from ._handle import Handle, ptr
 
 PRESSURE_NAMES = _lib.PRESSURE_NAMES
 PRESSURE_FRAME_NAMES = _lib.PRESSURE_FRAME_NAMES
@@ -36,7 +36,7 @@ def _check_model(max_contacts: int, pad_px: int, E_mpa: float, nu: float, thickn
         raise ValueError("thickness_mm must be > 0 or math.inf")
 
 
-class PressureReadout(Readout):
+class PressureReadout(Handle):
     """A pressure read-out for h x w planes, at most `max_batch` frames per call, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` that feeds it; 0: the plane and the frame row only).  The depth plane is zero-filled to (h + pad_px) x (w + pad_px)
     before the transform, which is what keeps the periodic images of a contact away from it."""
@@ -48,9 +48,8 @@ class PressureReadout(Readout):
         self.E_mpa, self.nu, self.thickness_mm = float(E_mpa), float(nu), float(thickness_mm)
         _check_model(self.max_contacts, self.pad_px, self.E_mpa, self.nu, self.thickness_mm)
         self._open(device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_pressure_create(self.h, self.w, self.max_batch, self.max_contacts, self.pad_px, self.E_mpa, self.nu,
-                                                        self.thickness_mm, ctypes.byref(self._h)))
+        self._call("vistaf_pressure_create", self.h, self.w, self.max_batch, self.max_contacts, self.pad_px, self.E_mpa, self.nu, self.thickness_mm,
+                   ctypes.byref(self._h))
 
     def measure(self, depth_mm, mm_per_px, depth_eps_mm: float, contact_index=None, contacts=None, count=None, force_N=None,
                 status=None) -> Dict[str, torch.Tensor]:
@@ -80,8 +79,6 @@ class PressureReadout(Readout):
                "frame": torch.empty((b, _lib.NPRESSUREFRAME), dtype=torch.float64, device=self.device)}
         if k > 0:
             out["rows"] = torch.empty((b, k, _lib.NPRESSURE), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_pressure_measure(self._h, dep.data_ptr(), ptr(idx), ptr(tab), ptr(cnt), mpp.data_ptr(), ptr(frc), ptr(sta),
-                                                         float(depth_eps_mm), b, out["pressure_kpa"].data_ptr(), ptr(out.get("rows")),
-                                                         out["frame"].data_ptr(), self._stream()))
+        self._call("vistaf_pressure_measure", self._h, dep.data_ptr(), ptr(idx), ptr(tab), ptr(cnt), mpp.data_ptr(), ptr(frc), ptr(sta),
+                   float(depth_eps_mm), b, out["pressure_kpa"].data_ptr(), ptr(out.get("rows")), out["frame"].data_ptr(), self._stream())
         return out

@@ -13,13 +13,13 @@ import math
 import torch
 
 from . import _lib
-from ._readout import Readout
+from ._handle import Handle
 
 SHAPE_NAMES = _lib.SHAPE_NAMES
 SHAPE_FIT = _lib.SHAPE_FIT
 
 
-class ContactShapes(Readout):
+class ContactShapes(Handle):
     """A shape read-out for h x w planes, at most `max_batch` frames per call, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` call that feeds it).  The cap is fitted to the contact pixels at least `fit_min_fraction` of the contact's peak
     deep (0: every contact pixel)."""
@@ -33,9 +33,7 @@ class ContactShapes(Readout):
         if not 0.0 <= self.fit_min_fraction < 1.0:
             raise ValueError("fit_min_fraction must be in [0, 1)")
         self._open(device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_shape_create(self.h, self.w, self.max_batch, self.max_contacts, self.fit_min_fraction,
-                                                     ctypes.byref(self._h)))
+        self._call("vistaf_shape_create", self.h, self.w, self.max_batch, self.max_contacts, self.fit_min_fraction, ctypes.byref(self._h))
 
     def measure(self, depth_mm, contact_index, contacts, count, mm_per_px, depth_eps_mm: float) -> torch.Tensor:
         """depth_mm [B,h,w] float32 (the height map of a predict), contact_index [B,h,w] int8, contacts [B,K,16] float64 and count [B] int32
@@ -53,7 +51,6 @@ class ContactShapes(Readout):
         if not math.isfinite(float(depth_eps_mm)):
             raise ValueError("depth_eps_mm must be finite")
         out = torch.empty((b, self.max_contacts, _lib.NSHAPE), dtype=torch.float64, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_shape_measure(self._h, dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), mpp.data_ptr(),
-                                                      float(depth_eps_mm), b, out.data_ptr(), self._stream()))
+        self._call("vistaf_shape_measure", self._h, dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), mpp.data_ptr(),
+                   float(depth_eps_mm), b, out.data_ptr(), self._stream())
         return out

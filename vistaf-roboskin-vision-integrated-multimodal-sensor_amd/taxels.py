@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._readout import Readout, ptr
+from ._handle import Handle, ptr
 
 TAXEL_NAMES = _lib.TAXEL_NAMES
 TAXEL_FRAME_NAMES = _lib.TAXEL_FRAME_NAMES
@@ -106,7 +106,7 @@ def from_map(array, origin=None, n_taxels: Optional[int] = None, names=None) -> 
     return TaxelLayout(np.where(none, NONE, a).astype(np.uint16), n_taxels, origin if origin is not None else ((w - 1) / 2.0, (h - 1) / 2.0), names)
 
 
-class TaxelReadout(Readout):
+class TaxelReadout(Handle):
     """A taxel read-out for planes of the layout's size, at most `max_batch` frames per call.  The layout is inverted here, on the host;
     `layout_info` needs no device, `measure` does."""
     _destroy = "vistaf_taxel_destroy"
@@ -116,13 +116,13 @@ class TaxelReadout(Readout):
         self.h, self.w = layout.shape
         self.n_taxels = layout.n_taxels
         self._open(device, need_device=False)
-        _lib.check(self._lib.vistaf_taxel_create(self.h, self.w, self.max_batch, layout.map.ctypes.data, self.n_taxels, layout.origin[0],
-                                                 layout.origin[1], ctypes.byref(self._h)))
+        self._call("vistaf_taxel_create", self.h, self.w, self.max_batch, layout.map.ctypes.data, self.n_taxels, layout.origin[0], layout.origin[1],
+                   ctypes.byref(self._h), on_device=False)
 
     def layout_info(self) -> np.ndarray:
         """[T, 4] float64: pixels of the taxel, mean x and mean y of its pixels (NaN for a taxel without pixels), reserved."""
         info = np.empty((self.n_taxels, 4), dtype=np.float64)
-        _lib.check(self._lib.vistaf_taxel_layout_info(self._h, info.ctypes.data))
+        self._call("vistaf_taxel_layout_info", self._h, info.ctypes.data, on_device=False)
         return info
 
     def measure(self, depth_mm, mm_per_px, depth_eps_mm: float, force_N=None, status=None):
@@ -140,7 +140,6 @@ class TaxelReadout(Readout):
             raise ValueError("depth_eps_mm must be finite")
         out = {"taxels": torch.empty((b, self.n_taxels, _lib.NTAXEL), dtype=torch.float64, device=self.device),
                "frame": torch.empty((b, _lib.NTAXELFRAME), dtype=torch.float64, device=self.device)}
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_taxel_measure(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(frc), ptr(sta), float(depth_eps_mm), b,
-                                                      out["taxels"].data_ptr(), out["frame"].data_ptr(), self._stream()))
+        self._call("vistaf_taxel_measure", self._h, dep.data_ptr(), mpp.data_ptr(), ptr(frc), ptr(sta), float(depth_eps_mm), b,
+                   out["taxels"].data_ptr(), out["frame"].data_ptr(), self._stream())
         return out

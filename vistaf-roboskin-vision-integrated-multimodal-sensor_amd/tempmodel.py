@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle, call, stream
 
 FEATURE_NAMES = ("L", "a", "b", "gray")            # plane order of the C ABI (VISTAF_TMODEL_PLANE_*)
 DEFAULT_FEATURES = {3: ("L", "a", "b"), 4: ("L", "a", "b", "gray")}   # the colour and the black model of the reference
@@ -45,6 +46,15 @@ def _f64_vector(v, n: int, what: str) -> np.ndarray:
     if not np.all(np.isfinite(a)):
         raise ValueError(f"{what} must be finite")
     return a
+
+
+class _DeviceModel(Handle):
+    """The copy of a model's parameters on one device (vistaf_tmodel_create)"""
+    _destroy = "vistaf_tmodel_destroy"
+
+    def __init__(self, device: torch.device, *params):
+        self._open(device, need_device=False)
+        self._call("vistaf_tmodel_create", *params, ctypes.byref(self._h))
 
 
 class TempModel:
@@ -107,7 +117,7 @@ class TempModel:
             if oob not in OUT_OF_BOUNDS:
                 raise ValueError(f"isotonic out_of_bounds must be 'clip' or 'nan', got {oob!r}")
             self.isotonic = {"x_thresholds": xt, "y_thresholds": yt, "x_min": xmin, "x_max": xmax, "out_of_bounds": oob}
-        self._handles: Dict[int, ctypes.c_void_p] = {}
+        self._handles: Dict[int, _DeviceModel] = {}
 
     @property
     def degree(self) -> int:
@@ -203,35 +213,24 @@ class TempModel:
         idx = device.index if device.index is not None else torch.cuda.current_device()
         h = self._handles.get(idx)
         if h is None:
-            lib = _lib.load()
-            h = ctypes.c_void_p()
             i32p, dp = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)
             planes = np.asarray([FEATURE_NAMES.index(f) for f in self.features], dtype=np.int32)
             powers = np.ascontiguousarray(self.powers, dtype=np.int32)
             iso = self.isotonic
             xt = np.ascontiguousarray(iso["x_thresholds"]) if iso else None
             yt = np.ascontiguousarray(iso["y_thresholds"]) if iso else None
-            with torch.cuda.device(idx):
-                _lib.check(lib.vistaf_tmodel_create(
-                    len(self.features), planes.ctypes.data_as(i32p), self.mean.ctypes.data_as(dp), self.scale.ctypes.data_as(dp),
-                    int(self.with_mean), int(self.with_std), powers.shape[0], powers.ctypes.data_as(i32p), self.coef.ctypes.data_as(dp),
-                    self.intercept, xt.shape[0] if iso else 0, xt.ctypes.data_as(dp) if iso else None, yt.ctypes.data_as(dp) if iso else None,
-                    iso["x_min"] if iso else 0.0, iso["x_max"] if iso else 0.0, OUT_OF_BOUNDS[iso["out_of_bounds"]] if iso else 0,
-                    ctypes.byref(h)))
-            self._handles[idx] = h
-        return h
+            h = self._handles[idx] = _DeviceModel(
+                torch.device("cuda", idx), len(self.features), planes.ctypes.data_as(i32p), self.mean.ctypes.data_as(dp),
+                self.scale.ctypes.data_as(dp), int(self.with_mean), int(self.with_std), powers.shape[0], powers.ctypes.data_as(i32p),
+                self.coef.ctypes.data_as(dp), self.intercept, xt.shape[0] if iso else 0, xt.ctypes.data_as(dp) if iso else None,
+                yt.ctypes.data_as(dp) if iso else None, iso["x_min"] if iso else 0.0, iso["x_max"] if iso else 0.0,
+                OUT_OF_BOUNDS[iso["out_of_bounds"]] if iso else 0)
+        return h._h
 
     def close(self):
         handles, self._handles = getattr(self, "_handles", {}), {}
         for h in handles.values():
-            if h.value:
-                _lib.load().vistaf_tmodel_destroy(h)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            h.close()
 
     # ---- prediction -----------------------------------------------------------------------------------------------------------------
     def predict(self, X, device=None):
@@ -248,9 +247,7 @@ class TempModel:
         x = x.to(dev).contiguous()
         out = torch.empty(x.shape[0], dtype=torch.float64, device=dev)
         h = self._handle(dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().vistaf_tmodel_predict_rows(h, x.data_ptr(), 0 if x.dtype == torch.float32 else 1, x.shape[0], out.data_ptr(),
-                                                              int(torch.cuda.current_stream(dev).cuda_stream)))
+        call(dev, "vistaf_tmodel_predict_rows", h, x.data_ptr(), 0 if x.dtype == torch.float32 else 1, x.shape[0], out.data_ptr(), stream(dev))
         return out if on_dev else out.cpu().numpy()
 
     def predict_map_for_mask(self, planes, mask, device=None):
@@ -302,7 +299,5 @@ def predict_maps(planes, *pairs: Tuple[TempModel, Any], device=None):
     c_masks = (VP * n)(*[m.data_ptr() for m in masks])
     c_outs = (VP * n)(*[o.data_ptr() for o in outs])
     c_planes = (VP * 4)(*[dplanes[k].data_ptr() if k in dplanes else None for k in FEATURE_NAMES])
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().vistaf_tmodel_predict_maps(n, c_models, c_masks, c_outs, c_planes, shape[0], shape[1],
-                                                          int(torch.cuda.current_stream(dev).cuda_stream)))
+    call(dev, "vistaf_tmodel_predict_maps", n, c_models, c_masks, c_outs, c_planes, shape[0], shape[1], stream(dev))
     return tuple(outs) if on_dev else tuple(o.cpu().numpy() for o in outs)

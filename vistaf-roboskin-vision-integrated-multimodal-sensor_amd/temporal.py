@@ -15,13 +15,13 @@ from typing import Dict
 import torch
 
 from . import _lib
-from ._readout import Readout, ptr
+from ._handle import Handle, ptr
 
 TEMPORAL_NAMES = _lib.TEMPORAL_NAMES
 TEMPORAL_EVENTS = _lib.TEMPORAL_EVENTS
 
 
-class TemporalReadout(Readout):
+class TemporalReadout(Handle):
     """A temporal read-out for h x w planes, at most `max_batch` frames per update.  alpha in (0, 1] is the filter's weight of the new
     frame, on_mm > off_mm >= 0 the thresholds of the touch bit (each rounded once to float32), frame_period_s > 0 the fixed time between
     frames.  Frames of one update are consecutive in time, and frame 0 of an update follows the last frame of the update before it: the
@@ -32,8 +32,8 @@ class TemporalReadout(Readout):
         self.h, self.w, self.max_batch = int(h), int(w), int(max_batch)
         self.alpha, self.on_mm, self.off_mm, self.frame_period_s = float(alpha), float(on_mm), float(off_mm), float(frame_period_s)
         self._open(device, need_device=False)
-        _lib.check(self._lib.vistaf_temporal_create(self.h, self.w, self.max_batch, self.alpha, self.on_mm, self.off_mm, self.frame_period_s,
-                                                    ctypes.byref(self._h)))
+        self._call("vistaf_temporal_create", self.h, self.w, self.max_batch, self.alpha, self.on_mm, self.off_mm, self.frame_period_s,
+                   ctypes.byref(self._h), on_device=False)
 
     def update(self, depth, mm_per_px, status=None, planes: bool = False) -> Dict[str, torch.Tensor]:
         """depth [B,h,w] float32 (the height map of a predict), mm_per_px [B] float64, status [B] int32 or None (every frame OK; a frame
@@ -51,10 +51,8 @@ class TemporalReadout(Readout):
         if planes:
             out["filtered"] = torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device)
             out["touch"] = torch.empty((b, self.h, self.w), dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temporal_update(self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), b,
-                                                        out["frames"].data_ptr(), out["filtered"].data_ptr() if planes else None,
-                                                        out["touch"].data_ptr() if planes else None, self._stream()))
+        self._call("vistaf_temporal_update", self._h, dep.data_ptr(), mpp.data_ptr(), ptr(sta), b, out["frames"].data_ptr(),
+                   out["filtered"].data_ptr() if planes else None, out["touch"].data_ptr() if planes else None, self._stream())
         return out
 
     def state(self) -> Dict[str, torch.Tensor]:
@@ -66,11 +64,10 @@ class TemporalReadout(Readout):
                "touch": torch.empty((self.h, self.w), dtype=torch.uint8, device=self.device),
                "dwell": torch.empty((self.h, self.w), dtype=torch.int32, device=self.device),
                "hold": torch.empty((self.h, self.w), dtype=torch.float32, device=self.device)}
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temporal_state(self._h, out["filt"].data_ptr(), out["rate"].data_ptr(), out["touch"].data_ptr(),
-                                                       out["dwell"].data_ptr(), out["hold"].data_ptr(), self._stream()))
+        self._call("vistaf_temporal_state", self._h, out["filt"].data_ptr(), out["rate"].data_ptr(), out["touch"].data_ptr(), out["dwell"].data_ptr(),
+                   out["hold"].data_ptr(), self._stream())
         return out
 
     def reset(self):
         """forget the stream: the next update starts from an untouched, unprimed state"""
-        _lib.check(self._lib.vistaf_temporal_reset(self._h))
+        self._call("vistaf_temporal_reset", self._h, on_device=False)

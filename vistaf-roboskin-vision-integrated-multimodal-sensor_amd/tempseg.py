@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle
 
 
 @dataclasses.dataclass
@@ -94,31 +95,16 @@ def crop2d(arr: np.ndarray, bbox: Optional[Tuple[int, int, int, int]]) -> np.nda
     return arr[y0:y1, x0:x1]
 
 
-class TempSegmenter:
+class TempSegmenter(Handle):
     """One segmentation session for H x W photographs (workspace, hipFFT plan and tables allocated once)."""
+    _destroy = "vistaf_tempseg_destroy"
 
     def __init__(self, H: int, W: int, config: Optional[TempSegConfig] = None, device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
-        if not torch.cuda.is_available():
-            raise RuntimeError("TempSegmenter needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-        self.device = torch.device(device)
+        self._open(device)
         self.config = config or TempSegConfig()
         self.H, self.W = int(H), int(W)
         cc = self.config.to_c()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_tempseg_create(ctypes.byref(cc), self.H, self.W, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_tempseg_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("vistaf_tempseg_create", ctypes.byref(cc), self.H, self.W, ctypes.byref(self._h))
 
     def segment(self, image_bgr, roi_full) -> Tuple[np.ndarray, np.ndarray, Dict[str, Any]]:
         """segment_dark_light_gratings_periodic_fft(image_bgr, roi_full) -> (dark_final, light_final, pack); pack holds the reference's
@@ -134,10 +120,8 @@ class TempSegmenter:
         roi = (roi.to(self.device) != 0).to(torch.uint8).contiguous()
         outs = [torch.empty((self.H, self.W), dtype=torch.uint8, device=self.device) for _ in range(4)]
         info = (ctypes.c_double * _lib.TEMPSEG_NINFO)()
-        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_tempseg_segment(self._h, img.data_ptr(), roi.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(),
-                                                        outs[2].data_ptr(), outs[3].data_ptr(), info, stream))
+        self._call("vistaf_tempseg_segment", self._h, img.data_ptr(), roi.data_ptr(), outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(),
+                   outs[3].data_ptr(), info, self._stream())
         dark, light, roi_eff, sat = (o.cpu().numpy().astype(bool) for o in outs)
         dbg = {
             "peak_x": int(info[0]), "peak_y": int(info[1]), "phi0_rad": float(info[2]), "mean_gray_A": float(info[3]), "mean_gray_B": float(info[4]),
@@ -163,10 +147,8 @@ class TempSegmenter:
             raise ValueError(f"image must be [{self.H},{self.W},3] uint8 (BGR)")
         img = img.to(self.device).contiguous()
         planes = {k: torch.empty((self.H, self.W), dtype=torch.float32, device=self.device) for k in ("L", "a", "b", "gray")}
-        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_feature_planes(self._h, img.data_ptr(), int(blur_ksize), planes["L"].data_ptr(), planes["a"].data_ptr(),
-                                                            planes["b"].data_ptr(), planes["gray"].data_ptr(), stream))
+        self._call("vistaf_temp_feature_planes", self._h, img.data_ptr(), int(blur_ksize), planes["L"].data_ptr(), planes["a"].data_ptr(),
+                   planes["b"].data_ptr(), planes["gray"].data_ptr(), self._stream())
         return planes
 
     def feature_planes(self, image_bgr, blur_ksize: int = BLUR_KSIZE) -> Dict[str, np.ndarray]:
@@ -182,10 +164,8 @@ class TempSegmenter:
         light, roi_e, sat_m = self._dev_u8(light_mask, "light"), self._dev_u8(roi_eff, "roi_eff"), self._dev_u8(sat, "sat")
         chroma = torch.empty((self.H, self.W), dtype=torch.float32, device=self.device)
         support = torch.empty((self.H, self.W), dtype=torch.uint8, device=self.device)
-        stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_color_support(self._h, a.data_ptr(), b.data_ptr(), light.data_ptr(), roi_e.data_ptr(), sat_m.data_ptr(),
-                                                           float(chroma_min), int(dilate_ksize), chroma.data_ptr(), support.data_ptr(), stream))
+        self._call("vistaf_temp_color_support", self._h, a.data_ptr(), b.data_ptr(), light.data_ptr(), roi_e.data_ptr(), sat_m.data_ptr(),
+                   float(chroma_min), int(dilate_ksize), chroma.data_ptr(), support.data_ptr(), self._stream())
         return support.cpu().numpy().astype(bool), chroma.cpu().numpy()
 
     # ---- third slice: the map-domain stages behind the regressors (parity unpinned, see include/vistaf_temp.h) ------------------------
@@ -195,23 +175,18 @@ class TempSegmenter:
             raise ValueError(f"{what} must be float32 [H, W]")
         return t.to(self.device).contiguous()
 
-    def _stream(self):
-        return int(torch.cuda.current_stream(self.device).cuda_stream)
-
     def clamp_map(self, m, roi, lo: float, hi: float) -> np.ndarray:
         """clamp_map (:538-543)"""
         mp, r = self._dev_f32(m, "map"), self._dev_u8(roi, "roi")
         out = torch.empty_like(mp)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_clamp_map(self._h, mp.data_ptr(), r.data_ptr(), float(lo), float(hi), out.data_ptr(), self._stream()))
+        self._call("vistaf_temp_clamp_map", self._h, mp.data_ptr(), r.data_ptr(), float(lo), float(hi), out.data_ptr(), self._stream())
         return out.cpu().numpy()
 
     def inpaint_temperature_map(self, temp_map, roi_mask, radius: int = 7) -> np.ndarray:
         """inpaint_temperature_map (:546-580)"""
         mp, r = self._dev_f32(temp_map, "map"), self._dev_u8(roi_mask, "roi")
         out = torch.empty_like(mp)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_inpaint_map(self._h, mp.data_ptr(), r.data_ptr(), int(radius), out.data_ptr(), self._stream()))
+        self._call("vistaf_temp_inpaint_map", self._h, mp.data_ptr(), r.data_ptr(), int(radius), out.data_ptr(), self._stream())
         return out.cpu().numpy()
 
     def fuse_maps_per_pixel(self, roi, wide_map, color_map, fuse_config: Optional["_lib.CTempFuseConfig"] = None):
@@ -221,9 +196,8 @@ class TempSegmenter:
         src = torch.empty((self.H, self.W), dtype=torch.uint8, device=self.device)
         cfg = fuse_config or _lib.CTempFuseConfig(COLOR_T_MIN, COLOR_T_MAX, COLOR_GUARD_BAND, SWITCH_MARGIN_C, FINAL_T_MIN, FINAL_T_MAX)
         counts = (ctypes.c_int64 * 4)()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_fuse_maps(self._h, r.data_ptr(), wm.data_ptr(), cm.data_ptr(), ctypes.byref(cfg), fin.data_ptr(), src.data_ptr(),
-                                                       counts, self._stream()))
+        self._call("vistaf_temp_fuse_maps", self._h, r.data_ptr(), wm.data_ptr(), cm.data_ptr(), ctypes.byref(cfg), fin.data_ptr(), src.data_ptr(),
+                   counts, self._stream())
         dbg = {"roi_pixels": int(counts[0]), "wide_ok_pixels": int(counts[1]), "color_ok_pixels": int(counts[2]), "blend_pixels": int(counts[3])}
         return fin.cpu().numpy(), src.cpu().numpy(), dbg
 
@@ -231,9 +205,8 @@ class TempSegmenter:
         """oriented_gaussian_blur_float (:705-747)"""
         mp, r = self._dev_f32(map_f, "map"), self._dev_u8(roi, "roi")
         out = torch.empty_like(mp)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_temp_oriented_blur(self._h, mp.data_ptr(), r.data_ptr(), float(angle_rad), float(sigma_across), float(sigma_along),
-                                                           out.data_ptr(), self._stream()))
+        self._call("vistaf_temp_oriented_blur", self._h, mp.data_ptr(), r.data_ptr(), float(angle_rad), float(sigma_across), float(sigma_along),
+                   out.data_ptr(), self._stream())
         return out.cpu().numpy()
 
 

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._handle import Handle
 from .tempmodel import TempModel
 from .tempseg import (BLUR_KSIZE, COLOR_CHROMA_MIN, COLOR_GUARD_BAND, COLOR_SUPPORT_DILATE, COLOR_T_MAX, COLOR_T_MIN, FINAL_SMOOTH_SIGMA_ACROSS,
                       FINAL_SMOOTH_SIGMA_ALONG, FINAL_T_MAX, FINAL_T_MIN, OUTER_CIRCLE, SWITCH_MARGIN_C, TempSegConfig, roi_mask_from_circle)
@@ -63,30 +64,19 @@ def _stats_dict(v) -> Dict[str, Any]:
     return st
 
 
-class _StatsWorkspace:
+class _StatsWorkspace(Handle):
     """Workspace of vistaf_tsensor_map_statistics for one map size on one device"""
+    _destroy = "vistaf_tsensor_stats_destroy"
 
     def __init__(self, H: int, W: int, device: torch.device):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
-        self.H, self.W, self.device = H, W, device
-        with torch.cuda.device(device):
-            _lib.check(self._lib.vistaf_tsensor_stats_create(H, W, ctypes.byref(self._h)))
+        self._open(device, need_device=False)
+        self.H, self.W = H, W
+        self._call("vistaf_tsensor_stats_create", H, W, ctypes.byref(self._h))
 
     def run(self, m: torch.Tensor, valid: Optional[torch.Tensor]) -> Dict[str, Any]:
         out = (ctypes.c_double * _lib.TSENSOR_NSTATS)()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_tsensor_map_statistics(self._h, m.data_ptr(), None if valid is None else valid.data_ptr(), None, out,
-                                                               int(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._call("vistaf_tsensor_map_statistics", self._h, m.data_ptr(), None if valid is None else valid.data_ptr(), None, out, self._stream())
         return _stats_dict(out)
-
-    def __del__(self):
-        try:
-            if self._h.value:
-                self._lib.vistaf_tsensor_stats_destroy(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
 
 _workspaces: Dict[Tuple[int, int, int], _StatsWorkspace] = {}
@@ -115,19 +105,16 @@ def map_statistics(temp_map_C, valid=None, device=None) -> Dict[str, Any]:
     return ws.run(m, v)
 
 
-class TempSensor:
+class TempSensor(Handle):
     """One session of temperature_sensor.main() for H x W photographs: every buffer, workspace and the smoothing taps are allocated at
     construction (H a multiple of 16, both sides >= 64, as the segmentation needs); `predict` allocates nothing on the library side."""
+    _destroy = "vistaf_tsensor_destroy"
 
     def __init__(self, wide_model: TempModel, color_model: TempModel, frame_shape, roi_full=None, config: Optional[TempSensorConfig] = None,
                  device="cuda:0"):
-        self._lib = _lib.load()
-        self._h = ctypes.c_void_p()
-        if not torch.cuda.is_available():
-            raise RuntimeError("TempSensor needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
+        self._open(device)
         if not isinstance(wide_model, TempModel) or not isinstance(color_model, TempModel):
             raise ValueError("TempSensor needs a wide and a colour TempModel")
-        self.device = torch.device(device)
         self.config = config or TempSensorConfig()
         self.H, self.W = (int(v) for v in tuple(frame_shape)[:2])
         self.wide_model, self.color_model = wide_model, color_model           # the session keeps their device handles
@@ -138,20 +125,8 @@ class TempSensor:
             raise ValueError("roi_full shape does not match the frame")
         self.roi_full = (r.to(self.device) != 0).to(torch.uint8).contiguous()
         cc = self.config.to_c()
-        with torch.cuda.device(self.device):
-            wh, ch = wide_model._handle(self.device), color_model._handle(self.device)
-            _lib.check(self._lib.vistaf_tsensor_create(ctypes.byref(cc), self.H, self.W, wh, ch, ctypes.byref(self._h)))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.vistaf_tsensor_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        wh, ch = wide_model._handle(self.device), color_model._handle(self.device)
+        self._call("vistaf_tsensor_create", ctypes.byref(cc), self.H, self.W, wh, ch, ctypes.byref(self._h))
 
     def predict(self, image_bgr) -> Dict[str, Any]:
         """temperature_sensor.main() on one [H, W, 3] uint8 BGR photograph.  Returns "temperature_map_C" (float32, NaN outside the ROI),
@@ -171,10 +146,8 @@ class TempSensor:
         masks = torch.empty((_lib.TSENSOR_NMASKS,) + shp, dtype=torch.uint8, device=dev)
         info = (ctypes.c_double * _lib.TSENSOR_NINFO)()
         stats = (ctypes.c_double * _lib.TSENSOR_NSTATS)()
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.vistaf_tsensor_predict(self._h, img.data_ptr(), self.roi_full.data_ptr(), final.data_ptr(), source.data_ptr(),
-                                                        wide.data_ptr(), color.data_ptr(), masks.data_ptr(), info, None, stats,
-                                                        int(torch.cuda.current_stream(dev).cuda_stream)))
+        self._call("vistaf_tsensor_predict", self._h, img.data_ptr(), self.roi_full.data_ptr(), final.data_ptr(), source.data_ptr(), wide.data_ptr(),
+                   color.data_ptr(), masks.data_ptr(), info, None, stats, self._stream())
         n0 = _lib.TEMPSEG_NINFO
         dbg = {
             "peak_x": int(info[0]), "peak_y": int(info[1]), "phi0_rad": float(info[2]), "mean_gray_A": float(info[3]), "mean_gray_B": float(info[4]),

@@ -15,13 +15,13 @@ import math
 import torch
 
 from . import _lib
-from ._readout import Readout, ptr
+from ._handle import Handle, ptr
 
 THERMAL_NAMES = _lib.THERMAL_NAMES
 THERMAL_FRAME_NAMES = _lib.THERMAL_FRAME_NAMES
 
 
-class ThermalReadout(Readout):
+class ThermalReadout(Handle):
     """A thermal read-out for h x w crops of H x W photographs cropped at `crop_origin` = (x1, y1), at most `max_batch` frames per call,
     tables of `max_contacts` rows (the K of the `FtpSensor.contacts` call that feeds it).  `apply_global_shift` is the aligner's flag: whether
     the recorded shift was applied to the photograph.  The surround of a contact is its box grown by `surround_margin_px`."""
@@ -38,8 +38,8 @@ class ThermalReadout(Readout):
         if not 0 <= self.surround_margin_px <= 4096:
             raise ValueError("surround_margin_px must be 0..4096")
         self._open(device)
-        _lib.check(self._lib.vistaf_thermal_create(self.h, self.w, self.H, self.W, *self.crop_origin, int(self.apply_global_shift), self.max_batch,
-                                                   self.max_contacts, self.surround_margin_px, ctypes.byref(self._h)))
+        self._call("vistaf_thermal_create", self.h, self.w, self.H, self.W, *self.crop_origin, int(self.apply_global_shift), self.max_batch,
+                   self.max_contacts, self.surround_margin_px, ctypes.byref(self._h), on_device=False)
 
     @classmethod
     def from_aligner(cls, aligner, max_batch=None, max_contacts: int = 8, surround_margin_px: int = 8):
@@ -60,9 +60,7 @@ class ThermalReadout(Readout):
         if not 1 <= b <= self.max_batch:
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         out = torch.empty((b, self.h, self.w), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_thermal_register(self._h, t.data_ptr(), ptr(info), b, out.data_ptr(),
-                                                         self._stream()))
+        self._call("vistaf_thermal_register", self._h, t.data_ptr(), ptr(info), b, out.data_ptr(), self._stream())
         return out
 
     def measure(self, temp_crop, depth_mm, contact_index, contacts, count, depth_eps_mm: float, status=None):
@@ -83,8 +81,6 @@ class ThermalReadout(Readout):
             raise ValueError("depth_eps_mm must be finite")
         out = {"thermal": torch.empty((b, self.max_contacts, _lib.NTHERMAL), dtype=torch.float64, device=self.device),
                "frame": torch.empty((b, _lib.NTHERMALFRAME), dtype=torch.float64, device=self.device)}
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_thermal_measure(self._h, tmp.data_ptr(), dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(),
-                                                        ptr(st), float(depth_eps_mm), b, out["thermal"].data_ptr(),
-                                                        out["frame"].data_ptr(), self._stream()))
+        self._call("vistaf_thermal_measure", self._h, tmp.data_ptr(), dep.data_ptr(), idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), ptr(st),
+                   float(depth_eps_mm), b, out["thermal"].data_ptr(), out["frame"].data_ptr(), self._stream())
         return out

@@ -14,13 +14,13 @@ from typing import Dict
 import torch
 
 from . import _lib
-from ._readout import Readout
+from ._handle import Handle
 
 TRACK_NAMES = _lib.TRACK_NAMES
 TRACK_EVENTS = _lib.TRACK_EVENTS
 
 
-class ContactTracker(Readout):
+class ContactTracker(Handle):
     """A tracker for h x w index planes, at most `max_batch` frames per update, tables of `max_contacts` rows (the K of the
     `FtpSensor.contacts` calls that feed it).  gate_px > 0 adds the gate stage: contacts without any overlap are linked when their centroids
     are no further apart than gate_px, nearest pair first.  Frames of one update are consecutive in time, and frame 0 of an update follows
@@ -34,8 +34,7 @@ class ContactTracker(Readout):
         if not (math.isfinite(self.gate_px) and self.gate_px >= 0.0):
             raise ValueError("gate_px must be finite and >= 0")
         self._open(device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_track_create(self.h, self.w, self.max_batch, self.max_contacts, self.gate_px, ctypes.byref(self._h)))
+        self._call("vistaf_track_create", self.h, self.w, self.max_batch, self.max_contacts, self.gate_px, ctypes.byref(self._h))
 
     def update(self, contact_index, contacts, count) -> Dict[str, torch.Tensor]:
         """contact_index [B,h,w] int8, contacts [B,K,16] float64, count [B] int32, as `FtpSensor.contacts(K, index_plane=True)` returns them
@@ -49,11 +48,10 @@ class ContactTracker(Readout):
             raise ValueError(f"batch {b} outside 1..max_batch {self.max_batch}")
         out = {"tracks": torch.empty((b, self.max_contacts, _lib.NTRACK), dtype=torch.float64, device=self.device),
                "fate": torch.empty((b, self.max_contacts), dtype=torch.int32, device=self.device)}
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.vistaf_track_update(self._h, idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), b, out["tracks"].data_ptr(),
-                                                     out["fate"].data_ptr(), self._stream()))
+        self._call("vistaf_track_update", self._h, idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), b, out["tracks"].data_ptr(),
+                   out["fate"].data_ptr(), self._stream())
         return out
 
     def reset(self):
         """forget the carried frame and restart ids at 0"""
-        _lib.check(self._lib.vistaf_track_reset(self._h))
+        self._call("vistaf_track_reset", self._h, on_device=False)
