@@ -177,7 +177,7 @@ def test_unwrap_with_true_wraps_and_parent_tree(pkg, cal):
     assert np.array_equal(sensor.intermediate("unwrapped", nb).cpu().numpy(), uw_all, equal_nan=True)
     assert np.array_equal(out_flood["height_map_mm"].cpu().numpy(), out["height_map_mm"].cpu().numpy(), equal_nan=True)
     par_all = sensor.intermediate("parent", nb, torch.int32).cpu().numpy()
-    saw_wrap = False
+    saw_wrap, compared = False, 0
     for b in range(nb):
         o = O.process_frame(frames[b], rs, cfg, *cal, keep_intermediates=True)
         it = o["inter"]
@@ -195,10 +195,19 @@ def test_unwrap_with_true_wraps_and_parent_tree(pkg, cal):
         from oracle import cvlite
         _, par_o, _ = cvlite.unwrap_quality_guided(it["wrapped"], o["reliable"], it["quality"], want_tree=True)
         qg = sensor.intermediate("quality", nb).cpu().numpy()[b * P:(b + 1) * P].reshape(n, n)
+        par_g = par_all[b * P:(b + 1) * P].reshape(n, n)
         if np.array_equal(qg, it["quality"]):       # identical keys -> identical tree, bit for bit
-            assert np.array_equal(par_all[b * P:(b + 1) * P].reshape(n, n), par_o)
+            assert np.array_equal(par_g, par_o)
+        # and whatever the planes' last bits: the heap order on the session's OWN wrapped, quality and reliable planes gives its tree and counts
+        rel_g = sensor.intermediate("reliable", nb, torch.uint8).cpu().numpy()[b * P:(b + 1) * P].reshape(n, n)
+        assert np.array_equal(rel_g != 0, o["reliable"])
+        u_own, par_own, _ = cvlite.unwrap_quality_guided(wr, rel_g, qg, want_tree=True)
+        assert np.array_equal(par_g, par_own)
+        assert np.array_equal(par_own >= 0, ~np.isnan(uw)) and int(m.sum()) > 1000 and int((par_own == np.arange(P).reshape(n, n)).sum()) == 1
+        assert np.array_equal(k_gpu, np.rint((u_own[m] - wr[m]) / (2 * np.pi)))
+        compared += 1
         _check_frame(out, b, o, n)
-    assert saw_wrap
+    assert saw_wrap and compared == nb
 
 
 def test_big_frame_flood_and_its_handback_reproduce_the_heap_order(pkg, cal):

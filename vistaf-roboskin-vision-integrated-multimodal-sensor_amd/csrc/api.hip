@@ -1025,6 +1025,24 @@ int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const i
     return hook_finish(peak_bits, nullptr, (hipStream_t)stream);
 }
 
+// ---- the unwrap launcher (consistency check, rank kernels, floods, replay / tree) on caller-supplied device planes
+int vistaf_ftp_test_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent, int32_t *need,
+                           int32_t *status, int B, int h, int w, int variant, void *stream)
+{
+    if (!wrapped || !quality || !mask || !unwrapped || !parent || !status || B < 1 || h < 8 || w < 8 || (size_t)h * w > 0x7fffffffull)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    if (variant == 0 && (!need || !unwrap_fast_supported(h, w)))
+        return fail(VISTAF_E_INVALID, "variant 0: need is null, or the consistency check does not take this shape");
+    const int tier = unwrap_tier(h, w, variant == 2);
+    void *scratch = nullptr;
+    HIPCHK(hipMalloc(&scratch, unwrap_scratch_bytes(B, h, w)));
+    launch_unwrap(wrapped, quality, mask, unwrapped, parent, scratch, status, B, h, w, (hipStream_t)stream, nullptr, nullptr, variant == 2,
+                  variant == 0 ? need : nullptr);
+    const int rc = hook_finish(scratch, nullptr, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+
 int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
                                     size_t *total)
 {

@@ -256,10 +256,18 @@ void launch_unwrap_rank32(const float *quality, const uint8_t *mask, uint32_t *g
 void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t *n, const uint32_t *inv, size_t inv_stride, int32_t *ppar,
                              size_t gstride, int32_t *need_generic, bool force_generic, int B, int h, int w, hipStream_t st, const int32_t *need);
 
+// the flood of an h x w frame (UnwrapTier); with big_handback the frames of the bitmap range still get their 32-bit ranks, and the generic flood grows them
+int unwrap_tier(int h, int w, bool big_handback)
+{
+    if (unwrap_ranked_supported(h, w)) return UWT_RANK16;
+    return unwrap_big_supported(h, w) && !big_handback ? UWT_BITMAP : UWT_GENERIC;
+}
+
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
                    void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid, hipEvent_t ev_flood, bool big_handback,
                    int32_t *need_buf)
 {
+    const int tier = unwrap_tier(h, w);      // by shape: big_handback acts inside the bitmap branch, frame by frame
     const int P = h * w;
     ScratchLayout L(scratch);
     const UnwrapScratch S = unwrap_scratch(L, B, h, w);
@@ -272,12 +280,12 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
         launch_unwrap_fast(wrapped, quality, mask, unwrapped, need_buf, S.check, B, h, w, st);
         need = need_buf;
     }
-    if (unwrap_ranked_supported(h, w)) {
+    if (tier == UWT_RANK16) {
         // frames of at most 65533 padded pixels: uint16 ranks, the batched flood in LDS, then the replay of its pop log
         launch_unwrap_ranked(quality, mask, S.sort_a, S.sort_b, S.ppar, EN, (uint16_t *)S.rank, S.seed, B, h, w, st, ev_flood, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
         launch_unwrap_replay(wrapped, S.pop_log, 2 * EN, S.ppar, EN, parent, unwrapped, B, h, w, st, need);
-    } else if (unwrap_big_supported(h, w)) {
+    } else if (tier == UWT_BITMAP) {
         // frames beyond the uint16 rank range (native crops): 32-bit ranks, bitmap priority queue in LDS, plane in global memory
         // (k_unwrap_big.hip); masks too large for the bitmap (big_handback: every mask) go through the generic kernel, frame by frame
         launch_unwrap_rank32(quality, mask, S.sort_a, S.sort_b, EN, (uint32_t *)S.rank, S.seed, S.nmask, B, h, w, st, need);

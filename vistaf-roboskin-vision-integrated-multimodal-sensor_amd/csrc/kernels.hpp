@@ -204,7 +204,12 @@ struct UfPlanes {
     int rcap, ecap;
 };
 UfPlanes unwrap_fast_planes(ScratchLayout &L, int B, int h, int w);
+bool unwrap_fast_supported(int h, int w);      // the shapes the consistency check takes; launch_unwrap floods every frame of any other
 size_t unwrap_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
+// the priority flood launch_unwrap starts for an h x w frame: uint16 ranks and the batched flood in LDS, 32-bit ranks and the bitmap flood, or
+// the generic one-wave flood; big_handback: the bitmap flood hands every frame to the generic one (a mask beyond its bitmap does so on its own)
+enum UnwrapTier { UWT_RANK16 = 0, UWT_BITMAP = 1, UWT_GENERIC = 2 };
+int unwrap_tier(int h, int w, bool big_handback = false);
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
                    void *scratch, int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_mid,
                    hipEvent_t ev_flood = nullptr, bool big_handback = false, int32_t *need_buf = nullptr);      // need_buf [B]: enables the consistency check (k_unwrap_fast.hip)

@@ -113,6 +113,29 @@ int vistaf_ftp_test_chamfer_dispatch(const uint8_t *mask, int pair, int invert, 
 int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const int32_t *labels, const float *gmax, double min_peak_mm, double rel_frac,
                                 uint8_t *kept, int B, int P, void *stream);
 
+/* launch_unwrap (k_unwrap.hip: the consistency check of k_unwrap_fast.hip, then the rank kernels, the priority flood and the replay / tree
+ * kernel of the frames it hands on) on device planes [B, h, w] of the caller.  Its scratch (unwrap_scratch_bytes) is allocated and freed by
+ * the call, which runs on `stream` and waits for it.
+ * unwrapped[b][p] = float32(float64(wrapped[b][p]) + 2 pi k) with k the integer wrap count of unwrap_quality_guided's spanning tree from the
+ * seed (the largest quality on the mask, the first such pixel in raster order), the quiet NaN 0x7fc00000 wherever the growth never arrives;
+ * parent[b][p] = the pixel's parent in that tree (the seed: itself; -1 where the growth never arrives).  The parent plane is a by-product of
+ * the flood: a frame the consistency check settles (need[b] == 0) leaves parent[b] as the caller passed it.
+ * variant: 0 as a session does: the consistency check first, need[b] = 0 for the frames it settles (an empty mask among them: nothing on it
+ *            contradicts, the plane is all NaN) and 1 for the frames handed to the flood (an inconsistent pair, a pair within 1e-5 of the
+ *            branch cut, more runs or edges than the check's tables, a wrap count beyond +-126),
+ *          1 the floods only (the check is off; `need` may be NULL and is not written),
+ *          2 as 1, with big_handback: the bitmap flood hands every frame to the generic one-wave flood.
+ * Returns UnwrapTier of kernels.hpp, the value of the pure function launch_unwrap dispatches on: 0 uint16 ranks and the batched flood in LDS
+ * ((h + 2)(w + 2) <= 65533), 1 32-bit ranks and the bitmap flood, 2 the generic flood (variant 2 beyond the uint16 range, and every frame of
+ * 2^26 padded pixels and more).  status[b] is only ever written with 2 (the generic flood's frontier overflowed): pass zeros.
+ * Refused with VISTAF_E_INVALID before anything is allocated: a NULL plane (`need` too under variant 0), B < 1, h < 8 or w < 8 (what
+ * vistaf_ftp_create accepts), an unknown variant, variant 0 on a shape the check does not take (h > 32767 or w > 65535).
+ * Contract on the planes, which a session guarantees and the kernels rely on: quality is finite and >= +0 on the mask (compute_reliable_mask
+ * excludes non-finite values, and the blur of a non-negative product has no -0.0: the rank keys order by the float's bits); wrapped is finite
+ * and in [-pi, pi] (float32 pi included), so every pixel pair differs by at most 2 pi. */
+int vistaf_ftp_test_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent, int32_t *need,
+                           int32_t *status, int B, int h, int w, int variant, void *stream);
+
 /* The scratch layout of one stage, from a counting pass of the function its launcher carves with (ScratchLayout, host_util.hpp).  Makes no HIP
  * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored),
  * and "pressure" (the workspace of vistaf_pressure.h; range = pad_px).
