@@ -56,6 +56,32 @@ extern "C" {
 #define VISTAF_FMT_BGR_U8 1     /* [B,h,w,3] uint8 interleaved, OpenCV channel order           */
 #define VISTAF_FMT_GRAY_F16 2   /* [B,h,w] IEEE half holding integral values 0..255            */
 #define VISTAF_FMT_BGR_F16 3    /* [B,h,w,3] IEEE half, interleaved                            */
+/* Camera-native layouts.  Each lands on the plane the four above land on -- float32 holding an integral gray value 0..255 per pixel -- so
+ * a frame in one of them gives the bits of the equivalent GRAY_U8 frame.  GRAY(b, g, r) = (b*3735 + g*19235 + r*9798 + 16384) >> 15, the
+ * fixed point of BGR_U8.  Frames of a batch follow each other without padding (frame stride = the bytes of one frame).
+ *   YUV: gray is the Y byte as delivered (what cv2.COLOR_YUV2GRAY_* gives); chroma is never read.  No range expansion: a limited-range
+ *     camera yields 16..235.  NV21, I420 and YV12 frames have NV12's Y plane and frame size: pass them as NV12.
+ *   Bayer: the name spells the colours of the top-left 2x2 block in reading order, (0,0) (0,1) (1,0) (1,1).  OpenCV names its
+ *     COLOR_Bayer* constants differently (by the second row's second and third pixel): do not map them by name.  The demosaic is this project's own
+ *     definition; the reference never sees a mosaic, so its parity is unpinned.  Integer arithmetic throughout; neighbours outside the
+ *     frame by reflect-101 (-1 -> 1, h -> h-2), which keeps the colour parity, so every h, w >= 2 is legal.  With C the pixel and
+ *     N S W E NW NE SW SE its neighbours:
+ *         cross = (N+S+W+E+2) >> 2   diag = (NW+NE+SW+SE+2) >> 2   hor = (W+E+1) >> 1   ver = (N+S+1) >> 1
+ *         R site: r = C, g = cross, b = diag                 B site: b = C, g = cross, r = diag
+ *         G site in a row with R: g = C, r = hor, b = ver    G site in a row with B: g = C, b = hor, r = ver
+ *     and the pixel's gray is GRAY(b, g, r).
+ * Refused with VISTAF_E_INVALID before any launch: YUYV / UYVY on a session of odd w, NV12 on one of odd h or w, Bayer below 2 x 2.
+ * Pointer alignment the caller owes: 4 bytes for BGRA / RGBA / YUYV / UYVY, 2 for the two F16 formats, 1 for the rest. */
+#define VISTAF_FMT_RGB_U8 4     /* [B,h,w,3] uint8, R first: GRAY(s[2], s[1], s[0])            */
+#define VISTAF_FMT_BGRA_U8 5    /* [B,h,w,4] uint8: GRAY(s[0], s[1], s[2]), alpha ignored      */
+#define VISTAF_FMT_RGBA_U8 6    /* [B,h,w,4] uint8: GRAY(s[2], s[1], s[0]), alpha ignored      */
+#define VISTAF_FMT_YUYV_U8 7    /* [B,h,w/2,4] uint8 = Y0 U Y1 V (V4L2 YUYV / YUY2)            */
+#define VISTAF_FMT_UYVY_U8 8    /* [B,h,w/2,4] uint8 = U Y0 V Y1                               */
+#define VISTAF_FMT_NV12_U8 9    /* per frame h*w bytes of Y, then h*w/2 bytes of chroma: frame stride 3*h*w/2 */
+#define VISTAF_FMT_BAYER_RGGB_U8 10 /* [B,h,w] uint8 mosaic                                    */
+#define VISTAF_FMT_BAYER_GRBG_U8 11
+#define VISTAF_FMT_BAYER_GBRG_U8 12
+#define VISTAF_FMT_BAYER_BGGR_U8 13
 
 /* calibration curve types (shape_ftp.py:682-700, force_sensor.py:129-167) */
 #define VISTAF_CURVE_LINEAR0 0           /* a*v                       */

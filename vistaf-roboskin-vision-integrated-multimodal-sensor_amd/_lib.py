@@ -64,6 +64,12 @@ PRESSURE_FRAME_NAMES = ["contacts", "force_model_N", "tensile_model_N", "outside
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
+# the camera-native layouts (VISTAF_FMT_*, include/vistaf_ftp.h)
+FMT_RGB_U8, FMT_BGRA_U8, FMT_RGBA_U8, FMT_YUYV_U8, FMT_UYVY_U8, FMT_NV12_U8 = 4, 5, 6, 7, 8, 9
+FMT_BAYER_RGGB_U8, FMT_BAYER_GRBG_U8, FMT_BAYER_GBRG_U8, FMT_BAYER_BGGR_U8 = 10, 11, 12, 13
+# the name a caller gives as `format=` -> code; the header's VISTAF_FMT_<NAME>_U8 is the name in capitals (the two F16 formats keep their suffix)
+FORMATS = {"gray": 0, "bgr": 1, "gray_f16": 2, "bgr_f16": 3, "rgb": 4, "bgra": 5, "rgba": 6, "yuyv": 7, "uyvy": 8, "nv12": 9,
+           "bayer_rggb": 10, "bayer_grbg": 11, "bayer_gbrg": 12, "bayer_bggr": 13}
 FRAME_OK, FRAME_EMPTY_RELIABLE, FRAME_QUEUE_OVERFLOW, FRAME_NO_CARRIER = 0, 1, 2, 3
 CURVE_TYPES = {"linear0": 0, "linear": 1, "poly2": 2, "sat_exp": 3, "growth": 4, "hinge_saturating": 5}
 

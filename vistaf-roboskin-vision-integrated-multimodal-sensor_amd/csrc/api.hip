@@ -180,6 +180,17 @@ void select(vistaf_ftp_handle *hd, const float *vals, const uint8_t *mask, size_
     launch_select(vals, mask, mask_stride, le_thr, use_abs, reqs, nreq, out, counts, B, hd->P, st, chain_scratch(hd), hd->tiers.select_resident != 0);
 }
 
+// the frames of a predict or a reference against the session's size: a format the size cannot hold or a pointer below the format's
+// alignment is refused here, before any launch (frame_layout, host_util.hpp)
+int check_frames(const vistaf_ftp_handle *hd, int format, const void *a, const void *b)
+{
+    const FrameLayout fl = frame_layout(format, hd->h, hd->w);
+    if (fl.refusal) return fail(VISTAF_E_INVALID, std::string(fl.refusal) + " (format " + std::to_string(format) + ", frames of " + std::to_string(hd->h) + " x " + std::to_string(hd->w) + ")");
+    if (((uintptr_t)a | (uintptr_t)b) & (uintptr_t)(fl.align - 1))
+        return fail(VISTAF_E_INVALID, "frame format " + std::to_string(format) + " needs frames aligned to " + std::to_string(fl.align) + " bytes");
+    return 0;
+}
+
 // preprocessing shared by reference and deformed frames: frames -> iw (apodised, normalised) and mu
 // frames2 (pair mode, when the workspace holds 2 * nframes): a second set of nframes frames preprocessed in the SAME launches, as frames
 // [nframes, 2 * nframes) of every plane -- the one-wave-per-frame march then runs once over twice as many CUs instead of twice
@@ -188,8 +199,8 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     const vistaf_ftp_config &c = hd->cfg;
     int h = hd->h, w = hd->w, P = hd->P;
     if (timed) hipEventRecord(hd->ev[ST_GRAY_BAD], st);
-    launch_to_gray(frames, format, hd->img, nframes, P, st);
-    if (frames2) launch_to_gray(frames2, format, hd->img + (size_t)nframes * P, nframes, P, st);
+    launch_to_gray(frames, format, hd->img, nframes, P, st, w);
+    if (frames2) launch_to_gray(frames2, format, hd->img + (size_t)nframes * P, nframes, P, st, w);
     const int B = frames2 ? 2 * nframes : nframes;
     hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);
     if (c.bad_pixel_enable) {
@@ -488,7 +499,7 @@ static int reference_search(vistaf_ftp_handle *hd, int nb, CarrierGeom *geom_dev
 int vistaf_ftp_set_reference(vistaf_ftp_handle *hd, const void *d_ref, int format, void *stream)
 {
     if (!hd || !d_ref) return fail(VISTAF_E_INVALID, "null argument");
-    if (format < 0 || format > 3) return fail(VISTAF_E_INVALID, "bad frame format");
+    TRY(check_frames(hd, format, d_ref, nullptr));
     hipStream_t st = (hipStream_t)stream;
     const vistaf_ftp_config &c = hd->cfg;
     int h = hd->h, w = hd->w, Hf = hd->Hf, Wf = hd->Wf, pad = std::max(0, c.fft_pad_px);
@@ -723,7 +734,7 @@ int vistaf_ftp_predict_batch(vistaf_ftp_handle *hd, const void *d_frames, int fo
     if (!hd || !d_frames) return fail(VISTAF_E_INVALID, "null argument");
     if (!hd->have_ref) return fail(VISTAF_E_STATE, "set_reference has not been called");
     if (B < 1 || B > hd->maxB) return fail(VISTAF_E_STATE, "batch exceeds max_batch");
-    if (format < 0 || format > 3) return fail(VISTAF_E_INVALID, "bad frame format");
+    TRY(check_frames(hd, format, d_frames, nullptr));
     if (!(hd->period > 1e-12)) return fail(VISTAF_E_STATE, "Invalid estimated_grating_period_px");
     hipStream_t st = (hipStream_t)stream;
     int h = hd->h, w = hd->w;
@@ -749,7 +760,7 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
 {
     if (!hd || !d_refs || !d_defs) return fail(VISTAF_E_INVALID, "null argument");
     if (B < 1 || B > hd->maxB) return fail(VISTAF_E_STATE, "batch exceeds max_batch");
-    if (format < 0 || format > 3) return fail(VISTAF_E_INVALID, "bad frame format");
+    TRY(check_frames(hd, format, d_refs, d_defs));
     hipStream_t st = (hipStream_t)stream;
     const vistaf_ftp_config &c = hd->cfg;
     int h = hd->h, w = hd->w, P = hd->P, pad = std::max(0, c.fft_pad_px), pm = hd->pmax;

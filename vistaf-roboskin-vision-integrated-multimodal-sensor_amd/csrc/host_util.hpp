@@ -125,6 +125,39 @@ int ensure_carved(DeviceAllocs &owner, void *&buf, Bufs *bufs, Layout layout)
     return 0;
 }
 
+// One frame of h x w pixels in an input format (VISTAF_FMT_*, include/vistaf_ftp.h): its bytes -- the frame stride of a batch -- and the
+// pointer alignment the kernels of that format rely on, or the text of the refusal (then bytes and align are 0).  The one statement of the
+// table in the header: api.hip refuses by it, launch_to_gray strides by it.
+struct FrameLayout { size_t bytes; int align; const char *refusal; };
+inline FrameLayout frame_layout(int format, int h, int w)
+{
+    if (h < 1 || w < 1) return {0, 0, "frame size below 1 x 1"};
+    const size_t P = (size_t)h * (size_t)w;
+    switch (format) {
+    case VISTAF_FMT_GRAY_U8: return {P, 1, nullptr};
+    case VISTAF_FMT_BGR_U8: return {3 * P, 1, nullptr};
+    case VISTAF_FMT_GRAY_F16: return {2 * P, 2, nullptr};
+    case VISTAF_FMT_BGR_F16: return {6 * P, 2, nullptr};
+    case VISTAF_FMT_RGB_U8: return {3 * P, 1, nullptr};
+    case VISTAF_FMT_BGRA_U8:
+    case VISTAF_FMT_RGBA_U8: return {4 * P, 4, nullptr};
+    case VISTAF_FMT_YUYV_U8:
+    case VISTAF_FMT_UYVY_U8:
+        if (w % 2) return {0, 0, format == VISTAF_FMT_YUYV_U8 ? "frame format YUYV needs an even width" : "frame format UYVY needs an even width"};
+        return {2 * P, 4, nullptr};
+    case VISTAF_FMT_NV12_U8:
+        if (h % 2 || w % 2) return {0, 0, "frame format NV12 needs an even height and an even width"};
+        return {P + P / 2, 1, nullptr};
+    case VISTAF_FMT_BAYER_RGGB_U8:
+    case VISTAF_FMT_BAYER_GRBG_U8:
+    case VISTAF_FMT_BAYER_GBRG_U8:
+    case VISTAF_FMT_BAYER_BGGR_U8:
+        if (h < 2 || w < 2) return {0, 0, "frame format Bayer needs at least 2 x 2 pixels"};
+        return {P, 1, nullptr};
+    default: return {0, 0, "bad frame format: not one of VISTAF_FMT_* (0..13)"};
+    }
+}
+
 inline int cv_round(double v) { return (int)std::nearbyint(v); }      // cvRound: half to even
 inline int odd_up(int k) { return (k % 2) ? k : k + 1; }
 inline dim3 grid1(size_t n) { return dim3((unsigned)((n + 255) / 256)); }

@@ -31,8 +31,9 @@ __global__ void k_to_gray(const void *__restrict__ frames, int format, float *__
     gray[i] = v;
 }
 
-void launch_to_gray(const void *frames, int format, float *gray, int B, int P, hipStream_t st)
+void launch_to_gray(const void *frames, int format, float *gray, int B, int P, hipStream_t st, int w)
 {
+    if (format > 3) { launch_camera_gray(frames, format, gray, B, P / w, w, st); return; }      // the camera formats: k_formats.hip
     dim3 grid((P + 255) / 256, B);
     hipLaunchKernelGGL(k_to_gray, grid, dim3(256), 0, st, frames, format, gray, P);
 }

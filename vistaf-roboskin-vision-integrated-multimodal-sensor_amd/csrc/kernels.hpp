@@ -43,7 +43,8 @@ struct RowSpanSE {      // structuring element as per-row x spans (cv::getStruct
 };
 
 // ---- k_basic.hip ------------------------------------------------------------------------------
-void launch_to_gray(const void *frames, int format, float *gray, int B, int P, hipStream_t st);
+// w: the frame's width, which the camera formats (VISTAF_FMT_RGB_U8 and up, k_formats.hip) need; formats 0..3 are planes of P pixels
+void launch_to_gray(const void *frames, int format, float *gray, int B, int P, hipStream_t st, int w = 0);
 void launch_sobel_mag(const float *img, float *grad, int B, int h, int w, hipStream_t st);
 void launch_bad_flags(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g,
                       uint8_t *bad, int B, int P, hipStream_t st);
@@ -58,7 +59,12 @@ void launch_illum_norm(const float *img, const float *blur, float *out, int B, i
 void launch_mul_static(const float *a, const float *stat, float *out, int B, int P, hipStream_t st);
 void launch_count_u8(const uint8_t *m, int *counts, int B, int P, hipStream_t st);
 
-constexpr int GF_MAXK = 15;     // longest Gaussian that takes the one-kernel LDS tile (gauss_tile.hpp); longer ones run a row and a column kernel
+// ---- k_formats.hip: the camera formats (VISTAF_FMT_RGB_U8 .. VISTAF_FMT_BAYER_BGGR_U8) onto the gray plane; launch_to_gray dispatches here ----
+// frames: B frames of h x w in `format`, one behind the other (host_util.hpp frame_layout states the stride and the pointer alignment relied
+// on); gray: [B, h*w] float32, 8-byte aligned.  The caller has checked format and size with frame_layout.
+void launch_camera_gray(const void *frames, int format, float *gray, int B, int h, int w, hipStream_t st);
+
+constexpr int GF_MAXK = 15;    // longest Gaussian that takes the one-kernel LDS tile (gauss_tile.hpp); longer ones run a row and a column kernel
 
 // ---- k_blurchain.hip: short blurs (ksize <= GF_MAXK) with their neighbouring element-wise passes fused in ------------------------------
 // iw = blur(img / (blur_illum + 1e-6) - 1) * apo

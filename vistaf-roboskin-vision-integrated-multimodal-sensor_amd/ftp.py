@@ -119,6 +119,78 @@ def depth_map_to_volume_cm3(height_map_mm, roi_mask, mm_per_px: float, depth_eps
     return res
 
 
+# ---- input frame layouts (VISTAF_FMT_*, include/vistaf_ftp.h): device-free ---------------------------------------------------------------
+_FORMAT_NAMES = {code: name for name, code in _lib.FORMATS.items()}
+_F16_FORMATS = (_lib.FMT_GRAY_F16, _lib.FMT_BGR_F16)
+_CHANNELS = {_lib.FMT_BGR_U8: 3, _lib.FMT_BGR_F16: 3, _lib.FMT_RGB_U8: 3, _lib.FMT_BGRA_U8: 4, _lib.FMT_RGBA_U8: 4}
+_YUV422 = (_lib.FMT_YUYV_U8, _lib.FMT_UYVY_U8)
+_ALIGN = {_lib.FMT_GRAY_F16: 2, _lib.FMT_BGR_F16: 2, _lib.FMT_BGRA_U8: 4, _lib.FMT_RGBA_U8: 4, _lib.FMT_YUYV_U8: 4, _lib.FMT_UYVY_U8: 4}
+
+
+def _format_code(format) -> int:
+    """a name of `_lib.FORMATS` or a VISTAF_FMT_* code -> the code; ValueError for anything else"""
+    if isinstance(format, str):
+        if format not in _lib.FORMATS:
+            raise ValueError(f"unknown frame format {format!r}: one of {', '.join(_lib.FORMATS)}")
+        return _lib.FORMATS[format]
+    if isinstance(format, bool) or not isinstance(format, (int, np.integer)) or int(format) not in _FORMAT_NAMES:
+        raise ValueError(f"unknown frame format {format!r}: a name of _lib.FORMATS or a code 0..{len(_FORMAT_NAMES) - 1}")
+    return int(format)
+
+
+def _frame_shapes(code: int, h: int, w: int):
+    """the shapes one frame of h x w pixels may come in, the layout of the header's table first; ValueError where the format cannot hold the size"""
+    name = _FORMAT_NAMES[code]
+    if h < 1 or w < 1:
+        raise ValueError(f"frame size {h} x {w} is below 1 x 1")
+    if code in _CHANNELS:
+        return [(h, w, _CHANNELS[code])]
+    if code in _YUV422:
+        if w % 2:
+            raise ValueError(f"frame format {name} needs an even width, not {w}")
+        return [(h, w // 2, 4), (h, 2 * w)]
+    if code == _lib.FMT_NV12_U8:
+        if h % 2 or w % 2:
+            raise ValueError(f"frame format nv12 needs an even height and an even width, not {h} x {w}")
+        return [(3 * h // 2, w), (3 * h * w // 2,)]
+    if code >= _lib.FMT_BAYER_RGGB_U8 and (h < 2 or w < 2):
+        raise ValueError(f"frame format {name} needs at least 2 x 2 pixels, not {h} x {w}")
+    return [(h, w)]
+
+
+def frame_layout(format, h: int, w: int):
+    """One frame of h x w pixels in `format` (a name of `_lib.FORMATS` or a VISTAF_FMT_* code): (shape, dtype, nbytes).  A batch is
+    [B, *shape]; its frames follow each other without padding.  yuyv / uyvy may also come as [h, 2w] and nv12 (shape [3h/2, w]: the Y plane,
+    then the chroma rows) as [3hw/2].  ValueError for an unknown format and for a size the format cannot hold: yuyv / uyvy at odd w, nv12
+    at odd h or w, a Bayer mosaic below 2 x 2.  Needs no device."""
+    code = _format_code(format)
+    shape = _frame_shapes(code, int(h), int(w))[0]
+    dtype = torch.float16 if code in _F16_FORMATS else torch.uint8
+    return shape, dtype, int(np.prod(shape)) * (2 if code in _F16_FORMATS else 1)
+
+
+def _frame_size(code: int, shape) -> Tuple[int, int]:
+    """(h, w) of a single frame of this shape (a leading batch dimension of 1 allowed): what a session reads off its reference frame"""
+    shape = tuple(int(v) for v in shape)
+    rank = 3 if code in _CHANNELS else 2
+    if code in _YUV422 and len(shape) >= 3 and shape[-1] == 4:
+        rank = 3
+    if len(shape) == rank + 1 and shape[0] == 1:
+        shape = shape[1:]
+    bad = ValueError(f"a reference frame of shape {shape} is not one frame in format {_FORMAT_NAMES[code]}")
+    if len(shape) != rank:
+        raise bad
+    if code in _YUV422:
+        if rank == 2 and shape[1] % 2:
+            raise bad
+        return shape[0], shape[1] * 2 if rank == 3 else shape[1] // 2
+    if code == _lib.FMT_NV12_U8:
+        if shape[0] % 3:
+            raise bad
+        return shape[0] // 3 * 2, shape[1]
+    return shape[0], shape[1]
+
+
 class FtpSensor(Handle):
     """One FTP session: a reference frame, an ROI circle, constants and the two calibration curves.
 
@@ -130,9 +202,9 @@ class FtpSensor(Handle):
     def __init__(self, reference, roi_circle: Optional[Tuple[int, int, int]] = None, config: Optional[FtpConfig] = None,
                  height_model: Optional[Dict[str, Any]] = None, use_negated_height: bool = True,
                  force_model: Optional[Dict[str, Any]] = None, max_batch: int = 256, device="cuda:0",
-                 frame_shape: Optional[Tuple[int, int]] = None):
+                 frame_shape: Optional[Tuple[int, int]] = None, format=None):
         """reference: the session's reference frame, or None for a session that only runs `predict_pairs` (every sample then brings its
-        own reference frame; `frame_shape` = (h, w) is needed instead)."""
+        own reference frame; `frame_shape` = (h, w) is needed instead).  format: the layout of `reference` (see `predict_batch`)."""
         self._readouts: Dict[str, Tuple[tuple, Any]] = {}          # the live read-outs: name -> (the parameters it was built with, the object)
         self._open(device)
         self.config = config or FtpConfig.as_shipped()
@@ -143,11 +215,16 @@ class FtpSensor(Handle):
                 raise ValueError("a session without a reference frame needs frame_shape=(h, w)")
             ref = None
             self.h, self.w = int(frame_shape[0]), int(frame_shape[1])
+        elif format is not None:
+            shape = reference.shape if hasattr(reference, "shape") else np.asarray(reference).shape
+            self.h, self.w = _frame_size(_format_code(format), shape)
+            ref, ref_format = self._frames_in(reference, format)
         else:
             ref = self._as_frames(reference)
             if ref.shape[0] != 1:
                 raise ValueError("reference must be a single frame")
             self.h, self.w = int(ref.shape[1]), int(ref.shape[2])
+            ref_format = self._format_of(ref)
         if roi_circle is None:
             roi_circle = (self.w // 2, self.h // 2, min(self.h, self.w) // 2 - 1)
         self.roi_circle = tuple(int(v) for v in roi_circle)
@@ -159,7 +236,7 @@ class FtpSensor(Handle):
                    int(bool(use_negated_height)), ctypes.byref(fc), ctypes.byref(self._h))
         self.reference_info = None
         if ref is not None:
-            self._call("vistaf_ftp_set_reference", self._h, ref.data_ptr(), self._format_of(ref), self._stream())
+            self._call("vistaf_ftp_set_reference", self._h, ref.data_ptr(), ref_format, self._stream())
             info = (ctypes.c_double * _lib.NREFINFO)()
             self._call("vistaf_ftp_get_reference_info", self._h, info, on_device=False)
             self.reference_info = self._info_dict(info, 0)
@@ -189,6 +266,31 @@ class FtpSensor(Handle):
         if t.dtype == torch.uint8:
             return _lib.FMT_BGR_U8 if t.dim() == 4 else _lib.FMT_GRAY_U8
         return _lib.FMT_BGR_F16 if t.dim() == 4 else _lib.FMT_GRAY_F16
+
+    def _frames_in(self, frames, format) -> Tuple[torch.Tensor, int]:
+        """(frames as a contiguous device tensor [B, ...], their VISTAF_FMT_* code).  format None: the format follows from dtype and rank
+        (`_as_frames`, `_format_of`).  A name or a code: one frame or a batch in one of that format's shapes for the session's size
+        (`frame_layout`), ValueError otherwise -- nothing is converted or reinterpreted on the way."""
+        if format is None:
+            t = self._as_frames(frames)
+            if t.shape[1] != self.h or t.shape[2] != self.w:
+                raise RuntimeError("Reference and deformed images have different sizes.")   # shape_ftp.py:1477-1478
+            return t, self._format_of(t)
+        code = _format_code(format)
+        shapes = _frame_shapes(code, self.h, self.w)
+        dtype = torch.float16 if code in _F16_FORMATS else torch.uint8
+        t = frames if torch.is_tensor(frames) else torch.from_numpy(np.ascontiguousarray(frames))
+        if t.dtype != dtype:
+            raise ValueError(f"frames in format {_FORMAT_NAMES[code]} must be {dtype}, not {t.dtype}")
+        if tuple(t.shape) in shapes:
+            t = t[None]
+        elif t.dim() < 2 or tuple(t.shape[1:]) not in shapes:
+            raise ValueError(f"frames of shape {tuple(t.shape)} are not {self.h} x {self.w} frames in format {_FORMAT_NAMES[code]}: "
+                             f"one frame is {' or '.join(str(list(v)) for v in shapes)}, a batch [B, ...] of that")
+        t = t.to(self.device).contiguous()
+        if t.data_ptr() % _ALIGN.get(code, 1):
+            t = t.clone()                  # a view that starts below the alignment the format's kernel loads with
+        return t, code
 
     def close(self):
         for name in list(getattr(self, "_readouts", {})):
@@ -243,37 +345,37 @@ class FtpSensor(Handle):
         }
 
     # -- batched device API ------------------------------------------------------------------------
-    def predict_batch(self, frames, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
-        """frames: [B,h,w] or [B,h,w,3], uint8 or float16 (device or host).  Returns device tensors:
+    def predict_batch(self, frames, out: Optional[Dict[str, torch.Tensor]] = None, format=None) -> Dict[str, torch.Tensor]:
+        """frames: [B,h,w] or [B,h,w,3], uint8 or float16 (device or host), or, with format= a name of `_lib.FORMATS` ("rgb", "bgra",
+        "rgba", "yuyv", "uyvy", "nv12", "bayer_rggb", ...) or a VISTAF_FMT_* code, frames in that layout (`frame_layout`; ValueError when
+        they are not).  Returns device tensors:
         height_map_mm [B,h,w] f32 (NaN outside ROI), output_reliable [B,h,w] u8, scalars [B,16] f64, status [B] i32."""
-        t = self._as_frames(frames)
+        t, code = self._frames_in(frames, format)
         b = int(t.shape[0])
-        if t.shape[1] != self.h or t.shape[2] != self.w:
-            raise RuntimeError("Reference and deformed images have different sizes.")   # shape_ftp.py:1477-1478
         if b > self.max_batch:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
             out = self._new_out(b)
-        self._call("vistaf_ftp_predict_batch", self._h, t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(),
+        self._call("vistaf_ftp_predict_batch", self._h, t.data_ptr(), code, b, out["height_map_mm"].data_ptr(),
                    out["output_reliable"].data_ptr(), out["scalars"].data_ptr(), out["status"].data_ptr(), self._stream())
         self._last_out = out
         return out
 
-    def predict_pairs(self, references, frames, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    def predict_pairs(self, references, frames, out: Optional[Dict[str, torch.Tensor]] = None, format=None) -> Dict[str, torch.Tensor]:
         """Uncached pairs: sample b = (references[b], frames[b]); every sample's reference frame is demodulated with its own carrier
         search, as Code/height_to_force.py:384 does by calling shape_ftp.main once per image.  Same outputs as predict_batch; status 3
-        marks a sample whose reference spectrum holds no usable carrier."""
-        r, t = self._as_frames(references), self._as_frames(frames)
-        if r.shape != t.shape or r.dtype != t.dtype:
-            raise RuntimeError("Reference and deformed images have different sizes.")   # shape_ftp.py:1477-1478
+        marks a sample whose reference spectrum holds no usable carrier.  format: the layout of both frame sets, as in `predict_batch`."""
+        (r, rcode), (t, code) = self._frames_in(references, format), self._frames_in(frames, format)
+        if r.shape != t.shape or rcode != code:
+            if format is None:
+                raise RuntimeError("Reference and deformed images have different sizes.")   # shape_ftp.py:1477-1478
+            raise ValueError(f"{r.shape[0]} reference frames for {t.shape[0]} deformed frames")
         b = int(t.shape[0])
-        if t.shape[1] != self.h or t.shape[2] != self.w:
-            raise RuntimeError("Reference and deformed images have different sizes.")
         if b > self.max_batch:
             raise RuntimeError(f"batch {b} exceeds max_batch {self.max_batch}")
         if out is None:
             out = self._new_out(b)
-        self._call("vistaf_ftp_predict_pairs", self._h, r.data_ptr(), t.data_ptr(), self._format_of(t), b, out["height_map_mm"].data_ptr(),
+        self._call("vistaf_ftp_predict_pairs", self._h, r.data_ptr(), t.data_ptr(), code, b, out["height_map_mm"].data_ptr(),
                    out["output_reliable"].data_ptr(), out["scalars"].data_ptr(), out["status"].data_ptr(), self._stream())
         self._last_out = out
         return out
@@ -506,10 +608,11 @@ class FtpSensor(Handle):
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
-                motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
+        format: the layout of `image`, as in `predict_batch`.
         contacts=K adds a "contacts" key: the frame's (at most K) contacts as dicts of CONTACT_NAMES plus `centroid_xy`, `argmax_xy` and
         `bbox` in crop coordinates, and "contact_count"; without it the dict has exactly the reference's keys plus the scalars.
         shapes=True (with contacts=K) adds a "shapes" key: one dict of SHAPE_NAMES per entry of "contacts" (`FtpSensor.shapes`).
@@ -535,7 +638,7 @@ class FtpSensor(Handle):
             raise ValueError("shapes=True needs contacts=K")
         if thermal is not None and contacts is None:
             raise ValueError("thermal=temperature_crop needs contacts=K")
-        o = self.predict_batch(image)
+        o = self.predict_batch(image, format=format)
         torch.cuda.synchronize(self.device)
         status = int(o["status"][0].item())
         if status == _lib.FRAME_EMPTY_RELIABLE:
@@ -620,10 +723,10 @@ class FtpSensor(Handle):
 _default_sensor: Optional[FtpSensor] = None
 
 
-def predict(image, reference=None, taxels=None, **kwargs) -> Optional[Dict[str, Any]]:
+def predict(image, reference=None, taxels=None, format=None, **kwargs) -> Optional[Dict[str, Any]]:
     """predict(image[, reference]) -> force map dict.  With `reference` (and, the first time, the keyword
     arguments of FtpSensor) a session is (re)built; later calls reuse it.  taxels=layout adds the "taxels" and
-    "taxel_frame" keys of `FtpSensor.predict`."""
+    "taxel_frame" keys of `FtpSensor.predict`.  format: the layout of `image` and of `reference` (`FtpSensor.predict_batch`)."""
     global _default_sensor
     if reference is not None or _default_sensor is None:
         if reference is None:
@@ -631,5 +734,5 @@ def predict(image, reference=None, taxels=None, **kwargs) -> Optional[Dict[str, 
         if _default_sensor is not None:
             _default_sensor.close()
         kwargs.setdefault("max_batch", 1)
-        _default_sensor = FtpSensor(reference, **kwargs)
-    return _default_sensor.predict(image, taxels=taxels)
+        _default_sensor = FtpSensor(reference, format=format, **kwargs)
+    return _default_sensor.predict(image, taxels=taxels, format=format)
