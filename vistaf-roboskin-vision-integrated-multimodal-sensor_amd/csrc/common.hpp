@@ -59,6 +59,17 @@ __device__ inline unsigned long long bcast63(unsigned long long v)
 {
     return ((unsigned long long)bcast63((uint32_t)(v >> 32)) << 32) | bcast63((uint32_t)v);
 }
+// lane l's 64-bit value in every lane (l wave-uniform)
+__device__ inline unsigned long long readlane64(unsigned long long v, int l)
+{
+    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+// relaxed atomic load / store at memory scope SCOPE (__HIP_MEMORY_SCOPE_WORKGROUP, _AGENT): a value another wave may write, read past the
+// caches that scope does not share.  The scope is spelled at every call site
+template <int SCOPE, typename T>
+__device__ inline T ld_relaxed(const T *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE); }
+template <int SCOPE, typename T>
+__device__ inline void st_relaxed(T *p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, SCOPE); }
 // RAW = bits of the value (uint32_t or unsigned long long); op combines two RAW words; id = bits of op's identity
 template <typename RAW, typename F>
 __device__ inline RAW wave_reduce_raw(RAW v, RAW id, F op)

@@ -18,11 +18,9 @@
 //                   so any evaluation order gives the tree's exact counts) and writes u = w + 2*pi*k.
 // In exact arithmetic u[p] - w[p] is the same multiple of 2*pi as in the reference's
 // u[p] = u[parent] + angle(exp(1j*(w[p]-w[parent]))) chain; only float32 rounding along the chain differs.
-#include "host_util.hpp"
+#include "unwrap.hpp"
 
 namespace vf {
-
-__device__ inline uint8_t ld_st(const uint8_t *st, int i) { return __hip_atomic_load(st + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // fq / fi / st: the frontier keys and indices (cap entries per frame) and the pixel states, in global memory
 __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ quality_all, const uint8_t *__restrict__ mask_all,
@@ -46,7 +44,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
         st[p] = 0;
         parent[p] = -1;
         if (mask[p]) {
-            unsigned long long k = ((unsigned long long)f2key(quality[p]) << 32) | (uint32_t)(0xffffffffu - (uint32_t)p);
+            unsigned long long k = argmax_key(quality[p], (unsigned)p);
             if (k > best) best = k;
         }
     }
@@ -65,9 +63,10 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
         int np = -1;
         uint8_t s = 255;
         if (lane < 8) {
-            int l = lane < 4 ? lane : lane + 1;          // skip the centre of the 3x3
-            int ny = y + l / 3 - 1, nx = x + l % 3 - 1;
-            if (ny >= 0 && ny < h && nx >= 0 && nx < w) { np = ny * w + nx; s = ld_st(st, np); }
+            int dy, dx;
+            neighbour_slot(lane, dy, dx);
+            int ny = y + dy, nx = x + dx;
+            if (ny >= 0 && ny < h && nx >= 0 && nx < w) { np = ny * w + nx; s = ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(st + np); }
         }
         unsigned long long vis = __ballot(s == 2);
         int par = cur;
@@ -126,9 +125,6 @@ __global__ __launch_bounds__(64) void k_unwrap_flood(const float *__restrict__ q
 // load, so any interleaving is consistent; rounds repeat until every pixel points at the seed.
 // ppar_all (optional): parents in PADDED (h+2)x(w+2) index space as written by the bitmap flood (k_unwrap_big.hip);
 // they are converted here and stored to parent_all (the plane the parity tests read back).
-__device__ inline unsigned long long ld_u64c(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void st_u64c(unsigned long long *p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
 __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ wrapped_all, int32_t *parent_all,
                                                       const int32_t *__restrict__ ppar_in, size_t gstride, unsigned long long *words_all,
                                                       float *__restrict__ unwrapped_all, int h, int w, const int32_t *__restrict__ plain_parents, const int32_t *__restrict__ need_frame)
@@ -142,25 +138,17 @@ __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ 
     const float *wrapped = wrapped_all + b * (size_t)P;
     int32_t *tree = parent_all + b * (size_t)P;
     unsigned long long *word = words_all + b * gstride;
-    const double twopi = 6.283185307179586476925286766559, pi_d = 3.14159265358979323846;
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
         int par;
         if (ppar_all) {
             const int W2 = w + 2;
             int y = p / w, x = p - y * w;
-            int pp = ppar_all[b * gstride + (size_t)(y + 1) * W2 + x + 1];
-            par = pp < 0 ? -1 : (pp / W2 - 1) * w + (pp % W2 - 1);
+            int pp = ppar_all[b * gstride + (size_t)pad_index(y, x, W2)];
+            par = pp < 0 ? -1 : unpad_index(pp, 0u, W2);
             tree[p] = par;
         } else par = tree[p];
         int v = 0;
-        if (par >= 0 && par != p) {
-            double d = (double)wrapped[p] - (double)wrapped[par];
-            double k = -rint(d / twopi);
-            double dd = d + twopi * k;
-            if (dd <= -pi_d) k += 1.0;
-            else if (dd > pi_d) k -= 1.0;
-            v = (int)k;
-        }
+        if (par >= 0 && par != p) v = wrap_count((double)wrapped[p] - (double)wrapped[par]);
         word[p] = (unsigned long long)(uint32_t)par | ((unsigned long long)(uint32_t)v << 32);
     }
     __threadfence();
@@ -173,9 +161,9 @@ __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ 
             unsigned long long wv[4], wq[4];
             int pp[4];
 #pragma unroll
-            for (int u = 0; u < 4; u++) { pp[u] = p0 + u * blockDim.x; wv[u] = pp[u] < P ? ld_u64c(word + pp[u]) : ~0ull; }
+            for (int u = 0; u < 4; u++) { pp[u] = p0 + u * blockDim.x; wv[u] = pp[u] < P ? ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(word + pp[u]) : ~0ull; }
 #pragma unroll
-            for (int u = 0; u < 4; u++) { int par = (int)(uint32_t)wv[u]; wq[u] = (par >= 0 && par != pp[u]) ? ld_u64c(word + par) : ~0ull; }
+            for (int u = 0; u < 4; u++) { int par = (int)(uint32_t)wv[u]; wq[u] = (par >= 0 && par != pp[u]) ? ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(word + par) : ~0ull; }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 int par = (int)(uint32_t)wv[u];
@@ -183,7 +171,7 @@ __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ 
                 int pq = (int)(uint32_t)wq[u];
                 if (pq != par && pq >= 0) {
                     int v = (int)(uint32_t)(wv[u] >> 32) + (int)(uint32_t)(wq[u] >> 32);
-                    st_u64c(word + pp[u], (unsigned long long)(uint32_t)pq | ((unsigned long long)(uint32_t)v << 32));
+                    st_relaxed<__HIP_MEMORY_SCOPE_AGENT>(word + pp[u], (unsigned long long)(uint32_t)pq | ((unsigned long long)(uint32_t)v << 32));
                     changed = 1;
                 }
             }
@@ -197,14 +185,10 @@ __global__ __launch_bounds__(1024) void k_unwrap_tree(const float *__restrict__ 
     }
     float *unwrapped = unwrapped_all + b * (size_t)P;
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
-        unsigned long long wv = ld_u64c(word + p);
-        float u = __uint_as_float(0x7fc00000u);
-        if ((int)(uint32_t)wv >= 0) u = (float)((double)wrapped[p] + twopi * (double)(int)(uint32_t)(wv >> 32));
-        unwrapped[p] = u;
+        unsigned long long wv = ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(word + p);
+        unwrapped[p] = (int)(uint32_t)wv >= 0 ? unwrap_value(wrapped[p], (int)(uint32_t)(wv >> 32)) : nanf32();
     }
 }
-
-bool unwrap_ranked_supported(int h, int w);
 
 // The flood's planes, then the check's.  EN = (h + 2)(w + 2) is the per-frame stride of the uint32 planes; sort_a and sort_b are two of them
 // each (2 EN per frame), and what they hold changes along a path:
@@ -212,7 +196,7 @@ struct UnwrapScratch {
     uint8_t *state;                     // [B, P] pixel states of the generic flood
     uint32_t *sort_a, *sort_b;          // [B, 2 EN] the rank kernels' 8-byte sort records; sort_a then holds the sorted pixel indices (stride 2 EN)
     int32_t *ppar;                      // [B, EN] parents in padded index space (batched and bitmap floods)
-    void *rank;                         // [B, EN + 8] rank codes: uint16 while EN <= 65533, else uint32
+    void *rank;                         // [B, code_stride(EN)] rank codes: uint16 in the uint16 rank range, else uint32
     int32_t *seed, *nmask, *need_generic;   // [B]
     uint32_t *pop_log;                  // = sort_b: the batched flood's pop log (stride 2 EN), written once the ranks are out
     uint32_t *frontier_q, *frontier_i;  // = sort_a, sort_a + B EN: the generic flood's frontier (stride P), the sorted indices being dead by then
@@ -223,14 +207,15 @@ struct UnwrapScratch {
 static UnwrapScratch unwrap_scratch(ScratchLayout &L, int B, int h, int w)
 {
     UnwrapScratch S;
-    S.EN = (size_t)(h + 2) * (w + 2);
+    S.EN = (size_t)padded_pixels(h, w);
     const size_t nb = (size_t)B, gn = nb * S.EN;
     S.state = L.take<uint8_t>(nb * h * w, 256, "state");
     S.sort_a = L.take<uint32_t>(2 * gn, 256, "sort_a");
     S.sort_b = L.take<uint32_t>(2 * gn, 256, "sort_b");
     S.ppar = L.take<int32_t>(gn, 256, "ppar");
-    if (unwrap_ranked_supported(h, w)) S.rank = L.take<uint16_t>(gn + 8 * nb, 256, "rank");
-    else S.rank = L.take<uint32_t>(gn + 8 * nb, 256, "rank");
+    const size_t codes = nb * (size_t)code_stride((long)S.EN);
+    if (unwrap_ranked_supported(h, w)) S.rank = L.take<uint16_t>(codes, 256, "rank");
+    else S.rank = L.take<uint32_t>(codes, 256, "rank");
     S.seed = L.take<int32_t>(nb, 256, "seed");
     S.nmask = L.take<int32_t>(nb, 256, "nmask");
     S.need_generic = L.take<int32_t>(nb, 256, "need_generic");
@@ -243,24 +228,10 @@ static UnwrapScratch unwrap_scratch(ScratchLayout &L, int B, int h, int w)
 }
 size_t unwrap_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); unwrap_scratch(L, B, h, w); return L.bytes(); }
 
-void launch_unwrap_ranked(const float *quality, const uint8_t *mask, uint32_t *g0, uint32_t *g2, int32_t *ppar, size_t gstride, uint16_t *rank16,
-                          int32_t *seed, int B, int h, int w, hipStream_t st, hipEvent_t ev_flood, const int32_t *need);
-void launch_unwrap_replay(const float *wrapped, const uint32_t *order, size_t ostride, const int32_t *ppar, size_t gstride, int32_t *tree,
-                          float *unwrapped, int B, int h, int w, hipStream_t st, const int32_t *need);
-bool unwrap_big_supported(int h, int w);
-bool unwrap_fast_supported(int h, int w);
-void launch_unwrap_fast(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *need, const UfPlanes &U, int B, int h, int w,
-                        hipStream_t st);
-void launch_unwrap_rank32(const float *quality, const uint8_t *mask, uint32_t *gA, uint32_t *gB, size_t gstride, uint32_t *rank32, int32_t *seed,
-                          int32_t *n_out, int B, int h, int w, hipStream_t st, const int32_t *need);
-void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t *n, const uint32_t *inv, size_t inv_stride, int32_t *ppar,
-                             size_t gstride, int32_t *need_generic, bool force_generic, int B, int h, int w, hipStream_t st, const int32_t *need);
-
 // the flood of an h x w frame (UnwrapTier); with big_handback the frames of the bitmap range still get their 32-bit ranks, and the generic flood grows them
 int unwrap_tier(int h, int w, bool big_handback)
 {
-    if (unwrap_ranked_supported(h, w)) return UWT_RANK16;
-    return unwrap_big_supported(h, w) && !big_handback ? UWT_BITMAP : UWT_GENERIC;
+    return unwrap_tier_of(h, w, big_handback);
 }
 
 void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent,
@@ -280,8 +251,15 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
         launch_unwrap_fast(wrapped, quality, mask, unwrapped, need_buf, S.check, B, h, w, st);
         need = need_buf;
     }
+    // the generic flood (frontier and pixel states in global memory) and the tree kernel; only: the frames that take it, null for all of
+    // them; ppar: padded parents of the other frames, from the bitmap flood
+    auto flood_and_tree = [&](const int32_t *only, const int32_t *ppar) {
+        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, S.state, S.frontier_q, S.frontier_i, P, status, h, w, only, need);
+        if (ev_mid) hipEventRecord(ev_mid, st);
+        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, ppar, EN, S.tree_words, unwrapped, h, w, only, need);
+    };
     if (tier == UWT_RANK16) {
-        // frames of at most 65533 padded pixels: uint16 ranks, the batched flood in LDS, then the replay of its pop log
+        // frames of the uint16 rank range: uint16 ranks, the batched flood in LDS, then the replay of its pop log
         launch_unwrap_ranked(quality, mask, S.sort_a, S.sort_b, S.ppar, EN, (uint16_t *)S.rank, S.seed, B, h, w, st, ev_flood, need);
         if (ev_mid) hipEventRecord(ev_mid, st);
         launch_unwrap_replay(wrapped, S.pop_log, 2 * EN, S.ppar, EN, parent, unwrapped, B, h, w, st, need);
@@ -291,17 +269,11 @@ void launch_unwrap(const float *wrapped, const float *quality, const uint8_t *ma
         launch_unwrap_rank32(quality, mask, S.sort_a, S.sort_b, EN, (uint32_t *)S.rank, S.seed, S.nmask, B, h, w, st, need);
         if (ev_flood) hipEventRecord(ev_flood, st);
         launch_unwrap_flood_big((uint32_t *)S.rank, S.seed, S.nmask, S.sort_a, 2 * EN, S.ppar, EN, S.need_generic, big_handback, B, h, w, st, need);
-        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, S.state, S.frontier_q, S.frontier_i, P, status, h, w, S.need_generic, need);
-        if (ev_mid) hipEventRecord(ev_mid, st);
-        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)S.ppar, EN, S.tree_words, unwrapped, h, w,
-                           S.need_generic, need);
+        flood_and_tree(S.need_generic, S.ppar);
     } else {
-        // frames of 2^26 padded pixels and more: the generic kernel, frontier and pixel states in global memory
+        // frames of 2^26 padded pixels and more: the generic kernel for every frame
         if (ev_flood) hipEventRecord(ev_flood, st);
-        hipLaunchKernelGGL(k_unwrap_flood, dim3(B), dim3(64), 0, st, quality, mask, parent, S.state, S.frontier_q, S.frontier_i, P, status, h, w, (const int32_t *)nullptr, need);
-        if (ev_mid) hipEventRecord(ev_mid, st);
-        hipLaunchKernelGGL(k_unwrap_tree, dim3(B), dim3(1024), 0, st, wrapped, parent, (const int32_t *)nullptr, EN, S.tree_words, unwrapped, h, w,
-                           (const int32_t *)nullptr, need);
+        flood_and_tree(nullptr, nullptr);
     }
 }
 

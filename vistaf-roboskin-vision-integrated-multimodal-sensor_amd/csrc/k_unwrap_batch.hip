@@ -19,15 +19,15 @@
 // Everything else about a pop (parent = lexicographically smallest visited neighbour, fresh neighbours to the
 // frontier) touches only the candidate's own 3x3 block, so the committed pops are independent.
 #include <cstdio>
-#include "kernels.hpp"
+#include "unwrap.hpp"
 
 namespace vf {
 
 constexpr int BT_NW = 1024;    // 64-bit words of the cold bitmap (codes < 65536)
 constexpr int BT_K = 8;        // candidates per step
 // LDS of k_unwrap_flood_batch: rank plane, cold bitmap + its summary words, refill staging, inv slice
-constexpr long batch_lds_bytes(long EN) { return ((EN + 7) & ~7L) * 2 + (BT_NW + 16) * 8 + 256 + 512; }
-static_assert(batch_lds_bytes(65533) <= 160 * 1024, "every frame of the uint16 rank range (unwrap_ranked_supported) fits the LDS");
+constexpr long batch_lds_bytes(long EN) { return code_stride(EN) * 2 + (BT_NW + 16) * 8 + 256 + 512; }
+static_assert(batch_lds_bytes(UW_RANK16_MAX_EN) <= 160 * 1024, "every frame of the uint16 rank range (unwrap_ranked_supported) fits the LDS");
 #ifdef VISTAF_DEBUG
 __device__ unsigned long long g_batch_dbg[8];      // frame 0: steps, candidates, commits, steps cut by (i) / (ii), refills, HOT inserts
 #define BT_COUNT(i, v) do { if (b == 0 && lane == 0) g_batch_dbg[i] += (unsigned long long)(v); } while (0)
@@ -45,8 +45,9 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
-    const int W2 = w + 2, EN = (h + 2) * W2;
-    const int EN8 = (EN + 7) & ~7;
+    const int W2 = w + 2, EN = (int)padded_pixels(h, w);
+    const int EN8 = (int)code_stride(EN);
+    __builtin_assume(magic != 0u);                                       // every frame of the uint16 rank range has one (padded_magic)
     uint32_t *order = order_all + b * ostride;                           // pop record: parent << 16 | pixel (padded indices); order[ostride-1] = count
     int npop = 0;
     uint16_t *kp = (uint16_t *)lds_raw;                                  // [EN8] pixel state / rank code
@@ -71,11 +72,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
     const int seed = __builtin_amdgcn_readfirstlane(seed_in[b]);
     if (seed < 0) { if (lane == 0) order[ostride - 1] = 0u; return; }   // empty mask (shape_ftp.py:1047-1048)
     const int ci = lane >> 3, n = lane & 7;                              // candidate slot, neighbour slot
-    int doff;
-    {
-        int l = n < 4 ? n : n + 1;
-        doff = (l / 3 - 1) * W2 + (l % 3 - 1);
-    }
+    const int doff = neighbour_offset(n, W2);
     // the seed is the first frontier entry; its own parent is itself (shape_ftp.py:1051)
     uint32_t hot = 0;            // sorted descending over lanes 0..H-1, 0 elsewhere
     {
@@ -100,9 +97,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
             if (nz == 0ull) cold_any = false;
             else {
                 int top1 = 63 - __clzll((long long)nz);
-                uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)l1, top1);
-                uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(l1 >> 32), top1);
-                unsigned long long w1 = ((unsigned long long)hi << 32) | lo;
+                const unsigned long long w1 = readlane64(l1, top1);
                 const int wtop = top1 * 64 + (63 - __clzll((long long)w1));
                 const int wi = wtop - lane;
                 const unsigned long long word = wi >= 0 ? L0[wi] : 0ull;
@@ -120,9 +115,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
                 while (wm) {
                     const int wl = __ffsll((long long)wm) - 1;
                     wm &= wm - 1ull;
-                    const uint32_t xlo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)word, wl);
-                    const uint32_t xhi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(word >> 32), wl);
-                    const unsigned long long x = ((unsigned long long)xhi << 32) | xlo;
+                    const unsigned long long x = readlane64(word, wl);
                     const int xpre = __builtin_amdgcn_readlane(pre, wl);
                     const int xtake = __builtin_amdgcn_readlane(take, wl);
                     const int xwi = wtop - wl;
@@ -169,10 +162,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
         const int np = idx + doff;
         const uint32_t v = valid ? kp[np] : 0u;
         const int oi = (int)(co & 0xffffu);
-        const int y = (int)__umulhi((uint32_t)idx, magic), x = idx - y * W2;
-        const int oy = (int)__umulhi((uint32_t)oi, magic), ox = oi - oy * W2;
-        const int dy = y - oy, dx = x - ox;
-        const bool conflict = valid && n < ci && dy >= -2 && dy <= 2 && dx >= -2 && dx <= 2;
+        const bool conflict = valid && n < ci && within_two(idx, oi, magic, W2);
         const uint32_t clast = (uint32_t)__builtin_amdgcn_readlane((int)hot, mav - 1);
         const bool fresh = v >= 3u;
         const uint32_t e = fresh ? ((v << 16) | (uint32_t)np) : 0u;
@@ -221,19 +211,12 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_batch(const uint16_t *__res
             else {
                 // HOT was full: its old tail falls into COLD
                 const uint32_t tc = displaced >> 16;
-                if (lane == 0) {
-                    atomicOr(&L0[tc >> 6], 1ull << (tc & 63u));
-                    atomicOr(&L1[tc >> 12], 1ull << ((tc >> 6) & 63u));
-                }
+                if (lane == 0) bitmap_push<2>(tc, L0, L1);
                 cold_any = true;
                 tailv = (uint32_t)__builtin_amdgcn_readlane((int)hot, 63);
             }
         }
-        if ((coldb >> lane) & 1ull) {
-            const uint32_t cc = e >> 16;
-            atomicOr(&L0[cc >> 6], 1ull << (cc & 63u));
-            atomicOr(&L1[cc >> 12], 1ull << ((cc >> 6) & 63u));
-        }
+        if ((coldb >> lane) & 1ull) bitmap_push<2>(e >> 16, L0, L1);
         if (coldb) cold_any = true;
     }
     if (lane == 0) order[ostride - 1] = (uint32_t)npop;
@@ -266,16 +249,16 @@ __global__ __launch_bounds__(64 * RP_NW) void k_unwrap_replay(const float *__res
     int16_t *ks = (int16_t *)lds_raw;                                     // [EN8]
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const size_t b = blockIdx.x;
-    const int P = h * w, W2 = w + 2, EN = (h + 2) * W2;
+    const int P = h * w, W2 = w + 2, EN = (int)padded_pixels(h, w);
+    __builtin_assume(magic != 0u);                                       // as in k_unwrap_flood_batch
     const uint32_t *order = order_all + b * ostride;
     const float *wrapped = wrapped_all + b * (size_t)P;
     int32_t *tree = tree_all + b * (size_t)P;
     float *unwrapped = unwrapped_all + b * (size_t)P;
-    const double twopi = 6.283185307179586476925286766559, pi_d = 3.14159265358979323846;
     {
         uint32_t fill = ((uint32_t)(uint16_t)RP_UNSET << 16) | (uint16_t)RP_UNSET;
         uint32_t *k32 = (uint32_t *)ks;
-        for (int i = tid; i < ((EN + 7) & ~7) / 2; i += 64 * RP_NW) k32[i] = fill;
+        for (int i = tid; i < (int)code_stride(EN) / 2; i += 64 * RP_NW) k32[i] = fill;
     }
     const int npop = (int)order[ostride - 1];
     __syncthreads();
@@ -284,27 +267,17 @@ __global__ __launch_bounds__(64 * RP_NW) void k_unwrap_replay(const float *__res
         const bool valid = i < npop;
         const uint32_t rec = valid ? order[i] : 0u;
         const int idx = (int)(rec & 0xffffu), pp = (int)(rec >> 16);
-        const int y = (int)__umulhi((uint32_t)idx, magic), x = idx - y * W2;
-        const int py = (int)__umulhi((uint32_t)pp, magic), px = pp - py * W2;
-        const int p = valid ? (y - 1) * w + (x - 1) : 0, par = valid ? (py - 1) * w + (px - 1) : 0;
+        const int p = valid ? unpad_index(idx, magic, W2) : 0, par = valid ? unpad_index(pp, magic, W2) : 0;
         const float wp = wrapped[p], wq = wrapped[par];
-        int v = 0;
-        if (pp != idx) {
-            double dd0 = (double)wp - (double)wq;
-            double k = -rint(dd0 / twopi);
-            double dd = dd0 + twopi * k;
-            if (dd <= -pi_d) k += 1.0;
-            else if (dd > pi_d) k -= 1.0;
-            v = (int)k;
-        }
+        const int v = pp != idx ? wrap_count((double)wp - (double)wq) : 0;
         bool done = !valid;
-        if (valid && pp == idx) { done = true; __hip_atomic_store(&ks[idx], (int16_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+        if (valid && pp == idx) { done = true; st_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>(&ks[idx], (int16_t)0); }
         while (__ballot(!done)) {
             if (!done) {
-                int16_t kq = __hip_atomic_load(&ks[pp], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                int16_t kq = ld_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>(&ks[pp]);
                 if (kq != RP_UNSET) {
                     const int kf = (int)kq + v;
-                    __hip_atomic_store(&ks[idx], (int16_t)kf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    st_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>(&ks[idx], (int16_t)kf);
                     done = true;
                 }
             }
@@ -316,41 +289,31 @@ __global__ __launch_bounds__(64 * RP_NW) void k_unwrap_replay(const float *__res
     const int32_t *ppar = ppar_all + b * gstride;
     for (int p = tid; p < P; p += 64 * RP_NW) {
         const int y = p / w, x = p - y * w;
-        const int idx = (y + 1) * W2 + x + 1;
+        const int idx = pad_index(y, x, W2);
         const int16_t kq = ks[idx];
-        float u = __uint_as_float(0x7fc00000u);
-        int par = -1;
-        if (kq != RP_UNSET) {
-            u = (float)((double)wrapped[p] + twopi * (double)kq);
-            const int pp = ppar[idx];
-            const int py = (int)__umulhi((uint32_t)pp, magic), px = pp - py * W2;
-            par = (py - 1) * w + (px - 1);
-        }
-        unwrapped[p] = u;
-        tree[p] = par;
+        const bool reached = kq != RP_UNSET;
+        unwrapped[p] = reached ? unwrap_value(wrapped[p], kq) : nanf32();
+        tree[p] = reached ? unpad_index(ppar[idx], magic, W2) : -1;
     }
 }
 
 void launch_unwrap_flood_batch(const uint16_t *rank16, const int32_t *seed, const uint32_t *inv, size_t inv_stride, int32_t *ppar, size_t gstride,
                                uint32_t *order, size_t ostride, int B, int h, int w, hipStream_t st, const int32_t *need)
 {
-    const size_t lds = (size_t)batch_lds_bytes((long)(h + 2) * (w + 2));
+    const size_t lds = (size_t)batch_lds_bytes(padded_pixels(h, w));
     static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_unwrap_flood_batch, 160 * 1024);
-    const uint32_t magic = (uint32_t)(0x100000000ull / (unsigned)(w + 2)) + 1u;     // idx / (w + 2) == umulhi(idx, magic) for idx < 65536
-    hipLaunchKernelGGL(k_unwrap_flood_batch, dim3(B), dim3(64), lds, st, rank16, seed, inv, inv_stride, ppar, gstride, order, ostride, h, w, magic, need);
+    ensure_dyn_lds(lds_once, (const void *)k_unwrap_flood_batch, 160 * 1024);
+    hipLaunchKernelGGL(k_unwrap_flood_batch, dim3(B), dim3(64), lds, st, rank16, seed, inv, inv_stride, ppar, gstride, order, ostride, h, w, padded_magic(h, w), need);
 }
 
 // unwrapped = wrapped + 2*pi*k along the growth tree; NaN / parent -1 where the growth never arrived
 void launch_unwrap_replay(const float *wrapped, const uint32_t *order, size_t ostride, const int32_t *ppar, size_t gstride, int32_t *tree,
                           float *unwrapped, int B, int h, int w, hipStream_t st, const int32_t *need)
 {
-    long EN = (long)(h + 2) * (w + 2);
-    size_t lds = (size_t)(((EN + 7) & ~7L)) * 2;
+    const size_t lds = (size_t)code_stride(padded_pixels(h, w)) * 2;
     static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_unwrap_replay, 160 * 1024);
-    const uint32_t magic = (uint32_t)(0x100000000ull / (unsigned)(w + 2)) + 1u;
-    hipLaunchKernelGGL(k_unwrap_replay, dim3(B), dim3(64 * RP_NW), lds, st, wrapped, order, ostride, ppar, gstride, tree, unwrapped, h, w, magic, need);
+    ensure_dyn_lds(lds_once, (const void *)k_unwrap_replay, 160 * 1024);
+    hipLaunchKernelGGL(k_unwrap_replay, dim3(B), dim3(64 * RP_NW), lds, st, wrapped, order, ostride, ppar, gstride, tree, unwrapped, h, w, padded_magic(h, w), need);
 }
 
 }  // namespace vf

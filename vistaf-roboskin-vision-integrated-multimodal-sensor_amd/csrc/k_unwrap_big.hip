@@ -17,7 +17,7 @@
 //   A step costs two dependent global round trips (sorted index -> pixel, pixel -> neighbour codes) instead of a scan of the whole
 //   frontier array per pop (k_unwrap_flood, which stays the fallback for masks of more than 1.23 M pixels).
 #include <cstdio>
-#include "kernels.hpp"
+#include "unwrap.hpp"
 
 namespace vf {
 
@@ -25,15 +25,9 @@ namespace {
 constexpr int BG_NW0 = 19200;                        // L0 words: 150 KB
 constexpr int BG_K = 8;                              // candidates per step
 
-__device__ inline uint32_t bg_ld(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void bg_st(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ inline int bg_top(unsigned long long v) { return 63 - __clzll((long long)v); }
-__device__ inline unsigned long long bg_lane64(unsigned long long v, int l)
-{
-    return ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
 #ifdef VISTAF_DEBUG
-__device__ unsigned long long g_big_dbg[8];        // frame 0: steps, candidates, commits, steps cut by rule (i) / (ii) / (iii)
+__device__ unsigned long long g_big_dbg[8];        // frame 0: steps, candidates, commits, steps cut by rule (i) / (ii), [6] L0 words found
 #define BG_COUNT(i, v) do { if (b == 0 && lane == 0) g_big_dbg[i] += (unsigned long long)(v); } while (0)
 #else
 #define BG_COUNT(i, v) do { } while (0)
@@ -54,8 +48,8 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
     unsigned long long *L2 = L1 + nw1;
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
-    const int W2 = w + 2, EN = (h + 2) * W2;
-    uint32_t *code = code_all + b * (size_t)((EN + 7) & ~7);
+    const int W2 = w + 2, EN = (int)padded_pixels(h, w);
+    uint32_t *code = code_all + b * (size_t)code_stride(EN);
     const uint32_t *inv = inv_all + b * inv_stride;
     int32_t *ppar = ppar_all + b * gstride;
     const int n = __builtin_amdgcn_readfirstlane(n_in[b]);
@@ -69,20 +63,13 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
     __syncthreads();
     // the seed (rank n - 1) is the first frontier entry
     if (lane == 0) {
-        const int r = n - 1;
-        L0[r >> 6] = 1ull << (r & 63);
-        L1[r >> 12] = 1ull << ((r >> 6) & 63);
-        L2[r >> 18] = 1ull << ((r >> 12) & 63);
-        bg_st(code + seed, 2u);
+        bitmap_push<3>((uint32_t)(n - 1), L0, L1, L2);
+        st_relaxed<__HIP_MEMORY_SCOPE_AGENT>(code + seed, 2u);
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     __syncthreads();
     const int ci = lane >> 3, nb = lane & 7;                              // candidate slot, neighbour slot
-    int doff;
-    {
-        const int l = nb < 4 ? nb : nb + 1;                              // the 3 x 3 block without its centre, lexicographic (dy, dx)
-        doff = (l / 3 - 1) * W2 + (l % 3 - 1);
-    }
+    const int doff = neighbour_offset(nb, W2);
     // Candidates of a step: the top set bit of up to 8 consecutive non-empty L0 words under the top non-empty L1 word (three dependent LDS
     // rounds), and the read of their pixels from the sorted-index array.  It runs at the END of a step, before the fence that drains the
     // step's stores: the bitmap is final by then, and the index read overlaps the drain.
@@ -94,9 +81,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
         const unsigned long long nz2 = __ballot(v2 != 0ull);
         if (nz2 == 0ull) return;                                         // frontier exhausted: C = 0
         const int t2 = 63 - __clzll((long long)nz2);
-        const unsigned long long top2 = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(v2 >> 32), t2) << 32) |
-                                        (uint32_t)__builtin_amdgcn_readlane((int)v2, t2);
-        const int w1 = t2 * 64 + bg_top(top2);
+        const int w1 = t2 * 64 + bg_top(readlane64(v2, t2));
         unsigned long long v1 = L1[w1];                                  // uniform, non-zero
         // lane k < 8 takes the k-th highest set bit of v1
         {
@@ -115,7 +100,7 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
         {
             int cnt = 0;
             for (int j = 0; j < have && cnt < BG_K; j++) {
-                unsigned long long t = bg_lane64(v0, j);
+                unsigned long long t = readlane64(v0, j);
                 const int w0j = __builtin_amdgcn_readlane(myw0, j);
                 while (t != 0ull && cnt < BG_K) {
                     const int bt = bg_top(t);
@@ -137,16 +122,13 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
         const bool live = ci < C;
         const int np = cpix + doff;
         uint32_t cd = 0;
-        if (live) cd = bg_ld(code + np);
+        if (live) cd = ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(code + np);
         // ---- the prefix that pops in this order
         // (i) candidate j is blocked by an earlier candidate within Chebyshev distance 2: lane = j * 8 + i tests the pair (i < j)
         int L;
         {
-            const int pj = cpix, pi = (int)(uint32_t)__builtin_amdgcn_ds_bpermute(nb << 2, (int)mypix);
-            // row = index / W2 as a multiply-high (exact while EN * W2 < 2^32; magic == 0: plain division)
-            const int yj = magic ? (int)__umulhi((uint32_t)pj, magic) : pj / W2, yi = magic ? (int)__umulhi((uint32_t)pi, magic) : pi / W2;
-            const int xj = pj - yj * W2, xi = pi - yi * W2;
-            const bool close = live && nb < ci && abs(yj - yi) <= 2 && abs(xj - xi) <= 2;
+            const int pi = (int)(uint32_t)__builtin_amdgcn_ds_bpermute(nb << 2, (int)mypix);
+            const bool close = live && nb < ci && within_two(cpix, pi, magic, W2);
             const unsigned long long cl = __ballot(close);
             L = C;
             if (cl) L = min(L, (int)((__ffsll((long long)cl) - 1) >> 3));
@@ -178,14 +160,8 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
         {
             const unsigned int vis8 = (unsigned int)(vis >> (ci << 3)) & 0xffu;
             if (com && nb == 0) {
-                int par = cpix;
-                if (vis8) {
-                    const int l0 = __ffs((int)vis8) - 1;
-                    const int l = l0 < 4 ? l0 : l0 + 1;
-                    par = cpix + (l / 3 - 1) * W2 + (l % 3 - 1);
-                }
-                ppar[cpix] = par;
-                bg_st(code + cpix, 1u);
+                ppar[cpix] = vis8 ? cpix + neighbour_offset(__ffs((int)vis8) - 1, W2) : cpix;
+                st_relaxed<__HIP_MEMORY_SCOPE_AGENT>(code + cpix, 1u);
             }
         }
         // clear the committed candidates' bits (several may share an L0 word: the atomic that empties it clears the summaries)
@@ -201,11 +177,8 @@ __global__ __launch_bounds__(64) void k_unwrap_flood_big(uint32_t *__restrict__ 
         __builtin_amdgcn_wave_barrier();
         // fresh neighbours enter the frontier
         if (fr) {
-            const int r = (int)(cd - 3u);
-            bg_st(code + np, 2u);
-            atomicOr(&L0[r >> 6], 1ull << (r & 63));
-            atomicOr(&L1[r >> 12], 1ull << ((r >> 6) & 63));
-            atomicOr(&L2[r >> 18], 1ull << ((r >> 12) & 63));
+            st_relaxed<__HIP_MEMORY_SCOPE_AGENT>(code + np, 2u);
+            bitmap_push<3>(cd - 3u, L0, L1, L2);
         }
         __builtin_amdgcn_wave_barrier();
         search();                                                        // next step's candidates; its index read overlaps the drain below
@@ -219,16 +192,10 @@ void unwrap_big_debug_dump()
 {
     unsigned long long h[8];
     if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_big_dbg), sizeof(h)) != hipSuccess) return;
-    printf("[flood big dbg] frame 0, all calls: steps %llu | candidates %llu (words found %llu) | commits %llu | steps cut by (i) %llu (ii) %llu (iii) %llu\n", h[0], h[1],
-           h[6], h[2], h[3], h[4], h[5]);
+    printf("[flood big dbg] frame 0, all calls: steps %llu | candidates %llu (words found %llu) | commits %llu | steps cut by (i) %llu (ii) %llu\n", h[0], h[1],
+           h[6], h[2], h[3], h[4]);
 }
 #endif
-
-bool unwrap_big_supported(int h, int w)
-{
-    const long EN = (long)(h + 2) * (w + 2);
-    return EN > 65533 && EN < (1L << 26);
-}
 
 // force_generic (test hook big_flood_handback): hand every frame back, which exercises the per-frame fallback plumbing on masks that fit the bitmap
 void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t *n, const uint32_t *inv, size_t inv_stride, int32_t *ppar,
@@ -236,15 +203,13 @@ void launch_unwrap_flood_big(uint32_t *code, const int32_t *seed, const int32_t 
 {
     // the bitmap is sized for the frame (at most one rank per pixel), up to the 150 KB of BG_NW0 words: mid-size frames leave LDS to others
     const long P = (long)h * w;
-    const unsigned long long EN = (unsigned long long)(h + 2) * (w + 2), W2 = (unsigned long long)w + 2;
-    const uint32_t magic = EN * W2 < 0x100000000ull ? (uint32_t)(0x100000000ull / W2) + 1u : 0u;
     const int nw0 = (int)std::min<long>(BG_NW0, (P + 63) / 64);
     const int nw1 = (nw0 + 63) / 64, nw2 = (nw1 + 63) / 64;
     const size_t lds = (size_t)(nw0 + nw1 + nw2) * 8 + 64;
     static DynLdsOnce lds_once;
     ensure_dyn_lds(lds_once, (const void *)k_unwrap_flood_big, 160 * 1024);
     hipLaunchKernelGGL(k_unwrap_flood_big, dim3(B), dim3(64), lds, st, code, seed, n, inv, inv_stride, ppar, gstride, need_generic,
-                       force_generic ? 0 : nw0 * 64, nw0, h, w, magic, need);
+                       force_generic ? 0 : nw0 * 64, nw0, h, w, padded_magic(h, w), need);
 }
 
 }  // namespace vf

@@ -8,7 +8,7 @@
 // then summing c along any path from the seed gives k: every spanning tree -- the quality-guided one included -- yields exactly this k, and
 // u = w + 2 pi k is the reference's result (in this library's integer-count form, see k_unwrap_tree).  So, for all frames of the batch at once:
 //   k_uf_count / k_uf_scan   horizontal runs of the mask per row, numbered in raster order; the seed (best quality, first in raster order);
-//   k_uf_rows                k relative to the run's first pixel (a prefix sum of c along the row), the run table;
+//   k_uf_rows                k relative to the run's first pixel (a prefix sum of c along the row);
 //   k_uf_edges               one edge per pair of touching runs of adjacent rows (8-adjacency) with the offset difference a contact pair implies;
 //   k_uf_propagate           offsets spread from the seed's run over the edges until nothing changes (runs never reached stay NaN, as pixels the
 //                            flood never reaches do) -- one workgroup per frame, run table and edges in LDS when they fit;
@@ -23,7 +23,7 @@
 // kernels serve 224 x 224 and the native 1182 x 1182 crops.
 #include <algorithm>
 #include <cstdio>
-#include "host_util.hpp"
+#include "unwrap.hpp"
 
 namespace vf {
 
@@ -33,8 +33,8 @@ constexpr int UF_PASSES = 8;          // sweeps over the edge list between two b
 constexpr int UF_LDS_RUNS = 6144, UF_LDS_EDGES = 12288;      // propagation in LDS: 4 B per run + 6 B per edge = 96 KB
 enum { UFC_NEDGE = 0, UFC_FAIL = 1, UFC_R = 2, UFC_N = 4 };
 
-// c(a -> b): the integer k that brings d = w[b] - w[a] into (-pi, pi], i.e. what k_unwrap_tree's float64  k = -rint(d / 2 pi) + one correction
-// step yields.  The wrapped plane comes from atan2, so |d| <= 2 pi and k is -1, 0 or +1: decided here by comparing the float32 difference
+// c(a -> b): the integer k that brings d = w[b] - w[a] into (-pi, pi], i.e. what wrap_count (unwrap.hpp), the float64 rule of the tree and
+// replay kernels, yields.  The wrapped plane comes from atan2, so |d| <= 2 pi and k is -1, 0 or +1: decided here by comparing the float32 difference
 // with pi (four of these per pixel: the float64 form made the check VALU-bound).  The float32 subtraction is off by at most 2^-23 |d| < 8e-7,
 // so the decision can differ from the float64 one only for pairs within 8e-7 of the branch cut -- and every pair within 1e-5 of the cut is
 // reported as a tie (the frame then takes the flood), which also covers the pairs exactly on the cut, where c depends on the direction the
@@ -47,17 +47,71 @@ __device__ inline int uf_c(float wa, float wb, bool &tie)
         tie = tie || fabsf(ad - pi_f) < 1e-5f;
         return ad > pi_f ? (d > 0.f ? -1 : 1) : 0;
     }
-    const double twopi = 6.283185307179586476925286766559, pi_d = 3.14159265358979323846, inv2pi = 0.15915494309189533576888376337251;
-    const double dd0 = (double)wb - (double)wa;
-    double k = -rint(dd0 * inv2pi);
-    double dd = dd0 + twopi * k;
-    if (dd <= -pi_d) { k += 1.0; dd += twopi; }
-    else if (dd > pi_d) { k -= 1.0; dd -= twopi; }
-    tie = tie || fabs(fabs(dd) - pi_d) < 1e-5;
-    return (int)k;
+    const double dd = (double)wb - (double)wa;
+    const int k = wrap_count(dd);
+    tie = tie || fabs(fabs(dd + UW_TWOPI * (double)k) - UW_PI) < 1e-5;
+    return k;
 }
 
-// ---- runs per row, seed.  Every wave of the row kernels takes rw consecutive rows (small frames: fewer, longer-lived waves)
+// ---- the row walk of the row kernels.  Every wave takes rw consecutive rows (small frames: fewer, longer-lived waves) and walks a row in
+// chunks of 64 columns, the loads of UF_CH chunks in flight.
+// the rows of this wave below y_end
+template <typename F>
+__device__ __attribute__((always_inline)) inline void uf_wave_rows(int y_end, int rw, F row)
+{
+    const int first = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * rw;
+    for (int y = first; y < first + rw && y < y_end; y++) row(y);
+}
+// one row: load(j, x) for the UF_CH chunks of a group, all issued before the first use, then step(j, x) chunk by chunk from left to right.
+// x is this lane's column, beyond w in the lanes past the row's end (a chunk wholly past it is not stepped)
+template <typename L, typename S>
+__device__ __attribute__((always_inline)) inline void uf_row_chunks(int w, L load, S step)
+{
+    const int lane = threadIdx.x & 63;
+    for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
+#pragma unroll
+        for (int j = 0; j < UF_CH; j++) load(j, c0 + 64 * j + lane);
+#pragma unroll
+        for (int j = 0; j < UF_CH; j++) {
+            if (c0 + 64 * j >= w) break;
+            step(j, c0 + 64 * j + lane);
+        }
+    }
+}
+// the value of the column to the left: lane - 1's, for lane 0 lane 63's of the chunk before, 0 in the row's first column
+struct LeftColumn {
+    uint32_t last = 0;
+    __device__ uint32_t operator()(uint32_t v)
+    {
+        const uint32_t left = wave_shr1(v, last);
+        last = bcast63(v);
+        return left;
+    }
+    __device__ int operator()(int v) { return (int)(*this)((uint32_t)v); }
+    __device__ float operator()(float v) { return __uint_as_float((*this)(__float_as_uint(v))); }
+};
+// numbers the runs of a row in raster order, from the mask bit of each column: the run this column lies in (where it is in the mask; the row's
+// first run is first_run), whether that run starts here, and the mask bit of the column to the left
+struct Run { int index; bool start, left; };
+struct RunCounter {
+    LeftColumn left_on;
+    int seen;                                   // first_run + the runs started so far
+    __device__ explicit RunCounter(int first_run) : seen(first_run) {}
+    __device__ Run operator()(bool on)
+    {
+        const int lane = threadIdx.x & 63;
+        const bool left = left_on(on ? 1u : 0u) != 0u;
+        const unsigned long long sb = __ballot(on && !left);
+        const unsigned long long le_mask = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
+        const Run r = {seen + (int)__popcll(sb & le_mask) - 1, on && !left, left};
+        seen += (int)__popcll(sb);
+        return r;
+    }
+};
+// a frame fails as soon as one lane met something the check cannot settle
+__device__ inline void uf_fail_if(bool bad, int32_t *ctl) { if (__ballot(bad) && (threadIdx.x & 63) == 0) ctl[UFC_FAIL] = 1; }
+
+// ---- runs per row, seed
 __global__ __launch_bounds__(1024) void k_uf_count(const float *__restrict__ quality_all, const uint8_t *__restrict__ mask_all, UfPlanes U, int h, int w, int rw)
 {
     __shared__ unsigned long long s_best[16];
@@ -65,31 +119,22 @@ __global__ __launch_bounds__(1024) void k_uf_count(const float *__restrict__ qua
     const size_t b = blockIdx.y;
     const size_t P = (size_t)h * w;
     unsigned long long best = 0;
-    for (int r = 0; r < rw; r++) {
-        const int y = (blockIdx.x * nwv + wave) * rw + r;
-        if (y >= h) break;
+    uf_wave_rows(h, rw, [&](int y) {
         const float *q = quality_all + b * P + (size_t)y * w;
         const uint8_t *m = mask_all + b * P + (size_t)y * w;
-        int cnt = 0;
-        uint32_t last = 0;
-        for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
-            uint8_t mm[UF_CH];
-            float qq[UF_CH];
-#pragma unroll
-            for (int j = 0; j < UF_CH; j++) { const int x = c0 + 64 * j + lane; mm[j] = x < w ? m[x] : (uint8_t)0; qq[j] = x < w ? q[x] : 0.f; }
-#pragma unroll
-            for (int j = 0; j < UF_CH; j++) {
-                const int x = c0 + 64 * j + lane;
-                const uint32_t on = mm[j] ? 1u : 0u;
-                const uint32_t ml = wave_shr1(on, last);
-                cnt += __popcll(__ballot(on && !ml));
-                last = (uint32_t)__builtin_amdgcn_readlane((int)on, 63);
+        RunCounter runs(0);
+        uint8_t mm[UF_CH];
+        float qq[UF_CH];
+        uf_row_chunks(
+            w, [&](int j, int x) { mm[j] = x < w ? m[x] : (uint8_t)0; qq[j] = x < w ? q[x] : 0.f; },
+            [&](int j, int x) {
+                const bool on = mm[j] != 0;
+                runs(on);
                 const unsigned long long key = ((unsigned long long)f2key(qq[j]) << 32) | (uint32_t)(0x7fffffff - (y * w + x));
                 if (on && key > best) best = key;
-            }
-        }
-        if (lane == 0) U.rowbase[b * U.hp + y + 1] = cnt;
-    }
+            });
+        if (lane == 0) U.rowbase[b * U.hp + y + 1] = runs.seen;
+    });
     best = wave_max_u64(best);
     if (lane == 0) s_best[wave] = best;
     __syncthreads();
@@ -130,70 +175,48 @@ __global__ __launch_bounds__(1024) void k_uf_scan(UfPlanes U, int h)
     }
 }
 
-// ---- k along the rows, relative to the first pixel of the run; run table
+// ---- k along the rows, relative to the first pixel of the run; every run's word cleared
 __global__ __launch_bounds__(1024) void k_uf_rows(const float *__restrict__ wrapped_all, const uint8_t *__restrict__ mask_all, UfPlanes U, int h, int w, int rw)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63;
     const size_t b = blockIdx.y;
     if (U.ctl[b * UFC_N + UFC_FAIL]) return;
     const size_t P = (size_t)h * w;
     const size_t ro = b * (size_t)U.rcap;
-    const unsigned long long le_mask = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
     bool bad = false;
-    for (int r = 0; r < rw; r++) {
-    const int y = (blockIdx.x * nwv + wave) * rw + r;
-    if (y >= h) break;
-    const float *wr = wrapped_all + b * P + (size_t)y * w;
-    const uint8_t *m = mask_all + b * P + (size_t)y * w;
-    int8_t *kk = U.kk + b * U.P16 + (size_t)y * w;
-    const int rb = U.rowbase[b * U.hp + y];
-    uint32_t last_m = 0, last_w = 0;
-    int carry_v = 0, carry_n = 0;
-    for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
-        uint8_t mm[UF_CH], mr[UF_CH];
+    uf_wave_rows(h, rw, [&](int y) {
+        const float *wr = wrapped_all + b * P + (size_t)y * w;
+        const uint8_t *m = mask_all + b * P + (size_t)y * w;
+        int8_t *kk = U.kk + b * U.P16 + (size_t)y * w;
+        RunCounter runs(U.rowbase[b * U.hp + y]);
+        LeftColumn left_w;
+        int carry_v = 0;                        // k in lane 63 of the chunk before
+        uint8_t mm[UF_CH];
         float ww[UF_CH];
-#pragma unroll
-        for (int j = 0; j < UF_CH; j++) {
-            const int x = c0 + 64 * j + lane;
-            mm[j] = x < w ? m[x] : (uint8_t)0;
-            mr[j] = x + 1 < w ? m[x + 1] : (uint8_t)0;
-            ww[j] = x < w ? wr[x] : 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < UF_CH; j++) {
-            const int x = c0 + 64 * j + lane;
-            if (c0 + 64 * j >= w) break;
-            const uint32_t on = mm[j] ? 1u : 0u;
-            const uint32_t ml = wave_shr1(on, last_m);
-            const float wl = __uint_as_float(wave_shr1(__float_as_uint(ww[j]), last_w));
-            int v = 0;
-            if (on && ml) v = uf_c(wl, ww[j], bad);
-            const bool start = on && !ml;
-            // k relative to the run's first pixel = prefix sum of c along the row minus its value at the run's first pixel (where c = 0)
-            const uint32_t ps = wave_scan_add((uint32_t)v);
-            const uint32_t sl = wave_scan_max(start ? (uint32_t)lane + 1u : 0u);               // 0: the run began in an earlier chunk
-            const uint32_t pstart = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((sl ? sl - 1u : 0u) << 2), (int)ps);
-            v = sl ? (int)(ps - pstart) : (int)ps + carry_v;
-            const unsigned long long sb = __ballot(start);
-            const int idx = rb + carry_n + __popcll(sb & le_mask) - 1;
-            if (x < w) {
-                if (on) {
-                    bad = bad || v < -126 || v > 126;
-                    kk[x] = (int8_t)v;
-                    if (idx < U.rcap) {
-                        if (start) { U.rs[ro + idx] = (uint16_t)x; U.ry[ro + idx] = (uint16_t)y; U.rstate[ro + idx] = 0; }
-                        if (!mr[j]) U.re[ro + idx] = (uint16_t)x;
-                    }
-                } else kk[x] = (int8_t)-128;
-            }
-            carry_v = __builtin_amdgcn_readlane(v, 63);
-            carry_n += __popcll(sb);
-            last_m = (uint32_t)__builtin_amdgcn_readlane((int)on, 63);
-            last_w = (uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(ww[j]), 63);
-        }
-    }
-    }
-    if (__ballot(bad) && lane == 0) U.ctl[b * UFC_N + UFC_FAIL] = 1;
+        uf_row_chunks(
+            w, [&](int j, int x) { mm[j] = x < w ? m[x] : (uint8_t)0; ww[j] = x < w ? wr[x] : 0.f; },
+            [&](int j, int x) {
+                const bool on = mm[j] != 0;
+                const Run run = runs(on);
+                const float wl = left_w(ww[j]);
+                int v = 0;
+                if (on && run.left) v = uf_c(wl, ww[j], bad);
+                // k relative to the run's first pixel = prefix sum of c along the row minus its value at the run's first pixel (where c = 0)
+                const uint32_t ps = wave_scan_add((uint32_t)v);
+                const uint32_t sl = wave_scan_max(run.start ? (uint32_t)lane + 1u : 0u);           // 0: the run began in an earlier chunk
+                const uint32_t pstart = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((sl ? sl - 1u : 0u) << 2), (int)ps);
+                v = sl ? (int)(ps - pstart) : (int)ps + carry_v;
+                if (x < w) {
+                    if (on) {
+                        bad = bad || v < -126 || v > 126;
+                        kk[x] = (int8_t)v;
+                        if (run.start && run.index < U.rcap) U.rstate[ro + run.index] = 0;
+                    } else kk[x] = (int8_t)-128;
+                }
+                carry_v = __builtin_amdgcn_readlane(v, 63);
+            });
+    });
+    uf_fail_if(bad, U.ctl + b * UFC_N);
 }
 
 // ---- one edge per pair of touching runs of adjacent rows; the seed's run starts the propagation.  Streaming: the wave of row y holds rows
@@ -203,68 +226,51 @@ __global__ __launch_bounds__(1024) void k_uf_rows(const float *__restrict__ wrap
 // else).  Every pair of 8-adjacent runs gets exactly one edge; a run's number is its row's first run + the run starts seen so far.
 __global__ __launch_bounds__(1024) void k_uf_edges(const float *__restrict__ wrapped_all, UfPlanes U, int h, int w, int rw)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const size_t b = blockIdx.y;
     if (U.ctl[b * UFC_N + UFC_FAIL]) return;
     const size_t P = (size_t)h * w;
     const size_t ro = b * (size_t)U.rcap, eo = b * (size_t)U.ecap;
-    const unsigned long long le_mask = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
     const unsigned long long sk = U.seedkey[b];
     const int seed = sk ? 0x7fffffff - (int)(uint32_t)sk : -1, sy = seed >= 0 ? seed / w : -1, sx = seed >= 0 ? seed - sy * w : -1;
     int32_t *nedge = &U.ctl[b * UFC_N + UFC_NEDGE];
     bool bad = false;
-    for (int r = 0; r < rw; r++) {
-        const int y = (blockIdx.x * nwv + wave) * rw + r;
-        if (y >= h) break;
+    uf_wave_rows(h, rw, [&](int y) {
         const bool up = y > 0;
         const float *wD = wrapped_all + b * P + (size_t)y * w, *wU = wD - w;
         const int8_t *kD = U.kk + b * U.P16 + (size_t)y * w, *kU = kD - w;
-        const int rbD = U.rowbase[b * U.hp + y], rbU = up ? U.rowbase[b * U.hp + y - 1] : 0;
-        uint32_t lmU = 0, lmD = 0, lwU = 0, lwD = 0, lkU = 0, lkD = 0, liU = 0, liD = 0;      // lane 63 of the previous chunk
-        int cnU = 0, cnD = 0;
-        for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
-            int8_t kd[UF_CH], ku[UF_CH];
-            float wd[UF_CH], wu[UF_CH];
-#pragma unroll
-            for (int j = 0; j < UF_CH; j++) {
-                const int x = c0 + 64 * j + lane;
+        RunCounter runsD(U.rowbase[b * U.hp + y]), runsU(up ? U.rowbase[b * U.hp + y - 1] : 0);
+        LeftColumn left_iD, left_iU, left_kD, left_kU, left_wD, left_wU;
+        int8_t kd[UF_CH], ku[UF_CH];
+        float wd[UF_CH], wu[UF_CH];
+        uf_row_chunks(
+            w,
+            [&](int j, int x) {
                 kd[j] = x < w ? kD[x] : (int8_t)-128;
                 wd[j] = x < w ? wD[x] : 0.f;
                 ku[j] = up && x < w ? kU[x] : (int8_t)-128;
                 wu[j] = up && x < w ? wU[x] : 0.f;
-            }
-#pragma unroll
-            for (int j = 0; j < UF_CH; j++) {
-                const int x = c0 + 64 * j + lane;
-                if (c0 + 64 * j >= w) break;
-                const uint32_t mD = kd[j] != -128 ? 1u : 0u, mU = ku[j] != -128 ? 1u : 0u;
-                const uint32_t pmD = wave_shr1(mD, lmD), pmU = wave_shr1(mU, lmU);
-                const unsigned long long sbD = __ballot(mD && !pmD), sbU = __ballot(mU && !pmU);
-                const uint32_t iD = (uint32_t)(rbD + cnD + __popcll(sbD & le_mask) - 1), iU = (uint32_t)(rbU + cnU + __popcll(sbU & le_mask) - 1);
-                const uint32_t piD = wave_shr1(iD, liD), piU = wave_shr1(iU, liU);
-                const uint32_t kDu = (uint32_t)(int)kd[j], kUu = (uint32_t)(int)ku[j];
-                const uint32_t pkD = wave_shr1(kDu, lkD), pkU = wave_shr1(kUu, lkU);
-                const uint32_t wDu = __float_as_uint(wd[j]), wUu = __float_as_uint(wu[j]);
-                const uint32_t pwD = wave_shr1(wDu, lwD), pwU = wave_shr1(wUu, lwU);
-                if (mD && y == sy && x == sx && iD < (uint32_t)U.rcap) U.rstate[ro + iD] = UF_KNOWN | (uint32_t)(uint16_t)(int16_t)(-(int)kd[j]);
+            },
+            [&](int j, int x) {
+                const bool mD = kd[j] != -128, mU = ku[j] != -128;
+                const Run rD = runsD(mD), rU = runsU(mU);
+                const uint32_t iD = (uint32_t)rD.index, iU = (uint32_t)rU.index;
+                const uint32_t piD = left_iD(iD), piU = left_iU(iU);
+                const int kDv = kd[j], kUv = ku[j];
+                const int pkD = left_kD(kDv), pkU = left_kU(kUv);
+                const float pwD = left_wD(wd[j]), pwU = left_wU(wu[j]);
+                if (mD && y == sy && x == sx && iD < (uint32_t)U.rcap) U.rstate[ro + iD] = UF_KNOWN | (uint32_t)(uint16_t)(int16_t)(-kDv);
                 // (run above, run below, k above, k below, w above, w below) of the up to three pairs of this column
                 auto emit = [&](uint32_t i, uint32_t jn, int ka, int kb, float wa, float wb) {
                     const int c = uf_c(wa, wb, bad);
                     const int e = atomicAdd(nedge, 1);
                     if (e < U.ecap) { U.ei[eo + e] = (uint16_t)i; U.ej[eo + e] = (uint16_t)jn; U.ed[eo + e] = (int16_t)(ka + c - kb); }
                 };
-                if (mU && mD && !(pmU && pmD)) emit(iU, iD, (int)kUu, (int)kDu, wu[j], wd[j]);
-                if (pmU && mD && !mU && !pmD) emit(piU, iD, (int)pkU, (int)kDu, __uint_as_float(pwU), wd[j]);
-                if (mU && pmD && !pmU && !mD) emit(iU, piD, (int)kUu, (int)pkD, wu[j], __uint_as_float(pwD));
-                cnD += __popcll(sbD); cnU += __popcll(sbU);
-                lmD = (uint32_t)__builtin_amdgcn_readlane((int)mD, 63); lmU = (uint32_t)__builtin_amdgcn_readlane((int)mU, 63);
-                liD = (uint32_t)__builtin_amdgcn_readlane((int)iD, 63); liU = (uint32_t)__builtin_amdgcn_readlane((int)iU, 63);
-                lkD = (uint32_t)__builtin_amdgcn_readlane((int)kDu, 63); lkU = (uint32_t)__builtin_amdgcn_readlane((int)kUu, 63);
-                lwD = (uint32_t)__builtin_amdgcn_readlane((int)wDu, 63); lwU = (uint32_t)__builtin_amdgcn_readlane((int)wUu, 63);
-            }
-        }
-    }
-    if (__ballot(bad) && lane == 0) U.ctl[b * UFC_N + UFC_FAIL] = 1;
+                if (mU && mD && !(rU.left && rD.left)) emit(iU, iD, kUv, kDv, wu[j], wd[j]);
+                if (rU.left && mD && !mU && !rD.left) emit(piU, iD, pkU, kDv, pwU, wd[j]);
+                if (mU && rD.left && !rU.left && !mD) emit(iU, piD, kUv, pkD, wu[j], pwD);
+            });
+    });
+    uf_fail_if(bad, U.ctl + b * UFC_N);
 }
 
 // ---- offsets spread over the edges.  A run's word is written once (flag and offset together); a sweep may or may not see what another
@@ -324,88 +330,66 @@ __global__ __launch_bounds__(1024) void k_uf_propagate(UfPlanes U)
 // ---- absolute k of every reached pixel (-127: in the mask but never reached)
 __global__ __launch_bounds__(1024) void k_uf_absolute(UfPlanes U, int h, int w, int rw)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const size_t b = blockIdx.y;
     if (U.ctl[b * UFC_N + UFC_FAIL]) return;
     const uint32_t *rstate = U.rstate + b * (size_t)U.rcap;
-    const unsigned long long le_mask = lane == 63 ? ~0ull : (2ull << lane) - 1ull;
     bool bad = false;
-    for (int r = 0; r < rw; r++) {
-    const int y = (blockIdx.x * nwv + wave) * rw + r;
-    if (y >= h) break;
-    int8_t *kk = U.kk + b * U.P16 + (size_t)y * w;
-    const int rb = U.rowbase[b * U.hp + y];
-    uint32_t last_m = 0;
-    int carry_n = 0;
-    for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
+    uf_wave_rows(h, rw, [&](int y) {
+        int8_t *kk = U.kk + b * U.P16 + (size_t)y * w;
+        RunCounter runs(U.rowbase[b * U.hp + y]);
         int8_t kv[UF_CH];
-#pragma unroll
-        for (int j = 0; j < UF_CH; j++) { const int x = c0 + 64 * j + lane; kv[j] = x < w ? kk[x] : (int8_t)-128; }
-#pragma unroll
-        for (int j = 0; j < UF_CH; j++) {
-            const int x = c0 + 64 * j + lane;
-            if (c0 + 64 * j >= w) break;
-            const uint32_t on = kv[j] != -128 ? 1u : 0u;
-            const uint32_t ml = wave_shr1(on, last_m);
-            const unsigned long long sb = __ballot(on && !ml);
-            const int idx = rb + carry_n + __popcll(sb & le_mask) - 1;
-            if (on) {
-                const uint32_t st = rstate[idx];
+        uf_row_chunks(
+            w, [&](int j, int x) { kv[j] = x < w ? kk[x] : (int8_t)-128; },
+            [&](int j, int x) {
+                const bool on = kv[j] != -128;
+                const Run run = runs(on);
+                if (!on) return;
+                const uint32_t st = rstate[run.index];
                 int v = -127;
                 if (st & UF_KNOWN) { v = (int)kv[j] + (int)(int16_t)(uint16_t)st; bad = bad || v < -126 || v > 126; }
                 kk[x] = (int8_t)v;
-            }
-            carry_n += __popcll(sb);
-            last_m = (uint32_t)__builtin_amdgcn_readlane((int)on, 63);
-        }
-    }
-    }
-    if (__ballot(bad) && lane == 0) U.ctl[b * UFC_N + UFC_FAIL] = 1;
+            });
+    });
+    uf_fail_if(bad, U.ctl + b * UFC_N);
 }
 
 // ---- every vertical and diagonal pair of the reached component
 __global__ __launch_bounds__(1024) void k_uf_verify(const float *__restrict__ wrapped_all, UfPlanes U, int h, int w, int rw)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const size_t b = blockIdx.y;
     if (U.ctl[b * UFC_N + UFC_FAIL]) return;
     const size_t P = (size_t)h * w;
     bool bad = false;
-    for (int r = 0; r < rw; r++) {
-    const int y = (blockIdx.x * nwv + wave) * rw + r;
-    if (y + 1 >= h) break;
-    const float *w0 = wrapped_all + b * P + (size_t)y * w, *w1 = w0 + w;
-    const int8_t *k0 = U.kk + b * U.P16 + (size_t)y * w, *k1 = k0 + w;
-    for (int c0 = 0; c0 < w; c0 += 64 * UF_CH) {
+    uf_wave_rows(h - 1, rw, [&](int y) {
+        const float *w0 = wrapped_all + b * P + (size_t)y * w, *w1 = w0 + w;
+        const int8_t *k0 = U.kk + b * U.P16 + (size_t)y * w, *k1 = k0 + w;
         int8_t kp[UF_CH], kn[UF_CH][3];
         float wp[UF_CH], wn[UF_CH][3];
+        uf_row_chunks(
+            w,
+            [&](int j, int x) {
+                kp[j] = x < w ? k0[x] : (int8_t)-128;
+                wp[j] = x < w ? w0[x] : 0.f;
 #pragma unroll
-        for (int j = 0; j < UF_CH; j++) {
-            const int x = c0 + 64 * j + lane;
-            kp[j] = x < w ? k0[x] : (int8_t)-128;
-            wp[j] = x < w ? w0[x] : 0.f;
+                for (int d = 0; d < 3; d++) {
+                    const int xn = x + d - 1;
+                    const bool in = x < w && xn >= 0 && xn < w;
+                    kn[j][d] = in ? k1[xn] : (int8_t)-128;
+                    wn[j][d] = in ? w1[xn] : 0.f;
+                }
+            },
+            [&](int j, int) {
+                if (kp[j] == -128) return;
 #pragma unroll
-            for (int d = 0; d < 3; d++) {
-                const int xn = x + d - 1;
-                const bool in = x < w && xn >= 0 && xn < w;
-                kn[j][d] = in ? k1[xn] : (int8_t)-128;
-                wn[j][d] = in ? w1[xn] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < UF_CH; j++) {
-            if (kp[j] == -128) continue;
-#pragma unroll
-            for (int d = 0; d < 3; d++) {
-                if (kn[j][d] == -128) continue;
-                if (kp[j] == -127 && kn[j][d] == -127) continue;          // a component the seed's does not touch
-                const int c = uf_c(wp[j], wn[j][d], bad);
-                bad = bad || kp[j] == -127 || kn[j][d] == -127 || (int)kn[j][d] - (int)kp[j] != c;
-            }
-        }
-    }
-    }
-    if (__ballot(bad) && lane == 0) U.ctl[b * UFC_N + UFC_FAIL] = 1;
+                for (int d = 0; d < 3; d++) {
+                    if (kn[j][d] == -128) continue;
+                    if (kp[j] == -127 && kn[j][d] == -127) continue;          // a component the seed's does not touch
+                    const int c = uf_c(wp[j], wn[j][d], bad);
+                    bad = bad || kp[j] == -127 || kn[j][d] == -127 || (int)kn[j][d] - (int)kp[j] != c;
+                }
+            });
+    });
+    uf_fail_if(bad, U.ctl + b * UFC_N);
 }
 
 // ---- the plane (k_unwrap_tree's final expression) of the frames that passed; need[b] for the flood kernels
@@ -415,7 +399,6 @@ __global__ __launch_bounds__(256) void k_uf_plane(const float *__restrict__ wrap
     const int fail = U.ctl[b * UFC_N + UFC_FAIL];
     if (blockIdx.x == 0 && threadIdx.x == 0) need[b] = fail ? 1 : 0;
     if (fail) return;
-    const double twopi = 6.283185307179586476925286766559;
     const int p = (blockIdx.x * 256 + threadIdx.x) * 4;
     if (p >= P) return;
     const float *wr = wrapped_all + b * (size_t)P;
@@ -425,9 +408,7 @@ __global__ __launch_bounds__(256) void k_uf_plane(const float *__restrict__ wrap
     for (int u = 0; u < 4; u++) {
         if (p + u >= P) break;
         const int kp = kk[p + u];
-        float v = __uint_as_float(0x7fc00000u);
-        if (kp > -127) v = (float)((double)wr[p + u] + twopi * (double)kp);
-        out[p + u] = v;
+        out[p + u] = kp > -127 ? unwrap_value(wr[p + u], kp) : nanf32();
     }
 }
 
@@ -443,9 +424,6 @@ UfPlanes unwrap_fast_planes(ScratchLayout &L, int B, int h, int w)
     U.kk = L.take<int8_t>(U.P16 * nb, 256, "check.kk");
     U.rowbase = L.take<int32_t>(U.hp * nb, 256, "check.rowbase");
     U.rstate = L.take<uint32_t>(nr, 256, "check.rstate");
-    U.rs = L.take<uint16_t>(nr, 256, "check.rs");
-    U.re = L.take<uint16_t>(nr, 256, "check.re");
-    U.ry = L.take<uint16_t>(nr, 256, "check.ry");
     U.ei = L.take<uint16_t>(ne, 256, "check.ei");
     U.ej = L.take<uint16_t>(ne, 256, "check.ej");
     U.ed = L.take<int16_t>(ne, 256, "check.ed");

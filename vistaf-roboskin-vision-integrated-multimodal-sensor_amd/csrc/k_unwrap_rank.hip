@@ -8,13 +8,10 @@
 // Frames whose padded plane (h+2)*(w+2) has at most 65533 pixels get uint16 codes (k_unwrap_rank), which the batched growth loop
 // k_unwrap_flood_batch (k_unwrap_batch.hip) holds in LDS; larger frames get uint32 codes (k_unwrap_rank32) for the bitmap flood of
 // k_unwrap_big.hip.
-#include "kernels.hpp"
+#include "unwrap.hpp"
 #include "select.hpp"
 
 namespace vf {
-
-void launch_unwrap_flood_batch(const uint16_t *rank16, const int32_t *seed, const uint32_t *inv, size_t inv_stride, int32_t *ppar, size_t gstride,
-                               uint32_t *order, size_t ostride, int B, int h, int w, hipStream_t st, const int32_t *need);
 
 constexpr int RK_T = 1024;
 
@@ -26,8 +23,6 @@ constexpr int RK_T = 1024;
 // tile that share its digit with eleven ballots (peer mask) + mbcnt.
 // Every exchange through global memory in this kernel is between waves of ONE workgroup (one frame): workgroup scope is all the
 // ordering it needs.  (Agent scope would write back and invalidate the XCD's whole L2 at every fence: buffer_wbl2 / buffer_inv sc1.)
-__device__ inline uint32_t ld_u32c(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline unsigned long long ld_u64c(const unsigned long long *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
 constexpr int RK_BITS = 11, RK_NB = 1 << RK_BITS;   // 3 passes of 11 bits over the 32-bit keys
 constexpr int RK_U = 4;        // 64-element tiles in flight per wave (independent loads issued together)
@@ -46,12 +41,12 @@ __device__ __attribute__((always_inline)) inline void unwrap_rank_body(const flo
     __shared__ uint32_t wcount[16];
     const size_t b = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int P = h * w, W2 = w + 2, EN = (h + 2) * W2;
+    const int P = h * w, W2 = w + 2, EN = (int)padded_pixels(h, w);
     const float *q = quality_all + b * (size_t)P;
     const uint8_t *m = mask_all + b * (size_t)P;
     unsigned long long *rA = A_all + b * gstride, *rB = B_all + b * gstride;
     uint32_t *inv = (uint32_t *)rA;             // three passes leave the records in rB: rA is free for the sorted pixel indices
-    CodeT *rk = rank_all + b * (size_t)((EN + 7) & ~7);
+    CodeT *rk = rank_all + b * (size_t)code_stride(EN);
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
     for (int i = tid; i < EN; i += RK_T) rk[i] = 0;
@@ -88,7 +83,7 @@ __device__ __attribute__((always_inline)) inline void unwrap_rank_body(const flo
                 int p = P - 1 - (rb + u * 64 + lane);
                 int y = p / w, x = p - y * w;
                 uint32_t o = off + (uint32_t)__popcll(bm & lt_mask);
-                rA[o] = ((unsigned long long)f2key(qq[u]) << 32) | (uint32_t)((y + 1) * W2 + x + 1);
+                rA[o] = ((unsigned long long)f2key(qq[u]) << 32) | (uint32_t)pad_index(y, x, W2);
             }
             off += (uint32_t)__popcll(bm);
         }
@@ -109,7 +104,7 @@ __device__ __attribute__((always_inline)) inline void unwrap_rank_body(const flo
         for (int eb = e0; eb < e1; eb += 64 * RK_U) {
             uint32_t kk[RK_U];
 #pragma unroll
-            for (int u = 0; u < RK_U; u++) { int e = eb + u * 64 + lane; kk[u] = e < e1 ? ld_u32c((const uint32_t *)&rs[e] + 1) : 0u; }
+            for (int u = 0; u < RK_U; u++) { int e = eb + u * 64 + lane; kk[u] = e < e1 ? ld_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>((const uint32_t *)&rs[e] + 1) : 0u; }
 #pragma unroll
             for (int u = 0; u < RK_U; u++)
                 if (eb + u * 64 + lane < e1) atomicAdd(&whist[wid][(kk[u] >> shift) & (RK_NB - 1)], 1u);
@@ -138,7 +133,7 @@ __device__ __attribute__((always_inline)) inline void unwrap_rank_body(const flo
 #pragma unroll
             for (int u = 0; u < RK_U; u++) {
                 int e = eb + u * 64 + lane;
-                rr[u] = e < e1 ? ld_u64c(&rs[e]) : 0ull;
+                rr[u] = e < e1 ? ld_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>(&rs[e]) : 0ull;
             }
 #pragma unroll
             for (int u = 0; u < RK_U; u++) {
@@ -164,7 +159,7 @@ __device__ __attribute__((always_inline)) inline void unwrap_rank_body(const flo
     }
     // 3. rank = sorted position (ascending priority); uint16 code = rank + 3; inv[rank] = padded pixel index
     for (int e = tid; e < (int)n; e += RK_T) {
-        uint32_t ix = (uint32_t)ld_u64c(&rs[e]);
+        uint32_t ix = (uint32_t)ld_relaxed<__HIP_MEMORY_SCOPE_WORKGROUP>(&rs[e]);
         rk[ix] = (CodeT)(e + 3);
         inv[e] = ix;
         if (e == (int)n - 1) seed_out[b] = (int32_t)ix;
@@ -195,9 +190,7 @@ void launch_unwrap_rank32(const float *quality, const uint8_t *mask, uint32_t *g
                        (unsigned long long *)gB, gstride, rank32, seed, n_out, h, w, need);
 }
 
-bool unwrap_ranked_supported(int h, int w) { return (long)(h + 2) * (w + 2) <= 65533; }
-
-// Frames of at most 65533 padded pixels: uint16 ranks, then the batched growth loop (k_unwrap_batch.hip).  g0|g1 and g2|g3 (k_unwrap.hip:
+// Frames of the uint16 rank range: uint16 ranks, then the batched growth loop (k_unwrap_batch.hip).  g0|g1 and g2|g3 (k_unwrap.hip:
 // contiguous uint32 planes of gstride elements per frame) take the two planes of 8-byte sort records; the sorted pixel indices end up in g0
 // (stride 2 * gstride), and the growth loop logs its pops in g2 (stride 2 * gstride), dead once the ranks are out, for launch_unwrap_replay.
 // ppar: int32 plane of gstride elements.

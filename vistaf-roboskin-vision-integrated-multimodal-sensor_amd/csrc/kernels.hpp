@@ -196,20 +196,7 @@ void launch_inpaint_clusters(float *img, const uint8_t *bad, int range, void *sc
                              hipStream_t st);
 
 // ---- k_unwrap.hip -----------------------------------------------------------------------------
-// per-frame planes of the consistency check (k_unwrap_fast.hip), dead again before the flood kernels of a failed frame start
-struct UfPlanes {
-    int8_t *kk;                 // [P16] k of the pixel (relative to its run, later absolute); -128 = not in the mask, -127 = never reached
-    int32_t *rowbase;           // [hp] first run of each row; rowbase[h] = number of runs
-    uint32_t *rstate;           // [rcap] UF_KNOWN | (offset & 0xFFFF)
-    uint16_t *rs, *re, *ry;     // [rcap] first / last column, row
-    uint16_t *ei, *ej;          // [ecap] run above, run below
-    int16_t *ed;                // [ecap] offset[below] - offset[above]
-    unsigned long long *seedkey;// [B]
-    int32_t *ctl;               // [B][UFC_N]
-    size_t P16, hp;
-    int rcap, ecap;
-};
-UfPlanes unwrap_fast_planes(ScratchLayout &L, int B, int h, int w);
+// (the family's own helpers, planes and inner launchers: unwrap.hpp)
 bool unwrap_fast_supported(int h, int w);      // the shapes the consistency check takes; launch_unwrap floods every frame of any other
 size_t unwrap_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);
 // the priority flood launch_unwrap starts for an h x w frame: uint16 ranks and the batched flood in LDS, 32-bit ranks and the bitmap flood, or
