@@ -44,7 +44,10 @@ extern "C" {
 #define VISTAF_FRAME_EMPTY_RELIABLE 1   /* upstream: main() logs and returns None (shape_ftp.py:1677-1679) */
 #define VISTAF_FRAME_QUEUE_OVERFLOW 2   /* internal work queue exhausted (never for valid sizes).  Only the phase-unwrap queues can still
                                          * raise it: a frame whose big-cluster inpaint march (native-size crops) outgrows its queue is
-                                         * re-marched whole by the whole-frame kernel, whose queue holds every cell of the frame. */
+                                         * re-marched whole by the whole-frame kernel, and that kernel completes every frame -- it counts the
+                                         * frame's ring cells and hole pixels first, keeps its queue in LDS only when neither count exceeds
+                                         * the LDS capacity, and otherwise in a slice of global memory with a cell for every cell of the
+                                         * frame (a dense mask -- a checkerboard, scattered single pixels -- takes that slice). */
 #define VISTAF_FRAME_NO_CARRIER 3       /* pair mode: no usable carrier in this sample's reference frame -- no spectrum peak, or a
                                          * non-positive fringe period.  A carrier whose (2*patch_half_width_bins+1)^2 patch is clipped
                                          * by the spectrum border is processed with the clipped patch, as upstream (shape_ftp.py:930-948)

@@ -168,6 +168,7 @@ SIGNATURES = {
         "vistaf_ftp_test_chamfer_dispatch": (ci, [vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_blob_filter": (ci, [vp, vp, vp, vp, cd, cd, vp, ci, ci, vp]),
         "vistaf_ftp_test_unwrap": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_inpaint": (ci, [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_dft_full_mag": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     },
     "TEMP_EXPORTS": {        # include/vistaf_temp.h

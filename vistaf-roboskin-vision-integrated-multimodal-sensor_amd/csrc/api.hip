@@ -191,6 +191,43 @@ int check_frames(const vistaf_ftp_handle *hd, int format, const void *a, const v
     return 0;
 }
 
+// The Telea launches of a stage: what the bad-pixel stage (clusters_ok) and the hole stage (!clusters_ok) of a session start for `tiers`, and what
+// vistaf_ftp_test_inpaint runs under variants 0, 5 and 6.  Returns the plane [B] that marks the frames the whole-frame kernel took (null
+// under Tiers::inpaint 1, where it takes them all).  ev_march (stage timing, may be null): recorded where the march proper starts.
+struct InpaintBuffers { void *scratch, *cl_scratch, *win_scratch; int32_t *big_only; };
+const int32_t *inpaint_dispatch(float *img, const uint8_t *bad, int range, const Tiers &tiers, bool clusters_ok, const InpaintBuffers &buf,
+                                int32_t *status, int B, int h, int w, hipStream_t st, hipEvent_t ev_march)
+{
+    // default (Tiers::inpaint 2): the frame-window kernel (LDS-resident march), then the whole-frame kernel for the frames it hands
+    // back; 1: whole-frame kernel only; 0: cluster by cluster -- every independent cluster of hole pixels on its own wave, in an LDS
+    // window when it fits, on the frame's global planes otherwise.  At 224 x 224 the hole pixels form ONE cluster per frame, so the
+    // frame window is the better tool; frames much larger than its capacity (14 464 cells) -- the native 1182 x 1182 crops -- never
+    // fit one window, and there the crests are ~60 px apart: many independent clusters (march of eight native crops: 1.95 s with the
+    // whole-frame kernel, 0.54 s with LDS clusters + whole-frame kernel for the rest, 18 ms since k_inpaint_big.hip: DESIGN.md section 5a).
+    int mode = tiers.inpaint;
+    if (clusters_ok && mode == 2 && (size_t)h * w > (size_t)8 * 14464) mode = 0;
+    if (clusters_ok && mode == 0 && inpaint_clusters_supported(range)) {
+        // every independent cluster of hole pixels on its own wave: LDS windows for those that fit, the frame's global planes for the rest
+        uint8_t *bad_big = nullptr;
+        ClusterPlanes left;
+        launch_inpaint_clusters(img, bad, range, buf.cl_scratch, &bad_big, &left, B, h, w, st);
+        if (ev_march) hipEventRecord(ev_march, st);      // (after the LDS cluster pass: its bookkeeping counts as mask work)
+        launch_inpaint_big_clusters(img, bad_big, range, buf.scratch, status, left, B, h, w, st, tiers.big_queue_lds != 0, tiers.big_gq_cap);
+        // a frame whose big-cluster queue overflowed (status 2) goes whole to the whole-frame kernel, whose queue cannot overflow
+        // (~0.25 s per native crop: a rare path); the other frames only pay for the hand-back launch and two early-exit grids
+        if (!tiers.big_fallback) return nullptr;
+        launch_inpaint_big_handback(status, buf.big_only, B, st);
+        launch_inpaint_telea(img, bad_big, range, buf.scratch, status, buf.big_only, B, h, w, st);
+        return buf.big_only;
+    }
+    const int32_t *only = nullptr;
+    if (ev_march && mode == 1) hipEventRecord(ev_march, st);
+    if (mode != 1) only = launch_inpaint_window(img, bad, range, buf.win_scratch, B, h, w, st, ev_march, tiers.telea_two_tier != 0, tiers.telea_mw != 0);
+    launch_inpaint_telea(img, bad, range, buf.scratch, status, only, B, h, w, st);
+    return only;
+}
+InpaintBuffers inpaint_buffers(const vistaf_ftp_handle *hd) { return {hd->inpaint_scratch, hd->inpaint_cl_scratch, hd->inpaint_win_scratch, hd->big_only}; }
+
 // preprocessing shared by reference and deformed frames: frames -> iw (apodised, normalised) and mu
 // frames2 (pair mode, when the workspace holds 2 * nframes): a second set of nframes frames preprocessed in the SAME launches, as frames
 // [nframes, 2 * nframes) of every plane -- the one-wave-per-frame march then runs once over twice as many CUs instead of twice
@@ -213,39 +250,8 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
             for (int it = 0; it < c.bad_dilate_iters; it++) { launch_morph(src, dst, B, h, w, hd->se_bad, true, nullptr, nullptr, st); std::swap(src, dst); }
         if (src != hd->bad1) hipMemcpyAsync(hd->bad1, src, (size_t)B * P, hipMemcpyDeviceToDevice, st);
         launch_count_u8(hd->bad1, hd->bad_count, B, P, st);
-        {
-            int range = std::min(100, std::max(1, cv_round((double)c.bad_inpaint_radius)));   // cv::inpaint clamps the radius
-            const uint8_t *seq_mask = hd->bad1;
-            const int32_t *only = nullptr;
-            // default (Tiers::inpaint 2): the frame-window kernel (LDS-resident march), then the whole-frame kernel for the frames it hands
-            // back; 1: whole-frame kernel only; 0: cluster by cluster -- every independent cluster of hole pixels on its own wave, in an LDS
-            // window when it fits, on the frame's global planes otherwise.  At 224 x 224 the hole pixels form ONE cluster per frame, so the
-            // frame window is the better tool; frames much larger than its capacity (14 464 cells) -- the native 1182 x 1182 crops -- never
-            // fit one window, and there the crests are ~60 px apart: many independent clusters (march of eight native crops: 1.95 s with the
-            // whole-frame kernel, 0.54 s with LDS clusters + whole-frame kernel for the rest, 18 ms since k_inpaint_big.hip: DESIGN.md section 5a).
-            int mode = hd->tiers.inpaint;
-            if (mode == 2 && (size_t)h * w > (size_t)8 * 14464) mode = 0;
-            if (mode == 0 && inpaint_clusters_supported(range)) {
-                // every independent cluster of hole pixels on its own wave: LDS windows for those that fit, the frame's global planes for the rest
-                uint8_t *bad_big = nullptr;
-                ClusterPlanes left;
-                launch_inpaint_clusters(hd->img, hd->bad1, range, hd->inpaint_cl_scratch, &bad_big, &left, B, h, w, st);
-                if (timed) hipEventRecord(hd->ev[ST_INPAINT], st);      // (after the LDS cluster pass: its bookkeeping counts as mask work)
-                launch_inpaint_big_clusters(hd->img, bad_big, range, hd->inpaint_scratch, hd->status, left, B, h, w, st, hd->tiers.big_queue_lds != 0,
-                                            hd->tiers.big_gq_cap);
-                // a frame whose big-cluster queue overflowed (status 2) goes whole to the whole-frame kernel, whose queue cannot overflow
-                // (~0.25 s per native crop: a rare path); the other frames only pay for the hand-back launch and two early-exit grids
-                if (hd->tiers.big_fallback) {
-                    launch_inpaint_big_handback(hd->status, hd->big_only, B, st);
-                    launch_inpaint_telea(hd->img, bad_big, range, hd->inpaint_scratch, hd->status, hd->big_only, B, h, w, st);
-                }
-            } else {
-                if (timed && mode == 1) hipEventRecord(hd->ev[ST_INPAINT], st);
-                if (mode != 1) only = launch_inpaint_window(hd->img, seq_mask, range, hd->inpaint_win_scratch, B, h, w, st, timed ? hd->ev[ST_INPAINT] : nullptr,
-                                                               hd->tiers.telea_two_tier != 0, hd->tiers.telea_mw != 0);
-                launch_inpaint_telea(hd->img, seq_mask, range, hd->inpaint_scratch, hd->status, only, B, h, w, st);
-            }
-        }
+        inpaint_dispatch(hd->img, hd->bad1, std::min(100, std::max(1, cv_round((double)c.bad_inpaint_radius))),   // cv::inpaint clamps the radius
+                         hd->tiers, true, inpaint_buffers(hd), hd->status, B, h, w, st, timed ? hd->ev[ST_INPAINT] : nullptr);
     } else if (timed) hipEventRecord(hd->ev[ST_INPAINT], st);
     if (timed) hipEventRecord(hd->ev[ST_PREPROC], st);
     blur(hd, hd->img, hd->blurA, hd->g_illum, B, st);
@@ -661,9 +667,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         launch_hole_zin(hd->z0, hd->hole_fill, B, P, st);
         {
             const int range = std::min(100, std::max(1, cv_round((double)c.inpaint_radius)));
-            const int32_t *only = nullptr;
-            if (hd->tiers.inpaint != 1) only = launch_inpaint_window(hd->z0, hd->hole_cand, range, hd->inpaint_win_scratch, B, h, w, st, nullptr, hd->tiers.telea_two_tier != 0, hd->tiers.telea_mw != 0);
-            launch_inpaint_telea(hd->z0, hd->hole_cand, range, hd->inpaint_scratch, hd->status, only, B, h, w, st);
+            inpaint_dispatch(hd->z0, hd->hole_cand, range, hd->tiers, false, inpaint_buffers(hd), hd->status, B, h, w, st, nullptr);
         }
         launch_hole_merge(hd->hmap, hd->reliable, hd->hole_cand, hd->z0, hd->out_rel, B, P, st);
         orel = hd->out_rel;
@@ -1052,6 +1056,37 @@ int vistaf_ftp_test_unwrap(const float *wrapped, const float *quality, const uin
                   variant == 0 ? need : nullptr);
     const int rc = hook_finish(scratch, nullptr, (hipStream_t)stream);
     return rc ? rc : tier;
+}
+
+// ---- the Telea launchers (window tiers, cluster front end, big-cluster march, whole-frame kernel) on caller-supplied device planes
+int vistaf_ftp_test_inpaint(float *img_inout, const uint8_t *bad, int range, int round_u8, int32_t *fb, int32_t *status, int B, int h, int w, int variant,
+                            void *stream)
+{
+    if (!img_inout || !bad || !fb || !status || B < 1 || h < 8 || w < 8 || (size_t)h * w > 0x7fffffffull || range < 1 || range > 100)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 6) return fail(VISTAF_E_INVALID, "variant must be 0 .. 6");
+    if (round_u8 && variant != 1) return fail(VISTAF_E_INVALID, "round_u8: the whole-frame kernel (variant 1) only");
+    if (variant == 2 && !inpaint_window_mw_supported(range)) return fail(VISTAF_E_INVALID, "variant 2: the 16-wave window kernel does not take this range");
+    if ((variant == 5 || variant == 6) && !inpaint_clusters_supported(range))
+        return fail(VISTAF_E_INVALID, "variants 5 and 6: the cluster kernels do not take this range");
+    hipStream_t st = (hipStream_t)stream;
+    const bool dispatch = variant == 0 || variant >= 5;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t n_tel = variant <= 1 || variant >= 5 ? up(inpaint_scratch_bytes(B, h, w)) : 0, n_cl = dispatch ? up(inpaint_cl_scratch_bytes(B, h, w)) : 0,
+                 n_win = variant != 1 ? up(inpaint_win_scratch_bytes(B)) : 0, n_only = up((size_t)B * sizeof(int32_t));
+    uint8_t *base = nullptr;
+    HIPCHK(hipMalloc((void **)&base, n_tel + n_cl + n_win + n_only));
+    const InpaintBuffers buf = {base, base + n_tel, base + n_tel + n_cl, (int32_t *)(base + n_tel + n_cl + n_win)};
+    const int32_t *only = nullptr;
+    if (dispatch) {
+        Tiers tiers;                                        // the defaults of a session
+        if (variant >= 5) tiers.inpaint = 0;
+        if (variant == 6) tiers.big_queue_lds = 0;
+        only = inpaint_dispatch(img_inout, bad, range, tiers, true, buf, status, B, h, w, st, nullptr);
+    } else if (variant == 1) launch_inpaint_telea(img_inout, bad, range, buf.scratch, status, nullptr, B, h, w, st, round_u8 != 0);
+    else only = launch_inpaint_window(img_inout, bad, range, buf.win_scratch, B, h, w, st, nullptr, false, false, variant == 2 ? WNT_MW : variant == 3 ? WNT_FIRST : WNT_ALL);
+    if (only) (void)hipMemcpyAsync(fb, only, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+    return hook_finish(base, nullptr, st);
 }
 
 int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,

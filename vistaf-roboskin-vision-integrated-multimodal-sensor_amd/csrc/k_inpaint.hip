@@ -16,7 +16,7 @@
 
 namespace vf {
 
-constexpr int TQ_CAP = 6144;                 // LDS queue capacity (entries)
+constexpr int TQ_CAP = 6144;                 // LDS queue capacity (entries): frames with more ring cells or hole pixels queue in global memory
 constexpr uint8_t T_KNOWN = 0, T_BAND = 1, T_INSIDE = 2, T_CHANGE = 3, T_SEED = 0x80;   // T_SEED: bit flag, initial band
 
 __device__ inline float ldc(const float *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT); }
@@ -129,9 +129,9 @@ __device__ inline float fmm_dist(const uint8_t *f, const float *t, int p, int ec
 }
 
 // Parallel preparation (one thread per padded cell): Telea flags f (INSIDE on the hole), outside-pass flags fo
-// (ring = within Chebyshev `range` of the hole, seeds = 4-neighbour band), T = 1e6 / 0 on the band, hole count.
+// (ring = within Chebyshev `range` of the hole, seeds = 4-neighbour band), T = 1e6 / 0 on the band, hole and ring cell counts.
 __global__ void k_telea_prep(const uint8_t *__restrict__ bad_all, uint8_t *__restrict__ gflags, float *__restrict__ gT,
-                             int32_t *__restrict__ nbad_all, const int32_t *__restrict__ only, int range, int h, int w)
+                             int32_t *__restrict__ nbad_all, int32_t *__restrict__ nring_all, const int32_t *__restrict__ only, int range, int h, int w)
 {
     const int er = h + 2, ec = w + 2, en = er * ec;
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -160,6 +160,9 @@ __global__ void k_telea_prep(const uint8_t *__restrict__ bad_all, uint8_t *__res
     gflags[b * (size_t)en * 2 + en + i] = fov;
     gT[b * (size_t)en + i] = tv;
     if (in) atomicAdd(&nbad_all[b], 1);
+    // a dense mask puts most of the frame on the ring: one atomic per wave (the lanes that returned above take no part in the ballot)
+    const unsigned long long mr = __ballot(fov == T_INSIDE);
+    if (mr && (int)(threadIdx.x & 63) == __ffsll((long long)mr) - 1) atomicAdd(&nring_all[b], __popcll(mr));
 }
 
 // Window of a march in padded coordinates (inclusive) and the cluster it is restricted to: lab == nullptr marches every hole pixel of the
@@ -168,7 +171,8 @@ __global__ void k_telea_prep(const uint8_t *__restrict__ bad_all, uint8_t *__res
 // the march itself never leaves its own cluster (rings of different clusters are at least three cells apart).
 struct TeleaScan { int i0, i1, j0, j1; const int32_t *lab; int root; };
 
-template <bool LF>
+// LF: the flag planes are in LDS; LQ: so is the queue (else both in global memory, read with L2-served loads and drained stores)
+template <bool LF, bool LQ>
 __device__ __attribute__((always_inline)) inline void telea_march_global(float *img, int range, uint8_t *f, uint8_t *fo, float *t, TQueue &q,
                                                                          const TeleaScan sc, int h, int w, int lane, size_t b, bool round_u8 = false)
 {
@@ -198,7 +202,7 @@ __device__ __attribute__((always_inline)) inline void telea_march_global(float *
                 pend &= pend - 1;
                 p = base + l;
             } else {
-                p = tq_pop<LF>(q, lane);
+                p = tq_pop<LQ>(q, lane);
                 if (p < 0) break;
             }
             npop1++;
@@ -228,7 +232,7 @@ __device__ __attribute__((always_inline)) inline void telea_march_global(float *
                     float dk = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(dist), k * 4));
                     int pk = __builtin_amdgcn_readlane(pn, k * 4);
                     if (lane == 0) { t[pk] = dk; fo[pk] = T_BAND; }
-                    tq_push<LF>(q, dk, pk, lane);
+                    tq_push<LQ>(q, dk, pk, lane);
                 }
             }
             if (LF) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -279,7 +283,7 @@ __device__ __attribute__((always_inline)) inline void telea_march_global(float *
                 pend &= pend - 1;
                 p = base + l;
             } else {
-                p = tq_pop<LF>(q, lane);
+                p = tq_pop<LQ>(q, lane);
                 if (p < 0) break;
             }
             npop2++;
@@ -349,7 +353,7 @@ __device__ __attribute__((always_inline)) inline void telea_march_global(float *
                 }
                 const float val = round_u8 ? telea_estimate_u8(sIa, sJx, sJy, sS) : telea_estimate(sIa, sJx, sJy, sS);
                 if (lane == 0) { img[(size_t)(i - 1) * w + (j - 1)] = val; f[pi] = T_BAND; }
-                tq_push<LF>(q, dist, pi, lane);
+                tq_push<LQ>(q, dist, pi, lane);
                 if (LF) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
             }
         }
@@ -363,8 +367,8 @@ __device__ __attribute__((always_inline)) inline void telea_march_global(float *
 
 template <bool LF>
 __global__ __launch_bounds__(64) void k_telea(float *__restrict__ img_all, const uint8_t *__restrict__ bad_all, int range,
-                                              uint8_t *gflags, float *gT, uint32_t *gqueue, const int32_t *__restrict__ nbad_all, int32_t *status, int h,
-                                              int w, int round_u8)
+                                              uint8_t *gflags, float *gT, uint32_t *gqueue, const int32_t *__restrict__ nbad_all,
+                                              const int32_t *__restrict__ nring_all, int32_t *status, int h, int w, int round_u8)
 {
     extern __shared__ unsigned char lds_raw[];
     const int lane = threadIdx.x;
@@ -373,8 +377,6 @@ __global__ __launch_bounds__(64) void k_telea(float *__restrict__ img_all, const
     float *img = img_all + b * (size_t)P;
     float *t = gT + b * (size_t)en;
     TQueue q;
-    if (LF) { q.T = (uint32_t *)lds_raw; q.idx = (uint32_t *)(lds_raw + (size_t)TQ_CAP * 4); q.cap = TQ_CAP; }
-    else { q.T = gqueue + b * (size_t)en * 2; q.idx = q.T + en; q.cap = en; }   // large frames: queue in global memory
     q.head = q.tail = 0; q.overflow = 0;
     uint8_t *f, *fo;
     if (LF) { f = lds_raw + (size_t)TQ_CAP * 8; fo = f + ((en + 15) & ~15); }
@@ -388,7 +390,18 @@ __global__ __launch_bounds__(64) void k_telea(float *__restrict__ img_all, const
         __syncthreads();
     }
     const TeleaScan sc = {0, er - 1, 0, ec - 1, nullptr, 0};
-    telea_march_global<LF>(img, range, f, fo, t, q, sc, h, w, lane, b, round_u8 != 0);
+    // The outside pass pushes every ring cell once and the march every hole pixel once, and a pass starts with an empty queue: a frame
+    // with no more of either than TQ_CAP can never have more live entries than the LDS queue holds.  Any other frame -- a checkerboard, a
+    // lattice of single pixels, a few per cent of scattered pixels: their band alone is longer -- keeps the same sorted run in its slice of
+    // global memory, which holds a cell for every cell of the frame.  Same pushes, same pops, same order either way, so the same bits; and no
+    // frame overflows (the check in tq_push stays: status 2 would mean that this argument is broken, not that the mask is dense).
+    if (LF && max(nbad_all[b], nring_all[b]) <= TQ_CAP) {
+        q.T = (uint32_t *)lds_raw; q.idx = (uint32_t *)(lds_raw + (size_t)TQ_CAP * 4); q.cap = TQ_CAP;
+        telea_march_global<LF, true>(img, range, f, fo, t, q, sc, h, w, lane, b, round_u8 != 0);
+    } else {
+        q.T = gqueue + b * (size_t)en * 2; q.idx = q.T + en; q.cap = en;
+        telea_march_global<LF, false>(img, range, f, fo, t, q, sc, h, w, lane, b, round_u8 != 0);
+    }
     if (q.overflow && lane == 0) status[b] = 2;
     (void)bad_all;
 }
@@ -407,8 +420,8 @@ void telea_debug_dump()
 struct TeleaScratch {
     float *T;               // [B, en]
     uint8_t *flags;         // [B, 2 en] the two flag planes of a frame, one behind the other
-    uint32_t *queue;        // [B, 2 en] keys, then indices: the queue of frames too large for LDS
-    int32_t *nbad;          // [B]
+    uint32_t *queue;        // [B, 2 en] keys, then indices: the queue of the frames whose ring or hole outgrows the LDS queue, or whose flags do not fit LDS
+    int32_t *nbad, *nring;  // [B] hole pixels, ring cells; one region (one memset clears both)
 };
 static TeleaScratch telea_scratch(ScratchLayout &L, int B, int h, int w)
 {
@@ -417,7 +430,8 @@ static TeleaScratch telea_scratch(ScratchLayout &L, int B, int h, int w)
     S.T = L.take<float>(n, 256, "T");
     S.flags = L.take<uint8_t>(2 * n, 256, "flags");
     S.queue = L.take<uint32_t>(2 * n, 256, "queue");
-    S.nbad = L.take<int32_t>((size_t)B, 256, "nbad");
+    S.nbad = L.take<int32_t>(2 * (size_t)B, 256, "nbad");
+    S.nring = S.nbad ? S.nbad + B : nullptr;
     return S;
 }
 size_t telea_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); telea_scratch(L, B, h, w); return L.bytes(); }
@@ -435,15 +449,15 @@ void launch_inpaint_telea(float *img, const uint8_t *bad, int range, void *scrat
     const size_t en = (size_t)(h + 2) * (w + 2);
     ScratchLayout L(scratch);
     const TeleaScratch S = telea_scratch(L, B, h, w);
-    hipMemsetAsync(S.nbad, 0, sizeof(int32_t) * B, st);
-    hipLaunchKernelGGL(k_telea_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, bad, S.flags, S.T, S.nbad, only, range, h, w);
+    hipMemsetAsync(S.nbad, 0, sizeof(int32_t) * 2 * B, st);
+    hipLaunchKernelGGL(k_telea_prep, dim3((unsigned)((en + 255) / 256), B), dim3(256), 0, st, bad, S.flags, S.T, S.nbad, S.nring, only, range, h, w);
     size_t lds_full = telea_lds_bytes(h, w);
     if (lds_full <= 160 * 1024) {
         static DynLdsOnce lds_once;
         ensure_dyn_lds(lds_once, (const void *)k_telea<true>, 160 * 1024);
-        hipLaunchKernelGGL(k_telea<true>, dim3(B), dim3(64), lds_full, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, status, h, w, round_u8 ? 1 : 0);
+        hipLaunchKernelGGL(k_telea<true>, dim3(B), dim3(64), lds_full, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, S.nring, status, h, w, round_u8 ? 1 : 0);
     } else {
-        hipLaunchKernelGGL(k_telea<false>, dim3(B), dim3(64), 0, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, status, h, w, round_u8 ? 1 : 0);
+        hipLaunchKernelGGL(k_telea<false>, dim3(B), dim3(64), 0, st, img, bad, range, S.flags, S.T, S.queue, S.nbad, S.nring, status, h, w, round_u8 ? 1 : 0);
     }
 }
 

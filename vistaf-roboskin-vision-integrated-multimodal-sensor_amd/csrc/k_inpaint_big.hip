@@ -287,7 +287,7 @@ void launch_inpaint_big_clusters(float *img, const uint8_t *bad_big, int range, 
 }
 
 // A frame with an overflowed big cluster is left partly inpainted (the clusters that finished are written, the overflowed one is not).  The
-// whole-frame kernel, whose queue holds every cell of the frame, then re-marches ALL of the frame's big-cluster pixels: clusters are
+// whole-frame kernel, whose queue moves to a slice of global memory with a cell for every cell of the frame when it has to, then re-marches ALL of the frame's big-cluster pixels: clusters are
 // separated by more than the estimator's reach (k_inpaint_cl.hip), so the finished ones come out with the same bits again.
 __global__ void k_bg_handback(int32_t *__restrict__ status, int32_t *__restrict__ only, int B)
 {

@@ -395,7 +395,7 @@ size_t inpaint_win_scratch_bytes(int B, ScratchRec *rec) { ScratchLayout L(nullp
 
 // Returns the device pointer of the fallback flags.
 int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *scratch, int B, int h, int w, hipStream_t st, hipEvent_t ev_march,
-                               bool two_tier, bool mw)
+                               bool two_tier, bool mw, int alone)
 {
     ScratchLayout L(scratch);
     const WinScratch S = inpaint_win_scratch(L, B);
@@ -409,7 +409,10 @@ int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *
     ensure_dyn_lds(lds_once, (const void *)k_telea_window, 160 * 1024);
     ensure_dyn_lds(lds_once_retry, (const void *)k_telea_window_retry, 160 * 1024);
     if (ev_march) (void)hipEventRecord(ev_march, st);     // stage timing: the march starts here (the bbox pass belongs to the mask stage)
-    if (mw && inpaint_window_mw_supported(range)) {
+    if (alone == WNT_MW) launch_telea_window_mw(img, bad, S.box, S.fb, range, B, h, w, st);
+    else if (alone == WNT_FIRST)
+        hipLaunchKernelGGL(k_telea_window, dim3(B), dim3(64), lds_bytes(WN1_CELLS, WN1_QCAP), st, img, bad, S.box, S.fb, range, B, h, w, WN1_CELLS, WN1_QCAP);
+    else if (mw && inpaint_window_mw_supported(range)) {
         // first tier: one 16-wave workgroup per frame (k_inpaint_mw.hip); what it hands back goes to the full-size single-wave march
         launch_telea_window_mw(img, bad, S.box, S.fb, range, B, h, w, st);
         hipLaunchKernelGGL(k_telea_window_retry, dim3(std::min(B, WN2_GRID)), dim3(64), lds_bytes(WN_CELLS, WN_QCAP), st, img, bad, S.box, S.fb, range, B, h, w,

@@ -176,8 +176,12 @@ size_t inpaint_win_scratch_bytes(int B, ScratchRec *rec = nullptr);
 // ---- k_inpaint_mw.hip (16 waves per frame: ordering pass, then the estimates as a dataflow; flags the frames it cannot take in fb[])
 bool inpaint_window_mw_supported(int range);
 void launch_telea_window_mw(float *img, const uint8_t *bad, const int32_t *box, int32_t *fb, int range, int B, int h, int w, hipStream_t st);
+// alone (tests only): one first tier by itself, without the full-size retry behind it -- WNT_MW the 16-wave kernel (the caller has checked
+// inpaint_window_mw_supported), WNT_FIRST the single-wave kernel at first-tier capacity; the full-size single-wave kernel by itself is
+// two_tier = mw = false.  The flags returned are then that tier's own hand-backs.
+enum WindowTierAlone { WNT_ALL = 0, WNT_MW = 1, WNT_FIRST = 2 };
 int32_t *launch_inpaint_window(float *img, const uint8_t *bad, int range, void *scratch, int B, int h, int w, hipStream_t st,
-                               hipEvent_t ev_march = nullptr, bool two_tier = true, bool mw = true);
+                               hipEvent_t ev_march = nullptr, bool two_tier = true, bool mw = true, int alone = WNT_ALL);
 
 // ---- k_inpaint_cl.hip (cluster-parallel front end; leaves oversized clusters in *bad_big_out) ----------
 size_t inpaint_cl_scratch_bytes(int B, int h, int w, ScratchRec *rec = nullptr);

@@ -409,6 +409,8 @@ int vistaf_temp_inpaint_map(vistaf_tempseg_handle *h, const float *d_map, const 
     launch_tm_stats(d_map, d_roi, h->tm_stats, h->P, st);
     launch_tm_scale(d_map, d_roi, h->tm_stats, h->tmA, h->tmM1, h->P, st);
     (void)hipMemsetAsync(h->tm_status, 0, sizeof(int32_t), st);
+    // tm_status is not read back: the whole-frame kernel completes every frame, however dense the missing mask (it takes its queue to global
+    // memory when the frame's ring or hole outgrows the LDS queue, k_inpaint.hip), so there is no partly filled map to report
     launch_inpaint_telea(h->tmA, h->tmM1, radius, h->tm_scratch, h->tm_status, nullptr, 1, h->H, h->W, st, true);
     launch_tm_unscale(d_map, d_roi, h->tm_stats, h->tmA, d_out, h->P, st);
     return launch_ok("inpaint_temperature_map");

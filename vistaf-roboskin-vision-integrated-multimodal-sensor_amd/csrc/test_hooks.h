@@ -1,6 +1,10 @@
 /* Test-only entry points of libvistaf_ftp.so.  NOT part of the drop-in boundary (include/vistaf_ftp.h): nothing a caller of the
  * path needs lives here.  The parity tests use them to run the fallback / opt-in kernels of a stage against the default ones and
- * to read planes that the production path does not materialise. */
+ * to read planes that the production path does not materialise.
+ * Hooks: vistaf_ftp_test_set (tiers of a session); the production launchers on planes of the caller -- vistaf_ftp_test_select,
+ * _select_instance, _select_chained, _polyfit, _gauss (selection, IRLS fit, blur), _chamfer, _cc_label, _cc_largest, _chamfer_dispatch,
+ * _blob_filter (mask topology), _unwrap (phase unwrap), _inpaint (the Telea tiers); vistaf_ftp_test_scratch_regions (scratch layouts) and
+ * vistaf_ftp_test_dft_full_mag (a timing aid). */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
@@ -135,6 +139,25 @@ int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const i
  * and in [-pi, pi] (float32 pi included), so every pixel pair differs by at most 2 pi. */
 int vistaf_ftp_test_unwrap(const float *wrapped, const float *quality, const uint8_t *mask, float *unwrapped, int32_t *parent, int32_t *need,
                            int32_t *status, int B, int h, int w, int variant, void *stream);
+
+/* The Telea inpaint launchers (k_inpaint*.hip) on device planes [B, h, w] of the caller: img_inout[b] becomes cv2.inpaint(img, bad != 0, range,
+ * INPAINT_TELEA) of itself, bit for bit, known pixels untouched.  Scratch is allocated and freed by the call, which runs on `stream` and waits
+ * for it.  status [B]: pass zeros; only ever written with 2 (VISTAF_FRAME_QUEUE_OVERFLOW).  fb [B]: written by every variant but 1.
+ * variant: 0 what the bad-pixel stage of a session launches with the default tiers (inpaint_dispatch of api.hip, the session's own function):
+ *            the window tiers and the whole-frame kernel, or above 8 * 14464 pixels the cluster front end, the big-cluster march and its
+ *            hand-back.  fb[b] = 1: the whole-frame kernel took frame b,
+ *          1 launch_inpaint_telea alone on every frame; round_u8 != 0: 8-bit semantics (values 0..255, every estimate rounded as OpenCV's
+ *            uchar path does), which is what vistaf_temp_inpaint_map runs,
+ *          2 the bounding-box pass and the 16-wave window kernel alone (ranges 1..4), 3 the single-wave window kernel alone at first-tier
+ *            capacity, 4 at full size.  No retry, no whole-frame kernel: fb[b] = 1 is that tier's hand-back, and such a frame is exactly as
+ *            it was passed (nothing has been written back); fb[b] = 0: the tier completed the frame,
+ *          5 Tiers::inpaint 0: the cluster front end whatever the size, the big-cluster march (queue in LDS where the cell counts allow) and the
+ *            hand-back to the whole-frame kernel (fb[b] = 1: frame b went there), 6 as 5 with big_queue_lds off (ranges 1..5 for both).
+ * Refused with VISTAF_E_INVALID before anything is allocated: a NULL plane, B < 1, h < 8 or w < 8, range outside 1..100 (cv::inpaint clamps to
+ * that), an unknown variant, round_u8 with a variant other than 1, a range the variant's kernels do not take.
+ * Contract on the planes, which a session guarantees: the image is finite (the grey image; z0 after launch_hole_zin). */
+int vistaf_ftp_test_inpaint(float *img_inout, const uint8_t *bad, int range, int round_u8, int32_t *fb, int32_t *status, int B, int h, int w, int variant,
+                            void *stream);
 
 /* The scratch layout of one stage, from a counting pass of the function its launcher carves with (ScratchLayout, host_util.hpp).  Makes no HIP
  * call.  stage: "unwrap", "telea", "inpaint_big" (padding range + 1), "inpaint_cl", "inpaint_win", "big", "tstats" (one frame: B is ignored),
