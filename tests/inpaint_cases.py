@@ -293,6 +293,20 @@ def _m_column():
 _add("capacity", "column_1500x8", _m_column(), 3)              # window 1508 x 9: the row division at ww = 9
 
 
+def _m_strip_and_corner(w):
+    m = _mask(8, w)
+    m[2:6, 100:400] = 1          # cluster window 12 x 308 = 3696 cells (> CL2_CELLS): the big-cluster march
+    m[:3, -5:] = 1               # cluster window 11 x 13 = 143 cells: an LDS cluster, at the last column of the plane
+    return m
+
+
+# The big-cluster march's plane is the frame padded by r + 1 = 4: pitch w + 8 over 16 rows.  Its outside pass splits a cell into row and column
+# with one multiply-high, which is exact while cell * pitch < 2^32: name: (frame width, pitch, exact).  The smallest frames either side of that edge
+PLANE_EDGE = {"plane_8x16375": (16375, 16383, True), "plane_8x16376": (16376, 16384, False)}
+for _n, (_w, _pitch, _exact) in PLANE_EDGE.items():
+    _add("capacity", _n, _m_strip_and_corner(_w), 3)
+
+
 def _m_lattice3(h, w, n):
     return m_lattice(h, w, 3, 1 + 4, n)
 

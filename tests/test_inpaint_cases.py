@@ -88,6 +88,16 @@ def test_capacity_cases():
     # the row division of the window kernels at ww = 9: umulhi(li, 2^32 / ww + 1) is li // ww for every cell index the loops form
     li = np.arange(0, 1 << 16, dtype=np.uint64)
     assert np.array_equal((li * np.uint64((1 << 32) // 9 + 1)) >> np.uint64(32), li // np.uint64(9))
+    # the big-cluster march's padded plane either side of cell * pitch = 2^32, where its outside pass can no longer split a cell into row and
+    # column with one multiply-high
+    assert [v[2] for v in C.PLANE_EDGE.values()] == [True, False]
+    for name, (w, pitch, exact) in C.PLANE_EDGE.items():
+        _, bad, r = _frame(name)
+        assert bad.shape == (8, w) and r == 3 and pitch == w + 2 * (r + 1)
+        assert (pitch * pitch * (8 + 2 * (r + 1)) < 1 << 32) == exact
+        assert C.holes(bad)[2:6, 100:400].all() and C.holes(bad)[:3, -5:].all() and C.holes(bad).sum() == 4 * 300 + 3 * 5
+        assert C.cluster_cells(bad, r) == [3696, 143] and 143 <= C.CL2_CELLS < 3696          # the strip: big-cluster march; the corner: an LDS cluster
+    assert 16383 * 16383 * 16 < 1 << 32 <= 16384 * 16384 * 16
 
 
 def test_queue_cases():

@@ -159,6 +159,9 @@ def test_holes_on_the_frame_borders(pkg, name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", C.FAMILY["capacity"])
 def test_windows_either_side_of_each_tiers_capacity(pkg, name):
+    if name in C.PLANE_EDGE:                                    # the padded plane of the big-cluster march either side of cell * pitch = 2^32
+        check_case(pkg, name, (1, 5, 6))
+        return
     seen = check_case(pkg, name)
     if name in C.CAPACITY:
         assert tuple(int(seen[v][0]) for v in (2, 3, 4)) == C.CAPACITY[name][3]

@@ -205,7 +205,7 @@ const int32_t *inpaint_dispatch(float *img, const uint8_t *bad, int range, const
     // fit one window, and there the crests are ~60 px apart: many independent clusters (march of eight native crops: 1.95 s with the
     // whole-frame kernel, 0.54 s with LDS clusters + whole-frame kernel for the rest, 18 ms since k_inpaint_big.hip: DESIGN.md section 5a).
     int mode = tiers.inpaint;
-    if (clusters_ok && mode == 2 && (size_t)h * w > (size_t)8 * 14464) mode = 0;
+    if (clusters_ok && mode == 2 && (size_t)h * w > (size_t)8 * inpaint_window_cells_cap()) mode = 0;
     if (clusters_ok && mode == 0 && inpaint_clusters_supported(range)) {
         // every independent cluster of hole pixels on its own wave: LDS windows for those that fit, the frame's global planes for the rest
         uint8_t *bad_big = nullptr;

@@ -8,7 +8,6 @@
 // round trip to L2 for all of its reads (they are issued together, telea_pop_march) instead of one per dependent step.
 // The planes are shared by all clusters of a frame: clusters touch disjoint cells (k_inpaint_cl.hip), a wave only ever reads cells its own
 // cluster owns or cells nobody writes, and a wave sees its own global stores in program order.
-#include <type_traits>
 #include "host_util.hpp"
 #include "telea_common.hpp"
 
@@ -74,14 +73,9 @@ __global__ __launch_bounds__(256) void k_bg_prep(const float *__restrict__ img_a
         iv = img_all[b * (size_t)P + p];
         if (bad[p]) fv = W_HOLE;                                  // KNOWN for the outside pass
         else if (dil_all[b * (size_t)P + p]) {
-            if (hole(y, x - 1) || hole(y, x + 1) || hole(y - 1, x) || hole(y + 1, x)) { fv = W_SEED; tv = 0.f; }     // initial band
-            else {
-                bool near = false;
-                for (int a = -range; a <= range && !near; a++)
-                    for (int c = -range; c <= range; c++)
-                        if (hole(y + a, x + c)) { near = true; break; }
-                if (near) fv = W_INSIDE;                          // ring of the outside pass
-            }
+            const int kind = telea_known_pixel_kind(hole, y, x, range);
+            if (kind == TC_BAND) { fv = W_SEED; tv = 0.f; }       // initial band
+            else if (kind == TC_RING) fv = W_INSIDE;              // ring of the outside pass
         }
     }
     gf[b * (size_t)en + i] = fv;
@@ -163,35 +157,23 @@ __device__ __attribute__((always_inline)) inline bool bg_march(const BgWin &W, f
     q.cap = LQ ? lds_cap : gq_cap;
     q.ovf = 0;
     wq_init(q);
-    // ---- pass 1: outside T field (icvCalcFMM, negate): seeds first in raster order, then the queue, up to four pops per step
-    // (telea_pop_outside4: the row / column split of its distance test is exact as long as cell * pitch < 2^32; else one pop per step)
+    // ---- pass 1: outside T field (icvCalcFMM, negate): seeds first in raster order, then the queue, up to four pops per step -- one per
+    // step on a plane so large that a cell no longer splits exactly into row and column (telea_magic_plane: 0, telea_outside_prefix: 1)
     {
         const TeleaOutsideConsts oc = telea_outside_consts(lane, W.ew);
-        if ((unsigned long long)W.ew * W.ew * (unsigned long long)(W.h + 2 * W.M) < 0x100000000ull) {
-            FmmFlagState fst{t, f};
-            const uint32_t magic = telea_magic_ww(W.ew);
-            unsigned long long np = 0, ns = 0;
-            bg_seed_chunks(W, f, lane, [&](int base, unsigned long long pend) { telea_fmm_seed_chunk(fst, q, oc, base, pend, W.ew, magic, lane, np, ns); });
-            telea_fmm_queue(fst, q, oc, W.ew, magic, lane, np, ns);
-        } else {
-            auto push1 = [&](float T_, int idx_) { wq_push<false>(q, T_, idx_, lane); };
-            bg_seed_chunks(W, f, lane, [&](int base, unsigned long long pend) {
-                while (pend && !q.ovf) { const int l = __ffsll((long long)pend) - 1; pend &= pend - 1ull; telea_pop_outside(win, oc, base + l, true, lane, push1); }
-            });
-            while (!q.ovf) {
-                if (q.nh > 0) wq_merge<false>(q, lane);
-                if (q.ovf || q.head == q.tail) break;
-                const int p = (int)(uint32_t)q.e[q.head];
-                q.head++;
-                telea_pop_outside(win, oc, p, false, lane, push1);
-            }
-        }
+        FmmFlagState fst{t, f};
+        const uint32_t magic = telea_magic_plane(W.ew, W.h + 2 * W.M);
+        unsigned long long np = 0, ns = 0;
+        bg_seed_chunks(W, f, lane, [&](int base, unsigned long long pend) { telea_fmm_seed_chunk(fst, q, oc, base, pend, W.ew, magic, lane, np, ns); });
+        telea_fmm_queue(fst, q, oc, W.ew, magic, lane, np, ns);
     }
     if (q.ovf) return false;
     // negate T where the outside pass ran; switch the state bits to the march's flags (hole = INSIDE, rest KNOWN)
     bg_each(W, f, lane, [&](int cell, uint8_t v) {
-        if ((v & W_ST) == W_CHANGE) t[cell] = -t[cell];
-        f[cell] = (uint8_t)((v & (W_SEED | W_HOLE | W_BORDER)) | ((v & W_HOLE) ? W_INSIDE : W_KNOWN));
+        bool neg;
+        const uint8_t m = telea_to_march_state(v, neg);
+        if (neg) t[cell] = -t[cell];
+        f[cell] = m;
     });
     // ---- pass 2: Telea march (icvTeleaInpaintFMM)
     wq_init(q);
@@ -211,13 +193,7 @@ __device__ __attribute__((always_inline)) inline bool bg_march(const BgWin &W, f
             telea_pop_march<decltype(small)::value>(win, mc, p, true, lane, push);
         }
     };
-    switch (mc.ndisc) {
-    case 5: march(std::integral_constant<int, 5>{}); break;
-    case 13: march(std::integral_constant<int, 13>{}); break;
-    case 29: march(std::integral_constant<int, 29>{}); break;
-    case 49: march(std::integral_constant<int, 49>{}); break;
-    default: march(std::integral_constant<int, 0>{}); break;
-    }
+    telea_dispatch_ndisc(mc.ndisc, march);
     return !q.ovf;
 }
 

@@ -13,6 +13,7 @@
 //      and flags the ones whose queue overflowed;
 //   4. k_split_bad builds the hole mask of the flagged clusters for the frame-window / whole-frame kernels.
 #include "host_util.hpp"
+#include "telea_common.hpp"
 
 namespace vf {
 
@@ -59,9 +60,7 @@ __global__ void k_cluster_list(const int32_t *__restrict__ labels, const int32_t
     size_t i = b * (size_t)P + p;
     big[i] = 0;
     if (labels[i] != p || xmin[i] == 0x7f7f7f7f) return;
-    const int M = range + 1;
-    const int cells = (ymax[i] - ymin[i] + 1 + 2 * M) * (xmax[i] - xmin[i] + 1 + 2 * M);     // unclipped window (k_inpaint_win.hip)
-    if (cells > cells_cap) big[i] = 1;
+    if (telea_window_of_box(xmin[i], ymin[i], xmax[i], ymax[i], range).cells() > cells_cap) big[i] = 1;     // the unclipped window
     else { int k = atomicAdd(&count[b], 1); list[b * (size_t)P + k] = p; }
 }
 
@@ -117,10 +116,6 @@ static ClusterScratch inpaint_cl_scratch(ScratchLayout &L, int B, int h, int w)
 size_t inpaint_cl_scratch_bytes(int B, int h, int w, ScratchRec *rec) { ScratchLayout L(nullptr, rec); inpaint_cl_scratch(L, B, h, w); return L.bytes(); }
 
 bool inpaint_clusters_supported(int range) { return inpaint_big_supported(range); }     // the left-over clusters need k_inpaint_big.hip
-
-int inpaint_cluster_cells_cap();
-void launch_telea_clusters2(float *img, const uint8_t *bad, const int32_t *labels, const int32_t *list, const int32_t *count, const int32_t *xmin,
-                            const int32_t *ymin, const int32_t *xmax, const int32_t *ymax, uint8_t *big, int range, int B, int h, int w, hipStream_t st);
 
 // Marches every cluster that fits on its own window; *bad_big_out = hole mask of the clusters that were left over, *left = their roots
 // (list / count per frame, in no particular order), labels and bounding boxes for launch_inpaint_big_clusters.

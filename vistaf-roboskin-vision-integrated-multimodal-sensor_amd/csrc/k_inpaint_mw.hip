@@ -27,8 +27,6 @@
 #include <algorithm>
 #include <cstdio>
 #include <vector>
-#include "kernels.hpp"
-#include <type_traits>
 #include "telea_common.hpp"
 
 namespace vf {
@@ -38,7 +36,6 @@ constexpr int MW_T = MW_WAVES * 64;
 constexpr int MW_WAVES_OUT = 6;     // concurrent passes: waves [0, 6) run the outside pass, the other 10 the ordering pass (measured: 8 / 8 and 5 / 11 are slower)
 constexpr int MW_CELLS = 10752;     // window cells: 11 B each (T f32, image f32, fill number u16, flags u8)
 constexpr int MW_FILLS = 4096;      // hole pixels per frame
-constexpr int MW_RING_U = 6;
 constexpr int GP_POOL = 4096;       // pushes of one FMM pass (the pool is append-only: popped entries are blanked)
 constexpr int GP_GEN = 2048;        // entries of one generation
 constexpr int GP_MAXGEN = 32;
@@ -164,11 +161,7 @@ __device__ __attribute__((always_inline)) inline void gp_pop_loop(const GenScrat
                 if (ORDER) { const uint16_t s0 = fi[pn], s1 = fi[p1], s2 = fi[p2]; in0 = s0 == FI_INSIDE; in1 = s1 == FI_INSIDE; in2 = s2 == FI_INSIDE; }
                 else { const uint8_t s0 = f[pn], s1 = f[p1], s2 = f[p2]; in0 = (s0 & W_ST) == W_INSIDE; in1 = (s1 & W_ST) == W_INSIDE; in2 = (s2 & W_ST) == W_INSIDE; }
                 const unsigned v0 = fi[nin0 ? p + ndy[0] * ww + ndx[0] : p], v1 = fi[nin1 ? p + ndy[1] * ww + ndx[1] : p];
-                float dist = wn_solve(a11, a22, !in1, !in2);
-                {
-                    float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0xB1, 0xf, 0xf, false)); dist = o < dist ? o : dist;
-                    o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0x4E, 0xf, 0xf, false)); dist = o < dist ? o : dist;
-                }
+                const float dist = quad_min(wn_solve(a11, a22, !in1, !in2));
                 if (li == 0) {                          // the entry leaves the queue (this also drops its rank mark)
                     if (g == 0) {                       // a band pixel: the other pass may still hold its own mark on it
                         __hip_atomic_fetch_and((uint32_t *)fi + (p >> 1), ~((uint32_t)MB << ((p & 1) << 4)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -457,12 +450,8 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
     const int P = h * w;
     const int xmin = box[b], ymin = box[B + b], xmax = box[2 * B + b], ymax = box[3 * B + b];
     if (xmin == 0x7f7f7f7f) { if (tid == 0) fb[b] = 0; return; }          // no hole pixel: nothing to inpaint
-    const int M = range + 1;
-    // window in padded frame coordinates [i0, i1] x [j0, j1], not clipped (cells beyond the image: BORDER)
-    const int i0 = ymin + 1 - M, i1 = ymax + 1 + M;
-    const int j0 = xmin + 1 - M, j1 = xmax + 1 + M;
-    const int wh = i1 - i0 + 1, ww = j1 - j0 + 1;
-    const int cells = wh * ww;
+    const TeleaBoxWin bw = telea_window_of_box(xmin, ymin, xmax, ymax, range);
+    const int wh = bw.wh, ww = bw.ww, cells = bw.cells();
     if (cells > MW_CELLS) { if (tid == 0) fb[b] = 1; return; }
     float *img = img_all + (size_t)b * P;
     const uint8_t *bad = bad_all + (size_t)b * P;
@@ -476,7 +465,7 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
     int *ctl = cntv + 2 * GP_CNT;                                // [2][MWC_N] outside pass (and everything after the passes), ordering pass
     int *ctl2 = ctl + MWC_N;
     uint8_t *f = (uint8_t *)(ctl2 + MWC_N);                      // [MW_CELLS]
-    const uint32_t mg_ww = (uint32_t)(0x100000000ull / (unsigned)ww) + 1u;       // li / ww == umulhi(li, mg_ww) for li < 2^16
+    const uint32_t mg_ww = telea_magic_ww(ww);
     MSTAMP(0);
 #ifdef VISTAF_DEBUG
     if (tid == 0 && b < 1024) for (int i = 11; i < 16; i++) g_mw_dbg[b][i] = 0;
@@ -492,9 +481,8 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
         for (int k = 0; k < 4; k++) {
             const int li = base + k * MW_T + tid;
             const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-            const int gi = i0 + r, gj = j0 + cc;
-            interior[k] = li < cells && gi >= 1 && gi <= h && gj >= 1 && gj <= w;
-            const size_t gp = interior[k] ? (size_t)(gi - 1) * w + (gj - 1) : 0;
+            size_t gp;
+            interior[k] = bw.locate(li, cells, r, cc, h, w, gp);
             bd[k] = bad[gp];
         }
 #pragma unroll
@@ -509,51 +497,20 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
         }
     }
     __syncthreads();
-    // ring = within Chebyshev `range` of the hole (separable: rows, then columns); band = 4-neighbours of the hole
-    {
-        const bool unrolled = range <= MW_RING_U;
-        for (int li = tid; li < cells; li += MW_T) {
-            const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-            const uint8_t me = f[li];
-            uint8_t a = 0;
-            if (unrolled) {
-#pragma unroll
-                for (int d = -MW_RING_U; d <= MW_RING_U; d++) {
-                    const int c2 = cc + d;
-                    const bool in = d >= -range && d <= range && c2 >= 0 && c2 < ww;
-                    const uint8_t v = f[in ? li + d : li];
-                    a |= in ? v : (uint8_t)0;
-                }
-            } else {
-                const int lo = max(0, cc - range), hi = min(ww - 1, cc + range);
-                for (int c2 = lo; c2 <= hi; c2++) a |= f[r * ww + c2];
-            }
-            if (a & W_HOLE) f[li] = me | W_ROW;           // neighbours only look at bit 6, which this never changes
-        }
-        __syncthreads();
-        for (int li = tid; li < cells; li += MW_T) {
-            const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-            const uint8_t me = f[li];
-            // window edge cells are at distance range+1 from the hole: never band, their neighbours are not needed
-            const uint8_t nb4 = f[cc > 0 ? li - 1 : li] | f[cc < ww - 1 ? li + 1 : li] | f[r > 0 ? li - ww : li] | f[r < wh - 1 ? li + ww : li];
-            uint8_t a = 0;
-            if (unrolled) {
-#pragma unroll
-                for (int d = -MW_RING_U; d <= MW_RING_U; d++) {
-                    const int r2 = r + d;
-                    const bool in = d >= -range && d <= range && r2 >= 0 && r2 < wh;
-                    const uint8_t v = f[in ? li + d * ww : li];
-                    a |= in ? v : (uint8_t)0;
-                }
-            } else {
-                const int lo = max(0, r - range), hi = min(wh - 1, r + range);
-                for (int r2 = lo; r2 <= hi; r2++) a |= f[r2 * ww + cc];
-            }
-            // (reads of this sweep look at W_ROW / W_HOLE only, bits 5 and 6, which the byte stores below never change)
-            if (me & (W_BORDER | W_HOLE)) continue;                          // hole pixels are KNOWN for the outside pass
-            if (nb4 & W_HOLE) { f[li] = me | W_SEED; t[li] = 0.f; nband++; }
-            else if (a & W_ROW) { f[li] = me | W_INSIDE; nring++; }          // writes bits 0-1 only
-        }
+    // ring and band (telea_common.hpp: window build), one cell per thread and iteration
+    for (int li = tid; li < cells; li += MW_T) {
+        const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
+        const uint8_t me = f[li];
+        if (telea_ring_row_tap(f, li, r, cc, ww, range) & W_HOLE) f[li] = me | W_ROW;           // neighbours only look at bit 6, which this never changes
+    }
+    __syncthreads();
+    for (int li = tid; li < cells; li += MW_T) {
+        const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
+        const uint8_t me = f[li];
+        // (reads of this sweep look at W_ROW / W_HOLE only, bits 5 and 6, which the byte stores below never change)
+        const int kind = telea_cell_kind(me, telea_nb4_tap(f, li, r, cc, wh, ww), telea_ring_col_tap(f, li, r, cc, wh, ww, range));
+        if (kind == TC_BAND) { f[li] = me | W_SEED; t[li] = 0.f; nband++; }
+        else if (kind == TC_RING) { f[li] = me | W_INSIDE; nring++; }                           // writes bits 0-1 only
     }
     for (int o = 32; o; o >>= 1) { nhole += __shfl_xor(nhole, o, 64); nring += __shfl_xor(nring, o, 64); nband += __shfl_xor(nband, o, 64); }
     if (lane == 0) { atomicAdd(&ctl[MWC_NHOLE], nhole); atomicAdd(&ctl[MWC_NRING], nring); atomicAdd(&ctl[MWC_NBAND], nband); }
@@ -640,16 +597,17 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
             const int li = base + k * MW_T + tid;
             const bool interior = li < cells && !(f[li < cells ? li : 0] & W_BORDER);
             const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-            v[k] = interior ? img[(size_t)(i0 + r - 1) * w + (j0 + cc - 1)] : 0.f;
+            v[k] = interior ? img[bw.pixel(r, cc, w)] : 0.f;
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const int li = base + k * MW_T + tid;
             if (li >= cells) continue;
             im[li] = v[k];
-            const uint8_t fv = f[li];
-            if ((fv & W_ST) == W_CHANGE) t[li] = -t[li];
-            f[li] = (uint8_t)((fv & (W_SEED | W_HOLE | W_BORDER)) | ((fv & W_HOLE) ? W_INSIDE : W_KNOWN));
+            bool neg;
+            const uint8_t fv = telea_to_march_state(f[li], neg);
+            if (neg) t[li] = -t[li];
+            f[li] = fv;
         }
     }
     for (int k = tid; k < nfill; k += MW_T) { fi[flist[k]] = (uint16_t)k; rq[k] = 0xFFFFFFFFu; }
@@ -677,12 +635,8 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
         TeleaWin win;
         win.t = t; win.im = im; win.f = f; win.ww = ww;
         const TeleaMarchConsts mc = telea_march_consts(lane, ww, range);
-        switch (mc.ndisc) {
-        case 5: mw_fill_loop<5>(win, mc, fi, flist, dep, rq, ctl, nfill, lane); break;
-        case 13: mw_fill_loop<13>(win, mc, fi, flist, dep, rq, ctl, nfill, lane); break;
-        case 29: mw_fill_loop<29>(win, mc, fi, flist, dep, rq, ctl, nfill, lane); break;
-        default: mw_fill_loop<49>(win, mc, fi, flist, dep, rq, ctl, nfill, lane); break;       // range 4 (the launcher admits ranges 1..4 only)
-        }
+        // the launcher admits ranges 1..4 only: anything that is not 5, 13 or 29 positions is range 4
+        telea_dispatch_ndisc<49>(mc.ndisc, [&](auto ns) { mw_fill_loop<decltype(ns)::value>(win, mc, fi, flist, dep, rq, ctl, nfill, lane); });
     }
     __syncthreads();
     MSTAMP(5);
@@ -691,7 +645,7 @@ __global__ __launch_bounds__(MW_T) void k_telea_window_mw(float *__restrict__ im
     for (int li = tid; li < cells; li += MW_T) {
         if (!(f[li] & W_HOLE)) continue;
         const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-        img[(size_t)(i0 + r - 1) * w + (j0 + cc - 1)] = im[li];
+        img[bw.pixel(r, cc, w)] = im[li];
     }
     if (tid == 0) fb[b] = 0;
     MSTAMP(6);

@@ -8,7 +8,7 @@
 // flag plane plus the priority queue in LDS (<= 160 KB): every dependent read of the march is an LDS access
 // instead of an L2 round trip.  Raster order inside a rectangle equals raster order in the frame, so seeds
 // and queue ties pop in the same order as in the whole-frame kernel; T, the march order and therefore the
-// set of neighbours every estimate uses are identical (the float sums are reduced in a different order).
+// set of neighbours every estimate uses are identical, and the estimator's sums run in OpenCV's order: the result is bit-identical.
 // Frames whose window or queue does not fit raise fb[b]; the whole-frame kernel then handles exactly those.
 //
 // The march is a chain of dependent steps on ONE wave (about 8 cycles per dependent VALU op, 64+ per LDS
@@ -19,16 +19,14 @@
 //   * the four 4-neighbours of a popped pixel are tested by four lanes in one LDS round;
 //   * the neighbours' (flag, T) pairs loaded for the FMM solve are reused for grad T;
 //   * queue entries are packed (T bits << 32 | cell) so a push moves one 64-bit word per lane;
-//   * the (2r+1)^2 estimator terms are accumulated per lane over the 64-neighbour chunks and reduced once.
+//   * the estimator's terms are formed one window position per lane and summed in lane order (telea_common.hpp: wn_seq_sum).
 #include <cstdio>
 #include "host_util.hpp"
-#include <type_traits>
 #include "telea_common.hpp"
 
 namespace vf {
 
 constexpr int WN_LOAD_U = 8;         // window cells per lane in flight while the window is loaded
-constexpr int WN_RING_U = 6;         // inpaint ranges up to this have their ring taps unrolled (independent loads)
 constexpr int WN_QCAP = 4096;       // live queue entries (8 B each)
 constexpr int WN_CELLS = 14464;     // window cells (9 B each: T f32, image f32, flags u8)
 // First tier: 110.75 KB.  It leaves 49 KB of the CU's LDS to the kernels of the other sessions in flight (exact selection 37 KB, column
@@ -45,7 +43,6 @@ __device__ unsigned long long g_win_dbg[1024][16];
 #else
 #define WSTAMP(i) do { } while (0)
 #endif
-
 
 // box planes [4][B]: xmin, ymin (start 0x7f7f7f7f), xmax, ymax (start 0) of the hole pixels of each frame
 // VEC: 16 mask bytes per thread (P must be a multiple of 16); most words are zero, coordinates are only formed for set bytes
@@ -86,14 +83,17 @@ __global__ __launch_bounds__(256) void k_bad_bbox(const uint8_t *__restrict__ ba
     }
 }
 
-// (nothing has been written back).
+// The march on one window.  CL = false: the window holds every hole pixel of the frame (lab / rootp unused).  CL = true: only the hole
+// pixels of the cluster `rootp` (label plane `lab`) are INSIDE; hole pixels of other clusters that happen to lie in the window are treated as
+// known pixels -- they are farther than range + 1 from every pixel this march reads, and they are restored by their own march.  Returns false
+// when the queue overflowed (nothing has been written back).
 // always_inline: called from three kernels; left as a call the march's one-basic-block fill is laid out differently and the window
 // kernel gets 15 % slower (3.91 against 3.40 ms per batch, measured)
 template <bool CL>
 __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict__ img, const uint8_t *__restrict__ bad, const int32_t *__restrict__ lab, int rootp,
-                                int i0, int j0, int wh, int ww, int range, int h, int w, unsigned char *lds, int cells_cap, int qcap,
-                                int lane, int b)
+                                const TeleaBoxWin bw, int range, int h, int w, unsigned char *lds, int cells_cap, int qcap, int lane, int b)
 {
+    const int wh = bw.wh, ww = bw.ww;
     unsigned long long *qe = (unsigned long long *)lds;          // [qcap]
     float *t = (float *)(qe + qcap);                             // [cells_cap]
     float *im = t + cells_cap;                                   // [cells_cap]
@@ -105,7 +105,7 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
     // ---- load window: hole / border bits, T = 1e6, image.  Cells in flat order, WN_LOAD_U per lane in flight (a row-by-row loop is one
     // memory round trip per 64 cells on this lone wave)
     {
-        const uint32_t mg_ww = (uint32_t)(0x100000000ull / (unsigned)ww) + 1u;       // li / ww == umulhi(li, mg_ww) for li < 2^16
+        const uint32_t mg_ww = telea_magic_ww(ww);
         for (int base = 0; base < cells; base += 64 * WN_LOAD_U) {
             float v[WN_LOAD_U];
             uint8_t bd[WN_LOAD_U];
@@ -115,9 +115,8 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
             for (int k = 0; k < WN_LOAD_U; k++) {
                 const int li = base + k * 64 + lane;
                 const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
-                const int gi = i0 + r, gj = j0 + cc;
-                interior[k] = li < cells && gi >= 1 && gi <= h && gj >= 1 && gj <= w;
-                const size_t gp = interior[k] ? (size_t)(gi - 1) * w + (gj - 1) : 0;
+                size_t gp;
+                interior[k] = bw.locate(li, cells, r, cc, h, w, gp);
                 v[k] = img[gp];
                 bd[k] = bad[gp];
                 lab_v[k] = CL ? lab[gp] : 0;
@@ -136,12 +135,9 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
     }
     __builtin_amdgcn_wave_barrier();
     WSTAMP(1);
-    // ---- ring = within Chebyshev `range` of the hole (separable: rows, then columns).  Cells in flat order, two per lane and iteration;
-    // every tap of a cell is an independent load (clamped index + select: a loop over [-range, range] or a short-circuit test would be one
-    // dependent LDS round trip per tap on this lone wave).
+    // ---- ring and band (telea_common.hpp: window build).  Cells in flat order, two per lane and iteration
     {
-        const uint32_t mg_ww = (uint32_t)(0x100000000ull / (unsigned)ww) + 1u;
-        const bool unrolled = range <= WN_RING_U;
+        const uint32_t mg_ww = telea_magic_ww(ww);
         for (int base = 0; base < cells; base += 128) {
             uint8_t any[2], me[2];
 #pragma unroll
@@ -149,20 +145,7 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
                 const int li = min(base + k * 64 + lane, cells - 1);
                 const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
                 me[k] = f[li];
-                uint8_t a = 0;
-                if (unrolled) {
-#pragma unroll
-                    for (int d = -WN_RING_U; d <= WN_RING_U; d++) {
-                        const int c2 = cc + d;
-                        const bool in = d >= -range && d <= range && c2 >= 0 && c2 < ww;
-                        const uint8_t v = f[in ? li + d : li];
-                        a |= in ? v : (uint8_t)0;
-                    }
-                } else {
-                    const int lo = max(0, cc - range), hi = min(ww - 1, cc + range);
-                    for (int c2 = lo; c2 <= hi; c2++) a |= f[r * ww + c2];
-                }
-                any[k] = a;
+                any[k] = telea_ring_row_tap(f, li, r, cc, ww, range);
             }
 #pragma unroll
             for (int k = 0; k < 2; k++) {
@@ -178,31 +161,16 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
                 const int li = min(base + k * 64 + lane, cells - 1);
                 const int r = (int)__umulhi((uint32_t)li, mg_ww), cc = li - r * ww;
                 me[k] = f[li];
-                // window edge cells are at distance range+1 from the hole: never band, their neighbours are not needed (a clamped index
-                // reads the cell itself, which only matters when it is not a hole pixel)
-                nb4[k] = f[cc > 0 ? li - 1 : li] | f[cc < ww - 1 ? li + 1 : li] | f[r > 0 ? li - ww : li] | f[r < wh - 1 ? li + ww : li];
-                uint8_t a = 0;
-                if (unrolled) {
-#pragma unroll
-                    for (int d = -WN_RING_U; d <= WN_RING_U; d++) {
-                        const int r2 = r + d;
-                        const bool in = d >= -range && d <= range && r2 >= 0 && r2 < wh;
-                        const uint8_t v = f[in ? li + d * ww : li];
-                        a |= in ? v : (uint8_t)0;
-                    }
-                } else {
-                    const int lo = max(0, r - range), hi = min(wh - 1, r + range);
-                    for (int r2 = lo; r2 <= hi; r2++) a |= f[r2 * ww + cc];
-                }
-                any[k] = a;
+                nb4[k] = telea_nb4_tap(f, li, r, cc, wh, ww);
+                any[k] = telea_ring_col_tap(f, li, r, cc, wh, ww, range);
             }
             // reads of this iteration see W_ROW / W_HOLE only (bits 5 and 6), which the writes below never change
 #pragma unroll
             for (int k = 0; k < 2; k++) {
                 const int li = base + k * 64 + lane;
-                if (li >= cells || (me[k] & (W_BORDER | W_HOLE))) continue;     // hole pixels are KNOWN for the outside pass
-                if (nb4[k] & W_HOLE) { f[li] = me[k] | W_SEED; t[li] = 0.f; }
-                else if (any[k] & W_ROW) f[li] = me[k] | W_INSIDE;               // writes bits 0-1 only
+                const int kind = li < cells ? telea_cell_kind(me[k], nb4[k], any[k]) : TC_NONE;
+                if (kind == TC_BAND) { f[li] = me[k] | W_SEED; t[li] = 0.f; }
+                else if (kind == TC_RING) f[li] = me[k] | W_INSIDE;              // writes bits 0-1 only
             }
         }
         __builtin_amdgcn_wave_barrier();
@@ -223,11 +191,12 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
         telea_fmm_pass(fst, q, f, cells, ww, lane, np1, ns1);
     }
     WSTAMP(4);
-    // negate T where the outside pass ran; switch the state bits to the march's flags (hole = INSIDE, rest KNOWN)
+    // negate T where the outside pass ran; switch the state bits to the march's flags
     for (int li = lane; li < cells; li += 64) {
-        uint8_t v = f[li];
-        if ((v & W_ST) == W_CHANGE) t[li] = -t[li];
-        f[li] = (uint8_t)((v & (W_SEED | W_HOLE | W_BORDER)) | ((v & W_HOLE) ? W_INSIDE : W_KNOWN));
+        bool neg;
+        const uint8_t v = telea_to_march_state(f[li], neg);
+        if (neg) t[li] = -t[li];
+        f[li] = v;
     }
     __builtin_amdgcn_wave_barrier();
 
@@ -248,27 +217,18 @@ __device__ __attribute__((always_inline)) inline bool wn_march(float *__restrict
             }
         }
     };
-    // discs of the inpaint ranges 1..4 (5, 13, 29, 49 positions): straight-line estimator with that many lanes; anything else: chunk loop
-    switch (mc.ndisc) {
-    case 5: march(std::integral_constant<int, 5>{}); break;
-    case 13: march(std::integral_constant<int, 13>{}); break;
-    case 29: march(std::integral_constant<int, 29>{}); break;
-    case 49: march(std::integral_constant<int, 49>{}); break;
-    default: march(std::integral_constant<int, 0>{}); break;
-    }
+    telea_dispatch_ndisc(mc.ndisc, march);
     WSTAMP(7);
 #ifdef VISTAF_DEBUG
     if (!CL && lane == 0 && b < 1024) { g_win_dbg[b][8] = (np1 << 32) | np2; g_win_dbg[b][9] = (nfill << 32) | (unsigned)cells; g_win_dbg[b][10] = ns1; }
 #endif
     if (q.ovf) return false;
     // ---- write back the hole pixels
-    for (int r = 0; r < wh; r++) {
-        const int gi = i0 + r;
+    for (int r = 0; r < wh; r++)
         for (int cc = lane; cc < ww; cc += 64) {
             int li = r * ww + cc;
-            if (f[li] & W_HOLE) img[(size_t)(gi - 1) * w + (j0 + cc - 1)] = im[li];
+            if (f[li] & W_HOLE) img[bw.pixel(r, cc, w)] = im[li];
         }
-    }
     return true;
 }
 
@@ -285,13 +245,9 @@ __device__ __attribute__((always_inline)) inline void telea_window_body(float *_
         if (RETRY && fb[b] != 1) continue;
         const int xmin = box[b], ymin = box[B + b], xmax = box[2 * B + b], ymax = box[3 * B + b];
         if (xmin == 0x7f7f7f7f) continue;                        // no hole pixel: nothing to inpaint
-        const int M = range + 1;
-        // window in padded frame coordinates [i0, i1] x [j0, j1], not clipped (cells beyond the image: BORDER)
-        const int i0 = ymin + 1 - M, i1 = ymax + 1 + M;
-        const int j0 = xmin + 1 - M, j1 = xmax + 1 + M;
-        const int wh = i1 - i0 + 1, ww = j1 - j0 + 1;
-        bool ok = wh * ww <= cells_cap;
-        if (ok) ok = wn_march<false>(img_all + (size_t)b * P, bad_all + (size_t)b * P, nullptr, 0, i0, j0, wh, ww, range, h, w, wn_lds, cells_cap, qcap, lane, b);
+        const TeleaBoxWin bw = telea_window_of_box(xmin, ymin, xmax, ymax, range);
+        bool ok = bw.cells() <= cells_cap;
+        if (ok) ok = wn_march<false>(img_all + (size_t)b * P, bad_all + (size_t)b * P, nullptr, 0, bw, range, h, w, wn_lds, cells_cap, qcap, lane, b);
         if (lane == 0) fb[b] = ok ? 0 : 1;
     }
 }
@@ -329,22 +285,20 @@ __global__ __launch_bounds__(64) void k_telea_clusters2(float *__restrict__ img_
     const size_t b = blockIdx.y;
     const int P = h * w;
     const int ncl = count[b];
-    const int M = range + 1;
     for (int c = blockIdx.x; c < ncl; c += gridDim.x) {
         const int rootp = list_all[b * (size_t)P + c];
         const size_t root = b * (size_t)P + rootp;
-        const int i0 = ymin[root] + 1 - M, i1 = ymax[root] + 1 + M;
-        const int j0 = xmin[root] + 1 - M, j1 = xmax[root] + 1 + M;
-        const int wh = i1 - i0 + 1, ww = j1 - j0 + 1;
-        bool ok = wh * ww <= CL2_CELLS;
-        if (ok) ok = wn_march<true>(img_all + b * (size_t)P, bad_all + b * (size_t)P, labels_all + b * (size_t)P, rootp, i0, j0, wh, ww, range, h, w,
-                                    wn_lds, CL2_CELLS, CL2_QCAP, lane, 0);
+        const TeleaBoxWin bw = telea_window_of_box(xmin[root], ymin[root], xmax[root], ymax[root], range);
+        bool ok = bw.cells() <= CL2_CELLS;
+        if (ok) ok = wn_march<true>(img_all + b * (size_t)P, bad_all + b * (size_t)P, labels_all + b * (size_t)P, rootp, bw, range, h, w, wn_lds, CL2_CELLS,
+                                    CL2_QCAP, lane, 0);
         if (!ok && lane == 0) big[root] = 1;
         __builtin_amdgcn_wave_barrier();
     }
 }
 
 int inpaint_cluster_cells_cap() { return CL2_CELLS; }
+int inpaint_window_cells_cap() { return WN_CELLS; }
 
 void launch_telea_clusters2(float *img, const uint8_t *bad, const int32_t *labels, const int32_t *list, const int32_t *count, const int32_t *xmin,
                             const int32_t *ymin, const int32_t *xmax, const int32_t *ymax, uint8_t *big, int range, int B, int h, int w, hipStream_t st)

@@ -173,6 +173,8 @@ void launch_inpaint_telea(float *img, const uint8_t *bad, int range, void *scrat
 
 // ---- k_inpaint_win.hip (LDS-resident window kernel; returns the per-frame fallback flags for launch_inpaint_telea)
 size_t inpaint_win_scratch_bytes(int B, ScratchRec *rec = nullptr);
+int inpaint_window_cells_cap();         // window cells of the full-size single-wave tier
+int inpaint_cluster_cells_cap();        // window cells of one LDS cluster
 // ---- k_inpaint_mw.hip (16 waves per frame: ordering pass, then the estimates as a dataflow; flags the frames it cannot take in fb[])
 bool inpaint_window_mw_supported(int range);
 void launch_telea_window_mw(float *img, const uint8_t *bad, const int32_t *box, int32_t *fb, int range, int B, int h, int w, hipStream_t st);

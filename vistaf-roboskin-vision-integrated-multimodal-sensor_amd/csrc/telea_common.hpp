@@ -1,13 +1,125 @@
-// Shared pieces of the LDS-resident Telea march (k_inpaint_win.hip: frame-window and cluster kernels): flag byte layout, DPP helpers, the
-// two-run stable priority queue, the FMM quadrant solve and the raster seed scan.
+// The rules of the Telea inpaint family (k_inpaint*.hip), each stated once: the flag byte and its two state sets, the magic row division, the
+// window of a hole box, the window build's taps and its hole / band / ring classification, the FMM quadrant solve and the quad minimum, the
+// outside pass's per-pop body, the estimator's arithmetic, the ordered sums, and the two-run stable priority queue of the single-wave marches.
+// Private to the family.  Pure arithmetic is __host__ __device__ so that tests/diag/telea_host_check.hip can hold it against brute force.
 #pragma once
+#include <type_traits>
+#include "common.hpp"
 #include "kernels.hpp"
 
 namespace vf {
 
+// ---- the family's inner launcher (the public ones and the capacities are in kernels.hpp) --------------------------------------------------------
+// k_inpaint_win.hip: every cluster of the list on its own LDS window, one wave each; big[root] = 1 for those whose queue overflowed
+void launch_telea_clusters2(float *img, const uint8_t *bad, const int32_t *labels, const int32_t *list, const int32_t *count, const int32_t *xmin,
+                            const int32_t *ymin, const int32_t *xmax, const int32_t *ymax, uint8_t *big, int range, int B, int h, int w, hipStream_t st);
+
 // flag byte: bits 0-1 state, bit 4 outside the image, bit 5 scratch (hole in row range), bit 6 hole pixel,
 // bit 7 seed (initial band)
 constexpr uint8_t W_KNOWN = 0, W_BAND = 1, W_INSIDE = 2, W_CHANGE = 3, W_ST = 3, W_BORDER = 0x10, W_ROW = 0x20, W_HOLE = 0x40, W_SEED = 0x80;
+
+// cell / ww == umulhi(cell, magic) for every cell with cell * ww < 2^32
+__host__ __device__ inline uint32_t telea_magic_ww(int ww) { return (uint32_t)(0x100000000ull / (unsigned)ww) + 1u; }
+// the multiplier of a plane of `rows` rows of ww cells, 0 where the split is not exact for every cell of it (the convention of unwrap.hpp)
+__host__ __device__ inline uint32_t telea_magic_plane(int ww, int rows)
+{
+    return (unsigned long long)ww * (unsigned long long)ww * (unsigned long long)rows < 0x100000000ull ? telea_magic_ww(ww) : 0u;
+}
+
+// The window of a box of hole pixels (frame coordinates, inclusive): the box grown by range + 1, NOT clipped to the frame.  Cell (r, cc) is
+// pixel (i0 + r - 1, j0 + cc - 1): i0 / j0 are coordinates of the frame padded by one cell, cells beyond the image carry W_BORDER.
+struct TeleaBoxWin {
+    int i0, j0, wh, ww;
+    __host__ __device__ int cells() const { return wh * ww; }
+    // cell (r, cc) of a window of `ncell` cells (li = its index): inside the image?  gp = its pixel index there, else 0
+    __host__ __device__ __attribute__((always_inline)) bool locate(int li, int ncell, int r, int cc, int h, int w, size_t &gp) const
+    {
+        const int gi = i0 + r, gj = j0 + cc;
+        const bool in = li < ncell && gi >= 1 && gi <= h && gj >= 1 && gj <= w;
+        gp = in ? (size_t)(gi - 1) * w + (gj - 1) : 0;
+        return in;
+    }
+    __host__ __device__ __attribute__((always_inline)) size_t pixel(int r, int cc, int w) const { return (size_t)(i0 + r - 1) * w + (j0 + cc - 1); }
+};
+__host__ __device__ inline TeleaBoxWin telea_window_of_box(int xmin, int ymin, int xmax, int ymax, int range)
+{
+    const int M = range + 1;
+    const int i0 = ymin + 1 - M, i1 = ymax + 1 + M, j0 = xmin + 1 - M, j1 = xmax + 1 + M;      // [i0, i1] x [j0, j1] in padded frame coordinates
+    return {i0, j0, i1 - i0 + 1, j1 - j0 + 1};
+}
+
+// ---- window build: ring = within Chebyshev `range` of the hole, separable (rows into W_ROW, then columns); band = 4-neighbours of the hole.
+// Per-cell pieces; the kernels keep their own loops.  Every tap of a cell is an independent load (clamped index + select: a loop over
+// [-range, range] or a short-circuit test would be one dependent LDS round trip per tap); ranges above TELEA_RING_U loop.
+constexpr int TELEA_RING_U = 6;
+// OR of the flag bytes within `range` columns of cell li = (r, cc) in its row
+__host__ __device__ __attribute__((always_inline)) inline uint8_t telea_ring_row_tap(const uint8_t *f, int li, int r, int cc, int ww, int range)
+{
+    uint8_t a = 0;
+    if (range <= TELEA_RING_U) {
+#pragma unroll
+        for (int d = -TELEA_RING_U; d <= TELEA_RING_U; d++) {
+            const int c2 = cc + d;
+            const bool in = d >= -range && d <= range && c2 >= 0 && c2 < ww;
+            const uint8_t v = f[in ? li + d : li];
+            a |= in ? v : (uint8_t)0;
+        }
+    } else {
+        const int lo = cc - range > 0 ? cc - range : 0, hi = cc + range < ww - 1 ? cc + range : ww - 1;
+        for (int c2 = lo; c2 <= hi; c2++) a |= f[r * ww + c2];
+    }
+    return a;
+}
+// OR of the flag bytes within `range` rows of cell li = (r, cc) in its column
+__host__ __device__ __attribute__((always_inline)) inline uint8_t telea_ring_col_tap(const uint8_t *f, int li, int r, int cc, int wh, int ww, int range)
+{
+    uint8_t a = 0;
+    if (range <= TELEA_RING_U) {
+#pragma unroll
+        for (int d = -TELEA_RING_U; d <= TELEA_RING_U; d++) {
+            const int r2 = r + d;
+            const bool in = d >= -range && d <= range && r2 >= 0 && r2 < wh;
+            const uint8_t v = f[in ? li + d * ww : li];
+            a |= in ? v : (uint8_t)0;
+        }
+    } else {
+        const int lo = r - range > 0 ? r - range : 0, hi = r + range < wh - 1 ? r + range : wh - 1;
+        for (int r2 = lo; r2 <= hi; r2++) a |= f[r2 * ww + cc];
+    }
+    return a;
+}
+// OR of the flag bytes of the four 4-neighbours.  Window edge cells are at distance range + 1 from the hole: never band, their neighbours are
+// not needed (a clamped index reads the cell itself, which only matters when it is not a hole pixel)
+__host__ __device__ __attribute__((always_inline)) inline uint8_t telea_nb4_tap(const uint8_t *f, int li, int r, int cc, int wh, int ww)
+{
+    return f[cc > 0 ? li - 1 : li] | f[cc < ww - 1 ? li + 1 : li] | f[r > 0 ? li - ww : li] | f[r < wh - 1 ? li + ww : li];
+}
+// what the outside pass makes of a cell: nothing (a hole pixel -- KNOWN for that pass --, a cell beyond the image, or out of reach), a band
+// pixel (seed of both passes, T = 0) or a ring cell (INSIDE for the outside pass)
+enum TeleaCellKind { TC_NONE = 0, TC_BAND = 1, TC_RING = 2 };
+// me = the cell's flag byte, nb4 = telea_nb4_tap, col = telea_ring_col_tap over bytes that carry W_ROW
+__host__ __device__ __attribute__((always_inline)) inline int telea_cell_kind(uint8_t me, uint8_t nb4, uint8_t col)
+{
+    if (me & (W_BORDER | W_HOLE)) return TC_NONE;
+    if (nb4 & W_HOLE) return TC_BAND;
+    return (col & W_ROW) ? TC_RING : TC_NONE;
+}
+// the same classification of a known pixel (y, x) inside the image straight from a hole predicate (the prep kernels: one thread per cell)
+template <class Hole>
+__host__ __device__ __attribute__((always_inline)) inline int telea_known_pixel_kind(Hole hole, int y, int x, int range)
+{
+    if (hole(y, x - 1) || hole(y, x + 1) || hole(y - 1, x) || hole(y + 1, x)) return TC_BAND;
+    for (int a = -range; a <= range; a++)
+        for (int c = -range; c <= range; c++)
+            if (hole(y + a, x + c)) return TC_RING;
+    return TC_NONE;
+}
+// After the outside pass: the flag byte with the march's state (hole = INSIDE, rest KNOWN); neg = the outside pass ran here (CHANGE), T is negated
+__host__ __device__ __attribute__((always_inline)) inline uint8_t telea_to_march_state(uint8_t v, bool &neg)
+{
+    neg = (v & W_ST) == W_CHANGE;
+    return (uint8_t)((v & (W_SEED | W_HOLE | W_BORDER)) | ((v & W_HOLE) ? W_INSIDE : W_KNOWN));
+}
 
 __device__ inline float wn_lane_f(float v, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), l)); }
 
@@ -67,6 +179,51 @@ __device__ inline float telea_estimate_u8(float Ia, float Jx, float Jy, float s)
 }
 // 1 / (1 + |T - Tc|) formed in double and rounded to float (inpaint.cpp: lev = (float)(1./(1+fabs(...))))
 __device__ inline float telea_lev(float tk, float tc) { return (float)(1.0 / (1.0 + (double)fabsf(__fsub_rn(tk, tc)))); }
+// 1 / |r|^3 of the offset r = (rx, ry) from a window position to the pixel (dst = 1 / (|r|^2 * |r|), the product in float, the quotient in
+// double); 0 at the centre, which never contributes
+__device__ inline float telea_dstw(float rx, float ry)
+{
+    const float len2 = __fadd_rn(__fmul_rn(rx, rx), __fmul_rn(ry, ry));
+    return len2 > 0.f ? (float)(1. / (double)__fmul_rn(len2, sqrtf(len2))) : 0.f;
+}
+// r . grad T, replaced by 1e-6 where |.| <= 0.01 (float(0.01) < 0.01: the same set of floats as OpenCV's double compare)
+__device__ inline float telea_dir(float rx, float ry, float gtx, float gty)
+{
+    const float dir = __fadd_rn(__fmul_rn(rx, gtx), __fmul_rn(ry, gty));
+    return fabsf(dir) <= 0.01f ? 0.000001f : dir;
+}
+__device__ inline float telea_weight(float dstw, float lev, float dir) { return fabsf(__fmul_rn(__fmul_rn(dstw, lev), dir)); }
+// OpenCV's gradient along one axis from the states of the two neighbours: kp / km = the neighbour at +1 / -1 is not INSIDE; both usable:
+// the central difference, one: the one-sided difference, none: 0.  All three differences come evaluated and are SELECTED (two levels):
+// nested conditional expressions would come back as branches, and a taken branch costs a lone wave tens of cycles.
+__device__ __attribute__((always_inline)) inline float telea_grad_select(bool kp, bool km, float both, float fwd, float bwd)
+{
+    const float g_p = km ? both : fwd, g_n = km ? bwd : 0.f;
+    return kp ? g_p : g_n;
+}
+// grad T at the pixel being filled (tc: its own T just solved; tp / tm: its neighbours at +1 / -1)
+__device__ __attribute__((always_inline)) inline float telea_grad_T(bool kp, bool km, float tp, float tm, float tc)
+{
+    return telea_grad_select(kp, km, __fmul_rn(__fsub_rn(tp, tm), 0.5f), __fsub_rn(tp, tc), __fsub_rn(tc, tm));
+}
+// gradient of the image at a window position along one axis: vP / vM = the values at +1 / -1, vC = the position's own, vS = the value the
+// backward difference starts from (vC unless OpenCV's index shift at the image border moves it); kp / km as above
+__device__ __attribute__((always_inline)) inline float telea_grad_I(bool kp, bool km, float vP, float vM, float vC, float vS)
+{
+    return telea_grad_select(kp, km, __fmul_rn(__fsub_rn(vP, vM), 2.0f), __fsub_rn(vP, vC), __fsub_rn(vS, vM));
+}
+// terms of Ia += w * I, Jx -= w * (gix * rx), Jy -= w * (giy * ry), s += w of one window position; a position that is not used adds 0
+struct TeleaTerms { float Ia, Jx, Jy, s; };
+__device__ __attribute__((always_inline)) inline TeleaTerms telea_terms(bool use, float wgt, float vC, float gix, float giy, float rx, float ry)
+{
+    const float z = 0.f;
+    TeleaTerms a;
+    a.Ia = use ? __fmul_rn(wgt, vC) : z;
+    a.Jx = use ? -__fmul_rn(wgt, __fmul_rn(gix, rx)) : z;
+    a.Jy = use ? -__fmul_rn(wgt, __fmul_rn(giy, ry)) : z;
+    a.s = use ? wgt : z;
+    return a;
+}
 
 // Stable priority queue (T, push order), the semantics of OpenCV's CvPriorityQueueFloat.  Two sorted runs:
 //   * COLD: a sorted array of (T bits << 32 | cell) words in LDS, popped at its head;
@@ -208,12 +365,21 @@ __device__ inline float wn_solve(double a11, double a22, bool k1, bool k2)
     return (float)sol;
 }
 
-// next seed (initial band pixel) in raster order, -1 when exhausted; (base, pend) is the scan state
+// minimum over the four lanes of a quad (the four quadrant solves of one pixel), in each of them
+__device__ __attribute__((always_inline)) inline float quad_min(float v)
+{
+    float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, false)); v = o < v ? o : v;       // quad_perm [1,0,3,2]
+    o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, false)); return o < v ? o : v;           // quad_perm [2,3,0,1]
+}
+
+// next seed (initial band pixel) in raster order, -1 when exhausted; (base, pend) is the scan state.  LDS = false: the flag plane is in
+// global memory (the whole-frame kernel)
+template <bool LDS = true>
 __device__ inline int wn_next_seed(const uint8_t *f, int cells, int &base, unsigned long long &pend, int lane)
 {
     while (!pend && base < cells) {
         int li = base + lane;
-        pend = __ballot(li < cells && (f[li] & W_SEED));
+        pend = __ballot(li < cells && ((LDS ? f[li] : ld_relaxed<__HIP_MEMORY_SCOPE_WAVEFRONT>(f + li)) & W_SEED));
         if (!pend) base += 64;
     }
     if (!pend) return -1;
@@ -224,12 +390,7 @@ __device__ inline int wn_next_seed(const uint8_t *f, int cells, int &base, unsig
     return p;
 }
 
-// The march on one window.  CL = false: the window holds every hole pixel of the frame (lab / rootp unused).
-// CL = true: only the hole pixels of the cluster `rootp` (label plane `lab`) are INSIDE; hole pixels of other
-// clusters that happen to lie in the window are treated as known pixels -- they are farther than range + 1 from
-// every pixel this march reads, and they are restored by their own march.  Returns false when the queue overflowed
-
-// ---- the two per-pop bodies of the march, shared by the frame-window and the cluster kernel -------------------------
+// ---- the per-pop bodies of the two passes, shared by every tier whose planes are padded (windows in LDS, padded planes in global memory) ----
 struct TeleaWin {
     float *t, *im;          // LDS planes of the window: T field, image
     uint8_t *f;             // flag bytes
@@ -252,16 +413,24 @@ struct TeleaMarchConsts {
     float rx[2], ry[2], dstw[2];
     bool on[2];
 };
-__device__ inline TeleaMarchConsts telea_march_consts(int lane, int ww, int range)
+// The disc enumeration: which position (dk, dl) of the (2 range + 1)^2 estimator window lane `lane` takes in chunk c2 (0 or 1), and whether
+// it is inside the disc dk^2 + dl^2 <= range^2.  When the disc has at most 64 positions (range <= 4) lane i takes the i-th of them in
+// row-major order: positions outside the disc never contribute, and the sequential sums then need ndisc - 1 steps instead of side^2 - 1.
+// Larger ranges: all side^2 positions, row-major, 64 per chunk.
+struct TeleaDisc {
+    int nn, ndisc;              // positions enumerated (ndisc when compact, else side^2), positions inside the disc
+    int dk[2], dl[2];
+    bool on[2];
+};
+__host__ __device__ inline TeleaDisc telea_disc(int lane, int range)
 {
-    TeleaMarchConsts c;
-    c.range = range; c.r2 = range * range; c.side = 2 * range + 1; c.nn = c.side * c.side;
-    // When the disc has at most 64 positions (range <= 4) lane i takes the i-th of them in row-major order: positions outside the disc never
-    // contribute, and the sequential sums then need ndisc - 1 steps instead of side^2 - 1.  Larger ranges: all side^2 positions, row-major.
+    TeleaDisc c;
+    const int side = 2 * range + 1, r2 = range * range;
+    c.nn = side * side;
     int nd = 0, mine = -1;
     for (int i = 0; i < c.nn; i++) {
-        const int dk = i / c.side - range, dl = i % c.side - range;
-        if (dl * dl + dk * dk <= c.r2) { if (nd == lane) mine = i; nd++; }
+        const int dk = i / side - range, dl = i % side - range;
+        if (dl * dl + dk * dk <= r2) { if (nd == lane) mine = i; nd++; }
     }
     c.ndisc = nd;
     const bool compact = nd <= 64;
@@ -271,50 +440,47 @@ __device__ inline TeleaMarchConsts telea_march_consts(int lane, int ww, int rang
         int nidx = c2 * 64 + lane;
         bool valid = nidx < c.nn;
         if (compact) { valid = c2 == 0 && mine >= 0; nidx = valid ? mine : 0; }
-        int dk = nidx / c.side - range, dl = nidx % c.side - range;
-        c.on[c2] = valid && (dl * dl + dk * dk <= c.r2);
-        c.off[c2] = c.on[c2] ? dk * ww + dl : 0;              // lanes that are off may read, unused, the centre pixel
-        float ry = (float)(-dk), rx = (float)(-dl);
+        c.dk[c2] = nidx / side - range; c.dl[c2] = nidx % side - range;
+        c.on[c2] = valid && (c.dl[c2] * c.dl[c2] + c.dk[c2] * c.dk[c2] <= r2);
+    }
+    return c;
+}
+__device__ inline TeleaMarchConsts telea_march_consts(int lane, int ww, int range)
+{
+    TeleaMarchConsts c;
+    c.range = range; c.r2 = range * range; c.side = 2 * range + 1;
+    const TeleaDisc d = telea_disc(lane, range);
+    c.nn = d.nn; c.ndisc = d.ndisc;
+#pragma unroll
+    for (int c2 = 0; c2 < 2; c2++) {
+        c.on[c2] = d.on[c2];
+        c.off[c2] = c.on[c2] ? d.dk[c2] * ww + d.dl[c2] : 0;              // lanes that are off may read, unused, the centre pixel
+        float ry = (float)(-d.dk[c2]), rx = (float)(-d.dl[c2]);
         c.rx[c2] = rx; c.ry[c2] = ry;
-        float len2 = __fadd_rn(__fmul_rn(rx, rx), __fmul_rn(ry, ry));
-        c.dstw[c2] = len2 > 0.f ? (float)(1. / (double)__fmul_rn(len2, sqrtf(len2))) : 0.f;
+        c.dstw[c2] = telea_dstw(rx, ry);
     }
     c.d4 = (lane & 3) == 0 ? -ww : (lane & 3) == 1 ? -1 : (lane & 3) == 2 ? ww : 1;    // up, left, down, right
     return c;
 }
 
-// Outside T field (icvCalcFMM with `negate`): pop p (a seed of the initial band or a queue entry), give every ring
-// neighbour its T and push it.  States are those of OpenCV's `out` mask: ring = INSIDE, hole and everything else KNOWN.
-template <class Push>
-__device__ __attribute__((always_inline)) inline void telea_pop_outside(const TeleaWin &win, const TeleaOutsideConsts &oc, int p, bool seed, int lane,
-                                                                        Push push)
+// fn(std::integral_constant<int, NS>) with NS = the disc's positions for the inpaint ranges 1..4 (5, 13, 29, 49: the straight-line estimator
+// with that many lanes), anything else NS = OTHER (0: the chunk loop)
+template <int OTHER = 0, class F>
+__device__ __attribute__((always_inline)) inline void telea_dispatch_ndisc(int ndisc, F fn)
 {
-    float *t = win.t;
-    uint8_t *f = win.f;
-    const int dn = oc.dn, d1 = oc.d1, d2 = oc.d2;
-    if (lane == 0) f[p] = (uint8_t)(seed ? (W_SEED | W_CHANGE) : W_CHANGE);   // ring pixels carry no other bit that matters
-    const int pn = p + dn;
-    bool ok = lane < 16 && (f[pn] & W_ST) == W_INSIDE;
-    if (!__ballot(ok)) return;
-    float dist = 0.f;
-    if (ok) {
-        const int p1 = pn + d1, p2 = pn + d2;
-        float a11 = t[p1], a22 = t[p2];
-        uint8_t f1 = f[p1], f2 = f[p2];
-        dist = wn_solve(a11, a22, (f1 & W_ST) != W_INSIDE, (f2 & W_ST) != W_INSIDE);
-    }
-    float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0xB1, 0xf, 0xf, false)); dist = o < dist ? o : dist;
-    o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0x4E, 0xf, 0xf, false)); dist = o < dist ? o : dist;
-    for (int k = 0; k < 4; k++) {
-        bool okk = __builtin_amdgcn_readlane((int)ok, k * 4) != 0;
-        if (!okk) continue;
-        float dk = wn_lane_f(dist, k * 4);
-        int pk = __builtin_amdgcn_readlane(pn, k * 4);
-        if (lane == 0) { t[pk] = dk; f[pk] = W_BAND; }
-        push(dk, pk);
+    switch (ndisc) {
+    case 5: fn(std::integral_constant<int, 5>{}); break;
+    case 13: fn(std::integral_constant<int, 13>{}); break;
+    case 29: fn(std::integral_constant<int, 29>{}); break;
+    case 49:
+        if constexpr (OTHER != 49) { fn(std::integral_constant<int, 49>{}); break; }
+        [[fallthrough]];
+    default: fn(std::integral_constant<int, OTHER>{}); break;
     }
 }
 
+// Outside T field (icvCalcFMM with `negate`): a pop p (a seed of the initial band or a queue entry) gives every ring neighbour its T and
+// pushes it.  States are those of OpenCV's `out` mask: ring = INSIDE, hole and everything else KNOWN.
 // Up to FOUR pops of the outside pass at once.  A pop of this pass only uses 16 lanes (4 neighbours x 4 quadrants), so lane
 // group g = lane >> 4 takes the g-th of the next entries IN QUEUE ORDER, as long as the one-at-a-time loop would have popped
 // exactly these entries one after the other with the same data:
@@ -324,12 +490,9 @@ __device__ __attribute__((always_inline)) inline void telea_pop_outside(const Te
 //    entry first; T_new == T_member keeps the member first, FIFO): the batch is cut there before anything is written.
 // Pushes go group by group, neighbour by neighbour -- the push order of the sequential loop -- so the queue contents, the FIFO
 // order among equal T and every later pop are those of the sequential march: results are bit-identical.
-// `cells` = the candidate cells (wave-uniform), n = how many are valid; returns the longest admissible prefix by distance.
-__device__ inline int telea_outside_prefix(const int (&cells)[4], int n, int ww, uint32_t magic_ww)
+// the longest prefix of n <= 4 candidates at (r, c) in which every pair is at Manhattan distance >= 4
+__host__ __device__ inline int telea_prefix_by_distance(const int (&r)[4], const int (&c)[4], int n)
 {
-    int r[4], c[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) { r[i] = (int)__umulhi((uint32_t)cells[i], magic_ww); c[i] = cells[i] - r[i] * ww; }
     int m = 1;
 #pragma unroll
     for (int j = 1; j < 4; j++) {
@@ -339,6 +502,15 @@ __device__ inline int telea_outside_prefix(const int (&cells)[4], int n, int ww,
         if (m == j && j < n && !clash) m = j + 1;
     }
     return m;
+}
+// `cells` = the candidate cells (wave-uniform), n = how many are valid; returns the longest admissible prefix by distance.  magic_ww == 0
+// (telea_magic_plane: no exact row / column split on this plane): 1, one pop per step
+__host__ __device__ inline int telea_outside_prefix(const int (&cells)[4], int n, int ww, uint32_t magic_ww)
+{
+    int r[4], c[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) { r[i] = (int)(((unsigned long long)(uint32_t)cells[i] * magic_ww) >> 32); c[i] = cells[i] - r[i] * ww; }     // multiply-high
+    return magic_ww ? telea_prefix_by_distance(r, c, n) : 1;
 }
 // Where the FMM pass keeps its states: OpenCV's `out` flags in the window's flag bytes (outside pass: ring = INSIDE, hole and everything
 // else KNOWN).  (A policy rather than plain code so that the pass reads the same whichever plane holds the states.)
@@ -372,8 +544,7 @@ __device__ __attribute__((always_inline)) inline int telea_pop_outside4(State &s
             const bool k1 = !st.inside(p1), k2 = !st.inside(p2);           // p itself may be among them: BAND now, CHANGE after the pop -- not INSIDE either way
             dist = wn_solve(a11, a22, k1, k2);
         }
-        float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0xB1, 0xf, 0xf, false)); dist = o < dist ? o : dist;
-        o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(dist), 0x4E, 0xf, 0xf, false)); dist = o < dist ? o : dist;
+        dist = quad_min(dist);
         if (m > 1) {
             // smallest T pushed by each group (row = 16 lanes = one group); T >= 0, so the float bits order like the values
             uint32_t gm = ok ? __float_as_uint(dist) : 0x7f800000u, og;
@@ -470,15 +641,14 @@ __device__ __attribute__((always_inline)) inline void telea_fmm_queue(State &st,
         ns++;
     }
 }
-// cell / ww == umulhi(cell, magic) for every cell with cell * ww < 2^32
-__host__ __device__ inline uint32_t telea_magic_ww(int ww) { return (uint32_t)(0x100000000ull / (unsigned)ww) + 1u; }
-
+// a whole pass over a window of `cells` cells (an LDS window: far below the magic's limit)
 template <class State>
 __device__ __attribute__((always_inline)) inline void telea_fmm_pass(State &st, WQ &q, const uint8_t *f, int cells, int ww, int lane,
                                                                      unsigned long long &np, unsigned long long &ns)
 {
     const TeleaOutsideConsts oc = telea_outside_consts(lane, ww);
     const uint32_t magic_ww = telea_magic_ww(ww);
+    __builtin_assume(magic_ww != 0u);
     for (int base = 0; base < cells && !q.ovf; base += 64) {
         const int li = base + lane;
         telea_fmm_seed_chunk(st, q, oc, base, __ballot(li < cells && (f[li] & W_SEED)), ww, magic_ww, lane, np, ns);
@@ -486,14 +656,80 @@ __device__ __attribute__((always_inline)) inline void telea_fmm_pass(State &st, 
     telea_fmm_queue(st, q, oc, ww, magic_ww, lane, np, ns);
 }
 
+// cycle sums of the fill's phases (frame 0 only): diagnostics of builds with -DVISTAF_DEBUG.  FSTART() starts a clock `fclk` that the fill
+// block takes along; a fill that is not timed (the 16-wave kernel's) hands in a stopped one
 #ifdef VISTAF_DEBUG
-__device__ unsigned long long g_fill_dbg[8];          // cycle sums of the fill's phases (frame 0 only): diagnostics
-#define FSTAMP(k) do { if (blockIdx.x == 0 && lane == 0) { unsigned long long t_ = __builtin_amdgcn_s_memtime(); g_fill_dbg[k] += t_ - fstamp_; fstamp_ = t_; } } while (0)
-#define FSTART() unsigned long long fstamp_ = __builtin_amdgcn_s_memtime()
+__device__ unsigned long long g_fill_dbg[8];
+struct FillClock {
+    unsigned long long t;
+    bool on;
+    __device__ explicit FillClock(bool on_) : t(__builtin_amdgcn_s_memtime()), on(on_) {}
+    __device__ __attribute__((always_inline)) void stamp(int k, int lane)
+    {
+        if (on && blockIdx.x == 0 && lane == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); g_fill_dbg[k] += t_ - t; t = t_; }
+    }
+};
 #else
-#define FSTAMP(k) do { } while (0)
-#define FSTART() do { } while (0)
+struct FillClock {
+    __device__ explicit FillClock(bool) {}
+    __device__ __attribute__((always_inline)) void stamp(int, int) {}
+};
 #endif
+#define FSTART() FillClock fclk(true)
+#define FSTAMP(k) fclk.stamp(k, lane)
+
+// The image values of window position pk with OpenCV's index shifts at the first / last image row / column (km, kp, lm, lp; all 0 away
+// from the image border); sk / sK / sl / sL = 1 where the neighbour above / below / left / right is a BORDER cell (bit 4 of its flag byte):
+// vC the position's own value, vA / vB right / left, vE / vF below / above, vD / vG where the backward differences start (vC unless shifted)
+struct TeleaImg { float vC, vA, vB, vD, vE, vF, vG; };
+__device__ __attribute__((always_inline)) inline TeleaImg telea_img_taps(const float *im, int pk, int ww, int sk, int sK, int sl, int sL)
+{
+    const int rowm = pk + (sk ? ww : 0);
+    TeleaImg v;
+    v.vC = im[rowm + sl]; v.vA = im[rowm + 1 - sL]; v.vB = im[rowm + sl - 1]; v.vD = im[rowm - sL];
+    v.vE = im[pk + (sK ? 0 : ww) + sl]; v.vF = im[rowm - ww + sl]; v.vG = im[pk - (sK ? ww : 0) + sl];
+    return v;
+}
+
+// THE straight-line fill block: the estimate of pixel pi when the disc has NS <= 64 positions, one per lane.  ONE basic block: on a lone
+// wave a taken branch costs tens of cycles and a dependent instruction ~9, so every LDS read is issued up front (the T word read at pi
+// itself may be stale, but pi is INSIDE and never enters the sums), every condition is a per-lane select with all alternatives evaluated,
+// and whatever centre() computes (the march: the quadrant solve, an f64 chain) overlaps the image-gradient terms.  Lanes that are off read,
+// unused, around pi itself.
+// centre(tu, tl, td, tr, ku, kl, kd, kr) returns the pixel's own T from T of its up / left / down / right neighbours and whether each is
+// not INSIDE (per-lane values: as scalar conditions every select would become a branch); the block returns the estimate and leaves T in tc.
+template <int NS, class Centre>
+__device__ __attribute__((always_inline)) inline float telea_fill_block(const TeleaWin &win, const TeleaMarchConsts &mc, int pi, int lane, FillClock &fclk,
+                                                                        float &tc, Centre centre)
+{
+    static_assert(NS > 0 && NS <= 64, "one estimator chunk");
+    const float *t = win.t, *im = win.im;
+    const uint8_t *f = win.f;
+    const int ww = win.ww;
+    const uint8_t f4 = f[pi + mc.d4];
+    const float t4 = t[pi + mc.d4];
+    const int pk = pi + mc.off[0];
+    const uint8_t f0 = f[pk], fr = f[pk + 1], fl = f[pk - 1], fd = f[pk + ww], fu = f[pk - ww];
+    const float tk = t[pk];
+    const int sk = (fu >> 4) & 1, sK = (fd >> 4) & 1, sl = (fl >> 4) & 1, sL = (fr >> 4) & 1;
+    const TeleaImg v = telea_img_taps(im, pk, ww, sk, sK, sl, sL);
+    const float tu = wn_lane_f(t4, 0), tl = wn_lane_f(t4, 1), td = wn_lane_f(t4, 2), tr = wn_lane_f(t4, 3);
+    unsigned kv = (unsigned)__ballot((f4 & W_ST) != W_INSIDE) & 0xf;
+    asm volatile("" : "+v"(kv));
+    const bool ku = kv & 1, kl = kv & 2, kd = kv & 4, kr = kv & 8;
+    tc = centre(tu, tl, td, tr, ku, kl, kd, kr);
+    FSTAMP(0);                     // LDS reads + the centre's T
+    const float gtx = telea_grad_T(kr, kl, tr, tl, tc), gty = telea_grad_T(kd, ku, td, tu, tc);
+    const float rx = mc.rx[0], ry = mc.ry[0];
+    const bool use = (int)mc.on[0] & (int)((f0 & W_BORDER) == 0) & (int)((f0 & W_ST) != W_INSIDE);
+    const float wgt = telea_weight(mc.dstw[0], telea_lev(tk, tc), telea_dir(rx, ry, gtx, gty));
+    const bool nr = (fr & W_ST) != W_INSIDE, nl = (fl & W_ST) != W_INSIDE, nd = (fd & W_ST) != W_INSIDE, nu = (fu & W_ST) != W_INSIDE;
+    TeleaTerms s = telea_terms(use, wgt, v.vC, telea_grad_I(nr, nl, v.vA, v.vB, v.vC, v.vD), telea_grad_I(nd, nu, v.vE, v.vF, v.vC, v.vG), rx, ry);
+    FSTAMP(1);                     // weights and terms
+    wn_seq_sum4<NS>(s.Ia, s.Jx, s.Jy, s.s, 1.0e-20f, lane);        // s starts at 1e-20f
+    FSTAMP(2);                     // ordered sums
+    return telea_estimate(s.Ia, s.Jx, s.Jy, s.s);
+}
 
 // Telea march (icvTeleaInpaintFMM): pop p, fill every 4-neighbour that is still INSIDE and push it.  Returns the number of
 // pixels filled.
@@ -506,9 +742,6 @@ __device__ __attribute__((always_inline)) inline int telea_pop_march(const Telea
     float *t = win.t, *im = win.im;
     uint8_t *f = win.f;
     const int ww = win.ww, d4 = mc.d4, range = mc.range, nn = mc.nn, side = mc.side, r2 = mc.r2;
-    const int *h_off = mc.off;
-    const float *h_rx = mc.rx, *h_ry = mc.ry, *h_dstw = mc.dstw;
-    const bool *h_on = mc.on;
     int nfill = 0;
     if (from_queue && lane == 0) f[p] = (uint8_t)(W_HOLE | W_KNOWN);
     // the four 4-neighbours, one per lane: still INSIDE?  (a neighbour's fill never changes another's flag)
@@ -518,62 +751,17 @@ __device__ __attribute__((always_inline)) inline int telea_pop_march(const Telea
         todo &= todo - 1;
         const int pi = p + (qn == 0 ? -ww : qn == 1 ? -1 : qn == 2 ? ww : 1);
         nfill++;
+        // T of pi: the minimum over the quadrants (i-1,j-1) (i+1,j-1) (i-1,j+1) (i+1,j+1), one per lane of a quad
+        auto solve = [&](float tu, float tl, float td, float tr, bool ku, bool kl, bool kd, bool kr) -> float {
+            const int qd = lane & 3;
+            const float T = wn_lane_f(quad_min(wn_solve((qd & 1) ? td : tu, (qd & 2) ? tr : tl, (qd & 1) ? kd : ku, (qd & 2) ? kr : kl)), 0);
+            if (lane == 0) t[pi] = T;
+            return T;
+        };
         if constexpr (NS > 0) {
             FSTART();
-            // One estimator chunk (disc <= 64 positions), written as ONE basic block: on a lone wave a taken branch costs tens of cycles and a
-            // dependent instruction ~9, so every LDS read is issued up front (the T word read at pi itself is the stale one, but
-            // pi is INSIDE and never enters the sums), every condition is a per-lane select, and the quadrant solve (an f64 chain)
-            // overlaps the image-gradient terms of the estimator.  Lanes that are off read, unused, around pi itself.
-            const uint8_t f4 = f[pi + d4];
-            const float t4 = t[pi + d4];
-            const int pk = pi + h_off[0];
-            const uint8_t f0 = f[pk], fr = f[pk + 1], fl = f[pk - 1], fd = f[pk + ww], fu = f[pk - ww];
-            const float tk = t[pk];
-            // OpenCV's index shifts at the first / last image row / column (km, kp, lm, lp): all 0 away from the image border
-            const int sk = (fu >> 4) & 1, sK = (fd >> 4) & 1, sl = (fl >> 4) & 1, sL = (fr >> 4) & 1;
-            const int rowm = pk + (sk ? ww : 0);
-            const float vC = im[rowm + sl], vA = im[rowm + 1 - sL], vB = im[rowm + sl - 1], vD = im[rowm - sL];
-            const float vE = im[pk + (sK ? 0 : ww) + sl], vF = im[rowm - ww + sl], vG = im[pk - (sK ? ww : 0) + sl];
-            const float tu = wn_lane_f(t4, 0), tl = wn_lane_f(t4, 1), td = wn_lane_f(t4, 2), tr = wn_lane_f(t4, 3);
-            // the neighbour states are wave-uniform; as scalar conditions every select below would become a branch, so they are
-            // handed to the compiler as per-lane values
-            unsigned kv = (unsigned)__ballot((f4 & W_ST) != W_INSIDE) & 0xf;
-            asm volatile("" : "+v"(kv));
-            const bool ku = kv & 1, kl = kv & 2, kd = kv & 4, kr = kv & 8;
-            const int qd = lane & 3;
-            float sq = wn_solve((qd & 1) ? td : tu, (qd & 2) ? tr : tl, (qd & 1) ? kd : ku, (qd & 2) ? kr : kl);
-            float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sq), 0xB1, 0xf, 0xf, false)); sq = o < sq ? o : sq;
-            o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(sq), 0x4E, 0xf, 0xf, false)); sq = o < sq ? o : sq;
-            const float tc = wn_lane_f(sq, 0);
-            FSTAMP(0);                     // LDS reads + quadrant solve
-            if (lane == 0) t[pi] = tc;
-            // (all alternatives are evaluated, then selected: nested conditional expressions would come back as branches)
-            const float gx2 = __fmul_rn(__fsub_rn(tr, tl), 0.5f), gxr = __fsub_rn(tr, tc), gxl = __fsub_rn(tc, tl);
-            const float gy2 = __fmul_rn(__fsub_rn(td, tu), 0.5f), gyd = __fsub_rn(td, tc), gyu = __fsub_rn(tc, tu);
-            const float gtx_r = kl ? gx2 : gxr, gtx_n = kl ? gxl : 0.f, gtx = kr ? gtx_r : gtx_n;
-            const float gty_d = ku ? gy2 : gyd, gty_n = ku ? gyu : 0.f, gty = kd ? gty_d : gty_n;
-            const float rx = h_rx[0], ry = h_ry[0];
-            const bool use = (int)h_on[0] & (int)((f0 & W_BORDER) == 0) & (int)((f0 & W_ST) != W_INSIDE);
-            const float lev = telea_lev(tk, tc);
-            float dir = __fadd_rn(__fmul_rn(rx, gtx), __fmul_rn(ry, gty));
-            dir = fabsf(dir) <= 0.01f ? 0.000001f : dir;          // float(0.01) < 0.01: same set of floats as the double compare
-            const float wgt = fabsf(__fmul_rn(__fmul_rn(h_dstw[0], lev), dir));
-            const bool nr = (fr & W_ST) != W_INSIDE, nl = (fl & W_ST) != W_INSIDE, nd = (fd & W_ST) != W_INSIDE, nu = (fu & W_ST) != W_INSIDE;
-            const float ix2 = __fmul_rn(__fsub_rn(vA, vB), 2.0f), ixr = __fsub_rn(vA, vC), ixl = __fsub_rn(vD, vB);
-            const float iy2 = __fmul_rn(__fsub_rn(vE, vF), 2.0f), iyd = __fsub_rn(vE, vC), iyu = __fsub_rn(vG, vF);
-            const float gix_r = nl ? ix2 : ixr, gix_n = nl ? ixl : 0.f, gix = nr ? gix_r : gix_n;
-            const float giy_d = nu ? iy2 : iyd, giy_n = nu ? iyu : 0.f, giy = nd ? giy_d : giy_n;
-            // terms of Ia += w * I, Jx -= w * (gix * rx), Jy -= w * (giy * ry), s += w (s starts at 1e-20f); a skipped position adds 0
-            const float z = 0.f;
-            const float aIa = use ? __fmul_rn(wgt, vC) : z;
-            const float aJx = use ? -__fmul_rn(wgt, __fmul_rn(gix, rx)) : z;
-            const float aJy = use ? -__fmul_rn(wgt, __fmul_rn(giy, ry)) : z;
-            const float aS = use ? wgt : z;
-            float Ia = aIa, Jx = aJx, Jy = aJy, s = aS;
-            FSTAMP(1);                     // weights and terms
-            wn_seq_sum4<NS>(Ia, Jx, Jy, s, 1.0e-20f, lane);
-            FSTAMP(2);                     // ordered sums
-            const float val = telea_estimate(Ia, Jx, Jy, s);
+            float tc;
+            const float val = telea_fill_block<NS>(win, mc, pi, lane, fclk, tc, solve);
             if (lane == 0) { im[pi] = val; f[pi] = (uint8_t)(W_HOLE | W_BAND); }
             FSTAMP(3);                     // final estimate + stores
             push(tc, pi);
@@ -583,133 +771,65 @@ __device__ __attribute__((always_inline)) inline int telea_pop_march(const Telea
         // (flag, T) of pi's up / left / down / right neighbours on lanes 0..3, shared by all lanes
         const uint8_t f4 = f[pi + d4];
         const float t4 = t[pi + d4];
-        const bool k4 = (f4 & W_ST) != W_INSIDE;
         const float tu = wn_lane_f(t4, 0), tl = wn_lane_f(t4, 1), td = wn_lane_f(t4, 2), tr = wn_lane_f(t4, 3);
-        const unsigned kk = (unsigned)__ballot(k4) & 0xf;
+        const unsigned kk = (unsigned)__ballot((f4 & W_ST) != W_INSIDE) & 0xf;
         const bool ku = kk & 1, kl = kk & 2, kd = kk & 4, kr = kk & 8;
-        float dist;
-        {
-            const int qd = lane & 3;      // quadrants (i-1,j-1) (i+1,j-1) (i-1,j+1) (i+1,j+1)
-            float s = wn_solve((qd & 1) ? td : tu, (qd & 2) ? tr : tl, (qd & 1) ? kd : ku, (qd & 2) ? kr : kl);
-            float o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0xB1, 0xf, 0xf, false)); s = o < s ? o : s;
-            o = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), 0x4E, 0xf, 0xf, false)); s = o < s ? o : s;
-            dist = wn_lane_f(s, 0);
-        }
-        if (lane == 0) t[pi] = dist;
+        const float tc = solve(tu, tl, td, tr, ku, kl, kd, kr);
         __builtin_amdgcn_wave_barrier();
-        const float tc = dist;
-        float gtx, gty;
-        if (kr) gtx = kl ? __fmul_rn(__fsub_rn(tr, tl), 0.5f) : __fsub_rn(tr, tc);
-        else gtx = kl ? __fsub_rn(tc, tl) : 0.f;
-        if (kd) gty = ku ? __fmul_rn(__fsub_rn(td, tu), 0.5f) : __fsub_rn(td, tc);
-        else gty = ku ? __fsub_rn(tc, tu) : 0.f;
+        const float gtx = telea_grad_T(kr, kl, tr, tl, tc), gty = telea_grad_T(kd, ku, td, tu, tc);
         float Ia = 0.f, Jx = 0.f, Jy = 0.f, s = 1.0e-20f;       // running sums in OpenCV's order: chunk after chunk, lane after lane
         for (int n0 = 0; n0 < nn; n0 += 64) {
-            float aIa = 0.f, aJx = 0.f, aJy = 0.f, aS = 0.f;
+            TeleaTerms a = {0.f, 0.f, 0.f, 0.f};
             int off;
             float dstw, rx, ry;
             bool on;
-            if (n0 < 128) { int c2 = n0 >> 6; off = h_off[c2]; dstw = h_dstw[c2]; on = h_on[c2]; rx = h_rx[c2]; ry = h_ry[c2]; }
+            if (n0 < 128) { int c2 = n0 >> 6; off = mc.off[c2]; dstw = mc.dstw[c2]; on = mc.on[c2]; rx = mc.rx[c2]; ry = mc.ry[c2]; }
             else {
                 int nidx = n0 + lane;
                 int dk = nidx / side - range, dl = nidx % side - range;
                 off = dk * ww + dl;
                 on = nidx < nn && (dl * dl + dk * dk <= r2);
                 ry = (float)(-dk); rx = (float)(-dl);
-                float len2 = __fadd_rn(__fmul_rn(rx, rx), __fmul_rn(ry, ry));
-                dstw = len2 > 0.f ? (float)(1. / (double)__fmul_rn(len2, sqrtf(len2))) : 0.f;
+                dstw = telea_dstw(rx, ry);
             }
             if (on) {
                 const int pk = pi + off;                      // inside the window: margin range+1
                 const uint8_t f0 = f[pk], fr = f[pk + 1], fl = f[pk - 1], fd = f[pk + ww], fu = f[pk - ww];
                 const float tk = t[pk];
-                float vC = im[pk], vA = im[pk + 1], vB = im[pk - 1], vE = im[pk + ww], vF = im[pk - ww];
+                TeleaImg v;
+                v.vC = im[pk]; v.vA = im[pk + 1]; v.vB = im[pk - 1]; v.vE = im[pk + ww]; v.vF = im[pk - ww];
                 if (!(f0 & W_BORDER) && (f0 & W_ST) != W_INSIDE) {
-                    float vD = vC, vG = vC;
-                    if ((fr | fl | fd | fu) & W_BORDER) {
-                        // OpenCV's index shifts at the first / last image row / column (km, kp, lm, lp)
-                        const int sk = (fu & W_BORDER) ? 1 : 0, sK = (fd & W_BORDER) ? 1 : 0;
-                        const int sl = (fl & W_BORDER) ? 1 : 0, sL = (fr & W_BORDER) ? 1 : 0;
-                        const int rowm = pk + sk * ww;
-                        vC = im[rowm + sl]; vA = im[rowm + 1 - sL]; vB = im[rowm + sl - 1]; vD = im[rowm - sL];
-                        vE = im[pk + (1 - sK) * ww + sl]; vF = im[rowm - ww + sl]; vG = im[pk - sK * ww + sl];
-                    }
-                    float lev = telea_lev(tk, tc);
-                    float dir = __fadd_rn(__fmul_rn(rx, gtx), __fmul_rn(ry, gty));
-                    if (fabsf(dir) <= 0.01f) dir = 0.000001f;   // float(0.01) < 0.01: same set of floats as the double compare
-                    float wgt = fabsf(__fmul_rn(__fmul_rn(dstw, lev), dir));
+                    v.vD = v.vC; v.vG = v.vC;
+                    if ((fr | fl | fd | fu) & W_BORDER)
+                        v = telea_img_taps(im, pk, ww, (fu >> 4) & 1, (fd >> 4) & 1, (fl >> 4) & 1, (fr >> 4) & 1);      // shifted at the image border: read again
+                    const float wgt = telea_weight(dstw, telea_lev(tk, tc), telea_dir(rx, ry, gtx, gty));
                     const bool nr = (fr & W_ST) != W_INSIDE, nl = (fl & W_ST) != W_INSIDE, nd = (fd & W_ST) != W_INSIDE, nu = (fu & W_ST) != W_INSIDE;
-                    float gix, giy;
-                    if (nr) gix = nl ? __fmul_rn(__fsub_rn(vA, vB), 2.0f) : __fsub_rn(vA, vC);
-                    else gix = nl ? __fsub_rn(vD, vB) : 0.f;
-                    if (nd) giy = nu ? __fmul_rn(__fsub_rn(vE, vF), 2.0f) : __fsub_rn(vE, vC);
-                    else giy = nu ? __fsub_rn(vG, vF) : 0.f;
-                    aIa = __fmul_rn(wgt, vC);
-                    aJx = -__fmul_rn(wgt, __fmul_rn(gix, rx));
-                    aJy = -__fmul_rn(wgt, __fmul_rn(giy, ry));
-                    aS = wgt;
+                    a = telea_terms(true, wgt, v.vC, telea_grad_I(nr, nl, v.vA, v.vB, v.vC, v.vD), telea_grad_I(nd, nu, v.vE, v.vF, v.vC, v.vG), rx, ry);
                 }
             }
             const int nl = nn - n0 < 64 ? nn - n0 : 64;
-            Ia = wn_seq_sum_n(aIa, Ia, nl, lane); Jx = wn_seq_sum_n(aJx, Jx, nl, lane); Jy = wn_seq_sum_n(aJy, Jy, nl, lane); s = wn_seq_sum_n(aS, s, nl, lane);
+            Ia = wn_seq_sum_n(a.Ia, Ia, nl, lane); Jx = wn_seq_sum_n(a.Jx, Jx, nl, lane); Jy = wn_seq_sum_n(a.Jy, Jy, nl, lane); s = wn_seq_sum_n(a.s, s, nl, lane);
         }
         const float val = telea_estimate(Ia, Jx, Jy, s);
         if (lane == 0) { im[pi] = val; f[pi] = (uint8_t)(W_HOLE | W_BAND); }
-        push(dist, pi);
+        push(tc, pi);
     }
     return nfill;
 }
 
 // The estimate of ONE hole pixel pi whose T the ordering pass (k_inpaint_mw.hip) has already fixed: the fill block of telea_pop_march without
-// the quadrant solve and the push, same operations in the same order (so the value carries the same bits).  The caller guarantees that
+// the quadrant solve and the push (so the value carries the same bits).  The caller guarantees that
 // every fill within Chebyshev distance range + 1 of pi runs in march order (the block reads flags, T and image values that far out):
 // then "flag != INSIDE" in the live flag bytes is exactly the flag history cv::inpaint's march would have seen at this fill.
 // (T of cells that are still INSIDE already holds its final value instead of 1e6; every use of it is masked by the cell's flag.)
 template <int NS>
 __device__ __attribute__((always_inline)) inline void telea_fill_known_T(const TeleaWin &win, const TeleaMarchConsts &mc, int pi, int lane)
 {
-    static_assert(NS > 0 && NS <= 64, "one estimator chunk");
-    float *t = win.t, *im = win.im;
-    uint8_t *f = win.f;
-    const int ww = win.ww, d4 = mc.d4;
-    const uint8_t f4 = f[pi + d4];
-    const float t4 = t[pi + d4];
-    const float tcl = t[pi];
-    const int pk = pi + mc.off[0];
-    const uint8_t f0 = f[pk], fr = f[pk + 1], fl = f[pk - 1], fd = f[pk + ww], fu = f[pk - ww];
-    const float tk = t[pk];
-    const int sk = (fu >> 4) & 1, sK = (fd >> 4) & 1, sl = (fl >> 4) & 1, sL = (fr >> 4) & 1;
-    const int rowm = pk + (sk ? ww : 0);
-    const float vC = im[rowm + sl], vA = im[rowm + 1 - sL], vB = im[rowm + sl - 1], vD = im[rowm - sL];
-    const float vE = im[pk + (sK ? 0 : ww) + sl], vF = im[rowm - ww + sl], vG = im[pk - (sK ? ww : 0) + sl];
-    const float tu = wn_lane_f(t4, 0), tl = wn_lane_f(t4, 1), td = wn_lane_f(t4, 2), tr = wn_lane_f(t4, 3);
-    const float tc = wn_lane_f(tcl, 0);
-    unsigned kv = (unsigned)__ballot((f4 & W_ST) != W_INSIDE) & 0xf;
-    asm volatile("" : "+v"(kv));
-    const bool ku = kv & 1, kl = kv & 2, kd = kv & 4, kr = kv & 8;
-    const float gx2 = __fmul_rn(__fsub_rn(tr, tl), 0.5f), gxr = __fsub_rn(tr, tc), gxl = __fsub_rn(tc, tl);
-    const float gy2 = __fmul_rn(__fsub_rn(td, tu), 0.5f), gyd = __fsub_rn(td, tc), gyu = __fsub_rn(tc, tu);
-    const float gtx_r = kl ? gx2 : gxr, gtx_n = kl ? gxl : 0.f, gtx = kr ? gtx_r : gtx_n;
-    const float gty_d = ku ? gy2 : gyd, gty_n = ku ? gyu : 0.f, gty = kd ? gty_d : gty_n;
-    const float rx = mc.rx[0], ry = mc.ry[0];
-    const bool use = (int)mc.on[0] & (int)((f0 & W_BORDER) == 0) & (int)((f0 & W_ST) != W_INSIDE);
-    const float lev = telea_lev(tk, tc);
-    float dir = __fadd_rn(__fmul_rn(rx, gtx), __fmul_rn(ry, gty));
-    dir = fabsf(dir) <= 0.01f ? 0.000001f : dir;
-    const float wgt = fabsf(__fmul_rn(__fmul_rn(mc.dstw[0], lev), dir));
-    const bool nr = (fr & W_ST) != W_INSIDE, nl = (fl & W_ST) != W_INSIDE, nd = (fd & W_ST) != W_INSIDE, nu = (fu & W_ST) != W_INSIDE;
-    const float ix2 = __fmul_rn(__fsub_rn(vA, vB), 2.0f), ixr = __fsub_rn(vA, vC), ixl = __fsub_rn(vD, vB);
-    const float iy2 = __fmul_rn(__fsub_rn(vE, vF), 2.0f), iyd = __fsub_rn(vE, vC), iyu = __fsub_rn(vG, vF);
-    const float gix_r = nl ? ix2 : ixr, gix_n = nl ? ixl : 0.f, gix = nr ? gix_r : gix_n;
-    const float giy_d = nu ? iy2 : iyd, giy_n = nu ? iyu : 0.f, giy = nd ? giy_d : giy_n;
-    const float z = 0.f;
-    float Ia = use ? __fmul_rn(wgt, vC) : z;
-    float Jx = use ? -__fmul_rn(wgt, __fmul_rn(gix, rx)) : z;
-    float Jy = use ? -__fmul_rn(wgt, __fmul_rn(giy, ry)) : z;
-    float s = use ? wgt : z;
-    wn_seq_sum4<NS>(Ia, Jx, Jy, s, 1.0e-20f, lane);
-    const float val = telea_estimate(Ia, Jx, Jy, s);
-    if (lane == 0) { im[pi] = val; f[pi] = (uint8_t)(W_HOLE | W_BAND); }
+    const float tcl = win.t[pi];
+    FillClock fclk(false);
+    float tc;
+    const float val = telea_fill_block<NS>(win, mc, pi, lane, fclk, tc, [&](float, float, float, float, bool, bool, bool, bool) { return wn_lane_f(tcl, 0); });
+    if (lane == 0) { win.im[pi] = val; win.f[pi] = (uint8_t)(W_HOLE | W_BAND); }
 }
 
 }  // namespace vf
