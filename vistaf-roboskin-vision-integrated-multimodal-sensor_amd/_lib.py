@@ -170,6 +170,12 @@ SIGNATURES = {
         "vistaf_ftp_test_unwrap": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_inpaint": (ci, [vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_dft_full_mag": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_top_peaks": (ci, [vp, ci, ci, ci, ci, ci, vp, vp]),
+        "vistaf_ftp_test_carrier_choose": (ci, [vp, ci, vp, ci, ci, ci, cd, vp, vp, ci, vp]),
+        "vistaf_ftp_test_build_tables": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp]),
+        "vistaf_ftp_test_build_full_tables": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_dft_forward": (ci, [vp, vp, vp, vp, sz, sz, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_dft_inverse": (ci, [vp, ci, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
     },
     "TEMP_EXPORTS": {        # include/vistaf_temp.h
         "vistaf_tempseg_default_config": (ci, [P(CTempSegConfig)]),

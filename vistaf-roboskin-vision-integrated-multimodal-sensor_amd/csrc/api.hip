@@ -1120,6 +1120,146 @@ int vistaf_ftp_test_dft_full_mag(const float *planes, const void *Ex_half, const
     return launch_ok("launch_dft_full_mag");
 }
 
+// ---- the demodulation launchers (k_dft.hip, k_dft_tables.hip) on caller-supplied device planes and tables
+namespace {
+// CarrierGeom <-> the two caller arrays of the hooks, in struct order: gd[7] = peak_x, peak_y, kx, ky, dpx, dpy, period;
+// gi[10] = x0, y0, ph, pw, px_i, py_i, px_raw, py_raw, ok, keep_carrier
+CarrierGeom geom_pack(const double *gd, const int32_t *gi)
+{
+    CarrierGeom g;
+    g.peak_x = gd[0]; g.peak_y = gd[1]; g.kx = gd[2]; g.ky = gd[3]; g.dpx = gd[4]; g.dpy = gd[5]; g.period = gd[6];
+    g.x0 = gi[0]; g.y0 = gi[1]; g.ph = gi[2]; g.pw = gi[3]; g.px_i = gi[4]; g.py_i = gi[5]; g.px_raw = gi[6]; g.py_raw = gi[7];
+    g.ok = gi[8]; g.keep_carrier = gi[9];
+    return g;
+}
+void geom_unpack(const CarrierGeom &g, double *gd, int32_t *gi)
+{
+    gd[0] = g.peak_x; gd[1] = g.peak_y; gd[2] = g.kx; gd[3] = g.ky; gd[4] = g.dpx; gd[5] = g.dpy; gd[6] = g.period;
+    gi[0] = g.x0; gi[1] = g.y0; gi[2] = g.ph; gi[3] = g.pw; gi[4] = g.px_i; gi[5] = g.py_i; gi[6] = g.px_raw; gi[7] = g.py_raw;
+    gi[8] = g.ok; gi[9] = g.keep_carrier;
+}
+// the sizes every launcher of the family indexes with 32-bit integers, and the grid limits of a batch
+bool dft_sizes_ok(int B, int h, int w) { return B >= 1 && B <= 65535 && h >= 1 && w >= 1 && (size_t)B * h * w <= 0x7fffffffull; }
+bool padded_ok(int h, int w, int pad, int Hf, int Wf) { return pad >= 0 && pad <= (1 << 20) && Hf == h + 2 * pad && Wf == w + 2 * pad && (size_t)Hf * Wf <= 0x7fffffffull; }
+}  // namespace
+
+int vistaf_ftp_test_top_peaks(const double *mag, int B, int Hf, int Wf, int dc, int npeaks, double *out, void *stream)
+{
+    if (!mag || !out || !dft_sizes_ok(B, Hf, Wf) || dc < 0 || npeaks < 1 || npeaks > 64 || (size_t)Hf * Wf < (size_t)npeaks)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    launch_top_peaks(mag, B, Hf, Wf, dc, npeaks, out, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_carrier_choose(const double *peaks, int npk, const double *mag, int Hf, int Wf, int bw, double max_dy_frac, double *gd, int32_t *gi,
+                                   int B, void *stream)
+{
+    if (!peaks || !mag || !gd || !gi || !dft_sizes_ok(B, Hf, Wf) || npk < 1 || npk > 64 || bw < 0 || bw > (1 << 20) || !(max_dy_frac >= 0.0) ||
+        !(max_dy_frac <= 1e6))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    // the kernel reads the magnitude plane at the listed positions: a list that points outside the plane is refused, not launched
+    std::vector<double> pk((size_t)B * 192);
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpy(pk.data(), peaks, pk.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i < npk; i++) {
+            const double x = pk[(size_t)b * 192 + 3 * i], y = pk[(size_t)b * 192 + 3 * i + 1];
+            if (!(x >= 0.0 && x < (double)Wf && y >= 0.0 && y < (double)Hf)) return fail(VISTAF_E_INVALID, "a listed peak lies outside the plane");
+        }
+    CarrierGeom *geom = nullptr;
+    HIPCHK(hipMalloc((void **)&geom, (size_t)B * sizeof(CarrierGeom)));
+    launch_carrier_choose(peaks, npk, mag, Hf, Wf, bw, max_dy_frac, geom, B, st);
+    std::vector<CarrierGeom> g((size_t)B);
+    const hipError_t e0 = hipGetLastError();
+    const hipError_t e1 = e0 == hipSuccess ? hipMemcpyAsync(g.data(), geom, g.size() * sizeof(CarrierGeom), hipMemcpyDeviceToHost, st) : e0;
+    const int rc = hook_finish(geom, nullptr, st);
+    if (e1 != hipSuccess) return fail(VISTAF_E_HIP, std::string("launch_carrier_choose: ") + hipGetErrorString(e1));
+    if (rc) return rc;
+    for (int b = 0; b < B; b++) geom_unpack(g[b], gd + 7 * (size_t)b, gi + 10 * (size_t)b);
+    return 0;
+}
+
+int vistaf_ftp_test_build_tables(const double *gd, const int32_t *gi, int geom_stride, int B, int h, int w, int pad, int Hf, int Wf, int pmax, int pair,
+                                 void *Ex, void *Ey, void *Gx, void *Gy, float *win, void *stream)
+{
+    if (!gd || !gi || !Ex || !Ey || !Gx || !Gy || (pair && !win) || !dft_sizes_ok(B, h, w) || !padded_ok(h, w, pad, Hf, Wf) || pmax < 1 || pmax > 4096 ||
+        (geom_stride != 0 && geom_stride != 1) || (size_t)std::max(std::max(h, w), pmax) * pmax > 0x7fffffffull)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    const int ng = geom_stride ? B : 1;
+    std::vector<CarrierGeom> g((size_t)ng);
+    for (int b = 0; b < ng; b++) g[b] = geom_pack(gd + 7 * (size_t)b, gi + 10 * (size_t)b);
+    std::vector<float> tab;
+    if (pair) {                                             // as vistaf_ftp_predict_pairs builds hann_tab
+        tab.assign((size_t)(pmax + 1) * pmax, 0.0f);
+        for (int M = 1; M <= pmax; M++) {
+            const std::vector<float> row = hann_patch(1, M);
+            std::copy(row.begin(), row.end(), tab.begin() + (size_t)M * pmax);
+        }
+    }
+    CarrierGeom *geom = nullptr;
+    float *hann = nullptr;
+    HIPCHK(hipMalloc((void **)&geom, g.size() * sizeof(CarrierGeom)));
+    if (pair && hipMalloc((void **)&hann, tab.size() * sizeof(float)) != hipSuccess) { (void)hipFree(geom); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    if (hipMemcpy(geom, g.data(), g.size() * sizeof(CarrierGeom), hipMemcpyHostToDevice) != hipSuccess ||
+        (pair && hipMemcpy(hann, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)) {
+        (void)hipFree(geom); (void)hipFree(hann);
+        return fail(VISTAF_E_HIP, "memcpy geometry");
+    }
+    launch_build_tables(geom, geom_stride, (double2 *)Ex, (double2 *)Ey, (double2 *)Gx, (double2 *)Gy, (size_t)w * pmax, (size_t)h * pmax, B, h, w, pad, Hf,
+                        Wf, pmax, st, pair ? hann : nullptr, pair ? win : nullptr);
+    return hook_finish(geom, hann, st);
+}
+
+int vistaf_ftp_test_build_full_tables(void *Exf, void *Eyf, int h, int w, int pad, int Hf, int Wf, void *stream)
+{
+    if (!Exf || !Eyf || !dft_sizes_ok(1, h, w) || !padded_ok(h, w, pad, Hf, Wf)) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_build_full_tables((double2 *)Exf, (double2 *)Eyf, h, w, pad, Hf, Wf, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_dft_forward(const float *iw, const float *mu, const void *Ex, const void *Ey, size_t tab_stride_x, size_t tab_stride_y, const float *win,
+                                int win_stride, void *T, void *patch, int patch_stride, int B, int h, int w, int ph, int pw, void *stream)
+{
+    if (!iw || !Ex || !Ey || !win || !T || !patch || !dft_sizes_ok(B, h, w) || ph < 1 || pw < 1 || ph > 4096 || pw > 4096 ||
+        (size_t)B * h * pw > 0x7fffffffull)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if ((tab_stride_x == 0) != (tab_stride_y == 0) || (tab_stride_x && (tab_stride_x < (size_t)w * pw || tab_stride_y < (size_t)ph * h)) ||
+        (win_stride != 0 && win_stride < ph * pw) || patch_stride < ph * pw)
+        return fail(VISTAF_E_INVALID, "a stride is smaller than what it strides over, or only one table stride is zero");
+    launch_dft_forward(iw, mu, (const double2 *)Ex, (const double2 *)Ey, tab_stride_x, tab_stride_y, win, (double2 *)T, (double2 *)patch, patch_stride, B, h, w,
+                       ph, pw, (hipStream_t)stream, win_stride);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_dft_inverse(const void *patch, int patch_stride, const void *Gx, const void *Gy, size_t tab_stride_x, size_t tab_stride_y, void *Q, void *field,
+                                float *amp, const void *cref, const float *amp_ref, size_t ref_stride, float *prod, float *wrapped, const int32_t *gi_or_null,
+                                int B, int h, int w, int ph, int pw, void *stream)
+{
+    if (!patch || !Gx || !Gy || !Q || !amp || (cref && (!amp_ref || !prod || !wrapped)) || !dft_sizes_ok(B, h, w) || ph < 1 || pw < 1 || ph > 4096 ||
+        pw > 4096 || (size_t)B * ph * w > 0x7fffffffull)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if ((tab_stride_x == 0) != (tab_stride_y == 0) || (tab_stride_x && (tab_stride_x < (size_t)w * pw || tab_stride_y < (size_t)ph * h)) ||
+        patch_stride < ph * pw || (ref_stride != 0 && ref_stride < (size_t)h * w))
+        return fail(VISTAF_E_INVALID, "a stride is smaller than what it strides over, or only one table stride is zero");
+    hipStream_t st = (hipStream_t)stream;
+    CarrierGeom *geom = nullptr;
+    if (gi_or_null) {
+        const double zeros[7] = {0, 0, 0, 0, 0, 0, 0};
+        std::vector<CarrierGeom> g((size_t)B);
+        for (int b = 0; b < B; b++) g[b] = geom_pack(zeros, gi_or_null + 10 * (size_t)b);
+        HIPCHK(hipMalloc((void **)&geom, g.size() * sizeof(CarrierGeom)));
+        if (hipMemcpy(geom, g.data(), g.size() * sizeof(CarrierGeom), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(geom);
+            return fail(VISTAF_E_HIP, "memcpy geometry");
+        }
+    }
+    launch_dft_inverse((const double2 *)patch, patch_stride, (const double2 *)Gx, (const double2 *)Gy, tab_stride_x, tab_stride_y, (double2 *)Q, (double2 *)field, amp,
+                       (const double2 *)cref, amp_ref, ref_stride, prod, wrapped, B, h, w, ph, pw, st, geom);
+    return hook_finish(geom, nullptr, st);
+}
+
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,
                                double depth_eps_mm, double *d_out, void *stream)
 {

@@ -260,8 +260,9 @@ void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_hal
 // top-N magnitudes outside the DC box (find_top_peaks, shape_ftp.py:420-441), descending: out[b][3*i] = x, y, value.  One workgroup
 // per frame.  Magnitudes are non-negative doubles: their bit patterns order like the values.  ONE pass over the plane: every thread keeps
 // the TP_L largest of its strided elements (value bits, index) in registers; the N largest of the frame are then among the 1024 * TP_L
-// survivors unless one thread held more than TP_L of them -- detected (the thread's smallest kept value is then >= the N-th result) and
-// handled by the exact N-pass fallback.  Equal values: smaller linear index first.
+// survivors unless one thread held more than TP_L of them -- detected (the best element that thread discarded then comes before the N-th
+// result in the order below; a plane with fewer than N positive values included, where the N-th result is a zero) and handled by the exact
+// N-pass fallback.  Equal values: smaller linear index first.
 constexpr int TP_L = 4;
 __device__ inline bool tp_before(unsigned long long va, unsigned int ia, unsigned long long vb, unsigned int ib) { return va > vb || (va == vb && ia < ib); }
 
@@ -281,7 +282,7 @@ __global__ __launch_bounds__(1024) void k_top_peaks(const double *__restrict__ m
     if (npeaks > 64) npeaks = 64;
     // ---- per-thread top TP_L (sorted, best first); `dropped` = the best element this thread had to discard
     unsigned long long tv[TP_L], dropped_v = 0;
-    unsigned int ti[TP_L];
+    unsigned int ti[TP_L], dropped_i = 0xffffffffu;
     bool dropped = false;
 #pragma unroll
     for (int k = 0; k < TP_L; k++) { tv[k] = 0ull; ti[k] = 0xffffffffu; }
@@ -292,11 +293,14 @@ __global__ __launch_bounds__(1024) void k_top_peaks(const double *__restrict__ m
         unsigned long long cv = (unsigned long long)__double_as_longlong(v);
         unsigned int ci = (unsigned int)i;
         if (!tp_before(cv, ci, tv[TP_L - 1], ti[TP_L - 1])) {       // not better than the worst kept: discard
-            if (!dropped || cv > dropped_v) dropped_v = cv;
+            if (!dropped || tp_before(cv, ci, dropped_v, dropped_i)) { dropped_v = cv; dropped_i = ci; }
             dropped = true;
             continue;
         }
-        if (ti[TP_L - 1] != 0xffffffffu) { if (!dropped || tv[TP_L - 1] > dropped_v) dropped_v = tv[TP_L - 1]; dropped = true; }
+        if (ti[TP_L - 1] != 0xffffffffu) {
+            if (!dropped || tp_before(tv[TP_L - 1], ti[TP_L - 1], dropped_v, dropped_i)) { dropped_v = tv[TP_L - 1]; dropped_i = ti[TP_L - 1]; }
+            dropped = true;
+        }
 #pragma unroll
         for (int k = 0; k < TP_L; k++) {                            // sorted insertion
             if (tp_before(cv, ci, tv[k], ti[k])) { const unsigned long long xv = tv[k]; const unsigned int xi = ti[k]; tv[k] = cv; ti[k] = ci; cv = xv; ci = xi; }
@@ -308,6 +312,7 @@ __global__ __launch_bounds__(1024) void k_top_peaks(const double *__restrict__ m
     __syncthreads();
     // ---- N rounds of block-wide arg-max over the survivors
     unsigned long long last_v = 0;
+    unsigned int last_i = 0xffffffffu;
     for (int k = 0; k < npeaks; k++) {
         unsigned long long bv = 0;
         unsigned int bi = 0xffffffffu;
@@ -327,11 +332,12 @@ __global__ __launch_bounds__(1024) void k_top_peaks(const double *__restrict__ m
         }
         for (int j = tid; j < 1024 * TP_L; j += 1024)
             if (s_idx[j] == (unsigned int)mi) s_idx[j] = 0xffffffffu;
-        last_v = mv;
+        last_v = mv; last_i = (unsigned int)mi;
         __syncthreads();
     }
-    // a discarded element that would have made the list: redo exactly (never seen on spectra: the peaks are few and far apart)
-    if (dropped && dropped_v >= last_v && last_v > 0) s_overflow = 1;
+    // a discarded element that would have made the list: redo exactly (never seen on spectra: the peaks are few and far apart).  The test is
+    // the order itself, so an all-zero plane (every discarded zero lies behind the N-th index) stays on the one pass
+    if (dropped && tp_before(dropped_v, dropped_i, last_v, last_i)) s_overflow = 1;
     __syncthreads();
     if (!s_overflow) return;
     for (int k = 0; k < npeaks; k++) {

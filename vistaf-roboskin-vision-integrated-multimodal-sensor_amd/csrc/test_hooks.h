@@ -3,8 +3,10 @@
  * to read planes that the production path does not materialise.
  * Hooks: vistaf_ftp_test_set (tiers of a session); the production launchers on planes of the caller -- vistaf_ftp_test_select,
  * _select_instance, _select_chained, _polyfit, _gauss (selection, IRLS fit, blur), _chamfer, _cc_label, _cc_largest, _chamfer_dispatch,
- * _blob_filter (mask topology), _unwrap (phase unwrap), _inpaint (the Telea tiers); vistaf_ftp_test_scratch_regions (scratch layouts) and
- * vistaf_ftp_test_dft_full_mag (a timing aid). */
+ * _blob_filter (mask topology), _unwrap (phase unwrap), _inpaint (the Telea tiers), _top_peaks, _carrier_choose, _build_tables,
+ * _build_full_tables, _dft_forward, _dft_inverse (demodulation: peak search, carrier choice, twiddle tables, the float64 GEMM stages);
+ * vistaf_ftp_test_scratch_regions (scratch layouts) and vistaf_ftp_test_dft_full_mag (the full-spectrum magnitude, asynchronous: also a timing
+ * aid). */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
@@ -168,11 +170,54 @@ int vistaf_ftp_test_inpaint(float *img_inout, const uint8_t *bad, int range, int
 int vistaf_ftp_test_scratch_regions(const char *stage, int B, int h, int w, int range, int cap, char *names, size_t *offset, size_t *bytes, size_t *align,
                                     size_t *total);
 
-/* launch_dft_full_mag (the reference frame's full-spectrum magnitude, k_dft.hip) on planes and tables of the caller's, for the timing of
- * tests/diag/bench_pressure.py: planes [B,h,w] float32, Ex_half [w][Wf/2+1] and Ey_full [Hf][h] complex128, tmp [B*h][Wf/2+1] complex128,
+/* launch_dft_full_mag (the reference frame's full-spectrum magnitude, k_dft.hip) on planes and tables of the caller's, for the direct tests
+ * and the timing of tests/diag/bench_pressure.py: planes [B,h,w] float32, Ex_half [w][Wf/2+1] and Ey_full [Hf][h] complex128, tmp [B*h][Wf/2+1] complex128,
  * mag [B,Hf,Wf] float64, all on the device.  Asynchronous on `stream`. */
 int vistaf_ftp_test_dft_full_mag(const float *planes, const void *Ex_half, const void *Ey_full, void *tmp, double *mag, int B, int h, int w, int Hf,
                                  int Wf, void *stream);
+
+/* The demodulation launchers (k_dft.hip, k_dft_tables.hip) on device planes and tables of the caller's, so that a test chooses their contents.
+ * Every call refuses a NULL plane (the optional ones apart), a bad size and a stride smaller than what it strides over with VISTAF_E_INVALID
+ * before anything is allocated or launched, runs on `stream`, waits for it, and returns 0 or a negative VISTAF_E_* code.  complex128 planes
+ * and tables are arrays of (re, im) doubles.
+ * A CarrierGeom (kernels.hpp) crosses the boundary as two HOST arrays per frame, in struct order:
+ *   gd[7]  float64: peak_x, peak_y, kx, ky, dpx, dpy, period;   gi[10] int32: x0, y0, ph, pw, px_i, py_i, px_raw, py_raw, ok, keep_carrier. */
+
+/* launch_top_peaks: out[b][3 i .. 3 i + 2] = (x, y, value) of the i-th largest magnitude of mag[b] ([B, Hf, Wf] float64, non-negative) with the
+ * box [cy - dc, cy + dc) x [cx - dc, cx + dc) around the centre counted as zero; descending, equal values by ascending linear index.  out is
+ * [B][192]: entries from 3 * npeaks on are not written.  npeaks 1..64, Hf * Wf >= npeaks. */
+int vistaf_ftp_test_top_peaks(const double *mag, int B, int Hf, int Wf, int dc, int npeaks, double *out, void *stream);
+
+/* launch_carrier_choose on peak lists of the caller's (peaks [B][192] as above, the first npk entries of each, 1..64; integer positions inside the
+ * plane, or the call is refused) and the magnitude planes the refinement reads: choose_carrier_peak, refine_peak_parabolic_log and the patch
+ * geometry of half width bw, into gd [B][7] and gi [B][10] on the host. */
+int vistaf_ftp_test_carrier_choose(const double *peaks, int npk, const double *mag, int Hf, int Wf, int bw, double max_dy_frac, double *gd, int32_t *gi,
+                                   int B, void *stream);
+
+/* launch_build_tables from geometries of the caller's (gd / gi on the host: B of them for geom_stride 1, one for geom_stride 0), Hf = h + 2 pad,
+ * Wf = w + 2 pad.  Frame b's tables start at Ex / Gx + b * w * pmax and Ey / Gy + b * h * pmax elements.
+ * pair == 0: packed for the frame's own ph x pw (each clamped to pmax): Ex [w][pw], Ey [ph][h], Gx [pw][w], Gy [h][ph]; `win` is not touched.
+ * pair != 0: laid out for pmax x pmax with exact zeros beyond ph / pw, and win [B][pmax][pmax] receives hann(ph) x hann(pw) in float32 (zeros
+ * beyond), formed from the table of 1-D windows a pair session builds. */
+int vistaf_ftp_test_build_tables(const double *gd, const int32_t *gi, int geom_stride, int B, int h, int w, int pad, int Hf, int Wf, int pmax, int pair,
+                                 void *Ex, void *Ey, void *Gx, void *Gy, float *win, void *stream);
+
+/* launch_build_full_tables: Exf [w][Wf / 2 + 1], Eyf [Hf][h], the tables vistaf_ftp_test_dft_full_mag takes. */
+int vistaf_ftp_test_build_full_tables(void *Exf, void *Eyf, int h, int w, int pad, int Hf, int Wf, void *stream);
+
+/* launch_dft_forward: T [B * h][pw] = (float32(iw - mu[b])) . Ex (mu may be NULL: 0), patch[b * patch_stride + a * pw + c] =
+ * win[a][c] * sum_y Ey[a][y] T[b][y][c].  Table strides (elements per frame) are both 0 (one table for the batch: Ex [w][pw], Ey [ph][h]) or both
+ * non-zero (per-frame tables); win_stride 0 or elements per frame.  T belongs to the caller: the row stage can be read on its own. */
+int vistaf_ftp_test_dft_forward(const float *iw, const float *mu, const void *Ex, const void *Ey, size_t tab_stride_x, size_t tab_stride_y, const float *win,
+                                int win_stride, void *T, void *patch, int patch_stride, int B, int h, int w, int ph, int pw, void *stream);
+
+/* launch_dft_inverse: Q [B][ph][w] = patch . Gx (Gx [pw][w]), field = Gy . Q (Gy [h][ph]); amp = float32 |field|; field (may be NULL) the float64
+ * field itself; with cref (may be NULL; then amp_ref, prod and wrapped are not touched) wrapped = float32 angle(field * conj(cref)) and
+ * prod = amp_ref * amp, the reference planes at b * ref_stride (0: one for the batch).  gi_or_null: [B][10] on the host, of which ph and pw limit
+ * each frame's sums inside the ph x pw layout (rows a >= its ph of Q are not written). */
+int vistaf_ftp_test_dft_inverse(const void *patch, int patch_stride, const void *Gx, const void *Gy, size_t tab_stride_x, size_t tab_stride_y, void *Q, void *field,
+                                float *amp, const void *cref, const float *amp_ref, size_t ref_stride, float *prod, float *wrapped, const int32_t *gi_or_null,
+                                int B, int h, int w, int ph, int pw, void *stream);
 #ifdef __cplusplus
 }
 #endif
