@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "host_util.hpp"
+#include "mask_rules.hpp"      // chamfer_ball
 
 using namespace vf;
 #include "test_hooks.h"
@@ -124,30 +125,6 @@ int make_gkern(vistaf_ftp_handle *hd, double sigma, GKern *g)
     TRY(hd->allocs.upload(&g->d, f));
     g->k = (int)f.size();
     return 0;
-}
-
-// Row spans of the set { (dx, dy) : 3x3 chamfer metric <= margin } (integer metric of cv::distanceTransform DIST_L2 3x3: 0.955 -> 62587,
-// 1.3693 -> 89738 in 1/65536 units; dist = c / 65536 as float, exact, so "dist <= margin" is "c <= margin * 65536").  false: too large.
-bool chamfer_ball(float margin, RowSpanSE *se)
-{
-    const long long HV = 62587, DG = 89738;
-    const long long M = (long long)std::floor((double)margin * 65536.0);
-    if (M < 0) return false;
-    const int R = (int)(M / HV);
-    if (2 * R + 1 > 33 || R > 63) return false;
-    se->k = std::max(3, 2 * R + 1);
-    const int r = se->k / 2;
-    for (int i = 0; i < se->k; i++) {
-        const int dy = std::abs(i - r);
-        int a = -1;
-        for (int dx = 0; dx <= 63; dx++) {
-            const long long mn = std::min(dx, dy), mx = std::max(dx, dy);
-            if (HV * (mx - mn) + DG * mn <= M) a = dx; else break;
-        }
-        if (a < 0) { se->lo[i] = 1; se->hi[i] = -1; }       // empty row
-        else { se->lo[i] = (int8_t)-a; se->hi[i] = (int8_t)a; }
-    }
-    return true;
 }
 
 // cv2.getStructuringElement(MORPH_ELLIPSE, (k, k)), anchor at (k/2, k/2).  force_odd: the callers that first do `max(3, k | 1)`
@@ -976,18 +953,26 @@ int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int
     return hook_finish(taps, tmp, (hipStream_t)stream);
 }
 
-int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream)
+// The two chamfer hooks.  force: the one-wave two-pass kernel, which has no instance for every width; otherwise the dispatch, whose tier is
+// the return value
+static int chamfer_hook(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream, bool force)
 {
     if (!mask || !dist_a || (pair && !dist_b) || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || cap_px < 0)
         return fail(VISTAF_E_INVALID, "bad argument");
-    if (w > 512 && !(pair && w <= 1280)) return fail(VISTAF_E_INVALID, "no two-pass instance for this width");
+    if (force && w > 512 && !(pair && w <= 1280)) return fail(VISTAF_E_INVALID, "no two-pass instance for this width");
+    const int tier = force ? 0 : pair ? chamfer_pair_tier(B, h, w, cap_px) : chamfer_tier(h, w, cap_px);
     const size_t n = (size_t)B * h * w;
     int32_t *tmp_a = nullptr, *tmp_b = nullptr;
     HIPCHK(hipMalloc((void **)&tmp_a, n * sizeof(int32_t)));
     if (pair && hipMalloc((void **)&tmp_b, n * sizeof(int32_t)) != hipSuccess) { (void)hipFree(tmp_a); return fail(VISTAF_E_HIP, "hipMalloc"); }
-    if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, true);
-    else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, true);
-    return hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
+    if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, force);
+    else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, force);
+    const int rc = hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+int vistaf_ftp_test_chamfer(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream)
+{
+    return chamfer_hook(mask, pair, invert, dist_a, dist_b, B, h, w, cap_px, stream, true);
 }
 
 // ---- the mask topology launchers (labelling, largest component, chamfer dispatch, blob filter) on caller-supplied device planes
@@ -1017,17 +1002,7 @@ int vistaf_ftp_test_cc_largest(const int32_t *labels, const uint8_t *and_static,
 
 int vistaf_ftp_test_chamfer_dispatch(const uint8_t *mask, int pair, int invert, float *dist_a, float *dist_b, int B, int h, int w, int cap_px, void *stream)
 {
-    if (!mask || !dist_a || (pair && !dist_b) || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || cap_px < 0)
-        return fail(VISTAF_E_INVALID, "bad argument");
-    const int tier = pair ? chamfer_pair_tier(B, h, w, cap_px) : chamfer_tier(h, w, cap_px);
-    const size_t n = (size_t)B * h * w;
-    int32_t *tmp_a = nullptr, *tmp_b = nullptr;
-    HIPCHK(hipMalloc((void **)&tmp_a, n * sizeof(int32_t)));
-    if (pair && hipMalloc((void **)&tmp_b, n * sizeof(int32_t)) != hipSuccess) { (void)hipFree(tmp_a); return fail(VISTAF_E_HIP, "hipMalloc"); }
-    if (pair) launch_chamfer_pair(mask, tmp_a, dist_a, tmp_b, dist_b, B, h, w, cap_px, (hipStream_t)stream, false);
-    else launch_chamfer(mask, invert != 0, tmp_a, dist_a, B, h, w, cap_px, (hipStream_t)stream, false);
-    const int rc = hook_finish(tmp_a, tmp_b, (hipStream_t)stream);
-    return rc ? rc : tier;
+    return chamfer_hook(mask, pair, invert, dist_a, dist_b, B, h, w, cap_px, stream, false);
 }
 
 int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const int32_t *labels, const float *gmax, double min_peak_mm, double rel_frac,

@@ -1,8 +1,9 @@
 // Device code that k_backend.hip shares with the kernels it replaces (k_cc_label_lds in k_cc_dist.hip, k_blob_apply and k_tail in k_post.hip):
 // one definition, so the fused back end and the separate kernels execute the same operations in the same order.  Included by those three
-// files only.
+// files only; the mask family's rules it builds on are in mask_rules.hpp.
 #pragma once
 #include "kernels.hpp"
+#include "mask_rules.hpp"
 #include "pixel_ops.hpp"
 
 namespace vf {
@@ -47,9 +48,6 @@ __device__ inline void cc16_unite(uint16_t *L, int a, int b)
         b = (int)old;
     }
 }
-// dynamic LDS of cc_lds_build: the forest, and behind it the mask plane when that is staged too (MLDS)
-__host__ __device__ inline size_t cc_lds_forest_bytes(int P) { return (size_t)((P + 2 + 7) & ~7) * 2; }
-__host__ __device__ inline size_t cc_lds_bytes(int P) { return cc_lds_forest_bytes(P) + (size_t)P + 16; }
 // Builds the forest of one frame's mask `mg` in L16 (all threads of a 1024-thread workgroup call it): on return every union is done and
 // visible (the last statement is a barrier), cc16_find(L16, p) is the root -- the smallest pixel index -- of mask pixel p's 8-connected
 // component, and non-mask pixels hold 0xffff.  Returns the mask to test pixels with: the LDS copy for MLDS (every neighbour test is an
@@ -67,9 +65,9 @@ __device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, in
         __syncthreads();
     }
     const uint8_t *m = MLDS ? (const uint8_t *)ml : mg;
-    // Every pixel starts at the left end of its horizontal run (a prefix-max scan of the positions of the zero pixels of the row: 16
-    // waves, one row at a time each), so a run is one tree from the start and only the contacts between runs of adjacent rows are left
-    // to unite -- a few hundred unions per frame instead of four per pixel.  Roots are minimum pixel indices either way: same labels.
+    // Every pixel starts at the left end of its horizontal run (row_last_zero: 16 waves, one row at a time each), so a run is one tree
+    // from the start and only the contacts between runs of adjacent rows are left to unite -- a few hundred unions per frame instead of
+    // four per pixel.  Roots are minimum pixel indices either way: same labels.
     {
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nwv = blockDim.x >> 6;
         for (int y = wid; y < h; y += nwv) {
@@ -77,16 +75,7 @@ __device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, in
             for (int x0 = 0; x0 < w; x0 += 64) {
                 const int x = x0 + lane;
                 const bool on = x < w && m[y * w + x];
-                int lz = (x < w && !on) ? x : (int)0x80000000;
-                int t;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x111, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x112, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x114, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x118, 0xf, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x142, 0xa, 0xf, false); lz = t > lz ? t : lz;
-                t = __builtin_amdgcn_update_dpp((int)0x80000000, lz, 0x143, 0xc, 0xf, false); lz = t > lz ? t : lz;
-                lz = lz > carry ? lz : carry;
-                carry = __builtin_amdgcn_readlane(lz, 63);
+                const int lz = row_last_zero(x < w && !on, x, carry);
                 if (x < w) L16[y * w + x] = on ? (uint16_t)(y * w + lz + 1) : (uint16_t)0xffffu;
             }
         }
@@ -96,13 +85,7 @@ __device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, in
     for (int p = threadIdx.x; p < P; p += blockDim.x) {
         if (!m[p]) continue;
         const int y = p / w, x = p - y * w;
-        if (y == 0) continue;
-        const bool left = x > 0 && m[p - 1];
-        const bool ul = x > 0 && m[p - w - 1], up = m[p - w] != 0, ur = x < w - 1 && m[p - w + 1];
-        // the run above-left / above: already united through the left neighbour when that one touches it too
-        if ((ul || up) && !left) cc16_unite(L16, p, ul ? p - w - 1 : p - w);
-        // a run that starts above-right
-        if (ur && !up) cc16_unite(L16, p, p - w + 1);
+        cc_row_contacts(m, p, x, y, w, x > 0 && m[p - 1], [L16](int a, int b) { cc16_unite(L16, a, b); });
     }
     __syncthreads();
     return m;

@@ -126,6 +126,29 @@ __device__ inline uint32_t wave_scan_raw(uint32_t v, F op)
 __device__ inline uint32_t wave_scan_add(uint32_t v) { return wave_scan_raw(v, [](uint32_t a, uint32_t b) { return a + b; }); }
 __device__ inline int wave_scan_add(int v) { return (int)wave_scan_add((uint32_t)v); }
 __device__ inline uint32_t wave_scan_max(uint32_t v) { return wave_scan_raw(v, [](uint32_t a, uint32_t b) { return b > a ? b : a; }); }
+// The same scan for a signed value whose identity is not 0 (a maximum of values that may be negative, a minimum): lanes without a source
+// read `identity` (bound_ctrl off), in the row steps as in the broadcasts.
+template <typename F>
+__device__ inline int wave_scan_ident(int v, int identity, F op)
+{
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x111, 0xf, 0xf, false));
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x112, 0xf, 0xf, false));
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x114, 0xf, 0xf, false));
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x118, 0xf, 0xf, false));
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x142, 0xa, 0xf, false));
+    v = op(v, __builtin_amdgcn_update_dpp(identity, v, 0x143, 0xc, 0xf, false));
+    return v;
+}
+// inclusive prefix maximum / minimum over lanes 0..l; id: a value no input exceeds / falls below
+__device__ inline int wave_scan_max_i32(int v, int id) { return wave_scan_ident(v, id, [](int a, int b) { return b > a ? b : a; }); }
+__device__ inline int wave_scan_min_i32(int v, int id) { return wave_scan_ident(v, id, [](int a, int b) { return b < a ? b : a; }); }
+// inclusive suffix minimum over lanes l..63: mirror the lanes (ds_bpermute with 63 - lane), prefix minimum, mirror back
+__device__ inline int wave_suffix_min_i32(int v, int id, int lane)
+{
+    v = __builtin_amdgcn_ds_bpermute((63 - lane) << 2, v);
+    v = wave_scan_min_i32(v, id);
+    return __builtin_amdgcn_ds_bpermute((63 - lane) << 2, v);
+}
 // exclusive prefix sum and the wave total
 __device__ inline int wave_excl_scan(int v, int &total)
 {

@@ -39,29 +39,20 @@ __global__ __launch_bounds__(1024) void k_backend_fused(float *__restrict__ dept
             r = p;
             for (int q = ((volatile uint16_t *)L16)[r]; q != r; q = ((volatile uint16_t *)L16)[r]) r = q;
             L16[p] = (uint16_t)r;
-            if (r == p) __hip_atomic_store(&PB[p], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // instead of clearing the whole plane
+            if (r == p) st_relaxed<__HIP_MEMORY_SCOPE_AGENT>(&PB[p], 0u);      // instead of clearing the whole plane
         }
         labels[off + p] = r;
     }
     __threadfence_block();      // one workgroup per frame: the zeros are in L2 before this CU's atomics below (as k_cc_largest)
     __syncthreads();
 
-    // 2. per-component peak: one atomic per wave and root among its 64 consecutive pixels (k_blob_peaks)
+    // 2. per-component peak: one atomic per wave and root among its 64 consecutive pixels (wave_root_max, as k_blob_peaks)
     float *D = depth + off;
     {
         const int Pr = ((P + 63) / 64) * 64;
         for (int p = threadIdx.x; p < Pr; p += blockDim.x) {
             const int root = (p < P && m[p]) ? (int)L16[p] : -1;
-            const unsigned int v = root >= 0 ? __float_as_uint(D[p]) : 0u;
-            unsigned long long active = __ballot(root >= 0);
-            while (active) {
-                const int leader = __ffsll((long long)active) - 1;
-                const int r0 = __shfl(root, leader, 64);
-                const bool same = root == r0;
-                const unsigned int mx = wave_max_u32(same ? v : 0u);
-                if (lane == leader) atomicMax(&PB[r0], mx);
-                active &= ~__ballot(same);
-            }
+            wave_root_max(root, root >= 0 ? __float_as_uint(D[p]) : 0u, PB, lane);
         }
     }
     __threadfence_block();
@@ -74,7 +65,7 @@ __global__ __launch_bounds__(1024) void k_backend_fused(float *__restrict__ dept
         uint8_t *ml = const_cast<uint8_t *>(m);
         for (int p = threadIdx.x; p < P; p += blockDim.x) {
             if (!m[p] || (int)L16[p] != p) continue;
-            const float peak = __uint_as_float(__hip_atomic_load(&PB[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            const float peak = __uint_as_float(ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(&PB[p]));
             ml[p] = peak >= thr ? (uint8_t)2 : (uint8_t)1;
         }
     }
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(1024) void k_backend_fused(float *__restrict__ dept
 bool backend_fused_fits(int h, int w)
 {
     const size_t P = (size_t)h * w;
-    return P <= 65535 && cc_lds_bytes(h * w) + TAIL_STATIC_LDS <= 160 * 1024;
+    return P <= 65535 && cc_lds_bytes(h * w) + TAIL_STATIC_LDS <= (size_t)LDS_DYN_MAX;
 }
 
 void launch_backend_fused(float *depth, const uint8_t *cand, const unsigned int *gmax_bits, const float *unitless, const uint8_t *roi_static,
@@ -114,7 +105,7 @@ void launch_backend_fused(float *depth, const uint8_t *cand, const unsigned int 
                           hipStream_t st)
 {
     static DynLdsOnce lds_once;
-    ensure_dyn_lds(lds_once, (const void *)k_backend_fused, 160 * 1024 - TAIL_STATIC_LDS);
+    ensure_dyn_lds(lds_once, (const void *)k_backend_fused, LDS_DYN_MAX - TAIL_STATIC_LDS);
     hipLaunchKernelGGL(k_backend_fused, dim3(B), dim3(1024), cc_lds_bytes(h * w), st, depth, cand, gmax_bits, unitless, roi_static, reliable, status,
                        min_peak_mm, rel_frac, pp, labels, peak_bits, kept, scalars, nscal, out_h, out_r, h, w);
 }

@@ -5,8 +5,15 @@
 //   cc_largest       labels == 1 + argmax(areas)                           (shape_ftp.py:716-718)
 //   chamfer          cv2.distanceTransform(DIST_L2, 3)                     (shape_ftp.py:725, :1309, :1312)
 //
-// One 1024-thread workgroup owns one frame, so every union-find word is only touched by one CU; loads
-// of label words go through agent-scope relaxed atomics (served by L2, never a stale L1 line).
+// The rules the kernels share (contact rule, run-length counts, largest-root key, chamfer metric and closed form, LDS limits) are in
+// mask_rules.hpp; the LDS label forest is in backend_device.hpp.
+//
+// k_cc_label_lds, k_cc_largest, k_chamfer_lds and k_chamfer2 give a frame to one workgroup, so what they write for one another stays on
+// one CU: a __threadfence_block() orders it, and k_cc_largest's areas need no agent-scope write-back.  k_cc_init / k_cc_merge /
+// k_cc_flatten are grids over all pixels of the batch: workgroups on different CUs unite and flatten the same forest at the same time, so
+// there a label word is read with an agent-scope relaxed atomic load (served by L2, never a stale L1 line) and changed with an agent-scope
+// atomicMin.  k_ccl_area / k_ccl_best / k_ccl_out are such grids too; they meet only in integer atomics (areas, the best key), which the
+// next launch reads.
 #include <cstdlib>
 #include "kernels.hpp"
 #include "backend_device.hpp"
@@ -28,14 +35,10 @@ void launch_threshold_mask(const float *q, const uint8_t *roi, const float *thr,
 }
 
 // ---- union-find ---------------------------------------------------------------------------------
-__device__ inline int ld_label(const int32_t *L, int i)
-{
-    return __hip_atomic_load(&L[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ inline int cc_find(const int32_t *L, int i)
 {
-    int p = ld_label(L, i);
-    while (p != i) { i = p; p = ld_label(L, i); }
+    int p = ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(&L[i]);
+    while (p != i) { i = p; p = ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(&L[i]); }
     return i;
 }
 __device__ inline void cc_unite(int32_t *L, int a, int b)
@@ -89,14 +92,7 @@ __global__ void k_cc_merge(const uint8_t *__restrict__ mask, int32_t *__restrict
     int y = p / w, x = p - y * w;
     const bool left = x > 0 && m[p - 1];
     if ((threadIdx.x & 63) == 0 && left) cc_unite(L, p, p - 1);       // the run continues in the previous segment
-    if (y > 0) {
-        // only the contacts between runs of adjacent rows (as in k_cc_label_lds): a pixel whose left neighbour is set leaves the run above-left /
-        // above to that neighbour, and the pixel above-right only starts a new contact when the pixel above is clear -- a couple of unions per
-        // run instead of three per pixel (the big blob of a reliable mask made every one of them a walk to the same root)
-        const bool ul = x > 0 && m[p - w - 1], up = m[p - w] != 0, ur = x < w - 1 && m[p - w + 1];
-        if ((ul || up) && !left) cc_unite(L, p, ul ? p - w - 1 : p - w);
-        if (ur && !up) cc_unite(L, p, p - w + 1);
-    }
+    cc_row_contacts(m, p, x, y, w, left, [L](int a, int b) { cc_unite(L, a, b); });
 }
 __global__ void k_cc_flatten(const uint8_t *__restrict__ mask, int32_t *__restrict__ labels, int P)
 {
@@ -124,26 +120,23 @@ int cc_label_tier(int h, int w, bool force_global)
 {
     const int P = h * w;
     if (force_global || P > 65535) return CCT_GLOBAL;
-    if (cc_lds_bytes(P) <= 160 * 1024) return CCT_LDS_MASK;
-    return cc_lds_forest_bytes(P) <= 150 * 1024 ? CCT_LDS : CCT_GLOBAL;
+    if (cc_lds_bytes(P) <= (size_t)LDS_DYN_MAX) return CCT_LDS_MASK;
+    return cc_lds_forest_bytes(P) <= (size_t)LDS_DYN_HEADROOM ? CCT_LDS : CCT_GLOBAL;
 }
 
+template <bool MLDS>
+static void launch_cc_label_lds(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st)
+{
+    static DynLdsOnce lds_once;
+    ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<MLDS>, LDS_DYN_MAX);
+    hipLaunchKernelGGL(k_cc_label_lds<MLDS>, dim3(B), dim3(1024), MLDS ? cc_lds_bytes(h * w) : cc_lds_forest_bytes(h * w), st, mask, labels, h, w);
+}
 void launch_cc_label(const uint8_t *mask, int32_t *labels, int B, int h, int w, hipStream_t st, bool force_global)
 {
     int P = h * w;
     const int tier = cc_label_tier(h, w, force_global);
-    if (tier == CCT_LDS_MASK) {
-        static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<true>, 160 * 1024);
-        hipLaunchKernelGGL(k_cc_label_lds<true>, dim3(B), dim3(1024), cc_lds_bytes(P), st, mask, labels, h, w);
-        return;
-    }
-    if (tier == CCT_LDS) {
-        static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_cc_label_lds<false>, 160 * 1024);
-        hipLaunchKernelGGL(k_cc_label_lds<false>, dim3(B), dim3(1024), cc_lds_forest_bytes(P), st, mask, labels, h, w);
-        return;
-    }
+    if (tier == CCT_LDS_MASK) return launch_cc_label_lds<true>(mask, labels, B, h, w, st);
+    if (tier == CCT_LDS) return launch_cc_label_lds<false>(mask, labels, B, h, w, st);
     const dim3 g((P + 255) / 256, B);
     hipLaunchKernelGGL(k_cc_init, g, dim3(256), 0, st, mask, labels, P, w);
     hipLaunchKernelGGL(k_cc_merge, g, dim3(256), 0, st, mask, labels, h, w);
@@ -166,30 +159,15 @@ __global__ __launch_bounds__(1024) void k_cc_largest(const int32_t *__restrict__
     __threadfence_block();      // one workgroup per frame: no agent-scope write-back of the L2
     __syncthreads();
     int Pr = ((P + U * 1024 - 1) / (U * 1024)) * (U * 1024);
-    // run-length accumulation per wave: consecutive tiles mostly belong to the same (large) component, and an atomic per tile on one
-    // address serialises the whole frame in L2
     int run_root = -1, run_cnt = 0;
     for (int p0 = threadIdx.x; p0 < Pr; p0 += U * T) {
         int root[U];
 #pragma unroll
         for (int u = 0; u < U; u++) { int p = p0 + u * T; root[u] = p < P ? L[p] : -1; }
 #pragma unroll
-        for (int u = 0; u < U; u++) {
-            unsigned long long active = __ballot(root[u] >= 0);
-            while (active) {
-                int leader = __ffsll((long long)active) - 1;
-                int r0 = __builtin_amdgcn_readlane(root[u], leader);
-                unsigned long long same = __ballot(root[u] == r0);
-                if (r0 == run_root) run_cnt += (int)__popcll(same);
-                else {
-                    if (run_root >= 0 && lane == 0) atomicAdd(&A[run_root], run_cnt);
-                    run_root = r0; run_cnt = (int)__popcll(same);
-                }
-                active &= ~same;
-            }
-        }
+        for (int u = 0; u < U; u++) ccl_run_count(root[u], run_root, run_cnt, A, lane);
     }
-    if (run_root >= 0 && lane == 0) atomicAdd(&A[run_root], run_cnt);
+    ccl_run_flush(run_root, run_cnt, A, lane);
     __threadfence_block();      // one workgroup per frame: no agent-scope write-back of the L2
     __syncthreads();
     unsigned long long best = 0;
@@ -199,18 +177,18 @@ __global__ __launch_bounds__(1024) void k_cc_largest(const int32_t *__restrict__
         for (int u = 0; u < U; u++) {
             int p = p0 + u * T;
             lab[u] = p < P ? L[p] : -1;
-            ar[u] = p < P ? __hip_atomic_load(&A[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+            ar[u] = p < P ? ld_relaxed<__HIP_MEMORY_SCOPE_AGENT>(&A[p]) : 0;
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {
             int p = p0 + u * T;
             if (lab[u] != p) continue;
-            unsigned long long key = ((unsigned long long)(unsigned int)ar[u] << 32) | (unsigned int)(0x7fffffff - p);
+            const unsigned long long key = ccl_key(ar[u], p);
             if (key > best) best = key;
         }
     }
     best = block_max_u64(best, scratch);
-    int broot = (best >> 32) ? (0x7fffffff - (int)(best & 0xffffffffu)) : -2;
+    const int broot = ccl_root(best);
     for (int p0 = threadIdx.x; p0 < P; p0 += U * T) {
         int lab[U];
         uint8_t as[U];
@@ -237,29 +215,15 @@ __global__ __launch_bounds__(256) void k_ccl_area(const int32_t *__restrict__ la
     for (int u = 0; u < U; u++) { const int p = p0 + u * 64; root[u] = p < P ? L[p] : -1; }
     int run_root = -1, run_cnt = 0;
 #pragma unroll
-    for (int u = 0; u < U; u++) {
-        unsigned long long active = __ballot(root[u] >= 0);
-        while (active) {
-            const int leader = __ffsll((long long)active) - 1;
-            const int r0 = __builtin_amdgcn_readlane(root[u], leader);
-            const unsigned long long same = __ballot(root[u] == r0);
-            if (r0 == run_root) run_cnt += (int)__popcll(same);
-            else {
-                if (run_root >= 0 && lane == 0) atomicAdd(&A[run_root], run_cnt);
-                run_root = r0; run_cnt = (int)__popcll(same);
-            }
-            active &= ~same;
-        }
-    }
-    if (run_root >= 0 && lane == 0) atomicAdd(&A[run_root], run_cnt);
+    for (int u = 0; u < U; u++) ccl_run_count(root[u], run_root, run_cnt, A, lane);
+    ccl_run_flush(run_root, run_cnt, A, lane);
 }
 __global__ __launch_bounds__(256) void k_ccl_best(const int32_t *__restrict__ labels, const int32_t *__restrict__ area, unsigned long long *__restrict__ best, int P)
 {
     const size_t b = blockIdx.y;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long key = 0;
-    if (p < P && labels[b * (size_t)P + p] == p)
-        key = ((unsigned long long)(unsigned int)area[b * (size_t)P + p] << 32) | (unsigned int)(0x7fffffff - p);
+    if (p < P && labels[b * (size_t)P + p] == p) key = ccl_key(area[b * (size_t)P + p], p);
     if (!__ballot(key != 0)) return;
     for (int o = 32; o; o >>= 1) { const unsigned long long v = __shfl_xor(key, o, 64); key = v > key ? v : key; }
     if ((threadIdx.x & 63) == 0) atomicMax(&best[b], key);
@@ -270,8 +234,7 @@ __global__ __launch_bounds__(256) void k_ccl_out(const int32_t *__restrict__ lab
     const size_t b = blockIdx.y;
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= P) return;
-    const unsigned long long k = best[b];
-    const int broot = (k >> 32) ? (0x7fffffff - (int)(k & 0xffffffffu)) : -2;
+    const int broot = ccl_root(best[b]);
     out[b * (size_t)P + p] = (uint8_t)(labels[b * (size_t)P + p] == broot && (and_static ? and_static[p] : (uint8_t)1));
 }
 
@@ -298,10 +261,7 @@ void launch_cc_largest(const int32_t *labels, int32_t *area_scratch, unsigned lo
 }
 
 // ---- chamfer distance ---------------------------------------------------------------------------
-constexpr int CH_INF = 1 << 20;
-constexpr int CH_HV = 62587;    // cvRound(0.955  * 65536)
-constexpr int CH_DG = 89738;    // cvRound(1.3693 * 65536)
-constexpr int CH_DIST_MAX = 0x7fffffff >> 2;
+constexpr int CH_INF = 1 << 20;     // row distance of a row without a zero pixel (k_rowdist's plane)
 
 // horizontal distance to the nearest "zero" pixel of each row, CH_INF when the row has none: one wave per row, 64 columns at a time.
 // Left to right the position of the last zero pixel at or before x is a prefix maximum (DPP scan + carry across chunks), right to left the next
@@ -313,44 +273,26 @@ __global__ __launch_bounds__(256) void k_rowdist(const uint8_t *__restrict__ src
     if (row >= B * h) return;
     const uint8_t *s = src + (size_t)row * w;
     int32_t *o = g + (size_t)row * w;
-    const int none = (int)0x80000000;
-    int carry = none;
+    int carry = ROW_NO_ZERO;
     for (int x0 = 0; x0 < w; x0 += 64) {
         const int x = x0 + lane;
         const bool zero = x < w && (invert ? (s[x] != 0) : (s[x] == 0));
-        int lz = zero ? x : none, t;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x111, 0xf, 0xf, false); lz = t > lz ? t : lz;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x112, 0xf, 0xf, false); lz = t > lz ? t : lz;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x114, 0xf, 0xf, false); lz = t > lz ? t : lz;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x118, 0xf, 0xf, false); lz = t > lz ? t : lz;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x142, 0xa, 0xf, false); lz = t > lz ? t : lz;
-        t = __builtin_amdgcn_update_dpp(none, lz, 0x143, 0xc, 0xf, false); lz = t > lz ? t : lz;
-        lz = lz > carry ? lz : carry;
-        carry = __builtin_amdgcn_readlane(lz, 63);
-        if (x < w) o[x] = lz == none ? CH_INF : x - lz;
+        const int lz = row_last_zero(zero, x, carry);
+        if (x < w) o[x] = lz == ROW_NO_ZERO ? CH_INF : x - lz;
     }
     const int far = 0x7fffffff;
     carry = far;
     for (int x0 = ((w - 1) / 64) * 64; x0 >= 0; x0 -= 64) {
         const int x = x0 + lane;
         const bool zero = x < w && (invert ? (s[x] != 0) : (s[x] == 0));
-        // suffix minimum over lanes l..63: mirror the lanes, prefix-minimum, mirror back
-        int nz = zero ? x : far, t;
-        nz = __builtin_amdgcn_ds_bpermute((63 - lane) << 2, nz);
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x111, 0xf, 0xf, false); nz = t < nz ? t : nz;
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x112, 0xf, 0xf, false); nz = t < nz ? t : nz;
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x114, 0xf, 0xf, false); nz = t < nz ? t : nz;
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x118, 0xf, 0xf, false); nz = t < nz ? t : nz;
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x142, 0xa, 0xf, false); nz = t < nz ? t : nz;
-        t = __builtin_amdgcn_update_dpp(far, nz, 0x143, 0xc, 0xf, false); nz = t < nz ? t : nz;
-        nz = __builtin_amdgcn_ds_bpermute((63 - lane) << 2, nz);
+        int nz = wave_suffix_min_i32(zero ? x : far, far, lane);
         nz = nz < carry ? nz : carry;
         carry = __builtin_amdgcn_readlane(nz, 0);
         if (x < w && nz != far) { const int d = nz - x; if (d < o[x]) o[x] = d; }
     }
 }
 
-// d(x,y) = min over rows y' of HV*|g-dy| + DG*min(g,dy)  (the two-pass 3x3 chamfer result, closed form)
+// the closed form (chamfer_col_min) over k_rowdist's plane, a thread per pixel
 __global__ void k_chamfer_cols(const int32_t *__restrict__ g, float *__restrict__ dist, int h, int w, int cap)
 {
     int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -358,21 +300,8 @@ __global__ void k_chamfer_cols(const int32_t *__restrict__ g, float *__restrict_
     size_t b = blockIdx.z;
     if (x >= w) return;
     const int32_t *G = g + b * (size_t)h * w;
-    int best = CH_DIST_MAX;
-    for (int dy = 0; dy <= cap; dy++) {
-        if ((long long)dy * CH_HV >= best) break;
-        for (int s = 0; s < 2; s++) {
-            if (s && !dy) break;
-            int yy = s ? y + dy : y - dy;
-            if (yy < 0 || yy >= h) continue;
-            int gx = G[(size_t)yy * w + x];
-            if (gx >= CH_INF) continue;
-            int mn = gx < dy ? gx : dy, mx = gx < dy ? dy : gx;
-            int c = CH_HV * (mx - mn) + CH_DG * mn;
-            if (c < best) best = c;
-        }
-    }
-    dist[b * (size_t)h * w + (size_t)y * w + x] = (float)best * (1.0f / 65536.0f);
+    const int best = chamfer_col_min([G, w, x](int yy, int &gx) { gx = G[(size_t)yy * w + x]; return gx < CH_INF; }, y, h, cap);
+    dist[b * (size_t)h * w + (size_t)y * w + x] = chamfer_to_float(best);
 }
 
 // ---- the two-pass 3x3 chamfer itself (cv::distanceTransform DIST_L2, 3x3 mask: distanceTransform_3x3), one wave per frame.
@@ -387,22 +316,8 @@ __global__ void k_chamfer_cols(const int32_t *__restrict__ g, float *__restrict_
 // depth is what the 6-bit vmcnt counter can tell apart: with aligned rows (w a multiple of 4, planes aligned as hipMalloc leaves them) a
 // row is PPL / 4 dword loads of the mask or dwordx4 loads of the temporary plane and as many dwordx4 stores, 2 * PPL / 4 operations, and
 // at most 63 may be outstanding behind the load a row waits for.  Other widths load and store element by element (and wait earlier).
-constexpr int CH2_INF = 0x7fffffff >> 2;     // cv DIST_MAX: border / initial value of the temporary plane
 __host__ __device__ constexpr int ch2_ring(int ppl) { return ppl == 4 ? 31 : ppl == 8 ? 15 : 6; }
 
-// inclusive prefix minimum over lanes 0..l
-__device__ inline int ch2_scan_min_up(int v)
-{
-    const int big = 0x7fffffff;
-    int t;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x111, 0xf, 0xf, false); v = t < v ? t : v;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x112, 0xf, 0xf, false); v = t < v ? t : v;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x114, 0xf, 0xf, false); v = t < v ? t : v;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x118, 0xf, 0xf, false); v = t < v ? t : v;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x142, 0xa, 0xf, false); v = t < v ? t : v;
-    t = __builtin_amdgcn_update_dpp(big, v, 0x143, 0xc, 0xf, false); v = t < v ? t : v;
-    return v;
-}
 // mask bytes of columns x0 .. x0 + PPL of row y, four to a word (0 beyond the frame)
 template <int PPL>
 __device__ inline void ch2_load_mask(const uint8_t *__restrict__ src, int y, int h, int w, int x0, bool vec, uint32_t (&m)[PPL / 4])
@@ -424,14 +339,14 @@ __device__ inline void ch2_load_mask(const uint8_t *__restrict__ src, int y, int
         m[q] = v;
     }
 }
-// columns x0 .. x0 + PPL of row y of the temporary plane (CH2_INF beyond the frame; y < 0: no row)
+// columns x0 .. x0 + PPL of row y of the temporary plane (CH_DIST_MAX beyond the frame; y < 0: no row)
 template <int PPL>
 __device__ inline void ch2_load_tmp(const int32_t *__restrict__ tmp, int y, int w, int x0, bool vec, int (&v)[PPL])
 {
 #pragma unroll
     for (int q = 0; q < PPL / 4; q++) {
         const int x = x0 + 4 * q;
-        int4 t = make_int4(CH2_INF, CH2_INF, CH2_INF, CH2_INF);
+        int4 t = make_int4(CH_DIST_MAX, CH_DIST_MAX, CH_DIST_MAX, CH_DIST_MAX);
         if (y >= 0 && x < w) {
             const int32_t *s = tmp + (size_t)y * w + x;
             if (vec) t = *(const int4 *)s;
@@ -487,7 +402,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
     {
         int up[PPL];
 #pragma unroll
-        for (int j = 0; j < PPL; j++) up[j] = CH2_INF;
+        for (int j = 0; j < PPL; j++) up[j] = CH_DIST_MAX;
         uint32_t ring[RING][PPL / 4];
 #pragma unroll
         for (int r = 0; r < RING; r++) ch2_load_mask<PPL>(src, r, h, w, x0, vec, ring[r]);
@@ -496,7 +411,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
             for (int r = 0; r < RING; r++) {
                 const int y = y0 + r;
                 if (y >= h) break;
-                const int upl = wave_shr1(up[PPL - 1], CH2_INF), upr = wave_shl1(up[0], CH2_INF);
+                const int upl = wave_shr1(up[PPL - 1], CH_DIST_MAX), upr = wave_shl1(up[0], CH_DIST_MAX);
                 int t[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
@@ -513,8 +428,8 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
                 // d(x) = min(t(x), d(x-1) + HV): lane-local scan, carries across lanes by a wave scan of (last - step * lane)
 #pragma unroll
                 for (int j = 1; j < PPL; j++) { int v = t[j - 1] + CH_HV; t[j] = v < t[j] ? v : t[j]; }
-                const int sc = ch2_scan_min_up(t[PPL - 1] - step * lane) + step * lane;      // final value of this lane's last column
-                const int carry = wave_shr1(sc, CH2_INF);                                     // d(x0 - 1)
+                const int sc = wave_scan_min_i32(t[PPL - 1] - step * lane, 0x7fffffff) + step * lane;      // final value of this lane's last column
+                const int carry = wave_shr1(sc, CH_DIST_MAX);                                     // d(x0 - 1)
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     int v = carry + CH_HV * (j + 1);
@@ -529,7 +444,7 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
     {
         int dn[PPL];
 #pragma unroll
-        for (int j = 0; j < PPL; j++) dn[j] = CH2_INF;
+        for (int j = 0; j < PPL; j++) dn[j] = CH_DIST_MAX;
         int ring[RING][PPL];
 #pragma unroll
         for (int r = 0; r < RING; r++) ch2_load_tmp<PPL>(tmp, h - 1 - r, w, x0, vec, ring[r]);
@@ -538,34 +453,30 @@ __global__ __launch_bounds__(64) void k_chamfer2(const uint8_t *__restrict__ src
             for (int r = 0; r < RING; r++) {
                 const int y = h - 1 - (y0 + r);
                 if (y < 0) break;
-                const int dnl = wave_shr1(dn[PPL - 1], CH2_INF), dnr = wave_shl1(dn[0], CH2_INF);
+                const int dnl = wave_shr1(dn[PPL - 1], CH_DIST_MAX), dnr = wave_shl1(dn[0], CH_DIST_MAX);
                 int t[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     const int a = (j < PPL - 1 ? dn[j + 1] : dnr) + CH_DG, c = (j > 0 ? dn[j - 1] : dnl) + CH_DG, u = dn[j] + CH_HV;
                     int m = a < u ? a : u;
                     m = c < m ? c : m;
-                    const int cur = x0 + j < w ? ring[r][j] : CH2_INF;
+                    const int cur = x0 + j < w ? ring[r][j] : CH_DIST_MAX;
                     t[j] = m < cur ? m : cur;
                 }
                 ch2_load_tmp<PPL>(tmp, y - RING, w, x0, vec, ring[r]);
                 // d(x) = min(t(x), d(x+1) + HV): the same scan on mirrored lanes
 #pragma unroll
                 for (int j = PPL - 2; j >= 0; j--) { int v = t[j + 1] + CH_HV; t[j] = v < t[j] ? v : t[j]; }
-                // mirror: lane l' = 63 - l, so "lanes to the right" become a prefix
+                // "lanes to the right": a suffix minimum, taken of (first - step * mirrored lane)
                 const int ml = 63 - lane;
-                int first = t[0] - step * ml;
-                // prefix minimum over mirrored lanes = suffix minimum over lanes: scan the value permuted to mirrored order
-                first = __builtin_amdgcn_ds_bpermute(ml << 2, first);
-                first = ch2_scan_min_up(first);
-                first = __builtin_amdgcn_ds_bpermute(ml << 2, first) + step * ml;            // final value of this lane's first column
-                const int carry = wave_shl1(first, CH2_INF);                                  // d(x0 + PPL)
+                const int first = wave_suffix_min_i32(t[0] - step * ml, 0x7fffffff, lane) + step * ml;     // final value of this lane's first column
+                const int carry = wave_shl1(first, CH_DIST_MAX);                                  // d(x0 + PPL)
                 float o[PPL];
 #pragma unroll
                 for (int j = 0; j < PPL; j++) {
                     int v = carry + CH_HV * (PPL - j);
                     dn[j] = v < t[j] ? v : t[j];
-                    o[j] = (float)(dn[j] > CH2_INF ? CH2_INF : dn[j]) * (1.0f / 65536.0f);
+                    o[j] = chamfer_to_float(dn[j] > CH_DIST_MAX ? CH_DIST_MAX : dn[j]);
                 }
                 ch2_store_row<PPL, float, float4>(dist, y, w, x0, vec, o);
             }
@@ -640,36 +551,23 @@ __global__ __launch_bounds__(1024) void k_chamfer_lds(const uint8_t *__restrict_
     float *dist = dist_all + b * (size_t)P;
     for (int p = tid; p < P; p += 1024) {
         const int y = p / w, x = p - y * w;
-        int best = CH_DIST_MAX;
-        for (int dy = 0; dy <= cap; dy++) {
-            if ((long long)dy * CH_HV >= best) break;
-#pragma unroll
-            for (int s = 0; s < 2; s++) {
-                if (s && !dy) break;
-                const int yy = s ? y + dy : y - dy;
-                if (yy < 0 || yy >= h) continue;
-                const int gx = (int)chl_g[yy * w + x];
-                if (gx == (int)CHL_NONE) continue;
-                const int mn = gx < dy ? gx : dy, mx = gx < dy ? dy : gx;
-                const int c = CH_HV * (mx - mn) + CH_DG * mn;
-                if (c < best) best = c;
-            }
-        }
-        dist[p] = (float)best * (1.0f / 65536.0f);
+        const int best = chamfer_col_min([w, x](int yy, int &gx) { gx = (int)chl_g[yy * w + x]; return gx != (int)CHL_NONE; }, y, h, cap);
+        dist[p] = chamfer_to_float(best);
     }
 }
 
-// rows either side of a pixel that the closed form looks at: every zero pixel within cap_px + 2 of it lies that close
-static int chamfer_cap_rows(int h, int cap_px)
+// the two-pass kernel on nwg workgroups of one wave each, with the columns per lane that cover the width (no tier admits more than 1280)
+static void launch_chamfer2(const uint8_t *src, int invert, int32_t *tmp_a, float *dist_a, int32_t *tmp_b, float *dist_b, int nwg, int B, int h, int w,
+                            hipStream_t st)
 {
-    const int cap = (int)((cap_px + 2) / 0.955) + 2;
-    return cap > h ? h : cap;
+    auto *k = w <= 256 ? k_chamfer2<4> : w <= 512 ? k_chamfer2<8> : k_chamfer2<20>;
+    hipLaunchKernelGGL(k, dim3(nwg), dim3(64), 0, st, src, invert, tmp_a, dist_a, tmp_b, dist_b, B, h, w);
 }
 int chamfer_tier(int h, int w, int cap_px, bool force_twopass)
 {
     // small caps (the erosion margins): a handful of rows per pixel on 16 waves; for wide bands the per-pixel loop costs more than
     // the one-wave two-pass kernel (measured at cap 46: 345 us against 200 us)
-    if (!force_twopass && chamfer_cap_rows(h, cap_px) <= 16 && (size_t)h * w * 2 <= 150 * 1024 && w <= 512) return CHT_LDS;
+    if (!force_twopass && chamfer_cap_rows(h, cap_px) <= 16 && chamfer_lds_fits(h, w) && w <= 512) return CHT_LDS;
     // beyond the two-pass kernel's 512 columns: closed form of the same two passes, exact up to cap_px (all that the callers look at)
     return w <= 512 ? CHT_TWOPASS : CHT_ROWCOL;
 }
@@ -678,7 +576,7 @@ int chamfer_pair_tier(int B, int h, int w, int cap_px, bool force_twopass)
     // wide bands on wide frames (native crops, band 200 px): the closed form walks up to 2 * cap rows per pixel (0.3 ms per frame, all CUs),
     // the two-pass kernel a frame's rows once each way on one wave per frame and set (4 ms, all frames side by side): the latter from 16 frames on
     const int cap = chamfer_cap_rows(h, cap_px);
-    const bool two_pass = (force_twopass || cap > 16 || (size_t)h * w * 2 > 150 * 1024) && (w <= 512 || (w <= 1280 && cap > 64 && (B >= 16 || force_twopass)));
+    const bool two_pass = (force_twopass || cap > 16 || !chamfer_lds_fits(h, w)) && (w <= 512 || (w <= 1280 && cap > 64 && (B >= 16 || force_twopass)));
     return two_pass ? CHT_TWOPASS : chamfer_tier(h, w, cap_px, false);
 }
 
@@ -688,13 +586,12 @@ void launch_chamfer(const uint8_t *src, bool invert, int32_t *rowdist, float *di
     const int tier = chamfer_tier(h, w, cap_px, force_twopass);
     if (tier == CHT_LDS) {
         static DynLdsOnce lds_once;
-        ensure_dyn_lds(lds_once, (const void *)k_chamfer_lds, 160 * 1024);
+        ensure_dyn_lds(lds_once, (const void *)k_chamfer_lds, LDS_DYN_MAX);
         hipLaunchKernelGGL(k_chamfer_lds, dim3(B), dim3(1024), (size_t)h * w * 2, st, src, invert ? 1 : 0, dist, h, w, cap);
         return;
     }
     if (tier == CHT_TWOPASS) {
-        if (w <= 256) hipLaunchKernelGGL(k_chamfer2<4>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w);
-        else hipLaunchKernelGGL(k_chamfer2<8>, dim3(B), dim3(64), 0, st, src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, h, w);
+        launch_chamfer2(src, invert ? 1 : 0, rowdist, dist, nullptr, nullptr, B, B, h, w, st);
         return;
     }
     int rows = B * h;
@@ -713,9 +610,7 @@ void launch_chamfer_pair(const uint8_t *src, int32_t *tmp_a, float *dist_a, int3
         launch_chamfer(src, true, tmp_b, dist_b, B, h, w, cap_px, st, false);
         return;
     }
-    if (w <= 256) hipLaunchKernelGGL(k_chamfer2<4>, dim3(2 * B), dim3(64), 0, st, src, 0, tmp_a, dist_a, tmp_b, dist_b, B, h, w);
-    else if (w <= 512) hipLaunchKernelGGL(k_chamfer2<8>, dim3(2 * B), dim3(64), 0, st, src, 0, tmp_a, dist_a, tmp_b, dist_b, B, h, w);
-    else hipLaunchKernelGGL(k_chamfer2<20>, dim3(2 * B), dim3(64), 0, st, src, 0, tmp_a, dist_a, tmp_b, dist_b, B, h, w);
+    launch_chamfer2(src, 0, tmp_a, dist_a, tmp_b, dist_b, 2 * B, B, h, w, st);
 }
 
 __global__ void k_erode_by_dist(const float *__restrict__ dist, const uint8_t *__restrict__ src, float margin, uint8_t *__restrict__ out, size_t n)

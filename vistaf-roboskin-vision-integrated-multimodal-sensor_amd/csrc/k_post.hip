@@ -200,16 +200,7 @@ __global__ void k_blob_peaks(const float *__restrict__ depth, const int32_t *__r
     int Pr = ((P + 255) / 256) * 256;
     for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < Pr; p += gridDim.x * blockDim.x) {
         int root = p < P ? labels[b * (size_t)P + p] : -1;
-        unsigned int v = root >= 0 ? __float_as_uint(depth[b * (size_t)P + p]) : 0u;
-        unsigned long long active = __ballot(root >= 0);
-        while (active) {
-            int leader = __ffsll((long long)active) - 1;
-            int r0 = __shfl(root, leader, 64);
-            bool same = root == r0;
-            unsigned int m = wave_max_u32(same ? v : 0u);
-            if (lane == leader) atomicMax(&peak_bits[b * (size_t)P + r0], m);
-            active &= ~__ballot(same);
-        }
+        wave_root_max(root, root >= 0 ? __float_as_uint(depth[b * (size_t)P + p]) : 0u, peak_bits + b * (size_t)P, lane);
     }
 }
 __global__ void k_blob_apply(float *__restrict__ depth, const uint8_t *__restrict__ cand, const int32_t *__restrict__ labels,
