@@ -251,6 +251,14 @@ SIGNATURES = {
         "vistaf_pressure_destroy": (None, [vp]),
     },
 }
+# csrc/test_hooks_masks.h: the test entry points of the binary-mask chains, a table of their own beside the one above (load() applies both;
+# tests/test_mask_chains.py holds it against that header)
+MASK_CHAIN_SIGNATURES = {
+    "vistaf_ftp_test_mask_chain_fits": (ci, [ci, ci, ci, ci, ci, ci]),
+    "vistaf_ftp_test_bad_chain": (ci, [vp, vp, vp, vp, vp, ci, ci, vp, vp, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_reliable_chain": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_contact_chain": (ci, [vp, vp, vp, vp, cd, cd, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -269,7 +277,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in SIGNATURES.values():
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -13,9 +13,11 @@
 
 #include "host_util.hpp"
 #include "mask_rules.hpp"      // chamfer_ball
+#include "mask_bits.hpp"       // mask_chain_fits
 
 using namespace vf;
 #include "test_hooks.h"
+#include "test_hooks_masks.h"
 #ifdef VISTAF_DEBUG
 namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); void telea_window_mw_debug_dump(int B); void fit_debug_dump(); void unwrap_big_debug_dump(); void unwrap_batch_debug_dump(); }
 #endif
@@ -205,6 +207,113 @@ const int32_t *inpaint_dispatch(float *img, const uint8_t *bad, int range, const
 }
 InpaintBuffers inpaint_buffers(const vistaf_ftp_handle *hd) { return {hd->inpaint_scratch, hd->inpaint_cl_scratch, hd->inpaint_win_scratch, hd->big_only}; }
 
+// ---- the three binary-mask chains: what a session launches for them, and what the vistaf_ftp_test_*_chain hooks run on planes of the caller.
+// fused: the chain's bit of Tiers::fused_masks.  Each returns the tier taken -- 1 the one-launch kernel of k_maskchain.hip (frames
+// mask_chain_fits takes), 0 the separate kernels -- or a negative VISTAF_E_* code.
+int bad_chain_ops(int ksize, int iters) { return ksize > 1 ? std::max(0, iters) : 0; }
+int bad_mask_chain(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g, const RowSpanSE &se, int ksize,
+                   int iters, uint8_t *bad0, uint8_t *bad1, int *bad_count, bool fused, int B, int h, int w, hipStream_t st)
+{
+    const int P = h * w;
+    if (fused && mask_chain_fits(MCH_BAD, h, w, se, bad_chain_ops(ksize, iters))) {
+        launch_bad_chain(img, grad, valid, thr_hi, thr_g, se, bad_chain_ops(ksize, iters), bad1, bad_count, B, h, w, st);
+        return 1;
+    }
+    launch_bad_flags(img, grad, valid, thr_hi, thr_g, bad0, B, P, st);
+    uint8_t *src = bad0, *dst = bad1;
+    if (ksize > 1)
+        for (int it = 0; it < iters; it++) { launch_morph(src, dst, B, h, w, se, true, nullptr, nullptr, st); std::swap(src, dst); }
+    if (src != bad1) HIPCHK(hipMemcpyAsync(bad1, src, (size_t)B * P, hipMemcpyDeviceToDevice, st));
+    launch_count_u8(bad1, bad_count, B, P, st);
+    return 0;
+}
+
+struct ReliableScratch {        // planes [B, P] of the separate kernels (rel1, rel2: bytes; labels, area, rowdist: int32; dist: float), cc_best [B]
+    uint8_t *rel1, *rel2;
+    int32_t *labels, *area, *rowdist;
+    float *dist;
+    unsigned long long *cc_best;
+    uint16_t *morph_pre;
+};
+int reliable_mask_chain(const float *qual, const uint8_t *roi, const float *amp_thr, const RowSpanSE &se_close, int close_iters, int margin_px,
+                        const ReliableScratch &ws, bool chamfer_twopass, uint8_t *rel0, uint8_t *reliable, int *rel_count, int32_t *status, bool fused,
+                        int B, int h, int w, hipStream_t st)
+{
+    const int P = h * w;
+    // erode_by_distance (shape_ftp.py:368-377): keep a pixel when its 3x3-chamfer distance to the nearest zero pixel exceeds the margin,
+    // i.e. when no zero pixel lies in the chamfer ball of that radius: an erosion by the ball (image border: nothing to erode, as in
+    // cv::distanceTransform where the outside holds no zero pixel).  The ball is a symmetric row-span element: bit-plane kernel.
+    RowSpanSE ball;
+    const bool have_ball = margin_px > 0 && chamfer_ball((float)margin_px, &ball);
+    if (fused && mask_chain_fits(MCH_RELIABLE, h, w, se_close, 2 * std::max(0, close_iters), (float)margin_px)) {
+        launch_reliable_chain(qual, roi, amp_thr, se_close, std::max(0, close_iters), have_ball ? &ball : nullptr, ws.area, rel0, reliable, rel_count,
+                              status, B, h, w, st);
+        return 1;
+    }
+    launch_threshold_mask(qual, roi, amp_thr, rel0, B, P, st);
+    {
+        // MORPH_CLOSE with n iterations = n dilations then n erosions; the eroded-ROI mask applies to the result
+        uint8_t *src = rel0, *dst = ws.rel1;
+        if (close_iters >= 1 && 2 * close_iters <= 4) {
+            int ops[4];
+            for (int it = 0; it < close_iters; it++) { ops[it] = 1; ops[close_iters + it] = 0; }
+            launch_morph_seq(rel0, ws.rel1, ws.rel2, B, h, w, se_close, ops, 2 * close_iters, roi, nullptr, st, ws.morph_pre);
+            src = ws.rel1;
+        } else {
+            // rel1 / rel2 alternate; rel0 keeps the thresholded mask (the "rel0" intermediate)
+            for (int it = 0; it < 2 * close_iters; it++) {
+                const bool dil = it < close_iters;
+                launch_morph(src, dst, B, h, w, se_close, dil, it == 2 * close_iters - 1 ? roi : nullptr, nullptr, st, ws.morph_pre);
+                src = dst;
+                dst = dst == ws.rel1 ? ws.rel2 : ws.rel1;
+            }
+        }
+        launch_cc_label(src, ws.labels, B, h, w, st);
+        launch_cc_largest(ws.labels, ws.area, ws.cc_best, roi, ws.rel2, B, P, st);
+    }
+    if (margin_px > 0) {
+        if (have_ball) launch_morph(ws.rel2, reliable, B, h, w, ball, false, nullptr, nullptr, st, ws.morph_pre);
+        else {
+            launch_chamfer(ws.rel2, false, ws.rowdist, ws.dist, B, h, w, margin_px + 1, st, chamfer_twopass);
+            launch_erode_by_dist(ws.dist, ws.rel2, (float)margin_px, reliable, B, P, st);
+        }
+    } else HIPCHK(hipMemcpyAsync(reliable, ws.rel2, (size_t)B * P, hipMemcpyDeviceToDevice, st));
+    launch_count_u8(reliable, rel_count, B, P, st);
+    launch_mark_empty(rel_count, status, B, st);
+    return 0;
+}
+
+struct ContactScratchPlanes { uint8_t *contact, *tmp; uint16_t *morph_pre; };      // planes [B, P] of the separate kernels
+int contact_mask_chain(const float *resid, const uint8_t *reliable, const float *thr3, const int *rel_count, double min_frac, double max_frac,
+                       const RowSpanSE &se, int iters, const ContactScratchPlanes &ws, int *contact_count, float *thr_used, uint8_t *contact_d,
+                       uint8_t *background, int *bg_count, bool fused, int B, int h, int w, hipStream_t st)
+{
+    const int P = h * w;
+    if (fused && mask_chain_fits(MCH_CONTACT, h, w, se, std::max(0, iters))) {
+        launch_contact_chain(resid, reliable, thr3, rel_count, min_frac, max_frac, se, std::max(0, iters), contact_count, thr_used, contact_d,
+                             background, bg_count, B, h, w, st);
+        return 1;
+    }
+    launch_contact_mask(resid, reliable, thr3, rel_count, contact_count, min_frac, max_frac, ws.contact, thr_used, B, P, st);
+    // cv2.dilate with 0 iterations is a copy (contact is inside reliable already)
+    if (iters <= 0) HIPCHK(hipMemcpyAsync(contact_d, ws.contact, (size_t)B * P, hipMemcpyDeviceToDevice, st));
+    else if (iters <= 4) {
+        int ops[4] = {1, 1, 1, 1};
+        launch_morph_seq(ws.contact, contact_d, ws.tmp, B, h, w, se, ops, iters, nullptr, reliable, st, ws.morph_pre);
+    } else {
+        uint8_t *src = ws.contact, *dst = contact_d;
+        uint8_t *bufs[2] = {contact_d, ws.tmp};
+        for (int it = 0; it < iters; it++) {
+            dst = bufs[it & 1];
+            launch_morph(src, dst, B, h, w, se, true, nullptr, it == iters - 1 ? reliable : nullptr, st, ws.morph_pre);
+            src = dst;
+        }
+        if (src != contact_d) HIPCHK(hipMemcpyAsync(contact_d, src, (size_t)B * P, hipMemcpyDeviceToDevice, st));
+    }
+    launch_background(reliable, contact_d, rel_count, bg_count, background, B, P, st);
+    return 0;
+}
+
 // preprocessing shared by reference and deformed frames: frames -> iw (apodised, normalised) and mu
 // frames2 (pair mode, when the workspace holds 2 * nframes): a second set of nframes frames preprocessed in the SAME launches, as frames
 // [nframes, 2 * nframes) of every plane -- the one-wave-per-frame march then runs once over twice as many CUs instead of twice
@@ -216,17 +325,15 @@ void preprocess(vistaf_ftp_handle *hd, const void *frames, int format, int nfram
     launch_to_gray(frames, format, hd->img, nframes, P, st, w);
     if (frames2) launch_to_gray(frames2, format, hd->img + (size_t)nframes * P, nframes, P, st, w);
     const int B = frames2 ? 2 * nframes : nframes;
-    hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);
+    const bool fused_bad = c.bad_pixel_enable && (hd->tiers.fused_masks & MCH_BAD) &&
+                           mask_chain_fits(MCH_BAD, h, w, hd->se_bad, bad_chain_ops(c.bad_dilate_ksize, c.bad_dilate_iters));
+    if (!fused_bad) hipMemsetAsync(hd->bad_count, 0, sizeof(int) * B, st);      // (the fused chain stores the count)
     if (c.bad_pixel_enable) {
         launch_sobel_mag(hd->img, hd->grad, B, h, w, st);
         select(hd, hd->img, hd->valid, 0, nullptr, false, hd->req_hi, 1, hd->thr_hi, hd->cnt_valid, B, st);
         select(hd, hd->grad, hd->valid, 0, nullptr, false, hd->req_g, 1, hd->thr_g, nullptr, B, st);
-        launch_bad_flags(hd->img, hd->grad, hd->valid, hd->thr_hi, hd->thr_g, hd->bad0, B, P, st);
-        uint8_t *src = hd->bad0, *dst = hd->bad1;
-        if (c.bad_dilate_ksize > 1)
-            for (int it = 0; it < c.bad_dilate_iters; it++) { launch_morph(src, dst, B, h, w, hd->se_bad, true, nullptr, nullptr, st); std::swap(src, dst); }
-        if (src != hd->bad1) hipMemcpyAsync(hd->bad1, src, (size_t)B * P, hipMemcpyDeviceToDevice, st);
-        launch_count_u8(hd->bad1, hd->bad_count, B, P, st);
+        (void)bad_mask_chain(hd->img, hd->grad, hd->valid, hd->thr_hi, hd->thr_g, hd->se_bad, c.bad_dilate_ksize, c.bad_dilate_iters, hd->bad0, hd->bad1,
+                             hd->bad_count, fused_bad, B, h, w, st);
         inpaint_dispatch(hd->img, hd->bad1, std::min(100, std::max(1, cv_round((double)c.bad_inpaint_radius))),   // cv::inpaint clamps the radius
                          hd->tiers, true, inpaint_buffers(hd), hd->status, B, h, w, st, timed ? hd->ev[ST_INPAINT] : nullptr);
     } else if (timed) hipEventRecord(hd->ev[ST_INPAINT], st);
@@ -418,6 +525,7 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
     }
     hd->named["mu"] = {hd->mu, sizeof(float), true}; hd->named["thr_hi"] = {hd->thr_hi, sizeof(float), true}; hd->named["thr_g"] = {hd->thr_g, sizeof(float), true};
     hd->named["coef"] = {hd->coef, 6 * sizeof(float), true}; hd->named["thr3"] = {hd->thr3, 3 * sizeof(float), true};
+    hd->named["thr_used"] = {hd->thr_used, sizeof(float), true};
     hd->named["core_thr"] = {hd->core_thr, sizeof(float), true}; hd->named["core_med"] = {hd->core_med, sizeof(float), true};
     TRY(mem.upload(&hd->req_hi, std::vector<float>{q32_of(cfg->bad_intensity_percentile)}));
     TRY(mem.upload(&hd->req_g, std::vector<float>{q32_of(cfg->bad_gradient_percentile)}));
@@ -538,41 +646,13 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     else HIPCHK(hipMemcpyAsync(hd->quality, hd->prod, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     const float *qual = hd->quality;
     select(hd, qual, hd->roi, 0, nullptr, false, hd->req_amp, 1, hd->amp_thr, nullptr, B, st);
-    launch_threshold_mask(qual, hd->roi, hd->amp_thr, hd->rel0, B, P, st);
     {
-        // MORPH_CLOSE with n iterations = n dilations then n erosions; the eroded-ROI mask applies to the result
-        uint8_t *src = hd->rel0, *dst = hd->rel1;
-        if (c.valid_close_iters >= 1 && 2 * c.valid_close_iters <= 4) {
-            int ops[4];
-            for (int it = 0; it < c.valid_close_iters; it++) { ops[it] = 1; ops[c.valid_close_iters + it] = 0; }
-            launch_morph_seq(hd->rel0, hd->rel1, hd->rel2, B, h, w, hd->se_close, ops, 2 * c.valid_close_iters, hd->roi, nullptr, st, hd->morph_pre);
-            src = hd->rel1;
-        } else {
-            // rel1 / rel2 alternate; rel0 keeps the thresholded mask (the "rel0" intermediate)
-            for (int it = 0; it < 2 * c.valid_close_iters; it++) {
-                const bool dil = it < c.valid_close_iters;
-                launch_morph(src, dst, B, h, w, hd->se_close, dil, it == 2 * c.valid_close_iters - 1 ? hd->roi : nullptr, nullptr, st, hd->morph_pre);
-                src = dst;
-                dst = dst == hd->rel1 ? hd->rel2 : hd->rel1;
-            }
-        }
-        launch_cc_label(src, hd->labels, B, h, w, st);
-        launch_cc_largest(hd->labels, hd->area, hd->cc_best, hd->roi, hd->rel2, B, P, st);
+        const ReliableScratch ws = {hd->rel1, hd->rel2, hd->labels, hd->area, hd->rowdist, hd->dist, hd->cc_best, hd->morph_pre};
+        const int tier = reliable_mask_chain(qual, hd->roi, hd->amp_thr, hd->se_close, c.valid_close_iters, c.reliable_edge_margin_px, ws,
+                                             hd->tiers.chamfer_twopass != 0, hd->rel0, hd->reliable, hd->rel_count, hd->status,
+                                             (hd->tiers.fused_masks & MCH_RELIABLE) != 0, B, h, w, st);
+        if (tier < 0) return tier;
     }
-    if (c.reliable_edge_margin_px > 0) {
-        // erode_by_distance (shape_ftp.py:368-377): keep a pixel when its 3x3-chamfer distance to the nearest zero pixel exceeds the margin,
-        // i.e. when no zero pixel lies in the chamfer ball of that radius: an erosion by the ball (image border: nothing to erode, as in
-        // cv::distanceTransform where the outside holds no zero pixel).  The ball is a symmetric row-span element: bit-plane kernel.
-        RowSpanSE ball;
-        if (chamfer_ball((float)c.reliable_edge_margin_px, &ball))
-            launch_morph(hd->rel2, hd->reliable, B, h, w, ball, false, nullptr, nullptr, st, hd->morph_pre);
-        else {
-            launch_chamfer(hd->rel2, false, hd->rowdist, hd->dist, B, h, w, c.reliable_edge_margin_px + 1, st, hd->tiers.chamfer_twopass != 0);
-            launch_erode_by_dist(hd->dist, hd->rel2, (float)c.reliable_edge_margin_px, hd->reliable, B, P, st);
-        }
-    } else HIPCHK(hipMemcpyAsync(hd->reliable, hd->rel2, (size_t)B * P, hipMemcpyDeviceToDevice, st));
-    launch_count_u8(hd->reliable, hd->rel_count, B, P, st);
-    launch_mark_empty(hd->rel_count, hd->status, B, st);
 
     // ---- unwrap (shape_ftp.py:1702)
     if (timed) hipEventRecord(hd->ev[ST_UNWRAP_RANK], st);
@@ -588,27 +668,13 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
     launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
     select(hd, hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, st);
-    launch_contact_mask(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, hd->contact_count, c.min_contact_frac, c.max_contact_frac,
-                        hd->contact, hd->thr_used, B, P, st);
     {
-        // cv2.dilate with 0 iterations is a copy (contact is inside reliable already)
-        int iters = c.dilate_iters;
-        if (iters <= 0) HIPCHK(hipMemcpyAsync(hd->contact_d, hd->contact, (size_t)B * P, hipMemcpyDeviceToDevice, st));
-        else if (iters <= 4) {
-            int ops[4] = {1, 1, 1, 1};
-            launch_morph_seq(hd->contact, hd->contact_d, hd->cand, B, h, w, hd->se_contact, ops, iters, nullptr, hd->reliable, st, hd->morph_pre);   // cand is free until the blob filter
-        } else {
-            uint8_t *src = hd->contact, *dst = hd->contact_d;
-            uint8_t *bufs[2] = {hd->contact_d, hd->cand};
-            for (int it = 0; it < iters; it++) {
-                dst = bufs[it & 1];
-                launch_morph(src, dst, B, h, w, hd->se_contact, true, nullptr, it == iters - 1 ? hd->reliable : nullptr, st, hd->morph_pre);
-                src = dst;
-            }
-            if (src != hd->contact_d) HIPCHK(hipMemcpyAsync(hd->contact_d, src, (size_t)B * P, hipMemcpyDeviceToDevice, st));
-        }
+        const ContactScratchPlanes ws = {hd->contact, hd->cand, hd->morph_pre};      // cand is free until the blob filter
+        const int tier = contact_mask_chain(hd->resid0, hd->reliable, hd->thr3, hd->rel_count, c.min_contact_frac, c.max_contact_frac, hd->se_contact,
+                                            c.dilate_iters, ws, hd->contact_count, hd->thr_used, hd->contact_d, hd->background, hd->bg_count,
+                                            (hd->tiers.fused_masks & MCH_CONTACT) != 0, B, h, w, st);
+        if (tier < 0) return tier;
     }
-    launch_background(hd->reliable, hd->contact_d, hd->rel_count, hd->bg_count, hd->background, B, P, st);
     launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, chain_scratch(hd));
     select(hd, hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, st);
 
@@ -862,6 +928,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "select_resident") hd->tiers.select_resident = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
     else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
+    else if (n == "fused_masks" && value >= 0 && value <= 7) hd->tiers.fused_masks = value;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
     else return fail(VISTAF_E_INVALID, "unknown test hook or value: " + n);
     return 0;
@@ -1013,6 +1080,89 @@ int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const i
     HIPCHK(hipMalloc((void **)&peak_bits, (size_t)B * P * sizeof(unsigned int)));
     launch_blob_filter(depth_inout, cand, labels, peak_bits, (const unsigned int *)gmax, min_peak_mm, rel_frac, kept, B, P, (hipStream_t)stream);
     return hook_finish(peak_bits, nullptr, (hipStream_t)stream);
+}
+
+// ---- the three binary-mask chains (bad_mask_chain, reliable_mask_chain, contact_mask_chain above: the session's own functions) on
+// caller-supplied device planes
+namespace {
+// one allocation carved into regions of the given sizes (256-byte aligned)
+int hook_carve(const std::vector<size_t> &bytes, std::vector<void *> &out, void **base)
+{
+    size_t total = 0;
+    for (size_t b : bytes) total += (b + 255) & ~(size_t)255;
+    *base = nullptr;
+    HIPCHK(hipMalloc(base, total ? total : 256));
+    size_t off = 0;
+    out.clear();
+    for (size_t b : bytes) { out.push_back((char *)*base + off); off += (b + 255) & ~(size_t)255; }
+    return 0;
+}
+bool chain_shape_ok(int B, int h, int w, int ksize, int iters, int fused)
+{
+    return B >= 1 && h >= 1 && w >= 1 && (size_t)h * w <= 0x7fffffffull / 4 && ksize >= 1 && ksize <= 33 && iters >= 0 && iters <= 16 && (fused == 0 || fused == 1);
+}
+}  // namespace
+
+int vistaf_ftp_test_mask_chain_fits(int chain, int h, int w, int ksize, int nops, int margin_px)
+{
+    if (ksize < 1 || ksize > 33) return fail(VISTAF_E_INVALID, "bad argument");
+    RowSpanSE se;
+    TRY(make_se(ksize, &se, chain != MCH_CONTACT));
+    return mask_chain_fits(chain, h, w, se, nops, (float)margin_px) ? 1 : 0;
+}
+
+int vistaf_ftp_test_bad_chain(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g, int ksize, int iters,
+                              uint8_t *bad1, int *bad_count, int B, int h, int w, int fused, void *stream)
+{
+    if (!img || !grad || !valid || !thr_hi || !thr_g || !bad1 || !bad_count || !chain_shape_ok(B, h, w, ksize, iters, fused))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    RowSpanSE se;
+    TRY(make_se(ksize, &se));
+    void *base = nullptr;
+    std::vector<void *> r;
+    TRY(hook_carve({(size_t)B * h * w}, r, &base));
+    const int tier = bad_mask_chain(img, grad, valid, thr_hi, thr_g, se, ksize, iters, (uint8_t *)r[0], bad1, bad_count, fused != 0, B, h, w, (hipStream_t)stream);
+    const int rc = hook_finish(base, nullptr, (hipStream_t)stream);
+    return tier < 0 ? tier : rc ? rc : tier;
+}
+
+int vistaf_ftp_test_reliable_chain(const float *quality, const uint8_t *roi, const float *amp_thr, int close_ksize, int close_iters, int margin_px,
+                                   uint8_t *rel0, uint8_t *reliable, int *rel_count, int32_t *status, int B, int h, int w, int fused, void *stream)
+{
+    if (!quality || !roi || !amp_thr || !rel0 || !reliable || !rel_count || !status || !chain_shape_ok(B, h, w, close_ksize, close_iters, fused) ||
+        margin_px < 0 || margin_px > 1024)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    RowSpanSE se;
+    TRY(make_se(close_ksize, &se));
+    const size_t n = (size_t)B * h * w;
+    void *base = nullptr;
+    std::vector<void *> r;
+    TRY(hook_carve({n, n, n * 4, n * 4, n * 4, n * 4, (size_t)B * 8, n * 2}, r, &base));
+    const ReliableScratch ws = {(uint8_t *)r[0], (uint8_t *)r[1], (int32_t *)r[2], (int32_t *)r[3], (int32_t *)r[4], (float *)r[5], (unsigned long long *)r[6],
+                                (uint16_t *)r[7]};
+    const int tier = reliable_mask_chain(quality, roi, amp_thr, se, close_iters, margin_px, ws, false, rel0, reliable, rel_count, status, fused != 0, B, h, w,
+                                         (hipStream_t)stream);
+    const int rc = hook_finish(base, nullptr, (hipStream_t)stream);
+    return tier < 0 ? tier : rc ? rc : tier;
+}
+
+int vistaf_ftp_test_contact_chain(const float *resid, const uint8_t *reliable, const float *thr3, const int *rel_count, double min_frac, double max_frac,
+                                  int ksize, int iters, float *thr_used, uint8_t *contact_d, uint8_t *background, int *bg_count, int B, int h, int w,
+                                  int fused, void *stream)
+{
+    if (!resid || !reliable || !thr3 || !rel_count || !thr_used || !contact_d || !background || !bg_count || !chain_shape_ok(B, h, w, ksize, iters, fused))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    RowSpanSE se;
+    TRY(make_se(ksize, &se, false));
+    const size_t n = (size_t)B * h * w;
+    void *base = nullptr;
+    std::vector<void *> r;
+    TRY(hook_carve({n, n, n * 2, (size_t)B * sizeof(int)}, r, &base));
+    const ContactScratchPlanes ws = {(uint8_t *)r[0], (uint8_t *)r[1], (uint16_t *)r[2]};
+    const int tier = contact_mask_chain(resid, reliable, thr3, rel_count, min_frac, max_frac, se, iters, ws, (int *)r[3], thr_used, contact_d, background,
+                                        bg_count, fused != 0, B, h, w, (hipStream_t)stream);
+    const int rc = hook_finish(base, nullptr, (hipStream_t)stream);
+    return tier < 0 ? tier : rc ? rc : tier;
 }
 
 // ---- the unwrap launcher (consistency check, rank kernels, floods, replay / tree) on caller-supplied device planes

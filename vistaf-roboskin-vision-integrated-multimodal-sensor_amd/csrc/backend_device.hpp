@@ -48,23 +48,14 @@ __device__ inline void cc16_unite(uint16_t *L, int a, int b)
         b = (int)old;
     }
 }
-// Builds the forest of one frame's mask `mg` in L16 (all threads of a 1024-thread workgroup call it): on return every union is done and
+// Builds the forest of one frame's mask m in L16 (all threads of a 1024-thread workgroup call it): on return every union is done and
 // visible (the last statement is a barrier), cc16_find(L16, p) is the root -- the smallest pixel index -- of mask pixel p's 8-connected
-// component, and non-mask pixels hold 0xffff.  Returns the mask to test pixels with: the LDS copy for MLDS (every neighbour test is an
-// LDS read), else mg.
-template <bool MLDS>
-__device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, int h, int w, uint16_t *L16)
+// component, and non-mask pixels hold 0xffff.  m is indexed by pixel: a byte plane (in LDS or in memory), or the BitMask of a bit plane
+// in LDS.  m must be visible to the workgroup on entry.
+template <typename Mask>
+__device__ inline void cc_lds_forest(Mask m, int h, int w, uint16_t *L16)
 {
     const int P = h * w;
-    uint8_t *ml = (uint8_t *)(L16 + ((P + 2 + 7) & ~7));
-    if (MLDS) {
-        for (int p = threadIdx.x * 4; p < P; p += blockDim.x * 4) {
-            if (p + 3 < P && ((((uintptr_t)mg) & 3) == 0)) *(uint32_t *)(ml + p) = *(const uint32_t *)(mg + p);
-            else for (int k = 0; k < 4 && p + k < P; k++) ml[p + k] = mg[p + k];
-        }
-        __syncthreads();
-    }
-    const uint8_t *m = MLDS ? (const uint8_t *)ml : mg;
     // Every pixel starts at the left end of its horizontal run (row_last_zero: 16 waves, one row at a time each), so a run is one tree
     // from the start and only the contacts between runs of adjacent rows are left to unite -- a few hundred unions per frame instead of
     // four per pixel.  Roots are minimum pixel indices either way: same labels.
@@ -88,7 +79,36 @@ __device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, in
         cc_row_contacts(m, p, x, y, w, x > 0 && m[p - 1], [L16](int a, int b) { cc16_unite(L16, a, b); });
     }
     __syncthreads();
+}
+// The forest of the byte plane mg.  Returns the mask to test pixels with: for MLDS the LDS copy staged behind the forest (every neighbour
+// test is an LDS read), else mg.
+template <bool MLDS>
+__device__ inline const uint8_t *cc_lds_build(const uint8_t *__restrict__ mg, int h, int w, uint16_t *L16)
+{
+    const int P = h * w;
+    uint8_t *ml = (uint8_t *)(L16 + ((P + 2 + 7) & ~7));
+    if (MLDS) {
+        for (int p = threadIdx.x * 4; p < P; p += blockDim.x * 4) {
+            if (p + 3 < P && ((((uintptr_t)mg) & 3) == 0)) *(uint32_t *)(ml + p) = *(const uint32_t *)(mg + p);
+            else for (int k = 0; k < 4 && p + k < P; k++) ml[p + k] = mg[p + k];
+        }
+        __syncthreads();
+    }
+    const uint8_t *m = MLDS ? (const uint8_t *)ml : mg;
+    cc_lds_forest(m, h, w, L16);
     return m;
+}
+// Pixel p of the mask points at its root for good: a walk that writes nothing on its way, so when every thread of the workgroup does this
+// for its pixels between two barriers the only stores are roots -- no path-halving store of another thread's find can land on L16[p]
+// afterwards and leave an inner node there (a walk through p meanwhile reads its old parent or the root).  Returns the root.  This is the
+// walk of k_backend_fused's first step, which keeps its own three lines: routed through this function the compiler rotated that kernel's
+// loop differently and the kernel measured 210.2 us against 205.0 us (profiles/README.md, the mask chains).
+__device__ inline int cc16_settle(uint16_t *L16, int p)
+{
+    int r = p;
+    for (int q = ((volatile uint16_t *)L16)[r]; q != r; q = ((volatile uint16_t *)L16)[r]) r = q;
+    L16[p] = (uint16_t)r;
+    return r;
 }
 
 // blob filter (shape_ftp.py:1247-1250): the threshold is formed in float64 (Python floats); `peaks >= thr` then compares a float32 array with

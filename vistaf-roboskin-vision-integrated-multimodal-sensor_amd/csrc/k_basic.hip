@@ -8,6 +8,7 @@
 #include "kernels.hpp"
 #include "gauss_tile.hpp"
 #include "pixel_ops.hpp"
+#include "mask_bits.hpp"
 
 namespace vf {
 
@@ -69,7 +70,7 @@ __global__ void k_bad_flags(const float *__restrict__ img, const float *__restri
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    bad[i] = (uint8_t)(valid[p] && ((img[i] >= thr_hi[b]) || (grad[i] >= thr_g[b])));
+    bad[i] = (uint8_t)bad_flag_px(valid[p], img[i], grad[i], thr_hi[b], thr_g[b]);
 }
 
 void launch_bad_flags(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g,
@@ -173,14 +174,7 @@ __global__ void k_morph_prefix(const uint16_t *__restrict__ inc, uint8_t *__rest
 // packs the mask into 64-bit words with ballots (coalesced byte loads), dilates in LDS with word shifts -- a
 // 15x15 element costs a few hundred 64-bit ops per output word -- and unpacks.  Erosion is the dual: complement inside
 // the image, dilate, complement (out-of-image pixels never erode: cv::morphologyDefaultBorderValue).
-constexpr int MB_T = 1024;      // 16 waves: packing / unpacking a row is a global-memory round trip, so rows in flight are what counts
-constexpr int MB_RB = 2;        // rows per wave and iteration (MB_RB * 4 independent byte loads in flight per lane)
-constexpr int MB_MAXOPS = 4;
-struct MorphSeq {               // up to MB_MAXOPS operations applied back to back on the packed plane (close = dilate, erode; n-fold dilate)
-    int n;
-    int dilate[MB_MAXOPS];
-    RowSpanSE se[MB_MAXOPS];
-};
+// The steps themselves (mb_pack, mb_morph_step, mb_unpack) and morph_bits_ok are in mask_bits.hpp, shared with the fused mask chains.
 __global__ __launch_bounds__(MB_T) void k_morph_bits(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int h, int w, MorphSeq seq,
                                                      const uint8_t *__restrict__ and_static, const uint8_t *__restrict__ and_frame)
 {
@@ -188,88 +182,13 @@ __global__ __launch_bounds__(MB_T) void k_morph_bits(const uint8_t *__restrict__
     const int W64 = (w + 63) >> 6, nw = h * W64;
     unsigned long long *A = mb_lds, *O = mb_lds + nw;
     const size_t b = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const uint8_t *s = src + b * (size_t)h * w;
-    // pack: the byte loads of MB_RB rows are independent and issued together
-    for (int y0 = wid * MB_RB; y0 < h; y0 += (MB_T / 64) * MB_RB)
-        for (int j0 = 0; j0 < W64; j0 += 4) {
-            uint8_t px[MB_RB][4];
-#pragma unroll
-            for (int rr = 0; rr < MB_RB; rr++)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int y = y0 + rr, x = (j0 + u) * 64 + lane;
-                    px[rr][u] = (y < h && j0 + u < W64 && x < w) ? s[(size_t)y * w + x] : (uint8_t)0;
-                }
-#pragma unroll
-            for (int rr = 0; rr < MB_RB; rr++)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const unsigned long long word = __ballot(px[rr][u] != 0);
-                    if (lane == 0 && y0 + rr < h && j0 + u < W64) A[(y0 + rr) * W64 + j0 + u] = word;
-                }
-        }
+    mb_pack(A, h, w, [s, w](int y, int x) { return s[(size_t)y * w + x]; });
     __syncthreads();
-    const unsigned long long last_valid = (w & 63) ? ((1ull << (w & 63)) - 1ull) : ~0ull;     // columns of the last word that exist
-    for (int op = 0; op < seq.n; op++) {
-        const RowSpanSE &se = seq.se[op];
-        const bool dil = seq.dilate[op] != 0;
-        if (!dil) {                                             // erosion = complement inside the image, dilate, complement
-            for (int t = tid; t < nw; t += MB_T) { const int j = t % W64; A[t] = ~A[t] & (j == W64 - 1 ? last_valid : ~0ull); }
-            __syncthreads();
-        }
-        const int r = se.k / 2;
-        for (int t = tid; t < nw; t += MB_T) {
-            const int y = t / W64, j = t - y * W64;
-            unsigned long long acc = 0ull;
-            for (int i = 0; i < se.k; i++) {
-                const int yy = y + i - r, a = se.hi[i];
-                if (yy < 0 || yy >= h || a < 0) continue;
-                const unsigned long long *row = A + yy * W64;
-                const unsigned long long wc = row[j], wl = j > 0 ? row[j - 1] : 0ull, wr = j < W64 - 1 ? row[j + 1] : 0ull;
-                unsigned long long m = wc;
-                for (int dd = 1; dd <= a; dd++) m |= (wc >> dd) | (wr << (64 - dd)) | (wc << dd) | (wl >> (64 - dd));
-                acc |= m;
-            }
-            const unsigned long long valid = j == W64 - 1 ? last_valid : ~0ull;
-            O[t] = dil ? (acc & valid) : (~acc & valid);
-        }
-        __syncthreads();
-        unsigned long long *tmp = A; A = O; O = tmp;
-    }
-    // unpack (A holds the result); the optional AND masks of a row are loaded together
-    uint8_t *o = dst + b * (size_t)h * w;
-    for (int y0 = wid * MB_RB; y0 < h; y0 += (MB_T / 64) * MB_RB)
-        for (int j0 = 0; j0 < W64; j0 += 4) {
-            uint8_t ms[MB_RB][4], mf[MB_RB][4];
-#pragma unroll
-            for (int rr = 0; rr < MB_RB; rr++)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int y = y0 + rr, x = (j0 + u) * 64 + lane;
-                    const size_t p = (y < h && j0 + u < W64 && x < w) ? (size_t)y * w + x : 0;
-                    ms[rr][u] = and_static ? and_static[p] : (uint8_t)1;
-                    mf[rr][u] = and_frame ? and_frame[b * (size_t)h * w + p] : (uint8_t)1;
-                }
-#pragma unroll
-            for (int rr = 0; rr < MB_RB; rr++)
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const int y = y0 + rr, x = (j0 + u) * 64 + lane;
-                    if (y >= h || j0 + u >= W64 || x >= w) continue;
-                    const int v = (int)((A[y * W64 + j0 + u] >> lane) & 1ull);
-                    o[(size_t)y * w + x] = (uint8_t)(v && ms[rr][u] && mf[rr][u]);
-                }
-        }
-}
-
-static bool morph_bits_ok(const RowSpanSE &se, int h, int w)
-{
-    for (int i = 0; i < se.k; i++) {
-        if (se.lo[i] > se.hi[i]) { if (se.hi[i] >= 0) return false; continue; }      // empty rows must read hi < 0
-        if (se.lo[i] != -se.hi[i] || se.hi[i] > 63) return false;
-    }
-    return (size_t)h * ((w + 63) >> 6) * 16 <= 64 * 1024;
+    const unsigned long long last_valid = mb_last_valid(w);
+    for (int op = 0; op < seq.n; op++) mb_morph_step(A, O, h, W64, seq.se[op], seq.dilate[op] != 0, last_valid);
+    // unpack (A holds the result)
+    mb_unpack(A, dst + b * (size_t)h * w, h, w, and_static, and_frame ? and_frame + b * (size_t)h * w : nullptr);
 }
 
 void launch_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, const RowSpanSE &se, bool dilate,

@@ -26,8 +26,7 @@ __global__ void k_threshold_mask(const float *__restrict__ q, const uint8_t *__r
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     size_t b = blockIdx.y;
     if (p >= P) return;
-    float v = q[b * (size_t)P + p];
-    out[b * (size_t)P + p] = (uint8_t)(roi[p] && finitef(v) && v >= thr[b]);
+    out[b * (size_t)P + p] = (uint8_t)quality_mask_px(roi[p], q[b * (size_t)P + p], thr[b]);
 }
 void launch_threshold_mask(const float *q, const uint8_t *roi, const float *thr, uint8_t *out, int B, int P, hipStream_t st)
 {

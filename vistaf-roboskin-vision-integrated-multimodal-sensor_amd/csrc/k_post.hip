@@ -14,13 +14,10 @@ __global__ void k_contact_count(const float *__restrict__ res, const uint8_t *__
 {
     __shared__ int scratch[16];
     size_t b = blockIdx.y;
-    float thr = thr3[b * 3];
-    if (!finitef(thr)) thr = thr3[b * 3 + 1];
+    const float thr = contact_first_thr(thr3 + b * 3);
     int c = 0;
-    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x) {
-        float v = fabsf(res[b * (size_t)P + p]);
-        c += (reliable[b * (size_t)P + p] && finitef(v) && v >= thr);
-    }
+    for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < P; p += gridDim.x * blockDim.x)
+        c += contact_px(reliable[b * (size_t)P + p], res[b * (size_t)P + p], thr);
     c = block_sum<int>(c, scratch);
     if (threadIdx.x == 0 && c) atomicAdd(&counts[b], c);
 }
@@ -31,17 +28,10 @@ __global__ void k_contact_mask(const float *__restrict__ res, const uint8_t *__r
 {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     size_t b = blockIdx.y;
-    float thr = thr3[b * 3];
-    if (!finitef(thr)) thr = thr3[b * 3 + 1];
-    int rc = rel_count[b];
-    // float64 fraction against the float64 constants, as upstream's NumPy compares them (a bound narrowed to float32 moves the boundary)
-    double frac = (double)contact_count[b] / (double)(rc > 1 ? rc : 1);
-    if (frac < min_frac) { float t2 = thr3[b * 3 + 1]; if (finitef(t2)) thr = t2; }
-    else if (frac > max_frac) { float t2 = thr3[b * 3 + 2]; if (finitef(t2)) thr = t2; }
+    const float thr = contact_used_thr(thr3 + b * 3, contact_count[b], rel_count[b], min_frac, max_frac);
     if (p == 0) thr_used[b] = thr;
     if (p >= P) return;
-    float v = fabsf(res[b * (size_t)P + p]);
-    contact[b * (size_t)P + p] = (uint8_t)(reliable[b * (size_t)P + p] && finitef(v) && v >= thr);
+    contact[b * (size_t)P + p] = (uint8_t)contact_px(reliable[b * (size_t)P + p], res[b * (size_t)P + p], thr);
 }
 
 void launch_contact_mask(const float *res, const uint8_t *reliable, const float *thr3, const int *rel_count, int *contact_count,
@@ -66,8 +56,7 @@ __global__ void k_background_fix(const uint8_t *__restrict__ reliable, const int
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     size_t b = blockIdx.y;
     if (p >= P) return;
-    int limit = (int)(0.15 * (double)rel_count[b]);
-    if (bg_count[b] < limit) bg[b * (size_t)P + p] = reliable[b * (size_t)P + p];
+    if (background_falls_back(bg_count[b], rel_count[b])) bg[b * (size_t)P + p] = reliable[b * (size_t)P + p];
 }
 void launch_background(const uint8_t *reliable, const uint8_t *contact_d, const int *rel_count, int *bg_count, uint8_t *background,
                        int B, int P, hipStream_t st)
@@ -381,7 +370,7 @@ void launch_fill_scalars(double *scalars, int nscal, const int *rel_count, const
 __global__ void k_mark_empty(const int *__restrict__ rel_count, int32_t *__restrict__ status, int B)
 {
     int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B && rel_count[b] == 0 && status[b] == 0) status[b] = 1;
+    if (b < B && marks_empty(rel_count[b], status[b])) status[b] = 1;
 }
 void launch_mark_empty(const int *rel_count, int32_t *status, int B, hipStream_t st)
 {

@@ -24,6 +24,7 @@ struct Tiers {
     int telea_mw = 1;           // 1: the 16-wave window kernel (ordering pass + dataflow fills, k_inpaint_mw.hip) as first tier, single-wave tiers behind it; 0: single-wave tiers only
     int fused_backend = 1;      // 1: frames whose label forest fits LDS run blob filter, force tail and output copy in one launch per batch (k_backend.hip); 0: the separate kernels
     int select_resident = 1;    // 1: the exact selections of planes of up to 65536 pixels keep their keys in registers (k_select_resident) and the core threshold and core median share a launch; 0: the streaming k_select, one launch per selection
+    int fused_masks = 7;        // bits 1 / 2 / 4: the bad-pixel, reliable and contact mask chain of frames mask_chain_fits takes run as one launch each, bit planes in LDS (k_maskchain.hip); 0: the separate kernels
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
 
@@ -316,6 +317,20 @@ void launch_tm_mask_nan(const float *m, const uint8_t *keep, float *out, size_t 
 size_t tstats_scratch_bytes(int h, int w, ScratchRec *rec = nullptr);
 bool tstats_needs_big_scratch(int h, int w);
 void launch_tstats(const float *map, const uint8_t *valid, int h, int w, void *scratch, void *big_scratch, double *out, hipStream_t st);
+
+// ---- k_maskchain.hip (the three binary-mask chains of frames mask_chain_fits takes, mask_bits.hpp: the fused_masks tier) -------------------
+// bad1 = iters dilations by se of valid & (img >= thr_hi | grad >= thr_g); bad_count[b] its pixels (a plain store)
+void launch_bad_chain(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g, const RowSpanSE &se,
+                      int iters, uint8_t *bad1, int *bad_count, int B, int h, int w, hipStream_t st);
+// rel0 = roi & finite(q) & (q >= amp_thr); reliable = erosion by `ball` (null: none) of roi & the largest component of roi & closing of rel0;
+// rel_count[b] its pixels; status[b] = 1 where that is 0 and the status was 0.  area: a [B, P] plane, written at component roots only
+void launch_reliable_chain(const float *quality, const uint8_t *roi, const float *amp_thr, const RowSpanSE &se_close, int close_iters,
+                           const RowSpanSE *ball, int32_t *area, uint8_t *rel0, uint8_t *reliable, int *rel_count, int32_t *status, int B, int h,
+                           int w, hipStream_t st);
+// launch_contact_mask, iters dilations by se & reliable -> contact_d, launch_background
+void launch_contact_chain(const float *res, const uint8_t *reliable, const float *thr3, const int *rel_count, double min_frac, double max_frac,
+                          const RowSpanSE &se, int iters, int *contact_count, float *thr_used, uint8_t *contact_d, uint8_t *background,
+                          int *bg_count, int B, int h, int w, hipStream_t st);
 
 // ---- k_backend.hip (blob filter, force tail and output copy of LDS-sized frames in one launch: the fused_backend tier) -------------------
 bool backend_fused_fits(int h, int w);      // the frames launch_cc_label labels with the mask staged in LDS, less the tail's reduction scratch

@@ -23,9 +23,10 @@ __host__ __device__ inline size_t cc_lds_bytes(int P) { return cc_lds_forest_byt
 // the runs of row y - 1 that touch it: a pixel whose left neighbour is set leaves the run above-left / above to that neighbour, and the
 // pixel above-right starts a new contact only where the pixel above is clear -- a couple of unions per run instead of three per pixel.
 // left: x > 0 && m[p - 1], from the caller (k_cc_merge has it for its own union, and a second read of it behind that union's atomics
-// cost the kernel two registers and 4 % of its time).  unite(a, b) joins the components of pixels a and b.
-template <typename Unite>
-__host__ __device__ inline void cc_row_contacts(const uint8_t *m, int p, int x, int y, int w, bool left, Unite unite)
+// cost the kernel two registers and 4 % of its time).  unite(a, b) joins the components of pixels a and b.  m is the byte plane, or anything
+// indexed like it (BitMask of mask_bits.hpp: the bit plane in LDS).
+template <typename Mask, typename Unite>
+__host__ __device__ inline void cc_row_contacts(Mask m, int p, int x, int y, int w, bool left, Unite unite)
 {
     if (y == 0) return;
     const bool ul = x > 0 && m[p - w - 1], up = m[p - w] != 0, ur = x < w - 1 && m[p - w + 1];

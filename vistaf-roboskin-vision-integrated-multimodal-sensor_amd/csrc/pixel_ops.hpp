@@ -1,5 +1,6 @@
-// Per-pixel expressions of the element-wise passes around the short Gaussian blurs.  Each one is called by its own streaming kernel
-// (k_basic.hip, k_post.hip) and by the fused blur kernels (k_blurchain.hip), so both paths execute the same operations in the same order.
+// Per-pixel expressions of the element-wise passes around the short Gaussian blurs and of the binary-mask chains.  Each one is called by its
+// own streaming kernel (k_basic.hip, k_cc_dist.hip, k_post.hip) and by the fused kernels (k_blurchain.hip, k_maskchain.hip), so both paths
+// execute the same operations in the same order.
 // The explicit __f*_rn keep every rounding where the reference has it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -70,5 +71,40 @@ __device__ inline bool to_mm_px(float hgt, bool roi, const Curve &curve, int use
     depth = d;
     return roi && finitef(d) && d > 0.0f;
 }
+
+// ---- the binary-mask chains (k_maskchain.hip and the streaming kernels it replaces) ------------------------------------------------------
+// bad pixel (shape_ftp.py:638-639)
+__device__ inline bool bad_flag_px(uint8_t valid, float img, float grad, float thr_hi, float thr_g) { return valid && ((img >= thr_hi) || (grad >= thr_g)); }
+
+// quality threshold (shape_ftp.py:753); a NaN threshold leaves no pixel
+__device__ inline bool quality_mask_px(uint8_t roi, float q, float thr) { return roi && finitef(q) && q >= thr; }
+
+// contact pixel (shape_ftp.py:1719-1732)
+__device__ inline bool contact_px(uint8_t reliable, float res, float thr)
+{
+    const float v = fabsf(res);
+    return reliable && finitef(v) && v >= thr;
+}
+// the threshold the contact count is taken with: the first percentile, the second when the first is not finite.  t3: the frame's three.
+__device__ inline float contact_first_thr(const float *__restrict__ t3)
+{
+    float thr = t3[0];
+    if (!finitef(thr)) thr = t3[1];
+    return thr;
+}
+// the threshold the mask is formed with: float64 fraction against the float64 constants, as upstream's NumPy compares them (a bound narrowed
+// to float32 moves the boundary)
+__device__ inline float contact_used_thr(const float *__restrict__ t3, int contact_count, int rel_count, double min_frac, double max_frac)
+{
+    float thr = contact_first_thr(t3);
+    const double frac = (double)contact_count / (double)(rel_count > 1 ? rel_count : 1);
+    if (frac < min_frac) { const float t2 = t3[1]; if (finitef(t2)) thr = t2; }
+    else if (frac > max_frac) { const float t2 = t3[2]; if (finitef(t2)) thr = t2; }
+    return thr;
+}
+// background = reliable & ~contact_d falls back to reliable below 15 % of it (shape_ftp.py:1738-1741)
+__device__ inline bool background_falls_back(int bg_count, int rel_count) { return bg_count < (int)(0.15 * (double)rel_count); }
+// frames whose reliable mask is empty produce the upstream "return None" status, unless they carry a status already
+__device__ inline bool marks_empty(int rel_count, int32_t status) { return rel_count == 0 && status == 0; }
 
 }  // namespace vf

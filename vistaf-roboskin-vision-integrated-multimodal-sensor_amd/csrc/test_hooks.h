@@ -6,7 +6,7 @@
  * _blob_filter (mask topology), _unwrap (phase unwrap), _inpaint (the Telea tiers), _top_peaks, _carrier_choose, _build_tables,
  * _build_full_tables, _dft_forward, _dft_inverse (demodulation: peak search, carrier choice, twiddle tables, the float64 GEMM stages);
  * vistaf_ftp_test_scratch_regions (scratch layouts) and vistaf_ftp_test_dft_full_mag (the full-spectrum magnitude, asynchronous: also a timing
- * aid). */
+ * aid).  The entry points of the three binary-mask chains (vistaf_ftp_test_bad_chain and friends) are declared in test_hooks_masks.h. */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
@@ -37,6 +37,10 @@ extern "C" {
  *                      filter, the force tail and the copy to the caller's planes in one launch (k_backend.hip); 0 the separate kernels
  *                      (labels, peak plane clear, peaks, decision, tail, copy).  Same bits either way.  With stage timing on, the fused launch is charged
  *                      to the mm / blob stage as a whole (tail and copy included); the tail stage then holds k_fill_scalars and the two copies only
+ *       "fused_masks"  7 (default) bits 1 / 2 / 4: the bad-pixel, the reliable and the contact / background mask chain of frames whose bit planes (and,
+ *                      for the reliable mask, label forest) fit LDS -- mask_chain_fits of mask_bits.hpp -- run as one launch each (k_maskchain.hip) and
+ *                      the planes between their steps (bad0, rel1, rel2, contact, the reliable stage's labels; area off the roots) are not written;
+ *                      a cleared bit, or a frame or configuration the tier does not take: the separate kernels.  Same bits either way
  *       "select_resident" 1 (default) the exact selections of planes of up to 65536 pixels run k_select_resident (every element loaded once, its key
  *                      kept in a register for all sweeps) and the core threshold and the core median below it share one chained launch; 0 the
  *                      streaming k_select, one launch per selection (two for the core pair).  Same bits either way
