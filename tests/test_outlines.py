@@ -1,0 +1,441 @@
+"""The contact outline read-out (include_ext/vistaf_outline.h): boundary loops, holes, corner polylines, hull and caliper box of every contact.
+
+The reference is tests/outline_helpers.py: one walker that follows each loop edge by edge, the hull over all corners, the calipers as the header
+spells them.  On the CPU: the walker's own properties and a brute-force restatement of hull and calipers, the header against `_lib`'s
+tables, the refusals of the C ABI (they come before any HIP call) and the writers.  On the GPU: the integer fields, offsets and vertices
+must equal the walker's exactly; the doubles built from *, / and sqrt must have its bits; the three direction fields are held to 64 ulps of
+their scale (pi / 2), compared as directions (modulo pi), because the device atan2 is not NumPy's."""
+import csv
+import ctypes
+import os
+import re
+
+import numpy as np
+import pytest
+
+import contacts_helpers as CH
+import outline_helpers as OH
+from outline_helpers import O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG_NAME = "vistaf-roboskin-vision-integrated-multimodal-sensor_amd"
+G = os.path.join(ROOT, "tests", "golden")
+HEADER = os.path.join(ROOT, "include_ext", "vistaf_outline.h")
+ANGLE_BAR = 64.0 * 2.0 ** -52 * (np.pi / 2)
+E_INVALID = -1
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------ CPU
+def _random_masks(n, seed, top=9):
+    rng = np.random.default_rng(seed)
+    for _ in range(n):
+        h, w = rng.integers(1, top), rng.integers(1, top)
+        yield rng.random((h, w)) < rng.choice([0.3, 0.5, 0.7, 0.9])
+
+
+def test_tracer_properties_on_random_masks():
+    for m in _random_masks(300, 0):
+        Ls = OH.loops(m)
+        E = OH.edges(m)
+        assert sorted(e for L in Ls for e in L) == sorted(E)                                   # every edge on exactly one closed loop
+        a = [OH.area2(L) for L in Ls]
+        assert all(v != 0 and v % 2 == 0 for v in a)
+        assert sum(a) // 2 == m.sum()
+        assert sum(v > 0 for v in a) == OH.components(m, True)
+        assert sum(v < 0 for v in a) == OH.components(np.pad(~m, 1, constant_values=True), False) - 1
+        for L, v in zip(Ls, a):
+            assert L[0] == min(L, key=lambda t: (t[1], t[0], t[2]))
+            if v > 0:
+                assert L[0][2] == 0 and L[-1][2] != 0 and OH.corners(L)[0] == L[0][:2]
+
+
+def test_checkerboard_patch_numbers():
+    rec, cs = OH.measure_mask(np.indices((6, 6)).sum(0) % 2 == 0, 1.0)
+    assert [rec[O[n]] for n in ("pixels", "pieces", "holes", "edges", "enclosed_pixels")] == [18, 1, 8, 40, 26]
+    assert len(cs) == rec[O["corners"]] == 40 and cs[0] == (0, 0)
+
+
+def test_hull_and_calipers_agree_with_brute_force():
+    n = 0
+    for m in _random_masks(120, 1):
+        if not m.any():
+            continue
+        Ls = OH.loops(m)
+        pts = [c for L in Ls if OH.area2(L) > 0 for c in OH.corners(L)]
+        H = OH.hull(pts)
+        squares = [(x + dx, y + dy) for y, x in zip(*np.nonzero(m)) for dx in (0, 1) for dy in (0, 1)]
+        assert set(H) == OH.hull_brute(pts) == OH.hull_brute(squares)                           # corners of the loops = the union of the squares
+        k = len(H)
+        assert k >= 4 and H[0] == min(H, key=lambda p: (p[1], p[0]))
+        assert all(OH.cross(H[i], H[(i + 1) % k], H[(i + 2) % k]) > 0 for i in range(k))         # strictly convex, positive shoelace
+        s = 0.37
+        c, b = OH.calipers(H, s), OH.calipers_brute(H, s)
+        assert abs(c[0] - b["max_feret"]) <= 1e-12 * b["max_feret"] and abs(c[2] - b["min_feret"]) <= 1e-12 * b["min_feret"]
+        assert abs(c[5] * c[6] - b["area"] * s * s) <= 1e-12 * b["area"] and c[5] >= c[6] >= c[2] * (1 - 1e-15)
+        # the box centre and direction describe a rectangle that holds every hull vertex and touches them on all four sides
+        u = np.array([np.cos(c[7]), np.sin(c[7])])
+        P = (np.array(H, float) - np.array([c[3], c[4]])) @ np.array([u, [-u[1], u[0]]]).T * s
+        assert np.allclose(np.abs(P).max(0), [c[5] / 2, c[6] / 2], rtol=0, atol=1e-9)
+        assert -np.pi / 2 < c[7] <= np.pi / 2 and -np.pi / 2 < c[1] <= np.pi / 2
+        n += 1
+    assert n > 100
+
+
+def test_reference_capacity_rule_and_rows():
+    names, c = OH.hand_made(24, 32)
+    b = names.index("borders_and_corners")
+    full, verts, offs = OH.reference(c["index"], c["tab"], c["count"], c["mpp"], 64)
+    assert list(offs[b]) == list(range(0, 33, 4)) and len(verts[b]) == 32
+    cut, verts2, offs2 = OH.reference(c["index"], c["tab"], c["count"], c["mpp"], 10)
+    assert list(offs2[b]) == [0, 4, 8] + [8] * 6 and verts2[b] == verts[b][:8]
+    assert list(cut[b, :, O["corners_written"]]) == [4, 4, 0, 0, 0, 0, 0, 0] and np.array_equal(cut[b, :, O["corners"]], full[b, :, O["corners"]])
+    none = OH.reference(c["index"], c["tab"], c["count"], c["mpp"], None)[0]
+    assert (none[..., O["corners_written"]][~np.isnan(none[..., 0])] == 0).all()
+    t = names.index("two_pieces_and_empty")
+    assert full[t, 0, O["pieces"]] == 2 and full[t, 1, O["pixels"]] == 0 and np.isnan(full[t, 1, O["perimeter_mm"]])
+    assert full[t, 2, O["pixels"]] == 5 * 9 and full[t, 3, O["pixels"]] == 6 * 5                   # the box rules, in and out of the frame
+    assert np.isnan(full[names.index("count_zero")]).all() and not np.isnan(full[names.index("count_above_K"), :, 0]).any()
+
+
+def test_outline_names_and_signatures_follow_the_header(pkg):
+    hdr = open(HEADER).read()
+    idx = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define VISTAF_OUTLINE_(\w+)\s+(\d+)\b", hdr)}
+    assert sorted(idx.values()) == list(range(20))
+    for name, i in idx.items():
+        assert pkg.OUTLINE_NAMES[i] == name
+    assert list(pkg.OUTLINE_NAMES) == list(pkg._lib.OUTLINE_NAMES) == list(pkg.writers.OUTLINE_FIELDS) == list(OH.FIELDS)
+    assert int(re.search(r"#define VISTAF_NOUTLINE\s+(\d+)", hdr).group(1)) == pkg._lib.NOUTLINE == OH.NOUTLINE == 24
+    for name in ("outline", "OUTLINE_NAMES", "contact_outlines", "outlines_table", "write_outlines_csv", "outline_frame_record"):
+        assert name in pkg.__all__ and hasattr(pkg, name)
+    # the header is outside include/*.h, whose prototype count tests/test_abi_surface.py pins; the rule of that test, for these functions
+    text = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).split("\n") if not ln.lstrip().startswith("#"))
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vistaf_\w+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos
+        protos[name] = (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
+    table = pkg._lib.OUTLINE_SIGNATURES
+    assert sorted(protos) == sorted(table) == ["vistaf_outline_measure", "vistaf_outline_workspace_bytes"]
+    assert not set(table) & {n for g in pkg._lib.SIGNATURES.values() for n in g}
+    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "int64_t": ctypes.c_int64,
+               "size_t": ctypes.c_size_t}
+
+    def matches(c_text, ctype):
+        if "*" in c_text:
+            return ctype in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int)))
+        words = [w for w in re.findall(r"\w+", c_text) if w not in ("const", "unsigned", "signed")]
+        kind = next((w for w in words if w in scalars), None)
+        assert kind is not None, c_text
+        return ctype is scalars[kind]
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        assert len(argtypes) == len(params), name
+        for i, (p, a) in enumerate(zip(params, argtypes)):
+            assert matches(p, a), (name, i, p, a)
+        assert restype is not None and matches(ret, restype)
+    lib = pkg._lib.load()
+    for name in table:
+        assert hasattr(lib, name) and getattr(lib, name).argtypes == table[name][1]
+    for other in os.listdir(os.path.join(ROOT, "include")):
+        if other.endswith(".h"):
+            assert "vistaf_outline" not in open(os.path.join(ROOT, "include", other)).read(), other
+
+
+def test_outline_c_abi_refuses_with_the_arguments_name(pkg):
+    lib = pkg._lib.load()
+    err = lib.vistaf_ftp_last_error
+    n = ctypes.c_size_t(1)
+    assert lib.vistaf_outline_workspace_bytes(8, 8, 1, 8, None) == E_INVALID and b"bytes" in err()
+    for args, word in (((0, 8, 1, 8), b"h "), ((32768, 8, 1, 8), b"h "), ((8, 0, 1, 8), b"w "), ((8, 32768, 1, 8), b"w "),
+                       ((32767, 32767, 1, 8), b"h * w"), ((8, 8, 0, 8), b"batch"), ((8, 8, 1, 0), b"max_contacts"), ((8, 8, 1, 65), b"max_contacts")):
+        n.value = 1
+        assert lib.vistaf_outline_workspace_bytes(*args, ctypes.byref(n)) == E_INVALID and n.value == 0 and word in err(), args
+    assert lib.vistaf_outline_workspace_bytes(8, 8, 1, 8, ctypes.byref(n)) == 0 and n.value > 0
+    assert pkg.outline.workspace_bytes(8, 8, 1, 8) == n.value
+    with pytest.raises(ValueError, match="max_contacts"):
+        pkg.outline.workspace_bytes(8, 8, 1, 0)
+    # measure: host memory stands in for the device's, every call is refused before any HIP call
+    f64, i32, i8 = (ctypes.c_double * 256)(), (ctypes.c_int32 * 64)(), (ctypes.c_int8 * 64)()
+    raw = (ctypes.c_uint8 * 1024)()
+    ws = (ctypes.addressof(raw) + 255) & ~255
+    p = ctypes.addressof
+    good = dict(idx=p(i8), tab=p(f64), cnt=p(i32), mpp=p(f64), B=1, h=8, w=8, K=8, V=8, out=p(f64), verts=p(i32), offs=p(i32), ws=ws, n=n.value)
+
+    def call(**kw):
+        a = dict(good, **kw)
+        return lib.vistaf_outline_measure(a["idx"], a["tab"], a["cnt"], a["mpp"], a["B"], a["h"], a["w"], a["K"], a["V"], a["out"], a["verts"], a["offs"],
+                                          a["ws"], a["n"], None)
+    for kw, words in ((dict(idx=None), [b"d_contact_index"]), (dict(tab=None), [b"d_contacts"]), (dict(cnt=None), [b"d_count"]),
+                      (dict(mpp=None), [b"d_mm_per_px"]), (dict(out=None), [b"d_outlines"]), (dict(ws=None), [b"d_workspace"]),
+                      (dict(verts=None), [b"d_vertices", b"d_offsets"]), (dict(h=0), [b"h "]), (dict(w=32768), [b"w "]), (dict(B=0), [b"batch"]),
+                      (dict(K=0), [b"max_contacts"]), (dict(K=65), [b"max_contacts"]), (dict(V=-1), [b"max_vertices"]),
+                      (dict(tab=p(f64) + 4), [b"d_contacts", b"aligned"]), (dict(cnt=p(i32) + 2), [b"d_count", b"aligned"]),
+                      (dict(ws=ws + 128), [b"d_workspace", b"aligned"]), (dict(n=n.value - 1), [b"workspace_bytes"]), (dict(n=0), [b"workspace_bytes"])):
+        assert call(**kw) == E_INVALID, kw
+        assert all(word in err() for word in words), (kw, err())
+
+
+def _hand_table():
+    t = np.full((2, 3, 24), np.nan)
+    t[0, 0, :20] = [204, 1, 1, 76, 112, 5.5556, 253, 52, 52, 16, 1.5, 0.8, 1.4, 0.3, 1.3, 15.5, 11.5, 1.4, 1.3, np.pi / 2]
+    t[0, 1, [0, 1, 2, 3, 4, 7, 8, 9]] = 0
+    t[1, 0, :20] = [1, 1, 0, 4, 4, 0.4, 1, 4, 0, 4, 0.01, 1.0, 0.14, 0.78, 0.1, 7.5, 5.5, 0.1, 0.1, 0.0]
+    return t, np.array([2, 1], np.int32)
+
+
+def test_outline_writers_round_trip(pkg, tmp_path):
+    t, n = _hand_table()
+    rows = pkg.outlines_table(t, n)
+    assert [(r["frame"], r["contact"]) for r in rows] == [(0, 0), (0, 1), (1, 0)]
+    assert list(rows[0])[2:] == list(pkg.OUTLINE_NAMES) and isinstance(rows[0]["pixels"], int) and isinstance(rows[0]["enclosed_pixels"], float)
+    assert rows[1]["pixels"] == 0 and np.isnan(rows[1]["perimeter_mm"])
+    with pytest.raises(ValueError):
+        pkg.outlines_table(t[..., :10], n)
+    path = pkg.write_outlines_csv(str(tmp_path), t[:1], n[:1])
+    back = list(csv.DictReader(open(path)))
+    assert len(back) == 2 and list(back[0]) == ["frame", "contact"] + list(pkg.OUTLINE_NAMES)
+    for r, q in zip(rows, back):
+        for name in pkg.OUTLINE_NAMES:
+            v = float(q[name])
+            assert v == r[name] or (np.isnan(v) and np.isnan(r[name]))
+    verts = np.array([[7, 5], [8, 5], [8, 6], [7, 6], [0, 0], [0, 0]], np.int32)
+    rec = pkg.outline_frame_record(t[1, :1], verts, np.array([0, 0]), 1)
+    assert rec["polylines"] == [None] and rec["contact_count"] == 1                                # corners 4, written 0: left out
+    t[1, 0, 8] = 4
+    rec = pkg.outline_frame_record(t[1, :1], verts, np.array([0, 4]), 1)
+    assert rec["polylines"] == [[[7, 5], [8, 5], [8, 6], [7, 6]]] and rec["outlines"][0]["edges"] == 4 and "frame" not in rec["outlines"][0]
+    rec = pkg.outline_frame_record(t[0, :2], verts, np.array([0, 0, 0]), 2)
+    assert rec["outlines"][1]["perimeter_mm"] is None and rec["polylines"][1] == []
+    with pytest.raises(ValueError):
+        pkg.outline_frame_record(t[0, :2], verts, np.array([0, 0]), 2)
+
+
+def test_contact_outlines_needs_a_device_or_refuses_bad_arguments(pkg):
+    import torch
+    idx, tab = np.zeros((1, 8, 8), np.int8), np.zeros((1, 4, 16))
+    if not torch.cuda.is_available():
+        with pytest.raises(RuntimeError, match="HIP device"):
+            pkg.contact_outlines(idx, tab, [1], [0.1])
+        return
+    for bad in ((idx[0], tab, [1], [0.1]), (idx, tab[:, :, :8], [1], [0.1]), (idx, tab, [1, 2], [0.1]), (idx, tab, [1], [0.1, 0.2])):
+        with pytest.raises(ValueError):
+            pkg.contact_outlines(*bad)
+    with pytest.raises(ValueError):
+        pkg.contact_outlines(idx, tab, [1], [0.1], max_vertices=-1)
+
+
+# ------------------------------------------------------------------------------------------------------------- GPU, through the C ABI
+SENTINEL = -77
+
+
+def _abi(pkg, c, V, polylines=True, sel=None, batch_ws=None):
+    """vistaf_outline_measure on case c (frames `sel`): (outlines, vertices, offsets) as arrays; the polyline arrays are filled with SENTINEL
+    first, and are NULL with polylines=False"""
+    import torch
+    sel = slice(None) if sel is None else sel
+    dev = torch.device("cuda:0")
+    idx, tab = torch.as_tensor(c["index"][sel]).to(dev).contiguous(), torch.as_tensor(c["tab"][sel]).to(dev).contiguous()
+    cnt, mpp = torch.as_tensor(c["count"][sel]).to(dev).contiguous(), torch.as_tensor(c["mpp"][sel]).to(dev).contiguous()
+    B, h, w = idx.shape
+    K = tab.shape[1]
+    nbytes = pkg.outline.workspace_bytes(h, w, B, K)
+    ws = torch.empty((nbytes + 256,), dtype=torch.uint8, device=dev)
+    out = torch.full((B, K, 24), 123.0, dtype=torch.float64, device=dev)
+    verts = torch.full((B, max(V, 1), 2), SENTINEL, dtype=torch.int32, device=dev)
+    offs = torch.full((B, K + 1), SENTINEL, dtype=torch.int32, device=dev)
+    pkg._handle.call(dev, "vistaf_outline_measure", idx.data_ptr(), tab.data_ptr(), cnt.data_ptr(), mpp.data_ptr(), B, h, w, K, V, out.data_ptr(),
+                     verts.data_ptr() if polylines else None, offs.data_ptr() if polylines else None, (ws.data_ptr() + 255) & ~255, nbytes,
+                     pkg._handle.stream(dev))
+    torch.cuda.synchronize()
+    return out.cpu().numpy(), verts.cpu().numpy()[:, :V], offs.cpu().numpy()
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.int64), np.ascontiguousarray(b).view(np.int64))
+
+
+def _check(got, want, what):
+    """the record against the reference's: NaN in the same places, integer fields equal, *, / and sqrt doubles bit-equal, directions to the bar"""
+    out, verts, offs = got
+    ref, rverts, roffs = want
+    assert out.shape == ref.shape and np.array_equal(np.isnan(out), np.isnan(ref)), what
+    for name in OH.INT_FIELDS:
+        assert np.array_equal(out[..., O[name]], ref[..., O[name]], equal_nan=True), (what, name, out[..., O[name]], ref[..., O[name]])
+    for name in OH.EXACT_DOUBLE_FIELDS:
+        assert _same_bits(out[..., O[name]], ref[..., O[name]]), (what, name, out[..., O[name]], ref[..., O[name]])
+    worst = 0.0
+    for name in OH.ANGLE_FIELDS:
+        d = np.abs(out[..., O[name]] - ref[..., O[name]])
+        d = np.fmin(d, np.pi - d)                                  # directions: pi / 2 and -pi / 2 are the same one
+        if (~np.isnan(d)).any():
+            worst = max(worst, float(np.nanmax(d)))
+        g = out[..., O[name]][~np.isnan(d)]
+        assert ((g > -np.pi / 2) & (g <= np.pi / 2)).all(), (what, name)
+    print(what, "largest direction distance", worst, "bar", ANGLE_BAR)
+    assert worst <= ANGLE_BAR, (what, worst)
+    if roffs is not None:
+        assert np.array_equal(offs, roffs), (what, offs, roffs)
+        for b, vb in enumerate(rverts):
+            assert np.array_equal(verts[b, :len(vb)], np.array(vb, np.int32).reshape(-1, 2)), (what, b)
+            assert (verts[b, len(vb):] == SENTINEL).all(), (what, b, "the tail was written")
+
+
+_REF = {}
+
+
+def _hand_case(h, w, V):
+    key = (h, w, V)
+    if key not in _REF:
+        names, c = OH.hand_made(h, w)
+        _REF[key] = (names, c, OH.reference(c["index"], c["tab"], c["count"], c["mpp"], V))
+    return _REF[key]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("h,w", [(24, 32), (33, 47)])
+def test_hand_made_cases_equal_the_tracer(pkg, h, w):
+    names, c, want = _hand_case(h, w, 256)
+    ref = want[0]
+    cb, sp = names.index("checkerboard"), names.index("single_pixel")
+    assert [ref[cb, 0, O[n]] for n in ("pixels", "holes", "edges", "enclosed_pixels")] == [18, 8, 40, 26] and ref[sp, 0, O["corners"]] == 4
+    assert ref[names.index("diagonal_chain"), 0, O["corners"]] == ref[names.index("diagonal_chain"), 0, O["edges"]]      # every vertex a corner
+    assert ref[names.index("ring"), 0, O["holes"]] == 1 and ref[names.index("two_pieces_and_empty"), 0, O["pieces"]] == 2
+    got = _abi(pkg, c, 256)
+    _check(got, want, f"hand-made {h}x{w}")
+    assert (got[0][..., 20:] != got[0][..., 20:]).all()                                                                  # reserved: NaN
+
+
+@pytest.mark.gpu
+def test_capacity_rule_and_null_polylines(pkg):
+    h, w = 24, 32
+    names, c, full = _hand_case(h, w, 256)
+    b = names.index("borders_and_corners")
+    totals = np.cumsum(full[0][b, :, O["corners"]])
+    assert totals[1] < 10 < totals[2]                                           # between two rows' totals
+    cut = OH.reference(c["index"], c["tab"], c["count"], c["mpp"], 10)
+    got = _abi(pkg, c, 10)
+    _check(got, cut, "capacity 10")
+    assert list(got[0][b, :, O["corners_written"]]) == [4, 4, 0, 0, 0, 0, 0, 0]
+    ignore = [i for i in range(24) if i != O["corners_written"]]
+    zero = _abi(pkg, c, 0)
+    _check(zero, OH.reference(c["index"], c["tab"], c["count"], c["mpp"], 0), "capacity 0")
+    null = _abi(pkg, c, 256, polylines=False)
+    _check((null[0], None, None), (OH.reference(c["index"], c["tab"], c["count"], c["mpp"], None)[0], None, None), "NULL polylines")
+    assert (null[1] == SENTINEL).all() and (null[2] == SENTINEL).all()
+    whole = _abi(pkg, c, 256)[0]
+    for other in (got[0], zero[0], null[0]):
+        assert _same_bits(other[..., ignore], whole[..., ignore])               # the records do not depend on the capacity
+    used = ~np.isnan(whole[..., 0])
+    assert (zero[0][..., O["corners_written"]][used] == 0).all() and (null[0][..., O["corners_written"]][used] == 0).all()
+
+
+@pytest.mark.gpu
+def test_batch_positions_and_second_call_give_the_same_bits(pkg):
+    import torch
+    names, c, want = _hand_case(33, 47, 256)
+    pick = [names.index(n) for n in ("ring", "checkerboard", "touching", "two_pieces_and_empty", "u_shape")]
+    five = {k: (v[pick] if isinstance(v, np.ndarray) else v) for k, v in c.items()}
+    whole, again = _abi(pkg, five, 256), _abi(pkg, five, 256)
+    for a, b in zip(whole, again):
+        assert np.array_equal(a.view(np.int32), b.view(np.int32))
+    for i in range(5):
+        one = _abi(pkg, five, 256, sel=slice(i, i + 1))
+        assert all(np.array_equal(a.view(np.int32), b[i:i + 1].view(np.int32)) for a, b in zip(one, whole)), i
+    perm = [3, 0, 4, 2, 1]
+    moved = _abi(pkg, {k: (v[perm] if isinstance(v, np.ndarray) else v) for k, v in five.items()}, 256)
+    assert all(np.array_equal(a.view(np.int32), b[perm].view(np.int32)) for a, b in zip(moved, whole))
+    # a frame with a bad table among them changes no bit of the others
+    bad = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in five.items()}
+    bad["tab"][2] = np.nan
+    bad["count"][3] = 0
+    mixed = _abi(pkg, bad, 256)
+    for i in (0, 1, 4):
+        assert all(np.array_equal(a[i].view(np.int32), b[i].view(np.int32)) for a, b in zip(mixed, whole)), i
+    assert np.isnan(mixed[0][3]).all() and (mixed[0][2, :, O["pixels"]][:bad["count"][2]] == 0).all() and (mixed[2][2:4] == 0).all()
+    # the Python entry point: the same bits, the dict's keys, trim
+    r = pkg.contact_outlines(five["index"], five["tab"], five["count"], five["mpp"], max_vertices=256)
+    torch.cuda.synchronize()
+    assert set(r) == {"outlines", "vertices", "offsets"} and _same_bits(r["outlines"].cpu().numpy(), whole[0])
+    assert np.array_equal(r["offsets"].cpu().numpy(), whole[2])
+    t = pkg.outline.trim(r)
+    assert not t["overflow"] and [len(p) for p in t["polylines"]] == [int(n) for n in np.minimum(five["count"], 8)]
+    assert np.array_equal(t["polylines"][0][0], np.array(want[1][pick[0]], np.int32)[:len(t["polylines"][0][0])])
+    small = pkg.contact_outlines(five["index"], five["tab"], five["count"], five["mpp"], max_vertices=0)
+    assert set(small) == {"outlines"} and pkg.outline.trim(small)["overflow"]
+    assert tuple(pkg.contact_outlines(five["index"], five["tab"], five["count"], five["mpp"])["vertices"].shape) == (5, 4 * (33 + 47), 2)
+
+
+@pytest.mark.gpu
+def test_native_size_plane_ring_and_bar(pkg):
+    n, s = 1182, 0.05
+    sc = OH.Scene(n, n)
+    sc.paint(0, OH.ring(n, n, 640, 500, 75, 52))                                  # a ring about 150 px across
+    sc.paint(1, OH.rect(n, n, 1100, 3, 1181, 1181) | OH.rect(n, n, 20, 1150, 1181, 1181))      # an L along two frame borders: long runs, far coordinates
+    c = OH.pack([sc], s)
+    want = OH.reference(c["index"], c["tab"], c["count"], c["mpp"], 2048)
+    assert want[0][0, 0, O["holes"]] == 1 and want[0][0, 0, O["edges"]] > 500 and want[0][0, 1, O["edges"]] > 4000
+    _check(_abi(pkg, c, 2048), want, "native")
+
+
+# ---------------------------------------------------------------------------------------------------------------- GPU, through the session
+def _session(pkg, n, max_batch):
+    model, neg = pkg.load_calibration(os.path.join(G, "calibration_phase_to_height.json"))
+    fm = pkg.load_force_calibration(os.path.join(G, "calibration_height_to_force.json"))["best_model"]
+    return pkg.FtpSensor(pkg.synth.reference_frame(n), pkg.synth.roi_circle(n), pkg.FtpConfig.scaled(n), model, neg, fm, max_batch=max_batch)
+
+
+@pytest.mark.gpu
+def test_session_outlines_equal_the_tracer_and_leave_the_predict_alone(pkg):
+    import torch
+    n, nb, K = 64, 4, 8
+    s = _session(pkg, n, nb)
+    with pytest.raises(RuntimeError):
+        s.outlines()                                         # no predict yet
+    o = s.predict_batch(CH.multi_contact_batch(pkg, n, 0, nb))
+    before = {k: v.clone() for k, v in o.items()}
+    plain = {k: v.clone() for k, v in s.contacts(K, index_plane=True).items()}
+    r = s.outlines(K)
+    first = s._outlines
+    again = s.outlines(K)
+    assert s._outlines is first and s.outlines(4)["outlines"].shape == (nb, 4, 24) and s._outlines is not first       # kept; remade for another K
+    torch.cuda.synchronize()
+    assert set(r) == {"contacts", "count", "contact_index", "outlines", "vertices", "offsets"} and tuple(r["outlines"].shape) == (nb, K, 24)
+    assert tuple(r["vertices"].shape) == (nb, 4 * (n + n), 2) and tuple(r["offsets"].shape) == (nb, K + 1)
+    for k, v in before.items():
+        assert torch.equal(o[k].view(torch.uint8), v.view(torch.uint8)), k
+    for k, v in plain.items():
+        assert torch.equal(r[k].view(torch.uint8), v.view(torch.uint8)), k
+    got = tuple(r[k].cpu().numpy() for k in ("outlines", "vertices", "offsets"))
+    for a, k in zip(got, ("outlines", "vertices", "offsets")):              # a second call: the same bits in everything that is written
+        b = again[k].cpu().numpy()
+        written = np.arange(a.shape[1])[None, :, None] < got[2][:, -1][:, None, None] if k == "vertices" else np.ones(a.shape, bool)
+        assert np.array_equal(np.where(written, a, 0).view(np.int32), np.where(written, b, 0).view(np.int32)), k
+    idx, tab, cnt, mpp = r["contact_index"].cpu().numpy(), r["contacts"].cpu().numpy(), r["count"].cpu().numpy(), o["scalars"][:, 6].cpu().numpy()
+    s.close()
+    assert s._outlines is None
+    want = OH.reference(idx, tab, cnt, mpp, 4 * (n + n))
+    out, verts, offs = got
+    _check((out, np.where(np.arange(verts.shape[1])[None, :, None] < offs[:, -1][:, None, None], verts, SENTINEL), offs), want, "session")
+    used = ~np.isnan(out[..., 0])
+    print("session counts", cnt, "pixels", out[..., O["pixels"]][used])
+    assert used.sum() == np.minimum(cnt, K).sum() >= 1
+    assert np.array_equal(out[..., O["pixels"]][used], tab[..., 0][used])                    # VISTAF_CONTACT_PIXELS: the component itself
+    assert (out[..., O["pieces"]][used] == 1).all() and (out[..., O["corners_written"]][used] == out[..., O["corners"]][used]).all()
+
+
+@pytest.mark.gpu
+def test_predict_outlines_flag(pkg):
+    n = 64
+    s = _session(pkg, n, 1)
+    frame = CH.multi_contact_frame(pkg, n, 2)
+    plain, with_contacts = s.predict(frame), s.predict(frame, contacts=4)
+    res = s.predict(frame, contacts=4, outlines=True)
+    assert set(res) == set(with_contacts) | {"outlines", "outline_polylines"} and set(with_contacts) == set(plain) | {"contacts", "contact_count"}
+    assert len(res["outlines"]) == len(res["contacts"]) == len(res["outline_polylines"])
+    for ol, ct, line in zip(res["outlines"], res["contacts"], res["outline_polylines"]):
+        assert list(ol)[0] == "contact" and list(ol)[1:] == list(pkg.OUTLINE_NAMES)
+        assert ol["pixels"] == ct["pixels"] and len(line) == ol["corners"] == ol["corners_written"]
+    assert np.array_equal(res["height_map_mm_crop"], plain["height_map_mm_crop"], equal_nan=True) and "outlines" not in with_contacts
+    with pytest.raises(ValueError):
+        s.predict(frame, outlines=True)
+    s.close()

@@ -61,6 +61,11 @@ PRESSURE_NAMES = ["pixels", "force_model_N", "tensile_model_N", "force_N", "mean
                   "offset_y_mm", "peak_over_mean", "edge_share"]
 PRESSURE_FRAME_NAMES = ["contacts", "force_model_N", "tensile_model_N", "outside_model_N", "scale", "E_effective_MPa", "peak_kPa", "peak_index",
                         "peak_row", "cop_x", "cop_y", "status"]
+NOUTLINE = 24           # doubles per row of the contact outline read-out (VISTAF_NOUTLINE, include_ext/vistaf_outline.h)
+# fields of an outline row in the order of the VISTAF_OUTLINE_* indices; 20..23 are reserved
+OUTLINE_NAMES = ["pixels", "pieces", "holes", "edges", "edges_all", "perimeter_mm", "enclosed_pixels", "corners", "corners_written", "hull_vertices",
+                 "hull_area_mm2", "solidity", "max_feret_mm", "max_feret_angle_rad", "min_feret_mm", "box_cx", "box_cy", "box_length_mm",
+                 "box_width_mm", "box_angle_rad"]
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -259,6 +264,12 @@ MASK_CHAIN_SIGNATURES = {
     "vistaf_ftp_test_reliable_chain": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "vistaf_ftp_test_contact_chain": (ci, [vp, vp, vp, vp, cd, cd, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
 }
+# include_ext/vistaf_outline.h: the contact outline read-out, two plain functions outside the drop-in boundary of include/*.h, in a table of
+# their own as well (tests/test_outlines.py holds it against that header)
+OUTLINE_SIGNATURES = {
+    "vistaf_outline_workspace_bytes": (ci, [ci, ci, ci, ci, P(sz)]),
+    "vistaf_outline_measure": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -277,7 +288,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -342,4 +342,8 @@ void launch_backend_fused(float *depth, const uint8_t *cand, const unsigned int 
 // ---- k_pressure.hip (the pressure read-out, include/vistaf_pressure.h): its workspace of max_batch frames of h x w with pad_px of zero fill
 size_t pressure_scratch_bytes(int B, int h, int w, int pad, ScratchRec *rec = nullptr);
 
+// ---- k_outline.hip (the contact outline read-out, include_ext/vistaf_outline.h): the workspace its caller hands in, for B frames of h x w and
+// tables of K rows.  Its three launches are made by vistaf_outline_measure itself
+size_t outline_scratch_bytes(int B, int h, int w, int K, ScratchRec *rec = nullptr);
+
 }  // namespace vf

@@ -325,6 +325,7 @@ class FtpSensor(Handle):
     _cloud = property(lambda self: self._live("cloud"))
     _motion = property(lambda self: self._live("motion"))
     _pressure = property(lambda self: self._live("pressure"))
+    _outlines = property(lambda self: self._live("outlines"))
 
     def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
         last = getattr(self, "_last_out", None)
@@ -437,6 +438,22 @@ class FtpSensor(Handle):
             sh = self._keep("shapes", (k, frac), ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device))
         out["shapes"] = sh.measure(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
                                    self.config.depth_eps_mm)
+        return out
+
+    def outlines(self, max_contacts: int = 8, max_vertices: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the outline of every contact (outline.contact_outlines; an extension, the reference has
+        no counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands it and the frames' mm_per_px (the `scalars` column) to
+        the outline read-out; its workspace is the session's, made on first use and again when max_contacts changes.  Returns the contacts
+        dict plus outlines [B,K,24] f64 (fields OUTLINE_NAMES: loops, holes, perimeter, hull, Feret diameters, caliper box), vertices
+        [B,V,2] i32 and offsets [B,K+1] i32, the corner polylines of the principal loops (`outline.trim` cuts them).  max_vertices: V per
+        frame, by default 4 * (h + w) (`outline.default_max_vertices`); rows that do not fit show corners_written < corners; 0: no polylines."""
+        from .outline import OutlineWorkspace, contact_outlines
+        k = int(max_contacts)
+        ws = self._matching("outlines", (k,))
+        out = self.contacts(k, index_plane=True)
+        if ws is None:
+            ws = self._keep("outlines", (k,), OutlineWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out.update(contact_outlines(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), max_vertices, ws))
         return out
 
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
@@ -608,7 +625,8 @@ class FtpSensor(Handle):
     # -- single-frame API in the reference's vocabulary ---------------------------------------------
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
-                motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None) -> Optional[Dict[str, Any]]:
+                motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None,
+                outlines: bool = False) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -631,7 +649,11 @@ class FtpSensor(Handle):
         MOTION_FRAME_NAMES: this frame follows the frame of the previous predict that asked for it.
         pressure=dict(...) (the keyword arguments of `FtpSensor.pressure` but `max_contacts`: E_mpa, nu, thickness_mm, pad_px) adds
         "pressure_kpa", the ndarray [h,w] f32 of the contact pressure, "pressure_frame", a dict of PRESSURE_FRAME_NAMES, and, with contacts=K,
-        "pressure", one dict of PRESSURE_NAMES per entry of "contacts"."""
+        "pressure", one dict of PRESSURE_NAMES per entry of "contacts".
+        outlines=True (with contacts=K) adds "outlines", one dict of OUTLINE_NAMES per entry of "contacts" (`FtpSensor.outlines`), and
+        "outline_polylines", per entry the [n,2] list of its principal loop's corners (None for a row that did not fit the capacity)."""
+        if outlines and contacts is None:
+            raise ValueError("outlines=True needs contacts=K")
         if motion is not None and contacts is None:
             raise ValueError("motion=dict(...) needs contacts=K")
         if shapes and contacts is None:
@@ -690,6 +712,14 @@ class FtpSensor(Handle):
                 for r in res["tracks"] + res["motion"]:
                     r.pop("frame")
                 res["motion_frame"] = motion_frame_record(mo["motion_frame"][0].cpu().numpy())
+            if outlines:
+                from .writers import outline_frame_record, outlines_table
+                ol = self.outlines(int(contacts))
+                res["outlines"] = outlines_table(ol["outlines"].cpu().numpy(), ol["count"].cpu().numpy())
+                for r in res["outlines"]:
+                    r.pop("frame")
+                res["outline_polylines"] = outline_frame_record(ol["outlines"][0].cpu().numpy(), ol["vertices"][0].cpu().numpy(),
+                                                                ol["offsets"][0].cpu().numpy(), int(ol["count"][0].item()))["polylines"]
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table
             running = self._pressure                            # without contacts=K the table's size is nobody's concern: keep the running one

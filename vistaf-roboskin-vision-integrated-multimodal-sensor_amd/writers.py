@@ -61,6 +61,11 @@ SHAPE_FIELDS = ("contact_pixels", "boundary_pixels", "footprint_cx", "footprint_
                 "curvature_axis_rad", "radius_1_mm", "radius_2_mm", "fit_rms_mm")          # VISTAF_SHAPE_* order (include/vistaf_shape.h)
 SHAPE_INT_FIELDS = ("contact_pixels", "boundary_pixels", "fit_pixels", "fit_status")
 SHAPES_CSV_FIELDS = ("frame", "contact") + SHAPE_FIELDS
+OUTLINE_FIELDS = ("pixels", "pieces", "holes", "edges", "edges_all", "perimeter_mm", "enclosed_pixels", "corners", "corners_written", "hull_vertices",
+                  "hull_area_mm2", "solidity", "max_feret_mm", "max_feret_angle_rad", "min_feret_mm", "box_cx", "box_cy", "box_length_mm",
+                  "box_width_mm", "box_angle_rad")                                       # VISTAF_OUTLINE_* order (include_ext/vistaf_outline.h)
+OUTLINE_INT_FIELDS = ("pixels", "pieces", "holes", "edges", "edges_all", "corners", "corners_written", "hull_vertices")
+OUTLINES_CSV_FIELDS = ("frame", "contact") + OUTLINE_FIELDS
 TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                 "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
 TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
@@ -257,6 +262,37 @@ def shapes_table(shapes, contacts, count) -> list:
 def write_shapes_csv(output_dir: str, shapes, contacts, count, filename: str = "shapes.csv") -> str:
     """shapes.csv: one line per written contact, columns SHAPES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
     return _write_csv(output_dir, filename, SHAPES_CSV_FIELDS, shapes_table(shapes, contacts, count))
+
+
+def outlines_table(outlines, count) -> list:
+    """Row dicts of the contact outline table: outlines [B,K,>=20] (or [K,>=20] for one frame) float64 as `FtpSensor.outlines` returns it,
+    count [B].  One dict per written contact, as `contacts_table`: `frame`, `contact` and OUTLINE_FIELDS, the counts as ints; a row without
+    a pixel has NaN where the header leaves NaN (enclosed_pixels among them, which therefore stays a float)."""
+    return _table(outlines, count, OUTLINE_FIELDS, OUTLINE_INT_FIELDS, "outlines must be [B,K,>=20] with count [B]")
+
+
+def write_outlines_csv(output_dir: str, outlines, count, filename: str = "outlines.csv") -> str:
+    """outlines.csv: one line per written contact, columns OUTLINES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    return _write_csv(output_dir, filename, OUTLINES_CSV_FIELDS, outlines_table(outlines, count))
+
+
+def outline_frame_record(outlines, vertices, offsets, count) -> Dict[str, Any]:
+    """One frame's outlines for a JSON document of the caller's own: outlines [K,>=20], vertices [V,2], offsets [K+1], count (a scalar).
+    {"contact_count", "outlines": the row dicts without `frame`, NaN as null, "polylines": per row the [[x, y], ...] list of its
+    principal loop's corners, null for a row that was not written (corners_written < corners)}."""
+    rows = outlines_table(np.asarray(outlines, dtype=np.float64), np.asarray([count]))
+    v, o = np.asarray(vertices), np.asarray(offsets)
+    if v.ndim != 2 or v.shape[1] != 2 or o.ndim != 1 or o.shape[0] != np.asarray(outlines).shape[0] + 1:
+        raise ValueError("vertices must be [V,2] and offsets [K+1] for outlines [K,>=20]")
+    lines = []
+    for r in rows:
+        r.pop("frame")
+        k = r["contact"]
+        lines.append([[int(x), int(y)] for x, y in v[o[k]:o[k + 1]]] if r["corners_written"] == r["corners"] else None)
+        for name, val in r.items():
+            if isinstance(val, float) and not math.isfinite(val):
+                r[name] = None
+    return {"contact_count": int(count), "outlines": rows, "polylines": lines}
 
 
 def taxels_table(taxels) -> list:
