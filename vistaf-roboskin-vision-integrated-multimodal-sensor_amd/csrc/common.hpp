@@ -23,16 +23,16 @@ __host__ __device__ inline int reflect_edge(int p, int len)
     return p;
 }
 
-// order-preserving float <-> uint32 (ascending)
-__device__ inline uint32_t f2key(float f)
+// order-preserving float <-> uint32 (ascending): bit operations, the same on the host
+__host__ __device__ inline uint32_t f2key(float f)
 {
-    uint32_t u = __float_as_uint(f);
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
-__device__ inline float key2f(uint32_t k)
+__host__ __device__ inline float key2f(uint32_t k)
 {
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    return __uint_as_float(u);
+    return __builtin_bit_cast(float, u);
 }
 // arg-max key: the larger value wins, among equal values the smaller index
 __device__ inline unsigned long long argmax_key(float v, unsigned i) { return ((unsigned long long)f2key(v) << 32) | (0xffffffffu - i); }
@@ -40,8 +40,21 @@ __device__ inline unsigned long long argmax_key(float v, unsigned i) { return ((
 __device__ inline bool finitef(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ inline bool finitef(double v) { return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }
 // the quiet NaN every kernel writes (NumPy's np.nan bits)
-__device__ inline float nanf32() { return __uint_as_float(0x7fc00000u); }
+__host__ __device__ inline float nanf32() { return __builtin_bit_cast(float, 0x7fc00000u); }
 __device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// One correctly rounded float32 operation that is never contracted into an fma, for rules a host program calls too: the __f*_rn intrinsic on
+// the device, the plain operator on the host (the same operation under the -ffp-contract=off the library and every host check are built with)
+#ifdef __HIP_DEVICE_COMPILE__
+#define VF_RN(dev, host) return dev
+#else
+#define VF_RN(dev, host) return host
+#endif
+__host__ __device__ inline float rn_add(float a, float b) { VF_RN(__fadd_rn(a, b), a + b); }
+__host__ __device__ inline float rn_sub(float a, float b) { VF_RN(__fsub_rn(a, b), a - b); }
+__host__ __device__ inline float rn_mul(float a, float b) { VF_RN(__fmul_rn(a, b), a * b); }
+__host__ __device__ inline float rn_div(float a, float b) { VF_RN(__fdiv_rn(a, b), a / b); }
+#undef VF_RN
 
 // ---- wave-level reductions on the DPP network (no LDS round trips): quad xor 1, quad xor 2, row_half_mirror,
 // row_mirror leave the row result in every lane of a 16-lane row; row_bcast15 / row_bcast31 then carry it

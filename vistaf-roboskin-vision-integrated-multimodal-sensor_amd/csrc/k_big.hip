@@ -11,11 +11,13 @@
 //     level too (its histogram has one bucket per key; its sweep also keeps the smallest key above the range).
 //   robust_polyfit2d (shape_ftp.py:1100-1136): per IRLS step the 21 normal-equation sums as per-block partials reduced in a FIXED order
 //     (deterministic), float64 Cholesky on one thread, then the two medians through the selection above with the residual as the value.
-// Arithmetic per sample, keys, median / percentile interpolation and the residual plane are those of k_fit.hip / select.hpp.
+// The element rule, key range, plan and result of a request and the level rules are select.hpp's; coordinates, column form, weight, median
+// ranges, scale, gate and the assembly of the normal equations are fit_rules.hpp's.  The per-sample sums and the bucket search are this file's.
 #include <algorithm>
 #include <cstdio>
 #include "host_util.hpp"
 #include "select.hpp"
+#include "fit_rules.hpp"
 #include "chol.hpp"
 
 namespace vf {
@@ -34,18 +36,14 @@ struct SbReq {                      // one (frame, request)
 struct SbFrame { uint32_t n, kmin, kmax, nmask; };
 
 // ---- value sources -------------------------------------------------------------------------------------------------------------------
-struct PlaneSrc {                   // k_select's PlaneGetter
+struct PlaneSrc {                   // a plane under a mask (k_select.hip: PlaneGetter)
     static constexpr bool tiled = false;
     const float *v; const uint8_t *m; size_t mstride; const float *le; int use_abs; int P;
     __device__ bool key(size_t b, int i, uint32_t &k) const
     {
         const uint8_t mk = m[b * mstride + i];
-        float x = v[b * (size_t)P + i];
-        bool ok = mk != 0 && finitef(x);
-        if (use_abs) x = fabsf(x);
-        if (le && !(x <= le[b])) ok = false;
-        k = f2key(x);
-        return ok;
+        const float x = v[b * (size_t)P + i];
+        return sel_element(mk, x, use_abs != 0, le ? le + b : nullptr, k);
     }
 };
 struct FitState {                   // per frame
@@ -53,10 +51,10 @@ struct FitState {                   // per frame
     float med, csig, zmin, zmax;
     int do_fit, mode, n, pad;
 };
-// residual (mode 0) or |residual - med| (mode 1) of the fitted samples, k_fit.hip's arithmetic.  Tiled sweeps (sb_visit): a thread keeps one
+// residual (mode 0) or |residual - med| (mode 1) of the fitted samples.  Tiled sweeps (sb_visit): a thread keeps one
 // image column for SB_PX rows, so the terms that only depend on x -- the normalised coordinate, A(x) = c3 x^2 + c0 x + c2 and
 // B(x) = c4 x + c1 -- are formed once per block instead of once per pixel (with the pixel's row by an integer division on top): a sample is
-// then fit = A + y B + c5 y^2 exactly as in the column kernels of k_fit.hip.
+// then fit = A + y B + c5 y^2 (fit_rules.hpp: fit_col_eval), as in the column kernels of k_fit.hip.
 struct ResidSrc {
     static constexpr bool tiled = true;
     const float *z; const uint8_t *m; const FitState *fs; int h, w, tiles_x;
@@ -64,22 +62,15 @@ struct ResidSrc {
     __device__ Col column(size_t b, int x) const
     {
         const FitState &s = fs[b];
-        const float cxf = (float)((w - 1) / 2.0);
-        const float xn = __fdiv_rn(__fsub_rn((float)x, cxf), cxf);
-        Col c;
-        c.At = fmaf(s.coef[3], __fmul_rn(xn, xn), fmaf(s.coef[0], xn, s.coef[2]));
-        c.Bt = fmaf(s.coef[4], xn, s.coef[1]);
-        c.c5 = s.coef[5]; c.med = s.med; c.mode = s.mode; c.cyf = (float)((h - 1) / 2.0);
-        return c;
+        const FitCol ct = fit_col_terms(s.coef, fit_coord(x, fit_centre(w)));
+        return {ct.At, ct.Bt, s.coef[5], s.med, fit_centre(h), s.mode};
     }
     __device__ bool key(const Col &c, size_t b, int y, int x, uint32_t &k) const
     {
         const size_t i = b * (size_t)h * w + (size_t)y * w + x;
         const float zz = z[i];
         if (!m[i] || !finitef(zz)) return false;
-        const float yn = __fdiv_rn(__fsub_rn((float)y, c.cyf), c.cyf);
-        const float fit = __fadd_rn(fmaf(yn, c.Bt, c.At), __fmul_rn(c.c5, __fmul_rn(yn, yn)));
-        float r = __fsub_rn(zz, fit);
+        float r = __fsub_rn(zz, fit_col_eval(c.At, c.Bt, c.c5, fit_coord(y, c.cyf)));
         if (c.mode) r = fabsf(__fsub_rn(r, c.med));
         k = f2key(r);
         return true;
@@ -124,17 +115,15 @@ __global__ __launch_bounds__(SB_T) void k_sb_minmax(Src src, SbFrame *fr, int P)
     __shared__ unsigned long long s64[16];
     __shared__ uint32_t s32[16];
     const size_t b = blockIdx.y;
-    uint32_t c = 0;
-    unsigned long long mn = ~0ull, mx = 0;
-    sb_visit(src, b, P, [&](uint32_t k) { c++; if (k < mn) mn = k; if (k + 1ull > mx) mx = k + 1ull; });
+    SelRange rg;
+    sb_visit(src, b, P, [&](uint32_t k) { rg.add(k); });
     __syncthreads();
-    const uint32_t n = block_sum<uint32_t>(c, s32);
-    mn = block_min_u64(mn, s64);
-    mx = block_max_u64(mx, s64);
-    if (threadIdx.x == 0 && n) { atomicAdd(&fr[b].n, n); atomicMin(&fr[b].kmin, (uint32_t)mn); atomicMax(&fr[b].kmax, (uint32_t)(mx - 1)); }
+    uint32_t n, kmin, kmax;
+    rg.reduce(s32, s64, n, kmin, kmax);
+    if (threadIdx.x == 0 && n) { atomicAdd(&fr[b].n, n); atomicMin(&fr[b].kmin, kmin); atomicMax(&fr[b].kmax, kmax); }
 }
 
-// first level of every request: rank, interpolation weight, bucket width; median: q < 0
+// first level of every request: rank, interpolation weight and kind (SbReq::two) from sel_plan, bucket width; median: q < 0
 __global__ void k_sb_setup(SbReq *rq, const SbFrame *fr, const float *reqs, int nreq, int B)
 {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -145,22 +134,9 @@ __global__ void k_sb_setup(SbReq *rq, const SbFrame *fr, const float *reqs, int 
     const SbFrame f = fr[b];
     r.q = reqs ? reqs[j] : -1.f;
     r.lo = f.kmin; r.hi = f.kmax;
-    const uint32_t n = f.n;
-    if (n == 0) { r.done = 2; r.result = __uint_as_float(0x7fc00000u); }
-    else if (r.q < 0.f) {                                         // np.median
-        if (n == 1) { r.done = 2; r.result = key2f(f.kmin); }
-        else { r.k = (n & 1u) ? (n - 1) / 2 : n / 2 - 1; r.two = (n & 1u) ? 0u : 1u; r.gamma = 0.5f; }
-    } else {                                                      // np.percentile, method linear (block_percentile)
-        uint32_t k; float g; bool top;
-        np_percentile_index(n, r.q, k, g, top);
-        if (k + 1 >= n) { r.done = 2; r.result = key2f(f.kmax); }
-        else { r.k = k; r.gamma = g; r.two = 2u; }
-    }
-    if (!r.done) {
-        const uint32_t range = r.hi - r.lo;
-        const int bits = range ? 32 - __clz(range) : 0;
-        r.shift = bits > SB_BITS ? (uint32_t)(bits - SB_BITS) : 0u;
-    }
+    const SelPlan p = sel_plan(f.n, r.q, f.kmin, f.kmax);
+    if (p.done) { r.done = 2; r.result = p.result; }
+    else { r.k = p.k; r.gamma = p.gamma; r.two = p.kind(); r.shift = (uint32_t)sel_shift(r.lo, r.hi, SB_BITS); }
     rq[t] = r;
 }
 
@@ -241,18 +217,16 @@ __global__ __launch_bounds__(1024) void k_sb_pick(SbReq *rq, uint32_t *hist, int
             __syncthreads();
         }
         if (tid == 0) {
-            const uint32_t nlo = r.lo + (s_bucket << shift);
-            uint32_t nhi = shift ? nlo + ((1u << shift) - 1u) : nlo;
-            if (nhi > r.hi || nhi < nlo) nhi = r.hi;
-            const uint32_t lo_old = r.lo;
-            r.below += s_before; r.lo = nlo; r.hi = nhi;
+            const SelSpan nx = sel_narrow(r.lo, r.hi, s_bucket, shift);
+            const uint32_t nlo = nx.lo, lo_old = r.lo;
+            r.below += s_before; r.lo = nx.lo; r.hi = nx.hi;
             if (shift == 0) {
                 uint32_t nbm = 0xFFFFFFFFu;
                 for (int i = 0; i < 16; i++) nbm = wmin[i] < nbm ? wmin[i] : nbm;
                 r.a = nlo; r.done = 1;
                 r.cnt_le = r.below + s_cnt;                      // keys <= a
                 if (nbm != 0xFFFFFFFFu) r.min_gt = lo_old + nbm; // else: the smallest key above the range (k_sb_hist), 0xFFFFFFFF if none
-            } else r.shift = shift > (uint32_t)SB_BITS ? shift - SB_BITS : 0u;
+            } else r.shift = sel_shift_chain_next(shift, SB_BITS);
         }
         __syncthreads();
     }
@@ -264,11 +238,8 @@ __global__ void k_sb_finish(SbReq *rq, float *out, int *counts, const SbFrame *f
     if (t >= B * nreq) return;
     SbReq &r = rq[t];
     if (r.done == 1) {
-        uint32_t kb = r.a;
-        if (r.two) kb = (r.k + 1 < r.cnt_le || r.min_gt == 0xFFFFFFFFu) ? r.a : r.min_gt;
-        const float a = key2f(r.a), bb = key2f(kb);
-        if (r.two == 2u) r.result = np_lerp(a, bb, r.gamma);
-        else r.result = r.two ? __fdiv_rn(__fadd_rn(a, bb), 2.0f) : a;
+        const uint32_t kb = r.two != SEL_ONE ? sel_next(r.k, r.cnt_le, r.min_gt, r.a) : r.a;
+        r.result = sel_result_kind(r.two, r.gamma, r.a, kb);
         r.b = kb;
     }
     if (out) out[t] = r.result;
@@ -284,8 +255,8 @@ __global__ __launch_bounds__(FB_T) void k_fb_count(const float *__restrict__ z_a
     __shared__ unsigned long long s64[16];
     __shared__ uint32_t s32[16];
     const size_t b = blockIdx.y;
-    uint32_t c = 0, cm = 0;
-    unsigned long long mn = ~0ull, mx = 0;
+    uint32_t cm = 0;
+    SelRange rg;
     const int i0 = blockIdx.x * FB_T * FB_PX + threadIdx.x;
 #pragma unroll
     for (int u = 0; u < FB_PX; u++) {
@@ -294,16 +265,14 @@ __global__ __launch_bounds__(FB_T) void k_fb_count(const float *__restrict__ z_a
         const uint8_t mk = m_all[b * (size_t)P + i];
         const float zz = z_all[b * (size_t)P + i];
         cm += mk != 0;
-        if (mk && finitef(zz)) { const uint32_t k = f2key(zz); c++; if (k < mn) mn = k; if (k + 1ull > mx) mx = k + 1ull; }
+        if (mk && finitef(zz)) rg.add(f2key(zz));
     }
     __syncthreads();
-    const uint32_t n = block_sum<uint32_t>(c, s32);
-    const uint32_t nm = block_sum<uint32_t>(cm, s32);
-    mn = block_min_u64(mn, s64);
-    mx = block_max_u64(mx, s64);
+    uint32_t n, kmin, kmax;
+    rg.reduce(s32, s64, n, kmin, kmax, true, cm);
     if (threadIdx.x == 0) {
-        if (nm) atomicAdd(&fr[b].nmask, nm);
-        if (n) { atomicAdd(&fr[b].n, n); atomicMin(&fr[b].kmin, (uint32_t)mn); atomicMax(&fr[b].kmax, (uint32_t)(mx - 1)); }
+        if (cm) atomicAdd(&fr[b].nmask, cm);
+        if (n) { atomicAdd(&fr[b].n, n); atomicMin(&fr[b].kmin, kmin); atomicMax(&fr[b].kmax, kmax); }
     }
 }
 __global__ void k_fb_init(FitState *fs, const SbFrame *fr, int min_count, int min_mask_count, int B)
@@ -312,7 +281,7 @@ __global__ void k_fb_init(FitState *fs, const SbFrame *fr, int min_count, int mi
     if (b >= B) return;
     FitState s = {};
     s.n = (int)fr[b].n;
-    s.do_fit = s.n >= min_count && (min_mask_count <= 0 || (int)fr[b].nmask >= min_mask_count);
+    s.do_fit = fit_gate(s.n, (int)fr[b].nmask, min_count, min_mask_count);
     s.zmin = s.n ? key2f(fr[b].kmin) : 0.f; s.zmax = s.n ? key2f(fr[b].kmax) : 0.f;
     s.csig = 1.f;
     fs[b] = s;
@@ -327,7 +296,7 @@ __global__ __launch_bounds__(FB_T) void k_fb_sums(const float *__restrict__ z_al
     const FitState s = fs[b];
     if (!s.do_fit) return;
     const size_t P = (size_t)h * w;
-    const float cxf = (float)((w - 1) / 2.0), cyf = (float)((h - 1) / 2.0);
+    const float cxf = fit_centre(w), cyf = fit_centre(h);
     const float inv_csig = __fdiv_rn(1.0f, s.csig);
     double v[21];
 #pragma unroll
@@ -335,8 +304,8 @@ __global__ __launch_bounds__(FB_T) void k_fb_sums(const float *__restrict__ z_al
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
     const int x = tx * FB_T + threadIdx.x, y0 = ty * FB_PX;
     if (x < w) {
-        const float xn = __fdiv_rn(__fsub_rn((float)x, cxf), cxf);
-        const float At = fmaf(s.coef[3], __fmul_rn(xn, xn), fmaf(s.coef[0], xn, s.coef[2])), Bt = fmaf(s.coef[4], xn, s.coef[1]);
+        const float xn = fit_coord(x, cxf);
+        const FitCol ct = fit_col_terms(s.coef, xn);
         const double xd = xn;
         for (int u = 0; u < FB_PX; u++) {
             const int y = y0 + u;
@@ -344,15 +313,11 @@ __global__ __launch_bounds__(FB_T) void k_fb_sums(const float *__restrict__ z_al
             const size_t i = b * P + (size_t)y * w + x;
             const float zz = z_all[i];
             if (!m_all[i] || !finitef(zz)) continue;
-            const float yn = __fdiv_rn(__fsub_rn((float)y, cyf), cyf);
+            const float yn = fit_coord(y, cyf);
             float wt = 1.f;
-            if (it > 0) {
-                const float fit = __fadd_rn(fmaf(yn, Bt, At), __fmul_rn(s.coef[5], __fmul_rn(yn, yn)));
-                const float uu = __fmul_rn(__fsub_rn(zz, fit), inv_csig);
-                wt = __fdiv_rn(1.0f, __fadd_rn(1.0f, __fmul_rn(uu, uu)));
-            }
+            if (it > 0) wt = fit_cauchy(__fsub_rn(zz, fit_col_eval(ct.At, ct.Bt, s.coef[5], yn)), inv_csig);
             const double w2 = (double)wt * (double)wt, yd = yn, zw = w2 * (double)zz;
-            // monomials x^a y^b, b-major with 5, 4, 3, 2, 1 entries (k_fit.hip's index), then the six right-hand sides
+            // monomials x^a y^b at k = fit_mono(aa, bb, 4), then the six right-hand sides
             double yp = w2;
             int k = 0;
 #pragma unroll
@@ -377,7 +342,7 @@ __global__ __launch_bounds__(FB_T) void k_fb_sums(const float *__restrict__ z_al
 }
 
 constexpr int FS_CHUNKS = 12;           // 21 * 12 = 252 threads
-// partials in block order -> coefficients; the value range of the residuals for the two selections (bounds on |fit|, as k_fit.hip)
+// partials in block order -> coefficients; the key range of the residuals for the two selections (fit_resid_range)
 __global__ __launch_bounds__(256) void k_fb_solve(FitState *fs, const double *partial, SbFrame *sel_fr, int nblk, int order)
 {
     __shared__ double s_sum[21], s_chunk[FS_CHUNKS][21];
@@ -402,21 +367,14 @@ __global__ __launch_bounds__(256) void k_fb_solve(FitState *fs, const double *pa
     __syncthreads();
     if (threadIdx.x == 0) {
         const int nc = order >= 2 ? 6 : 3;
-        auto mono = [&](int a, int bb) -> double { const int base[5] = {0, 5, 9, 12, 14}; return s_sum[base[bb] + a]; };
-        const int ea[6] = {1, 0, 0, 2, 1, 0}, eb[6] = {0, 1, 0, 0, 1, 2};
         double A[6][6], rhs[6];
-        for (int i = 0; i < 6; i++) {
-            for (int j = 0; j < 6; j++) A[i][j] = mono(ea[i] + ea[j], eb[i] + eb[j]);
-            rhs[i] = s_sum[15 + i];
-        }
+        fit_assemble<6, 4>(s_sum, A, rhs);                      // the chain keeps all 21 sums at either order; order 1 solves the leading 3 x 3
         const bool ok = nc == 6 ? chol_solve<6>(A, rhs) : chol_solve<3>(A, rhs);
-        float fb = 0.f;
-        for (int i = 0; i < 6; i++) { s.coef[i] = (ok && i < nc) ? (float)rhs[i] : 0.f; fb += fabsf(s.coef[i]); }
-        fb = fb * 1.0001f + 1e-30f;
+        for (int i = 0; i < 6; i++) s.coef[i] = (ok && i < nc) ? (float)rhs[i] : 0.f;
+        const FitKeys kr = fit_resid_range(s.coef, s.zmin, s.zmax);
         s.mode = 0;
         sel_fr[b].n = (uint32_t)s.n;
-        sel_fr[b].kmin = f2key(s.zmin - fb - 1e-6f * fabsf(s.zmin));
-        sel_fr[b].kmax = f2key(s.zmax + fb + 1e-6f * fabsf(s.zmax));
+        sel_fr[b].kmin = kr.kmin; sel_fr[b].kmax = kr.kmax;
     }
 }
 // after the median of r: switch to |r - med| and its range; after the median of |r - med|: the next step's scale
@@ -428,12 +386,11 @@ __global__ void k_fb_after_median(FitState *fs, const SbReq *rq, SbFrame *sel_fr
     if (!s.do_fit) return;
     if (which == 0) {
         const float medr = rq[b].result;
-        const float hi1 = fabsf(__fsub_rn(key2f(sel_fr[b].kmax), medr)), hi2 = fabsf(__fsub_rn(key2f(sel_fr[b].kmin), medr));
+        const FitKeys ka = fit_mad_range({sel_fr[b].kmin, sel_fr[b].kmax}, medr);
         s.med = medr; s.mode = 1;
-        sel_fr[b].kmin = f2key(0.f); sel_fr[b].kmax = f2key(hi1 > hi2 ? hi1 : hi2);
+        sel_fr[b].kmin = ka.kmin; sel_fr[b].kmax = ka.kmax;
     } else {
-        const float mad = __fadd_rn(rq[b].result, 1e-6f);
-        s.csig = __fmul_rn(c, __fmul_rn(1.4826f, mad));
+        s.csig = fit_csig(c, rq[b].result);
         s.mode = 0;
     }
 }
@@ -446,18 +403,8 @@ __global__ __launch_bounds__(256) void k_fb_resid(const float *__restrict__ z_al
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (blockIdx.x == 0 && threadIdx.x < 6) coef_out[b * 6 + threadIdx.x] = s.do_fit ? s.coef[threadIdx.x] : 0.f;
     if (i >= P) return;
-    const float cxf = (float)((w - 1) / 2.0), cyf = (float)((h - 1) / 2.0);
     const int y = i / w, x = i - y * w;
-    float fit = 0.f;
-    if (s.do_fit) {                                     // eval_poly2d's operation order (:1093-1097)
-        const float xn = __fdiv_rn(__fsub_rn((float)x, cxf), cxf), yn = __fdiv_rn(__fsub_rn((float)y, cyf), cyf);
-        fit = __fadd_rn(__fadd_rn(__fmul_rn(s.coef[0], xn), __fmul_rn(s.coef[1], yn)), s.coef[2]);
-        if (order >= 2) {
-            fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(s.coef[3], xn), xn));
-            fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(s.coef[4], xn), yn));
-            fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(s.coef[5], yn), yn));
-        }
-    }
+    const float fit = s.do_fit ? fit_eval(s.coef, order, fit_coord(x, fit_centre(w)), fit_coord(y, fit_centre(h))) : 0.f;
     out_all[b * (size_t)P + i] = __fsub_rn(z_all[b * (size_t)P + i], fit);
 }
 

@@ -24,6 +24,7 @@ namespace vf { __device__ unsigned long long g_fit_dbg[16]; __device__ unsigned 
 #define FIT_START() do { } while (0)
 #endif
 #include "select.hpp"
+#include "fit_rules.hpp"
 #include "chol.hpp"
 
 namespace vf {
@@ -48,8 +49,9 @@ struct FitCtx {
     {
         int y = magic ? (int)__umulhi((uint32_t)i, magic) : i / w, x = i - y * w;
         if (use_tab) { xn = tab[x]; yn = tab[w + y]; }
-        else { xn = __fdiv_rn(__fsub_rn((float)x, cxf), cxf); yn = __fdiv_rn(__fsub_rn((float)y, cyf), cyf); }
+        else { xn = fit_coord(x, cxf); yn = fit_coord(y, cyf); }
     }
+    // this kernel's own residual for the weights and medians: an fma chain, not fit_eval's order and not the column form
     __device__ inline float resid(float zz, float xn, float yn) const
     {
         float f = __fmul_rn(coef[0], xn);
@@ -94,11 +96,11 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
     const int nc = order >= 2 ? 6 : 3;
     const float *z = z_all + b * (size_t)P;
     const uint8_t *m = mask_all + b * (size_t)P;
-    const float cxf = (float)((w - 1) / 2.0), cyf = (float)((h - 1) / 2.0);
+    const float cxf = fit_centre(w), cyf = fit_centre(h);
     const bool use_tab = w + h <= FIT_TAB;
     if (use_tab) {
         for (int i = tid; i < w + h; i += SEL_T)
-            s_tab[i] = i < w ? __fdiv_rn(__fsub_rn((float)i, cxf), cxf) : __fdiv_rn(__fsub_rn((float)(i - w), cyf), cyf);
+            s_tab[i] = i < w ? fit_coord(i, cxf) : fit_coord(i - w, cyf);
     }
     __syncthreads();
 
@@ -107,9 +109,15 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
     // thread only ever touches the pixels tid, tid + 1024, ...: its own stores, so no fence is needed.
     float *zc = resid_all + b * (size_t)P;
     // the same pass counts the fitted pixels and finds the range of z (coefficients are still zero: r = z)
-    uint32_t cnt0 = 0, cntm = 0;
-    unsigned long long mn0 = ~0ull, mx0 = 0;
+    uint32_t cntm = 0;
+    SelRange rg;
     {
+        const auto first = [&](int p, float zz, uint8_t mk) {
+            const bool ok = mk && finitef(zz);
+            cntm += mk != 0;
+            zc[p] = ok ? zz : nanf32();
+            if (ok) rg.add(f2key(zz));
+        };
         int p = tid;
         for (; p + (FIT_U - 1) * SEL_T < P; p += FIT_U * SEL_T) {
             float zz[FIT_U];
@@ -117,20 +125,9 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
 #pragma unroll
             for (int u = 0; u < FIT_U; u++) { zz[u] = z[p + u * SEL_T]; mk[u] = m[p + u * SEL_T]; }
 #pragma unroll
-            for (int u = 0; u < FIT_U; u++) {
-                const bool ok = mk[u] && finitef(zz[u]);
-                cntm += mk[u] != 0;
-                zc[p + u * SEL_T] = ok ? zz[u] : __uint_as_float(0x7fc00000u);
-                if (ok) { const uint32_t key = f2key(zz[u]); cnt0++; if (key < mn0) mn0 = key; if (key + 1ull > mx0) mx0 = key + 1ull; }
-            }
+            for (int u = 0; u < FIT_U; u++) first(p + u * SEL_T, zz[u], mk[u]);
         }
-        for (; p < P; p += SEL_T) {
-            const float zz = z[p];
-            const bool ok = m[p] && finitef(zz);
-            cntm += m[p] != 0;
-            zc[p] = ok ? zz : __uint_as_float(0x7fc00000u);
-            if (ok) { const uint32_t key = f2key(zz); cnt0++; if (key < mn0) mn0 = key; if (key + 1ull > mx0) mx0 = key + 1ull; }
-        }
+        for (; p < P; p += SEL_T) first(p, z[p], m[p]);
     }
     FitCtx ctx;
     ctx.z = zc; ctx.m = m; ctx.tab = s_tab; ctx.use_tab = use_tab; ctx.w = w; ctx.magic = magic; ctx.cxf = cxf; ctx.cyf = cyf;
@@ -139,17 +136,11 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
 
     // ---- number of fitted pixels (mask != 0 and finite z) and the range of z (coefficients are still zero: r = z)
     uint32_t n, zkmin, zkmax;
-    {
-        __syncthreads();
-        n = block_sum<uint32_t>(cnt0, sh.wsum);
-        if (min_mask_count > 0) cntm = block_sum<uint32_t>(cntm, sh.wsum);
-        mn0 = block_min_u64(mn0, sh.red64);
-        mx0 = block_max_u64(mx0, sh.red64);
-        zkmin = (uint32_t)mn0; zkmax = mx0 ? (uint32_t)(mx0 - 1) : 0;
-        __syncthreads();
-    }
+    __syncthreads();
+    rg.reduce(sh.wsum, sh.red64, n, zkmin, zkmax, min_mask_count > 0, cntm);
+    __syncthreads();
     const float zmin = key2f(zkmin), zmax = key2f(zkmax);
-    const bool do_fit = (int)n >= min_count && (min_mask_count <= 0 || (int)cntm >= min_mask_count);
+    const bool do_fit = fit_gate((int)n, (int)cntm, min_count, min_mask_count);
 
     float csig = 1.f;      // c * sigma of the previous iteration
     for (int it = 0; do_fit && it < iters; it++) {
@@ -222,31 +213,17 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
         __syncthreads();
         for (int i = 0; i < 6; i++) ctx.coef[i] = s_coef[i];
         if (it == iters - 1) break;   // the weights of the last iteration are never used upstream
-        // ---- sigma = 1.4826 * (median |r - median r| + 1e-6)
-        // range of r = z - fit without a pass over the data: |xn|, |yn| <= 1, so |fit| <= sum |coef| (plus rounding slack); the
-        // histogram refinement only needs a range that CONTAINS the values
-        uint32_t nn = n, kmin, kmax;
+        // ---- the next step's scale from the two medians; their key ranges come from bounds, not from passes (fit_rules.hpp)
         ctx.mode = 0;
-        {
-            float fb = 0.f;
-            for (int i = 0; i < 6; i++) fb += fabsf(ctx.coef[i]);
-            fb = fb * 1.0001f + 1e-30f;
-            kmin = f2key(zmin - fb - 1e-6f * fabsf(zmin)); kmax = f2key(zmax + fb + 1e-6f * fabsf(zmax));
-        }
-        float medr = block_median(ctx, P, sh, nn, kmin, kmax);
+        const FitKeys kr = fit_resid_range(ctx.coef, zmin, zmax);
+        float medr = block_median(ctx, P, sh, n, kr.kmin, kr.kmax);
         __syncthreads();
         ctx.med = medr; ctx.mode = 1;
-        {
-            // |r - med| lies in [0, max(rmax - med, med - rmin)] (float subtraction is monotone): no second min/max pass
-            float hi1 = fabsf(__fsub_rn(key2f(kmax), medr)), hi2 = fabsf(__fsub_rn(key2f(kmin), medr));
-            kmin = f2key(0.f); kmax = f2key(hi1 > hi2 ? hi1 : hi2);
-        }
-        float mad = block_median(ctx, P, sh, nn, kmin, kmax);
+        const FitKeys ka = fit_mad_range(kr, medr);
+        float mad = block_median(ctx, P, sh, n, ka.kmin, ka.kmax);
         __syncthreads();
         ctx.mode = 0;
-        mad = __fadd_rn(mad, 1e-6f);
-        float sigma = __fmul_rn(1.4826f, mad);
-        csig = __fmul_rn(c, sigma);
+        csig = fit_csig(c, mad);
     }
     if (tid < 6) coef_out[b * 6 + tid] = do_fit ? ctx.coef[tid] : 0.f;
     // residual plane: z - fit, fit evaluated as eval_poly2d does (shape_ftp.py:1093-1097, :1132-1135)
@@ -257,12 +234,7 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
         if (do_fit) {
             float xn, yn;
             ctx.coords(p, xn, yn);
-            fit = __fadd_rn(__fadd_rn(__fmul_rn(ctx.coef[0], xn), __fmul_rn(ctx.coef[1], yn)), ctx.coef[2]);
-            if (order >= 2) {
-                fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(ctx.coef[3], xn), xn));
-                fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(ctx.coef[4], xn), yn));
-                fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(ctx.coef[5], yn), yn));
-            }
+            fit = fit_eval(ctx.coef, order, xn, yn);
         }
         out[p] = __fsub_rn(zz, fit);
     }
@@ -312,16 +284,16 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     const int nc = order >= 2 ? 6 : 3;
     const float *z = z_all + b * (size_t)P;
     const uint8_t *m = mask_all + b * (size_t)P;
-    const float cxf = (float)((w - 1) / 2.0), cyf = (float)((h - 1) / 2.0);
-    for (int i = tid; i < FIT_YTAB; i += NT) s_yn[i] = __fdiv_rn(__fsub_rn((float)i, cyf), cyf);       // rows >= h: only read for samples that are NaN
+    const float cxf = fit_centre(w), cyf = fit_centre(h);
+    for (int i = tid; i < FIT_YTAB; i += NT) s_yn[i] = fit_coord(i, cyf);       // rows >= h: only read for samples that are NaN
     const int col = tid % cols_pad, grp = __builtin_amdgcn_readfirstlane(tid / cols_pad);   // uniform inside a wave (cols_pad % 64 == 0)
     const bool owner = col < w && grp < groups;
-    const float xn = __fdiv_rn(__fsub_rn((float)col, cxf), cxf);
-    const float qnan = __uint_as_float(0x7fc00000u);
+    const float xn = fit_coord(col, cxf);
+    const float qnan = nanf32();
     // ---- load this thread's column samples; count fitted / masked pixels, range of z
     float zr[RP];
-    uint32_t cnt0 = 0, cntm = 0;
-    unsigned long long mn0 = ~0ull, mx0 = 0;
+    uint32_t cntm = 0;
+    SelRange rg;
     {
         constexpr int LU = 8;
         uint8_t mk[LU];
@@ -345,20 +317,17 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
                     const bool ok = mk[v] && finitef(zz);
                     cntm += mk[v] != 0;
                     zr[u] = ok ? zz : qnan;
-                    if (ok) { const uint32_t key = f2key(zz); cnt0++; if (key < mn0) mn0 = key; if (key + 1ull > mx0) mx0 = key + 1ull; }
+                    if (ok) rg.add(f2key(zz));
                 }
             }
         }
     }
     __syncthreads();
-    const uint32_t n = block_sum<uint32_t>(cnt0, sh.wsum);
-    if (min_mask_count > 0) cntm = block_sum<uint32_t>(cntm, sh.wsum);
-    mn0 = block_min_u64(mn0, sh.red64);
-    mx0 = block_max_u64(mx0, sh.red64);
-    const uint32_t zkmin = (uint32_t)mn0, zkmax = mx0 ? (uint32_t)(mx0 - 1) : 0;
+    uint32_t n, zkmin, zkmax;
+    rg.reduce(sh.wsum, sh.red64, n, zkmin, zkmax, min_mask_count > 0, cntm);
     __syncthreads();
     const float zmin = key2f(zkmin), zmax = key2f(zkmax);
-    const bool do_fit = (int)n >= min_count && (min_mask_count <= 0 || (int)cntm >= min_mask_count);
+    const bool do_fit = fit_gate((int)n, (int)cntm, min_count, min_mask_count);
     SEL_STAMP(8);
 
     float coef[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -370,8 +339,7 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     // the samples (hundreds of spills)
     auto resid_of = [&](int g0, int u, float zz) -> float {
         const float yn = s_yn[g0 + groups * u];                      // < FIT_YTAB (checked by the launcher)
-        const float fit = __fadd_rn(fmaf(yn, Bt, At), __fmul_rn(coef[5], __fmul_rn(yn, yn)));
-        return __fsub_rn(zz, fit);
+        return __fsub_rn(zz, fit_col_eval(At, Bt, coef[5], yn));
     };
     auto each = [&](auto body) {
         int g0 = grp;
@@ -407,8 +375,7 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
             if (finitef(__fmul_rn(zz, inv_csig))) {               // (finite exactly when zz is; not invariant across the IRLS loop, see `each`)
                 float wt = 1.f;
                 if (it > 0) {
-                    const float uu = __fmul_rn(resid_of(g0, u, zz), inv_csig);
-                    wt = __fdiv_rn(1.0f, __fadd_rn(1.0f, __fmul_rn(uu, uu)));
+                    wt = fit_cauchy(resid_of(g0, u, zz), inv_csig);
                 }
                 const double yd = (double)s_yn[g0 + groups * u];
                 const double w2 = (double)wt * (double)wt;
@@ -432,7 +399,7 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
 #pragma unroll
             for (int bb = 0; bb <= DEG; bb++)
 #pragma unroll
-                for (int aa = 0; aa + bb <= DEG; aa++) vs[k++] = xp[aa] * Pb[bb];     // k = index of (a, b), b-major
+                for (int aa = 0; aa + bb <= DEG; aa++) vs[k++] = xp[aa] * Pb[bb];     // k = fit_mono(aa, bb, DEG)
             vs[NM + 0] = x1 * Qb[0]; vs[NM + 1] = Qb[1]; vs[NM + 2] = Qb[0];
             if constexpr (NC == 6) { vs[NM + 3] = x2 * Qb[0]; vs[NM + 4] = x1 * Qb[1]; vs[NM + 5] = Qb[2]; }
         }
@@ -455,18 +422,8 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
 #pragma unroll
             for (int i = 0; i < NV; i++) S[i] = readlane_f64(sv, i);
             SEL_STAMP(12);
-            // monomial (a, b) -> index in vs: b-major with DEG + 1, DEG, ... entries
-            const int ea[6] = {1, 0, 0, 2, 1, 0}, eb[6] = {0, 1, 0, 0, 1, 2};          // exponents of the basis [x, y, 1, x^2, xy, y^2]
             double A[6][6], rhs[6];
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-                    const int a = ea[i] + ea[j], bb = eb[i] + eb[j], k = bb * (DEG + 1) - bb * (bb - 1) / 2 + a;
-                    A[i][j] = (i < NC && j < NC) ? S[k < NM ? k : 0] : 0.0;
-                }
-                rhs[i] = i < NC ? S[NM + i] : 0.0;
-            }
+            fit_assemble<NC, DEG>(S, A, rhs);
             const bool ok = chol_solve<NC>(A, rhs);
             if (lane == 0) {
 #pragma unroll
@@ -476,35 +433,25 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         SEL_STAMP(13);
         __syncthreads();
         for (int i = 0; i < 6; i++) coef[i] = s_coef[i];
-        At = fmaf(coef[3], __fmul_rn(xn, xn), fmaf(coef[0], xn, coef[2]));
-        Bt = fmaf(coef[4], xn, coef[1]);
+        const FitCol ct = fit_col_terms(coef, xn);
+        At = ct.At; Bt = ct.Bt;
         SEL_STAMP(7);
     };
     for (int it = 0; do_fit && it < iters; it++) {
         if (nc == 6) irls_step(std::integral_constant<int, 6>(), it);
         else irls_step(std::integral_constant<int, 3>(), it);
         if (it == iters - 1) break;   // the weights of the last iteration are never used upstream
-        // ---- sigma = 1.4826 * (median |r - median r| + 1e-6); the value ranges come from bounds on |fit| (|xn|, |yn| <= 1)
-        uint32_t kmin, kmax;
+        // ---- the next step's scale from the two medians
         mode = 0;
-        {
-            float fb = 0.f;
-            for (int i = 0; i < 6; i++) fb += fabsf(coef[i]);
-            fb = fb * 1.0001f + 1e-30f;
-            kmin = f2key(zmin - fb - 1e-6f * fabsf(zmin)); kmax = f2key(zmax + fb + 1e-6f * fabsf(zmax));
-        }
-        const float medr = block_median_each<NT>(each, sh, n, kmin, kmax);
+        const FitKeys kr = fit_resid_range(coef, zmin, zmax);
+        const float medr = block_median_each<NT>(each, sh, n, kr.kmin, kr.kmax);
         __syncthreads();
         med = medr; mode = 1;
-        {
-            float hi1 = fabsf(__fsub_rn(key2f(kmax), medr)), hi2 = fabsf(__fsub_rn(key2f(kmin), medr));
-            kmin = f2key(0.f); kmax = f2key(hi1 > hi2 ? hi1 : hi2);
-        }
-        float mad = block_median_each<NT>(each, sh, n, kmin, kmax);
+        const FitKeys ka = fit_mad_range(kr, medr);
+        const float mad = block_median_each<NT>(each, sh, n, ka.kmin, ka.kmax);
         __syncthreads();
         mode = 0;
-        mad = __fadd_rn(mad, 1e-6f);
-        csig = __fmul_rn(c, __fmul_rn(1.4826f, mad));
+        csig = fit_csig(c, mad);
     }
     if (tid < 6) coef_out[b * 6 + tid] = do_fit ? coef[tid] : 0.f;
     // residual plane: z - fit over the WHOLE plane, unfitted pixels included (fit evaluated as eval_poly2d does, :1093-1097, :1132-1135)
@@ -521,16 +468,7 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         for (int u = 0; u < RP; u++) {
             const int y = grp + groups * u;
             if (y < h) {
-                float fit = 0.f;
-                if (do_fit) {
-                    const float yn = s_yn[y];
-                    fit = __fadd_rn(__fadd_rn(__fmul_rn(coef[0], xn), __fmul_rn(coef[1], yn)), coef[2]);
-                    if (order >= 2) {
-                        fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(coef[3], xn), xn));
-                        fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(coef[4], xn), yn));
-                        fit = __fadd_rn(fit, __fmul_rn(__fmul_rn(coef[5], yn), yn));
-                    }
-                }
+                const float fit = do_fit ? fit_eval(coef, order, xn, s_yn[y]) : 0.f;
                 out[(size_t)y * w + col] = __fsub_rn(zr[u], fit);
             }
         }

@@ -15,12 +15,8 @@ struct PlaneGetter {
     {
         // both loads unconditional, so that the SEL_U elements of a batch are all in flight together (select.hpp: sel_foreach)
         const uint8_t mk = m[i];
-        float x = v[i];
-        bool ok = mk != 0 && finitef(x);
-        if (use_abs) x = fabsf(x);
-        if (use_le && !(x <= le)) ok = false;
-        key = f2key(x);
-        return ok;
+        const float x = v[i];
+        return sel_element(mk, x, use_abs, use_le ? &le : nullptr, key);
     }
 };
 
@@ -51,7 +47,8 @@ constexpr int SEL_MAX_CHAIN = 4;
 // where the results go: plain, request j of frame b at p[0][b * nreq + j]; chained, at p[j][b]
 struct SelOut { float *p[SEL_MAX_CHAIN]; };
 
-// count / min / max of this thread's keys <= cut, reduced over the workgroup (block_minmax of select.hpp for registers)
+// count / min / max of this thread's keys <= cut, reduced over the workgroup: SelRange's rule (select.hpp) in this kernel's own spelling, on
+// 32-bit keys with SEL_NOKEY as "none" inside the NS-times unrolled loop; the 64-bit accumulator there would change the kernel's text
 template <int NS>
 __device__ inline void resident_minmax(const uint32_t (&key)[NS], uint32_t cut, SelShared &sh, uint32_t &n, uint32_t &kmin, uint32_t &kmax)
 {
@@ -116,21 +113,14 @@ __global__ __launch_bounds__(SEL_T) void k_select_resident(const float *__restri
                 resident_minmax<NS>(key, cut, sh, n, kmin, kmax);
             }
         }
-        // block_median_each / block_percentile of select.hpp, with the one block_select2_each they share written once (it is inlined, and
-        // its sweeps are unrolled NS times: a copy per kind of request doubles the kernel's code)
-        const float q = reqs[j];
-        const bool median = q < 0.f;
-        uint32_t k = 0; float gm = 0.f; bool top;
-        if (median) k = (n & 1u) ? (n - 1) / 2 : n / 2 - 1;
-        else if (n > 0) np_percentile_index(n, q, k, gm, top);
-        if (n == 0) r = nanf32();
-        else if (median && n == 1) r = key2f(kmin);
-        else if (!median && k + 1 >= n) r = key2f(kmax);          // last element: both neighbours are the maximum
+        // one block_select2_each for every kind of request (it is inlined, and its sweeps are unrolled NS times: a copy per kind, as
+        // block_median_each next to block_percentile would make, doubles the kernel's code)
+        const SelPlan p = sel_plan(n, reqs[j], kmin, kmax);
+        if (p.done) r = p.result;
         else {
             uint32_t ka, kb;
-            block_select2_each<SEL_T>(each, n, k, sh, kmin, kmax, ka, kb);
-            if (median) r = (n & 1u) ? key2f(ka) : __fdiv_rn(__fadd_rn(key2f(ka), key2f(kb)), 2.0f);
-            else r = np_lerp(key2f(ka), key2f(kb), gm);
+            block_select2_each<SEL_T>(each, n, p.k, sh, kmin, kmax, ka, kb);
+            r = sel_result(p, ka, kb);
         }
         if (threadIdx.x == 0) {
             if (chained) (j == 0 ? out.p[0] : j == 1 ? out.p[1] : j == 2 ? out.p[2] : out.p[3])[b] = r;      // no runtime index into the argument

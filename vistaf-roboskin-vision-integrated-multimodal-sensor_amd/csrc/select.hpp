@@ -28,6 +28,122 @@ struct SelShared {
     uint32_t s_bucket, s_before, s_cnt, s_ncand, s_a, s_b, s_found;
 };
 
+// ---- the rules every dataflow shares (k_select.hip, k_fit.hip, k_big.hip); tests/diag/fit_select_host_check.hip runs the host-callable ones
+#define SEL_RULE __device__ __attribute__((always_inline)) inline
+#define SEL_HRULE __host__ __device__ __attribute__((always_inline)) inline
+
+// Element rule: is the plane element (mask byte mk, value x) part of the selection, and its key.  le: the frame's threshold, or null.
+SEL_RULE bool sel_element(uint8_t mk, float x, bool use_abs, const float *le, uint32_t &key)
+{
+    bool ok = mk != 0 && finitef(x);
+    if (use_abs) x = fabsf(x);
+    if (le && !(x <= *le)) ok = false;
+    key = f2key(x);
+    return ok;
+}
+
+// Key range: count, smallest and largest key of the valid elements.  add() per element and thread; reduce() over the workgroup (blockDim.x
+// <= 1024, s32 / s64: 16 entries each), result in all threads.  All threads must have passed a barrier since s32 / s64 were last read,
+// and must pass one before they are written again.  with_extra: a second per-thread count is summed in between (the fit's mask pixels).
+struct SelRange {
+    uint32_t c = 0;
+    unsigned long long mn = ~0ull, mx = 0;          // smallest key; largest key + 1 (0: none)
+    SEL_RULE void add(uint32_t key) { c++; if (key < mn) mn = key; if (key + 1ull > mx) mx = key + 1ull; }
+    SEL_RULE void reduce(uint32_t *s32, unsigned long long *s64, uint32_t &n, uint32_t &kmin, uint32_t &kmax, bool with_extra, uint32_t &extra) const
+    {
+        n = block_sum<uint32_t>(c, s32);
+        if (with_extra) extra = block_sum<uint32_t>(extra, s32);
+        const unsigned long long bmn = block_min_u64(mn, s64), bmx = block_max_u64(mx, s64);
+        kmin = (uint32_t)bmn; kmax = bmx ? (uint32_t)(bmx - 1) : 0;
+    }
+    SEL_RULE void reduce(uint32_t *s32, unsigned long long *s64, uint32_t &n, uint32_t &kmin, uint32_t &kmax) const
+    {
+        uint32_t none = 0;
+        reduce(s32, s64, n, kmin, kmax, false, none);
+    }
+};
+
+// NumPy 2.x percentile (method 'linear') of float32 data, float32 arithmetic.  The linear method has its own virtual index,
+// (n - 1) * q (numpy/lib/_function_base_impl.py: _QuantileMethods['linear']), not the general n*q + (alpha + q*(1 - alpha - beta)) - 1:
+//   vi = (n-1)*q ; prev = floor(vi) ; gamma = vi - prev
+//   res = a + (b-a)*gamma  [ b - (b-a)*(1-gamma) when gamma >= 0.5 ]
+// (The general form rounds differently in float32 and moved the result by a few ulps: [-2.5, 7] at q = 8 gave 0xbfdeb84e for 0xbfdeb852.)
+__host__ __device__ inline void np_percentile_index(uint32_t n, float q32, uint32_t &k, float &gamma, bool &top)
+{
+    const float vi = rn_mul((float)(n - 1), q32);
+    top = vi >= (float)(n - 1);
+    if (vi < 0.0f) { k = 0; gamma = 0.0f; return; }
+    float pf = floorf(vi);
+    k = (uint32_t)pf;
+    gamma = rn_sub(vi, pf);
+    if (top) { k = n - 1; gamma = 0.0f; }
+}
+__host__ __device__ inline float np_lerp(float a, float b, float t)
+{
+    float d = rn_sub(b, a);
+    float r = rn_add(a, rn_mul(d, t));
+    if (t >= 0.5f) r = rn_sub(b, rn_mul(d, rn_sub(1.0f, t)));
+    return r;
+}
+
+// Plan of one request over n valid elements with keys in [kmin, kmax]; q = float32(percent) / float32(100), q < 0: np.median.  Either the
+// result is known (no element: the quiet NaN; a median of one element; a rank at the top: the maximum) or the keys of rank k and k + 1 are
+// wanted and sel_result turns them into the float: the lower one alone (median, odd n), their float32 mean (median, even n), np_lerp.
+// The kind is worked out from (n, q) where it is needed: held as a value of its own across a selection it cost the resident kernels a
+// register per thread (k_select_resident<64>: two more spilled).
+enum : uint32_t { SEL_ONE = 0, SEL_MEAN2 = 1, SEL_LERP = 2 };
+struct SelPlan {
+    bool done; float result; uint32_t k; float gamma; uint32_t n; float q;
+    __host__ __device__ uint32_t kind() const { return q < 0.f ? ((n & 1u) ? SEL_ONE : SEL_MEAN2) : SEL_LERP; }
+};
+SEL_HRULE SelPlan sel_plan(uint32_t n, float q, uint32_t kmin, uint32_t kmax)
+{
+    SelPlan p = {true, 0.f, 0u, 0.f, n, q};
+    if (n == 0) p.result = nanf32();
+    else if (q < 0.f) {
+        if (n == 1) p.result = key2f(kmin);
+        else { p.done = false; p.k = (n & 1u) ? (n - 1) / 2 : n / 2 - 1; p.gamma = 0.5f; }
+    } else {
+        bool top;
+        np_percentile_index(n, q, p.k, p.gamma, top);
+        if (p.k + 1 >= n) p.result = key2f(kmax);          // last element: both neighbours are the maximum
+        else p.done = false;
+    }
+    return p;
+}
+SEL_HRULE float sel_result_kind(uint32_t kind, float gamma, uint32_t key_a, uint32_t key_b)
+{
+    const float a = key2f(key_a), b = key2f(key_b);
+    if (kind == SEL_LERP) return np_lerp(a, b, gamma);
+    return kind == SEL_MEAN2 ? rn_div(rn_add(a, b), 2.0f) : a;
+}
+SEL_HRULE float sel_result(const SelPlan p, uint32_t key_a, uint32_t key_b) { return sel_result_kind(p.kind(), p.gamma, key_a, key_b); }
+
+// Level rules of the histogram refinement over the keys in [lo, hi], BITS digits per level: a key falls into bucket (key - lo) >> sel_shift
+SEL_HRULE int sel_shift(uint32_t lo, uint32_t hi, int BITS)
+{
+    const uint32_t range = hi - lo;
+    const int bits = range ? 32 - __builtin_clz(range) : 0;
+    return bits > BITS ? bits - BITS : 0;
+}
+// [lo, hi] narrowed to the chosen bucket.  The last bucket of a level is clipped at hi; `nhi < nlo` is the bucket that wraps past 2^32.
+struct SelSpan { uint32_t lo, hi; };
+SEL_HRULE SelSpan sel_narrow(uint32_t lo, uint32_t hi, uint32_t bucket, uint32_t shift)
+{
+    const uint32_t nlo = lo + (bucket << shift);
+    uint32_t nhi = shift ? nlo + ((1u << shift) - 1u) : nlo;
+    if (nhi > hi || nhi < nlo) nhi = hi;
+    return {nlo, nhi};
+}
+// The next level's width is NOT shared.  The per-frame code (block_select2_each) calls sel_shift on the narrowed range again; the chain
+// (k_big.hip: k_sb_pick) takes BITS digits off the previous width, so that its three launches per selection are fixed in advance.  The two
+// differ when the last bucket was clipped at hi (the narrowed range is then shorter than a bucket); both end at one key within three levels.
+SEL_HRULE uint32_t sel_shift_chain_next(uint32_t shift, int BITS) { return shift > (uint32_t)BITS ? shift - (uint32_t)BITS : 0u; }
+// The next order statistic after the key a of rank k: a again if it is duplicated (k + 1 < cnt_le, the number of keys <= a) or nothing lies
+// above (min_gt, the smallest key above a, is all ones: no valid key is), else min_gt.
+template <class K>
+SEL_HRULE uint32_t sel_next(uint32_t k, uint32_t cnt_le, K min_gt, uint32_t a) { return (k + 1 < cnt_le || min_gt == (K) ~(K)0) ? a : (uint32_t)min_gt; }
+
 // Visit every valid element (get(i, key) -> bool valid), SEL_U elements per thread at a time: the SEL_U loads of a
 // batch are issued together, so a pass costs P / (SEL_T * SEL_U) memory round trips per thread instead of P / SEL_T.
 constexpr int SEL_U = 8;
@@ -64,10 +180,8 @@ __device__ __attribute__((always_inline)) inline void block_select2_each(Each ea
     uint32_t lo = kmin, hi = kmax, below = 0;
     uint32_t a = 0, b = 0;
     for (;;) {
-        uint32_t range = hi - lo;
-        if (range == 0) { a = lo; break; }
-        int bits = 32 - __clz(range);
-        int shift = bits > SEL_BITS ? bits - SEL_BITS : 0;
+        if (hi == lo) { a = lo; break; }
+        const int shift = sel_shift(lo, hi, SEL_BITS);
         for (int i = tid; i < SEL_NB; i += NT) sh.hist[i] = 0;
         __syncthreads();
         SEL_STAMP(0);
@@ -100,10 +214,8 @@ __device__ __attribute__((always_inline)) inline void block_select2_each(Each ea
         __syncthreads();
         uint32_t bsel = sh.s_bucket, cnt = sh.s_cnt;
         below += sh.s_before;
-        uint32_t nlo = lo + (bsel << shift);
-        uint32_t nhi = shift ? nlo + ((1u << shift) - 1u) : nlo;
-        if (nhi > hi || nhi < nlo) nhi = hi;
-        lo = nlo; hi = nhi;
+        const SelSpan nx = sel_narrow(lo, hi, bsel, (uint32_t)shift);
+        lo = nx.lo; hi = nx.hi;
         __syncthreads();
         SEL_STAMP(2);
         if (shift == 0) { a = lo; break; }
@@ -168,7 +280,7 @@ __device__ __attribute__((always_inline)) inline void block_select2_each(Each ea
         __syncthreads();
         uint32_t tot = block_sum<uint32_t>(le, sh.wsum);
         unsigned long long mn = block_min_u64(nxt, sh.red64);
-        b = (k + 1 < tot || mn == ~0ull) ? a : (uint32_t)mn;
+        b = sel_next(k, tot, mn, a);
         __syncthreads();
         SEL_STAMP(5);
     }
@@ -187,70 +299,41 @@ __device__ inline void block_select2(F get, int P, uint32_t n, uint32_t k, SelSh
 template <class F>
 __device__ inline void block_minmax(F get, int P, SelShared &sh, uint32_t &n, uint32_t &kmin, uint32_t &kmax)
 {
-    uint32_t c = 0;
-    unsigned long long mn = ~0ull, mx = 0;
-    sel_foreach(get, P, [&](uint32_t key) { c++; if (key < mn) mn = key; if (key + 1ull > mx) mx = key + 1ull; });
+    SelRange rg;
+    sel_foreach(get, P, [&](uint32_t key) { rg.add(key); });
     __syncthreads();
-    n = block_sum<uint32_t>(c, sh.wsum);
-    mn = block_min_u64(mn, sh.red64);
-    mx = block_max_u64(mx, sh.red64);
-    kmin = (uint32_t)mn; kmax = mx ? (uint32_t)(mx - 1) : 0;
+    rg.reduce(sh.wsum, sh.red64, n, kmin, kmax);
     __syncthreads();
 }
 
-// NumPy 2.x percentile (method 'linear') of float32 data, float32 arithmetic.  The linear method has its own virtual index,
-// (n - 1) * q (numpy/lib/_function_base_impl.py: _QuantileMethods['linear']), not the general n*q + (alpha + q*(1 - alpha - beta)) - 1:
-//   vi = (n-1)*q ; prev = floor(vi) ; gamma = vi - prev
-//   res = a + (b-a)*gamma  [ b - (b-a)*(1-gamma) when gamma >= 0.5 ]
-// (The general form rounds differently in float32 and moved the result by a few ulps: [-2.5, 7] at q = 8 gave 0xbfdeb84e for 0xbfdeb852.)
-__device__ inline void np_percentile_index(uint32_t n, float q32, uint32_t &k, float &gamma, bool &top)
-{
-    const float vi = __fmul_rn((float)(n - 1), q32);
-    top = vi >= (float)(n - 1);
-    if (vi < 0.0f) { k = 0; gamma = 0.0f; return; }
-    float pf = floorf(vi);
-    k = (uint32_t)pf;
-    gamma = __fsub_rn(vi, pf);
-    if (top) { k = n - 1; gamma = 0.0f; }
-}
-__device__ inline float np_lerp(float a, float b, float t)
-{
-    float d = __fsub_rn(b, a);
-    float r = __fadd_rn(a, __fmul_rn(d, t));
-    if (t >= 0.5f) r = __fsub_rn(b, __fmul_rn(d, __fsub_rn(1.0f, t)));
-    return r;
-}
-
-// percentile (q32 = float32(q)/float32(100)) of valid elements; NaN when n == 0
+// percentile (q32 = float32(q)/float32(100) >= 0) of valid elements; NaN when n == 0
 template <class F>
 __device__ inline float block_percentile(F get, int P, float q32, SelShared &sh, uint32_t n, uint32_t kmin, uint32_t kmax)
 {
-    if (n == 0) return nanf32();
-    uint32_t k; float g; bool top;
-    np_percentile_index(n, q32, k, g, top);
+    const SelPlan p = sel_plan(n, q32, kmin, kmax);
+    if (p.done) return p.result;
     uint32_t ka, kb;
-    if (k + 1 >= n) {  // last element: both neighbours are the maximum
-        if (k >= n) k = n - 1;
-        return key2f(kmax);
-    }
-    block_select2(get, P, n, k, sh, kmin, kmax, ka, kb);
-    return np_lerp(key2f(ka), key2f(kb), g);
+    block_select2(get, P, n, p.k, sh, kmin, kmax, ka, kb);
+    return sel_result(p, ka, kb);
 }
 
 // np.median of valid elements (mean of the two middle values in float32 for even n)
 template <int NT = SEL_T, class Each>
 __device__ __attribute__((always_inline)) inline float block_median_each(Each each, SelShared &sh, uint32_t n, uint32_t kmin, uint32_t kmax)
 {
-    if (n == 0) return nanf32();
-    if (n == 1) return key2f(kmin);
+    const SelPlan p = sel_plan(n, -1.f, kmin, kmax);
+    if (p.done) return p.result;
     uint32_t ka, kb;
-    block_select2_each<NT>(each, n, (n & 1u) ? (n - 1) / 2 : n / 2 - 1, sh, kmin, kmax, ka, kb);
-    return (n & 1u) ? key2f(ka) : __fdiv_rn(__fadd_rn(key2f(ka), key2f(kb)), 2.0f);
+    block_select2_each<NT>(each, n, p.k, sh, kmin, kmax, ka, kb);
+    return sel_result(p, ka, kb);
 }
 template <class F>
 __device__ inline float block_median(F get, int P, SelShared &sh, uint32_t n, uint32_t kmin, uint32_t kmax)
 {
     return block_median_each<SEL_T>([&](auto body) { sel_foreach(get, P, body); }, sh, n, kmin, kmax);
 }
+
+#undef SEL_RULE
+#undef SEL_HRULE
 
 }  // namespace vf
