@@ -181,6 +181,9 @@ SIGNATURES = {
         "vistaf_ftp_test_build_full_tables": (ci, [vp, vp, ci, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_dft_forward": (ci, [vp, vp, vp, vp, sz, sz, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
         "vistaf_ftp_test_dft_inverse": (ci, [vp, ci, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, ci, ci, ci, ci, ci, vp]),
+        "vistaf_ftp_test_morph": (ci, [vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, ci, vp]),
+        "vistaf_ftp_test_tempseg_plane": (ci, [vp, cs, vp, sz, vp]),
+        "vistaf_ftp_test_tempseg_sign": (ci, [vp, cd, vp, vp, vp, P(cd), sz, vp]),
     },
     "TEMP_EXPORTS": {        # include/vistaf_temp.h
         "vistaf_tempseg_default_config": (ci, [P(CTempSegConfig)]),

@@ -1082,6 +1082,41 @@ int vistaf_ftp_test_blob_filter(float *depth_inout, const uint8_t *cand, const i
     return hook_finish(peak_bits, nullptr, (hipStream_t)stream);
 }
 
+// ---- launch_morph on caller-supplied device planes, each of its three kernels forced or dispatched
+namespace {
+// A test element no cv shape gives: row i spans |i - k / 2| either side of the anchor (widest at the first and last row, the anchor alone in
+// the middle).  Its rows are not nested towards the centre, so a pixel outside the image that wrongly took part would show.
+RowSpanSE hourglass_se(int k)
+{
+    RowSpanSE se;
+    se.k = k;
+    for (int i = 0; i < 33; i++) { se.lo[i] = 1; se.hi[i] = -1; }
+    for (int i = 0; i < k; i++) { const int a = std::abs(i - k / 2); se.lo[i] = (int8_t)(-a); se.hi[i] = (int8_t)a; }
+    return se;
+}
+}  // namespace
+int vistaf_ftp_test_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, int shape, int kx, int ky, int dilate, const uint8_t *and_static,
+                          const uint8_t *and_frame, int tier, void *stream)
+{
+    if (!src || !dst || src == dst || B < 1 || B > 65535 || h < 1 || h > 65535 || w < 1 || (size_t)B * h * w > 0x7fffffffull)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (shape < 0 || shape > 2) return fail(VISTAF_E_INVALID, "shape must be 0 (ellipse), 1 (rectangle) or 2 (hourglass)");
+    if (shape == 2 && (kx < 3 || kx > 33 || kx % 2 == 0)) return fail(VISTAF_E_INVALID, "hourglass size must be odd, 3..33");
+    if (shape == 0 && (kx < 1 || kx > 33)) return fail(VISTAF_E_INVALID, "ellipse size must be 1..33");
+    if (shape == 1 && (kx < 1 || kx > 127 || ky < 1 || ky > 33)) return fail(VISTAF_E_INVALID, "rectangle must be 1..127 wide and 1..33 tall");
+    if (tier < 0 || tier > 4) return fail(VISTAF_E_INVALID, "tier must be 0..4");
+    const RowSpanSE se = shape == 0 ? ellipse_se(kx) : shape == 1 ? rect_se(odd_up(kx), odd_up(ky)) : hourglass_se(kx);
+    if (tier == MORPH_PREFIX && w >= 65536) return fail(VISTAF_E_INVALID, "tier 2: the uint16 row counts take rows shorter than 65536");
+    if (tier == MORPH_BITS && !morph_bits_ok(se, h, w)) return fail(VISTAF_E_INVALID, "tier 3: the bit-plane kernel does not take this frame or element");
+    const bool scratch = tier == 0 || tier == MORPH_PREFIX;
+    const int ran = (tier == 0 || tier == 4) ? morph_tier(se, h, w, scratch) : tier;
+    uint16_t *prefix = nullptr;
+    if (scratch) HIPCHK(hipMalloc((void **)&prefix, (size_t)B * h * w * sizeof(uint16_t)));
+    launch_morph(src, dst, B, h, w, se, dilate != 0, and_static, and_frame, (hipStream_t)stream, prefix, (tier == 0 || tier == 4) ? 0 : tier);
+    const int rc = hook_finish(prefix, nullptr, (hipStream_t)stream);
+    return rc ? rc : ran;
+}
+
 // ---- the three binary-mask chains (bad_mask_chain, reliable_mask_chain, contact_mask_chain above: the session's own functions) on
 // caller-supplied device planes
 namespace {

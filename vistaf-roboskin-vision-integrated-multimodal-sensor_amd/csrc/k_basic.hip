@@ -192,9 +192,10 @@ __global__ __launch_bounds__(MB_T) void k_morph_bits(const uint8_t *__restrict__
 }
 
 void launch_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, const RowSpanSE &se, bool dilate,
-                  const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch)
+                  const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch, int force)
 {
-    if (morph_bits_ok(se, h, w)) {
+    const int tier = force ? force : morph_tier(se, h, w, prefix_scratch != nullptr);
+    if (tier == MORPH_BITS) {
         MorphSeq seq;
         seq.n = 1; seq.dilate[0] = dilate ? 1 : 0; seq.se[0] = se;
         size_t lds = (size_t)h * ((w + 63) >> 6) * 16;
@@ -202,7 +203,7 @@ void launch_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, const R
         return;
     }
     dim3 grid((w + 255) / 256, h, B);
-    if (prefix_scratch && se.k >= 7 && w < 65536) {
+    if (tier == MORPH_PREFIX) {
         int rows = B * h;
         hipLaunchKernelGGL(k_row_prefix, dim3((rows + 3) / 4), dim3(256), 0, st, src, prefix_scratch, rows, w);
         hipLaunchKernelGGL(k_morph_prefix, grid, dim3(256), 0, st, prefix_scratch, dst, h, w, se, dilate ? 1 : 0, and_static, and_frame);

@@ -49,8 +49,10 @@ void launch_to_gray(const void *frames, int format, float *gray, int B, int P, h
 void launch_sobel_mag(const float *img, float *grad, int B, int h, int w, hipStream_t st);
 void launch_bad_flags(const float *img, const float *grad, const uint8_t *valid, const float *thr_hi, const float *thr_g,
                       uint8_t *bad, int B, int P, hipStream_t st);
+// force: 0 the dispatch (morph_tier of mask_bits.hpp), or a MorphTier the caller has checked the frame and element for (vistaf_ftp_test_morph)
+enum MorphTier { MORPH_GENERIC = 1, MORPH_PREFIX = 2, MORPH_BITS = 3 };      // k_morph; k_row_prefix + k_morph_prefix; k_morph_bits
 void launch_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, const RowSpanSE &se, bool dilate,
-                  const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch = nullptr);
+                  const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch = nullptr, int force = 0);
 void launch_morph_seq(const uint8_t *src, uint8_t *dst, uint8_t *tmp, int B, int h, int w, const RowSpanSE &se, const int *dilates, int n,
                       const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch = nullptr);
 void launch_gauss_rows(const float *src, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st);

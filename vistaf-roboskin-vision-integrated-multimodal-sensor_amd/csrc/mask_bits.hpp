@@ -33,6 +33,13 @@ inline bool morph_bits_ok(const RowSpanSE &se, int h, int w)
     }
     return (size_t)h * ((w + 63) >> 6) * 16 <= 64 * 1024;
 }
+// The kernel launch_morph runs (MorphTier of kernels.hpp): the bit planes where they apply, the row prefix sums for elements of 7 rows and
+// more when the caller has scratch for them (uint16 counts: rows shorter than 65536), the span scan otherwise
+inline int morph_tier(const RowSpanSE &se, int h, int w, bool have_prefix)
+{
+    if (morph_bits_ok(se, h, w)) return MORPH_BITS;
+    return (have_prefix && se.k >= 7 && w < 65536) ? MORPH_PREFIX : MORPH_GENERIC;
+}
 
 // A bit plane read as a mask indexed by pixel, m[p] like the byte plane it stands for (cc_row_contacts, cc_lds_forest).  y = p / w is a
 // multiply-high by inv = floor(2^32 / w) + 1: exact for 0 <= p <= 65535 and 2 <= w <= 65535 (inv * w - 2^32 <= w, so the excess

@@ -18,6 +18,7 @@
 
 #include "../../include/vistaf_temp.h"
 #include "host_util.hpp"
+#include "test_hooks.h"
 
 using namespace vf;
 
@@ -154,6 +155,7 @@ struct vistaf_tempseg_handle {
     int32_t *tm_status = nullptr;
     unsigned long long *tm_counts = nullptr;
     bool tm_ready = false, seg_ready = false;       // raised once every buffer of the set is allocated (tm_ensure / seg_ensure)
+    bool seg_done = false;                          // the last segment call ran to its end: its planes are whole (vistaf_ftp_test_tempseg_plane)
     LabCoef lab;
 };
 
@@ -262,6 +264,7 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
     if (!h || !d_bgr || !d_roi) return set_error(VISTAF_E_INVALID, "null argument");
     if (h->H < 64 || h->W < 64 || h->H % 16)
         return set_error(VISTAF_E_INVALID, "segment: frame height must be a multiple of 16 (matrix-core strips of the band-pass DFT), both sides >= 64");
+    h->seg_done = false;
     int rc_ws = seg_ensure(h);
     if (rc_ws) return rc_ws;
     hipStream_t st = (hipStream_t)stream;
@@ -352,6 +355,47 @@ int vistaf_tempseg_segment(vistaf_tempseg_handle *h, const uint8_t *d_bgr, const
         info[VISTAF_TS_CARRIER_ANGLE_RAD] = std::atan2(dy, dx);
         info[VISTAF_TS_CARRIER_PERIOD_PX] = fmag > 1e-9 ? 1.0 / fmag : std::nan("");
     }
+    h->seg_done = true;
+    return 0;
+}
+
+// test_hooks.h: one plane of the last segment call, as the workspace holds it
+int vistaf_ftp_test_tempseg_plane(vistaf_tempseg_handle *h, const char *name, void *dst, size_t bytes, void *stream)
+{
+    if (!h || !name || !dst) return set_error(VISTAF_E_INVALID, "null argument");
+    if (!h->seg_done) return set_error(VISTAF_E_STATE, "no completed segment call on this session");
+    const std::string n(name);
+    const size_t P = h->P;
+    const void *src = nullptr;
+    size_t want = 0;
+    if (n == "gray") { src = h->gray; want = P * sizeof(float); }
+    else if (n == "g") { src = h->g; want = P * sizeof(float); }
+    else if (n == "blur") { src = h->blur; want = P * sizeof(float); }
+    else if (n == "norm") { src = h->norm; want = P * sizeof(float); }
+    else if (n == "inorm") { src = h->inorm; want = P * sizeof(float); }
+    else if (n == "sat0") { src = h->sat0; want = P; }
+    else if (n == "mask_a") { src = h->ma; want = P; }
+    else if (n == "mag") { src = h->mag; want = P * sizeof(double); }
+    else if (n == "peaks") { src = h->peaks; want = 192 * sizeof(double); }
+    else if (n == "z") { src = h->z; want = P * sizeof(double2); }
+    else if (n == "med") { src = h->med; want = sizeof(float); }
+    else if (n == "geom") want = 7 * sizeof(double) + 10 * sizeof(int32_t);
+    else return set_error(VISTAF_E_INVALID, "unknown plane: " + n);
+    if (bytes != want) return set_error(VISTAF_E_INVALID, "plane " + n + " holds " + std::to_string(want) + " bytes");
+    hipStream_t st = (hipStream_t)stream;
+    if (src) {
+        HIPCHK(hipMemcpyAsync(dst, src, want, hipMemcpyDeviceToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    CarrierGeom g;
+    HIPCHK(hipMemcpyAsync(&g, h->geom, sizeof(g), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    struct { double gd[7]; int32_t gi[10]; } out = {{g.peak_x, g.peak_y, g.kx, g.ky, g.dpx, g.dpy, g.period},
+                                                    {g.x0, g.y0, g.ph, g.pw, g.px_i, g.py_i, g.px_raw, g.py_raw, g.ok, g.keep_carrier}};
+    static_assert(sizeof(out) == 96, "gd[7] then gi[10], packed");
+    HIPCHK(hipMemcpyAsync(dst, &out, sizeof(out), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
 
@@ -377,6 +421,25 @@ int vistaf_temp_color_support(vistaf_tempseg_handle *h, const float *d_a, const 
     if (d_support && k > 1) { launch_morph(d_light, h->m1, 1, h->H, h->W, ellipse_se(k), true, nullptr, nullptr, st, h->prefix); light_d = h->m1; }
     launch_color_support(d_a, d_b, light_d, d_roi_eff, d_sat, (float)chroma_min, d_chroma, d_support, h->P, st);
     return launch_ok("launch");
+}
+
+// test_hooks.h: the sign split and its sums on planes of the caller
+int vistaf_ftp_test_tempseg_sign(const void *z, double phi0, const uint8_t *roi_eff, const float *gray, uint8_t *mask_a, double *sums4, size_t n,
+                                 void *stream)
+{
+    if (!z || !roi_eff || !gray || !mask_a || !sums4 || n < 1 || !std::isfinite(phi0)) return set_error(VISTAF_E_INVALID, "bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    double *partial = nullptr;
+    HIPCHK(hipMalloc((void **)&partial, ((size_t)4 * TS_RB + 4) * sizeof(double)));
+    double *sums = partial + (size_t)4 * TS_RB;
+    hipLaunchKernelGGL(k_ts_sign, dim3(TS_RB), dim3(256), 0, st, (const double2 *)z, std::cos(phi0), std::sin(phi0), roi_eff, gray, mask_a, partial, n);
+    hipLaunchKernelGGL(k_ts_final2, dim3(1), dim3(64), 0, st, partial, TS_RB, 4, sums);
+    const hipError_t e0 = hipGetLastError();
+    const hipError_t e1 = e0 == hipSuccess ? hipMemcpyAsync(sums4, sums, 4 * sizeof(double), hipMemcpyDeviceToHost, st) : e0;
+    const hipError_t e2 = hipStreamSynchronize(st);
+    (void)hipFree(partial);
+    if (e1 != hipSuccess || e2 != hipSuccess) return set_error(VISTAF_E_HIP, std::string("tempseg_sign: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
+    return 0;
 }
 
 // ---- map-domain stages (Code/temperature_sensor.py:538-640, :705-747); parity unpinned (k_tempmap.hip)

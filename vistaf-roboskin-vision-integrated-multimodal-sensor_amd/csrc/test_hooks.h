@@ -4,12 +4,14 @@
  * Hooks: vistaf_ftp_test_set (tiers of a session); the production launchers on planes of the caller -- vistaf_ftp_test_select,
  * _select_instance, _select_chained, _polyfit, _gauss (selection, IRLS fit, blur), _chamfer, _cc_label, _cc_largest, _chamfer_dispatch,
  * _blob_filter (mask topology), _unwrap (phase unwrap), _inpaint (the Telea tiers), _top_peaks, _carrier_choose, _build_tables,
- * _build_full_tables, _dft_forward, _dft_inverse (demodulation: peak search, carrier choice, twiddle tables, the float64 GEMM stages);
+ * _build_full_tables, _dft_forward, _dft_inverse (demodulation: peak search, carrier choice, twiddle tables, the float64 GEMM stages), _morph
+ * (the three dilate / erode kernels), _tempseg_plane, _tempseg_sign (the planes between the stages of the stripe segmentation, its sign split);
  * vistaf_ftp_test_scratch_regions (scratch layouts) and vistaf_ftp_test_dft_full_mag (the full-spectrum magnitude, asynchronous: also a timing
  * aid).  The entry points of the three binary-mask chains (vistaf_ftp_test_bad_chain and friends) are declared in test_hooks_masks.h. */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
+#include "../../include/vistaf_temp.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -222,6 +224,50 @@ int vistaf_ftp_test_dft_forward(const float *iw, const float *mu, const void *Ex
 int vistaf_ftp_test_dft_inverse(const void *patch, int patch_stride, const void *Gx, const void *Gy, size_t tab_stride_x, size_t tab_stride_y, void *Q, void *field,
                                 float *amp, const void *cref, const float *amp_ref, size_t ref_stride, float *prod, float *wrapped, const int32_t *gi_or_null,
                                 int B, int h, int w, int ph, int pw, void *stream);
+
+/* launch_morph (k_basic.hip) on device planes [B, h, w] of the caller: dst[b][p] = 1 where the dilation (dilate != 0: any pixel != 0 under the
+ * element) or the erosion (every pixel under the element != 0) of src[b] holds at p, pixels outside the image never contributing
+ * (cv::morphologyDefaultBorderValue), ANDed with and_static[p] != 0 (one [h, w] plane for the batch, or NULL) and and_frame[b][p] != 0 ([B, h, w], or
+ * NULL); 0 elsewhere.  src != dst.
+ * shape: 0 ellipse_se(kx), cv::getStructuringElement(MORPH_ELLIPSE, (kx, kx)) with the anchor at kx / 2 (ky ignored; kx 1..33, the even sizes
+ *          are not symmetric about the anchor),
+ *        1 rect_se(odd_up(kx), odd_up(ky)), the rectangle as the callers of launch_morph round its sides up to odd (kx 1..127, ky 1..33),
+ *        2 a test element no cv shape gives, the hourglass: row i of kx rows spans |i - kx / 2| pixels either side of the anchor (ky ignored;
+ *          kx odd, 3..33).  Its rows are not nested towards the centre as an ellipse's or a rectangle's are, so a pixel outside the image
+ *          that wrongly took part in an erosion changes the result (with the cv shapes the clamped pixel is always under the element anyway).
+ * tier:  0 dispatch as launch_morph does when the caller has prefix scratch (morph_tier of mask_bits.hpp),
+ *        1 k_morph (the span scan) forced,
+ *        2 k_row_prefix + k_morph_prefix (uint16 row counts) forced; refused for w >= 65536,
+ *        3 k_morph_bits (bit planes in LDS) forced; refused where morph_bits_ok says no (an element not symmetric about the anchor or wider
+ *          than 127, a frame beyond h * ceil(w / 64) = 4096 words),
+ *        4 dispatch without prefix scratch, as k_inpaint_cl.hip calls it.
+ * Returns the tier that ran (MorphTier of kernels.hpp: 1, 2 or 3) or a negative VISTAF_E_* code.  The prefix scratch is allocated and freed by the
+ * call, which runs on `stream` and waits for it.  Refused with VISTAF_E_INVALID before anything is allocated: a NULL src or dst, src == dst,
+ * B, h or w below 1 (or B or h above 65535: the grid), a size out of the ranges above, an unknown shape or tier. */
+int vistaf_ftp_test_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, int shape, int kx, int ky, int dilate, const uint8_t *and_static,
+                          const uint8_t *and_frame, int tier, void *stream);
+
+/* One plane that the LAST vistaf_tempseg_segment call left in the session's workspace (tempseg.hip), copied to the DEVICE pointer dst.  Nothing is
+ * computed: these are the planes the stages themselves read and write.  `bytes` must be the plane's exact size.
+ *   float32 [H, W]     "gray", "g", "blur", "norm", "inorm": BGR2GRAY; gray with the median outside the ROI; its Gaussian (not written when
+ *                      seg_illum_sigma <= 0); g / blur; norm / mean over roi_eff
+ *   uint8 [H, W]       "sat0", "mask_a": gray >= threshold inside the ROI, before the dilation; the sign mask A before the dark side is chosen
+ *   float64 [H, W]     "mag": |fftshift(fft2(inorm))| of the float32 transform
+ *   float64 [192]      "peaks": (x, y, value) of the n_peaks largest, as vistaf_ftp_test_top_peaks writes them
+ *   complex128 [H, W]  "z": the band-passed field
+ *   float32 [1]        "med": median of gray over roi_eff
+ *   96 bytes           "geom": gd[7] float64 then gi[10] int32 of the CarrierGeom, in the order given above
+ * Refused: a NULL argument, an unknown name or a wrong byte count (VISTAF_E_INVALID); a session whose last segment call did not return 0, or that
+ * has not segmented yet (VISTAF_E_STATE).  Runs on `stream` and waits for it. */
+int vistaf_ftp_test_tempseg_plane(vistaf_tempseg_handle *handle, const char *name, void *dst, size_t bytes, void *stream);
+
+/* k_ts_sign and its reduction (tempseg.hip) on device planes of n pixels of the caller: mask_a[i] = roi_eff[i] != 0 &&
+ * float32(Re(z[i] * exp(-i phi0))) >= 0, the real part formed as re * cos(phi0) - im * (-sin(phi0)) in float64 (so -0.0 and every value that
+ * rounds to a float32 zero count as >= 0), 0 elsewhere; sums4 (HOST, 4 doubles) = sum of gray and pixel count over A, then over roi_eff and
+ * not A.  z complex128 [n], gray float32 [n].  Refused with VISTAF_E_INVALID: a NULL argument, n < 1, a phi0 that is not finite.  The scratch
+ * is the call's own; runs on `stream` and waits for it. */
+int vistaf_ftp_test_tempseg_sign(const void *z, double phi0, const uint8_t *roi_eff, const float *gray, uint8_t *mask_a, double *sums4, size_t n,
+                                 void *stream);
 #ifdef __cplusplus
 }
 #endif
