@@ -66,6 +66,14 @@ NOUTLINE = 24           # doubles per row of the contact outline read-out (VISTA
 OUTLINE_NAMES = ["pixels", "pieces", "holes", "edges", "edges_all", "perimeter_mm", "enclosed_pixels", "corners", "corners_written", "hull_vertices",
                  "hull_area_mm2", "solidity", "max_feret_mm", "max_feret_angle_rad", "min_feret_mm", "box_cx", "box_cy", "box_length_mm",
                  "box_width_mm", "box_angle_rad"]
+NTEXTURE = 40           # doubles per row of the surface texture read-out (VISTAF_NTEXTURE, include_ext/vistaf_texture.h)
+# fields of a texture row in the order of the VISTAF_TEXTURE_* indices; 34..39 are reserved
+TEXTURE_NAMES = ["eval_pixels", "form_status", "form_c0", "form_c1", "form_c2", "form_c3", "form_c4", "form_c5", "sa_mm", "sq_mm", "ssk", "sku",
+                 "sp_mm", "sv_mm", "sz_mm", "sp_pixel", "sv_pixel", "grad_pixels", "sdq", "sdr", "grad_dir_x", "grad_dir_y", "coherence",
+                 "acf_valid_lags", "lobe_lags", "lobe_status", "sal_mm", "sal_lag_x", "sal_lag_y", "rmax_mm", "str", "pitch_mm", "pitch_acf",
+                 "profile_samples"]
+TEXTURE_FORM = {"ok": 0, "none": 1, "flat": 2}                       # VISTAF_TEXTUREFORM_*, values of the `form_status` field
+TEXTURE_MIN_LAG, TEXTURE_MAX_LAG = 2, 31                             # VISTAF_TEXTURE_MIN_LAG, _MAX_LAG
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -273,6 +281,11 @@ OUTLINE_SIGNATURES = {
     "vistaf_outline_workspace_bytes": (ci, [ci, ci, ci, ci, P(sz)]),
     "vistaf_outline_measure": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
 }
+# include_ext/vistaf_texture.h: the surface texture read-out, the same pattern (tests/test_textures.py holds it against that header)
+TEXTURE_SIGNATURES = {
+    "vistaf_texture_workspace_bytes": (ci, [ci, ci, ci, ci, ci, P(sz)]),
+    "vistaf_texture_measure": (ci, [vp, vp, vp, vp, vp, cf, cd, ci, ci, cd, cd, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -291,7 +304,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

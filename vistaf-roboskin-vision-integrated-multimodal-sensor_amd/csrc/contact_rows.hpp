@@ -1,4 +1,4 @@
-// What the kernels with one workgroup per (frame, row) of the contacts table share: k_shape, k_thermal_contacts, k_motion, k_pressure_rows.
+// What the kernels with one workgroup per (frame, row) of the contacts table share: k_shape, k_thermal_contacts, k_motion, k_pressure_rows, k_texture_*.
 // The reading of a row's box, the walk over it and the prologue of an unused row.  Device inline code only.
 #pragma once
 #include "../../include/vistaf_ftp.h"

@@ -15,8 +15,8 @@
 #include <string>
 
 #include "../../include/vistaf_shape.h"
-#include "chol.hpp"
 #include "contact_rows.hpp"
+#include "form_fit.hpp"
 #include "host_util.hpp"
 
 using namespace vf;
@@ -24,8 +24,8 @@ using namespace vf;
 namespace {
 
 constexpr int SH_NT = 512, SH_NW = SH_NT / 64;
-constexpr int SH_NF = 20, SH_NI = 8;                    // float64 sums (14 monomials beside m, 6 right-hand sides); integer sums (n, boundary, m, Sx, Sy, Sxx, Syy, Sxy)
-constexpr double SH_HALF_PI = 1.5707963267948966, SH_PIVOT_FLOOR = 1.0 / 4294967296.0;      // 2^-32 of the diagonal (header, step 5)
+constexpr int SH_NF = FIT_NF, SH_NI = 8;                // float64 sums (form_fit.hpp); integer sums (n, boundary, m, Sx, Sy, Sxx, Syy, Sxy)
+constexpr double SH_HALF_PI = 1.5707963267948966;
 
 // 0.5 * atan2(p, q) as a direction in (-pi/2, pi/2]; 0 when both are 0
 __device__ inline double sh_half_angle(double p, double q)
@@ -33,11 +33,6 @@ __device__ inline double sh_half_angle(double p, double q)
     if (p == 0.0 && q == 0.0) return 0.0;
     const double t = 0.5 * atan2(p, q);
     return t <= -SH_HALF_PI ? SH_HALF_PI : t;
-}
-
-__device__ inline double sh_poly(const double *c, double u, double v)
-{
-    return c[0] + c[1] * u + c[2] * v + c[3] * (u * u) + c[4] * (u * v) + c[5] * (v * v);
 }
 
 struct ShapeFrame {
@@ -84,8 +79,8 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
     int bx0 = 0, by0 = 0, bx1 = -1, by1 = -1;
     const bool box_ok = box_value(row[VISTAF_CONTACT_BBOX_X0], bx0) && box_value(row[VISTAF_CONTACT_BBOX_Y0], by0) &&
                         box_value(row[VISTAF_CONTACT_BBOX_X1], bx1) && box_value(row[VISTAF_CONTACT_BBOX_Y1], by1);
-    const double xc = ((double)bx0 + (double)bx1) / 2.0, yc = ((double)by0 + (double)by1) / 2.0;
-    const double hx = fmax(((double)bx1 - (double)bx0) / 2.0, 1.0), hy = fmax(((double)by1 - (double)by0) / 2.0, 1.0);
+    const FitCoords uv(bx0, by0, bx1, by1);
+    const double xc = uv.xc, yc = uv.yc, hx = uv.hx, hy = uv.hy;
     const int x0 = bx0 < 0 ? 0 : bx0, y0 = by0 < 0 ? 0 : by0, x1 = bx1 > w - 1 ? w - 1 : bx1, y1 = by1 > h - 1 ? h - 1 : by1;
     const int bw = box_ok && x1 >= x0 ? x1 - x0 + 1 : 0, bh = box_ok && y1 >= y0 ? y1 - y0 + 1 : 0;
     const int total = bw * bh;                                      // <= h * w < 2^31
@@ -113,11 +108,7 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
                 sx += ux; sy += uy; sxx += ux * ux; syy += uy * uy; sxy += ux * uy;
                 if (fit_all || d >= fit_thr) {
                     m++;
-                    const double u = ((double)px - xc) / hx, v = ((double)py - yc) / hy, dd = (double)d;
-                    const double u2 = u * u, uv = u * v, v2 = v * v, u3 = u2 * u, u2v = u2 * v, uv2 = u * v2, v3 = v2 * v;
-                    f[0] += u; f[1] += v; f[2] += u2; f[3] += uv; f[4] += v2; f[5] += u3; f[6] += u2v; f[7] += uv2; f[8] += v3;
-                    f[9] += u2 * u2; f[10] += u3 * v; f[11] += u2 * v2; f[12] += u * v3; f[13] += v2 * v2;
-                    f[14] += dd; f[15] += dd * u; f[16] += dd * v; f[17] += dd * u2; f[18] += dd * uv; f[19] += dd * v2;
+                    fit_accumulate(f, uv.u(px), uv.v(py), (double)d);
                 }
             }
             x += step_x;
@@ -170,19 +161,8 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
         }
         int status = VISTAF_SHAPEFIT_NONE;
         if (ti[2] >= 6) {
-            // basis 1, u, v, u*u, u*v, v*v; S(a, b) = sum u^a v^b
-            const double S[5][5] = {{dm, tf[1], tf[4], tf[8], tf[13]}, {tf[0], tf[3], tf[7], tf[12], 0}, {tf[2], tf[6], tf[11], 0, 0},
-                                    {tf[5], tf[10], 0, 0, 0}, {tf[9], 0, 0, 0, 0}};
-            constexpr int ea[6] = {0, 1, 0, 2, 1, 0}, eb[6] = {0, 0, 1, 0, 1, 2};
-            double A[6][6], A2[6][6], c[6] = {tf[14], tf[15], tf[16], tf[17], tf[18], tf[19]}, c2[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-            for (int i = 0; i < 6; i++)
-#pragma unroll
-                for (int j = 0; j < 6; j++) {
-                    A[i][j] = S[ea[i] + ea[j]][eb[i] + eb[j]];
-                    A2[i][j] = i == j ? A[i][j] - SH_PIVOT_FLOOR * A[i][j] : A[i][j];
-                }
-            if (chol_solve<6>(A2, c2) && chol_solve<6>(A, c)) {
+            double c[6];
+            if (fit_solve<6>(tf, dm, c)) {
                 const double ax = hx * s, ay = hy * s;
                 const double q3 = c[3] / (ax * ax), q4 = c[4] / (ax * ay), q5 = c[5] / (ay * ay);
                 const double mean = q3 + q5, dev = sqrt((q3 - q5) * (q3 - q5) + q4 * q4);
@@ -197,7 +177,7 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
                     const double ua = (c[4] * c[2] - 2.0 * c[5] * c[1]) / det, va = (c[4] * c[1] - 2.0 * c[3] * c[2]) / det;
                     out[VISTAF_SHAPE_APEX_X] = xc + ua * hx;
                     out[VISTAF_SHAPE_APEX_Y] = yc + va * hy;
-                    out[VISTAF_SHAPE_APEX_DEPTH_MM] = sh_poly(c, ua, va);
+                    out[VISTAF_SHAPE_APEX_DEPTH_MM] = fit_poly(c, ua, va);
                     out[VISTAF_SHAPE_RADIUS_1_MM] = -1.0 / k1;
                     out[VISTAF_SHAPE_RADIUS_2_MM] = -1.0 / k2;
                 }
@@ -220,8 +200,7 @@ __global__ __launch_bounds__(SH_NT) void k_shape(const float *__restrict__ depth
             const int px = x0 + x, py = y0 + y;
             float d;
             if (fr.contact(px, py, d) && (fit_all || d >= fit_thr)) {
-                const double u = ((double)px - xc) / hx, v = ((double)py - yc) / hy;
-                const double r = (double)d - sh_poly(c, u, v);
+                const double r = (double)d - fit_poly(c, uv.u(px), uv.v(py));
                 r2 += r * r;
             }
             x += step_x;

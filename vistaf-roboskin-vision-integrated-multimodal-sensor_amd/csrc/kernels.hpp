@@ -348,4 +348,9 @@ size_t pressure_scratch_bytes(int B, int h, int w, int pad, ScratchRec *rec = nu
 // tables of K rows.  Its three launches are made by vistaf_outline_measure itself
 size_t outline_scratch_bytes(int B, int h, int w, int K, ScratchRec *rec = nullptr);
 
+// ---- k_texture.hip (the surface texture read-out, include_ext/vistaf_texture.h): the workspace its caller hands in, for B frames, tables of K
+// rows and windows of L lags (the half-plane sums of the autocorrelation).  Its four launches (k_texture_form, k_texture_stats, k_texture_acf,
+// k_texture_rows) are made by vistaf_texture_measure itself
+size_t texture_scratch_bytes(int B, int K, int L, ScratchRec *rec = nullptr);
+
 }  // namespace vf

@@ -326,6 +326,7 @@ class FtpSensor(Handle):
     _motion = property(lambda self: self._live("motion"))
     _pressure = property(lambda self: self._live("pressure"))
     _outlines = property(lambda self: self._live("outlines"))
+    _textures = property(lambda self: self._live("textures"))
 
     def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
         last = getattr(self, "_last_out", None)
@@ -454,6 +455,26 @@ class FtpSensor(Handle):
         if ws is None:
             ws = self._keep("outlines", (k,), OutlineWorkspace(self.h, self.w, self.max_batch, k, self.device))
         out.update(contact_outlines(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), max_vertices, ws))
+        return out
+
+    def textures(self, max_contacts: int = 8, **params) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the surface texture of every contact (texture.contact_textures; an extension, the
+        reference has no counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map, the frames'
+        mm_per_px (the `scalars` column) and the session's depth_eps_mm to the texture read-out; its workspace is the session's, made on
+        first use and again when max_contacts or max_lag change.  params: the keyword arguments of `contact_textures` (eval_min_fraction,
+        form_degree, max_lag, acf_threshold, peak_min).  Returns the contacts dict plus textures [B,K,40] f64 (fields TEXTURE_NAMES:
+        form, roughness, gradient direction and coherence, lobe, pitch), residual [B,h,w] f32 and acf [B,K,2L+1,2L+1] f64."""
+        from .texture import TextureWorkspace, contact_textures
+        unknown = set(params) - {"eval_min_fraction", "form_degree", "max_lag", "acf_threshold", "peak_min"}
+        if unknown:
+            raise TypeError(f"textures() got unexpected keyword arguments {sorted(unknown)}")
+        k, lag = int(max_contacts), int(params.get("max_lag", 8))
+        ws = self._matching("textures", (k, lag))
+        out = self.contacts(k, index_plane=True)
+        if ws is None:
+            ws = self._keep("textures", (k, lag), TextureWorkspace(self.h, self.w, self.max_batch, k, lag, self.device))
+        out.update(contact_textures(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
+                                    self.config.depth_eps_mm, ws, **params))
         return out
 
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
@@ -626,7 +647,7 @@ class FtpSensor(Handle):
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
                 motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None,
-                outlines: bool = False) -> Optional[Dict[str, Any]]:
+                outlines: bool = False, textures: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -651,7 +672,11 @@ class FtpSensor(Handle):
         "pressure_kpa", the ndarray [h,w] f32 of the contact pressure, "pressure_frame", a dict of PRESSURE_FRAME_NAMES, and, with contacts=K,
         "pressure", one dict of PRESSURE_NAMES per entry of "contacts".
         outlines=True (with contacts=K) adds "outlines", one dict of OUTLINE_NAMES per entry of "contacts" (`FtpSensor.outlines`), and
-        "outline_polylines", per entry the [n,2] list of its principal loop's corners (None for a row that did not fit the capacity)."""
+        "outline_polylines", per entry the [n,2] list of its principal loop's corners (None for a row that did not fit the capacity).
+        textures=dict(...) (with contacts=K; the keyword arguments of `FtpSensor.textures` but `max_contacts`, possibly none) adds "textures",
+        one dict of TEXTURE_NAMES per entry of "contacts"."""
+        if textures is not None and contacts is None:
+            raise ValueError("textures=dict(...) needs contacts=K")
         if outlines and contacts is None:
             raise ValueError("outlines=True needs contacts=K")
         if motion is not None and contacts is None:
@@ -720,6 +745,12 @@ class FtpSensor(Handle):
                     r.pop("frame")
                 res["outline_polylines"] = outline_frame_record(ol["outlines"][0].cpu().numpy(), ol["vertices"][0].cpu().numpy(),
                                                                 ol["offsets"][0].cpu().numpy(), int(ol["count"][0].item()))["polylines"]
+            if textures is not None:
+                from .writers import textures_table
+                tx = self.textures(int(contacts), **dict(textures))
+                res["textures"] = textures_table(tx["textures"].cpu().numpy(), tx["count"].cpu().numpy())
+                for r in res["textures"]:
+                    r.pop("frame")
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table
             running = self._pressure                            # without contacts=K the table's size is nobody's concern: keep the running one

@@ -66,6 +66,13 @@ OUTLINE_FIELDS = ("pixels", "pieces", "holes", "edges", "edges_all", "perimeter_
                   "box_width_mm", "box_angle_rad")                                       # VISTAF_OUTLINE_* order (include_ext/vistaf_outline.h)
 OUTLINE_INT_FIELDS = ("pixels", "pieces", "holes", "edges", "edges_all", "corners", "corners_written", "hull_vertices")
 OUTLINES_CSV_FIELDS = ("frame", "contact") + OUTLINE_FIELDS
+TEXTURE_FIELDS = ("eval_pixels", "form_status", "form_c0", "form_c1", "form_c2", "form_c3", "form_c4", "form_c5", "sa_mm", "sq_mm", "ssk", "sku",
+                  "sp_mm", "sv_mm", "sz_mm", "sp_pixel", "sv_pixel", "grad_pixels", "sdq", "sdr", "grad_dir_x", "grad_dir_y", "coherence",
+                  "acf_valid_lags", "lobe_lags", "lobe_status", "sal_mm", "sal_lag_x", "sal_lag_y", "rmax_mm", "str", "pitch_mm", "pitch_acf",
+                  "profile_samples")                                                     # VISTAF_TEXTURE_* order (include_ext/vistaf_texture.h)
+TEXTURE_INT_FIELDS = ("eval_pixels", "form_status", "sp_pixel", "sv_pixel", "grad_pixels", "acf_valid_lags", "lobe_lags", "lobe_status", "sal_lag_x",
+                      "sal_lag_y", "profile_samples")                                    # -1 for NaN: what a status leaves out
+TEXTURES_CSV_FIELDS = ("frame", "contact") + TEXTURE_FIELDS
 TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                 "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
 TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
@@ -293,6 +300,38 @@ def outline_frame_record(outlines, vertices, offsets, count) -> Dict[str, Any]:
             if isinstance(val, float) and not math.isfinite(val):
                 r[name] = None
     return {"contact_count": int(count), "outlines": rows, "polylines": lines}
+
+
+def textures_table(textures, count) -> list:
+    """Row dicts of the surface texture table: textures [B,K,>=34] (or [K,>=34] for one frame) float64 as `FtpSensor.textures` returns it,
+    count [B].  One dict per written contact, as `contacts_table`: `frame`, `contact` and TEXTURE_FIELDS, the counts, statuses, pixel indices
+    and lags as ints (-1 where the row's status leaves the field NaN); every other field a status leaves out is NaN."""
+    return _table(textures, count, TEXTURE_FIELDS, TEXTURE_INT_FIELDS, "textures must be [B,K,>=34] with count [B]", int_conv=_int_or_minus_one)
+
+
+def write_textures_csv(output_dir: str, textures, count, filename: str = "textures.csv") -> str:
+    """textures.csv: one line per written contact, columns TEXTURES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    return _write_csv(output_dir, filename, TEXTURES_CSV_FIELDS, textures_table(textures, count))
+
+
+def texture_frame_record(textures, count, acf=None) -> Dict[str, Any]:
+    """One frame's textures for a JSON document of the caller's own: textures [K,>=34], count (a scalar), optionally acf [K,2L+1,2L+1].
+    {"contact_count", "textures": the row dicts without `frame`, NaN as null} and, with acf, "acf": per row its window as nested lists,
+    invalid lags as null."""
+    t = np.asarray(textures, dtype=np.float64)
+    rows = textures_table(t, np.asarray([count]))
+    for r in rows:
+        r.pop("frame")
+        for name, val in r.items():
+            if isinstance(val, float) and not math.isfinite(val):
+                r[name] = None
+    rec: Dict[str, Any] = {"contact_count": int(count), "textures": rows}
+    if acf is not None:
+        a = np.asarray(acf, dtype=np.float64)
+        if a.ndim != 3 or a.shape[0] != t.shape[0] or a.shape[1] != a.shape[2] or a.shape[1] % 2 != 1:
+            raise ValueError("acf must be [K,2L+1,2L+1] for textures [K,>=34]")
+        rec["acf"] = [[[None if not math.isfinite(v) else float(v) for v in line] for line in a[r["contact"]]] for r in rows]
+    return rec
 
 
 def taxels_table(taxels) -> list:
