@@ -74,6 +74,16 @@ TEXTURE_NAMES = ["eval_pixels", "form_status", "form_c0", "form_c1", "form_c2", 
                  "profile_samples"]
 TEXTURE_FORM = {"ok": 0, "none": 1, "flat": 2}                       # VISTAF_TEXTUREFORM_*, values of the `form_status` field
 TEXTURE_MIN_LAG, TEXTURE_MAX_LAG = 2, 31                             # VISTAF_TEXTURE_MIN_LAG, _MAX_LAG
+NMATCH = 24             # doubles per row of the indenter match read-out (VISTAF_NMATCH, include_ext/vistaf_match.h)
+# fields of a match row in the order of the VISTAF_MATCH_* indices; 23 is reserved
+MATCH_NAMES = ["status", "flags", "label", "template", "class", "rotation", "shift_x", "shift_y", "score", "angle_rad", "x_px", "y_px", "offset_x_mm",
+               "offset_y_mm", "second_class", "second_score", "margin", "rot_contrast", "scale", "base_mm", "resid_rms_mm", "support_pixels",
+               "valid_shifts"]
+MATCH_STATUS = {"ok": 0, "no_pixels": 1, "no_scale": 2, "no_support": 3}              # VISTAF_MATCHST_*, values of the `status` field
+MATCH_FLAGS = {"clipped": 1, "border_shift": 2, "weak": 4, "ambiguous": 8}            # VISTAF_MATCHFL_*, bits of the `flags` field
+# VISTAF_MATCH_MAGIC, _HEADER_INTS, _MIN_P, _MAX_P, _MAX_R, _MAX_T, _MAX_SYMMETRY, _MAX_SHIFT, _MAX_ROWS
+MATCH_MAGIC, MATCH_HEADER_INTS, MATCH_MIN_P, MATCH_MAX_P, MATCH_MAX_R, MATCH_MAX_T, MATCH_MAX_SYMMETRY, MATCH_MAX_SHIFT, MATCH_MAX_ROWS = \
+    0x31424d56, 16, 5, 33, 64, 64, 8, 8, 2048
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -286,6 +296,13 @@ TEXTURE_SIGNATURES = {
     "vistaf_texture_workspace_bytes": (ci, [ci, ci, ci, ci, ci, P(sz)]),
     "vistaf_texture_measure": (ci, [vp, vp, vp, vp, vp, cf, cd, ci, ci, cd, cd, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
 }
+# include_ext/vistaf_match.h: the indenter match read-out, four plain functions, the same pattern (tests/test_matches.py holds it against that header)
+MATCH_SIGNATURES = {
+    "vistaf_match_bank_bytes": (ci, [ci, ci, ci, P(i32), P(sz)]),
+    "vistaf_match_build_bank": (ci, [P(cf), P(i32), P(i32), ci, ci, ci, cd, vp, sz]),
+    "vistaf_match_workspace_bytes": (ci, [ci, ci, ci, ci, ci, ci, ci, P(sz)]),
+    "vistaf_match_measure": (ci, [vp, vp, vp, vp, vp, vp, sz, P(i32), cf, ci, ci, cd, cd, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -304,7 +321,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

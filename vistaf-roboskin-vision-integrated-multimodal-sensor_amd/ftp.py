@@ -327,6 +327,7 @@ class FtpSensor(Handle):
     _pressure = property(lambda self: self._live("pressure"))
     _outlines = property(lambda self: self._live("outlines"))
     _textures = property(lambda self: self._live("textures"))
+    _matches = property(lambda self: self._live("matches"))
 
     def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
         last = getattr(self, "_last_out", None)
@@ -475,6 +476,29 @@ class FtpSensor(Handle):
             ws = self._keep("textures", (k, lag), TextureWorkspace(self.h, self.w, self.max_batch, k, lag, self.device))
         out.update(contact_textures(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
                                     self.config.depth_eps_mm, ws, **params))
+        return out
+
+    def matches(self, bank, max_contacts: int = 8, **params) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the known indenter every contact matches (match.contact_matches; an extension, the
+        reference has no counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map, the frames'
+        mm_per_px (the `scalars` column) and the session's depth_eps_mm to the match read-out with `bank` (a match.TemplateBank); its
+        workspace is the session's, made on first use and again when max_contacts, max_shift or the bank's sizes change.  params: the keyword
+        arguments of `contact_matches` (max_shift, min_pixels, accept_score, accept_margin).  Returns the contacts dict plus matches [B,K,24]
+        f64 (fields MATCH_NAMES: status, label, template, rotation, position, scores, fit), scores [B,K,T] f64 and patches [B,K,S,S] f32."""
+        from .match import MatchWorkspace, TemplateBank, contact_matches
+        unknown = set(params) - {"max_shift", "min_pixels", "accept_score", "accept_margin"}
+        if unknown:
+            raise TypeError(f"matches() got unexpected keyword arguments {sorted(unknown)}")
+        if not isinstance(bank, TemplateBank):
+            raise TypeError("bank must be a match.TemplateBank")
+        k, m = int(max_contacts), int(params.get("max_shift", 3))
+        key = (k, bank.P, m, bank.M)
+        ws = self._matching("matches", key)
+        out = self.contacts(k, index_plane=True)
+        if ws is None:
+            ws = self._keep("matches", key, MatchWorkspace(self.h, self.w, self.max_batch, k, bank.P, m, bank.M, self.device))
+        out.update(contact_matches(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
+                                   self.config.depth_eps_mm, bank, ws, **params))
         return out
 
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
@@ -647,7 +671,8 @@ class FtpSensor(Handle):
     def predict(self, image, contacts: Optional[int] = None, shapes: bool = False, taxels=None, thermal=None,
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
                 motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None,
-                outlines: bool = False, textures: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                outlines: bool = False, textures: Optional[Dict[str, Any]] = None,
+                matches: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -674,7 +699,13 @@ class FtpSensor(Handle):
         outlines=True (with contacts=K) adds "outlines", one dict of OUTLINE_NAMES per entry of "contacts" (`FtpSensor.outlines`), and
         "outline_polylines", per entry the [n,2] list of its principal loop's corners (None for a row that did not fit the capacity).
         textures=dict(...) (with contacts=K; the keyword arguments of `FtpSensor.textures` but `max_contacts`, possibly none) adds "textures",
-        one dict of TEXTURE_NAMES per entry of "contacts"."""
+        one dict of TEXTURE_NAMES per entry of "contacts".
+        matches=dict(bank=..., ...) (with contacts=K; `bank` a match.TemplateBank and the keyword arguments of `FtpSensor.matches` but
+        `max_contacts`) adds "matches", one dict of MATCH_NAMES per entry of "contacts"."""
+        if matches is not None and contacts is None:
+            raise ValueError("matches=dict(bank=..., ...) needs contacts=K")
+        if matches is not None and "bank" not in matches:
+            raise ValueError("matches=dict(...) needs bank=, a match.TemplateBank")
         if textures is not None and contacts is None:
             raise ValueError("textures=dict(...) needs contacts=K")
         if outlines and contacts is None:
@@ -750,6 +781,12 @@ class FtpSensor(Handle):
                 tx = self.textures(int(contacts), **dict(textures))
                 res["textures"] = textures_table(tx["textures"].cpu().numpy(), tx["count"].cpu().numpy())
                 for r in res["textures"]:
+                    r.pop("frame")
+            if matches is not None:
+                from .writers import matches_table
+                mt = self.matches(max_contacts=int(contacts), **dict(matches))
+                res["matches"] = matches_table(mt["matches"].cpu().numpy(), mt["count"].cpu().numpy())
+                for r in res["matches"]:
                     r.pop("frame")
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table

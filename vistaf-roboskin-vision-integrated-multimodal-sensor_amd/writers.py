@@ -73,6 +73,12 @@ TEXTURE_FIELDS = ("eval_pixels", "form_status", "form_c0", "form_c1", "form_c2",
 TEXTURE_INT_FIELDS = ("eval_pixels", "form_status", "sp_pixel", "sv_pixel", "grad_pixels", "acf_valid_lags", "lobe_lags", "lobe_status", "sal_lag_x",
                       "sal_lag_y", "profile_samples")                                    # -1 for NaN: what a status leaves out
 TEXTURES_CSV_FIELDS = ("frame", "contact") + TEXTURE_FIELDS
+MATCH_FIELDS = ("status", "flags", "label", "template", "class", "rotation", "shift_x", "shift_y", "score", "angle_rad", "x_px", "y_px", "offset_x_mm",
+                "offset_y_mm", "second_class", "second_score", "margin", "rot_contrast", "scale", "base_mm", "resid_rms_mm", "support_pixels",
+                "valid_shifts")                                                          # VISTAF_MATCH_* order (include_ext/vistaf_match.h)
+MATCH_INT_FIELDS = ("status", "flags", "label", "template", "class", "rotation", "shift_x", "shift_y", "second_class", "support_pixels",
+                    "valid_shifts")                                                      # -1 for NaN: what a status leaves out
+MATCHES_CSV_FIELDS = ("frame", "contact") + MATCH_FIELDS
 TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                 "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
 TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
@@ -331,6 +337,39 @@ def texture_frame_record(textures, count, acf=None) -> Dict[str, Any]:
         if a.ndim != 3 or a.shape[0] != t.shape[0] or a.shape[1] != a.shape[2] or a.shape[1] % 2 != 1:
             raise ValueError("acf must be [K,2L+1,2L+1] for textures [K,>=34]")
         rec["acf"] = [[[None if not math.isfinite(v) else float(v) for v in line] for line in a[r["contact"]]] for r in rows]
+    return rec
+
+
+def matches_table(matches, count) -> list:
+    """Row dicts of the indenter match table: matches [B,K,>=23] (or [K,>=23] for one frame) float64 as `FtpSensor.matches` returns it, count
+    [B].  One dict per written contact, as `contacts_table`: `frame`, `contact` and MATCH_FIELDS, the status, flags, label, indices, shifts and
+    counts as ints (-1 where the row's status leaves the field NaN; a withheld label and a missing second class are -1 in the table itself);
+    every other field a status leaves out is NaN."""
+    return _table(matches, count, MATCH_FIELDS, MATCH_INT_FIELDS, "matches must be [B,K,>=23] with count [B]", int_conv=_int_or_minus_one)
+
+
+def write_matches_csv(output_dir: str, matches, count, filename: str = "matches.csv") -> str:
+    """matches.csv: one line per written contact, columns MATCHES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    return _write_csv(output_dir, filename, MATCHES_CSV_FIELDS, matches_table(matches, count))
+
+
+def match_frame_record(matches, count, scores=None) -> Dict[str, Any]:
+    """One frame's matches for a JSON document of the caller's own: matches [K,>=23], count (a scalar), optionally scores [K,T].
+    {"contact_count", "matches": the row dicts without `frame`, NaN as null} and, with scores, "scores": per row the best score of every
+    template, NaN as null."""
+    t = np.asarray(matches, dtype=np.float64)
+    rows = matches_table(t, np.asarray([count]))
+    for r in rows:
+        r.pop("frame")
+        for name, val in r.items():
+            if isinstance(val, float) and not math.isfinite(val):
+                r[name] = None
+    rec: Dict[str, Any] = {"contact_count": int(count), "matches": rows}
+    if scores is not None:
+        a = np.asarray(scores, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != t.shape[0]:
+            raise ValueError("scores must be [K,T] for matches [K,>=23]")
+        rec["scores"] = [[None if not math.isfinite(v) else float(v) for v in a[r["contact"]]] for r in rows]
     return rec
 
 
