@@ -285,6 +285,13 @@ MASK_CHAIN_SIGNATURES = {
     "vistaf_ftp_test_reliable_chain": (ci, [vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
     "vistaf_ftp_test_contact_chain": (ci, [vp, vp, vp, vp, cd, cd, ci, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
 }
+# csrc/test_hooks_dft.h: the demodulation launchers with a kernel variant, and what a shape takes (tests/test_dft_staged.py holds the table
+# against that header)
+DFT_STAGED_SIGNATURES = {
+    "vistaf_ftp_test_dft_forward_v": (ci, [vp, vp, vp, vp, sz, sz, vp, ci, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_dft_inverse_v": (ci, [vp, ci, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_dft_staged_fits": (ci, [ci, ci, ci, ci, ci]),
+}
 # include_ext/vistaf_outline.h: the contact outline read-out, two plain functions outside the drop-in boundary of include/*.h, in a table of
 # their own as well (tests/test_outlines.py holds it against that header)
 OUTLINE_SIGNATURES = {
@@ -321,7 +328,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

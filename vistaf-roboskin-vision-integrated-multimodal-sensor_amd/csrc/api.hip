@@ -18,6 +18,7 @@
 using namespace vf;
 #include "test_hooks.h"
 #include "test_hooks_masks.h"
+#include "test_hooks_dft.h"
 #ifdef VISTAF_DEBUG
 namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); void telea_window_mw_debug_dump(int B); void fit_debug_dump(); void unwrap_big_debug_dump(); void unwrap_batch_debug_dump(); }
 #endif
@@ -611,9 +612,9 @@ int vistaf_ftp_set_reference(vistaf_ftp_handle *hd, const void *d_ref, int forma
         HIPCHK(hipStreamSynchronize(st));         // `win` is a host temporary
     }
     launch_build_tables(hd->geom, 0, hd->Ex, hd->Ey, hd->Gx, hd->Gy, 0, 0, 1, h, w, pad, Hf, Wf, hd->pmax, st);
-    launch_dft_forward(hd->iw, hd->mu, hd->Ex, hd->Ey, 0, 0, hd->win, hd->tmpT, hd->patch, hd->pmax * hd->pmax, 1, h, w, hd->ph, hd->pw, st);
+    launch_dft_forward(hd->iw, hd->mu, hd->Ex, hd->Ey, 0, 0, hd->win, hd->tmpT, hd->patch, hd->pmax * hd->pmax, 1, h, w, hd->ph, hd->pw, st, 0, hd->tiers.dft_staged != 0);
     launch_dft_inverse(hd->patch, hd->pmax * hd->pmax, hd->Gx, hd->Gy, 0, 0, hd->tmpT, hd->cref, hd->amp_ref, nullptr, nullptr, 0, nullptr, nullptr,
-                       1, h, w, hd->ph, hd->pw, st);
+                       1, h, w, hd->ph, hd->pw, st, nullptr, hd->tiers.dft_staged != 0);
     HIPCHK(hipStreamSynchronize(st));
     // period estimate (shape_ftp.py:2015-2027) and scale (force_sensor.py:173-187); carrier is locked so k_def == k_ref
     hd->period = g.period;
@@ -793,9 +794,9 @@ int vistaf_ftp_predict_batch(vistaf_ftp_handle *hd, const void *d_frames, int fo
 
     // ---- demodulation, carrier locked to the reference (shape_ftp.py:1643-1653, :1681-1689)
     if (timed) hipEventRecord(hd->ev[ST_DEMOD], st);
-    launch_dft_forward(hd->iw, hd->mu, hd->Ex, hd->Ey, 0, 0, hd->win, hd->tmpT, hd->patch, hd->pmax * hd->pmax, B, h, w, hd->ph, hd->pw, st);
+    launch_dft_forward(hd->iw, hd->mu, hd->Ex, hd->Ey, 0, 0, hd->win, hd->tmpT, hd->patch, hd->pmax * hd->pmax, B, h, w, hd->ph, hd->pw, st, 0, hd->tiers.dft_staged != 0);
     launch_dft_inverse(hd->patch, hd->pmax * hd->pmax, hd->Gx, hd->Gy, 0, 0, hd->tmpT, hd->keep_planes ? hd->field : nullptr, hd->amp, hd->cref,
-                       hd->amp_ref, 0, hd->prod, hd->wrapped, B, h, w, hd->ph, hd->pw, st);
+                       hd->amp_ref, 0, hd->prod, hd->wrapped, B, h, w, hd->ph, hd->pw, st, nullptr, hd->tiers.dft_staged != 0);
     return post_demod(hd, B, d_height_mm, d_reliable, d_scalars, d_status, nullptr, st);
 }
 
@@ -845,15 +846,15 @@ int vistaf_ftp_predict_pairs(vistaf_ftp_handle *hd, const void *d_refs, const vo
     launch_pair_status(hd->pgeom, pm, hd->status, together ? hd->status + B : nullptr, B, st);
     // every sample's patch in a pmax x pmax slot: its own ph x pw bins (fewer where the spectrum border clips it), zeros beyond
     launch_build_tables(hd->pgeom, 1, hd->pEx, hd->pEy, hd->pGx, hd->pGy, sx, sy, B, h, w, pad, hd->Hf, hd->Wf, pm, st, hd->hann_tab, hd->pwin);
-    launch_dft_forward(hd->iw, hd->mu, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm);
+    launch_dft_forward(hd->iw, hd->mu, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm, hd->tiers.dft_staged != 0);
     launch_dft_inverse(hd->patch, pm * pm, hd->pGx, hd->pGy, sx, sy, hd->tmpT, hd->pcref, hd->pamp_ref, nullptr, nullptr, 0, nullptr, nullptr, B, h, w,
-                       pm, pm, st, hd->pgeom);
+                       pm, pm, st, hd->pgeom, hd->tiers.dft_staged != 0);
     // ---- deformed frames, carrier locked to their own reference
     if (!together) preprocess(hd, d_defs, format, B, st, timed);
     if (timed) hipEventRecord(hd->ev[ST_DEMOD], st);
-    launch_dft_forward(iw_def, mu_def, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm);
+    launch_dft_forward(iw_def, mu_def, hd->pEx, hd->pEy, sx, sy, hd->pwin, hd->tmpT, hd->patch, pm * pm, B, h, w, pm, pm, st, pm * pm, hd->tiers.dft_staged != 0);
     launch_dft_inverse(hd->patch, pm * pm, hd->pGx, hd->pGy, sx, sy, hd->tmpT, hd->keep_planes ? hd->field : nullptr, hd->amp, hd->pcref, hd->pamp_ref,
-                       (size_t)P, hd->prod, hd->wrapped, B, h, w, pm, pm, st, hd->pgeom);
+                       (size_t)P, hd->prod, hd->wrapped, B, h, w, pm, pm, st, hd->pgeom, hd->tiers.dft_staged != 0);
     return post_demod(hd, B, d_height_mm, d_reliable, d_scalars, d_status, hd->pgeom, st, bad_def);
 }
 
@@ -926,6 +927,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "unwrap_fast") hd->tiers.unwrap_fast = value != 0;
     else if (n == "big_chain") hd->tiers.big_chain = value != 0;
     else if (n == "select_resident") hd->tiers.select_resident = value != 0;
+    else if (n == "dft_staged") hd->tiers.dft_staged = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
     else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
     else if (n == "fused_masks" && value >= 0 && value <= 7) hd->tiers.fused_masks = value;
@@ -1379,8 +1381,26 @@ int vistaf_ftp_test_build_full_tables(void *Exf, void *Eyf, int h, int w, int pa
     return hook_finish(nullptr, nullptr, (hipStream_t)stream);
 }
 
+namespace {
+// the `staged` flag of the demodulation launchers for a hook's `variant`: 0 as a session dispatches (staged where dft_staged_fits says so), 1 the
+// kernels that read global memory, 2 the staged kernel of stage `bit`, an error where the shape does not take it
+int dft_hook_variant(int variant, int bit, int h, int w, int ph, int pw, bool per_frame, bool *staged)
+{
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    if (variant == 2 && !(dft_staged_fits(h, w, ph, pw, per_frame) & bit)) return fail(VISTAF_E_INVALID, "variant 2: the staged kernel does not take this shape");
+    *staged = variant != 1;
+    return 0;
+}
+}  // namespace
+
 int vistaf_ftp_test_dft_forward(const float *iw, const float *mu, const void *Ex, const void *Ey, size_t tab_stride_x, size_t tab_stride_y, const float *win,
                                 int win_stride, void *T, void *patch, int patch_stride, int B, int h, int w, int ph, int pw, void *stream)
+{
+    return vistaf_ftp_test_dft_forward_v(iw, mu, Ex, Ey, tab_stride_x, tab_stride_y, win, win_stride, T, patch, patch_stride, B, h, w, ph, pw, 0, stream);
+}
+
+int vistaf_ftp_test_dft_forward_v(const float *iw, const float *mu, const void *Ex, const void *Ey, size_t tab_stride_x, size_t tab_stride_y, const float *win,
+                                  int win_stride, void *T, void *patch, int patch_stride, int B, int h, int w, int ph, int pw, int variant, void *stream)
 {
     if (!iw || !Ex || !Ey || !win || !T || !patch || !dft_sizes_ok(B, h, w) || ph < 1 || pw < 1 || ph > 4096 || pw > 4096 ||
         (size_t)B * h * pw > 0x7fffffffull)
@@ -1388,8 +1408,10 @@ int vistaf_ftp_test_dft_forward(const float *iw, const float *mu, const void *Ex
     if ((tab_stride_x == 0) != (tab_stride_y == 0) || (tab_stride_x && (tab_stride_x < (size_t)w * pw || tab_stride_y < (size_t)ph * h)) ||
         (win_stride != 0 && win_stride < ph * pw) || patch_stride < ph * pw)
         return fail(VISTAF_E_INVALID, "a stride is smaller than what it strides over, or only one table stride is zero");
+    bool staged;
+    if (int rc = dft_hook_variant(variant, DFT_STAGED_FWD1, h, w, ph, pw, tab_stride_x != 0, &staged)) return rc;
     launch_dft_forward(iw, mu, (const double2 *)Ex, (const double2 *)Ey, tab_stride_x, tab_stride_y, win, (double2 *)T, (double2 *)patch, patch_stride, B, h, w,
-                       ph, pw, (hipStream_t)stream, win_stride);
+                       ph, pw, (hipStream_t)stream, win_stride, staged);
     return hook_finish(nullptr, nullptr, (hipStream_t)stream);
 }
 
@@ -1397,12 +1419,28 @@ int vistaf_ftp_test_dft_inverse(const void *patch, int patch_stride, const void 
                                 float *amp, const void *cref, const float *amp_ref, size_t ref_stride, float *prod, float *wrapped, const int32_t *gi_or_null,
                                 int B, int h, int w, int ph, int pw, void *stream)
 {
+    return vistaf_ftp_test_dft_inverse_v(patch, patch_stride, Gx, Gy, tab_stride_x, tab_stride_y, Q, field, amp, cref, amp_ref, ref_stride, prod, wrapped,
+                                         gi_or_null, B, h, w, ph, pw, 0, stream);
+}
+
+int vistaf_ftp_test_dft_staged_fits(int h, int w, int ph, int pw, int per_frame_tables)
+{
+    if (h < 1 || w < 1 || ph < 1 || pw < 1) return fail(VISTAF_E_INVALID, "bad argument");
+    return dft_staged_fits(h, w, ph, pw, per_frame_tables != 0);
+}
+
+int vistaf_ftp_test_dft_inverse_v(const void *patch, int patch_stride, const void *Gx, const void *Gy, size_t tab_stride_x, size_t tab_stride_y, void *Q,
+                                  void *field, float *amp, const void *cref, const float *amp_ref, size_t ref_stride, float *prod, float *wrapped,
+                                  const int32_t *gi_or_null, int B, int h, int w, int ph, int pw, int variant, void *stream)
+{
     if (!patch || !Gx || !Gy || !Q || !amp || (cref && (!amp_ref || !prod || !wrapped)) || !dft_sizes_ok(B, h, w) || ph < 1 || pw < 1 || ph > 4096 ||
         pw > 4096 || (size_t)B * ph * w > 0x7fffffffull)
         return fail(VISTAF_E_INVALID, "bad argument");
     if ((tab_stride_x == 0) != (tab_stride_y == 0) || (tab_stride_x && (tab_stride_x < (size_t)w * pw || tab_stride_y < (size_t)ph * h)) ||
         patch_stride < ph * pw || (ref_stride != 0 && ref_stride < (size_t)h * w))
         return fail(VISTAF_E_INVALID, "a stride is smaller than what it strides over, or only one table stride is zero");
+    bool staged;
+    if (int rc = dft_hook_variant(variant, DFT_STAGED_INV2, h, w, ph, pw, tab_stride_x != 0, &staged)) return rc;
     hipStream_t st = (hipStream_t)stream;
     CarrierGeom *geom = nullptr;
     if (gi_or_null) {
@@ -1416,7 +1454,7 @@ int vistaf_ftp_test_dft_inverse(const void *patch, int patch_stride, const void 
         }
     }
     launch_dft_inverse((const double2 *)patch, patch_stride, (const double2 *)Gx, (const double2 *)Gy, tab_stride_x, tab_stride_y, (double2 *)Q, (double2 *)field, amp,
-                       (const double2 *)cref, amp_ref, ref_stride, prod, wrapped, B, h, w, ph, pw, st, geom);
+                       (const double2 *)cref, amp_ref, ref_stride, prod, wrapped, B, h, w, ph, pw, st, geom, staged);
     return hook_finish(geom, nullptr, st);
 }
 

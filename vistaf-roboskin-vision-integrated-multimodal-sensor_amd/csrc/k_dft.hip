@@ -83,6 +83,128 @@ __global__ __launch_bounds__(256) void k_dft_fwd1_mfma(const float *__restrict__
     }
 }
 
+// What of the demodulation runs on the staged kernels (Tiers::dft_staged) at this shape: DFT_STAGED_FWD1 stage 1 as k_dft_fwd1_staged,
+// DFT_STAGED_INV2 stage 4 as k_dft_inv2_staged.  The limits are those of the kernels' LDS images and of the loads a thread issues per chunk;
+// frame size and table mode exclude nothing (the table goes in chunks, a workgroup stays inside one segment).  Every other shape, and
+// stages 2 and 3, take the kernels that read global memory.
+constexpr int FWD1_MAXPW = 24;                                   // 2 pw <= 48 columns: three tiles, one pass; three table loads per thread and chunk
+constexpr int INV2_MAXPH = 22;                                   // 2 KB of LDS per row + 4 KB: 48 KB; 6 staging loads per thread
+int dft_staged_fits(int h, int w, int ph, int pw, bool per_frame_tables)
+{
+    (void)per_frame_tables;
+    if (h < 1 || w < 1 || ph < 1 || pw < 1) return 0;
+    return (pw <= FWD1_MAXPW ? DFT_STAGED_FWD1 : 0) | (ph <= INV2_MAXPH ? DFT_STAGED_INV2 : 0);
+}
+
+// stage 1 with its operands staged in LDS (Tiers::dft_staged, patches dft_staged_fits takes: all column tiles in one pass).  A workgroup owns
+// four strips of ONE segment (its four waves; the grid is per segment, so no workgroup sees two tables) and walks x in chunks of FWD1_XC
+// columns: the chunk of the table (FWD1_XC rows of pw double2, contiguous in memory) and each wave's 16 rows x FWD1_XC floats are fetched with
+// coalesced loads into registers while the chunk before is multiplied, then handed to LDS; the k-loop reads LDS only.  The table lies in LDS
+// as the B operand wants it, [x][n] with the real parts of the pw bins, then their imaginary parts, rows FWD1_EST doubles apart: the two x of
+// a 32-lane group fall into opposite halves of the banks (FWD1_EST = 16 mod 32) and the read is conflict-free.  Every accumulator receives
+// the k-steps of k_dft_fwd1_mfma in their order with the same operands (the float32 difference iw - mu is formed at the read, as there):
+// equal bits.  The strip's rows of T, contiguous in memory, leave through LDS as whole 16-byte elements instead of 8-byte halves.
+constexpr int FWD1_XC = 32, FWD1_EST = 48, FWD1_IST = 36;        // chunk; LDS row strides of the table (doubles) and of a wave's input rows (floats)
+constexpr int FWD1_NLE = FWD1_XC * FWD1_MAXPW / 256, FWD1_NLI = 16 * FWD1_XC / 64;
+constexpr int FWD1_LDS_E = FWD1_XC * FWD1_EST * 8, FWD1_LDS_I = 16 * FWD1_IST * 4, FWD1_LDS_O = 16 * FWD1_MAXPW * 16;
+constexpr int FWD1_LDS = FWD1_LDS_E + 4 * FWD1_LDS_I > 4 * FWD1_LDS_O ? FWD1_LDS_E + 4 * FWD1_LDS_I : 4 * FWD1_LDS_O;
+// NT: the column tiles, (2 pw + 15) / 16.  It is a template parameter, and every LDS read and MFMA of the k-loop unconditional (a padding column
+// or a k beyond w multiplies a selected zero, as in k_dft_fwd1_mfma), so that the accumulators stay where the matrix cores leave them
+// (with the occupancy bound the compiler keeps them in VGPRs; without it they were copied to AGPRs and back around every k-step).
+template <int NT>
+__global__ __launch_bounds__(256, 4) void k_dft_fwd1_staged(const float *__restrict__ iw, const float *__restrict__ mu, const double2 *__restrict__ Ex_all,
+                                                         size_t ex_stride, double2 *__restrict__ T, int h, int w, int pw, int seg_rows, int nseg)
+{
+    __shared__ __attribute__((aligned(16))) unsigned char s_raw[FWD1_LDS];
+    double *sE = (double *)s_raw;                                // [FWD1_XC][FWD1_EST]
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    float *sI = (float *)(s_raw + FWD1_LDS_E) + wid * (16 * FWD1_IST);      // this wave's [16][FWD1_IST]
+    const int sps = (seg_rows + 15) / 16, wgps = (sps + 3) / 4;  // strips and workgroups per segment
+    const int seg = blockIdx.x / wgps, sstrip = (blockIdx.x - seg * wgps) * 4 + wid;
+    const bool active = sstrip < sps;                            // a wave without a strip still stages the table and joins the barriers
+    const int row0 = seg * seg_rows + sstrip * 16;
+    const int row_end = (seg + 1) * seg_rows;                    // one past the segment's last row
+    const int r = lane & 15, kk = lane >> 4;
+    const int grow = active ? min(row0 + r, row_end - 1) : 0;    // rows past the segment repeat its last one (never stored)
+    const double2 *E = Ex_all + (size_t)seg * ex_stride;
+    const float m = (mu && active) ? mu[grow / h] : 0.f;
+    const int ncol = 2 * pw;
+    v4f64 acc[NT];
+    bool colv[NT];                                               // false: padding column
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+        acc[t] = (v4f64){0.0, 0.0, 0.0, 0.0};
+        colv[t] = t * 16 + r < ncol;
+    }
+    double2 ve[FWD1_NLE];
+    float vi[FWD1_NLI];
+    // every load is issued, at an index clamped into the chunk; what lies past w is dropped (table) or zeroed (input) at the hand-over
+    auto fetch = [&](int xc0) {
+        const int ne = min(FWD1_XC, w - xc0) * pw;               // table elements of this chunk
+#pragma unroll
+        for (int j = 0; j < FWD1_NLE; j++) ve[j] = E[(size_t)xc0 * pw + min((int)threadIdx.x + 256 * j, ne - 1)];
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < FWD1_NLI; j++) {
+                const int e = lane + 64 * j, rr = e / FWD1_XC, x = xc0 + e % FWD1_XC;
+                vi[j] = iw[(size_t)min(row0 + rr, row_end - 1) * w + min(x, w - 1)];
+            }
+        }
+    };
+    fetch(0);
+    for (int xc0 = 0; xc0 < w; xc0 += FWD1_XC) {
+        if (xc0) __syncthreads();                                // the chunk before has been read
+        const int ne = min(FWD1_XC, w - xc0) * pw;
+#pragma unroll
+        for (int j = 0; j < FWD1_NLE; j++) {
+            const int e = threadIdx.x + 256 * j;
+            if (e < ne) {
+                const int xl = e / pw, c = e - xl * pw;
+                sE[xl * FWD1_EST + c] = ve[j].x;
+                sE[xl * FWD1_EST + pw + c] = ve[j].y;
+            }
+        }
+        if (active) {
+#pragma unroll
+            for (int j = 0; j < FWD1_NLI; j++) {
+                const int e = lane + 64 * j, rr = e / FWD1_XC, xl = e % FWD1_XC;
+                sI[rr * FWD1_IST + xl] = xc0 + xl < w ? vi[j] : 0.f;
+            }
+        }
+        __syncthreads();
+        if (xc0 + FWD1_XC < w) fetch(xc0 + FWD1_XC);             // in flight while this chunk is multiplied
+        if (active) {
+            const int nk = min(FWD1_XC, w - xc0);
+            for (int xl = 0; xl < nk; xl += 4) {
+                const bool in = xc0 + xl + kk < w;
+                const float af = sI[r * FWD1_IST + xl + kk];
+                const double a = in ? (double)__fsub_rn(af, m) : 0.0;
+                double bv[NT];
+#pragma unroll
+                for (int t = 0; t < NT; t++) bv[t] = sE[(xl + kk) * FWD1_EST + t * 16 + r];
+#pragma unroll
+                for (int t = 0; t < NT; t++) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, (in && colv[t]) ? bv[t] : 0.0, acc[t], 0, 0, 0);
+            }
+        }
+    }
+    __syncthreads();                                             // the last chunk has been read: LDS becomes the strips' rows of T
+    double2 *sO = (double2 *)s_raw + wid * (16 * FWD1_MAXPW);    // this wave's [16][pw]
+    if (active) {
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            if (!colv[t]) continue;
+            const int n = t * 16 + r, c = n < pw ? n : n - pw;
+#pragma unroll
+            for (int q = 0; q < 4; q++) ((double *)(sO + (kk + 4 * q) * pw + c))[n < pw ? 0 : 1] = acc[t][q];
+        }
+    }
+    __syncthreads();
+    if (active) {
+        const int no = min(16, row_end - row0) * pw;
+        for (int e = lane; e < no; e += 64) T[(size_t)row0 * pw + e] = sO[e];
+    }
+}
+
 // stage 2: patch[b, a, c] = win[a,c] * sum_y Ey[a, y] * T[b, y, c]   (complex128 spectrum value times the float32 window, as upstream's
 // `patch *= win` under complex128: both parts times the window in float64)
 __global__ void k_dft_fwd2(const double2 *__restrict__ T, const double2 *__restrict__ Ey_all, size_t ey_stride, const float *__restrict__ win_all,
@@ -115,12 +237,18 @@ __global__ void k_dft_fwd2(const double2 *__restrict__ T, const double2 *__restr
 
 void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, const double2 *Ey, size_t tab_stride_x, size_t tab_stride_y,
                         const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st,
-                        int win_stride)
+                        int win_stride, bool staged)
 {
     // per-frame tables (tab_stride_x != 0): one segment per frame; a shared table: the whole batch is one segment
     const int seg_rows = tab_stride_x ? h : B * h, nseg = tab_stride_x ? B : 1;
-    const int strips = nseg * ((seg_rows + 15) / 16);
-    hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3((strips + 3) / 4), dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
+    const int sps = (seg_rows + 15) / 16, strips = nseg * sps;
+    if (staged && (dft_staged_fits(h, w, ph, pw, tab_stride_x != 0) & DFT_STAGED_FWD1)) {
+        const dim3 grid(nseg * ((sps + 3) / 4));
+        if (pw <= 8) hipLaunchKernelGGL(k_dft_fwd1_staged<1>, grid, dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
+        else if (pw <= 16) hipLaunchKernelGGL(k_dft_fwd1_staged<2>, grid, dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
+        else hipLaunchKernelGGL(k_dft_fwd1_staged<3>, grid, dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
+    } else
+        hipLaunchKernelGGL(k_dft_fwd1_mfma, dim3((strips + 3) / 4), dim3(256), 0, st, iw, mu, Ex, tab_stride_x, tmpT, h, w, pw, seg_rows, nseg);
     hipLaunchKernelGGL(k_dft_fwd2, dim3(B), dim3(std::min(1024, ((ph * pw + 63) / 64) * 64)), 0, st, (const double2 *)tmpT, Ey, tab_stride_y, win, win_stride, patch, h,
                        ph, pw, patch_stride);
 }
@@ -195,13 +323,113 @@ __global__ __launch_bounds__(256) void k_dft_inv2_mfma(const double2 *__restrict
     }
 }
 
+// the epilogue of stage 4 for one 16 x 16 tile: the lane's column x and its four rows y + 4 qd (re and im of an element sit in the same lane and
+// register index), for k_dft_inv2_staged.  The expressions are those of k_dft_inv2_mfma's epilogue, which stays as it was compiled: the bits of
+// amp, wrapped and prod hang on them.
+// cv / av: cref and amp_ref at the tile's four pixels (fetched at clamped positions by the caller; read only where cref is given).
+__device__ __forceinline__ void inv2_finish_tile(const v4f64 &cre, const v4f64 &cim, int x, int y, size_t b, int h, int w, double2 *__restrict__ field,
+                                                 float *__restrict__ amp, bool cref, const double2 (&cv)[4], const float (&av)[4],
+                                                 float *__restrict__ prod, float *__restrict__ wrapped)
+{
+    if (x >= w) return;
+#pragma unroll
+    for (int qd = 0; qd < 4; qd++, y += 4) {
+        if (y >= h) continue;
+        const double ar = cre[qd], ai = cim[qd];
+        const size_t p = (size_t)y * w + x, i = b * (size_t)h * w + p;
+        if (field) field[i] = make_double2(ar, ai);
+        const float am = (float)sqrt(fma(ar, ar, ai * ai));
+        amp[i] = am;
+        if (cref) {
+            const double2 c = cv[qd];
+            const double rr = ar * c.x + ai * c.y;
+            const double ri = ai * c.x - ar * c.y;
+            wrapped[i] = (float)atan2(ri, rr);
+            prod[i] = __fmul_rn(av[qd], am);
+        }
+    }
+}
+
+// stage 4 with its operands staged in LDS (Tiers::dft_staged, patches dft_staged_fits takes): the same grid, the same tile per wave and the
+// same k-steps as k_dft_inv2_mfma, fed differently.  The workgroup loads its 64 columns of Q once for its four waves (ph x 64 double2, coalesced
+// 16-byte loads, all in flight together), each wave its 16 rows of Gy (contiguous in memory); the k-loop reads LDS only (cgemm16_lds_mfma).
+// A wave walks its four column tiles in passes of INV2_NT and finishes each pass before the next starts, so 2 INV2_NT accumulators instead of
+// eight are live across the epilogue; tiles wholly beyond w are skipped (at w = 224 an eighth of the parent's MFMAs).  An accumulator still
+// receives the k-steps of the parent in their order with the same operands: equal bits.  LDS: 2 KB per row of the patch + 4 KB.  The
+// reference field and amplitude of a pass's pixels are fetched before its k-loop, so that they arrive while the matrix cores work.
+constexpr int INV2_NT = 2;
+__global__ __launch_bounds__(256, 3) void k_dft_inv2_staged(const double2 *__restrict__ Q, const double2 *__restrict__ Gy_all, size_t gy_stride,
+                                                         double2 *__restrict__ field, float *__restrict__ amp, const double2 *__restrict__ cref_all,
+                                                         const float *__restrict__ amp_ref_all, size_t ref_stride, float *__restrict__ prod,
+                                                         float *__restrict__ wrapped, int h, int w, int ph, const CarrierGeom *__restrict__ geom)
+{
+    extern __shared__ double2 s_inv2[];                          // Q columns [ph][64], the four waves' Gy rows [16][ph] each, 256 spare elements
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int x0 = blockIdx.x * 64, y0 = (blockIdx.y * 4 + wid) * 16;
+    const size_t b = blockIdx.z;
+    const int r = lane & 15, kk = lane >> 4;
+    const double2 *Qb = Q + b * (size_t)ph * w;
+    const int phb = geom ? max(0, min(geom[b].ph, ph)) : ph;     // the sample's own extent: K and the re / im split as a launch of that size
+    double2 *sQ = s_inv2, *sG = s_inv2 + ph * 64 + wid * 16 * ph;
+    constexpr int NLD = (INV2_MAXPH * 64 + 255) / 256;
+    // Every load is issued, at an index clamped into what is staged, and every store too (what is not staged goes to a spare element per
+    // thread behind the images): no branch stands between the loads, one round trip for all of them.
+    const int spare = ph * 128 + threadIdx.x;
+    if (phb > 0) {  // rows 0..phb-1 of Q (the rows beyond are never read: pair mode leaves them unwritten), columns clamped to w - 1 as the parent's loads
+        double2 v[NLD];
+        const int c = min(x0 + lane, w - 1);
+#pragma unroll
+        for (int j = 0; j < NLD; j++) v[j] = Qb[(size_t)min(wid + 4 * j, phb - 1) * w + c];
+#pragma unroll
+        for (int j = 0; j < NLD; j++) sQ[wid + 4 * j < phb ? (wid + 4 * j) * 64 + lane : spare] = v[j];
+    }
+    if (y0 < h) {
+        const double2 *Gs = Gy_all + b * gy_stride + (size_t)y0 * ph;
+        const int n = min(16, h - y0) * ph;
+        double2 v[NLD];
+#pragma unroll
+        for (int j = 0; j < NLD; j++) v[j] = Gs[min(lane + 64 * j, n - 1)];
+#pragma unroll
+        for (int j = 0; j < NLD; j++) (lane + 64 * j < n ? sG + lane + 64 * j : sQ + spare)[0] = v[j];
+    }
+    __syncthreads();
+    if (y0 >= h) return;
+    const int ra = min(r, h - 1 - y0);                           // rows past the frame repeat its last one (never stored)
+    const double2 *cref = cref_all ? cref_all + b * ref_stride : nullptr;
+    const float *amp_ref = amp_ref_all ? amp_ref_all + b * ref_stride : nullptr;
+    for (int t0 = 0; t0 < 4 && x0 + 16 * t0 < w; t0 += INV2_NT) {
+        v4f64 cre[INV2_NT], cim[INV2_NT];
+        double2 cv[INV2_NT][4];
+        float av[INV2_NT][4];
+        if (cref) {
+#pragma unroll
+            for (int t = 0; t < INV2_NT; t++)
+#pragma unroll
+                for (int qd = 0; qd < 4; qd++) {
+                    const size_t p = (size_t)min(y0 + kk + 4 * qd, h - 1) * w + min(x0 + 16 * (t0 + t) + r, w - 1);
+                    cv[t][qd] = cref[p];
+                    av[t][qd] = amp_ref[p];
+                }
+        }
+        cgemm16_lds_mfma<INV2_NT>((const double *)sG, ph, phb, sQ, ra, t0, lane, cre, cim);
+#pragma unroll
+        for (int t = 0; t < INV2_NT; t++)
+            inv2_finish_tile(cre[t], cim[t], x0 + 16 * (t0 + t) + r, y0 + kk, b, h, w, field, amp, cref != nullptr, cv[t], av[t], prod, wrapped);
+    }
+}
+
 void launch_dft_inverse(const double2 *patch, int patch_stride, const double2 *Gx, const double2 *Gy, size_t tab_stride_x, size_t tab_stride_y,
                         double2 *tmpQ, double2 *field, float *amp, const double2 *cref, const float *amp_ref, size_t ref_stride, float *prod,
-                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom)
+                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom, bool staged)
 {
     hipLaunchKernelGGL(k_dft_inv1, dim3((w + 255) / 256, ph, B), dim3(256), 0, st, patch, patch_stride, Gx, tab_stride_x, tmpQ, w, ph, pw, geom);
-    hipLaunchKernelGGL(k_dft_inv2_mfma, dim3((w + 63) / 64, (h + 63) / 64, B), dim3(256), 0, st, (const double2 *)tmpQ, Gy, tab_stride_y, field, amp, cref,
-                       amp_ref, ref_stride, prod, wrapped, h, w, ph, geom);
+    const dim3 grid((w + 63) / 64, (h + 63) / 64, B);
+    if (staged && (dft_staged_fits(h, w, ph, pw, tab_stride_x != 0) & DFT_STAGED_INV2))
+        hipLaunchKernelGGL(k_dft_inv2_staged, grid, dim3(256), (size_t)ph * 2048 + 4096, st, (const double2 *)tmpQ, Gy, tab_stride_y, field, amp, cref, amp_ref,
+                           ref_stride, prod, wrapped, h, w, ph, geom);
+    else
+        hipLaunchKernelGGL(k_dft_inv2_mfma, grid, dim3(256), 0, st, (const double2 *)tmpQ, Gy, tab_stride_y, field, amp, cref, amp_ref, ref_stride, prod,
+                           wrapped, h, w, ph, geom);
 }
 
 // ---- full spectrum magnitude (reference-frame carrier search, shape_ftp.py:867-872), float64 as np.abs(fft2(float64)) ----

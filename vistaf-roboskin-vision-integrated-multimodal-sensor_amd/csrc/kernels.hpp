@@ -25,6 +25,7 @@ struct Tiers {
     int fused_backend = 1;      // 1: frames whose label forest fits LDS run blob filter, force tail and output copy in one launch per batch (k_backend.hip); 0: the separate kernels
     int select_resident = 1;    // 1: the exact selections of planes of up to 65536 pixels keep their keys in registers (k_select_resident) and the core threshold and core median share a launch; 0: the streaming k_select, one launch per selection
     int fused_masks = 7;        // bits 1 / 2 / 4: the bad-pixel, reliable and contact mask chain of frames mask_chain_fits takes run as one launch each, bit planes in LDS (k_maskchain.hip); 0: the separate kernels
+    int dft_staged = 1;         // 1: the demodulation stages dft_staged_fits names take their operands from LDS (k_dft.hip: k_dft_fwd1_staged, k_dft_inv2_staged); 0: every stage reads global memory / L2 per k-step
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
 };
 
@@ -117,13 +118,17 @@ struct CarrierGeom {
 // own extents inside it, tables and window zero beyond them); win_stride: elements per frame of the window (0: one window for the batch)
 void launch_dft_forward(const float *iw, const float *mu, const double2 *Ex, const double2 *Ey, size_t tab_stride_x, size_t tab_stride_y,
                         const float *win, double2 *tmpT, double2 *patch, int patch_stride, int B, int h, int w, int ph, int pw, hipStream_t st,
-                        int win_stride = 0);
+                        int win_stride = 0, bool staged = true);
 // field (may be null): float64 field out; cref/amp_ref (may be null): reference field -> wrapped phase difference and amp product.
-// geom (pair mode, may be null): the sums run over each sample's own geom[b].ph x geom[b].pw bins of the ph x pw layout, in the order of a
+// staged: Tiers::dft_staged.  geom (pair mode, may be null): the sums run over each sample's own geom[b].ph x geom[b].pw bins of the ph x pw layout, in the order of a
 // ph x pw launch of that size (session mode), so a clipped patch gives the bits of its own session
 void launch_dft_inverse(const double2 *patch, int patch_stride, const double2 *Gx, const double2 *Gy, size_t tab_stride_x, size_t tab_stride_y,
                         double2 *tmpQ, double2 *field, float *amp, const double2 *cref, const float *amp_ref, size_t ref_stride, float *prod,
-                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom = nullptr);
+                        float *wrapped, int B, int h, int w, int ph, int pw, hipStream_t st, const CarrierGeom *geom = nullptr, bool staged = true);
+// the stages that run on the LDS-staged kernels at this shape when `staged` is set (Tiers::dft_staged), as bits; every other stage and shape
+// takes the kernels that read their operands from global memory.  per_frame_tables: pair mode (table strides != 0)
+enum DftStaged { DFT_STAGED_FWD1 = 1, DFT_STAGED_INV2 = 2 };     // stage 1: k_dft_fwd1_staged; stage 4: k_dft_inv2_staged
+int dft_staged_fits(int h, int w, int ph, int pw, bool per_frame_tables);
 void launch_dft_full_mag(const float *iw, const float *mu, const double2 *Ex_full, const double2 *Ey_full, double2 *tmp,
                          double *mag, int B, int h, int w, int Hf, int Wf, hipStream_t st);
 // stage 1 of launch_dft_full_mag alone (the row transform of the pressure read-out too): T [B*h][nc] = (iw - mu) . Ex, Ex [w][nc]; mu may be null

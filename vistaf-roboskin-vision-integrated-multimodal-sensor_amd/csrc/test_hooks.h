@@ -46,6 +46,12 @@ extern "C" {
  *       "select_resident" 1 (default) the exact selections of planes of up to 65536 pixels run k_select_resident (every element loaded once, its key
  *                      kept in a register for all sweeps) and the core threshold and the core median below it share one chained launch; 0 the
  *                      streaming k_select, one launch per selection (two for the core pair).  Same bits either way
+ *       "dft_staged"   1 (default) the demodulation stages whose patch dft_staged_fits takes (kernels.hpp; vistaf_ftp_test_dft_staged_fits of test_hooks_dft.h tells)
+ *                      read their GEMM operands from LDS: the row stage (k_dft_fwd1_staged: the twiddle table in chunks of 32 columns, the next chunk
+ *                      in flight) and the last stage with its epilogue (k_dft_inv2_staged: the workgroup's columns of Q and each wave's rows of Gy,
+ *                      the column tiles finished two at a time); 0 the kernels that fetch one element per lane and k-step from global memory.  Every
+ *                      accumulator receives the same k-steps in the same order with the same operands: same bits either way.  test_hooks_dft.h has the
+ *                      direct hooks that run either kernel of a stage
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
