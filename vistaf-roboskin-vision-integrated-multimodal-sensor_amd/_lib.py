@@ -292,6 +292,11 @@ DFT_STAGED_SIGNATURES = {
     "vistaf_ftp_test_dft_inverse_v": (ci, [vp, ci, vp, vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp]),
     "vistaf_ftp_test_dft_staged_fits": (ci, [ci, ci, ci, ci, ci]),
 }
+# csrc/test_hooks_gauss.h: the plain blur with a kernel variant, and what a blur takes (tests/test_gauss_strip.py holds the table against that header)
+GAUSS_STRIP_SIGNATURES = {
+    "vistaf_ftp_test_gauss_variant": (ci, [vp, vp, cd, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_gauss_strip_fits": (ci, [ci, ci, ci]),
+}
 # include_ext/vistaf_outline.h: the contact outline read-out, two plain functions outside the drop-in boundary of include/*.h, in a table of
 # their own as well (tests/test_outlines.py holds it against that header)
 OUTLINE_SIGNATURES = {
@@ -328,7 +333,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

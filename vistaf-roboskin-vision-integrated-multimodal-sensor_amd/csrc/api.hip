@@ -19,6 +19,7 @@ using namespace vf;
 #include "test_hooks.h"
 #include "test_hooks_masks.h"
 #include "test_hooks_dft.h"
+#include "test_hooks_gauss.h"
 #ifdef VISTAF_DEBUG
 namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); void telea_window_mw_debug_dump(int B); void fit_debug_dump(); void unwrap_big_debug_dump(); void unwrap_batch_debug_dump(); }
 #endif
@@ -142,7 +143,7 @@ int make_se(int k, RowSpanSE *se, bool force_odd = true)
 
 void blur(vistaf_ftp_handle *hd, const float *src, float *dst, const GKern &g, int B, hipStream_t st)
 {
-    launch_gauss_blur(src, hd->tmpf, dst, g.d, g.k, B, hd->h, hd->w, st);
+    launch_gauss_blur(src, hd->tmpf, dst, g.d, g.k, B, hd->h, hd->w, st, hd->tiers.gauss_strip != 0);
 }
 
 // whether the element-wise passes around this blur run inside its tile (k_blurchain.hip): short kernels only, Tiers::fused_chains
@@ -722,12 +723,15 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
     bool use_band = c.frontier_zero_band_px > 0;
     float band = (float)c.frontier_zero_band_px;
     // both distance transforms of the reliable mask (to its outside for the taper, to its inside for the final blend) in one launch; the
-    // second one lands in planes that are idle at this point (`area` as the integer temporary, `depth` -- written by to_mm below)
-    if (use_band) launch_chamfer_pair(orel, hd->rowdist, hd->dist, hd->area, hd->depth, B, h, w, c.frontier_zero_band_px + 2, st, hd->tiers.chamfer_twopass != 0);
-    else HIPCHK(hipMemsetAsync(hd->dist, 0x7f, (size_t)B * P * sizeof(float), st));   // huge distance: taper weight 1
+    // second one lands in a plane that is idle at this point (`area` is the integer temporary): `depth`, which to_mm writes below, or, when
+    // the fused compose runs, `snum`, which only the kernel sequence writes -- the fused kernel reads the distance and writes `depth` in one
+    // pass, and with the two apart none of its pointers alias
     const bool fuse_compose = fuses(hd, hd->g_unrel);      // then the mm curve runs in the same kernel and counts as composition
+    float *dist2 = fuse_compose ? hd->snum : hd->depth;
+    if (use_band) launch_chamfer_pair(orel, hd->rowdist, hd->dist, hd->area, dist2, B, h, w, c.frontier_zero_band_px + 2, st, hd->tiers.chamfer_twopass != 0);
+    else HIPCHK(hipMemsetAsync(hd->dist, 0x7f, (size_t)B * P * sizeof(float), st));   // huge distance: taper weight 1
     if (fuse_compose)
-        launch_compose_finalize_mm(hd->hmap, orel, hd->roi, hd->dist, use_band ? band : 1.0f, hd->roi_den, use_band ? hd->depth : hd->dist, band,
+        launch_compose_finalize_mm(hd->hmap, orel, hd->roi, hd->dist, use_band ? band : 1.0f, hd->roi_den, use_band ? dist2 : hd->dist, band,
                                    use_band ? 1 : 0, hd->hcurve, hd->use_neg, hd->unitless, hd->depth, hd->cand, hd->gmax, hd->g_unrel.d, hd->g_unrel.k,
                                    B, h, w, st);
     else {
@@ -929,6 +933,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "select_resident") hd->tiers.select_resident = value != 0;
     else if (n == "dft_staged") hd->tiers.dft_staged = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
+    else if (n == "gauss_strip") hd->tiers.gauss_strip = value != 0;
     else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
     else if (n == "fused_masks" && value >= 0 && value <= 7) hd->tiers.fused_masks = value;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
@@ -1006,11 +1011,13 @@ int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int 
     return rc ? rc : inst;
 }
 
-int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream)
+int vistaf_ftp_test_gauss_variant(const float *src, float *dst, double sigma, int B, int h, int w, int variant, void *stream)
 {
     if (!src || !dst || src == dst || B < 1 || h < 1 || w < 1 || !(sigma > 0)) return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
     if (gauss_ksize(sigma) > 511) return fail(VISTAF_E_INVALID, "gaussian sigma too large (ksize > 511)");
     const std::vector<float> f = gauss_taps(sigma);
+    if (variant == 2 && !gauss_strip_fits(h, w, (int)f.size())) return fail(VISTAF_E_INVALID, "variant 2: the strip kernel does not take this blur");
     float *taps = nullptr, *tmp = nullptr;
     HIPCHK(hipMalloc((void **)&taps, f.size() * sizeof(float)));
     if (hipMalloc((void **)&tmp, (size_t)B * h * w * sizeof(float)) != hipSuccess) { (void)hipFree(taps); return fail(VISTAF_E_HIP, "hipMalloc"); }
@@ -1018,8 +1025,19 @@ int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int
         (void)hipFree(taps); (void)hipFree(tmp);
         return fail(VISTAF_E_HIP, "memcpy taps");
     }
-    launch_gauss_blur(src, tmp, dst, taps, (int)f.size(), B, h, w, (hipStream_t)stream);
-    return hook_finish(taps, tmp, (hipStream_t)stream);
+    const int tier = launch_gauss_blur(src, tmp, dst, taps, (int)f.size(), B, h, w, (hipStream_t)stream, Tiers().gauss_strip != 0, variant);
+    const int rc = hook_finish(taps, tmp, (hipStream_t)stream);
+    return rc ? rc : tier;
+}
+int vistaf_ftp_test_gauss_strip_fits(int h, int w, int ksize)
+{
+    if (h < 1 || w < 1 || ksize < 1 || !(ksize & 1)) return fail(VISTAF_E_INVALID, "bad argument");
+    return gauss_strip_fits(h, w, ksize) ? 1 : 0;
+}
+int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream)
+{
+    const int rc = vistaf_ftp_test_gauss_variant(src, dst, sigma, B, h, w, 0, stream);
+    return rc < 0 ? rc : 0;
 }
 
 // The two chamfer hooks.  force: the one-wave two-pass kernel, which has no instance for every width; otherwise the dispatch, whose tier is

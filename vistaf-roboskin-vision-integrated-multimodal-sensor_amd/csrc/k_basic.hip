@@ -353,15 +353,106 @@ __global__ __launch_bounds__(256) void k_gauss_fused(const float *__restrict__ s
                kern, ksize, h, w);
 }
 
-// separable blur src -> dst (tmp: intermediate plane of the two-kernel path)
-void launch_gauss_blur(const float *src, float *tmp, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st)
+// Both passes in one kernel for long kernels on frames whose height fits LDS (gauss_strip_fits, kernels.hpp): a workgroup owns GS_TX output
+// columns of one frame over the full height.  Row pass: the strip's input, GS_TX + 2r columns wide, goes through an LDS tile in chunks of GS_CH
+// rows; the next chunk's loads are in flight (in registers) while the current one is filtered by gauss_row4_ahead into the LDS plane
+// mid[h][GS_TX], rounded to float exactly as the intermediate plane of the two-kernel path is.  Column pass: gauss_col_symm's sequence
+// (gauss_col_symm_ahead) out of that plane, rows beyond the frame as reflect101 indices into it, so a strip needs no row halo and any radius
+// works.  Same taps, same order per output: same bits as k_gauss_rows + k_gauss_cols.  src != dst: neighbouring strips read each other's
+// columns.  The taps are copied to LDS first: at three waves per SIMD the kernel lives on having the next step's LDS reads in flight, and
+// scalar loads of the taps inside the loops would share a counter with them and drain it every step.
+//
+// A wave loads, stores and filters the same eight rows of a chunk, 2 wv + {0, 1} + {0, 8, 16, 24}: with a pitch that is an odd multiple of
+// four floats, rows 8 apart lie 32 banks apart, and the lanes that one ds_read_b128 lane group serves (quartets 0 / 3 / 5 / 6 and
+// 1 / 2 / 4 / 7 of each half wave) are given rows that tile the 64 banks.
+// The strips of a frame share most of their input columns, and consecutive workgroups go to different XCDs, each with an L2 of its own:
+// the block index is remapped so that a frame's strips run on one XCD (nblk = B * nstrip blocks, bijective for any nblk).
+__global__ __launch_bounds__(256) void k_gauss_strip(const float *__restrict__ src, float *__restrict__ dst, const float *__restrict__ kern,
+                                                     int ksize, int h, int w, int nstrip, int nblk)
 {
-    if (ksize <= GF_MAXK && src != dst) {
+    extern __shared__ float4 gs_lds[];
+    static_assert(GS_CH == 32 && GS_TX == 32, "four waves of eight rows, eight quads per row");
+    constexpr int NL = GS_CH / 4;      // rows a wave owns per chunk
+    int b, x0;
+    {
+        const int i = blockIdx.x, q = nblk >> 3, rem = nblk & 7, g = i & 7;
+        const int id = (g < rem ? g * (q + 1) : rem * (q + 1) + (g - rem) * q) + (i >> 3);
+        b = id / nstrip;
+        x0 = (id - b * nstrip) * GS_TX;
+    }
+    const int r = ksize / 2, tw = GS_TX + 2 * r, pitch = gs_pitch(ksize);
+    float *mid = reinterpret_cast<float *>(gs_lds);      // [h][GS_TX]
+    float *tile = mid + (size_t)h * GS_TX;               // [GS_CH][pitch]
+    float *ktap = tile + GS_CH * pitch, *kshift = ktap + GS_KPAD;      // the taps k[i], and k[i + 1] (the row pass reads them as aligned float4)
+    if (threadIdx.x < GS_KPAD) {
+        const int i = threadIdx.x;
+        ktap[i] = i < ksize ? kern[i] : 0.0f;
+        kshift[i] = i + 1 < ksize ? kern[i + 1] : 0.0f;
+    }
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const float *plane = src + (size_t)b * h * w;
+    // the lane's (at most two) source columns, reflected once; lanes without a second column repeat their first one (no branch between the loads)
+    const bool one = lane < tw, two = lane + 64 < tw;
+    const int sx0 = reflect101(x0 + (one ? lane : 0) - r, w), sx1 = reflect101(x0 + (two ? lane + 64 : 0) - r, w);
+    // the row this lane filters: quartet pairs (octets) 0..3 of a half wave take rows +0, +16, +8, +24
+    const int oct = lane >> 3;
+    const int frow = 2 * wv + (oct >> 2) + 8 * (((oct & 1) << 1) | ((oct >> 1) & 1)), tx = (lane & 7) * 4;
+    const int nch = (h + GS_CH - 1) / GS_CH;
+    float va[NL], vb[NL];
+    // all loads of a chunk are issued before the first store (rows past the frame repeat its last row and are not filtered into mid)
+#define GS_REQUEST(c)                                                                             \
+    _Pragma("unroll") for (int i = 0; i < NL; i++) {                                              \
+        const float *row = plane + (size_t)min((c) * GS_CH + 2 * wv + (i & 1) + 8 * (i >> 1), h - 1) * w; \
+        va[i] = row[sx0];                                                                         \
+        vb[i] = row[sx1];                                                                         \
+    }
+    GS_REQUEST(0)
+    for (int c = 0; c < nch; c++) {
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+            float *trow = tile + (2 * wv + (i & 1) + 8 * (i >> 1)) * pitch;
+            if (one) trow[lane] = va[i];
+            if (two) trow[lane + 64] = vb[i];
+        }
+        __syncthreads();
+        if (c + 1 < nch) { GS_REQUEST(c + 1) }
+        const int y = c * GS_CH + frow;
+        const float4 o = gauss_row4_ahead(reinterpret_cast<const float4 *>(tile + frow * pitch + tx), reinterpret_cast<const float4 *>(kshift), ktap[0], ksize);
+        if (y < h) *reinterpret_cast<float4 *>(mid + y * GS_TX + tx) = o;
+        __syncthreads();      // the tile is free for the next chunk; after the last chunk: mid is complete
+    }
+#undef GS_REQUEST
+    // column pass: GC_R consecutive rows of one column per thread, 64 rows of the strip per round
+    const int col = threadIdx.x & 31, x = x0 + col;
+    const float *tc = mid + col;
+    float *out = dst + (size_t)b * h * w;
+    for (int yb = (threadIdx.x >> 5) * GC_R; yb < h; yb += 8 * GC_R) {
+        float acc[GC_R];
+        const auto kl = [&](int j) { return ktap[r + j]; };
+        if (yb >= r && yb + GC_R - 1 + r < h) gauss_col_symm_ahead([&](int i) { return tc[(yb + i) * GS_TX]; }, kl, r, acc);
+        else gauss_col_symm_ahead([&](int i) { return tc[reflect101(yb + i, h) * GS_TX]; }, kl, r, acc);
+        if (x < w) {
+#pragma unroll
+            for (int o = 0; o < GC_R; o++)
+                if (yb + o < h) out[(size_t)(yb + o) * w + x] = acc[o];
+        }
+    }
+}
+
+int launch_gauss_blur(const float *src, float *tmp, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st, bool strip, int force)
+{
+    if (!force && ksize <= GF_MAXK && src != dst) {
         VF_LAUNCH_GAUSS_TILE(k_gauss_fused, ksize, B, h, w, st, src, dst, kern, ksize, h, w);
-        return;
+        return GAUSS_TILE;
+    }
+    if (force ? force == GAUSS_STRIP : (strip && src != dst && gauss_strip_fits(h, w, ksize))) {
+        const int nstrip = (w + GS_TX - 1) / GS_TX, nblk = B * nstrip;
+        hipLaunchKernelGGL(k_gauss_strip, dim3(nblk), dim3(256), gauss_strip_lds(h, ksize), st, src, dst, kern, ksize, h, w, nstrip, nblk);
+        return GAUSS_STRIP;
     }
     launch_gauss_rows(src, tmp, kern, ksize, B, h, w, st);
     launch_gauss_cols(tmp, dst, kern, ksize, B, h, w, st);
+    return GAUSS_TWO;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -58,15 +58,18 @@ void launch_smooth_reliable(const float *detr, const float *bg_med, const uint8_
 }
 
 // ---- frontier taper -> unreliable-region blur -> clamp -> mm curve: k_frontier_compose, k_gauss_fused, k_finalize_unitless, k_to_mm ------
-// dist_out and depth may be the same plane (the second distance transform lands in `depth`): a pixel's distance is read and its depth
-// written by the same thread and no other thread looks at it, so neither pointer is __restrict__.
+// dist_out is never a plane the kernel writes (post_demod puts the second distance transform into a plane that is idle when this kernel
+// runs, not into `depth`), so every pointer is __restrict__ and the store step's reads of a tile's eight output rows (GaussTile's `pre`)
+// are all in flight before the float64 mm curve of the first row is evaluated.
+struct ComposeRowIn { uint8_t roi, rel; float den, dist; };
 template <int RMAX>
 __global__ __launch_bounds__(256) void k_compose_finalize_mm(const float *__restrict__ hmap, const uint8_t *__restrict__ reliable,
                                                              const uint8_t *__restrict__ roi, const float *__restrict__ dist_in, float taper_band,
-                                                             const float *__restrict__ roi_den, const float *dist_out, float band, int use_band,
-                                                             Curve curve, int use_neg, float *__restrict__ unitless, float *depth,
-                                                             uint8_t *__restrict__ cand, unsigned int *__restrict__ gmax_bits,
-                                                             const float *__restrict__ kern, int ksize, int h, int w)
+                                                             const float *__restrict__ roi_den, const float *__restrict__ dist_out, float band,
+                                                             int use_band, Curve curve, int use_neg, float *__restrict__ unitless,
+                                                             float *__restrict__ depth, uint8_t *__restrict__ cand,
+                                                             unsigned int *__restrict__ gmax_bits, const float *__restrict__ kern, int ksize, int h,
+                                                             int w)
 {
     __shared__ __align__(16) GaussTile<RMAX, 1> tile;
     __shared__ unsigned long long scratch[16];
@@ -79,10 +82,16 @@ __global__ __launch_bounds__(256) void k_compose_finalize_mm(const float *__rest
                    const float hgt = hmap[i], din = dist_in[i];
                    v[0] = frontier_compose_px(rel && in_roi, hgt, din, taper_band);
                },
-               [&](size_t b, int y, int x, const float (&blur)[1], const float (&z0)[1]) {
+               [&](size_t b, int y, int x) {
                    const size_t p = (size_t)y * w + x, i = b * P + p;
-                   const bool in_roi = roi[p] != 0, rel = in_roi && reliable[i] != 0;
-                   const float u = finalize_unitless_px(in_roi, rel, z0[0], true, blur[0], roi_den[p], use_band != 0, dist_out[i], band);
+                   ComposeRowIn c;
+                   c.roi = roi[p]; c.rel = reliable[i]; c.den = roi_den[p]; c.dist = dist_out[i];
+                   return c;
+               },
+               [&](size_t b, int y, int x, const float (&blur)[1], const float (&z0)[1], const ComposeRowIn &in) {
+                   const size_t i = b * P + (size_t)y * w + x;
+                   const bool in_roi = in.roi != 0, rel = in_roi && in.rel != 0;
+                   const float u = finalize_unitless_px(in_roi, rel, z0[0], true, blur[0], in.den, use_band != 0, in.dist, band);
                    unitless[i] = u;
                    float d;
                    const bool c = to_mm_px(u, in_roi, curve, use_neg, d);

@@ -27,6 +27,7 @@ struct Tiers {
     int fused_masks = 7;        // bits 1 / 2 / 4: the bad-pixel, reliable and contact mask chain of frames mask_chain_fits takes run as one launch each, bit planes in LDS (k_maskchain.hip); 0: the separate kernels
     int dft_staged = 1;         // 1: the demodulation stages dft_staged_fits names take their operands from LDS (k_dft.hip: k_dft_fwd1_staged, k_dft_inv2_staged); 0: every stage reads global memory / L2 per k-step
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
+    int gauss_strip = 1;        // 1: a session's long Gaussians (> 15 taps) on frames gauss_strip_fits takes run both passes in one launch, the intermediate in LDS (k_gauss_strip); 0: the row and the column kernel
 };
 
 // Frames of 512 x 512 pixels and more: the ones whose per-frame stages are split over the chip (k_big.hip and the chunked tiers)
@@ -57,7 +58,11 @@ void launch_morph(const uint8_t *src, uint8_t *dst, int B, int h, int w, const R
 void launch_morph_seq(const uint8_t *src, uint8_t *dst, uint8_t *tmp, int B, int h, int w, const RowSpanSE &se, const int *dilates, int n,
                       const uint8_t *and_static, const uint8_t *and_frame, hipStream_t st, uint16_t *prefix_scratch = nullptr);
 void launch_gauss_rows(const float *src, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st);
-void launch_gauss_blur(const float *src, float *tmp, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st);
+// separable blur src -> dst (tmp: intermediate plane of the two-kernel path).  strip: Tiers::gauss_strip.  force: 0 the dispatch, or GAUSS_TWO, or
+// GAUSS_STRIP where the caller has checked gauss_strip_fits and src != dst (vistaf_ftp_test_gauss_variant).  Returns the tier launched
+enum GaussTier { GAUSS_TWO = 1, GAUSS_STRIP = 2, GAUSS_TILE = 3 };      // k_gauss_rows + k_gauss_cols[_lds]; k_gauss_strip; k_gauss_fused
+int launch_gauss_blur(const float *src, float *tmp, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st, bool strip = false,
+                      int force = 0);
 void launch_gauss_cols(const float *src, float *dst, const float *kern, int ksize, int B, int h, int w, hipStream_t st);
 void launch_illum_norm(const float *img, const float *blur, float *out, int B, int P, hipStream_t st);
 void launch_mul_static(const float *a, const float *stat, float *out, int B, int P, hipStream_t st);
@@ -70,6 +75,21 @@ void launch_camera_gray(const void *frames, int format, float *gray, int B, int 
 
 constexpr int GF_MAXK = 15;    // longest Gaussian that takes the one-kernel LDS tile (gauss_tile.hpp); longer ones run a row and a column kernel
 
+// ---- k_gauss_strip (k_basic.hip): both passes of a long Gaussian in one launch.  A workgroup owns GS_TX output columns of one frame over the full
+// height: the row pass streams chunks of GS_CH rows x (GS_TX + 2r) columns through an LDS tile into an LDS plane mid[h][GS_TX], the column pass
+// runs out of that plane.  GS_MAXK: the longest kernel whose chunk row two loads per lane cover (GS_TX + 2r <= 128)
+constexpr int GS_TX = 32, GS_CH = 32, GS_MAXK = 97, GS_KPAD = 104;      // GS_KPAD: floats per LDS copy of the taps (GS_MAXK + 1 and a multiple of four, zero-filled)
+constexpr size_t GS_LDS_MAX = 48 * 1024;      // what a kernel may hold beside the window march's 111 KB ("Sharing a CU")
+// floats between the rows of the chunk tile: an ODD multiple of four, so that rows 8 apart lie 32 banks apart (the row pass pairs them in a
+// ds_read_b128 lane group, gauss_strip_rows)
+constexpr int gs_pitch(int ksize) { return 4 * (((GS_TX + 2 * (ksize / 2) + 3) / 4) | 1); }
+inline size_t gauss_strip_lds(int h, int ksize) { return ((size_t)h * GS_TX + (size_t)GS_CH * gs_pitch(ksize) + 2 * GS_KPAD) * sizeof(float); }
+// whether launch_gauss_blur may take k_gauss_strip for a ksize-tap blur of h x w frames (src != dst is the caller's to know)
+inline bool gauss_strip_fits(int h, int w, int ksize)
+{
+    return h >= 1 && w >= 1 && ksize > GF_MAXK && ksize <= GS_MAXK && gauss_strip_lds(h, ksize) <= GS_LDS_MAX;
+}
+
 // ---- k_blurchain.hip: short blurs (ksize <= GF_MAXK) with their neighbouring element-wise passes fused in ------------------------------
 // iw = blur(img / (blur_illum + 1e-6) - 1) * apo
 void launch_illum_pre_apod(const float *img, const float *blur_illum, const float *apo, float *iw, const float *kern, int ksize, int B, int h,
@@ -77,7 +97,7 @@ void launch_illum_pre_apod(const float *img, const float *blur_illum, const floa
 // hmap = blur(z0) / (blur(m) + 1e-6), (z0, m) of launch_sub_scalar_mask
 void launch_smooth_reliable(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, const float *kern, int ksize, int B,
                             int h, int w, hipStream_t st);
-// launch_frontier_compose, blur, launch_finalize_unitless and launch_to_mm in one; dist_out may be the plane `depth`
+// launch_frontier_compose, blur, launch_finalize_unitless and launch_to_mm in one; dist_out must not be a plane the kernel writes (unitless, depth, cand)
 void launch_compose_finalize_mm(const float *hmap, const uint8_t *reliable, const uint8_t *roi, const float *dist_in, float taper_band,
                                 const float *roi_den, const float *dist_out, float band, int use_band, Curve curve, int use_neg, float *unitless,
                                 float *depth, uint8_t *cand, unsigned int *gmax_bits, const float *kern, int ksize, int B, int h, int w,

@@ -52,6 +52,9 @@ extern "C" {
  *                      the column tiles finished two at a time); 0 the kernels that fetch one element per lane and k-step from global memory.  Every
  *                      accumulator receives the same k-steps in the same order with the same operands: same bits either way.  test_hooks_dft.h has the
  *                      direct hooks that run either kernel of a stage
+ *       "gauss_strip"  1 (default) a Gaussian of more than 15 taps on frames gauss_strip_fits (kernels.hpp) takes -- up to 97 taps, the strip's LDS need
+ *                      within 48 KB -- runs both passes in one launch, a workgroup per frame and strip of 32 columns with the intermediate plane in
+ *                      LDS (k_gauss_strip); 0, or a blur it does not take: the row and the column kernel.  Same bits either way
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
@@ -90,9 +93,10 @@ int vistaf_ftp_test_select_chained(const float *vals, const uint8_t *mask, size_
 int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,
                             float *resid, int B, int h, int w, int variant, void *stream);
 
-/* launch_gauss_blur (src != dst) with the taps a session builds for `sigma`: up to 15 taps the one-kernel LDS tile, beyond the row and
- * the column kernel. */
+/* launch_gauss_blur (src != dst) with the taps a session builds for `sigma`, dispatched as a session does: up to 15 taps the one-kernel LDS
+ * tile, beyond that the strip kernel where gauss_strip_fits (kernels.hpp) takes the blur, else the row and the column kernel. */
 int vistaf_ftp_test_gauss(const float *src, float *dst, double sigma, int B, int h, int w, void *stream);
+/* (test_hooks_gauss.h: the same with a kernel variant, and what a blur takes) */
 
 /* The one-wave two-pass chamfer transform (cv::distanceTransform DIST_L2, 3x3) forced, whatever kernel a session would pick for (h, w, cap_px).
  * pair != 0: launch_chamfer_pair, ONE launch for dist_a[b] = distance to the zero pixels and dist_b[b] = distance to the non-zero pixels of
