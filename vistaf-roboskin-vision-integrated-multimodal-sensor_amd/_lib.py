@@ -84,6 +84,15 @@ MATCH_FLAGS = {"clipped": 1, "border_shift": 2, "weak": 4, "ambiguous": 8}      
 # VISTAF_MATCH_MAGIC, _HEADER_INTS, _MIN_P, _MAX_P, _MAX_R, _MAX_T, _MAX_SYMMETRY, _MAX_SHIFT, _MAX_ROWS
 MATCH_MAGIC, MATCH_HEADER_INTS, MATCH_MIN_P, MATCH_MAX_P, MATCH_MAX_R, MATCH_MAX_T, MATCH_MAX_SYMMETRY, MATCH_MAX_SHIFT, MATCH_MAX_ROWS = \
     0x31424d56, 16, 5, 33, 64, 64, 8, 8, 2048
+NCENTRELINE = 40        # doubles per row of the centreline read-out (VISTAF_NCENTRELINE, include_ext/vistaf_centreline.h)
+# fields of a centreline row in the order of the VISTAF_CENTRELINE_* indices; 37..39 are reserved
+CENTRELINE_NAMES = ["pixels", "skeleton_pixels", "thinning_passes", "end_pixels", "branch_pixels", "stations", "stations_written", "status", "a_x",
+                    "a_y", "b_x", "b_y", "path_length_mm", "length_mm", "chord_mm", "tortuosity", "sagitta_mm", "sagitta_station",
+                    "interior_stations", "width_mean_mm", "width_min_mm", "width_min_station", "width_max_mm", "width_max_station", "width_seed_mm",
+                    "elongation", "a_tx", "a_ty", "b_tx", "b_ty", "a_at_border", "b_at_border", "depth_mean_mm", "depth_a_mm", "depth_b_mm",
+                    "depth_peak_mm", "depth_peak_station"]
+# VISTAF_CLST_*: values (ok, no_pixels, point) and flags (branched, truncated) of the `status` field
+CENTRELINE_STATUS = {"ok": 0, "no_pixels": 1, "point": 2, "branched": 8, "truncated": 16}
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -315,6 +324,15 @@ MATCH_SIGNATURES = {
     "vistaf_match_workspace_bytes": (ci, [ci, ci, ci, ci, ci, ci, ci, P(sz)]),
     "vistaf_match_measure": (ci, [vp, vp, vp, vp, vp, vp, sz, P(i32), cf, ci, ci, cd, cd, ci, ci, ci, ci, vp, vp, vp, vp, sz, vp]),
 }
+# include_ext/vistaf_centreline.h: the centreline read-out, two plain functions, the same pattern (tests/test_centrelines.py holds it
+# against that header), and csrc/test_hooks_centreline.h: which storage tier a box takes
+CENTRELINE_SIGNATURES = {
+    "vistaf_centreline_workspace_bytes": (ci, [ci, ci, ci, ci, P(sz)]),
+    "vistaf_centreline_measure": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, sz, vp]),
+}
+CENTRELINE_TEST_SIGNATURES = {
+    "vistaf_ftp_test_centreline_tier": (ci, [ci, ci]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -333,7 +351,8 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES,
+                                                 CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -328,6 +328,7 @@ class FtpSensor(Handle):
     _outlines = property(lambda self: self._live("outlines"))
     _textures = property(lambda self: self._live("textures"))
     _matches = property(lambda self: self._live("matches"))
+    _centrelines = property(lambda self: self._live("centrelines"))
 
     def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
         last = getattr(self, "_last_out", None)
@@ -501,6 +502,28 @@ class FtpSensor(Handle):
                                    self.config.depth_eps_mm, bank, ws, **params))
         return out
 
+    def centrelines(self, max_contacts: int = 8, max_stations: Optional[int] = None, **params) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the centreline of every contact (centreline.contact_centrelines; an extension, the
+        reference has no counterpart).  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map (the depth
+        plane of the DEPTH_* fields) and the frames' mm_per_px (the `scalars` column) to the centreline read-out; its workspace is the
+        session's, made on first use and again when max_contacts changes.  params: tangent_span (default 8), skeleton (default True).
+        Returns the contacts dict plus centrelines [B,K,40] f64 (fields CENTRELINE_NAMES: skeleton counts, ends, lengths, bend, widths,
+        tangents, border flags, depth along the path), stations [B,V,2] i32, station_d2 [B,V] i32 and offsets [B,K+1] i32, the axis paths
+        and their squared half-widths (`centreline.trim` cuts them), and skeleton [B,h,w] i8.  max_stations: V per frame, by default
+        2 * (h + w) (`centreline.default_max_stations`); rows that do not fit show stations_written < stations; 0: no polylines."""
+        from .centreline import CentrelineWorkspace, contact_centrelines
+        unknown = set(params) - {"tangent_span", "skeleton"}
+        if unknown:
+            raise TypeError(f"centrelines() got unexpected keyword arguments {sorted(unknown)}")
+        k = int(max_contacts)
+        ws = self._matching("centrelines", (k,))
+        out = self.contacts(k, index_plane=True)
+        if ws is None:
+            ws = self._keep("centrelines", (k,), CentrelineWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out.update(contact_centrelines(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), self._last_out["height_map_mm"],
+                                       max_stations=max_stations, workspace=ws, **params))
+        return out
+
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
         """Taxel read-out of the last predict (taxels.TaxelReadout; an extension, the reference has no counterpart): the height map reduced to
         the fixed cells of `layout` (taxels.grid_layout, polar_layout, from_map) and to the frame's wrench.  Hands the predict's height map,
@@ -672,7 +695,7 @@ class FtpSensor(Handle):
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
                 motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None,
                 outlines: bool = False, textures: Optional[Dict[str, Any]] = None,
-                matches: Optional[Dict[str, Any]] = None) -> Optional[Dict[str, Any]]:
+                matches: Optional[Dict[str, Any]] = None, centrelines=False) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -701,7 +724,13 @@ class FtpSensor(Handle):
         textures=dict(...) (with contacts=K; the keyword arguments of `FtpSensor.textures` but `max_contacts`, possibly none) adds "textures",
         one dict of TEXTURE_NAMES per entry of "contacts".
         matches=dict(bank=..., ...) (with contacts=K; `bank` a match.TemplateBank and the keyword arguments of `FtpSensor.matches` but
-        `max_contacts`) adds "matches", one dict of MATCH_NAMES per entry of "contacts"."""
+        `max_contacts`) adds "matches", one dict of MATCH_NAMES per entry of "contacts".
+        centrelines=True or dict(...) (with contacts=K; the keyword arguments of `FtpSensor.centrelines` but `max_contacts` and `skeleton`)
+        adds "centrelines", one dict of CENTRELINE_NAMES per entry of "contacts", "centreline_stations", per entry the [n,2] list of its axis
+        path from A to B (None for a row that did not fit the capacity), and "centreline_d2", per entry the squared half-widths along it."""
+        want_centrelines = centrelines is not None and centrelines is not False
+        if want_centrelines and contacts is None:
+            raise ValueError("centrelines=True needs contacts=K")
         if matches is not None and contacts is None:
             raise ValueError("matches=dict(bank=..., ...) needs contacts=K")
         if matches is not None and "bank" not in matches:
@@ -788,6 +817,18 @@ class FtpSensor(Handle):
                 res["matches"] = matches_table(mt["matches"].cpu().numpy(), mt["count"].cpu().numpy())
                 for r in res["matches"]:
                     r.pop("frame")
+            if want_centrelines:
+                from .writers import centreline_frame_record, centrelines_table
+                cl = self.centrelines(int(contacts), skeleton=False, **({} if centrelines is True else dict(centrelines)))
+                res["centrelines"] = centrelines_table(cl["centrelines"].cpu().numpy(), cl["count"].cpu().numpy())
+                for r in res["centrelines"]:
+                    r.pop("frame")
+                if "stations" in cl:
+                    rec = centreline_frame_record(cl["centrelines"][0].cpu().numpy(), cl["stations"][0].cpu().numpy(), cl["station_d2"][0].cpu().numpy(),
+                                                  cl["offsets"][0].cpu().numpy(), int(cl["count"][0].item()))
+                    res["centreline_stations"], res["centreline_d2"] = rec["stations"], rec["d2"]
+                else:                                           # max_stations=0: no polylines were asked for
+                    res["centreline_stations"], res["centreline_d2"] = [None] * len(res["centrelines"]), [None] * len(res["centrelines"])
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table
             running = self._pressure                            # without contacts=K the table's size is nobody's concern: keep the running one

@@ -79,6 +79,15 @@ MATCH_FIELDS = ("status", "flags", "label", "template", "class", "rotation", "sh
 MATCH_INT_FIELDS = ("status", "flags", "label", "template", "class", "rotation", "shift_x", "shift_y", "second_class", "support_pixels",
                     "valid_shifts")                                                      # -1 for NaN: what a status leaves out
 MATCHES_CSV_FIELDS = ("frame", "contact") + MATCH_FIELDS
+CENTRELINE_FIELDS = ("pixels", "skeleton_pixels", "thinning_passes", "end_pixels", "branch_pixels", "stations", "stations_written", "status", "a_x",
+                     "a_y", "b_x", "b_y", "path_length_mm", "length_mm", "chord_mm", "tortuosity", "sagitta_mm", "sagitta_station",
+                     "interior_stations", "width_mean_mm", "width_min_mm", "width_min_station", "width_max_mm", "width_max_station", "width_seed_mm",
+                     "elongation", "a_tx", "a_ty", "b_tx", "b_ty", "a_at_border", "b_at_border", "depth_mean_mm", "depth_a_mm", "depth_b_mm",
+                     "depth_peak_mm", "depth_peak_station")                              # VISTAF_CENTRELINE_* order (include_ext/vistaf_centreline.h)
+CENTRELINE_INT_FIELDS = ("pixels", "skeleton_pixels", "thinning_passes", "end_pixels", "branch_pixels", "stations", "stations_written", "status",
+                         "a_x", "a_y", "b_x", "b_y", "sagitta_station", "interior_stations", "width_min_station", "width_max_station",
+                         "a_at_border", "b_at_border", "depth_peak_station")             # -1 for NaN: what a row without pixels, or without depth, leaves out
+CENTRELINES_CSV_FIELDS = ("frame", "contact") + CENTRELINE_FIELDS
 TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                 "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
 TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
@@ -351,6 +360,40 @@ def matches_table(matches, count) -> list:
 def write_matches_csv(output_dir: str, matches, count, filename: str = "matches.csv") -> str:
     """matches.csv: one line per written contact, columns MATCHES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
     return _write_csv(output_dir, filename, MATCHES_CSV_FIELDS, matches_table(matches, count))
+
+
+def centrelines_table(centrelines, count) -> list:
+    """Row dicts of the centreline table: centrelines [B,K,>=37] (or [K,>=37] for one frame) float64 as `FtpSensor.centrelines` returns it,
+    count [B].  One dict per written contact, as `contacts_table`: `frame`, `contact` and CENTRELINE_FIELDS, the counts, status, end pixels,
+    station numbers and border flags as ints (-1 where the header leaves the field NaN); every other field it leaves out is NaN."""
+    return _table(centrelines, count, CENTRELINE_FIELDS, CENTRELINE_INT_FIELDS, "centrelines must be [B,K,>=37] with count [B]", int_conv=_int_or_minus_one)
+
+
+def write_centrelines_csv(output_dir: str, centrelines, count, filename: str = "centrelines.csv") -> str:
+    """centrelines.csv: one line per written contact, columns CENTRELINES_CSV_FIELDS, floats with repr(); lines match contacts.csv's one to one."""
+    return _write_csv(output_dir, filename, CENTRELINES_CSV_FIELDS, centrelines_table(centrelines, count))
+
+
+def centreline_frame_record(centrelines, stations, station_d2, offsets, count) -> Dict[str, Any]:
+    """One frame's centrelines for a JSON document of the caller's own: centrelines [K,>=37], stations [V,2], station_d2 [V], offsets [K+1],
+    count (a scalar).  {"contact_count", "centrelines": the row dicts without `frame`, NaN as null, "stations": per row the [[x, y], ...]
+    list of its axis path from end A to end B, null for a row that was not written (stations_written < stations), "d2": per row the
+    squared distances to the rim that go with them}."""
+    rows = centrelines_table(np.asarray(centrelines, dtype=np.float64), np.asarray([count]))
+    v, d, o = np.asarray(stations), np.asarray(station_d2), np.asarray(offsets)
+    if v.ndim != 2 or v.shape[1] != 2 or d.ndim != 1 or d.shape[0] != v.shape[0] or o.ndim != 1 or o.shape[0] != np.asarray(centrelines).shape[0] + 1:
+        raise ValueError("stations must be [V,2], station_d2 [V] and offsets [K+1] for centrelines [K,>=37]")
+    lines, widths = [], []
+    for r in rows:
+        r.pop("frame")
+        k = r["contact"]
+        whole = r["stations_written"] == r["stations"]
+        lines.append([[int(x), int(y)] for x, y in v[o[k]:o[k + 1]]] if whole else None)
+        widths.append([int(q) for q in d[o[k]:o[k + 1]]] if whole else None)
+        for name, val in r.items():
+            if isinstance(val, float) and not math.isfinite(val):
+                r[name] = None
+    return {"contact_count": int(count), "centrelines": rows, "stations": lines, "d2": widths}
 
 
 def match_frame_record(matches, count, scores=None) -> Dict[str, Any]:
