@@ -306,6 +306,13 @@ GAUSS_STRIP_SIGNATURES = {
     "vistaf_ftp_test_gauss_variant": (ci, [vp, vp, cd, ci, ci, ci, ci, vp]),
     "vistaf_ftp_test_gauss_strip_fits": (ci, [ci, ci, ci]),
 }
+# csrc/test_hooks_fit.h: the IRLS fit through the window kernel, alone and as a chained pair, and the instance a frame size takes
+# (tests/test_fit_window.py holds the table against that header)
+FIT_WINDOW_SIGNATURES = {
+    "vistaf_ftp_test_polyfit_window": (ci, [vp, vp, ci, ci, cf, ci, ci, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "vistaf_ftp_test_polyfit_chain": (ci, [vp, vp, ci, ci, ci, cf, ci, ci, ci, vp, vp, vp, ci, ci, ci, ci, vp, vp]),
+    "vistaf_ftp_test_polyfit_window_instance": (ci, [ci, ci, ci]),
+}
 # include_ext/vistaf_outline.h: the contact outline read-out, two plain functions outside the drop-in boundary of include/*.h, in a table of
 # their own as well (tests/test_outlines.py holds it against that header)
 OUTLINE_SIGNATURES = {
@@ -351,7 +358,8 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES, MATCH_SIGNATURES,
+    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, FIT_WINDOW_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES,
+                                                 MATCH_SIGNATURES,
                                                  CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)

@@ -20,6 +20,7 @@ using namespace vf;
 #include "test_hooks_masks.h"
 #include "test_hooks_dft.h"
 #include "test_hooks_gauss.h"
+#include "test_hooks_fit.h"
 #ifdef VISTAF_DEBUG
 namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); void telea_window_mw_debug_dump(int B); void fit_debug_dump(); void unwrap_big_debug_dump(); void unwrap_batch_debug_dump(); }
 #endif
@@ -88,6 +89,7 @@ struct vistaf_ftp_handle {
     void *inpaint_scratch, *inpaint_cl_scratch, *inpaint_win_scratch, *unwrap_scratch;
     void *big_scratch = nullptr;      // k_big.hip (large_frame), else null
     size_t big_scratch_bytes = 0;
+    int32_t *fit_need;          // [max_batch] of the window kernel of the detrend's chained first two fits: 1 the frame's mask rows did not fit the window and the plain-size kernel ran it, 0 the window kernel did, -1 never written
     int32_t *unwrap_need;       // [max_batch] 1: the frame went through the priority flood, 0: the consistency check settled it
     // small per-frame arrays
     float *thr_hi, *thr_g, *mu, *amp_thr, *thr3, *thr_used, *bg_med, *core_thr, *core_med, *coef;
@@ -499,6 +501,8 @@ int vistaf_ftp_create(const vistaf_ftp_config *cfg, int h, int w, int cx, int cy
         }
         TRY(dalloc(hd, &hd->unwrap_need, (size_t)max_batch, "unwrap_need", sizeof(int32_t)));
         HIPCHK(hipMemset(hd->unwrap_need, 0xff, (size_t)max_batch * sizeof(int32_t)));        // -1: never written (the check is off or does not cover this frame size)
+        TRY(dalloc(hd, &hd->fit_need, (size_t)max_batch, "fit_need", sizeof(int32_t)));
+        HIPCHK(hipMemset(hd->fit_need, 0xff, (size_t)max_batch * sizeof(int32_t)));           // -1: never written (no window instance for this frame size, or "fit_window" = 0)
     }
     int pmax = 2 * bwp + 1;
     hd->pmax = pmax;
@@ -663,12 +667,17 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
 
     // ---- plane removal + two-pass detrend (shape_ftp.py:1706, :1716-1751)
     if (timed) hipEventRecord(hd->ev[ST_DETREND], st);
-    if (c.plane_order_for_removal > 0)
-        // debug_ramp gates on the reliable count, NaN pixels included (:1364-1366), robust_polyfit2d on 200 finite samples (:1103)
-        launch_robust_polyfit(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, B, h, w, st, chain_scratch(hd));
-    else   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
+    const bool fit_win = hd->tiers.fit_window != 0;
+    if (c.plane_order_for_removal > 0) {
+        // debug_ramp gates on the reliable count, NaN pixels included (:1364-1366), robust_polyfit2d on 200 finite samples (:1103); the first detrend
+        // fit takes its output under the same mask: one chained launch where a column kernel applies, else the two launches
+        const FitSecond detrend1 = {c.poly_order, 0, hd->resid0};
+        launch_robust_polyfit_window(hd->unwrapped, hd->reliable, c.plane_order_for_removal, c.irls_iters, (float)c.irls_c, 200, 500, hd->coef, hd->phase1, &detrend1,
+                                     hd->fit_need, fit_win, 0, B, h, w, st, chain_scratch(hd));
+    } else {   // no debug_ramp (the constants of Code/phase_to_height.py): the unwrapped phase goes to the detrend as it is
         HIPCHK(hipMemcpyAsync(hd->phase1, hd->unwrapped, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
-    launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
+        launch_robust_polyfit(hd->phase1, hd->reliable, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->resid0, B, h, w, st, chain_scratch(hd));
+    }
     select(hd, hd->resid0, hd->reliable, (size_t)P, nullptr, true, hd->req_contact, 3, hd->thr3, nullptr, B, st);
     {
         const ContactScratchPlanes ws = {hd->contact, hd->cand, hd->morph_pre};      // cand is free until the blob filter
@@ -677,6 +686,7 @@ static int post_demod(vistaf_ftp_handle *hd, int B, float *d_height_mm, uint8_t 
                                             (hd->tiers.fused_masks & MCH_CONTACT) != 0, B, h, w, st);
         if (tier < 0) return tier;
     }
+    // (the window kernel alone does not pay on a single fit, DESIGN.md section 6: the third fit keeps the plain kernel)
     launch_robust_polyfit(hd->phase1, hd->background, c.poly_order, c.irls_iters, (float)c.irls_c, 200, 0, hd->coef, hd->detr, B, h, w, st, chain_scratch(hd));
     select(hd, hd->detr, hd->background, (size_t)P, nullptr, false, hd->req_med, 1, hd->bg_med, nullptr, B, st);
 
@@ -934,6 +944,7 @@ int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value)
     else if (n == "dft_staged") hd->tiers.dft_staged = value != 0;
     else if (n == "fused_chains") hd->tiers.fused_chains = value != 0;
     else if (n == "gauss_strip") hd->tiers.gauss_strip = value != 0;
+    else if (n == "fit_window") hd->tiers.fit_window = value != 0;
     else if (n == "fused_backend") hd->tiers.fused_backend = value != 0;
     else if (n == "fused_masks" && value >= 0 && value <= 7) hd->tiers.fused_masks = value;
     else if (n == "keep_planes") hd->keep_planes = value != 0;
@@ -1009,6 +1020,48 @@ int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int 
     launch_robust_polyfit(z, mask, order, iters, c, min_count, min_mask_count, coef, resid, B, h, w, (hipStream_t)stream, scratch);
     rc = hook_finish(scratch, nullptr, (hipStream_t)stream);
     return rc ? rc : inst;
+}
+
+// csrc/test_hooks_fit.h
+static int fit_window_hook(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef, float *resid,
+                           const FitSecond *second, int B, int h, int w, int variant, int32_t *need_out, void *stream)
+{
+    if (!z || !mask || !coef || !resid || (second && !second->resid_out) || B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull || order < 1 || order > 2 ||
+        (second && (second->order < 1 || second->order > 2)) || iters < 1)
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    void *scratch = nullptr;
+    int rc = hook_scratch(0, B, h, w, big_frames(B, h * w), &scratch);
+    if (rc) return rc;
+    const bool has_window = polyfit_window_variant(B, h, w, scratch != nullptr) >= 0;
+    if (variant == 1 && !has_window) { if (scratch) (void)hipFree(scratch); return fail(VISTAF_E_INVALID, "variant 1: no window instance for this frame size"); }
+    int32_t *need = nullptr;
+    if (hipMalloc((void **)&need, (size_t)B * sizeof(int32_t)) != hipSuccess) { if (scratch) (void)hipFree(scratch); return fail(VISTAF_E_HIP, "hipMalloc"); }
+    hipError_t e = hipMemsetAsync(need, 0xff, (size_t)B * sizeof(int32_t), (hipStream_t)stream);       // -1: no window kernel ran
+    const int inst = launch_robust_polyfit_window(z, mask, order, iters, c, min_count, min_mask_count, coef, resid, second, need, Tiers().fit_window != 0, variant,
+                                                  B, h, w, (hipStream_t)stream, scratch);
+    if (e == hipSuccess && need_out) e = hipMemcpyAsync(need_out, need, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, (hipStream_t)stream);
+    rc = hook_finish(scratch, need, (hipStream_t)stream);
+    if (!rc && e != hipSuccess) rc = fail(VISTAF_E_HIP, std::string("need: ") + hipGetErrorString(e));
+    return rc ? rc : inst;
+}
+int vistaf_ftp_test_polyfit_window(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,
+                                   float *resid, int B, int h, int w, int variant, int32_t *need_out, void *stream)
+{
+    return fit_window_hook(z, mask, order, iters, c, min_count, min_mask_count, coef, resid, nullptr, B, h, w, variant, need_out, stream);
+}
+int vistaf_ftp_test_polyfit_chain(const float *z, const uint8_t *mask, int order1, int order2, int iters, float c, int min_count, int min_mask_count1,
+                                  int min_mask_count2, float *coef, float *resid1, float *resid2, int B, int h, int w, int variant, int32_t *need_out, void *stream)
+{
+    const FitSecond second = {order2, min_mask_count2, resid2};
+    return fit_window_hook(z, mask, order1, iters, c, min_count, min_mask_count1, coef, resid1, &second, B, h, w, variant, need_out, stream);
+}
+int vistaf_ftp_test_polyfit_window_instance(int B, int h, int w)
+{
+    if (B < 1 || h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull) return fail(VISTAF_E_INVALID, "bad argument");
+    const bool big = large_frame((size_t)h * w);
+    const int plain = polyfit_variant(B, h, w, big), win = polyfit_window_variant(B, h, w, big);
+    return win >= 0 ? win : plain;
 }
 
 int vistaf_ftp_test_gauss_variant(const float *src, float *dst, double sigma, int B, int h, int w, int variant, void *stream)

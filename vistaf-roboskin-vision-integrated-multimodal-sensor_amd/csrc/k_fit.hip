@@ -263,10 +263,29 @@ __device__ inline double readlane_f64(double v, int l)
 // Medians are exact order statistics as before.  The residual plane is evaluated with eval_poly2d's own operation order (:1093-1097).
 // GT: row groups as a compile-time constant (0: the runtime value).  With a constant stride every yn read is one LDS read at an immediate
 // offset from a single base; with a runtime stride the RP row addresses of a pass are scalar values of their own (hundreds of SGPR spills).
-template <int RP, int NT, int GT>
+//
+// Two compile-time flags give the window kernel and the chained launches the same body (the plain kernels are the instances with both off, and
+// their code is what it was before the flags existed):
+// WIN    A thread keeps RP slots of its unit starting at its OWN first slot u0, not at slot 0: it reads the mask bytes of all
+//        need = ceil(h / groups) <= fit_plain_rp(RP) rows of its unit first (a 64-bit map per lane), takes u0 = first mask row and
+//        extent = last - first + 1 from the map, and the workgroup writes need_flag[b] = (any extent > RP).  A flagged frame returns with
+//        nothing else written (the retry kernel runs it); otherwise the thread's rows are grp + groups * (u0 + u), u < RP, which hold every
+//        mask pixel of the unit, in ascending order, in the same lane of the same wave as in the plain kernel: the same sums, the same keys.
+//        u0 is clamped to need - RP, so the window never leaves the unit and the yn table needs no more rows.
+// PASSES The fit runs ex.npass (1 or 2) times as a loop over a parameter list {order, min_mask_count, output plane}: pass 1 fits what pass 0 has
+//        stored, from the registers (the stored float where the mask is set, NaN elsewhere), under the same mask and window.
+struct FitChain {
+    int *need_flag;             // WIN: [B], written 0 / 1 for every frame.  !WIN && PASSES: read, frames with 0 return at once (null: none does)
+    int npass;                  // 1 or 2
+    int order2, min_mask_count2;
+    float *resid2_all;          // pass 1's output plane (pass 1's input is resid_all, pass 0's output)
+};
+constexpr int fit_plain_rp(int rp) { return rp == 16 ? 32 : rp == 32 ? 48 : rp == 48 ? 56 : 64; }      // the plain instance a window of rp slots stands in for
+template <int RP, int NT, int GT, bool WIN = false, bool PASSES = false>
 __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(const float *__restrict__ z_all, const uint8_t *__restrict__ mask_all, int order,
                                                               int iters, float c, int min_count, int min_mask_count, float *__restrict__ coef_out,
-                                                              float *__restrict__ resid_all, int h, int w, int cols_pad, int groups_rt)
+                                                              float *__restrict__ resid_all, int h, int w, int cols_pad, int groups_rt,
+                                                              const FitChain ex = FitChain())
 {
     // everything below that depends on the workgroup size takes it from NT (block reductions through 16-entry scratch arrays, NT / 64
     // partial sums, the selection's NT-strided loops): the launcher must start exactly NT threads and derive the row groups from NT
@@ -281,9 +300,12 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     __shared__ float s_yn[FIT_YTAB];
     const size_t b = blockIdx.x;
     const int P = h * w, tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int nc = order >= 2 ? 6 : 3;
+    int nc = order >= 2 ? 6 : 3;
     const float *z = z_all + b * (size_t)P;
     const uint8_t *m = mask_all + b * (size_t)P;
+    if constexpr (PASSES && !WIN) {
+        if (ex.need_flag && ex.need_flag[b] == 0) return;                         // the window kernel has done this frame
+    }
     const float cxf = fit_centre(w), cyf = fit_centre(h);
     for (int i = tid; i < FIT_YTAB; i += NT) s_yn[i] = fit_coord(i, cyf);       // rows >= h: only read for samples that are NaN
     const int col = tid % cols_pad, grp = __builtin_amdgcn_readfirstlane(tid / cols_pad);   // uniform inside a wave (cols_pad % 64 == 0)
@@ -294,7 +316,64 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     float zr[RP];
     uint32_t cntm = 0;
     SelRange rg;
-    {
+    // WIN / PASSES: the unit's mask as a bit per slot, the thread's first slot, its row and its 32-bit element offset in the frame (P < 2^31),
+    // the offset from one slot to the next, and the rows of a unit
+    unsigned long long mbits = 0;
+    int u0 = 0, y0 = grp;
+    const uint32_t gw = (uint32_t)(groups * w);
+    const int need = (h + groups - 1) / groups;
+    if constexpr (WIN) {
+        constexpr int RPF = fit_plain_rp(RP), MU = 16;
+        static_assert(RPF <= 64, "one bit per slot");
+        const uint32_t mo = (uint32_t)(grp * w + col);
+#pragma unroll
+        for (int a = 0; a < RPF; a += MU) {
+            uint8_t mk[MU];
+#pragma unroll
+            for (int v = 0; v < MU; v++) {
+                const int u = a + v;
+                if (u < RPF) mk[v] = (owner && grp + groups * u < h) ? m[mo + (uint32_t)u * gw] : (uint8_t)0;
+            }
+#pragma unroll
+            for (int v = 0; v < MU; v++) {
+                const int u = a + v;
+                if (u < RPF) mbits |= (unsigned long long)(mk[v] != 0) << u;
+            }
+        }
+        const int first = mbits ? __builtin_ctzll(mbits) : 0, last = mbits ? 63 - __builtin_clzll(mbits) : -1;
+        const int over = __syncthreads_or(last - first + 1 > RP);
+        if (tid == 0) ex.need_flag[b] = over ? 1 : 0;
+        if (over) return;
+        u0 = max(0, min(first, need - RP));
+        y0 = grp + groups * u0;
+        mbits >>= u0;                                                             // bit u: slot u of the window
+    }
+    const uint32_t o0 = (uint32_t)(y0 * w + col);
+    if constexpr (WIN || PASSES) {
+        constexpr int LU = 8;
+#pragma unroll
+        for (int a = 0; a < RP; a += LU) {
+            uint8_t mk[LU];
+#pragma unroll
+            for (int v = 0; v < LU; v++) {
+                const int u = a + v;
+                if (u < RP) {
+                    const bool in = owner && y0 + groups * u < h;
+                    zr[u] = in ? z[o0 + (uint32_t)u * gw] : qnan;
+                    if constexpr (!WIN) mk[v] = in ? m[o0 + (uint32_t)u * gw] : (uint8_t)0;
+                }
+            }
+            if constexpr (!WIN) {
+#pragma unroll
+                for (int v = 0; v < LU; v++) {
+                    const int u = a + v;
+                    if (u < RP) mbits |= (unsigned long long)(mk[v] != 0) << u;
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RP; u++) zr[u] = (mbits >> u & 1) ? zr[u] : qnan;   // the fitted-pixel test itself is the pass loop's
+    } else {
         constexpr int LU = 8;
         uint8_t mk[LU];
 #pragma unroll
@@ -322,6 +401,28 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
             }
         }
     }
+    // the fits of this launch: one, or with PASSES ex.npass of them over {order, min_mask_count, zsrc -> out}
+    const int npass = PASSES ? ex.npass : 1;
+    const float *zsrc = z;                       // what the residual phase reads for the pixels that are not fitted
+    float *out = nullptr;
+#pragma unroll 1
+    for (int pass = 0;; pass++) {
+    if constexpr (PASSES) {
+        if (pass) { order = ex.order2; nc = order >= 2 ? 6 : 3; min_mask_count = ex.min_mask_count2; zsrc = out; out = ex.resid2_all + b * (size_t)P; }
+        else out = resid_all + b * (size_t)P;
+        // count, range and finiteness from the registers: the first pass's loaded samples, or what the pass before has stored
+        cntm = (uint32_t)__builtin_popcountll(mbits);
+        rg = SelRange();
+        // (below, mb / oo / gg: opaque copies per pass -- as invariants of the pass loop the RP mask tests and element offsets would be
+        // hoisted out of it and kept live next to the samples, like the row coordinates of `each`)
+#pragma unroll
+        for (int u = 0; u < RP; u++) {
+            const float zz = zr[u];
+            const bool ok = finitef(zz);
+            zr[u] = ok ? zz : qnan;
+            if (ok) rg.add(f2key(zz));
+        }
+    }
     __syncthreads();
     uint32_t n, zkmin, zkmax;
     rg.reduce(sh.wsum, sh.red64, n, zkmin, zkmax, min_mask_count > 0, cntm);
@@ -342,8 +443,9 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         return __fsub_rn(zz, fit_col_eval(At, Bt, coef[5], yn));
     };
     auto each = [&](auto body) {
-        int g0 = grp;
-        asm volatile("" : "+s"(g0));
+        int g0 = y0;
+        if constexpr (WIN) asm volatile("" : "+v"(g0));      // a lane's own first row
+        else asm volatile("" : "+s"(g0));
 #pragma unroll
         for (int u = 0; u < RP; u++) {
             // the test is on the RESIDUAL (NaN for a sample that is not fitted), not on the sample: "is zr[u] finite" is invariant across
@@ -367,8 +469,9 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         // ---- column sums P_b = sum w^2 yn^b (b = 0..DEG), Q_b = sum w^2 z yn^b (b = 0..DEG / 2), float64
         double Pb[5] = {0.0, 0.0, 0.0, 0.0, 0.0}, Qb[3] = {0.0, 0.0, 0.0};
         const float inv_csig = __fdiv_rn(1.0f, csig);
-        int g0 = grp;
-        asm volatile("" : "+s"(g0));
+        int g0 = y0;
+        if constexpr (WIN) asm volatile("" : "+v"(g0));      // a lane's own first row
+        else asm volatile("" : "+s"(g0));
 #pragma unroll
         for (int u = 0; u < RP; u++) {
             const float zz = zr[u];
@@ -455,7 +558,50 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     }
     if (tid < 6) coef_out[b * 6 + tid] = do_fit ? coef[tid] : 0.f;
     // residual plane: z - fit over the WHOLE plane, unfitted pixels included (fit evaluated as eval_poly2d does, :1093-1097, :1132-1135)
-    float *out = resid_all + b * (size_t)P;
+    if constexpr (!PASSES) out = resid_all + b * (size_t)P;
+    if constexpr (WIN || PASSES) {
+        if (owner) {
+            // as below, through the 32-bit offsets; a chained launch keeps what it stores where the mask is set: the next pass's samples
+            unsigned long long mb = mbits;
+            uint32_t oo = o0, gg = gw;
+            int yy = y0;
+            asm volatile("" : "+v"(mb), "+v"(oo), "+s"(gg), "+v"(yy));
+#pragma unroll
+            for (int u = 0; u < RP; u++) {
+                if (yy + groups * u < h && !finitef(zr[u])) zr[u] = zsrc[oo + (uint32_t)u * gg];
+            }
+#pragma unroll
+            for (int u = 0; u < RP; u++) {
+                const int y = yy + groups * u;
+                if (y < h) {
+                    const float fit = do_fit ? fit_eval(coef, order, xn, s_yn[y]) : 0.f;
+                    const float o = __fsub_rn(zr[u], fit);
+                    out[oo + (uint32_t)u * gg] = o;
+                    if constexpr (PASSES) zr[u] = (mb >> u & 1) ? o : qnan;
+                }
+            }
+            if constexpr (WIN) {
+                // the need - RP rows of the unit outside the window: slots (u0 + RP + j) mod need, none of them under the mask
+                constexpr int NO = fit_plain_rp(RP) - RP;
+                float zo[NO];
+                int yo[NO];
+#pragma unroll
+                for (int j = 0; j < NO; j++) {
+                    int s = u0 + RP + j;
+                    if (s >= need) s -= need;
+                    yo[j] = (j < need - RP && grp + groups * s < h) ? grp + groups * s : -1;
+                    zo[j] = yo[j] >= 0 ? zsrc[(uint32_t)(yo[j] * w + col)] : 0.f;
+                }
+#pragma unroll
+                for (int j = 0; j < NO; j++) {
+                    if (yo[j] >= 0) {
+                        const float fit = do_fit ? fit_eval(coef, order, xn, s_yn[yo[j]]) : 0.f;
+                        out[(uint32_t)(yo[j] * w + col)] = __fsub_rn(zo[j], fit);
+                    }
+                }
+            }
+        }
+    } else {
     if (owner) {
         // fitted pixels still sit in the registers; the others (masked out or NaN upstream) are read again -- all of those loads first, in
         // batches of independent requests (one dependent load per row made this loop a tenth of the kernel), then arithmetic and stores
@@ -473,7 +619,11 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
             }
         }
     }
+    }
     SEL_STAMP(9);
+    if constexpr (!PASSES) break;
+    else if (pass + 1 >= npass) break;
+    }       // pass
 }
 
 #ifdef VISTAF_DEBUG
@@ -491,6 +641,16 @@ void fit_debug_dump()
 #define VF_FIT_PASS z_all, mask_all, order, iters, c, min_count, min_mask_count, coef_out, resid_all, h, w, cols_pad, groups
 template <int RP, int GT>
 __global__ __launch_bounds__(SEL_T) void k_robust_polyfit_col(VF_FIT_ARGS) { robust_polyfit_col_body<RP, SEL_T, GT>(VF_FIT_PASS); }
+// The window kernel (see robust_polyfit_col_body: WIN, PASSES) and the kernel behind it: the chained body at the plain RP for the frames the
+// window kernel has flagged in need_flag (every frame when need_flag is null).  npass = 1: one fit, the second parameter set is not read.
+#define VF_FIT_CHAIN_ARGS int order2, int min_mask_count2, float *resid2_all, int npass, int *need_flag
+#define VF_FIT_CHAIN_PASS FitChain{need_flag, npass, order2, min_mask_count2, resid2_all}
+template <int RP, int GT>
+__global__ __launch_bounds__(SEL_T) void k_robust_polyfit_colwin(VF_FIT_ARGS, VF_FIT_CHAIN_ARGS) { robust_polyfit_col_body<RP, SEL_T, GT, true, true>(VF_FIT_PASS, VF_FIT_CHAIN_PASS); }
+template <int RP, int GT>
+__global__ __launch_bounds__(SEL_T) void k_robust_polyfit_col_retry(VF_FIT_ARGS, VF_FIT_CHAIN_ARGS) { robust_polyfit_col_body<RP, SEL_T, GT, false, true>(VF_FIT_PASS, VF_FIT_CHAIN_PASS); }
+#undef VF_FIT_CHAIN_ARGS
+#undef VF_FIT_CHAIN_PASS
 #undef VF_FIT_ARGS
 #undef VF_FIT_PASS
 
@@ -543,6 +703,74 @@ void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int i
         break;
     }
 #undef VF_FIT_COL
+}
+
+// The window instance of a plain column variant: the ladder step below it with the same GT, or -1 (the smallest step, the generic and the
+// big variants have none).  A frame takes it when no thread's mask rows span more slots than the instance keeps.
+int polyfit_window_of(int plain_variant)
+{
+    switch (plain_variant) {
+    case FITV_COL32: return FITV_WIN16;
+    case FITV_COL48: return FITV_WIN32;
+    case FITV_COL56: return FITV_WIN48;
+    case FITV_COL64: return FITV_WIN56;
+    case FITV_COL48_G4: return FITV_WIN32_G4;
+    case FITV_COL56_G4: return FITV_WIN48_G4;
+    case FITV_COL64_G4: return FITV_WIN56_G4;
+    default: return -1;
+    }
+}
+int polyfit_window_variant(int B, int h, int w, bool big) { return polyfit_window_of(polyfit_variant(B, h, w, big)); }
+
+namespace {
+using FitChainKernel = void (*)(const float *, const uint8_t *, int, int, float, int, int, float *, float *, int, int, int, int, int, int, float *, int, int *);
+struct FitWindowKernels { FitChainKernel win, retry; int gt; };     // retry: the chained body at the plain variant's RP
+FitWindowKernels fit_window_kernels(int plain_variant)
+{
+    switch (plain_variant) {
+    case FITV_COL16: return {nullptr, k_robust_polyfit_col_retry<16, 0>, 0};
+    case FITV_COL32: return {k_robust_polyfit_colwin<16, 0>, k_robust_polyfit_col_retry<32, 0>, 0};
+    case FITV_COL48: return {k_robust_polyfit_colwin<32, 0>, k_robust_polyfit_col_retry<48, 0>, 0};
+    case FITV_COL56: return {k_robust_polyfit_colwin<48, 0>, k_robust_polyfit_col_retry<56, 0>, 0};
+    case FITV_COL64: return {k_robust_polyfit_colwin<56, 0>, k_robust_polyfit_col_retry<64, 0>, 0};
+    case FITV_COL48_G4: return {k_robust_polyfit_colwin<32, 4>, k_robust_polyfit_col_retry<48, 4>, 4};
+    case FITV_COL56_G4: return {k_robust_polyfit_colwin<48, 4>, k_robust_polyfit_col_retry<56, 4>, 4};
+    case FITV_COL64_G4: return {k_robust_polyfit_colwin<56, 4>, k_robust_polyfit_col_retry<64, 4>, 4};
+    default: return {nullptr, nullptr, 0};
+    }
+}
+}  // namespace
+
+// One fit, or with `second` two chained ones (the second fits the first's output plane under the same mask), through the window kernel.
+// window: Tiers::fit_window.  force: 0 the dispatch -- with `window` and a column variant the window kernel, then the kernel behind it for the
+// frames flagged in need_flag ([B] ints; a column variant without a window instance runs the chained body alone); otherwise the plain launches,
+// two of them for a chain -- FIT_WINDOW_ONLY the window kernel alone (the caller has checked polyfit_window_variant), FIT_PLAIN the plain
+// launches.  Returns the FitVariant of the first kernel launched.
+int launch_robust_polyfit_window(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
+                                 float *resid_out, const FitSecond *second, int *need_flag, bool window, int force, int B, int h, int w, hipStream_t st,
+                                 void *big_scratch)
+{
+    int cols_pad = 0, groups = 0;
+    const int variant = polyfit_variant(B, h, w, big_scratch != nullptr, &cols_pad, &groups);
+    const FitWindowKernels k = fit_window_kernels(variant);
+    if (force == FIT_PLAIN || (force == 0 && (!window || !k.retry))) {
+        launch_robust_polyfit(z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, B, h, w, st, big_scratch);
+        if (second) launch_robust_polyfit(resid_out, mask, second->order, iters, c, min_count, second->min_mask_count, coef_out, second->resid_out, B, h, w, st, big_scratch);
+        return variant;
+    }
+    const int gr = k.gt ? k.gt : groups;
+    const int order2 = second ? second->order : order, mmc2 = second ? second->min_mask_count : 0, npass = second ? 2 : 1;
+    float *resid2 = second ? second->resid_out : nullptr;
+#define VF_FIT_CHAIN(KERNEL, NEED) hipLaunchKernelGGL(KERNEL, dim3(B), dim3(SEL_T), 0, st, z, mask, order, iters, c, min_count, min_mask_count, coef_out, resid_out, h, w, cols_pad, gr, \
+                                                      order2, mmc2, resid2, npass, NEED)
+    if (!k.win) {                                                // the smallest ladder step: no window, the chained body for every frame
+        VF_FIT_CHAIN(k.retry, (int *)nullptr);
+        return variant;
+    }
+    VF_FIT_CHAIN(k.win, need_flag);
+    if (force != FIT_WINDOW_ONLY) VF_FIT_CHAIN(k.retry, need_flag);
+#undef VF_FIT_CHAIN
+    return polyfit_window_of(variant);
 }
 
 }  // namespace vf

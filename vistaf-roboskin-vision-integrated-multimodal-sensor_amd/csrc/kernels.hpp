@@ -28,6 +28,7 @@ struct Tiers {
     int dft_staged = 1;         // 1: the demodulation stages dft_staged_fits names take their operands from LDS (k_dft.hip: k_dft_fwd1_staged, k_dft_inv2_staged); 0: every stage reads global memory / L2 per k-step
     int fused_chains = 1;       // 1: the element-wise passes around a short Gaussian (<= 15 taps) run inside the blur's tile (k_blurchain.hip); 0: one streaming kernel each
     int gauss_strip = 1;        // 1: a session's long Gaussians (> 15 taps) on frames gauss_strip_fits takes run both passes in one launch, the intermediate in LDS (k_gauss_strip); 0: the row and the column kernel
+    int fit_window = 1;         // 1: where a column variant has a window instance, the ramp removal and the first detrend fit share one launch of the window kernel one ladder step down (k_robust_polyfit_colwin), the chained plain-size body behind it for the frames it flags; 0: one plain kernel per fit
 };
 
 // Frames of 512 x 512 pixels and more: the ones whose per-frame stages are split over the chip (k_big.hip and the chunked tiers)
@@ -248,8 +249,16 @@ void launch_robust_polyfit(const float *z, const uint8_t *mask, int order, int i
 // the kernel launch_robust_polyfit starts for (B, h, w); big: scratch for the k_big.hip chain is at hand.  FITV_COL<RP>[_G4]: k_robust_polyfit_col<RP, 0 | 4>,
 // FITV_GENERIC / FITV_GENERIC_DIV: k_robust_polyfit with the multiply-high row index / with a plain division (h * w * w >= 2^32)
 enum FitVariant { FITV_BIG = 0, FITV_GENERIC, FITV_GENERIC_DIV, FITV_COL16, FITV_COL32, FITV_COL48, FITV_COL56, FITV_COL64, FITV_COL48_G4, FITV_COL56_G4,
-                  FITV_COL64_G4, FITV_COUNT };
+                  FITV_COL64_G4, FITV_WIN16, FITV_WIN32, FITV_WIN48, FITV_WIN56, FITV_WIN32_G4, FITV_WIN48_G4, FITV_WIN56_G4, FITV_COUNT };
 int polyfit_variant(int B, int h, int w, bool big, int *cols_pad_out = nullptr, int *groups_out = nullptr);   // the column kernels' launch geometry, if asked
+// FITV_WIN<RP>[_G4]: k_robust_polyfit_colwin<RP, 0 | 4>, the window kernel that stands in for the plain column variant one ladder step up (64 -> 56,
+// 56 -> 48, 48 -> 32, 32 -> 16, same GT) on frames whose mask rows span at most RP slots in every thread; -1: the variant has none
+int polyfit_window_variant(int B, int h, int w, bool big);
+struct FitSecond { int order, min_mask_count; float *resid_out; };      // the second fit of a chained launch: it fits the first fit's output plane
+enum FitForce { FIT_WINDOW_ONLY = 1, FIT_PLAIN = 2 };
+int launch_robust_polyfit_window(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef_out,
+                                 float *resid_out, const FitSecond *second, int *need_flag, bool window, int force, int B, int h, int w, hipStream_t st,
+                                 void *big_scratch);
 
 // ---- k_holes.hip (hole stage, shape_ftp.py:1153-1204, :1770-1801; live only when reliable_smooth_sigma_px == 0) ----------------------
 void launch_zeroed_keep_nan(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, int B, int P, hipStream_t st);

@@ -55,6 +55,12 @@ extern "C" {
  *       "gauss_strip"  1 (default) a Gaussian of more than 15 taps on frames gauss_strip_fits (kernels.hpp) takes -- up to 97 taps, the strip's LDS need
  *                      within 48 KB -- runs both passes in one launch, a workgroup per frame and strip of 32 columns with the intermediate plane in
  *                      LDS (k_gauss_strip); 0, or a blur it does not take: the row and the column kernel.  Same bits either way
+ *       "fit_window"   1 (default) on frame sizes with a window instance (polyfit_window_variant of kernels.hpp: the column kernels of 32 rows per
+ *                      thread and more) the ramp removal and the first detrend fit, which fits its output under the same mask, share one launch
+ *                      of the window kernel one ladder step down (k_robust_polyfit_colwin: a thread's slots start at its own first mask row, the
+ *                      second fit takes its samples from the registers), followed by the chained plain-size kernel for the frames whose mask
+ *                      rows did not fit ("fit_need" of vistaf_ftp_get_intermediate: 1 per such frame); 0, or plane_order_for_removal = 0: one
+ *                      plain kernel per fit.  The third fit always runs the plain kernel.  Same bits either way.  test_hooks_fit.h has the direct hooks
  *       "keep_planes"   1 also writes the float64 demodulated field of every frame ("field" of vistaf_ftp_get_intermediate) */
 int vistaf_ftp_test_set(vistaf_ftp_handle *hd, const char *name, int value);
 
@@ -92,6 +98,8 @@ int vistaf_ftp_test_select_chained(const float *vals, const uint8_t *mask, size_
  * 3..7 column kernels of 16, 32, 48, 56, 64 rows per thread, 8..10 the four-group kernels of 48, 56, 64 rows) or a negative error. */
 int vistaf_ftp_test_polyfit(const float *z, const uint8_t *mask, int order, int iters, float c, int min_count, int min_mask_count, float *coef,
                             float *resid, int B, int h, int w, int variant, void *stream);
+
+/* (test_hooks_fit.h: the same with the window kernel and as a chained pair of fits) */
 
 /* launch_gauss_blur (src != dst) with the taps a session builds for `sigma`, dispatched as a session does: up to 15 taps the one-kernel LDS
  * tile, beyond that the strip kernel where gauss_strip_fits (kernels.hpp) takes the blur, else the row and the column kernel. */

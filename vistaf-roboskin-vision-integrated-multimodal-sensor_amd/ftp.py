@@ -657,7 +657,7 @@ class FtpSensor(Handle):
     def _test_set(self, name: str, value: int):
         """Test hook (csrc/test_hooks.h, not part of the boundary): select a fallback / opt-in kernel tier of a stage
         ("inpaint_tier", "big_flood_handback", "chamfer_twopass", "telea_two_tier", "telea_mw", "unwrap_fast", "big_chain", "big_queue_lds",
-        "big_gq_cap", "big_fallback", "fused_chains", "fused_backend", "fused_masks", "select_resident", "dft_staged", "gauss_strip") or keep debug planes ("keep_planes")."""
+        "big_gq_cap", "big_fallback", "fused_chains", "fused_backend", "fused_masks", "select_resident", "dft_staged", "gauss_strip", "fit_window") or keep debug planes ("keep_planes")."""
         self._call("vistaf_ftp_test_set", self._h, name.encode(), int(value), on_device=False)
 
     def masks(self, index: int = 0) -> Dict[str, np.ndarray]:
