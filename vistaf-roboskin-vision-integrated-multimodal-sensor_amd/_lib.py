@@ -93,6 +93,12 @@ CENTRELINE_NAMES = ["pixels", "skeleton_pixels", "thinning_passes", "end_pixels"
                     "depth_peak_mm", "depth_peak_station"]
 # VISTAF_CLST_*: values (ok, no_pixels, point) and flags (branched, truncated) of the `status` field
 CENTRELINE_STATUS = {"ok": 0, "no_pixels": 1, "point": 2, "branched": 8, "truncated": 16}
+NLOBE, NLOBEROW, LOBES_MAX = 16, 12, 64                              # VISTAF_NLOBE, VISTAF_NLOBEROW, VISTAF_LOBES_MAX (include_ext/vistaf_lobes.h)
+# fields of a lobe record in the order of the VISTAF_LOBE_* indices, and of a row record (VISTAF_LOBEROW_*; 9..11 are reserved)
+LOBE_NAMES = ["x", "y", "depth_mm", "prominence_mm", "saddle_x", "saddle_y", "saddle_depth_mm", "neighbour", "pixels", "contact_pixels", "area_mm2",
+              "volume_cm3", "centroid_x", "centroid_y", "force_share_N", "basins"]
+LOBE_ROW_NAMES = ["pixels", "raw_maxima", "peaks", "peaks_written", "status", "threshold_mm", "separation_mm", "deepest_saddle_mm", "next_prominence_mm"]
+LOBE_STATUS = {"ok": 0, "no_pixels": 1, "truncated": 16}              # VISTAF_LOBEST_*: values (ok, no_pixels) and flag (truncated) of `status`
 ALIGN_NINFO = 12        # doubles per frame record of vistaf_align_batch (VISTAF_ALIGN_NINFO, include/vistaf_align.h)
 
 FMT_GRAY_U8, FMT_BGR_U8, FMT_GRAY_F16, FMT_BGR_F16 = 0, 1, 2, 3
@@ -340,6 +346,15 @@ CENTRELINE_SIGNATURES = {
 CENTRELINE_TEST_SIGNATURES = {
     "vistaf_ftp_test_centreline_tier": (ci, [ci, ci]),
 }
+# include_ext/vistaf_lobes.h: the lobe read-out, two plain functions, the same pattern (tests/test_lobes.py holds it against that header), and
+# csrc/test_hooks_lobes.h: which storage tier a box takes
+LOBES_SIGNATURES = {
+    "vistaf_lobes_workspace_bytes": (ci, [ci, ci, ci, ci, P(sz)]),
+    "vistaf_lobes_measure": (ci, [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, cd, cd, cd, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]),
+}
+LOBES_TEST_SIGNATURES = {
+    "vistaf_ftp_test_lobes_tier": (ci, [ci, ci]),
+}
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -360,7 +375,7 @@ def load():
     lib = ctypes.CDLL(LIB_PATH)
     for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, FIT_WINDOW_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES,
                                                  MATCH_SIGNATURES,
-                                                 CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES]:
+                                                 CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES, LOBES_SIGNATURES, LOBES_TEST_SIGNATURES]:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -329,6 +329,7 @@ class FtpSensor(Handle):
     _textures = property(lambda self: self._live("textures"))
     _matches = property(lambda self: self._live("matches"))
     _centrelines = property(lambda self: self._live("centrelines"))
+    _lobes = property(lambda self: self._live("lobes"))
 
     def _last(self, who: str, what: str = "predict_batch / predict_pairs") -> Dict[str, torch.Tensor]:
         last = getattr(self, "_last_out", None)
@@ -524,6 +525,30 @@ class FtpSensor(Handle):
                                        max_stations=max_stations, workspace=ws, **params))
         return out
 
+    def lobes(self, max_contacts: int = 8, max_lobes: int = 4, min_prominence_mm: Optional[float] = None,
+              min_prominence_frac: Optional[float] = None, split: bool = True) -> Dict[str, torch.Tensor]:
+        """Per-contact table of the last predict plus the lobes every contact splits into at the saddles of its depth relief
+        (lobes.contact_lobes; an extension, the reference has no counterpart): two fingertips whose footprints joined are one row of the
+        contacts table and two lobes here.  Calls `contacts(max_contacts, index_plane=True)` and hands it, the predict's height map, the
+        frames' mm_per_px (the `scalars` column) and the session's depth_eps_mm to the lobe read-out; its workspace is the session's, made
+        on first use and again when max_contacts changes.  min_prominence_mm / min_prominence_frac: None takes the defaults of `lobes`
+        (0.02 mm and 0.10 of the contact's greatest depth: a judgement about noise nobody has measured on this sensor).  Returns the
+        contacts dict plus lobes [B,K,max_lobes,16] f64 (fields LOBE_NAMES), lobe_rows [B,K,12] f64 (fields LOBE_ROW_NAMES), lobe_index
+        [B,h,w] i8 and, with split, split_contacts [B,K,16] f64, split_count [B] i32, split_index [B,h,w] i8 -- the lobes as a contacts
+        table the tracker and the other read-outs take unchanged; its force_N is each lobe's share of its parent's force -- and
+        split_parent [B,K,2] i32."""
+        from .lobes import DEFAULT_MIN_PROMINENCE_FRAC, DEFAULT_MIN_PROMINENCE_MM, LobesWorkspace, contact_lobes
+        k = int(max_contacts)
+        ws = self._matching("lobes", (k,))
+        out = self.contacts(k, index_plane=True)
+        if ws is None:
+            ws = self._keep("lobes", (k,), LobesWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out.update(contact_lobes(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), self._last_out["height_map_mm"],
+                                 max_lobes=max_lobes, min_prominence_mm=DEFAULT_MIN_PROMINENCE_MM if min_prominence_mm is None else min_prominence_mm,
+                                 min_prominence_frac=DEFAULT_MIN_PROMINENCE_FRAC if min_prominence_frac is None else min_prominence_frac,
+                                 depth_eps_mm=self.config.depth_eps_mm, split=split, workspace=ws))
+        return out
+
     def taxels(self, layout) -> Dict[str, torch.Tensor]:
         """Taxel read-out of the last predict (taxels.TaxelReadout; an extension, the reference has no counterpart): the height map reduced to
         the fixed cells of `layout` (taxels.grid_layout, polar_layout, from_map) and to the frame's wrench.  Hands the predict's height map,
@@ -695,7 +720,7 @@ class FtpSensor(Handle):
                 temporal: Optional[Dict[str, Any]] = None, cloud: Optional[Dict[str, Any]] = None,
                 motion: Optional[Dict[str, Any]] = None, pressure: Optional[Dict[str, Any]] = None, format=None,
                 outlines: bool = False, textures: Optional[Dict[str, Any]] = None,
-                matches: Optional[Dict[str, Any]] = None, centrelines=False) -> Optional[Dict[str, Any]]:
+                matches: Optional[Dict[str, Any]] = None, centrelines=False, lobes=False) -> Optional[Dict[str, Any]]:
         """One deformed frame -> the dict shape_ftp.main(..., return_results=True) returns
         (Code/shape_ftp.py:2029-2037) plus the force tail of multimodal_sensor.py:388-419.
         Returns None when the reliable mask is empty, as upstream does (shape_ftp.py:1677-1679).
@@ -727,7 +752,14 @@ class FtpSensor(Handle):
         `max_contacts`) adds "matches", one dict of MATCH_NAMES per entry of "contacts".
         centrelines=True or dict(...) (with contacts=K; the keyword arguments of `FtpSensor.centrelines` but `max_contacts` and `skeleton`)
         adds "centrelines", one dict of CENTRELINE_NAMES per entry of "contacts", "centreline_stations", per entry the [n,2] list of its axis
-        path from A to B (None for a row that did not fit the capacity), and "centreline_d2", per entry the squared half-widths along it."""
+        path from A to B (None for a row that did not fit the capacity), and "centreline_d2", per entry the squared half-widths along it.
+        lobes=True or dict(...) (with contacts=K; the keyword arguments of `FtpSensor.lobes` but `max_contacts` and `split`) adds "lobes",
+        per entry of "contacts" the list of its written lobes as dicts of LOBE_NAMES, "lobe_rows", one dict of LOBE_ROW_NAMES per entry, and
+        "split_contacts", the lobes of the frame as a contacts list of their own (dicts of CONTACT_NAMES plus `parent`, the (row, lobe) each
+        came from; `force_N` is the lobe's share of its parent's force)."""
+        want_lobes = lobes is not None and lobes is not False
+        if want_lobes and contacts is None:
+            raise ValueError("lobes=True needs contacts=K")
         want_centrelines = centrelines is not None and centrelines is not False
         if want_centrelines and contacts is None:
             raise ValueError("centrelines=True needs contacts=K")
@@ -829,6 +861,12 @@ class FtpSensor(Handle):
                     res["centreline_stations"], res["centreline_d2"] = rec["stations"], rec["d2"]
                 else:                                           # max_stations=0: no polylines were asked for
                     res["centreline_stations"], res["centreline_d2"] = [None] * len(res["centrelines"]), [None] * len(res["centrelines"])
+            if want_lobes:
+                from .writers import lobe_frame_record
+                lb = self.lobes(int(contacts), split=True, **({} if lobes is True else dict(lobes)))
+                rec = lobe_frame_record(lb["lobes"][0].cpu().numpy(), lb["lobe_rows"][0].cpu().numpy(), int(lb["count"][0].item()),
+                                        lb["split_contacts"][0].cpu().numpy(), int(lb["split_count"][0].item()), lb["split_parent"][0].cpu().numpy())
+                res["lobes"], res["lobe_rows"], res["split_contacts"] = rec["lobes"], rec["lobe_rows"], rec["split_contacts"]
         if pressure is not None:
             from .writers import pressure_frame_record, pressure_table
             running = self._pressure                            # without contacts=K the table's size is nobody's concern: keep the running one

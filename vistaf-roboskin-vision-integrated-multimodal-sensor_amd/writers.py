@@ -88,6 +88,13 @@ CENTRELINE_INT_FIELDS = ("pixels", "skeleton_pixels", "thinning_passes", "end_pi
                          "a_x", "a_y", "b_x", "b_y", "sagitta_station", "interior_stations", "width_min_station", "width_max_station",
                          "a_at_border", "b_at_border", "depth_peak_station")             # -1 for NaN: what a row without pixels, or without depth, leaves out
 CENTRELINES_CSV_FIELDS = ("frame", "contact") + CENTRELINE_FIELDS
+LOBE_FIELDS = ("x", "y", "depth_mm", "prominence_mm", "saddle_x", "saddle_y", "saddle_depth_mm", "neighbour", "pixels", "contact_pixels", "area_mm2",
+               "volume_cm3", "centroid_x", "centroid_y", "force_share_N", "basins")       # VISTAF_LOBE_* order (include_ext/vistaf_lobes.h)
+LOBE_INT_FIELDS = ("x", "y", "saddle_x", "saddle_y", "neighbour", "pixels", "contact_pixels", "basins")   # -1 for NaN: a peak without a saddle
+LOBE_ROW_FIELDS = ("pixels", "raw_maxima", "peaks", "peaks_written", "status", "threshold_mm", "separation_mm", "deepest_saddle_mm",
+                   "next_prominence_mm")                                                 # VISTAF_LOBEROW_* order
+LOBE_ROW_INT_FIELDS = ("pixels", "raw_maxima", "peaks", "peaks_written", "status")
+LOBES_CSV_FIELDS = ("frame", "contact", "lobe") + LOBE_FIELDS
 TAXEL_FIELDS = ("contact_pixels", "contact_area_mm2", "volume_cm3", "mean_depth_mm", "max_depth_mm", "argmax_index", "centroid_x", "centroid_y",
                 "force_N", "pressure_kPa")                                                # VISTAF_TAXEL_* order (include/vistaf_taxel.h)
 TAXEL_INT_FIELDS = ("contact_pixels", "argmax_index")                                     # argmax_index is -1 for a taxel without contact
@@ -394,6 +401,61 @@ def centreline_frame_record(centrelines, stations, station_d2, offsets, count) -
             if isinstance(val, float) and not math.isfinite(val):
                 r[name] = None
     return {"contact_count": int(count), "centrelines": rows, "stations": lines, "d2": widths}
+
+
+def lobes_table(lobes, lobe_rows, count) -> list:
+    """Row dicts of the lobe read-out: lobes [B,K,L,>=16] and lobe_rows [B,K,>=9] (or [K,L,..] and [K,..] for one frame) float64 as
+    `FtpSensor.lobes` returns them, count [B].  One dict per written lobe (the first peaks_written records of every row in use), frames,
+    contacts and lobes in order: `frame`, `contact`, `lobe` and LOBE_FIELDS, the pixels, counts and the neighbour as ints (-1 where the
+    header leaves the field NaN)."""
+    t, r = np.asarray(lobes, dtype=np.float64), np.asarray(lobe_rows, dtype=np.float64)
+    n = np.atleast_1d(np.asarray(count)).astype(np.int64)
+    if t.ndim == 3 and r.ndim == 2:
+        t, r = t[None], r[None]
+    if t.ndim != 4 or r.ndim != 3 or t.shape[:2] != r.shape[:2] or t.shape[3] < len(LOBE_FIELDS) or r.shape[2] < len(LOBE_ROW_FIELDS) or t.shape[0] != n.shape[0]:
+        raise ValueError("lobes must be [B,K,L,>=16] with lobe_rows [B,K,>=9] and count [B]")
+    out = []
+    for b in range(t.shape[0]):
+        for k in range(min(max(int(n[b]), 0), t.shape[1])):
+            for j in range(min(_int_or_minus_one(r[b, k, LOBE_ROW_FIELDS.index("peaks_written")]), t.shape[2])):
+                row: Dict[str, Any] = {"frame": b, "contact": k, "lobe": j}
+                for i, name in enumerate(LOBE_FIELDS):
+                    row[name] = _int_or_minus_one(t[b, k, j, i]) if name in LOBE_INT_FIELDS else float(t[b, k, j, i])
+                out.append(row)
+    return out
+
+
+def write_lobes_csv(output_dir: str, lobes, lobe_rows, count, filename: str = "lobes.csv") -> str:
+    """lobes.csv: one line per written lobe, columns LOBES_CSV_FIELDS, floats with repr() (they read back to the same doubles)."""
+    return _write_csv(output_dir, filename, LOBES_CSV_FIELDS, lobes_table(lobes, lobe_rows, count))
+
+
+def lobe_frame_record(lobes, lobe_rows, count, split_contacts=None, split_count=None, split_parent=None) -> Dict[str, Any]:
+    """One frame's lobes for a JSON document of the caller's own: lobes [K,L,>=16], lobe_rows [K,>=9], count (a scalar) and, if given, the
+    split table [K,>=13] with its count and parents [K,2].  {"contact_count", "lobes": per row in use the list of its written lobes as dicts
+    of LOBE_FIELDS, "lobe_rows": per row in use a dict of LOBE_ROW_FIELDS} and, with the split table, "split_count" and "split_contacts":
+    the row dicts of `contacts_table` without `frame`, each with `parent` = [row, lobe].  NaN becomes null."""
+    t, r = np.asarray(lobes, dtype=np.float64), np.asarray(lobe_rows, dtype=np.float64)
+    if t.ndim != 3 or r.ndim != 2:
+        raise ValueError("lobes must be [K,L,>=16] with lobe_rows [K,>=9]")
+
+    def clean(d):
+        return {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in d.items()}
+    used = min(max(int(count), 0), t.shape[0])
+    per_row = [[] for _ in range(used)]
+    for row in lobes_table(t, r, np.asarray([count])):
+        row.pop("frame")
+        per_row[row.pop("contact")].append(clean(row))
+    rec: Dict[str, Any] = {"contact_count": int(count), "lobes": per_row,
+                           "lobe_rows": [clean(_frame_record(r[k], LOBE_ROW_FIELDS, LOBE_ROW_INT_FIELDS)) for k in range(used)]}
+    if split_contacts is not None:
+        par = np.asarray(split_parent)
+        rows = contacts_table(np.asarray(split_contacts, dtype=np.float64), np.asarray([split_count]))
+        for row in rows:
+            row.pop("frame")
+            row["parent"] = [int(v) for v in par[row["contact"]]]
+        rec["split_count"], rec["split_contacts"] = int(split_count), [clean(row) for row in rows]
+    return rec
 
 
 def match_frame_record(matches, count, scores=None) -> Dict[str, Any]:
