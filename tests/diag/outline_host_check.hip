@@ -1,6 +1,7 @@
 // Stand-alone host check of the contact outline read-out's C ABI (include_ext/vistaf_outline.h): the argument checking of both functions and
-// the workspace layout, for a run under the host sanitizers.  It includes the translation unit itself, so outline_scratch is the one the library
-// carves with; every call here is refused before a launch, nothing needs a device.  Build and run (no GPU needed):
+// the workspace layout, for a run under the host sanitizers, and the capacity rule of the polylines (row_capacity, contact_rows.hpp: the one
+// k_outline_poly and k_centreline_poly apply) against a direct restatement.  It includes the translation unit itself, so outline_scratch is the
+// one the library carves with; every call here is refused before a launch, nothing needs a device.  Build and run (no GPU needed):
 //   hipcc --offload-arch=gfx950 -std=c++17 -ffp-contract=off -Xarch_host -fsanitize=address,undefined -o outline_host_check tests/diag/outline_host_check.hip
 //   ASAN_OPTIONS=detect_leaks=0 ./outline_host_check
 #include <cstdio>
@@ -89,6 +90,38 @@ int main()
     a.ws = ws + 64; EXPECT(call(a) == VISTAF_E_INVALID && says("d_workspace") && says("aligned")); a = good;
     a.n = bytes - 1; EXPECT(call(a) == VISTAF_E_INVALID && says("workspace_bytes")); a = good;
     a.n = 0; EXPECT(call(a) == VISTAF_E_INVALID && says("workspace_bytes"));
+
+    // the capacity rule, exhaustively: every count vector of K <= 4 rows with entries 0..3, every number of rows in use, every capacity 0..12.
+    // The restatement walks the rows once: a row in use is written while no row before it was left out and it still fits.  Frame 1 of a
+    // table of two, so that the frame stride counts; frame 0 holds counts that would overflow everything.
+    for (int K = 1; K <= 4; K++) {
+        int total = 1;
+        for (int j = 0; j < K; j++) total *= 4;
+        for (int code = 0; code < total; code++) {
+            double table[2 * 4 * VISTAF_NOUTLINE];
+            for (double &v : table) v = 1000.0;
+            int c[4] = {0, 0, 0, 0};
+            for (int j = 0, q = code; j < K; j++, q /= 4) {
+                c[j] = q % 4;
+                table[(size_t)(K + j) * VISTAF_NOUTLINE + VISTAF_OUTLINE_CORNERS] = (double)c[j];
+            }
+            for (int kk = 0; kk <= K; kk++)
+                for (int cap = 0; cap <= 12; cap++) {
+                    int run = 0, end = 0;
+                    bool open = true;
+                    for (int k = 0; k < K; k++) {
+                        const bool fits = k < kk && open && run + c[k] <= cap;
+                        if (k < kk && !fits) open = false;                    // the first row left out: nothing behind it is written
+                        const RowCapacity got = row_capacity(table, VISTAF_NOUTLINE, VISTAF_OUTLINE_CORNERS, 1, K, k, kk, cap);
+                        EXPECT(got.before == run && got.written == (fits ? c[k] : 0));
+                        EXPECT(got.before == end && got.before + got.written <= cap);      // offsets[k] .. offsets[k + 1]: monotone, within V
+                        EXPECT(open || got.written == 0);
+                        end = got.before + got.written;
+                        run += got.written;
+                    }
+                }
+        }
+    }
     std::printf("outline host check ok\n");
     return 0;
 }

@@ -15,6 +15,8 @@ import pytest
 
 import centreline_helpers as CL
 import contacts_helpers as CH
+from abi_helpers import _hold_against, _prototypes
+from abi_helpers import _same_f64_bits as _same_bits
 from centreline_helpers import F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -113,37 +115,6 @@ def test_reference_capacity_and_table_rules():
     assert (out[q, 2:5, F["status"]] == CL.NO_PIXELS).all()
     assert np.isnan(out[names.index("count_zero")]).all() and not np.isnan(out[names.index("count_above_K"), :, 0]).any()
     assert (full["skeleton"][names.index("count_zero")] == -1).all()
-
-
-def _prototypes(text):
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).split("\n") if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vistaf_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos
-        protos[name] = (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
-    return protos
-
-
-def _hold_against(protos, table, lib):
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "int64_t": ctypes.c_int64,
-               "size_t": ctypes.c_size_t}
-
-    def matches(c_text, ctype):
-        if "*" in c_text:
-            return ctype in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int)))
-        words = [w for w in re.findall(r"\w+", c_text) if w not in ("const", "unsigned", "signed")]
-        kind = next((w for w in words if w in scalars), None)
-        assert kind is not None, c_text
-        return ctype is scalars[kind]
-    assert sorted(protos) == sorted(table)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = table[name]
-        assert len(argtypes) == len(params), name
-        for i, (p, a) in enumerate(zip(params, argtypes)):
-            assert matches(p, a), (name, i, p, a)
-        assert restype is not None and matches(ret, restype)
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
 
 
 def test_centreline_names_and_signatures_follow_the_header(pkg):
@@ -312,13 +283,6 @@ def _abi(pkg, c, V, span=8, depth=True, polylines=True, d2=True, skeleton=True, 
     torch.cuda.synchronize()
     return {"centrelines": out.cpu().numpy(), "stations": st.cpu().numpy()[:, :V], "d2": sd.cpu().numpy()[:, :V], "offsets": offs.cpu().numpy(),
             "skeleton": sk.cpu().numpy()}
-
-
-def _same_bits(a, b):
-    """bit for bit, NaN in the same places"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.int64)[~na], b.view(np.int64)[~nb])
 
 
 def _check(got, want, what, polylines=True, d2=True, skeleton=True):

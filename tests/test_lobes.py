@@ -17,6 +17,8 @@ import pytest
 
 import contacts_helpers as CH
 import lobes_helpers as LH
+from abi_helpers import _hold_against, _prototypes
+from abi_helpers import _same_f64_bits as _same_bits
 from lobes_helpers import LF, RF
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -152,37 +154,6 @@ def test_split_table_rules_on_the_reference():
     assert (rows[q, 3:5, RF["status"]] == LH.NO_PIXELS).all() and lobes[q, 2, 0, LF["contact_pixels"]] == 0 and np.isnan(lobes[q, 2, 0, LF["centroid_x"]])
     p = names.index("plateau_and_ring")
     assert rows[p, 0, RF["raw_maxima"]] == 2 and rows[p, 0, RF["peaks"]] == 1 and rows[p, 0, RF["next_prominence_mm"]] == 0.0
-
-
-def _prototypes(text):
-    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).split("\n") if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vistaf_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos
-        protos[name] = (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
-    return protos
-
-
-def _hold_against(protos, table, lib):
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "int64_t": ctypes.c_int64,
-               "size_t": ctypes.c_size_t}
-
-    def matches(c_text, ctype):
-        if "*" in c_text:
-            return ctype in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int)))
-        words = [w for w in re.findall(r"\w+", c_text) if w not in ("const", "unsigned", "signed")]
-        kind = next((w for w in words if w in scalars), None)
-        assert kind is not None, c_text
-        return ctype is scalars[kind]
-    assert sorted(protos) == sorted(table)
-    for name, (ret, params) in protos.items():
-        restype, argtypes = table[name]
-        assert len(argtypes) == len(params), name
-        for i, (p, a) in enumerate(zip(params, argtypes)):
-            assert matches(p, a), (name, i, p, a)
-        assert restype is not None and matches(ret, restype)
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == argtypes
 
 
 def test_lobe_names_and_signatures_follow_the_header(pkg):
@@ -357,13 +328,6 @@ def _abi(pkg, c, L, tau_mm, tau_frac, eps, lobe_index=True, split=True, sel=None
     torch.cuda.synchronize()
     return {"lobes": lobes.cpu().numpy(), "rows": rows.cpu().numpy(), "lobe_index": lidx.cpu().numpy(), "split_contacts": sp.cpu().numpy(),
             "split_count": scnt.cpu().numpy(), "split_index": sidx.cpu().numpy(), "split_parent": par.cpu().numpy()}
-
-
-def _same_bits(a, b):
-    """bit for bit, NaN in the same places"""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    na, nb = np.isnan(a), np.isnan(b)
-    return a.shape == b.shape and np.array_equal(na, nb) and np.array_equal(a.view(np.int64)[~na], b.view(np.int64)[~nb])
 
 
 def _within(got, ref, rel, what, bucket):

@@ -18,6 +18,7 @@ import pytest
 
 import contacts_helpers as CH
 import match_helpers as MH
+from abi_helpers import _hold_against, _prototypes, _same_bits
 from match_helpers import F
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,32 +95,11 @@ def test_match_names_and_signatures_follow_the_header(pkg):
     for name in ("match", "MATCH_NAMES", "TemplateBank", "MatchWorkspace", "contact_matches", "matches_table", "write_matches_csv", "match_frame_record"):
         assert name in pkg.__all__ and hasattr(pkg, name)
     # the header is outside include/*.h, whose prototype count tests/test_abi_surface.py pins; the rule of that test, for these functions
-    text = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).split("\n") if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vistaf_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos
-        protos[name] = (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
+    protos = _prototypes(hdr)
     table = L.MATCH_SIGNATURES
     assert sorted(protos) == sorted(table) == ["vistaf_match_bank_bytes", "vistaf_match_build_bank", "vistaf_match_measure", "vistaf_match_workspace_bytes"]
     assert not set(table) & ({n for g in L.SIGNATURES.values() for n in g} | set(L.OUTLINE_SIGNATURES) | set(L.TEXTURE_SIGNATURES))
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-
-    def matches(c_text, ctype):
-        if "*" in c_text:
-            return ctype in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int)))
-        kind = next((w for w in re.findall(r"\w+", c_text) if w in scalars), None)
-        assert kind is not None, c_text
-        return ctype is scalars[kind]
-    for name, (ret, params) in protos.items():
-        restype, argtypes = table[name]
-        assert len(argtypes) == len(params), name
-        for i, (p, a) in enumerate(zip(params, argtypes)):
-            assert matches(p, a), (name, i, p, a)
-        assert matches(ret, restype)
-    lib = L.load()
-    for name in table:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == table[name][1]
+    _hold_against(protos, table, L.load())
     for other in os.listdir(os.path.join(ROOT, "include")):
         if other.endswith(".h"):
             assert "vistaf_match" not in open(os.path.join(ROOT, "include", other)).read(), other
@@ -328,10 +308,6 @@ def _measure(pkg, fr, bank, ws=None, eps=MH.EPS, **kw):
 
 def _ref(fr, bank, **kw):
     return MH.numpy_matches(fr["depth"], fr["index"], fr["contacts"], fr["count"], fr["mm_per_px"], bank, **kw)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
 
 
 def _pick(fr, sel):

@@ -20,6 +20,7 @@ import pytest
 
 import contacts_helpers as CH
 import texture_helpers as TH
+from abi_helpers import _hold_against, _prototypes
 from texture_helpers import T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -62,32 +63,11 @@ def test_texture_names_and_signatures_follow_the_header(pkg):
     for name in ("texture", "TEXTURE_NAMES", "TextureWorkspace", "contact_textures", "textures_table", "write_textures_csv", "texture_frame_record"):
         assert name in pkg.__all__ and hasattr(pkg, name)
     # the header is outside include/*.h, whose prototype count tests/test_abi_surface.py pins; the rule of that test, for these functions
-    text = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
-    text = "\n".join(ln for ln in re.sub(r"//[^\n]*", " ", text).split("\n") if not ln.lstrip().startswith("#"))
-    protos = {}
-    for ret, name, params in re.findall(r"([A-Za-z_][\w \t\*]*?)\b(vistaf_\w+)\s*\(([^()]*)\)\s*;", text):
-        assert name not in protos
-        protos[name] = (" ".join(ret.split()), [" ".join(p.split()) for p in params.split(",")])
+    protos = _prototypes(hdr)
     table = pkg._lib.TEXTURE_SIGNATURES
     assert sorted(protos) == sorted(table) == ["vistaf_texture_measure", "vistaf_texture_workspace_bytes"]
     assert not set(table) & ({n for g in pkg._lib.SIGNATURES.values() for n in g} | set(pkg._lib.OUTLINE_SIGNATURES))
-    scalars = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "double": ctypes.c_double, "float": ctypes.c_float, "size_t": ctypes.c_size_t}
-
-    def matches(c_text, ctype):
-        if "*" in c_text:
-            return ctype in (ctypes.c_void_p, ctypes.c_char_p) or isinstance(ctype, type(ctypes.POINTER(ctypes.c_int)))
-        kind = next((w for w in re.findall(r"\w+", c_text) if w in scalars), None)
-        assert kind is not None, c_text
-        return ctype is scalars[kind]
-    for name, (ret, params) in protos.items():
-        restype, argtypes = table[name]
-        assert len(argtypes) == len(params), name
-        for i, (p, a) in enumerate(zip(params, argtypes)):
-            assert matches(p, a), (name, i, p, a)
-        assert matches(ret, restype)
-    lib = pkg._lib.load()
-    for name in table:
-        assert hasattr(lib, name) and getattr(lib, name).argtypes == table[name][1]
+    _hold_against(protos, table, pkg._lib.load())
     for other in os.listdir(os.path.join(ROOT, "include")):
         if other.endswith(".h"):
             assert "vistaf_texture" not in open(os.path.join(ROOT, "include", other)).read(), other

@@ -355,6 +355,9 @@ LOBES_SIGNATURES = {
 LOBES_TEST_SIGNATURES = {
     "vistaf_ftp_test_lobes_tier": (ci, [ci, ci]),
 }
+# every table beside SIGNATURES, a sixth read-out's included: load() applies what is listed here
+EXTENSION_SIGNATURES = [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, FIT_WINDOW_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES,
+                        MATCH_SIGNATURES, CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES, LOBES_SIGNATURES, LOBES_TEST_SIGNATURES]
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())
@@ -373,9 +376,7 @@ def load():
             "This package has no CPU path."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for group in list(SIGNATURES.values()) + [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, FIT_WINDOW_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES,
-                                                 MATCH_SIGNATURES,
-                                                 CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES, LOBES_SIGNATURES, LOBES_TEST_SIGNATURES]:
+    for group in list(SIGNATURES.values()) + EXTENSION_SIGNATURES:
         for name, (restype, argtypes) in group.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = restype, argtypes

@@ -169,6 +169,42 @@ __device__ inline int wave_excl_scan(int v, int &total)
     total = __builtin_amdgcn_readlane(incl, 63);
     return incl - v;
 }
+// exclusive prefix sum over the threads of a workgroup of NW waves and the workgroup's total; wtot: NW ints of LDS, free to reuse once the
+// next barrier is passed (the one in front of the write orders the reads of an earlier call).  Every thread calls it
+template <int NW>
+__device__ inline int block_excl_scan(int v, int *wtot, int &total)
+{
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int wt;
+    const int ex = wave_excl_scan(v, wt);
+    __syncthreads();
+    if (lane == 0) wtot[wid] = wt;
+    __syncthreads();
+    int pre = 0, tot = 0;
+#pragma unroll
+    for (int q = 0; q < NW; q++) {
+        const int t = wtot[q];
+        pre += q < wid ? t : 0;
+        tot += t;
+    }
+    total = tot;
+    return pre + ex;
+}
+// workgroup barrier, and workgroup OR, that also order the stores to tables that are in LDS for one workgroup and in global memory for
+// another (the tiers of k_centreline_rows, k_lobes_rows) before the loads behind them
+__device__ __forceinline__ void block_sync_fenced()
+{
+    __threadfence_block();
+    __syncthreads();
+    __threadfence_block();
+}
+__device__ __forceinline__ int block_any_fenced(bool p)
+{
+    __threadfence_block();
+    const int r = __syncthreads_or(p ? 1 : 0);
+    __threadfence_block();
+    return r;
+}
 // the value of lane - 1 / lane + 1 (wave_shr:1 / wave_shl:1); the lane without a source takes `fill`
 __device__ inline uint32_t wave_shr1(uint32_t v, uint32_t fill) { return (uint32_t)__builtin_amdgcn_update_dpp((int)fill, (int)v, 0x138, 0xf, 0xf, false); }
 __device__ inline int wave_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138, 0xf, 0xf, false); }

@@ -1,5 +1,7 @@
-// What the kernels with one workgroup per (frame, row) of the contacts table share: k_shape, k_thermal_contacts, k_motion, k_pressure_rows, k_texture_*.
-// The reading of a row's box, the walk over it and the prologue of an unused row.  Device inline code only.
+// What the kernels with one workgroup per (frame, row) of the contacts table share: k_shape, k_thermal_contacts, k_motion, k_pressure_rows, and
+// the read-outs with a workspace of the caller's, k_texture_*, k_match_*, k_outline_*, k_centreline_*, k_lobes_*.  The reading of a row's box, the
+// walk over it, the prologues of an unused row and of a row without a pixel; for the last three also the capacity rule of their polylines, the
+// LDS a row's tables may take and the -1 fill of an int8 plane.  Inline code, and one kernel template with its launcher.
 #pragma once
 #include "../../include/vistaf_ftp.h"
 #include "common.hpp"
@@ -77,5 +79,50 @@ __device__ inline bool nan_row(bool unused, double *out, int n)
     if (unused && (int)threadIdx.x < n) out[threadIdx.x] = nan64();
     return unused;
 }
+
+// A row in use without a pixel (k_centreline_rows, k_lobes_rows): n fields (n <= the workgroup's threads), 0 before the status field, `status`
+// in it, NaN behind it
+__device__ inline void empty_row(double *out, int n, int status_field, int status)
+{
+    const int t = threadIdx.x;
+    if (t < n) out[t] = t < status_field ? 0.0 : (t == status_field ? (double)status : nan64());
+}
+
+// The capacity rule of a frame's polylines (k_outline_poly over CORNERS, k_centreline_poly over STATIONS): row k of the kk rows in use is
+// written when the counts of the rows up to it, table[(b * K + j) * stride + field], sum to at most `capacity`.  before: the elements of the
+// written rows in front of k, where k's start; written: k's own count, or 0.  The totals only grow, so the rows up to k pass together and no
+// row behind the first that does not fit is written.
+struct RowCapacity { int before, written; };
+__host__ __device__ inline RowCapacity row_capacity(const double *table, int stride, int field, int b, int K, int k, int kk, int capacity)
+{
+    long long cum = 0;
+    int before = 0, mine = 0;
+    for (int j = 0; j <= k && j < kk; j++) {
+        const int c = (int)table[((size_t)b * K + j) * stride + field];
+        cum += c;
+        if (j < k && cum <= capacity) before = (int)cum;
+        if (j == k) mine = c;
+    }
+    return {before, k < kk && cum <= capacity ? mine : 0};
+}
+
+// The LDS the tables of a row's box may take in a kernel that falls back to the caller's workspace for a larger box (k_centreline_rows,
+// k_lobes_rows).  60 KB keeps the launch within the 64 KB every kernel may ask for without an attribute (the static reduction scratch and
+// chunk arrays come on top) and lets two workgroups share a CU's 160 KB at the limit.
+constexpr int ROW_LDS_BUDGET = 60 * 1024;
+
+// v over an int8 plane of n elements (the skeleton plane, the lobe plane): 256 threads, 16 elements each, at most 65 536 workgroups
+template <int V>
+__global__ __launch_bounds__(256) void k_fill_i8(int8_t *__restrict__ plane, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) plane[i] = (int8_t)V;
+}
+inline dim3 fill_grid(size_t n)
+{
+    const size_t blocks = (n + 256 * 16 - 1) / (256 * 16);
+    return dim3((unsigned)(blocks < 65536 ? blocks : 65536));
+}
+template <int V>
+inline void launch_fill_i8(int8_t *plane, size_t n, hipStream_t st) { hipLaunchKernelGGL(k_fill_i8<V>, fill_grid(n), dim3(256), 0, st, plane, n); }
 
 }  // namespace vf

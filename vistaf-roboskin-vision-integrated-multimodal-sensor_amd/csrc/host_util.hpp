@@ -109,19 +109,90 @@ private:
     size_t off_ = 0;
 };
 
+// the size query: the bytes layout(ScratchLayout &) takes, counted with a null base; rec: its regions
+template <class Layout>
+size_t scratch_bytes(Layout layout, ScratchRec *rec = nullptr)
+{
+    ScratchLayout L(nullptr, rec);
+    layout(L);
+    return L.bytes();
+}
+
 // The lazily built workspace of a handle: one buffer of `owner`, laid out by layout(ScratchLayout &), which returns the struct of its
 // pointers.  Sizes it with a null layout, allocates, carves; *bufs and buf are set only when all of it succeeded.  A no-op once buf is set.
 template <class Bufs, class Layout>
 int ensure_carved(DeviceAllocs &owner, void *&buf, Bufs *bufs, Layout layout)
 {
     if (buf) return 0;
-    ScratchLayout size(nullptr);
-    layout(size);
     uint8_t *p = nullptr;
-    TRY(owner.alloc(&p, size.bytes()));
+    TRY(owner.alloc(&p, scratch_bytes(layout)));
     ScratchLayout carve(p);
     *bufs = layout(carve);
     buf = p;
+    return 0;
+}
+
+// ---- The host side of the read-outs with two plain functions and a workspace of the caller's (vistaf_X_workspace_bytes, vistaf_X_measure:
+// outline, texture, match, centreline, lobes).  What their argument checks share; the checks of a read-out's own outputs, parameters and
+// alignment sentences stay in its file.
+
+// The sizes a read-out of the index plane takes (outline, centreline, lobes: coordinates are packed into 15 bits, edge slots into 31), and
+// those of a read-out of the depth plane (texture, match; batch_text names the argument, batch or max_batch): the text of the refusal, or null
+inline const char *plane_sizes_refusal(int h, int w, int batch, int max_contacts)
+{
+    if (h < 1 || h > 32767) return "h must be 1..32767";
+    if (w < 1 || w > 32767) return "w must be 1..32767";
+    if ((long long)h * w > 0x1fffffffll) return "h * w must be below 2^29";
+    if (batch < 1 || batch > (1 << 24)) return "batch must be 1..2^24";
+    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
+    return nullptr;
+}
+inline const char *depth_sizes_refusal(int h, int w, int batch, const char *batch_text, int max_contacts)
+{
+    if (h < 1) return "h must be >= 1";
+    if (w < 1) return "w must be >= 1";
+    if ((long long)h * w > 0x7fffffffll) return "h * w must be below 2^31";
+    if (batch < 1 || batch > (1 << 19)) return batch_text;
+    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
+    return nullptr;
+}
+
+// The answer of a vistaf_X_workspace_bytes: `refusal` is what the read-out's size checks said, need() the bytes, asked only for sizes they took
+template <class Need>
+int workspace_bytes_answer(size_t *bytes, const char *refusal, Need need)
+{
+    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
+    *bytes = 0;
+    if (refusal) return set_error(VISTAF_E_INVALID, refusal);
+    *bytes = need();
+    return 0;
+}
+
+// the answer of a tier hook (test_hooks_centreline.h, test_hooks_lobes.h): 1 when in_lds(bw, bh) says a bw x bh box works in LDS, else 0
+template <class Rule>
+int tier_hook_answer(int bw, int bh, Rule in_lds)
+{
+    if (bw < 1 || bw > 32767) return set_error(VISTAF_E_INVALID, "bw must be 1..32767");
+    if (bh < 1 || bh > 32767) return set_error(VISTAF_E_INVALID, "bh must be 1..32767");
+    return in_lds(bw, bh) ? 1 : 0;
+}
+
+// the four inputs vistaf_ftp_contacts wrote: the text of the refusal, or null
+inline const char *table_inputs_refusal(const void *d_contact_index, const void *d_contacts, const void *d_count, const void *d_mm_per_px)
+{
+    if (!d_contact_index) return "d_contact_index is null";
+    if (!d_contacts) return "d_contacts is null";
+    if (!d_count) return "d_count is null";
+    if (!d_mm_per_px) return "d_mm_per_px is null";
+    return nullptr;
+}
+
+// the caller's workspace against `need` bytes; sizer: the function that tells the caller how many
+inline int workspace_ok(const void *d_workspace, size_t workspace_bytes, size_t need, const char *sizer)
+{
+    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
+    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
+    if (workspace_bytes < need) return set_error(VISTAF_E_INVALID, std::string("workspace_bytes is below what ") + sizer + " gives for these sizes");
     return 0;
 }
 

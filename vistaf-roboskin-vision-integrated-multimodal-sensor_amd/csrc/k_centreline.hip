@@ -6,7 +6,7 @@
 // W64 = ceil(bw / 64) words with a zero row above and below, seven planes: the mask M, two skeleton buffers, two frontier buffers and two
 // planes that hold a walk's hop count modulo 4.  A box whose planes fit CL_LDS_BUDGET works in LDS; a larger one runs the same code over
 // planes in the caller's workspace (cl_box_in_lds; test_hooks_centreline.h tells the tiers apart).
-//   k_centreline_fill  (only with d_skeleton) writes -1 over the skeleton plane.
+//   k_fill_i8<-1>      (only with d_skeleton; contact_rows.hpp) writes -1 over the skeleton plane.
 //   k_centreline_rows  packs M with wave ballots; thins it (Guo-Hall, the two conditions and the small sums bit-sliced on 64 pixels per word,
 //                      the buffers swapped after each sub-iteration, one workgroup barrier-with-OR per sub-iteration); counts skeleton, end and
 //                      branch pixels bit-sliced; finds the seed by a max-reduction over D2, which is not a plane here: D2 of one pixel is
@@ -36,10 +36,9 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int CL_NT = 256, CL_PLANES = 7;
-// The LDS a row's planes may take.  60 KB keeps the launch within the 64 KB every kernel may ask for without an attribute (the chunk arrays
-// and reduction scratch are static and come on top), lets two workgroups share a CU's 160 KB at the limit, and holds a box of a whole
-// 224 x 224 frame (226 rows x 4 words x 8 bytes x 7 planes = 50,624 bytes), where three fit.
-constexpr int CL_LDS_BUDGET = 60 * 1024;
+// The LDS a row's planes may take (contact_rows.hpp): it holds a box of a whole 224 x 224 frame (226 rows x 4 words x 8 bytes x 7 planes =
+// 50,624 bytes), where three workgroups share a CU.
+constexpr int CL_LDS_BUDGET = ROW_LDS_BUDGET;
 constexpr int CL_NONE = -1;
 
 // ---- pure rules -----------------------------------------------------------------------------------------------------------------------
@@ -70,9 +69,7 @@ CentrelineBufs centreline_scratch(ScratchLayout &L, int B, int h, int w, int K)
 
 size_t centreline_scratch_bytes(int B, int h, int w, int K, ScratchRec *rec = nullptr)
 {
-    ScratchLayout L(nullptr, rec);
-    centreline_scratch(L, B, h, w, K);
-    return L.bytes();
+    return scratch_bytes([&](ScratchLayout &L) { return centreline_scratch(L, B, h, w, K); }, rec);
 }
 
 struct ClArgs {
@@ -91,15 +88,6 @@ struct ClArgs {
 __device__ __forceinline__ int cl_dx(int d) { return d == 1 || d == 4 || d == 5 ? 1 : (d == 3 || d == 6 || d == 7 ? -1 : 0); }
 __device__ __forceinline__ int cl_dy(int d) { return d == 2 || d == 5 || d == 6 ? 1 : (d == 0 || d == 4 || d == 7 ? -1 : 0); }
 __device__ __forceinline__ int cl_back(int d) { return d < 4 ? (d + 2) & 3 : 4 + ((d + 2) & 3); }
-
-// workgroup OR that also orders the planes' stores, LDS or global, before the loads behind it
-__device__ __forceinline__ int cl_any(bool p)
-{
-    __threadfence_block();
-    const int r = __syncthreads_or(p ? 1 : 0);
-    __threadfence_block();
-    return r;
-}
 
 // The geometry of a row's planes and the word-level steps on them.  r is the box row, 0..bh-1; plane row r + 1.
 struct ClGeom {
@@ -203,13 +191,13 @@ __device__ __forceinline__ int cl_walk(PL S, PL V, PL F, PL Fn, PL L0, PL L1, co
         V[i] = 0ull; F[i] = 0ull; Fn[i] = 0ull;
         if (RECORD) { L0[i] = 0ull; L1[i] = 0ull; }
     }
-    cl_any(false);
+    block_any_fenced(false);
     if (tid == 0) {
         const size_t i = (size_t)(sy + 1) * g.W64 + (sx >> 6);
         F[i] = 1ull << (sx & 63);
         V[i] = 1ull << (sx & 63);
     }
-    cl_any(false);
+    block_any_fenced(false);
     int lev = 0;
     for (;;) {
         bool any = false;
@@ -233,7 +221,7 @@ __device__ __forceinline__ int cl_walk(PL S, PL V, PL F, PL Fn, PL L0, PL L1, co
                 any = true;
             }
         }
-        if (!cl_any(any)) break;
+        if (!block_any_fenced(any)) break;
         PL tmp = F; F = Fn; Fn = tmp;
         lev++;
     }
@@ -309,12 +297,12 @@ __device__ __forceinline__ void cl_row(PL pl, const ClArgs &a, const ContactBox 
             }
         }
     }
-    npix = block_sum(npix, red);            // its barriers order the LDS planes; the workspace planes are fenced by the cl_any below
+    npix = block_sum(npix, red);            // its barriers order the LDS planes; the workspace planes are fenced by the block_any_fenced below
     if (npix == 0) {
-        if (tid < VISTAF_NCENTRELINE) out[tid] = tid < VISTAF_CENTRELINE_STATUS ? 0.0 : (tid == VISTAF_CENTRELINE_STATUS ? (double)VISTAF_CLST_NO_PIXELS : nan64());
+        empty_row(out, VISTAF_NCENTRELINE, VISTAF_CENTRELINE_STATUS, VISTAF_CLST_NO_PIXELS);
         return;
     }
-    cl_any(false);
+    block_any_fenced(false);
 
     // ---- thinning: every sub-iteration reads one buffer and writes the other; a pair leaves S in Sa again
     int passes = 0;
@@ -330,7 +318,7 @@ __device__ __forceinline__ void cl_row(PL pl, const ClArgs &a, const ContactBox 
                 dst[g.at(t)] = cc & ~del;
                 any = any || del != 0ull;
             }
-            pair |= cl_any(any);
+            pair |= block_any_fenced(any);
         }
         if (!pair) break;
         passes++;
@@ -369,7 +357,7 @@ __device__ __forceinline__ void cl_row(PL pl, const ClArgs &a, const ContactBox 
     nbranch = block_sum(nbranch, red);
     seed = block_max_u64(seed, red);
     if (nskel == 0) {                                          // Guo-Hall empties no mask; were it to, the row reads as one without pixels
-        if (tid < VISTAF_NCENTRELINE) out[tid] = tid < VISTAF_CENTRELINE_STATUS ? 0.0 : (tid == VISTAF_CENTRELINE_STATUS ? (double)VISTAF_CLST_NO_PIXELS : nan64());
+        empty_row(out, VISTAF_NCENTRELINE, VISTAF_CENTRELINE_STATUS, VISTAF_CLST_NO_PIXELS);
         return;
     }
     const int seed_d2 = (int)(seed >> 32), seed_p = (int)(0xffffffffu - (uint32_t)seed), seed_y = seed_p / g.bw, seed_x = seed_p - seed_y * g.bw;
@@ -390,7 +378,7 @@ __device__ __forceinline__ void cl_row(PL pl, const ClArgs &a, const ContactBox 
             cl_set_link(K0, K1, K2, g, x, y, cl_back(d));
         }
     }
-    cl_any(false);
+    block_any_fenced(false);
 
     // ---- the stations in listed order, in chunks: lane 0 lists, every thread measures one, lane 0 folds
     const int Ax = a_is_a0 ? ax : bx, Ay = a_is_a0 ? ay : by, Bx = a_is_a0 ? bx : ax, By = a_is_a0 ? by : ay;     // box coordinates
@@ -512,11 +500,6 @@ __device__ __forceinline__ void cl_row(PL pl, const ClArgs &a, const ContactBox 
     }
 }
 
-__global__ __launch_bounds__(256) void k_centreline_fill(int8_t *__restrict__ skeleton, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) skeleton[i] = (int8_t)-1;
-}
-
 __global__ __launch_bounds__(CL_NT) void k_centreline_rows(ClArgs a)
 {
     extern __shared__ u64 cl_lds[];
@@ -525,8 +508,7 @@ __global__ __launch_bounds__(CL_NT) void k_centreline_rows(ClArgs a)
     if (nan_row(k >= clamp_count(a.count[b], a.K), out, VISTAF_NCENTRELINE)) return;
     const ContactBox box(a.contacts + (size_t)blockIdx.x * VISTAF_NCONTACT, a.h, a.w);
     if (!box.total()) {
-        if (threadIdx.x < VISTAF_NCENTRELINE)
-            out[threadIdx.x] = threadIdx.x < VISTAF_CENTRELINE_STATUS ? 0.0 : (threadIdx.x == VISTAF_CENTRELINE_STATUS ? (double)VISTAF_CLST_NO_PIXELS : nan64());
+        empty_row(out, VISTAF_NCENTRELINE, VISTAF_CENTRELINE_STATUS, VISTAF_CLST_NO_PIXELS);
         return;
     }
     if (cl_box_in_lds(box.bw, box.bh)) cl_row<u64 *>(cl_lds, a, box, b, k);
@@ -539,23 +521,15 @@ __global__ __launch_bounds__(CL_NT) void k_centreline_poly(const int8_t *__restr
 {
     const int b = blockIdx.x / K, k = blockIdx.x - b * K, tid = threadIdx.x;
     const int kk = clamp_count(count[b], K);
-    // the capacity rule: the rows before k that were written, and whether k is (the totals only grow, so the rows up to k pass together)
-    long long cum = 0;
-    int before = 0, mine = 0;
-    for (int j = 0; j <= k && j < kk; j++) {
-        const int c = (int)centrelines[((size_t)b * K + j) * VISTAF_NCENTRELINE + VISTAF_CENTRELINE_STATIONS];
-        cum += c;
-        if (j < k && cum <= max_stations) before = (int)cum;
-        if (j == k) mine = c;
-    }
-    const int written = k < kk && cum <= max_stations ? mine : 0;
+    const RowCapacity cap = row_capacity(centrelines, VISTAF_NCENTRELINE, VISTAF_CENTRELINE_STATIONS, b, K, k, kk, max_stations);
+    const int before = cap.before, written = cap.written;
     if (tid == 0) {
         double *out = centrelines + (size_t)blockIdx.x * VISTAF_NCENTRELINE;
         if (k == 0) offsets[(size_t)b * (K + 1)] = 0;
         offsets[(size_t)b * (K + 1) + k + 1] = before + written;
         if (k < kk) {
             out[VISTAF_CENTRELINE_STATIONS_WRITTEN] = (double)written;
-            if (written == mine) out[VISTAF_CENTRELINE_STATUS] = (double)((int)out[VISTAF_CENTRELINE_STATUS] & ~VISTAF_CLST_TRUNCATED);
+            if (written == (int)out[VISTAF_CENTRELINE_STATIONS]) out[VISTAF_CENTRELINE_STATUS] = (double)((int)out[VISTAF_CENTRELINE_STATUS] & ~VISTAF_CLST_TRUNCATED);
         }
     }
     if (!written) return;
@@ -577,33 +551,13 @@ __global__ __launch_bounds__(CL_NT) void k_centreline_poly(const int8_t *__restr
 
 }  // namespace
 
-// the size checks both functions share: the text of the refusal, or null
-static const char *centreline_sizes_refusal(int h, int w, int batch, int max_contacts)
-{
-    if (h < 1 || h > 32767) return "h must be 1..32767";
-    if (w < 1 || w > 32767) return "w must be 1..32767";
-    if ((long long)h * w > 0x1fffffffll) return "h * w must be below 2^29";
-    if (batch < 1 || batch > (1 << 24)) return "batch must be 1..2^24";
-    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
-    return nullptr;
-}
-
 extern "C" {
 
-int vistaf_ftp_test_centreline_tier(int bw, int bh)
-{
-    if (bw < 1 || bw > 32767) return set_error(VISTAF_E_INVALID, "bw must be 1..32767");
-    if (bh < 1 || bh > 32767) return set_error(VISTAF_E_INVALID, "bh must be 1..32767");
-    return cl_box_in_lds(bw, bh) ? 1 : 0;
-}
+int vistaf_ftp_test_centreline_tier(int bw, int bh) { return tier_hook_answer(bw, bh, cl_box_in_lds); }
 
 int vistaf_centreline_workspace_bytes(int h, int w, int batch, int max_contacts, size_t *bytes)
 {
-    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
-    *bytes = 0;
-    if (const char *why = centreline_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
-    *bytes = centreline_scratch_bytes(batch, h, w, max_contacts);
-    return 0;
+    return workspace_bytes_answer(bytes, plane_sizes_refusal(h, w, batch, max_contacts), [&] { return centreline_scratch_bytes(batch, h, w, max_contacts); });
 }
 
 int vistaf_centreline_measure(const int8_t *d_contact_index, const double *d_contacts, const int32_t *d_count, const double *d_mm_per_px,
@@ -611,13 +565,9 @@ int vistaf_centreline_measure(const int8_t *d_contact_index, const double *d_con
                               double *d_centrelines, int32_t *d_stations, int32_t *d_station_d2, int32_t *d_offsets, int8_t *d_skeleton,
                               void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (!d_contact_index) return set_error(VISTAF_E_INVALID, "d_contact_index is null");
-    if (!d_contacts) return set_error(VISTAF_E_INVALID, "d_contacts is null");
-    if (!d_count) return set_error(VISTAF_E_INVALID, "d_count is null");
-    if (!d_mm_per_px) return set_error(VISTAF_E_INVALID, "d_mm_per_px is null");
+    if (const char *why = table_inputs_refusal(d_contact_index, d_contacts, d_count, d_mm_per_px)) return set_error(VISTAF_E_INVALID, why);
     if (!d_centrelines) return set_error(VISTAF_E_INVALID, "d_centrelines is null");
-    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
-    if (const char *why = centreline_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
+    if (const char *why = plane_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
     if (tangent_span < 1 || tangent_span > 1024) return set_error(VISTAF_E_INVALID, "tangent_span must be 1..1024");
     if (max_stations < 0) return set_error(VISTAF_E_INVALID, "max_stations must be >= 0");
     if (!d_stations && d_offsets) return set_error(VISTAF_E_INVALID, "d_stations is null although d_offsets is given");
@@ -627,9 +577,7 @@ int vistaf_centreline_measure(const int8_t *d_contact_index, const double *d_con
         return set_error(VISTAF_E_INVALID, "d_contacts, d_mm_per_px and d_centrelines must be 8-byte aligned");
     if (((uintptr_t)d_count | (uintptr_t)d_depth_mm | (uintptr_t)d_stations | (uintptr_t)d_station_d2 | (uintptr_t)d_offsets) & 3)
         return set_error(VISTAF_E_INVALID, "d_count, d_depth_mm, d_stations, d_station_d2 and d_offsets must be 4-byte aligned");
-    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
-    if (workspace_bytes < centreline_scratch_bytes(batch, h, w, max_contacts))
-        return set_error(VISTAF_E_INVALID, "workspace_bytes is below what vistaf_centreline_workspace_bytes gives for these sizes");
+    TRY(workspace_ok(d_workspace, workspace_bytes, centreline_scratch_bytes(batch, h, w, max_contacts), "vistaf_centreline_workspace_bytes"));
     ScratchLayout L(d_workspace);
     ClArgs a;
     a.index = d_contact_index; a.contacts = d_contacts; a.count = d_count; a.mm_per_px = d_mm_per_px; a.depth = d_depth_mm;
@@ -638,10 +586,7 @@ int vistaf_centreline_measure(const int8_t *d_contact_index, const double *d_con
     a.bf = centreline_scratch(L, batch, h, w, max_contacts);
     const dim3 grid((unsigned)(batch * max_contacts));
     hipStream_t st = (hipStream_t)stream;
-    if (d_skeleton) {
-        const size_t n = (size_t)batch * h * w, blocks = (n + 256 * 16 - 1) / (256 * 16);
-        hipLaunchKernelGGL(k_centreline_fill, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, st, d_skeleton, n);
-    }
+    if (d_skeleton) launch_fill_i8<-1>(d_skeleton, (size_t)batch * h * w, st);
     hipLaunchKernelGGL(k_centreline_rows, grid, dim3(CL_NT), cl_launch_lds(h, w), st, a);
     if (d_stations)
         hipLaunchKernelGGL(k_centreline_poly, grid, dim3(CL_NT), 0, st, d_contact_index, d_contacts, d_count, h, w, max_contacts, max_stations, a.bf,

@@ -5,7 +5,7 @@
 // One workgroup of 1024 threads per (frame, row) on the row's clipped box of n = bw * bh pixels, with tables per pixel (depth key, top, basin)
 // and per maximum (at most ceil(bw / 2) * ceil(bh / 2): two maxima are never 8-adjacent).  A box whose tables fit LB_LDS_BUDGET works in
 // LDS; a larger one runs the same code over tables in the caller's workspace (lb_box_in_lds; test_hooks_lobes.h tells the tiers apart).
-//   k_lobes_fill   writes -1 over the lobe plane.
+//   k_fill_i8<-1>  (contact_rows.hpp) writes -1 over the lobe plane.
 //   k_lobes_rows   packs the order of the header's step 1 into one unsigned key per pixel; finds up(p) in one sweep and top(p) by pointer
 //                  jumping; lists the maxima in row-major order with a block scan; builds the maximum spanning forest of the basin graph under
 //                  the pass order by Boruvka rounds (every crossing pair offers its packed pass key to both components' best-edge slots with
@@ -34,10 +34,9 @@ typedef unsigned long long u64;
 // 1024 threads for the row kernel: a workgroup's time is sweeps of the box, each a chain of dependent loads, so the threads of a workgroup
 // are what hides their latency on a large box (measured: DESIGN.md); the frame kernel has little to do
 constexpr int LB_NT = 1024, LB_SPLIT_NT = 256, LB_MAXL = VISTAF_LOBES_MAX;
-// The LDS a row's tables may take.  60 KB keeps the launch within the 64 KB every kernel may ask for without an attribute (the reduction
-// scratch is static and comes on top) and lets two workgroups share a CU's 160 KB at the limit.  A 51 x 51 box fits (12 bytes per pixel,
-// 32 per possible maximum, 8 per slot of the sort); no occupancy or time has been measured for this kernel.
-constexpr int LB_LDS_BUDGET = 60 * 1024;
+// The LDS a row's tables may take (contact_rows.hpp).  A 51 x 51 box fits (12 bytes per pixel, 32 per possible maximum, 8 per slot of the
+// sort); no occupancy or time has been measured for this kernel.
+constexpr int LB_LDS_BUDGET = ROW_LDS_BUDGET;
 constexpr int LB_AUX = 4;          // per written lobe, for k_lobes_split: depth sum bits, peak key, x0 | y0 << 32, x1 | y1 << 32
 
 // ---- pure rules -----------------------------------------------------------------------------------------------------------------------
@@ -77,9 +76,7 @@ LobesBufs lobes_scratch(ScratchLayout &L, int B, int h, int w, int K)
 
 size_t lobes_scratch_bytes(int B, int h, int w, int K, ScratchRec *rec = nullptr)
 {
-    ScratchLayout L(nullptr, rec);
-    lobes_scratch(L, B, h, w, K);
-    return L.bytes();
+    return scratch_bytes([&](ScratchLayout &L) { return lobes_scratch(L, B, h, w, K); }, rec);
 }
 
 struct LbArgs {
@@ -95,21 +92,6 @@ struct LbArgs {
     int8_t *plane;           // the caller's lobe plane or the workspace's
     LobesBufs bf;
 };
-
-// workgroup barrier that also orders the tables' stores, LDS or global, before the loads behind it
-__device__ __forceinline__ void lb_sync()
-{
-    __threadfence_block();
-    __syncthreads();
-    __threadfence_block();
-}
-__device__ __forceinline__ int lb_any(bool p)
-{
-    __threadfence_block();
-    const int r = __syncthreads_or(p ? 1 : 0);
-    __threadfence_block();
-    return r;
-}
 
 // the tables of a row carved from `base` (8-byte aligned), and the rules on them
 struct LbTab {
@@ -180,15 +162,14 @@ __device__ inline void lb_sort_desc(u64 *e, int n2)
                     if (((i & k) == 0) ? a < b : a > b) { e[i] = b; e[o] = a; }
                 }
             }
-            lb_sync();
+            block_sync_fenced();
         }
 }
 
 __device__ inline void lb_empty_row(const LbArgs &a, double *row, double *lobes)
 {
-    const int tid = threadIdx.x;
-    if (tid < VISTAF_NLOBEROW) row[tid] = tid < VISTAF_LOBEROW_STATUS ? 0.0 : (tid == VISTAF_LOBEROW_STATUS ? (double)VISTAF_LOBEST_NO_PIXELS : nan64());
-    for (int i = tid; i < a.max_lobes * VISTAF_NLOBE; i += LB_NT) lobes[i] = nan64();
+    empty_row(row, VISTAF_NLOBEROW, VISTAF_LOBEROW_STATUS, VISTAF_LOBEST_NO_PIXELS);
+    for (int i = threadIdx.x; i < a.max_lobes * VISTAF_NLOBE; i += LB_NT) lobes[i] = nan64();
 }
 
 // The body of k_lobes_rows for a row with a box: base holds the tables, in LDS or in the workspace
@@ -224,7 +205,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
     npix = block_sum(npix, red);
     if (npix == 0) { lb_empty_row(a, row, lobes); return; }
     if (tid == 0) nedges_s = 0;
-    lb_sync();
+    block_sync_fenced();
 
     // ---- up(p), then top(p) by pointer jumping
     for (int p = tid; p < n; p += LB_NT) {
@@ -239,7 +220,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
         }
         t.top[p] = up;
     }
-    lb_sync();
+    block_sync_fenced();
     for (;;) {
         bool moved = false;
         for (int p = tid; p < n; p += LB_NT) {
@@ -248,7 +229,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
             const int uu = t.top[u];
             if (uu != u) { t.top[p] = uu; moved = true; }
         }
-        if (!lb_any(moved)) break;
+        if (!block_any_fenced(moved)) break;
     }
 
     // ---- the maxima in row-major order; lab(p) = the number of top(p) in that list
@@ -256,7 +237,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
     for (int p0 = 0; p0 < n; p0 += LB_NT) {
         const int p = p0 + tid;
         const int flag = p < n && t.top[p] == p ? 1 : 0;
-        int tot;
+        int tot;                                 // its own block scan: with common.hpp's block_excl_scan the call measured 0.6 % above the parent's range
         const int ex = wave_excl_scan(flag, tot);
         if (lane == 0) wtot[wid] = tot;
         __syncthreads();
@@ -266,18 +247,18 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
         M += all;
         __syncthreads();
     }
-    lb_sync();
+    block_sync_fenced();
     for (int p = tid; p < n; p += LB_NT) {
         const int u = t.top[p];
         if (u >= 0 && u != p) t.lab[p] = t.lab[u];
     }
     for (int i = tid; i < M; i += LB_NT) t.comp[i] = i;
-    lb_sync();
+    block_sync_fenced();
 
     // ---- Boruvka rounds over the basin graph: the passes of the maximum spanning forest go to edges[]
     for (;;) {
         for (int i = tid; i < M; i += LB_NT) t.best[i] = 0ull;
-        lb_sync();
+        block_sync_fenced();
         bool offered = false;
         for (int p = tid; p < n; p += LB_NT) {
             if (!t.dk[p]) continue;
@@ -296,7 +277,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
                 offered = true;
             }
         }
-        if (!lb_any(offered)) break;
+        if (!block_any_fenced(offered)) break;
         for (int i = tid; i < M; i += LB_NT) {
             int hook = -1;
             const u64 e = t.best[i];
@@ -310,17 +291,17 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
             }
             t.into[i] = hook;
         }
-        lb_sync();
+        block_sync_fenced();
         for (int i = tid; i < M; i += LB_NT)
             if (t.into[i] >= 0) t.comp[i] = t.into[i];
-        lb_sync();
+        block_sync_fenced();
         for (;;) {
             bool moved = false;
             for (int i = tid; i < M; i += LB_NT) {
                 const int c = t.comp[i], cc = t.comp[c];
                 if (cc != c) { t.comp[i] = cc; moved = true; }
             }
-            if (!lb_any(moved)) break;
+            if (!block_any_fenced(moved)) break;
         }
     }
     const int nedges = nedges_s;
@@ -328,7 +309,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
 
     // ---- the forest's passes in descending order, their two basins decoded by all threads; then lane 0 replays them for the elder rule
     for (int i = nedges + tid; i < M2; i += LB_NT) t.edges[i] = 0ull;
-    lb_sync();
+    block_sync_fenced();
     lb_sort_desc(t.edges, M2);
     for (int i = tid; i < M; i += LB_NT) {
         if (i < nedges) {
@@ -340,7 +321,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
         t.sad[i] = 0ull;
         t.into[i] = -1;
     }
-    lb_sync();
+    block_sync_fenced();
     if (tid == 0) {
         for (int j = 0; j < nedges; j++) {
             const int ba = (int)(t.best[j] >> 32), bb = (int)(t.best[j] & 0xffffffffull);
@@ -353,7 +334,7 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
             else { t.sad[eb] = t.edges[j]; t.into[eb] = ba; t.comp[rb] = ra; }
         }
     }
-    lb_sync();
+    block_sync_fenced();
 
     // ---- the threshold, the peaks, the chain of into() down to a peak
     u64 gk = 0;
@@ -377,25 +358,25 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
     next = block_max_u64(next, red);
     deepest = block_max_u64(deepest, red);
     const int peaks = (int)block_sum(npeaks, red);
-    lb_sync();
+    block_sync_fenced();
     for (int round = 0; round < 32; round++) {          // the chain ends (header, step 6); 2^32 exceeds any number of maxima
         bool moved = false;
         for (int i = tid; i < M; i += LB_NT) {
             const int c = t.ptr[i], cc = t.ptr[c];
             if (cc != c) { t.ptr[i] = cc; moved = true; }
         }
-        if (!lb_any(moved)) break;
+        if (!block_any_fenced(moved)) break;
     }
 
     // ---- the lobes' numbers: the peaks in descending order; comp[] now holds the lobe of every maximum
     for (int i = tid; i < M2; i += LB_NT) t.edges[i] = i < M && t.ptr[i] == i ? t.max_key(i) : 0ull;
-    lb_sync();
+    block_sync_fenced();
     lb_sort_desc(t.edges, M2);
     for (int j = tid; j < peaks; j += LB_NT) t.comp[t.lab[(int)(0xffffffffu - (uint32_t)t.edges[j])]] = j;
-    lb_sync();
+    block_sync_fenced();
     for (int i = tid; i < M; i += LB_NT)
         if (t.ptr[i] != i) t.comp[i] = t.comp[t.ptr[i]];
-    lb_sync();
+    block_sync_fenced();
 
     // ---- the lobe plane, the depth sum of the whole contact
     const int L = peaks < a.max_lobes ? peaks : a.max_lobes;
@@ -487,11 +468,6 @@ __device__ __forceinline__ void lb_row(uint8_t *base, const LbArgs &a, const Con
     }
 }
 
-__global__ __launch_bounds__(256) void k_lobes_fill(int8_t *__restrict__ plane, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) plane[i] = (int8_t)-1;
-}
-
 __global__ __launch_bounds__(LB_NT) void k_lobes_rows(LbArgs a)
 {
     extern __shared__ u64 lb_lds[];
@@ -581,35 +557,15 @@ __global__ __launch_bounds__(256) void k_lobes_plane(const int8_t *__restrict__ 
 
 }  // namespace
 
-// the size checks both functions share: the text of the refusal, or null
-static const char *lobes_sizes_refusal(int h, int w, int batch, int max_contacts)
-{
-    if (h < 1 || h > 32767) return "h must be 1..32767";
-    if (w < 1 || w > 32767) return "w must be 1..32767";
-    if ((long long)h * w > 0x1fffffffll) return "h * w must be below 2^29";
-    if (batch < 1 || batch > (1 << 24)) return "batch must be 1..2^24";
-    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
-    return nullptr;
-}
-
 static bool lobes_finite_nonneg(double v) { return v >= 0.0 && v <= 1.7976931348623157e308; }
 
 extern "C" {
 
-int vistaf_ftp_test_lobes_tier(int bw, int bh)
-{
-    if (bw < 1 || bw > 32767) return set_error(VISTAF_E_INVALID, "bw must be 1..32767");
-    if (bh < 1 || bh > 32767) return set_error(VISTAF_E_INVALID, "bh must be 1..32767");
-    return lb_box_in_lds(bw, bh) ? 1 : 0;
-}
+int vistaf_ftp_test_lobes_tier(int bw, int bh) { return tier_hook_answer(bw, bh, lb_box_in_lds); }
 
 int vistaf_lobes_workspace_bytes(int h, int w, int batch, int max_contacts, size_t *bytes)
 {
-    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
-    *bytes = 0;
-    if (const char *why = lobes_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
-    *bytes = lobes_scratch_bytes(batch, h, w, max_contacts);
-    return 0;
+    return workspace_bytes_answer(bytes, plane_sizes_refusal(h, w, batch, max_contacts), [&] { return lobes_scratch_bytes(batch, h, w, max_contacts); });
 }
 
 int vistaf_lobes_measure(const int8_t *d_contact_index, const double *d_contacts, const int32_t *d_count, const double *d_mm_per_px,
@@ -618,15 +574,11 @@ int vistaf_lobes_measure(const int8_t *d_contact_index, const double *d_contacts
                          double *d_split_contacts, int32_t *d_split_count, int8_t *d_split_index, int32_t *d_split_parent, void *d_workspace,
                          size_t workspace_bytes, void *stream)
 {
-    if (!d_contact_index) return set_error(VISTAF_E_INVALID, "d_contact_index is null");
-    if (!d_contacts) return set_error(VISTAF_E_INVALID, "d_contacts is null");
-    if (!d_count) return set_error(VISTAF_E_INVALID, "d_count is null");
-    if (!d_mm_per_px) return set_error(VISTAF_E_INVALID, "d_mm_per_px is null");
+    if (const char *why = table_inputs_refusal(d_contact_index, d_contacts, d_count, d_mm_per_px)) return set_error(VISTAF_E_INVALID, why);
     if (!d_depth_mm) return set_error(VISTAF_E_INVALID, "d_depth_mm is null");
     if (!d_lobes) return set_error(VISTAF_E_INVALID, "d_lobes is null");
     if (!d_rows) return set_error(VISTAF_E_INVALID, "d_rows is null");
-    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
-    if (const char *why = lobes_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
+    if (const char *why = plane_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
     if (max_lobes < 1 || max_lobes > VISTAF_LOBES_MAX) return set_error(VISTAF_E_INVALID, "max_lobes must be 1..64");
     if (!lobes_finite_nonneg(min_prominence_mm)) return set_error(VISTAF_E_INVALID, "min_prominence_mm must be finite and >= 0");
     if (!lobes_finite_nonneg(min_prominence_frac)) return set_error(VISTAF_E_INVALID, "min_prominence_frac must be finite and >= 0");
@@ -638,9 +590,7 @@ int vistaf_lobes_measure(const int8_t *d_contact_index, const double *d_contacts
         return set_error(VISTAF_E_INVALID, "d_contacts, d_mm_per_px, d_lobes, d_rows and d_split_contacts must be 8-byte aligned");
     if (((uintptr_t)d_count | (uintptr_t)d_depth_mm | (uintptr_t)d_split_count | (uintptr_t)d_split_parent) & 3)
         return set_error(VISTAF_E_INVALID, "d_count, d_depth_mm, d_split_count and d_split_parent must be 4-byte aligned");
-    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
-    if (workspace_bytes < lobes_scratch_bytes(batch, h, w, max_contacts))
-        return set_error(VISTAF_E_INVALID, "workspace_bytes is below what vistaf_lobes_workspace_bytes gives for these sizes");
+    TRY(workspace_ok(d_workspace, workspace_bytes, lobes_scratch_bytes(batch, h, w, max_contacts), "vistaf_lobes_workspace_bytes"));
     ScratchLayout L(d_workspace);
     LbArgs a;
     a.index = d_contact_index; a.contacts = d_contacts; a.count = d_count; a.mm_per_px = d_mm_per_px; a.depth = d_depth_mm;
@@ -651,14 +601,13 @@ int vistaf_lobes_measure(const int8_t *d_contact_index, const double *d_contacts
     a.plane = d_lobe_index ? d_lobe_index : a.bf.plane;
     const dim3 grid((unsigned)(batch * max_contacts));
     hipStream_t st = (hipStream_t)stream;
-    const size_t P = (size_t)h * w, n = (size_t)batch * P, blocks = (n + 256 * 16 - 1) / (256 * 16);
-    const dim3 flat((unsigned)(blocks < 65536 ? blocks : 65536));
-    hipLaunchKernelGGL(k_lobes_fill, flat, dim3(256), 0, st, a.plane, n);
+    const size_t P = (size_t)h * w, n = (size_t)batch * P;
+    launch_fill_i8<-1>(a.plane, n, st);
     hipLaunchKernelGGL(k_lobes_rows, grid, dim3(LB_NT), lb_launch_lds(h, w), st, a);
     if (d_split_contacts) {
         hipLaunchKernelGGL(k_lobes_split, dim3((unsigned)batch), dim3(LB_SPLIT_NT), 0, st, d_lobes, d_rows, d_count, d_mm_per_px, max_contacts, max_lobes, a.bf,
                            d_split_contacts, d_split_count, d_split_parent);
-        hipLaunchKernelGGL(k_lobes_plane, flat, dim3(256), 0, st, d_contact_index, (const int8_t *)a.plane, d_count, (const int32_t *)a.bf.rank,
+        hipLaunchKernelGGL(k_lobes_plane, fill_grid(n), dim3(256), 0, st, d_contact_index, (const int8_t *)a.plane, d_count, (const int32_t *)a.bf.rank,
                            max_contacts, P, n, d_split_index);
     }
     return launch_ok("k_lobes");

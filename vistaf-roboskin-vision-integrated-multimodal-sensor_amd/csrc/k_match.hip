@@ -138,9 +138,7 @@ MatchBufs match_scratch(ScratchLayout &S, int B, int K, int m, int M)
 
 size_t match_scratch_bytes(int B, int K, int m, int M, ScratchRec *rec = nullptr)
 {
-    ScratchLayout S(nullptr, rec);
-    match_scratch(S, B, K, m, M);
-    return S.bytes();
+    return scratch_bytes([&](ScratchLayout &S) { return match_scratch(S, B, K, m, M); }, rec);
 }
 
 // header, step 1, on the host: the bilinear sample of a P x P template, 0 outside the square
@@ -446,11 +444,7 @@ __global__ __launch_bounds__(MT_NT) void k_match_rows(const double *__restrict__
 // the size checks the workspace function and measure share: the text of the refusal, or null
 const char *match_sizes_refusal(int h, int w, int batch, const char *batch_text, int max_contacts, int P, int max_shift, int M)
 {
-    if (h < 1) return "h must be >= 1";
-    if (w < 1) return "w must be >= 1";
-    if ((long long)h * w > 0x7fffffffll) return "h * w must be below 2^31";
-    if (batch < 1 || batch > (1 << 19)) return batch_text;
-    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
+    if (const char *why = depth_sizes_refusal(h, w, batch, batch_text, max_contacts)) return why;
     if (P < VISTAF_MATCH_MIN_P || P > VISTAF_MATCH_MAX_P || P % 2 == 0) return "P must be odd and in 5..33";
     if (max_shift < 0 || max_shift > VISTAF_MATCH_MAX_SHIFT) return "max_shift must be 0..8";
     if (M < 1 || M > VISTAF_MATCH_MAX_ROWS) return "M must be 1..2048";
@@ -536,11 +530,8 @@ int vistaf_match_build_bank(const float *templates, const int32_t *klass, const 
 
 int vistaf_match_workspace_bytes(int h, int w, int max_batch, int max_contacts, int P, int max_shift, int M, size_t *bytes)
 {
-    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
-    *bytes = 0;
-    if (const char *why = match_sizes_refusal(h, w, max_batch, "max_batch must be 1..2^19", max_contacts, P, max_shift, M)) return set_error(VISTAF_E_INVALID, why);
-    *bytes = match_scratch_bytes(max_batch, max_contacts, max_shift, M);
-    return 0;
+    return workspace_bytes_answer(bytes, match_sizes_refusal(h, w, max_batch, "max_batch must be 1..2^19", max_contacts, P, max_shift, M),
+                                  [&] { return match_scratch_bytes(max_batch, max_contacts, max_shift, M); });
 }
 
 int vistaf_match_measure(const float *d_depth_mm, const int8_t *d_contact_index, const double *d_contacts, const int32_t *d_count,
@@ -549,16 +540,12 @@ int vistaf_match_measure(const float *d_depth_mm, const int8_t *d_contact_index,
                          double *d_matches, double *d_scores, float *d_patches, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     if (!d_depth_mm) return set_error(VISTAF_E_INVALID, "d_depth_mm is null");
-    if (!d_contact_index) return set_error(VISTAF_E_INVALID, "d_contact_index is null");
-    if (!d_contacts) return set_error(VISTAF_E_INVALID, "d_contacts is null");
-    if (!d_count) return set_error(VISTAF_E_INVALID, "d_count is null");
-    if (!d_mm_per_px) return set_error(VISTAF_E_INVALID, "d_mm_per_px is null");
+    if (const char *why = table_inputs_refusal(d_contact_index, d_contacts, d_count, d_mm_per_px)) return set_error(VISTAF_E_INVALID, why);
     if (!d_bank) return set_error(VISTAF_E_INVALID, "d_bank is null");
     if (!h_bank_header) return set_error(VISTAF_E_INVALID, "h_bank_header is null");
     if (!d_matches) return set_error(VISTAF_E_INVALID, "d_matches is null");
     if (!d_scores) return set_error(VISTAF_E_INVALID, "d_scores is null");
     if (!d_patches) return set_error(VISTAF_E_INVALID, "d_patches is null");
-    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
     // the header, by value: what the builder wrote, held against bank_bytes
     const int T = h_bank_header[1], P = h_bank_header[2], R = h_bank_header[3], M = h_bank_header[4], D = h_bank_header[5], Dp = h_bank_header[6];
     double tmpp;
@@ -578,9 +565,7 @@ int vistaf_match_measure(const float *d_depth_mm, const int8_t *d_contact_index,
         return set_error(VISTAF_E_INVALID, "d_contacts, d_mm_per_px, d_bank, d_matches and d_scores must be 8-byte aligned");
     if (((uintptr_t)d_depth_mm | (uintptr_t)d_count | (uintptr_t)d_patches) & 3)
         return set_error(VISTAF_E_INVALID, "d_depth_mm, d_count and d_patches must be 4-byte aligned");
-    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
-    if (workspace_bytes < match_scratch_bytes(batch, max_contacts, max_shift, M))
-        return set_error(VISTAF_E_INVALID, "workspace_bytes is below what vistaf_match_workspace_bytes gives for these sizes");
+    TRY(workspace_ok(d_workspace, workspace_bytes, match_scratch_bytes(batch, max_contacts, max_shift, M), "vistaf_match_workspace_bytes"));
     const int rows = batch * max_contacts, rtiles = (M + 15) / 16;
     if ((long long)rows * rtiles > 0x7fffffffll) return set_error(VISTAF_E_INVALID, "batch * max_contacts * ceil(M / 16) must be below 2^31");
     ScratchLayout S(d_workspace);

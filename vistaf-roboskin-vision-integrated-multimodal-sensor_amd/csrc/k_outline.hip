@@ -100,26 +100,6 @@ struct OlRow {
     }
 };
 
-// exclusive prefix sum over the workgroup's threads and the total; wtot: OL_NW ints of LDS.  Every thread calls it
-__device__ inline int ol_block_excl_scan(int v, int *wtot, int &total)
-{
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int wt;
-    const int ex = wave_excl_scan(v, wt);
-    __syncthreads();
-    if (lane == 0) wtot[wid] = wt;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int q = 0; q < OL_NW; q++) {
-        const int t = wtot[q];
-        pre += q < wid ? t : 0;
-        tot += t;
-    }
-    total = tot;
-    return pre + ex;
-}
-
 __device__ inline long long ol_cross(int ox, int oy, int ax, int ay, int bx, int by)
 {
     return (long long)(ax - ox) * (by - oy) - (long long)(ay - oy) * (bx - ox);
@@ -195,7 +175,7 @@ __global__ __launch_bounds__(OL_NT) void k_outline_rank(const int8_t *__restrict
     // ---- the slot of every pixel's first edge, thread-major (the threads' edge counts are k_outline_count's: the same walk), and every edge's
     // start vertex, direction and key
     int total;
-    int at = seg + ol_block_excl_scan(bf.tcnt[(size_t)blockIdx.x * OL_NT + tid], wtot, total);
+    int at = seg + block_excl_scan<OL_NW>(bf.tcnt[(size_t)blockIdx.x * OL_NT + tid], wtot, total);
     int rounds = 0;
     while ((1 << rounds) < E) rounds++;
     const OlJump j0(bf.jump[0], b, P);
@@ -439,16 +419,8 @@ __global__ __launch_bounds__(OL_NT) void k_outline_poly(const int32_t *__restric
     __shared__ int wtot[OL_NW];
     const int b = blockIdx.x / K, k = blockIdx.x - b * K, tid = threadIdx.x;
     const int kk = clamp_count(count[b], K);
-    // the capacity rule: the rows before k that were written, and whether k is (the totals only grow, so the rows up to k pass together)
-    long long cum = 0;
-    int before = 0, corners = 0;
-    for (int j = 0; j <= k && j < kk; j++) {
-        const int c = (int)outlines[((size_t)b * K + j) * VISTAF_NOUTLINE + VISTAF_OUTLINE_CORNERS];
-        cum += c;
-        if (j < k && cum <= max_vertices) before = (int)cum;
-        if (j == k) corners = c;
-    }
-    const int written = k < kk && cum <= max_vertices ? corners : 0;
+    const RowCapacity cap = row_capacity(outlines, VISTAF_NOUTLINE, VISTAF_OUTLINE_CORNERS, b, K, k, kk, max_vertices);
+    const int before = cap.before, written = cap.written;
     if (tid == 0) {
         if (k == 0) offsets[(size_t)b * (K + 1)] = 0;
         offsets[(size_t)b * (K + 1) + k + 1] = before + written;
@@ -478,7 +450,7 @@ __global__ __launch_bounds__(OL_NT) void k_outline_poly(const int32_t *__restric
         const int q = base + tid;
         const uint32_t v = q < L ? slot[q] : 0xffffffffu;
         int total;
-        const int at = done + ol_block_excl_scan(v != 0xffffffffu ? 1 : 0, wtot, total);
+        const int at = done + block_excl_scan<OL_NW>(v != 0xffffffffu ? 1 : 0, wtot, total);
         if (v != 0xffffffffu) {
             dst[2 * at] = ol_x(v);
             dst[2 * at + 1] = ol_y(v);
@@ -493,53 +465,30 @@ namespace vf {
 
 size_t outline_scratch_bytes(int B, int h, int w, int K, ScratchRec *rec)
 {
-    ScratchLayout L(nullptr, rec);
-    outline_scratch(L, B, h, w, K);
-    return L.bytes();
+    return scratch_bytes([&](ScratchLayout &L) { return outline_scratch(L, B, h, w, K); }, rec);
 }
 
 }  // namespace vf
-
-// the size checks both functions share: the text of the refusal, or null
-static const char *outline_sizes_refusal(int h, int w, int batch, int max_contacts)
-{
-    if (h < 1 || h > 32767) return "h must be 1..32767";
-    if (w < 1 || w > 32767) return "w must be 1..32767";
-    if ((long long)h * w > 0x1fffffffll) return "h * w must be below 2^29";
-    if (batch < 1 || batch > (1 << 24)) return "batch must be 1..2^24";
-    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
-    return nullptr;
-}
 
 extern "C" {
 
 int vistaf_outline_workspace_bytes(int h, int w, int batch, int max_contacts, size_t *bytes)
 {
-    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
-    *bytes = 0;
-    if (const char *why = outline_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
-    *bytes = outline_scratch_bytes(batch, h, w, max_contacts, nullptr);
-    return 0;
+    return workspace_bytes_answer(bytes, plane_sizes_refusal(h, w, batch, max_contacts), [&] { return outline_scratch_bytes(batch, h, w, max_contacts, nullptr); });
 }
 
 int vistaf_outline_measure(const int8_t *d_contact_index, const double *d_contacts, const int32_t *d_count, const double *d_mm_per_px, int batch,
                            int h, int w, int max_contacts, int max_vertices, double *d_outlines, int32_t *d_vertices, int32_t *d_offsets,
                            void *d_workspace, size_t workspace_bytes, void *stream)
 {
-    if (!d_contact_index) return set_error(VISTAF_E_INVALID, "d_contact_index is null");
-    if (!d_contacts) return set_error(VISTAF_E_INVALID, "d_contacts is null");
-    if (!d_count) return set_error(VISTAF_E_INVALID, "d_count is null");
-    if (!d_mm_per_px) return set_error(VISTAF_E_INVALID, "d_mm_per_px is null");
+    if (const char *why = table_inputs_refusal(d_contact_index, d_contacts, d_count, d_mm_per_px)) return set_error(VISTAF_E_INVALID, why);
     if (!d_outlines) return set_error(VISTAF_E_INVALID, "d_outlines is null");
-    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
-    if (const char *why = outline_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
+    if (const char *why = plane_sizes_refusal(h, w, batch, max_contacts)) return set_error(VISTAF_E_INVALID, why);
     if (max_vertices < 0) return set_error(VISTAF_E_INVALID, "max_vertices must be >= 0");
     if (!d_vertices && d_offsets) return set_error(VISTAF_E_INVALID, "d_vertices is null although d_offsets is given");
     if (((uintptr_t)d_contacts | (uintptr_t)d_mm_per_px | (uintptr_t)d_outlines) & 7) return set_error(VISTAF_E_INVALID, "d_contacts, d_mm_per_px and d_outlines must be 8-byte aligned");
     if (((uintptr_t)d_count | (uintptr_t)d_vertices | (uintptr_t)d_offsets) & 3) return set_error(VISTAF_E_INVALID, "d_count, d_vertices and d_offsets must be 4-byte aligned");
-    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
-    if (workspace_bytes < outline_scratch_bytes(batch, h, w, max_contacts, nullptr))
-        return set_error(VISTAF_E_INVALID, "workspace_bytes is below what vistaf_outline_workspace_bytes gives for these sizes");
+    TRY(workspace_ok(d_workspace, workspace_bytes, outline_scratch_bytes(batch, h, w, max_contacts, nullptr), "vistaf_outline_workspace_bytes"));
     ScratchLayout L(d_workspace);
     const OutlineBufs bf = outline_scratch(L, batch, h, w, max_contacts);
     const dim3 grid((unsigned)(batch * max_contacts)), block(OL_NT);

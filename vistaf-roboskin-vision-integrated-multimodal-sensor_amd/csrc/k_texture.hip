@@ -515,9 +515,7 @@ namespace vf {
 
 size_t texture_scratch_bytes(int B, int K, int L, ScratchRec *rec)
 {
-    ScratchLayout S(nullptr, rec);
-    texture_scratch(S, B, K, L);
-    return S.bytes();
+    return scratch_bytes([&](ScratchLayout &S) { return texture_scratch(S, B, K, L); }, rec);
 }
 
 }  // namespace vf
@@ -525,11 +523,7 @@ size_t texture_scratch_bytes(int B, int K, int L, ScratchRec *rec)
 // the size checks both functions share: the text of the refusal, or null
 static const char *texture_sizes_refusal(int h, int w, int batch, const char *batch_text, int max_contacts, int max_lag)
 {
-    if (h < 1) return "h must be >= 1";
-    if (w < 1) return "w must be >= 1";
-    if ((long long)h * w > 0x7fffffffll) return "h * w must be below 2^31";
-    if (batch < 1 || batch > (1 << 19)) return batch_text;
-    if (max_contacts < 1 || max_contacts > VISTAF_MAX_CONTACTS) return "max_contacts must be 1..64";
+    if (const char *why = depth_sizes_refusal(h, w, batch, batch_text, max_contacts)) return why;
     if (max_lag < VISTAF_TEXTURE_MIN_LAG || max_lag > VISTAF_TEXTURE_MAX_LAG) return "max_lag must be 2..31";
     return nullptr;
 }
@@ -538,11 +532,8 @@ extern "C" {
 
 int vistaf_texture_workspace_bytes(int h, int w, int max_batch, int max_contacts, int max_lag, size_t *bytes)
 {
-    if (!bytes) return set_error(VISTAF_E_INVALID, "bytes is null");
-    *bytes = 0;
-    if (const char *why = texture_sizes_refusal(h, w, max_batch, "max_batch must be 1..2^19", max_contacts, max_lag)) return set_error(VISTAF_E_INVALID, why);
-    *bytes = texture_scratch_bytes(max_batch, max_contacts, max_lag, nullptr);
-    return 0;
+    return workspace_bytes_answer(bytes, texture_sizes_refusal(h, w, max_batch, "max_batch must be 1..2^19", max_contacts, max_lag),
+                                  [&] { return texture_scratch_bytes(max_batch, max_contacts, max_lag, nullptr); });
 }
 
 int vistaf_texture_measure(const float *d_depth_mm, const int8_t *d_contact_index, const double *d_contacts, const int32_t *d_count,
@@ -551,14 +542,10 @@ int vistaf_texture_measure(const float *d_depth_mm, const int8_t *d_contact_inde
                            float *d_residual_mm, double *d_acf, void *d_workspace, size_t workspace_bytes, void *stream)
 {
     if (!d_depth_mm) return set_error(VISTAF_E_INVALID, "d_depth_mm is null");
-    if (!d_contact_index) return set_error(VISTAF_E_INVALID, "d_contact_index is null");
-    if (!d_contacts) return set_error(VISTAF_E_INVALID, "d_contacts is null");
-    if (!d_count) return set_error(VISTAF_E_INVALID, "d_count is null");
-    if (!d_mm_per_px) return set_error(VISTAF_E_INVALID, "d_mm_per_px is null");
+    if (const char *why = table_inputs_refusal(d_contact_index, d_contacts, d_count, d_mm_per_px)) return set_error(VISTAF_E_INVALID, why);
     if (!d_textures) return set_error(VISTAF_E_INVALID, "d_textures is null");
     if (!d_residual_mm) return set_error(VISTAF_E_INVALID, "d_residual_mm is null");
     if (!d_acf) return set_error(VISTAF_E_INVALID, "d_acf is null");
-    if (!d_workspace) return set_error(VISTAF_E_INVALID, "d_workspace is null");
     if (const char *why = texture_sizes_refusal(h, w, batch, "batch must be 1..2^19", max_contacts, max_lag)) return set_error(VISTAF_E_INVALID, why);
     if (!std::isfinite(depth_eps_mm)) return set_error(VISTAF_E_INVALID, "depth_eps_mm must be finite");
     if (!(eval_min_fraction >= 0.0) || !(eval_min_fraction < 1.0)) return set_error(VISTAF_E_INVALID, "eval_min_fraction must be in [0, 1)");
@@ -569,9 +556,7 @@ int vistaf_texture_measure(const float *d_depth_mm, const int8_t *d_contact_inde
         return set_error(VISTAF_E_INVALID, "d_contacts, d_mm_per_px, d_textures and d_acf must be 8-byte aligned");
     if (((uintptr_t)d_depth_mm | (uintptr_t)d_count | (uintptr_t)d_residual_mm) & 3)
         return set_error(VISTAF_E_INVALID, "d_depth_mm, d_count and d_residual_mm must be 4-byte aligned");
-    if ((uintptr_t)d_workspace & 255) return set_error(VISTAF_E_INVALID, "d_workspace must be 256-byte aligned");
-    if (workspace_bytes < texture_scratch_bytes(batch, max_contacts, max_lag, nullptr))
-        return set_error(VISTAF_E_INVALID, "workspace_bytes is below what vistaf_texture_workspace_bytes gives for these sizes");
+    TRY(workspace_ok(d_workspace, workspace_bytes, texture_scratch_bytes(batch, max_contacts, max_lag, nullptr), "vistaf_texture_workspace_bytes"));
     ScratchLayout S(d_workspace);
     const TextureBufs bf = texture_scratch(S, batch, max_contacts, max_lag);
     const int rows = batch * max_contacts;

@@ -313,6 +313,13 @@ class FtpSensor(Handle):
         self._readouts[name] = (key, readout)
         return readout
 
+    def _table_and(self, name: str, key: tuple, make):
+        """The contacts dict of the last predict for key[0] rows, with the index plane, and the session's read-out `name` built with the
+        parameters `key`: the live one, else make() -- called after the table is read, so a session without a predict builds nothing."""
+        live = self._matching(name, key)
+        out = self.contacts(key[0], index_plane=True)
+        return out, live if live is not None else self._keep(name, key, make())
+
     def _live(self, name: str):
         live = getattr(self, "_readouts", {}).get(name)
         return live and live[1]
@@ -436,10 +443,7 @@ class FtpSensor(Handle):
         ellipse, boundary pixels, apex, curvatures and radii of the fitted cap, residual)."""
         from .shapes import ContactShapes
         k, frac = int(max_contacts), float(fit_min_fraction)
-        sh = self._matching("shapes", (k, frac))
-        out = self.contacts(k, index_plane=True)
-        if sh is None:
-            sh = self._keep("shapes", (k, frac), ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device))
+        out, sh = self._table_and("shapes", (k, frac), lambda: ContactShapes(self.h, self.w, self.max_batch, k, frac, device=self.device))
         out["shapes"] = sh.measure(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
                                    self.config.depth_eps_mm)
         return out
@@ -453,10 +457,7 @@ class FtpSensor(Handle):
         frame, by default 4 * (h + w) (`outline.default_max_vertices`); rows that do not fit show corners_written < corners; 0: no polylines."""
         from .outline import OutlineWorkspace, contact_outlines
         k = int(max_contacts)
-        ws = self._matching("outlines", (k,))
-        out = self.contacts(k, index_plane=True)
-        if ws is None:
-            ws = self._keep("outlines", (k,), OutlineWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out, ws = self._table_and("outlines", (k,), lambda: OutlineWorkspace(self.h, self.w, self.max_batch, k, self.device))
         out.update(contact_outlines(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), max_vertices, ws))
         return out
 
@@ -472,10 +473,7 @@ class FtpSensor(Handle):
         if unknown:
             raise TypeError(f"textures() got unexpected keyword arguments {sorted(unknown)}")
         k, lag = int(max_contacts), int(params.get("max_lag", 8))
-        ws = self._matching("textures", (k, lag))
-        out = self.contacts(k, index_plane=True)
-        if ws is None:
-            ws = self._keep("textures", (k, lag), TextureWorkspace(self.h, self.w, self.max_batch, k, lag, self.device))
+        out, ws = self._table_and("textures", (k, lag), lambda: TextureWorkspace(self.h, self.w, self.max_batch, k, lag, self.device))
         out.update(contact_textures(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
                                     self.config.depth_eps_mm, ws, **params))
         return out
@@ -494,11 +492,7 @@ class FtpSensor(Handle):
         if not isinstance(bank, TemplateBank):
             raise TypeError("bank must be a match.TemplateBank")
         k, m = int(max_contacts), int(params.get("max_shift", 3))
-        key = (k, bank.P, m, bank.M)
-        ws = self._matching("matches", key)
-        out = self.contacts(k, index_plane=True)
-        if ws is None:
-            ws = self._keep("matches", key, MatchWorkspace(self.h, self.w, self.max_batch, k, bank.P, m, bank.M, self.device))
+        out, ws = self._table_and("matches", (k, bank.P, m, bank.M), lambda: MatchWorkspace(self.h, self.w, self.max_batch, k, bank.P, m, bank.M, self.device))
         out.update(contact_matches(self._last_out["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"),
                                    self.config.depth_eps_mm, bank, ws, **params))
         return out
@@ -517,10 +511,7 @@ class FtpSensor(Handle):
         if unknown:
             raise TypeError(f"centrelines() got unexpected keyword arguments {sorted(unknown)}")
         k = int(max_contacts)
-        ws = self._matching("centrelines", (k,))
-        out = self.contacts(k, index_plane=True)
-        if ws is None:
-            ws = self._keep("centrelines", (k,), CentrelineWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out, ws = self._table_and("centrelines", (k,), lambda: CentrelineWorkspace(self.h, self.w, self.max_batch, k, self.device))
         out.update(contact_centrelines(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), self._last_out["height_map_mm"],
                                        max_stations=max_stations, workspace=ws, **params))
         return out
@@ -539,10 +530,7 @@ class FtpSensor(Handle):
         split_parent [B,K,2] i32."""
         from .lobes import DEFAULT_MIN_PROMINENCE_FRAC, DEFAULT_MIN_PROMINENCE_MM, LobesWorkspace, contact_lobes
         k = int(max_contacts)
-        ws = self._matching("lobes", (k,))
-        out = self.contacts(k, index_plane=True)
-        if ws is None:
-            ws = self._keep("lobes", (k,), LobesWorkspace(self.h, self.w, self.max_batch, k, self.device))
+        out, ws = self._table_and("lobes", (k,), lambda: LobesWorkspace(self.h, self.w, self.max_batch, k, self.device))
         out.update(contact_lobes(out["contact_index"], out["contacts"], out["count"], self._scalar("mm_per_px"), self._last_out["height_map_mm"],
                                  max_lobes=max_lobes, min_prominence_mm=DEFAULT_MIN_PROMINENCE_MM if min_prominence_mm is None else min_prominence_mm,
                                  min_prominence_frac=DEFAULT_MIN_PROMINENCE_FRAC if min_prominence_frac is None else min_prominence_frac,
@@ -573,11 +561,9 @@ class FtpSensor(Handle):
         Returns the contacts dict plus thermal [B,K,16] f64 (fields THERMAL_NAMES) and thermal_frame [B,8] f64 (fields THERMAL_FRAME_NAMES)."""
         from .thermal import ThermalReadout
         k, margin = int(max_contacts), int(surround_margin_px)
-        th = self._matching("thermal", (k, margin))
-        out = self.contacts(k, index_plane=True)
-        if th is None:                                     # measure needs the crop's size only; the photograph's is register's business
-            th = self._keep("thermal", (k, margin), ThermalReadout(self.h, self.w, max(self.h, 2), max(self.w, 2), (0, 0), False, self.max_batch, k,
-                                                                  margin, device=self.device))
+        # measure needs the crop's size only; the photograph's is register's business
+        out, th = self._table_and("thermal", (k, margin), lambda: ThermalReadout(self.h, self.w, max(self.h, 2), max(self.w, 2), (0, 0), False, self.max_batch,
+                                                                                 k, margin, device=self.device))
         last = self._last_out
         r = th.measure(temperature_crop, last["height_map_mm"], out["contact_index"], out["contacts"], out["count"], self.config.depth_eps_mm,
                        status=last["status"])

@@ -13,13 +13,14 @@ measured on this sensor; `min_prominence_frac` exists so that one setting serves
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Any, Dict, Optional
 
 import torch
 
 from . import _lib
 from ._handle import call, stream
+from ._workspace import Workspace, table_inputs
+from ._workspace import workspace_bytes as _workspace_bytes
 
 LOBE_NAMES = _lib.LOBE_NAMES
 LOBE_ROW_NAMES = _lib.LOBE_ROW_NAMES
@@ -30,30 +31,17 @@ DEFAULT_MIN_PROMINENCE_MM, DEFAULT_MIN_PROMINENCE_FRAC = 0.02, 0.10
 def workspace_bytes(h: int, w: int, batch: int, max_contacts: int) -> int:
     """the bytes of the workspace `contact_lobes` needs for `batch` frames of h x w and tables of max_contacts rows; ValueError for sizes the
     read-out does not take.  Needs no device."""
-    n = ctypes.c_size_t()
-    call(None, "vistaf_lobes_workspace_bytes", int(h), int(w), int(batch), int(max_contacts), ctypes.byref(n))
-    return int(n.value)
+    return _workspace_bytes(LobesWorkspace._sizer, h, w, batch, max_contacts)
 
 
-class LobesWorkspace:
+class LobesWorkspace(Workspace):
     """The device memory of the read-out for up to `batch` frames of h x w and tables of max_contacts rows: one tensor, nothing of the
     library's.  `close()` drops it."""
 
+    _sizer = "vistaf_lobes_workspace_bytes"
+
     def __init__(self, h: int, w: int, batch: int, max_contacts: int = 8, device="cuda:0"):
-        self.h, self.w, self.batch, self.max_contacts = int(h), int(w), int(batch), int(max_contacts)
-        self.device = torch.device(device)
-        self.nbytes = workspace_bytes(self.h, self.w, self.batch, self.max_contacts)
-        self.buffer: Optional[torch.Tensor] = torch.empty((self.nbytes + 255,), dtype=torch.uint8, device=self.device)
-
-    def fits(self, h: int, w: int, batch: int, max_contacts: int) -> bool:
-        return self.buffer is not None and (self.h, self.w, self.max_contacts) == (int(h), int(w), int(max_contacts)) and int(batch) <= self.batch
-
-    def pointer(self) -> int:
-        """the first 256-byte aligned address of the buffer"""
-        return (self.buffer.data_ptr() + 255) & ~255
-
-    def close(self):
-        self.buffer = None
+        super().__init__(device, h, w, batch, max_contacts)
 
 
 def contact_lobes(contact_index, contacts, count, mm_per_px, depth_mm, max_lobes: int = 4, min_prominence_mm: float = DEFAULT_MIN_PROMINENCE_MM,
@@ -68,30 +56,14 @@ def contact_lobes(contact_index, contacts, count, mm_per_px, depth_mm, max_lobes
     a touch of its own when its prominence exceeds max(min_prominence_mm, min_prominence_frac * the contact's greatest depth) (the module
     docstring on the defaults); depth_eps_mm: the session's, for contact_pixels and the sums.  workspace: a LobesWorkspace that fits, else
     one is made for the call."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("contact_lobes needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-    idx = torch.as_tensor(contact_index)
-    dev = idx.device if idx.is_cuda else torch.device(device)
-    idx = idx.to(dev, torch.int8).contiguous()
-    if idx.dim() != 3:
-        raise ValueError("contact_index must be [B,h,w]")
-    b, h, w = (int(v) for v in idx.shape)
-    tab = torch.as_tensor(contacts).to(dev, torch.float64).contiguous()
-    if tab.dim() != 3 or tab.shape[0] != b or tab.shape[2] != _lib.NCONTACT or not 1 <= tab.shape[1] <= _lib.MAX_CONTACTS:
-        raise ValueError(f"contacts must be [B,K,{_lib.NCONTACT}] with K in 1..{_lib.MAX_CONTACTS} for the B frames of contact_index")
-    k = int(tab.shape[1])
-    cnt, mpp = torch.as_tensor(count).to(dev, torch.int32).contiguous(), torch.as_tensor(mm_per_px).to(dev, torch.float64).contiguous()
-    if tuple(cnt.shape) != (b,) or tuple(mpp.shape) != (b,):
-        raise ValueError("count and mm_per_px must be [B] for the B frames of contact_index")
-    if depth_mm is None:
+    dev, idx, tab, cnt, mpp, dep, b, h, w, k = table_inputs("contact_lobes", contact_index, contacts, count, mm_per_px, device, depth_mm,
+                                                            "depth_mm must be [B,h,w] like contact_index")
+    if dep is None:
         raise ValueError("depth_mm is required: the lobes are those of the depth relief")
-    dep = torch.as_tensor(depth_mm).to(dev, torch.float32).contiguous()
-    if tuple(dep.shape) != (b, h, w):
-        raise ValueError("depth_mm must be [B,h,w] like contact_index")
     n = int(max_lobes)
     if not 1 <= n <= _lib.LOBES_MAX:
         raise ValueError(f"max_lobes must be 1..{_lib.LOBES_MAX}")
-    ws = workspace if workspace is not None and workspace.fits(h, w, b, k) and workspace.device == dev else LobesWorkspace(h, w, b, k, dev)
+    ws = LobesWorkspace.fitting(workspace, dev, h, w, b, k)
     res = {"lobes": torch.empty((b, k, n, _lib.NLOBE), dtype=torch.float64, device=dev),
            "lobe_rows": torch.empty((b, k, _lib.NLOBEROW), dtype=torch.float64, device=dev)}
     if lobe_index:

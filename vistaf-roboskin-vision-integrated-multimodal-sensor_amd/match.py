@@ -19,6 +19,8 @@ import torch
 
 from . import _lib
 from ._handle import call, stream
+from ._workspace import Workspace, table_inputs
+from ._workspace import workspace_bytes as _workspace_bytes
 
 MATCH_NAMES = _lib.MATCH_NAMES
 MATCH_STATUS = _lib.MATCH_STATUS
@@ -44,9 +46,7 @@ def bank_bytes(T: int, P: int, R: int, symmetry) -> int:
 def workspace_bytes(h: int, w: int, max_batch: int, max_contacts: int, P: int, max_shift: int, M: int) -> int:
     """the bytes of the workspace `contact_matches` needs for up to max_batch frames of h x w, tables of max_contacts rows, a bank of M rows
     of P x P templates and shifts up to max_shift; ValueError for sizes the read-out does not take.  Needs no device."""
-    n = ctypes.c_size_t()
-    call(None, "vistaf_match_workspace_bytes", int(h), int(w), int(max_batch), int(max_contacts), int(P), int(max_shift), int(M), ctypes.byref(n))
-    return int(n.value)
+    return _workspace_bytes(MatchWorkspace._sizer, h, w, max_batch, max_contacts, P, max_shift, M)
 
 
 class TemplateBank:
@@ -107,26 +107,14 @@ class TemplateBank:
         return self._device[key]
 
 
-class MatchWorkspace:
+class MatchWorkspace(Workspace):
     """The device memory of the read-out for up to `batch` frames of h x w, tables of max_contacts rows, a bank of M rows of P x P templates
     and shifts up to max_shift: one tensor, nothing of the library's.  `close()` drops it."""
 
+    _sizer = "vistaf_match_workspace_bytes"
+
     def __init__(self, h: int, w: int, batch: int, max_contacts: int, P: int, max_shift: int, M: int, device="cuda:0"):
-        self.key = (int(h), int(w), int(max_contacts), int(P), int(max_shift), int(M))
-        self.batch = int(batch)
-        self.device = torch.device(device)
-        self.nbytes = workspace_bytes(int(h), int(w), self.batch, int(max_contacts), int(P), int(max_shift), int(M))
-        self.buffer: Optional[torch.Tensor] = torch.empty((self.nbytes + 255,), dtype=torch.uint8, device=self.device)
-
-    def fits(self, h: int, w: int, batch: int, max_contacts: int, P: int, max_shift: int, M: int) -> bool:
-        return self.buffer is not None and self.key == (int(h), int(w), int(max_contacts), int(P), int(max_shift), int(M)) and int(batch) <= self.batch
-
-    def pointer(self) -> int:
-        """the first 256-byte aligned address of the buffer"""
-        return (self.buffer.data_ptr() + 255) & ~255
-
-    def close(self):
-        self.buffer = None
+        super().__init__(device, h, w, batch, max_contacts, P, max_shift, M)
 
 
 def contact_matches(depth, contact_index, contacts, count, mm_per_px, eps: float, bank: TemplateBank, ws: Optional[MatchWorkspace] = None,
@@ -140,30 +128,14 @@ def contact_matches(depth, contact_index, contacts, count, mm_per_px, eps: float
     device tensors: matches [B,K,24] f64 (fields MATCH_NAMES, unused rows NaN), scores [B,K,T] f64 (per template its best score) and patches
     [B,K,S,S] f32, S = P + 2m (the metric crop about each contact that was matched).  ws: a MatchWorkspace that fits, else one is made for
     the call."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("contact_matches needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
+    dev, idx, tab, cnt, mpp, dep, b, h, w, k = table_inputs("contact_matches", contact_index, contacts, count, mm_per_px, device, depth,
+                                                            "depth must be [B,h,w] as contact_index")
     if not isinstance(bank, TemplateBank):
         raise TypeError("bank must be a TemplateBank")
-    idx = torch.as_tensor(contact_index)
-    dev = idx.device if idx.is_cuda else torch.device(device)
-    idx = idx.to(dev, torch.int8).contiguous()
-    if idx.dim() != 3:
-        raise ValueError("contact_index must be [B,h,w]")
-    b, h, w = (int(v) for v in idx.shape)
-    dep = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
-    if tuple(dep.shape) != (b, h, w):
-        raise ValueError("depth must be [B,h,w] as contact_index")
-    tab = torch.as_tensor(contacts).to(dev, torch.float64).contiguous()
-    if tab.dim() != 3 or tab.shape[0] != b or tab.shape[2] != _lib.NCONTACT or not 1 <= tab.shape[1] <= _lib.MAX_CONTACTS:
-        raise ValueError(f"contacts must be [B,K,{_lib.NCONTACT}] with K in 1..{_lib.MAX_CONTACTS} for the B frames of contact_index")
-    k, m = int(tab.shape[1]), int(max_shift)
-    cnt, mpp = torch.as_tensor(count).to(dev, torch.int32).contiguous(), torch.as_tensor(mm_per_px).to(dev, torch.float64).contiguous()
-    if tuple(cnt.shape) != (b,) or tuple(mpp.shape) != (b,):
-        raise ValueError("count and mm_per_px must be [B] for the B frames of contact_index")
+    m = int(max_shift)
     if not 0 <= m <= _lib.MATCH_MAX_SHIFT:
         raise ValueError(f"max_shift must be 0..{_lib.MATCH_MAX_SHIFT}")
-    size = (h, w, b, k, bank.P, m, bank.M)
-    work = ws if ws is not None and ws.fits(*size) and ws.device == dev else MatchWorkspace(*size, dev)
+    work = MatchWorkspace.fitting(ws, dev, h, w, b, k, bank.P, m, bank.M)
     s = bank.P + 2 * m
     res = {"matches": torch.empty((b, k, _lib.NMATCH), dtype=torch.float64, device=dev),
            "scores": torch.empty((b, k, bank.T), dtype=torch.float64, device=dev),

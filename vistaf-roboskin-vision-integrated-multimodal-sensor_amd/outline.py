@@ -8,13 +8,14 @@ PyTorch is used only for device memory and streams.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Any, Dict, Optional
 
 import torch
 
 from . import _lib
 from ._handle import call, stream
+from ._workspace import Workspace, table_inputs
+from ._workspace import workspace_bytes as _workspace_bytes
 
 OUTLINE_NAMES = _lib.OUTLINE_NAMES
 
@@ -22,9 +23,7 @@ OUTLINE_NAMES = _lib.OUTLINE_NAMES
 def workspace_bytes(h: int, w: int, batch: int, max_contacts: int) -> int:
     """the bytes of the workspace `contact_outlines` needs for `batch` frames of h x w and tables of max_contacts rows; ValueError for sizes
     the read-out does not take.  Needs no device."""
-    n = ctypes.c_size_t()
-    call(None, "vistaf_outline_workspace_bytes", int(h), int(w), int(batch), int(max_contacts), ctypes.byref(n))
-    return int(n.value)
+    return _workspace_bytes(OutlineWorkspace._sizer, h, w, batch, max_contacts)
 
 
 def default_max_vertices(h: int, w: int) -> int:
@@ -32,25 +31,14 @@ def default_max_vertices(h: int, w: int) -> int:
     return 4 * (int(h) + int(w))
 
 
-class OutlineWorkspace:
+class OutlineWorkspace(Workspace):
     """The device memory of the read-out for up to `batch` frames of h x w and tables of max_contacts rows: one tensor, nothing of the
     library's.  `close()` drops it."""
 
+    _sizer = "vistaf_outline_workspace_bytes"
+
     def __init__(self, h: int, w: int, batch: int, max_contacts: int = 8, device="cuda:0"):
-        self.h, self.w, self.batch, self.max_contacts = int(h), int(w), int(batch), int(max_contacts)
-        self.device = torch.device(device)
-        self.nbytes = workspace_bytes(self.h, self.w, self.batch, self.max_contacts)
-        self.buffer: Optional[torch.Tensor] = torch.empty((self.nbytes + 255,), dtype=torch.uint8, device=self.device)
-
-    def fits(self, h: int, w: int, batch: int, max_contacts: int) -> bool:
-        return self.buffer is not None and (self.h, self.w, self.max_contacts) == (int(h), int(w), int(max_contacts)) and int(batch) <= self.batch
-
-    def pointer(self) -> int:
-        """the first 256-byte aligned address of the buffer"""
-        return (self.buffer.data_ptr() + 255) & ~255
-
-    def close(self):
-        self.buffer = None
+        super().__init__(device, h, w, batch, max_contacts)
 
 
 def contact_outlines(contact_index, contacts, count, mm_per_px, max_vertices: Optional[int] = None, workspace: Optional[OutlineWorkspace] = None,
@@ -61,25 +49,11 @@ def contact_outlines(contact_index, contacts, count, mm_per_px, max_vertices: Op
     vertices[b, offsets[b,k]:offsets[b,k+1]]); only `outlines` with max_vertices=0.  V = max_vertices per frame, by default
     `default_max_vertices(h, w)` = 4 * (h + w); a row that does not fit, and every row after it, is left out and shows
     corners_written < corners (`trim` reports it).  workspace: an OutlineWorkspace that fits, else one is made for the call."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("contact_outlines needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-    idx = torch.as_tensor(contact_index)
-    dev = idx.device if idx.is_cuda else torch.device(device)
-    idx = idx.to(dev, torch.int8).contiguous()
-    if idx.dim() != 3:
-        raise ValueError("contact_index must be [B,h,w]")
-    b, h, w = (int(v) for v in idx.shape)
-    tab = torch.as_tensor(contacts).to(dev, torch.float64).contiguous()
-    if tab.dim() != 3 or tab.shape[0] != b or tab.shape[2] != _lib.NCONTACT or not 1 <= tab.shape[1] <= _lib.MAX_CONTACTS:
-        raise ValueError(f"contacts must be [B,K,{_lib.NCONTACT}] with K in 1..{_lib.MAX_CONTACTS} for the B frames of contact_index")
-    k = int(tab.shape[1])
-    cnt, mpp = torch.as_tensor(count).to(dev, torch.int32).contiguous(), torch.as_tensor(mm_per_px).to(dev, torch.float64).contiguous()
-    if tuple(cnt.shape) != (b,) or tuple(mpp.shape) != (b,):
-        raise ValueError("count and mm_per_px must be [B] for the B frames of contact_index")
+    dev, idx, tab, cnt, mpp, _, b, h, w, k = table_inputs("contact_outlines", contact_index, contacts, count, mm_per_px, device)
     v = default_max_vertices(h, w) if max_vertices is None else int(max_vertices)
     if v < 0:
         raise ValueError("max_vertices must be >= 0")
-    ws = workspace if workspace is not None and workspace.fits(h, w, b, k) and workspace.device == dev else OutlineWorkspace(h, w, b, k, dev)
+    ws = OutlineWorkspace.fitting(workspace, dev, h, w, b, k)
     res = {"outlines": torch.empty((b, k, _lib.NOUTLINE), dtype=torch.float64, device=dev)}
     if v > 0:
         res["vertices"] = torch.empty((b, v, 2), dtype=torch.int32, device=dev)

@@ -9,13 +9,14 @@ header.  PyTorch is used only for device memory and streams.
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Dict, Optional
 
 import torch
 
 from . import _lib
 from ._handle import call, stream
+from ._workspace import Workspace, table_inputs
+from ._workspace import workspace_bytes as _workspace_bytes
 
 TEXTURE_NAMES = _lib.TEXTURE_NAMES
 TEXTURE_FORM = _lib.TEXTURE_FORM
@@ -24,31 +25,18 @@ TEXTURE_FORM = _lib.TEXTURE_FORM
 def workspace_bytes(h: int, w: int, max_batch: int, max_contacts: int, max_lag: int) -> int:
     """the bytes of the workspace `contact_textures` needs for up to max_batch frames of h x w, tables of max_contacts rows and windows of
     max_lag; ValueError for sizes the read-out does not take.  Needs no device."""
-    n = ctypes.c_size_t()
-    call(None, "vistaf_texture_workspace_bytes", int(h), int(w), int(max_batch), int(max_contacts), int(max_lag), ctypes.byref(n))
-    return int(n.value)
+    return _workspace_bytes(TextureWorkspace._sizer, h, w, max_batch, max_contacts, max_lag)
 
 
-class TextureWorkspace:
+class TextureWorkspace(Workspace):
     """The device memory of the read-out for up to `batch` frames of h x w, tables of max_contacts rows and windows of max_lag: one tensor,
     nothing of the library's.  `close()` drops it."""
 
+    _sizer = "vistaf_texture_workspace_bytes"
+    max_lag = property(lambda self: self.key[3])
+
     def __init__(self, h: int, w: int, batch: int, max_contacts: int = 8, max_lag: int = 8, device="cuda:0"):
-        self.h, self.w, self.batch, self.max_contacts, self.max_lag = int(h), int(w), int(batch), int(max_contacts), int(max_lag)
-        self.device = torch.device(device)
-        self.nbytes = workspace_bytes(self.h, self.w, self.batch, self.max_contacts, self.max_lag)
-        self.buffer: Optional[torch.Tensor] = torch.empty((self.nbytes + 255,), dtype=torch.uint8, device=self.device)
-
-    def fits(self, h: int, w: int, batch: int, max_contacts: int, max_lag: int) -> bool:
-        return self.buffer is not None and (self.h, self.w, self.max_contacts, self.max_lag) == (int(h), int(w), int(max_contacts), int(max_lag)) and \
-            int(batch) <= self.batch
-
-    def pointer(self) -> int:
-        """the first 256-byte aligned address of the buffer"""
-        return (self.buffer.data_ptr() + 255) & ~255
-
-    def close(self):
-        self.buffer = None
+        super().__init__(device, h, w, batch, max_contacts, max_lag)
 
 
 def contact_textures(depth, contact_index, contacts, count, mm_per_px, eps: float, ws: Optional[TextureWorkspace] = None,
@@ -61,27 +49,12 @@ def contact_textures(depth, contact_index, contacts, count, mm_per_px, eps: floa
     level that bounds the central lobe; peak_min: the least autocorrelation of a pitch peak.  Returns device tensors: textures [B,K,40] f64
     (fields TEXTURE_NAMES, unused rows and fields NaN), residual [B,h,w] f32 (NaN where no residual is defined) and acf [B,K,2L+1,2L+1] f64
     (entry [dy+L][dx+L], NaN for an invalid lag).  ws: a TextureWorkspace that fits, else one is made for the call."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("contact_textures needs a HIP device (torch.cuda.is_available() is False); there is no CPU path")
-    idx = torch.as_tensor(contact_index)
-    dev = idx.device if idx.is_cuda else torch.device(device)
-    idx = idx.to(dev, torch.int8).contiguous()
-    if idx.dim() != 3:
-        raise ValueError("contact_index must be [B,h,w]")
-    b, h, w = (int(v) for v in idx.shape)
-    dep = torch.as_tensor(depth).to(dev, torch.float32).contiguous()
-    if tuple(dep.shape) != (b, h, w):
-        raise ValueError("depth must be [B,h,w] as contact_index")
-    tab = torch.as_tensor(contacts).to(dev, torch.float64).contiguous()
-    if tab.dim() != 3 or tab.shape[0] != b or tab.shape[2] != _lib.NCONTACT or not 1 <= tab.shape[1] <= _lib.MAX_CONTACTS:
-        raise ValueError(f"contacts must be [B,K,{_lib.NCONTACT}] with K in 1..{_lib.MAX_CONTACTS} for the B frames of contact_index")
-    k, lag = int(tab.shape[1]), int(max_lag)
-    cnt, mpp = torch.as_tensor(count).to(dev, torch.int32).contiguous(), torch.as_tensor(mm_per_px).to(dev, torch.float64).contiguous()
-    if tuple(cnt.shape) != (b,) or tuple(mpp.shape) != (b,):
-        raise ValueError("count and mm_per_px must be [B] for the B frames of contact_index")
+    dev, idx, tab, cnt, mpp, dep, b, h, w, k = table_inputs("contact_textures", contact_index, contacts, count, mm_per_px, device, depth,
+                                                            "depth must be [B,h,w] as contact_index")
+    lag = int(max_lag)
     if not _lib.TEXTURE_MIN_LAG <= lag <= _lib.TEXTURE_MAX_LAG:
         raise ValueError(f"max_lag must be {_lib.TEXTURE_MIN_LAG}..{_lib.TEXTURE_MAX_LAG}")
-    work = ws if ws is not None and ws.fits(h, w, b, k, lag) and ws.device == dev else TextureWorkspace(h, w, b, k, lag, dev)
+    work = TextureWorkspace.fitting(ws, dev, h, w, b, k, lag)
     d = 2 * lag + 1
     res = {"textures": torch.empty((b, k, _lib.NTEXTURE), dtype=torch.float64, device=dev),
            "residual": torch.empty((b, h, w), dtype=torch.float32, device=dev),
