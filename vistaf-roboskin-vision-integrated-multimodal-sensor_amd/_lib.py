@@ -355,9 +355,25 @@ LOBES_SIGNATURES = {
 LOBES_TEST_SIGNATURES = {
     "vistaf_ftp_test_lobes_tier": (ci, [ci, ci]),
 }
+# csrc/test_hooks_post.h: the back end of a predict (smoothing, sign flip, hole glue, composition and mm curve, blob filter, force tail, output
+# copy) on planes of the caller (tests/test_post_direct.py holds the table against that header)
+POST_SIGNATURES = {
+    "vistaf_ftp_test_smooth_reliable": (ci, [vp, vp, vp, cd, vp, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_core_flip": (ci, [vp, vp, vp, ci, ci, vp]),
+    "vistaf_ftp_test_hole_candidates": (ci, [vp, vp, vp, ci, cf, cf, vp, ci, ci, ci, vp]),
+    "vistaf_ftp_test_hole_tmp": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
+    "vistaf_ftp_test_hole_zin": (ci, [vp, vp, ci, ci, vp]),
+    "vistaf_ftp_test_hole_merge": (ci, [vp, vp, vp, vp, vp, ci, ci, vp]),
+    "vistaf_ftp_test_height_finish": (ci, [vp, vp, vp, vp, vp, vp, cf, ci, cd, ci, cd, cd, cd, ci, vp, vp, vp, vp, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_to_mm": (ci, [vp, vp, ci, cd, cd, cd, ci, vp, vp, vp, ci, ci, vp]),
+    "vistaf_ftp_test_tail": (ci, [vp, vp, vp, vp, cd, cd, cd, ci, cd, cd, cd, vp, ci, vp, ci, ci, ci, vp]),
+    "vistaf_ftp_test_backend": (ci, [vp, vp, vp, vp, vp, vp, vp, cd, cd, cd, cd, cd, ci, cd, cd, cd, vp, vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp]),
+    "vistaf_ftp_test_backend_fits": (ci, [ci, ci]),
+    "vistaf_ftp_test_frame_records": (ci, [vp, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp]),
+}
 # every table beside SIGNATURES, a sixth read-out's included: load() applies what is listed here
 EXTENSION_SIGNATURES = [MASK_CHAIN_SIGNATURES, DFT_STAGED_SIGNATURES, GAUSS_STRIP_SIGNATURES, FIT_WINDOW_SIGNATURES, OUTLINE_SIGNATURES, TEXTURE_SIGNATURES,
-                        MATCH_SIGNATURES, CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES, LOBES_SIGNATURES, LOBES_TEST_SIGNATURES]
+                        MATCH_SIGNATURES, CENTRELINE_SIGNATURES, CENTRELINE_TEST_SIGNATURES, LOBES_SIGNATURES, LOBES_TEST_SIGNATURES, POST_SIGNATURES]
 # the names of each group, for the tests that hold them against the headers
 (EXPORTS, ALIGN_EXPORTS, TEST_EXPORTS, TEMP_EXPORTS, TEMPMODEL_EXPORTS, TSENSOR_EXPORTS, TRACK_EXPORTS, SHAPE_EXPORTS, TAXEL_EXPORTS, THERMAL_EXPORTS,
  TEMPORAL_EXPORTS, CLOUD_EXPORTS, MOTION_EXPORTS, PRESSURE_EXPORTS) = (list(group) for group in SIGNATURES.values())

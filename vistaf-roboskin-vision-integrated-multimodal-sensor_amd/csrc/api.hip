@@ -21,6 +21,7 @@ using namespace vf;
 #include "test_hooks_dft.h"
 #include "test_hooks_gauss.h"
 #include "test_hooks_fit.h"
+#include "test_hooks_post.h"
 #ifdef VISTAF_DEBUG
 namespace vf { void telea_debug_dump(); void telea_window_debug_dump(int B); void telea_window_mw_debug_dump(int B); void fit_debug_dump(); void unwrap_big_debug_dump(); void unwrap_batch_debug_dump(); }
 #endif
@@ -1527,6 +1528,234 @@ int vistaf_ftp_test_dft_inverse_v(const void *patch, int patch_stride, const voi
     launch_dft_inverse((const double2 *)patch, patch_stride, (const double2 *)Gx, (const double2 *)Gy, tab_stride_x, tab_stride_y, (double2 *)Q, (double2 *)field, amp,
                        (const double2 *)cref, amp_ref, ref_stride, prod, wrapped, B, h, w, ph, pw, st, geom, staged);
     return hook_finish(geom, nullptr, st);
+}
+
+// ---- csrc/test_hooks_post.h: the back end of post_demod (smoothing, sign flip, hole glue, composition and mm curve, blob filter, force tail,
+// output copy) on caller-supplied device planes
+}  // extern "C"
+namespace {
+// the scratch planes of one hook call: all allocated before the first launch, all freed after the stream has drained
+struct HookBufs {
+    std::vector<void *> p;
+    template <typename T>
+    bool get(T **out, size_t count)
+    {
+        void *q = nullptr;
+        if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) return false;
+        p.push_back(q);
+        *out = (T *)q;
+        return true;
+    }
+    void release() { for (void *q : p) (void)hipFree(q); p.clear(); }
+    int no_memory() { release(); return fail(VISTAF_E_HIP, "hipMalloc or the upload of the taps failed"); }
+    int finish(hipStream_t st, int tier)
+    {
+        const int rc = hook_finish(nullptr, nullptr, st);
+        release();
+        return rc ? rc : tier;
+    }
+};
+bool sigma_ok(double sigma) { return sigma >= 0 && sigma <= 1e6 && gauss_ksize(sigma > 0 ? sigma : 1.0) <= 511; }
+// the session's taps for `sigma` on the device (none for sigma == 0)
+bool upload_taps(HookBufs &bufs, const std::vector<float> &f, float **taps)
+{
+    *taps = nullptr;
+    if (f.empty()) return true;
+    return bufs.get(taps, f.size()) && hipMemcpy(*taps, f.data(), f.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+}
+// B is a grid's y extent; the pixel count leaves room for the launchers' rounding up to whole workgroups in int
+bool frame_ok(int B, int h, int w) { return B >= 1 && B <= 65535 && h >= 1 && w >= 1 && (size_t)h * w <= 0x40000000ull; }
+bool curve_ok(int type, double a, double b, double c) { return type >= 0 && type <= 5 && a == a && b == b && c == c; }
+PostParams hook_post_params(double mm_per_px, double depth_eps_mm, double period_px, const Curve &force)
+{
+    PostParams pp;
+    pp.mm_per_px = mm_per_px; pp.depth_eps_mm = depth_eps_mm; pp.period_px = period_px; pp.force_curve = force;
+    return pp;
+}
+// the chain scratch of launch_tail as a session of frames of P pixels holds it: none below large_frame
+bool tail_hook_scratch(HookBufs &bufs, int B, int P, bool want, unsigned long long **scratch, size_t *bytes)
+{
+    *scratch = nullptr; *bytes = 0;
+    if (!want) return true;
+    *bytes = tail_scratch_bytes(B, P);
+    return bufs.get(scratch, *bytes / sizeof(unsigned long long));
+}
+}  // namespace
+extern "C" {
+
+int vistaf_ftp_test_smooth_reliable(const float *detr, const float *bg_med, const uint8_t *reliable, double sigma, float *hmap, int B, int h, int w,
+                                    int variant, void *stream)
+{
+    if (!detr || !bg_med || !reliable || !hmap || !frame_ok(B, h, w) || !sigma_ok(sigma)) return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    const std::vector<float> f = sigma > 0 ? gauss_taps(sigma) : std::vector<float>();
+    const int k = (int)f.size(), P = h * w;
+    const bool tile_ok = k > 0 && k <= GF_MAXK;
+    if (variant == 2 && !tile_ok) return fail(VISTAF_E_INVALID, "variant 2: the tile kernel takes 1..15 taps");
+    hipStream_t st = (hipStream_t)stream;
+    HookBufs bufs;
+    if (k == 0) {
+        launch_zeroed_keep_nan(detr, bg_med, reliable, hmap, B, P, st);
+        return bufs.finish(st, 3);
+    }
+    float *taps = nullptr;
+    if (!upload_taps(bufs, f, &taps)) return bufs.no_memory();
+    if (variant == 2 || (variant == 0 && Tiers().fused_chains && tile_ok)) {
+        launch_smooth_reliable(detr, bg_med, reliable, hmap, taps, k, B, h, w, st);
+        return bufs.finish(st, 2);
+    }
+    const size_t n = (size_t)B * P;
+    float *z0 = nullptr, *m = nullptr, *num = nullptr, *den = nullptr, *tmp = nullptr;
+    if (!bufs.get(&z0, n) || !bufs.get(&m, n) || !bufs.get(&num, n) || !bufs.get(&den, n) || !bufs.get(&tmp, n)) return bufs.no_memory();
+    launch_sub_scalar_mask(detr, bg_med, reliable, z0, m, B, P, st);
+    launch_gauss_blur(z0, tmp, num, taps, k, B, h, w, st, Tiers().gauss_strip != 0);
+    launch_gauss_blur(m, tmp, den, taps, k, B, h, w, st, Tiers().gauss_strip != 0);
+    launch_div_planes(num, den, hmap, B, P, st);
+    return bufs.finish(st, 1);
+}
+
+int vistaf_ftp_test_core_flip(float *hmap_inout, const float *core_med, int32_t *flipped, int B, int P, void *stream)
+{
+    if (!hmap_inout || !core_med || !flipped || !frame_ok(B, 1, P)) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_core_flip(hmap_inout, core_med, flipped, B, P, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_hole_candidates(const float *hmap, const uint8_t *reliable, const float *dist, int ksize, float frac_thr, float min_dist, uint8_t *cand,
+                                    int B, int h, int w, void *stream)
+{
+    if (!hmap || !reliable || !dist || !cand || !frame_ok(B, h, w) || h > 65535 || ksize < 3 || ksize > 511 || !(ksize & 1))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    launch_hole_candidates(hmap, reliable, dist, ksize, frac_thr, min_dist, cand, B, h, w, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_hole_tmp(const float *hmap, const uint8_t *reliable, const uint8_t *cand, const float *med, float *tmp, int B, int P, void *stream)
+{
+    if (!hmap || !reliable || !cand || !med || !tmp || !frame_ok(B, 1, P)) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_hole_tmp(hmap, reliable, cand, med, tmp, B, P, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+int vistaf_ftp_test_hole_zin(float *tmp_zin, const float *fill, int B, int P, void *stream)
+{
+    if (!tmp_zin || !fill || !frame_ok(B, 1, P)) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_hole_zin(tmp_zin, fill, B, P, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+int vistaf_ftp_test_hole_merge(float *hmap_inout, const uint8_t *reliable, const uint8_t *cand, const float *zin, uint8_t *out_rel, int B, int P,
+                               void *stream)
+{
+    if (!hmap_inout || !reliable || !cand || !zin || !out_rel || !frame_ok(B, 1, P)) return fail(VISTAF_E_INVALID, "bad argument");
+    launch_hole_merge(hmap_inout, reliable, cand, zin, out_rel, B, P, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_height_finish(const float *hmap, const uint8_t *reliable, const uint8_t *roi, const float *dist_in, const float *dist_out,
+                                  const float *roi_den, float band, int use_band, double sigma_unrel, int curve_type, double curve_a, double curve_b,
+                                  double curve_c, int use_neg, float *unitless, float *depth, uint8_t *cand, float *gmax, int B, int h, int w, int variant,
+                                  void *stream)
+{
+    if (!hmap || !reliable || !roi || !dist_in || !dist_out || !roi_den || !unitless || !depth || !cand || !gmax || !frame_ok(B, h, w) ||
+        !sigma_ok(sigma_unrel) || (use_band != 0 && use_band != 1) || (use_band && !(band > 0.f)) || !curve_ok(curve_type, curve_a, curve_b, curve_c))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    const std::vector<float> f = sigma_unrel > 0 ? gauss_taps(sigma_unrel) : std::vector<float>();
+    const int k = (int)f.size(), P = h * w;
+    const bool tile_ok = k > 0 && k <= GF_MAXK;
+    if (variant == 2 && !tile_ok) return fail(VISTAF_E_INVALID, "variant 2: the tile kernel takes 1..15 taps");
+    hipStream_t st = (hipStream_t)stream;
+    const Curve curve{curve_type, curve_a, curve_b, curve_c};
+    const float taper_band = use_band ? band : 1.0f;
+    HookBufs bufs;
+    float *taps = nullptr;
+    if (!upload_taps(bufs, f, &taps)) return bufs.no_memory();
+    if (variant == 2 || (variant == 0 && Tiers().fused_chains && tile_ok)) {
+        launch_compose_finalize_mm(hmap, reliable, roi, dist_in, taper_band, roi_den, dist_out, band, use_band, curve, use_neg != 0, unitless, depth, cand,
+                                   (unsigned int *)gmax, taps, k, B, h, w, st);
+        return bufs.finish(st, 2);
+    }
+    const size_t n = (size_t)B * P;
+    float *z0f = nullptr, *snum = nullptr, *tmp = nullptr;
+    if (!bufs.get(&z0f, n) || (k && (!bufs.get(&snum, n) || !bufs.get(&tmp, n)))) return bufs.no_memory();
+    launch_frontier_compose(hmap, reliable, roi, dist_in, taper_band, z0f, B, P, st);
+    if (k) launch_gauss_blur(z0f, tmp, snum, taps, k, B, h, w, st, Tiers().gauss_strip != 0);
+    launch_finalize_unitless(z0f, k ? snum : nullptr, roi_den, reliable, roi, dist_out, band, use_band, unitless, B, P, st);
+    launch_to_mm(unitless, roi, curve, use_neg != 0, depth, cand, (unsigned int *)gmax, B, P, st);
+    return bufs.finish(st, 1);
+}
+
+int vistaf_ftp_test_to_mm(const float *unitless, const uint8_t *roi, int curve_type, double curve_a, double curve_b, double curve_c, int use_neg, float *depth,
+                          uint8_t *cand, float *gmax, int B, int P, void *stream)
+{
+    if (!unitless || !roi || !depth || !cand || !gmax || !frame_ok(B, 1, P) || !curve_ok(curve_type, curve_a, curve_b, curve_c))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    launch_to_mm(unitless, roi, Curve{curve_type, curve_a, curve_b, curve_c}, use_neg != 0, depth, cand, (unsigned int *)gmax, B, P, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
+}
+
+int vistaf_ftp_test_tail(const float *height, const uint8_t *roi_frame, const float *unitless, const uint8_t *roi_static, double mm_per_px,
+                         double depth_eps_mm, double period_px, int force_type, double force_a, double force_b, double force_c, double *scalars, int nscal,
+                         double *out3, int B, int P, int variant, void *stream)
+{
+    if (!height || (!scalars && !out3) || (scalars && (!roi_static || nscal < 9)) || !frame_ok(B, 1, P) ||
+        !curve_ok(force_type, force_a, force_b, force_c))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    hipStream_t st = (hipStream_t)stream;
+    HookBufs bufs;
+    unsigned long long *scratch = nullptr;
+    size_t bytes = 0;
+    if (!tail_hook_scratch(bufs, B, P, variant == 2 || (variant == 0 && large_frame((size_t)P)), &scratch, &bytes)) return bufs.no_memory();
+    const int force = variant == 0 ? 0 : variant == 1 ? TAIL_FRAME : TAIL_BLOCKS;
+    const int tier = tail_tier(B, P, scratch != nullptr, bytes, force);
+    launch_tail(height, roi_frame, unitless, roi_static, hook_post_params(mm_per_px, depth_eps_mm, period_px, Curve{force_type, force_a, force_b, force_c}),
+                scalars, nscal, out3, B, P, st, scratch, bytes, force);
+    return bufs.finish(st, tier);
+}
+
+int vistaf_ftp_test_backend_fits(int h, int w)
+{
+    if (h < 1 || w < 1 || (size_t)h * w > 0x7fffffffull) return fail(VISTAF_E_INVALID, "bad argument");
+    return backend_fused_fits(h, w) ? 1 : 0;
+}
+
+int vistaf_ftp_test_backend(float *depth_inout, const uint8_t *cand, const float *gmax, const float *unitless, const uint8_t *roi_static,
+                            const uint8_t *reliable, const int32_t *status, double min_peak_mm, double rel_frac, double mm_per_px, double depth_eps_mm,
+                            double period_px, int force_type, double force_a, double force_b, double force_c, int32_t *labels, uint32_t *peak_bits,
+                            uint8_t *kept, double *scalars, int nscal, float *out_h, uint8_t *out_r, int B, int h, int w, int variant, void *stream)
+{
+    if (!depth_inout || !cand || !gmax || !roi_static || !reliable || !status || !labels || !peak_bits || !scalars || nscal < 9 || !frame_ok(B, h, w) ||
+        !curve_ok(force_type, force_a, force_b, force_c))
+        return fail(VISTAF_E_INVALID, "bad argument");
+    if (variant < 0 || variant > 2) return fail(VISTAF_E_INVALID, "variant must be 0, 1 or 2");
+    const bool fits = backend_fused_fits(h, w);
+    if (variant == 2 && !fits) return fail(VISTAF_E_INVALID, "variant 2: the fused back end does not take this frame size");
+    hipStream_t st = (hipStream_t)stream;
+    const int P = h * w;
+    const PostParams pp = hook_post_params(mm_per_px, depth_eps_mm, period_px, Curve{force_type, force_a, force_b, force_c});
+    HookBufs bufs;
+    if (variant == 2 || (variant == 0 && Tiers().fused_backend && fits)) {
+        launch_backend_fused(depth_inout, cand, (const unsigned int *)gmax, unitless, roi_static, reliable, status, min_peak_mm, rel_frac, pp, labels, peak_bits,
+                             kept, scalars, nscal, out_h, out_r, B, h, w, st);
+        return bufs.finish(st, 2);
+    }
+    unsigned long long *scratch = nullptr;
+    size_t bytes = 0;
+    if (!tail_hook_scratch(bufs, B, P, large_frame((size_t)P), &scratch, &bytes)) return bufs.no_memory();
+    launch_cc_label(cand, labels, B, h, w, st);
+    launch_blob_filter(depth_inout, cand, labels, peak_bits, (const unsigned int *)gmax, min_peak_mm, rel_frac, kept, B, P, st);
+    launch_tail(depth_inout, nullptr, unitless, roi_static, pp, scalars, nscal, nullptr, B, P, st, scratch, bytes);
+    launch_copy_out(depth_inout, reliable, status, out_h, out_r, B, P, st);
+    return bufs.finish(st, 1);
+}
+
+int vistaf_ftp_test_frame_records(const int *rel_count, const int *flipped, const float *amp_thr, const float *contact_thr, const float *bg_med,
+                                  const int *bad_count, double *scalars, int nscal, int32_t *status, int B, void *stream)
+{
+    if (!rel_count || (!scalars && !status) || (scalars && nscal < 16) || B < 1) return fail(VISTAF_E_INVALID, "bad argument");
+    if (scalars) launch_fill_scalars(scalars, nscal, rel_count, flipped, amp_thr, contact_thr, bg_med, bad_count, B, (hipStream_t)stream);
+    if (status) launch_mark_empty(rel_count, status, B, (hipStream_t)stream);
+    return hook_finish(nullptr, nullptr, (hipStream_t)stream);
 }
 
 int vistaf_depth_map_to_volume(const float *d_height, const uint8_t *d_roi, int batch, int h, int w, double mm_per_px,

@@ -170,7 +170,7 @@ __device__ inline void tail_frame(HeightFn height, const uint8_t *__restrict__ R
                 if (key > am) am = key;
             }
             if (rs[k] && finitef(u[k])) {          // arg-min of unitless height over roi & finite: first occurrence of the minimum
-                const unsigned long long key = ((unsigned long long)f2key(u[k]) << 32) | (unsigned int)p;
+                const unsigned long long key = argmin_key(u[k], (unsigned int)p);
                 if (key < an) an = key;
             }
         }

@@ -34,8 +34,17 @@ __host__ __device__ inline float key2f(uint32_t k)
     uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
     return __builtin_bit_cast(float, u);
 }
-// arg-max key: the larger value wins, among equal values the smaller index
-__device__ inline unsigned long long argmax_key(float v, unsigned i) { return ((unsigned long long)f2key(v) << 32) | (0xffffffffu - i); }
+// the same with -0.0 on +0.0's key: the order of ==, under which the two zeros are one value (key2f gives +0.0 back for either).  For keys
+// that carry an index behind the value: a tie between the two zeros is then decided by the index, as NumPy's argmax / argmin decide it
+__host__ __device__ inline uint32_t f2key_eq(float f)
+{
+    const uint32_t u = __builtin_bit_cast(uint32_t, f);
+    return (u << 1) == 0 ? 0x80000000u : f2key(f);
+}
+// arg-max key: the larger value wins, among equal values (-0.0 == +0.0 among them) the smaller index
+__device__ inline unsigned long long argmax_key(float v, unsigned i) { return ((unsigned long long)f2key_eq(v) << 32) | (0xffffffffu - i); }
+// arg-min key: the smaller value wins, among equal values the smaller index; ~0 is above every key
+__device__ inline unsigned long long argmin_key(float v, unsigned i) { return ((unsigned long long)f2key_eq(v) << 32) | i; }
 
 __device__ inline bool finitef(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 __device__ inline bool finitef(double v) { return ((unsigned long long)__double_as_longlong(v) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull; }

@@ -22,7 +22,8 @@ __global__ void k_zeroed_keep_nan(const float *__restrict__ detr, const float *_
     size_t b = blockIdx.y;
     if (p >= P) return;
     size_t i = b * (size_t)P + p;
-    hmap[i] = reliable[i] ? __fsub_rn(detr[i], bg_med[b]) : nanf32();
+    const float v = __fsub_rn(detr[i], bg_med[b]);
+    hmap[i] = reliable[i] && v == v ? v : nanf32();      // one NaN: the difference negates the sign bit of a NaN median
 }
 void launch_zeroed_keep_nan(const float *detr, const float *bg_med, const uint8_t *reliable, float *hmap, int B, int P, hipStream_t st)
 {

@@ -108,7 +108,8 @@ __global__ void k_core_flip(float *__restrict__ hmap, const float *__restrict__ 
     bool flip = finitef(m) && m > 0.f;
     if (p == 0) flipped[b] = flip ? 1 : 0;
     if (p >= P || !flip) return;
-    hmap[b * (size_t)P + p] = __fmul_rn(hmap[b * (size_t)P + p], -1.0f);
+    const float v = hmap[b * (size_t)P + p];
+    hmap[b * (size_t)P + p] = v == v ? __fmul_rn(v, -1.0f) : v;      // a NaN stays the NaN it is (the product would flip its sign bit)
 }
 void launch_core_flip(float *hmap, const float *core_med, int *flipped, int B, int P, hipStream_t st)
 {
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(TP_T) void k_tail_part(const float *__restrict__ he
             if (key > am) am = key;
         }
         if (rs && finitef(uu)) {
-            const unsigned long long key = ((unsigned long long)f2key(uu) << 32) | (unsigned int)p;
+            const unsigned long long key = argmin_key(uu, (unsigned int)p);
             if (key < an) an = key;
         }
     }
@@ -327,12 +328,24 @@ __global__ __launch_bounds__(TP_T) void k_tail_final(const unsigned long long *_
     }
 }
 
+size_t tail_scratch_bytes(int B, int P)
+{
+    const size_t nblk = ((size_t)P + TP_T * TP_PX - 1) / (TP_T * TP_PX);
+    return (size_t)B * nblk * TP_WORDS * 8;
+}
+int tail_tier(int B, int P, bool have_scratch, size_t scratch_bytes, int force)
+{
+    const bool room = have_scratch && tail_scratch_bytes(B, P) <= scratch_bytes;
+    if (force) return force == TAIL_BLOCKS && !room ? TAIL_FRAME : force;      // the block chain never runs without room for its records
+    return room && big_frames(B, P) ? TAIL_BLOCKS : TAIL_FRAME;
+}
 // scratch (optional): room for the per-block records of the chain above, `scratch_bytes` long; without it, or for small frames: k_tail
 void launch_tail(const float *height_mm, const uint8_t *roi_or_null, const float *unitless_or_null, const uint8_t *roi_static,
-                 PostParams pp, double *scalars, int nscal, double *out3_or_null, int B, int P, hipStream_t st, void *scratch, size_t scratch_bytes)
+                 PostParams pp, double *scalars, int nscal, double *out3_or_null, int B, int P, hipStream_t st, void *scratch, size_t scratch_bytes,
+                 int force)
 {
     const int nblk = (P + TP_T * TP_PX - 1) / (TP_T * TP_PX);
-    if (scratch && big_frames(B, P) && (size_t)B * nblk * TP_WORDS * 8 <= scratch_bytes) {
+    if (tail_tier(B, P, scratch != nullptr, scratch_bytes, force) == TAIL_BLOCKS) {
         unsigned long long *part = (unsigned long long *)scratch;
         hipLaunchKernelGGL(k_tail_part, dim3(nblk, B), dim3(TP_T), 0, st, height_mm, roi_or_null, unitless_or_null, roi_static, (float)pp.depth_eps_mm,
                            scalars != nullptr ? 1 : 0, part, P);

@@ -301,9 +301,14 @@ void launch_to_mm(const float *unitless, const uint8_t *roi, Curve curve, int us
 void launch_blob_filter(float *depth, const uint8_t *cand, const int32_t *labels, unsigned int *peak_bits,
                         const unsigned int *gmax_bits, double min_peak_mm, double rel_frac, uint8_t *kept, int B, int P,
                         hipStream_t st);
+// the kernels launch_tail starts: k_tail (one workgroup per frame) or k_tail_part + k_tail_final (big_frames, and scratch of
+// tail_scratch_bytes at hand).  force: 0 dispatch, else the tier itself (tests only; TAIL_BLOCKS without that scratch runs TAIL_FRAME)
+enum TailTier { TAIL_FRAME = 1, TAIL_BLOCKS = 2 };
+size_t tail_scratch_bytes(int B, int P);
+int tail_tier(int B, int P, bool have_scratch, size_t scratch_bytes, int force = 0);
 void launch_tail(const float *height_mm, const uint8_t *roi_or_null, const float *unitless_or_null, const uint8_t *roi_static,
                  PostParams pp, double *scalars, int nscal, double *out3_or_null, int B, int P, hipStream_t st, void *scratch = nullptr,
-                 size_t scratch_bytes = 0);
+                 size_t scratch_bytes = 0, int force = 0);
 void launch_fill_scalars(double *scalars, int nscal, const int *rel_count, const int *flipped, const float *amp_thr,
                          const float *contact_thr, const float *bg_med, const int *bad_count, int B, hipStream_t st);
 void launch_mark_empty(const int *rel_count, int32_t *status, int B, hipStream_t st);

@@ -54,7 +54,9 @@ __device__ inline float finalize_unitless_px(bool roi, bool rel, float z0, bool 
                 if (de <= band) v = 0.f;
             }
         }
-        if (finitef(v)) v = fminf(v, 0.0f);
+        // np.minimum(v, 0.0) hands back its second operand when the two are equal: a zero of either sign becomes +0.0 (the taper leaves -0.0
+        // at the mask's edge, a negative height times weight 0)
+        if (finitef(v)) v = __fadd_rn(fminf(v, 0.0f), 0.0f);
     }
     return v;
 }

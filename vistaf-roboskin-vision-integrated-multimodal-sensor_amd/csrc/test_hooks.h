@@ -7,7 +7,10 @@
  * _build_full_tables, _dft_forward, _dft_inverse (demodulation: peak search, carrier choice, twiddle tables, the float64 GEMM stages), _morph
  * (the three dilate / erode kernels), _tempseg_plane, _tempseg_sign (the planes between the stages of the stripe segmentation, its sign split);
  * vistaf_ftp_test_scratch_regions (scratch layouts) and vistaf_ftp_test_dft_full_mag (the full-spectrum magnitude, asynchronous: also a timing
- * aid).  The entry points of the three binary-mask chains (vistaf_ftp_test_bad_chain and friends) are declared in test_hooks_masks.h. */
+ * aid).  The entry points of the three binary-mask chains (vistaf_ftp_test_bad_chain and friends) are declared in test_hooks_masks.h, those of
+ * the back end of a predict in test_hooks_post.h: vistaf_ftp_test_smooth_reliable, _core_flip, _hole_candidates, _hole_tmp, _hole_zin, _hole_merge,
+ * _height_finish (frontier taper, composition, clamp, mm curve), _to_mm (the mm curve alone), _tail (the force tails), _backend (blob filter, tail and output copy, fused or
+ * separate), _backend_fits and _frame_records (launch_fill_scalars, launch_mark_empty). */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
