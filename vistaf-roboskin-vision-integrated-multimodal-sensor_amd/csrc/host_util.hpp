@@ -18,7 +18,8 @@ struct vistaf_tempseg_handle;
 
 namespace vf {
 
-// records the calling thread's last-error text (vistaf_ftp_last_error) and returns `code`; defined in api.hip
+// records the calling thread's last-error text (vistaf_ftp_last_error) and returns `code`; defined in api.hip, used by every
+// other translation unit of the ABI (stages.hip, api_hooks.hip, the read-outs)
 int set_error(int code, const std::string &msg);
 
 #define HIPCHK(x)                                                                                                     \

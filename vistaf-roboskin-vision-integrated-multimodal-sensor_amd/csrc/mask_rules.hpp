@@ -1,6 +1,6 @@
 // The rules of the mask-topology family (threshold, 8-connected labelling, largest component, chamfer distance tiers, blob peak, fused back
 // end), one definition each.  Private to the family: k_cc_dist.hip, backend_device.hpp (cc_lds_build), k_backend.hip, the blob kernels of
-// k_post.hip, api.hip for chamfer_ball.  The pure rules come first and are __host__ __device__ (or host only), so that
+// k_post.hip, stages.hip for chamfer_ball.  The pure rules come first and are __host__ __device__ (or host only), so that
 // tests/diag/mask_host_check.hip holds them against brute force; the wave-level rules follow.
 #pragma once
 #include <algorithm>

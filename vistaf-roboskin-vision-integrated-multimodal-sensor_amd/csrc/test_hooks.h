@@ -10,7 +10,10 @@
  * aid).  The entry points of the three binary-mask chains (vistaf_ftp_test_bad_chain and friends) are declared in test_hooks_masks.h, those of
  * the back end of a predict in test_hooks_post.h: vistaf_ftp_test_smooth_reliable, _core_flip, _hole_candidates, _hole_tmp, _hole_zin, _hole_merge,
  * _height_finish (frontier taper, composition, clamp, mm curve), _to_mm (the mm curve alone), _tail (the force tails), _backend (blob filter, tail and output copy, fused or
- * separate), _backend_fits and _frame_records (launch_fill_scalars, launch_mark_empty). */
+ * separate), _backend_fits and _frame_records (launch_fill_scalars, launch_mark_empty).
+ * Definitions: vistaf_ftp_test_set, which reads the handle, in api.hip; the _tempseg hooks in tempseg.hip; every other hook in api_hooks.hip,
+ * which never sees a handle.  Where a stage of a predict chooses between kernel tiers the hook calls the function the session calls
+ * (stages.hpp). */
 #ifndef VISTAF_TEST_HOOKS_H
 #define VISTAF_TEST_HOOKS_H
 #include "../../include/vistaf_ftp.h"
@@ -172,7 +175,7 @@ int vistaf_ftp_test_unwrap(const float *wrapped, const float *quality, const uin
 /* The Telea inpaint launchers (k_inpaint*.hip) on device planes [B, h, w] of the caller: img_inout[b] becomes cv2.inpaint(img, bad != 0, range,
  * INPAINT_TELEA) of itself, bit for bit, known pixels untouched.  Scratch is allocated and freed by the call, which runs on `stream` and waits
  * for it.  status [B]: pass zeros; only ever written with 2 (VISTAF_FRAME_QUEUE_OVERFLOW).  fb [B]: written by every variant but 1.
- * variant: 0 what the bad-pixel stage of a session launches with the default tiers (inpaint_dispatch of api.hip, the session's own function):
+ * variant: 0 what the bad-pixel stage of a session launches with the default tiers (inpaint_dispatch of stages.hpp, the session's own function):
  *            the window tiers and the whole-frame kernel, or above 8 * 14464 pixels the cluster front end, the big-cluster march and its
  *            hand-back.  fb[b] = 1: the whole-frame kernel took frame b,
  *          1 launch_inpaint_telea alone on every frame; round_u8 != 0: 8-bit semantics (values 0..255, every estimate rounded as OpenCV's

@@ -7,7 +7,7 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* The three binary-mask chains of a predict, as a session runs them (the session's own functions in api.hip), on device planes [B, h, w] of the
+/* The three binary-mask chains of a predict, as a session runs them (the session's own functions, stages.hpp; the hooks are in api_hooks.hip), on device planes [B, h, w] of the
  * caller.  fused: 1 the one-launch kernel of k_maskchain.hip where mask_chain_fits takes (h, w, element, operations), 0 the separate kernels.
  * Every call refuses a NULL plane, B, h or w below 1, a kernel size outside 1..33, iterations outside 0..16 and a `fused` other than 0 / 1 with
  * VISTAF_E_INVALID before anything is allocated, runs on `stream`, waits for it and returns the tier taken (1 the fused kernel, 0 the separate

@@ -8,7 +8,10 @@
  * runs on `stream`, waits for it, and returns the tier it launched (>= 0) or a negative VISTAF_E_* code (text in vistaf_ftp_last_error).  A NULL
  * plane (the ones marked optional apart), a size below 1, an unknown variant and a variant the shape or blur does not take are refused with
  * VISTAF_E_INVALID before anything is allocated or launched.  Scratch planes are allocated and freed by the call.  Blurs take the taps a
- * session builds for their sigma (gauss_taps of host_util.hpp) and the session's default blur tiers. */
+ * session builds for their sigma (gauss_taps of host_util.hpp) and the session's default blur tiers.  The hooks are in api_hooks.hip; the three
+ * with tiers of their own (_smooth_reliable, _height_finish, _backend) call the functions post_demod calls (smooth_stage, height_finish_stage,
+ * backend_stage of stages.hpp), variant 0 with the default of the tier's flag, and may allocate the scratch of the separate kernels whichever
+ * tier runs. */
 #ifndef VISTAF_TEST_HOOKS_POST_H
 #define VISTAF_TEST_HOOKS_POST_H
 #include "../../include/vistaf_ftp.h"
