@@ -19,6 +19,9 @@
 // [5] second order statistic by a pass, [6] column sums, [7] reduction + solve, [8] load, [9] residual plane, [10] launches
 namespace vf { __device__ unsigned long long g_fit_dbg[16]; __device__ unsigned long long g_fit_last; }
 #define SEL_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); vf::g_fit_dbg[i] += t_ - vf::g_fit_last; vf::g_fit_last = t_; } } while (0)
+// g_fit_m: over ALL frames, how many levels of a median chose a bucket of <= 64, <= 128, <= 256, <= 512, <= 1024, more keys (the last: another level)
+namespace vf { __device__ unsigned int g_fit_m[6]; }
+#define SEL_COUNT_M(m) do { if (threadIdx.x == 0) { const unsigned m_ = (m); atomicAdd(&vf::g_fit_m[m_ <= 64u ? 0 : m_ <= 128u ? 1 : m_ <= 256u ? 2 : m_ <= 512u ? 3 : m_ <= 1024u ? 4 : 5], 1u); } } while (0)
 #define FIT_START() do { if (blockIdx.x == 0 && threadIdx.x == 0) { vf::g_fit_last = __builtin_amdgcn_s_memtime(); vf::g_fit_dbg[10]++; } } while (0)
 #else
 #define FIT_START() do { } while (0)
@@ -102,6 +105,7 @@ __global__ __launch_bounds__(SEL_T) void k_robust_polyfit(const float *__restric
         for (int i = tid; i < w + h; i += SEL_T)
             s_tab[i] = i < w ? fit_coord(i, cxf) : fit_coord(i - w, cyf);
     }
+    sel_init(sh);
     __syncthreads();
 
     // Working copy in the output plane (it is only written at the very end): z where the pixel is fitted, NaN elsewhere.  The ~40 passes
@@ -293,6 +297,9 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     static_assert(RP >= 1 && RP <= 128, "rows per thread live in registers");
     static_assert(GT >= 0 && (GT == 0 || (RP - 1) * GT + GT + 15 < FIT_YTAB), "row table");
     const int groups = GT > 0 ? GT : groups_rt;
+    // select.hpp's SELF: the window and chained instances run the self-cleaning levels; the plain instances keep the levels' former
+    // bookkeeping, with which the compiler spills less than the parent build (k_robust_polyfit_col<56,4>: 39 spills for 40, with SELF 46)
+    constexpr bool SF = WIN || PASSES;
     FIT_START();
     __shared__ SelShared sh;
     __shared__ double s_part[NT / 64][21];
@@ -308,6 +315,7 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
     }
     const float cxf = fit_centre(w), cyf = fit_centre(h);
     for (int i = tid; i < FIT_YTAB; i += NT) s_yn[i] = fit_coord(i, cyf);       // rows >= h: only read for samples that are NaN
+    if constexpr (SF) sel_init<NT>(sh);                                         // the barriers around the first range reduction come before the first median
     const int col = tid % cols_pad, grp = __builtin_amdgcn_readfirstlane(tid / cols_pad);   // uniform inside a wave (cols_pad % 64 == 0)
     const bool owner = col < w && grp < groups;
     const float xn = fit_coord(col, cxf);
@@ -547,11 +555,11 @@ __device__ __attribute__((always_inline)) inline void robust_polyfit_col_body(co
         // ---- the next step's scale from the two medians
         mode = 0;
         const FitKeys kr = fit_resid_range(coef, zmin, zmax);
-        const float medr = block_median_each<NT>(each, sh, n, kr.kmin, kr.kmax);
+        const float medr = block_median_each<NT, SF>(each, sh, n, kr.kmin, kr.kmax);
         __syncthreads();
         med = medr; mode = 1;
         const FitKeys ka = fit_mad_range(kr, medr);
-        const float mad = block_median_each<NT>(each, sh, n, ka.kmin, ka.kmax);
+        const float mad = block_median_each<NT, SF>(each, sh, n, ka.kmin, ka.kmax);
         __syncthreads();
         mode = 0;
         csig = fit_csig(c, mad);
@@ -633,6 +641,9 @@ void fit_debug_dump()
     if (hipMemcpyFromSymbol(d, HIP_SYMBOL(g_fit_dbg), sizeof(d)) != hipSuccess) return;
     printf("[fit dbg] frame 0, %llu launches so far, cycle sums: load %llu | column sums %llu | reduce+solve %llu | hist clear %llu | hist pass %llu | bucket search %llu | "
            "collect %llu | sort %llu | second statistic pass %llu | residual plane %llu || of reduce+solve: wave sums %llu | partials %llu | solve %llu | rest in [reduce+solve]\n", d[10], d[8], d[6], d[7], d[0], d[1], d[2], d[3], d[4], d[5], d[9], d[11], d[12], d[13]);
+    unsigned int mm[6];
+    if (hipMemcpyFromSymbol(mm, HIP_SYMBOL(g_fit_m), sizeof(mm)) != hipSuccess) return;
+    printf("[fit dbg] all frames, chosen buckets by count: <=64 %u | <=128 %u | <=256 %u | <=512 %u | <=1024 %u | more %u\n", mm[0], mm[1], mm[2], mm[3], mm[4], mm[5]);
 }
 #endif
 

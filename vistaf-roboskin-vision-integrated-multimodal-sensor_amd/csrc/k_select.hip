@@ -28,6 +28,7 @@ __global__ __launch_bounds__(SEL_T) void k_select(const float *__restrict__ vals
     size_t b = blockIdx.x;
     PlaneGetter g{vals + b * (size_t)P, mask + b * mask_stride, le_thr ? le_thr[b] : 0.f, le_thr != nullptr, use_abs != 0};
     uint32_t n, kmin, kmax;
+    sel_init(sh);                                  // block_minmax's barriers stand between this and the first sweep
     block_minmax(g, P, sh, n, kmin, kmax);
     if (threadIdx.x == 0 && counts) counts[b] = (int)n;
     for (int j = 0; j < nreq; j++) {
@@ -101,6 +102,7 @@ __global__ __launch_bounds__(SEL_T) void k_select_resident(const float *__restri
         }
     };
     uint32_t n, kmin, kmax;
+    sel_init(sh);                                  // resident_minmax's barriers stand between this and the first sweep
     resident_minmax<NS>(key, cut, sh, n, kmin, kmax);
     if (threadIdx.x == 0 && counts) counts[b] = (int)n;
     float r = 0.f;
